@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- PSMs/s of the Ascore hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--psms M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--psms M] [--dump-outputs DIR]
 
 A *step* is one pass of the hot path (bin_spectra -> score_signatures -> rank_and_localize)
 over one batch of synthetic PSMs of the named BASELINE config whose spectra are already
@@ -221,7 +221,8 @@ def cpu_baseline(batch, settings, target_seconds=12.0):
     import subprocess
     import tempfile
     from oracle import orc
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "oracle", "ref"])
+    # (make says what it did about oracle/_ref: to stderr, stdout carries ONE JSON line)
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "oracle", "ref"], stdout=sys.stderr)
     kind = "ref" if orc.available("ref") else "oracle"
     cores, cores_why = effective_cores()
     worker = os.path.join(ROOT, "oracle", "cpu_worker.py")
@@ -322,6 +323,36 @@ def timed_blocks(torch, dist, dev, pipe, plan, steps, n_blocks):
             el_own = el
         blocks.append((el, el_own, k_ms / max(steps, 1), pipe.gather_wait_s))
     return blocks
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, res):
+    """--dump-outputs: `res` (name -> host array, one row per PSM: the results of the last timed step) as DIR/<name>.npy,
+    so that two builds can be compared output for output on the same seeded job.  float32 stays float32 and int32 becomes
+    float64; a 64-bit mask (best_sig, alt_mask: one bit per site) becomes its two 32-bit halves, low then high, as float64
+    along a new last axis: every value is exact.  A result over DUMP_LIMIT_BYTES in all is cut to a sample of its PSMs, the
+    same on every run (fixed seed); rows.npy names the PSMs that were kept."""
+    out = {}
+    for name, a in res.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype in (np.int64, np.uint64):
+            a = a.astype("<u8").view("<u4").reshape(a.shape + (2,)).astype(np.float64)
+        elif a.dtype != np.float32:
+            a = a.astype(np.float64)
+        out[name] = a
+    n = len(out["best_score"])
+    rows = np.arange(n)
+    row_bytes = 8 + sum(a.nbytes // max(n, 1) for a in out.values())
+    keep = (DUMP_LIMIT_BYTES - 128 * (len(out) + 1)) // row_bytes          # (128 bytes: a .npy file's header)
+    if n > keep:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+    out = {name: a[rows] for name, a in out.items()}
+    out["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 FAMILY_NAMES = ["pya_bin_spectra_kernel", "pya_score_signatures_kernel", "pya_score_localize_kernel", "pya_localize_kernel"]
@@ -517,7 +548,7 @@ def launcher_dry_run(args, rank, world):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps of every block (--blocks)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--psms", type=int, default=None, help="PSMs per GPU (default: the config's size)")
@@ -542,7 +573,14 @@ def main():
                     help="(internal) run ONE leg of `other_configs` in this process and print its record")
     ap.add_argument("--no-host-api", action="store_true",
                     help="skip the host-array legs (profiling runs: only the timed device-resident steps launch kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the results of the LAST timed step (what the timed path hands "
+                         "its caller: best_score, n_sig, best_sig, ascores, alt_mask of every PSM of the job) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB in all; the job is seeded, so two runs with the same arguments "
+                         "score the same inputs")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs a timed step (--steps >= 1)")
 
     if args.leg:
         return leg_child(args)
@@ -557,6 +595,8 @@ def main():
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run)" % (args.gpus, world))
     if os.environ.get("PYA_BENCH_BACKEND", "nccl") != "nccl":
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: the dry run scores nothing")
         return launcher_dry_run(args, rank, world)
 
     # ---- CPU only up to the marked line: the job, this rank's shard, and the CPU baseline's worker
@@ -654,6 +694,14 @@ def main():
     order = sorted(range(len(blocks)), key=lambda i: blocks[i][0])
     elapsed, elapsed_own, kern_ms, gather_wait_s = blocks[order[len(order) // 2]]
     block_ms = [1e3 * b[0] / max(args.steps, 1) for b in blocks]
+    if args.dump_outputs and rank == 0:
+        # (read before anything else runs on the device: the last block's last step, whose gather has landed)
+        if use_dist:
+            from pyascore_amd.device import unpack_summary
+            res = unpack_summary(pipe.gathered(ranges).cpu().numpy(), job_max_k)
+        else:
+            res = {k: getattr(plan, k).cpu().numpy() for k in ("best_score", "n_sig", "best_sig", "ascores", "alt_mask")}
+        dump_outputs(args.dump_outputs, res)
 
     per_rank = None
     if use_dist:

@@ -44,3 +44,14 @@ def test_a_rank_count_that_disagrees_with_the_environment_is_refused():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr
+
+
+def test_the_cpu_baseline_writes_nothing_to_stdout(capfd):
+    """bench.py's stdout is the one JSON line: what the baseline's children say (make on the checker libraries, the
+    workers) must not land there."""
+    import bench
+    from pyascore_amd import synth
+    batch, settings = synth.make_batch("cfg2", n_psm=64, seed=3)
+    cpu = bench.cpu_baseline(batch, settings, target_seconds=0.3)
+    assert cpu["value"] > 0 and cpu["kind"] in ("reference", "port")
+    assert capfd.readouterr().out == ""
