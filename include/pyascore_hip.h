@@ -176,7 +176,9 @@ int pya_plan_run(pya_plan *plan, const double *d_mz, const double *d_intensity,
                  void *hip_stream, const pya_results *d_out);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
- * synchronises */
+ * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside
+ * the scoring and localize kernels: ms[2] is then that stream's interval, it OVERLAPS ms[1] and ms[3], and the
+ * four no longer sum to the step. */
 int pya_plan_timings(pya_plan *plan, float ms[4]);
 /* the same, summed over the runs since the last call of this function (the events live in a ring of 128 runs:
  * of more runs than that only the latest 128 count); *n_runs = how many; synchronises with the latest run only,

@@ -303,7 +303,7 @@ int pya_calculate_ambiguity(pya_handle *h, uint64_t psm, uint64_t ref_bits, cons
     std::memcpy(host_scores.data(), ref_scores, NT * sizeof(float));
     std::memcpy(host_scores.data() + NT, other_scores, NT * sizeof(float));
     DevBuf<float> d_scores, d_out;
-    refresh_shared(p);
+    shared_tables(h, p->dev);
     HIPCHK(h, d_scores.upload(host_scores.data(), host_scores.size()));
     HIPCHK(h, d_out.alloc(2));
     int e;

@@ -35,12 +35,12 @@ ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, uint32_t max_k) {
             const int64_t P = std::max<int64_t>(0, b->peak_off[i + 1] - b->peak_off[i]);
             const int64_t L = b->pep_off[i + 1] - b->pep_off[i];
             double sigs = 0;
-            if (L >= 1 && L <= PYA_MAX_PEPTIDE_LEN) {
-                uint32_t ns = 0;
-                const bool ok = h->scan_peptide(b->pep + b->pep_off[i], L, &ns);
-                if (ok && ns < 255u) c.sites[i] = (uint8_t)ns;
+            uint32_t n_sites = 0;
+            if (psm_letters_ok(h, b->pep + b->pep_off[i], L, &n_sites)) {
+                const uint32_t ns = n_sites;
+                if (ns < 255u) c.sites[i] = (uint8_t)ns;
                 uint64_t N = 0;
-                if (ok && ns <= PYA_MAX_SITES && b->n_of_mod[i] >= 0 && (uint32_t)b->n_of_mod[i] <= ns) {
+                if (ns <= PYA_MAX_SITES && b->n_of_mod[i] >= 0 && (uint32_t)b->n_of_mod[i] <= ns) {
                     uint64_t &cached = h->binom_cache[ns][b->n_of_mod[i]];      /* benign race: same value */
                     if (cached == 0) cached = binom(ns, (uint32_t)b->n_of_mod[i]);
                     N = cached;
@@ -61,14 +61,7 @@ ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, uint32_t max_k) {
             c.arena[i] = 8.0 * (double)(P + 1) + 8.0 + (4.0 + 4.0 * (double)h->rec_words()) * sigs + extra + (double)L + 2.0 * PYA_GRID_CELLS + 96.0 + 12.0 * max_k;
         }
     };
-    unsigned nt = n >= 20000 ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
-    if (nt == 1) {
-        work(0, n);
-    } else {
-        std::vector<std::thread> th;
-        for (unsigned t = 0; t < nt; t++) th.emplace_back(work, n * t / nt, n * (t + 1) / nt);
-        for (auto &x : th) x.join();
-    }
+    for_psm_ranges(n, work);
     return c;
 }
 

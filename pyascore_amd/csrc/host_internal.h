@@ -12,8 +12,9 @@
  *
  * This header holds what the host files share (handle, plan, buckets, device buffers, the kernels' launchers);
  * the code is in host_abi.cpp (handles, settings, strings, retained records), host_tables.cpp (DevConfig, score table,
- * order tables, environment switches), host_plan.cpp (plans: pre-pass, arena, launches), host_batch.cpp
- * (pya_score_batch: chunking and pipelining) and host_one.cpp (pya_score_one).
+ * order tables, environment switches), host_plan.cpp (creating a plan: the pre-pass in phases, the arena), host_run.cpp
+ * (running it: the launch families, the timing ring), host_batch.cpp (pya_score_batch: chunking and pipelining) and
+ * host_one.cpp (pya_score_one).
  */
 #ifndef PYA_HOST_INTERNAL_H
 #define PYA_HOST_INTERNAL_H
@@ -122,7 +123,7 @@ int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const u
 const size_t kMaxLds = 160 * 1024;
 const uint32_t kBucketLimits[] = {64, 512, 4096, PYA_FAST_SIGNATURES};
 const int kNumBuckets = 4;
-const uint64_t kTinyBatch = 64;         /* up to this many PSMs go through the fused single-launch kernel */
+const size_t kRedoHead = 64;            /* words in front of the ids of a hand-over list (d_redo .. d_redo5): its counts */
 const size_t kStageLimit = 1u << 20;   /* batches whose transfers are smaller than this go through one staged copy */
 
 template <typename T>
@@ -194,6 +195,8 @@ inline uint64_t binom(uint32_t n, uint32_t k) {
     }
     return (uint64_t)r;
 }
+
+uint32_t next_pow2(uint32_t v);              /* (host_tables.cpp) */
 
 inline bool is_forward(char t) { return t == 'b' || t == 'c'; }
 inline bool is_backward(char t) { return t == 'y' || t == 'z' || t == 'Z'; }
@@ -427,6 +430,34 @@ struct Bucket {
         uint32_t v = (push_max + 3u) & ~3u;
         return v > PYA_MAX_PUSHED ? PYA_MAX_PUSHED : v;
     }
+    /* The caps grow in two ways only.  cover(): one more PSM -- N site assignments, L residues, charge z, k modifications
+     * on ns modifiable residues, per_type fragments per ion type. */
+    void cover(const pya_handle &h, uint32_t N, uint32_t L, uint32_t z, uint32_t k, uint32_t ns, uint32_t per_type) {
+        const uint32_t n_uniq = (uint32_t)h.cfg.n_uniq;
+        n_cap = std::max(n_cap, N);
+        list_cap = std::max(list_cap, next_pow2(std::max(per_type, 1u)));
+        pos_cap = std::max(pos_cap, std::max(L - 1u, 1u));
+        n_types = (uint32_t)h.cfg.n_types;
+        k_max = std::max(k_max, k);
+        ns_max = std::max(ns_max, ns);
+        push_max = std::max(push_max, k <= ns ? k * (ns - k) : 0u);
+        z_max = std::max(z_max, z);
+        pair_cap = std::max(pair_cap, (L - 1u) * n_uniq);
+        list_max = std::max(list_max, per_type);
+        if (N <= 64) {
+            node_words = std::max(node_words, 2u * (ns + 1u) * (1u + (N + 7u) / 8u));
+            auto sc = h.shape_cols.find(ns << 8 | k);
+            if (sc != h.shape_cols.end()) node_cols = std::max(node_cols, sc->second);
+        }
+    }
+    /* absorb(): the PSMs of another bucket join this one's launches -- EVERY cap, so that no launch of this bucket is
+     * sized without them, whichever caps it reads. */
+    void absorb(const Bucket &o) {
+        for (uint32_t Bucket::*cap : {&Bucket::n_cap, &Bucket::list_cap, &Bucket::pos_cap, &Bucket::n_types, &Bucket::k_max, &Bucket::ns_max,
+                                      &Bucket::z_max, &Bucket::push_max, &Bucket::list_max, &Bucket::pair_cap, &Bucket::node_words,
+                                      &Bucket::node_cols})
+            this->*cap = std::max(this->*cap, o.*cap);
+    }
 };
 
 struct pya_plan {
@@ -461,6 +492,11 @@ struct pya_plan {
     struct IdList {
         uint32_t off, n, cap, ncls;
     };
+    static bool any_ids(const std::vector<IdList> &lists) {         /* (lists exist per class even when no PSM is in them) */
+        bool any = false;
+        for (const IdList &l : lists) any = any || l.n != 0;
+        return any;
+    }
     std::vector<uint32_t> bin_ids, score_ids, fused_ids, big_ids;
     std::vector<IdList> bin_lists, score_lists, big_lists;
     /* launches of the fused kernel: per peak class and charge class, and -- since the kernel's speed
@@ -564,8 +600,71 @@ int build_dev_config(pya_handle *h);
 int sync_config(pya_handle *h);
 int ensure_lut(pya_handle *h, uint32_t n_max);
 uint32_t shape_offset(pya_handle *h, uint32_t n, uint32_t k);
-uint32_t next_pow2(uint32_t v);
-/* host_plan.cpp: plans (host pre-pass, arena, launches) */
+/* the signature order / inverse / binomial tables on the device (uploaded again when a new shape extended them) */
+int upload_shared_tables(pya_handle *h);
+/* ... and the handle's tables as the kernels see them: seven fields of every BatchDev */
+void shared_tables(const pya_handle *h, BatchDev &d);
+
+/* Which scoring kernel instantiation the settings allow (read at launch time: the handle's settings may change between
+ * the runs of a plan). */
+inline bool plain_types(const DevConfig &c) { return c.n_nl == 0 && c.n_fwd <= 1 && c.n_types - c.n_fwd <= 1; }
+inline bool general_settings(const DevConfig &c) { return !plain_types(c); }     /* neutral losses, or several ion types per direction */
+inline uint32_t with_nl(const DevConfig &c) { return c.n_nl != 0 ? 1u : 0u; }
+/* loss states the scoring kernels' LDS table has room for: 2 bits per neutral-loss class */
+inline uint32_t nl_cap(const DevConfig &c) {
+    const uint32_t nnl = (uint32_t)c.n_nl;
+    return nnl >= 4u ? 256u : (nnl == 0u ? 4u : 1u << (2u * nnl));
+}
+/* launches of more than 64 site assignments share the walk over the first sites between signatures ... */
+inline uint32_t score_prefix(const pya_handle *h, uint32_t n_cap) { return (n_cap >= 128 && !h->kn.no_prefix) ? 1u : 0u; }
+/* ... with compact prefix entries when every PSM is on the straight-line walker */
+inline uint32_t score_compact(const DevConfig &c, uint32_t z_max) { return (plain_types(c) && z_max == 1) ? 1u : 0u; }
+
+/* fn(lo, hi) over the PSMs [0, n): on up to eight threads when the batch is big enough to pay for them */
+template <typename F>
+void for_psm_ranges(uint64_t n, const F &fn) {
+    const unsigned nt = n >= 20000 ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
+    if (nt == 1) return fn(0, n);
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nt; t++) th.emplace_back(fn, n * t / nt, n * (t + 1) / nt);
+    for (auto &x : th) x.join();
+}
+
+/* ---- one PSM's validity: the plan's pre-pass and pya_score_one ask the same questions, in the same order, and give the
+ * same messages ("PSM <i>: ...", written to msg[kPsmMsg]); the return value is PYA_OK or the error code ---- */
+const size_t kPsmMsg = 400;
+/* the letters alone, without an explanation (the threaded scans): valid residues, *ns = the modifiable ones */
+inline bool psm_letters_ok(const pya_handle *h, const uint8_t *pep, int64_t L, uint32_t *ns) {
+    return L >= 1 && L <= PYA_MAX_PEPTIDE_LEN && h->scan_peptide(pep, L, ns);
+}
+/* ranges, letters, fixed-modification positions (n_aux < 0: the batch's aux_off runs backwards); *ns on success */
+int check_psm_shape(const pya_handle *h, uint64_t i, int64_t P, int64_t L, int32_t k, int32_t z, const uint8_t *pep,
+                    const uint32_t *aux_pos, int64_t n_aux, uint32_t *ns, char *msg);
+/* the limits of a PSM whose shape is fine: *N = C(ns, k) (0 when k > ns), *per_type = its fragments per ion type */
+inline int check_psm_limits(pya_handle *h, uint64_t i, int64_t L, int32_t k, int32_t z, uint32_t ns, uint64_t *N,
+                            uint32_t *per_type, char *msg) {
+    *N = 0;
+    if ((uint32_t)k <= ns) {
+        uint64_t &cached = h->binom_cache[ns][k];
+        if (cached == 0) cached = binom(ns, (uint32_t)k);
+        *N = cached;
+    }
+    *per_type = (uint32_t)(L - 1) * (uint32_t)z * (uint32_t)h->cfg.n_uniq;
+    if (*N <= PYA_MAX_SIGNATURES && *per_type <= PYA_MAX_FRAGMENTS_PER_TYPE) return PYA_OK;
+    if (*N > PYA_MAX_SIGNATURES)
+        std::snprintf(msg, kPsmMsg, "PSM %llu: C(%u,%d) site assignments exceed the limit of %d", (unsigned long long)i, ns, k, PYA_MAX_SIGNATURES);
+    else
+        std::snprintf(msg, kPsmMsg, "PSM %llu: %u fragments per ion type exceed %d", (unsigned long long)i, *per_type, PYA_MAX_FRAGMENTS_PER_TYPE);
+    return PYA_ERR_LIMIT;
+}
+/* descriptor words 4 and 5 (common.h: BatchDev.desc) */
+inline void pack_desc_tail(uint64_t L, uint64_t n_aux, int32_t k, uint32_t ns, int32_t z, uint32_t N, uint32_t order_off,
+                           uint64_t *w) {
+    w[4] = L | n_aux << 16 | (uint64_t)((uint32_t)k & 0xffffu) << 32 | (uint64_t)ns << 48 | (uint64_t)((uint32_t)z & 0xffu) << 56;
+    w[5] = (uint64_t)N | (uint64_t)order_off << 32;
+}
+
+/* host_plan.cpp: creating a plan (the host pre-pass in phases, the arena); host_run.cpp: running it */
 struct IoReq {                       /* pya_score_batch: spectra and results live in the plan's arena too */
     const double *mz, *inten;
     uint32_t max_k;
@@ -573,8 +672,6 @@ struct IoReq {                       /* pya_score_batch: spectra and results liv
     hipStream_t stream;              /* metadata upload: on this stream, waited for alone (nullptr: device-wide) */
     const uint8_t *pre_sites;        /* letter scan already done by the caller: sites per PSM, 255 = invalid letters */
 };
-void refresh_shared(pya_plan *p);
-void fill_dev(pya_plan *p);
 int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, pya_plan **out);
 int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid = false);
 /* host_batch.cpp */

@@ -96,44 +96,28 @@ int one_run(pya_handle *h, bool keep, uint32_t max_k) {
     pya_handle::One &o = h->one;
     const OneMeta &m = o.meta;
     BatchDev d = o.dev;
-    d.order_tab = h->d_order.p;
-    d.inv_tab = h->d_inv.p;
-    d.binom = h->d_binom.p;
-    d.cfg = h->d_cfg.p;
-    d.lut = h->d_lut.p;
-    d.lut_off = h->d_lut_off.p;
-    d.lut_n_max = h->lut_uploaded_n - 1;
+    shared_tables(h, d);
     d.max_k = max_k;
     d.keep = keep ? 1u : 0u;
     d.debug = h->kn.debug & 0xffffu;
     /* caps of this one PSM (the rules of the plan's buckets, for a bucket of one) */
+    const uint32_t L = m.L, z = (uint32_t)m.max_charge, k = (uint32_t)m.n_of_mod, ns = m.n_sites, N = m.n_sig;
     Bucket bk;
     bk.take_knobs(h->kn);
-    const uint32_t L = m.L, z = (uint32_t)m.max_charge, k = (uint32_t)m.n_of_mod, ns = m.n_sites, N = m.n_sig;
-    const uint32_t n_uniq = (uint32_t)h->cfg.n_uniq, n_types = (uint32_t)h->cfg.n_types;
-    const uint32_t per_type = (L - 1) * z * n_uniq;
-    bk.n_cap = N;
-    bk.list_cap = next_pow2(std::max<uint32_t>(per_type, 1));
-    bk.pos_cap = std::max<uint32_t>(L - 1, 1);
-    bk.n_types = n_types;
-    bk.k_max = std::max<uint32_t>(k, 1);
-    bk.push_max = std::max<uint32_t>(k < ns ? k * (ns - k) : 1, 1);
-    bk.z_max = z;
+    bk.cover(*h, N, L, z, k, ns, (L - 1) * z * (uint32_t)h->cfg.n_uniq);
     const uint32_t cap = (m.n_peaks + 31u) & ~31u;
-    const uint32_t prefix = (N >= 128 && !h->kn.no_prefix) ? 1u : 0u;
-    const bool plain_types = h->cfg.n_nl == 0 && h->cfg.n_fwd <= 1 && h->cfg.n_types - h->cfg.n_fwd <= 1;
-    const uint32_t compact = (plain_types && z == 1) ? 1u : 0u;
+    const uint32_t prefix = score_prefix(h, N), compact = score_compact(h->cfg, z);
     const bool both = h->cfg.n_fwd > 0 && h->cfg.n_fwd < h->cfg.n_types;
     uint32_t use_fused = 0, f_n_cap = 4, f_stride = 8, f_ent = 1, f_push = 8;
     const uint32_t frags = (both ? 2u : 1u) * (L - 1) * z;
-    if (!keep && plain_types && !h->kn.no_fused && k < ns && N > 0 && N <= (both ? 32u : 64u) && frags <= 255u) {
+    if (!keep && plain_types(h->cfg) && !h->kn.no_fused && k < ns && N > 0 && N <= (both ? 32u : 64u) && frags <= 255u) {
         use_fused = both ? 1u : 2u;
         f_n_cap = (N + 3u) & ~3u;
         f_stride = (both ? 2u : 1u) * f_n_cap + 4u;
         f_ent = std::max<uint32_t>((L - 1) * z, 1);
         f_push = std::max<uint32_t>(8u, bk.push_cap());
     }
-    if (pya_one_lds_bytes(cap, prefix, h->cfg.n_nl != 0, compact, bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(), bk.sb(), use_fused,
+    if (pya_one_lds_bytes(cap, prefix, with_nl(h->cfg), compact, bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(), bk.sb(), use_fused,
                           f_n_cap, f_stride, f_ent, f_push, z > 1) > kMaxLds)
         return PYA_ERR_STATE;        /* no room in one workgroup's LDS: declined, the caller takes the batch path (per-stage kernels) */
     volatile uint32_t *flag = (volatile uint32_t *)(o.host + kOneFlag);
@@ -145,7 +129,7 @@ int one_run(pya_handle *h, bool keep, uint32_t max_k) {
     const int32_t kUnset = INT32_MIN;
     *n_sig_word = kUnset;
     const auto t_launch = std::chrono::steady_clock::now();
-    int e = pya_launch_one(&d, &m, cap, prefix, h->cfg.n_nl != 0 ? 1u : 0u, compact, bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(),
+    int e = pya_launch_one(&d, &m, cap, prefix, with_nl(h->cfg), compact, bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(),
                            bk.sb(), bk.gtp(), use_fused, f_n_cap, f_stride, f_ent, f_push, z > 1 ? 1u : 0u,
                            (int32_t *)(o.host_dev + kOneStatus), (uint32_t *)(o.host_dev + kOneFlag), o.stream);
     if (e) return h->hip_fail((hipError_t)e, "score (one PSM) launch");
@@ -208,34 +192,13 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
     if (!out->best_score || !out->best_sig || !out->n_sig || !out->ascores || !out->alt_mask)
         return h->fail(PYA_ERR_ARG, -1, "NULL array in results");
     if (n_aux && (!aux_pos || !aux_mass)) return h->fail(PYA_ERR_ARG, -1, "NULL fixed-modification arrays");
-    /* validation: what plan_create_impl checks for a PSM (same messages) */
-    if (n_peaks == 0) return h->fail(PYA_ERR_PSM, 0, "PSM 0: empty spectrum");
-    if (n_peaks > PYA_MAX_PEAKS) return h->fail(PYA_ERR_LIMIT, 0, "PSM 0: %llu peaks exceed the limit of %d", (unsigned long long)n_peaks, PYA_MAX_PEAKS);
-    if (L < 1 || L > PYA_MAX_PEPTIDE_LEN)
-        return h->fail(L < 1 ? PYA_ERR_PSM : PYA_ERR_LIMIT, 0, "PSM 0: peptide length %lld outside 1..%d", (long long)L, PYA_MAX_PEPTIDE_LEN);
-    if (n_of_mod < 0) return h->fail(PYA_ERR_PSM, 0, "PSM 0: negative n_of_mod");
-    if (max_charge < 1 || max_charge > PYA_MAX_CHARGE)
-        return h->fail(max_charge < 1 ? PYA_ERR_PSM : PYA_ERR_LIMIT, 0, "PSM 0: max_fragment_charge %d outside 1..%d", max_charge, PYA_MAX_CHARGE);
-    uint32_t ns = 0;
-    for (uint64_t j = 0; j < L; j++) {
-        if (!h->is_residue[pep[j]])
-            return h->fail(PYA_ERR_PSM, 0, "PSM 0: unknown residue '%c' at position %lld", (char)pep[j], (long long)(j + 1));
-        if (h->letter_modifiable((char)pep[j], (size_t)j, (size_t)L)) ns++;
-    }
-    for (uint64_t a = 0; a < n_aux; a++)
-        if (aux_pos[a] > (uint32_t)L) return h->fail(PYA_ERR_PSM, 0, "PSM 0: aux_mod_pos %u beyond the peptide", aux_pos[a]);
-    if (ns > PYA_MAX_SITES) return h->fail(PYA_ERR_LIMIT, 0, "PSM 0: %u modifiable residues exceed %d", ns, PYA_MAX_SITES);
+    /* validation: the questions of the plan's pre-pass (check_psm_shape / check_psm_limits: same order, same messages) */
+    char msg[kPsmMsg];
+    uint32_t ns = 0, per_type = 0;
     uint64_t N = 0;
-    if ((uint32_t)n_of_mod <= ns) {
-        uint64_t &cached = h->binom_cache[ns][n_of_mod];
-        if (cached == 0) cached = binom(ns, (uint32_t)n_of_mod);
-        N = cached;
-    }
-    if (N > PYA_MAX_SIGNATURES)
-        return h->fail(PYA_ERR_LIMIT, 0, "PSM 0: C(%u,%d) site assignments exceed the limit of %d", ns, n_of_mod, PYA_MAX_SIGNATURES);
-    const uint32_t per_type = (uint32_t)(L - 1) * (uint32_t)max_charge * (uint32_t)h->cfg.n_uniq;
-    if (per_type > PYA_MAX_FRAGMENTS_PER_TYPE)
-        return h->fail(PYA_ERR_LIMIT, 0, "PSM 0: %u fragments per ion type exceed %d", per_type, PYA_MAX_FRAGMENTS_PER_TYPE);
+    int code = check_psm_shape(h, 0, (int64_t)n_peaks, (int64_t)L, n_of_mod, max_charge, pep, aux_pos, (int64_t)n_aux, &ns, msg);
+    if (!code) code = check_psm_limits(h, 0, (int64_t)L, n_of_mod, max_charge, ns, &N, &per_type, msg);
+    if (code) return h->fail(code, 0, "%s", msg);
     /* (beyond a limit of the fast kernels: the caller takes the batch path, which has the general kernel) */
     if (h->all_general() || n_peaks > PYA_FAST_PEAKS || L > PYA_FAST_PEPTIDE_LEN || N > PYA_FAST_SIGNATURES || per_type > PYA_FAST_FRAGMENTS_PER_TYPE) return PYA_ERR_STATE;
     if (n_aux > PYA_ONE_MAX_AUX || (uint32_t)n_of_mod > 64u) return PYA_ERR_STATE;     /* (the caller takes the batch path) */
@@ -251,18 +214,8 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
     }
     rc = ensure_lut(h, per_type * (uint32_t)h->cfg.n_types);
     if (rc) return rc;
-    if (h->order_uploaded != h->order_tab.size() || !h->d_order.p) {
-        HIPCHK(h, h->d_order.upload(h->order_tab.data(), h->order_tab.size()));
-        HIPCHK(h, h->d_inv.upload(h->inv_tab.data(), h->inv_tab.size()));
-        if (!h->d_binom.p) {
-            std::vector<uint32_t> bt(64 * 64);
-            for (uint32_t pp = 0; pp < 64; pp++)
-                for (uint32_t t = 0; t < 64; t++) bt[pp * 64 + t] = (uint32_t)std::min<uint64_t>(binom(pp, t), 0xffffffffull);
-            HIPCHK(h, h->d_binom.upload(bt.data(), bt.size()));
-        }
-        HIPCHK(h, hipDeviceSynchronize());
-        h->order_uploaded = h->order_tab.size();
-    }
+    rc = upload_shared_tables(h);
+    if (rc) return rc;
     rc = one_prepare(h, (uint32_t)N);
     if (rc) return rc;
     pya_handle::One &o = h->one;
@@ -286,13 +239,7 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
         m.aux_pos[a] = aux_pos[a];
         m.aux_mass[a] = aux_mass[a];
     }
-    m.desc[0] = 0;
-    m.desc[1] = 0;
-    m.desc[2] = 0;
-    m.desc[3] = 0;
-    m.desc[4] = (uint64_t)L | (uint64_t)n_aux << 16 | (uint64_t)((uint32_t)n_of_mod & 0xffffu) << 32 | (uint64_t)ns << 48 |
-                (uint64_t)((uint32_t)max_charge & 0xffu) << 56;
-    m.desc[5] = (uint64_t)N | (uint64_t)ooff << 32;
+    pack_desc_tail(L, n_aux, n_of_mod, ns, max_charge, (uint32_t)N, ooff, m.desc);      /* (words 0 .. 3, the batch offsets, stay 0) */
     o.have_last = true;
     const uint32_t mk = out->max_k;
     if (mk > 64) return PYA_ERR_STATE;

@@ -1,0 +1,416 @@
+/* host_run.cpp -- running a plan: the launch families of pya_plan_run, the fork onto the side stream and the ONE way back
+ * from it, the timing ring, the per-PSM status. */
+#include "host_internal.h"
+
+namespace {
+
+/* which scoring kernel a list of one C(n,k) class gets, and with what caps -- decided at every run from the handle's
+ * settings and switches as they are then */
+struct ScoreRoute {
+    enum Kind { kCountNodes, kCountNodesGeneral, kSignatures } kind;
+    uint32_t prefix, compact, kc, node_cap, node_cols, res_cap, nl_cap;
+};
+
+ScoreRoute pick_score_route(const pya_handle *h, const Bucket &bk, uint32_t ncls, uint32_t peak_cap) {
+    const DevConfig &c = h->cfg;
+    ScoreRoute r = {ScoreRoute::kSignatures, score_prefix(h, bk.n_cap), score_compact(c, bk.z_max), 8u, 0u, 0u, 0u, nl_cap(c)};
+    const bool general = general_settings(c);
+    /* the count-node tables: fragment tolerance below half a unit, room for the launch's k and site counts */
+    const bool cnt_ok = h->mz_error <= 0.49f && bk.k_max + 1u <= 31u && bk.ns_max <= 32u && !h->kn.no_cnt && !(h->kn.debug & 0x8000u);
+    /* many site assignments (classes above 64) under the plain settings with both directions, charge 1: the count-node
+     * table decides the fragments (score_cnt.hip) */
+    if (ncls >= 1 && !general && c.n_fwd == 1 && c.n_types == 2 && bk.z_max == 1 && cnt_ok) {
+        while (r.kc < bk.k_max + 1u) r.kc <<= 1;
+        if (pya_score_cnt_lds_bytes(peak_cap, bk.pos_cap, r.kc, bk.k_max, bk.ns_max) <= 64u * 1024u) {
+            r.kind = ScoreRoute::kCountNodes;
+            return r;
+        }
+    }
+    /* general settings: the count nodes carry over when the loss variants depend on the count too (score_cntg.hip; the
+     * kernel checks that per peptide and walks what does not qualify) */
+    if (general && cnt_ok && pya_score_cntg_lds_bytes(peak_cap, bk.pos_cap, bk.k_max, bk.ns_max, r.nl_cap) <= 64u * 1024u) {
+        r.kind = ScoreRoute::kCountNodesGeneral;
+        return r;
+    }
+    /* score_signatures -- under general settings with one lookup set per distinct node of the assignment tree instead of
+     * one per signature (score_core.hip.h: score_nodes_dir).  The node kernel's LDS decides its occupancy: residue and
+     * loss-state tables by the launch, room for 320 nodes per direction -- cfg4's shape needs 186 on average, 328 at
+     * most; a direction with more is walked */
+    r.node_cols = std::max<uint32_t>(8u, (bk.node_cols + 7u) & ~7u);
+    r.res_cap = std::min<uint32_t>(64u, (bk.pos_cap + 1u + 3u) & ~3u);
+    if (general && !r.prefix && !h->kn.no_nodes && bk.node_words) {
+        r.node_cap = std::min<uint32_t>(320u, (bk.pos_cap * std::min<uint32_t>(bk.n_cap, 64u) + 1u) & ~1u);
+        if (h->kn.node_cap >= 0) r.node_cap = (uint32_t)h->kn.node_cap & ~1u;
+        if (pya_score_node_lds_bytes(peak_cap, with_nl(c), r.node_cap, r.node_cols, bk.node_words, r.res_cap, r.nl_cap) > 64u * 1024u)
+            r.node_cap = 0;
+    }
+    return r;
+}
+
+/* PYA_FLAG_TIMING: the events of this run in the plan's ring (without the flag mark() does nothing) */
+struct RunMarks {
+    pya_handle *h;
+    hipStream_t st;
+    hipEvent_t *ev;
+    uint8_t *alias;
+    /* boundary i of the run: a new event if the family before it launched anything, else the previous boundary's */
+    int operator()(int i, bool launched) const {
+        if (!ev) return PYA_OK;
+        if (i > 0 && !launched) {
+            alias[i] = alias[i - 1];
+            return PYA_OK;
+        }
+        alias[i] = (uint8_t)i;
+        if (hipEventRecord(ev[i], st) != hipSuccess) return h->hip_fail(hipGetLastError(), "hipEventRecord");
+        return PYA_OK;
+    }
+};
+
+/* A handful of PSMs (PyAscore.score is a batch of one) is launch-bound: one fused launch, one wavefront per PSM, instead of
+ * the five of the three-kernel path (tiny_batch.hip).  *done = whether the batch went that way. */
+int run_tiny(pya_plan *p, const BatchDev &d, hipStream_t st, bool *done) {
+    pya_handle *h = p->h;
+    *done = false;
+    if ((p->flags & PYA_FLAG_TIMING) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty())
+        return PYA_OK;
+    /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
+     * caps count too -- leaving them out sized this launch's work areas for the other PSMs only) */
+    Bucket m;
+    m.take_knobs(h->kn);
+    for (const Bucket &bk : p->buckets)
+        if (!bk.ids.empty()) m.absorb(bk);
+    if (!p->fusedb.ids.empty()) m.absorb(p->fusedb);
+    if (p->n_big_inline != 0) m.absorb(p->bigloc);
+    const uint32_t prefix = score_prefix(h, m.n_cap), compact = score_compact(h->cfg, m.z_max);
+    /* the merged caps (maxima over the buckets) can ask for more LDS than any single bucket does:
+     * such a batch takes the three-kernel path, whose launches are sized per bucket */
+    if (pya_tiny_lds_bytes(p->peak_cap, prefix, with_nl(h->cfg), compact, m.push_cap(), m.n_cap, m.pos_cap, m.pool_cap(), m.sb()) > kMaxLds)
+        return PYA_OK;
+    int e = pya_launch_tiny(&d, (uint32_t)p->n_psm, p->peak_cap, prefix, with_nl(h->cfg), compact, m.push_cap(), m.n_cap, m.pos_cap,
+                            m.pool_cap(), m.sb(), m.gtp(), st);
+    if (e) return h->hip_fail((hipError_t)e, "tiny_batch launch");
+    *done = true;
+    return PYA_OK;
+}
+
+int run_binning(pya_plan *p, const BatchDev &d, hipStream_t st) {
+    pya_handle *h = p->h;
+    int e = 0;
+    for (const pya_plan::IdList &l : p->bin_lists) {
+        /* dense classes: selection first (bin_select.hip.h); the all-pairs ranking of bin_fast is O(window^2) and holds 13 bytes
+         * of LDS per raw peak */
+        const uint32_t scap = (uint32_t)std::min<int64_t>(std::max<int64_t>(h->kn.bin_select_scap, 64), 4096) & ~31u;
+        if ((int64_t)l.cap > h->kn.bin_select_min)
+            e = pya_launch_bin_select(&d, p->d_bin_ids.p + l.off, l.n, scap, st);
+        else
+            e = pya_launch_bin(&d, p->d_bin_ids.p + l.off, l.n, l.cap, st);
+        if (e) return h->hip_fail((hipError_t)e, "bin_spectra launch");
+    }
+    e = pya_launch_bin_exact(&d, (uint32_t)p->n_psm, p->peak_cap, st);
+    if (e) return h->hip_fail((hipError_t)e, "bin_spectra (exact) launch");
+    e = pya_launch_bin_global(&d, p->d_bigbin_ids.p, (uint32_t)p->bigbin_ids.size(), p->d_bigbin_scratch.p, p->bigbin_stride, p->bigbin_cap, st);
+    if (e) return h->hip_fail((hipError_t)e, "bin_spectra (global) launch");
+    return PYA_OK;
+}
+
+/* the fused family: few site assignments, plain settings, scored and localised in one pass (score_localize.hip), one PSM
+ * per wavefront; what it hands over goes through the general localize instantiation.  On `fs`: the plan's side stream when
+ * the run forks (every other family is independent of it: other PSMs, other hand-over lists), else the caller's. */
+int run_fused_family(pya_plan *p, const BatchDev &d, hipStream_t fs) {
+    pya_handle *h = p->h;
+    const Bucket &fb = p->fusedb;
+    for (const pya_plan::FusedLaunch &l : p->fused_launches) {
+        int fe = pya_launch_fused(&d, p->d_fused_ids.p + l.off, l.n, l.cap, l.n_cap, l.stride, l.pos_cap, l.ent_cap, l.push_cap,
+                                  p->fused_both, l.multi_z, d.redo4_count, d.redo4_ids, fs);
+        if (fe) return h->hip_fail((hipError_t)fe, "score_localize launch");
+    }
+    int fe = pya_launch_localize_redo(&d, d.redo4_count, d.redo4_ids, p->n_fused_total, fb.push_cap(), fb.n_cap,
+                                      fb.pos_cap, fb.pool_cap(), fb.sb(), fb.gtp(), fs);
+    if (fe) return h->hip_fail((hipError_t)fe, "localize (hand-over) launch");
+    return PYA_OK;
+}
+
+/* the scoring kernels of every PSM that is not fused and not general: per C(n,k) class and peak class, then score_big's */
+int run_scoring(pya_plan *p, const BatchDev &d, hipStream_t st) {
+    pya_handle *h = p->h;
+    int e = 0;
+    for (const pya_plan::IdList &l : p->score_lists) {
+        const Bucket &bk = p->buckets[l.ncls];
+        const uint32_t *ids = p->d_score_ids.p + l.off;
+        const ScoreRoute r = pick_score_route(h, bk, l.ncls, l.cap);
+        switch (r.kind) {
+            case ScoreRoute::kCountNodes:
+                e = pya_launch_score_cnt(&d, ids, l.n, l.cap, bk.pos_cap, r.kc, bk.k_max, bk.ns_max, st);
+                if (e) return h->hip_fail((hipError_t)e, "score_cnt launch");
+                break;
+            case ScoreRoute::kCountNodesGeneral:
+                e = pya_launch_score_cntg(&d, ids, l.n, l.cap, bk.pos_cap, bk.k_max, bk.ns_max, r.nl_cap, st);
+                if (e) return h->hip_fail((hipError_t)e, "score_cntg launch");
+                break;
+            case ScoreRoute::kSignatures:
+                e = pya_launch_score(&d, ids, l.n, l.cap, r.prefix, with_nl(h->cfg), r.compact, r.node_cap, r.node_cols, bk.node_words,
+                                     r.res_cap, r.nl_cap, st);
+                if (e) return h->hip_fail((hipError_t)e, "score_signatures launch");
+                break;
+        }
+    }
+    for (const pya_plan::IdList &l : p->big_lists) {
+        e = pya_launch_score_big(&d, p->d_big_ids.p + l.off, l.n, l.cap, p->big_pos_cap, p->big_kc(), p->big_inline ? 1u : 0u, st);
+        if (e) return h->hip_fail((hipError_t)e, "score_big launch");
+    }
+    return PYA_OK;
+}
+
+/* what score_big scored in its summary mode: the lean body with recounted signatures and the winner score_big
+ * named; what that declines is scored again with count records and goes to the general localize body */
+int run_big_inline(pya_plan *p, const BatchDev &d, hipStream_t st) {
+    pya_handle *h = p->h;
+    const Bucket &bl = p->bigloc;
+    uint32_t *count = d.redo_count + 2, *ids = p->d_redo5.p + kRedoHead;
+    int e = pya_launch_localize_recount(&d, bl.d_ids.p, (uint32_t)bl.ids.size(), 0u, bl.push_cap(), bl.pos_cap, bl.pool_cap(),
+                                        bl.sb(), bl.gtp(), count, ids, st);
+    if (e) return h->hip_fail((hipError_t)e, "localize (recount) launch");
+    e = pya_launch_score_big_list(&d, count, ids, p->n_big_inline, p->peak_cap, p->big_pos_cap, p->big_kc(), st);
+    if (e) return h->hip_fail((hipError_t)e, "score_big (hand-over) launch");
+    e = pya_launch_localize_redo(&d, count, ids, p->n_big_inline, bl.push_cap(), (uint32_t)pya_big_inline_max(),
+                                 bl.pos_cap, bl.pool_cap(), bl.sb(), bl.gtp(), st);
+    if (e) return h->hip_fail((hipError_t)e, "localize (score_big hand-over) launch");
+    return PYA_OK;
+}
+
+/* every class: the lean instantiation for its plain PSMs, then the general one (hash route where its tables fit) */
+int run_localize(pya_plan *p, const BatchDev &d, hipStream_t st) {
+    pya_handle *h = p->h;
+    const uint32_t nnl = (uint32_t)h->cfg.n_nl;
+    for (Bucket &bk : p->buckets) {
+        /* more than sort_room_max signatures: the lean launch without room for the sort emulation (LDS ->
+         * occupancy); PSMs with a tie at the top go through the hand-over list to a second lean pass that has it */
+        const uint32_t sort_room = (bk.n_cap <= h->kn.sort_room_max || h->kn.sort_room) ? 1u : 0u;
+        int e = pya_launch_localize(&d, bk.d_ids.p, bk.n_plain, bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(), bk.sb(),
+                                    bk.gtp(), 1u, sort_room, st);
+        if (e) return h->hip_fail((hipError_t)e, "localize launch");
+        if (h->kn.host_timing && !bk.ids.empty() && p->n_runs == 1)    /* diagnostics: what decides the general route's occupancy */
+            std::fprintf(stderr, "[pya plan] localize bucket: %zu PSMs, LDS hash route %zu B (vc %u hs %u pp %u sb %u push %u), list route %zu B\n",
+                         bk.ids.size(), pya_localize_hash_lds_bytes(bk.push_cap(), bk.n_cap, bk.pos_cap, bk.sb(), bk.hash_vc(), bk.hash_hs(),
+                                                                    bk.hash_pp(), p->max_k, nnl),
+                         bk.hash_vc(), bk.hash_hs(), bk.hash_pp(), bk.sb(), bk.push_cap(),
+                         pya_localize_lds_bytes(bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(), bk.sb()));
+        const uint32_t *general_ids = bk.d_ids.p + bk.n_plain, n_general = (uint32_t)bk.ids.size() - bk.n_plain;
+        if (!h->kn.no_loc_hash && bk.hash_ok(p->max_k, nnl))
+            e = pya_launch_localize_hash(&d, general_ids, n_general, bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(), bk.sb(),
+                                         bk.gtp(), bk.hash_vc(), bk.hash_hs(), bk.hash_pp(), nnl, st);
+        else
+            e = pya_launch_localize(&d, general_ids, n_general, bk.push_cap(), bk.n_cap, bk.pos_cap, bk.pool_cap(), bk.sb(),
+                                    bk.gtp(), 0u, 1u, st);
+        if (e) return h->hip_fail((hipError_t)e, "localize launch");
+    }
+    return PYA_OK;
+}
+
+int run_general(pya_plan *p, const BatchDev &d, hipStream_t st) {
+    int e = pya_launch_general(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), p->d_gen_scratch.p, p->d_gen_off.p, p->gen_l_cap,
+                               p->gen_list_cap, st);
+    if (e) return p->h->hip_fail((hipError_t)e, "general kernel launch");
+    return PYA_OK;
+}
+
+/* Everything of a run behind the binning.  A forked run has recorded ev_fork on `st` by now and pya_plan_run joins the
+ * side stream whatever this returns: nothing in here leaves pya_plan_run on its own. */
+int run_behind_binning(pya_plan *p, const BatchDev &d, hipStream_t st, const RunMarks &mark) {
+    pya_handle *h = p->h;
+    int rc;
+    if (mark.alias) mark.alias[5] = 0;
+    if (p->fork) {
+        HIPCHK(h, hipStreamWaitEvent(p->side, p->ev_fork, 0));
+        if (mark.ev) {
+            mark.alias[5] = 1;
+            HIPCHK(h, hipEventRecord(mark.ev[5], p->side));
+        }
+        if ((rc = run_fused_family(p, d, p->side))) return rc;
+        if (mark.ev) HIPCHK(h, hipEventRecord(mark.ev[6], p->side));
+    }
+    if ((rc = run_scoring(p, d, st))) return rc;
+    if ((rc = mark(2, pya_plan::any_ids(p->score_lists) || pya_plan::any_ids(p->big_lists)))) return rc;
+    const bool fused_here = p->n_fused_total != 0 && !p->fork;
+    if (fused_here && (rc = run_fused_family(p, d, st))) return rc;
+    if ((rc = mark(3, fused_here))) return rc;
+    const bool big_inline = p->big_inline && !p->bigloc.ids.empty();
+    if (big_inline && (rc = run_big_inline(p, d, st))) return rc;
+    if ((rc = run_localize(p, d, st))) return rc;
+    if (!p->gen_ids.empty() && (rc = run_general(p, d, st))) return rc;
+    if (mark.ev) {
+        bool loc = big_inline || !p->gen_ids.empty();
+        for (const Bucket &bk : p->buckets) loc = loc || !bk.ids.empty();
+        if ((rc = mark(4, loc))) return rc;
+        p->ev_runs++;
+        if (p->ev_runs - p->ev_read > pya_plan::kEvRing) p->ev_read = p->ev_runs - pya_plan::kEvRing;   /* (overwritten) */
+    }
+    return PYA_OK;
+}
+
+}  // namespace
+
+int pya_plan_run(pya_plan *p, const double *d_mz, const double *d_inten, void *hip_stream,
+                 const pya_results *o) {
+    if (!p || !o) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!d_mz || !d_inten || !o->best_score || !o->best_sig || !o->n_sig || !o->ascores || !o->alt_mask)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_run");
+    if (o->max_k < p->max_k)
+        return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)",
+                       o->max_k, p->max_k);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.mz = d_mz;
+    d.inten = d_inten;
+    d.best_score = o->best_score;
+    d.best_sig = o->best_sig;
+    d.n_sig_out = o->n_sig;
+    d.ascores = o->ascores;
+    d.alt_mask = o->alt_mask;
+    d.max_k = o->max_k;
+    bool tiny = false;
+    int rc = run_tiny(p, d, st, &tiny);
+    if (rc) return rc;
+    if (!tiny) {
+        const bool timing = p->flags & PYA_FLAG_TIMING;
+        const RunMarks mark = {h, st, timing ? p->ev_set(p->ev_runs) : nullptr, timing ? p->ev_alias(p->ev_runs) : nullptr};
+        if ((rc = mark(0, true))) return rc;
+        /* hand-over counts (bin_spectra's, the fused kernel's, the recount's): two sets at the head of d_redo, taken in turn;
+         * the binning kernel of a run zeroes the set of the next (bin_spectra.hip), so only a plan without such a launch --
+         * every spectrum binned by the global kernel, or set aside -- and the first run need a memset */
+        uint32_t *cnt = p->d_redo.p + 8 * (p->n_runs & 1u);
+        d.redo_count = cnt;
+        d.redo4_count = cnt + 1;
+        d.zero_next = p->d_redo.p + 8 * ((p->n_runs + 1u) & 1u);
+        if (p->n_runs == 0 || !pya_plan::any_ids(p->bin_lists)) HIPCHK(h, hipMemsetAsync(p->d_redo.p, 0, 16 * sizeof(uint32_t), st));
+        p->n_runs++;
+        if ((rc = run_binning(p, d, st))) return rc;
+        if ((rc = mark(1, true))) return rc;
+        if (!p->fork) {
+            if ((rc = run_behind_binning(p, d, st, mark))) return rc;
+        } else {
+            /* From the fork to the join there is ONE way out, failing or not: whatever the caller enqueues behind this run
+             * -- the plan's next run included -- waits for the side stream too (after boundary 4, so that the localize
+             * family's interval does not include the wait).  The first error is what the call returns. */
+            HIPCHK(h, hipEventRecord(p->ev_fork, st));
+            rc = run_behind_binning(p, d, st, mark);
+            hipError_t ej = hipEventRecord(p->ev_join, p->side);
+            if (ej == hipSuccess) ej = hipStreamWaitEvent(st, p->ev_join, 0);
+            if (ej != hipSuccess && !rc) rc = h->hip_fail(ej, "joining the side stream");
+        }
+    }
+    p->last_stream = st;
+    p->ran = true;
+    p->dev = d;
+    return rc;
+}
+
+namespace {
+/* The four intervals of the runs [r0, r1) added to ms[] (waits for the latest of them): boundary to boundary on the caller's
+ * stream, and the fused family's own interval on the side stream when a run forked (boundaries 2 and 3 are then one event). */
+int add_run_intervals(pya_plan *p, uint64_t r0, uint64_t r1, double ms[4]) {
+    pya_handle *h = p->h;
+    HIPCHK(h, hipEventSynchronize(p->ev_set(r1 - 1)[p->ev_alias(r1 - 1)[4]]));
+    if (p->ev_alias(r1 - 1)[5]) HIPCHK(h, hipEventSynchronize(p->ev_set(r1 - 1)[6]));
+    for (uint64_t r = r0; r < r1; r++) {
+        hipEvent_t *ev = p->ev_set(r);
+        const uint8_t *al = p->ev_alias(r);
+        for (int i = 0; i < 4; i++) {
+            float t = 0.f;
+            if (al[i] != al[i + 1]) HIPCHK(h, hipEventElapsedTime(&t, ev[al[i]], ev[al[i + 1]]));
+            ms[i] += (double)t;
+        }
+        float side = 0.f;
+        if (al[5]) HIPCHK(h, hipEventElapsedTime(&side, ev[5], ev[6]));
+        ms[2] += (double)side;
+    }
+    return PYA_OK;
+}
+}  // namespace
+
+int pya_plan_timings(pya_plan *p, float ms[4]) {
+    if (!p || !ms) return PYA_ERR_ARG;
+    if (!(p->flags & PYA_FLAG_TIMING) || p->ev_runs == 0) return p->h->fail(PYA_ERR_STATE, -1, "plan has no timing events");
+    double sum[4] = {0., 0., 0., 0.};
+    const int rc = add_run_intervals(p, p->ev_runs - 1, p->ev_runs, sum);
+    for (int i = 0; i < 4; i++) ms[i] = (float)sum[i];
+    return rc;
+}
+
+int pya_plan_timings_sum(pya_plan *p, double ms[4], uint32_t *n_runs) {
+    if (!p || !ms || !n_runs) return PYA_ERR_ARG;
+    if (!(p->flags & PYA_FLAG_TIMING)) return p->h->fail(PYA_ERR_STATE, -1, "plan has no timing events");
+    for (int i = 0; i < 4; i++) ms[i] = 0.;
+    *n_runs = (uint32_t)(p->ev_runs - p->ev_read);
+    if (*n_runs == 0) return PYA_OK;
+    const int rc = add_run_intervals(p, p->ev_read, p->ev_runs, ms);
+    if (rc) return rc;
+    p->ev_read = p->ev_runs;
+    return PYA_OK;
+}
+
+int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid) {
+    if (skip_invalid) return PYA_OK;                    /* codes are reported per PSM instead */
+    for (uint64_t i = 0; i < n; i++) {
+        switch (st[i]) {
+            case PYA_ST_OK: break;
+            case PYA_ST_INVALID:
+            case PYA_ST_OVER_LIMIT:
+                return h->fail(st[i] == PYA_ST_INVALID ? PYA_ERR_PSM : PYA_ERR_LIMIT, (int64_t)i,
+                               "PSM %llu was set aside by the host pre-pass", (unsigned long long)i);
+            case PYA_ST_NO_BINS:
+                return h->fail(PYA_ERR_PSM, (int64_t)i, "PSM %llu: all peaks sit on one multiple of 100 m/z; the "
+                               "spectrum has no windows", (unsigned long long)i);
+            case PYA_ST_TOO_MANY_BINS:
+                return h->fail(PYA_ERR_LIMIT, (int64_t)i, "PSM %llu: more than 65535 m/z windows", (unsigned long long)i);
+            case PYA_ST_LUT_RANGE:
+                return h->fail(PYA_ERR_LIMIT, (int64_t)i, "PSM %llu: trial count outside the score table", (unsigned long long)i);
+            case PYA_ST_PUSHED_OVERFLOW:
+                return h->fail(PYA_ERR_LIMIT, (int64_t)i, "PSM %llu: more than %d tied competitors", (unsigned long long)i, PYA_MAX_PUSHED);
+            case PYA_ST_ROUTE_CAPS:
+                return h->fail(PYA_ERR_STATE, (int64_t)i, "PSM %llu reached a kernel whose launch was not sized for it (modifications or "
+                               "modifiable residues beyond the launch's caps): a routing error of this library", (unsigned long long)i);
+            default:
+                return h->fail(PYA_ERR_HIP, (int64_t)i, "PSM %llu: unexpected kernel status %d", (unsigned long long)i, st[i]);
+        }
+    }
+    return PYA_OK;
+}
+
+int pya_plan_check(pya_plan *p) {
+    if (!p) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (!p->ran || p->n_psm == 0) return PYA_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(p->last_stream));
+    std::vector<int32_t> st(p->n_psm);
+    HIPCHK(h, hipMemcpy(st.data(), p->d_status.p, p->n_psm * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (h->kn.host_timing) {                               /* diagnostics: how many PSMs the lean kernels handed over */
+        uint32_t r3 = 0, r4 = 0;
+        (void)hipMemcpy(&r3, p->d_redo3.p, 4, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(&r4, p->d_redo.p + 8 * ((p->n_runs + 1u) & 1u) + 1, 4, hipMemcpyDeviceToHost);   /* (the last run's set) */
+        std::fprintf(stderr, "[pya plan] handed over: %u by the lean localize instantiation (last bucket), %u of %u by the fused kernel\n",
+                     r3, r4, p->n_fused_total);
+    }
+    const bool skip = (p->flags & PYA_FLAG_SKIP_INVALID) != 0;
+    if (skip) h->last_status = st;
+    return check_status(h, st.data(), p->n_psm, skip);
+}
+
+int pya_pack_records(pya_handle *h, const pya_results *d_res, uint64_t n_psm, uint32_t k, int32_t *d_out, void *hip_stream) {
+    if (!h) return PYA_ERR_ARG;
+    if (!d_res || !d_out || !d_res->best_score || !d_res->best_sig || !d_res->n_sig || !d_res->ascores || !d_res->alt_mask)
+        return h->fail(PYA_ERR_ARG, -1, "pya_pack_records: null result array");
+    if (k < d_res->max_k || k > 64 || d_res->max_k == 0)
+        return h->fail(PYA_ERR_ARG, -1, "pya_pack_records: record width k = %u is narrower than the results' rows (%u) or above 64", k,
+                       d_res->max_k);
+    HIPCHK(h, hipSetDevice(h->device));
+    const int e = pya_launch_pack_records(d_res->best_score, d_res->n_sig, d_res->best_sig, d_res->ascores, d_res->alt_mask, k,
+                                          d_res->max_k, n_psm, d_out, (hipStream_t)hip_stream);
+    if (e) return h->fail(PYA_ERR_HIP, -1, "pya_pack_records: launch failed (%d)", e);
+    return PYA_OK;
+}

@@ -275,4 +275,29 @@ uint32_t next_pow2(uint32_t v) {
     return p;
 }
 
-/* tables owned by the handle may have been re-uploaded (grown) since the plan was made */
+int upload_shared_tables(pya_handle *h) {
+    if (h->order_uploaded == h->order_tab.size() && h->d_order.p) return PYA_OK;
+    HIPCHK(h, h->d_order.upload(h->order_tab.data(), h->order_tab.size()));
+    HIPCHK(h, h->d_inv.upload(h->inv_tab.data(), h->inv_tab.size()));
+    if (!h->d_binom.p) {
+        std::vector<uint32_t> bt(64 * 64);
+        for (uint32_t pp = 0; pp < 64; pp++)
+            for (uint32_t t = 0; t < 64; t++) bt[pp * 64 + t] = (uint32_t)std::min<uint64_t>(binom(pp, t), 0xffffffffull);
+        HIPCHK(h, h->d_binom.upload(bt.data(), bt.size()));
+    }
+    /* (null-stream copies; the kernels that read these tables may run on a non-blocking stream) */
+    HIPCHK(h, hipDeviceSynchronize());
+    h->order_uploaded = h->order_tab.size();
+    return PYA_OK;
+}
+
+/* (asked for at every run: tables owned by the handle may have been re-uploaded, grown, since the plan was made) */
+void shared_tables(const pya_handle *h, BatchDev &d) {
+    d.order_tab = h->d_order.p;
+    d.inv_tab = h->d_inv.p;
+    d.binom = h->d_binom.p;
+    d.cfg = h->d_cfg.p;
+    d.lut = h->d_lut.p;
+    d.lut_off = h->d_lut_off.p;
+    d.lut_n_max = h->lut_uploaded_n - 1;
+}
