@@ -12,6 +12,8 @@
  *                                    ModifiedPeptide::consumePeptide/consumePeak
  *                                    cpp/ModifiedPeptide.cpp:105-142, Ascore::score
  *                                    cpp/Ascore.cpp:256-271)
+ *   pya_score_batch_shared /      the hit_depth loop of the command line: every hit of a scan is scored against
+ *   pya_plan_create_shared        the scan's ONE spectrum           pyascore/__main__.py (groupby(psms, scan), hit_depth)
  *   pya_results fields            best_score / ascores / alt_sites / best signature
  *                                                                     Ascore.pyx:232-288
  *   pya_get_pep_scores            PyAscore.pep_scores                 Ascore.pyx:241-252
@@ -158,10 +160,29 @@ int64_t pya_error_index(const pya_handle *h);
 int pya_score_batch(pya_handle *h, const pya_batch *batch, const double *mz,
                     const double *intensity, uint32_t flags, const pya_results *out);
 
+/* Several PSMs against one spectrum -- the reference's command line groups the identifications by scan and scores the first
+ * --hit_depth of every group against the scan's spectrum (pyascore/__main__.py, the groupby(psms, scan) loop); ranked hits of
+ * a search engine and co-isolated peptides of a chimeric spectrum are the same case.  pya_score_batch with
+ *   - batch->peak_off of n_spectra + 1 entries: it describes the SPECTRA (mz / intensity hold every spectrum once),
+ *   - spec_of[i] = the spectrum of PSM i, 0 <= spec_of[i] < n_spectra, NON-DECREASING in i: the PSMs of a spectrum are
+ *     consecutive.
+ * Every spectrum is uploaded and binned once, and its retained peaks are held once.  The binning depends on the peaks and
+ * the scorer's bin_size / n_top alone (cpp/Spectra.cpp:43-68), so every result is bit-equal to what pya_score_batch gives
+ * for the same PSMs with the spectrum repeated, whatever the cut into chunks.
+ *   - spec_of out of range or decreasing, or n_spectra == 0 with PSMs present: PYA_ERR_ARG, the message names the PSM;
+ *   - a spectrum no PSM refers to is legal: it is uploaded with the rest and neither binned nor given workspace;
+ *   - what belongs to the spectrum (empty, more than PYA_MAX_PEAKS peaks, PYA_PSM_NO_WINDOWS, PYA_PSM_TOO_MANY_WINDOWS)
+ *     hits EVERY PSM of that spectrum with the code the repeated-spectrum batch gives it; an invalid peptide hits its own
+ *     PSM only, its siblings are scored.  Flags as for pya_score_batch; pya_last_batch_status, pya_get_pep_scores* and
+ *     pya_calculate_ambiguity go by PSM number. */
+int pya_score_batch_shared(pya_handle *h, const pya_batch *batch, const uint32_t *spec_of, uint64_t n_spectra,
+                           const double *mz, const double *intensity, uint32_t flags, const pya_results *out);
+
 /* Device memory one pya_score_batch call may hold at a time (upload ring + workspace; default 6 GiB,
  * or PYA_WORKSPACE_MB).  Calls that need more -- and every call with more than 32 MB of spectra -- are
  * cut into chunks of consecutive PSMs and pipelined: the upload of chunk c + 1 runs under the kernels
- * and the result copy of chunk c.  Results do not depend on the cut. */
+ * and the result copy of chunk c.  Results do not depend on the cut.  (pya_score_batch_shared: a chunk holds each of its
+ * spectra once; a group of PSMs bigger than a chunk is cut, its spectrum then travels with both parts.) */
 int pya_set_workspace_budget(pya_handle *h, uint64_t bytes);
 /* the budget in force (the value set, PYA_WORKSPACE_MB, or the default of 6 GiB) */
 uint64_t pya_get_workspace_budget(const pya_handle *h);
@@ -172,6 +193,12 @@ int pya_last_batch_status(pya_handle *h, int32_t *status, uint64_t n);
 
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
+/* the same for a batch whose PSMs share spectra (pya_score_batch_shared: batch->peak_off describes n_spectra spectra,
+ * spec_of[i] names PSM i's; the reference's hit_depth loop, pyascore/__main__.py).  pya_plan_run and every other pya_plan_*
+ * function take such a plan unchanged: d_mz / d_intensity are laid out by the spectra's peak_off, results and status are per
+ * PSM.  pya_plan_workspace_bytes is smaller than the repeated-spectrum plan's by the retained tables saved. */
+int pya_plan_create_shared(pya_handle *h, const pya_batch *batch, const uint32_t *spec_of, uint64_t n_spectra,
+                           uint32_t flags, pya_plan **out);
 int pya_plan_run(pya_plan *plan, const double *d_mz, const double *d_intensity,
                  void *hip_stream, const pya_results *d_out);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,

@@ -19,6 +19,12 @@ def _as_ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _renumber_psm(message, perm):
+    """'PSM <j>: ...' of a batch that was scored in the order ``perm`` -> the caller's number of that PSM."""
+    import re
+    return re.sub(r"^PSM (\d+)", lambda m: "PSM %d" % perm[int(m.group(1))] if int(m.group(1)) < len(perm) else m.group(0), message)
+
+
 def _check_f64(name, a):
     if a is None:
         raise TypeError("Argument '%s' must not be None" % name)
@@ -297,7 +303,29 @@ class PyAscore:
         ``skip_invalid=True``: a PSM that is invalid (unknown residue, empty spectrum, ...) or beyond
         a documented limit of this implementation does not fail the call; it gets best_score -1,
         n_sig -1 and a non-zero code in the extra ``status`` array (include/pyascore_hip.h PYA_PSM_*),
-        and ``status_message`` describes the first such PSM."""
+        and ``status_message`` describes the first such PSM.
+
+        Shared spectra: a batch dict with ``spec_of`` (and ``n_spectra``; ``synth.pack_shared_batch``) holds every
+        spectrum once, ``peak_off`` describes the spectra and PSM i is scored against spectrum ``spec_of[i]`` -- the hits
+        of one scan (`pyascore/__main__.py`, the hit_depth loop).  Each spectrum is uploaded and binned once; the results
+        are those of the repeated-spectrum batch (``synth.expand_shared_batch``), bit for bit.  The library wants the PSMs
+        of a spectrum consecutive: a batch in any other order is sorted stably by spectrum, scored, and its rows are put
+        back, so the caller always sees input order (with ``keep=True`` such a batch is scored in its expanded form
+        instead: the retained records are addressed by PSM number)."""
+        if batch.get("spec_of") is not None:
+            from .synth import expand_shared_batch, spectrum_order, take_psms
+            perm, inv = spectrum_order(batch["spec_of"])
+            if perm is not None and keep:
+                return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid)
+            if perm is not None:
+                try:
+                    res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid)
+                except ValueError as e:
+                    raise ValueError(_renumber_psm(str(e), perm)) from None
+                res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
+                if res.get("status_message"):
+                    res["status_message"] = _renumber_psm(res["status_message"], perm)
+                return res
         # the records behind pep_scores / calculate_ambiguity of the last score() PSM are produced on demand by
         # replaying what score() staged in the library: before another call reuses that staging, produce them
         self._ensure_kept()
@@ -313,7 +341,14 @@ class PyAscore:
             aux_pos=np.ascontiguousarray(batch["aux_pos"], np.uint32),
             aux_mass=np.ascontiguousarray(batch["aux_mass"], np.float32),
             aux_off=np.ascontiguousarray(batch["aux_off"], np.int64))
-        if arrs["peak_off"].size != n + 1 or arrs["pep_off"].size != n + 1 or arrs["aux_off"].size != n + 1:
+        spec_of = None
+        n_spec = n
+        if batch.get("spec_of") is not None:
+            spec_of = np.ascontiguousarray(batch["spec_of"], np.uint32)
+            n_spec = int(batch.get("n_spectra", arrs["peak_off"].size - 1))
+            if spec_of.size != n or arrs["peak_off"].size != n_spec + 1:
+                raise ValueError("a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
+        if arrs["peak_off"].size != n_spec + 1 or arrs["pep_off"].size != n + 1 or arrs["aux_off"].size != n + 1:
             raise ValueError("offset arrays must have n_psm + 1 entries")
         if n and (mz.size < arrs["peak_off"][-1] or it.size < arrs["peak_off"][-1]):
             raise ValueError("peak_off runs past the end of the spectrum arrays")
@@ -336,12 +371,19 @@ class PyAscore:
         if keep and n > 1:
             budget = int(self._lib.pya_get_workspace_budget(self._h))
             try:
-                per_psm = self._retained_bytes(dict(arrs, n_of_mod=arrs["n_of_mod"]))
+                # (a shared batch: priced, and re-scored by batch_pep_scores(), in its expanded form)
+                lazy_arrs = arrs if spec_of is None else dict(arrs, peak_off=np.concatenate(
+                    [[0], np.cumsum(np.diff(arrs["peak_off"])[spec_of])]).astype(np.int64))
+                per_psm = self._retained_bytes(dict(lazy_arrs, n_of_mod=arrs["n_of_mod"]))
                 lazy_keep = float(per_psm.sum()) > 0.8 * budget
             except (IndexError, ValueError):
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0)
-        rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), flags, C.byref(r))
+        if spec_of is None:
+            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), flags, C.byref(r))
+        else:
+            rc = self._lib.pya_score_batch_shared(self._h, C.byref(b), _as_ptr(spec_of), n_spec, _as_ptr(mz), _as_ptr(it), flags,
+                                                  C.byref(r))
         if rc:
             self._raise(rc)
         self._batch_n = n if keep else None
@@ -351,6 +393,9 @@ class PyAscore:
             # (references, not copies: a batch this size is gigabytes.  The arrays must not be modified before
             # batch_pep_scores() has been read -- it re-scores the ranges it is asked for from them.)
             self._lazy_batch = dict(arrs, mz=mz, intensity=it, n_psm=n, per_psm=per_psm, budget=budget)
+            if spec_of is not None:
+                from .synth import expand_shared_batch
+                self._lazy_batch = expand_shared_batch(dict(self._lazy_batch, spec_of=spec_of))
         if skip_invalid:
             out["status"] = np.zeros(n, np.int32)
             rc = self._lib.pya_last_batch_status(self._h, _as_ptr(out["status"]), n)

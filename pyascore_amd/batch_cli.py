@@ -17,7 +17,7 @@ from itertools import groupby
 import numpy as np
 
 from .ascore import PyAscore
-from .synth import pack_batch
+from .synth import pack_batch, pack_shared_batch
 
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
 
@@ -96,6 +96,20 @@ def select_psms(psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment
     return picked, scans
 
 
+def pack_hits(picked, scans):
+    """``select_psms``' output as one batch in which the hits of a scan share the scan's spectrum: consecutive PSMs of
+    one scan (the reference scores every one of them against ``spectra_map[scan]``, `__main__.py:129-164`) refer to ONE
+    copy of its peaks.  With one hit per scan this is ``pack_batch(picked)``, array for array."""
+    spectra, spec_of = [], []
+    for i, psm in enumerate(picked):
+        if not (i and scans[i] == scans[i - 1] and psm["mz"] is picked[i - 1]["mz"] and psm["intensity"] is picked[i - 1]["intensity"]):
+            spectra.append(dict(mz=psm["mz"], intensity=psm["intensity"]))
+        spec_of.append(len(spectra) - 1)
+    if len(spectra) == len(picked):
+        return pack_batch(picked)
+    return pack_shared_batch(spectra, [dict(p, spectrum=s) for p, s in zip(picked, spec_of)])
+
+
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
@@ -108,7 +122,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
                                 mod_correction_tol, zero_based, match_save)
     if not picked:
         return []
-    batch = pack_batch(picked)
+    batch = pack_hits(picked, scans)
     # One PSM the kernels cannot take (longer than 64 residues, more than 15 000 site assignments,
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.

@@ -97,6 +97,29 @@ __global__ __launch_bounds__(64) void pya_bin_global_kernel(BatchDev b, const ui
     bin_store(b, psm, R, status, r_mz, r_rank);
 }
 
+/* Shared spectra (pya_plan_create_shared; the hit_depth loop of the reference's __main__.py scores every hit of a scan
+ * against the same spectrum): the kernels above then run over spectrum ids and leave ret_n and the binning status per
+ * SPECTRUM.  This gives every PSM its spectrum's two words, after the whole binning family (the exact and the global
+ * kernel included) and before the first scoring launch, whose prologues read ret_n[psm] and status[psm] without an
+ * indirection.  spec_of[psm] == ~0u: set aside by the host pre-pass, no spectrum was binned for it and its status stays. */
+__global__ __launch_bounds__(256) void pya_fan_out_kernel(const uint32_t *spec_of, const uint32_t *spec_ret_n, const int32_t *spec_status,
+                                                          uint32_t *ret_n, int32_t *status, uint32_t n_psm) {
+    const uint32_t psm = blockIdx.x * 256u + threadIdx.x;
+    if (psm >= n_psm) return;
+    const uint32_t s = spec_of[psm];
+    if (s == 0xffffffffu) return;
+    ret_n[psm] = spec_ret_n[s];
+    status[psm] = spec_status[s];
+}
+
+extern "C" int pya_launch_fan_out(const uint32_t *d_spec_of, const uint32_t *d_spec_ret_n, const int32_t *d_spec_status, uint32_t *d_ret_n,
+                                  int32_t *d_status, uint32_t n_psm, hipStream_t stream) {
+    if (n_psm == 0) return 0;
+    hipLaunchKernelGGL(pya_fan_out_kernel, dim3((n_psm + 255u) / 256u), dim3(256), 0, stream, d_spec_of, d_spec_ret_n, d_spec_status,
+                       d_ret_n, d_status, n_psm);
+    return (int)hipGetLastError();
+}
+
 extern "C" size_t pya_bin_global_scratch_bytes(uint32_t cap) { return PYA_BIN_WAVE_BYTES(cap); }
 
 extern "C" int pya_launch_bin_global(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, unsigned char *d_scratch,

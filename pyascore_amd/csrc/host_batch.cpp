@@ -22,17 +22,20 @@ namespace {
  * and metadata).  C(n,k) comes from the peptide letters, as in the plan's pre-pass. */
 struct ChunkCost {
     std::vector<double> arena, io;             /* per PSM */
+    std::vector<double> ret;                   /* shared spectra: the retained table, kept out of `arena` -- it and `io` count once per spectrum of a chunk */
     std::vector<uint8_t> sites;                /* modifiable residues per PSM, 255 = invalid letters / length */
 };
-ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, uint32_t max_k) {
+ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, const SpecShare *sh, uint32_t max_k) {
     const uint64_t n = b->n_psm;
     ChunkCost c;
     c.arena.resize(n);
     c.io.resize(n);
+    if (sh) c.ret.resize(n);
     c.sites.assign(n, 255);
     auto work = [&](uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; i++) {
-            const int64_t P = std::max<int64_t>(0, b->peak_off[i + 1] - b->peak_off[i]);
+            const uint64_t s = sh ? sh->spec_of[i] : i;
+            const int64_t P = std::max<int64_t>(0, b->peak_off[s + 1] - b->peak_off[s]);
             const int64_t L = b->pep_off[i + 1] - b->pep_off[i];
             double sigs = 0;
             uint32_t n_sites = 0;
@@ -58,7 +61,9 @@ ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, uint32_t max_k) {
                 extra += (double)pya_general_scratch_bytes((uint32_t)sigs, kk <= ns ? ((kk * (ns - kk)) + 3u) & ~3u : 0u) + 256.0;
                 if (P > PYA_FAST_PEAKS) extra += 16.0 * (double)PYA_MAX_PEAKS;
             }
-            c.arena[i] = 8.0 * (double)(P + 1) + 8.0 + (4.0 + 4.0 * (double)h->rec_words()) * sigs + extra + (double)L + 2.0 * PYA_GRID_CELLS + 96.0 + 12.0 * max_k;
+            const double ret = 8.0 * (double)(P + 1);
+            if (sh) c.ret[i] = ret;
+            c.arena[i] = (sh ? 0. : ret) + 8.0 + (4.0 + 4.0 * (double)h->rec_words()) * sigs + extra + (double)L + 2.0 * PYA_GRID_CELLS + 96.0 + 12.0 * max_k;
         }
     };
     for_psm_ranges(n, work);
@@ -81,10 +86,14 @@ void rebase_error(pya_handle *h, uint64_t lo) {
  * PCIe (the bound of this entry point: 16 bytes per peak) into the other slot of a two-slot ring
  * while this thread plans chunk c, runs its kernels and brings its results back on a second
  * stream.  A call of any size completes; it never fails for lack of workspace. */
-static int score_batch_chunked(pya_handle *h, const pya_batch *b, const double *mz, const double *inten,
+static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const double *mz, const double *inten,
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
                                const uint8_t *pre_sites) {
     const size_t nchunk = cuts.size() - 1;
+    /* the spectra [first, last) of chunk c: its PSMs' own unless spectra are shared -- then from the first PSM's to the last
+     * PSM's, each uploaded once (a group cut in two travels with both parts) */
+    auto spec_lo = [&](size_t c) -> uint64_t { return sh ? sh->spec_of[cuts[c]] : cuts[c]; };
+    auto spec_hi = [&](size_t c) -> uint64_t { return sh ? (uint64_t)sh->spec_of[cuts[c + 1] - 1] + 1 : cuts[c + 1]; };
     const uint32_t mk = out->max_k;
     const bool skip = (flags & PYA_FLAG_SKIP_INVALID) != 0;
     HIPCHK(h, hipSetDevice(h->device));
@@ -92,7 +101,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const double *
     if (!h->run_stream) HIPCHK(h, hipStreamCreateWithFlags(&h->run_stream, hipStreamNonBlocking));
     size_t slot_peaks = 0;
     for (size_t c = 0; c < nchunk; c++)
-        slot_peaks = std::max<size_t>(slot_peaks, (size_t)(b->peak_off[cuts[c + 1]] - b->peak_off[cuts[c]]));
+        slot_peaks = std::max<size_t>(slot_peaks, (size_t)(b->peak_off[spec_hi(c)] - b->peak_off[spec_lo(c)]));
     for (auto &slot : h->io_ring)
         if (slot.n < slot_peaks * 2) HIPCHK(h, slot.alloc(slot_peaks * 2));
     if (skip) h->last_status.assign(b->n_psm, 0);
@@ -112,7 +121,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const double *
                 cv.wait(lk, [&] { return stop || c < consumed + 2; });
                 if (stop) break;
             }
-            const int64_t p0 = b->peak_off[cuts[c]], np = b->peak_off[cuts[c + 1]] - p0;
+            const int64_t p0 = b->peak_off[spec_lo(c)], np = b->peak_off[spec_hi(c)] - p0;
             double *dst = h->io_ring[c & 1].p;
             if (np > 0) {
                 e = hipMemcpyAsync(dst, mz + p0, (size_t)np * 8, hipMemcpyHostToDevice, h->copy_stream);
@@ -144,17 +153,19 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const double *
      * chunk c; two plans alive at a time */
     auto make_plan = [&](size_t c, pya_plan **pp) -> int {
         const uint64_t lo = cuts[c], hi = cuts[c + 1];
-        const int64_t np = b->peak_off[hi] - b->peak_off[lo];
+        const uint64_t s_lo = spec_lo(c), s_hi = spec_hi(c);
+        const int64_t np = b->peak_off[s_hi] - b->peak_off[s_lo];
         pya_batch sub = *b;
         sub.n_psm = hi - lo;
-        sub.peak_off = b->peak_off + lo;
+        sub.peak_off = b->peak_off + s_lo;
+        const SpecShare sub_sh = {sh ? sh->spec_of + lo : nullptr, s_hi - s_lo, (uint32_t)s_lo};
         sub.pep_off = b->pep_off + lo;
         sub.n_of_mod = b->n_of_mod + lo;
         sub.max_charge = b->max_charge + lo;
         if (b->aux_off) sub.aux_off = b->aux_off + lo;
         IoReq io = {mz, inten, mk, h->io_ring[c & 1].p, h->io_ring[c & 1].p + np, h->run_stream,
                     pre_sites ? pre_sites + lo : nullptr};
-        int rc = plan_create_impl(h, &sub, flags & ~(PYA_FLAG_TIMING | PYA_FLAG_KEEP), &io, pp);
+        int rc = plan_create_impl(h, &sub, flags & ~(PYA_FLAG_TIMING | PYA_FLAG_KEEP), &io, sh ? &sub_sh : nullptr, pp);
         if (rc) rebase_error(h, lo);
         return rc;
     };
@@ -233,9 +244,10 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const double *
     return finish(PYA_OK);
 }
 
-int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const double *inten, uint32_t flags,
-                    const pya_results *out) {
-    if (!h || !b || !out) return PYA_ERR_ARG;
+/* pya_score_batch (sh == nullptr: PSM i has spectrum i) and pya_score_batch_shared */
+static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *sh, const double *mz, const double *inten, uint32_t flags,
+                            const pya_results *out) {
+    const uint64_t n_spec = sh ? sh->n_spectra : b->n_psm;       /* b->peak_off has n_spec + 1 entries */
     h->last_status.clear();
     if (b->n_psm == 0) return PYA_OK;
     if (!mz || !inten) return h->fail(PYA_ERR_ARG, -1, "NULL spectrum arrays");
@@ -243,11 +255,11 @@ int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const d
         return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     if (!out->best_score || !out->best_sig || !out->n_sig || !out->ascores || !out->alt_mask)
         return h->fail(PYA_ERR_ARG, -1, "NULL array in results");
-    if (b->peak_off[b->n_psm] < b->peak_off[0]) return h->fail(PYA_ERR_ARG, -1, "peak_off is not monotone");
+    if (b->peak_off[n_spec] < b->peak_off[0]) return h->fail(PYA_ERR_ARG, -1, "peak_off is not monotone");
     /* (not while the records of a pya_score_one PSM are retained in the one-PSM workspace: this call would overwrite
      * what pya_get_pep_scores / pya_calculate_ambiguity still read there) */
     const bool one_view_live = h->kept && h->kept == h->one.view;
-    if (b->n_psm == 1 && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING)) && !one_view_live) {
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING)) && !one_view_live) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -266,27 +278,30 @@ int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const d
         /* Chunking: needed when the call does not fit the device budget, worthwhile (pipelining)
          * when there is enough PCIe traffic to hide the kernels under.  A retained batch
          * (PYA_FLAG_KEEP) stays one plan: its records are queried by PSM afterwards. */
-        const size_t io_total = (size_t)(b->peak_off[b->n_psm] - b->peak_off[0]) * 16;
+        const size_t io_total = (size_t)(b->peak_off[n_spec] - b->peak_off[0]) * 16;
         if (!(flags & PYA_FLAG_KEEP) && io_total >= kChunkMin && !h->kn.no_chunks) {
             const size_t budget = workspace_budget(h);
-            const ChunkCost cost = chunk_costs(h, b, out->max_k);
+            const ChunkCost cost = chunk_costs(h, b, sh, out->max_k);
             double io_target = (double)kChunkTarget;
             if (h->kn.chunk_mb > 0.) io_target = h->kn.chunk_mb * 1048576.0;
             std::vector<uint64_t> cuts{0};
             double io = 0, arena = 0;
             for (uint64_t i = 0; i < b->n_psm; i++) {
-                const double io2 = io + cost.io[i], ar2 = arena + cost.arena[i];
+                /* (shared spectra: a spectrum's bytes and its retained table count for the first of its PSMs in the chunk) */
+                const bool opens = !sh || i == 0 || sh->spec_of[i] != sh->spec_of[i - 1];
+                const double own = cost.arena[i] + (sh ? cost.ret[i] : 0.);
+                const double io2 = io + (opens ? cost.io[i] : 0.), ar2 = arena + (opens ? own : cost.arena[i]);
                 if (i > cuts.back() && (io2 > io_target || 2.0 * io2 + ar2 > (double)budget)) {
                     cuts.push_back(i);
                     io = cost.io[i];
-                    arena = cost.arena[i];
+                    arena = own;
                 } else {
                     io = io2;
                     arena = ar2;
                 }
             }
             cuts.push_back(b->n_psm);
-            if (cuts.size() > 2) return score_batch_chunked(h, b, mz, inten, flags, out, cuts, cost.sites.data());
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, mz, inten, flags, out, cuts, cost.sites.data());
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -302,7 +317,7 @@ int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const d
     IoReq io = {mz, inten, out->max_k, nullptr, nullptr, nullptr, nullptr};
     /* Big batches: the spectra (16 bytes per peak, PCIe-bound) go up on a helper thread while this
      * one runs the host pre-pass of the plan; small ones ride in the plan's single staged copy. */
-    const int64_t peaks_lo = b->peak_off[0], n_peaks = b->peak_off[b->n_psm] - peaks_lo;
+    const int64_t peaks_lo = b->peak_off[0], n_peaks = b->peak_off[n_spec] - peaks_lo;
     std::thread uploader;
     hipError_t up_err = hipSuccess;
     if (n_peaks > 0 && (size_t)n_peaks * 16 > kStageLimit && !h->kn.no_upload_thread) {
@@ -319,7 +334,7 @@ int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const d
                 up_err = hipMemcpy(io.d_inten_ext, inten + peaks_lo, (size_t)n_peaks * 8, hipMemcpyHostToDevice);
         });
     }
-    int rc = plan_create_impl(h, b, flags & ~PYA_FLAG_TIMING, &io, &p);
+    int rc = plan_create_impl(h, b, flags & ~PYA_FLAG_TIMING, &io, sh, &p);
     if (uploader.joinable()) uploader.join();
     if (rc) return rc;
     if (up_err != hipSuccess) {
@@ -365,4 +380,22 @@ int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const d
         h->kept = guard.release();
     }
     return PYA_OK;
+}
+
+int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const double *inten, uint32_t flags,
+                    const pya_results *out) {
+    if (!h || !b || !out) return PYA_ERR_ARG;
+    return score_batch_impl(h, b, nullptr, mz, inten, flags, out);
+}
+
+int pya_score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const double *mz,
+                           const double *inten, uint32_t flags, const pya_results *out) {
+    if (!h || !b || !out) return PYA_ERR_ARG;
+    h->last_status.clear();
+    if (b->n_psm == 0) return PYA_OK;
+    if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
+    const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
+    if (rc) return rc;
+    const SpecShare sh = {spec_of, n_spectra, 0u};
+    return score_batch_impl(h, b, &sh, mz, inten, flags, out);
 }

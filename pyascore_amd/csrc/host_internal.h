@@ -50,6 +50,8 @@ int pya_launch_bin(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uin
 int pya_launch_bin_select(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t scap, hipStream_t stream);
 size_t pya_bin_select_lds_bytes(uint32_t scap);
 int pya_launch_bin_exact(const BatchDev *b, uint32_t n_total, uint32_t cap, hipStream_t stream);
+int pya_launch_fan_out(const uint32_t *d_spec_of, const uint32_t *d_spec_ret_n, const int32_t *d_spec_status, uint32_t *d_ret_n,
+                       int32_t *d_status, uint32_t n_psm, hipStream_t stream);
 int pya_launch_score(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap, uint32_t prefix,
                      uint32_t with_nl, uint32_t compact, uint32_t node_cap, uint32_t node_cols, uint32_t node_words,
                      uint32_t res_cap, uint32_t nl_cap, hipStream_t stream);
@@ -481,6 +483,25 @@ struct pya_plan {
     DevBuf<PeakEntry> d_ret;             /* retained tables, 8-byte entries, every PSM's from an even offset */
     DevBuf<int64_t> d_ret_off;
     std::vector<int64_t> ret_off;        /* [n_psm + 1] */
+    /* Shared spectra (pya_plan_create_shared): PSM i is scored against spectrum spec_of[i], the PSMs of a spectrum are
+     * consecutive.  peak_off / d_peak_off then describe the n_spec spectra, every spectrum is binned ONCE into one retained
+     * table (sret_off; a spectrum no PSM uses has none), and the binning kernels see a spectrum-side view of the plan:
+     * ids, ret_off, ret_n and status by spectrum.  ret_off[i] and descriptor word 0 of PSM i carry its spectrum's offset;
+     * after the binning pya_fan_out_kernel gives every PSM its spectrum's ret_n and status, so that nothing behind the
+     * binning knows the difference.  Unshared plans: spec_of is empty, PSM i has spectrum i. */
+    bool shared = false;
+    uint64_t n_spec = 0;
+    std::vector<uint32_t> spec_of;       /* [n_psm] */
+    std::vector<int64_t> sret_off;       /* [n_spec + 1] */
+    DevBuf<uint32_t> d_spec_of;          /* [n_psm] as the fan-out reads it: ~0u = set aside by the host pre-pass, keeps its status */
+    DevBuf<int64_t> d_sret_off;
+    DevBuf<uint32_t> d_sret_n;
+    DevBuf<int32_t> d_sstatus;
+    uint64_t spec(uint64_t i) const { return spec_of.empty() ? i : spec_of[i]; }
+    int64_t n_peaks(uint64_t i) const {
+        const uint64_t s = spec(i);
+        return peak_off[s + 1] - peak_off[s];
+    }
     DevBuf<uint16_t> d_grid;
     DevBuf<uint32_t> d_redo3;            /* the same for localize's lean instantiation */
     DevBuf<uint32_t> d_redo;             /* [1 + n_psm]: count, then the ids bin_spectra hands to its exact variant */
@@ -672,7 +693,15 @@ struct IoReq {                       /* pya_score_batch: spectra and results liv
     hipStream_t stream;              /* metadata upload: on this stream, waited for alone (nullptr: device-wide) */
     const uint8_t *pre_sites;        /* letter scan already done by the caller: sites per PSM, 255 = invalid letters */
 };
-int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, pya_plan **out);
+/* which spectrum every PSM uses (pya_score_batch_shared / pya_plan_create_shared): spec_of[i] - base, one of the n_spectra
+ * that b->peak_off describes -- checked by check_spec_of before it gets here */
+struct SpecShare {
+    const uint32_t *spec_of;
+    uint64_t n_spectra;
+    uint32_t base;                   /* (a chunk of a bigger call: its first spectrum) */
+};
+int check_spec_of(pya_handle *h, uint64_t n_psm, const uint32_t *spec_of, uint64_t n_spectra);
+int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, const SpecShare *sh, pya_plan **out);
 int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid = false);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);

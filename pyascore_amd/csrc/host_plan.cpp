@@ -39,6 +39,7 @@ struct PlanBuild {
     pya_handle *h;
     const pya_batch *b;
     const IoReq *io;
+    const SpecShare *sh;                 /* shared spectra (pya_plan::shared), or nullptr */
     uint32_t flags;
     pya_plan *p;
     uint64_t n;
@@ -56,8 +57,8 @@ struct PlanBuild {
     std::vector<uint32_t> caps;          /* peak classes: caps, ascending ... */
     std::vector<uint8_t> pcls;           /* ... [n] and the class of every PSM binned by the fast kernels */
 
-    PlanBuild(pya_handle *h_, const pya_batch *b_, const IoReq *io_, uint32_t flags_, pya_plan *p_)
-        : h(h_), b(b_), io(io_), flags(flags_), p(p_), n(b_->n_psm) {
+    PlanBuild(pya_handle *h_, const pya_batch *b_, const IoReq *io_, const SpecShare *sh_, uint32_t flags_, pya_plan *p_)
+        : h(h_), b(b_), io(io_), sh(sh_), flags(flags_), p(p_), n(b_->n_psm) {
         const DevConfig &c = h->cfg;
         const Knobs &kn = h->kn;
         has_aux = b->aux_off && b->aux_pos && b->aux_mass;
@@ -88,12 +89,14 @@ struct Lap {
     }
 };
 
-/* the batch's arrays with offsets that start at 0; where every PSM's retained table goes */
+/* the batch's arrays with offsets that start at 0; where every PSM's retained table goes (shared spectra: every
+ * spectrum's, and which of them every PSM reads) */
 int copy_meta(PlanBuild &B) {
     pya_plan *p = B.p;
     const pya_batch *b = B.b;
     const uint64_t n = B.n;
-    p->peak_off.assign(b->peak_off, b->peak_off + n + 1);
+    const uint64_t ns = p->n_spec;                      /* spectra that peak_off describes: n unless they are shared */
+    p->peak_off.assign(b->peak_off, b->peak_off + ns + 1);
     p->pep_off.assign(b->pep_off, b->pep_off + n + 1);
     p->n_of_mod.assign(b->n_of_mod, b->n_of_mod + n);
     p->max_charge.assign(b->max_charge, b->max_charge + n);
@@ -102,23 +105,38 @@ int copy_meta(PlanBuild &B) {
     B.peak_base = n ? p->peak_off[0] : 0;
     B.pep_base = n ? p->pep_off[0] : 0;
     B.aux_base = n ? p->aux_off[0] : 0;
-    p->total_peaks = n ? p->peak_off[n] - B.peak_base : 0;
+    p->total_peaks = n ? p->peak_off[ns] - B.peak_base : 0;
     const int64_t total_pep = n ? p->pep_off[n] - B.pep_base : 0;
     B.total_aux = n ? p->aux_off[n] - B.aux_base : 0;
     if (p->total_peaks < 0 || total_pep < 0 || B.total_aux < 0)
         return B.h->fail(PYA_ERR_ARG, -1, "offset arrays are not monotone (the last offset is below the first)");
     p->pep.assign(b->pep + B.pep_base, b->pep + B.pep_base + total_pep);
+    for (uint64_t s = 0; s <= ns; s++) p->peak_off[s] -= B.peak_base;
     for (uint64_t i = 0; i <= n; i++) {
-        p->peak_off[i] -= B.peak_base;
         p->pep_off[i] -= B.pep_base;
         p->aux_off[i] -= B.aux_base;
     }
     p->ret_off.resize(n + 1);
-    int64_t at = 0;                                     /* every PSM's retained table starts at an even entry */
-    for (uint64_t i = 0; i < n; i++) {
-        p->ret_off[i] = at;
-        const int64_t P = p->peak_off[i + 1] - p->peak_off[i];
-        at += ((P > 0 ? P : 0) + 1) & ~(int64_t)1;
+    int64_t at = 0;                                     /* every retained table starts at an even entry */
+    if (!p->shared) {
+        for (uint64_t i = 0; i < n; i++) {
+            p->ret_off[i] = at;
+            const int64_t P = p->peak_off[i + 1] - p->peak_off[i];
+            at += ((P > 0 ? P : 0) + 1) & ~(int64_t)1;
+        }
+    } else {
+        /* one table per spectrum some PSM uses; a PSM's offset is its spectrum's */
+        p->spec_of.resize(n);
+        std::vector<uint8_t> used(ns, 0);
+        for (uint64_t i = 0; i < n; i++) used[p->spec_of[i] = B.sh->spec_of[i] - B.sh->base] = 1;
+        p->sret_off.resize(ns + 1);
+        for (uint64_t s = 0; s < ns; s++) {
+            p->sret_off[s] = at;
+            const int64_t P = p->peak_off[s + 1] - p->peak_off[s];
+            if (used[s]) at += ((P > 0 ? P : 0) + 1) & ~(int64_t)1;
+        }
+        p->sret_off[ns] = at;
+        for (uint64_t i = 0; i < n; i++) p->ret_off[i] = p->sret_off[p->spec_of[i]];
     }
     p->ret_off[n] = at;
     return PYA_OK;
@@ -135,7 +153,7 @@ void scan_letters(PlanBuild &B) {
     B.bad.assign(n, 0);
     auto scan = [&](uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; i++) {
-            const int64_t P = p->peak_off[i + 1] - p->peak_off[i];
+            const int64_t P = p->n_peaks(i);
             const int64_t L = p->pep_off[i + 1] - p->pep_off[i];
             const int32_t k = p->n_of_mod[i], z = p->max_charge[i];
             bool ok = P > 0 && P <= PYA_MAX_PEAKS && L >= 1 && L <= PYA_MAX_PEPTIDE_LEN && k >= 0 && z >= 1 && z <= PYA_MAX_CHARGE &&
@@ -204,7 +222,9 @@ inline void route_one(PlanBuild &B, uint64_t i, int64_t P, int64_t L, int32_t k,
         p->gen_l_cap = std::max<uint32_t>(p->gen_l_cap, (uint32_t)L);
         p->gen_list_cap = std::max<uint32_t>(p->gen_list_cap, per_type);
         if (P > PYA_FAST_PEAKS) {
-            p->bigbin_ids.push_back((uint32_t)i);
+            /* (the id of the spectrum: the PSM's own number unless spectra are shared, then once for its consecutive PSMs) */
+            const uint32_t s = (uint32_t)p->spec(i);
+            if (p->bigbin_ids.empty() || p->bigbin_ids.back() != s) p->bigbin_ids.push_back(s);
             p->bigbin_cap = std::max<uint32_t>(p->bigbin_cap, ((uint32_t)P + 31u) & ~31u);
         }
         return;
@@ -253,7 +273,7 @@ int route_psms(PlanBuild &B) {
     char msg[kPsmMsg];
     p->pre_status.assign(B.n, 0);
     for (uint64_t i = 0; i < B.n; i++) {
-        const int64_t P = p->peak_off[i + 1] - p->peak_off[i];
+        const int64_t P = p->n_peaks(i);
         const int64_t L = p->pep_off[i + 1] - p->pep_off[i];
         const int32_t k = p->n_of_mod[i], z = p->max_charge[i];
         uint32_t ns = p->n_sites[i], per_type = 0;
@@ -349,11 +369,11 @@ void peak_classes_and_lists(PlanBuild &B) {
         /* (the order statistics from a histogram of the counts -- they are at most PYA_FAST_PEAKS here --: one pass
          * instead of three std::nth_element over the batch) */
         std::vector<uint32_t> hist(PYA_FAST_PEAKS + 2, 0);
-        std::vector<uint8_t> global_bin(p->bigbin_ids.empty() ? 0 : n, 0);
+        std::vector<uint8_t> global_bin(p->bigbin_ids.empty() ? 0 : p->n_spec, 0);
         for (uint32_t id : p->bigbin_ids) global_bin[id] = 1;      /* (binned by their own kernel) */
         for (uint64_t i = 0; i < n; i++) {
-            uint32_t v = p->pre_status[i] ? 1u : (uint32_t)(p->peak_off[i + 1] - p->peak_off[i]);
-            if (!global_bin.empty() && global_bin[i]) v = 1u;
+            uint32_t v = p->pre_status[i] ? 1u : (uint32_t)p->n_peaks(i);
+            if (!global_bin.empty() && global_bin[p->spec(i)]) v = 1u;
             hist[v > PYA_FAST_PEAKS ? PYA_FAST_PEAKS + 1 : v]++;
         }
         for (double q : {0.5, 0.9, 0.99}) {
@@ -375,14 +395,18 @@ void peak_classes_and_lists(PlanBuild &B) {
     const size_t nc = caps.size();
     std::vector<uint32_t> cnt_bin(nc, 0), cnt_score(nc * kNumBuckets, 0), cnt_big(nc, 0);
     B.pcls.resize(n);
+    /* the binning lists hold spectra: PSM numbers unless spectra are shared, then a spectrum once for its consecutive PSMs
+     * (the first of them that is not set aside lists it) */
+    int64_t listed = -1;
     for (uint64_t i = 0; i < n; i++) {
         if (p->pre_status[i]) continue;                  /* set aside: neither binned nor scored */
-        const uint32_t P = (uint32_t)(p->peak_off[i + 1] - p->peak_off[i]);
+        const uint32_t P = (uint32_t)p->n_peaks(i);
         if (P > PYA_FAST_PEAKS) continue;               /* (pya_bin_global_kernel; scored by the general kernel) */
         size_t c = 0;
         while (caps[c] < P) c++;
         B.pcls[i] = (uint8_t)c;
-        cnt_bin[c]++;
+        if ((int64_t)p->spec(i) != listed) cnt_bin[c]++;
+        listed = (int64_t)p->spec(i);
         if (p->fused[i] || p->gen[i]) continue;
         if (p->big[i]) cnt_big[c]++;
         else cnt_score[p->ncls[i] * nc + c]++;
@@ -403,11 +427,13 @@ void peak_classes_and_lists(PlanBuild &B) {
     p->bin_ids.resize(n_bin);
     p->score_ids.resize(n_score);
     p->big_ids.resize(n_big);
+    listed = -1;
     for (uint64_t i = 0; i < n; i++) {
         if (p->pre_status[i]) continue;
-        if (p->peak_off[i + 1] - p->peak_off[i] > PYA_FAST_PEAKS) continue;
+        if (p->n_peaks(i) > PYA_FAST_PEAKS) continue;
         pya_plan::IdList &bl = p->bin_lists[B.pcls[i]];
-        p->bin_ids[bl.off + bl.n++] = (uint32_t)i;
+        if ((int64_t)p->spec(i) != listed) p->bin_ids[bl.off + bl.n++] = (uint32_t)p->spec(i);
+        listed = (int64_t)p->spec(i);
         if (p->fused[i] || p->gen[i]) continue;         /* (listed by fused_launches / in gen_ids) */
         pya_plan::IdList &sl = p->big[i] ? p->big_lists[B.pcls[i]] : p->score_lists[p->ncls[i] * nc + B.pcls[i]];
         (p->big[i] ? p->big_ids : p->score_ids)[sl.off + sl.n++] = (uint32_t)i;
@@ -580,7 +606,7 @@ int layout_and_upload(PlanBuild &B) {
     const size_t n = B.n, n_aux = (size_t)B.total_aux, n_sigs = (size_t)B.sig_total, n_peaks = (size_t)p->total_peaks;
     ArenaLayout A;
     A.add(p->d_ret_off, n + 1, p->ret_off.data());
-    A.add(p->d_peak_off, n + 1, p->peak_off.data());
+    A.add(p->d_peak_off, p->peak_off.size(), p->peak_off.data());
     A.add(p->d_pep_off, n + 1, p->pep_off.data());
     A.add(p->d_aux_off, n + 1, p->aux_off.data());
     A.add(p->d_sig_off, n + 1, p->sig_off.data());
@@ -602,6 +628,14 @@ int layout_and_upload(PlanBuild &B) {
     A.add(p->d_gen_off, p->gen_off.size(), p->gen_off.data());
     A.add(p->d_bigbin_ids, p->bigbin_ids.size(), p->bigbin_ids.data());
     for (Bucket &bk : p->buckets) A.add(bk.d_ids, bk.ids.size(), bk.ids.data());
+    std::vector<uint32_t> fan_spec;                   /* (uploaded before this function returns) */
+    if (p->shared) {
+        fan_spec = p->spec_of;
+        for (size_t i = 0; i < n; i++)
+            if (p->pre_status[i]) fan_spec[i] = 0xffffffffu;    /* set aside: the fan-out leaves its status alone */
+        A.add(p->d_spec_of, n, fan_spec.data());
+        A.add(p->d_sret_off, p->sret_off.size(), p->sret_off.data());
+    }
     if (io && !io->d_mz_ext) {                        /* pya_score_batch: the spectra ride in the same copy ... */
         A.add(p->d_mz, n_peaks, io->mz + B.peak_base);
         A.add(p->d_inten, n_peaks, io->inten + B.peak_base);
@@ -621,6 +655,10 @@ int layout_and_upload(PlanBuild &B) {
     }
     p->d2h_bytes = A.total - p->o_status;
     A.add(p->d_ret_n, n);
+    if (p->shared) {
+        A.add(p->d_sret_n, (size_t)p->n_spec);
+        A.add(p->d_sstatus, (size_t)p->n_spec);
+    }
     A.add(p->d_ret, (size_t)p->ret_off[n] + 8);      /* (eight entries of slack behind the last table) */
     A.add(p->d_grid, n * PYA_GRID_CELLS);
     A.add(p->d_redo, kRedoHead + n);
@@ -731,7 +769,25 @@ void fill_dev(pya_plan *p) {
 
 }  // namespace
 
-int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, pya_plan **out) {
+int check_spec_of(pya_handle *h, uint64_t n_psm, const uint32_t *spec_of, uint64_t n_spectra) {
+    h->err.clear();
+    h->err_index = -1;
+    if (n_psm == 0) return PYA_OK;
+    if (!spec_of) return h->fail(PYA_ERR_ARG, -1, "NULL spec_of");
+    if (n_spectra == 0) return h->fail(PYA_ERR_ARG, 0, "PSM 0: the batch has PSMs and no spectra (n_spectra is 0)");
+    if (n_spectra >= 0xffffffffull) return h->fail(PYA_ERR_LIMIT, -1, "more than 2^32 - 2 spectra in one batch");
+    for (uint64_t i = 0; i < n_psm; i++) {
+        if (spec_of[i] >= n_spectra)
+            return h->fail(PYA_ERR_ARG, (int64_t)i, "PSM %llu: spec_of is %u, the batch has %llu spectra", (unsigned long long)i, spec_of[i],
+                           (unsigned long long)n_spectra);
+        if (i && spec_of[i] < spec_of[i - 1])
+            return h->fail(PYA_ERR_ARG, (int64_t)i, "PSM %llu: spec_of decreases (%u after %u); the PSMs of a spectrum must be consecutive",
+                           (unsigned long long)i, spec_of[i], spec_of[i - 1]);
+    }
+    return PYA_OK;
+}
+
+int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, const SpecShare *sh, pya_plan **out) {
     if (!h || !b || !out) return PYA_ERR_ARG;
     *out = nullptr;
     h->err.clear();
@@ -751,7 +807,9 @@ int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const Io
     p->bigloc.take_knobs(h->kn);
     p->flags = flags;
     p->n_psm = n;
-    PlanBuild B(h, b, io, flags, p.get());
+    p->shared = sh != nullptr && n != 0;
+    p->n_spec = p->shared ? sh->n_spectra : n;
+    PlanBuild B(h, b, io, sh, flags, p.get());
     if ((rc = copy_meta(B))) return rc;
     lap("copy meta");
     p->n_sites.resize(n);
@@ -789,7 +847,17 @@ int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const Io
 }
 
 int pya_plan_create(pya_handle *h, const pya_batch *b, uint32_t flags, pya_plan **out) {
-    return plan_create_impl(h, b, flags, nullptr, out);
+    return plan_create_impl(h, b, flags, nullptr, nullptr, out);
+}
+
+int pya_plan_create_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, uint32_t flags,
+                           pya_plan **out) {
+    if (!h || !b || !out) return PYA_ERR_ARG;
+    *out = nullptr;
+    const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
+    if (rc) return rc;
+    const SpecShare sh = {spec_of, n_spectra, 0u};
+    return plan_create_impl(h, b, flags, nullptr, &sh, out);
 }
 
 uint64_t pya_plan_workspace_bytes(const pya_plan *p) { return p ? p->workspace_bytes() : 0; }

@@ -71,7 +71,9 @@ struct RunMarks {
 int run_tiny(pya_plan *p, const BatchDev &d, hipStream_t st, bool *done) {
     pya_handle *h = p->h;
     *done = false;
-    if ((p->flags & PYA_FLAG_TIMING) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty())
+    /* (the tiny kernel bins per PSM from the PSM's own peaks: a shared batch, however small, takes the plan's launches) */
+    if ((p->flags & PYA_FLAG_TIMING) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+        p->shared)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
      * caps count too -- leaving them out sized this launch's work areas for the other PSMs only) */
@@ -110,6 +112,21 @@ int run_binning(pya_plan *p, const BatchDev &d, hipStream_t st) {
     if (e) return h->hip_fail((hipError_t)e, "bin_spectra (exact) launch");
     e = pya_launch_bin_global(&d, p->d_bigbin_ids.p, (uint32_t)p->bigbin_ids.size(), p->d_bigbin_scratch.p, p->bigbin_stride, p->bigbin_cap, st);
     if (e) return h->hip_fail((hipError_t)e, "bin_spectra (global) launch");
+    return PYA_OK;
+}
+
+/* Shared spectra: the binning family over SPECTRUM ids with the spectrum-side view of the plan (peak_off is the spectra's
+ * already; ret_off, ret_n and status by spectrum), then the fan-out that gives every PSM its spectrum's ret_n and status --
+ * behind it every kernel reads by PSM number, as in an unshared plan. */
+int run_binning_shared(pya_plan *p, const BatchDev &d, hipStream_t st) {
+    BatchDev sd = d;
+    sd.ret_off = p->d_sret_off.p;
+    sd.ret_n = p->d_sret_n.p;
+    sd.status = p->d_sstatus.p;
+    const int rc = run_binning(p, sd, st);
+    if (rc) return rc;
+    const int e = pya_launch_fan_out(p->d_spec_of.p, p->d_sret_n.p, p->d_sstatus.p, d.ret_n, d.status, (uint32_t)p->n_psm, st);
+    if (e) return p->h->hip_fail((hipError_t)e, "fan-out launch");
     return PYA_OK;
 }
 
@@ -288,7 +305,7 @@ int pya_plan_run(pya_plan *p, const double *d_mz, const double *d_inten, void *h
         d.zero_next = p->d_redo.p + 8 * ((p->n_runs + 1u) & 1u);
         if (p->n_runs == 0 || !pya_plan::any_ids(p->bin_lists)) HIPCHK(h, hipMemsetAsync(p->d_redo.p, 0, 16 * sizeof(uint32_t), st));
         p->n_runs++;
-        if ((rc = run_binning(p, d, st))) return rc;
+        if ((rc = p->shared ? run_binning_shared(p, d, st) : run_binning(p, d, st))) return rc;
         if ((rc = mark(1, true))) return rc;
         if (!p->fork) {
             if ((rc = run_behind_binning(p, d, st, mark))) return rc;

@@ -16,7 +16,8 @@ class DevicePlan:
     """One batch planned once (host pre-pass, tables, workspace), runnable many times.
 
     ``spectra`` are two float64 CUDA/HIP tensors (m/z, intensity) laid out as the batch's
-    ``peak_off`` says.  ``run()`` enqueues the three kernels on torch's current stream and
+    ``peak_off`` says (a batch with ``spec_of``: the spectra's, each held once and shared by its PSMs,
+    which must be consecutive).  ``run()`` enqueues the three kernels on torch's current stream and
     returns the result tensors (device).  ``max_k`` widens the per-site result rows beyond this
     batch's own largest n_of_mod: ranks that gather fixed-size records pass the job-wide value."""
 
@@ -48,8 +49,16 @@ class DevicePlan:
                        _as_ptr(m["n_of_mod"]), _as_ptr(m["max_charge"]), _as_ptr(m["aux_pos"]),
                        _as_ptr(m["aux_mass"]), _as_ptr(m["aux_off"]))
         self._plan = C.c_void_p()
-        rc = self._lib.pya_plan_create(scorer._h, C.byref(b), _lib.PYA_FLAG_TIMING if timing else 0,
-                                       C.byref(self._plan))
+        flags = _lib.PYA_FLAG_TIMING if timing else 0
+        if batch.get("spec_of") is not None:
+            # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
+            spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
+            n_spec = int(batch.get("n_spectra", m["peak_off"].size - 1))
+            if spec_of.size != self.n_psm or m["peak_off"].size != n_spec + 1:
+                raise ValueError("a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
+            rc = self._lib.pya_plan_create_shared(scorer._h, C.byref(b), _as_ptr(spec_of), n_spec, flags, C.byref(self._plan))
+        else:
+            rc = self._lib.pya_plan_create(scorer._h, C.byref(b), flags, C.byref(self._plan))
         if rc:
             self._plan = None
             scorer._raise(rc)

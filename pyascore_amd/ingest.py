@@ -633,9 +633,10 @@ def to_batch(psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_ch
              mod_correction_tol=1.0):
     """Parsed identifications + spectra -> (CSR batch for ``PyAscore.score_batch``, the scan of each of
     its PSMs), with the reference CLI's per-PSM decisions (`__main__.py:127-164`: hit depth, variable /
-    fixed split, charge heuristic).  PSMs without an unlocalised modification are left out, as there."""
-    from .batch_cli import select_psms
-    from .synth import pack_batch
+    fixed split, charge heuristic).  PSMs without an unlocalised modification are left out, as there.
+    With ``hit_depth`` beyond 1 the hits of a scan share ONE copy of the scan's spectrum: the batch then carries
+    ``spec_of`` / ``n_spectra`` and ``peak_off`` describes the spectra (``batch_cli.pack_hits``)."""
+    from .batch_cli import pack_hits, select_psms
     picked, scans = select_psms(sorted(psms, key=lambda p: p["scan"]), spectra_map, residues, mod_mass, hit_depth,
                                 max_fragment_charge, mod_correction_tol)
-    return (pack_batch(picked) if picked else None), scans
+    return (pack_hits(picked, scans) if picked else None), scans

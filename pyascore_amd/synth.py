@@ -311,6 +311,73 @@ def pack_batch(psms):
     )
 
 
+def pack_shared_batch(spectra, psms):
+    """Several PSMs per spectrum (the hits of one scan, `pyascore/__main__.py`'s hit_depth loop): ``spectra`` is a list of
+    dicts {mz, intensity}, ``psms`` a list of dicts {spectrum, peptide, n_of_mod, max_charge, aux_pos, aux_mass} whose
+    ``spectrum`` is an index into ``spectra``.  Returns the CSR dict of ``pack_batch`` with every spectrum in ``mz`` /
+    ``intensity`` ONCE (``peak_off`` has len(spectra) + 1 entries) plus ``spec_of`` (uint32 per PSM) and ``n_spectra``:
+    what ``PyAscore.score_batch`` and ``device.DevicePlan`` send through the shared entry points of the library."""
+    spec_of = np.asarray([int(p["spectrum"]) for p in psms], np.int64)
+    if spec_of.size and (spec_of.min() < 0 or spec_of.max() >= len(spectra)):
+        raise ValueError("a PSM's spectrum index is outside the list of spectra")
+    empty = dict(mz=(), intensity=())
+    out = pack_batch([dict(p, **empty) for p in psms])
+    side = pack_batch([dict(mz=sp["mz"], intensity=sp["intensity"], peptide="", n_of_mod=0) for sp in spectra])
+    out.update(mz=side["mz"], intensity=side["intensity"], peak_off=side["peak_off"],
+               spec_of=spec_of.astype(np.uint32), n_spectra=len(spectra))
+    return out
+
+
+def expand_shared_batch(batch):
+    """The repeated-spectrum batch of a shared one (``pack_shared_batch``): PSM i gets a private copy of spectrum
+    spec_of[i], in PSM order -- what the library scored before spectra could be shared, and the yardstick of the shared
+    path (results are bit-equal)."""
+    po = np.asarray(batch["peak_off"], np.int64)
+    so = np.asarray(batch["spec_of"], np.int64)
+    cnt = (po[1:] - po[:-1])[so]
+    off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+    idx = np.repeat(po[so] - off[:-1], cnt) + np.arange(off[-1], dtype=np.int64)
+    out = {k: v for k, v in batch.items() if k not in ("spec_of", "n_spectra")}
+    out.update(mz=np.ascontiguousarray(np.asarray(batch["mz"], np.float64)[idx]),
+               intensity=np.ascontiguousarray(np.asarray(batch["intensity"], np.float64)[idx]), peak_off=off)
+    return out
+
+
+def spectrum_order(spec_of):
+    """The library wants the PSMs of a spectrum consecutive (``spec_of`` non-decreasing).  Returns (perm, inv): the stable
+    order by spectrum -- row j of the sorted batch is PSM perm[j] -- and its inverse, sorted_rows[inv] = input order; or
+    (None, None) when ``spec_of`` is in order already."""
+    so = np.asarray(spec_of, np.int64)
+    if so.size < 2 or not np.any(so[1:] < so[:-1]):
+        return None, None
+    perm = np.argsort(so, kind="stable")
+    inv = np.empty_like(perm)
+    inv[perm] = np.arange(perm.size)
+    return perm, inv
+
+
+def take_psms(batch, perm):
+    """The PSMs ``perm`` of a shared batch, in that order (peptides, fixed modifications, ``spec_of``); the spectra stay
+    where they are."""
+    perm = np.asarray(perm, np.int64)
+
+    def gather(values, offsets):
+        o = np.asarray(offsets, np.int64)
+        cnt = (o[1:] - o[:-1])[perm]
+        new = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        idx = np.repeat(o[perm] - new[:-1], cnt) + np.arange(new[-1], dtype=np.int64)
+        return np.ascontiguousarray(np.asarray(values)[idx]), new
+
+    out = dict(batch)
+    out["pep"], out["pep_off"] = gather(batch["pep"], batch["pep_off"])
+    out["aux_pos"], out["aux_off"] = gather(batch["aux_pos"], batch["aux_off"])
+    out["aux_mass"], _ = gather(batch["aux_mass"], batch["aux_off"])
+    for k in ("n_of_mod", "max_charge", "spec_of"):
+        out[k] = np.ascontiguousarray(np.asarray(batch[k])[perm])
+    out["n_psm"] = int(perm.size)
+    return out
+
+
 def unpack_psm(batch, i):
     """PSM ``i`` of a CSR batch as the keyword arguments of ``PyAscore.score``."""
     a, b = batch["peak_off"][i], batch["peak_off"][i + 1]
