@@ -38,6 +38,11 @@ int pya_set_debug(pya_handle *h, const char *key, const char *value);
  * No reference counterpart. */
 int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]);
 
+/* Plans the last pya_score_batch / pya_score_batch_shared / pya_score_batch_typed call on the handle was cut into (1: one
+ * plan, not pipelined; 0: no call yet).  The tests read from it that a budget cuts a float32 batch into no more chunks than
+ * the same batch widened.  No reference counterpart. */
+uint64_t pya_debug_last_chunks(const pya_handle *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,33 @@ int pya_score_batch(pya_handle *h, const pya_batch *batch, const double *mz,
 int pya_score_batch_shared(pya_handle *h, const pya_batch *batch, const uint32_t *spec_of, uint64_t n_spectra,
                            const double *mz, const double *intensity, uint32_t flags, const pya_results *out);
 
+/* Typed spectra (no reference counterpart -- the reference's one entry point, PyAscore.score, takes two float64 buffers
+ * and raises on anything else, Ascore.pyx:103; pya_score_one / PyAscore.score keep that contract).  The batch entry points
+ * take the arrays in the precision their source holds them in: mzML as msconvert writes it has 64-bit m/z and 32-bit
+ * intensities, mzXML 32-bit pairs, and widening them on the host only adds bytes to the PCIe copy that bounds
+ * pya_score_batch.  float32 -> float64 is exact and the binning kernels widen every value where they load it, so the
+ * results are bit-equal to those of the same arrays widened by the caller and sent through pya_score_batch /
+ * pya_score_batch_shared / pya_plan_run; no widened copy is made on the host or on the device.
+ *   (mz_type, intensity_type) = (PYA_F64, PYA_F64): 16 bytes per peak, behaves as the float64 entry points (which are
+ *                                                   thin wrappers of these two);
+ *                               (PYA_F64, PYA_F32): 12 bytes per peak;
+ *                               (PYA_F32, PYA_F32):  8 bytes per peak;
+ *                               (PYA_F32, PYA_F64): REFUSED with PYA_ERR_ARG and a message (no file format stores it);
+ *   any other type value: PYA_ERR_ARG.
+ * (The struct is not called pya_spectra: that is pyascore_aux.h's PyBinnedSpectra counterpart.) */
+#define PYA_F64 0u
+#define PYA_F32 1u
+typedef struct pya_typed_spectra {  /* host pointers for pya_score_batch_typed, device pointers for pya_plan_run_typed */
+    const void *mz, *intensity;
+    uint32_t mz_type, intensity_type;   /* PYA_F64 / PYA_F32 */
+} pya_typed_spectra;
+/* pya_score_batch (spec_of == NULL; n_spectra is ignored) or pya_score_batch_shared (spec_of != NULL) for typed arrays:
+ * same validation, messages, per-PSM status codes, flags and retained records (PYA_FLAG_KEEP).  Upload ring, chunk cuts
+ * (PYA_CHUNK_MB, the workspace budget) and the spectra in the plan's arena count the arrays' real bytes.  A batch of one PSM
+ * takes pya_score_one's low-latency kernel only when both arrays are float64. */
+int pya_score_batch_typed(pya_handle *h, const pya_batch *batch, const uint32_t *spec_of, uint64_t n_spectra,
+                          const pya_typed_spectra *spectra, uint32_t flags, const pya_results *out);
+
 /* Device memory one pya_score_batch call may hold at a time (upload ring + workspace; default 6 GiB,
  * or PYA_WORKSPACE_MB).  Calls that need more -- and every call with more than 32 MB of spectra -- are
  * cut into chunks of consecutive PSMs and pipelined: the upload of chunk c + 1 runs under the kernels
@@ -201,6 +228,12 @@ int pya_plan_create_shared(pya_handle *h, const pya_batch *batch, const uint32_t
                            uint32_t flags, pya_plan **out);
 int pya_plan_run(pya_plan *plan, const double *d_mz, const double *d_intensity,
                  void *hip_stream, const pya_results *d_out);
+/* pya_plan_run with typed device arrays (pya_typed_spectra above: the same combinations, the same refusals).  A plan is not
+ * tied to a type: pya_plan_create / pya_plan_create_shared know nothing of it, one plan may be run with float64 arrays and
+ * then with float32 ones, and the type selects the binning kernels' instantiation at launch time.  The arrays need the
+ * alignment of their element type only.  A typed run of a handful of PSMs takes the plan's launches (the one-launch kernel
+ * for tiny batches reads float64).  No reference counterpart. */
+int pya_plan_run_typed(pya_plan *plan, const pya_typed_spectra *d_spectra, void *hip_stream, const pya_results *d_out);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

@@ -84,7 +84,9 @@ def run(args, log=print):
     stamp = lambda: datetime.now().strftime("%m/%d/%y %H:%M:%S")
     log("{} -- Ascore Started".format(stamp()))
     log("{} -- Reading spectra from: {}".format(stamp(), args.spec_file))
-    spectra = ingest.SpectraParser(args.spec_file, args.spec_file_type).to_dict()
+    # (the arrays in the precision the file holds them: float32 ones go to the device as they are, results are those of
+    # the widened arrays bit for bit)
+    spectra = ingest.SpectraParser(args.spec_file, args.spec_file_type, native_precision=True).to_dict()
     log("{} -- Reading identifications from: {}".format(stamp(), args.ident_file))
     static = static_mods_of(args)
     known = dict(ingest.COMMON_MODS)                       # `__main__.py:30-35`

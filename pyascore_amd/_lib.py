@@ -34,6 +34,23 @@ class Results(C.Structure):
                 ("ascores", _vp), ("alt_mask", _vp)]
 
 
+class TypedSpectra(C.Structure):
+    """pya_typed_spectra: host (pya_score_batch_typed) or device (pya_plan_run_typed) arrays and their element types"""
+    _fields_ = [("mz", _vp), ("intensity", _vp), ("mz_type", C.c_uint32), ("intensity_type", C.c_uint32)]
+
+
+PYA_F64, PYA_F32 = 0, 1
+
+
+def spectrum_type(dtype):
+    """PYA_F64 / PYA_F32 for a numpy dtype (or its name: 'float64', 'float32'); anything else is no spectrum type."""
+    name = getattr(dtype, "name", None) or str(dtype).replace("torch.", "")
+    try:
+        return {"float64": PYA_F64, "float32": PYA_F32}[name]
+    except KeyError:
+        raise ValueError("spectrum arrays are float64 or float32, not %s" % name) from None
+
+
 # every symbol include/pyascore_hip.h declares
 SYMBOLS = {
     "pya_create": (C.c_int, [C.POINTER(Config), C.POINTER(_vp)]),
@@ -42,6 +59,7 @@ SYMBOLS = {
     "pya_reload_env": (C.c_int, [_vp]),
     "pya_set_debug": (C.c_int, [_vp, C.c_char_p, C.c_char_p]),          # include/pyascore_debug.h (test-only)
     "pya_debug_wave_ops": (C.c_int, [_vp, _vp, _vp]),         # (test-only)
+    "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
     "pya_score_one": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int32, C.c_int32, _vp, _vp, C.c_uint64,
                                 C.c_uint32, C.POINTER(Results)]),
     "pya_rescore_last_keep": (C.c_int, [_vp]),
@@ -49,6 +67,8 @@ SYMBOLS = {
     "pya_error_index": (C.c_int64, [_vp]),
     "pya_score_batch": (C.c_int, [_vp, C.POINTER(Batch), _vp, _vp, C.c_uint32, C.POINTER(Results)]),
     "pya_score_batch_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, _vp, _vp, C.c_uint32, C.POINTER(Results)]),
+    "pya_score_batch_typed": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.POINTER(TypedSpectra), C.c_uint32, C.POINTER(Results)]),
+    "pya_plan_run_typed": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.POINTER(Results)]),
     "pya_set_workspace_budget": (C.c_int, [_vp, C.c_uint64]),
     "pya_get_workspace_budget": (C.c_uint64, [_vp]),
     "pya_last_batch_status": (C.c_int, [_vp, _vp, C.c_uint64]),

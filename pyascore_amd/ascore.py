@@ -19,6 +19,16 @@ def _as_ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _typed_spectra(mz, intensity):
+    """The spectrum arrays of a batch as the library takes them: contiguous, float32 arrays as they are (no widening
+    copy), everything else float64 -- and float64 for both when only the m/z are float32 (a combination the library
+    refuses)."""
+    mz, intensity = np.asarray(mz), np.asarray(intensity)
+    it_t = np.float32 if intensity.dtype == np.float32 else np.float64
+    mz_t = np.float32 if mz.dtype == np.float32 and it_t == np.float32 else np.float64
+    return np.ascontiguousarray(mz, mz_t), np.ascontiguousarray(intensity, it_t)
+
+
 def _renumber_psm(message, perm):
     """'PSM <j>: ...' of a batch that was scored in the order ``perm`` -> the caller's number of that PSM."""
     import re
@@ -180,9 +190,9 @@ class PyAscore:
             self._raise(rc)
         self._budget = int(n_bytes)
 
-    def _retained_bytes(self, arrs):
-        """Device bytes a retained (keep=True) plan of this batch holds, per PSM: 16 per raw peak (spectra) + 8 per
-        peak (retained table) + per site assignment the score, the order and the count record (4 + 4 + 4 x its words:
+    def _retained_bytes(self, arrs, peak_bytes=16):
+        """Device bytes a retained (keep=True) plan of this batch holds, per PSM: ``peak_bytes`` per raw peak (spectra:
+        16 for float64 arrays, 12 or 8 for typed ones) + 8 per peak (retained table) + per site assignment the score, the order and the count record (4 + 4 + 4 x its words:
         32 bytes for n_top = 10, 44 for 16; with n_top > 10 also the general kernel's sort area, 8 more) + grid,
         descriptor, results."""
         from .shard import comb_table, count_sites
@@ -192,7 +202,7 @@ class PyAscore:
         peaks = np.diff(arrs["peak_off"]).astype(np.float64)
         rec_words = (self._n_top + 1) // 2 + 1
         per_sig = 8.0 + 4.0 * rec_words + (8.5 if self._n_top != 10 else 0.0)
-        return 24.0 * peaks + per_sig * sigs + 1024.0
+        return (8.0 + peak_bytes) * peaks + per_sig * sigs + 1024.0
 
     def score(self, mz_arr, int_arr, peptide, n_of_mod, max_fragment_charge=1, aux_mod_pos=None,
               aux_mod_mass=None):
@@ -311,7 +321,13 @@ class PyAscore:
         are those of the repeated-spectrum batch (``synth.expand_shared_batch``), bit for bit.  The library wants the PSMs
         of a spectrum consecutive: a batch in any other order is sorted stably by spectrum, scored, and its rows are put
         back, so the caller always sees input order (with ``keep=True`` such a batch is scored in its expanded form
-        instead: the retained records are addressed by PSM number)."""
+        instead: the retained records are addressed by PSM number).
+
+        Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
+        m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
+        ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
+        of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
+        float64 intensities."""
         if batch.get("spec_of") is not None:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
@@ -330,8 +346,7 @@ class PyAscore:
         # replaying what score() staged in the library: before another call reuses that staging, produce them
         self._ensure_kept()
         n = int(batch["n_psm"])
-        mz = np.ascontiguousarray(batch["mz"], np.float64)
-        it = np.ascontiguousarray(batch["intensity"], np.float64)
+        mz, it = _typed_spectra(batch["mz"], batch["intensity"])
         arrs = dict(
             peak_off=np.ascontiguousarray(batch["peak_off"], np.int64),
             pep=np.ascontiguousarray(batch["pep"], np.uint8),
@@ -374,16 +389,12 @@ class PyAscore:
                 # (a shared batch: priced, and re-scored by batch_pep_scores(), in its expanded form)
                 lazy_arrs = arrs if spec_of is None else dict(arrs, peak_off=np.concatenate(
                     [[0], np.cumsum(np.diff(arrs["peak_off"])[spec_of])]).astype(np.int64))
-                per_psm = self._retained_bytes(dict(lazy_arrs, n_of_mod=arrs["n_of_mod"]))
+                per_psm = self._retained_bytes(dict(lazy_arrs, n_of_mod=arrs["n_of_mod"]), mz.itemsize + it.itemsize)
                 lazy_keep = float(per_psm.sum()) > 0.8 * budget
             except (IndexError, ValueError):
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0)
-        if spec_of is None:
-            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), flags, C.byref(r))
-        else:
-            rc = self._lib.pya_score_batch_shared(self._h, C.byref(b), _as_ptr(spec_of), n_spec, _as_ptr(mz), _as_ptr(it), flags,
-                                                  C.byref(r))
+        rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r)
         if rc:
             self._raise(rc)
         self._batch_n = n if keep else None
@@ -404,6 +415,16 @@ class PyAscore:
             out["status_message"] = (self._lib.pya_last_error(self._h).decode("utf8", "replace")
                                      if out["status"].any() else "")
         return out
+
+    def _score_batch_call(self, b, spec_of, n_spec, mz, it, flags, r):
+        """float64 arrays through the entry points the reference's interface stands beside, float32 ones through the typed."""
+        if mz.dtype == np.float32 or it.dtype == np.float32:
+            sp = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(it), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(it.dtype))
+            return self._lib.pya_score_batch_typed(self._h, C.byref(b), _as_ptr(spec_of), n_spec, C.byref(sp), flags, C.byref(r))
+        if spec_of is None:
+            return self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), flags, C.byref(r))
+        return self._lib.pya_score_batch_shared(self._h, C.byref(b), _as_ptr(spec_of), n_spec, _as_ptr(mz), _as_ptr(it), flags,
+                                                C.byref(r))
 
     def format_batch(self, batch, sig_bits, valid=None, rec_psm=None):
         """Modified-sequence strings (``best_sequence`` / the ``sequence`` of ``pep_scores`` records) for
@@ -551,10 +572,9 @@ class PyAscore:
                            _as_ptr(arrs["aux_mass"]), _as_ptr(arrs["aux_off"]))
             r = _lib.Results(mk, _as_ptr(tmp["best_score"]), _as_ptr(tmp["best_sig"]), _as_ptr(tmp["n_sig"]),
                              _as_ptr(tmp["ascores"]), _as_ptr(tmp["alt_mask"]))
-            mz = np.ascontiguousarray(sub["mz"])
+            mz = np.ascontiguousarray(sub["mz"])              # (as the batch was scored: float64 or typed)
             it = np.ascontiguousarray(sub["intensity"])
-            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it),
-                                           _lib.PYA_FLAG_KEEP | _lib.PYA_FLAG_SKIP_INVALID, C.byref(r))
+            rc = self._score_batch_call(b, None, m, mz, it, _lib.PYA_FLAG_KEEP | _lib.PYA_FLAG_SKIP_INVALID, r)
             if rc:
                 self._raise(rc)
             parts.append(self._range_pep_scores(0, m))

@@ -99,7 +99,8 @@ def select_psms(psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment
 def pack_hits(picked, scans):
     """``select_psms``' output as one batch in which the hits of a scan share the scan's spectrum: consecutive PSMs of
     one scan (the reference scores every one of them against ``spectra_map[scan]``, `__main__.py:129-164`) refer to ONE
-    copy of its peaks.  With one hit per scan this is ``pack_batch(picked)``, array for array."""
+    copy of its peaks.  With one hit per scan this is ``pack_batch(picked)``, array for array.  Spectra read with
+    ``ingest.SpectraParser(native_precision=True)`` keep their float32 arrays through the pack (typed batch)."""
     spectra, spec_of = [], []
     for i, psm in enumerate(picked):
         if not (i and scans[i] == scans[i - 1] and psm["mz"] is picked[i - 1]["mz"] and psm["intensity"] is picked[i - 1]["intensity"]):

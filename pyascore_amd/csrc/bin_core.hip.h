@@ -239,6 +239,13 @@ DEV double lane_next_f64_or_zero(double x) {
  * PRE: the caller has the first block of the spectrum in registers already (the one-PSM kernel issues these loads
  * before anything else: its spectrum sits in host memory, a round trip of microseconds) and knows the peak count;
  * the spectrum starts at offset 0 of b.mz / b.inten then. */
+/* TYPED SPECTRA: the raw arrays are float64 or float32 (MZ / IT: pya_plan_run_typed picks the instantiation).  A value is
+ * widened in a register where it is loaded -- an exact conversion -- and everything behind the load is the float64 code:
+ * window ids, keys, ranks, tie order and the (float) m/z of the table are those of the widened arrays. */
+/* the high word of the float64 that intensity i is (or widens to) */
+DEV uint32_t inten_hw(const double *inten, uint32_t i) { return ((const uint32_t *)inten + 1)[2 * i]; }
+DEV uint32_t inten_hw(const float *inten, uint32_t i) { return (uint32_t)((uint64_t)__double_as_longlong((double)inten[i]) >> 32); }
+
 struct BinPre {
     uint32_t P;                 /* peaks */
     double v[BIN_BLOCK];        /* m/z of peak u * 64 + lane (past the end: the last peak's) */
@@ -246,20 +253,20 @@ struct BinPre {
     double mx;                  /* m/z of the last peak */
 };
 /* the loads behind a BinPre (all issued, none waited for) */
-DEV void bin_preload(const double *mz, const double *inten, uint32_t P, BinPre *pre) {
-    const uint32_t *inten_hi = (const uint32_t *)inten + 1;
+template <typename MZ, typename IT>
+DEV void bin_preload(const MZ *mz, const IT *inten, uint32_t P, BinPre *pre) {
     pre->P = P;
 #pragma unroll
     for (uint32_t u = 0; u < BIN_BLOCK; u++) {
         const uint32_t i = u * 64 + (uint32_t)lane_id();
         const uint32_t ic = i < P ? i : P - 1;
         pre->v[u] = mz[ic];
-        pre->hw[u] = inten_hi[2 * ic];
+        pre->hw[u] = inten_hw(inten, ic);
     }
     pre->mx = mz[P - 1];
 }
 
-template <bool DIRECT, bool PRE = false>
+template <bool DIRECT, bool PRE = false, typename MZ = double, typename IT = double>
 DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t cap, const float **out_mz,
                  const uint8_t **out_rank, int *status, const BinPre *pre = nullptr) {
     const int lane = lane_id();
@@ -273,8 +280,8 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
     STAMP_T(b, 1, -1);
     const int64_t p0 = PRE ? 0 : b.peak_off[psm];
     const uint32_t P = PRE ? pre->P : (uint32_t)(b.peak_off[psm + 1] - p0);
-    const double *mz = b.mz + p0;
-    const double *inten = b.inten + p0;
+    const MZ *mz = (const MZ *)b.mz + p0;
+    const IT *inten = (const IT *)b.inten + p0;
     const float bin_size = b.cfg->bin_size;
     const int ntop = b.cfg->n_top;                           /* peaks retained per window */
     /* (an estimate of the reciprocal is enough: the quotients below are corrected with an exact remainder) */
@@ -326,12 +333,11 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
     constexpr uint32_t KMAX = (1u << PYA_BIN_KEY_BITS) - 1u;
     w_first[lane] = 0xffffu;                                  /* (no peak) */
     /* only the high word of an intensity is needed here (the keys; sign, infinity and NaN show in it too) */
-    const uint32_t *inten_hi = (const uint32_t *)inten + 1;
     uint32_t maxhw = 0;
     int bad = 0;
     /* (a spectrum of more than one block: the later blocks' intensities once more, for the key base) */
     for (uint32_t i = 64 * U + (uint32_t)lane; i < P; i += 64) {
-        const uint32_t hw = inten_hi[2 * i];
+        const uint32_t hw = inten_hw(inten, i);
         bad |= hw >= 0x7ff00000u ? 1 : 0;
         maxhw = hw > maxhw ? hw : maxhw;
     }
@@ -356,7 +362,7 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
                 hw[u] = pre->hw[u];
             } else {
                 v[u] = mz[ic];
-                hw[u] = inten_hi[2 * ic];
+                hw[u] = inten_hw(inten, ic);
             }
         }
         if (base == 0) {
@@ -547,7 +553,7 @@ DEV void bin_sync() {
 /* The general body (see above): any peak order, any number of windows, equal intensities resolved as
  * std::nth_element + std::sort resolve them.  LDS: inten f64[cap] | mzf f32[cap] | window u16[cap] | rank u8[cap]
  * (+ 192 bytes of window starts behind it). */
-template <bool GLOBAL>
+template <bool GLOBAL, typename MZ = double, typename IT = double>
 DEV int bin_exact(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t cap, const float **out_mz,
                   const uint8_t **out_rank, int *status) {
     const int lane = lane_id();
@@ -560,8 +566,8 @@ DEV int bin_exact(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t 
     STAMP_T(b, 1, -1);
     const int64_t p0 = b.peak_off[psm];
     const int P = (int)(b.peak_off[psm + 1] - p0);
-    const double *mz = b.mz + p0;
-    const double *inten = b.inten + p0;
+    const MZ *mz = (const MZ *)b.mz + p0;
+    const IT *inten = (const IT *)b.inten + p0;
     const DevConfig *cfg = b.cfg;
     (void)cfg;
 
@@ -840,11 +846,11 @@ DEV int bin_exact(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t 
     return total;
 }
 
-template <bool EXACT>
+template <bool EXACT, typename MZ = double, typename IT = double>
 DEV int bin_core(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t cap, const float **out_mz,
                  const uint8_t **out_rank, int *status) {
-    if (EXACT) return bin_exact<false>(b, psm, lds, cap, out_mz, out_rank, status);
-    return bin_fast<false>(b, psm, lds, cap, out_mz, out_rank, status);
+    if (EXACT) return bin_exact<false, MZ, IT>(b, psm, lds, cap, out_mz, out_rank, status);
+    return bin_fast<false, false, MZ, IT>(b, psm, lds, cap, out_mz, out_rank, status);
 }
 
 /* retained table of one spectrum (or its error status) to global memory */

@@ -37,6 +37,7 @@ __host__ __device__ static inline size_t pya_bin_sel_area(uint32_t scap) {
 }
 #define PYA_BIN_SEL_BYTES(scap) (pya_bin_sel_area(scap) + PYA_BIN_SEL_TAIL)
 
+template <typename MZ = double, typename IT = double>
 DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t scap, int *status) {
     const int lane = lane_id();
     uint32_t *hist = (uint32_t *)lds;
@@ -55,9 +56,8 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
     STAMP_T(b, 1, -1);
     const int64_t p0 = b.peak_off[psm];
     const uint32_t P = (uint32_t)(b.peak_off[psm + 1] - p0);
-    const double *mz = b.mz + p0;
-    const double *inten = b.inten + p0;
-    const uint32_t *inten_hi = (const uint32_t *)inten + 1;
+    const MZ *mz = (const MZ *)b.mz + p0;                    /* (typed spectra: widened where they are loaded, bin_core.hip.h) */
+    const IT *inten = (const IT *)b.inten + p0;
     const float bin_size = b.cfg->bin_size;
     const int ntop = b.cfg->n_top;
     const double bsd = (double)bin_size, inv_bs = __builtin_amdgcn_rcp(bsd);
@@ -112,7 +112,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
             const uint32_t i = base + u * 64 + (uint32_t)lane;
             const uint32_t ic = i < P ? i : P - 1;
             v[u] = mz[ic];
-            hw[u] = inten_hi[2 * ic];
+            hw[u] = inten_hw(inten, ic);
         }
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
@@ -142,7 +142,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
             const uint32_t i = base + u * 64 + (uint32_t)lane;
             const uint32_t ic = i < P ? i : P - 1;
             v[u] = mz[ic];
-            hw[u] = inten_hi[2 * ic];
+            hw[u] = inten_hw(inten, ic);
         }
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
@@ -191,7 +191,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
                 const uint32_t i = base + u * 64 + (uint32_t)lane;
                 const uint32_t ic = i < P ? i : P - 1;
                 v[u] = mz[ic];
-                hw[u] = inten_hi[2 * ic];
+                hw[u] = inten_hw(inten, ic);
             }
 #pragma unroll
             for (uint32_t u = 0; u < U; u++) {
@@ -230,7 +230,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
             const uint32_t i = base + u * 64 + (uint32_t)lane;
             const uint32_t ic = i < P ? i : P - 1;
             v[u] = mz[ic];
-            hw[u] = inten_hi[2 * ic];
+            hw[u] = inten_hw(inten, ic);
         }
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {

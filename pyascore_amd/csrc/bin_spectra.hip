@@ -7,7 +7,10 @@
  * cache of the reference holds (ModifiedPeptide.cpp:126-142).
  *
  * HBM traffic: reads 16 B per raw peak once (coalesced, 8 B per lane), writes 8 B per retained
- * peak.  Everything else lives in LDS (bin_core.hip.h).
+ * peak.  Everything else lives in LDS (bin_core.hip.h).  Typed spectra (pya_plan_run_typed): every kernel
+ * of the family exists for <double, double>, <double, float> and <float, float> m/z and intensity arrays
+ * (12 and 8 B per raw peak); a value is widened where it is loaded, so the three compute the same table
+ * from arrays that hold the same values, and a hand-over list is worked off by the same types.
  *
  * Two kernels: pya_bin_spectra_kernel takes the common case (peaks in m/z order, no two equal
  * intensities inside a window) and appends every other spectrum to a list that
@@ -21,6 +24,7 @@
 #define BIN_WAVES 4     /* independent spectra per workgroup when LDS allows (no cross-wave sync) */
 #endif
 
+template <typename MZ, typename IT>
 __global__ __launch_bounds__(64 * BIN_WAVES) void pya_bin_spectra_kernel(BatchDev b, const uint32_t *psm_ids,
                                                                          uint32_t n_ids, uint32_t cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
@@ -37,7 +41,7 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void pya_bin_spectra_kernel(BatchDe
     const float *r_mz;
     const uint8_t *r_rank;
     int status;
-    const int R = bin_fast<true>(b, psm, lds_raw, cap, &r_mz, &r_rank, &status);   /* (stores the table itself) */
+    const int R = bin_fast<true, false, MZ, IT>(b, psm, lds_raw, cap, &r_mz, &r_rank, &status);   /* (stores the table itself) */
     if (R == PYA_BIN_REDO) {
         /* peaks out of m/z order or equal intensities in a window: left to pya_bin_exact_kernel */
         if (lane_id() == 0) b.redo_ids[atomicAdd(b.redo_count, 1u)] = psm;
@@ -49,6 +53,7 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void pya_bin_spectra_kernel(BatchDe
 /* Dense spectra (the host sends the peak classes above pya_handle.kn.bin_select_min here): selection by per-window
  * histograms, then bin_fast's ranking over the survivors only (bin_select.hip.h) -- O(peaks), LDS independent of the peak
  * count.  What it declines goes to the same list. */
+template <typename MZ, typename IT>
 __global__ __launch_bounds__(64 * BIN_WAVES) void pya_bin_select_kernel(BatchDev b, const uint32_t *psm_ids, uint32_t n_ids,
                                                                         uint32_t scap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
@@ -59,7 +64,7 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void pya_bin_select_kernel(BatchDev
     unsigned char *lds_raw = lds_all + (size_t)wave * PYA_BIN_SEL_BYTES(scap);
     const uint32_t psm = psm_ids[slot];
     int status;
-    const int R = bin_select(b, psm, lds_raw, scap, &status);
+    const int R = bin_select<MZ, IT>(b, psm, lds_raw, scap, &status);
     if (R == PYA_BIN_REDO) {
         if (lane_id() == 0) b.redo_ids[atomicAdd(b.redo_count, 1u)] = psm;
         return;
@@ -68,6 +73,7 @@ __global__ __launch_bounds__(64 * BIN_WAVES) void pya_bin_select_kernel(BatchDev
 }
 
 /* the spectra the kernels above declined, one per wavefront, a fixed grid striding over the list */
+template <typename MZ, typename IT>
 __global__ __launch_bounds__(64) void pya_bin_exact_kernel(BatchDev b, uint32_t cap) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_all[];
     const uint32_t n = *b.redo_count;
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(64) void pya_bin_exact_kernel(BatchDev b, uint32_t 
         const float *r_mz;
         const uint8_t *r_rank;
         int status;
-        const int R = bin_core<true>(b, psm, lds_all, cap, &r_mz, &r_rank, &status);
+        const int R = bin_core<true, MZ, IT>(b, psm, lds_all, cap, &r_mz, &r_rank, &status);
         bin_store(b, psm, R, status, r_mz, r_rank);
         wave_lds_sync();
     }
@@ -86,6 +92,7 @@ __global__ __launch_bounds__(64) void pya_bin_exact_kernel(BatchDev b, uint32_t 
  * area of the workspace instead of LDS, one spectrum per wavefront.  Slow (every array access is a trip to memory)
  * and rare; the PSMs behind such spectra are scored by the general kernel, which reads the retained table from the
  * workspace like this kernel leaves it. */
+template <typename MZ, typename IT>
 __global__ __launch_bounds__(64) void pya_bin_global_kernel(BatchDev b, const uint32_t *ids, uint32_t n_ids, unsigned char *scratch,
                                                             uint64_t stride, uint32_t cap) {
     if (blockIdx.x >= n_ids) return;
@@ -93,7 +100,7 @@ __global__ __launch_bounds__(64) void pya_bin_global_kernel(BatchDev b, const ui
     const float *r_mz;
     const uint8_t *r_rank;
     int status;
-    const int R = bin_exact<true>(b, psm, scratch + (size_t)blockIdx.x * stride, cap, &r_mz, &r_rank, &status);
+    const int R = bin_exact<true, MZ, IT>(b, psm, scratch + (size_t)blockIdx.x * stride, cap, &r_mz, &r_rank, &status);
     bin_store(b, psm, R, status, r_mz, r_rank);
 }
 
@@ -120,51 +127,78 @@ extern "C" int pya_launch_fan_out(const uint32_t *d_spec_of, const uint32_t *d_s
     return (int)hipGetLastError();
 }
 
+/* The launchers take the element types of b->mz / b->inten (common.h: PYA_SPEC_*) and launch that instantiation; a value
+ * that names none is refused -- there is no kernel to fall back to. */
+#define PYA_BY_TYPES(types, fn, ...)                                            \
+    ((types) == PYA_SPEC_F64_F64   ? fn<double, double>(__VA_ARGS__)            \
+     : (types) == PYA_SPEC_F64_F32 ? fn<double, float>(__VA_ARGS__)             \
+     : (types) == PYA_SPEC_F32_F32 ? fn<float, float>(__VA_ARGS__)              \
+                                   : (int)hipErrorInvalidValue)
+
 extern "C" size_t pya_bin_global_scratch_bytes(uint32_t cap) { return PYA_BIN_WAVE_BYTES(cap); }
 
-extern "C" int pya_launch_bin_global(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, unsigned char *d_scratch,
-                                     uint64_t stride, uint32_t cap, hipStream_t stream) {
-    if (n_ids == 0) return 0;
-    hipLaunchKernelGGL(pya_bin_global_kernel, dim3(n_ids), dim3(64), 0, stream, *b, d_ids, n_ids, d_scratch, stride, cap);
+template <typename MZ, typename IT>
+static int launch_bin_global(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, unsigned char *d_scratch, uint64_t stride,
+                             uint32_t cap, hipStream_t stream) {
+    hipLaunchKernelGGL((pya_bin_global_kernel<MZ, IT>), dim3(n_ids), dim3(64), 0, stream, *b, d_ids, n_ids, d_scratch, stride, cap);
     return (int)hipGetLastError();
+}
+extern "C" int pya_launch_bin_global(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, unsigned char *d_scratch,
+                                     uint64_t stride, uint32_t cap, uint32_t types, hipStream_t stream) {
+    if (n_ids == 0) return 0;
+    return PYA_BY_TYPES(types, launch_bin_global, b, d_ids, n_ids, d_scratch, stride, cap, stream);
 }
 
 extern "C" size_t pya_bin_lds_bytes(uint32_t cap) { return PYA_BIN_FAST_BYTES(cap); }
 
-extern "C" int pya_launch_bin(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap,
-                              hipStream_t stream) {
-    if (n_ids == 0) return 0;
+template <typename MZ, typename IT>
+static int launch_bin(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap, hipStream_t stream) {
     const size_t per_wave = PYA_BIN_FAST_BYTES(cap);
     const uint32_t nw = per_wave * BIN_WAVES <= 64 * 1024 ? BIN_WAVES : 1;
     size_t lds = nw * per_wave;
-    hipError_t e = PYA_ENSURE_MAX_LDS(pya_bin_spectra_kernel);
+    hipError_t e = PYA_ENSURE_MAX_LDS((pya_bin_spectra_kernel<MZ, IT>));
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pya_bin_spectra_kernel, dim3((n_ids + nw - 1) / nw), dim3(64 * nw), lds, stream, *b, d_ids,
+    hipLaunchKernelGGL((pya_bin_spectra_kernel<MZ, IT>), dim3((n_ids + nw - 1) / nw), dim3(64 * nw), lds, stream, *b, d_ids,
                        n_ids, cap);
     return (int)hipGetLastError();
+}
+extern "C" int pya_launch_bin(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap, uint32_t types,
+                              hipStream_t stream) {
+    if (n_ids == 0) return 0;
+    return PYA_BY_TYPES(types, launch_bin, b, d_ids, n_ids, cap, stream);
 }
 
 extern "C" size_t pya_bin_select_lds_bytes(uint32_t scap) { return PYA_BIN_SEL_BYTES(scap); }
 
 /* scap: survivor slots per spectrum (a multiple of 32) */
-extern "C" int pya_launch_bin_select(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t scap, hipStream_t stream) {
-    if (n_ids == 0) return 0;
+template <typename MZ, typename IT>
+static int launch_bin_select(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t scap, hipStream_t stream) {
     const size_t per_wave = PYA_BIN_SEL_BYTES(scap);
     const uint32_t nw = per_wave * BIN_WAVES <= 64 * 1024 ? BIN_WAVES : 1;
-    hipError_t e = PYA_ENSURE_MAX_LDS(pya_bin_select_kernel);
+    hipError_t e = PYA_ENSURE_MAX_LDS((pya_bin_select_kernel<MZ, IT>));
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pya_bin_select_kernel, dim3((n_ids + nw - 1) / nw), dim3(64 * nw), nw * per_wave, stream, *b, d_ids, n_ids, scap);
+    hipLaunchKernelGGL((pya_bin_select_kernel<MZ, IT>), dim3((n_ids + nw - 1) / nw), dim3(64 * nw), nw * per_wave, stream, *b, d_ids, n_ids,
+                       scap);
     return (int)hipGetLastError();
 }
+extern "C" int pya_launch_bin_select(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t scap, uint32_t types,
+                                     hipStream_t stream) {
+    if (n_ids == 0) return 0;
+    return PYA_BY_TYPES(types, launch_bin_select, b, d_ids, n_ids, scap, stream);
+}
 
-/* after every pya_launch_bin of a batch: the spectra they declined (b->redo_count must have been
- * zeroed before the first of them) */
-extern "C" int pya_launch_bin_exact(const BatchDev *b, uint32_t n_total, uint32_t cap, hipStream_t stream) {
-    if (n_total == 0) return 0;
+template <typename MZ, typename IT>
+static int launch_bin_exact(const BatchDev *b, uint32_t n_total, uint32_t cap, hipStream_t stream) {
     const size_t per_wave = PYA_BIN_WAVE_BYTES(cap);
-    hipError_t e = PYA_ENSURE_MAX_LDS(pya_bin_exact_kernel);
+    hipError_t e = PYA_ENSURE_MAX_LDS((pya_bin_exact_kernel<MZ, IT>));
     if (e != hipSuccess) return (int)e;
     const uint32_t grid = n_total < 16384u ? n_total : 16384u;   /* all spectra may need it (count-like intensities) */
-    hipLaunchKernelGGL(pya_bin_exact_kernel, dim3(grid), dim3(64), per_wave, stream, *b, cap);
+    hipLaunchKernelGGL((pya_bin_exact_kernel<MZ, IT>), dim3(grid), dim3(64), per_wave, stream, *b, cap);
     return (int)hipGetLastError();
+}
+/* after every pya_launch_bin of a batch, with their types: the spectra they declined (b->redo_count must have been
+ * zeroed before the first of them) */
+extern "C" int pya_launch_bin_exact(const BatchDev *b, uint32_t n_total, uint32_t cap, uint32_t types, hipStream_t stream) {
+    if (n_total == 0) return 0;
+    return PYA_BY_TYPES(types, launch_bin_exact, b, n_total, cap, stream);
 }

@@ -61,11 +61,16 @@ struct DevConfig {
     uint8_t cand_a[PYA_MAX_NL_CANDS], cand_b[PYA_MAX_NL_CANDS], cand_u[PYA_MAX_NL_CANDS];
 };
 
+/* element types of the raw spectrum arrays (BatchDev.mz, .inten) as the binning launchers take them */
+#define PYA_SPEC_F64_F64 0u
+#define PYA_SPEC_F64_F32 1u        /* float64 m/z, float32 intensities (mzML as msconvert writes it) */
+#define PYA_SPEC_F32_F32 2u
+
 /* device pointers + scalars of one launch family; passed by value as kernel argument */
 struct BatchDev {
     /* inputs */
-    const double *mz;
-    const double *inten;
+    const void *mz;                 /* float64 or float32 each (typed spectra): the binning launchers are told which and pick */
+    const void *inten;              /* the instantiation; every other reader of raw peaks (tiny_batch.hip) has float64    */
     const int64_t *peak_off;
     const uint8_t *pep;
     const int64_t *pep_off;

@@ -1,5 +1,8 @@
-/* host_batch.cpp -- pya_score_batch: host arrays in, host results out; chunking and the upload / kernels / download pipeline. */
+/* host_batch.cpp -- pya_score_batch: host arrays in, host results out; chunking and the upload / kernels / download pipeline.
+ * The spectra are typed (pya_typed_spectra: float64 or float32 per array, pya_score_batch_typed); every count of their
+ * bytes below is of the real ones. */
 #include "host_internal.h"
+#include "../../include/pyascore_debug.h"
 
 namespace {
 
@@ -25,7 +28,7 @@ struct ChunkCost {
     std::vector<double> ret;                   /* shared spectra: the retained table, kept out of `arena` -- it and `io` count once per spectrum of a chunk */
     std::vector<uint8_t> sites;                /* modifiable residues per PSM, 255 = invalid letters / length */
 };
-ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, const SpecShare *sh, uint32_t max_k) {
+ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, const SpecShare *sh, uint32_t max_k, size_t peak_bytes) {
     const uint64_t n = b->n_psm;
     ChunkCost c;
     c.arena.resize(n);
@@ -50,7 +53,7 @@ ChunkCost chunk_costs(pya_handle *h, const pya_batch *b, const SpecShare *sh, ui
                 }
                 sigs = N > PYA_MAX_SIGNATURES ? 0. : (double)N;
             }
-            c.io[i] = 16.0 * (double)P;
+            c.io[i] = (double)peak_bytes * (double)P;
             /* per site assignment: PepScore 4 + count record 4 x rec_words (6 for n_top = 10, 9 for 16); a PSM beyond the fast
              * kernels' limits (or any PSM of a scorer with n_top > 10) also has its slice of the general kernel's scratch, a
              * spectrum of more than PYA_FAST_PEAKS peaks the global binning kernel's 15 bytes per peak (sized by the largest) */
@@ -83,10 +86,10 @@ void rebase_error(pya_handle *h, uint64_t lo) {
 
 /* Big pya_score_batch calls: the batch is cut into chunks of consecutive PSMs that fit the device
  * budget and the chunks are pipelined -- a helper thread streams the spectra of chunk c + 1 over
- * PCIe (the bound of this entry point: 16 bytes per peak) into the other slot of a two-slot ring
+ * PCIe (the bound of this entry point: 16, 12 or 8 bytes per peak) into the other slot of a two-slot ring
  * while this thread plans chunk c, runs its kernels and brings its results back on a second
  * stream.  A call of any size completes; it never fails for lack of workspace. */
-static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const double *mz, const double *inten,
+static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp,
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
                                const uint8_t *pre_sites) {
     const size_t nchunk = cuts.size() - 1;
@@ -102,8 +105,9 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
     size_t slot_peaks = 0;
     for (size_t c = 0; c < nchunk; c++)
         slot_peaks = std::max<size_t>(slot_peaks, (size_t)(b->peak_off[spec_hi(c)] - b->peak_off[spec_lo(c)]));
+    const size_t mzb = spec_elem_bytes(sp.mz_type), itb = spec_elem_bytes(sp.intensity_type);
     for (auto &slot : h->io_ring)
-        if (slot.n < slot_peaks * 2) HIPCHK(h, slot.alloc(slot_peaks * 2));
+        if (slot.n < spec_pair_bytes(slot_peaks, sp)) HIPCHK(h, slot.alloc(spec_pair_bytes(slot_peaks, sp)));
     if (skip) h->last_status.assign(b->n_psm, 0);
 
     /* uploader: chunk c may be written once chunk c - 2 has been consumed */
@@ -122,11 +126,12 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
                 if (stop) break;
             }
             const int64_t p0 = b->peak_off[spec_lo(c)], np = b->peak_off[spec_hi(c)] - p0;
-            double *dst = h->io_ring[c & 1].p;
+            unsigned char *dst = h->io_ring[c & 1].p;
             if (np > 0) {
-                e = hipMemcpyAsync(dst, mz + p0, (size_t)np * 8, hipMemcpyHostToDevice, h->copy_stream);
+                e = hipMemcpyAsync(dst, spec_at(sp.mz, sp.mz_type, p0), (size_t)np * mzb, hipMemcpyHostToDevice, h->copy_stream);
                 if (e == hipSuccess)
-                    e = hipMemcpyAsync(dst + np, inten + p0, (size_t)np * 8, hipMemcpyHostToDevice, h->copy_stream);
+                    e = hipMemcpyAsync(dst + spec_inten_offset((size_t)np, sp.mz_type), spec_at(sp.intensity, sp.intensity_type, p0),
+                                       (size_t)np * itb, hipMemcpyHostToDevice, h->copy_stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(h->copy_stream);
             }
             std::lock_guard<std::mutex> lk(mu);
@@ -163,7 +168,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         sub.n_of_mod = b->n_of_mod + lo;
         sub.max_charge = b->max_charge + lo;
         if (b->aux_off) sub.aux_off = b->aux_off + lo;
-        IoReq io = {mz, inten, mk, h->io_ring[c & 1].p, h->io_ring[c & 1].p + np, h->run_stream,
+        IoReq io = {sp, mk, h->io_ring[c & 1].p, h->io_ring[c & 1].p + spec_inten_offset((size_t)np, sp.mz_type), h->run_stream,
                     pre_sites ? pre_sites + lo : nullptr};
         int rc = plan_create_impl(h, &sub, flags & ~(PYA_FLAG_TIMING | PYA_FLAG_KEEP), &io, sh ? &sub_sh : nullptr, pp);
         if (rc) rebase_error(h, lo);
@@ -186,7 +191,8 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
             }
         }
         pya_results d_out = {mk, p->d_best_score.p, p->d_best_sig.p, p->d_n_sig_out.p, p->d_ascores.p, p->d_alt.p};
-        rc = pya_plan_run(p, p->d_mz.p, p->d_inten.p, h->run_stream, &d_out);
+        const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
+        rc = pya_plan_run_typed(p, &d_sp, h->run_stream, &d_out);
         if (rc) return finish(rc);
         /* status + results are adjacent in the arena: one asynchronous copy into pinned memory */
         void *&pin = h->pinned_stage[c & 1];
@@ -245,11 +251,17 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
 }
 
 /* pya_score_batch (sh == nullptr: PSM i has spectrum i) and pya_score_batch_shared */
-static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *sh, const double *mz, const double *inten, uint32_t flags,
+static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp, uint32_t flags,
                             const pya_results *out) {
     const uint64_t n_spec = sh ? sh->n_spectra : b->n_psm;       /* b->peak_off has n_spec + 1 entries */
+    const void *mz = sp.mz, *inten = sp.intensity;
     h->last_status.clear();
+    h->last_chunks = 1;
     if (b->n_psm == 0) return PYA_OK;
+    uint32_t types = 0;
+    const int rc_types = spectra_types(h, &sp, "pya_score_batch_typed", &types);
+    if (rc_types) return rc_types;
+    const size_t mzb = spec_elem_bytes(sp.mz_type), itb = spec_elem_bytes(sp.intensity_type);
     if (!mz || !inten) return h->fail(PYA_ERR_ARG, -1, "NULL spectrum arrays");
     if (!b->peak_off || !b->pep || !b->pep_off || !b->n_of_mod || !b->max_charge)
         return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
@@ -259,13 +271,13 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     /* (not while the records of a pya_score_one PSM are retained in the one-PSM workspace: this call would overwrite
      * what pya_get_pep_scores / pya_calculate_ambiguity still read there) */
     const bool one_view_live = h->kept && h->kept == h->one.view;
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING)) && !one_view_live) {
-        /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING)) && !one_view_live && types == PYA_SPEC_F64_F64) {
+        /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
         const int64_t P1 = b->peak_off[1] - b->peak_off[0], L1 = b->pep_off[1] - b->pep_off[0];
         if (a1 >= a0 && P1 >= 0 && L1 >= 0) {
-            int rc1 = pya_score_one(h, mz + b->peak_off[0], inten + b->peak_off[0], (uint64_t)P1, b->pep + b->pep_off[0], (uint64_t)L1,
+            int rc1 = pya_score_one(h, (const double *)mz + b->peak_off[0], (const double *)inten + b->peak_off[0], (uint64_t)P1, b->pep + b->pep_off[0], (uint64_t)L1,
                                     b->n_of_mod[0], b->max_charge[0], has_aux1 ? b->aux_pos + a0 : nullptr,
                                     has_aux1 ? b->aux_mass + a0 : nullptr, (uint64_t)(a1 - a0), flags & PYA_FLAG_KEEP, out);
             /* the one-PSM staging now holds THIS PSM: pya_rescore_last_keep must not replay it as the caller's last
@@ -278,10 +290,10 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         /* Chunking: needed when the call does not fit the device budget, worthwhile (pipelining)
          * when there is enough PCIe traffic to hide the kernels under.  A retained batch
          * (PYA_FLAG_KEEP) stays one plan: its records are queried by PSM afterwards. */
-        const size_t io_total = (size_t)(b->peak_off[n_spec] - b->peak_off[0]) * 16;
+        const size_t io_total = (size_t)(b->peak_off[n_spec] - b->peak_off[0]) * (mzb + itb);
         if (!(flags & PYA_FLAG_KEEP) && io_total >= kChunkMin && !h->kn.no_chunks) {
             const size_t budget = workspace_budget(h);
-            const ChunkCost cost = chunk_costs(h, b, sh, out->max_k);
+            const ChunkCost cost = chunk_costs(h, b, sh, out->max_k, mzb + itb);
             double io_target = (double)kChunkTarget;
             if (h->kn.chunk_mb > 0.) io_target = h->kn.chunk_mb * 1048576.0;
             std::vector<uint64_t> cuts{0};
@@ -301,7 +313,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
                 }
             }
             cuts.push_back(b->n_psm);
-            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, mz, inten, flags, out, cuts, cost.sites.data());
+            h->last_chunks = cuts.size() - 1;
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data());
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -314,24 +327,24 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         t0 = t1;
     };
     pya_plan *p = nullptr;
-    IoReq io = {mz, inten, out->max_k, nullptr, nullptr, nullptr, nullptr};
-    /* Big batches: the spectra (16 bytes per peak, PCIe-bound) go up on a helper thread while this
+    IoReq io = {sp, out->max_k, nullptr, nullptr, nullptr, nullptr};
+    /* Big batches: the spectra (16, 12 or 8 bytes per peak, PCIe-bound) go up on a helper thread while this
      * one runs the host pre-pass of the plan; small ones ride in the plan's single staged copy. */
     const int64_t peaks_lo = b->peak_off[0], n_peaks = b->peak_off[n_spec] - peaks_lo;
     std::thread uploader;
     hipError_t up_err = hipSuccess;
-    if (n_peaks > 0 && (size_t)n_peaks * 16 > kStageLimit && !h->kn.no_upload_thread) {
+    if (n_peaks > 0 && (size_t)n_peaks * (mzb + itb) > kStageLimit && !h->kn.no_upload_thread) {
         HIPCHK(h, hipSetDevice(h->device));
-        if (h->io_buf.n < (size_t)n_peaks * 2) HIPCHK(h, h->io_buf.alloc((size_t)n_peaks * 2));
+        if (h->io_buf.n < spec_pair_bytes((size_t)n_peaks, sp)) HIPCHK(h, h->io_buf.alloc(spec_pair_bytes((size_t)n_peaks, sp)));
         io.d_mz_ext = h->io_buf.p;
-        io.d_inten_ext = h->io_buf.p + n_peaks;
+        io.d_inten_ext = h->io_buf.p + spec_inten_offset((size_t)n_peaks, sp.mz_type);
         const int device = h->device;
         uploader = std::thread([&, device]() {
             up_err = hipSetDevice(device);
             if (up_err == hipSuccess)
-                up_err = hipMemcpy(io.d_mz_ext, mz + peaks_lo, (size_t)n_peaks * 8, hipMemcpyHostToDevice);
+                up_err = hipMemcpy(io.d_mz_ext, spec_at(mz, sp.mz_type, peaks_lo), (size_t)n_peaks * mzb, hipMemcpyHostToDevice);
             if (up_err == hipSuccess)
-                up_err = hipMemcpy(io.d_inten_ext, inten + peaks_lo, (size_t)n_peaks * 8, hipMemcpyHostToDevice);
+                up_err = hipMemcpy(io.d_inten_ext, spec_at(inten, sp.intensity_type, peaks_lo), (size_t)n_peaks * itb, hipMemcpyHostToDevice);
         });
     }
     int rc = plan_create_impl(h, b, flags & ~PYA_FLAG_TIMING, &io, sh, &p);
@@ -346,7 +359,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     const uint64_t n = b->n_psm;
     const uint32_t mk = out->max_k;
     pya_results d_out = {mk, p->d_best_score.p, p->d_best_sig.p, p->d_n_sig_out.p, p->d_ascores.p, p->d_alt.p};
-    rc = pya_plan_run(p, p->d_mz.p, p->d_inten.p, nullptr, &d_out);
+    const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
+    rc = pya_plan_run_typed(p, &d_sp, nullptr, &d_out);
     if (rc) return rc;
     if (p->d2h_bytes <= kStageLimit) {
         /* status and results are adjacent in the arena: one copy, which also waits for the kernels */
@@ -385,17 +399,34 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
 int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const double *inten, uint32_t flags,
                     const pya_results *out) {
     if (!h || !b || !out) return PYA_ERR_ARG;
-    return score_batch_impl(h, b, nullptr, mz, inten, flags, out);
+    const pya_typed_spectra sp = {mz, inten, PYA_F64, PYA_F64};
+    return score_batch_impl(h, b, nullptr, sp, flags, out);
 }
 
-int pya_score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const double *mz,
-                           const double *inten, uint32_t flags, const pya_results *out) {
-    if (!h || !b || !out) return PYA_ERR_ARG;
+static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const pya_typed_spectra &sp,
+                              uint32_t flags, const pya_results *out) {
     h->last_status.clear();
     if (b->n_psm == 0) return PYA_OK;
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
     if (rc) return rc;
     const SpecShare sh = {spec_of, n_spectra, 0u};
-    return score_batch_impl(h, b, &sh, mz, inten, flags, out);
+    return score_batch_impl(h, b, &sh, sp, flags, out);
 }
+
+int pya_score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const double *mz,
+                           const double *inten, uint32_t flags, const pya_results *out) {
+    if (!h || !b || !out) return PYA_ERR_ARG;
+    const pya_typed_spectra sp = {mz, inten, PYA_F64, PYA_F64};
+    return score_batch_shared(h, b, spec_of, n_spectra, sp, flags, out);
+}
+
+int pya_score_batch_typed(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const pya_typed_spectra *spectra,
+                          uint32_t flags, const pya_results *out) {
+    if (!h || !b || !out) return PYA_ERR_ARG;
+    if (!spectra) return h->fail(PYA_ERR_ARG, -1, "NULL spectrum arrays");
+    return spec_of ? score_batch_shared(h, b, spec_of, n_spectra, *spectra, flags, out) : score_batch_impl(h, b, nullptr, *spectra, flags, out);
+}
+
+/* (include/pyascore_debug.h) */
+uint64_t pya_debug_last_chunks(const pya_handle *h) { return h ? h->last_chunks : 0; }

@@ -46,10 +46,11 @@ extern "C" {
 size_t pya_bin_lds_bytes(uint32_t cap);
 size_t pya_score_lds_bytes(uint32_t cap, uint32_t prefix, uint32_t with_nl, uint32_t compact);
 size_t pya_localize_lds_bytes(uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb);
-int pya_launch_bin(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap, hipStream_t stream);
-int pya_launch_bin_select(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t scap, hipStream_t stream);
+/* (the binning launchers: `types` = PYA_SPEC_*, the element types of b->mz and b->inten) */
+int pya_launch_bin(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap, uint32_t types, hipStream_t stream);
+int pya_launch_bin_select(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t scap, uint32_t types, hipStream_t stream);
 size_t pya_bin_select_lds_bytes(uint32_t scap);
-int pya_launch_bin_exact(const BatchDev *b, uint32_t n_total, uint32_t cap, hipStream_t stream);
+int pya_launch_bin_exact(const BatchDev *b, uint32_t n_total, uint32_t cap, uint32_t types, hipStream_t stream);
 int pya_launch_fan_out(const uint32_t *d_spec_of, const uint32_t *d_spec_ret_n, const int32_t *d_spec_status, uint32_t *d_ret_n,
                        int32_t *d_status, uint32_t n_psm, hipStream_t stream);
 int pya_launch_score(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap, uint32_t prefix,
@@ -106,7 +107,7 @@ int pya_launch_score_cntg(const BatchDev *b, const uint32_t *d_ids, uint32_t n_i
                           uint32_t nl_cap, hipStream_t stream);
 size_t pya_bin_global_scratch_bytes(uint32_t cap);
 int pya_launch_bin_global(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, unsigned char *d_scratch, uint64_t stride,
-                          uint32_t cap, hipStream_t stream);
+                          uint32_t cap, uint32_t types, hipStream_t stream);
 size_t pya_general_lds_bytes(uint32_t l_cap, uint32_t list_cap);
 size_t pya_general_scratch_bytes(uint32_t n_cap, uint32_t push_cap);
 int pya_launch_general(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, unsigned char *d_scratch, const uint64_t *d_scratch_off,
@@ -275,8 +276,9 @@ struct pya_handle {
     DevBuf<unsigned char> spare_arena, spare_arena2;   /* two: chunked calls keep two plans alive */
     void *pinned_stage[2] = {nullptr, nullptr};        /* chunked calls: results of chunk c land in slot c % 2 */
     size_t pinned_bytes[2] = {0, 0};
-    DevBuf<double> io_buf;                     /* spectra of big pya_score_batch calls (uploaded by a helper thread) */
-    DevBuf<double> io_ring[2];                 /* chunked calls: spectra of chunk c in slot c % 2 */
+    uint64_t last_chunks = 0;                  /* plans the last pya_score_batch call was cut into (pya_debug_last_chunks) */
+    DevBuf<unsigned char> io_buf;              /* spectra of big pya_score_batch calls (uploaded by a helper thread) */
+    DevBuf<unsigned char> io_ring[2];          /* chunked calls: spectra of chunk c in slot c % 2 */
     hipStream_t copy_stream = nullptr, run_stream = nullptr;   /* chunked calls: uploads / kernels + results */
     size_t ws_budget = 0;                      /* device bytes one pya_score_batch call may hold (0 = default) */
     std::vector<unsigned char> stage;          /* host staging of small batches: one copy each way */
@@ -571,7 +573,7 @@ struct pya_plan {
     uint64_t n_skipped = 0;
     DevBuf<uint32_t> d_bin_ids, d_score_ids;
     /* owned copies of inputs/outputs (pya_score_batch path) */
-    DevBuf<double> d_mz, d_inten;
+    DevBuf<unsigned char> d_mz, d_inten;  /* (bytes: float64 or float32 elements, IoReq::sp says which) */
     DevBuf<float> d_best_score, d_ascores;
     DevBuf<uint64_t> d_best_sig, d_alt;
     DevBuf<int32_t> d_n_sig_out;
@@ -686,10 +688,25 @@ inline void pack_desc_tail(uint64_t L, uint64_t n_aux, int32_t k, uint32_t ns, i
 }
 
 /* host_plan.cpp: creating a plan (the host pre-pass in phases, the arena); host_run.cpp: running it */
+/* Typed spectra (pya_typed_spectra): bytes of one element, 0 for a value that is no type */
+inline size_t spec_elem_bytes(uint32_t type) { return type == PYA_F64 ? 8u : type == PYA_F32 ? 4u : 0u; }
+/* the supported combinations as the binning launchers name them (common.h: PYA_SPEC_*); anything else: PYA_ERR_ARG with a
+ * message that starts with `who` */
+int spectra_types(pya_handle *h, const pya_typed_spectra *s, const char *who, uint32_t *types);
+/* where the intensities start behind n m/z values of one allocation: at the arena's granule, which aligns every load the
+ * kernels make of either type */
+inline size_t spec_inten_offset(size_t n_peaks, uint32_t mz_type) { return (n_peaks * spec_elem_bytes(mz_type) + 255) & ~(size_t)255; }
+inline size_t spec_pair_bytes(size_t n_peaks, const pya_typed_spectra &s) {
+    return spec_inten_offset(n_peaks, s.mz_type) + n_peaks * spec_elem_bytes(s.intensity_type);
+}
+inline const unsigned char *spec_at(const void *arr, uint32_t type, int64_t peak) {
+    return (const unsigned char *)arr + (size_t)peak * spec_elem_bytes(type);
+}
+
 struct IoReq {                       /* pya_score_batch: spectra and results live in the plan's arena too */
-    const double *mz, *inten;
+    pya_typed_spectra sp;            /* the caller's host arrays and their element types */
     uint32_t max_k;
-    double *d_mz_ext, *d_inten_ext;  /* ... unless the caller uploads the spectra itself (big batches) */
+    unsigned char *d_mz_ext, *d_inten_ext;  /* ... unless the caller uploads the spectra itself (big batches) */
     hipStream_t stream;              /* metadata upload: on this stream, waited for alone (nullptr: device-wide) */
     const uint8_t *pre_sites;        /* letter scan already done by the caller: sites per PSM, 255 = invalid letters */
 };

@@ -637,11 +637,12 @@ int layout_and_upload(PlanBuild &B) {
         A.add(p->d_sret_off, p->sret_off.size(), p->sret_off.data());
     }
     if (io && !io->d_mz_ext) {                        /* pya_score_batch: the spectra ride in the same copy ... */
-        A.add(p->d_mz, n_peaks, io->mz + B.peak_base);
-        A.add(p->d_inten, n_peaks, io->inten + B.peak_base);
+        const size_t mzb = spec_elem_bytes(io->sp.mz_type), itb = spec_elem_bytes(io->sp.intensity_type);   /* (real bytes) */
+        A.add(p->d_mz, n_peaks * mzb, spec_at(io->sp.mz, io->sp.mz_type, B.peak_base));
+        A.add(p->d_inten, n_peaks * itb, spec_at(io->sp.intensity, io->sp.intensity_type, B.peak_base));
     } else if (io) {                                  /* ... unless the caller uploads them itself */
-        p->d_mz.adopt(io->d_mz_ext, n_peaks);
-        p->d_inten.adopt(io->d_inten_ext, n_peaks);
+        p->d_mz.adopt(io->d_mz_ext, n_peaks * spec_elem_bytes(io->sp.mz_type));
+        p->d_inten.adopt(io->d_inten_ext, n_peaks * spec_elem_bytes(io->sp.intensity_type));
     }
     const size_t h2d_bytes = A.total;
     p->o_status = A.add(p->d_status, n);
@@ -768,6 +769,16 @@ void fill_dev(pya_plan *p) {
 }
 
 }  // namespace
+
+int spectra_types(pya_handle *h, const pya_typed_spectra *s, const char *who, uint32_t *types) {
+    if (!spec_elem_bytes(s->mz_type) || !spec_elem_bytes(s->intensity_type))
+        return h->fail(PYA_ERR_ARG, -1, "%s: spectrum types (%u, %u) are not PYA_F64 (%u) / PYA_F32 (%u)", who, s->mz_type, s->intensity_type,
+                       PYA_F64, PYA_F32);
+    if (s->mz_type == PYA_F32 && s->intensity_type == PYA_F64)
+        return h->fail(PYA_ERR_ARG, -1, "%s: float32 m/z with float64 intensities is not supported (pass both as float32 or widen the m/z)", who);
+    *types = s->mz_type == PYA_F32 ? PYA_SPEC_F32_F32 : s->intensity_type == PYA_F32 ? PYA_SPEC_F64_F32 : PYA_SPEC_F64_F64;
+    return PYA_OK;
+}
 
 int check_spec_of(pya_handle *h, uint64_t n_psm, const uint32_t *spec_of, uint64_t n_spectra) {
     h->err.clear();

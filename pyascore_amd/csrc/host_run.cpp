@@ -68,12 +68,13 @@ struct RunMarks {
 
 /* A handful of PSMs (PyAscore.score is a batch of one) is launch-bound: one fused launch, one wavefront per PSM, instead of
  * the five of the three-kernel path (tiny_batch.hip).  *done = whether the batch went that way. */
-int run_tiny(pya_plan *p, const BatchDev &d, hipStream_t st, bool *done) {
+int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, bool *done) {
     pya_handle *h = p->h;
     *done = false;
-    /* (the tiny kernel bins per PSM from the PSM's own peaks: a shared batch, however small, takes the plan's launches) */
+    /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
+     * however small, take the plan's launches) */
     if ((p->flags & PYA_FLAG_TIMING) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
-        p->shared)
+        p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
      * caps count too -- leaving them out sized this launch's work areas for the other PSMs only) */
@@ -95,7 +96,9 @@ int run_tiny(pya_plan *p, const BatchDev &d, hipStream_t st, bool *done) {
     return PYA_OK;
 }
 
-int run_binning(pya_plan *p, const BatchDev &d, hipStream_t st) {
+/* `types`: the element types of d.mz / d.inten (PYA_SPEC_*) -- every launch of the family, the exact kernel that works off what
+ * the others hand over included, is the instantiation for them */
+int run_binning(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st) {
     pya_handle *h = p->h;
     int e = 0;
     for (const pya_plan::IdList &l : p->bin_lists) {
@@ -103,14 +106,14 @@ int run_binning(pya_plan *p, const BatchDev &d, hipStream_t st) {
          * of LDS per raw peak */
         const uint32_t scap = (uint32_t)std::min<int64_t>(std::max<int64_t>(h->kn.bin_select_scap, 64), 4096) & ~31u;
         if ((int64_t)l.cap > h->kn.bin_select_min)
-            e = pya_launch_bin_select(&d, p->d_bin_ids.p + l.off, l.n, scap, st);
+            e = pya_launch_bin_select(&d, p->d_bin_ids.p + l.off, l.n, scap, types, st);
         else
-            e = pya_launch_bin(&d, p->d_bin_ids.p + l.off, l.n, l.cap, st);
+            e = pya_launch_bin(&d, p->d_bin_ids.p + l.off, l.n, l.cap, types, st);
         if (e) return h->hip_fail((hipError_t)e, "bin_spectra launch");
     }
-    e = pya_launch_bin_exact(&d, (uint32_t)p->n_psm, p->peak_cap, st);
+    e = pya_launch_bin_exact(&d, (uint32_t)p->n_psm, p->peak_cap, types, st);
     if (e) return h->hip_fail((hipError_t)e, "bin_spectra (exact) launch");
-    e = pya_launch_bin_global(&d, p->d_bigbin_ids.p, (uint32_t)p->bigbin_ids.size(), p->d_bigbin_scratch.p, p->bigbin_stride, p->bigbin_cap, st);
+    e = pya_launch_bin_global(&d, p->d_bigbin_ids.p, (uint32_t)p->bigbin_ids.size(), p->d_bigbin_scratch.p, p->bigbin_stride, p->bigbin_cap, types, st);
     if (e) return h->hip_fail((hipError_t)e, "bin_spectra (global) launch");
     return PYA_OK;
 }
@@ -118,12 +121,12 @@ int run_binning(pya_plan *p, const BatchDev &d, hipStream_t st) {
 /* Shared spectra: the binning family over SPECTRUM ids with the spectrum-side view of the plan (peak_off is the spectra's
  * already; ret_off, ret_n and status by spectrum), then the fan-out that gives every PSM its spectrum's ret_n and status --
  * behind it every kernel reads by PSM number, as in an unshared plan. */
-int run_binning_shared(pya_plan *p, const BatchDev &d, hipStream_t st) {
+int run_binning_shared(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st) {
     BatchDev sd = d;
     sd.ret_off = p->d_sret_off.p;
     sd.ret_n = p->d_sret_n.p;
     sd.status = p->d_sstatus.p;
-    const int rc = run_binning(p, sd, st);
+    const int rc = run_binning(p, sd, types, st);
     if (rc) return rc;
     const int e = pya_launch_fan_out(p->d_spec_of.p, p->d_sret_n.p, p->d_sstatus.p, d.ret_n, d.status, (uint32_t)p->n_psm, st);
     if (e) return p->h->hip_fail((hipError_t)e, "fan-out launch");
@@ -269,9 +272,19 @@ int run_behind_binning(pya_plan *p, const BatchDev &d, hipStream_t st, const Run
 
 int pya_plan_run(pya_plan *p, const double *d_mz, const double *d_inten, void *hip_stream,
                  const pya_results *o) {
+    const pya_typed_spectra sp = {d_mz, d_inten, PYA_F64, PYA_F64};
+    return pya_plan_run_typed(p, &sp, hip_stream, o);
+}
+
+int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_stream, const pya_results *o) {
     if (!p || !o) return PYA_ERR_ARG;
     pya_handle *h = p->h;
     if (p->n_psm == 0) return PYA_OK;
+    if (!sp) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_run");
+    uint32_t types = 0;
+    const int rc_types = spectra_types(h, sp, "pya_plan_run_typed", &types);
+    if (rc_types) return rc_types;
+    const void *d_mz = sp->mz, *d_inten = sp->intensity;
     if (!d_mz || !d_inten || !o->best_score || !o->best_sig || !o->n_sig || !o->ascores || !o->alt_mask)
         return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_run");
     if (o->max_k < p->max_k)
@@ -290,7 +303,7 @@ int pya_plan_run(pya_plan *p, const double *d_mz, const double *d_inten, void *h
     d.alt_mask = o->alt_mask;
     d.max_k = o->max_k;
     bool tiny = false;
-    int rc = run_tiny(p, d, st, &tiny);
+    int rc = run_tiny(p, d, types, st, &tiny);
     if (rc) return rc;
     if (!tiny) {
         const bool timing = p->flags & PYA_FLAG_TIMING;
@@ -305,7 +318,7 @@ int pya_plan_run(pya_plan *p, const double *d_mz, const double *d_inten, void *h
         d.zero_next = p->d_redo.p + 8 * ((p->n_runs + 1u) & 1u);
         if (p->n_runs == 0 || !pya_plan::any_ids(p->bin_lists)) HIPCHK(h, hipMemsetAsync(p->d_redo.p, 0, 16 * sizeof(uint32_t), st));
         p->n_runs++;
-        if ((rc = p->shared ? run_binning_shared(p, d, st) : run_binning(p, d, st))) return rc;
+        if ((rc = p->shared ? run_binning_shared(p, d, types, st) : run_binning(p, d, types, st))) return rc;
         if ((rc = mark(1, true))) return rc;
         if (!p->fork) {
             if ((rc = run_behind_binning(p, d, st, mark))) return rc;

@@ -87,7 +87,7 @@ __global__ __launch_bounds__(64) void pya_one_kernel(BatchDev b, OneMeta m, uint
     /* the spectrum sits in host memory: the loads of its first 384 peaks go out before anything else and travel while
      * the scalars below are put into place (the peak count is a kernel argument, the spectrum starts at offset 0) */
     BinPre pre;
-    bin_preload(b.mz, b.inten, m.n_peaks, &pre);
+    bin_preload((const double *)b.mz, (const double *)b.inten, m.n_peaks, &pre);
     /* the PSM's scalars into the batch arrays (all of them arrays of one PSM at offset 0) */
     if (lane == 0) {
         int64_t *w;

@@ -15,7 +15,7 @@ from .ascore import PyAscore, _as_ptr
 class DevicePlan:
     """One batch planned once (host pre-pass, tables, workspace), runnable many times.
 
-    ``spectra`` are two float64 CUDA/HIP tensors (m/z, intensity) laid out as the batch's
+    ``spectra`` are two float64 or float32 CUDA/HIP tensors (m/z, intensity) laid out as the batch's
     ``peak_off`` says (a batch with ``spec_of``: the spectra's, each held once and shared by its PSMs,
     which must be consecutive).  ``run()`` enqueues the three kernels on torch's current stream and
     returns the result tensors (device).  ``max_k`` widens the per-site result rows beyond this
@@ -89,13 +89,24 @@ class DevicePlan:
         return int(self._lib.pya_plan_total_signatures(self._plan))
 
     def run(self, d_mz, d_intensity):
+        """Enqueues the plan on torch's current stream.  The tensors are float64, or typed: float64 m/z with float32
+        intensities, or both float32 (the binning kernels widen at the load; results as for the widened tensors, bit for
+        bit).  One plan takes any of the three from run to run."""
         torch = self._torch
         for t in (d_mz, d_intensity):
-            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("spectra must be contiguous float64 device tensors")
+            if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("spectra must be contiguous float64 device tensors (or float32: float64 m/z with float32 "
+                                 "intensities, or both float32)")
+        if d_mz.dtype == torch.float32 and d_intensity.dtype == torch.float64:
+            raise ValueError("spectra must be contiguous float64 device tensors (float32 m/z beside float64 intensities is "
+                             "not supported)")
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._lib.pya_plan_run(self._plan, d_mz.data_ptr(), d_intensity.data_ptr(), stream,
-                                    C.byref(self._res))
+        if d_intensity.dtype == torch.float64:
+            rc = self._lib.pya_plan_run(self._plan, d_mz.data_ptr(), d_intensity.data_ptr(), stream, C.byref(self._res))
+        else:
+            sp = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype),
+                                   _lib.spectrum_type(d_intensity.dtype))
+            rc = self._lib.pya_plan_run_typed(self._plan, C.byref(sp), stream, C.byref(self._res))
         if rc:
             self.scorer._raise(rc)
         return self

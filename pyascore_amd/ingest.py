@@ -224,8 +224,18 @@ def _decode(text, dtype, compressed):
     return np.frombuffer(raw, dtype=dtype)
 
 
+def _as_native(values, width, native_precision):
+    """decoded values as a writable array in host byte order: float64 (the reference's), or -- native_precision -- the
+    precision the file declares (``width``: 'f8' / 'f4')"""
+    return values.astype(np.float32 if native_precision and width == "f4" else np.float64)
+
+
 class MzMLExtractor:
-    """<spectrum> element -> record (spec_parsers.py:49-113)."""
+    """<spectrum> element -> record (spec_parsers.py:49-113).  ``native_precision``: each array keeps the precision its
+    binaryDataArray declares instead of being widened to float64."""
+
+    def __init__(self, native_precision=False):
+        self.native_precision = native_precision
 
     def extract(self, spectrum):
         params = {}
@@ -256,13 +266,13 @@ class MzMLExtractor:
         if arrays is not None:
             for arr in _children(arrays, "binaryDataArray"):
                 names = {cv.get("name") for cv in _children(arr, "cvParam")}
-                dtype = "<f8" if "64-bit float" in names else ("<f4" if "32-bit float" in names else None)
+                dtype = "f8" if "64-bit float" in names else ("f4" if "32-bit float" in names else None)
                 kind = "mz" if "m/z array" in names else ("int" if "intensity array" in names else None)
                 if dtype is None or kind is None:
                     continue
                 binary = _first(arr, "binary")
-                got[kind] = _decode(binary.text if binary is not None else "", dtype,
-                                    "zlib compression" in names).astype(np.float64)
+                got[kind] = _as_native(_decode(binary.text if binary is not None else "", "<" + dtype, "zlib compression" in names),
+                                       dtype, self.native_precision)
         if "mz" in got and "int" in got:
             mz, inten = got["mz"], got["int"]
         return {"scan": scan, "ms_level": ms_level, "precursor_mz": precursor_mz,
@@ -270,7 +280,11 @@ class MzMLExtractor:
 
 
 class MzXMLExtractor:
-    """<scan> element -> record (spec_parsers.py:115-172)."""
+    """<scan> element -> record (spec_parsers.py:115-172).  ``native_precision``: both arrays keep the precision the
+    <peaks> element declares (32 unless it says 64) instead of being widened to float64."""
+
+    def __init__(self, native_precision=False):
+        self.native_precision = native_precision
 
     def extract(self, scan):
         num = int(scan.get("num")) if scan.get("num") is not None else -1
@@ -289,7 +303,7 @@ class MzXMLExtractor:
             width = "f8" if peaks.get("precision", "32") == "64" else "f4"
             order = "<" if peaks.get("byteOrder", "network") != "network" else ">"
             pairs = _decode(peaks.text.strip(), order + width, peaks.get("compressionType", "none") == "zlib")
-            pairs = pairs.astype(np.float64)
+            pairs = _as_native(pairs, width, self.native_precision)
             mz, inten = pairs[0::2].copy(), pairs[1::2].copy()
         return {"scan": num, "ms_level": ms_level, "precursor_mz": precursor_mz,
                 "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten}
@@ -311,13 +325,15 @@ class SpectraParser:
 
     ``ms_level``: only scans of this MSn level are returned (0 = all); ``custom_filter``: a callable
     record -> bool.  ``to_list()`` is sorted by scan number, ``to_dict()`` maps scan -> record (without
-    its "scan" field)."""
+    its "scan" field).  ``native_precision=True``: ``mz_values`` / ``intensity_values`` keep the precision the file
+    declares (mzML per array -- msconvert writes 64-bit m/z and 32-bit intensities --, mzXML per ``precision``) instead of
+    the reference's float64; ``PyAscore.score_batch`` takes float32 arrays as they are."""
 
-    def __init__(self, spec_file_name, spec_file_format, ms_level=2, custom_filter=None):
+    def __init__(self, spec_file_name, spec_file_format, ms_level=2, custom_filter=None, native_precision=False):
         if spec_file_format == "mzML":
-            self._records = lambda: (MzMLExtractor().extract(s) for s in _stream(spec_file_name, {"spectrum"}))
+            self._records = lambda: (MzMLExtractor(native_precision).extract(s) for s in _stream(spec_file_name, {"spectrum"}))
         elif spec_file_format == "mzXML":
-            self._records = lambda: (MzXMLExtractor().extract(s) for s in _mzxml_scans(spec_file_name))
+            self._records = lambda: (MzXMLExtractor(native_precision).extract(s) for s in _mzxml_scans(spec_file_name))
         else:
             raise ValueError("{} not supported at this time."
                              " Should be one of: mzML or mzXML".format(spec_file_format))

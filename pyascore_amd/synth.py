@@ -287,11 +287,20 @@ def make_slice(desc, lo=0, hi=None, threads=None):
     return concat_batches(parts)
 
 
+def _spectrum_dtype(arrays):
+    """float32 when every non-empty array of the list is float32 (typed spectra keep their type through a pack), else
+    float64: a mix widens."""
+    kinds = {np.asarray(a).dtype for a in arrays if np.size(a)}
+    return np.float32 if kinds == {np.dtype(np.float32)} else np.float64
+
+
 def pack_batch(psms):
-    """List of dicts {mz, intensity, peptide, n_of_mod, max_charge, aux_pos, aux_mass} -> CSR."""
+    """List of dicts {mz, intensity, peptide, n_of_mod, max_charge, aux_pos, aux_mass} -> CSR.  ``mz`` and ``intensity``
+    come out float32 when every PSM's array is (``PyAscore.score_batch`` sends such arrays as they are), else float64."""
     n = len(psms)
-    mz = [np.asarray(p["mz"], np.float64) for p in psms]
-    it = [np.asarray(p["intensity"], np.float64) for p in psms]
+    mz_t, it_t = _spectrum_dtype([p["mz"] for p in psms]), _spectrum_dtype([p["intensity"] for p in psms])
+    mz = [np.asarray(p["mz"], mz_t) for p in psms]
+    it = [np.asarray(p["intensity"], it_t) for p in psms]
     pep = [np.frombuffer(p["peptide"].encode(), dtype=np.uint8) for p in psms]
     ap = [np.asarray(p.get("aux_pos", ()), np.uint32) for p in psms]
     am = [np.asarray(p.get("aux_mass", ()), np.float32) for p in psms]
@@ -303,7 +312,7 @@ def pack_batch(psms):
         return np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
 
     return dict(
-        n_psm=n, mz=cat(mz, np.float64), intensity=cat(it, np.float64), peak_off=off(mz),
+        n_psm=n, mz=cat(mz, mz_t), intensity=cat(it, it_t), peak_off=off(mz),
         pep=cat(pep, np.uint8), pep_off=off(pep),
         n_of_mod=np.asarray([p["n_of_mod"] for p in psms], np.int32),
         max_charge=np.asarray([p.get("max_charge", 1) for p in psms], np.int32),
@@ -338,9 +347,27 @@ def expand_shared_batch(batch):
     off = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
     idx = np.repeat(po[so] - off[:-1], cnt) + np.arange(off[-1], dtype=np.int64)
     out = {k: v for k, v in batch.items() if k not in ("spec_of", "n_spectra")}
-    out.update(mz=np.ascontiguousarray(np.asarray(batch["mz"], np.float64)[idx]),
-               intensity=np.ascontiguousarray(np.asarray(batch["intensity"], np.float64)[idx]), peak_off=off)
+    out.update(mz=np.ascontiguousarray(_spectrum_array(batch["mz"])[idx]),
+               intensity=np.ascontiguousarray(_spectrum_array(batch["intensity"])[idx]), peak_off=off)
     return out
+
+
+def _spectrum_array(a):
+    """a spectrum array of a batch as numpy: float32 stays, everything else is float64"""
+    a = np.asarray(a)
+    return a if a.dtype == np.float32 else np.asarray(a, np.float64)
+
+
+def narrow_batch(batch, mz=np.float32, intensity=np.float32):
+    """``batch`` with its spectrum arrays ROUNDED to the given types (typed spectra: float32 m/z and / or intensities, as
+    mzML and mzXML files hold them); everything else is shared with ``batch``.  ``widen_batch`` of the result holds the
+    same values in float64 -- the batch the typed path is held bit-equal to."""
+    return dict(batch, mz=np.ascontiguousarray(batch["mz"], mz), intensity=np.ascontiguousarray(batch["intensity"], intensity))
+
+
+def widen_batch(batch):
+    """``batch`` with its spectrum arrays as float64 holding the same values (float32 -> float64 is exact)."""
+    return narrow_batch(batch, np.float64, np.float64)
 
 
 def spectrum_order(spec_of):
