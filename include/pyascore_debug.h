@@ -43,6 +43,25 @@ int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]);
  * the same batch widened.  No reference counterpart. */
 uint64_t pya_debug_last_chunks(const pya_handle *h);
 
+/* The retained-peak table the binning kernels left in a plan's workspace for entry `index`, copied to the host: mz[i], rank[i]
+ * = (float m/z, rank in its window) of table entry i, in table order (m/z ascending).  index = the PSM number, or the SPECTRUM
+ * number for a plan with shared spectra (every spectrum has one table).  *n = the entry count the kernel stored (the +inf
+ * entry padded behind an odd count is not part of it); *status = the status word beside it as the run left it, a PYA_ST_* code
+ * of csrc/common.h (0 ok, 1 no windows, 2 too many windows -- the values of PYA_PSM_NO_WINDOWS / PYA_PSM_TOO_MANY_WINDOWS;
+ * a shared plan's word is the spectrum's, written by the binning alone, a private PSM's may carry a later stage's code
+ * instead).  Nothing of a plan's arena overlays the table after the binning (host_plan.cpp: layout_and_upload gives every
+ * buffer its own range; the retained records and pya_calculate_ambiguity read the table later), so it is what the scoring
+ * kernels read.  Waits for the stream of the plan's last run before it copies.
+ * PYA_ERR_ARG: no plan or a plan that has not run, index out of range, an entry that was never binned (a PSM the pre-pass of
+ * PYA_FLAG_SKIP_INVALID set aside: *status has its code; a shared spectrum without a scored PSM), n > cap (then *n says how
+ * many; mz and rank may be NULL with cap 0 to ask).  TEST-ONLY; no reference counterpart (BinnedSpectra keeps its windows
+ * private too: oracle/oracle_abi.h orc_binned is the checker's read-back). */
+int pya_debug_plan_retained_table(pya_plan *p, uint64_t index, float *mz, uint32_t *rank, uint64_t cap, uint64_t *n, int32_t *status);
+/* ... of the handle's retained plan (the last PYA_FLAG_KEEP batch, or the view pya_rescore_last_keep made of the last
+ * pya_score_one PSM); a handle that retains nothing: the workspace of the last pya_score_one call, index 0 (the one-PSM kernel
+ * stores its table whether the call retains or not, and also when the call failed with a binning status). */
+int pya_debug_retained_table(pya_handle *h, uint64_t index, float *mz, uint32_t *rank, uint64_t cap, uint64_t *n, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,8 @@ SYMBOLS = {
     "pya_set_debug": (C.c_int, [_vp, C.c_char_p, C.c_char_p]),          # include/pyascore_debug.h (test-only)
     "pya_debug_wave_ops": (C.c_int, [_vp, _vp, _vp]),         # (test-only)
     "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
+    "pya_debug_plan_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
+    "pya_debug_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
     "pya_score_one": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int32, C.c_int32, _vp, _vp, C.c_uint64,
                                 C.c_uint32, C.POINTER(Results)]),
     "pya_rescore_last_keep": (C.c_int, [_vp]),

@@ -357,4 +357,63 @@ int pya_debug_sort(pya_handle *h, const float *keys, uint32_t n, uint32_t *perm)
     return PYA_OK;
 }
 
+/* (include/pyascore_debug.h) the retained table the binning family left for one entry of a plan; p == NULL: the one-PSM
+ * workspace `d`, one table at offset 0 (the one-PSM view of pya_rescore_last_keep has no offsets of its own either) */
+static int debug_retained_table(pya_handle *h, const pya_plan *p, const BatchDev &d, hipStream_t last, uint64_t index, float *mz,
+                                uint32_t *rank, uint64_t cap, uint64_t *n, int32_t *status) {
+    *n = 0;
+    *status = PYA_ST_OK;
+    if (p && p->ret_off.empty()) p = nullptr;
+    const bool shared = p && p->shared;
+    const uint64_t entries = !p ? 1 : (shared ? p->n_spec : p->n_psm);
+    if (index >= entries)
+        return h->fail(PYA_ERR_ARG, -1, "retained table: entry %llu of %llu", (unsigned long long)index, (unsigned long long)entries);
+    int64_t off = 0;
+    if (p) {
+        /* an entry the binning family never saw has no table: a PSM the host pre-pass set aside (its code is the status), a
+         * shared spectrum whose PSMs were all set aside or that no PSM uses */
+        bool binned = false;
+        for (uint64_t i = shared ? 0 : index; i < (shared ? p->n_psm : index + 1); i++)
+            binned = binned || (p->spec(i) == index && !p->pre_status[i]);
+        if (!binned) {
+            if (!shared) *status = p->pre_status[index];
+            return h->fail(PYA_ERR_ARG, (int64_t)index, "retained table: entry %llu was not binned (set aside by the pre-pass, or a "
+                           "spectrum without PSMs)", (unsigned long long)index);
+        }
+        off = shared ? p->sret_off[index] : p->ret_off[index];
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipStreamSynchronize(last));
+    const uint32_t *d_n = shared ? p->d_sret_n.p : d.ret_n;
+    const int32_t *d_st = shared ? p->d_sstatus.p : d.status;
+    uint32_t rn = 0;
+    HIPCHK(h, hipMemcpy(&rn, d_n + index, sizeof rn, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(status, d_st + index, sizeof *status, hipMemcpyDeviceToHost));
+    *n = rn;
+    if (rn == 0) return PYA_OK;
+    if (rn > cap || !mz || !rank)
+        return h->fail(PYA_ERR_ARG, (int64_t)index, "retained table: %u entries, room for %llu", rn, (unsigned long long)cap);
+    std::vector<PeakEntry> e(rn);
+    HIPCHK(h, hipMemcpy(e.data(), d.ret + off, (size_t)rn * sizeof(PeakEntry), hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < rn; i++) {
+        mz[i] = e[i].mz;
+        rank[i] = e[i].rank;
+    }
+    return PYA_OK;
+}
+
+int pya_debug_plan_retained_table(pya_plan *p, uint64_t index, float *mz, uint32_t *rank, uint64_t cap, uint64_t *n, int32_t *status) {
+    if (!p || !n || !status) return PYA_ERR_ARG;
+    if (!p->ran) return p->h->fail(PYA_ERR_ARG, -1, "retained table: the plan has not run");
+    return debug_retained_table(p->h, p, p->dev, p->last_stream, index, mz, rank, cap, n, status);
+}
+
+int pya_debug_retained_table(pya_handle *h, uint64_t index, float *mz, uint32_t *rank, uint64_t cap, uint64_t *n, int32_t *status) {
+    if (!h || !n || !status) return PYA_ERR_ARG;
+    if (h->kept) return pya_debug_plan_retained_table(h->kept, index, mz, rank, cap, n, status);
+    if (!h->one.have_last || !h->one.ws.p)
+        return h->fail(PYA_ERR_ARG, -1, "retained table: nothing retained and no pya_score_one call yet");
+    return debug_retained_table(h, nullptr, h->one.dev, h->one.stream, index, mz, rank, cap, n, status);
+}
+
 } /* extern "C" */
