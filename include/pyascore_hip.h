@@ -22,6 +22,8 @@
  *   pya_format_peptide(s)         ModifiedPeptide::getPeptide         cpp/ModifiedPeptide.cpp:199-253
  *   pya_plan_*                    (new) device-resident variant of pya_score_batch for callers
  *                                 that keep spectra in HBM and own a HIP stream
+ *   pya_evidence / pya_plan_evidence /   what Ascore::calculateAmbiguity holds while it works and drops
+ *   pya_last_batch_evidence       (max_score_depth, ion_counts, ion_trials)      cpp/Ascore.cpp:157-210
  *
  * Conventions
  *   - plain pointers and sizes only; no C++ or framework types cross the boundary;
@@ -76,6 +78,9 @@ extern "C" {
 #define PYA_FLAG_SKIP_INVALID 4u /* a PSM that is invalid, exceeds a limit or is rejected by a  */
                             /* kernel does not fail the call: it gets best_score -1, n_sig -1, */
                             /* and its code in pya_last_batch_status(); the rest is scored      */
+#define PYA_FLAG_EVIDENCE 8u /* pya_score_batch*: the evidence records of every site as well       */
+                            /* (pya_last_batch_evidence); pya_plan_create*: the plan's runs take   */
+                            /* the per-stage launches whatever its size (pya_plan_evidence)        */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -85,6 +90,36 @@ extern "C" {
 #define PYA_PSM_TIED_OVERFLOW 4
 #define PYA_PSM_INVALID 16         /* unknown residue, empty spectrum, bad charge, ...           */
 #define PYA_PSM_OVER_LIMIT 17      /* beyond a documented limit (length, sites, C(n,k), peaks)   */
+
+/* What stands behind one Ascore: the depth it was taken at, the site-determining ions of the winning localisation and of
+ * the competitor it was measured against, and that competitor.  Ascore::calculateAmbiguity computes all of it and returns
+ * the one float (cpp/Ascore.cpp:157-210: max_score_depth :164-172, ion_counts / ion_trials :177-197); the reference never
+ * exposes the competitor's PepScore (AscoreContainer.pep_scores).  One record per (PSM, modified site of the winner), in the
+ * order of pya_results.ascores / alt_mask, row stride max_k.
+ *   The competitors of site j are the positions in alt_mask[j] (the single-move competitors that share the site's best
+ *   PepScore, Ascore.cpp:212-250); that PepScore is comp_score.
+ *   PYA_EV_TIED     it is within 1e-6 of the winner's: the reference returns 0 before it looks at an ion (:159-161); depth
+ *                   and counts are 0, comp_pos is the smallest alternative position.
+ *   PYA_EV_COUNTED  the row belongs to the competitor whose ambiguity IS ascores[j] (getAscores takes the minimum; among
+ *                   equal ones the smallest position), and
+ *                       score(depth, ref_possible, ref_matched) - score(depth, comp_possible, comp_matched)
+ *                   has the bit pattern of ascores[j], score(d, n, k) = |-10 log10 P(X >= k)|, X ~ Binomial(n, 2 mz_error
+ *                   (d + 1) / 100) in the reference's float chain (Ascore.cpp:28-33, :199-207).
+ *   PYA_EV_NONE     nothing to compare: ascores[j] is +inf, the PSM was not scored (status != 0, n_sig <= 0), or the column
+ *                   is >= the PSM's n_of_mod.  Every other field is 0.
+ * comp_pos is a 1-based peptide position for every peptide length (alt_mask switches to modifiable-residue bits above 64
+ * residues; this does not). */
+#define PYA_EV_NONE 0
+#define PYA_EV_COUNTED 1
+#define PYA_EV_TIED 2
+typedef struct pya_evidence {      /* 16 bytes */
+    float comp_score;              /* PepScore of the competitor */
+    uint16_t comp_pos;             /* 1-based peptide position the modification moves to; 0 = none */
+    uint8_t depth;                 /* 0-based peak depth the Ascore was taken at */
+    uint8_t kind;                  /* PYA_EV_* */
+    uint16_t ref_matched, ref_possible;    /* site-determining ions of the winner: matched at `depth`, all (ion_counts[0], ion_trials[0]) */
+    uint16_t comp_matched, comp_possible;  /* ... of the competitor (ion_counts[1], ion_trials[1]) */
+} pya_evidence;
 
 typedef struct pya_handle pya_handle;
 typedef struct pya_plan pya_plan;
@@ -133,7 +168,8 @@ int pya_add_neutral_loss(pya_handle *h, const char *group, float mass);
  * host memory the device reads directly, the PSM's scalars travel in the kernel's arguments, one wavefront runs
  * the whole path and writes the results straight back into pinned host memory.  Results as row 0 of `out`
  * (out->max_k <= 64).  flags: PYA_FLAG_KEEP retains the per-signature records at once; without it
- * pya_rescore_last_keep() retains them on demand (the properties only a few callers read).  Returns
+ * pya_rescore_last_keep() retains them on demand (the properties only a few callers read).  PYA_FLAG_EVIDENCE is
+ * refused with PYA_ERR_ARG: the evidence records come from the batch path (a batch of one with the flag).  Returns
  * PYA_ERR_STATE without an error message when the PSM needs the batch path (more than 8 fixed
  * modifications): call pya_score_batch then. */
 int pya_score_one(pya_handle *h, const double *mz, const double *intensity, uint64_t n_peaks, const uint8_t *peptide,
@@ -218,6 +254,12 @@ uint64_t pya_get_workspace_budget(const pya_handle *h);
  * that batch's n_psm.  All zeros unless PYA_FLAG_SKIP_INVALID let PSMs be set aside. */
 int pya_last_batch_status(pya_handle *h, int32_t *status, uint64_t n);
 
+/* The evidence records of the last pya_score_batch / _shared / _typed call on this handle that was given
+ * PYA_FLAG_EVIDENCE: out[n_psm * max_k], n_psm and max_k as in that call (anything else: PYA_ERR_ARG).  PYA_ERR_STATE when
+ * the last batch was scored without the flag.  The rows of a PSM that was set aside (PYA_FLAG_SKIP_INVALID) are all zero;
+ * rows do not depend on how the batch was cut into chunks.  What it answers for in the reference: see pya_evidence. */
+int pya_last_batch_evidence(pya_handle *h, pya_evidence *out, uint64_t n_psm, uint32_t max_k);
+
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
 /* the same for a batch whose PSMs share spectra (pya_score_batch_shared: batch->peak_off describes n_spectra spectra,
@@ -234,6 +276,14 @@ int pya_plan_run(pya_plan *plan, const double *d_mz, const double *d_intensity,
  * alignment of their element type only.  A typed run of a handful of PSMs takes the plan's launches (the one-launch kernel
  * for tiny batches reads float64).  No reference counterpart. */
 int pya_plan_run_typed(pya_plan *plan, const pya_typed_spectra *d_spectra, void *hip_stream, const pya_results *d_out);
+/* The evidence records (pya_evidence above; cpp/Ascore.cpp:157-210) of the results the last pya_plan_run* of this plan
+ * wrote: d_res is that run's results structure (device pointers), d_out device memory for n_psm * d_res->max_k records.
+ * Enqueues the evidence kernel (csrc/evidence.hip) on hip_stream, stream-ordered like pya_plan_run: it waits for that run
+ * -- the plan's side stream included when the run forked -- also when hip_stream is not the run's stream.  It reads the
+ * retained tables of the run, so it is valid until the plan is run again; it may be called more than once.  A run issues
+ * the launches it issues without this call, and no kernel of a run knows of it.  PYA_ERR_STATE when the plan has not been
+ * run.  PSMs the kernels rejected surface through pya_plan_check as they do for a run; their rows are all zero. */
+int pya_plan_evidence(pya_plan *plan, const pya_results *d_res, void *hip_stream, pya_evidence *d_out);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

@@ -3,7 +3,8 @@
 MI355X scorer: the files are read by :mod:`pyascore_amd.ingest`, every selected PSM is scored in ONE
 batched call (:func:`pyascore_amd.batch_cli.localize`) and the TSV of docs/source/cli.rst:135-180 is
 written.  ``--parameter_file`` takes ``name = value`` lines ('#' starts a comment); options on the
-command line override it.  ``--device`` (HIP ordinal) is the one addition."""
+command line override it.  ``--device`` (HIP ordinal) and ``--evidence`` (three more columns: what stands behind every
+Ascore) are the additions."""
 import argparse
 import re
 import sys
@@ -44,6 +45,9 @@ def build_parser():
     p.add_argument("--spec_file_type", type=str, default="mzML", help="mzML or mzXML")
     p.add_argument("--ident_file_type", type=str, default="pepXML", help="pepXML, mzIdentML, percolatorTXT or mokapotTXT")
     p.add_argument("--device", type=int, default=None, help="HIP device ordinal (default: LOCAL_RANK or 0)")
+    p.add_argument("--evidence", action="store_true",
+                   help="append Depth, SiteIons and CompScore: per site the peak depth of the Ascore, the site-determining ions "
+                        "matched/possible of the winner | of the competitor, and the competitor's PepScore")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -104,8 +108,9 @@ def run(args, log=print):
             ascore.add_neutral_loss(group, float(mass))
     rows = batch_cli.localize(ascore, psms, spectra, args.residues, args.mod_mass, args.hit_depth,
                               args.max_fragment_charge, args.mod_correction_tol, args.zero_based,
-                              match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)))
-    batch_cli.write_tsv(rows, args.out_file)
+                              match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
+                              evidence=args.evidence)
+    batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence)
     log("{} -- Ascore Completed".format(stamp()))
     return rows
 

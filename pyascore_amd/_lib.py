@@ -11,7 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYA_LIB") or os.path.join(_HERE, "libpyascore_hip.so")   # PYA_LIB: A/B builds
 
 PYA_OK, PYA_ERR_ARG, PYA_ERR_HIP, PYA_ERR_PSM, PYA_ERR_LIMIT, PYA_ERR_STATE = 0, -1, -2, -3, -4, -5
-PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID = 1, 2, 4
+PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID, PYA_FLAG_EVIDENCE = 1, 2, 4, 8
+PYA_EV_NONE, PYA_EV_COUNTED, PYA_EV_TIED = 0, 1, 2
 PYA_MAX_PEPTIDE_LEN = 511
 
 _vp = C.c_void_p
@@ -38,6 +39,18 @@ class TypedSpectra(C.Structure):
     """pya_typed_spectra: host (pya_score_batch_typed) or device (pya_plan_run_typed) arrays and their element types"""
     _fields_ = [("mz", _vp), ("intensity", _vp), ("mz_type", C.c_uint32), ("intensity_type", C.c_uint32)]
 
+
+class Evidence(C.Structure):
+    """pya_evidence: what stands behind one Ascore (depth, site-determining ion counts, the competitor)"""
+    _fields_ = [("comp_score", C.c_float), ("comp_pos", C.c_uint16), ("depth", C.c_uint8), ("kind", C.c_uint8),
+                ("ref_matched", C.c_uint16), ("ref_possible", C.c_uint16),
+                ("comp_matched", C.c_uint16), ("comp_possible", C.c_uint16)]
+
+
+assert C.sizeof(Evidence) == 16, "pya_evidence is a 16-byte record"
+# the same record as a numpy structured dtype (a view on the C buffer, no copy)
+EVIDENCE_DTYPE = [("comp_score", "<f4"), ("comp_pos", "<u2"), ("depth", "u1"), ("kind", "u1"),
+                  ("ref_matched", "<u2"), ("ref_possible", "<u2"), ("comp_matched", "<u2"), ("comp_possible", "<u2")]
 
 PYA_F64, PYA_F32 = 0, 1
 
@@ -74,6 +87,8 @@ SYMBOLS = {
     "pya_set_workspace_budget": (C.c_int, [_vp, C.c_uint64]),
     "pya_get_workspace_budget": (C.c_uint64, [_vp]),
     "pya_last_batch_status": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "pya_last_batch_evidence": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32]),
+    "pya_plan_evidence": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp]),
     "pya_plan_create": (C.c_int, [_vp, C.POINTER(Batch), C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_create_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_run": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Results)]),

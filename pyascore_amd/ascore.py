@@ -69,6 +69,8 @@ try:                                  # the compiled way into pya_score_one (csr
 except ImportError:                   # not built for this interpreter
     _fast = None
 
+EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)      # pya_evidence, 16 bytes
+assert EVIDENCE_DTYPE.itemsize == 16
 _NO_U32 = np.zeros(0, np.uint32)
 _NO_F32 = np.zeros(0, np.float32)
 
@@ -218,7 +220,7 @@ class PyAscore:
                 self._batch_n = None
                 self._last = _Last(peptide=peptide, k=r[6], aux_pos=aux_mod_pos.copy() if have_aux else _NO_U32,
                                    aux_mass=aux_mod_mass.copy() if have_aux else _NO_F32, best_score=r[1], best_sig=r[2],
-                                   n_sig=r[3], _asc=r[4], _alt=r[5], lazy=True)
+                                   n_sig=r[3], _asc=r[4], _alt=r[5], lazy=True, mz=mz_arr, it=int_arr, z=max_fragment_charge)
                 return
             # (an error code, or PYA_ERR_STATE = "not for the one-PSM kernel": the way below handles both)
         mz_arr = _check_f64("mz_arr", mz_arr)
@@ -287,7 +289,7 @@ class PyAscore:
         self._last = dict(pep=pep, peptide=peptide, k=int(n_of_mod), aux_pos=ap.copy(), aux_mass=am.copy(),
                           best_score=float(one["best_score"][0]), best_sig=int(one["best_sig"][0]),
                           n_sig=int(one["n_sig"][0]), ascores=one["ascores"][0].copy(),
-                          alt_mask=one["alt_mask"][0].copy(), lazy=lazy)
+                          alt_mask=one["alt_mask"][0].copy(), lazy=lazy, mz=mz_arr, it=int_arr, z=int(max_fragment_charge))
 
     def _ensure_kept(self):
         """Retains the per-signature records of the last ``score()`` PSM (its inputs are still where
@@ -303,7 +305,7 @@ class PyAscore:
             last["lazy"] = False
             self._batch_n = 1
 
-    def score_batch(self, batch, keep=False, skip_invalid=False):
+    def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -314,6 +316,12 @@ class PyAscore:
         a documented limit of this implementation does not fail the call; it gets best_score -1,
         n_sig -1 and a non-zero code in the extra ``status`` array (include/pyascore_hip.h PYA_PSM_*),
         and ``status_message`` describes the first such PSM.
+
+        ``evidence=True`` adds ``evidence``: a structured array ``[n, max_k]`` (``EVIDENCE_DTYPE``, the 16-byte
+        ``pya_evidence`` of include/pyascore_hip.h) with what stands behind every Ascore -- the peak depth it was taken at,
+        the site-determining ions possible and matched for the winner and for the competitor, the competitor's position and
+        PepScore (``kind``: 0 nothing to compare, 1 counted, 2 the competitor ties the winner).  Every other result is what
+        it is without the option.
 
         Shared spectra: a batch dict with ``spec_of`` (and ``n_spectra``; ``synth.pack_shared_batch``) holds every
         spectrum once, ``peak_off`` describes the spectra and PSM i is scored against spectrum ``spec_of[i]`` -- the hits
@@ -332,10 +340,10 @@ class PyAscore:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
-                return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid)
+                return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence)
             if perm is not None:
                 try:
-                    res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid)
+                    res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
@@ -372,6 +380,8 @@ class PyAscore:
                    n_sig=np.zeros(n, np.int32), ascores=np.zeros((n, max_k), np.float32),
                    alt_mask=np.zeros((n, max_k), np.uint64))
         if n == 0:
+            if evidence:
+                out["evidence"] = np.zeros((0, max_k), EVIDENCE_DTYPE)
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -393,7 +403,8 @@ class PyAscore:
                 lazy_keep = float(per_psm.sum()) > 0.8 * budget
             except (IndexError, ValueError):
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
-        flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0)
+        flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
+            (_lib.PYA_FLAG_EVIDENCE if evidence else 0)
         rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r)
         if rc:
             self._raise(rc)
@@ -414,6 +425,11 @@ class PyAscore:
                 self._raise(rc)
             out["status_message"] = (self._lib.pya_last_error(self._h).decode("utf8", "replace")
                                      if out["status"].any() else "")
+        if evidence:
+            out["evidence"] = np.zeros((n, max_k), EVIDENCE_DTYPE)
+            rc = self._lib.pya_last_batch_evidence(self._h, _as_ptr(out["evidence"]), n, max_k)
+            if rc:
+                self._raise(rc)
         return out
 
     def _score_batch_call(self, b, spec_of, n_spec, mz, it, flags, r):
@@ -591,6 +607,37 @@ class PyAscore:
         if self._last is None:
             return np.zeros(0, np.float32)
         return self._last["ascores"][: self._last["k"]].astype(np.float32)
+
+    @property
+    def evidence(self):
+        """What stands behind the Ascores of the last ``score()`` PSM: one ``EVIDENCE_DTYPE`` record per modified site
+        (see ``score_batch(evidence=True)``).  Produced the first time it is read, by sending that PSM -- the arrays
+        ``score()`` was given -- through the batch path as a batch of one; ``score()`` itself does nothing for it."""
+        last = self._last
+        if last is None:
+            return np.zeros(0, EVIDENCE_DTYPE)
+        if "evidence" not in last:
+            mz, it = _check_f64("mz_arr", last["mz"]), _check_f64("int_arr", last["it"])
+            pep, ap, am = last["pep"], np.ascontiguousarray(last["aux_pos"], np.uint32), np.ascontiguousarray(last["aux_mass"], np.float32)
+            k = max(1, int(last["k"]))
+            off = {name: np.array([0, v], np.int64) for name, v in (("peak", mz.size), ("pep", pep.size), ("aux", ap.size))}
+            kz = np.array([int(last["k"])], np.int32), np.array([int(last["z"])], np.int32)
+            res = (np.zeros(1, np.float32), np.zeros(1, np.uint64), np.zeros(1, np.int32), np.zeros((1, k), np.float32),
+                   np.zeros((1, k), np.uint64))
+            b = _lib.Batch(1, _as_ptr(off["peak"]), _as_ptr(pep), _as_ptr(off["pep"]), _as_ptr(kz[0]), _as_ptr(kz[1]),
+                           _as_ptr(ap), _as_ptr(am), _as_ptr(off["aux"]))
+            r = _lib.Results(k, *[_as_ptr(a) for a in res])
+            # (no PYA_FLAG_KEEP: the plan path leaves the staging and the retained records of score()'s PSM alone)
+            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), _lib.PYA_FLAG_EVIDENCE, C.byref(r))
+            ev = np.zeros((1, k), EVIDENCE_DTYPE)
+            if not rc:
+                rc = self._lib.pya_last_batch_evidence(self._h, _as_ptr(ev), 1, k)
+            if rc:
+                self._raise(rc)
+            if int(res[1][0]) != int(last["best_sig"]):
+                raise RuntimeError("the arrays passed to score() changed before evidence was read")
+            last["evidence"] = ev[0]
+        return last["evidence"][: last["k"]].copy()
 
     @property
     def alt_sites(self):

@@ -20,6 +20,8 @@ from .ascore import PyAscore
 from .synth import pack_batch, pack_shared_batch
 
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
+# ``--evidence``: what stands behind every Ascore (pya_evidence), one entry per modified site like Ascores
+EVIDENCE_COLUMNS = ("Depth", "SiteIons", "CompScore")
 
 
 def process_mods(residues, mod_mass, sequence, positions, masses, mod_correction_tol=1.0,
@@ -112,11 +114,12 @@ def pack_hits(picked, scans):
 
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
-             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None):
+             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
-    nan -- and are reported through ``log`` (a callable taking one string) with their count, scans and codes."""
+    nan -- and are reported through ``log`` (a callable taking one string) with their count, scans and codes.
+    ``evidence=True`` appends three fields per row, ';'-joined per site (``evidence_fields``): Depth, SiteIons, CompScore."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     picked, scans = select_psms(psms, spectra_map, residues, mod_mass, hit_depth, max_fragment_charge,
@@ -127,7 +130,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     # One PSM the kernels cannot take (longer than 64 residues, more than 15 000 site assignments,
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.
-    res = ascore.score_batch(batch, skip_invalid=True)
+    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence)
     bad = np.flatnonzero(res["status"])
     if bad.size:
         import warnings
@@ -143,20 +146,37 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     rows = []
     for i, psm in enumerate(picked):
         if res["status"][i]:
-            rows.append([scans[i], "", float("nan"), "", ""])
+            rows.append([scans[i], "", float("nan"), "", ""] + (["", "", ""] if evidence else []))
             continue
         k = psm["n_of_mod"]
         ascores = ";".join(str(s) for s in res["ascores"][i, :k])
         alts = ";".join(",".join(str(q) for q in ascore.alt_positions(m, psm["peptide"].encode("utf8")))
                         for m in res["alt_mask"][i, :k])
-        rows.append([scans[i], seqs[i], float(res["best_score"][i]), ascores, alts])
+        rows.append([scans[i], seqs[i], float(res["best_score"][i]), ascores, alts] +
+                    (evidence_fields(res["evidence"][i, :k]) if evidence else []))
     return rows
 
 
-def write_tsv(rows, path):
+def evidence_fields(ev):
+    """The three ``--evidence`` fields of one PSM from its evidence records (one per modified site): Depth -- the peak
+    depth the Ascore was taken at, 1-based as a user counts the peaks of a window; SiteIons -- ``matched/possible`` of
+    the winner, ``|``, the same of the competitor, or ``tie`` where the competitor's PepScore ties the winner's;
+    CompScore -- the competitor's PepScore.  A site with nothing to compare (kind 0) has empty entries."""
+    depth, ions, comp = [], [], []
+    for e in ev:
+        kind = int(e["kind"])
+        depth.append(str(int(e["depth"]) + 1) if kind == 1 else "")
+        ions.append("%d/%d|%d/%d" % (e["ref_matched"], e["ref_possible"], e["comp_matched"], e["comp_possible"]) if kind == 1
+                    else ("tie" if kind == 2 else ""))
+        comp.append(str(e["comp_score"]) if kind else "")
+    return [";".join(depth), ";".join(ions), ";".join(comp)]
+
+
+def write_tsv(rows, path, evidence=False):
     """Same file pandas' ``DataFrame(rows, columns=COLUMNS).to_csv(path, sep="\\t", index=False)``
-    writes in the reference (`__main__.py:166-172`)."""
+    writes in the reference (`__main__.py:166-172`); ``evidence=True``: the rows of ``localize(..., evidence=True)``,
+    with their three columns behind the reference's."""
     with open(path, "w") as out:
-        out.write("\t".join(COLUMNS) + "\n")
-        for scan, seq, pep_score, ascores, alts in rows:
-            out.write("%s\t%s\t%s\t%s\t%s\n" % (scan, seq, repr(float(pep_score)), ascores, alts))
+        out.write("\t".join(COLUMNS + (EVIDENCE_COLUMNS if evidence else ())) + "\n")
+        for scan, seq, pep_score, ascores, alts, *more in rows:
+            out.write("\t".join(["%s" % scan, "%s" % seq, repr(float(pep_score)), ascores, alts] + list(more)) + "\n")

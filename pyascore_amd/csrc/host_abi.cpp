@@ -60,6 +60,7 @@ void pya_destroy(pya_handle *h) {
     if (h->one.stream) (void)hipStreamDestroy(h->one.stream);
     for (void *ps : h->pinned_stage)
         if (ps) (void)hipHostFree(ps);
+    if (h->evid_host) (void)hipHostFree(h->evid_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->run_stream) (void)hipStreamDestroy(h->run_stream);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
@@ -225,6 +226,16 @@ int pya_last_batch_status(pya_handle *h, int32_t *status, uint64_t n) {
     }
     if (n != h->last_status.size()) return h->fail(PYA_ERR_ARG, -1, "the last batch had %zu PSMs", h->last_status.size());
     std::memcpy(status, h->last_status.data(), n * sizeof(int32_t));
+    return PYA_OK;
+}
+
+int pya_last_batch_evidence(pya_handle *h, pya_evidence *out, uint64_t n_psm, uint32_t max_k) {
+    if (!h) return PYA_ERR_ARG;
+    if (!h->evid_valid) return h->fail(PYA_ERR_STATE, -1, "the last batch was scored without PYA_FLAG_EVIDENCE");
+    if (n_psm != h->evid_n || max_k != h->evid_k)
+        return h->fail(PYA_ERR_ARG, -1, "the last batch had %llu PSMs and rows of %u", (unsigned long long)h->evid_n, h->evid_k);
+    if (!out && n_psm * max_k != 0) return h->fail(PYA_ERR_ARG, -1, "NULL evidence array");
+    if (n_psm * max_k != 0) std::memcpy(out, h->evid_host, (size_t)n_psm * max_k * sizeof(pya_evidence));
     return PYA_OK;
 }
 

@@ -84,6 +84,35 @@ void rebase_error(pya_handle *h, uint64_t lo) {
 
 }  // namespace
 
+/* PYA_FLAG_EVIDENCE: the evidence launch of a plan behind its kernels on `st`, and its rows on their way into the handle's
+ * pinned block at PSM `lo` (asynchronous: whoever waits for the chunk's results waits for them too) */
+static int evidence_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, uint64_t lo, hipStream_t st) {
+    const size_t n_rec = (size_t)p->n_psm * d_out->max_k;
+    if (n_rec == 0) return PYA_OK;
+    HIPCHK(h, p->d_evid.alloc(n_rec));
+    const int rc = pya_plan_evidence(p, d_out, st, p->d_evid.p);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->evid_host + lo * d_out->max_k, p->d_evid.p, n_rec * sizeof(pya_evidence), hipMemcpyDeviceToHost, st));
+    return PYA_OK;
+}
+
+/* the handle's block for the rows of a batch of n PSMs (zeroed: a PSM no plan reaches has PYA_EV_NONE rows) */
+static int evidence_host_block(pya_handle *h, uint64_t n, uint32_t mk) {
+    const size_t n_rec = (size_t)n * mk;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->evid_cap < n_rec) {
+        if (h->evid_host) (void)hipHostFree(h->evid_host);
+        h->evid_host = nullptr;
+        h->evid_cap = 0;
+        HIPCHK(h, hipHostMalloc((void **)&h->evid_host, std::max<size_t>(n_rec, 1) * sizeof(pya_evidence), hipHostMallocDefault));
+        h->evid_cap = std::max<size_t>(n_rec, 1);
+    }
+    std::memset(h->evid_host, 0, n_rec * sizeof(pya_evidence));
+    h->evid_n = n;
+    h->evid_k = mk;
+    return PYA_OK;
+}
+
 /* Big pya_score_batch calls: the batch is cut into chunks of consecutive PSMs that fit the device
  * budget and the chunks are pipelined -- a helper thread streams the spectra of chunk c + 1 over
  * PCIe (the bound of this entry point: 16, 12 or 8 bytes per peak) into the other slot of a two-slot ring
@@ -207,6 +236,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         unsigned char *sg = (unsigned char *)pin;
         hipError_t e = hipMemcpyAsync(sg, p->arena.p + p->o_status, p->d2h_bytes, hipMemcpyDeviceToHost, h->run_stream);
         if (e != hipSuccess) return finish(h->hip_fail(e, "results copy"));
+        if ((flags & PYA_FLAG_EVIDENCE) && (rc = evidence_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -247,6 +277,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         std::memcpy(out->alt_mask + lo * mk, sg + (p->o_alt - o), n * mk * sizeof(uint64_t));
         cur = std::move(next);
     }
+    h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
     return finish(PYA_OK);
 }
 
@@ -257,7 +288,13 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     const void *mz = sp.mz, *inten = sp.intensity;
     h->last_status.clear();
     h->last_chunks = 1;
-    if (b->n_psm == 0) return PYA_OK;
+    h->evid_valid = false;
+    if (b->n_psm == 0) {
+        h->evid_n = 0;
+        h->evid_k = out->max_k;
+        h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
+        return PYA_OK;
+    }
     uint32_t types = 0;
     const int rc_types = spectra_types(h, &sp, "pya_score_batch_typed", &types);
     if (rc_types) return rc_types;
@@ -271,7 +308,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     /* (not while the records of a pya_score_one PSM are retained in the one-PSM workspace: this call would overwrite
      * what pya_get_pep_scores / pya_calculate_ambiguity still read there) */
     const bool one_view_live = h->kept && h->kept == h->one.view;
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING)) && !one_view_live && types == PYA_SPEC_F64_F64) {
+    if (flags & PYA_FLAG_EVIDENCE) {
+        const int rc_ev = evidence_host_block(h, b->n_psm, out->max_k);
+        if (rc_ev) return rc_ev;
+    }
+    /* (a batch of one with PYA_FLAG_EVIDENCE takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE)) && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -388,6 +430,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         HIPCHK(h, hipMemcpy(out->ascores, p->d_ascores.p, n * mk * sizeof(float), hipMemcpyDeviceToHost));
         HIPCHK(h, hipMemcpy(out->alt_mask, p->d_alt.p, n * mk * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
+    if (flags & PYA_FLAG_EVIDENCE) {
+        if ((rc = evidence_behind_run(h, p, &d_out, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        h->evid_valid = true;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -406,7 +453,8 @@ int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const d
 static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const pya_typed_spectra &sp,
                               uint32_t flags, const pya_results *out) {
     h->last_status.clear();
-    if (b->n_psm == 0) return PYA_OK;
+    h->evid_valid = false;
+    if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
     if (rc) return rc;

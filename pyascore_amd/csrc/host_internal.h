@@ -115,6 +115,9 @@ int pya_launch_general(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids,
 int pya_launch_general_ambiguity(const BatchDev *b, uint32_t psm, uint32_t l_cap, uint32_t list_cap, uint64_t ref_bits,
                                  uint64_t oth_bits, const float *d_scores, uint32_t n_scores, float ref_ws, float oth_ws,
                                  float *d_out, hipStream_t stream);
+size_t pya_evidence_lds_bytes(uint32_t l_cap, uint32_t list_cap);
+int pya_launch_evidence(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, void *d_out, uint32_t l_cap, uint32_t list_cap,
+                        hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -304,6 +307,13 @@ struct pya_handle {
     std::string err;
     int64_t err_index = -1;
     std::vector<int32_t> last_status;         /* per-PSM codes of the last pya_score_batch */
+    /* PYA_FLAG_EVIDENCE: the records of the last pya_score_batch, pinned so that a chunk's rows come back asynchronously
+     * behind its results (pya_last_batch_evidence copies them out) */
+    pya_evidence *evid_host = nullptr;
+    size_t evid_cap = 0;                      /* records the block has room for */
+    uint64_t evid_n = 0;                      /* PSMs of the batch they belong to */
+    uint32_t evid_k = 0;                      /* its row stride */
+    bool evid_valid = false;                  /* the last batch was scored with the flag */
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -604,6 +614,14 @@ struct pya_plan {
     hipStream_t side = nullptr;          /* the handle's (pya_handle::side_stream: created once, plans share it) */
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipStream_t last_stream = nullptr;
+    /* pya_plan_evidence: the launch caps of the PSMs inside the fast limits (their longest peptide and fragment list, for
+     * the loss sums the handle had then) and, when the plan has general PSMs too, the list of the others; the records of a
+     * pya_score_batch plan; the event a call on another stream than the run's waits for */
+    bool evid_caps = false;
+    uint32_t evid_uniq = 0, evid_l_cap = 1, evid_list_cap = 1, evid_n_fast = 0;
+    DevBuf<uint32_t> d_evid_ids;
+    DevBuf<pya_evidence> d_evid;
+    hipEvent_t ev_evid = nullptr;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -613,6 +631,7 @@ struct pya_plan {
             if (e) (void)hipEventDestroy(e);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
+        if (ev_evid) (void)hipEventDestroy(ev_evid);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
@@ -722,5 +741,6 @@ int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const Io
 int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid = false);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
+static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");
 
 #endif

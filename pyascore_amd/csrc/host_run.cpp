@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & PYA_FLAG_TIMING) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -429,6 +429,71 @@ int pya_plan_check(pya_plan *p) {
     const bool skip = (p->flags & PYA_FLAG_SKIP_INVALID) != 0;
     if (skip) h->last_status = st;
     return check_status(h, st.data(), p->n_psm, skip);
+}
+
+/* The evidence stage: one launch for the PSMs inside the fast limits, sized by THEIR longest peptide and fragment list,
+ * one for the plan's general PSMs with the general kernel's caps (a single 400-residue peptide must not set the LDS, hence
+ * the occupancy, of a batch of 20-mers). */
+int pya_plan_evidence(pya_plan *p, const pya_results *r, void *hip_stream, pya_evidence *d_out) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_evidence: the plan has not been run");
+    if (!d_out || !r->best_score || !r->best_sig || !r->n_sig || !r->ascores || !r->alt_mask)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_evidence");
+    if (r->max_k < p->max_k)
+        return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)", r->max_k, p->max_k);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const uint32_t n_uniq = (uint32_t)h->cfg.n_uniq;
+    if (!p->evid_caps || p->evid_uniq != n_uniq) {
+        std::vector<uint32_t> fast_ids;
+        uint32_t l_cap = 1, list_cap = 1;
+        const bool listed = !p->gen_ids.empty();
+        for (uint64_t i = 0; i < p->n_psm; i++) {
+            if (!p->gen.empty() && p->gen[i]) continue;
+            if (listed) fast_ids.push_back((uint32_t)i);
+            if (!p->pre_status.empty() && p->pre_status[i]) continue;       /* (set aside: nothing of it is read) */
+            const int64_t L = p->pep_off[i + 1] - p->pep_off[i];
+            if (L < 1 || L > PYA_MAX_PEPTIDE_LEN || p->max_charge[i] < 1) continue;
+            l_cap = std::max(l_cap, (uint32_t)L);
+            list_cap = std::max(list_cap, (uint32_t)(L - 1) * (uint32_t)p->max_charge[i] * n_uniq);
+        }
+        p->evid_n_fast = listed ? (uint32_t)fast_ids.size() : (uint32_t)p->n_psm;
+        if (listed && !fast_ids.empty()) {
+            /* (a blocking copy: the vector does not outlive this call) */
+            HIPCHK(h, p->d_evid_ids.alloc(fast_ids.size()));
+            HIPCHK(h, hipMemcpy(p->d_evid_ids.p, fast_ids.data(), fast_ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        }
+        p->evid_l_cap = l_cap;
+        p->evid_list_cap = list_cap;
+        p->evid_uniq = n_uniq;
+        p->evid_caps = true;
+    }
+    if (pya_evidence_lds_bytes(p->evid_l_cap, p->evid_list_cap) > kMaxLds ||
+        (!p->gen_ids.empty() && pya_evidence_lds_bytes(p->gen_l_cap, p->gen_list_cap) > kMaxLds))
+        return h->fail(PYA_ERR_LIMIT, -1, "pya_plan_evidence: %u fragments per ion type exceed the evidence kernel's room",
+                       std::max(p->evid_list_cap, p->gen_ids.empty() ? 0u : p->gen_list_cap));
+    /* behind the run: its stream has joined the side stream already (pya_plan_run_typed); another stream waits for it */
+    if (st != p->last_stream) {
+        if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
+        HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
+    }
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.best_score = r->best_score;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    d.ascores = r->ascores;
+    d.alt_mask = r->alt_mask;
+    d.max_k = r->max_k;
+    int e = pya_launch_evidence(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, d_out, p->evid_l_cap,
+                                p->evid_list_cap, st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_evidence(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_out, p->gen_l_cap, p->gen_list_cap, st);
+    if (e) return h->hip_fail((hipError_t)e, "evidence launch");
+    return PYA_OK;
 }
 
 int pya_pack_records(pya_handle *h, const pya_results *d_res, uint64_t n_psm, uint32_t k, int32_t *d_out, void *hip_stream) {

@@ -19,9 +19,12 @@ class DevicePlan:
     ``peak_off`` says (a batch with ``spec_of``: the spectra's, each held once and shared by its PSMs,
     which must be consecutive).  ``run()`` enqueues the three kernels on torch's current stream and
     returns the result tensors (device).  ``max_k`` widens the per-site result rows beyond this
-    batch's own largest n_of_mod: ranks that gather fixed-size records pass the job-wide value."""
+    batch's own largest n_of_mod: ranks that gather fixed-size records pass the job-wide value.
+    ``evidence()`` after ``run()`` gives the evidence records of every site (``pya_plan_evidence``); ``evidence=True``
+    tells the plan at creation that they will be asked for (a plan of a handful of PSMs then takes the per-stage
+    launches instead of the one-launch kernel)."""
 
-    def __init__(self, scorer, batch, timing=False, max_k=None):
+    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -49,7 +52,7 @@ class DevicePlan:
                        _as_ptr(m["n_of_mod"]), _as_ptr(m["max_charge"]), _as_ptr(m["aux_pos"]),
                        _as_ptr(m["aux_mass"]), _as_ptr(m["aux_off"]))
         self._plan = C.c_void_p()
-        flags = _lib.PYA_FLAG_TIMING if timing else 0
+        flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -111,6 +114,23 @@ class DevicePlan:
             self.scorer._raise(rc)
         return self
 
+    def evidence(self, out=None):
+        """The evidence records of the last ``run()`` as a ``torch.uint8`` device tensor ``[n_psm, max_k, 16]`` (one
+        16-byte ``pya_evidence`` per modified site, rows as ``ascores``): ONE launch family of the library behind the run,
+        on torch's current stream.  Valid for the results of the last run; ``evidence_rows`` turns a host copy into the
+        structured array."""
+        torch = self._torch
+        shape = (self.n_psm, self.max_k, 16)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous uint8 device tensor of shape %r" % (shape,))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_plan_evidence(self._plan, C.byref(self._res), stream, out.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return out
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -153,6 +173,18 @@ class DevicePlan:
         if rc:
             self.scorer._raise(rc)
         return out
+
+
+EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)
+
+
+def evidence_rows(raw):
+    """A host copy of ``DevicePlan.evidence()`` (``.cpu().numpy()``, uint8 ``[n_psm, max_k, 16]``) as the structured
+    array ``[n_psm, max_k]`` that ``PyAscore.score_batch(..., evidence=True)`` returns; a view, no copy."""
+    a = np.ascontiguousarray(raw, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != EVIDENCE_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n_psm, max_k, %d)" % EVIDENCE_DTYPE.itemsize)
+    return a.view(EVIDENCE_DTYPE).reshape(a.shape[0], a.shape[1])
 
 
 def unpack_summary(packed, max_k):
