@@ -24,6 +24,9 @@
  *                                 that keep spectra in HBM and own a HIP stream
  *   pya_evidence / pya_plan_evidence /   what Ascore::calculateAmbiguity holds while it works and drops
  *   pya_last_batch_evidence       (max_score_depth, ion_counts, ion_trials)      cpp/Ascore.cpp:157-210
+ *   pya_ion / pya_plan_ions_count /      the matched fragments of the best localisation and the site-determining ions
+ *   pya_plan_ions / pya_last_batch_ions  of every counted pair, one record per ion (per PSM: ModifiedPeptide::getMatch,
+ *                                 getSiteDeterminingIons, FragmentGraph)         cpp/ModifiedPeptide.cpp:126-150, :259-320
  *
  * Conventions
  *   - plain pointers and sizes only; no C++ or framework types cross the boundary;
@@ -81,6 +84,9 @@ extern "C" {
 #define PYA_FLAG_EVIDENCE 8u /* pya_score_batch*: the evidence records of every site as well       */
                             /* (pya_last_batch_evidence); pya_plan_create*: the plan's runs take   */
                             /* the per-stage launches whatever its size (pya_plan_evidence)        */
+#define PYA_FLAG_IONS 16u   /* pya_score_batch*: the ion records of every PSM as well              */
+                            /* (pya_last_batch_ions); pya_plan_create*: as PYA_FLAG_EVIDENCE       */
+                            /* (pya_plan_ions_count / pya_plan_ions)                               */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -120,6 +126,42 @@ typedef struct pya_evidence {      /* 16 bytes */
     uint16_t ref_matched, ref_possible;    /* site-determining ions of the winner: matched at `depth`, all (ion_counts[0], ion_trials[0]) */
     uint16_t comp_matched, comp_possible;  /* ... of the competitor (ion_counts[1], ion_trials[1]) */
 } pya_evidence;
+
+/* Which ions stand behind a PSM: one record per ion, the records of a PSM in one range (ion_off[psm] .. ion_off[psm + 1])
+ * of two sections.
+ *   1. The winner's annotation (site == PYA_ION_WINNER): every theoretical fragment of the best localisation that has a
+ *      match among the retained peaks -- one record per fragment Ascore::accumulateCounts visits (cpp/Ascore.cpp:53-121:
+ *      every ion type of the scorer, charges 1 .. max_charge, neutral-loss variants; two fragments of one m/z are two
+ *      records).  The match is ModifiedPeptide::consumePeak's (cpp/ModifiedPeptide.cpp:126-142, the mz - .5 lower bound for
+ *      mz_error > 0.49 included): the lowest rank inside the open window and, among equal ranks, the lowest m/z.  Fragments
+ *      without a match are not listed.  The number of records with rank <= d is the winner's count at depth d (pep_scores).
+ *      PYA_ION_COUNTED is never set here (there is no row and no depth).
+ *   2. Site-determining ions, for every column j of ascores / evidence whose evidence row is PYA_EV_COUNTED: the two lists
+ *      that survive the greedy walk (cpp/ModifiedPeptide.cpp:259-320) of the winner against that row's competitor
+ *      (comp_pos), matched or not (rank 255, peak_mz 0 when not).  There are ref_possible records of the winner, of which
+ *      ref_matched carry PYA_ION_COUNTED, and comp_possible / comp_matched of the competitor (PYA_ION_COMP).  PYA_EV_TIED
+ *      and PYA_EV_NONE columns have no records.
+ * PSMs that were set aside or rejected have no records; a PSM without a competing localisation has section 1 only.
+ * Order (fixed: two runs, every route and every cut into chunks give the same bytes).  Section 1: N-terminal ion types (b, c)
+ * before C-terminal ones (y, z, Z); inside a direction blocks of 64 consecutive fragment sizes, inside a block by loss sum
+ * (none first, then ascending), ion type in the scorer's order, charge, size.  Section 2: column after column; inside a
+ * column the winner's records, then the competitor's; inside a side ion type after ion type in the scorer's order, ascending
+ * theo_mz inside a type (equal m/z: size, loss sum, charge). */
+#define PYA_ION_WINNER 255   /* pya_ion.site of section 1 */
+#define PYA_ION_LOSS 1       /* pya_ion.flags: a neutral-loss variant */
+#define PYA_ION_COMP 2       /* ... belongs to the competitor's list (else the winner's) */
+#define PYA_ION_COUNTED 4    /* ... matched with rank <= the row's depth */
+typedef struct pya_ion {     /* 16 bytes, one store */
+    float theo_mz;           /* the fragment's m/z as the float32 the reference keys its match cache by */
+    float peak_mz;           /* the retained peak it matched ((float)mz of the table); 0 when none */
+    uint16_t size;           /* residues in the fragment, 1 .. L-1 */
+    uint8_t type;            /* 'b' 'y' 'c' 'z' 'Z' */
+    uint8_t charge;
+    uint8_t rank;            /* 0-based rank of that peak in its window = first depth it counts at; 255: no match */
+    uint8_t site;            /* PYA_ION_WINNER, or the column j of ascores / evidence the ion is site-determining for */
+    uint8_t flags;           /* PYA_ION_* */
+    uint8_t reserved;        /* 0 */
+} pya_ion;
 
 typedef struct pya_handle pya_handle;
 typedef struct pya_plan pya_plan;
@@ -168,8 +210,8 @@ int pya_add_neutral_loss(pya_handle *h, const char *group, float mass);
  * host memory the device reads directly, the PSM's scalars travel in the kernel's arguments, one wavefront runs
  * the whole path and writes the results straight back into pinned host memory.  Results as row 0 of `out`
  * (out->max_k <= 64).  flags: PYA_FLAG_KEEP retains the per-signature records at once; without it
- * pya_rescore_last_keep() retains them on demand (the properties only a few callers read).  PYA_FLAG_EVIDENCE is
- * refused with PYA_ERR_ARG: the evidence records come from the batch path (a batch of one with the flag).  Returns
+ * pya_rescore_last_keep() retains them on demand (the properties only a few callers read).  PYA_FLAG_EVIDENCE and
+ * PYA_FLAG_IONS are refused with PYA_ERR_ARG: those records come from the batch path (a batch of one with the flag).  Returns
  * PYA_ERR_STATE without an error message when the PSM needs the batch path (more than 8 fixed
  * modifications): call pya_score_batch then. */
 int pya_score_one(pya_handle *h, const double *mz, const double *intensity, uint64_t n_peaks, const uint8_t *peptide,
@@ -260,6 +302,14 @@ int pya_last_batch_status(pya_handle *h, int32_t *status, uint64_t n);
  * rows do not depend on how the batch was cut into chunks.  What it answers for in the reference: see pya_evidence. */
 int pya_last_batch_evidence(pya_handle *h, pya_evidence *out, uint64_t n_psm, uint32_t max_k);
 
+/* The ion records (pya_ion above) of the last pya_score_batch / _shared / _typed call on this handle that was given
+ * PYA_FLAG_IONS, with the size-query convention of pya_get_pep_scores_range: ion_off[n_psm + 1] always (n_psm of that
+ * batch; ion_off[n_psm] = the number of records), the records when cap is not 0 -- cap below that number: PYA_ERR_ARG.
+ * PYA_ERR_STATE when the last batch was scored without the flag.  The records do not depend on how the batch was cut into
+ * chunks.  The flag makes the library compute the evidence rows it needs; pya_last_batch_evidence still answers only when
+ * PYA_FLAG_EVIDENCE was given. */
+int pya_last_batch_ions(pya_handle *h, int64_t *ion_off, pya_ion *out, uint64_t cap);
+
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
 /* the same for a batch whose PSMs share spectra (pya_score_batch_shared: batch->peak_off describes n_spectra spectra,
@@ -284,6 +334,18 @@ int pya_plan_run_typed(pya_plan *plan, const pya_typed_spectra *d_spectra, void 
  * the launches it issues without this call, and no kernel of a run knows of it.  PYA_ERR_STATE when the plan has not been
  * run.  PSMs the kernels rejected surface through pya_plan_check as they do for a run; their rows are all zero. */
 int pya_plan_evidence(pya_plan *plan, const pya_results *d_res, void *hip_stream, pya_evidence *d_out);
+/* The ion records (pya_ion above) of the results the last pya_plan_run* of this plan wrote, in two stream-ordered steps
+ * without a host synchronisation inside (csrc/ions.hip); d_res as for pya_plan_evidence, and the same validity: until the
+ * plan is run again; both wait for the run, its side stream included.  PYA_ERR_STATE before the first run.
+ *   pya_plan_ions_count  the count kernel and an exclusive scan on the device: d_ion_off[n_psm + 1], d_ion_off[n_psm] = the
+ *                        number of records.  The caller reads that number in its own time and allocates.
+ *   pya_plan_ions        the fill: d_out[cap] records at the offsets of the count (the same d_ion_off; PYA_ERR_STATE when
+ *                        the run has not been counted).  A PSM whose records would pass cap writes nothing -- no write
+ *                        ever lies at or past d_out + cap -- and pya_plan_check reports it (PYA_ERR_LIMIT) until the fill
+ *                        is repeated with room or the plan is run again.
+ * PYA_ERR_LIMIT when a fragment list needs more LDS than a compute unit has, as for pya_plan_evidence. */
+int pya_plan_ions_count(pya_plan *plan, const pya_results *d_res, void *hip_stream, int64_t *d_ion_off);
+int pya_plan_ions(pya_plan *plan, const pya_results *d_res, void *hip_stream, const int64_t *d_ion_off, pya_ion *d_out, uint64_t cap);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

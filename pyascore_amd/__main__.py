@@ -3,8 +3,8 @@
 MI355X scorer: the files are read by :mod:`pyascore_amd.ingest`, every selected PSM is scored in ONE
 batched call (:func:`pyascore_amd.batch_cli.localize`) and the TSV of docs/source/cli.rst:135-180 is
 written.  ``--parameter_file`` takes ``name = value`` lines ('#' starts a comment); options on the
-command line override it.  ``--device`` (HIP ordinal) and ``--evidence`` (three more columns: what stands behind every
-Ascore) are the additions."""
+command line override it.  ``--device`` (HIP ordinal), ``--evidence`` (three more columns: what stands behind every
+Ascore) and ``--ions FILE`` (a second table: which ions, one line each) are the additions."""
 import argparse
 import re
 import sys
@@ -48,6 +48,9 @@ def build_parser():
     p.add_argument("--evidence", action="store_true",
                    help="append Depth, SiteIons and CompScore: per site the peak depth of the Ascore, the site-determining ions "
                         "matched/possible of the winner | of the competitor, and the competitor's PepScore")
+    p.add_argument("--ions", type=str, default="", metavar="FILE",
+                   help="write the ion table to FILE: one line per matched fragment of the reported localisation and per "
+                        "site-determining ion of every site (Scan, Hit, Section, Site, Side, Ion, TheoMz, PeakMz, Rank, Counted)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -106,11 +109,14 @@ def run(args, log=print):
     if args.neutral_loss_groups and args.neutral_loss_masses:
         for group, mass in zip(args.neutral_loss_groups.split(","), args.neutral_loss_masses.split(",")):
             ascore.add_neutral_loss(group, float(mass))
+    ion_rows = [] if args.ions else None
     rows = batch_cli.localize(ascore, psms, spectra, args.residues, args.mod_mass, args.hit_depth,
                               args.max_fragment_charge, args.mod_correction_tol, args.zero_based,
                               match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
-                              evidence=args.evidence)
+                              evidence=args.evidence, ions=ion_rows)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence)
+    if ion_rows is not None:
+        batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))
     return rows
 

@@ -11,8 +11,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYA_LIB") or os.path.join(_HERE, "libpyascore_hip.so")   # PYA_LIB: A/B builds
 
 PYA_OK, PYA_ERR_ARG, PYA_ERR_HIP, PYA_ERR_PSM, PYA_ERR_LIMIT, PYA_ERR_STATE = 0, -1, -2, -3, -4, -5
-PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID, PYA_FLAG_EVIDENCE = 1, 2, 4, 8
+PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID, PYA_FLAG_EVIDENCE, PYA_FLAG_IONS = 1, 2, 4, 8, 16
 PYA_EV_NONE, PYA_EV_COUNTED, PYA_EV_TIED = 0, 1, 2
+PYA_ION_WINNER, PYA_ION_LOSS, PYA_ION_COMP, PYA_ION_COUNTED = 255, 1, 2, 4
 PYA_MAX_PEPTIDE_LEN = 511
 
 _vp = C.c_void_p
@@ -52,6 +53,17 @@ assert C.sizeof(Evidence) == 16, "pya_evidence is a 16-byte record"
 EVIDENCE_DTYPE = [("comp_score", "<f4"), ("comp_pos", "<u2"), ("depth", "u1"), ("kind", "u1"),
                   ("ref_matched", "<u2"), ("ref_possible", "<u2"), ("comp_matched", "<u2"), ("comp_possible", "<u2")]
 
+
+class Ion(C.Structure):
+    """pya_ion: one matched fragment of the winner, or one site-determining ion of a counted pair"""
+    _fields_ = [("theo_mz", C.c_float), ("peak_mz", C.c_float), ("size", C.c_uint16), ("type", C.c_uint8), ("charge", C.c_uint8),
+                ("rank", C.c_uint8), ("site", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+assert C.sizeof(Ion) == 16, "pya_ion is a 16-byte record"
+ION_DTYPE = [("theo_mz", "<f4"), ("peak_mz", "<f4"), ("size", "<u2"), ("type", "u1"), ("charge", "u1"),
+             ("rank", "u1"), ("site", "u1"), ("flags", "u1"), ("reserved", "u1")]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -89,6 +101,9 @@ SYMBOLS = {
     "pya_last_batch_status": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_last_batch_evidence": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32]),
     "pya_plan_evidence": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp]),
+    "pya_last_batch_ions": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "pya_plan_ions_count": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp]),
+    "pya_plan_ions": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, C.c_uint64]),
     "pya_plan_create": (C.c_int, [_vp, C.POINTER(Batch), C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_create_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_run": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Results)]),

@@ -71,6 +71,8 @@ except ImportError:                   # not built for this interpreter
 
 EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)      # pya_evidence, 16 bytes
 assert EVIDENCE_DTYPE.itemsize == 16
+ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
+assert ION_DTYPE.itemsize == 16
 _NO_U32 = np.zeros(0, np.uint32)
 _NO_F32 = np.zeros(0, np.float32)
 
@@ -305,7 +307,7 @@ class PyAscore:
             last["lazy"] = False
             self._batch_n = 1
 
-    def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False):
+    def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -322,6 +324,12 @@ class PyAscore:
         the site-determining ions possible and matched for the winner and for the competitor, the competitor's position and
         PepScore (``kind``: 0 nothing to compare, 1 counted, 2 the competitor ties the winner).  Every other result is what
         it is without the option.
+
+        ``ions=True`` adds ``ion_off`` (int64 ``[n + 1]``) and ``ions`` (``ION_DTYPE``, the 16-byte ``pya_ion``): the
+        records of PSM i are ``ions[ion_off[i]:ion_off[i + 1]]`` -- first every fragment of the best localisation that
+        matched a retained peak (``site`` 255), then, for every site whose evidence row is counted, the site-determining
+        ions of the winner and of that row's competitor (``site`` = the column, ``flags``: 1 loss variant, 2 the
+        competitor's, 4 matched at the row's depth).  Every other result is what it is without the option.
 
         Shared spectra: a batch dict with ``spec_of`` (and ``n_spectra``; ``synth.pack_shared_batch``) holds every
         spectrum once, ``peak_off`` describes the spectra and PSM i is scored against spectrum ``spec_of[i]`` -- the hits
@@ -340,13 +348,19 @@ class PyAscore:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
-                return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence)
+                return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions)
             if perm is not None:
                 try:
-                    res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence)
+                    res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
+                csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
+                if ions:                     # the ranges of the PSMs, back in input order
+                    n_rec = np.diff(csr[0])[inv]
+                    res["ion_off"] = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
+                    take = np.repeat(csr[0][:-1][inv] - res["ion_off"][:-1], n_rec) + np.arange(int(n_rec.sum()))
+                    res["ions"] = csr[1][take]
                 if res.get("status_message"):
                     res["status_message"] = _renumber_psm(res["status_message"], perm)
                 return res
@@ -382,6 +396,8 @@ class PyAscore:
         if n == 0:
             if evidence:
                 out["evidence"] = np.zeros((0, max_k), EVIDENCE_DTYPE)
+            if ions:
+                out["ion_off"], out["ions"] = np.zeros(1, np.int64), np.zeros(0, ION_DTYPE)
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -404,7 +420,7 @@ class PyAscore:
             except (IndexError, ValueError):
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
-            (_lib.PYA_FLAG_EVIDENCE if evidence else 0)
+            (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0)
         rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r)
         if rc:
             self._raise(rc)
@@ -430,7 +446,22 @@ class PyAscore:
             rc = self._lib.pya_last_batch_evidence(self._h, _as_ptr(out["evidence"]), n, max_k)
             if rc:
                 self._raise(rc)
+        if ions:
+            out["ion_off"], out["ions"] = self._last_batch_ions(n)
         return out
+
+    def _last_batch_ions(self, n):
+        """pya_last_batch_ions: the size query, then the records"""
+        off = np.zeros(n + 1, np.int64)
+        rc = self._lib.pya_last_batch_ions(self._h, _as_ptr(off), None, 0)
+        if rc:
+            self._raise(rc)
+        rec = np.zeros(int(off[-1]), ION_DTYPE)
+        if rec.size:
+            rc = self._lib.pya_last_batch_ions(self._h, _as_ptr(off), _as_ptr(rec), rec.size)
+            if rc:
+                self._raise(rc)
+        return off, rec
 
     def _score_batch_call(self, b, spec_of, n_spec, mz, it, flags, r):
         """float64 arrays through the entry points the reference's interface stands beside, float32 ones through the typed."""
@@ -616,6 +647,23 @@ class PyAscore:
         last = self._last
         if last is None:
             return np.zeros(0, EVIDENCE_DTYPE)
+        self._batch_of_one_records()
+        return last["evidence"][: last["k"]].copy()
+
+    @property
+    def ions(self):
+        """Which ions stand behind the last ``score()`` PSM: its ``ION_DTYPE`` records (see ``score_batch(ions=True)``),
+        the winner's matched fragments first, then the site-determining ions of every counted site.  Produced when read,
+        like ``evidence``."""
+        last = self._last
+        if last is None:
+            return np.zeros(0, ION_DTYPE)
+        self._batch_of_one_records()
+        return last["ions"].copy()
+
+    def _batch_of_one_records(self):
+        """evidence and ions of score()'s PSM: the arrays it was given, through the batch path as a batch of one"""
+        last = self._last
         if "evidence" not in last:
             mz, it = _check_f64("mz_arr", last["mz"]), _check_f64("int_arr", last["it"])
             pep, ap, am = last["pep"], np.ascontiguousarray(last["aux_pos"], np.uint32), np.ascontiguousarray(last["aux_mass"], np.float32)
@@ -628,7 +676,8 @@ class PyAscore:
                            _as_ptr(ap), _as_ptr(am), _as_ptr(off["aux"]))
             r = _lib.Results(k, *[_as_ptr(a) for a in res])
             # (no PYA_FLAG_KEEP: the plan path leaves the staging and the retained records of score()'s PSM alone)
-            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), _lib.PYA_FLAG_EVIDENCE, C.byref(r))
+            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), _lib.PYA_FLAG_EVIDENCE | _lib.PYA_FLAG_IONS,
+                                           C.byref(r))
             ev = np.zeros((1, k), EVIDENCE_DTYPE)
             if not rc:
                 rc = self._lib.pya_last_batch_evidence(self._h, _as_ptr(ev), 1, k)
@@ -636,8 +685,8 @@ class PyAscore:
                 self._raise(rc)
             if int(res[1][0]) != int(last["best_sig"]):
                 raise RuntimeError("the arrays passed to score() changed before evidence was read")
+            last["ions"] = self._last_batch_ions(1)[1]
             last["evidence"] = ev[0]
-        return last["evidence"][: last["k"]].copy()
 
     @property
     def alt_sites(self):

@@ -22,6 +22,8 @@ from .synth import pack_batch, pack_shared_batch
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
 # ``--evidence``: what stands behind every Ascore (pya_evidence), one entry per modified site like Ascores
 EVIDENCE_COLUMNS = ("Depth", "SiteIons", "CompScore")
+# ``--ions FILE``: one line per ion record (pya_ion), long format
+ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
 def process_mods(residues, mod_mass, sequence, positions, masses, mod_correction_tol=1.0,
@@ -114,12 +116,14 @@ def pack_hits(picked, scans):
 
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
-             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False):
+             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
     nan -- and are reported through ``log`` (a callable taking one string) with their count, scans and codes.
-    ``evidence=True`` appends three fields per row, ';'-joined per site (``evidence_fields``): Depth, SiteIons, CompScore."""
+    ``evidence=True`` appends three fields per row, ';'-joined per site (``evidence_fields``): Depth, SiteIons, CompScore.
+    ``ions``: a list that receives the ion table of the scored PSMs, one ``ion_fields`` row per record behind the PSM's
+    scan and its hit number inside the scan (``write_ions_tsv``)."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     picked, scans = select_psms(psms, spectra_map, residues, mod_mass, hit_depth, max_fragment_charge,
@@ -130,7 +134,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     # One PSM the kernels cannot take (longer than 64 residues, more than 15 000 site assignments,
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.
-    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence)
+    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None)
     bad = np.flatnonzero(res["status"])
     if bad.size:
         import warnings
@@ -144,7 +148,11 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ok = (res["status"] == 0) & (res["n_sig"] > 0)
     seqs = ascore.format_batch(batch, res["best_sig"], valid=ok.astype(np.int32))   # every string in one call
     rows = []
+    hit = 0
     for i, psm in enumerate(picked):
+        hit = hit + 1 if i and scans[i] == scans[i - 1] else 1
+        if ions is not None:
+            ions.extend([scans[i], hit] + ion_fields(rec) for rec in res["ions"][res["ion_off"][i]:res["ion_off"][i + 1]])
         if res["status"][i]:
             rows.append([scans[i], "", float("nan"), "", ""] + (["", "", ""] if evidence else []))
             continue
@@ -170,6 +178,27 @@ def evidence_fields(ev):
                     else ("tie" if kind == 2 else ""))
         comp.append(str(e["comp_score"]) if kind else "")
     return [";".join(depth), ";".join(ions), ";".join(comp)]
+
+
+def ion_fields(rec):
+    """One ion record as the fields behind Scan and Hit of the ``--ions`` table: Section (``winner``: a matched fragment of
+    the reported localisation; ``site``: a site-determining ion), Site (which Ascore of the PSM, 1-based; empty for
+    ``winner``), Side (``winner`` or ``competitor``), Ion (type, size, ``+`` per charge, ``*`` for a neutral-loss variant:
+    ``y7++*``), TheoMz, PeakMz and Rank (1-based like Depth; empty without a match), Counted (1: matched at the site's depth)."""
+    flags, matched = int(rec["flags"]), int(rec["rank"]) != 255
+    winner_section = int(rec["site"]) == 255
+    ion = "%s%d%s%s" % (chr(int(rec["type"])), int(rec["size"]), "+" * int(rec["charge"]), "*" if flags & 1 else "")
+    return ["winner" if winner_section else "site", "" if winner_section else str(int(rec["site"]) + 1),
+            "competitor" if flags & 2 else "winner", ion, str(rec["theo_mz"]), str(rec["peak_mz"]) if matched else "",
+            str(int(rec["rank"]) + 1) if matched else "", "1" if flags & 4 else "0"]
+
+
+def write_ions_tsv(ion_rows, path):
+    """The ``--ions`` table: the rows ``localize(..., ions=[])`` collected, under ``ION_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(ION_COLUMNS) + "\n")
+        for row in ion_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
 
 
 def write_tsv(rows, path, evidence=False):

@@ -61,6 +61,7 @@ void pya_destroy(pya_handle *h) {
     for (void *ps : h->pinned_stage)
         if (ps) (void)hipHostFree(ps);
     if (h->evid_host) (void)hipHostFree(h->evid_host);
+    if (h->ions_host) (void)hipHostFree(h->ions_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->run_stream) (void)hipStreamDestroy(h->run_stream);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
@@ -236,6 +237,19 @@ int pya_last_batch_evidence(pya_handle *h, pya_evidence *out, uint64_t n_psm, ui
         return h->fail(PYA_ERR_ARG, -1, "the last batch had %llu PSMs and rows of %u", (unsigned long long)h->evid_n, h->evid_k);
     if (!out && n_psm * max_k != 0) return h->fail(PYA_ERR_ARG, -1, "NULL evidence array");
     if (n_psm * max_k != 0) std::memcpy(out, h->evid_host, (size_t)n_psm * max_k * sizeof(pya_evidence));
+    return PYA_OK;
+}
+
+int pya_last_batch_ions(pya_handle *h, int64_t *ion_off, pya_ion *out, uint64_t cap) {
+    if (!h || !ion_off) return PYA_ERR_ARG;
+    if (!h->ions_valid) return h->fail(PYA_ERR_STATE, -1, "the last batch was scored without PYA_FLAG_IONS");
+    std::memcpy(ion_off, h->ions_off.data(), h->ions_off.size() * sizeof(int64_t));
+    const uint64_t total = (uint64_t)h->ions_off.back();
+    if (total == 0 || cap == 0) return PYA_OK;
+    if (cap < total)
+        return h->fail(PYA_ERR_ARG, -1, "capacity %llu < %llu records", (unsigned long long)cap, (unsigned long long)total);
+    if (!out) return h->fail(PYA_ERR_ARG, -1, "NULL ion array");
+    std::memcpy(out, h->ions_host, (size_t)total * sizeof(pya_ion));
     return PYA_OK;
 }
 

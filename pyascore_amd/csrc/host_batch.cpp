@@ -113,6 +113,39 @@ static int evidence_host_block(pya_handle *h, uint64_t n, uint32_t mk) {
     return PYA_OK;
 }
 
+/* PYA_FLAG_IONS: count and scan behind a plan's kernels on `st`, the one wait of the stage (the number of records decides
+ * what is allocated), then the fill and the records on their way into the handle's pinned block behind those of the PSMs
+ * before `lo` (chunks come in PSM order).  The wait also covers whatever an earlier chunk still copied into the block,
+ * which may move when it grows. */
+static int ions_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0) return PYA_OK;
+    HIPCHK(h, p->d_ion_off.alloc(n + 1));
+    int rc = pya_plan_ions_count(p, d_out, st, p->d_ion_off.p);
+    if (rc) return rc;
+    std::vector<int64_t> off(n + 1);
+    HIPCHK(h, hipMemcpyAsync(off.data(), p->d_ion_off.p, (n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    const int64_t base = h->ions_off[lo], total = off[n];
+    if (total < 0) return h->fail(PYA_ERR_HIP, -1, "corrupt ion offsets");
+    for (uint64_t i = 0; i < n; i++) h->ions_off[lo + 1 + i] = base + off[i + 1];
+    if (total == 0) return PYA_OK;
+    const size_t need = (size_t)(base + total);
+    if (h->ions_cap < need) {
+        pya_ion *grown = nullptr;
+        const size_t cap = need + need / 4;
+        HIPCHK(h, hipHostMalloc((void **)&grown, cap * sizeof(pya_ion), hipHostMallocDefault));
+        if (base) std::memcpy(grown, h->ions_host, (size_t)base * sizeof(pya_ion));
+        if (h->ions_host) (void)hipHostFree(h->ions_host);
+        h->ions_host = grown;
+        h->ions_cap = cap;
+    }
+    HIPCHK(h, p->d_ions.alloc((size_t)total));
+    if ((rc = pya_plan_ions(p, d_out, st, p->d_ion_off.p, p->d_ions.p, (uint64_t)total))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->ions_host + base, p->d_ions.p, (size_t)total * sizeof(pya_ion), hipMemcpyDeviceToHost, st));
+    return PYA_OK;
+}
+
 /* Big pya_score_batch calls: the batch is cut into chunks of consecutive PSMs that fit the device
  * budget and the chunks are pipelined -- a helper thread streams the spectra of chunk c + 1 over
  * PCIe (the bound of this entry point: 16, 12 or 8 bytes per peak) into the other slot of a two-slot ring
@@ -237,6 +270,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         hipError_t e = hipMemcpyAsync(sg, p->arena.p + p->o_status, p->d2h_bytes, hipMemcpyDeviceToHost, h->run_stream);
         if (e != hipSuccess) return finish(h->hip_fail(e, "results copy"));
         if ((flags & PYA_FLAG_EVIDENCE) && (rc = evidence_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_IONS) && (rc = ions_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -278,6 +312,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         cur = std::move(next);
     }
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
+    h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
     return finish(PYA_OK);
 }
 
@@ -289,10 +324,13 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->last_status.clear();
     h->last_chunks = 1;
     h->evid_valid = false;
+    h->ions_valid = false;
+    if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
     if (b->n_psm == 0) {
         h->evid_n = 0;
         h->evid_k = out->max_k;
         h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
+        h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
         return PYA_OK;
     }
     uint32_t types = 0;
@@ -312,8 +350,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_ev = evidence_host_block(h, b->n_psm, out->max_k);
         if (rc_ev) return rc_ev;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE)) && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE or PYA_FLAG_IONS takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS)) && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -435,6 +473,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         HIPCHK(h, hipStreamSynchronize(nullptr));
         h->evid_valid = true;
     }
+    if (flags & PYA_FLAG_IONS) {
+        if ((rc = ions_behind_run(h, p, &d_out, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        h->ions_valid = true;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -454,6 +497,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
                               uint32_t flags, const pya_results *out) {
     h->last_status.clear();
     h->evid_valid = false;
+    h->ions_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);

@@ -118,6 +118,11 @@ int pya_launch_general_ambiguity(const BatchDev *b, uint32_t psm, uint32_t l_cap
 size_t pya_evidence_lds_bytes(uint32_t l_cap, uint32_t list_cap);
 int pya_launch_evidence(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, void *d_out, uint32_t l_cap, uint32_t list_cap,
                         hipStream_t stream);
+size_t pya_ions_lds_bytes(uint32_t l_cap, uint32_t list_cap);
+uint32_t pya_ions_scan_tiles(uint32_t n);
+int pya_launch_ions(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const void *d_evid, int64_t *d_off, void *d_out, uint64_t cap,
+                    uint32_t *d_over, uint32_t l_cap, uint32_t list_cap, hipStream_t stream);
+int pya_launch_ions_scan(int64_t *d_off, uint32_t n, uint64_t *d_tiles, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -314,6 +319,12 @@ struct pya_handle {
     uint64_t evid_n = 0;                      /* PSMs of the batch they belong to */
     uint32_t evid_k = 0;                      /* its row stride */
     bool evid_valid = false;                  /* the last batch was scored with the flag */
+    /* PYA_FLAG_IONS: the ion records of the last pya_score_batch in PSM order (pinned: a chunk's records come back
+     * asynchronously behind its offsets) and the offsets of every PSM into them (pya_last_batch_ions copies them out) */
+    pya_ion *ions_host = nullptr;
+    size_t ions_cap = 0;                      /* records the block has room for */
+    std::vector<int64_t> ions_off;            /* [n_psm + 1] of the batch they belong to */
+    bool ions_valid = false;                  /* the last batch was scored with the flag */
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -622,6 +633,18 @@ struct pya_plan {
     DevBuf<uint32_t> d_evid_ids;
     DevBuf<pya_evidence> d_evid;
     hipEvent_t ev_evid = nullptr;
+    /* pya_plan_ions_count / pya_plan_ions: the evidence rows the two passes read (competitor and depth of every counted
+     * column), the tile sums of the scan, the overflow report of the last fill (count, 0xffffffff - smallest PSM), the
+     * event the fill and pya_plan_check wait for, and how far the last run has come (0: no count yet, 1: counted, 2: filled);
+     * offsets and records of a pya_score_batch plan */
+    DevBuf<pya_evidence> d_ions_evid;
+    DevBuf<uint64_t> d_ions_tiles;
+    DevBuf<uint32_t> d_ions_over;
+    DevBuf<int64_t> d_ion_off;
+    DevBuf<pya_ion> d_ions;
+    hipEvent_t ev_ions = nullptr;
+    uint32_t ions_max_k = 0;
+    int ions_state = 0;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -632,6 +655,7 @@ struct pya_plan {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_evid) (void)hipEventDestroy(ev_evid);
+        if (ev_ions) (void)hipEventDestroy(ev_ions);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
@@ -742,5 +766,6 @@ int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");
+static_assert(sizeof(pya_ion) == 16, "pya_ion is one 16-byte store of ions.hip");
 
 #endif

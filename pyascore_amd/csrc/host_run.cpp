@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -335,6 +335,7 @@ int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_strea
     }
     p->last_stream = st;
     p->ran = true;
+    p->ions_state = 0;                       /* (counts, offsets and the overflow report belonged to the run before) */
     p->dev = d;
     return rc;
 }
@@ -428,7 +429,16 @@ int pya_plan_check(pya_plan *p) {
     }
     const bool skip = (p->flags & PYA_FLAG_SKIP_INVALID) != 0;
     if (skip) h->last_status = st;
-    return check_status(h, st.data(), p->n_psm, skip);
+    const int rc = check_status(h, st.data(), p->n_psm, skip);
+    if (rc || p->ions_state != 2) return rc;
+    /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
+    uint32_t over[2] = {0u, 0u};
+    HIPCHK(h, hipEventSynchronize(p->ev_ions));
+    HIPCHK(h, hipMemcpy(over, p->d_ions_over.p, sizeof(over), hipMemcpyDeviceToHost));
+    if (over[0])
+        return h->fail(PYA_ERR_LIMIT, (int64_t)(0xffffffffu - over[1]), "pya_plan_ions: the records of %u PSMs (PSM %u the first) pass the "
+                       "cap of the call; nothing of them was written", over[0], 0xffffffffu - over[1]);
+    return PYA_OK;
 }
 
 /* The evidence stage: one launch for the PSMs inside the fast limits, sized by THEIR longest peptide and fragment list,
@@ -493,6 +503,90 @@ int pya_plan_evidence(pya_plan *p, const pya_results *r, void *hip_stream, pya_e
     if (!e && !p->gen_ids.empty())
         e = pya_launch_evidence(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_out, p->gen_l_cap, p->gen_list_cap, st);
     if (e) return h->hip_fail((hipError_t)e, "evidence launch");
+    return PYA_OK;
+}
+
+namespace {
+/* the results of the caller's structure in place of the run's (pya_plan_evidence does the same) */
+BatchDev ions_view(pya_plan *p, const pya_results *r) {
+    BatchDev d = p->dev;
+    d.best_score = r->best_score;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    d.ascores = r->ascores;
+    d.alt_mask = r->alt_mask;
+    d.max_k = r->max_k;
+    return d;
+}
+
+/* the two launches of pya_plan_evidence, with their caps (d_out NULL: the count pass) */
+int ions_launches(pya_plan *p, const BatchDev &d, int64_t *d_off, pya_ion *d_out, uint64_t cap, hipStream_t st) {
+    int e = pya_launch_ions(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, p->d_ions_evid.p, d_off, d_out, cap,
+                            p->d_ions_over.p, p->evid_l_cap, p->evid_list_cap, st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_ions(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), p->d_ions_evid.p, d_off, d_out, cap, p->d_ions_over.p,
+                            p->gen_l_cap, p->gen_list_cap, st);
+    return e;
+}
+}  // namespace
+
+/* The ion stage, first half: the evidence rows of the results into the plan's own block (competitor and depth of every
+ * counted column; pya_plan_evidence waits for the run and sets the caps of the two launches), the count pass on the same
+ * two launches, the scan.  Nothing waits on the host. */
+int pya_plan_ions_count(pya_plan *p, const pya_results *r, void *hip_stream, int64_t *d_ion_off) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (!d_ion_off) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_ions_count");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (p->n_psm == 0) {
+        HIPCHK(h, hipMemsetAsync(d_ion_off, 0, sizeof(int64_t), st));
+        return PYA_OK;
+    }
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_ions_count: the plan has not been run");
+    const size_t n_rows = (size_t)p->n_psm * r->max_k;
+    if (p->d_ions_evid.n < std::max<size_t>(n_rows, 1)) HIPCHK(h, p->d_ions_evid.alloc(std::max<size_t>(n_rows, 1)));
+    const uint32_t tiles = pya_ions_scan_tiles((uint32_t)p->n_psm);
+    if (p->d_ions_tiles.n < tiles) HIPCHK(h, p->d_ions_tiles.alloc(tiles));
+    if (!p->d_ions_over.p) HIPCHK(h, p->d_ions_over.alloc(2));
+    if (!p->ev_ions) HIPCHK(h, hipEventCreateWithFlags(&p->ev_ions, hipEventDisableTiming));
+    p->ions_state = 0;
+    const int rc = pya_plan_evidence(p, r, hip_stream, p->d_ions_evid.p);
+    if (rc) return rc;
+    if (pya_ions_lds_bytes(p->evid_l_cap, p->evid_list_cap) > kMaxLds ||
+        (!p->gen_ids.empty() && pya_ions_lds_bytes(p->gen_l_cap, p->gen_list_cap) > kMaxLds))
+        return h->fail(PYA_ERR_LIMIT, -1, "pya_plan_ions_count: %u fragments per ion type exceed the ion kernel's room",
+                       std::max(p->evid_list_cap, p->gen_ids.empty() ? 0u : p->gen_list_cap));
+    const BatchDev d = ions_view(p, r);
+    int e = ions_launches(p, d, d_ion_off, nullptr, 0, st);
+    if (!e) e = pya_launch_ions_scan(d_ion_off, (uint32_t)p->n_psm, p->d_ions_tiles.p, st);
+    if (e) return h->hip_fail((hipError_t)e, "ion count launch");
+    HIPCHK(h, hipEventRecord(p->ev_ions, st));
+    p->ions_max_k = r->max_k;
+    p->ions_state = 1;
+    return PYA_OK;
+}
+
+/* ... second half: the fill pass behind the count (whatever stream that was on) */
+int pya_plan_ions(pya_plan *p, const pya_results *r, void *hip_stream, const int64_t *d_ion_off, pya_ion *d_out, uint64_t cap) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_ions: the plan has not been run");
+    if (p->ions_state == 0) return h->fail(PYA_ERR_STATE, -1, "pya_plan_ions: pya_plan_ions_count has not been called for this run");
+    if (!d_ion_off || !d_out || !r->best_score || !r->best_sig || !r->n_sig || !r->ascores || !r->alt_mask)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_ions");
+    if (r->max_k != p->ions_max_k)
+        return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is not the one pya_plan_ions_count was given (%u)", r->max_k, p->ions_max_k);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    HIPCHK(h, hipStreamWaitEvent(st, p->ev_ions, 0));
+    HIPCHK(h, hipMemsetAsync(p->d_ions_over.p, 0, 2 * sizeof(uint32_t), st));
+    const BatchDev d = ions_view(p, r);
+    const int e = ions_launches(p, d, const_cast<int64_t *>(d_ion_off), d_out, cap, st);
+    if (e) return h->hip_fail((hipError_t)e, "ion fill launch");
+    HIPCHK(h, hipEventRecord(p->ev_ions, st));
+    p->ions_state = 2;
     return PYA_OK;
 }
 

@@ -22,9 +22,10 @@ class DevicePlan:
     batch's own largest n_of_mod: ranks that gather fixed-size records pass the job-wide value.
     ``evidence()`` after ``run()`` gives the evidence records of every site (``pya_plan_evidence``); ``evidence=True``
     tells the plan at creation that they will be asked for (a plan of a handful of PSMs then takes the per-stage
-    launches instead of the one-launch kernel)."""
+    launches instead of the one-launch kernel).  ``ions()`` / ``ions=True``: the same for the ion records
+    (``pya_plan_ions_count``, ``pya_plan_ions``)."""
 
-    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False):
+    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -52,7 +53,8 @@ class DevicePlan:
                        _as_ptr(m["n_of_mod"]), _as_ptr(m["max_charge"]), _as_ptr(m["aux_pos"]),
                        _as_ptr(m["aux_mass"]), _as_ptr(m["aux_off"]))
         self._plan = C.c_void_p()
-        flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0)
+        flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
+            (_lib.PYA_FLAG_IONS if ions else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -131,6 +133,27 @@ class DevicePlan:
             self.scorer._raise(rc)
         return out
 
+    def ions(self, cap=None):
+        """The ion records of the last ``run()``: ``(ion_off, records)``, an ``int64`` device tensor ``[n_psm + 1]`` and a
+        ``torch.uint8`` device tensor ``[total, 16]`` (one 16-byte ``pya_ion`` each; ``ion_records`` turns a host copy into
+        the structured array).  Count and scan are enqueued on torch's current stream; the one wait is this method reading
+        the total to allocate (a caller that knows a bound passes ``cap`` and nothing waits: ``records`` then has ``cap``
+        rows, ``check()`` reports a PSM that did not fit).  Valid for the results of the last run."""
+        torch = self._torch
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            off = torch.empty(self.n_psm + 1, dtype=torch.int64, device=self.device)
+            rc = self._lib.pya_plan_ions_count(self._plan, C.byref(self._res), stream, off.data_ptr())
+            if rc:
+                self.scorer._raise(rc)
+            total = int(off[-1].item()) if cap is None else int(cap)
+            out = torch.zeros((total, 16), dtype=torch.uint8, device=self.device)
+        if total and self.n_psm:
+            rc = self._lib.pya_plan_ions(self._plan, C.byref(self._res), stream, off.data_ptr(), out.data_ptr(), total)
+            if rc:
+                self.scorer._raise(rc)
+        return off, out
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -176,6 +199,7 @@ class DevicePlan:
 
 
 EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)
+ION_DTYPE = np.dtype(_lib.ION_DTYPE)
 
 
 def evidence_rows(raw):
@@ -198,3 +222,12 @@ def unpack_summary(packed, max_k):
         ascores=np.ascontiguousarray(p[:, 4:4 + k]).view(np.float32),
         alt_mask=np.ascontiguousarray(p[:, 4 + k:4 + 3 * k]).view(np.uint64).reshape(-1, k),
     )
+
+
+def ion_records(raw):
+    """A host copy of the records of ``DevicePlan.ions()`` (``.cpu().numpy()``, uint8 ``[total, 16]``) as the structured
+    array ``PyAscore.score_batch(..., ions=True)`` returns; a view, no copy."""
+    a = np.ascontiguousarray(raw)
+    if a.ndim != 2 or a.shape[1] != ION_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (total, %d)" % ION_DTYPE.itemsize)
+    return a.view(ION_DTYPE).reshape(a.shape[0])
