@@ -27,6 +27,8 @@
  *   pya_ion / pya_plan_ions_count /      the matched fragments of the best localisation and the site-determining ions
  *   pya_plan_ions / pya_last_batch_ions  of every counted pair, one record per ion (per PSM: ModifiedPeptide::getMatch,
  *                                 getSiteDeterminingIons, FragmentGraph)         cpp/ModifiedPeptide.cpp:126-150, :259-320
+ *   pya_named / pya_plan_named /         PyAscore.pep_scores and PyAscore.calculate_ambiguity(pep_scores[0], rec) for the
+ *   pya_score_batch_named         site assignments the CALLER names, in bulk     Ascore.pyx:208-252, cpp/Ascore.cpp:53-210
  *
  * Conventions
  *   - plain pointers and sizes only; no C++ or framework types cross the boundary;
@@ -87,6 +89,8 @@ extern "C" {
 #define PYA_FLAG_IONS 16u   /* pya_score_batch*: the ion records of every PSM as well              */
                             /* (pya_last_batch_ions); pya_plan_create*: as PYA_FLAG_EVIDENCE       */
                             /* (pya_plan_ions_count / pya_plan_ions)                               */
+#define PYA_FLAG_NAMED 32u  /* pya_plan_create*: as PYA_FLAG_EVIDENCE, for pya_plan_named;          */
+                            /* pya_score_batch*: no effect (pya_score_batch_named takes the queries) */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -162,6 +166,47 @@ typedef struct pya_ion {     /* 16 bytes, one store */
     uint8_t flags;           /* PYA_ION_* */
     uint8_t reserved;        /* 0 */
 } pya_ion;
+
+/* Localisations the caller names.  The evidence and ion records answer for the competitor the library picked; a user asks
+ * about a site assignment of their own: the search engine's reported sites, the known site of a synthetic peptide, a
+ * runner-up.  The reference answers per PSM with PyAscore.pep_scores (the ScoreContainer of every site assignment,
+ * Ascore.pyx:241-252, cpp/Ascore.cpp:53-139) and PyAscore.calculate_ambiguity(ref, other) (Ascore.pyx:208-230,
+ * cpp/Ascore.cpp:157-210); this is both, in bulk, for exactly the signatures asked for.
+ *   Queries: a CSR list per PSM of sig bits (above: bit j = the j-th modifiable residue from the N-terminus, for every
+ *   peptide length): q_off[n_psm + 1] (q_off[0] == 0, non-decreasing), q_bits[q_off[n_psm]].  A PSM may have no query,
+ *   many, or the same one twice.  One record per query, in query order; sig_bits echoes the query in every record.
+ *   Tests, in this order:
+ *   PYA_NAMED_NONE     the PSM was not scored (status != 0, or n_sig <= 0: that includes n_of_mod above the number of
+ *                      modifiable residues).  Every field but sig_bits is 0.
+ *   PYA_NAMED_WINNER   the query IS best_sig: pep_score has the bits of best_score, ambiguity 0, no ion is looked at.
+ *   PYA_NAMED_INVALID  the bits do not name exactly n_of_mod of the PSM's modifiable residues (popcount, or a bit at or above
+ *                      the number of sites).  Every field but sig_bits and kind is 0.  Never an error of the call.
+ *   PYA_NAMED_TIED     its PepScore is within 1e-6 of the winner's: the reference returns 0 before it looks at an ion
+ *                      (cpp/Ascore.cpp:159-161); ambiguity 0.
+ *   PYA_NAMED_COUNTED  ambiguity = Ascore::calculateAmbiguity(winner, query) for any number of moved modifications (it can
+ *                      be negative: it is what the reference returns), and
+ *                          score(depth, ref_possible, ref_matched) - score(depth, comp_possible, comp_matched)
+ *                      has its bit pattern (score as for pya_evidence); depth follows cpp/Ascore.cpp:164-172 (strict > from
+ *                      0: depth 0 when no depth favours the winner).
+ *   WINNER, TIED and COUNTED carry the container: pep_score, total_fragments, n_moved and the rows of the two optional
+ *   arrays are bit-equal to the record with the same sig_bits that pya_get_pep_scores* returns from a PYA_FLAG_KEEP batch.
+ *   depth and the four ion counts are 0 unless COUNTED; the optional rows of NONE and INVALID are zero; reserved is 0, so
+ *   records compare as 32 raw bytes.
+ *   The winner with site j moved to an evidence row's comp_pos gives that row's depth and four counts, and ambiguity ==
+ *   ascores[j] when the row is PYA_EV_COUNTED (PYA_NAMED_TIED when it is PYA_EV_TIED). */
+#define PYA_NAMED_NONE 0
+#define PYA_NAMED_INVALID 1
+#define PYA_NAMED_WINNER 2
+#define PYA_NAMED_TIED 3
+#define PYA_NAMED_COUNTED 4
+typedef struct pya_named {         /* 32 bytes, two 16-byte stores */
+    uint64_t sig_bits;             /* the query, echoed */
+    float pep_score;               /* ScoreContainer.weighted_score of that site assignment */
+    float ambiguity;               /* Ascore::calculateAmbiguity(winner, this) */
+    uint32_t total_fragments;      /* ScoreContainer.total_fragments */
+    uint8_t kind, depth, n_moved, reserved;   /* PYA_NAMED_*; n_moved = n_of_mod - |winner AND query| */
+    uint16_t ref_matched, ref_possible, comp_matched, comp_possible;   /* as in pya_evidence; COUNTED only */
+} pya_named;
 
 typedef struct pya_handle pya_handle;
 typedef struct pya_plan pya_plan;
@@ -283,6 +328,20 @@ typedef struct pya_typed_spectra {  /* host pointers for pya_score_batch_typed, 
 int pya_score_batch_typed(pya_handle *h, const pya_batch *batch, const uint32_t *spec_of, uint64_t n_spectra,
                           const pya_typed_spectra *spectra, uint32_t flags, const pya_results *out);
 
+/* pya_score_batch_typed with named localisations (pya_named above): the queries q_off[n_psm + 1] / q_bits[q_off[n_psm]] in, one
+ * record per query out in named_out[q_off[n_psm]], and, where not NULL, the containers' cumulative counts and depth scores in
+ * counts / scores [q_off[n_psm] * n_top], laid out like pya_get_pep_scores.  spec_of NULL: private spectra.  Every flag of
+ * pya_score_batch keeps its meaning, and pya_results, status, evidence and ions are byte for byte what the call without
+ * queries gives.  The stage (csrc/named.hip) runs behind the kernels of every chunk with that chunk's slice of the queries
+ * and its records come back behind the chunk's results; they do not depend on the cut into chunks, on the route a PSM took
+ * or on shared / typed input.  A batch of one or a handful takes the plan's launches.  The PSMs PYA_FLAG_SKIP_INVALID sets
+ * aside have PYA_NAMED_NONE records.  q_off[0] != 0 or a decreasing q_off: PYA_ERR_ARG, the message names the PSM; a
+ * malformed signature is a PYA_NAMED_INVALID record, never an error.  (PyAscore.pep_scores, PyAscore.calculate_ambiguity:
+ * Ascore.pyx:208-252.) */
+int pya_score_batch_named(pya_handle *h, const pya_batch *batch, const uint32_t *spec_of, uint64_t n_spectra,
+                          const pya_typed_spectra *spectra, uint32_t flags, const pya_results *out, const int64_t *q_off,
+                          const uint64_t *q_bits, pya_named *named_out, int32_t *counts, float *scores);
+
 /* Device memory one pya_score_batch call may hold at a time (upload ring + workspace; default 6 GiB,
  * or PYA_WORKSPACE_MB).  Calls that need more -- and every call with more than 32 MB of spectra -- are
  * cut into chunks of consecutive PSMs and pipelined: the upload of chunk c + 1 runs under the kernels
@@ -346,6 +405,18 @@ int pya_plan_evidence(pya_plan *plan, const pya_results *d_res, void *hip_stream
  * PYA_ERR_LIMIT when a fragment list needs more LDS than a compute unit has, as for pya_plan_evidence. */
 int pya_plan_ions_count(pya_plan *plan, const pya_results *d_res, void *hip_stream, int64_t *d_ion_off);
 int pya_plan_ions(pya_plan *plan, const pya_results *d_res, void *hip_stream, const int64_t *d_ion_off, pya_ion *d_out, uint64_t cap);
+/* The named-localisation records (pya_named above; cpp/Ascore.cpp:53-210) of the results the last pya_plan_run* of this plan
+ * wrote, for the queries d_q_off[n_psm + 1] / d_q_bits (device memory): d_out[n_q] records, d_counts / d_scores NULL or
+ * [n_q * n_top].  d_res as for pya_plan_evidence.  Enqueues the kernel (csrc/named.hip) on hip_stream, stream-ordered, no
+ * host synchronisation inside; it waits for that run -- the side stream included -- also when hip_stream is not the run's
+ * stream, is valid until the plan is run again, and may be called again with other queries.  n_q is the host-known size of
+ * the output (d_q_off[n_psm] of a well-formed list): no write ever lies at or past d_out + n_q (rows of d_counts / d_scores
+ * alike) whatever d_q_off holds -- a PSM whose range is not inside [0, n_q] writes nothing and pya_plan_check reports it
+ * (PYA_ERR_LIMIT) until the call is repeated or the plan is run again.  PYA_ERR_STATE when the plan has not been run,
+ * PYA_ERR_LIMIT when a fragment list needs more LDS than a compute unit has.  A plan of a handful of PSMs must have been
+ * created with PYA_FLAG_NAMED (or PYA_FLAG_EVIDENCE / PYA_FLAG_IONS): the one-launch kernel leaves no retained tables. */
+int pya_plan_named(pya_plan *plan, const pya_results *d_res, void *hip_stream, const int64_t *d_q_off, const uint64_t *d_q_bits,
+                   uint64_t n_q, pya_named *d_out, int32_t *d_counts, float *d_scores);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

@@ -4,7 +4,8 @@ MI355X scorer: the files are read by :mod:`pyascore_amd.ingest`, every selected 
 batched call (:func:`pyascore_amd.batch_cli.localize`) and the TSV of docs/source/cli.rst:135-180 is
 written.  ``--parameter_file`` takes ``name = value`` lines ('#' starts a comment); options on the
 command line override it.  ``--device`` (HIP ordinal), ``--evidence`` (three more columns: what stands behind every
-Ascore) and ``--ions FILE`` (a second table: which ions, one line each) are the additions."""
+Ascore), ``--ions FILE`` (a second table: which ions, one line each) and ``--reported`` (three more columns: the search
+engine's own site assignment, scored against the winner) are the additions."""
 import argparse
 import re
 import sys
@@ -51,6 +52,9 @@ def build_parser():
     p.add_argument("--ions", type=str, default="", metavar="FILE",
                    help="write the ion table to FILE: one line per matched fragment of the reported localisation and per "
                         "site-determining ion of every site (Scan, Hit, Section, Site, Side, Ion, TheoMz, PeakMz, Rank, Counted)")
+    p.add_argument("--reported", action="store_true",
+                   help="append ReportedSequence, ReportedPepScore and ReportedAscore: the site assignment the identification "
+                        "file reports, its PepScore, and the ambiguity of the winner against it (0: Ascore kept the site)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -113,8 +117,8 @@ def run(args, log=print):
     rows = batch_cli.localize(ascore, psms, spectra, args.residues, args.mod_mass, args.hit_depth,
                               args.max_fragment_charge, args.mod_correction_tol, args.zero_based,
                               match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
-                              evidence=args.evidence, ions=ion_rows)
-    batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence)
+                              evidence=args.evidence, ions=ion_rows, reported=args.reported)
+    batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

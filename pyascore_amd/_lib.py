@@ -12,6 +12,8 @@ LIB_PATH = os.environ.get("PYA_LIB") or os.path.join(_HERE, "libpyascore_hip.so"
 
 PYA_OK, PYA_ERR_ARG, PYA_ERR_HIP, PYA_ERR_PSM, PYA_ERR_LIMIT, PYA_ERR_STATE = 0, -1, -2, -3, -4, -5
 PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID, PYA_FLAG_EVIDENCE, PYA_FLAG_IONS = 1, 2, 4, 8, 16
+PYA_FLAG_NAMED = 32
+PYA_NAMED_NONE, PYA_NAMED_INVALID, PYA_NAMED_WINNER, PYA_NAMED_TIED, PYA_NAMED_COUNTED = 0, 1, 2, 3, 4
 PYA_EV_NONE, PYA_EV_COUNTED, PYA_EV_TIED = 0, 1, 2
 PYA_ION_WINNER, PYA_ION_LOSS, PYA_ION_COMP, PYA_ION_COUNTED = 255, 1, 2, 4
 PYA_MAX_PEPTIDE_LEN = 511
@@ -64,6 +66,21 @@ assert C.sizeof(Ion) == 16, "pya_ion is a 16-byte record"
 ION_DTYPE = [("theo_mz", "<f4"), ("peak_mz", "<f4"), ("size", "<u2"), ("type", "u1"), ("charge", "u1"),
              ("rank", "u1"), ("site", "u1"), ("flags", "u1"), ("reserved", "u1")]
 
+
+
+class Named(C.Structure):
+    """pya_named: the score container of a localisation the caller named, and its ambiguity against the winner"""
+    _fields_ = [("sig_bits", C.c_uint64), ("pep_score", C.c_float), ("ambiguity", C.c_float), ("total_fragments", C.c_uint32),
+                ("kind", C.c_uint8), ("depth", C.c_uint8), ("n_moved", C.c_uint8), ("reserved", C.c_uint8),
+                ("ref_matched", C.c_uint16), ("ref_possible", C.c_uint16),
+                ("comp_matched", C.c_uint16), ("comp_possible", C.c_uint16)]
+
+
+assert C.sizeof(Named) == 32, "pya_named is a 32-byte record"
+NAMED_DTYPE = [("sig_bits", "<u8"), ("pep_score", "<f4"), ("ambiguity", "<f4"), ("total_fragments", "<u4"),
+               ("kind", "u1"), ("depth", "u1"), ("n_moved", "u1"), ("reserved", "u1"),
+               ("ref_matched", "<u2"), ("ref_possible", "<u2"), ("comp_matched", "<u2"), ("comp_possible", "<u2")]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -95,6 +112,9 @@ SYMBOLS = {
     "pya_score_batch": (C.c_int, [_vp, C.POINTER(Batch), _vp, _vp, C.c_uint32, C.POINTER(Results)]),
     "pya_score_batch_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, _vp, _vp, C.c_uint32, C.POINTER(Results)]),
     "pya_score_batch_typed": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.POINTER(TypedSpectra), C.c_uint32, C.POINTER(Results)]),
+    "pya_score_batch_named": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.POINTER(TypedSpectra), C.c_uint32, C.POINTER(Results),
+                                        _vp, _vp, _vp, _vp, _vp]),
+    "pya_plan_named": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "pya_plan_run_typed": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.POINTER(Results)]),
     "pya_set_workspace_budget": (C.c_int, [_vp, C.c_uint64]),
     "pya_get_workspace_budget": (C.c_uint64, [_vp]),

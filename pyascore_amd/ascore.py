@@ -73,6 +73,7 @@ EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)      # pya_evidence, 16 bytes
 assert EVIDENCE_DTYPE.itemsize == 16
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
 assert ION_DTYPE.itemsize == 16
+from .named import NAMED_DTYPE, query_csr, sig_bits_batch, sig_bits_of, take_queries  # noqa: E402,F401
 _NO_U32 = np.zeros(0, np.uint32)
 _NO_F32 = np.zeros(0, np.float32)
 
@@ -307,7 +308,7 @@ class PyAscore:
             last["lazy"] = False
             self._batch_n = 1
 
-    def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False):
+    def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -331,6 +332,16 @@ class PyAscore:
         ions of the winner and of that row's competitor (``site`` = the column, ``flags``: 1 loss variant, 2 the
         competitor's, 4 matched at the row's depth).  Every other result is what it is without the option.
 
+        ``named``: localisations the caller names (``pya_score_batch_named``) -- the search engine's reported sites, a
+        known site, a runner-up.  Either the CSR pair ``(q_off int64[n + 1], sig_bits uint64)`` as a tuple, or a list with
+        one sequence of signatures per PSM (bit j = the j-th modifiable residue from the N-terminus; ``sig_bits_of`` makes
+        them from peptide positions).  Adds ``named_off`` (int64 ``[n + 1]``), ``named`` (``NAMED_DTYPE``, the 32-byte
+        ``pya_named``, one record per query in query order: the signature's PepScore and total fragments, its ambiguity
+        against the winner -- ``calculate_ambiguity(pep_scores[0], rec)`` -- with depth and site-determining ion counts, and
+        ``kind``: 0 PSM not scored, 1 not a site assignment of the PSM, 2 it is the winner, 3 it ties the winner, 4 counted)
+        and ``named_counts`` / ``named_scores`` (``[n_q, n_top]``, the cumulative counts and depth scores of ``pep_scores``).
+        Every other result is what it is without the option.
+
         Shared spectra: a batch dict with ``spec_of`` (and ``n_spectra``; ``synth.pack_shared_batch``) holds every
         spectrum once, ``peak_off`` describes the spectra and PSM i is scored against spectrum ``spec_of[i]`` -- the hits
         of one scan (`pyascore/__main__.py`, the hit_depth loop).  Each spectrum is uploaded and binned once; the results
@@ -348,14 +359,26 @@ class PyAscore:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
-                return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions)
+                return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
+                                        named=named)
             if perm is not None:
+                moved = None
+                if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
+                    q_off, q_bits = query_csr(named, int(batch["n_psm"]))
+                    moved = take_queries(q_off, q_bits, perm)
                 try:
-                    res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions)
+                    res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
+                                           named=None if moved is None else (moved[0], moved[1]))
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
+                per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
+                if moved is not None:
+                    res["named_off"] = q_off
+                    for k in ("named", "named_counts", "named_scores"):
+                        res[k] = np.zeros_like(per_query[k])
+                        res[k][moved[2]] = per_query[k]
                 if ions:                     # the ranges of the PSMs, back in input order
                     n_rec = np.diff(csr[0])[inv]
                     res["ion_off"] = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
@@ -393,6 +416,15 @@ class PyAscore:
         out = dict(best_score=np.zeros(n, np.float32), best_sig=np.zeros(n, np.uint64),
                    n_sig=np.zeros(n, np.int32), ascores=np.zeros((n, max_k), np.float32),
                    alt_mask=np.zeros((n, max_k), np.uint64))
+        nq = None
+        if named is not None:
+            q_off, q_bits = query_csr(named, n)
+            n_q = max(int(q_off[-1]), 0) if q_off.size else 0
+            out["named_off"] = q_off
+            out["named"] = np.zeros(n_q, NAMED_DTYPE)
+            out["named_counts"] = np.zeros((n_q, self._n_top), np.int32)
+            out["named_scores"] = np.zeros((n_q, self._n_top), np.float32)
+            nq = (q_off, q_bits, out["named"], out["named_counts"], out["named_scores"])
         if n == 0:
             if evidence:
                 out["evidence"] = np.zeros((0, max_k), EVIDENCE_DTYPE)
@@ -421,7 +453,7 @@ class PyAscore:
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
             (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0)
-        rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r)
+        rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         if rc:
             self._raise(rc)
         self._batch_n = n if keep else None
@@ -463,8 +495,13 @@ class PyAscore:
                 self._raise(rc)
         return off, rec
 
-    def _score_batch_call(self, b, spec_of, n_spec, mz, it, flags, r):
-        """float64 arrays through the entry points the reference's interface stands beside, float32 ones through the typed."""
+    def _score_batch_call(self, b, spec_of, n_spec, mz, it, flags, r, nq=None):
+        """float64 arrays through the entry points the reference's interface stands beside, float32 ones through the typed;
+        with queries (``nq``: offsets, signatures, the three output arrays) through the named entry point, which takes both."""
+        if nq is not None:
+            sp = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(it), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(it.dtype))
+            return self._lib.pya_score_batch_named(self._h, C.byref(b), _as_ptr(spec_of), n_spec, C.byref(sp), flags, C.byref(r),
+                                                   *[_as_ptr(a) for a in nq])
         if mz.dtype == np.float32 or it.dtype == np.float32:
             sp = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(it), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(it.dtype))
             return self._lib.pya_score_batch_typed(self._h, C.byref(b), _as_ptr(spec_of), n_spec, C.byref(sp), flags, C.byref(r))
@@ -660,6 +697,27 @@ class PyAscore:
             return np.zeros(0, ION_DTYPE)
         self._batch_of_one_records()
         return last["ions"].copy()
+
+    def named(self, signatures):
+        """The named-localisation records (``NAMED_DTYPE``, see ``score_batch(named=...)``) of the last ``score()`` PSM for
+        ``signatures`` (signature bits, or 0 / 1 arrays like ``pep_scores[i]["signature"]``): dict(named, counts, scores).
+        Produced when called, by sending that PSM through the batch path as a batch of one, like ``evidence``."""
+        last = self._last
+        if last is None:
+            raise RuntimeError("named needs a scored PSM")
+        bits = [sum(1 << j for j, v in enumerate(s) if int(v)) if np.ndim(s) else int(s) for s in signatures]
+        mz, it = _check_f64("mz_arr", last["mz"]), _check_f64("int_arr", last["it"])
+        psm = dict(n_psm=1, mz=mz, intensity=it, peak_off=np.array([0, mz.size], np.int64), pep=last["pep"],
+                   pep_off=np.array([0, last["pep"].size], np.int64), n_of_mod=np.array([int(last["k"])], np.int32),
+                   max_charge=np.array([int(last["z"])], np.int32), aux_pos=last["aux_pos"], aux_mass=last["aux_mass"],
+                   aux_off=np.array([0, np.size(last["aux_pos"])], np.int64))
+        self._ensure_kept()          # (score_batch does: before the state it leaves is put back)
+        state = (self._last, self._batch_n, self._lazy_batch)
+        res = self.score_batch(psm, named=[np.array(bits, np.uint64)])
+        self._last, self._batch_n, self._lazy_batch = state
+        if int(res["best_sig"][0]) != int(last["best_sig"]):
+            raise RuntimeError("the arrays passed to score() changed before named() was called")
+        return dict(named=res["named"], counts=res["named_counts"], scores=res["named_scores"])
 
     def _batch_of_one_records(self):
         """evidence and ions of score()'s PSM: the arrays it was given, through the batch path as a batch of one"""

@@ -17,11 +17,14 @@ from itertools import groupby
 import numpy as np
 
 from .ascore import PyAscore
+from .named import sig_bits_of
 from .synth import pack_batch, pack_shared_batch
 
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
 # ``--evidence``: what stands behind every Ascore (pya_evidence), one entry per modified site like Ascores
 EVIDENCE_COLUMNS = ("Depth", "SiteIons", "CompScore")
+# ``--reported``: the search engine's own site assignment, scored (pya_named)
+REPORTED_COLUMNS = ("ReportedSequence", "ReportedPepScore", "ReportedAscore")
 # ``--ions FILE``: one line per ion record (pya_ion), long format
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
@@ -48,6 +51,19 @@ def process_mods(residues, mod_mass, sequence, positions, masses, mod_correction
     return np.array(const_pos, dtype=np.uint32), np.array(const_masses, dtype=np.float32), n_variable
 
 
+def reported_positions(residues, mod_mass, sequence, positions, masses, mod_correction_tol=1.0, zero_based=False):
+    """Where the search engine put the modifications ``process_mods`` counts as variable: their 1-based peptide
+    positions (0 = n-terminus), in input order -- the site assignment `__main__.py:83-103` reads and drops."""
+    shift = 1 if zero_based else 0
+    out = []
+    for pos, mass in zip(positions, masses):
+        pos = int(pos)
+        aa = "n" if pos + shift == 0 else sequence[pos - 1 + shift]
+        if np.isclose(mod_mass, mass, rtol=1e-6, atol=mod_correction_tol) and aa in residues:
+            out.append(pos + shift)
+    return out
+
+
 def psm_charge(match, spectrum):
     """Charge used to bound the fragment charge (`__main__.py:138-145`): the identification's
     charge, else the spectrum's precursor charge, else 2; never below 2."""
@@ -71,12 +87,13 @@ def save_match(spectra, match):
 
 
 def select_psms(psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
-                mod_correction_tol=1.0, zero_based=False, match_save=False):
+                mod_correction_tol=1.0, zero_based=False, match_save=False, reported=None):
     """The reference's loop header (`__main__.py:129-147`): group by scan (input sorted by scan),
     take the first ``hit_depth`` hits of a scan (negative = all), drop PSMs without an
     unlocalised modification.  Returns (list of PSM dicts for pack_batch, list of scans).
     ``match_save``: the reference dumps every PSM it is about to score over the previous one
-    (`__main__.py:148-149`), so what it leaves behind is the last one: that is what is written here."""
+    (`__main__.py:148-149`), so what it leaves behind is the last one: that is what is written here.
+    ``reported``: a list that receives the ``reported_positions`` of every picked PSM."""
     picked, scans = [], []
     last = None
     for _, group in groupby(psms, lambda m: m["scan"]):
@@ -94,6 +111,9 @@ def select_psms(psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment
                                max_charge=min(max_fragment_charge, psm_charge(match, spectrum) - 1),
                                aux_pos=const_pos, aux_mass=const_masses))
             scans.append(match["scan"])
+            if reported is not None:
+                reported.append(reported_positions(residues, mod_mass, match["peptide"], match["mod_positions"], match["mod_masses"],
+                                                   mod_correction_tol, zero_based))
             last = (spectrum, match)
     if match_save and last is not None:
         save_match(*last)
@@ -116,25 +136,29 @@ def pack_hits(picked, scans):
 
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
-             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None):
+             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
     nan -- and are reported through ``log`` (a callable taking one string) with their count, scans and codes.
     ``evidence=True`` appends three fields per row, ';'-joined per site (``evidence_fields``): Depth, SiteIons, CompScore.
     ``ions``: a list that receives the ion table of the scored PSMs, one ``ion_fields`` row per record behind the PSM's
-    scan and its hit number inside the scan (``write_ions_tsv``)."""
+    scan and its hit number inside the scan (``write_ions_tsv``).
+    ``reported=True`` appends three fields per row (``reported_fields``): the search engine's own site assignment as a
+    sequence, its PepScore, and the ambiguity of the winner against it -- did Ascore move the site, and by how much."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
+    where = [] if reported else None
     picked, scans = select_psms(psms, spectra_map, residues, mod_mass, hit_depth, max_fragment_charge,
-                                mod_correction_tol, zero_based, match_save)
+                                mod_correction_tol, zero_based, match_save, reported=where)
     if not picked:
         return []
     batch = pack_hits(picked, scans)
+    named = [[sig_bits_of(p["peptide"], q, residues)] for p, q in zip(picked, where)] if reported else None
     # One PSM the kernels cannot take (longer than 64 residues, more than 15 000 site assignments,
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.
-    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None)
+    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None, named=named)
     bad = np.flatnonzero(res["status"])
     if bad.size:
         import warnings
@@ -147,6 +171,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
             log("set-aside scans: %s%s" % (shown, " ..." if bad.size > 50 else ""))
     ok = (res["status"] == 0) & (res["n_sig"] > 0)
     seqs = ascore.format_batch(batch, res["best_sig"], valid=ok.astype(np.int32))   # every string in one call
+    if reported:                                 # (one query per PSM: record i belongs to PSM i)
+        rep_seqs = ascore.format_batch(batch, res["named"]["sig_bits"], valid=(res["named"]["kind"] >= 2).astype(np.int32))
     rows = []
     hit = 0
     for i, psm in enumerate(picked):
@@ -154,15 +180,27 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         if ions is not None:
             ions.extend([scans[i], hit] + ion_fields(rec) for rec in res["ions"][res["ion_off"][i]:res["ion_off"][i + 1]])
         if res["status"][i]:
-            rows.append([scans[i], "", float("nan"), "", ""] + (["", "", ""] if evidence else []))
+            rows.append([scans[i], "", float("nan"), "", ""] + (["", "", ""] if evidence else []) + (["", "", ""] if reported else []))
             continue
         k = psm["n_of_mod"]
         ascores = ";".join(str(s) for s in res["ascores"][i, :k])
         alts = ";".join(",".join(str(q) for q in ascore.alt_positions(m, psm["peptide"].encode("utf8")))
                         for m in res["alt_mask"][i, :k])
         rows.append([scans[i], seqs[i], float(res["best_score"][i]), ascores, alts] +
-                    (evidence_fields(res["evidence"][i, :k]) if evidence else []))
+                    (evidence_fields(res["evidence"][i, :k]) if evidence else []) +
+                    (reported_fields(res["named"][i], rep_seqs[i]) if reported else []))
     return rows
+
+
+def reported_fields(rec, sequence):
+    """The three ``--reported`` fields of one PSM from the named record of the search engine's site assignment:
+    ReportedSequence -- that assignment in the notation of LocalizedSequence; ReportedPepScore -- its PepScore;
+    ReportedAscore -- the ambiguity of the winner against it (``0``: it IS the winner; ``tie``: its PepScore ties the
+    winner's).  All empty where the reported positions are no site assignment of the PSM, or the PSM was not scored."""
+    kind = int(rec["kind"])
+    if kind < 2:
+        return ["", "", ""]
+    return [sequence, repr(float(rec["pep_score"])), "0" if kind == 2 else ("tie" if kind == 3 else str(rec["ambiguity"]))]
 
 
 def evidence_fields(ev):
@@ -201,11 +239,11 @@ def write_ions_tsv(ion_rows, path):
             out.write("\t".join("%s" % f for f in row) + "\n")
 
 
-def write_tsv(rows, path, evidence=False):
+def write_tsv(rows, path, evidence=False, reported=False):
     """Same file pandas' ``DataFrame(rows, columns=COLUMNS).to_csv(path, sep="\\t", index=False)``
     writes in the reference (`__main__.py:166-172`); ``evidence=True``: the rows of ``localize(..., evidence=True)``,
-    with their three columns behind the reference's."""
+    with their three columns behind the reference's; ``reported=True``: those of ``localize(..., reported=True)`` behind them."""
     with open(path, "w") as out:
-        out.write("\t".join(COLUMNS + (EVIDENCE_COLUMNS if evidence else ())) + "\n")
+        out.write("\t".join(COLUMNS + (EVIDENCE_COLUMNS if evidence else ()) + (REPORTED_COLUMNS if reported else ())) + "\n")
         for scan, seq, pep_score, ascores, alts, *more in rows:
             out.write("\t".join(["%s" % scan, "%s" % seq, repr(float(pep_score)), ascores, alts] + list(more)) + "\n")

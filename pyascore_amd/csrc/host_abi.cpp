@@ -62,6 +62,7 @@ void pya_destroy(pya_handle *h) {
         if (ps) (void)hipHostFree(ps);
     if (h->evid_host) (void)hipHostFree(h->evid_host);
     if (h->ions_host) (void)hipHostFree(h->ions_host);
+    if (h->named_host) (void)hipHostFree(h->named_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->run_stream) (void)hipStreamDestroy(h->run_stream);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);

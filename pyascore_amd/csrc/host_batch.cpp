@@ -146,6 +146,68 @@ static int ions_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out,
     return PYA_OK;
 }
 
+/* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
+ * counts, [n_q * n_top] scores -- zeroed */
+static int named_host_block(pya_handle *h, uint64_t n_q) {
+    const size_t bytes = (size_t)n_q * (sizeof(pya_named) + 8 * (size_t)h->n_top);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->named_cap < bytes) {
+        if (h->named_host) (void)hipHostFree(h->named_host);
+        h->named_host = nullptr;
+        h->named_cap = 0;
+        HIPCHK(h, hipHostMalloc((void **)&h->named_host, bytes + bytes / 4, hipHostMallocDefault));
+        h->named_cap = bytes + bytes / 4;
+    }
+    if (bytes) std::memset(h->named_host, 0, bytes);
+    return PYA_OK;
+}
+
+/* ... a plan's slice of the queries (the PSMs from `lo` of the call) on its way to the device on `st`, ahead of the plan's
+ * kernels: the offsets rebased to the slice live in the plan, the bits are the caller's, borrowed for the call */
+static int named_upload(pya_handle *h, pya_plan *p, const NamedReq *nq, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    const int64_t base = nq->q_off[lo], cnt = nq->q_off[lo + n] - base;
+    if (n == 0 || cnt == 0) return PYA_OK;
+    p->named_q_off.resize(n + 1);
+    for (uint64_t i = 0; i <= n; i++) p->named_q_off[i] = nq->q_off[lo + i] - base;
+    HIPCHK(h, p->d_named_q_off.alloc(n + 1));
+    HIPCHK(h, p->d_named_q_bits.alloc((size_t)cnt));
+    HIPCHK(h, p->d_named.alloc((size_t)cnt * (sizeof(pya_named) + 8 * (size_t)h->n_top)));
+    HIPCHK(h, hipMemcpyAsync(p->d_named_q_off.p, p->named_q_off.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(p->d_named_q_bits.p, nq->q_bits + base, (size_t)cnt * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    return PYA_OK;
+}
+
+/* ... the named launch of a plan behind its kernels on `st`, and its records on their way into the handle's pinned block at
+ * the slice's first query (asynchronous: whoever waits for the chunk's results waits for them too) */
+static int named_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, const NamedReq *nq, uint64_t lo, uint64_t n_q,
+                            hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    const int64_t base = nq->q_off[lo], cnt = nq->q_off[lo + n] - base;
+    if (n == 0 || cnt == 0) return PYA_OK;
+    const size_t row = 4 * (size_t)h->n_top;
+    unsigned char *d_rec = p->d_named.p, *d_cnt = d_rec + (size_t)cnt * sizeof(pya_named), *d_sc = d_cnt + (size_t)cnt * row;
+    const int rc = pya_plan_named(p, d_out, st, p->d_named_q_off.p, p->d_named_q_bits.p, (uint64_t)cnt, (pya_named *)d_rec,
+                                  nq->counts ? (int32_t *)d_cnt : nullptr, nq->scores ? (float *)d_sc : nullptr);
+    if (rc) return rc;
+    unsigned char *h_rec = h->named_host, *h_cnt = h_rec + (size_t)n_q * sizeof(pya_named), *h_sc = h_cnt + (size_t)n_q * row;
+    HIPCHK(h, hipMemcpyAsync(h_rec + (size_t)base * sizeof(pya_named), d_rec, (size_t)cnt * sizeof(pya_named), hipMemcpyDeviceToHost, st));
+    if (nq->counts) HIPCHK(h, hipMemcpyAsync(h_cnt + (size_t)base * row, d_cnt, (size_t)cnt * row, hipMemcpyDeviceToHost, st));
+    if (nq->scores) HIPCHK(h, hipMemcpyAsync(h_sc + (size_t)base * row, d_sc, (size_t)cnt * row, hipMemcpyDeviceToHost, st));
+    return PYA_OK;
+}
+
+/* ... and, once they have arrived, out of the block into the caller's arrays */
+static void named_deliver(pya_handle *h, const NamedReq *nq, uint64_t lo, uint64_t hi, uint64_t n_q) {
+    const int64_t base = nq->q_off[lo], cnt = nq->q_off[hi] - base;
+    if (cnt == 0) return;
+    const size_t row = 4 * (size_t)h->n_top;
+    const unsigned char *h_rec = h->named_host, *h_cnt = h_rec + (size_t)n_q * sizeof(pya_named), *h_sc = h_cnt + (size_t)n_q * row;
+    std::memcpy(nq->out + base, h_rec + (size_t)base * sizeof(pya_named), (size_t)cnt * sizeof(pya_named));
+    if (nq->counts) std::memcpy(nq->counts + (size_t)base * h->n_top, h_cnt + (size_t)base * row, (size_t)cnt * row);
+    if (nq->scores) std::memcpy(nq->scores + (size_t)base * h->n_top, h_sc + (size_t)base * row, (size_t)cnt * row);
+}
+
 /* Big pya_score_batch calls: the batch is cut into chunks of consecutive PSMs that fit the device
  * budget and the chunks are pipelined -- a helper thread streams the spectra of chunk c + 1 over
  * PCIe (the bound of this entry point: 16, 12 or 8 bytes per peak) into the other slot of a two-slot ring
@@ -153,8 +215,9 @@ static int ions_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out,
  * stream.  A call of any size completes; it never fails for lack of workspace. */
 static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp,
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
-                               const uint8_t *pre_sites) {
+                               const uint8_t *pre_sites, const NamedReq *nq) {
     const size_t nchunk = cuts.size() - 1;
+    const uint64_t n_q = nq ? (uint64_t)nq->q_off[b->n_psm] : 0;
     /* the spectra [first, last) of chunk c: its PSMs' own unless spectra are shared -- then from the first PSM's to the last
      * PSM's, each uploaded once (a group cut in two travels with both parts) */
     auto spec_lo = [&](size_t c) -> uint64_t { return sh ? sh->spec_of[cuts[c]] : cuts[c]; };
@@ -254,6 +317,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         }
         pya_results d_out = {mk, p->d_best_score.p, p->d_best_sig.p, p->d_n_sig_out.p, p->d_ascores.p, p->d_alt.p};
         const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
+        if (nq && (rc = named_upload(h, p, nq, lo, h->run_stream))) return finish(rc);
         rc = pya_plan_run_typed(p, &d_sp, h->run_stream, &d_out);
         if (rc) return finish(rc);
         /* status + results are adjacent in the arena: one asynchronous copy into pinned memory */
@@ -271,6 +335,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if (e != hipSuccess) return finish(h->hip_fail(e, "results copy"));
         if ((flags & PYA_FLAG_EVIDENCE) && (rc = evidence_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_IONS) && (rc = ions_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
+        if (nq && (rc = named_behind_run(h, p, &d_out, nq, lo, n_q, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -309,6 +374,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         std::memcpy(out->n_sig + lo, sg + (p->o_n_sig_out - o), n * sizeof(int32_t));
         std::memcpy(out->ascores + lo * mk, sg + (p->o_ascores - o), n * mk * sizeof(float));
         std::memcpy(out->alt_mask + lo * mk, sg + (p->o_alt - o), n * mk * sizeof(uint64_t));
+        if (nq) named_deliver(h, nq, lo, lo + n, n_q);
         cur = std::move(next);
     }
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
@@ -318,7 +384,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
 
 /* pya_score_batch (sh == nullptr: PSM i has spectrum i) and pya_score_batch_shared */
 static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp, uint32_t flags,
-                            const pya_results *out) {
+                            const pya_results *out, const NamedReq *nq = nullptr) {
     const uint64_t n_spec = sh ? sh->n_spectra : b->n_psm;       /* b->peak_off has n_spec + 1 entries */
     const void *mz = sp.mz, *inten = sp.intensity;
     h->last_status.clear();
@@ -343,6 +409,20 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if (!out->best_score || !out->best_sig || !out->n_sig || !out->ascores || !out->alt_mask)
         return h->fail(PYA_ERR_ARG, -1, "NULL array in results");
     if (b->peak_off[n_spec] < b->peak_off[0]) return h->fail(PYA_ERR_ARG, -1, "peak_off is not monotone");
+    /* named localisations: the queries are checked before anything is scored; the plans take the per-stage launches */
+    uint64_t n_q = 0;
+    if (nq) {
+        if (!nq->q_off) return h->fail(PYA_ERR_ARG, -1, "NULL query offsets");
+        if (nq->q_off[0] != 0) return h->fail(PYA_ERR_ARG, 0, "PSM 0: the query offsets do not start at 0");
+        for (uint64_t i = 0; i < b->n_psm; i++)
+            if (nq->q_off[i + 1] < nq->q_off[i])
+                return h->fail(PYA_ERR_ARG, (int64_t)i, "PSM %llu: the query offsets decrease", (unsigned long long)i);
+        n_q = (uint64_t)nq->q_off[b->n_psm];
+        if (n_q && (!nq->q_bits || !nq->out)) return h->fail(PYA_ERR_ARG, -1, "NULL query signatures or named records");
+        const int rc_nm = named_host_block(h, n_q);
+        if (rc_nm) return rc_nm;
+        flags |= PYA_FLAG_NAMED;
+    }
     /* (not while the records of a pya_score_one PSM are retained in the one-PSM workspace: this call would overwrite
      * what pya_get_pep_scores / pya_calculate_ambiguity still read there) */
     const bool one_view_live = h->kept && h->kept == h->one.view;
@@ -351,7 +431,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         if (rc_ev) return rc_ev;
     }
     /* (a batch of one with PYA_FLAG_EVIDENCE or PYA_FLAG_IONS takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS)) && !one_view_live && types == PYA_SPEC_F64_F64) {
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -394,7 +474,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
             }
             cuts.push_back(b->n_psm);
             h->last_chunks = cuts.size() - 1;
-            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data());
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq);
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -440,6 +520,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     const uint32_t mk = out->max_k;
     pya_results d_out = {mk, p->d_best_score.p, p->d_best_sig.p, p->d_n_sig_out.p, p->d_ascores.p, p->d_alt.p};
     const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
+    if (nq && (rc = named_upload(h, p, nq, 0, nullptr))) return rc;
     rc = pya_plan_run_typed(p, &d_sp, nullptr, &d_out);
     if (rc) return rc;
     if (p->d2h_bytes <= kStageLimit) {
@@ -478,6 +559,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         HIPCHK(h, hipStreamSynchronize(nullptr));
         h->ions_valid = true;
     }
+    if (nq) {
+        if ((rc = named_behind_run(h, p, &d_out, nq, 0, n_q, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        named_deliver(h, nq, 0, n, n_q);
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -494,16 +580,16 @@ int pya_score_batch(pya_handle *h, const pya_batch *b, const double *mz, const d
 }
 
 static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const pya_typed_spectra &sp,
-                              uint32_t flags, const pya_results *out) {
+                              uint32_t flags, const pya_results *out, const NamedReq *nq = nullptr) {
     h->last_status.clear();
     h->evid_valid = false;
     h->ions_valid = false;
-    if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out);
+    if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
     if (rc) return rc;
     const SpecShare sh = {spec_of, n_spectra, 0u};
-    return score_batch_impl(h, b, &sh, sp, flags, out);
+    return score_batch_impl(h, b, &sh, sp, flags, out, nq);
 }
 
 int pya_score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const double *mz,
@@ -518,6 +604,15 @@ int pya_score_batch_typed(pya_handle *h, const pya_batch *b, const uint32_t *spe
     if (!h || !b || !out) return PYA_ERR_ARG;
     if (!spectra) return h->fail(PYA_ERR_ARG, -1, "NULL spectrum arrays");
     return spec_of ? score_batch_shared(h, b, spec_of, n_spectra, *spectra, flags, out) : score_batch_impl(h, b, nullptr, *spectra, flags, out);
+}
+
+int pya_score_batch_named(pya_handle *h, const pya_batch *b, const uint32_t *spec_of, uint64_t n_spectra, const pya_typed_spectra *spectra,
+                          uint32_t flags, const pya_results *out, const int64_t *q_off, const uint64_t *q_bits, pya_named *named_out,
+                          int32_t *counts, float *scores) {
+    if (!h || !b || !out) return PYA_ERR_ARG;
+    if (!spectra) return h->fail(PYA_ERR_ARG, -1, "NULL spectrum arrays");
+    const NamedReq nq = {q_off, q_bits, named_out, counts, scores};
+    return spec_of ? score_batch_shared(h, b, spec_of, n_spectra, *spectra, flags, out, &nq) : score_batch_impl(h, b, nullptr, *spectra, flags, out, &nq);
 }
 
 /* (include/pyascore_debug.h) */

@@ -24,6 +24,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -123,6 +124,10 @@ uint32_t pya_ions_scan_tiles(uint32_t n);
 int pya_launch_ions(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const void *d_evid, int64_t *d_off, void *d_out, uint64_t cap,
                     uint32_t *d_over, uint32_t l_cap, uint32_t list_cap, hipStream_t stream);
 int pya_launch_ions_scan(int64_t *d_off, uint32_t n, uint64_t *d_tiles, hipStream_t stream);
+size_t pya_named_lds_bytes(uint32_t l_cap, uint32_t list_cap);
+int pya_launch_named(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_q_off, const uint64_t *d_q_bits,
+                     uint64_t n_q, void *d_out, int32_t *d_counts, float *d_scores, uint32_t *d_over, uint32_t l_cap,
+                     uint32_t list_cap, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -325,6 +330,10 @@ struct pya_handle {
     size_t ions_cap = 0;                      /* records the block has room for */
     std::vector<int64_t> ions_off;            /* [n_psm + 1] of the batch they belong to */
     bool ions_valid = false;                  /* the last batch was scored with the flag */
+    /* pya_score_batch_named: the records of the call's queries, pinned so that a chunk's slice comes back asynchronously
+     * behind its results: [n_q] pya_named, then [n_q * n_top] counts and [n_q * n_top] scores where asked for */
+    unsigned char *named_host = nullptr;
+    size_t named_cap = 0;                     /* bytes of the block */
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -645,6 +654,16 @@ struct pya_plan {
     hipEvent_t ev_ions = nullptr;
     uint32_t ions_max_k = 0;
     int ions_state = 0;
+    /* pya_plan_named: the report of the last call (PSMs whose query range is not inside the output: count, 0xffffffff -
+     * the smallest), the event pya_plan_check waits for, whether the last run has been asked; a pya_score_batch_named plan's
+     * slice of the queries (host offsets rebased to the chunk: they outlive the asynchronous upload) and its records */
+    DevBuf<uint32_t> d_named_over;
+    hipEvent_t ev_named = nullptr;
+    bool named_asked = false;
+    std::vector<int64_t> named_q_off;
+    DevBuf<int64_t> d_named_q_off;
+    DevBuf<uint64_t> d_named_q_bits;
+    DevBuf<unsigned char> d_named;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -656,6 +675,7 @@ struct pya_plan {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_evid) (void)hipEventDestroy(ev_evid);
         if (ev_ions) (void)hipEventDestroy(ev_ions);
+        if (ev_named) (void)hipEventDestroy(ev_named);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
@@ -767,5 +787,19 @@ int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");
 static_assert(sizeof(pya_ion) == 16, "pya_ion is one 16-byte store of ions.hip");
+static_assert(sizeof(pya_named) == 32 && offsetof(pya_named, pep_score) == 8 && offsetof(pya_named, ambiguity) == 12 &&
+                  offsetof(pya_named, total_fragments) == 16 && offsetof(pya_named, kind) == 20 && offsetof(pya_named, depth) == 21 &&
+                  offsetof(pya_named, n_moved) == 22 && offsetof(pya_named, reserved) == 23 && offsetof(pya_named, ref_matched) == 24 &&
+                  offsetof(pya_named, ref_possible) == 26 && offsetof(pya_named, comp_matched) == 28 &&
+                  offsetof(pya_named, comp_possible) == 30,
+              "pya_named is two 16-byte stores of named.hip");
+/* pya_score_batch_named's queries and outputs (host arrays of the caller), nullptr for the other batch entry points */
+struct NamedReq {
+    const int64_t *q_off;
+    const uint64_t *q_bits;
+    pya_named *out;
+    int32_t *counts;
+    float *scores;
+};
 
 #endif

@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -336,6 +336,7 @@ int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_strea
     p->last_stream = st;
     p->ran = true;
     p->ions_state = 0;                       /* (counts, offsets and the overflow report belonged to the run before) */
+    p->named_asked = false;
     p->dev = d;
     return rc;
 }
@@ -430,9 +431,18 @@ int pya_plan_check(pya_plan *p) {
     const bool skip = (p->flags & PYA_FLAG_SKIP_INVALID) != 0;
     if (skip) h->last_status = st;
     const int rc = check_status(h, st.data(), p->n_psm, skip);
-    if (rc || p->ions_state != 2) return rc;
-    /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
+    if (rc) return rc;
     uint32_t over[2] = {0u, 0u};
+    if (p->named_asked) {
+        /* the last pya_plan_named of this run: PSMs whose query range is not inside the output of the call */
+        HIPCHK(h, hipEventSynchronize(p->ev_named));
+        HIPCHK(h, hipMemcpy(over, p->d_named_over.p, sizeof(over), hipMemcpyDeviceToHost));
+        if (over[0])
+            return h->fail(PYA_ERR_LIMIT, (int64_t)(0xffffffffu - over[1]), "pya_plan_named: the query ranges of %u PSMs (PSM %u the first) "
+                           "are not inside the n_q records of the call; nothing of them was written", over[0], 0xffffffffu - over[1]);
+    }
+    if (p->ions_state != 2) return PYA_OK;
+    /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
     HIPCHK(h, hipEventSynchronize(p->ev_ions));
     HIPCHK(h, hipMemcpy(over, p->d_ions_over.p, sizeof(over), hipMemcpyDeviceToHost));
     if (over[0])
@@ -441,20 +451,13 @@ int pya_plan_check(pya_plan *p) {
     return PYA_OK;
 }
 
-/* The evidence stage: one launch for the PSMs inside the fast limits, sized by THEIR longest peptide and fragment list,
- * one for the plan's general PSMs with the general kernel's caps (a single 400-residue peptide must not set the LDS, hence
- * the occupancy, of a batch of 20-mers). */
-int pya_plan_evidence(pya_plan *p, const pya_results *r, void *hip_stream, pya_evidence *d_out) {
-    if (!p || !r) return PYA_ERR_ARG;
+namespace {
+/* What a stage behind a run does before it launches.  Two launches: one for the PSMs inside the fast limits, sized by THEIR
+ * longest peptide and fragment list, one for the plan's general PSMs with the general kernel's caps (a single 400-residue
+ * peptide must not set the LDS, hence the occupancy, of a batch of 20-mers).  This sets the caps of the first (once per plan
+ * and set of loss sums), asks whether `lds_bytes` of either fits a compute unit, and makes `st` wait for the last run. */
+int stage_behind_run(pya_plan *p, hipStream_t st, const char *who, const char *kernel, size_t (*lds_bytes)(uint32_t, uint32_t)) {
     pya_handle *h = p->h;
-    if (p->n_psm == 0) return PYA_OK;
-    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_evidence: the plan has not been run");
-    if (!d_out || !r->best_score || !r->best_sig || !r->n_sig || !r->ascores || !r->alt_mask)
-        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_evidence");
-    if (r->max_k < p->max_k)
-        return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)", r->max_k, p->max_k);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)hip_stream;
     const uint32_t n_uniq = (uint32_t)h->cfg.n_uniq;
     if (!p->evid_caps || p->evid_uniq != n_uniq) {
         std::vector<uint32_t> fast_ids;
@@ -480,16 +483,33 @@ int pya_plan_evidence(pya_plan *p, const pya_results *r, void *hip_stream, pya_e
         p->evid_uniq = n_uniq;
         p->evid_caps = true;
     }
-    if (pya_evidence_lds_bytes(p->evid_l_cap, p->evid_list_cap) > kMaxLds ||
-        (!p->gen_ids.empty() && pya_evidence_lds_bytes(p->gen_l_cap, p->gen_list_cap) > kMaxLds))
-        return h->fail(PYA_ERR_LIMIT, -1, "pya_plan_evidence: %u fragments per ion type exceed the evidence kernel's room",
-                       std::max(p->evid_list_cap, p->gen_ids.empty() ? 0u : p->gen_list_cap));
+    if (lds_bytes(p->evid_l_cap, p->evid_list_cap) > kMaxLds || (!p->gen_ids.empty() && lds_bytes(p->gen_l_cap, p->gen_list_cap) > kMaxLds))
+        return h->fail(PYA_ERR_LIMIT, -1, "%s: %u fragments per ion type exceed the %s kernel's room", who,
+                       std::max(p->evid_list_cap, p->gen_ids.empty() ? 0u : p->gen_list_cap), kernel);
     /* behind the run: its stream has joined the side stream already (pya_plan_run_typed); another stream waits for it */
     if (st != p->last_stream) {
         if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
         HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
         HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
     }
+    return PYA_OK;
+}
+}  // namespace
+
+/* The evidence stage (csrc/evidence.hip) */
+int pya_plan_evidence(pya_plan *p, const pya_results *r, void *hip_stream, pya_evidence *d_out) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_evidence: the plan has not been run");
+    if (!d_out || !r->best_score || !r->best_sig || !r->n_sig || !r->ascores || !r->alt_mask)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_evidence");
+    if (r->max_k < p->max_k)
+        return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)", r->max_k, p->max_k);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int rc = stage_behind_run(p, st, "pya_plan_evidence", "evidence", pya_evidence_lds_bytes);
+    if (rc) return rc;
     shared_tables(h, p->dev);
     BatchDev d = p->dev;
     d.best_score = r->best_score;
@@ -503,6 +523,41 @@ int pya_plan_evidence(pya_plan *p, const pya_results *r, void *hip_stream, pya_e
     if (!e && !p->gen_ids.empty())
         e = pya_launch_evidence(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_out, p->gen_l_cap, p->gen_list_cap, st);
     if (e) return h->hip_fail((hipError_t)e, "evidence launch");
+    return PYA_OK;
+}
+
+/* The named stage (csrc/named.hip): the same two launches behind the same wait.  It reads best_sig and n_sig of the caller's
+ * results structure and nothing else of it. */
+int pya_plan_named(pya_plan *p, const pya_results *r, void *hip_stream, const int64_t *d_q_off, const uint64_t *d_q_bits, uint64_t n_q,
+                   pya_named *d_out, int32_t *d_counts, float *d_scores) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0 || n_q == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_named: the plan has not been run");
+    if (!d_q_off || !d_q_bits || !d_out || !r->best_score || !r->best_sig || !r->n_sig)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_named");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->d_named_over.p) HIPCHK(h, p->d_named_over.alloc(2));
+    if (!p->ev_named) HIPCHK(h, hipEventCreateWithFlags(&p->ev_named, hipEventDisableTiming));
+    const int rc = stage_behind_run(p, st, "pya_plan_named", "named", pya_named_lds_bytes);
+    if (rc) return rc;
+    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
+    if (p->named_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_named, 0));
+    HIPCHK(h, hipMemsetAsync(p->d_named_over.p, 0, 2 * sizeof(uint32_t), st));
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.best_score = r->best_score;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    int e = pya_launch_named(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, d_q_off, d_q_bits, n_q, d_out, d_counts,
+                             d_scores, p->d_named_over.p, p->evid_l_cap, p->evid_list_cap, st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_named(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_q_off, d_q_bits, n_q, d_out, d_counts, d_scores,
+                             p->d_named_over.p, p->gen_l_cap, p->gen_list_cap, st);
+    if (e) return h->hip_fail((hipError_t)e, "named launch");
+    HIPCHK(h, hipEventRecord(p->ev_named, st));
+    p->named_asked = true;
     return PYA_OK;
 }
 

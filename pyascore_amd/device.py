@@ -23,9 +23,10 @@ class DevicePlan:
     ``evidence()`` after ``run()`` gives the evidence records of every site (``pya_plan_evidence``); ``evidence=True``
     tells the plan at creation that they will be asked for (a plan of a handful of PSMs then takes the per-stage
     launches instead of the one-launch kernel).  ``ions()`` / ``ions=True``: the same for the ion records
-    (``pya_plan_ions_count``, ``pya_plan_ions``)."""
+    (``pya_plan_ions_count``, ``pya_plan_ions``).  ``named()`` / ``named=True``: the same for the records of localisations
+    the caller names (``pya_plan_named``)."""
 
-    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False):
+    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -54,7 +55,7 @@ class DevicePlan:
                        _as_ptr(m["aux_mass"]), _as_ptr(m["aux_off"]))
         self._plan = C.c_void_p()
         flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
-            (_lib.PYA_FLAG_IONS if ions else 0)
+            (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -154,6 +155,33 @@ class DevicePlan:
                 self.scorer._raise(rc)
         return off, out
 
+    def named(self, q_off, sig_bits, counts=False, scores=False):
+        """The named-localisation records of the last ``run()`` for the queries ``q_off`` (int64 device tensor
+        ``[n_psm + 1]``) / ``sig_bits`` (int64 device tensor holding the uint64 bit patterns, ``[n_q]``): a ``torch.uint8``
+        device tensor ``[n_q, 32]`` (one ``pya_named`` each; ``named_records`` turns a host copy into the structured array),
+        or ``(records, counts, scores)`` with ``counts`` int32 / ``scores`` float32 ``[n_q, n_top]`` (``None`` where not
+        asked for).  One launch family of the library behind the run on torch's current stream; nothing waits on the host:
+        the size of the output is ``sig_bits.numel()``, and no write passes it whatever ``q_off`` holds (``check()``
+        reports a PSM whose range does).  Valid for the results of the last run; may be called again with other queries."""
+        torch = self._torch
+        for t, what in ((q_off, "q_off"), (sig_bits, "sig_bits")):
+            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError("%s must be a contiguous one-dimensional int64 device tensor" % what)
+        if q_off.numel() != self.n_psm + 1:
+            raise ValueError("q_off must have n_psm + 1 entries")
+        n_q, n_top = int(sig_bits.numel()), self.scorer._n_top
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            out = torch.zeros((n_q, 32), dtype=torch.uint8, device=self.device)
+            d_counts = torch.zeros((n_q, n_top), dtype=torch.int32, device=self.device) if counts else None
+            d_scores = torch.zeros((n_q, n_top), dtype=torch.float32, device=self.device) if scores else None
+        rc = self._lib.pya_plan_named(self._plan, C.byref(self._res), stream, q_off.data_ptr(), sig_bits.data_ptr(), n_q,
+                                      out.data_ptr(), d_counts.data_ptr() if counts else None,
+                                      d_scores.data_ptr() if scores else None)
+        if rc:
+            self.scorer._raise(rc)
+        return (out, d_counts, d_scores) if counts or scores else out
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -200,6 +228,7 @@ class DevicePlan:
 
 EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)
+NAMED_DTYPE = np.dtype(_lib.NAMED_DTYPE)
 
 
 def evidence_rows(raw):
@@ -231,3 +260,12 @@ def ion_records(raw):
     if a.ndim != 2 or a.shape[1] != ION_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (total, %d)" % ION_DTYPE.itemsize)
     return a.view(ION_DTYPE).reshape(a.shape[0])
+
+
+def named_records(raw):
+    """A host copy of the records of ``DevicePlan.named()`` (``.cpu().numpy()``, uint8 ``[n_q, 32]``) as the structured
+    array ``PyAscore.score_batch(..., named=...)`` returns; a view, no copy."""
+    a = np.ascontiguousarray(raw)
+    if a.ndim != 2 or a.shape[1] != NAMED_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n_q, %d)" % NAMED_DTYPE.itemsize)
+    return a.view(NAMED_DTYPE).reshape(a.shape[0])
