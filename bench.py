@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- PSMs/s of the Ascore hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--psms M] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--psms M] [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path (bin_spectra -> score_signatures -> rank_and_localize)
 over one batch of synthetic PSMs of the named BASELINE config whose spectra are already
@@ -11,9 +11,15 @@ The job is ONE seeded description (per-PSM shapes) cut by pyascore_amd.shard.par
 work-balanced contiguous ranges; a rank generates and scores its own range only.  --scaling strong
 keeps the job size fixed as N grows (e.g. --config cfg3 --scaling strong: 1M PSMs over N GPUs).
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
+A plain run does what the headline needs and nothing else: it generates the job, builds the plan, warms
+up, times the steps, writes --dump-outputs and prints ONE JSON line on rank 0, including
   roofline     : the dominant kernel's achieved algorithmic GB/s vs the 8 TB/s HBM peak,
-                 timed with HIP events on the launch stream inside the timed region;
+                 timed with HIP events on the launch stream inside the timed region.
+--full adds every measurement that takes runs of its own, each under its own key of the same line:
+  roofline     : + the copy rate this device reaches (`achievable_peak`) and, per kernel family, the
+                 HBM traffic and busy shares of the newest committed counters of the config;
+  host_api     : host arrays in -> host results out (PyAscore.score_batch) beside what PCIe alone costs;
+  other_configs: BASELINE's other single-GPU workloads and the dense-spectrum legs, a child process each;
   cpu_baseline : the reference's own C++ core (oracle/_ref, if its prebuilt library travelled;
                  otherwise this repo's CPU restatement) on the host cores, one PROCESS per core
                  (fresh children started before this program's first GPU call), on a bounded
@@ -561,18 +567,22 @@ def main():
     ap.add_argument("--blocks", type=int, default=5,
                     help="timed blocks of --steps steps each (every block bracketed by barrier + synchronize); the line "
                          "reports the MEDIAN block, and every block's ms per step beside it")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else this program measures, in runs of their own: the CPU baseline, "
+                         "`other_configs`, `host_api`, the device's copy rate and the committed counters of `roofline` "
+                         "(about a minute more); the --no-... options below leave one of them out again")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without `cpu_baseline`")
     ap.add_argument("--debug", action="append", default=[], metavar="KEY=VALUE",
                     help="A/B experiments: a debug switch of the scorer (include/pyascore_debug.h), e.g. --debug PYA_NO_FUSED=1; "
                          "the line then carries `debug_switches` and is not the headline")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="N = 1, default cfg2 run only: leave out the short timed legs of BASELINE's other configs "
-                         "(`other_configs` in the line)")
+                    help="--full without the short timed legs of BASELINE's other configs (`other_configs` in the line, "
+                         "N = 1, default cfg2 run only)")
     ap.add_argument("--other-blocks", type=int, default=2, help="timed blocks per config of `other_configs`")
     ap.add_argument("--leg", choices=sorted(LEGS), default=None,
                     help="(internal) run ONE leg of `other_configs` in this process and print its record")
     ap.add_argument("--no-host-api", action="store_true",
-                    help="skip the host-array legs (profiling runs: only the timed device-resident steps launch kernels)")
+                    help="--full without the host-array legs (`host_api`)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, rank 0 writes the results of the LAST timed step (what the timed path hands "
                          "its caller: best_score, n_sig, best_sig, ascores, alt_mask of every PSM of the job) as DIR/<name>.npy "
@@ -623,11 +633,11 @@ def main():
     job_max_k = max(1, int(desc["n_mod"].max()))
     longest = max(h - l for l, h in ranges)
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(batch, settings)
     default_size = args.psms is None and args.max_charge is None and args.scaling == "weak" and not args.debug
     others = None
-    if world == 1 and default_size and args.config == "cfg2" and not args.no_other_configs:
+    if args.full and world == 1 and default_size and args.config == "cfg2" and not args.no_other_configs:
         # BASELINE's other workloads and the dense-spectrum legs on this GPU, so that the driver's record carries every
         # config: child processes, one after the other, BEFORE this process touches the GPU.  The headline fields are
         # cfg2's and only cfg2's.
@@ -720,7 +730,7 @@ def main():
         achieved = alg / (kern_ms[dom] * 1e-3) / 1e9 if kern_ms[dom] > 0 else 0.0
         # host API rate (host arrays in -> host results out; PCIe and host pre-pass included)
         host = None
-        if not args.no_host_api:
+        if args.full and not args.no_host_api:
             scorer.score_batch(batch)                          # first call allocates the workspace (reused afterwards)
             host_s = []
             for _ in range(3):
@@ -748,8 +758,10 @@ def main():
                     "note": "PyAscore.score_batch: host arrays in, host results out (chunked, upload pipelined "
                             "with planning, kernels and result copies); pcie_only = the same bytes copied up "
                             "and back with nothing else"}
-        copy_gbs = achievable_hbm_gbs(torch, dev)
-        counters, fams = profiled_counters(args.config, kern_ms, names, default_size, scorer._lib.pya_version().decode())
+        # (a plain run launches nothing beside its steps and reads no counters: those keys of `roofline` are null)
+        copy_gbs = achievable_hbm_gbs(torch, dev) if args.full else None
+        counters, fams = (profiled_counters(args.config, kern_ms, names, default_size, scorer._lib.pya_version().decode())
+                          if args.full else (None, None))
         dom_c = (fams or {}).get(names[dom], {})
         traffic_path = counters["whole_path_traffic"] if counters else None
         line = {
@@ -782,7 +794,8 @@ def main():
                          "whole_step_frac": (alg / (min(float(kern_ms.sum()), 1e3 * elapsed / max(args.steps, 1)) * 1e-3) / 1e9 / HBM_PEAK_GBS) if kern_ms.sum() > 0 else 0.0,
                          "families_overlap": bool(float(kern_ms.sum()) > 1.001 * 1e3 * elapsed / max(args.steps, 1)),
                          "traffic_source": counters["source"] if counters and counters.get("families") is not None else None,
-                         "traffic_refused": counters.get("refused") if counters else "no committed counters for this config",
+                         "traffic_refused": counters.get("refused") if counters else (
+                             "no committed counters for this config" if args.full else "the committed counters are read with --full"),
                          # HBM bytes the dominant kernel family really moved (counters) over its live duration
                          "hbm_actual": dom_c.get("hbm_actual"),
                          # what actually bounds the kernel: share of SIMD time its vector instructions need at the
@@ -793,7 +806,7 @@ def main():
                          "traffic_whole_path": traffic_path,
                          "traffic_over_algorithmic": (traffic_path / alg) if traffic_path else None,
                          "algorithmic_bytes_per_launch": alg,
-                         "achievable_peak": copy_gbs, "frac_of_achievable": achieved / copy_gbs,
+                         "achievable_peak": copy_gbs, "frac_of_achievable": achieved / copy_gbs if copy_gbs else None,
                          "whole_path_gbs": alg / (min(float(kern_ms.sum()), 1e3 * elapsed / max(args.steps, 1)) * 1e-3) / 1e9 if kern_ms.sum() > 0 else 0.0,
                          "kernel_ms": {n: float(m) for n, m in zip(names, kern_ms)},
                          "per_kernel": fams},

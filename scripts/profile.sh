@@ -13,7 +13,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 for c in $CFGS; do
   extra="--no-cpu-baseline"; [ "$c" = "cfg2" ] && extra=""
-  timeout 900 python3 bench.py --config $c $extra 2>$OUT/${TAG}_bench_$c.err | tail -1 > $OUT/${TAG}_bench_$c.json
+  timeout 900 python3 bench.py --full --config $c $extra 2>$OUT/${TAG}_bench_$c.err | tail -1 > $OUT/${TAG}_bench_$c.json
   [ -s $OUT/${TAG}_bench_$c.json ] && rm -f $OUT/${TAG}_bench_$c.err
 done
 for PCFG in $PCFGS; do

@@ -1,4 +1,4 @@
-"""The bench line the round commits (profiles/*_bench_cfg2.json, written by bench.py on the GPU box) keeps the driver's
+"""The bench line the round commits (profiles/*_bench_cfg2.json, written by bench.py --full on the GPU box) keeps the driver's
 contract and is consistent with itself and with the counters it names -- checked on the CPU, so that a hand-edited or
 stale record fails here: every contract key; value = PSMs / step time; roofline.achieved = algorithmic bytes of the
 workload (recomputed from the synthetic batch) / the dominant kernel family's duration; frac = achieved /
