@@ -91,6 +91,9 @@ extern "C" {
                             /* (pya_plan_ions_count / pya_plan_ions)                               */
 #define PYA_FLAG_NAMED 32u  /* pya_plan_create*: as PYA_FLAG_EVIDENCE, for pya_plan_named;          */
                             /* pya_score_batch*: no effect (pya_score_batch_named takes the queries) */
+#define PYA_FLAG_SITES 64u  /* pya_score_batch* / pya_score_batch_named: the site table of every PSM as */
+                            /* well (pya_last_batch_sites); pya_plan_create*: as PYA_FLAG_EVIDENCE      */
+                            /* (pya_plan_site_offsets / pya_plan_sites)                                 */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -207,6 +210,43 @@ typedef struct pya_named {         /* 32 bytes, two 16-byte stores */
     uint8_t kind, depth, n_moved, reserved;   /* PYA_NAMED_*; n_moved = n_of_mod - |winner AND query| */
     uint16_t ref_matched, ref_possible, comp_matched, comp_possible;   /* as in pya_evidence; COUNTED only */
 } pya_named;
+
+/* Site tables.  Everything above answers for one localisation (the winner), for the competitor the library picked per
+ * modified site, or for signatures the caller names; a site-level table has a row for EVERY modifiable residue of the
+ * peptide, and a delta score needs the runner-up.  Both are reductions over all site assignments of the PSM -- the
+ * reference's pep_scores list (Ascore.pyx:241-252, cpp/Ascore.cpp:53-139) -- done on the device: per PSM and modifiable
+ * residue, the best PepScore among the site assignments that modify the residue and the best among those that leave it
+ * unmodified (the two max-marginals).  One record per (PSM, modifiable residue), the residues of a PSM from the N- to the
+ * C-terminus, which is the bit order of sig bits; CSR per PSM through site_off[n_psm + 1], offsets the host knows from its
+ * pre-pass.  A PSM the host pre-pass set aside (PYA_FLAG_SKIP_INVALID) has an empty range.
+ *   Every score is the maximum of ScoreContainer.weighted_score over the matching records of the PSM's pep_scores, bit for
+ *   bit (what pya_get_pep_scores* returns from a PYA_FLAG_KEEP batch).
+ *   Which assignment is named when several attain the maximum ("attain" is float equality): best_sig if it is one of them,
+ *   otherwise the numerically smallest sig bits.  The rule does not depend on the reference's std::sort order.
+ *   So a residue of best_sig has with_score == best_score (bits) and with_sig == best_sig; any other residue has
+ *   without_score == best_score and without_sig == best_sig; the largest without_score among the residues of best_sig is
+ *   the runner-up localisation's PepScore, its without_sig the runner-up.  With n_of_mod == 1, without_score of the modified
+ *   residue has the bits of the PSM's evidence comp_score; for any n_of_mod, comp_score of modified site j is <= the
+ *   without_score of that site and <= the with_score of the residue at comp_pos (the Ascore looks at single moves only).
+ *   PYA_SITE_NONE    the PSM was not scored (status != 0, n_sig <= 0): every field but pos is 0.
+ *   PYA_SITE_OVER    n_sig is above the sig_cap of the call: pos and PYA_SITE_IN_BEST only, the rest 0.
+ *   PYA_SITE_SCORED  otherwise.  n_of_mod == 0: nothing modifies a residue, with_score -1 and with_sig 0. */
+#define PYA_SITE_NONE   0
+#define PYA_SITE_SCORED 1
+#define PYA_SITE_OVER   2
+#define PYA_SITE_IN_BEST       1   /* flags: best_sig modifies this residue                                  */
+#define PYA_SITE_WITH_TIED     2   /* more than one site assignment attains with_score                       */
+#define PYA_SITE_WITHOUT_TIED  4   /* ... without_score                                                      */
+#define PYA_SITE_NO_WITHOUT    8   /* n_of_mod == n_sites: nothing leaves it unmodified; without_score -1    */
+typedef struct pya_site {          /* 32 bytes, two 16-byte stores */
+    uint64_t with_sig;             /* a best site assignment that modifies the residue (sig bits)            */
+    uint64_t without_sig;          /* a best one that leaves it unmodified; 0 with PYA_SITE_NO_WITHOUT       */
+    float with_score;              /* its PepScore = max over the assignments that modify the residue        */
+    float without_score;           /* max over those that do not; -1 with PYA_SITE_NO_WITHOUT                */
+    uint16_t pos;                  /* peptide position, numbered as pya_evidence.comp_pos                    */
+    uint8_t kind, flags;           /* PYA_SITE_*                                                             */
+    uint32_t reserved;             /* 0: records compare as 32 raw bytes                                     */
+} pya_site;
 
 typedef struct pya_handle pya_handle;
 typedef struct pya_plan pya_plan;
@@ -369,6 +409,18 @@ int pya_last_batch_evidence(pya_handle *h, pya_evidence *out, uint64_t n_psm, ui
  * PYA_FLAG_EVIDENCE was given. */
 int pya_last_batch_ions(pya_handle *h, int64_t *ion_off, pya_ion *out, uint64_t cap);
 
+/* The site records (pya_site above) of the last pya_score_batch / _shared / _typed / _named call on this handle that was
+ * given PYA_FLAG_SITES, with the size-query convention of pya_last_batch_ions: site_off[n_psm + 1] always (site_off[n_psm]
+ * = the number of records), the records when cap is not 0 -- cap below that number: PYA_ERR_ARG.  PYA_ERR_STATE when the
+ * last batch was scored without the flag.  The records do not depend on the route that scored a PSM, on how the batch was
+ * cut into chunks, or on shared / typed input. */
+int pya_last_batch_sites(pya_handle *h, int64_t *site_off, pya_site *out, uint64_t cap);
+/* The most site assignments of a PSM the site stage of a batch call enumerates (PYA_SITE_OVER above it); 0: no cap.  The
+ * general kernel takes up to PYA_MAX_SIGNATURES per PSM, and the stage scores every one of them a second time.  The default
+ * is PYA_FAST_SIGNATURES. */
+int pya_set_site_sig_cap(pya_handle *h, uint32_t sig_cap);
+uint32_t pya_get_site_sig_cap(const pya_handle *h);
+
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
 /* the same for a batch whose PSMs share spectra (pya_score_batch_shared: batch->peak_off describes n_spectra spectra,
@@ -417,6 +469,18 @@ int pya_plan_ions(pya_plan *plan, const pya_results *d_res, void *hip_stream, co
  * created with PYA_FLAG_NAMED (or PYA_FLAG_EVIDENCE / PYA_FLAG_IONS): the one-launch kernel leaves no retained tables. */
 int pya_plan_named(pya_plan *plan, const pya_results *d_res, void *hip_stream, const int64_t *d_q_off, const uint64_t *d_q_bits,
                    uint64_t n_q, pya_named *d_out, int32_t *d_counts, float *d_scores);
+/* The site records (pya_site above) of the results the last pya_plan_run* of this plan wrote.
+ *   pya_plan_site_offsets  site_off[n_psm + 1] (host memory): where the records of every PSM lie; known from the plan's
+ *                          pre-pass, so it may be called before a run, and no scan runs on the device.
+ *   pya_plan_sites         d_out[site_off[n_psm]] records; d_res as for pya_plan_evidence; sig_cap: PSMs with more site
+ *                          assignments get PYA_SITE_OVER records, 0 = no cap.  Enqueues the kernel (csrc/sites.hip) on
+ *                          hip_stream, stream-ordered, no host synchronisation inside; it waits for that run -- the side
+ *                          stream included -- also when hip_stream is not the run's stream, is valid until the plan is run
+ *                          again, and may be called again.  PYA_ERR_STATE when the plan has not been run, PYA_ERR_LIMIT as
+ *                          for pya_plan_evidence.  A plan of a handful of PSMs must have been created with PYA_FLAG_SITES
+ *                          (or PYA_FLAG_EVIDENCE / _IONS / _NAMED): the one-launch kernel leaves no retained tables. */
+int pya_plan_site_offsets(const pya_plan *plan, int64_t *site_off);
+int pya_plan_sites(pya_plan *plan, const pya_results *d_res, void *hip_stream, uint32_t sig_cap, pya_site *d_out);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

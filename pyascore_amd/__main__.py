@@ -5,7 +5,8 @@ batched call (:func:`pyascore_amd.batch_cli.localize`) and the TSV of docs/sourc
 written.  ``--parameter_file`` takes ``name = value`` lines ('#' starts a comment); options on the
 command line override it.  ``--device`` (HIP ordinal), ``--evidence`` (three more columns: what stands behind every
 Ascore), ``--ions FILE`` (a second table: which ions, one line each) and ``--reported`` (three more columns: the search
-engine's own site assignment, scored against the winner) are the additions."""
+engine's own site assignment, scored against the winner) and ``--sites FILE`` (a table with a line per candidate residue, and
+the runner-up localisation in the main one) are the additions."""
 import argparse
 import re
 import sys
@@ -55,6 +56,10 @@ def build_parser():
     p.add_argument("--reported", action="store_true",
                    help="append ReportedSequence, ReportedPepScore and ReportedAscore: the site assignment the identification "
                         "file reports, its PepScore, and the ambiguity of the winner against it (0: Ascore kept the site)")
+    p.add_argument("--sites", type=str, default="", metavar="FILE",
+                   help="write the site table to FILE: one line per candidate residue of every scored PSM (Scan, Peptide, Position, "
+                        "Residue, InBest, WithScore, WithoutScore, Delta, BestWith, BestWithout), and append RunnerUpSequence and "
+                        "DeltaPepScore to the main table: the best localisation that differs from the reported one, and its distance")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -114,11 +119,14 @@ def run(args, log=print):
         for group, mass in zip(args.neutral_loss_groups.split(","), args.neutral_loss_masses.split(",")):
             ascore.add_neutral_loss(group, float(mass))
     ion_rows = [] if args.ions else None
+    site_rows = [] if args.sites else None
     rows = batch_cli.localize(ascore, psms, spectra, args.residues, args.mod_mass, args.hit_depth,
                               args.max_fragment_charge, args.mod_correction_tol, args.zero_based,
                               match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
-                              evidence=args.evidence, ions=ion_rows, reported=args.reported)
-    batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported)
+                              evidence=args.evidence, ions=ion_rows, reported=args.reported, sites=site_rows)
+    batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None)
+    if site_rows is not None:
+        batch_cli.write_sites_tsv(site_rows, args.sites)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

@@ -13,6 +13,10 @@ LIB_PATH = os.environ.get("PYA_LIB") or os.path.join(_HERE, "libpyascore_hip.so"
 PYA_OK, PYA_ERR_ARG, PYA_ERR_HIP, PYA_ERR_PSM, PYA_ERR_LIMIT, PYA_ERR_STATE = 0, -1, -2, -3, -4, -5
 PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID, PYA_FLAG_EVIDENCE, PYA_FLAG_IONS = 1, 2, 4, 8, 16
 PYA_FLAG_NAMED = 32
+PYA_FLAG_SITES = 64
+PYA_SITE_NONE, PYA_SITE_SCORED, PYA_SITE_OVER = 0, 1, 2
+PYA_SITE_IN_BEST, PYA_SITE_WITH_TIED, PYA_SITE_WITHOUT_TIED, PYA_SITE_NO_WITHOUT = 1, 2, 4, 8
+PYA_FAST_SIGNATURES = 15000
 PYA_NAMED_NONE, PYA_NAMED_INVALID, PYA_NAMED_WINNER, PYA_NAMED_TIED, PYA_NAMED_COUNTED = 0, 1, 2, 3, 4
 PYA_EV_NONE, PYA_EV_COUNTED, PYA_EV_TIED = 0, 1, 2
 PYA_ION_WINNER, PYA_ION_LOSS, PYA_ION_COMP, PYA_ION_COUNTED = 255, 1, 2, 4
@@ -81,6 +85,18 @@ NAMED_DTYPE = [("sig_bits", "<u8"), ("pep_score", "<f4"), ("ambiguity", "<f4"), 
                ("kind", "u1"), ("depth", "u1"), ("n_moved", "u1"), ("reserved", "u1"),
                ("ref_matched", "<u2"), ("ref_possible", "<u2"), ("comp_matched", "<u2"), ("comp_possible", "<u2")]
 
+
+
+class Site(C.Structure):
+    """pya_site: the best PepScore with and without one modifiable residue, and the site assignments that attain them"""
+    _fields_ = [("with_sig", C.c_uint64), ("without_sig", C.c_uint64), ("with_score", C.c_float), ("without_score", C.c_float),
+                ("pos", C.c_uint16), ("kind", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Site) == 32, "pya_site is a 32-byte record"
+SITE_DTYPE = [("with_sig", "<u8"), ("without_sig", "<u8"), ("with_score", "<f4"), ("without_score", "<f4"),
+              ("pos", "<u2"), ("kind", "u1"), ("flags", "u1"), ("reserved", "<u4")]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -124,6 +140,11 @@ SYMBOLS = {
     "pya_last_batch_ions": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
     "pya_plan_ions_count": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp]),
     "pya_plan_ions": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, C.c_uint64]),
+    "pya_last_batch_sites": (C.c_int, [_vp, _vp, _vp, C.c_uint64]),
+    "pya_set_site_sig_cap": (C.c_int, [_vp, C.c_uint32]),
+    "pya_get_site_sig_cap": (C.c_uint32, [_vp]),
+    "pya_plan_site_offsets": (C.c_int, [_vp, _vp]),
+    "pya_plan_sites": (C.c_int, [_vp, C.POINTER(Results), _vp, C.c_uint32, _vp]),
     "pya_plan_create": (C.c_int, [_vp, C.POINTER(Batch), C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_create_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_run": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Results)]),

@@ -70,6 +70,7 @@ except ImportError:                   # not built for this interpreter
     _fast = None
 
 EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)      # pya_evidence, 16 bytes
+SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)              # pya_site, 32 bytes
 assert EVIDENCE_DTYPE.itemsize == 16
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
 assert ION_DTYPE.itemsize == 16
@@ -308,7 +309,8 @@ class PyAscore:
             last["lazy"] = False
             self._batch_n = 1
 
-    def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None):
+    def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
+                    site_sig_cap=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -340,6 +342,13 @@ class PyAscore:
         against the winner -- ``calculate_ambiguity(pep_scores[0], rec)`` -- with depth and site-determining ion counts, and
         ``kind``: 0 PSM not scored, 1 not a site assignment of the PSM, 2 it is the winner, 3 it ties the winner, 4 counted)
         and ``named_counts`` / ``named_scores`` (``[n_q, n_top]``, the cumulative counts and depth scores of ``pep_scores``).
+        ``sites=True`` adds ``site_off`` (int64 ``[n + 1]``) and ``sites`` (``SITE_DTYPE``, the 32-byte ``pya_site``): one
+        record per modifiable residue of PSM i in ``sites[site_off[i]:site_off[i + 1]]``, N- to C-terminus -- the best
+        PepScore among the site assignments that modify the residue and among those that do not, and a site assignment
+        that attains each (``pyascore_amd.sites`` has ``deltas``, ``runner_up`` and ``table``).  A PSM with more than
+        ``site_sig_cap`` site assignments (default: the library's, ``PYA_FAST_SIGNATURES``; 0: no cap) gets
+        ``PYA_SITE_OVER`` records; a PSM that was set aside has none.
+
         Every other result is what it is without the option.
 
         Shared spectra: a batch dict with ``spec_of`` (and ``n_spectra``; ``synth.pack_shared_batch``) holds every
@@ -360,7 +369,7 @@ class PyAscore:
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
-                                        named=named)
+                                        named=named, sites=sites, site_sig_cap=site_sig_cap)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -368,10 +377,12 @@ class PyAscore:
                     moved = take_queries(q_off, q_bits, perm)
                 try:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
-                                           named=None if moved is None else (moved[0], moved[1]))
+                                           named=None if moved is None else (moved[0], moved[1]), sites=sites,
+                                           site_sig_cap=site_sig_cap)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
+                site_csr = (res.pop("site_off"), res.pop("sites")) if sites else None
                 per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
                 if moved is not None:
@@ -384,6 +395,11 @@ class PyAscore:
                     res["ion_off"] = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
                     take = np.repeat(csr[0][:-1][inv] - res["ion_off"][:-1], n_rec) + np.arange(int(n_rec.sum()))
                     res["ions"] = csr[1][take]
+                if sites:
+                    n_rec = np.diff(site_csr[0])[inv]
+                    res["site_off"] = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
+                    take = np.repeat(site_csr[0][:-1][inv] - res["site_off"][:-1], n_rec) + np.arange(int(n_rec.sum()))
+                    res["sites"] = site_csr[1][take]
                 if res.get("status_message"):
                     res["status_message"] = _renumber_psm(res["status_message"], perm)
                 return res
@@ -430,6 +446,8 @@ class PyAscore:
                 out["evidence"] = np.zeros((0, max_k), EVIDENCE_DTYPE)
             if ions:
                 out["ion_off"], out["ions"] = np.zeros(1, np.int64), np.zeros(0, ION_DTYPE)
+            if sites:
+                out["site_off"], out["sites"] = np.zeros(1, np.int64), np.zeros(0, SITE_DTYPE)
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -452,8 +470,16 @@ class PyAscore:
             except (IndexError, ValueError):
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
-            (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0)
-        rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
+            (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0)
+        if sites and site_sig_cap is not None:          # for this call; the handle's own setting comes back
+            cap_before = int(self._lib.pya_get_site_sig_cap(self._h))
+            self._lib.pya_set_site_sig_cap(self._h, int(site_sig_cap))
+            try:
+                rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
+            finally:
+                self._lib.pya_set_site_sig_cap(self._h, cap_before)
+        else:
+            rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         if rc:
             self._raise(rc)
         self._batch_n = n if keep else None
@@ -480,7 +506,22 @@ class PyAscore:
                 self._raise(rc)
         if ions:
             out["ion_off"], out["ions"] = self._last_batch_ions(n)
+        if sites:
+            out["site_off"], out["sites"] = self._last_batch_sites(n)
         return out
+
+    def _last_batch_sites(self, n):
+        """pya_last_batch_sites: the size query, then the records"""
+        off = np.zeros(n + 1, np.int64)
+        rc = self._lib.pya_last_batch_sites(self._h, _as_ptr(off), None, 0)
+        if rc:
+            self._raise(rc)
+        rec = np.zeros(int(off[-1]), SITE_DTYPE)
+        if rec.size:
+            rc = self._lib.pya_last_batch_sites(self._h, _as_ptr(off), _as_ptr(rec), rec.size)
+            if rc:
+                self._raise(rc)
+        return off, rec
 
     def _last_batch_ions(self, n):
         """pya_last_batch_ions: the size query, then the records"""
@@ -697,6 +738,29 @@ class PyAscore:
             return np.zeros(0, ION_DTYPE)
         self._batch_of_one_records()
         return last["ions"].copy()
+
+    @property
+    def sites(self):
+        """The site table of the last ``score()`` PSM: one ``SITE_DTYPE`` record per modifiable residue (see
+        ``score_batch(sites=True)``; no cap on the site assignments).  Produced the first time it is read, by sending that
+        PSM through the batch path as a batch of one, like ``evidence``."""
+        last = self._last
+        if last is None:
+            return np.zeros(0, SITE_DTYPE)
+        if "sites" not in last:
+            mz, it = _check_f64("mz_arr", last["mz"]), _check_f64("int_arr", last["it"])
+            psm = dict(n_psm=1, mz=mz, intensity=it, peak_off=np.array([0, mz.size], np.int64), pep=last["pep"],
+                       pep_off=np.array([0, last["pep"].size], np.int64), n_of_mod=np.array([int(last["k"])], np.int32),
+                       max_charge=np.array([int(last["z"])], np.int32), aux_pos=last["aux_pos"], aux_mass=last["aux_mass"],
+                       aux_off=np.array([0, np.size(last["aux_pos"])], np.int64))
+            self._ensure_kept()          # (score_batch does: before the state it leaves is put back)
+            state = (self._last, self._batch_n, self._lazy_batch)
+            res = self.score_batch(psm, sites=True, site_sig_cap=0)
+            self._last, self._batch_n, self._lazy_batch = state
+            if int(res["best_sig"][0]) != int(last["best_sig"]):
+                raise RuntimeError("the arrays passed to score() changed before sites was read")
+            last["sites"] = res["sites"]
+        return last["sites"].copy()
 
     def named(self, signatures):
         """The named-localisation records (``NAMED_DTYPE``, see ``score_batch(named=...)``) of the last ``score()`` PSM for

@@ -18,6 +18,7 @@ import numpy as np
 
 from .ascore import PyAscore
 from .named import sig_bits_of
+from . import sites as site_tables
 from .synth import pack_batch, pack_shared_batch
 
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
@@ -26,6 +27,9 @@ EVIDENCE_COLUMNS = ("Depth", "SiteIons", "CompScore")
 # ``--reported``: the search engine's own site assignment, scored (pya_named)
 REPORTED_COLUMNS = ("ReportedSequence", "ReportedPepScore", "ReportedAscore")
 # ``--ions FILE``: one line per ion record (pya_ion), long format
+# ``--sites FILE``: one line per (scan, candidate residue) (pya_site), and two more columns of the main table
+SITE_COLUMNS = ("Scan", "Peptide", "Position", "Residue", "InBest", "WithScore", "WithoutScore", "Delta", "BestWith", "BestWithout")
+RUNNER_UP_COLUMNS = ("RunnerUpSequence", "DeltaPepScore")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -136,7 +140,8 @@ def pack_hits(picked, scans):
 
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
-             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False):
+             mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
+             sites=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -145,7 +150,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``ions``: a list that receives the ion table of the scored PSMs, one ``ion_fields`` row per record behind the PSM's
     scan and its hit number inside the scan (``write_ions_tsv``).
     ``reported=True`` appends three fields per row (``reported_fields``): the search engine's own site assignment as a
-    sequence, its PepScore, and the ambiguity of the winner against it -- did Ascore move the site, and by how much."""
+    sequence, its PepScore, and the ambiguity of the winner against it -- did Ascore move the site, and by how much.
+    ``sites``: a list that receives the site table of the scored PSMs, one ``site_fields`` row per candidate residue
+    (``write_sites_tsv``); every row of the main table then ends with two more fields (``RUNNER_UP_COLUMNS``): the best
+    localisation that differs from the winner, and how far its PepScore lies behind."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -158,7 +166,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     # One PSM the kernels cannot take (longer than 64 residues, more than 15 000 site assignments,
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.
-    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None, named=named)
+    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None, named=named,
+                             sites=sites is not None)
     bad = np.flatnonzero(res["status"])
     if bad.size:
         import warnings
@@ -173,14 +182,27 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     seqs = ascore.format_batch(batch, res["best_sig"], valid=ok.astype(np.int32))   # every string in one call
     if reported:                                 # (one query per PSM: record i belongs to PSM i)
         rep_seqs = ascore.format_batch(batch, res["named"]["sig_bits"], valid=(res["named"]["kind"] >= 2).astype(np.int32))
+    if sites is not None:                        # every sequence of the site table and the runner-up column in one call each
+        rec, off = res["sites"], res["site_off"]
+        rec_psm = np.repeat(np.arange(len(picked), dtype=np.int64), np.diff(off))
+        scored = rec["kind"] == site_tables.SCORED
+        with_seqs = ascore.format_batch(batch, rec["with_sig"], valid=(scored & (rec["with_score"] >= 0)).astype(np.int32), rec_psm=rec_psm)
+        without_seqs = ascore.format_batch(batch, rec["without_sig"], valid=(scored & (rec["without_score"] >= 0)).astype(np.int32),
+                                           rec_psm=rec_psm)
+        runner = site_tables.runner_up(rec, off, res["best_sig"])
+        runner_seqs = ascore.format_batch(batch, runner["sig"], valid=runner["found"].astype(np.int32))
     rows = []
     hit = 0
     for i, psm in enumerate(picked):
         hit = hit + 1 if i and scans[i] == scans[i - 1] else 1
+        if sites is not None:
+            sites.extend([scans[i]] + site_fields(rec[r], psm["peptide"], with_seqs[r], without_seqs[r])
+                         for r in range(int(off[i]), int(off[i + 1])))
         if ions is not None:
             ions.extend([scans[i], hit] + ion_fields(rec) for rec in res["ions"][res["ion_off"][i]:res["ion_off"][i + 1]])
         if res["status"][i]:
-            rows.append([scans[i], "", float("nan"), "", ""] + (["", "", ""] if evidence else []) + (["", "", ""] if reported else []))
+            rows.append([scans[i], "", float("nan"), "", ""] + (["", "", ""] if evidence else []) + (["", "", ""] if reported else []) +
+                        (["", ""] if sites is not None else []))
             continue
         k = psm["n_of_mod"]
         ascores = ";".join(str(s) for s in res["ascores"][i, :k])
@@ -188,8 +210,33 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
                         for m in res["alt_mask"][i, :k])
         rows.append([scans[i], seqs[i], float(res["best_score"][i]), ascores, alts] +
                     (evidence_fields(res["evidence"][i, :k]) if evidence else []) +
-                    (reported_fields(res["named"][i], rep_seqs[i]) if reported else []))
+                    (reported_fields(res["named"][i], rep_seqs[i]) if reported else []) +
+                    ([runner_seqs[i], str(runner["delta"][i])] if sites is not None and runner["found"][i] else
+                     (["", ""] if sites is not None else [])))
     return rows
+
+
+def site_fields(rec, peptide, with_sequence, without_sequence):
+    """One site record as the fields behind Scan of the ``--sites`` table: Peptide, Position (1-based), Residue, InBest (1:
+    the reported localisation modifies the residue), WithScore / WithoutScore -- the best PepScore among the site
+    assignments that modify the residue / leave it unmodified, Delta = WithScore - WithoutScore, BestWith / BestWithout --
+    site assignments that attain the two scores, in the notation of LocalizedSequence.  A PSM that was not scored, or has
+    more site assignments than the stage enumerates, has the first four fields only; a side without any assignment is empty."""
+    pos = int(rec["pos"])
+    scored = int(rec["kind"]) == site_tables.SCORED
+    has_with, has_without = scored and rec["with_score"] >= 0, scored and rec["without_score"] >= 0
+    return [peptide, str(pos), peptide[pos - 1] if 1 <= pos <= len(peptide) else "", "1" if int(rec["flags"]) & site_tables.IN_BEST else "0",
+            str(rec["with_score"]) if has_with else "", str(rec["without_score"]) if has_without else "",
+            str(np.float32(rec["with_score"]) - np.float32(rec["without_score"])) if has_with and has_without else "",
+            with_sequence if has_with else "", without_sequence if has_without else ""]
+
+
+def write_sites_tsv(site_rows, path):
+    """The ``--sites`` table: the rows ``localize(..., sites=[])`` collected, under ``SITE_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(SITE_COLUMNS) + "\n")
+        for row in site_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
 
 
 def reported_fields(rec, sequence):
@@ -239,11 +286,13 @@ def write_ions_tsv(ion_rows, path):
             out.write("\t".join("%s" % f for f in row) + "\n")
 
 
-def write_tsv(rows, path, evidence=False, reported=False):
+def write_tsv(rows, path, evidence=False, reported=False, sites=False):
     """Same file pandas' ``DataFrame(rows, columns=COLUMNS).to_csv(path, sep="\\t", index=False)``
     writes in the reference (`__main__.py:166-172`); ``evidence=True``: the rows of ``localize(..., evidence=True)``,
-    with their three columns behind the reference's; ``reported=True``: those of ``localize(..., reported=True)`` behind them."""
+    with their three columns behind the reference's; ``reported=True``: those of ``localize(..., reported=True)`` behind them;
+    ``sites=True``: the two of ``localize(..., sites=[])`` last."""
     with open(path, "w") as out:
-        out.write("\t".join(COLUMNS + (EVIDENCE_COLUMNS if evidence else ()) + (REPORTED_COLUMNS if reported else ())) + "\n")
+        out.write("\t".join(COLUMNS + (EVIDENCE_COLUMNS if evidence else ()) + (REPORTED_COLUMNS if reported else ()) +
+                            (RUNNER_UP_COLUMNS if sites else ())) + "\n")
         for scan, seq, pep_score, ascores, alts, *more in rows:
             out.write("\t".join(["%s" % scan, "%s" % seq, repr(float(pep_score)), ascores, alts] + list(more)) + "\n")

@@ -63,6 +63,7 @@ void pya_destroy(pya_handle *h) {
     if (h->evid_host) (void)hipHostFree(h->evid_host);
     if (h->ions_host) (void)hipHostFree(h->ions_host);
     if (h->named_host) (void)hipHostFree(h->named_host);
+    if (h->sites_host) (void)hipHostFree(h->sites_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->run_stream) (void)hipStreamDestroy(h->run_stream);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
@@ -253,6 +254,27 @@ int pya_last_batch_ions(pya_handle *h, int64_t *ion_off, pya_ion *out, uint64_t 
     std::memcpy(out, h->ions_host, (size_t)total * sizeof(pya_ion));
     return PYA_OK;
 }
+
+int pya_last_batch_sites(pya_handle *h, int64_t *site_off, pya_site *out, uint64_t cap) {
+    if (!h || !site_off) return PYA_ERR_ARG;
+    if (!h->sites_valid) return h->fail(PYA_ERR_STATE, -1, "the last batch was scored without PYA_FLAG_SITES");
+    std::memcpy(site_off, h->sites_off.data(), h->sites_off.size() * sizeof(int64_t));
+    const uint64_t total = (uint64_t)h->sites_off.back();
+    if (total == 0 || cap == 0) return PYA_OK;
+    if (cap < total)
+        return h->fail(PYA_ERR_ARG, -1, "capacity %llu < %llu records", (unsigned long long)cap, (unsigned long long)total);
+    if (!out) return h->fail(PYA_ERR_ARG, -1, "NULL site array");
+    std::memcpy(out, h->sites_host, (size_t)total * sizeof(pya_site));
+    return PYA_OK;
+}
+
+int pya_set_site_sig_cap(pya_handle *h, uint32_t sig_cap) {
+    if (!h) return PYA_ERR_ARG;
+    h->site_sig_cap = sig_cap;
+    return PYA_OK;
+}
+
+uint32_t pya_get_site_sig_cap(const pya_handle *h) { return h ? h->site_sig_cap : 0u; }
 
 int pya_get_pep_scores_range(pya_handle *h, uint64_t psm_begin, uint64_t psm_end, uint64_t cap, int64_t *rec_off,
                              uint64_t *sig_bits, int32_t *counts, float *scores, float *ws_out,

@@ -146,6 +146,45 @@ static int ions_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out,
     return PYA_OK;
 }
 
+/* PYA_FLAG_SITES: the handle's pinned block for the site records of a batch.  A PSM has at most as many records as its
+ * peptide has modifiable letters (none when it is set aside), and the chunks come in PSM order, so a block of that many
+ * never has to grow -- or move -- while a chunk's copy is on its way into it. */
+static int sites_host_block(pya_handle *h, const pya_batch *b) {
+    size_t bound = 0;
+    for (uint64_t i = 0; i < b->n_psm; i++) {
+        uint32_t ns = 0;
+        if (psm_letters_ok(h, b->pep + b->pep_off[i], b->pep_off[i + 1] - b->pep_off[i], &ns) && ns <= PYA_MAX_SITES) bound += ns;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->sites_cap < bound) {
+        if (h->sites_host) (void)hipHostFree(h->sites_host);
+        h->sites_host = nullptr;
+        h->sites_cap = 0;
+        HIPCHK(h, hipHostMalloc((void **)&h->sites_host, (bound + bound / 4) * sizeof(pya_site), hipHostMallocDefault));
+        h->sites_cap = bound + bound / 4;
+    }
+    h->sites_off.assign(b->n_psm + 1, 0);                     /* (a PSM no plan reaches has no records) */
+    return PYA_OK;
+}
+
+/* ... the site launch of a plan behind its kernels on `st`, and its records on their way into the block behind those of the
+ * PSMs before `lo` (asynchronous: whoever waits for the chunk's results waits for them too) */
+static int sites_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0) return PYA_OK;
+    std::vector<int64_t> off(n + 1);
+    int rc = pya_plan_site_offsets(p, off.data());
+    if (rc) return rc;
+    const int64_t base = h->sites_off[lo], total = off[n];
+    for (uint64_t i = 0; i < n; i++) h->sites_off[lo + 1 + i] = base + off[i + 1];
+    if (total == 0) return PYA_OK;
+    if ((size_t)(base + total) > h->sites_cap) return h->fail(PYA_ERR_STATE, -1, "site records beyond the block sized for them");
+    HIPCHK(h, p->d_sites.alloc((size_t)total));
+    if ((rc = pya_plan_sites(p, d_out, st, h->site_sig_cap, p->d_sites.p))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->sites_host + base, p->d_sites.p, (size_t)total * sizeof(pya_site), hipMemcpyDeviceToHost, st));
+    return PYA_OK;
+}
+
 /* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
  * counts, [n_q * n_top] scores -- zeroed */
 static int named_host_block(pya_handle *h, uint64_t n_q) {
@@ -336,6 +375,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_EVIDENCE) && (rc = evidence_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_IONS) && (rc = ions_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if (nq && (rc = named_behind_run(h, p, &d_out, nq, lo, n_q, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_SITES) && (rc = sites_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -379,6 +419,8 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
     }
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
     h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
+    /* (chunks behind the last PSM with records: their offsets stay at the total) */
+    h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
     return finish(PYA_OK);
 }
 
@@ -391,12 +433,15 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->last_chunks = 1;
     h->evid_valid = false;
     h->ions_valid = false;
+    h->sites_valid = false;
     if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
+    if (flags & PYA_FLAG_SITES) h->sites_off.assign(b->n_psm + 1, 0);
     if (b->n_psm == 0) {
         h->evid_n = 0;
         h->evid_k = out->max_k;
         h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
         h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
+        h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
         return PYA_OK;
     }
     uint32_t types = 0;
@@ -430,8 +475,13 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_ev = evidence_host_block(h, b->n_psm, out->max_k);
         if (rc_ev) return rc_ev;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE or PYA_FLAG_IONS takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    if (flags & PYA_FLAG_SITES) {
+        if (b->pep_off[b->n_psm] < b->pep_off[0]) return h->fail(PYA_ERR_ARG, -1, "pep_off is not monotone");
+        const int rc_st = sites_host_block(h, b);
+        if (rc_st) return rc_st;
+    }
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS or _SITES takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -564,6 +614,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         HIPCHK(h, hipStreamSynchronize(nullptr));
         named_deliver(h, nq, 0, n, n_q);
     }
+    if (flags & PYA_FLAG_SITES) {
+        if ((rc = sites_behind_run(h, p, &d_out, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        h->sites_valid = true;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -584,6 +639,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->last_status.clear();
     h->evid_valid = false;
     h->ions_valid = false;
+    h->sites_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);

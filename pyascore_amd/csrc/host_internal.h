@@ -128,6 +128,9 @@ size_t pya_named_lds_bytes(uint32_t l_cap, uint32_t list_cap);
 int pya_launch_named(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_q_off, const uint64_t *d_q_bits,
                      uint64_t n_q, void *d_out, int32_t *d_counts, float *d_scores, uint32_t *d_over, uint32_t l_cap,
                      uint32_t list_cap, hipStream_t stream);
+size_t pya_sites_lds_bytes(uint32_t l_cap, uint32_t list_cap);
+int pya_launch_sites(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_site_off, uint64_t n_out,
+                     uint32_t sig_cap, void *d_out, uint32_t l_cap, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -334,6 +337,14 @@ struct pya_handle {
      * behind its results: [n_q] pya_named, then [n_q * n_top] counts and [n_q * n_top] scores where asked for */
     unsigned char *named_host = nullptr;
     size_t named_cap = 0;                     /* bytes of the block */
+    /* PYA_FLAG_SITES: the site records of the last pya_score_batch in PSM order (pinned, sized before the first chunk from
+     * the peptides' letters: a chunk's records come back asynchronously behind its results) and the offsets of every PSM
+     * into them (pya_last_batch_sites copies them out); the cap on site assignments per PSM the stage is launched with */
+    pya_site *sites_host = nullptr;
+    size_t sites_cap = 0;                     /* records the block has room for */
+    std::vector<int64_t> sites_off;           /* [n_psm + 1] of the batch they belong to */
+    bool sites_valid = false;                 /* the last batch was scored with the flag */
+    uint32_t site_sig_cap = PYA_FAST_SIGNATURES;
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -664,6 +675,14 @@ struct pya_plan {
     DevBuf<int64_t> d_named_q_off;
     DevBuf<uint64_t> d_named_q_bits;
     DevBuf<unsigned char> d_named;
+    /* pya_plan_sites: the record offsets of the PSMs (the pre-pass's modifiable residues, summed; a PSM set aside has none),
+     * their copy on the device (uploaded by the first call, on its stream), the event a later call on another stream waits
+     * for; the records of a pya_score_batch plan */
+    std::vector<int64_t> site_off;
+    DevBuf<int64_t> d_site_off;
+    hipEvent_t ev_sites = nullptr;
+    bool site_off_sent = false;
+    DevBuf<pya_site> d_sites;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -676,6 +695,7 @@ struct pya_plan {
         if (ev_evid) (void)hipEventDestroy(ev_evid);
         if (ev_ions) (void)hipEventDestroy(ev_ions);
         if (ev_named) (void)hipEventDestroy(ev_named);
+        if (ev_sites) (void)hipEventDestroy(ev_sites);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
@@ -793,6 +813,10 @@ static_assert(sizeof(pya_named) == 32 && offsetof(pya_named, pep_score) == 8 && 
                   offsetof(pya_named, ref_possible) == 26 && offsetof(pya_named, comp_matched) == 28 &&
                   offsetof(pya_named, comp_possible) == 30,
               "pya_named is two 16-byte stores of named.hip");
+static_assert(sizeof(pya_site) == 32 && offsetof(pya_site, without_sig) == 8 && offsetof(pya_site, with_score) == 16 &&
+                  offsetof(pya_site, without_score) == 20 && offsetof(pya_site, pos) == 24 && offsetof(pya_site, kind) == 26 &&
+                  offsetof(pya_site, flags) == 27 && offsetof(pya_site, reserved) == 28,
+              "pya_site is two 16-byte stores of sites.hip");
 /* pya_score_batch_named's queries and outputs (host arrays of the caller), nullptr for the other batch entry points */
 struct NamedReq {
     const int64_t *q_off;

@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_SITES)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -558,6 +558,60 @@ int pya_plan_named(pya_plan *p, const pya_results *r, void *hip_stream, const in
     if (e) return h->hip_fail((hipError_t)e, "named launch");
     HIPCHK(h, hipEventRecord(p->ev_named, st));
     p->named_asked = true;
+    return PYA_OK;
+}
+
+/* The site stage (csrc/sites.hip).  The offsets are the pre-pass's: a PSM has as many records as modifiable residues, a PSM
+ * that was set aside none. */
+static void site_offsets(pya_plan *p) {
+    if (p->site_off.size() == p->n_psm + 1) return;
+    p->site_off.assign(p->n_psm + 1, 0);
+    for (uint64_t i = 0; i < p->n_psm; i++) p->site_off[i + 1] = p->site_off[i] + (int64_t)p->n_sites[i];
+}
+
+int pya_plan_site_offsets(const pya_plan *plan, int64_t *site_off) {
+    if (!plan || !site_off) return PYA_ERR_ARG;
+    pya_plan *p = const_cast<pya_plan *>(plan);              /* (the offsets are made once and kept) */
+    site_offsets(p);
+    std::memcpy(site_off, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t));
+    return PYA_OK;
+}
+
+/* ... the same two launches behind the same wait as the evidence stage.  It reads best_sig and n_sig of the caller's results
+ * structure and nothing else of it. */
+int pya_plan_sites(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t sig_cap, pya_site *d_out) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_sites: the plan has not been run");
+    site_offsets(p);
+    const uint64_t n_out = (uint64_t)p->site_off[p->n_psm];
+    if (n_out == 0) return PYA_OK;
+    if (!d_out || !r->best_score || !r->best_sig || !r->n_sig) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_sites");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->ev_sites) HIPCHK(h, hipEventCreateWithFlags(&p->ev_sites, hipEventDisableTiming));
+    const int rc = stage_behind_run(p, st, "pya_plan_sites", "site", pya_sites_lds_bytes);
+    if (rc) return rc;
+    if (!p->site_off_sent) {
+        /* (from the plan's own vector, which outlives the copy; a later call on another stream waits for it below) */
+        HIPCHK(h, p->d_site_off.alloc(p->n_psm + 1));
+        HIPCHK(h, hipMemcpyAsync(p->d_site_off.p, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        p->site_off_sent = true;
+    } else {
+        HIPCHK(h, hipStreamWaitEvent(st, p->ev_sites, 0));
+    }
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.best_score = r->best_score;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    int e = pya_launch_sites(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, p->d_site_off.p, n_out, sig_cap, d_out,
+                             p->evid_l_cap, st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_sites(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), p->d_site_off.p, n_out, sig_cap, d_out, p->gen_l_cap, st);
+    if (e) return h->hip_fail((hipError_t)e, "site launch");
+    HIPCHK(h, hipEventRecord(p->ev_sites, st));
     return PYA_OK;
 }
 

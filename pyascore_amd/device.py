@@ -24,9 +24,10 @@ class DevicePlan:
     tells the plan at creation that they will be asked for (a plan of a handful of PSMs then takes the per-stage
     launches instead of the one-launch kernel).  ``ions()`` / ``ions=True``: the same for the ion records
     (``pya_plan_ions_count``, ``pya_plan_ions``).  ``named()`` / ``named=True``: the same for the records of localisations
-    the caller names (``pya_plan_named``)."""
+    the caller names (``pya_plan_named``).  ``sites()`` / ``sites=True``: the same for the site tables
+    (``pya_plan_site_offsets``, ``pya_plan_sites``)."""
 
-    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False):
+    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -55,7 +56,7 @@ class DevicePlan:
                        _as_ptr(m["aux_mass"]), _as_ptr(m["aux_off"]))
         self._plan = C.c_void_p()
         flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
-            (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0)
+            (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -182,6 +183,35 @@ class DevicePlan:
             self.scorer._raise(rc)
         return (out, d_counts, d_scores) if counts or scores else out
 
+    def site_offsets(self):
+        """``site_off`` (int64 numpy ``[n_psm + 1]``): where the site records of every PSM lie.  Known from the plan's host
+        pre-pass, so it needs no run and nothing on the device."""
+        off = np.zeros(self.n_psm + 1, np.int64)
+        rc = self._lib.pya_plan_site_offsets(self._plan, _as_ptr(off))
+        if rc:
+            self.scorer._raise(rc)
+        return off
+
+    def sites(self, sig_cap=0, out=None):
+        """The site table of the last ``run()``: ``(site_off, records)``, the host offsets of ``site_offsets()`` and a
+        ``torch.uint8`` device tensor ``[site_off[-1], 32]`` (one ``pya_site`` per modifiable residue; ``site_records``
+        turns a host copy into the structured array).  One launch family of the library behind the run on torch's current
+        stream; nothing waits on the host.  ``sig_cap``: PSMs with more site assignments get ``PYA_SITE_OVER`` records
+        (0: no cap).  Valid for the results of the last run; may be called again."""
+        torch = self._torch
+        off = self.site_offsets()
+        shape = (int(off[-1]), 32)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous uint8 device tensor of shape %r" % (shape,))
+        rc = self._lib.pya_plan_sites(self._plan, C.byref(self._res), stream, int(sig_cap), out.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return off, out
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -229,6 +259,7 @@ class DevicePlan:
 EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)
 NAMED_DTYPE = np.dtype(_lib.NAMED_DTYPE)
+SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)
 
 
 def evidence_rows(raw):
@@ -260,6 +291,15 @@ def ion_records(raw):
     if a.ndim != 2 or a.shape[1] != ION_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (total, %d)" % ION_DTYPE.itemsize)
     return a.view(ION_DTYPE).reshape(a.shape[0])
+
+
+def site_records(raw):
+    """A host copy of the records of ``DevicePlan.sites()`` (``.cpu().numpy()``, uint8 ``[n, 32]``) as the structured array
+    ``PyAscore.score_batch(..., sites=True)`` returns; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != SITE_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % SITE_DTYPE.itemsize)
+    return a.view(SITE_DTYPE).reshape(a.shape[0])
 
 
 def named_records(raw):
