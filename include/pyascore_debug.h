@@ -20,7 +20,8 @@ extern "C" {
  * switch back to its production default.  pya_reload_env resets all of them.  Unknown names: PYA_ERR_ARG.
  *   flags (any non-NULL value = on): PYA_NO_PLAIN PYA_NO_FUSED PYA_NO_BIG PYA_NO_TINY PYA_NO_PREFIX PYA_NO_CHUNKS
  *     PYA_NO_UPLOAD_THREAD PYA_ONE_PEAK_CLASS PYA_PEAK_CLASSES PYA_ONE_LDS_CLASS PYA_SORT_ROOM PYA_NO_BIG_INLINE
- *     PYA_NO_LOC_HASH PYA_NO_NODES PYA_NO_CNT PYA_HOST_TIMING PYA_STAMPS PYA_SLOW_NULL_STREAM PYA_NO_FORK (r06: the
+ *     PYA_NO_LOC_HASH PYA_NO_NODES PYA_NO_CNT PYA_NO_PROB_CNT (the probability stage scores every PSM with its
+ *     general front end, csrc/probs.hip) PYA_HOST_TIMING PYA_STAMPS PYA_SLOW_NULL_STREAM PYA_NO_FORK (r06: the
  *     fused family behind the scoring kernels on the caller's stream instead of beside them on the plan's side stream)
  *   numbers: PYA_DEBUG (bit set, common.h) PYA_PLAIN_MIN PYA_BIG_MIN_N PYA_TINY_MAX PYA_SORT_ROOM_MAX PYA_SB PYA_GTP
  *     PYA_HASH_PP PYA_NODE_CAP PYA_CHUNK_MB PYA_WORKSPACE_MB
@@ -42,6 +43,18 @@ int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]);
  * plan, not pipelined; 0: no call yet).  The tests read from it that a budget cuts a float32 batch into no more chunks than
  * the same batch widened.  No reference counterpart. */
 uint64_t pya_debug_last_chunks(const pya_handle *h);
+
+/* What the last pya_plan_probs call on a plan of this handle launched (a batch call with PYA_FLAG_PROBS makes one per chunk),
+ * for its two launches -- [0] the PSMs inside the fast kernels' limits, [1] the plan's general list: front_ends = 1 the
+ * count-node tables alone (every scored PSM of the launch went through them), 2 the general front end alone, 3 both carved
+ * (the kernel chooses per PSM), 0 no launch; lds_bytes = the dynamic LDS of the launch.  No reference counterpart. */
+int pya_debug_last_probs_launch(const pya_handle *h, uint32_t front_ends[2], uint64_t lds_bytes[2]);
+
+/* The signature list of PSM `psm` of the handle's retained batch (the last PYA_FLAG_KEEP call): the sig bits of its site
+ * assignments in the order every kernel scores them in and the probability stage sums them in (pya_get_pep_scores* returns
+ * the reference's sorted order instead).  *n = their number; sig_bits may be NULL with cap 0 to ask.  No reference
+ * counterpart. */
+int pya_debug_signature_list(pya_handle *h, uint64_t psm, uint64_t *sig_bits, uint64_t cap, uint64_t *n);
 
 /* The retained-peak table the binning kernels left in a plan's workspace for entry `index`, copied to the host: mz[i], rank[i]
  * = (float m/z, rank in its window) of table entry i, in table order (m/z ascending).  index = the PSM number, or the SPECTRUM

@@ -94,6 +94,9 @@ extern "C" {
 #define PYA_FLAG_SITES 64u  /* pya_score_batch* / pya_score_batch_named: the site table of every PSM as */
                             /* well (pya_last_batch_sites); pya_plan_create*: as PYA_FLAG_EVIDENCE      */
                             /* (pya_plan_site_offsets / pya_plan_sites)                                 */
+#define PYA_FLAG_PROBS 128u /* pya_score_batch* / pya_score_batch_named: the site probabilities of every PSM as */
+                            /* well (pya_last_batch_probs); pya_plan_create*: as PYA_FLAG_EVIDENCE              */
+                            /* (pya_plan_site_offsets / pya_plan_probs)                                         */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -247,6 +250,37 @@ typedef struct pya_site {          /* 32 bytes, two 16-byte stores */
     uint8_t kind, flags;           /* PYA_SITE_*                                                             */
     uint32_t reserved;             /* 0: records compare as 32 raw bytes                                     */
 } pya_site;
+
+/* Site probabilities.  The site table above holds the two MAX-marginals of a PSM's PepScores; these are the two
+ * SUM-marginals: the posterior over the site assignments that their PepScores imply, summed per modifiable residue -- the
+ * localisation probability phosphoproteomics pipelines filter on ("class I site: p >= 0.75") -- and the posterior of the
+ * reported localisation.  It is a PepScore-based posterior, MaxQuant's construction (a PepScore is -10 log10 of a chance
+ * probability, so 10^(s / 10) is read as a likelihood ratio); it is NOT part of the Ascore publication and the reference
+ * has no counterpart.  For a scored PSM with site assignments i = 0 .. n_sig - 1 in the order of its shape's signature
+ * list (the list every route scores from; NOT the order of pya_get_pep_scores*' records, which is the reference's sorted
+ * one), PepScores s_i (float32, bit-equal to the pep_scores records) and s* = best_score:
+ *   w_i = exp2(((double)s_i - (double)s*) * C),  C = 0.33219280948873623 (log2(10) / 10): the likelihood ratio
+ *         10^((s_i - s*) / 10).  The subtraction is exact in double; w of the winner is exactly 1.
+ *   Z = sum w_i;  W_with[r] = sum of w_i over the assignments that modify residue r,  W_without[r] over those that do not.
+ *         Each is a SEQUENTIAL double sum in list order (i ascending): given the w_i a host loop reproduces the sums bit
+ *         for bit, and they do not depend on the route that scored the PSM, on chunk cuts or on batch neighbours.
+ *   pya_site_prob  per modifiable residue, N- to C-terminus, at the offsets of the site table (pya_plan_site_offsets,
+ *         site_off): with_prob = W_with / Z, without_prob = W_without / Z.  Both are kept: 1 - p loses everything near 1.
+ *   pya_psm_prob   per PSM: z = Z (the posterior of the reported localisation is 1 / z), n_summed = n_sig, kind:
+ *         PYA_SITE_NONE    the PSM was not scored (set aside, status != 0, n_sig <= 0): all zeros, residue records 0 / 0;
+ *         PYA_SITE_OVER    n_sig is above the sig_cap of the call: z = 0, n_summed = 0, residue records -1 / -1;
+ *         PYA_SITE_SCORED  otherwise.  n_of_mod == 0: z = 1, every residue 0 / 1.  n_of_mod == n_sites: every residue 1 / 0.
+ * Only exp2 separates the device from a host restatement of this: floats agree to a few ulps, everything else exactly. */
+typedef struct pya_site_prob {     /* 16 bytes, one store */
+    double with_prob;              /* P(the residue is modified | spectrum, n_of_mod)                          */
+    double without_prob;           /* P(it is not)                                                             */
+} pya_site_prob;
+typedef struct pya_psm_prob {      /* 16 bytes, one store */
+    double z;                      /* sum of the likelihood ratios against the winner; 1 / z = its posterior   */
+    uint32_t n_summed;             /* site assignments summed (n_sig)                                          */
+    uint8_t kind;                  /* PYA_SITE_NONE / _SCORED / _OVER                                          */
+    uint8_t pad[3];                /* 0                                                                        */
+} pya_psm_prob;
 
 typedef struct pya_handle pya_handle;
 typedef struct pya_plan pya_plan;
@@ -420,6 +454,14 @@ int pya_last_batch_sites(pya_handle *h, int64_t *site_off, pya_site *out, uint64
  * is PYA_FAST_SIGNATURES. */
 int pya_set_site_sig_cap(pya_handle *h, uint32_t sig_cap);
 uint32_t pya_get_site_sig_cap(const pya_handle *h);
+/* The site probabilities (pya_site_prob / pya_psm_prob above) of the last pya_score_batch / _shared / _typed / _named call on
+ * this handle that was given PYA_FLAG_PROBS, with the size-query convention of pya_last_batch_sites: site_off[n_psm + 1]
+ * always (the offsets of the site table), sites[site_off[n_psm]] and psms[n_psm] when cap is not 0 -- cap below
+ * site_off[n_psm]: PYA_ERR_ARG, as is a NULL array then.  PYA_ERR_STATE when the last batch was scored without the flag.  A
+ * PSM that was set aside has an empty range and a PYA_SITE_NONE record.  The cap on site assignments per PSM is
+ * pya_set_site_sig_cap's.  The records do not depend on the route that scored a PSM, on how the batch was cut into chunks,
+ * or on shared / typed input. */
+int pya_last_batch_probs(pya_handle *h, int64_t *site_off, pya_site_prob *sites, pya_psm_prob *psms, uint64_t cap);
 
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
@@ -481,6 +523,12 @@ int pya_plan_named(pya_plan *plan, const pya_results *d_res, void *hip_stream, c
  *                          (or PYA_FLAG_EVIDENCE / _IONS / _NAMED): the one-launch kernel leaves no retained tables. */
 int pya_plan_site_offsets(const pya_plan *plan, int64_t *site_off);
 int pya_plan_sites(pya_plan *plan, const pya_results *d_res, void *hip_stream, uint32_t sig_cap, pya_site *d_out);
+/* The site probabilities of the results the last pya_plan_run* of this plan wrote: d_sites[site_off[n_psm]] records at the
+ * offsets of pya_plan_site_offsets, d_psms[n_psm] records, device memory.  Everything else as for pya_plan_sites:
+ * stream-ordered (csrc/probs.hip), no host synchronisation inside, waits for the run, valid until the plan is run again, may
+ * be called again; no write lies at or past d_sites + site_off[n_psm].  It reads best_score, best_sig and n_sig of d_res. */
+int pya_plan_probs(pya_plan *plan, const pya_results *d_res, void *hip_stream, uint32_t sig_cap, pya_site_prob *d_sites,
+                   pya_psm_prob *d_psms);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

@@ -6,7 +6,8 @@ written.  ``--parameter_file`` takes ``name = value`` lines ('#' starts a commen
 command line override it.  ``--device`` (HIP ordinal), ``--evidence`` (three more columns: what stands behind every
 Ascore), ``--ions FILE`` (a second table: which ions, one line each) and ``--reported`` (three more columns: the search
 engine's own site assignment, scored against the winner) and ``--sites FILE`` (a table with a line per candidate residue, and
-the runner-up localisation in the main one) are the additions."""
+the runner-up localisation in the main one) and ``--probs`` (two more columns: the localisation probability of every
+candidate residue and the posterior of the reported localisation) are the additions."""
 import argparse
 import re
 import sys
@@ -60,6 +61,10 @@ def build_parser():
                    help="write the site table to FILE: one line per candidate residue of every scored PSM (Scan, Peptide, Position, "
                         "Residue, InBest, WithScore, WithoutScore, Delta, BestWith, BestWithout), and append RunnerUpSequence and "
                         "DeltaPepScore to the main table: the best localisation that differs from the reported one, and its distance")
+    p.add_argument("--probs", action="store_true",
+                   help="append SiteProbs and BestProb: the peptide with the localisation probability of every candidate residue "
+                        "behind it, AS(0.98)PT(0.02)K, and the posterior of the reported localisation -- a PepScore-based "
+                        "posterior (MaxQuant's construction), not part of the Ascore publication")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -123,8 +128,10 @@ def run(args, log=print):
     rows = batch_cli.localize(ascore, psms, spectra, args.residues, args.mod_mass, args.hit_depth,
                               args.max_fragment_charge, args.mod_correction_tol, args.zero_based,
                               match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
-                              evidence=args.evidence, ions=ion_rows, reported=args.reported, sites=site_rows)
-    batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None)
+                              evidence=args.evidence, ions=ion_rows, reported=args.reported, sites=site_rows,
+                              probs=args.probs)
+    batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
+                        probs=args.probs)
     if site_rows is not None:
         batch_cli.write_sites_tsv(site_rows, args.sites)
     if ion_rows is not None:

@@ -14,6 +14,7 @@ PYA_OK, PYA_ERR_ARG, PYA_ERR_HIP, PYA_ERR_PSM, PYA_ERR_LIMIT, PYA_ERR_STATE = 0,
 PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID, PYA_FLAG_EVIDENCE, PYA_FLAG_IONS = 1, 2, 4, 8, 16
 PYA_FLAG_NAMED = 32
 PYA_FLAG_SITES = 64
+PYA_FLAG_PROBS = 128
 PYA_SITE_NONE, PYA_SITE_SCORED, PYA_SITE_OVER = 0, 1, 2
 PYA_SITE_IN_BEST, PYA_SITE_WITH_TIED, PYA_SITE_WITHOUT_TIED, PYA_SITE_NO_WITHOUT = 1, 2, 4, 8
 PYA_FAST_SIGNATURES = 15000
@@ -97,6 +98,21 @@ assert C.sizeof(Site) == 32, "pya_site is a 32-byte record"
 SITE_DTYPE = [("with_sig", "<u8"), ("without_sig", "<u8"), ("with_score", "<f4"), ("without_score", "<f4"),
               ("pos", "<u2"), ("kind", "u1"), ("flags", "u1"), ("reserved", "<u4")]
 
+
+class SiteProb(C.Structure):
+    """pya_site_prob: the posterior probability that one modifiable residue is modified, and that it is not"""
+    _fields_ = [("with_prob", C.c_double), ("without_prob", C.c_double)]
+
+
+class PsmProb(C.Structure):
+    """pya_psm_prob: the sum of the likelihood ratios of a PSM's site assignments against the winner (1 / z: its posterior)"""
+    _fields_ = [("z", C.c_double), ("n_summed", C.c_uint32), ("kind", C.c_uint8), ("pad", C.c_uint8 * 3)]
+
+
+assert C.sizeof(SiteProb) == 16 and C.sizeof(PsmProb) == 16, "pya_site_prob and pya_psm_prob are 16-byte records"
+SITE_PROB_DTYPE = [("with_prob", "<f8"), ("without_prob", "<f8")]
+PSM_PROB_DTYPE = [("z", "<f8"), ("n_summed", "<u4"), ("kind", "u1"), ("pad", "u1", (3,))]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -118,6 +134,8 @@ SYMBOLS = {
     "pya_set_debug": (C.c_int, [_vp, C.c_char_p, C.c_char_p]),          # include/pyascore_debug.h (test-only)
     "pya_debug_wave_ops": (C.c_int, [_vp, _vp, _vp]),         # (test-only)
     "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
+    "pya_debug_last_probs_launch": (C.c_int, [_vp, _vp, _vp]),        # (test-only)
+    "pya_debug_signature_list": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp]),   # (test-only)
     "pya_debug_plan_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
     "pya_debug_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
     "pya_score_one": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_int32, C.c_int32, _vp, _vp, C.c_uint64,
@@ -145,6 +163,8 @@ SYMBOLS = {
     "pya_get_site_sig_cap": (C.c_uint32, [_vp]),
     "pya_plan_site_offsets": (C.c_int, [_vp, _vp]),
     "pya_plan_sites": (C.c_int, [_vp, C.POINTER(Results), _vp, C.c_uint32, _vp]),
+    "pya_last_batch_probs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64]),
+    "pya_plan_probs": (C.c_int, [_vp, C.POINTER(Results), _vp, C.c_uint32, _vp, _vp]),
     "pya_plan_create": (C.c_int, [_vp, C.POINTER(Batch), C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_create_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_run": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Results)]),

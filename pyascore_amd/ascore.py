@@ -71,6 +71,9 @@ except ImportError:                   # not built for this interpreter
 
 EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)      # pya_evidence, 16 bytes
 SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)              # pya_site, 32 bytes
+SITE_PROB_DTYPE = np.dtype(_lib.SITE_PROB_DTYPE)    # pya_site_prob, 16 bytes
+PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)      # pya_psm_prob, 16 bytes
+assert SITE_PROB_DTYPE.itemsize == 16 and PSM_PROB_DTYPE.itemsize == 16
 assert EVIDENCE_DTYPE.itemsize == 16
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
 assert ION_DTYPE.itemsize == 16
@@ -310,7 +313,7 @@ class PyAscore:
             self._batch_n = 1
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
-                    site_sig_cap=None):
+                    site_sig_cap=None, probs=False):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -348,6 +351,12 @@ class PyAscore:
         that attains each (``pyascore_amd.sites`` has ``deltas``, ``runner_up`` and ``table``).  A PSM with more than
         ``site_sig_cap`` site assignments (default: the library's, ``PYA_FAST_SIGNATURES``; 0: no cap) gets
         ``PYA_SITE_OVER`` records; a PSM that was set aside has none.
+        ``probs=True`` adds ``site_off`` (the same offsets), ``site_probs`` (``SITE_PROB_DTYPE``, the 16-byte
+        ``pya_site_prob``: per modifiable residue the posterior probability that it is modified, ``with_prob``, and that it
+        is not, ``without_prob``) and ``psm_probs`` (``PSM_PROB_DTYPE``, ``[n]``: ``z``, the sum of the likelihood ratios
+        10^((PepScore - best) / 10) over the site assignments -- the posterior of the reported localisation is ``1 / z`` --,
+        ``n_summed`` and ``kind`` as for ``sites``).  A PepScore-based posterior (MaxQuant's construction), not part of the
+        Ascore publication; ``pyascore_amd.probs`` has ``best_prob``, ``table`` and ``annotate``.  ``site_sig_cap`` applies.
 
         Every other result is what it is without the option.
 
@@ -369,7 +378,7 @@ class PyAscore:
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
-                                        named=named, sites=sites, site_sig_cap=site_sig_cap)
+                                        named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -378,11 +387,13 @@ class PyAscore:
                 try:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
-                                           site_sig_cap=site_sig_cap)
+                                           site_sig_cap=site_sig_cap, probs=probs)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
-                site_csr = (res.pop("site_off"), res.pop("sites")) if sites else None
+                site_csr = (res["site_off"], res.pop("sites")) if sites else None
+                prob_csr = (res["site_off"], res.pop("site_probs")) if probs else None
+                res.pop("site_off", None)
                 per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
                 if moved is not None:
@@ -400,6 +411,11 @@ class PyAscore:
                     res["site_off"] = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
                     take = np.repeat(site_csr[0][:-1][inv] - res["site_off"][:-1], n_rec) + np.arange(int(n_rec.sum()))
                     res["sites"] = site_csr[1][take]
+                if probs:                    # (psm_probs is per PSM: it came back with the other per-PSM arrays)
+                    n_rec = np.diff(prob_csr[0])[inv]
+                    res["site_off"] = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
+                    take = np.repeat(prob_csr[0][:-1][inv] - res["site_off"][:-1], n_rec) + np.arange(int(n_rec.sum()))
+                    res["site_probs"] = prob_csr[1][take]
                 if res.get("status_message"):
                     res["status_message"] = _renumber_psm(res["status_message"], perm)
                 return res
@@ -448,6 +464,8 @@ class PyAscore:
                 out["ion_off"], out["ions"] = np.zeros(1, np.int64), np.zeros(0, ION_DTYPE)
             if sites:
                 out["site_off"], out["sites"] = np.zeros(1, np.int64), np.zeros(0, SITE_DTYPE)
+            if probs:
+                out["site_off"], out["site_probs"], out["psm_probs"] = np.zeros(1, np.int64), np.zeros(0, SITE_PROB_DTYPE), np.zeros(0, PSM_PROB_DTYPE)
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -470,8 +488,9 @@ class PyAscore:
             except (IndexError, ValueError):
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
-            (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0)
-        if sites and site_sig_cap is not None:          # for this call; the handle's own setting comes back
+            (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
+            (_lib.PYA_FLAG_PROBS if probs else 0)
+        if (sites or probs) and site_sig_cap is not None:          # for this call; the handle's own setting comes back
             cap_before = int(self._lib.pya_get_site_sig_cap(self._h))
             self._lib.pya_set_site_sig_cap(self._h, int(site_sig_cap))
             try:
@@ -508,7 +527,21 @@ class PyAscore:
             out["ion_off"], out["ions"] = self._last_batch_ions(n)
         if sites:
             out["site_off"], out["sites"] = self._last_batch_sites(n)
+        if probs:
+            out["site_off"], out["site_probs"], out["psm_probs"] = self._last_batch_probs(n)
         return out
+
+    def _last_batch_probs(self, n):
+        """pya_last_batch_probs: the size query, then the records"""
+        off = np.zeros(n + 1, np.int64)
+        rc = self._lib.pya_last_batch_probs(self._h, _as_ptr(off), None, None, 0)
+        if rc:
+            self._raise(rc)
+        rec, psms = np.zeros(int(off[-1]), SITE_PROB_DTYPE), np.zeros(n, PSM_PROB_DTYPE)
+        rc = self._lib.pya_last_batch_probs(self._h, _as_ptr(off), _as_ptr(rec), _as_ptr(psms), max(rec.size, 1))
+        if rc:
+            self._raise(rc)
+        return off, rec, psms
 
     def _last_batch_sites(self, n):
         """pya_last_batch_sites: the size query, then the records"""
@@ -761,6 +794,29 @@ class PyAscore:
                 raise RuntimeError("the arrays passed to score() changed before sites was read")
             last["sites"] = res["sites"]
         return last["sites"].copy()
+
+    @property
+    def probs(self):
+        """The site probabilities of the last ``score()`` PSM: dict(site_probs, psm_prob) -- one ``SITE_PROB_DTYPE`` record
+        per modifiable residue and the PSM's ``PSM_PROB_DTYPE`` record (see ``score_batch(probs=True)``; no cap on the site
+        assignments).  Produced the first time it is read, by sending that PSM through the batch path as a batch of one."""
+        last = self._last
+        if last is None:
+            return dict(site_probs=np.zeros(0, SITE_PROB_DTYPE), psm_prob=np.zeros(1, PSM_PROB_DTYPE)[0])
+        if "probs" not in last:
+            mz, it = _check_f64("mz_arr", last["mz"]), _check_f64("int_arr", last["it"])
+            psm = dict(n_psm=1, mz=mz, intensity=it, peak_off=np.array([0, mz.size], np.int64), pep=last["pep"],
+                       pep_off=np.array([0, last["pep"].size], np.int64), n_of_mod=np.array([int(last["k"])], np.int32),
+                       max_charge=np.array([int(last["z"])], np.int32), aux_pos=last["aux_pos"], aux_mass=last["aux_mass"],
+                       aux_off=np.array([0, np.size(last["aux_pos"])], np.int64))
+            self._ensure_kept()          # (score_batch does: before the state it leaves is put back)
+            state = (self._last, self._batch_n, self._lazy_batch)
+            res = self.score_batch(psm, probs=True, site_sig_cap=0)
+            self._last, self._batch_n, self._lazy_batch = state
+            if int(res["best_sig"][0]) != int(last["best_sig"]):
+                raise RuntimeError("the arrays passed to score() changed before probs was read")
+            last["probs"] = (res["site_probs"], res["psm_probs"][0])
+        return dict(site_probs=last["probs"][0].copy(), psm_prob=last["probs"][1].copy())
 
     def named(self, signatures):
         """The named-localisation records (``NAMED_DTYPE``, see ``score_batch(named=...)``) of the last ``score()`` PSM for

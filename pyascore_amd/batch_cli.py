@@ -19,6 +19,7 @@ import numpy as np
 from .ascore import PyAscore
 from .named import sig_bits_of
 from . import sites as site_tables
+from . import probs as site_probs
 from .synth import pack_batch, pack_shared_batch
 
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
@@ -30,6 +31,8 @@ REPORTED_COLUMNS = ("ReportedSequence", "ReportedPepScore", "ReportedAscore")
 # ``--sites FILE``: one line per (scan, candidate residue) (pya_site), and two more columns of the main table
 SITE_COLUMNS = ("Scan", "Peptide", "Position", "Residue", "InBest", "WithScore", "WithoutScore", "Delta", "BestWith", "BestWithout")
 RUNNER_UP_COLUMNS = ("RunnerUpSequence", "DeltaPepScore")
+# ``--probs``: the localisation probabilities of a PSM (pya_site_prob, pya_psm_prob)
+PROB_COLUMNS = ("SiteProbs", "BestProb")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -141,7 +144,7 @@ def pack_hits(picked, scans):
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
-             sites=None):
+             sites=None, probs=False):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -153,7 +156,9 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     sequence, its PepScore, and the ambiguity of the winner against it -- did Ascore move the site, and by how much.
     ``sites``: a list that receives the site table of the scored PSMs, one ``site_fields`` row per candidate residue
     (``write_sites_tsv``); every row of the main table then ends with two more fields (``RUNNER_UP_COLUMNS``): the best
-    localisation that differs from the winner, and how far its PepScore lies behind."""
+    localisation that differs from the winner, and how far its PepScore lies behind.
+    ``probs=True`` appends two fields per row, last (``prob_fields``): the peptide with the localisation probability of every
+    candidate residue, and the posterior of the reported localisation."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -167,7 +172,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.
     res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None, named=named,
-                             sites=sites is not None)
+                             sites=sites is not None, probs=probs)
     bad = np.flatnonzero(res["status"])
     if bad.size:
         import warnings
@@ -202,7 +207,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
             ions.extend([scans[i], hit] + ion_fields(rec) for rec in res["ions"][res["ion_off"][i]:res["ion_off"][i + 1]])
         if res["status"][i]:
             rows.append([scans[i], "", float("nan"), "", ""] + (["", "", ""] if evidence else []) + (["", "", ""] if reported else []) +
-                        (["", ""] if sites is not None else []))
+                        (["", ""] if sites is not None else []) + (["", ""] if probs else []))
             continue
         k = psm["n_of_mod"]
         ascores = ";".join(str(s) for s in res["ascores"][i, :k])
@@ -212,8 +217,22 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
                     (evidence_fields(res["evidence"][i, :k]) if evidence else []) +
                     (reported_fields(res["named"][i], rep_seqs[i]) if reported else []) +
                     ([runner_seqs[i], str(runner["delta"][i])] if sites is not None and runner["found"][i] else
-                     (["", ""] if sites is not None else [])))
+                     (["", ""] if sites is not None else [])) +
+                    (prob_fields(res["site_probs"][res["site_off"][i]:res["site_off"][i + 1]], res["psm_probs"][i], psm["peptide"],
+                                 residues) if probs else []))
     return rows
+
+
+def prob_fields(site_recs, psm_rec, peptide, residues):
+    """The two ``--probs`` fields of one PSM: SiteProbs -- the peptide with the probability that it is modified behind every
+    candidate residue, ``AS(0.98)PT(0.02)K`` --, and BestProb -- the posterior of the reported localisation, ``1 / z``.  Both
+    are empty for a PSM that was not scored or has more site assignments than the stage sums; SiteProbs alone when the
+    candidate residues cannot be told from the letters of ``residues`` (a modification group with a terminus)."""
+    if int(psm_rec["kind"]) != site_probs.SCORED:
+        return ["", ""]
+    pos = site_probs.positions_of(peptide, residues)
+    text = site_probs.annotate(peptide, pos, site_recs["with_prob"]) if len(pos) == len(site_recs) else ""
+    return [text, repr(float(site_probs.best_prob(np.asarray([psm_rec], site_probs.PSM_PROB_DTYPE))[0]))]
 
 
 def site_fields(rec, peptide, with_sequence, without_sequence):
@@ -286,13 +305,13 @@ def write_ions_tsv(ion_rows, path):
             out.write("\t".join("%s" % f for f in row) + "\n")
 
 
-def write_tsv(rows, path, evidence=False, reported=False, sites=False):
+def write_tsv(rows, path, evidence=False, reported=False, sites=False, probs=False):
     """Same file pandas' ``DataFrame(rows, columns=COLUMNS).to_csv(path, sep="\\t", index=False)``
     writes in the reference (`__main__.py:166-172`); ``evidence=True``: the rows of ``localize(..., evidence=True)``,
     with their three columns behind the reference's; ``reported=True``: those of ``localize(..., reported=True)`` behind them;
-    ``sites=True``: the two of ``localize(..., sites=[])`` last."""
+    ``sites=True``: the two of ``localize(..., sites=[])`` behind those; ``probs=True``: the two of ``localize(..., probs=True)`` last."""
     with open(path, "w") as out:
         out.write("\t".join(COLUMNS + (EVIDENCE_COLUMNS if evidence else ()) + (REPORTED_COLUMNS if reported else ()) +
-                            (RUNNER_UP_COLUMNS if sites else ())) + "\n")
+                            (RUNNER_UP_COLUMNS if sites else ()) + (PROB_COLUMNS if probs else ())) + "\n")
         for scan, seq, pep_score, ascores, alts, *more in rows:
             out.write("\t".join(["%s" % scan, "%s" % seq, repr(float(pep_score)), ascores, alts] + list(more)) + "\n")

@@ -31,6 +31,12 @@
 #define PYA_ST_INVALID 16          /* set aside by the host pre-pass (PYA_FLAG_SKIP_INVALID): invalid PSM    */
 #define PYA_ST_OVER_LIMIT 17       /* ... or one that exceeds a documented limit of this implementation     */
 
+/* the count-node caps of a launch of the probability stage (probs_cnt.hip.h): peaks of a retained table, steps (L - 1), a
+ * power of two >= 8 and > k_cap, modifications, modifiable residues -- score_cnt.hip's launch arguments */
+struct PcCaps {
+    uint32_t cap, pos_cap, kc, k_cap, n_cap;
+};
+
 /* Scorer configuration as the kernels see it (one copy in device memory per handle).
  * Residue tables are indexed by (letter - 'A') & 31.                                      */
 struct DevConfig {

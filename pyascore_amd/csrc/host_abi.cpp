@@ -64,6 +64,7 @@ void pya_destroy(pya_handle *h) {
     if (h->ions_host) (void)hipHostFree(h->ions_host);
     if (h->named_host) (void)hipHostFree(h->named_host);
     if (h->sites_host) (void)hipHostFree(h->sites_host);
+    if (h->probs_host) (void)hipHostFree(h->probs_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->run_stream) (void)hipStreamDestroy(h->run_stream);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
@@ -265,6 +266,20 @@ int pya_last_batch_sites(pya_handle *h, int64_t *site_off, pya_site *out, uint64
         return h->fail(PYA_ERR_ARG, -1, "capacity %llu < %llu records", (unsigned long long)cap, (unsigned long long)total);
     if (!out) return h->fail(PYA_ERR_ARG, -1, "NULL site array");
     std::memcpy(out, h->sites_host, (size_t)total * sizeof(pya_site));
+    return PYA_OK;
+}
+
+int pya_last_batch_probs(pya_handle *h, int64_t *site_off, pya_site_prob *sites, pya_psm_prob *psms, uint64_t cap) {
+    if (!h || !site_off) return PYA_ERR_ARG;
+    if (!h->probs_valid) return h->fail(PYA_ERR_STATE, -1, "the last batch was scored without PYA_FLAG_PROBS");
+    std::memcpy(site_off, h->probs_off.data(), h->probs_off.size() * sizeof(int64_t));
+    const uint64_t total = (uint64_t)h->probs_off.back(), n_psm = h->probs_off.size() - 1;
+    if (cap == 0 || n_psm == 0) return PYA_OK;
+    if (cap < total)
+        return h->fail(PYA_ERR_ARG, -1, "capacity %llu < %llu records", (unsigned long long)cap, (unsigned long long)total);
+    if (!psms || (total && !sites)) return h->fail(PYA_ERR_ARG, -1, "NULL probability array");
+    if (total) std::memcpy(sites, h->probs_sites(), (size_t)total * sizeof(pya_site_prob));
+    std::memcpy(psms, h->probs_psms(), (size_t)n_psm * sizeof(pya_psm_prob));
     return PYA_OK;
 }
 

@@ -185,6 +185,50 @@ static int sites_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out
     return PYA_OK;
 }
 
+/* PYA_FLAG_PROBS: the handle's pinned block for the probability records of a batch -- residue records bounded as the site
+ * records are, then one record per PSM, zeroed (PYA_SITE_NONE until a chunk's copy lands) -- sized before the first chunk */
+static int probs_host_block(pya_handle *h, const pya_batch *b) {
+    size_t bound = 0;
+    for (uint64_t i = 0; i < b->n_psm; i++) {
+        uint32_t ns = 0;
+        if (psm_letters_ok(h, b->pep + b->pep_off[i], b->pep_off[i + 1] - b->pep_off[i], &ns) && ns <= PYA_MAX_SITES) bound += ns;
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->probs_cap < bound || h->probs_psm_cap < b->n_psm) {
+        if (h->probs_host) (void)hipHostFree(h->probs_host);
+        h->probs_host = nullptr;
+        h->probs_cap = h->probs_psm_cap = 0;
+        const size_t n_sites = bound + bound / 4, n_psms = (size_t)b->n_psm + (size_t)b->n_psm / 4;
+        HIPCHK(h, hipHostMalloc((void **)&h->probs_host, n_sites * sizeof(pya_site_prob) + n_psms * sizeof(pya_psm_prob), hipHostMallocDefault));
+        h->probs_cap = n_sites;
+        h->probs_psm_cap = n_psms;
+    }
+    std::memset(h->probs_psms(), 0, (size_t)b->n_psm * sizeof(pya_psm_prob));
+    h->probs_off.assign(b->n_psm + 1, 0);                     /* (a PSM no plan reaches has no records) */
+    return PYA_OK;
+}
+
+/* ... the probability launches of a plan behind its kernels on `st`, and the records on their way into the block behind
+ * those of the PSMs before `lo` */
+static int probs_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0) return PYA_OK;
+    std::vector<int64_t> off(n + 1);
+    int rc = pya_plan_site_offsets(p, off.data());
+    if (rc) return rc;
+    const int64_t base = h->probs_off[lo], total = off[n];
+    for (uint64_t i = 0; i < n; i++) h->probs_off[lo + 1 + i] = base + off[i + 1];
+    if ((size_t)(base + total) > h->probs_cap || lo + n > h->probs_psm_cap)
+        return h->fail(PYA_ERR_STATE, -1, "probability records beyond the block sized for them");
+    HIPCHK(h, p->d_prob_sites.alloc((size_t)std::max<int64_t>(total, 1)));
+    HIPCHK(h, p->d_prob_psms.alloc((size_t)n));
+    if ((rc = pya_plan_probs(p, d_out, st, h->site_sig_cap, p->d_prob_sites.p, p->d_prob_psms.p))) return rc;
+    if (total)
+        HIPCHK(h, hipMemcpyAsync(h->probs_sites() + base, p->d_prob_sites.p, (size_t)total * sizeof(pya_site_prob), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(h->probs_psms() + lo, p->d_prob_psms.p, (size_t)n * sizeof(pya_psm_prob), hipMemcpyDeviceToHost, st));
+    return PYA_OK;
+}
+
 /* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
  * counts, [n_q * n_top] scores -- zeroed */
 static int named_host_block(pya_handle *h, uint64_t n_q) {
@@ -376,6 +420,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_IONS) && (rc = ions_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if (nq && (rc = named_behind_run(h, p, &d_out, nq, lo, n_q, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_SITES) && (rc = sites_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_PROBS) && (rc = probs_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -421,6 +466,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
     h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
     /* (chunks behind the last PSM with records: their offsets stay at the total) */
     h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
+    h->probs_valid = (flags & PYA_FLAG_PROBS) != 0;
     return finish(PYA_OK);
 }
 
@@ -434,14 +480,17 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->evid_valid = false;
     h->ions_valid = false;
     h->sites_valid = false;
+    h->probs_valid = false;
     if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
     if (flags & PYA_FLAG_SITES) h->sites_off.assign(b->n_psm + 1, 0);
+    if (flags & PYA_FLAG_PROBS) h->probs_off.assign(b->n_psm + 1, 0);
     if (b->n_psm == 0) {
         h->evid_n = 0;
         h->evid_k = out->max_k;
         h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
         h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
         h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
+        h->probs_valid = (flags & PYA_FLAG_PROBS) != 0;
         return PYA_OK;
     }
     uint32_t types = 0;
@@ -480,8 +529,13 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_st = sites_host_block(h, b);
         if (rc_st) return rc_st;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS or _SITES takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    if (flags & PYA_FLAG_PROBS) {
+        if (b->pep_off[b->n_psm] < b->pep_off[0]) return h->fail(PYA_ERR_ARG, -1, "pep_off is not monotone");
+        const int rc_pb = probs_host_block(h, b);
+        if (rc_pb) return rc_pb;
+    }
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES or _PROBS takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -619,6 +673,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         HIPCHK(h, hipStreamSynchronize(nullptr));
         h->sites_valid = true;
     }
+    if (flags & PYA_FLAG_PROBS) {
+        if ((rc = probs_behind_run(h, p, &d_out, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        h->probs_valid = true;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -640,6 +699,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->evid_valid = false;
     h->ions_valid = false;
     h->sites_valid = false;
+    h->probs_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
@@ -673,3 +733,23 @@ int pya_score_batch_named(pya_handle *h, const pya_batch *b, const uint32_t *spe
 
 /* (include/pyascore_debug.h) */
 uint64_t pya_debug_last_chunks(const pya_handle *h) { return h ? h->last_chunks : 0; }
+
+int pya_debug_last_probs_launch(const pya_handle *h, uint32_t front_ends[2], uint64_t lds_bytes[2]) {
+    if (!h || !front_ends || !lds_bytes) return PYA_ERR_ARG;
+    for (int i = 0; i < 2; i++) {
+        front_ends[i] = h->last_probs_sw[i];
+        lds_bytes[i] = h->last_probs_lds[i];
+    }
+    return PYA_OK;
+}
+
+int pya_debug_signature_list(pya_handle *h, uint64_t psm, uint64_t *sig_bits, uint64_t cap, uint64_t *n) {
+    if (!h || !n) return PYA_ERR_ARG;
+    const pya_plan *p = h->kept;
+    if (!p || psm >= p->n_psm) return h->fail(PYA_ERR_ARG, -1, "pya_debug_signature_list: no retained batch, or no such PSM in it");
+    *n = p->n_sig[psm];
+    if (cap == 0) return PYA_OK;
+    if (cap < *n || !sig_bits) return h->fail(PYA_ERR_ARG, -1, "pya_debug_signature_list: room for %llu of %llu", (unsigned long long)cap, (unsigned long long)*n);
+    std::memcpy(sig_bits, h->order_tab.data() + p->order_off[psm], (size_t)*n * sizeof(uint64_t));
+    return PYA_OK;
+}

@@ -131,6 +131,10 @@ int pya_launch_named(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, c
 size_t pya_sites_lds_bytes(uint32_t l_cap, uint32_t list_cap);
 int pya_launch_sites(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_site_off, uint64_t n_out,
                      uint32_t sig_cap, void *d_out, uint32_t l_cap, hipStream_t stream);
+size_t pya_probs_lds_bytes(uint32_t l_cap, const PcCaps *caps, uint32_t sw);
+size_t pya_probs_cnt_bytes(const PcCaps *caps);
+int pya_launch_probs(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_site_off, uint64_t n_out,
+                     uint32_t sig_cap, void *d_out, void *d_psms, uint32_t l_cap, const PcCaps *caps, uint32_t sw, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -243,7 +247,7 @@ struct Knobs {
     bool no_plain = false, no_fused = false, no_big = false, no_tiny = false, no_prefix = false, no_chunks = false;
     bool no_upload_thread = false, one_peak_class = false, peak_classes = false, one_lds_class = false;
     bool host_timing = false, stamps = false, sort_room = false, no_big_inline = false;
-    bool no_loc_hash = false, no_nodes = false, no_cnt = false;
+    bool no_loc_hash = false, no_nodes = false, no_cnt = false, no_prob_cnt = false;
     bool no_fork = false;                       /* r06: the fused family on the plan's stream behind the scoring kernels instead of beside them */
     bool slow_null_stream = false;              /* host_one.cpp: widens the window of a (fixed) workspace race for its regression test */
     uint32_t debug = 0;
@@ -292,6 +296,10 @@ struct pya_handle {
     DevBuf<unsigned char> spare_arena, spare_arena2;   /* two: chunked calls keep two plans alive */
     void *pinned_stage[2] = {nullptr, nullptr};        /* chunked calls: results of chunk c land in slot c % 2 */
     size_t pinned_bytes[2] = {0, 0};
+    /* what the last pya_plan_probs of a plan of this handle launched, per launch (the PSMs inside the fast limits, the general
+     * list): the front ends carved (probs.hip: PB_CNT 1 | PB_GEN 2; 0: no launch) and the LDS bytes (pya_debug_last_probs_launch) */
+    uint32_t last_probs_sw[2] = {0u, 0u};
+    uint64_t last_probs_lds[2] = {0u, 0u};
     uint64_t last_chunks = 0;                  /* plans the last pya_score_batch call was cut into (pya_debug_last_chunks) */
     DevBuf<unsigned char> io_buf;              /* spectra of big pya_score_batch calls (uploaded by a helper thread) */
     DevBuf<unsigned char> io_ring[2];          /* chunked calls: spectra of chunk c in slot c % 2 */
@@ -345,6 +353,14 @@ struct pya_handle {
     std::vector<int64_t> sites_off;           /* [n_psm + 1] of the batch they belong to */
     bool sites_valid = false;                 /* the last batch was scored with the flag */
     uint32_t site_sig_cap = PYA_FAST_SIGNATURES;
+    /* PYA_FLAG_PROBS: the same for the probability records -- one pinned block, [probs_cap] pya_site_prob at the offsets of
+     * the site table, then [probs_psm_cap] pya_psm_prob (zeroed: a PSM no plan reaches is PYA_SITE_NONE) */
+    unsigned char *probs_host = nullptr;
+    size_t probs_cap = 0, probs_psm_cap = 0;
+    std::vector<int64_t> probs_off;
+    bool probs_valid = false;
+    pya_site_prob *probs_sites() const { return (pya_site_prob *)probs_host; }
+    pya_psm_prob *probs_psms() const { return (pya_psm_prob *)(probs_host + probs_cap * sizeof(pya_site_prob)); }
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -683,6 +699,18 @@ struct pya_plan {
     hipEvent_t ev_sites = nullptr;
     bool site_off_sent = false;
     DevBuf<pya_site> d_sites;
+    /* pya_plan_probs: the count-node caps of its two launches (the PSMs inside the fast limits, the general list) -- the
+     * largest L - 1, n_of_mod and n_sites among the PSMs of a list whose shape the count-node front end takes, the peaks a
+     * staged table may then have inside the 64 KiB the tables are held to, the largest spectrum (rounded up to 32 peaks)
+     * among the PSMs that qualify, how many those are and how many PSMs of the list will be scored at all (host_run.cpp:
+     * prob_lists) --, the records of a pya_score_batch plan */
+    struct ProbList {
+        uint32_t pos_max = 1, k_max = 0, ns_max = 0, kc = 8, peak_room = 0, peak_max = 0, n_fit = 0, n_scored = 0;
+    };
+    ProbList prob_lists[2];
+    bool prob_lists_made = false;
+    DevBuf<pya_site_prob> d_prob_sites;
+    DevBuf<pya_psm_prob> d_prob_psms;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -817,6 +845,9 @@ static_assert(sizeof(pya_site) == 32 && offsetof(pya_site, without_sig) == 8 && 
                   offsetof(pya_site, without_score) == 20 && offsetof(pya_site, pos) == 24 && offsetof(pya_site, kind) == 26 &&
                   offsetof(pya_site, flags) == 27 && offsetof(pya_site, reserved) == 28,
               "pya_site is two 16-byte stores of sites.hip");
+static_assert(sizeof(pya_site_prob) == 16 && offsetof(pya_site_prob, without_prob) == 8 && sizeof(pya_psm_prob) == 16 &&
+                  offsetof(pya_psm_prob, n_summed) == 8 && offsetof(pya_psm_prob, kind) == 12,
+              "pya_site_prob and pya_psm_prob are one 16-byte store of probs.hip each");
 /* pya_score_batch_named's queries and outputs (host arrays of the caller), nullptr for the other batch entry points */
 struct NamedReq {
     const int64_t *q_off;

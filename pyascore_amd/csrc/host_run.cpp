@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_SITES)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_SITES | PYA_FLAG_PROBS)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -612,6 +612,120 @@ int pya_plan_sites(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t
         e = pya_launch_sites(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), p->d_site_off.p, n_out, sig_cap, d_out, p->gen_l_cap, st);
     if (e) return h->hip_fail((hipError_t)e, "site launch");
     HIPCHK(h, hipEventRecord(p->ev_sites, st));
+    return PYA_OK;
+}
+
+/* The probability stage (csrc/probs.hip): the site stage's offsets, wait and two launches.  Each launch carves the front
+ * ends its PSMs need: the count-node tables (probs_cnt.hip.h) with the caps of the PSMs that qualify for them, the general
+ * front end when a PSM of the list does not -- or none does: other settings, PYA_NO_PROB_CNT.
+ * The host's test of a PSM is the kernel's (probs_cnt.hip.h: pc_fits) term for term, with the spectrum's peak count standing
+ * for the retained table's (a table never has more entries than its spectrum has peaks; the plan's peak_cap is NOT that
+ * bound: it leaves out the spectra above PYA_FAST_PEAKS), so a list whose PSMs all pass can be launched with the tables
+ * alone.  Like a score_cnt bucket the tables are held to 64 KiB: the shapes of the qualifying PSMs fix everything but the
+ * staged peak table, what is left of the 64 KiB is the room for peaks, and a PSM with a larger spectrum takes the general
+ * front end instead of setting the footprint of the whole launch.  PSMs that no front end will see -- set aside, more
+ * modifications than sites, no site assignment -- neither qualify nor stand in the way. */
+static const size_t kProbCntLds = 64u * 1024u;
+static void prob_lists(pya_plan *p) {
+    if (p->prob_lists_made) return;
+    auto list_of = [&](uint64_t i) -> pya_plan::ProbList & { return p->prob_lists[!p->gen.empty() && p->gen[i] ? 1 : 0]; };
+    auto shape_ok = [&](uint64_t i) {
+        const int64_t L = p->pep_off[i + 1] - p->pep_off[i];
+        const int32_t k = p->n_of_mod[i];
+        return L >= 2 && L <= 64 && p->max_charge[i] == 1 && k + 1 <= 31 && p->n_sites[i] <= 32u;
+    };
+    auto scored = [&](uint64_t i) {
+        return (p->pre_status.empty() || !p->pre_status[i]) && p->n_of_mod[i] >= 0 && (uint32_t)p->n_of_mod[i] <= p->n_sites[i] && p->n_sig[i] > 0;
+    };
+    for (uint64_t i = 0; i < p->n_psm; i++) {
+        if (!scored(i)) continue;
+        pya_plan::ProbList &l = list_of(i);
+        l.n_scored++;
+        if (!shape_ok(i)) continue;
+        l.pos_max = std::max(l.pos_max, (uint32_t)(p->pep_off[i + 1] - p->pep_off[i] - 1));
+        l.k_max = std::max(l.k_max, (uint32_t)p->n_of_mod[i]);
+        l.ns_max = std::max(l.ns_max, (uint32_t)p->n_sites[i]);
+    }
+    for (pya_plan::ProbList &l : p->prob_lists) {
+        PcCaps c = {0u, l.pos_max, 8u, l.k_max, l.ns_max};
+        while (c.kc < c.k_cap + 1u) c.kc <<= 1;
+        l.kc = c.kc;
+        const size_t fixed = pya_probs_cnt_bytes(&c) + 64u * 16u;            /* (with the slice's 64 pairs) */
+        l.peak_room = fixed < kProbCntLds ? (uint32_t)((kProbCntLds - fixed) / sizeof(PeakEntry)) & ~31u : 0u;
+    }
+    for (uint64_t i = 0; i < p->n_psm; i++) {
+        if (!scored(i) || !shape_ok(i)) continue;
+        pya_plan::ProbList &l = list_of(i);
+        const uint64_t P = ((uint64_t)p->n_peaks(i) + 31u) & ~(uint64_t)31u;
+        if (P > l.peak_room) continue;
+        l.n_fit++;
+        l.peak_max = std::max(l.peak_max, (uint32_t)P);
+    }
+    p->prob_lists_made = true;
+}
+
+int pya_plan_probs(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t sig_cap, pya_site_prob *d_sites, pya_psm_prob *d_psms) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_probs: the plan has not been run");
+    site_offsets(p);
+    const uint64_t n_out = (uint64_t)p->site_off[p->n_psm];
+    if (!d_psms || (n_out && !d_sites) || !r->best_score || !r->best_sig || !r->n_sig)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_probs");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->ev_sites) HIPCHK(h, hipEventCreateWithFlags(&p->ev_sites, hipEventDisableTiming));
+    prob_lists(p);
+    const DevConfig &c = h->cfg;
+    const bool plain = c.n_nl == 0 && c.n_types == 2 && c.n_fwd == 1 && c.n_top == PYA_NTOP && h->mz_error <= 0.49f && !h->kn.no_prob_cnt;
+    PcCaps caps[2] = {};
+    uint32_t sw[2] = {2u, 2u};                                 /* (probs.hip: PB_CNT 1, PB_GEN 2) */
+    for (int li = 0; li < 2; li++) {
+        const pya_plan::ProbList &l = p->prob_lists[li];
+        if (!plain || l.n_fit == 0) continue;
+        const PcCaps k = {l.peak_max, l.pos_max, l.kc, l.k_max, l.ns_max};
+        caps[li] = k;
+        /* the tables alone only for the list of the PSMs inside the fast limits, and only when every PSM of it that will be
+         * scored passed the kernel's own test on the host: whatever else is in a list needs the general front end */
+        sw[li] = li == 0 && l.n_fit == l.n_scored ? 1u : 3u;
+    }
+    /* (stage_behind_run sizes the general front end's LDS: l_cap alone counts, the stage keeps no fragment list) */
+    struct Room {
+        static size_t general(uint32_t l_cap, uint32_t) {
+            const PcCaps none = {};
+            return pya_probs_lds_bytes(l_cap, &none, 2u);
+        }
+    };
+    const int rc = stage_behind_run(p, st, "pya_plan_probs", "probability", Room::general);
+    if (rc) return rc;
+    if (pya_probs_lds_bytes(p->evid_l_cap, &caps[0], sw[0]) > kMaxLds) sw[0] = 2u;
+    if (pya_probs_lds_bytes(p->gen_l_cap, &caps[1], sw[1]) > kMaxLds) sw[1] = 2u;
+    if (!p->site_off_sent) {
+        /* (from the plan's own vector, which outlives the copy; a later call on another stream waits for it below) */
+        HIPCHK(h, p->d_site_off.alloc(p->n_psm + 1));
+        HIPCHK(h, hipMemcpyAsync(p->d_site_off.p, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipEventRecord(p->ev_sites, st));
+        p->site_off_sent = true;
+    } else {
+        HIPCHK(h, hipStreamWaitEvent(st, p->ev_sites, 0));
+    }
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.best_score = r->best_score;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    int e = pya_launch_probs(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, p->d_site_off.p, n_out, sig_cap, d_sites, d_psms,
+                             p->evid_l_cap, &caps[0], sw[0], st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_probs(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), p->d_site_off.p, n_out, sig_cap, d_sites, d_psms, p->gen_l_cap,
+                             &caps[1], sw[1], st);
+    if (e) return h->hip_fail((hipError_t)e, "probability launch");
+    for (int li = 0; li < 2; li++) {                            /* (pya_debug_last_probs_launch) */
+        const bool launched = li == 0 ? p->evid_n_fast != 0 : !p->gen_ids.empty();
+        h->last_probs_sw[li] = launched ? sw[li] : 0u;
+        h->last_probs_lds[li] = launched ? pya_probs_lds_bytes(li == 0 ? p->evid_l_cap : p->gen_l_cap, &caps[li], sw[li]) : 0u;
+    }
     return PYA_OK;
 }
 

@@ -25,9 +25,10 @@ class DevicePlan:
     launches instead of the one-launch kernel).  ``ions()`` / ``ions=True``: the same for the ion records
     (``pya_plan_ions_count``, ``pya_plan_ions``).  ``named()`` / ``named=True``: the same for the records of localisations
     the caller names (``pya_plan_named``).  ``sites()`` / ``sites=True``: the same for the site tables
-    (``pya_plan_site_offsets``, ``pya_plan_sites``)."""
+    (``pya_plan_site_offsets``, ``pya_plan_sites``).  ``probs()`` / ``probs=True``: the same for the site probabilities
+    (``pya_plan_probs``)."""
 
-    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False):
+    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -56,7 +57,8 @@ class DevicePlan:
                        _as_ptr(m["aux_mass"]), _as_ptr(m["aux_off"]))
         self._plan = C.c_void_p()
         flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
-            (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0)
+            (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
+            (_lib.PYA_FLAG_PROBS if probs else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -212,6 +214,30 @@ class DevicePlan:
             self.scorer._raise(rc)
         return off, out
 
+    def probs(self, sig_cap=0, out=None):
+        """The site probabilities of the last ``run()``: ``(site_off, site_probs, psm_probs)`` -- the host offsets of
+        ``site_offsets()``, a ``torch.float64`` device tensor ``[site_off[-1], 2]`` (``with_prob``, ``without_prob`` per
+        modifiable residue) and a ``torch.uint8`` device tensor ``[n_psm, 16]`` (one ``pya_psm_prob`` each; ``psm_prob_records``
+        turns a host copy into the structured array).  One launch family of the library behind the run on torch's current
+        stream; nothing waits on the host.  ``sig_cap`` as for ``sites()``; ``out``: the two tensors of an earlier call, to be
+        written again.  Valid for the results of the last run."""
+        torch = self._torch
+        off = self.site_offsets()
+        shapes = ((int(off[-1]), 2), (self.n_psm, 16))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = (torch.zeros(shapes[0], dtype=torch.float64, device=self.device),
+                       torch.zeros(shapes[1], dtype=torch.uint8, device=self.device))
+        site_probs, psm_probs = out
+        for t, shape, dtype in ((site_probs, shapes[0], torch.float64), (psm_probs, shapes[1], torch.uint8)):
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("out must be contiguous device tensors: float64 %r and uint8 %r" % shapes)
+        rc = self._lib.pya_plan_probs(self._plan, C.byref(self._res), stream, int(sig_cap), site_probs.data_ptr(), psm_probs.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return off, site_probs, psm_probs
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -260,6 +286,7 @@ EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)
 NAMED_DTYPE = np.dtype(_lib.NAMED_DTYPE)
 SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)
+PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)
 
 
 def evidence_rows(raw):
@@ -300,6 +327,15 @@ def site_records(raw):
     if a.ndim != 2 or a.shape[1] != SITE_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, %d)" % SITE_DTYPE.itemsize)
     return a.view(SITE_DTYPE).reshape(a.shape[0])
+
+
+def psm_prob_records(raw):
+    """A host copy of the PSM records of ``DevicePlan.probs()`` (``.cpu().numpy()``, uint8 ``[n, 16]``) as the structured
+    array ``PyAscore.score_batch(..., probs=True)`` returns in ``psm_probs``; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != PSM_PROB_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % PSM_PROB_DTYPE.itemsize)
+    return a.view(PSM_PROB_DTYPE).reshape(a.shape[0])
 
 
 def named_records(raw):
