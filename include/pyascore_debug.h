@@ -50,6 +50,11 @@ uint64_t pya_debug_last_chunks(const pya_handle *h);
  * (the kernel chooses per PSM), 0 no launch; lds_bytes = the dynamic LDS of the launch.  No reference counterpart. */
 int pya_debug_last_probs_launch(const pya_handle *h, uint32_t front_ends[2], uint64_t lds_bytes[2]);
 
+/* The same for the last pya_plan_ranked call (a batch call with PYA_FLAG_RANKED makes one per chunk): the front ends and
+ * the LDS bytes of its two launches, with the meanings above.  PYA_NO_PROB_CNT holds for this stage as well.  No reference
+ * counterpart. */
+int pya_debug_last_ranked_launch(const pya_handle *h, uint32_t front_ends[2], uint64_t lds_bytes[2]);
+
 /* The signature list of PSM `psm` of the handle's retained batch (the last PYA_FLAG_KEEP call): the sig bits of its site
  * assignments in the order every kernel scores them in and the probability stage sums them in (pya_get_pep_scores* returns
  * the reference's sorted order instead).  *n = their number; sig_bits may be NULL with cap 0 to ask.  No reference

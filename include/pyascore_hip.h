@@ -97,6 +97,9 @@ extern "C" {
 #define PYA_FLAG_PROBS 128u /* pya_score_batch* / pya_score_batch_named: the site probabilities of every PSM as */
                             /* well (pya_last_batch_probs); pya_plan_create*: as PYA_FLAG_EVIDENCE              */
                             /* (pya_plan_site_offsets / pya_plan_probs)                                         */
+#define PYA_FLAG_RANKED 256u /* pya_score_batch* / pya_score_batch_named: the ranked localisations of every PSM as */
+                             /* well (pya_last_batch_ranked, pya_set_ranked_k); pya_plan_create*: as               */
+                             /* PYA_FLAG_EVIDENCE (pya_plan_ranked)                                                */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -282,6 +285,41 @@ typedef struct pya_psm_prob {      /* 16 bytes, one store */
     uint8_t pad[3];                /* 0                                                                        */
 } pya_psm_prob;
 
+/* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
+ * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
+ * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
+ * 3 PepScore units of the winner", "how many assignments tie the best score".  The reference has no counterpart but a sort
+ * of its pep_scores records.  The stage writes K records per PSM at a fixed stride, out[psm * K + r], r = 0 .. K - 1,
+ * 1 <= K <= PYA_MAX_RANKED.  For a scored PSM with n_sig site assignments the rows 0 .. min(n_sig, K) - 1 hold:
+ *   row 0        the reported localisation: sig_bits == best_sig, pep_score has the bits of best_score.  It is the
+ *                reference's winner with the reference's own tie-break and is not decided again here.
+ *   rows 1 ..    every OTHER site assignment by PepScore descending, compared as float32; equal floats by numerically
+ *                ascending sig_bits.  The rule does not depend on the reference's std::sort order, on the route that scored
+ *                the PSM, on chunk cuts, on batch neighbours or on K: for K' < K the K' list is bytewise the prefix of the K
+ *                list, and no field says "last row" or anything else that depends on K.
+ * No assignment scores above best_score.  Every pep_score is bit-equal to ScoreContainer.weighted_score of the record with
+ * the same sig bits from a PYA_FLAG_KEEP batch.  n_of_mod == 0 is one assignment with sig 0 and n_of_mod == n_sites one with
+ * every site: row 0 only.  kind:
+ *   PYA_RANK_NONE    the PSM was not scored (set aside, status != 0, n_sig <= 0), or the row is at or beyond n_sig: all 16
+ *                    bytes 0;
+ *   PYA_RANK_OVER    n_sig is above the sig_cap of the call (as for pya_plan_sites; 0: no cap): row 0 only, with best_sig,
+ *                    best_score and the kind (flags 0), the rows behind it zero;
+ *   PYA_RANK_SCORED  otherwise.  flags: PYA_RANK_TIED_PREV the pep_score is float-equal to the row above's,
+ *                    PYA_RANK_IN_BEST_TIE it is float-equal to best_score (row 0 carries it too). */
+#define PYA_MAX_RANKED 64
+#define PYA_RANK_NONE 0
+#define PYA_RANK_SCORED 1
+#define PYA_RANK_OVER 2
+#define PYA_RANK_TIED_PREV 1
+#define PYA_RANK_IN_BEST_TIE 2
+typedef struct pya_ranked {        /* 16 bytes, one store; records compare as raw bytes */
+    uint64_t sig_bits;             /* the site assignment: bit j = the j-th modifiable residue is modified    */
+    float pep_score;               /* its PepScore                                                            */
+    uint16_t rank;                 /* = r, the row                                                            */
+    uint8_t kind;                  /* PYA_RANK_NONE / _SCORED / _OVER                                         */
+    uint8_t flags;                 /* PYA_RANK_TIED_PREV | PYA_RANK_IN_BEST_TIE                               */
+} pya_ranked;
+
 typedef struct pya_handle pya_handle;
 typedef struct pya_plan pya_plan;
 
@@ -462,6 +500,17 @@ uint32_t pya_get_site_sig_cap(const pya_handle *h);
  * pya_set_site_sig_cap's.  The records do not depend on the route that scored a PSM, on how the batch was cut into chunks,
  * or on shared / typed input. */
 int pya_last_batch_probs(pya_handle *h, int64_t *site_off, pya_site_prob *sites, pya_psm_prob *psms, uint64_t cap);
+/* The ranked localisations (pya_ranked above) of the last pya_score_batch / _shared / _typed / _named call on this handle
+ * that was given PYA_FLAG_RANKED: out[n_psm * top_k], the rows of PSM i at out[i * top_k].  n_psm and top_k must be those of
+ * the call (top_k: what pya_get_ranked_k returned when it was made), anything else is PYA_ERR_ARG, as is a NULL array for a
+ * batch that has PSMs.  PYA_ERR_STATE when the last batch was scored without the flag.  A PSM that was set aside has
+ * PYA_RANK_NONE rows.  The cap on site assignments per PSM is pya_set_site_sig_cap's.  The records do not depend on the route
+ * that scored a PSM, on how the batch was cut into chunks, or on shared / typed input. */
+int pya_last_batch_ranked(pya_handle *h, pya_ranked *out, uint64_t n_psm, uint32_t top_k);
+/* The list length K of the batch calls with PYA_FLAG_RANKED (the counterpart of pya_set_site_sig_cap; pya_plan_ranked takes
+ * its own): 1 .. PYA_MAX_RANKED, anything else is PYA_ERR_ARG and changes nothing.  The default is 5. */
+int pya_set_ranked_k(pya_handle *h, uint32_t top_k);
+uint32_t pya_get_ranked_k(const pya_handle *h);
 
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
@@ -529,6 +578,13 @@ int pya_plan_sites(pya_plan *plan, const pya_results *d_res, void *hip_stream, u
  * be called again; no write lies at or past d_sites + site_off[n_psm].  It reads best_score, best_sig and n_sig of d_res. */
 int pya_plan_probs(pya_plan *plan, const pya_results *d_res, void *hip_stream, uint32_t sig_cap, pya_site_prob *d_sites,
                    pya_psm_prob *d_psms);
+/* The ranked localisations of the results the last pya_plan_run* of this plan wrote: d_out[n_psm * top_k] records, device
+ * memory, the rows of PSM i at d_out[i * top_k]; top_k 1 .. PYA_MAX_RANKED (anything else: PYA_ERR_ARG).  Everything else as
+ * for pya_plan_probs: stream-ordered (csrc/ranked.hip), no host synchronisation inside, waits for the run, valid until the
+ * plan is run again, may be called again (with another top_k too); no write lies at or past d_out + n_psm * top_k.  It reads
+ * best_score, best_sig and n_sig of d_res.  A plan of a handful of PSMs is created with PYA_FLAG_RANKED (or another stage
+ * flag): the one-launch kernel leaves no retained tables. */
+int pya_plan_ranked(pya_plan *plan, const pya_results *d_res, void *hip_stream, uint32_t top_k, uint32_t sig_cap, pya_ranked *d_out);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

@@ -7,7 +7,8 @@ command line override it.  ``--device`` (HIP ordinal), ``--evidence`` (three mor
 Ascore), ``--ions FILE`` (a second table: which ions, one line each) and ``--reported`` (three more columns: the search
 engine's own site assignment, scored against the winner) and ``--sites FILE`` (a table with a line per candidate residue, and
 the runner-up localisation in the main one) and ``--probs`` (two more columns: the localisation probability of every
-candidate residue and the posterior of the reported localisation) are the additions."""
+candidate residue and the posterior of the reported localisation) and ``--ranked FILE`` with ``--ranked_depth K`` (a table
+with a line per ranked site assignment: the K best localisations of every PSM, in order) are the additions."""
 import argparse
 import re
 import sys
@@ -65,6 +66,12 @@ def build_parser():
                    help="append SiteProbs and BestProb: the peptide with the localisation probability of every candidate residue "
                         "behind it, AS(0.98)PT(0.02)K, and the posterior of the reported localisation -- a PepScore-based "
                         "posterior (MaxQuant's construction), not part of the Ascore publication")
+    p.add_argument("--ranked", type=str, default=None, metavar="FILE",
+                   help="write the ranked localisations to FILE: one line per (scan, hit, rank) for the --ranked_depth best site "
+                        "assignments of every scored PSM in order, the reported localisation first (Scan, Hit, Rank, "
+                        "LocalizedSequence, PepScore, DeltaToBest, Tied); the main table does not change")
+    p.add_argument("--ranked_depth", type=int, default=5, metavar="K",
+                   help="how many site assignments per PSM --ranked lists, 1 .. 64 (default 5)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -125,15 +132,21 @@ def run(args, log=print):
             ascore.add_neutral_loss(group, float(mass))
     ion_rows = [] if args.ions else None
     site_rows = [] if args.sites else None
+    ranked_rows = [] if args.ranked else None
+    if ranked_rows is not None:
+        from .ranked import check_k
+        check_k(args.ranked_depth)
     rows = batch_cli.localize(ascore, psms, spectra, args.residues, args.mod_mass, args.hit_depth,
                               args.max_fragment_charge, args.mod_correction_tol, args.zero_based,
                               match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
                               evidence=args.evidence, ions=ion_rows, reported=args.reported, sites=site_rows,
-                              probs=args.probs)
+                              probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
         batch_cli.write_sites_tsv(site_rows, args.sites)
+    if ranked_rows is not None:
+        batch_cli.write_ranked_tsv(ranked_rows, args.ranked)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

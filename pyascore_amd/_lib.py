@@ -15,6 +15,10 @@ PYA_FLAG_KEEP, PYA_FLAG_TIMING, PYA_FLAG_SKIP_INVALID, PYA_FLAG_EVIDENCE, PYA_FL
 PYA_FLAG_NAMED = 32
 PYA_FLAG_SITES = 64
 PYA_FLAG_PROBS = 128
+PYA_FLAG_RANKED = 256
+PYA_MAX_RANKED = 64
+PYA_RANK_NONE, PYA_RANK_SCORED, PYA_RANK_OVER = 0, 1, 2
+PYA_RANK_TIED_PREV, PYA_RANK_IN_BEST_TIE = 1, 2
 PYA_SITE_NONE, PYA_SITE_SCORED, PYA_SITE_OVER = 0, 1, 2
 PYA_SITE_IN_BEST, PYA_SITE_WITH_TIED, PYA_SITE_WITHOUT_TIED, PYA_SITE_NO_WITHOUT = 1, 2, 4, 8
 PYA_FAST_SIGNATURES = 15000
@@ -113,6 +117,15 @@ assert C.sizeof(SiteProb) == 16 and C.sizeof(PsmProb) == 16, "pya_site_prob and 
 SITE_PROB_DTYPE = [("with_prob", "<f8"), ("without_prob", "<f8")]
 PSM_PROB_DTYPE = [("z", "<f8"), ("n_summed", "<u4"), ("kind", "u1"), ("pad", "u1", (3,))]
 
+
+class Ranked(C.Structure):
+    """pya_ranked: one row of a PSM's ranked localisations -- a site assignment, its PepScore, its rank"""
+    _fields_ = [("sig_bits", C.c_uint64), ("pep_score", C.c_float), ("rank", C.c_uint16), ("kind", C.c_uint8), ("flags", C.c_uint8)]
+
+
+assert C.sizeof(Ranked) == 16, "pya_ranked is a 16-byte record"
+RANKED_DTYPE = [("sig_bits", "<u8"), ("pep_score", "<f4"), ("rank", "<u2"), ("kind", "u1"), ("flags", "u1")]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -135,6 +148,7 @@ SYMBOLS = {
     "pya_debug_wave_ops": (C.c_int, [_vp, _vp, _vp]),         # (test-only)
     "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
     "pya_debug_last_probs_launch": (C.c_int, [_vp, _vp, _vp]),        # (test-only)
+    "pya_debug_last_ranked_launch": (C.c_int, [_vp, _vp, _vp]),       # (test-only)
     "pya_debug_signature_list": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp]),   # (test-only)
     "pya_debug_plan_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
     "pya_debug_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
@@ -165,6 +179,10 @@ SYMBOLS = {
     "pya_plan_sites": (C.c_int, [_vp, C.POINTER(Results), _vp, C.c_uint32, _vp]),
     "pya_last_batch_probs": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64]),
     "pya_plan_probs": (C.c_int, [_vp, C.POINTER(Results), _vp, C.c_uint32, _vp, _vp]),
+    "pya_last_batch_ranked": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32]),
+    "pya_set_ranked_k": (C.c_int, [_vp, C.c_uint32]),
+    "pya_get_ranked_k": (C.c_uint32, [_vp]),
+    "pya_plan_ranked": (C.c_int, [_vp, C.POINTER(Results), _vp, C.c_uint32, C.c_uint32, _vp]),
     "pya_plan_create": (C.c_int, [_vp, C.POINTER(Batch), C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_create_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_run": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Results)]),

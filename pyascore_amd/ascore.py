@@ -74,10 +74,13 @@ SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)              # pya_site, 32 bytes
 SITE_PROB_DTYPE = np.dtype(_lib.SITE_PROB_DTYPE)    # pya_site_prob, 16 bytes
 PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)      # pya_psm_prob, 16 bytes
 assert SITE_PROB_DTYPE.itemsize == 16 and PSM_PROB_DTYPE.itemsize == 16
+RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)          # pya_ranked, 16 bytes
+assert RANKED_DTYPE.itemsize == 16
 assert EVIDENCE_DTYPE.itemsize == 16
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
 assert ION_DTYPE.itemsize == 16
 from .named import NAMED_DTYPE, query_csr, sig_bits_batch, sig_bits_of, take_queries  # noqa: E402,F401
+from .ranked import check_k as check_ranked_k  # noqa: E402
 _NO_U32 = np.zeros(0, np.uint32)
 _NO_F32 = np.zeros(0, np.float32)
 
@@ -313,7 +316,7 @@ class PyAscore:
             self._batch_n = 1
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
-                    site_sig_cap=None, probs=False):
+                    site_sig_cap=None, probs=False, ranked=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -357,6 +360,11 @@ class PyAscore:
         10^((PepScore - best) / 10) over the site assignments -- the posterior of the reported localisation is ``1 / z`` --,
         ``n_summed`` and ``kind`` as for ``sites``).  A PepScore-based posterior (MaxQuant's construction), not part of the
         Ascore publication; ``pyascore_amd.probs`` has ``best_prob``, ``table`` and ``annotate``.  ``site_sig_cap`` applies.
+        ``ranked=K`` (1 .. 64) adds ``ranked`` (``RANKED_DTYPE``, the 16-byte ``pya_ranked``, shape ``[n, K]``): per PSM its K
+        best site assignments in order -- row 0 the reported localisation, the others by PepScore descending, equal scores
+        by ascending ``sig_bits``; rows at and beyond ``n_sig`` and the rows of a PSM that was not scored are zero
+        (``pyascore_amd.ranked`` has ``lengths``, ``within`` and ``best_tie_size``).  ``site_sig_cap`` applies: a PSM with
+        more site assignments has row 0 alone, of kind ``PYA_RANK_OVER``.
 
         Every other result is what it is without the option.
 
@@ -373,12 +381,13 @@ class PyAscore:
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
         of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
         float64 intensities."""
+        ranked_k = None if ranked is None or ranked is False else check_ranked_k(ranked)
         if batch.get("spec_of") is not None:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
-                                        named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs)
+                                        named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -387,7 +396,7 @@ class PyAscore:
                 try:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
-                                           site_sig_cap=site_sig_cap, probs=probs)
+                                           site_sig_cap=site_sig_cap, probs=probs, ranked=ranked)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
@@ -466,6 +475,8 @@ class PyAscore:
                 out["site_off"], out["sites"] = np.zeros(1, np.int64), np.zeros(0, SITE_DTYPE)
             if probs:
                 out["site_off"], out["site_probs"], out["psm_probs"] = np.zeros(1, np.int64), np.zeros(0, SITE_PROB_DTYPE), np.zeros(0, PSM_PROB_DTYPE)
+            if ranked_k:
+                out["ranked"] = np.zeros((0, ranked_k), RANKED_DTYPE)
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -489,16 +500,22 @@ class PyAscore:
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
             (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
-            (_lib.PYA_FLAG_PROBS if probs else 0)
-        if (sites or probs) and site_sig_cap is not None:          # for this call; the handle's own setting comes back
+            (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0)
+        # for this call; the handle's own settings come back
+        cap_before = k_before = None
+        if (sites or probs or ranked_k) and site_sig_cap is not None:
             cap_before = int(self._lib.pya_get_site_sig_cap(self._h))
             self._lib.pya_set_site_sig_cap(self._h, int(site_sig_cap))
-            try:
-                rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
-            finally:
-                self._lib.pya_set_site_sig_cap(self._h, cap_before)
-        else:
+        if ranked_k:
+            k_before = int(self._lib.pya_get_ranked_k(self._h))
+            self._lib.pya_set_ranked_k(self._h, ranked_k)
+        try:
             rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
+        finally:
+            if cap_before is not None:
+                self._lib.pya_set_site_sig_cap(self._h, cap_before)
+            if k_before is not None:
+                self._lib.pya_set_ranked_k(self._h, k_before)
         if rc:
             self._raise(rc)
         self._batch_n = n if keep else None
@@ -529,6 +546,11 @@ class PyAscore:
             out["site_off"], out["sites"] = self._last_batch_sites(n)
         if probs:
             out["site_off"], out["site_probs"], out["psm_probs"] = self._last_batch_probs(n)
+        if ranked_k:
+            out["ranked"] = np.zeros((n, ranked_k), RANKED_DTYPE)
+            rc = self._lib.pya_last_batch_ranked(self._h, _as_ptr(out["ranked"]), n, ranked_k)
+            if rc:
+                self._raise(rc)
         return out
 
     def _last_batch_probs(self, n):
@@ -817,6 +839,30 @@ class PyAscore:
                 raise RuntimeError("the arrays passed to score() changed before probs was read")
             last["probs"] = (res["site_probs"], res["psm_probs"][0])
         return dict(site_probs=last["probs"][0].copy(), psm_prob=last["probs"][1].copy())
+
+    def ranked(self, top_k=5):
+        """The ranked localisations of the last ``score()`` PSM: ``RANKED_DTYPE`` ``[top_k]`` -- row 0 the reported
+        localisation, then the other site assignments by PepScore (see ``score_batch(ranked=K)``; no cap on the site
+        assignments).  Produced by sending that PSM through the batch path as a batch of one, once per ``top_k``."""
+        top_k = check_ranked_k(top_k)
+        last = self._last
+        if last is None:
+            return np.zeros(top_k, RANKED_DTYPE)
+        got = last.setdefault("ranked", {})
+        if top_k not in got:
+            mz, it = _check_f64("mz_arr", last["mz"]), _check_f64("int_arr", last["it"])
+            psm = dict(n_psm=1, mz=mz, intensity=it, peak_off=np.array([0, mz.size], np.int64), pep=last["pep"],
+                       pep_off=np.array([0, last["pep"].size], np.int64), n_of_mod=np.array([int(last["k"])], np.int32),
+                       max_charge=np.array([int(last["z"])], np.int32), aux_pos=last["aux_pos"], aux_mass=last["aux_mass"],
+                       aux_off=np.array([0, np.size(last["aux_pos"])], np.int64))
+            self._ensure_kept()          # (score_batch does: before the state it leaves is put back)
+            state = (self._last, self._batch_n, self._lazy_batch)
+            res = self.score_batch(psm, ranked=top_k, site_sig_cap=0)
+            self._last, self._batch_n, self._lazy_batch = state
+            if int(res["best_sig"][0]) != int(last["best_sig"]):
+                raise RuntimeError("the arrays passed to score() changed before ranked() was called")
+            got[top_k] = res["ranked"][0]
+        return got[top_k].copy()
 
     def named(self, signatures):
         """The named-localisation records (``NAMED_DTYPE``, see ``score_batch(named=...)``) of the last ``score()`` PSM for

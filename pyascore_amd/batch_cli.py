@@ -20,6 +20,7 @@ from .ascore import PyAscore
 from .named import sig_bits_of
 from . import sites as site_tables
 from . import probs as site_probs
+from . import ranked as ranked_lists
 from .synth import pack_batch, pack_shared_batch
 
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
@@ -33,6 +34,8 @@ SITE_COLUMNS = ("Scan", "Peptide", "Position", "Residue", "InBest", "WithScore",
 RUNNER_UP_COLUMNS = ("RunnerUpSequence", "DeltaPepScore")
 # ``--probs``: the localisation probabilities of a PSM (pya_site_prob, pya_psm_prob)
 PROB_COLUMNS = ("SiteProbs", "BestProb")
+# ``--ranked FILE``: one line per (scan, hit, rank) (pya_ranked)
+RANKED_COLUMNS = ("Scan", "Hit", "Rank", "LocalizedSequence", "PepScore", "DeltaToBest", "Tied")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -144,7 +147,7 @@ def pack_hits(picked, scans):
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
-             sites=None, probs=False):
+             sites=None, probs=False, ranked=None, ranked_depth=5):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -158,7 +161,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     (``write_sites_tsv``); every row of the main table then ends with two more fields (``RUNNER_UP_COLUMNS``): the best
     localisation that differs from the winner, and how far its PepScore lies behind.
     ``probs=True`` appends two fields per row, last (``prob_fields``): the peptide with the localisation probability of every
-    candidate residue, and the posterior of the reported localisation."""
+    candidate residue, and the posterior of the reported localisation.
+    ``ranked``: a list that receives the ranked localisations of the scored PSMs, the ``ranked_depth`` best site assignments
+    of each in order, one ``[scan, hit] + ranked_fields`` row per assignment (``write_ranked_tsv``); the main table does not
+    change."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -172,7 +178,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.
     res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None, named=named,
-                             sites=sites is not None, probs=probs)
+                             sites=sites is not None, probs=probs, ranked=ranked_depth if ranked is not None else None)
     bad = np.flatnonzero(res["status"])
     if bad.size:
         import warnings
@@ -196,10 +202,18 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
                                            rec_psm=rec_psm)
         runner = site_tables.runner_up(rec, off, res["best_sig"])
         runner_seqs = ascore.format_batch(batch, runner["sig"], valid=runner["found"].astype(np.int32))
+    if ranked is not None:                       # every sequence of the ranked table in one call
+        rk = res["ranked"]
+        rk_psm = np.repeat(np.arange(len(picked), dtype=np.int64), rk.shape[1])
+        rk_seqs = ascore.format_batch(batch, rk["sig_bits"].ravel(), valid=(rk["kind"].ravel() != ranked_lists.NONE).astype(np.int32),
+                                      rec_psm=rk_psm)
     rows = []
     hit = 0
     for i, psm in enumerate(picked):
         hit = hit + 1 if i and scans[i] == scans[i - 1] else 1
+        if ranked is not None:
+            ranked.extend([scans[i], hit] + ranked_fields(rk[i, r], rk[i, 0], rk_seqs[i * rk.shape[1] + r])
+                          for r in range(int(ranked_lists.lengths(rk[i])[0])))
         if sites is not None:
             sites.extend([scans[i]] + site_fields(rec[r], psm["peptide"], with_seqs[r], without_seqs[r])
                          for r in range(int(off[i]), int(off[i + 1])))
@@ -233,6 +247,23 @@ def prob_fields(site_recs, psm_rec, peptide, residues):
     pos = site_probs.positions_of(peptide, residues)
     text = site_probs.annotate(peptide, pos, site_recs["with_prob"]) if len(pos) == len(site_recs) else ""
     return [text, repr(float(site_probs.best_prob(np.asarray([psm_rec], site_probs.PSM_PROB_DTYPE))[0]))]
+
+
+def ranked_fields(rec, first, sequence):
+    """One ranked record as the fields behind Scan and Hit of the ``--ranked`` table: Rank (1: the reported localisation),
+    LocalizedSequence -- the site assignment in the notation of the main table --, PepScore, DeltaToBest -- how far the
+    PepScore lies behind the reported localisation's (``first``, row 0 of the PSM) --, Tied (1: the PepScore equals the row
+    above's).  A PSM with more site assignments than the stage enumerates has its first row alone."""
+    return [str(int(rec["rank"]) + 1), sequence, repr(float(rec["pep_score"])),
+            str(np.float32(first["pep_score"]) - np.float32(rec["pep_score"])), "1" if int(rec["flags"]) & ranked_lists.TIED_PREV else "0"]
+
+
+def write_ranked_tsv(ranked_rows, path):
+    """The ``--ranked`` table: the rows ``localize(..., ranked=[])`` collected, under ``RANKED_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(RANKED_COLUMNS) + "\n")
+        for row in ranked_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
 
 
 def site_fields(rec, peptide, with_sequence, without_sequence):

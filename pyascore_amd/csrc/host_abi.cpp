@@ -65,6 +65,7 @@ void pya_destroy(pya_handle *h) {
     if (h->named_host) (void)hipHostFree(h->named_host);
     if (h->sites_host) (void)hipHostFree(h->sites_host);
     if (h->probs_host) (void)hipHostFree(h->probs_host);
+    if (h->ranked_host) (void)hipHostFree(h->ranked_host);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
     if (h->run_stream) (void)hipStreamDestroy(h->run_stream);
     if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
@@ -282,6 +283,27 @@ int pya_last_batch_probs(pya_handle *h, int64_t *site_off, pya_site_prob *sites,
     std::memcpy(psms, h->probs_psms(), (size_t)n_psm * sizeof(pya_psm_prob));
     return PYA_OK;
 }
+
+int pya_last_batch_ranked(pya_handle *h, pya_ranked *out, uint64_t n_psm, uint32_t top_k) {
+    if (!h) return PYA_ERR_ARG;
+    if (!h->ranked_valid) return h->fail(PYA_ERR_STATE, -1, "the last batch was scored without PYA_FLAG_RANKED");
+    if (n_psm != h->ranked_n || top_k != h->ranked_batch_k)
+        return h->fail(PYA_ERR_ARG, -1, "the last batch has %llu PSMs with %u rows each, not %llu with %u", (unsigned long long)h->ranked_n,
+                       h->ranked_batch_k, (unsigned long long)n_psm, top_k);
+    if (n_psm == 0) return PYA_OK;
+    if (!out) return h->fail(PYA_ERR_ARG, -1, "NULL record array");
+    std::memcpy(out, h->ranked_host, (size_t)n_psm * top_k * sizeof(pya_ranked));
+    return PYA_OK;
+}
+
+int pya_set_ranked_k(pya_handle *h, uint32_t top_k) {
+    if (!h) return PYA_ERR_ARG;
+    if (top_k < 1u || top_k > PYA_MAX_RANKED) return h->fail(PYA_ERR_ARG, -1, "ranked list length %u is not in 1 .. %d", top_k, PYA_MAX_RANKED);
+    h->ranked_k = top_k;
+    return PYA_OK;
+}
+
+uint32_t pya_get_ranked_k(const pya_handle *h) { return h ? h->ranked_k : 0u; }
 
 int pya_set_site_sig_cap(pya_handle *h, uint32_t sig_cap) {
     if (!h) return PYA_ERR_ARG;

@@ -229,6 +229,39 @@ static int probs_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out
     return PYA_OK;
 }
 
+/* PYA_FLAG_RANKED: the handle's pinned block for the ranked localisations of a batch -- ranked_k rows per PSM, zeroed
+ * (PYA_RANK_NONE until a chunk's copy lands) -- sized before the first chunk; the list length is fixed for the call here */
+static int ranked_host_block(pya_handle *h, const pya_batch *b) {
+    const size_t need = (size_t)b->n_psm * h->ranked_k;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->ranked_cap < need) {
+        if (h->ranked_host) (void)hipHostFree(h->ranked_host);
+        h->ranked_host = nullptr;
+        h->ranked_cap = 0;
+        const size_t n = need + need / 4;
+        HIPCHK(h, hipHostMalloc((void **)&h->ranked_host, n * sizeof(pya_ranked), hipHostMallocDefault));
+        h->ranked_cap = n;
+    }
+    std::memset(h->ranked_host, 0, need * sizeof(pya_ranked));
+    h->ranked_n = b->n_psm;
+    h->ranked_batch_k = h->ranked_k;
+    return PYA_OK;
+}
+
+/* ... the ranked launches of a plan behind its kernels on `st`, and the records on their way into the block at the rows of
+ * PSM `lo` */
+static int ranked_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    const uint32_t K = h->ranked_batch_k;
+    if (n == 0) return PYA_OK;
+    if ((size_t)(lo + n) * K > h->ranked_cap) return h->fail(PYA_ERR_STATE, -1, "ranked records beyond the block sized for them");
+    HIPCHK(h, p->d_ranked.alloc((size_t)n * K));
+    const int rc = pya_plan_ranked(p, d_out, st, K, h->site_sig_cap, p->d_ranked.p);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->ranked_host + (size_t)lo * K, p->d_ranked.p, (size_t)n * K * sizeof(pya_ranked), hipMemcpyDeviceToHost, st));
+    return PYA_OK;
+}
+
 /* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
  * counts, [n_q * n_top] scores -- zeroed */
 static int named_host_block(pya_handle *h, uint64_t n_q) {
@@ -421,6 +454,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if (nq && (rc = named_behind_run(h, p, &d_out, nq, lo, n_q, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_SITES) && (rc = sites_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PROBS) && (rc = probs_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_RANKED) && (rc = ranked_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -467,6 +501,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
     /* (chunks behind the last PSM with records: their offsets stay at the total) */
     h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
     h->probs_valid = (flags & PYA_FLAG_PROBS) != 0;
+    h->ranked_valid = (flags & PYA_FLAG_RANKED) != 0;
     return finish(PYA_OK);
 }
 
@@ -481,6 +516,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->ions_valid = false;
     h->sites_valid = false;
     h->probs_valid = false;
+    h->ranked_valid = false;
     if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
     if (flags & PYA_FLAG_SITES) h->sites_off.assign(b->n_psm + 1, 0);
     if (flags & PYA_FLAG_PROBS) h->probs_off.assign(b->n_psm + 1, 0);
@@ -491,6 +527,9 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
         h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
         h->probs_valid = (flags & PYA_FLAG_PROBS) != 0;
+        h->ranked_valid = (flags & PYA_FLAG_RANKED) != 0;
+        h->ranked_n = 0;
+        h->ranked_batch_k = h->ranked_k;
         return PYA_OK;
     }
     uint32_t types = 0;
@@ -534,8 +573,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_pb = probs_host_block(h, b);
         if (rc_pb) return rc_pb;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES or _PROBS takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    if (flags & PYA_FLAG_RANKED) {
+        const int rc_rk = ranked_host_block(h, b);
+        if (rc_rk) return rc_rk;
+    }
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS or _RANKED takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -678,6 +721,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         HIPCHK(h, hipStreamSynchronize(nullptr));
         h->probs_valid = true;
     }
+    if (flags & PYA_FLAG_RANKED) {
+        if ((rc = ranked_behind_run(h, p, &d_out, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        h->ranked_valid = true;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -700,6 +748,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->ions_valid = false;
     h->sites_valid = false;
     h->probs_valid = false;
+    h->ranked_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
@@ -739,6 +788,15 @@ int pya_debug_last_probs_launch(const pya_handle *h, uint32_t front_ends[2], uin
     for (int i = 0; i < 2; i++) {
         front_ends[i] = h->last_probs_sw[i];
         lds_bytes[i] = h->last_probs_lds[i];
+    }
+    return PYA_OK;
+}
+
+int pya_debug_last_ranked_launch(const pya_handle *h, uint32_t front_ends[2], uint64_t lds_bytes[2]) {
+    if (!h || !front_ends || !lds_bytes) return PYA_ERR_ARG;
+    for (int i = 0; i < 2; i++) {
+        front_ends[i] = h->last_ranked_sw[i];
+        lds_bytes[i] = h->last_ranked_lds[i];
     }
     return PYA_OK;
 }

@@ -135,6 +135,9 @@ size_t pya_probs_lds_bytes(uint32_t l_cap, const PcCaps *caps, uint32_t sw);
 size_t pya_probs_cnt_bytes(const PcCaps *caps);
 int pya_launch_probs(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_site_off, uint64_t n_out,
                      uint32_t sig_cap, void *d_out, void *d_psms, uint32_t l_cap, const PcCaps *caps, uint32_t sw, hipStream_t stream);
+size_t pya_ranked_lds_bytes(uint32_t l_cap, const PcCaps *caps, uint32_t sw);
+int pya_launch_ranked(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_site_off, uint32_t top_k,
+                      uint32_t sig_cap, void *d_out, uint32_t l_cap, const PcCaps *caps, uint32_t sw, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -300,6 +303,8 @@ struct pya_handle {
      * list): the front ends carved (probs.hip: PB_CNT 1 | PB_GEN 2; 0: no launch) and the LDS bytes (pya_debug_last_probs_launch) */
     uint32_t last_probs_sw[2] = {0u, 0u};
     uint64_t last_probs_lds[2] = {0u, 0u};
+    uint32_t last_ranked_sw[2] = {0u, 0u};     /* the same for the last pya_plan_ranked (pya_debug_last_ranked_launch) */
+    uint64_t last_ranked_lds[2] = {0u, 0u};
     uint64_t last_chunks = 0;                  /* plans the last pya_score_batch call was cut into (pya_debug_last_chunks) */
     DevBuf<unsigned char> io_buf;              /* spectra of big pya_score_batch calls (uploaded by a helper thread) */
     DevBuf<unsigned char> io_ring[2];          /* chunked calls: spectra of chunk c in slot c % 2 */
@@ -361,6 +366,14 @@ struct pya_handle {
     bool probs_valid = false;
     pya_site_prob *probs_sites() const { return (pya_site_prob *)probs_host; }
     pya_psm_prob *probs_psms() const { return (pya_psm_prob *)(probs_host + probs_cap * sizeof(pya_site_prob)); }
+    /* PYA_FLAG_RANKED: the ranked localisations of the last pya_score_batch, [ranked_n * ranked_batch_k] pya_ranked in PSM
+     * order (pinned, zeroed: a PSM no plan reaches is PYA_RANK_NONE); ranked_k: the list length of the next batch call
+     * (pya_set_ranked_k) */
+    pya_ranked *ranked_host = nullptr;
+    size_t ranked_cap = 0;                    /* records */
+    uint64_t ranked_n = 0;
+    uint32_t ranked_k = 5, ranked_batch_k = 0;
+    bool ranked_valid = false;
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -711,6 +724,7 @@ struct pya_plan {
     bool prob_lists_made = false;
     DevBuf<pya_site_prob> d_prob_sites;
     DevBuf<pya_psm_prob> d_prob_psms;
+    DevBuf<pya_ranked> d_ranked;         /* pya_plan_ranked: the records of a pya_score_batch plan */
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -848,6 +862,9 @@ static_assert(sizeof(pya_site) == 32 && offsetof(pya_site, without_sig) == 8 && 
 static_assert(sizeof(pya_site_prob) == 16 && offsetof(pya_site_prob, without_prob) == 8 && sizeof(pya_psm_prob) == 16 &&
                   offsetof(pya_psm_prob, n_summed) == 8 && offsetof(pya_psm_prob, kind) == 12,
               "pya_site_prob and pya_psm_prob are one 16-byte store of probs.hip each");
+static_assert(sizeof(pya_ranked) == 16 && offsetof(pya_ranked, pep_score) == 8 && offsetof(pya_ranked, rank) == 12 &&
+                  offsetof(pya_ranked, kind) == 14 && offsetof(pya_ranked, flags) == 15,
+              "pya_ranked is one 16-byte store of ranked.hip");
 /* pya_score_batch_named's queries and outputs (host arrays of the caller), nullptr for the other batch entry points */
 struct NamedReq {
     const int64_t *q_off;

@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_SITES | PYA_FLAG_PROBS)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -664,6 +664,26 @@ static void prob_lists(pya_plan *p) {
     p->prob_lists_made = true;
 }
 
+/* ... and what the two launches of a stage that scores with these front ends carve (slice_score.hip.h: PB_CNT 1, PB_GEN 2):
+ * caps[li], sw[li] for the PSMs inside the fast limits (0) and the general list (1) */
+static void prob_front_ends(pya_plan *p, PcCaps caps[2], uint32_t sw[2]) {
+    pya_handle *h = p->h;
+    prob_lists(p);
+    const DevConfig &c = h->cfg;
+    const bool plain = c.n_nl == 0 && c.n_types == 2 && c.n_fwd == 1 && c.n_top == PYA_NTOP && h->mz_error <= 0.49f && !h->kn.no_prob_cnt;
+    for (int li = 0; li < 2; li++) {
+        const pya_plan::ProbList &l = p->prob_lists[li];
+        caps[li] = PcCaps{};
+        sw[li] = 2u;
+        if (!plain || l.n_fit == 0) continue;
+        const PcCaps k = {l.peak_max, l.pos_max, l.kc, l.k_max, l.ns_max};
+        caps[li] = k;
+        /* the tables alone only for the list of the PSMs inside the fast limits, and only when every PSM of it that will be
+         * scored passed the kernel's own test on the host: whatever else is in a list needs the general front end */
+        sw[li] = li == 0 && l.n_fit == l.n_scored ? 1u : 3u;
+    }
+}
+
 int pya_plan_probs(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t sig_cap, pya_site_prob *d_sites, pya_psm_prob *d_psms) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
@@ -676,20 +696,9 @@ int pya_plan_probs(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (!p->ev_sites) HIPCHK(h, hipEventCreateWithFlags(&p->ev_sites, hipEventDisableTiming));
-    prob_lists(p);
-    const DevConfig &c = h->cfg;
-    const bool plain = c.n_nl == 0 && c.n_types == 2 && c.n_fwd == 1 && c.n_top == PYA_NTOP && h->mz_error <= 0.49f && !h->kn.no_prob_cnt;
     PcCaps caps[2] = {};
-    uint32_t sw[2] = {2u, 2u};                                 /* (probs.hip: PB_CNT 1, PB_GEN 2) */
-    for (int li = 0; li < 2; li++) {
-        const pya_plan::ProbList &l = p->prob_lists[li];
-        if (!plain || l.n_fit == 0) continue;
-        const PcCaps k = {l.peak_max, l.pos_max, l.kc, l.k_max, l.ns_max};
-        caps[li] = k;
-        /* the tables alone only for the list of the PSMs inside the fast limits, and only when every PSM of it that will be
-         * scored passed the kernel's own test on the host: whatever else is in a list needs the general front end */
-        sw[li] = li == 0 && l.n_fit == l.n_scored ? 1u : 3u;
-    }
+    uint32_t sw[2] = {2u, 2u};
+    prob_front_ends(p, caps, sw);
     /* (stage_behind_run sizes the general front end's LDS: l_cap alone counts, the stage keeps no fragment list) */
     struct Room {
         static size_t general(uint32_t l_cap, uint32_t) {
@@ -725,6 +734,61 @@ int pya_plan_probs(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t
         const bool launched = li == 0 ? p->evid_n_fast != 0 : !p->gen_ids.empty();
         h->last_probs_sw[li] = launched ? sw[li] : 0u;
         h->last_probs_lds[li] = launched ? pya_probs_lds_bytes(li == 0 ? p->evid_l_cap : p->gen_l_cap, &caps[li], sw[li]) : 0u;
+    }
+    return PYA_OK;
+}
+
+/* The ranked stage (csrc/ranked.hip): the probability stage's front ends, offsets (a PSM's modifiable residues are the
+ * difference of two), wait and two launches; the list it keeps lives in registers, so its LDS is the front ends' alone. */
+int pya_plan_ranked(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t top_k, uint32_t sig_cap, pya_ranked *d_out) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (top_k < 1u || top_k > PYA_MAX_RANKED)
+        return h->fail(PYA_ERR_ARG, -1, "pya_plan_ranked: top_k %u is not in 1 .. %d", top_k, PYA_MAX_RANKED);
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_ranked: the plan has not been run");
+    if (!d_out || !r->best_score || !r->best_sig || !r->n_sig) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_ranked");
+    site_offsets(p);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->ev_sites) HIPCHK(h, hipEventCreateWithFlags(&p->ev_sites, hipEventDisableTiming));
+    PcCaps caps[2] = {};
+    uint32_t sw[2] = {2u, 2u};
+    prob_front_ends(p, caps, sw);
+    struct Room {
+        static size_t general(uint32_t l_cap, uint32_t) {
+            const PcCaps none = {};
+            return pya_ranked_lds_bytes(l_cap, &none, 2u);
+        }
+    };
+    const int rc = stage_behind_run(p, st, "pya_plan_ranked", "ranked", Room::general);
+    if (rc) return rc;
+    if (pya_ranked_lds_bytes(p->evid_l_cap, &caps[0], sw[0]) > kMaxLds) sw[0] = 2u;
+    if (pya_ranked_lds_bytes(p->gen_l_cap, &caps[1], sw[1]) > kMaxLds) sw[1] = 2u;
+    if (!p->site_off_sent) {
+        /* (from the plan's own vector, which outlives the copy; a later call on another stream waits for it below) */
+        HIPCHK(h, p->d_site_off.alloc(p->n_psm + 1));
+        HIPCHK(h, hipMemcpyAsync(p->d_site_off.p, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipEventRecord(p->ev_sites, st));
+        p->site_off_sent = true;
+    } else {
+        HIPCHK(h, hipStreamWaitEvent(st, p->ev_sites, 0));
+    }
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.best_score = r->best_score;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    int e = pya_launch_ranked(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, p->d_site_off.p, top_k, sig_cap, d_out,
+                              p->evid_l_cap, &caps[0], sw[0], st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_ranked(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), p->d_site_off.p, top_k, sig_cap, d_out, p->gen_l_cap, &caps[1],
+                              sw[1], st);
+    if (e) return h->hip_fail((hipError_t)e, "ranked launch");
+    for (int li = 0; li < 2; li++) {                            /* (pya_debug_last_ranked_launch) */
+        const bool launched = li == 0 ? p->evid_n_fast != 0 : !p->gen_ids.empty();
+        h->last_ranked_sw[li] = launched ? sw[li] : 0u;
+        h->last_ranked_lds[li] = launched ? pya_ranked_lds_bytes(li == 0 ? p->evid_l_cap : p->gen_l_cap, &caps[li], sw[li]) : 0u;
     }
     return PYA_OK;
 }

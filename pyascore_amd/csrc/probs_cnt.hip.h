@@ -1,5 +1,5 @@
 /* probs_cnt.hip.h -- the count-node front end of a stage that needs the PepScore of EVERY site assignment of a PSM behind
- * a run (probs.hip today; sites.hip may adopt it): under the plain settings of score_cnt.hip (no neutral loss, fragment
+ * a run (probs.hip and ranked.hip today, through slice_score.hip.h; sites.hip may adopt it): under the plain settings of score_cnt.hip (no neutral loss, fragment
  * charge 1, one ion type per direction, both directions, mz_error <= 0.49, n_top = PYA_NTOP) the tables of walk_core.hip.h
  * are built ONCE per PSM in LDS from the retained table the run left, and a site assignment then costs k reads of the
  * (t, site) table and the ten score reads instead of a binary search per fragment.

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import _lib
 from .ascore import PyAscore, _as_ptr
+from .ranked import check_k as check_ranked_k
 
 
 class DevicePlan:
@@ -26,9 +27,10 @@ class DevicePlan:
     (``pya_plan_ions_count``, ``pya_plan_ions``).  ``named()`` / ``named=True``: the same for the records of localisations
     the caller names (``pya_plan_named``).  ``sites()`` / ``sites=True``: the same for the site tables
     (``pya_plan_site_offsets``, ``pya_plan_sites``).  ``probs()`` / ``probs=True``: the same for the site probabilities
-    (``pya_plan_probs``)."""
+    (``pya_plan_probs``).  ``ranked()`` / ``ranked=True``: the same for the ranked localisations (``pya_plan_ranked``)."""
 
-    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False):
+    def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
+                 ranked=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -58,7 +60,7 @@ class DevicePlan:
         self._plan = C.c_void_p()
         flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
             (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
-            (_lib.PYA_FLAG_PROBS if probs else 0)
+            (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -238,6 +240,27 @@ class DevicePlan:
             self.scorer._raise(rc)
         return off, site_probs, psm_probs
 
+    def ranked(self, top_k=5, sig_cap=0, out=None):
+        """The ranked localisations of the last ``run()``: a ``torch.uint8`` device tensor ``[n_psm, top_k, 16]`` (one
+        ``pya_ranked`` per row; ``ranked_records`` turns a host copy into the structured array ``[n_psm, top_k]``) -- row 0 of
+        a PSM its reported localisation, then its other site assignments by PepScore descending, equal scores by ascending
+        sig bits.  One launch family of the library behind the run on torch's current stream; nothing waits on the host.
+        ``top_k``: 1 .. 64; ``sig_cap`` as for ``sites()``; ``out``: the tensor of an earlier call with the same ``top_k``, to
+        be written again.  Valid for the results of the last run; may be called again, with another ``top_k`` too."""
+        torch = self._torch
+        top_k = check_ranked_k(top_k)
+        shape = (self.n_psm, top_k, 16)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous uint8 device tensor of shape %r" % (shape,))
+        rc = self._lib.pya_plan_ranked(self._plan, C.byref(self._res), stream, top_k, int(sig_cap), out.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return out
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -287,6 +310,7 @@ ION_DTYPE = np.dtype(_lib.ION_DTYPE)
 NAMED_DTYPE = np.dtype(_lib.NAMED_DTYPE)
 SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)
 PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)
+RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)
 
 
 def evidence_rows(raw):
@@ -336,6 +360,15 @@ def psm_prob_records(raw):
     if a.ndim != 2 or a.shape[1] != PSM_PROB_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, %d)" % PSM_PROB_DTYPE.itemsize)
     return a.view(PSM_PROB_DTYPE).reshape(a.shape[0])
+
+
+def ranked_records(raw):
+    """A host copy of the records of ``DevicePlan.ranked()`` (``.cpu().numpy()``, uint8 ``[n, K, 16]``) as the structured
+    array ``PyAscore.score_batch(..., ranked=K)`` returns in ``ranked``, shape ``[n, K]``; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 3 or a.shape[2] != RANKED_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, K, %d)" % RANKED_DTYPE.itemsize)
+    return a.view(RANKED_DTYPE).reshape(a.shape[0], a.shape[1])
 
 
 def named_records(raw):
