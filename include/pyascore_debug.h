@@ -55,6 +55,10 @@ int pya_debug_last_probs_launch(const pya_handle *h, uint32_t front_ends[2], uin
  * counterpart. */
 int pya_debug_last_ranked_launch(const pya_handle *h, uint32_t front_ends[2], uint64_t lds_bytes[2]);
 
+/* The last pya_plan_rollup call (a batch call with PYA_FLAG_ROLLUP makes one per chunk): the blocks of its two launches,
+ * 0 when the plan had no residue records; *n_records = the records it walked.  No reference counterpart. */
+int pya_debug_last_rollup_launch(const pya_handle *h, uint32_t grid[2], uint64_t *n_records);
+
 /* The signature list of PSM `psm` of the handle's retained batch (the last PYA_FLAG_KEEP call): the sig bits of its site
  * assignments in the order every kernel scores them in and the probability stage sums them in (pya_get_pep_scores* returns
  * the reference's sorted order instead).  *n = their number; sig_bits may be NULL with cap 0 to ask.  No reference

@@ -100,6 +100,9 @@ extern "C" {
 #define PYA_FLAG_RANKED 256u /* pya_score_batch* / pya_score_batch_named: the ranked localisations of every PSM as */
                              /* well (pya_last_batch_ranked, pya_set_ranked_k); pya_plan_create*: as               */
                              /* PYA_FLAG_EVIDENCE (pya_plan_ranked)                                                */
+#define PYA_FLAG_ROLLUP 512u /* pya_score_batch* / pya_score_batch_named: the site roll-up of the batch as well, into the */
+                             /* slots lent by pya_set_rollup (pya_last_batch_rollup); the library runs the probability    */
+                             /* stage for itself; pya_plan_create*: as PYA_FLAG_EVIDENCE (pya_plan_rollup)                */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -284,6 +287,43 @@ typedef struct pya_psm_prob {      /* 16 bytes, one store */
     uint8_t kind;                  /* PYA_SITE_NONE / _SCORED / _OVER                                          */
     uint8_t pad[3];                /* 0                                                                        */
 } pya_psm_prob;
+
+/* Site roll-up.  Everything above is a view of ONE PSM; this is the first reduction ACROSS PSMs: the probability records of
+ * many PSMs collapsed onto a dense table of caller-defined slots -- "one site" in whatever key the caller uses (peptide +
+ * position, protein + position, ...) --, the site-level table of a phosphoproteomics report (MaxQuant's Phospho (STY)Sites,
+ * the "class I sites" of a paper).  The caller names the slot of every residue record (slot[site_off[n_psm]], int32, in the
+ * records' order; negative: the record is left out) and the number a PSM is known by (psm_id); the stage accumulates into
+ * table[n_slots].  A record CONTRIBUTES when its PSM's pya_psm_prob.kind is PYA_SITE_SCORED and its slot lies in
+ * [0, n_slots); PYA_SITE_NONE and PYA_SITE_OVER PSMs, PSMs that were set aside (they have no records) and negative slots
+ * contribute nothing, a slot at or above n_slots writes nothing and is reported by pya_plan_check.  Two records of one PSM may
+ * name one slot: both contribute.  Per slot, over its contributing records:
+ *   best_prob    the largest with_prob, compared as the uint64 bit pattern (non-negative doubles order like their bits);
+ *   best_psm     the smallest psm_id among the records whose with_prob has exactly those bits;
+ *   n_psm        their number;  n_confident  ... of them with with_prob >= threshold (compared as doubles);
+ *   n_in_best    ... of them whose PSM's best_sig modifies the residue (record r of a PSM is its r-th modifiable residue,
+ *                bit r of best_sig);
+ *   best_ascore  the largest Ascore of those: ascores[psm * max_k + popcount(best_sig & ((1 << r) - 1))], the column of the
+ *                residue among the modified ones.  Largest under the total order of the bit patterns, -NaN < -inf < ... < -0
+ *                < +0 < ... < +inf < +NaN: the float order wherever floats have one (an Ascore may be negative, and is
+ *                +inf for a localisation without a competitor).
+ * THE TABLE IS A FUNCTION OF THE MULTISET OF CONTRIBUTING RECORDS (slot, with_prob, psm_id, in-best, Ascore) AND OF NOTHING
+ * ELSE: every field is an integer count, a max over bit patterns or a min over ids.  It does not depend on the order of the
+ * atomics, on the route that scored a PSM, on shared or typed input, on chunk cuts, or on whether the PSMs came in one call
+ * or were accumulated over several -- the table a caller holds between calls IS this record, and rolling more PSMs into it
+ * gives the bytes of one call over all of them.  For the same reason two tables over the same slots can be merged on the
+ * host: max / min / sum per field (best_psm: of the side with the larger best_prob, the smaller id on equal bits; best_ascore
+ * only among sides with n_in_best != 0).  The empty slot is NOT all-zero bytes: pya_rollup_clear writes it.  Counts are
+ * 32-bit and are not checked for overflow. */
+#define PYA_ROLLUP_NO_PSM 0xffffffffu
+typedef struct pya_site_rollup {   /* 32 bytes; records compare as raw bytes */
+    double best_prob;              /* max with_prob over the contributing records; 0 when none                 */
+    uint32_t best_psm;             /* psm_id of a PSM attaining it: the smallest such id; PYA_ROLLUP_NO_PSM none */
+    uint32_t n_psm;                /* contributing records (scored PSMs that cover the slot)                   */
+    uint32_t n_confident;          /* ... of them with with_prob >= threshold                                  */
+    uint32_t n_in_best;            /* ... of them whose best_sig modifies the residue                          */
+    float best_ascore;             /* max Ascore over those n_in_best records; 0 when n_in_best == 0           */
+    uint32_t reserved;             /* 0                                                                        */
+} pya_site_rollup;
 
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
@@ -511,6 +551,26 @@ int pya_last_batch_ranked(pya_handle *h, pya_ranked *out, uint64_t n_psm, uint32
  * its own): 1 .. PYA_MAX_RANKED, anything else is PYA_ERR_ARG and changes nothing.  The default is 5. */
 int pya_set_ranked_k(pya_handle *h, uint32_t top_k);
 uint32_t pya_get_ranked_k(const pya_handle *h);
+/* Lends the library what the NEXT pya_score_batch / _shared / _typed / _named call with PYA_FLAG_ROLLUP rolls its PSMs into
+ * (pya_site_rollup above): slot[n_records], host memory that must stay valid until that call returns -- one entry per
+ * residue record of the batch in the records' order, n_records = the batch's site_off[n_psm] (what pya_last_batch_probs or
+ * pya_plan_site_offsets report: the modifiable residues of every PSM that is not set aside, summed); n_slots, the size of
+ * the table; threshold, the "confident" cut of n_confident (e.g. 0.75); psm_id[n_psm] or NULL: PSM i of the batch is known as
+ * i.  The batch call computes the probability records for itself (pya_last_batch_probs still answers only with
+ * PYA_FLAG_PROBS; the cap is pya_set_site_sig_cap's), uploads a chunk's slice of slot and psm_id with the chunk and runs the
+ * stage behind every chunk's probability stage into one device table that lives for the call.  The loan ends with the first
+ * batch call with the flag that gets as far as its PSMs, whatever that call returns.  A batch whose records are not n_records
+ * (checked chunk by chunk BEFORE anything is read past the array, and at the end), or a flag without a loan: PYA_ERR_ARG with a
+ * message; a slot at or above n_slots: PYA_ERR_LIMIT.
+ * NULL slot with n_records != 0, or n_slots above 2^31 - 1: PYA_ERR_ARG. */
+int pya_set_rollup(pya_handle *h, const int32_t *slot, uint64_t n_records, uint64_t n_slots, double threshold, const uint32_t *psm_id);
+/* The table of the last batch call on this handle that was given PYA_FLAG_ROLLUP: out[n_slots], n_slots as lent
+ * (anything else: PYA_ERR_ARG, as is a NULL array for a table that has slots).  PYA_ERR_STATE when the last batch was scored
+ * without the flag. */
+int pya_last_batch_rollup(pya_handle *h, pya_site_rollup *out, uint64_t n_slots);
+/* Puts a DEVICE table of n_slots records into the empty state (best_psm = PYA_ROLLUP_NO_PSM, everything else 0), on
+ * hip_stream, stream-ordered, no host synchronisation inside. */
+int pya_rollup_clear(pya_handle *h, pya_site_rollup *d_table, uint64_t n_slots, void *hip_stream);
 
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
@@ -585,6 +645,19 @@ int pya_plan_probs(pya_plan *plan, const pya_results *d_res, void *hip_stream, u
  * best_score, best_sig and n_sig of d_res.  A plan of a handful of PSMs is created with PYA_FLAG_RANKED (or another stage
  * flag): the one-launch kernel leaves no retained tables. */
 int pya_plan_ranked(pya_plan *plan, const pya_results *d_res, void *hip_stream, uint32_t top_k, uint32_t sig_cap, pya_ranked *d_out);
+/* Rolls the probability records of this plan's PSMs into d_table[n_slots] (pya_site_rollup above; device memory, brought to
+ * the empty state once by pya_rollup_clear): the stage ACCUMULATES, so the same table may take the records of other plans,
+ * other runs and other calls.  d_site_probs / d_psm_probs: probability records laid out at the plan's site offsets
+ * (pya_plan_site_offsets) -- normally what pya_plan_probs wrote for the same run, on the same stream or one that waits for
+ * it; d_slot[site_off[n_psm]]; d_psm_id[n_psm] device memory, or NULL: PSM i is known as psm_base + i.  It reads best_sig and
+ * ascores (row stride max_k, which must not be below the plan's largest n_of_mod) of d_res.  Two launches of csrc/rollup.hip,
+ * stream-ordered, no host synchronisation inside, waits for the run, valid until the plan is run again, may be called
+ * again with other slots or another table.  No write ever lies at or past d_table + n_slots: a record whose slot is at or
+ * above n_slots writes nothing, and pya_plan_check reports it (PYA_ERR_LIMIT) until the call is repeated or the plan is run
+ * again.  n_slots above 2^31 - 1: PYA_ERR_ARG. */
+int pya_plan_rollup(pya_plan *plan, const pya_results *d_res, void *hip_stream, const pya_site_prob *d_site_probs,
+                    const pya_psm_prob *d_psm_probs, const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id,
+                    uint32_t psm_base, pya_site_rollup *d_table);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

@@ -8,7 +8,8 @@ Ascore), ``--ions FILE`` (a second table: which ions, one line each) and ``--rep
 engine's own site assignment, scored against the winner) and ``--sites FILE`` (a table with a line per candidate residue, and
 the runner-up localisation in the main one) and ``--probs`` (two more columns: the localisation probability of every
 candidate residue and the posterior of the reported localisation) and ``--ranked FILE`` with ``--ranked_depth K`` (a table
-with a line per ranked site assignment: the K best localisations of every PSM, in order) are the additions."""
+with a line per ranked site assignment: the K best localisations of every PSM, in order) and ``--site_table FILE`` with
+``--site_table_threshold P`` (a site-level table over all PSMs, a line per peptide and position) are the additions."""
 import argparse
 import re
 import sys
@@ -72,6 +73,12 @@ def build_parser():
                         "LocalizedSequence, PepScore, DeltaToBest, Tied); the main table does not change")
     p.add_argument("--ranked_depth", type=int, default=5, metavar="K",
                    help="how many site assignments per PSM --ranked lists, 1 .. 64 (default 5)")
+    p.add_argument("--site_table", type=str, default=None, metavar="FILE",
+                   help="write the site-level table to FILE: one line per (unmodified peptide, position) over all scored PSMs "
+                        "(Peptide, Position, Residue, BestProb, BestScan, PSMs, Confident, InBest, BestAscore), rolled up on the "
+                        "device from the localisation probabilities; the main table does not change")
+    p.add_argument("--site_table_threshold", type=float, default=0.75, metavar="P",
+                   help="the localisation probability from which a PSM counts as Confident in --site_table (default 0.75)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -133,6 +140,7 @@ def run(args, log=print):
     ion_rows = [] if args.ions else None
     site_rows = [] if args.sites else None
     ranked_rows = [] if args.ranked else None
+    site_table_rows = [] if args.site_table else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -140,13 +148,16 @@ def run(args, log=print):
                               args.max_fragment_charge, args.mod_correction_tol, args.zero_based,
                               match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
                               evidence=args.evidence, ions=ion_rows, reported=args.reported, sites=site_rows,
-                              probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth)
+                              probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth, site_table=site_table_rows,
+                              site_table_threshold=args.site_table_threshold)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
         batch_cli.write_sites_tsv(site_rows, args.sites)
     if ranked_rows is not None:
         batch_cli.write_ranked_tsv(ranked_rows, args.ranked)
+    if site_table_rows is not None:
+        batch_cli.write_site_table_tsv(site_table_rows, args.site_table)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

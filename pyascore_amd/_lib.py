@@ -16,6 +16,8 @@ PYA_FLAG_NAMED = 32
 PYA_FLAG_SITES = 64
 PYA_FLAG_PROBS = 128
 PYA_FLAG_RANKED = 256
+PYA_FLAG_ROLLUP = 512
+PYA_ROLLUP_NO_PSM = 0xFFFFFFFF
 PYA_MAX_RANKED = 64
 PYA_RANK_NONE, PYA_RANK_SCORED, PYA_RANK_OVER = 0, 1, 2
 PYA_RANK_TIED_PREV, PYA_RANK_IN_BEST_TIE = 1, 2
@@ -126,6 +128,18 @@ class Ranked(C.Structure):
 assert C.sizeof(Ranked) == 16, "pya_ranked is a 16-byte record"
 RANKED_DTYPE = [("sig_bits", "<u8"), ("pep_score", "<f4"), ("rank", "<u2"), ("kind", "u1"), ("flags", "u1")]
 
+
+class SiteRollup(C.Structure):
+    """pya_site_rollup: one slot of a site roll-up -- the best localisation probability any PSM gives a site, who gives it,
+    how many PSMs cover it, how many confidently, how many report it, and the best Ascore of those"""
+    _fields_ = [("best_prob", C.c_double), ("best_psm", C.c_uint32), ("n_psm", C.c_uint32), ("n_confident", C.c_uint32),
+                ("n_in_best", C.c_uint32), ("best_ascore", C.c_float), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(SiteRollup) == 32, "pya_site_rollup is a 32-byte record"
+ROLLUP_DTYPE = [("best_prob", "<f8"), ("best_psm", "<u4"), ("n_psm", "<u4"), ("n_confident", "<u4"), ("n_in_best", "<u4"),
+                ("best_ascore", "<f4"), ("reserved", "<u4")]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -149,6 +163,7 @@ SYMBOLS = {
     "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
     "pya_debug_last_probs_launch": (C.c_int, [_vp, _vp, _vp]),        # (test-only)
     "pya_debug_last_ranked_launch": (C.c_int, [_vp, _vp, _vp]),       # (test-only)
+    "pya_debug_last_rollup_launch": (C.c_int, [_vp, _vp, _vp]),       # (test-only)
     "pya_debug_signature_list": (C.c_int, [_vp, C.c_uint64, _vp, C.c_uint64, _vp]),   # (test-only)
     "pya_debug_plan_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
     "pya_debug_retained_table": (C.c_int, [_vp, C.c_uint64, _vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),  # (test-only)
@@ -183,6 +198,10 @@ SYMBOLS = {
     "pya_set_ranked_k": (C.c_int, [_vp, C.c_uint32]),
     "pya_get_ranked_k": (C.c_uint32, [_vp]),
     "pya_plan_ranked": (C.c_int, [_vp, C.POINTER(Results), _vp, C.c_uint32, C.c_uint32, _vp]),
+    "pya_set_rollup": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_double, _vp]),
+    "pya_last_batch_rollup": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "pya_rollup_clear": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "pya_plan_rollup": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_uint64, C.c_double, _vp, C.c_uint32, _vp]),
     "pya_plan_create": (C.c_int, [_vp, C.POINTER(Batch), C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_create_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_run": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Results)]),

@@ -76,13 +76,43 @@ PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)      # pya_psm_prob, 16 bytes
 assert SITE_PROB_DTYPE.itemsize == 16 and PSM_PROB_DTYPE.itemsize == 16
 RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)          # pya_ranked, 16 bytes
 assert RANKED_DTYPE.itemsize == 16
+ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)          # pya_site_rollup, 32 bytes
+assert ROLLUP_DTYPE.itemsize == 32
 assert EVIDENCE_DTYPE.itemsize == 16
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
 assert ION_DTYPE.itemsize == 16
 from .named import NAMED_DTYPE, query_csr, sig_bits_batch, sig_bits_of, take_queries  # noqa: E402,F401
 from .ranked import check_k as check_ranked_k  # noqa: E402
 _NO_U32 = np.zeros(0, np.uint32)
+
 _NO_F32 = np.zeros(0, np.float32)
+
+
+def _rollup_request(rollup, n_psm):
+    """``score_batch(rollup=...)`` as contiguous arrays: dict(slot int32, n_slots, threshold, psm_id uint32 | None,
+    site_off int64 | None)"""
+    unknown = set(rollup) - {"slot", "n_slots", "threshold", "psm_id", "site_off"}
+    if unknown or "slot" not in rollup or "n_slots" not in rollup:
+        raise ValueError("rollup takes slot, n_slots and optionally threshold, psm_id and site_off%s"
+                         % ("; not " + ", ".join(sorted(unknown)) if unknown else ""))
+    slot = np.asarray(rollup["slot"])
+    if slot.ndim != 1 or (slot.size and slot.dtype.kind not in "iu"):
+        raise ValueError("rollup: slot is one integer per residue record")
+    if slot.size and (int(slot.max()) > 0x7FFFFFFF or int(slot.min()) < -0x80000000):
+        raise ValueError("rollup: slot does not fit int32")
+    n_slots = int(rollup["n_slots"])
+    if not 0 <= n_slots <= 0x7FFFFFFF:
+        raise ValueError("rollup: n_slots must be in 0 .. 2^31 - 1")
+    psm_id = rollup.get("psm_id")
+    if psm_id is not None:
+        psm_id = np.ascontiguousarray(psm_id, np.uint32)
+        if psm_id.shape != (n_psm,):
+            raise ValueError("rollup: psm_id has one entry per PSM")
+    site_off = rollup.get("site_off")
+    if site_off is not None:
+        site_off = np.ascontiguousarray(site_off, np.int64)
+    return dict(slot=np.ascontiguousarray(slot, np.int32), n_slots=n_slots, threshold=float(rollup.get("threshold", 0.75)),
+                psm_id=psm_id, site_off=site_off)
 
 
 class _Last(dict):
@@ -316,7 +346,7 @@ class PyAscore:
             self._batch_n = 1
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
-                    site_sig_cap=None, probs=False, ranked=None):
+                    site_sig_cap=None, probs=False, ranked=None, rollup=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -365,6 +395,13 @@ class PyAscore:
         by ascending ``sig_bits``; rows at and beyond ``n_sig`` and the rows of a PSM that was not scored are zero
         (``pyascore_amd.ranked`` has ``lengths``, ``within`` and ``best_tie_size``).  ``site_sig_cap`` applies: a PSM with
         more site assignments has row 0 alone, of kind ``PYA_RANK_OVER``.
+        ``rollup=dict(slot=..., n_slots=..., threshold=0.75)`` adds ``rollup`` (``ROLLUP_DTYPE``, the 32-byte
+        ``pya_site_rollup``, shape ``[n_slots]``): the residue records of the whole batch collapsed on the device onto the
+        caller's slots -- ``slot`` has one int32 per residue record in the records' order (``site_off`` of ``probs=True``;
+        negative: left out), see ``pyascore_amd.rollup`` for the slot builders and the table.  ``best_psm`` is in the caller's
+        PSM numbering, or in ``psm_id`` (uint32 per PSM) when the dict has it.  ``site_off`` in the dict (the record offsets
+        per PSM, ``site_offsets(batch)``) spares a shared batch that is out of spectrum order the pre-pass that finds them.
+        ``site_sig_cap`` applies: a PSM over it contributes nothing.
 
         Every other result is what it is without the option.
 
@@ -382,27 +419,43 @@ class PyAscore:
         of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
         float64 intensities."""
         ranked_k = None if ranked is None or ranked is False else check_ranked_k(ranked)
+        roll = None if rollup is None else _rollup_request(rollup, int(batch["n_psm"]))
         if batch.get("spec_of") is not None:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
-                                        named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked)
+                                        named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
                     q_off, q_bits = query_csr(named, int(batch["n_psm"]))
                     moved = take_queries(q_off, q_bits, perm)
+                roll_moved = None
+                if roll is not None:         # the slots travel with their PSMs, the ids say who they were
+                    r_off = roll["site_off"]
+                    if r_off is None:
+                        r_off = self.site_offsets(batch, skip_invalid)
+                    if r_off.size != perm.size + 1 or int(r_off[-1]) != roll["slot"].size:
+                        raise ValueError("rollup: %d slots do not match the residue records of the batch; pass their offsets "
+                                         "per PSM as site_off" % roll["slot"].size)
+                    n_rec = np.diff(r_off)[perm]
+                    new_off = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
+                    take = np.repeat(r_off[:-1][perm] - new_off[:-1], n_rec) + np.arange(int(n_rec.sum()))
+                    ids = perm.astype(np.uint32) if roll["psm_id"] is None else roll["psm_id"][perm]
+                    roll_moved = dict(slot=roll["slot"][take], n_slots=roll["n_slots"], threshold=roll["threshold"], psm_id=ids,
+                                      site_off=new_off)
                 try:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
-                                           site_sig_cap=site_sig_cap, probs=probs, ranked=ranked)
+                                           site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
                 site_csr = (res["site_off"], res.pop("sites")) if sites else None
                 prob_csr = (res["site_off"], res.pop("site_probs")) if probs else None
                 res.pop("site_off", None)
+                table = res.pop("rollup", None)         # (per slot, not per PSM)
                 per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
                 if moved is not None:
@@ -425,6 +478,8 @@ class PyAscore:
                     res["site_off"] = np.concatenate([[0], np.cumsum(n_rec)]).astype(np.int64)
                     take = np.repeat(prob_csr[0][:-1][inv] - res["site_off"][:-1], n_rec) + np.arange(int(n_rec.sum()))
                     res["site_probs"] = prob_csr[1][take]
+                if table is not None:
+                    res["rollup"] = table
                 if res.get("status_message"):
                     res["status_message"] = _renumber_psm(res["status_message"], perm)
                 return res
@@ -477,6 +532,11 @@ class PyAscore:
                 out["site_off"], out["site_probs"], out["psm_probs"] = np.zeros(1, np.int64), np.zeros(0, SITE_PROB_DTYPE), np.zeros(0, PSM_PROB_DTYPE)
             if ranked_k:
                 out["ranked"] = np.zeros((0, ranked_k), RANKED_DTYPE)
+            if roll is not None:
+                if roll["slot"].size:
+                    raise ValueError("rollup: %d slots for a batch without residue records" % roll["slot"].size)
+                out["rollup"] = np.zeros(roll["n_slots"], ROLLUP_DTYPE)
+                out["rollup"]["best_psm"] = _lib.PYA_ROLLUP_NO_PSM
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -500,17 +560,22 @@ class PyAscore:
                 lazy_keep = False            # malformed offsets: the library's own validation reports them
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
             (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
-            (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0)
+            (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0) | \
+            (_lib.PYA_FLAG_ROLLUP if roll is not None else 0)
         # for this call; the handle's own settings come back
         cap_before = k_before = None
-        if (sites or probs or ranked_k) and site_sig_cap is not None:
+        if (sites or probs or ranked_k or roll is not None) and site_sig_cap is not None:
             cap_before = int(self._lib.pya_get_site_sig_cap(self._h))
             self._lib.pya_set_site_sig_cap(self._h, int(site_sig_cap))
         if ranked_k:
             k_before = int(self._lib.pya_get_ranked_k(self._h))
             self._lib.pya_set_ranked_k(self._h, ranked_k)
         try:
-            rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
+            # (the library borrows the arrays of `roll` for the call: they live until it returns)
+            rc = 0 if roll is None else self._lib.pya_set_rollup(self._h, _as_ptr(roll["slot"]), roll["slot"].size, roll["n_slots"],
+                                                                 roll["threshold"], _as_ptr(roll["psm_id"]))
+            if not rc:
+                rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         finally:
             if cap_before is not None:
                 self._lib.pya_set_site_sig_cap(self._h, cap_before)
@@ -551,7 +616,45 @@ class PyAscore:
             rc = self._lib.pya_last_batch_ranked(self._h, _as_ptr(out["ranked"]), n, ranked_k)
             if rc:
                 self._raise(rc)
+        if roll is not None:
+            out["rollup"] = np.zeros(roll["n_slots"], ROLLUP_DTYPE)
+            rc = self._lib.pya_last_batch_rollup(self._h, _as_ptr(out["rollup"]), roll["n_slots"])
+            if rc:
+                self._raise(rc)
         return out
+
+    def site_offsets(self, batch, skip_invalid=False):
+        """``site_off`` (int64 ``[n_psm + 1]``) of a batch BEFORE it is scored: where the residue records of every PSM will
+        lie -- what ``rollup=`` needs one slot per entry of.  From the host pre-pass of a plan that is never run
+        (``pya_plan_create``, ``pya_plan_site_offsets``): no kernel, and with ``skip_invalid`` the PSMs the library will set
+        aside have no records here either."""
+        n = int(batch["n_psm"])
+        if n == 0:
+            return np.zeros(1, np.int64)
+        arrs = [np.ascontiguousarray(batch[k], t) for k, t in (("peak_off", np.int64), ("pep", np.uint8), ("pep_off", np.int64),
+                                                               ("n_of_mod", np.int32), ("max_charge", np.int32), ("aux_pos", np.uint32),
+                                                               ("aux_mass", np.float32), ("aux_off", np.int64))]
+        b = _lib.Batch(n, *[_as_ptr(a) for a in arrs])
+        flags = _lib.PYA_FLAG_ROLLUP | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0)
+        plan = C.c_void_p()
+        if batch.get("spec_of") is not None:
+            from .synth import spectrum_order, take_psms
+            perm, inv = spectrum_order(batch["spec_of"])
+            if perm is not None:                 # (the library wants the PSMs of a spectrum together: counted there, put back)
+                counts = np.diff(self.site_offsets(take_psms(batch, perm), skip_invalid))[inv]
+                return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            spec_of = np.ascontiguousarray(batch["spec_of"], np.uint32)
+            rc = self._lib.pya_plan_create_shared(self._h, C.byref(b), _as_ptr(spec_of), arrs[0].size - 1, flags, C.byref(plan))
+        else:
+            rc = self._lib.pya_plan_create(self._h, C.byref(b), flags, C.byref(plan))
+        if rc:
+            self._raise(rc)
+        off = np.zeros(n + 1, np.int64)
+        rc = self._lib.pya_plan_site_offsets(plan, _as_ptr(off))
+        self._lib.pya_plan_destroy(plan)
+        if rc:
+            self._raise(rc)
+        return off
 
     def _last_batch_probs(self, n):
         """pya_last_batch_probs: the size query, then the records"""

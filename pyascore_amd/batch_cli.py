@@ -21,6 +21,7 @@ from .named import sig_bits_of
 from . import sites as site_tables
 from . import probs as site_probs
 from . import ranked as ranked_lists
+from . import rollup as site_rollup
 from .synth import pack_batch, pack_shared_batch
 
 COLUMNS = ("Scan", "LocalizedSequence", "PepScore", "Ascores", "AltSites")
@@ -36,6 +37,8 @@ RUNNER_UP_COLUMNS = ("RunnerUpSequence", "DeltaPepScore")
 PROB_COLUMNS = ("SiteProbs", "BestProb")
 # ``--ranked FILE``: one line per (scan, hit, rank) (pya_ranked)
 RANKED_COLUMNS = ("Scan", "Hit", "Rank", "LocalizedSequence", "PepScore", "DeltaToBest", "Tied")
+# ``--site_table FILE``: one line per (peptide, position) over all PSMs (pya_site_rollup)
+SITE_TABLE_COLUMNS = ("Peptide", "Position", "Residue", "BestProb", "BestScan", "PSMs", "Confident", "InBest", "BestAscore")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -147,7 +150,7 @@ def pack_hits(picked, scans):
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
-             sites=None, probs=False, ranked=None, ranked_depth=5):
+             sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -164,7 +167,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     candidate residue, and the posterior of the reported localisation.
     ``ranked``: a list that receives the ranked localisations of the scored PSMs, the ``ranked_depth`` best site assignments
     of each in order, one ``[scan, hit] + ranked_fields`` row per assignment (``write_ranked_tsv``); the main table does not
-    change."""
+    change.
+    ``site_table``: a list that receives the site-level table over ALL scored PSMs, one ``site_table_fields`` row per
+    (unmodified peptide, position) (``write_site_table_tsv``): the residue records of the batch are rolled up on the device,
+    ``site_table_threshold`` being the "confident" cut; the main table does not change."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -177,8 +183,17 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     # One PSM the kernels cannot take (longer than 64 residues, more than 15 000 site assignments,
     # an unknown residue, ...) must not cost the whole run its output: such PSMs are set aside by the
     # library, reported here, and written as rows without a localisation.
-    res = ascore.score_batch(batch, skip_invalid=True, evidence=evidence, ions=ions is not None, named=named,
-                             sites=sites is not None, probs=probs, ranked=ranked_depth if ranked is not None else None)
+    stages = dict(skip_invalid=True, evidence=evidence, ions=ions is not None, named=named, sites=sites is not None, probs=probs,
+                  ranked=ranked_depth if ranked is not None else None)
+    keys = None
+    if site_table is not None:
+        peptides = [p["peptide"] for p in picked]
+        # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything
+        # is scored)
+        slot, n_slots, keys = site_rollup.peptide_slots(peptides, ascore.site_offsets(batch, skip_invalid=True), residues=residues)
+        res = ascore.score_batch(batch, rollup=dict(slot=slot, n_slots=n_slots, threshold=float(site_table_threshold)), **stages)
+    else:
+        res = ascore.score_batch(batch, **stages)
     bad = np.flatnonzero(res["status"])
     if bad.size:
         import warnings
@@ -207,6 +222,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         rk_psm = np.repeat(np.arange(len(picked), dtype=np.int64), rk.shape[1])
         rk_seqs = ascore.format_batch(batch, rk["sig_bits"].ravel(), valid=(rk["kind"].ravel() != ranked_lists.NONE).astype(np.int32),
                                       rec_psm=rk_psm)
+    if site_table is not None:
+        site_table.extend(site_table_fields(row, scans) for row in site_rollup.table(res["rollup"], keys))
     rows = []
     hit = 0
     for i, psm in enumerate(picked):
@@ -247,6 +264,26 @@ def prob_fields(site_recs, psm_rec, peptide, residues):
     pos = site_probs.positions_of(peptide, residues)
     text = site_probs.annotate(peptide, pos, site_recs["with_prob"]) if len(pos) == len(site_recs) else ""
     return [text, repr(float(site_probs.best_prob(np.asarray([psm_rec], site_probs.PSM_PROB_DTYPE))[0]))]
+
+
+def site_table_fields(row, scans):
+    """One row of ``pyascore_amd.rollup.table`` keyed by (peptide, position) as the fields of the ``--site_table`` table:
+    Peptide, Position (1-based), Residue, BestProb -- the best localisation probability any PSM gives the site --, BestScan --
+    the scan that attains it (the first PSM of the input among equals) --, PSMs -- scored PSMs that cover the site --, Confident
+    -- those that put it at or above the threshold --, InBest -- those that report it as the localisation --, BestAscore -- the
+    best Ascore of those, empty when no PSM reports the site."""
+    peptide, pos = row["key"]
+    return [peptide, str(pos), peptide[pos - 1] if 1 <= pos <= len(peptide) else "?", repr(row["best_prob"]),
+            scans[row["best_psm"]] if row["best_psm"] < len(scans) else "", str(row["n_psm"]), str(row["n_confident"]), str(row["n_in_best"]),
+            "" if row["best_ascore"] is None else str(np.float32(row["best_ascore"]))]
+
+
+def write_site_table_tsv(site_table_rows, path):
+    """The ``--site_table`` table: the rows ``localize(..., site_table=[])`` collected, under ``SITE_TABLE_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(SITE_TABLE_COLUMNS) + "\n")
+        for row in site_table_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
 
 
 def ranked_fields(rec, first, sequence):

@@ -296,6 +296,43 @@ int pya_last_batch_ranked(pya_handle *h, pya_ranked *out, uint64_t n_psm, uint32
     return PYA_OK;
 }
 
+int pya_set_rollup(pya_handle *h, const int32_t *slot, uint64_t n_records, uint64_t n_slots, double threshold, const uint32_t *psm_id) {
+    if (!h) return PYA_ERR_ARG;
+    h->rollup_loan = pya_handle::RollupLoan{};
+    if (n_records && !slot) return h->fail(PYA_ERR_ARG, -1, "pya_set_rollup: NULL slot array for %llu records", (unsigned long long)n_records);
+    if (n_slots > 0x7fffffffull) return h->fail(PYA_ERR_ARG, -1, "pya_set_rollup: %llu slots are more than an int32 slot can name", (unsigned long long)n_slots);
+    h->rollup_loan.slot = slot;
+    h->rollup_loan.psm_id = psm_id;
+    h->rollup_loan.n_records = n_records;
+    h->rollup_loan.n_slots = n_slots;
+    h->rollup_loan.threshold = threshold;
+    h->rollup_loan.set = true;
+    return PYA_OK;
+}
+
+int pya_last_batch_rollup(pya_handle *h, pya_site_rollup *out, uint64_t n_slots) {
+    if (!h) return PYA_ERR_ARG;
+    if (!h->rollup_valid) return h->fail(PYA_ERR_STATE, -1, "the last batch was scored without PYA_FLAG_ROLLUP");
+    if (n_slots != h->rollup_host.size())
+        return h->fail(PYA_ERR_ARG, -1, "the table of the last batch has %llu slots, not %llu", (unsigned long long)h->rollup_host.size(),
+                       (unsigned long long)n_slots);
+    if (n_slots == 0) return PYA_OK;
+    if (!out) return h->fail(PYA_ERR_ARG, -1, "NULL record array");
+    std::memcpy(out, h->rollup_host.data(), (size_t)n_slots * sizeof(pya_site_rollup));
+    return PYA_OK;
+}
+
+int pya_rollup_clear(pya_handle *h, pya_site_rollup *d_table, uint64_t n_slots, void *hip_stream) {
+    if (!h) return PYA_ERR_ARG;
+    if (n_slots == 0) return PYA_OK;
+    if (!d_table) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_rollup_clear");
+    if (n_slots > 0x7fffffffull) return h->fail(PYA_ERR_ARG, -1, "pya_rollup_clear: %llu slots are more than an int32 slot can name", (unsigned long long)n_slots);
+    HIPCHK(h, hipSetDevice(h->device));
+    const int e = pya_launch_rollup_clear(d_table, n_slots, (hipStream_t)hip_stream);
+    if (e) return h->hip_fail((hipError_t)e, "roll-up clear launch");
+    return PYA_OK;
+}
+
 int pya_set_ranked_k(pya_handle *h, uint32_t top_k) {
     if (!h) return PYA_ERR_ARG;
     if (top_k < 1u || top_k > PYA_MAX_RANKED) return h->fail(PYA_ERR_ARG, -1, "ranked list length %u is not in 1 .. %d", top_k, PYA_MAX_RANKED);

@@ -262,6 +262,82 @@ static int ranked_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_ou
     return PYA_OK;
 }
 
+/* PYA_FLAG_ROLLUP: the loan of pya_set_rollup becomes the call's; the device table that lives for the call is sized here and
+ * cleared in front of the first chunk's launches, on their stream */
+static int rollup_begin(pya_handle *h, pya_handle::RollupLoan *loan) {
+    *loan = h->rollup_loan;
+    h->rollup_loan = pya_handle::RollupLoan{};                /* (the loan ends with this call, whatever it returns) */
+    if (!loan->set) return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_ROLLUP without slots: call pya_set_rollup before the batch call");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->d_rollup.n < loan->n_slots || !h->d_rollup.p) HIPCHK(h, h->d_rollup.alloc((size_t)loan->n_slots));
+    h->rollup_seen = 0;
+    h->rollup_cleared = false;
+    return PYA_OK;
+}
+
+/* ... the plan's slice of the caller's slots and ids on its way to the device on `st`, IN FRONT of the plan's run: the arrays
+ * are the caller's pageable memory, a copy from there holds this thread until the stream gets to it, and in front of the run
+ * the stream is idle (the chunk before has been waited for) -- behind the run it would keep the host pre-pass of the next
+ * chunk from overlapping this chunk's kernels.  The first plan clears the call's table here too. */
+static int rollup_upload(pya_handle *h, pya_plan *p, const pya_handle::RollupLoan &loan, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (!h->rollup_cleared) {
+        const int rc0 = pya_rollup_clear(h, h->d_rollup.p, loan.n_slots, st);
+        if (rc0) return rc0;
+        h->rollup_cleared = true;
+    }
+    if (n == 0) return PYA_OK;
+    std::vector<int64_t> off(n + 1);
+    const int rc = pya_plan_site_offsets(p, off.data());
+    if (rc) return rc;
+    const uint64_t base = h->rollup_seen, total = (uint64_t)off[n];
+    if (base + total > loan.n_records)
+        return h->fail(PYA_ERR_ARG, -1, "pya_set_rollup lent %llu slots, the PSMs up to %llu have %llu residue records already",
+                       (unsigned long long)loan.n_records, (unsigned long long)(lo + n), (unsigned long long)(base + total));
+    h->rollup_seen = base + total;
+    if (total == 0) return PYA_OK;
+    HIPCHK(h, p->d_rollup_slot.alloc((size_t)total));
+    HIPCHK(h, hipMemcpyAsync(p->d_rollup_slot.p, loan.slot + base, (size_t)total * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (loan.psm_id) {
+        HIPCHK(h, p->d_rollup_id.alloc((size_t)n));
+        HIPCHK(h, hipMemcpyAsync(p->d_rollup_id.p, loan.psm_id + lo, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    return PYA_OK;
+}
+
+/* ... and the roll-up of the plan behind its probability stage on `st` (the stage of PYA_FLAG_PROBS when the call has it, its
+ * own otherwise: the records stay on the device) */
+static int rollup_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, const pya_handle::RollupLoan &loan, uint32_t flags, uint64_t lo,
+                             hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0) return PYA_OK;
+    const uint64_t total = p->d_rollup_slot.n;               /* (rollup_upload: the plan's residue records) */
+    if (!(flags & PYA_FLAG_PROBS)) {
+        HIPCHK(h, p->d_prob_sites.alloc((size_t)std::max<uint64_t>(total, 1)));
+        HIPCHK(h, p->d_prob_psms.alloc((size_t)n));
+        const int rc = pya_plan_probs(p, d_out, st, h->site_sig_cap, p->d_prob_sites.p, p->d_prob_psms.p);
+        if (rc) return rc;
+    }
+    if (total == 0) return PYA_OK;
+    return pya_plan_rollup(p, d_out, st, p->d_prob_sites.p, p->d_prob_psms.p, p->d_rollup_slot.p, loan.n_slots, loan.threshold,
+                           loan.psm_id ? p->d_rollup_id.p : nullptr, (uint32_t)lo, h->d_rollup.p);
+}
+
+/* ... and the end of the call, when every chunk has been waited for: the records must have been exactly the lent ones; the
+ * table comes to the host */
+static int rollup_end(pya_handle *h, const pya_handle::RollupLoan &loan) {
+    if (h->rollup_seen != loan.n_records)
+        return h->fail(PYA_ERR_ARG, -1, "pya_set_rollup lent %llu slots, the batch has %llu residue records", (unsigned long long)loan.n_records,
+                       (unsigned long long)h->rollup_seen);
+    pya_site_rollup empty = {};
+    empty.best_psm = PYA_ROLLUP_NO_PSM;
+    h->rollup_host.assign((size_t)loan.n_slots, empty);
+    if (loan.n_slots && h->rollup_cleared)
+        HIPCHK(h, hipMemcpy(h->rollup_host.data(), h->d_rollup.p, (size_t)loan.n_slots * sizeof(pya_site_rollup), hipMemcpyDeviceToHost));
+    h->rollup_valid = true;
+    return PYA_OK;
+}
+
 /* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
  * counts, [n_q * n_top] scores -- zeroed */
 static int named_host_block(pya_handle *h, uint64_t n_q) {
@@ -331,7 +407,7 @@ static void named_deliver(pya_handle *h, const NamedReq *nq, uint64_t lo, uint64
  * stream.  A call of any size completes; it never fails for lack of workspace. */
 static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp,
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
-                               const uint8_t *pre_sites, const NamedReq *nq) {
+                               const uint8_t *pre_sites, const NamedReq *nq, const pya_handle::RollupLoan &loan) {
     const size_t nchunk = cuts.size() - 1;
     const uint64_t n_q = nq ? (uint64_t)nq->q_off[b->n_psm] : 0;
     /* the spectra [first, last) of chunk c: its PSMs' own unless spectra are shared -- then from the first PSM's to the last
@@ -434,6 +510,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         pya_results d_out = {mk, p->d_best_score.p, p->d_best_sig.p, p->d_n_sig_out.p, p->d_ascores.p, p->d_alt.p};
         const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
         if (nq && (rc = named_upload(h, p, nq, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, lo, h->run_stream))) return finish(rc);
         rc = pya_plan_run_typed(p, &d_sp, h->run_stream, &d_out);
         if (rc) return finish(rc);
         /* status + results are adjacent in the arena: one asynchronous copy into pinned memory */
@@ -455,6 +532,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_SITES) && (rc = sites_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PROBS) && (rc = probs_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_RANKED) && (rc = ranked_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_behind_run(h, p, &d_out, loan, flags, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -494,8 +572,11 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         std::memcpy(out->ascores + lo * mk, sg + (p->o_ascores - o), n * mk * sizeof(float));
         std::memcpy(out->alt_mask + lo * mk, sg + (p->o_alt - o), n * mk * sizeof(uint64_t));
         if (nq) named_deliver(h, nq, lo, lo + n, n_q);
+        /* (a slot outside the table: the report of this chunk's roll-up, whose kernels the event above waited for) */
+        if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_report(p, lo))) return finish(rc);
         cur = std::move(next);
     }
+    if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_end(h, loan))) return finish(rc);
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
     h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
     /* (chunks behind the last PSM with records: their offsets stay at the total) */
@@ -517,6 +598,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->sites_valid = false;
     h->probs_valid = false;
     h->ranked_valid = false;
+    h->rollup_valid = false;
+    pya_handle::RollupLoan loan;
+    if (flags & PYA_FLAG_ROLLUP) {
+        const int rc_ru = rollup_begin(h, &loan);
+        if (rc_ru) return rc_ru;
+    }
     if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
     if (flags & PYA_FLAG_SITES) h->sites_off.assign(b->n_psm + 1, 0);
     if (flags & PYA_FLAG_PROBS) h->probs_off.assign(b->n_psm + 1, 0);
@@ -530,7 +617,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         h->ranked_valid = (flags & PYA_FLAG_RANKED) != 0;
         h->ranked_n = 0;
         h->ranked_batch_k = h->ranked_k;
-        return PYA_OK;
+        return (flags & PYA_FLAG_ROLLUP) ? rollup_end(h, loan) : PYA_OK;
     }
     uint32_t types = 0;
     const int rc_types = spectra_types(h, &sp, "pya_score_batch_typed", &types);
@@ -577,8 +664,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_rk = ranked_host_block(h, b);
         if (rc_rk) return rc_rk;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS or _RANKED takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED or _ROLLUP takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -621,7 +708,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
             }
             cuts.push_back(b->n_psm);
             h->last_chunks = cuts.size() - 1;
-            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq);
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan);
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -668,6 +755,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     pya_results d_out = {mk, p->d_best_score.p, p->d_best_sig.p, p->d_n_sig_out.p, p->d_ascores.p, p->d_alt.p};
     const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
     if (nq && (rc = named_upload(h, p, nq, 0, nullptr))) return rc;
+    if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, 0, nullptr))) return rc;
     rc = pya_plan_run_typed(p, &d_sp, nullptr, &d_out);
     if (rc) return rc;
     if (p->d2h_bytes <= kStageLimit) {
@@ -726,6 +814,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         HIPCHK(h, hipStreamSynchronize(nullptr));
         h->ranked_valid = true;
     }
+    if (flags & PYA_FLAG_ROLLUP) {
+        if ((rc = rollup_behind_run(h, p, &d_out, loan, flags, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        if ((rc = rollup_report(p, 0))) return rc;
+        if ((rc = rollup_end(h, loan))) return rc;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -749,6 +843,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->sites_valid = false;
     h->probs_valid = false;
     h->ranked_valid = false;
+    h->rollup_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
@@ -798,6 +893,14 @@ int pya_debug_last_ranked_launch(const pya_handle *h, uint32_t front_ends[2], ui
         front_ends[i] = h->last_ranked_sw[i];
         lds_bytes[i] = h->last_ranked_lds[i];
     }
+    return PYA_OK;
+}
+
+int pya_debug_last_rollup_launch(const pya_handle *h, uint32_t grid[2], uint64_t *n_records) {
+    if (!h || !grid || !n_records) return PYA_ERR_ARG;
+    grid[0] = h->last_rollup_grid[0];
+    grid[1] = h->last_rollup_grid[1];
+    *n_records = h->last_rollup_records;
     return PYA_OK;
 }
 

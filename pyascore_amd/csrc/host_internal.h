@@ -138,6 +138,11 @@ int pya_launch_probs(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, c
 size_t pya_ranked_lds_bytes(uint32_t l_cap, const PcCaps *caps, uint32_t sw);
 int pya_launch_ranked(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int64_t *d_site_off, uint32_t top_k,
                       uint32_t sig_cap, void *d_out, uint32_t l_cap, const PcCaps *caps, uint32_t sw, hipStream_t stream);
+int pya_launch_rollup_clear(void *d_table, uint64_t n_slots, hipStream_t stream);
+int pya_launch_rollup(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec, const void *d_site_probs, const void *d_psm_probs,
+                      const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id, uint32_t psm_base,
+                      const uint64_t *best_sig, const float *ascores, uint32_t max_k, void *d_table, uint32_t *d_over, uint32_t grid[2],
+                      hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -305,6 +310,8 @@ struct pya_handle {
     uint64_t last_probs_lds[2] = {0u, 0u};
     uint32_t last_ranked_sw[2] = {0u, 0u};     /* the same for the last pya_plan_ranked (pya_debug_last_ranked_launch) */
     uint64_t last_ranked_lds[2] = {0u, 0u};
+    uint32_t last_rollup_grid[2] = {0u, 0u};   /* the blocks of the last pya_plan_rollup's launches, and the records it walked */
+    uint64_t last_rollup_records = 0;          /* (pya_debug_last_rollup_launch) */
     uint64_t last_chunks = 0;                  /* plans the last pya_score_batch call was cut into (pya_debug_last_chunks) */
     DevBuf<unsigned char> io_buf;              /* spectra of big pya_score_batch calls (uploaded by a helper thread) */
     DevBuf<unsigned char> io_ring[2];          /* chunked calls: spectra of chunk c in slot c % 2 */
@@ -374,6 +381,21 @@ struct pya_handle {
     uint64_t ranked_n = 0;
     uint32_t ranked_k = 5, ranked_batch_k = 0;
     bool ranked_valid = false;
+    /* PYA_FLAG_ROLLUP: what pya_set_rollup lent for the next batch call (the caller's host arrays; the loan ends with that
+     * call), the device table that lives for the call, the residue records the chunks so far had, whether the table has been
+     * cleared, and the table of the last such call on the host */
+    struct RollupLoan {
+        const int32_t *slot = nullptr;
+        const uint32_t *psm_id = nullptr;
+        uint64_t n_records = 0, n_slots = 0;
+        double threshold = 0.;
+        bool set = false;
+    } rollup_loan;
+    DevBuf<pya_site_rollup> d_rollup;
+    uint64_t rollup_seen = 0;
+    bool rollup_cleared = false;
+    std::vector<pya_site_rollup> rollup_host;
+    bool rollup_valid = false;
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -725,6 +747,14 @@ struct pya_plan {
     DevBuf<pya_site_prob> d_prob_sites;
     DevBuf<pya_psm_prob> d_prob_psms;
     DevBuf<pya_ranked> d_ranked;         /* pya_plan_ranked: the records of a pya_score_batch plan */
+    /* pya_plan_rollup: the report of the last call (records whose slot is at or above n_slots: count, 0xffffffff - the
+     * smallest PSM), the event pya_plan_check waits for, whether the last run has been asked; a pya_score_batch plan's slice
+     * of the caller's slots and ids */
+    DevBuf<uint32_t> d_rollup_over;
+    hipEvent_t ev_rollup = nullptr;
+    bool rollup_asked = false;
+    DevBuf<int32_t> d_rollup_slot;
+    DevBuf<uint32_t> d_rollup_id;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -738,6 +768,7 @@ struct pya_plan {
         if (ev_ions) (void)hipEventDestroy(ev_ions);
         if (ev_named) (void)hipEventDestroy(ev_named);
         if (ev_sites) (void)hipEventDestroy(ev_sites);
+        if (ev_rollup) (void)hipEventDestroy(ev_rollup);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
@@ -845,6 +876,7 @@ struct SpecShare {
 int check_spec_of(pya_handle *h, uint64_t n_psm, const uint32_t *spec_of, uint64_t n_spectra);
 int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, const SpecShare *sh, pya_plan **out);
 int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid = false);
+int rollup_report(pya_plan *p, uint64_t psm_lo);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");
@@ -865,6 +897,10 @@ static_assert(sizeof(pya_site_prob) == 16 && offsetof(pya_site_prob, without_pro
 static_assert(sizeof(pya_ranked) == 16 && offsetof(pya_ranked, pep_score) == 8 && offsetof(pya_ranked, rank) == 12 &&
                   offsetof(pya_ranked, kind) == 14 && offsetof(pya_ranked, flags) == 15,
               "pya_ranked is one 16-byte store of ranked.hip");
+static_assert(sizeof(pya_site_rollup) == 32 && offsetof(pya_site_rollup, best_psm) == 8 && offsetof(pya_site_rollup, n_psm) == 12 &&
+                  offsetof(pya_site_rollup, n_confident) == 16 && offsetof(pya_site_rollup, n_in_best) == 20 &&
+                  offsetof(pya_site_rollup, best_ascore) == 24 && offsetof(pya_site_rollup, reserved) == 28,
+              "pya_site_rollup is the 4 x 8 bytes rollup.hip addresses");
 /* pya_score_batch_named's queries and outputs (host arrays of the caller), nullptr for the other batch entry points */
 struct NamedReq {
     const int64_t *q_off;

@@ -192,6 +192,7 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
     h->sites_valid = false;
     h->probs_valid = false;
     h->ranked_valid = false;
+    h->rollup_valid = false;
     if (flags & PYA_FLAG_EVIDENCE)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_EVIDENCE: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_IONS)
@@ -202,6 +203,8 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_PROBS: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_RANKED)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_RANKED: score the PSM as a batch of one (pya_score_batch)");
+    if (flags & PYA_FLAG_ROLLUP)
+        return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_ROLLUP: score the PSM as a batch of one (pya_score_batch)");
     if (h->kn.no_tiny) return PYA_ERR_STATE;               /* (route switch of the tests: the kernel-per-stage path) */
     if (!mz || !inten || !pep) return h->fail(PYA_ERR_ARG, -1, "NULL array");
     if (!out->best_score || !out->best_sig || !out->n_sig || !out->ascores || !out->alt_mask)

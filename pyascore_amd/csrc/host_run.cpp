@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -337,6 +337,7 @@ int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_strea
     p->ran = true;
     p->ions_state = 0;                       /* (counts, offsets and the overflow report belonged to the run before) */
     p->named_asked = false;
+    p->rollup_asked = false;
     p->dev = d;
     return rc;
 }
@@ -413,6 +414,20 @@ int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid
     return PYA_OK;
 }
 
+/* the last pya_plan_rollup of this run: records whose slot is not inside the table of the call (psm_lo: what the plan's
+ * first PSM is called in the message, a chunk's place in its batch) */
+int rollup_report(pya_plan *p, uint64_t psm_lo) {
+    pya_handle *h = p->h;
+    if (!p->rollup_asked) return PYA_OK;
+    uint32_t over[2] = {0u, 0u};
+    HIPCHK(h, hipEventSynchronize(p->ev_rollup));
+    HIPCHK(h, hipMemcpy(over, p->d_rollup_over.p, sizeof(over), hipMemcpyDeviceToHost));
+    if (!over[0]) return PYA_OK;
+    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
+    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_rollup: %u residue records (PSM %llu the first) name a slot at or above the "
+                   "n_slots of the call; nothing of them was written", over[0], (unsigned long long)first);
+}
+
 int pya_plan_check(pya_plan *p) {
     if (!p) return PYA_ERR_ARG;
     pya_handle *h = p->h;
@@ -441,6 +456,8 @@ int pya_plan_check(pya_plan *p) {
             return h->fail(PYA_ERR_LIMIT, (int64_t)(0xffffffffu - over[1]), "pya_plan_named: the query ranges of %u PSMs (PSM %u the first) "
                            "are not inside the n_q records of the call; nothing of them was written", over[0], 0xffffffffu - over[1]);
     }
+    const int rc_ru = rollup_report(p, 0);
+    if (rc_ru) return rc_ru;
     if (p->ions_state != 2) return PYA_OK;
     /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
     HIPCHK(h, hipEventSynchronize(p->ev_ions));
@@ -569,6 +586,22 @@ static void site_offsets(pya_plan *p) {
     for (uint64_t i = 0; i < p->n_psm; i++) p->site_off[i + 1] = p->site_off[i] + (int64_t)p->n_sites[i];
 }
 
+/* ... and their copy on the device for a stage on `st`: uploaded by the first call (from the plan's own vector, which
+ * outlives the copy), waited for by a later call, which may be on another stream */
+static int site_offsets_on_device(pya_plan *p, hipStream_t st) {
+    pya_handle *h = p->h;
+    if (!p->ev_sites) HIPCHK(h, hipEventCreateWithFlags(&p->ev_sites, hipEventDisableTiming));
+    if (!p->site_off_sent) {
+        HIPCHK(h, p->d_site_off.alloc(p->n_psm + 1));
+        HIPCHK(h, hipMemcpyAsync(p->d_site_off.p, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipEventRecord(p->ev_sites, st));
+        p->site_off_sent = true;
+    } else {
+        HIPCHK(h, hipStreamWaitEvent(st, p->ev_sites, 0));
+    }
+    return PYA_OK;
+}
+
 int pya_plan_site_offsets(const pya_plan *plan, int64_t *site_off) {
     if (!plan || !site_off) return PYA_ERR_ARG;
     pya_plan *p = const_cast<pya_plan *>(plan);              /* (the offsets are made once and kept) */
@@ -590,17 +623,10 @@ int pya_plan_sites(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t
     if (!d_out || !r->best_score || !r->best_sig || !r->n_sig) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_sites");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!p->ev_sites) HIPCHK(h, hipEventCreateWithFlags(&p->ev_sites, hipEventDisableTiming));
     const int rc = stage_behind_run(p, st, "pya_plan_sites", "site", pya_sites_lds_bytes);
     if (rc) return rc;
-    if (!p->site_off_sent) {
-        /* (from the plan's own vector, which outlives the copy; a later call on another stream waits for it below) */
-        HIPCHK(h, p->d_site_off.alloc(p->n_psm + 1));
-        HIPCHK(h, hipMemcpyAsync(p->d_site_off.p, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        p->site_off_sent = true;
-    } else {
-        HIPCHK(h, hipStreamWaitEvent(st, p->ev_sites, 0));
-    }
+    const int rc_off = site_offsets_on_device(p, st);
+    if (rc_off) return rc_off;
     shared_tables(h, p->dev);
     BatchDev d = p->dev;
     d.best_score = r->best_score;
@@ -710,15 +736,8 @@ int pya_plan_probs(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t
     if (rc) return rc;
     if (pya_probs_lds_bytes(p->evid_l_cap, &caps[0], sw[0]) > kMaxLds) sw[0] = 2u;
     if (pya_probs_lds_bytes(p->gen_l_cap, &caps[1], sw[1]) > kMaxLds) sw[1] = 2u;
-    if (!p->site_off_sent) {
-        /* (from the plan's own vector, which outlives the copy; a later call on another stream waits for it below) */
-        HIPCHK(h, p->d_site_off.alloc(p->n_psm + 1));
-        HIPCHK(h, hipMemcpyAsync(p->d_site_off.p, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipEventRecord(p->ev_sites, st));
-        p->site_off_sent = true;
-    } else {
-        HIPCHK(h, hipStreamWaitEvent(st, p->ev_sites, 0));
-    }
+    const int rc_off = site_offsets_on_device(p, st);
+    if (rc_off) return rc_off;
     shared_tables(h, p->dev);
     BatchDev d = p->dev;
     d.best_score = r->best_score;
@@ -765,15 +784,8 @@ int pya_plan_ranked(pya_plan *p, const pya_results *r, void *hip_stream, uint32_
     if (rc) return rc;
     if (pya_ranked_lds_bytes(p->evid_l_cap, &caps[0], sw[0]) > kMaxLds) sw[0] = 2u;
     if (pya_ranked_lds_bytes(p->gen_l_cap, &caps[1], sw[1]) > kMaxLds) sw[1] = 2u;
-    if (!p->site_off_sent) {
-        /* (from the plan's own vector, which outlives the copy; a later call on another stream waits for it below) */
-        HIPCHK(h, p->d_site_off.alloc(p->n_psm + 1));
-        HIPCHK(h, hipMemcpyAsync(p->d_site_off.p, p->site_off.data(), (p->n_psm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipEventRecord(p->ev_sites, st));
-        p->site_off_sent = true;
-    } else {
-        HIPCHK(h, hipStreamWaitEvent(st, p->ev_sites, 0));
-    }
+    const int rc_off = site_offsets_on_device(p, st);
+    if (rc_off) return rc_off;
     shared_tables(h, p->dev);
     BatchDev d = p->dev;
     d.best_score = r->best_score;
@@ -790,6 +802,46 @@ int pya_plan_ranked(pya_plan *p, const pya_results *r, void *hip_stream, uint32_
         h->last_ranked_sw[li] = launched ? sw[li] : 0u;
         h->last_ranked_lds[li] = launched ? pya_ranked_lds_bytes(li == 0 ? p->evid_l_cap : p->gen_l_cap, &caps[li], sw[li]) : 0u;
     }
+    return PYA_OK;
+}
+
+/* The roll-up stage (csrc/rollup.hip): no kernel of it reads a retained table, a fragment list or LDS, so it takes nothing of
+ * stage_behind_run but the wait for the run; the offsets are the site stage's.  Two launches, one thread per residue record,
+ * into the caller's table; the report of slots outside the table goes the way of pya_plan_named's. */
+int pya_plan_rollup(pya_plan *p, const pya_results *r, void *hip_stream, const pya_site_prob *d_site_probs, const pya_psm_prob *d_psm_probs,
+                    const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id, uint32_t psm_base,
+                    pya_site_rollup *d_table) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (n_slots > 0x7fffffffull) return h->fail(PYA_ERR_ARG, -1, "pya_plan_rollup: %llu slots are more than an int32 slot can name", (unsigned long long)n_slots);
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_rollup: the plan has not been run");
+    site_offsets(p);
+    const uint64_t n_rec = (uint64_t)p->site_off[p->n_psm];
+    if (!d_psm_probs || (n_rec && (!d_site_probs || !d_slot)) || (n_slots && !d_table) || !r->best_sig || !r->ascores)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_rollup");
+    if (r->max_k < p->max_k)
+        return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)", r->max_k, p->max_k);
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->d_rollup_over.p) HIPCHK(h, p->d_rollup_over.alloc(2));
+    if (!p->ev_rollup) HIPCHK(h, hipEventCreateWithFlags(&p->ev_rollup, hipEventDisableTiming));
+    if (st != p->last_stream) {                                 /* (behind the run, as stage_behind_run waits for it) */
+        if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
+        HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
+    }
+    const int rc_off = site_offsets_on_device(p, st);
+    if (rc_off) return rc_off;
+    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
+    if (p->rollup_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_rollup, 0));
+    HIPCHK(h, hipMemsetAsync(p->d_rollup_over.p, 0, 2 * sizeof(uint32_t), st));
+    const int e = pya_launch_rollup(p->d_site_off.p, p->n_psm, n_rec, d_site_probs, d_psm_probs, d_slot, n_slots, threshold, d_psm_id, psm_base,
+                                    r->best_sig, r->ascores, r->max_k, d_table, p->d_rollup_over.p, h->last_rollup_grid, st);
+    if (e) return h->hip_fail((hipError_t)e, "roll-up launch");
+    h->last_rollup_records = n_rec;
+    HIPCHK(h, hipEventRecord(p->ev_rollup, st));
+    p->rollup_asked = true;
     return PYA_OK;
 }
 

@@ -27,10 +27,11 @@ class DevicePlan:
     (``pya_plan_ions_count``, ``pya_plan_ions``).  ``named()`` / ``named=True``: the same for the records of localisations
     the caller names (``pya_plan_named``).  ``sites()`` / ``sites=True``: the same for the site tables
     (``pya_plan_site_offsets``, ``pya_plan_sites``).  ``probs()`` / ``probs=True``: the same for the site probabilities
-    (``pya_plan_probs``).  ``ranked()`` / ``ranked=True``: the same for the ranked localisations (``pya_plan_ranked``)."""
+    (``pya_plan_probs``).  ``ranked()`` / ``ranked=True``: the same for the ranked localisations (``pya_plan_ranked``).  ``rollup()`` /
+    ``rollup=True``: the probability records rolled into a table of the caller's slots (``pya_plan_rollup``)."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
-                 ranked=False):
+                 ranked=False, rollup=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -60,7 +61,8 @@ class DevicePlan:
         self._plan = C.c_void_p()
         flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
             (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
-            (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0)
+            (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0) | \
+            (_lib.PYA_FLAG_ROLLUP if rollup else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -261,6 +263,51 @@ class DevicePlan:
             self.scorer._raise(rc)
         return out
 
+    def rollup_clear(self, n_slots=None, table=None):
+        """A roll-up table in the empty state: a ``torch.uint8`` device tensor ``[n_slots, 32]`` (one ``pya_site_rollup`` per
+        slot; ``rollup_records`` turns a host copy into the structured array), new or -- ``table`` -- an earlier one to be
+        emptied again.  One launch on torch's current stream.  The empty slot is not all-zero bytes (``best_psm`` is "no
+        PSM"): a table must come from here before ``rollup()`` accumulates into it."""
+        torch = self._torch
+        if table is None:
+            with torch.cuda.device(self.device):
+                table = torch.empty((int(n_slots), 32), dtype=torch.uint8, device=self.device)
+        if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 32 or not table.is_contiguous() or not table.is_cuda:
+            raise ValueError("table must be a contiguous uint8 device tensor of shape (n_slots, 32)")
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_rollup_clear(self.scorer._h, table.data_ptr(), table.shape[0], stream)
+        if rc:
+            self.scorer._raise(rc)
+        return table
+
+    def rollup(self, site_probs, psm_probs, slot, table, threshold=0.75, psm_id=None, psm_base=0):
+        """Rolls the probability records of the last ``run()`` -- the two tensors of ``probs()`` -- into ``table`` (of
+        ``rollup_clear``), which ACCUMULATES: the same table takes other plans, runs and calls, and the bytes are those of one
+        call over all of their PSMs.  ``slot``: ``torch.int32`` device tensor, one entry per residue record
+        (``site_offsets()[-1]``), the slot the record goes to, negative to leave it out; ``psm_id``: ``torch.int32`` /
+        ``torch.uint32`` device tensor ``[n_psm]``, the numbers the PSMs are known by in ``best_psm``, or None: PSM i is
+        ``psm_base + i``.  Two launches of the library on torch's current stream; nothing waits on the host.  A slot at or
+        above the table's size writes nothing and is reported by ``check()``.  Returns ``table``."""
+        torch = self._torch
+        n_rec = int(self.site_offsets()[-1])
+        if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 32 or not table.is_contiguous() or not table.is_cuda:
+            raise ValueError("table must be a contiguous uint8 device tensor of shape (n_slots, 32)")
+        if slot.dtype != torch.int32 or tuple(slot.shape) != (n_rec,) or not slot.is_contiguous() or not slot.is_cuda:
+            raise ValueError("slot must be a contiguous int32 device tensor of %d entries" % n_rec)
+        if site_probs.dtype != torch.float64 or tuple(site_probs.shape) != (n_rec, 2) or not site_probs.is_contiguous() or not site_probs.is_cuda \
+                or psm_probs.dtype != torch.uint8 or tuple(psm_probs.shape) != (self.n_psm, 16) or not psm_probs.is_contiguous() or not psm_probs.is_cuda:
+            raise ValueError("site_probs and psm_probs must be the tensors of probs()")
+        if psm_id is not None and (psm_id.element_size() != 4 or psm_id.is_floating_point() or tuple(psm_id.shape) != (self.n_psm,)
+                                   or not psm_id.is_contiguous() or not psm_id.is_cuda):
+            raise ValueError("psm_id must be a contiguous 32-bit integer device tensor of %d entries" % self.n_psm)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_plan_rollup(self._plan, C.byref(self._res), stream, site_probs.data_ptr(), psm_probs.data_ptr(), slot.data_ptr(),
+                                       table.shape[0], float(threshold), None if psm_id is None else psm_id.data_ptr(), int(psm_base),
+                                       table.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return table
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -311,6 +358,7 @@ NAMED_DTYPE = np.dtype(_lib.NAMED_DTYPE)
 SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)
 PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)
 RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)
+ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)
 
 
 def evidence_rows(raw):
@@ -369,6 +417,15 @@ def ranked_records(raw):
     if a.ndim != 3 or a.shape[2] != RANKED_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, K, %d)" % RANKED_DTYPE.itemsize)
     return a.view(RANKED_DTYPE).reshape(a.shape[0], a.shape[1])
+
+
+def rollup_records(raw):
+    """A host copy of a roll-up table (``.cpu().numpy()``, uint8 ``[n_slots, 32]``) as the structured array
+    ``PyAscore.score_batch(..., rollup=...)`` returns in ``rollup``; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != ROLLUP_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % ROLLUP_DTYPE.itemsize)
+    return a.view(ROLLUP_DTYPE).reshape(a.shape[0])
 
 
 def named_records(raw):

@@ -1,0 +1,138 @@
+"""Site roll-up: the slots ``PyAscore.score_batch(rollup=...)`` rolls the residue records of a batch into, and the table it
+returns turned into the rows of a site-level report.
+
+Pure Python / numpy: nothing here needs a scorer.  A batch has one residue record per modifiable residue of every PSM that
+was not set aside, N- to C-terminus, at ``site_off[i]:site_off[i + 1]`` (``score_batch(probs=True)`` returns ``site_off``;
+``site_offsets`` below finds it from the peptides).  A *slot* is one site in the key the caller chooses; ``slot`` names the
+slot of every record (negative: the record is left out), and the table (``ROLLUP_DTYPE``, the 32-byte ``pya_site_rollup`` of
+include/pyascore_hip.h) has one record per slot: the best localisation probability any PSM gives the site and which PSM
+gives it, how many PSMs cover it, how many put it at or above the threshold, how many report it as the localisation, and the
+best Ascore of those.
+"""
+import numpy as np
+
+from . import _lib
+from .named import site_residues
+
+ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)          # pya_site_rollup, 32 bytes
+assert ROLLUP_DTYPE.itemsize == 32
+NO_PSM = _lib.PYA_ROLLUP_NO_PSM
+
+
+def _text(peptide):
+    return peptide.decode("ascii", "replace") if isinstance(peptide, (bytes, bytearray)) else str(peptide)
+
+
+def empty(n_slots):
+    """A table of ``n_slots`` empty slots (``best_psm`` is ``NO_PSM``, everything else 0)."""
+    t = np.zeros(int(n_slots), ROLLUP_DTYPE)
+    t["best_psm"] = NO_PSM
+    return t
+
+
+def site_offsets(peptides, residues):
+    """``(site_off, positions)`` of a batch whose PSMs are all scored: the record offsets (int64 ``[n + 1]``) and the 1-based
+    position of every record (int64), for a scorer whose modification group is ``residues`` (``n`` / ``c`` in it: the first /
+    last residue whatever its letter).  A PSM that the library sets aside has no records: take ``site_off`` from the batch
+    then."""
+    pos = [[j + 1 for j in site_residues(_text(p), residues)] for p in peptides]
+    off = np.concatenate([[0], np.cumsum([len(p) for p in pos])]).astype(np.int64)
+    return off, np.array([j for p in pos for j in p], np.int64)
+
+
+def _positions(peptides, site_off, positions, residues):
+    site_off = np.asarray(site_off, np.int64)
+    if site_off.size != len(peptides) + 1:
+        raise ValueError("site_off must have one entry per PSM and one more")
+    if positions is None:
+        if residues is None:
+            raise ValueError("the slots need the residues of the modification group, or the position of every record")
+        off, positions = site_offsets(peptides, residues)
+        # (a PSM without records was set aside: its positions are dropped)
+        keep = np.repeat(np.diff(site_off) != 0, np.diff(off))
+        positions = positions[keep]
+    positions = np.asarray(positions, np.int64)
+    if positions.size != int(site_off[-1]):
+        raise ValueError("%d positions for %d residue records" % (positions.size, int(site_off[-1])))
+    return site_off, positions
+
+
+def _number(keys_of_records):
+    """slots in order of first appearance"""
+    index, keys = {}, []
+    slot = np.empty(len(keys_of_records), np.int32)
+    for r, k in enumerate(keys_of_records):
+        s = index.get(k)
+        if s is None:
+            s = index[k] = len(keys)
+            keys.append(k)
+        slot[r] = s
+    return slot, len(keys), keys
+
+
+def peptide_slots(peptides, site_off, positions=None, residues=None):
+    """``(slot, n_slots, keys)`` keyed by (unmodified peptide sequence, 1-based position): every PSM of a peptide lands on the
+    same slots.  Slots are numbered in order of first appearance; ``keys[s]`` is the key of slot ``s``.  ``peptides``: one
+    str / bytes per PSM; ``positions``: one per record (e.g. ``sites["pos"]`` of the same batch), or found from ``residues``,
+    the scorer's modification group."""
+    site_off, positions = _positions(peptides, site_off, positions, residues)
+    owner = np.repeat(np.arange(len(peptides)), np.diff(site_off))
+    text = [_text(p) for p in peptides]
+    return _number([(text[i], int(p)) for i, p in zip(owner, positions)])
+
+
+def protein_slots(protein_of, start_of, site_off, positions):
+    """``(slot, n_slots, keys)`` keyed by (protein id, absolute 1-based position): ``protein_of[i]`` is the protein of PSM
+    ``i``'s peptide and ``start_of[i]`` the 1-based position of its first residue there, so two overlapping peptides land on
+    one slot.  A PSM whose ``protein_of`` is None is left out (slot -1)."""
+    site_off = np.asarray(site_off, np.int64)
+    positions = np.asarray(positions, np.int64)
+    if site_off.size != len(protein_of) + 1 or len(start_of) != len(protein_of) or positions.size != int(site_off[-1]):
+        raise ValueError("protein_of and start_of have one entry per PSM, positions one per residue record")
+    owner = np.repeat(np.arange(len(protein_of)), np.diff(site_off))
+    known = np.array([protein_of[i] is not None for i in owner], bool)
+    slot = np.full(positions.size, -1, np.int32)
+    got, n_slots, keys = _number([(protein_of[i], int(start_of[i]) + int(p) - 1) for i, p in zip(owner[known], positions[known])])
+    slot[known] = got
+    return slot, n_slots, keys
+
+
+def merge(a, b):
+    """The table of the PSMs behind ``a`` and the PSMs behind ``b`` together (same slots, same threshold): every field is a
+    max, a min or a count, so tables of several ranks, files or runs add up on the host to the bytes of one call over all of
+    their PSMs."""
+    a, b = np.asarray(a, ROLLUP_DTYPE), np.asarray(b, ROLLUP_DTYPE)
+    if a.shape != b.shape:
+        raise ValueError("tables over different slots")
+    out = a.copy()
+    pa, pb = a["best_prob"].view(np.uint64), b["best_prob"].view(np.uint64)
+    out["best_prob"] = np.where(pb > pa, b["best_prob"], a["best_prob"])
+    out["best_psm"] = np.where(pb > pa, b["best_psm"], np.where(pb == pa, np.minimum(a["best_psm"], b["best_psm"]), a["best_psm"]))
+    for f in ("n_psm", "n_confident", "n_in_best"):
+        out[f] = a[f] + b[f]
+    ka, kb = _ascore_key(a["best_ascore"]), _ascore_key(b["best_ascore"])
+    ka[a["n_in_best"] == 0] = -1
+    kb[b["n_in_best"] == 0] = -1
+    out["best_ascore"] = np.where(kb > ka, b["best_ascore"], a["best_ascore"])
+    return out
+
+
+def _ascore_key(x):
+    """the order-preserving image of float32 bit patterns (int64): -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN"""
+    bits = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.int64)
+    return np.where(bits >> 31 != 0, 0xFFFFFFFF - bits, bits + 0x80000000)
+
+
+def table(rollup, keys):
+    """Rows for a site-level report, one per slot that any PSM covers: dicts with ``key`` (``keys[s]``), ``best_prob``,
+    ``best_psm``, ``n_psm``, ``n_confident``, ``n_in_best`` and ``best_ascore`` (None when no PSM reports the site)."""
+    rollup = np.asarray(rollup, ROLLUP_DTYPE)
+    if len(keys) != rollup.size:
+        raise ValueError("%d keys for %d slots" % (len(keys), rollup.size))
+    rows = []
+    for s in np.flatnonzero(rollup["n_psm"]):
+        r = rollup[s]
+        rows.append(dict(key=keys[s], best_prob=float(r["best_prob"]), best_psm=int(r["best_psm"]), n_psm=int(r["n_psm"]),
+                         n_confident=int(r["n_confident"]), n_in_best=int(r["n_in_best"]),
+                         best_ascore=float(r["best_ascore"]) if r["n_in_best"] else None))
+    return rows
