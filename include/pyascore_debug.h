@@ -59,6 +59,14 @@ int pya_debug_last_ranked_launch(const pya_handle *h, uint32_t front_ends[2], ui
  * 0 when the plan had no residue records; *n_records = the records it walked.  No reference counterpart. */
 int pya_debug_last_rollup_launch(const pya_handle *h, uint32_t grid[2], uint64_t *n_records);
 
+/* pya_rollup_flr with HIP events between its phases: ms[0] the key build, ms[1 .. 9] the nine sort passes (histogram, scan,
+ * scatter each), ms[10] the scans over the sorted order and the records, ms[11] the whole stage.  Synchronises hip_stream
+ * before it returns.  For scripts/flr_probe.py.  No reference counterpart. */
+#define PYA_FLR_PHASES 11
+int pya_debug_rollup_flr_timed(pya_handle *h, const pya_site_rollup *d_table, uint64_t n_slots, const uint8_t *d_cls, uint32_t flags,
+                               void *hip_stream, void *d_work, uint64_t work_bytes, pya_site_flr *d_out, uint32_t *d_order,
+                               uint32_t *d_n_ranked, float ms[PYA_FLR_PHASES + 1]);
+
 /* The signature list of PSM `psm` of the handle's retained batch (the last PYA_FLAG_KEEP call): the sig bits of its site
  * assignments in the order every kernel scores them in and the probability stage sums them in (pya_get_pep_scores* returns
  * the reference's sorted order instead).  *n = their number; sig_bits may be NULL with cap 0 to ask.  No reference

@@ -325,6 +325,37 @@ typedef struct pya_site_rollup {   /* 32 bytes; records compare as raw bytes */
     uint32_t reserved;             /* 0                                                                        */
 } pya_site_rollup;
 
+/* Site FLR.  The roll-up says how good every site's best localisation is; this says which sites may be reported at a given
+ * false-localisation rate: the slots sorted by best_prob, the expected errors 1 - p accumulated down the list and, with decoy
+ * residues in the modification group (Ala / Pro / Gly beside STY), the decoys above every cut turned into a q-value.  Input:
+ * a table in any state pya_plan_rollup or a host merge can leave it in, and optionally a class byte per slot, cls[n_slots] --
+ * PYA_FLR_TARGET, PYA_FLR_DECOY, PYA_FLR_LEFT_OUT; NULL: every slot is a target.  A slot is RANKED when n_psm != 0, its class
+ * is target or decoy and, with PYA_FLR_REPORTED_ONLY, n_in_best != 0.  The ranked slots are ordered by best_prob descending,
+ * compared as the uint64 bit pattern (as the roll-up orders them), equal bits by ascending slot index.  A TIE GROUP is the set
+ * of ranked slots with identical best_prob bits; every member of a group gets the same values, the cumulative ones at the END
+ * of its group.  THE RECORD OF A SLOT IS A FUNCTION OF THE MULTISET OF (best_prob bits, class) OF THE RANKED SLOTS AND OF
+ * NOTHING ELSE: rank and n_decoy are integer counts, err_sum is a sum of integers -- err(p) = (uint64_t)(max(0.0, 1.0 - p) *
+ * 4294967296.0), one double subtraction, an exact scaling by 2^32, truncation; below 2^63 for n_slots <= 2^31 - 1 --, flr and
+ * decoy_q are one correctly rounded division each of exactly converted integers.  Permuting the slots permutes the records.
+ * flr needs no running minimum: the running mean of a non-decreasing sequence is non-decreasing.  An unranked slot's record
+ * is 32 zero bytes.  csrc/flr.hip; the library is built without fast-math. */
+#define PYA_FLR_TARGET 0u
+#define PYA_FLR_DECOY 1u
+#define PYA_FLR_LEFT_OUT 2u
+#define PYA_FLR_REPORTED_ONLY 1u   /* flag: slots with n_in_best == 0 are not ranked */
+#define PYA_FLR_TILE 1024u         /* slots per workgroup and sort pass (the sizes a test of the stage wants to straddle) */
+typedef struct pya_site_flr {      /* 32 bytes; records compare as raw bytes */
+    uint32_t rank;                 /* ranked slots whose best_prob bits are >= this slot's; 0: the slot is not ranked  */
+    uint32_t n_decoy;              /* ... of them with class PYA_FLR_DECOY                                             */
+    uint64_t err_sum;              /* sum of err(best_prob) over them                                                  */
+    double flr;                    /* (double)err_sum / (double)((uint64_t)rank << 32): the model-based FLR of the cut  */
+                                   /* "this site and everything at least as good"                                      */
+    double decoy_q;                /* min over this group and every group with SMALLER best_prob of (double)n_decoy /   */
+                                   /* (double)max(rank - n_decoy, 1): the q-value of the raw decoy / target ratio (the  */
+                                   /* caller multiplies by the target-to-decoy residue frequency ratio, a positive      */
+                                   /* constant that commutes with the minimum); 0 when no slot is a decoy              */
+} pya_site_flr;
+
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
  * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
@@ -571,6 +602,26 @@ int pya_last_batch_rollup(pya_handle *h, pya_site_rollup *out, uint64_t n_slots)
 /* Puts a DEVICE table of n_slots records into the empty state (best_psm = PYA_ROLLUP_NO_PSM, everything else 0), on
  * hip_stream, stream-ordered, no host synchronisation inside. */
 int pya_rollup_clear(pya_handle *h, pya_site_rollup *d_table, uint64_t n_slots, void *hip_stream);
+
+/* The device bytes pya_rollup_flr needs as its workspace for a table of n_slots (keys and payloads double-buffered, digit
+ * histograms, tile sums: about 25 bytes per slot); 0 for an empty table. */
+uint64_t pya_flr_workspace_bytes(uint64_t n_slots);
+/* Site FLR (pya_site_flr above) of the DEVICE table d_table[n_slots]: d_out[n_slots] the records, d_order[n_slots] (or NULL)
+ * the ranked slots in order, then the unranked ones by ascending index, d_n_ranked[2] the number of ranked slots and an error
+ * word -- the number of class bytes that are none of 0, 1, 2 (such a slot is treated as left out).  d_cls[n_slots] or NULL;
+ * flags: PYA_FLR_REPORTED_ONLY or 0.  Everything is stream-ordered on hip_stream: no host synchronisation and no allocation
+ * inside, the caller lends d_work (work_bytes >= pya_flr_workspace_bytes(n_slots), 16-byte aligned as d_table and d_out are)
+ * and reads the results after the stream reaches them.  The table is only read.  No write lies outside d_out[0 .. n_slots),
+ * d_order[0 .. n_slots), d_n_ranked[0 .. 2) and d_work[0 .. pya_flr_workspace_bytes(n_slots)).  n_slots == 0 is valid and
+ * launches nothing (d_n_ranked is zeroed).  PYA_ERR_ARG, with nothing launched: n_slots above 2^31 - 1, unknown flag bits, a
+ * workspace that is too small, NULL or misaligned where an array is needed. */
+int pya_rollup_flr(pya_handle *h, const pya_site_rollup *d_table, uint64_t n_slots, const uint8_t *d_cls, uint32_t flags, void *hip_stream,
+                   void *d_work, uint64_t work_bytes, pya_site_flr *d_out, uint32_t *d_order, uint32_t *d_n_ranked);
+/* The same for a HOST table (a table merged over several files, ...): uploads, runs pya_rollup_flr on the handle's stream
+ * with a workspace of its own, downloads and checks the error word.  order may be NULL.  A class byte above 2: PYA_ERR_ARG
+ * (pya_error_index names the slot), before anything is uploaded. */
+int pya_rollup_flr_host(pya_handle *h, const pya_site_rollup *table, uint64_t n_slots, const uint8_t *cls, uint32_t flags, pya_site_flr *out,
+                        uint32_t *order, uint32_t *n_ranked);
 
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);

@@ -9,7 +9,8 @@ engine's own site assignment, scored against the winner) and ``--sites FILE`` (a
 the runner-up localisation in the main one) and ``--probs`` (two more columns: the localisation probability of every
 candidate residue and the posterior of the reported localisation) and ``--ranked FILE`` with ``--ranked_depth K`` (a table
 with a line per ranked site assignment: the K best localisations of every PSM, in order) and ``--site_table FILE`` with
-``--site_table_threshold P`` (a site-level table over all PSMs, a line per peptide and position) are the additions."""
+``--site_table_threshold P`` (a site-level table over all PSMs, a line per peptide and position; ``--site_table_flr`` ranks
+its sites and adds false-localisation rates, ``--site_table_decoys LETTERS`` names decoy residues) are the additions."""
 import argparse
 import re
 import sys
@@ -79,6 +80,13 @@ def build_parser():
                         "device from the localisation probabilities; the main table does not change")
     p.add_argument("--site_table_threshold", type=float, default=0.75, metavar="P",
                    help="the localisation probability from which a PSM counts as Confident in --site_table (default 0.75)")
+    p.add_argument("--site_table_flr", action="store_true",
+                   help="rank the sites of --site_table on the device: its rows come best site first and gain the columns Rank "
+                        "(sites at least as good), FLR (the model-based false-localisation rate of that cut) and DecoyQ (the "
+                        "q-value of the decoy / target ratio); without this option the file is unchanged")
+    p.add_argument("--site_table_decoys", type=str, default="", metavar="LETTERS",
+                   help="with --site_table_flr: sites on these residues are decoys (meaningful when the letters are in "
+                        "--residues, e.g. --residues STYA --site_table_decoys A)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -149,7 +157,8 @@ def run(args, log=print):
                               match_save=args.match_save, log=lambda m: log("{} -- {}".format(stamp(), m)),
                               evidence=args.evidence, ions=ion_rows, reported=args.reported, sites=site_rows,
                               probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth, site_table=site_table_rows,
-                              site_table_threshold=args.site_table_threshold)
+                              site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
+                              site_table_decoys=args.site_table_decoys)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -157,7 +166,7 @@ def run(args, log=print):
     if ranked_rows is not None:
         batch_cli.write_ranked_tsv(ranked_rows, args.ranked)
     if site_table_rows is not None:
-        batch_cli.write_site_table_tsv(site_table_rows, args.site_table)
+        batch_cli.write_site_table_tsv(site_table_rows, args.site_table, flr=args.site_table_flr)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

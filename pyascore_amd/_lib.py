@@ -18,6 +18,10 @@ PYA_FLAG_PROBS = 128
 PYA_FLAG_RANKED = 256
 PYA_FLAG_ROLLUP = 512
 PYA_ROLLUP_NO_PSM = 0xFFFFFFFF
+PYA_FLR_TARGET, PYA_FLR_DECOY, PYA_FLR_LEFT_OUT = 0, 1, 2
+PYA_FLR_REPORTED_ONLY = 1
+PYA_FLR_TILE = 1024          # slots per workgroup and sort pass of csrc/flr.hip
+PYA_FLR_PHASES = 11          # (include/pyascore_debug.h: pya_debug_rollup_flr_timed)
 PYA_MAX_RANKED = 64
 PYA_RANK_NONE, PYA_RANK_SCORED, PYA_RANK_OVER = 0, 1, 2
 PYA_RANK_TIED_PREV, PYA_RANK_IN_BEST_TIE = 1, 2
@@ -140,6 +144,16 @@ assert C.sizeof(SiteRollup) == 32, "pya_site_rollup is a 32-byte record"
 ROLLUP_DTYPE = [("best_prob", "<f8"), ("best_psm", "<u4"), ("n_psm", "<u4"), ("n_confident", "<u4"), ("n_in_best", "<u4"),
                 ("best_ascore", "<f4"), ("reserved", "<u4")]
 
+
+class SiteFlr(C.Structure):
+    """pya_site_flr: one slot of a roll-up table under the cut "this site and everything at least as good" -- how many
+    ranked sites, how many decoys among them, their summed expected error, the model FLR and the decoy q-value"""
+    _fields_ = [("rank", C.c_uint32), ("n_decoy", C.c_uint32), ("err_sum", C.c_uint64), ("flr", C.c_double), ("decoy_q", C.c_double)]
+
+
+assert C.sizeof(SiteFlr) == 32, "pya_site_flr is a 32-byte record"
+FLR_DTYPE = [("rank", "<u4"), ("n_decoy", "<u4"), ("err_sum", "<u8"), ("flr", "<f8"), ("decoy_q", "<f8")]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -202,6 +216,10 @@ SYMBOLS = {
     "pya_last_batch_rollup": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_rollup_clear": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
     "pya_plan_rollup": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_uint64, C.c_double, _vp, C.c_uint32, _vp]),
+    "pya_flr_workspace_bytes": (C.c_uint64, [C.c_uint64]),
+    "pya_rollup_flr": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
+    "pya_rollup_flr_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "pya_debug_rollup_flr_timed": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp, _vp]),   # (test-only)
     "pya_plan_create": (C.c_int, [_vp, C.POINTER(Batch), C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_create_shared": (C.c_int, [_vp, C.POINTER(Batch), _vp, C.c_uint64, C.c_uint32, C.POINTER(_vp)]),
     "pya_plan_run": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(Results)]),

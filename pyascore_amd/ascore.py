@@ -77,6 +77,7 @@ assert SITE_PROB_DTYPE.itemsize == 16 and PSM_PROB_DTYPE.itemsize == 16
 RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)          # pya_ranked, 16 bytes
 assert RANKED_DTYPE.itemsize == 16
 ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)          # pya_site_rollup, 32 bytes
+FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)                # pya_site_flr, 32 bytes
 assert ROLLUP_DTYPE.itemsize == 32
 assert EVIDENCE_DTYPE.itemsize == 16
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
@@ -655,6 +656,28 @@ class PyAscore:
         if rc:
             self._raise(rc)
         return off
+
+    def rollup_flr(self, table, cls=None, reported_only=False):
+        """Site FLR of a roll-up table on the device (``pya_rollup_flr_host``): ``table`` is a ``ROLLUP_DTYPE`` array as
+        ``score_batch(rollup=...)`` returns it or ``pyascore_amd.rollup.merge`` makes it of several, ``cls`` one byte per slot
+        (0 target, 1 decoy, 2 left out; ``pyascore_amd.rollup.decoy_classes``) or None: every slot is a target;
+        ``reported_only``: slots no PSM reports (``n_in_best == 0``) are not ranked.  Returns ``(records, order, n_ranked)``:
+        ``FLR_DTYPE`` (the 32-byte ``pya_site_flr``) per slot, the ranked slots best first then the others by index
+        (uint32), and the number of ranked slots.  ``pyascore_amd.rollup.flr`` gives the same bytes on the host."""
+        table = np.ascontiguousarray(table, ROLLUP_DTYPE)
+        if table.ndim != 1:
+            raise ValueError("rollup_flr: the table is one record per slot")
+        n = table.size
+        if cls is not None:
+            cls = np.ascontiguousarray(cls, np.uint8)
+            if cls.shape != (n,):
+                raise ValueError("rollup_flr: cls has one byte per slot")
+        records, order, n_ranked = np.zeros(n, FLR_DTYPE), np.zeros(n, np.uint32), np.zeros(1, np.uint32)
+        rc = self._lib.pya_rollup_flr_host(self._h, _as_ptr(table), n, _as_ptr(cls), _lib.PYA_FLR_REPORTED_ONLY if reported_only else 0,
+                                           _as_ptr(records), _as_ptr(order), _as_ptr(n_ranked))
+        if rc:
+            self._raise(rc)
+        return records, order, int(n_ranked[0])
 
     def _last_batch_probs(self, n):
         """pya_last_batch_probs: the size query, then the records"""

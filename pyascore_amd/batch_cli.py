@@ -39,6 +39,8 @@ PROB_COLUMNS = ("SiteProbs", "BestProb")
 RANKED_COLUMNS = ("Scan", "Hit", "Rank", "LocalizedSequence", "PepScore", "DeltaToBest", "Tied")
 # ``--site_table FILE``: one line per (peptide, position) over all PSMs (pya_site_rollup)
 SITE_TABLE_COLUMNS = ("Peptide", "Position", "Residue", "BestProb", "BestScan", "PSMs", "Confident", "InBest", "BestAscore")
+# ``--site_table_flr``: three more columns of the ``--site_table`` table (pya_site_flr), its rows best site first
+SITE_TABLE_FLR_COLUMNS = ("Rank", "FLR", "DecoyQ")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -150,7 +152,8 @@ def pack_hits(picked, scans):
 
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
-             sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75):
+             sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
+             site_table_flr=False, site_table_decoys=""):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -170,7 +173,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     change.
     ``site_table``: a list that receives the site-level table over ALL scored PSMs, one ``site_table_fields`` row per
     (unmodified peptide, position) (``write_site_table_tsv``): the residue records of the batch are rolled up on the device,
-    ``site_table_threshold`` being the "confident" cut; the main table does not change."""
+    ``site_table_threshold`` being the "confident" cut; the main table does not change.  ``site_table_flr=True``: the rows
+    come best site first and end with three more fields (``SITE_TABLE_FLR_COLUMNS``) -- the number of sites at least as good,
+    the model-based false-localisation rate of that cut, and the decoy q-value --, computed on the device over the table;
+    ``site_table_decoys``: the letters of the modification group that are decoy residues (sites on them count as decoys)."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -223,7 +229,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         rk_seqs = ascore.format_batch(batch, rk["sig_bits"].ravel(), valid=(rk["kind"].ravel() != ranked_lists.NONE).astype(np.int32),
                                       rec_psm=rk_psm)
     if site_table is not None:
-        site_table.extend(site_table_fields(row, scans) for row in site_rollup.table(res["rollup"], keys))
+        flr = None
+        if site_table_flr:
+            flr = ascore.rollup_flr(res["rollup"], site_rollup.decoy_classes(keys, decoys=site_table_decoys) if site_table_decoys else None)
+        site_table.extend(site_table_fields(row, scans) for row in site_rollup.table(res["rollup"], keys, flr=flr))
     rows = []
     hit = 0
     for i, psm in enumerate(picked):
@@ -271,17 +280,28 @@ def site_table_fields(row, scans):
     Peptide, Position (1-based), Residue, BestProb -- the best localisation probability any PSM gives the site --, BestScan --
     the scan that attains it (the first PSM of the input among equals) --, PSMs -- scored PSMs that cover the site --, Confident
     -- those that put it at or above the threshold --, InBest -- those that report it as the localisation --, BestAscore -- the
-    best Ascore of those, empty when no PSM reports the site."""
+    best Ascore of those, empty when no PSM reports the site.  A row of ``table(..., flr=...)`` has three more
+    (``SITE_TABLE_FLR_COLUMNS``): Rank -- the sites at least as good as this one, ties included --, FLR and DecoyQ of that cut;
+    empty for a site that is not ranked."""
     peptide, pos = row["key"]
+    more = []
+    if "rank" in row:
+        more = ["", "", ""] if row["rank"] is None else [str(row["rank"]), repr(row["flr"]), repr(row["decoy_q"])]
+    return _site_table_fields(row, scans, peptide, pos) + more
+
+
+def _site_table_fields(row, scans, peptide, pos):
     return [peptide, str(pos), peptide[pos - 1] if 1 <= pos <= len(peptide) else "?", repr(row["best_prob"]),
             scans[row["best_psm"]] if row["best_psm"] < len(scans) else "", str(row["n_psm"]), str(row["n_confident"]), str(row["n_in_best"]),
             "" if row["best_ascore"] is None else str(np.float32(row["best_ascore"]))]
 
 
-def write_site_table_tsv(site_table_rows, path):
-    """The ``--site_table`` table: the rows ``localize(..., site_table=[])`` collected, under ``SITE_TABLE_COLUMNS``."""
+def write_site_table_tsv(site_table_rows, path, flr=False):
+    """The ``--site_table`` table: the rows ``localize(..., site_table=[])`` collected, under ``SITE_TABLE_COLUMNS`` (and,
+    ``flr=True``, ``SITE_TABLE_FLR_COLUMNS``: the rows of ``localize(..., site_table_flr=True)``)."""
+    wide = bool(flr)
     with open(path, "w") as out:
-        out.write("\t".join(SITE_TABLE_COLUMNS) + "\n")
+        out.write("\t".join(SITE_TABLE_COLUMNS + (SITE_TABLE_FLR_COLUMNS if wide else ())) + "\n")
         for row in site_table_rows:
             out.write("\t".join("%s" % f for f in row) + "\n")
 

@@ -143,6 +143,9 @@ int pya_launch_rollup(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec,
                       const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id, uint32_t psm_base,
                       const uint64_t *best_sig, const float *ascores, uint32_t max_k, void *d_table, uint32_t *d_over, uint32_t grid[2],
                       hipStream_t stream);
+uint64_t pya_flr_layout_bytes(uint64_t n_slots);
+int pya_launch_flr(const void *d_table, uint64_t n_slots, const uint8_t *d_cls, uint32_t reported_only, void *d_work, void *d_out,
+                   uint32_t *d_order, uint32_t *d_n_ranked, hipEvent_t *phase, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -901,6 +904,9 @@ static_assert(sizeof(pya_site_rollup) == 32 && offsetof(pya_site_rollup, best_ps
                   offsetof(pya_site_rollup, n_confident) == 16 && offsetof(pya_site_rollup, n_in_best) == 20 &&
                   offsetof(pya_site_rollup, best_ascore) == 24 && offsetof(pya_site_rollup, reserved) == 28,
               "pya_site_rollup is the 4 x 8 bytes rollup.hip addresses");
+static_assert(sizeof(pya_site_flr) == 32 && offsetof(pya_site_flr, n_decoy) == 4 && offsetof(pya_site_flr, err_sum) == 8 &&
+                  offsetof(pya_site_flr, flr) == 16 && offsetof(pya_site_flr, decoy_q) == 24,
+              "pya_site_flr is two 16-byte stores of flr.hip");
 /* pya_score_batch_named's queries and outputs (host arrays of the caller), nullptr for the other batch entry points */
 struct NamedReq {
     const int64_t *q_off;

@@ -308,6 +308,35 @@ class DevicePlan:
             self.scorer._raise(rc)
         return table
 
+    def rollup_flr(self, table, cls=None, reported_only=False):
+        """Site FLR of the roll-up table (of ``rollup_clear()`` / ``rollup()``), where it lies (``pya_rollup_flr``): ``cls`` a
+        ``torch.uint8`` device tensor of one byte per slot (0 target, 1 decoy, 2 left out) or None.  Returns device tensors
+        ``(records, order, n_ranked)``: ``torch.uint8 [n_slots, 32]`` (one ``pya_site_flr`` per slot; ``flr_records`` turns a
+        host copy into the structured array), the slots in order as ``torch.int32 [n_slots]`` (the bits of a uint32), and
+        ``torch.int32 [2]``: the number of ranked slots and the number of class bytes that are none of 0, 1, 2.  The
+        workspace is a torch tensor that lives for the call; everything is launched on torch's current stream and nothing
+        waits on the host.  The table is only read."""
+        torch = self._torch
+        if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != 32 or not table.is_contiguous() or not table.is_cuda:
+            raise ValueError("table must be a contiguous uint8 device tensor of shape (n_slots, 32)")
+        n = int(table.shape[0])
+        if cls is not None and (cls.dtype != torch.uint8 or tuple(cls.shape) != (n,) or not cls.is_contiguous() or not cls.is_cuda):
+            raise ValueError("cls must be a contiguous uint8 device tensor of %d entries" % n)
+        work_bytes = int(self._lib.pya_flr_workspace_bytes(n))
+        with torch.cuda.device(self.device):
+            work = torch.empty(max(work_bytes, 1), dtype=torch.uint8, device=self.device)
+            records = torch.empty((n, 32), dtype=torch.uint8, device=self.device)
+            order = torch.empty(n, dtype=torch.int32, device=self.device)
+            n_ranked = torch.empty(2, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device)
+        rc = self._lib.pya_rollup_flr(self.scorer._h, table.data_ptr(), n, None if cls is None else cls.data_ptr(),
+                                      _lib.PYA_FLR_REPORTED_ONLY if reported_only else 0, stream.cuda_stream, work.data_ptr(), work_bytes,
+                                      records.data_ptr(), order.data_ptr(), n_ranked.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        work.record_stream(stream)                 # (the caching allocator must not hand the workspace on before the stream is past it)
+        return records, order, n_ranked
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -359,6 +388,7 @@ SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)
 PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)
 RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)
 ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)
+FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)
 
 
 def evidence_rows(raw):
@@ -426,6 +456,15 @@ def rollup_records(raw):
     if a.ndim != 2 or a.shape[1] != ROLLUP_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, %d)" % ROLLUP_DTYPE.itemsize)
     return a.view(ROLLUP_DTYPE).reshape(a.shape[0])
+
+
+def flr_records(raw):
+    """A host copy of the records of ``DevicePlan.rollup_flr()`` (``.cpu().numpy()``, uint8 ``[n_slots, 32]``) as the
+    structured array ``PyAscore.rollup_flr`` returns; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != FLR_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % FLR_DTYPE.itemsize)
+    return a.view(FLR_DTYPE).reshape(a.shape[0])
 
 
 def named_records(raw):

@@ -8,6 +8,11 @@ slot of every record (negative: the record is left out), and the table (``ROLLUP
 include/pyascore_hip.h) has one record per slot: the best localisation probability any PSM gives the site and which PSM
 gives it, how many PSMs cover it, how many put it at or above the threshold, how many report it as the localisation, and the
 best Ascore of those.
+
+``flr`` turns such a table into false-localisation rates (``FLR_DTYPE``, the 32-byte ``pya_site_flr``): the slots sorted by
+``best_prob``, the expected errors ``1 - p`` accumulated down the list, and -- with decoy residues in the modification group,
+``decoy_classes`` -- the decoys above every cut as a q-value.  ``PyAscore.rollup_flr`` and ``DevicePlan.rollup_flr`` do the
+same on the device; the function here is the host form, with the same bytes.  ``cut`` names the slots reportable at a rate.
 """
 import numpy as np
 
@@ -17,6 +22,9 @@ from .named import site_residues
 ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)          # pya_site_rollup, 32 bytes
 assert ROLLUP_DTYPE.itemsize == 32
 NO_PSM = _lib.PYA_ROLLUP_NO_PSM
+FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)                # pya_site_flr, 32 bytes
+assert FLR_DTYPE.itemsize == 32
+TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
 def _text(peptide):
@@ -123,16 +131,108 @@ def _ascore_key(x):
     return np.where(bits >> 31 != 0, 0xFFFFFFFF - bits, bits + 0x80000000)
 
 
-def table(rollup, keys):
+def flr(table, cls=None, reported_only=False):
+    """``(records, order, n_ranked)`` of a roll-up table, on the host: ``records`` (``FLR_DTYPE``) one per slot, ``order``
+    (uint32) the ranked slots by ``best_prob`` descending (as bit patterns; equal bits by slot), then the others by index.
+    ``cls``: one byte per slot, ``TARGET`` / ``DECOY`` / ``LEFT_OUT``, or None: all targets; ``reported_only``: a slot no PSM
+    reports is not ranked.  A slot's ``rank``, ``n_decoy``, ``err_sum`` count the ranked slots at least as good as it, TIES
+    INCLUDED (every member of a tie group has the values at the group's end); ``flr`` is their mean expected error, ``decoy_q``
+    the smallest decoy / target ratio of this cut and every wider one.  The bytes are those of ``PyAscore.rollup_flr``."""
+    table = np.ascontiguousarray(table, ROLLUP_DTYPE)
+    n = table.size
+    if n > 0x7FFFFFFF:
+        raise ValueError("more than 2^31 - 1 slots")
+    ranked = table["n_psm"] != 0
+    if cls is not None:
+        cls = np.ascontiguousarray(cls, np.uint8)
+        if cls.shape != (n,):
+            raise ValueError("cls has one byte per slot")
+        if (cls > LEFT_OUT).any():
+            raise ValueError("class byte %d of slot %d is none of 0, 1, 2" % (cls[cls > LEFT_OUT][0], np.flatnonzero(cls > LEFT_OUT)[0]))
+        ranked &= cls < LEFT_OUT
+    if reported_only:
+        ranked &= table["n_in_best"] != 0
+    bits = table["best_prob"].view(np.uint64)
+    idx = np.flatnonzero(ranked)
+    idx = idx[np.argsort(~bits[idx], kind="stable")]                 # bits descending, slots ascending within equal bits
+    order = np.concatenate([idx, np.flatnonzero(~ranked)]).astype(np.uint32)
+    records = np.zeros(n, FLR_DTYPE)
+    m = idx.size
+    if m == 0:
+        return records, order, 0
+    sb = bits[idx]
+    with np.errstate(invalid="ignore"):
+        d = 1.0 - table["best_prob"][idx]
+        err = (np.where(d > 0.0, d, 0.0) * 4294967296.0).astype(np.uint64)
+    decoy = (cls[idx] == DECOY) if cls is not None else np.zeros(m, bool)
+    end = np.flatnonzero(np.concatenate([sb[1:] != sb[:-1], [True]]))      # last position of every tie group
+    group = np.searchsorted(end, np.arange(m))                             # the group of every position
+    rank = (end + 1).astype(np.uint64)
+    n_decoy = np.cumsum(decoy, dtype=np.uint64)[end]
+    err_sum = np.cumsum(err, dtype=np.uint64)[end]
+    ratio = n_decoy.astype(np.float64) / np.maximum(rank - n_decoy, 1).astype(np.float64)
+    q = np.minimum.accumulate(ratio[::-1])[::-1]
+    r = records[idx]
+    r["rank"], r["n_decoy"], r["err_sum"] = rank[group], n_decoy[group], err_sum[group]
+    r["flr"] = (err_sum.astype(np.float64) / (rank << np.uint64(32)).astype(np.float64))[group]
+    r["decoy_q"] = q[group]
+    records[idx] = r
+    return records, order, int(m)
+
+
+def decoy_classes(keys, peptides_or_letters=None, decoys="A"):
+    """``cls`` for ``flr``: ``DECOY`` for the slots on a decoy residue, ``TARGET`` for the others.  ``keys``: the
+    (peptide, 1-based position) keys of ``peptide_slots``; the residue is the letter of the key's peptide at its position --
+    or ``peptides_or_letters`` says it: one letter per slot (a str of ``len(keys)`` letters or a sequence of them), or a
+    mapping from a key's first element (a protein id, ...) to the sequence the position counts in.  ``decoys``: the decoy
+    letters of the modification group (Ala, Pro, Gly, ... beside STY)."""
+    cls = np.zeros(len(keys), np.uint8)
+    letters = peptides_or_letters
+    if letters is not None and not hasattr(letters, "get") and len(letters) != len(keys):
+        raise ValueError("%d letters for %d slots" % (len(letters), len(keys)))
+    for s, key in enumerate(keys):
+        if letters is None or hasattr(letters, "get"):
+            seq = _text(key[0] if letters is None else letters.get(key[0], ""))
+            pos = int(key[1])
+            letter = seq[pos - 1] if 1 <= pos <= len(seq) else ""
+        else:
+            letter = _text(letters[s])
+        if letter and letter in decoys:
+            cls[s] = DECOY
+    return cls
+
+
+def cut(records, order, n_ranked, flr=0.01):
+    """The slots reportable at model FLR ``flr``, best first: the longest prefix of the ranked slots whose cut has
+    ``records["flr"] <= flr`` (the rate does not decrease down the list, and a tie group is taken or left as a whole)."""
+    records = np.asarray(records, FLR_DTYPE)
+    ranked = np.asarray(order)[:int(n_ranked)].astype(np.int64)
+    return ranked[:int(np.searchsorted(records["flr"][ranked], float(flr), side="right"))].astype(np.uint32)
+
+
+def table(rollup, keys, flr=None):
     """Rows for a site-level report, one per slot that any PSM covers: dicts with ``key`` (``keys[s]``), ``best_prob``,
-    ``best_psm``, ``n_psm``, ``n_confident``, ``n_in_best`` and ``best_ascore`` (None when no PSM reports the site)."""
+    ``best_psm``, ``n_psm``, ``n_confident``, ``n_in_best`` and ``best_ascore`` (None when no PSM reports the site).
+    ``flr``: the ``(records, order, n_ranked)`` of ``flr`` / ``rollup_flr`` over the same table; the rows then come in
+    ``order`` and gain ``rank``, ``flr`` and ``decoy_q`` (None for a slot that is not ranked)."""
     rollup = np.asarray(rollup, ROLLUP_DTYPE)
     if len(keys) != rollup.size:
         raise ValueError("%d keys for %d slots" % (len(keys), rollup.size))
+    slots = np.flatnonzero(rollup["n_psm"])
+    if flr is not None:
+        records, order = np.asarray(flr[0], FLR_DTYPE), np.asarray(flr[1]).astype(np.int64)
+        if records.size != rollup.size or order.size != rollup.size:
+            raise ValueError("FLR records over another table")
+        slots = order[rollup["n_psm"][order] != 0]
     rows = []
-    for s in np.flatnonzero(rollup["n_psm"]):
+    for s in slots:
         r = rollup[s]
         rows.append(dict(key=keys[s], best_prob=float(r["best_prob"]), best_psm=int(r["best_psm"]), n_psm=int(r["n_psm"]),
                          n_confident=int(r["n_confident"]), n_in_best=int(r["n_in_best"]),
                          best_ascore=float(r["best_ascore"]) if r["n_in_best"] else None))
+        if flr is not None:
+            f = records[s]
+            on = int(f["rank"]) != 0
+            rows[-1].update(rank=int(f["rank"]) if on else None, flr=float(f["flr"]) if on else None,
+                            decoy_q=float(f["decoy_q"]) if on else None)
     return rows
