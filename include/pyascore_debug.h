@@ -67,6 +67,14 @@ int pya_debug_rollup_flr_timed(pya_handle *h, const pya_site_rollup *d_table, ui
                                void *hip_stream, void *d_work, uint64_t work_bytes, pya_site_flr *d_out, uint32_t *d_order,
                                uint32_t *d_n_ranked, float ms[PYA_FLR_PHASES + 1]);
 
+/* HIP events between the phases of the peptidoform stage (pya_plan_peptidoforms, pya_peptidoform_reduce and the batch calls
+ * of this handle) while `on`: pya_debug_last_peptidoform_ms waits for the last such call and gives ms[0] the entries, ms[1]
+ * the thirteen sort passes, ms[2] the segmented reduction, ms[3] the finish, ms[4] the whole stage.  PYA_ERR_STATE when no
+ * call with entries was timed.  For scripts/peptidoforms_probe.py.  No reference counterpart. */
+#define PYA_PFORM_PHASES 4
+int pya_debug_peptidoform_timing(pya_handle *h, int on);
+int pya_debug_last_peptidoform_ms(pya_handle *h, float ms[PYA_PFORM_PHASES + 1]);
+
 /* The signature list of PSM `psm` of the handle's retained batch (the last PYA_FLAG_KEEP call): the sig bits of its site
  * assignments in the order every kernel scores them in and the probability stage sums them in (pya_get_pep_scores* returns
  * the reference's sorted order instead).  *n = their number; sig_bits may be NULL with cap 0 to ask.  No reference

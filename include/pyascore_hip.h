@@ -103,6 +103,10 @@ extern "C" {
 #define PYA_FLAG_ROLLUP 512u /* pya_score_batch* / pya_score_batch_named: the site roll-up of the batch as well, into the */
                              /* slots lent by pya_set_rollup (pya_last_batch_rollup); the library runs the probability    */
                              /* stage for itself; pya_plan_create*: as PYA_FLAG_EVIDENCE (pya_plan_rollup)                */
+#define PYA_FLAG_PEPTIDOFORMS 1024u /* pya_score_batch* / pya_score_batch_named: the peptidoform list of the batch as well, */
+                                    /* over the groups lent by pya_set_peptidoforms (pya_last_batch_peptidoforms); the       */
+                                    /* library runs the probability stage for itself; pya_plan_create*: as                  */
+                                    /* PYA_FLAG_EVIDENCE (pya_plan_peptidoforms)                                            */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -355,6 +359,39 @@ typedef struct pya_site_flr {      /* 32 bytes; records compare as raw bytes */
                                    /* caller multiplies by the target-to-decoy residue frequency ratio, a positive      */
                                    /* constant that commutes with the minimum); 0 when no slot is a decoy              */
 } pya_site_flr;
+
+/* Peptidoform roll-up.  The site roll-up has one record per caller-keyed SITE; this is the second reduction across PSMs: one
+ * record per localised PEPTIDOFORM, a peptide together with the site assignment reported for it -- MaxQuant's
+ * modification-specific peptides, a "class I peptidoforms" list, the positional isomers seen for one peptide.  Its key holds
+ * best_sig, which exists only after the run, so the records are a sorted LIST, not a dense table.  The caller names the
+ * peptide of every PSM (group[n_psm], any non-negative int32, not dense; negative: the PSM is left out) and the number a PSM
+ * is known by (psm_id).  A PSM CONTRIBUTES when its pya_psm_prob.kind is PYA_SITE_SCORED and its group is not negative;
+ * PYA_SITE_NONE and PYA_SITE_OVER PSMs and PSMs that were set aside contribute nothing.  Per contributing PSM:
+ *   min_prob    the smallest with_prob among its residue records r with bit r of best_sig set, compared as the uint64 bit
+ *               pattern; exactly 1.0 for best_sig == 0;
+ *   min_ascore  the smallest of ascores[psm * max_k + c], c = 0 .. popcount(best_sig) - 1, under the total order of bit
+ *               patterns pya_site_rollup.best_ascore documents; +inf for popcount == 0.
+ * THE LIST is one record per distinct (group, sig_bits) among the contributing PSMs, ordered by group ascending as uint32,
+ * then by sig_bits ascending as uint64.  IT IS A FUNCTION OF THE MULTISET OF CONTRIBUTING (group, sig, min_prob, z,
+ * min_ascore, psm_id) TUPLES AND OF NOTHING ELSE: the stage does no floating-point arithmetic (it copies and compares bits and
+ * counts; only n_confident compares two doubles), so it does not depend on the order of the PSMs, on the route that scored a
+ * PSM, on shared or typed input, on chunk cuts, or on how the PSMs were spread over calls -- a list fed back as d_prev with
+ * more PSMs gives the bytes of one call over all of them, and two lists merge by pya_peptidoform_reduce or on the host:
+ * counts add, best_min_prob the max over bits (best_psm of the side with the larger bits, the smaller id on equal bits),
+ * best_z the min over bits, best_min_ascore the max under the total order, n_isomers recomputed.  A PSM is a record with
+ * n_psm == 1.  Counts are 32-bit and are not checked for overflow.  csrc/peptidoforms.hip. */
+#define PYA_PFORM_TILE 1024u       /* entries per workgroup and sort pass (the sizes a test of the stage wants to straddle) */
+typedef struct pya_peptidoform {   /* 48 bytes, three 16-byte stores; records compare as raw bytes */
+    uint64_t sig_bits;             /* the site assignment: best_sig of the PSMs behind the record              */
+    uint32_t group;                /* the caller's key of the peptide                                          */
+    uint32_t n_psm;                /* contributing PSMs                                                        */
+    uint32_t n_confident;          /* ... of them with min_prob >= threshold (compared as doubles)             */
+    uint32_t best_psm;             /* smallest psm_id among the PSMs whose min_prob has exactly the best bits  */
+    double best_min_prob;          /* max over the PSMs of min_prob, compared as uint64 bit patterns           */
+    double best_z;                 /* min over the PSMs of pya_psm_prob.z, compared as uint64 bit patterns     */
+    float best_min_ascore;         /* max over the PSMs of min_ascore, under the roll-up's total order of bits */
+    uint32_t n_isomers;            /* distinct sig_bits among the records of this group (same in all of them)  */
+} pya_peptidoform;
 
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
@@ -623,6 +660,37 @@ int pya_rollup_flr(pya_handle *h, const pya_site_rollup *d_table, uint64_t n_slo
 int pya_rollup_flr_host(pya_handle *h, const pya_site_rollup *table, uint64_t n_slots, const uint8_t *cls, uint32_t flags, pya_site_flr *out,
                         uint32_t *order, uint32_t *n_ranked);
 
+/* Lends the library what the NEXT batch call with PYA_FLAG_PEPTIDOFORMS lists its PSMs by (pya_peptidoform above):
+ * group[n_psm] and psm_id[n_psm] (or NULL: PSM i of the batch is known as i), host memory that must stay valid until that
+ * call returns; threshold, the "confident" cut of n_confident.  The lifetime rules are pya_set_rollup's: the loan ends with
+ * the first batch call with the flag that gets as far as its PSMs, whatever it returns; a batch of another size or a flag
+ * without a loan is PYA_ERR_ARG.  The batch call computes the probability records for itself and feeds every chunk's list
+ * into the next chunk's call as d_prev.  NULL group with n_psm != 0, or n_psm above 2^31 - 1: PYA_ERR_ARG. */
+int pya_set_peptidoforms(pya_handle *h, const int32_t *group, uint64_t n_psm, double threshold, const uint32_t *psm_id);
+/* The list of the last batch call on this handle that was given PYA_FLAG_PEPTIDOFORMS: *n its length, the first
+ * min(*n, cap) records into out (out may be NULL with cap == 0: the length alone).  PYA_ERR_STATE when the last batch was
+ * scored without the flag. */
+int pya_last_batch_peptidoforms(pya_handle *h, pya_peptidoform *out, uint64_t cap, uint64_t *n);
+/* The device bytes pya_plan_peptidoforms / pya_peptidoform_reduce need as their workspace for n_entries entries (PSMs of the
+ * plan + records of d_prev; records of d_a + d_b): keys double-buffered, the entries, the staged list, digit histograms, tile
+ * totals, about 133 bytes per entry; 0 for no entries (and above 2^31 - 1, which the calls refuse). */
+uint64_t pya_peptidoform_workspace_bytes(uint64_t n_entries);
+/* The same pipeline as pya_plan_peptidoforms without a plan, over one or two DEVICE arrays of records (d_b may be NULL with
+ * n_b == 0): the list over all of them.  The records may be in any order and may repeat keys; records with n_psm == 0 are
+ * skipped; the incoming n_isomers is ignored and recomputed.  Merging the lists of two ranks or two files is this call.
+ * d_out[cap] must not alias an input; d_n[2]: the true length of the list (when it is longer than cap the first cap records
+ * in order are written) and an error word, 0 here.  Stream-ordered on hip_stream, no host synchronisation and no allocation
+ * inside; the caller lends d_work (work_bytes >= pya_peptidoform_workspace_bytes(n_a + n_b); 16-byte aligned, as the record
+ * arrays are).  The inputs are only read.  No write lies outside d_out[0 .. cap), d_n[0 .. 2) and d_work[0 ..
+ * workspace_bytes).  No entries is valid and launches nothing (d_n is zeroed).  PYA_ERR_ARG, with nothing launched: more
+ * than 2^31 - 1 entries, a workspace that is too small, NULL or misaligned where an array is needed. */
+int pya_peptidoform_reduce(pya_handle *h, const pya_peptidoform *d_a, uint64_t n_a, const pya_peptidoform *d_b, uint64_t n_b, void *hip_stream,
+                           void *d_work, uint64_t work_bytes, pya_peptidoform *d_out, uint64_t cap, uint32_t *d_n);
+/* The same for HOST arrays: uploads, runs pya_peptidoform_reduce on the handle's stream with a workspace of its own and
+ * downloads.  *n: the length of the list; the first min(*n, cap) records into out. */
+int pya_peptidoform_reduce_host(pya_handle *h, const pya_peptidoform *a, uint64_t n_a, const pya_peptidoform *b, uint64_t n_b,
+                                pya_peptidoform *out, uint64_t cap, uint64_t *n);
+
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
 /* the same for a batch whose PSMs share spectra (pya_score_batch_shared: batch->peak_off describes n_spectra spectra,
@@ -709,6 +777,24 @@ int pya_plan_ranked(pya_plan *plan, const pya_results *d_res, void *hip_stream, 
 int pya_plan_rollup(pya_plan *plan, const pya_results *d_res, void *hip_stream, const pya_site_prob *d_site_probs,
                     const pya_psm_prob *d_psm_probs, const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id,
                     uint32_t psm_base, pya_site_rollup *d_table);
+/* The peptidoform list (pya_peptidoform above) over this plan's contributing PSMs and the n_prev records of an earlier list
+ * d_prev (only read, must not alias d_out; NULL with n_prev == 0): bytewise what one call over all the PSMs behind both would
+ * give.  d_site_probs / d_psm_probs as for pya_plan_rollup; d_group[n_psm] device memory; d_psm_id[n_psm] device memory, or
+ * NULL: PSM i is known as psm_base + i.  It reads best_sig and ascores (row stride max_k, not below the plan's largest
+ * n_of_mod) of d_res.  d_n[0]: the true number of peptidoforms -- when the list is longer than cap the first cap records in
+ * order are written, and no write ever lies at or past d_out + cap; d_n[1]: an error word, 0 when all is well: the number of
+ * PSMs whose best_sig names a residue record the PSM does not have or more residues than max_k (results that are not this
+ * plan's; such a PSM is left out).  Stream-ordered (csrc/peptidoforms.hip), no host synchronisation and no allocation inside:
+ * the caller lends d_work (work_bytes >= pya_peptidoform_workspace_bytes(n_psm + n_prev), 16-byte aligned as d_prev and d_out
+ * are); waits for the run as pya_plan_rollup does, valid until the plan is run again, may be called again.  No write lies
+ * outside d_out[0 .. cap), d_n[0 .. 2) and d_work[0 .. workspace_bytes).  PYA_ERR_ARG, with nothing launched: more than
+ * 2^31 - 1 entries, a workspace that is too small, NULL or misaligned where an array is needed; PYA_ERR_STATE before the
+ * plan's first run.  A plan of a handful of PSMs is created with PYA_FLAG_PEPTIDOFORMS (or another stage flag), as for
+ * pya_plan_rollup. */
+int pya_plan_peptidoforms(pya_plan *plan, const pya_results *d_res, void *hip_stream, const pya_site_prob *d_site_probs,
+                          const pya_psm_prob *d_psm_probs, const int32_t *d_group, double threshold, const uint32_t *d_psm_id,
+                          uint32_t psm_base, const pya_peptidoform *d_prev, uint64_t n_prev, void *d_work, uint64_t work_bytes,
+                          pya_peptidoform *d_out, uint64_t cap, uint32_t *d_n);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

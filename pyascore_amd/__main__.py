@@ -10,7 +10,9 @@ the runner-up localisation in the main one) and ``--probs`` (two more columns: t
 candidate residue and the posterior of the reported localisation) and ``--ranked FILE`` with ``--ranked_depth K`` (a table
 with a line per ranked site assignment: the K best localisations of every PSM, in order) and ``--site_table FILE`` with
 ``--site_table_threshold P`` (a site-level table over all PSMs, a line per peptide and position; ``--site_table_flr`` ranks
-its sites and adds false-localisation rates, ``--site_table_decoys LETTERS`` names decoy residues) are the additions."""
+its sites and adds false-localisation rates, ``--site_table_decoys LETTERS`` names decoy residues) and
+``--peptidoform_table FILE`` with ``--peptidoform_threshold P`` (a line per peptide and reported site assignment) are the
+additions."""
 import argparse
 import re
 import sys
@@ -87,6 +89,12 @@ def build_parser():
     p.add_argument("--site_table_decoys", type=str, default="", metavar="LETTERS",
                    help="with --site_table_flr: sites on these residues are decoys (meaningful when the letters are in "
                         "--residues, e.g. --residues STYA --site_table_decoys A)")
+    p.add_argument("--peptidoform_table", type=str, default=None, metavar="FILE",
+                   help="write the peptidoform table to FILE: one line per (unmodified peptide, reported site assignment) over all "
+                        "scored PSMs (Peptide, Positions, PSMs, Confident, BestScan, BestMinProb, BestPosterior, BestMinAscore, "
+                        "Isomers), reduced on the device; the main table does not change")
+    p.add_argument("--peptidoform_threshold", type=float, default=0.75, metavar="P",
+                   help="the smallest site probability from which a PSM counts as Confident in --peptidoform_table (default 0.75)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -149,6 +157,7 @@ def run(args, log=print):
     site_rows = [] if args.sites else None
     ranked_rows = [] if args.ranked else None
     site_table_rows = [] if args.site_table else None
+    peptidoform_rows = [] if args.peptidoform_table else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -158,7 +167,8 @@ def run(args, log=print):
                               evidence=args.evidence, ions=ion_rows, reported=args.reported, sites=site_rows,
                               probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth, site_table=site_table_rows,
                               site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
-                              site_table_decoys=args.site_table_decoys)
+                              site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
+                              peptidoform_threshold=args.peptidoform_threshold)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -167,6 +177,8 @@ def run(args, log=print):
         batch_cli.write_ranked_tsv(ranked_rows, args.ranked)
     if site_table_rows is not None:
         batch_cli.write_site_table_tsv(site_table_rows, args.site_table, flr=args.site_table_flr)
+    if peptidoform_rows is not None:
+        batch_cli.write_peptidoform_table_tsv(peptidoform_rows, args.peptidoform_table)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

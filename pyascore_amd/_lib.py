@@ -17,6 +17,9 @@ PYA_FLAG_SITES = 64
 PYA_FLAG_PROBS = 128
 PYA_FLAG_RANKED = 256
 PYA_FLAG_ROLLUP = 512
+PYA_FLAG_PEPTIDOFORMS = 1024
+PYA_PFORM_TILE = 1024        # entries per workgroup and sort pass of csrc/peptidoforms.hip
+PYA_PFORM_PHASES = 4         # (include/pyascore_debug.h: pya_debug_last_peptidoform_ms)
 PYA_ROLLUP_NO_PSM = 0xFFFFFFFF
 PYA_FLR_TARGET, PYA_FLR_DECOY, PYA_FLR_LEFT_OUT = 0, 1, 2
 PYA_FLR_REPORTED_ONLY = 1
@@ -152,6 +155,17 @@ class SiteFlr(C.Structure):
 
 
 assert C.sizeof(SiteFlr) == 32, "pya_site_flr is a 32-byte record"
+class Peptidoform(C.Structure):
+    """pya_peptidoform: one localised peptidoform -- a peptide (the caller's group) with one site assignment: how many PSMs
+    report it, how many confidently, the best of their minimum site probabilities and who has it, the best posterior
+    (1 / best_z), the best minimum Ascore, and how many assignments the peptide was seen with"""
+    _fields_ = [("sig_bits", C.c_uint64), ("group", C.c_uint32), ("n_psm", C.c_uint32), ("n_confident", C.c_uint32), ("best_psm", C.c_uint32),
+                ("best_min_prob", C.c_double), ("best_z", C.c_double), ("best_min_ascore", C.c_float), ("n_isomers", C.c_uint32)]
+
+
+assert C.sizeof(Peptidoform) == 48, "pya_peptidoform is a 48-byte record"
+PEPTIDOFORM_DTYPE = [("sig_bits", "<u8"), ("group", "<u4"), ("n_psm", "<u4"), ("n_confident", "<u4"), ("best_psm", "<u4"),
+                     ("best_min_prob", "<f8"), ("best_z", "<f8"), ("best_min_ascore", "<f4"), ("n_isomers", "<u4")]
 FLR_DTYPE = [("rank", "<u4"), ("n_decoy", "<u4"), ("err_sum", "<u8"), ("flr", "<f8"), ("decoy_q", "<f8")]
 
 PYA_F64, PYA_F32 = 0, 1
@@ -216,6 +230,15 @@ SYMBOLS = {
     "pya_last_batch_rollup": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_rollup_clear": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
     "pya_plan_rollup": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_uint64, C.c_double, _vp, C.c_uint32, _vp]),
+    "pya_set_peptidoforms": (C.c_int, [_vp, _vp, C.c_uint64, C.c_double, _vp]),
+    "pya_last_batch_peptidoforms": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "pya_peptidoform_workspace_bytes": (C.c_uint64, [C.c_uint64]),
+    "pya_peptidoform_reduce": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
+    "pya_peptidoform_reduce_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
+    "pya_plan_peptidoforms": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_double, _vp, C.c_uint32, _vp, C.c_uint64, _vp,
+                                        C.c_uint64, _vp, C.c_uint64, _vp]),
+    "pya_debug_peptidoform_timing": (C.c_int, [_vp, C.c_int]),        # (test-only)
+    "pya_debug_last_peptidoform_ms": (C.c_int, [_vp, _vp]),           # (test-only)
     "pya_flr_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "pya_rollup_flr": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp]),
     "pya_rollup_flr_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp]),

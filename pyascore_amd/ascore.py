@@ -79,6 +79,8 @@ assert RANKED_DTYPE.itemsize == 16
 ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)          # pya_site_rollup, 32 bytes
 FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)                # pya_site_flr, 32 bytes
 assert ROLLUP_DTYPE.itemsize == 32
+PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)    # pya_peptidoform, 48 bytes
+assert PEPTIDOFORM_DTYPE.itemsize == 48
 assert EVIDENCE_DTYPE.itemsize == 16
 ION_DTYPE = np.dtype(_lib.ION_DTYPE)                # pya_ion, 16 bytes
 assert ION_DTYPE.itemsize == 16
@@ -87,6 +89,27 @@ from .ranked import check_k as check_ranked_k  # noqa: E402
 _NO_U32 = np.zeros(0, np.uint32)
 
 _NO_F32 = np.zeros(0, np.float32)
+
+
+def _peptidoform_request(req, n_psm):
+    """``score_batch(peptidoforms=...)`` as contiguous arrays: dict(group int32, threshold, psm_id uint32 | None)"""
+    if not isinstance(req, dict):
+        raise ValueError("peptidoforms takes a dict: group and optionally threshold and psm_id")
+    unknown = set(req) - {"group", "threshold", "psm_id"}
+    if unknown or "group" not in req:
+        raise ValueError("peptidoforms takes group and optionally threshold and psm_id%s"
+                         % ("; unknown: " + ", ".join(sorted(unknown)) if unknown else ""))
+    group = np.asarray(req["group"])
+    if group.ndim != 1 or (group.size and group.dtype.kind not in "iu") or group.size != n_psm:
+        raise ValueError("peptidoforms: group is one integer per PSM")
+    if group.size and (group.max() > 0x7FFFFFFF or group.min() < -0x80000000):
+        raise ValueError("peptidoforms: group does not fit int32")
+    psm_id = req.get("psm_id")
+    if psm_id is not None:
+        psm_id = np.ascontiguousarray(psm_id, np.uint32)
+        if psm_id.shape != (n_psm,):
+            raise ValueError("peptidoforms: psm_id has one entry per PSM")
+    return dict(group=np.ascontiguousarray(group, np.int32), threshold=float(req.get("threshold", 0.75)), psm_id=psm_id)
 
 
 def _rollup_request(rollup, n_psm):
@@ -347,7 +370,7 @@ class PyAscore:
             self._batch_n = 1
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
-                    site_sig_cap=None, probs=False, ranked=None, rollup=None):
+                    site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -414,6 +437,11 @@ class PyAscore:
         back, so the caller always sees input order (with ``keep=True`` such a batch is scored in its expanded form
         instead: the retained records are addressed by PSM number).
 
+        ``peptidoforms=dict(group=..., threshold=0.75, psm_id=None)`` adds ``peptidoforms`` (``PEPTIDOFORM_DTYPE``, the
+        48-byte ``pya_peptidoform``): one record per distinct (group, best_sig) of the scored PSMs, ordered by group then
+        sig_bits, reduced on the device (``group`` is one non-negative int32 per PSM, e.g. from
+        ``pyascore_amd.rollup.peptide_groups``; negative: the PSM is left out).  ``best_psm`` is in the caller's numbering.
+
         Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
         m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
@@ -421,12 +449,14 @@ class PyAscore:
         float64 intensities."""
         ranked_k = None if ranked is None or ranked is False else check_ranked_k(ranked)
         roll = None if rollup is None else _rollup_request(rollup, int(batch["n_psm"]))
+        pform = None if peptidoforms is None else _peptidoform_request(peptidoforms, int(batch["n_psm"]))
         if batch.get("spec_of") is not None:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
-                                        named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup)
+                                        named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup,
+                                        peptidoforms=peptidoforms)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -446,10 +476,15 @@ class PyAscore:
                     ids = perm.astype(np.uint32) if roll["psm_id"] is None else roll["psm_id"][perm]
                     roll_moved = dict(slot=roll["slot"][take], n_slots=roll["n_slots"], threshold=roll["threshold"], psm_id=ids,
                                       site_off=new_off)
+                pform_moved = None
+                if pform is not None:        # the groups travel with their PSMs, the ids say who they were
+                    pform_moved = dict(group=pform["group"][perm], threshold=pform["threshold"],
+                                       psm_id=perm.astype(np.uint32) if pform["psm_id"] is None else pform["psm_id"][perm])
                 try:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
-                                           site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved)
+                                           site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved,
+                                           peptidoforms=pform_moved)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
@@ -457,6 +492,7 @@ class PyAscore:
                 prob_csr = (res["site_off"], res.pop("site_probs")) if probs else None
                 res.pop("site_off", None)
                 table = res.pop("rollup", None)         # (per slot, not per PSM)
+                forms = res.pop("peptidoforms", None)   # (per peptidoform)
                 per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
                 if moved is not None:
@@ -481,6 +517,8 @@ class PyAscore:
                     res["site_probs"] = prob_csr[1][take]
                 if table is not None:
                     res["rollup"] = table
+                if forms is not None:
+                    res["peptidoforms"] = forms
                 if res.get("status_message"):
                     res["status_message"] = _renumber_psm(res["status_message"], perm)
                 return res
@@ -538,6 +576,8 @@ class PyAscore:
                     raise ValueError("rollup: %d slots for a batch without residue records" % roll["slot"].size)
                 out["rollup"] = np.zeros(roll["n_slots"], ROLLUP_DTYPE)
                 out["rollup"]["best_psm"] = _lib.PYA_ROLLUP_NO_PSM
+            if pform is not None:
+                out["peptidoforms"] = np.zeros(0, PEPTIDOFORM_DTYPE)
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -562,10 +602,10 @@ class PyAscore:
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
             (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0) | \
-            (_lib.PYA_FLAG_ROLLUP if roll is not None else 0)
+            (_lib.PYA_FLAG_ROLLUP if roll is not None else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if pform is not None else 0)
         # for this call; the handle's own settings come back
         cap_before = k_before = None
-        if (sites or probs or ranked_k or roll is not None) and site_sig_cap is not None:
+        if (sites or probs or ranked_k or roll is not None or pform is not None) and site_sig_cap is not None:
             cap_before = int(self._lib.pya_get_site_sig_cap(self._h))
             self._lib.pya_set_site_sig_cap(self._h, int(site_sig_cap))
         if ranked_k:
@@ -575,6 +615,8 @@ class PyAscore:
             # (the library borrows the arrays of `roll` for the call: they live until it returns)
             rc = 0 if roll is None else self._lib.pya_set_rollup(self._h, _as_ptr(roll["slot"]), roll["slot"].size, roll["n_slots"],
                                                                  roll["threshold"], _as_ptr(roll["psm_id"]))
+            if not rc and pform is not None:
+                rc = self._lib.pya_set_peptidoforms(self._h, _as_ptr(pform["group"]), n, pform["threshold"], _as_ptr(pform["psm_id"]))
             if not rc:
                 rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         finally:
@@ -622,7 +664,28 @@ class PyAscore:
             rc = self._lib.pya_last_batch_rollup(self._h, _as_ptr(out["rollup"]), roll["n_slots"])
             if rc:
                 self._raise(rc)
+        if pform is not None:
+            count = C.c_uint64(0)
+            out["peptidoforms"] = np.zeros(n, PEPTIDOFORM_DTYPE)       # (a list is no longer than the batch)
+            rc = self._lib.pya_last_batch_peptidoforms(self._h, _as_ptr(out["peptidoforms"]), n, C.byref(count))
+            if rc:
+                self._raise(rc)
+            out["peptidoforms"] = out["peptidoforms"][:count.value].copy()
         return out
+
+    def peptidoform_reduce(self, a, b=None):
+        """The peptidoform list over one or two arrays of ``PEPTIDOFORM_DTYPE`` records, reduced on the device
+        (``pya_peptidoform_reduce_host``): the records may be in any order and may repeat keys, records with ``n_psm == 0``
+        are skipped, ``n_isomers`` is recomputed.  Merging the lists of two files or two ranks is this call;
+        ``pyascore_amd.rollup.merge_peptidoforms`` gives the same bytes on the host."""
+        a = np.ascontiguousarray(a, PEPTIDOFORM_DTYPE).reshape(-1)
+        b = np.zeros(0, PEPTIDOFORM_DTYPE) if b is None else np.ascontiguousarray(b, PEPTIDOFORM_DTYPE).reshape(-1)
+        total = a.size + b.size
+        out, count = np.zeros(total, PEPTIDOFORM_DTYPE), C.c_uint64(0)
+        rc = self._lib.pya_peptidoform_reduce_host(self._h, _as_ptr(a), a.size, _as_ptr(b), b.size, _as_ptr(out), total, C.byref(count))
+        if rc:
+            self._raise(rc)
+        return out[:count.value].copy()
 
     def site_offsets(self, batch, skip_invalid=False):
         """``site_off`` (int64 ``[n_psm + 1]``) of a batch BEFORE it is scored: where the residue records of every PSM will

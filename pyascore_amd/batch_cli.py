@@ -41,6 +41,9 @@ RANKED_COLUMNS = ("Scan", "Hit", "Rank", "LocalizedSequence", "PepScore", "Delta
 SITE_TABLE_COLUMNS = ("Peptide", "Position", "Residue", "BestProb", "BestScan", "PSMs", "Confident", "InBest", "BestAscore")
 # ``--site_table_flr``: three more columns of the ``--site_table`` table (pya_site_flr), its rows best site first
 SITE_TABLE_FLR_COLUMNS = ("Rank", "FLR", "DecoyQ")
+# ``--peptidoform_table FILE``: one line per (peptide, reported site assignment) over all PSMs (pya_peptidoform)
+PEPTIDOFORM_TABLE_COLUMNS = ("Peptide", "Positions", "PSMs", "Confident", "BestScan", "BestMinProb", "BestPosterior", "BestMinAscore",
+                             "Isomers")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -153,7 +156,7 @@ def pack_hits(picked, scans):
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
-             site_table_flr=False, site_table_decoys=""):
+             site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -176,7 +179,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``site_table_threshold`` being the "confident" cut; the main table does not change.  ``site_table_flr=True``: the rows
     come best site first and end with three more fields (``SITE_TABLE_FLR_COLUMNS``) -- the number of sites at least as good,
     the model-based false-localisation rate of that cut, and the decoy q-value --, computed on the device over the table;
-    ``site_table_decoys``: the letters of the modification group that are decoy residues (sites on them count as decoys)."""
+    ``site_table_decoys``: the letters of the modification group that are decoy residues (sites on them count as decoys).
+    ``peptidoform_table``: a list that receives one ``peptidoform_table_fields`` row per (unmodified peptide, reported site
+    assignment) over ALL scored PSMs (``write_peptidoform_table_tsv``), reduced on the device; ``peptidoform_threshold`` is
+    the "confident" cut on a PSM's smallest site probability; the main table does not change."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -192,6 +198,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     stages = dict(skip_invalid=True, evidence=evidence, ions=ions is not None, named=named, sites=sites is not None, probs=probs,
                   ranked=ranked_depth if ranked is not None else None)
     keys = None
+    form_keys = None
+    if peptidoform_table is not None:
+        group, _, form_keys = site_rollup.peptide_groups([p["peptide"] for p in picked])
+        stages["peptidoforms"] = dict(group=group, threshold=float(peptidoform_threshold))
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything
@@ -233,6 +243,9 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         if site_table_flr:
             flr = ascore.rollup_flr(res["rollup"], site_rollup.decoy_classes(keys, decoys=site_table_decoys) if site_table_decoys else None)
         site_table.extend(site_table_fields(row, scans) for row in site_rollup.table(res["rollup"], keys, flr=flr))
+    if peptidoform_table is not None:
+        peptidoform_table.extend(peptidoform_table_fields(row, scans)
+                                 for row in site_rollup.peptidoform_table(res["peptidoforms"], form_keys, residues=residues))
     rows = []
     hit = 0
     for i, psm in enumerate(picked):
@@ -303,6 +316,26 @@ def write_site_table_tsv(site_table_rows, path, flr=False):
     with open(path, "w") as out:
         out.write("\t".join(SITE_TABLE_COLUMNS + (SITE_TABLE_FLR_COLUMNS if wide else ())) + "\n")
         for row in site_table_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
+
+
+def peptidoform_table_fields(row, scans):
+    """One row of ``pyascore_amd.rollup.peptidoform_table`` as the fields of the ``--peptidoform_table`` table: Peptide,
+    Positions -- the modified positions, 1-based, joined by ``;`` --, PSMs -- scored PSMs that report this assignment --,
+    Confident -- those whose smallest site probability is at or above the threshold --, BestScan -- the scan with the best
+    such probability (the first PSM of the input among equals) --, BestMinProb, BestPosterior (``1 / best_z``), BestMinAscore
+    and Isomers -- the assignments the peptide was seen with."""
+    return [row["peptide"], ";".join(str(p) for p in row["sites"]), str(row["n_psm"]), str(row["n_confident"]),
+            scans[row["best_psm"]] if row["best_psm"] < len(scans) else "", repr(row["best_min_prob"]), repr(row["best_posterior"]),
+            str(np.float32(row["best_min_ascore"])), str(row["n_isomers"])]
+
+
+def write_peptidoform_table_tsv(peptidoform_rows, path):
+    """The ``--peptidoform_table`` table: the rows ``localize(..., peptidoform_table=[])`` collected, under
+    ``PEPTIDOFORM_TABLE_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(PEPTIDOFORM_TABLE_COLUMNS) + "\n")
+        for row in peptidoform_rows:
             out.write("\t".join("%s" % f for f in row) + "\n")
 
 

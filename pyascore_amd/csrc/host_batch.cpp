@@ -338,6 +338,86 @@ static int rollup_end(pya_handle *h, const pya_handle::RollupLoan &loan) {
     return PYA_OK;
 }
 
+/* PYA_FLAG_PEPTIDOFORMS: the loan of pya_set_peptidoforms becomes the call's; the two device lists that live for the call
+ * (a list cannot be longer than the batch has PSMs) are sized here */
+static int pform_begin(pya_handle *h, pya_handle::PformLoan *loan, uint64_t n_psm) {
+    *loan = h->pform_loan;
+    h->pform_loan = pya_handle::PformLoan{};                  /* (the loan ends with this call, whatever it returns) */
+    if (!loan->set) return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_PEPTIDOFORMS without groups: call pya_set_peptidoforms before the batch call");
+    if (loan->n_psm != n_psm)
+        return h->fail(PYA_ERR_ARG, -1, "pya_set_peptidoforms lent the groups of %llu PSMs, the batch has %llu", (unsigned long long)loan->n_psm,
+                       (unsigned long long)n_psm);
+    HIPCHK(h, hipSetDevice(h->device));
+    for (auto &d : h->d_pform)
+        if (d.n < n_psm || !d.p) HIPCHK(h, d.alloc((size_t)n_psm));
+    if (!h->d_pform_n.p) HIPCHK(h, h->d_pform_n.alloc(2));
+    h->pform_len = 0;
+    h->pform_cur = 0;
+    return PYA_OK;
+}
+
+/* ... the plan's slice of the caller's groups and ids on its way to the device on `st`, in front of the plan's run as the
+ * roll-up's slots are (rollup_upload says why), and the workspace for the plan's PSMs and the list so far, which the host
+ * knows: the chunk before has been waited for */
+static int pform_upload(pya_handle *h, pya_plan *p, const pya_handle::PformLoan &loan, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0) return PYA_OK;
+    std::vector<int64_t> off(n + 1);
+    const int rc = pya_plan_site_offsets(p, off.data());
+    if (rc) return rc;
+    p->pform_records = (uint64_t)off[n];
+    HIPCHK(h, p->d_pform_group.alloc((size_t)n));
+    HIPCHK(h, hipMemcpyAsync(p->d_pform_group.p, loan.group + lo, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    if (loan.psm_id) {
+        HIPCHK(h, p->d_pform_id.alloc((size_t)n));
+        HIPCHK(h, hipMemcpyAsync(p->d_pform_id.p, loan.psm_id + lo, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    const uint64_t need = pya_peptidoform_workspace_bytes(n + h->pform_len);
+    if (h->d_pform_work.n < need || !h->d_pform_work.p) HIPCHK(h, h->d_pform_work.alloc((size_t)need));
+    return PYA_OK;
+}
+
+/* ... the stage of the plan behind its probability stage on `st` (the stage of PYA_FLAG_PROBS or of the roll-up when the call
+ * has one, its own otherwise): the list so far goes in as d_prev, the other list takes the result, its length follows */
+static int pform_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, const pya_handle::PformLoan &loan, uint32_t flags, uint64_t lo,
+                            hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0) return PYA_OK;
+    if (!(flags & (PYA_FLAG_PROBS | PYA_FLAG_ROLLUP))) {
+        HIPCHK(h, p->d_prob_sites.alloc((size_t)std::max<uint64_t>(p->pform_records, 1)));
+        HIPCHK(h, p->d_prob_psms.alloc((size_t)n));
+        const int rc = pya_plan_probs(p, d_out, st, h->site_sig_cap, p->d_prob_sites.p, p->d_prob_psms.p);
+        if (rc) return rc;
+    }
+    const int cur = h->pform_cur;
+    const int rc = pya_plan_peptidoforms(p, d_out, st, p->d_prob_sites.p, p->d_prob_psms.p, p->d_pform_group.p, loan.threshold,
+                                         loan.psm_id ? p->d_pform_id.p : nullptr, (uint32_t)lo, h->d_pform[cur].p, h->pform_len, h->d_pform_work.p,
+                                         h->d_pform_work.n, h->d_pform[cur ^ 1].p, h->d_pform[cur ^ 1].n, h->d_pform_n.p);
+    if (rc) return rc;
+    h->pform_cur = cur ^ 1;
+    HIPCHK(h, hipMemcpyAsync(h->pform_n_host, h->d_pform_n.p, sizeof h->pform_n_host, hipMemcpyDeviceToHost, st));
+    return PYA_OK;
+}
+
+/* ... once the plan's stream has been waited for: the length of the list, and the error word */
+static int pform_collect(pya_handle *h, pya_plan *p, uint64_t lo) {
+    if (p->n_psm == 0) return PYA_OK;
+    h->pform_len = h->pform_n_host[0];
+    if (h->pform_n_host[1])
+        return h->fail(PYA_ERR_STATE, (int64_t)lo, "peptidoforms: %u PSMs from %llu have a best_sig that does not fit their residue records",
+                       h->pform_n_host[1], (unsigned long long)lo);
+    return PYA_OK;
+}
+
+/* ... and the end of the call: the list comes to the host */
+static int pform_end(pya_handle *h) {
+    h->pform_host.resize((size_t)h->pform_len);
+    if (h->pform_len)
+        HIPCHK(h, hipMemcpy(h->pform_host.data(), h->d_pform[h->pform_cur].p, (size_t)h->pform_len * sizeof(pya_peptidoform), hipMemcpyDeviceToHost));
+    h->pform_valid = true;
+    return PYA_OK;
+}
+
 /* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
  * counts, [n_q * n_top] scores -- zeroed */
 static int named_host_block(pya_handle *h, uint64_t n_q) {
@@ -407,7 +487,8 @@ static void named_deliver(pya_handle *h, const NamedReq *nq, uint64_t lo, uint64
  * stream.  A call of any size completes; it never fails for lack of workspace. */
 static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp,
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
-                               const uint8_t *pre_sites, const NamedReq *nq, const pya_handle::RollupLoan &loan) {
+                               const uint8_t *pre_sites, const NamedReq *nq, const pya_handle::RollupLoan &loan,
+                               const pya_handle::PformLoan &pf_loan) {
     const size_t nchunk = cuts.size() - 1;
     const uint64_t n_q = nq ? (uint64_t)nq->q_off[b->n_psm] : 0;
     /* the spectra [first, last) of chunk c: its PSMs' own unless spectra are shared -- then from the first PSM's to the last
@@ -511,6 +592,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
         if (nq && (rc = named_upload(h, p, nq, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, lo, h->run_stream))) return finish(rc);
         rc = pya_plan_run_typed(p, &d_sp, h->run_stream, &d_out);
         if (rc) return finish(rc);
         /* status + results are adjacent in the arena: one asynchronous copy into pinned memory */
@@ -533,6 +615,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_PROBS) && (rc = probs_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_RANKED) && (rc = ranked_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_behind_run(h, p, &d_out, loan, flags, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_behind_run(h, p, &d_out, pf_loan, flags, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -574,9 +657,11 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if (nq) named_deliver(h, nq, lo, lo + n, n_q);
         /* (a slot outside the table: the report of this chunk's roll-up, whose kernels the event above waited for) */
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_report(p, lo))) return finish(rc);
+        if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_collect(h, p, lo))) return finish(rc);
         cur = std::move(next);
     }
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_end(h, loan))) return finish(rc);
+    if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_end(h))) return finish(rc);
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
     h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
     /* (chunks behind the last PSM with records: their offsets stay at the total) */
@@ -599,10 +684,16 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->probs_valid = false;
     h->ranked_valid = false;
     h->rollup_valid = false;
+    h->pform_valid = false;
     pya_handle::RollupLoan loan;
     if (flags & PYA_FLAG_ROLLUP) {
         const int rc_ru = rollup_begin(h, &loan);
         if (rc_ru) return rc_ru;
+    }
+    pya_handle::PformLoan pf_loan;
+    if (flags & PYA_FLAG_PEPTIDOFORMS) {
+        const int rc_pf = pform_begin(h, &pf_loan, b->n_psm);
+        if (rc_pf) return rc_pf;
     }
     if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
     if (flags & PYA_FLAG_SITES) h->sites_off.assign(b->n_psm + 1, 0);
@@ -617,6 +708,10 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         h->ranked_valid = (flags & PYA_FLAG_RANKED) != 0;
         h->ranked_n = 0;
         h->ranked_batch_k = h->ranked_k;
+        if (flags & PYA_FLAG_PEPTIDOFORMS) {
+            const int rc_pf = pform_end(h);
+            if (rc_pf) return rc_pf;
+        }
         return (flags & PYA_FLAG_ROLLUP) ? rollup_end(h, loan) : PYA_OK;
     }
     uint32_t types = 0;
@@ -664,8 +759,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_rk = ranked_host_block(h, b);
         if (rc_rk) return rc_rk;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED or _ROLLUP takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP or _PEPTIDOFORMS takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -708,7 +803,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
             }
             cuts.push_back(b->n_psm);
             h->last_chunks = cuts.size() - 1;
-            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan);
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan, pf_loan);
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -756,6 +851,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     const pya_typed_spectra d_sp = {p->d_mz.p, p->d_inten.p, sp.mz_type, sp.intensity_type};
     if (nq && (rc = named_upload(h, p, nq, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, 0, nullptr))) return rc;
+    if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, 0, nullptr))) return rc;
     rc = pya_plan_run_typed(p, &d_sp, nullptr, &d_out);
     if (rc) return rc;
     if (p->d2h_bytes <= kStageLimit) {
@@ -820,6 +916,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         if ((rc = rollup_report(p, 0))) return rc;
         if ((rc = rollup_end(h, loan))) return rc;
     }
+    if (flags & PYA_FLAG_PEPTIDOFORMS) {
+        if ((rc = pform_behind_run(h, p, &d_out, pf_loan, flags, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        if ((rc = pform_collect(h, p, 0))) return rc;
+        if ((rc = pform_end(h))) return rc;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -844,6 +946,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->probs_valid = false;
     h->ranked_valid = false;
     h->rollup_valid = false;
+    h->pform_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);

@@ -146,6 +146,11 @@ int pya_launch_rollup(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec,
 uint64_t pya_flr_layout_bytes(uint64_t n_slots);
 int pya_launch_flr(const void *d_table, uint64_t n_slots, const uint8_t *d_cls, uint32_t reported_only, void *d_work, void *d_out,
                    uint32_t *d_order, uint32_t *d_n_ranked, hipEvent_t *phase, hipStream_t stream);
+uint64_t pya_pform_layout_bytes(uint64_t n_entries);
+int pya_launch_pform(const int64_t *d_site_off, uint64_t n_psm, const void *d_site_probs, const void *d_psm_probs, const int32_t *d_group,
+                     double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const uint64_t *best_sig, const float *ascores, uint32_t max_k,
+                     const void *d_src0, uint64_t n0, const void *d_src1, uint64_t n1, void *d_work, void *d_out, uint64_t cap, uint32_t *d_n,
+                     hipEvent_t *phase, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -399,6 +404,27 @@ struct pya_handle {
     bool rollup_cleared = false;
     std::vector<pya_site_rollup> rollup_host;
     bool rollup_valid = false;
+    /* PYA_FLAG_PEPTIDOFORMS: what pya_set_peptidoforms lent for the next batch call, the two device lists of the call (a
+     * chunk reads the one the chunk before wrote), the workspace and the two words of the stage, the length of the current
+     * list as the host knows it, and the list of the last such call on the host */
+    struct PformLoan {
+        const int32_t *group = nullptr;
+        const uint32_t *psm_id = nullptr;
+        uint64_t n_psm = 0;
+        double threshold = 0.;
+        bool set = false;
+    } pform_loan;
+    DevBuf<pya_peptidoform> d_pform[2];
+    DevBuf<unsigned char> d_pform_work;
+    DevBuf<uint32_t> d_pform_n;
+    uint32_t pform_n_host[2] = {0u, 0u};
+    uint64_t pform_len = 0;
+    int pform_cur = 0;
+    std::vector<pya_peptidoform> pform_host;
+    bool pform_valid = false;
+    /* pya_debug_peptidoform_timing: events between the phases of the stage's next calls (include/pyascore_debug.h) */
+    bool pform_timed = false, pform_ev_recorded = false;
+    hipEvent_t pform_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -758,6 +784,10 @@ struct pya_plan {
     bool rollup_asked = false;
     DevBuf<int32_t> d_rollup_slot;
     DevBuf<uint32_t> d_rollup_id;
+    /* a pya_score_batch plan's slice of the caller's groups and ids (PYA_FLAG_PEPTIDOFORMS), and its residue records */
+    DevBuf<int32_t> d_pform_group;
+    DevBuf<uint32_t> d_pform_id;
+    uint64_t pform_records = 0;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -880,6 +910,14 @@ int check_spec_of(pya_handle *h, uint64_t n_psm, const uint32_t *spec_of, uint64
 int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, const SpecShare *sh, pya_plan **out);
 int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid = false);
 int rollup_report(pya_plan *p, uint64_t psm_lo);
+/* host_peptidoforms.cpp: everything the peptidoform calls refuse, before anything is launched (*run: there are entries), and
+ * the stage on `st` behind it: d_n zeroed, then the launches of csrc/peptidoforms.hip */
+int pform_check(pya_handle *h, const char *who, uint64_t n_first, const void *d_second, uint64_t n_second, const void *d_work, uint64_t work_bytes,
+                const void *d_out, uint64_t cap, const uint32_t *d_n, bool *run);
+int pform_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const void *d_site_probs, const void *d_psm_probs, const int32_t *d_group,
+              double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const uint64_t *best_sig, const float *ascores, uint32_t max_k,
+              const void *d_src0, uint64_t n0, const void *d_src1, uint64_t n1, void *d_work, void *d_out, uint64_t cap, uint32_t *d_n, bool run,
+              hipStream_t st);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");
@@ -904,6 +942,11 @@ static_assert(sizeof(pya_site_rollup) == 32 && offsetof(pya_site_rollup, best_ps
                   offsetof(pya_site_rollup, n_confident) == 16 && offsetof(pya_site_rollup, n_in_best) == 20 &&
                   offsetof(pya_site_rollup, best_ascore) == 24 && offsetof(pya_site_rollup, reserved) == 28,
               "pya_site_rollup is the 4 x 8 bytes rollup.hip addresses");
+static_assert(sizeof(pya_peptidoform) == 48 && offsetof(pya_peptidoform, group) == 8 && offsetof(pya_peptidoform, n_psm) == 12 &&
+                  offsetof(pya_peptidoform, n_confident) == 16 && offsetof(pya_peptidoform, best_psm) == 20 &&
+                  offsetof(pya_peptidoform, best_min_prob) == 24 && offsetof(pya_peptidoform, best_z) == 32 &&
+                  offsetof(pya_peptidoform, best_min_ascore) == 40 && offsetof(pya_peptidoform, n_isomers) == 44,
+              "pya_peptidoform is the three 16-byte stores of peptidoforms.hip");
 static_assert(sizeof(pya_site_flr) == 32 && offsetof(pya_site_flr, n_decoy) == 4 && offsetof(pya_site_flr, err_sum) == 8 &&
                   offsetof(pya_site_flr, flr) == 16 && offsetof(pya_site_flr, decoy_q) == 24,
               "pya_site_flr is two 16-byte stores of flr.hip");

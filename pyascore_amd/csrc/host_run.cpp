@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -843,6 +843,41 @@ int pya_plan_rollup(pya_plan *p, const pya_results *r, void *hip_stream, const p
     HIPCHK(h, hipEventRecord(p->ev_rollup, st));
     p->rollup_asked = true;
     return PYA_OK;
+}
+
+/* The peptidoform stage (csrc/peptidoforms.hip): like the roll-up it takes nothing of stage_behind_run but the wait for the
+ * run, and the offsets are the site stage's.  The argument checks and the launches are host_peptidoforms.cpp's. */
+int pya_plan_peptidoforms(pya_plan *p, const pya_results *r, void *hip_stream, const pya_site_prob *d_site_probs, const pya_psm_prob *d_psm_probs,
+                          const int32_t *d_group, double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const pya_peptidoform *d_prev,
+                          uint64_t n_prev, void *d_work, uint64_t work_bytes, pya_peptidoform *d_out, uint64_t cap, uint32_t *d_n) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    bool run;
+    const int rc = pform_check(h, "pya_plan_peptidoforms", p->n_psm, d_prev, n_prev, d_work, work_bytes, d_out, cap, d_n, &run);
+    if (rc) return rc;
+    uint64_t n_rec = 0;
+    if (p->n_psm) {
+        if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_peptidoforms: the plan has not been run");
+        site_offsets(p);
+        n_rec = (uint64_t)p->site_off[p->n_psm];
+        if (!d_psm_probs || !d_group || (n_rec && !d_site_probs) || !r->best_sig || !r->ascores)
+            return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_peptidoforms");
+        if (r->max_k < p->max_k)
+            return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)", r->max_k, p->max_k);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (p->n_psm) {
+        if (st != p->last_stream) {                             /* (behind the run, as pya_plan_rollup waits for it) */
+            if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
+            HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
+            HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
+        }
+        const int rc_off = site_offsets_on_device(p, st);
+        if (rc_off) return rc_off;
+    }
+    return pform_run(h, p->n_psm ? p->d_site_off.p : nullptr, p->n_psm, d_site_probs, d_psm_probs, d_group, threshold, d_psm_id, psm_base,
+                     r->best_sig, r->ascores, r->max_k, d_prev, n_prev, nullptr, 0, d_work, d_out, cap, d_n, run, st);
 }
 
 namespace {

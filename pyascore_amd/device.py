@@ -28,10 +28,12 @@ class DevicePlan:
     the caller names (``pya_plan_named``).  ``sites()`` / ``sites=True``: the same for the site tables
     (``pya_plan_site_offsets``, ``pya_plan_sites``).  ``probs()`` / ``probs=True``: the same for the site probabilities
     (``pya_plan_probs``).  ``ranked()`` / ``ranked=True``: the same for the ranked localisations (``pya_plan_ranked``).  ``rollup()`` /
-    ``rollup=True``: the probability records rolled into a table of the caller's slots (``pya_plan_rollup``)."""
+    ``rollup=True``: the probability records rolled into a table of the caller's slots (``pya_plan_rollup``).
+    ``peptidoforms()`` / ``peptidoforms=True``: the PSMs collapsed onto one record per (group, best_sig)
+    (``pya_plan_peptidoforms``); ``peptidoform_reduce()`` merges such lists."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
-                 ranked=False, rollup=False):
+                 ranked=False, rollup=False, peptidoforms=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -62,7 +64,7 @@ class DevicePlan:
         flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
             (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0) | \
-            (_lib.PYA_FLAG_ROLLUP if rollup else 0)
+            (_lib.PYA_FLAG_ROLLUP if rollup else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if peptidoforms else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -337,6 +339,74 @@ class DevicePlan:
         work.record_stream(stream)                 # (the caching allocator must not hand the workspace on before the stream is past it)
         return records, order, n_ranked
 
+    def _pform_records(self, t, what):
+        torch = self._torch
+        if t is None:
+            return None, 0
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != 48 or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("%s must be a contiguous uint8 device tensor of shape (n, 48)" % what)
+        return t, int(t.shape[0])
+
+    def _pform_buffers(self, n_entries, cap):
+        torch = self._torch
+        cap = n_entries if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("cap must not be negative")
+        work_bytes = int(self._lib.pya_peptidoform_workspace_bytes(n_entries))
+        with torch.cuda.device(self.device):
+            work = torch.empty(max(work_bytes, 1), dtype=torch.uint8, device=self.device)
+            records = torch.empty((cap, 48), dtype=torch.uint8, device=self.device)
+            n = torch.empty(2, dtype=torch.int32, device=self.device)
+        return work, work_bytes, records, cap, n
+
+    def peptidoforms(self, site_probs, psm_probs, group, threshold=0.75, psm_id=None, psm_base=0, prev=None, cap=None):
+        """The peptidoform list of the last ``run()`` (``pya_plan_peptidoforms``): one 48-byte ``pya_peptidoform`` per distinct
+        (group, best_sig) among the scored PSMs with a non-negative group, ordered by group, then sig_bits.  ``site_probs`` /
+        ``psm_probs``: the two tensors of ``probs()``; ``group``: ``torch.int32`` device tensor ``[n_psm]``; ``psm_id`` /
+        ``psm_base`` as for ``rollup()``; ``prev``: the records of an earlier list (``torch.uint8 [n_prev, 48]``, only read) --
+        the result is then the list over the PSMs behind both, the bytes of one call over all of them; ``cap``: the room of
+        the result (default: PSMs + earlier records, which always suffices).  Returns device tensors ``(records, n)``:
+        ``torch.uint8 [cap, 48]`` (``peptidoform_records`` turns a host copy of the first ``n[0]`` into the structured array)
+        and ``torch.int32 [2]``: the length of the list and an error word.  The workspace is a torch tensor that lives for
+        the call; everything is launched on torch's current stream and nothing waits on the host."""
+        torch = self._torch
+        n_rec = int(self.site_offsets()[-1])
+        if group.dtype != torch.int32 or tuple(group.shape) != (self.n_psm,) or not group.is_contiguous() or not group.is_cuda:
+            raise ValueError("group must be a contiguous int32 device tensor of %d entries" % self.n_psm)
+        if site_probs.dtype != torch.float64 or tuple(site_probs.shape) != (n_rec, 2) or not site_probs.is_contiguous() or not site_probs.is_cuda \
+                or psm_probs.dtype != torch.uint8 or tuple(psm_probs.shape) != (self.n_psm, 16) or not psm_probs.is_contiguous() or not psm_probs.is_cuda:
+            raise ValueError("site_probs and psm_probs must be the tensors of probs()")
+        if psm_id is not None and (psm_id.element_size() != 4 or psm_id.is_floating_point() or tuple(psm_id.shape) != (self.n_psm,)
+                                   or not psm_id.is_contiguous() or not psm_id.is_cuda):
+            raise ValueError("psm_id must be a contiguous 32-bit integer device tensor of %d entries" % self.n_psm)
+        prev, n_prev = self._pform_records(prev, "prev")
+        work, work_bytes, records, cap, n = self._pform_buffers(self.n_psm + n_prev, cap)
+        stream = torch.cuda.current_stream(self.device)
+        rc = self._lib.pya_plan_peptidoforms(self._plan, C.byref(self._res), stream.cuda_stream, site_probs.data_ptr(), psm_probs.data_ptr(),
+                                             group.data_ptr(), float(threshold), None if psm_id is None else psm_id.data_ptr(), int(psm_base),
+                                             None if not n_prev else prev.data_ptr(), n_prev, work.data_ptr(), work_bytes,
+                                             records.data_ptr(), cap, n.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        work.record_stream(stream)                 # (the caching allocator must not hand the workspace on before the stream is past it)
+        return records, n
+
+    def peptidoform_reduce(self, a, b=None, cap=None):
+        """The list over one or two device arrays of peptidoform records (``torch.uint8 [n, 48]``, any order, keys may repeat,
+        records with ``n_psm == 0`` are skipped; ``pya_peptidoform_reduce``): merging two lists is this call.  Returns
+        ``(records, n)`` as ``peptidoforms()`` does; the inputs are only read."""
+        torch = self._torch
+        a, n_a = self._pform_records(a, "a")
+        b, n_b = self._pform_records(b, "b")
+        work, work_bytes, records, cap, n = self._pform_buffers(n_a + n_b, cap)
+        stream = torch.cuda.current_stream(self.device)
+        rc = self._lib.pya_peptidoform_reduce(self.scorer._h, None if not n_a else a.data_ptr(), n_a, None if not n_b else b.data_ptr(), n_b,
+                                              stream.cuda_stream, work.data_ptr(), work_bytes, records.data_ptr(), cap, n.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        work.record_stream(stream)
+        return records, n
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -389,6 +459,7 @@ PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)
 RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)
 ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)
 FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)
+PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)
 
 
 def evidence_rows(raw):
@@ -456,6 +527,15 @@ def rollup_records(raw):
     if a.ndim != 2 or a.shape[1] != ROLLUP_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, %d)" % ROLLUP_DTYPE.itemsize)
     return a.view(ROLLUP_DTYPE).reshape(a.shape[0])
+
+
+def peptidoform_records(raw):
+    """A host copy of the records of ``DevicePlan.peptidoforms()`` / ``peptidoform_reduce()`` (``[:n].cpu().numpy()``, uint8
+    ``[n, 48]``) as the structured array ``PyAscore.score_batch(..., peptidoforms=...)`` returns; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != PEPTIDOFORM_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % PEPTIDOFORM_DTYPE.itemsize)
+    return a.view(PEPTIDOFORM_DTYPE).reshape(a.shape[0])
 
 
 def flr_records(raw):

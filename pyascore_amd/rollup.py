@@ -13,6 +13,11 @@ best Ascore of those.
 ``best_prob``, the expected errors ``1 - p`` accumulated down the list, and -- with decoy residues in the modification group,
 ``decoy_classes`` -- the decoys above every cut as a q-value.  ``PyAscore.rollup_flr`` and ``DevicePlan.rollup_flr`` do the
 same on the device; the function here is the host form, with the same bytes.  ``cut`` names the slots reportable at a rate.
+
+Peptidoforms: ``peptide_groups`` numbers the peptides of a batch for ``score_batch(peptidoforms=dict(group=...))``, which
+returns one record per (peptide, reported site assignment) (``PEPTIDOFORM_DTYPE``, the 48-byte ``pya_peptidoform``);
+``merge_peptidoforms`` is the host form of ``PyAscore.peptidoform_reduce`` with the same bytes, and ``peptidoform_table``
+turns a list into the rows of a report.
 """
 import numpy as np
 
@@ -24,6 +29,8 @@ assert ROLLUP_DTYPE.itemsize == 32
 NO_PSM = _lib.PYA_ROLLUP_NO_PSM
 FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)                # pya_site_flr, 32 bytes
 assert FLR_DTYPE.itemsize == 32
+PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)    # pya_peptidoform, 48 bytes
+assert PEPTIDOFORM_DTYPE.itemsize == 48
 TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
@@ -235,4 +242,73 @@ def table(rollup, keys, flr=None):
             on = int(f["rank"]) != 0
             rows[-1].update(rank=int(f["rank"]) if on else None, flr=float(f["flr"]) if on else None,
                             decoy_q=float(f["decoy_q"]) if on else None)
+    return rows
+
+
+def peptide_groups(peptides):
+    """``(group, n_groups, keys)`` keyed by the unmodified peptide sequence: ``group`` (int32, one per PSM) is what
+    ``score_batch(peptidoforms=dict(group=...))`` takes, numbered in order of first appearance; ``keys[g]`` is the sequence
+    of group ``g``.  ``peptides``: one str / bytes per PSM."""
+    return _number([_text(p) for p in peptides])
+
+
+def merge_peptidoforms(a, b=None):
+    """The peptidoform list over the records of ``a`` and ``b`` (``PEPTIDOFORM_DTYPE``; any order, keys may repeat, records
+    with ``n_psm == 0`` are skipped, ``n_isomers`` is recomputed): one record per (group, sig_bits), ordered by group then
+    sig_bits.  Counts add, ``best_min_prob`` is the max over bit patterns with the smallest ``best_psm`` that has them,
+    ``best_z`` the min over bit patterns, ``best_min_ascore`` the max under the total order of float32 bit patterns: the host
+    form of ``PyAscore.peptidoform_reduce`` / ``pya_peptidoform_reduce``, with the same bytes."""
+    r = np.ascontiguousarray(a, PEPTIDOFORM_DTYPE).reshape(-1)
+    if b is not None:
+        r = np.concatenate([r, np.ascontiguousarray(b, PEPTIDOFORM_DTYPE).reshape(-1)])
+    r = r[r["n_psm"] != 0]
+    if r.size == 0:
+        return np.zeros(0, PEPTIDOFORM_DTYPE)
+    r = r[np.lexsort((r["sig_bits"], r["group"]))]
+    head = np.ones(r.size, bool)
+    head[1:] = (r["group"][1:] != r["group"][:-1]) | (r["sig_bits"][1:] != r["sig_bits"][:-1])
+    first = np.flatnonzero(head)
+    seg = np.cumsum(head) - 1
+    out = np.zeros(first.size, PEPTIDOFORM_DTYPE)
+    out["sig_bits"], out["group"] = r["sig_bits"][first], r["group"][first]
+    for f in ("n_psm", "n_confident"):
+        out[f] = np.add.reduceat(r[f].astype(np.uint64), first).astype(np.uint32)       # (32-bit counts wrap, as on the device)
+    bits = np.ascontiguousarray(r["best_min_prob"]).view(np.uint64)
+    top = np.maximum.reduceat(bits, first)
+    out["best_min_prob"] = top.view(np.float64)
+    out["best_psm"] = np.minimum.reduceat(np.where(bits == top[seg], r["best_psm"], np.uint32(0xFFFFFFFF)), first)
+    out["best_z"] = np.minimum.reduceat(np.ascontiguousarray(r["best_z"]).view(np.uint64), first).view(np.float64)
+    key = np.maximum.reduceat(_ascore_key(r["best_min_ascore"]), first)
+    out["best_min_ascore"] = np.where(key >> 31 != 0, key - 0x80000000, 0xFFFFFFFF - key).astype(np.uint32).view(np.float32)
+    ghead = np.ones(first.size, bool)
+    ghead[1:] = out["group"][1:] != out["group"][:-1]
+    gfirst = np.flatnonzero(ghead)
+    out["n_isomers"] = np.repeat(np.diff(np.append(gfirst, first.size)), np.diff(np.append(gfirst, first.size))).astype(np.uint32)
+    return out
+
+
+def peptidoform_table(records, keys, residues=None):
+    """The list as the rows of a report, in the list's order: one dict per peptidoform with ``peptide`` (``keys[group]``),
+    ``sites`` -- the modified residues: their 1-based positions when ``residues``, the scorer's modification group, is given,
+    otherwise the ordinals of the modifiable residues (bit numbers of ``sig_bits``) --, ``n_psm``, ``n_confident``,
+    ``best_psm``, ``best_min_prob``, ``best_posterior`` (``1 / best_z``), ``best_min_ascore`` and ``n_isomers``."""
+    records = np.asarray(records, PEPTIDOFORM_DTYPE)
+    rows = []
+    for rec in records:
+        g = int(rec["group"])
+        if g >= len(keys):
+            raise ValueError("group %d has no key (%d keys)" % (g, len(keys)))
+        sig = int(rec["sig_bits"])
+        ordinals = [r for r in range(64) if sig >> r & 1]
+        text = _text(keys[g])
+        if residues is not None:
+            where = site_residues(text, residues)
+            if ordinals and ordinals[-1] >= len(where):
+                raise ValueError("peptide %s has %d modifiable residues, sig_bits names residue %d" % (text, len(where), ordinals[-1]))
+            ordinals = [where[r] + 1 for r in ordinals]
+        z = float(rec["best_z"])
+        rows.append(dict(peptide=text, sites=ordinals, n_psm=int(rec["n_psm"]), n_confident=int(rec["n_confident"]),
+                         best_psm=int(rec["best_psm"]), best_min_prob=float(rec["best_min_prob"]),
+                         best_posterior=1.0 / z if z > 0.0 else 0.0, best_min_ascore=float(rec["best_min_ascore"]),
+                         n_isomers=int(rec["n_isomers"])))
     return rows

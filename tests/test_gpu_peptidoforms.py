@@ -1,0 +1,410 @@
+"""Peptidoform roll-up on the GPU (pya_peptidoform: the PSMs of a run collapsed onto one record per (group, best_sig)).
+Yardstick: tests/peptidoforms_ref.py -- for the reduce on the record arrays of tests/peptidoform_lists.py, for the plan path
+fed with the arrays score_batch(probs=True) returns for the same batch.  Every comparison is on the raw bytes of the 48-byte
+records: the stage does no arithmetic, so there is no tolerance."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import peptidoform_lists as pl
+import peptidoforms_ref as ref
+import switches
+from conftest import GOLDEN, golden_cases
+from oracle import harness
+from pyascore_amd import _lib, probs as pb, rollup as ru, synth
+
+pytestmark = pytest.mark.gpu
+
+T = _lib.PYA_PFORM_TILE
+GUARD = 4096
+THR = 0.75
+DT = ref.DTYPE
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    import torch
+    from pyascore_amd import PyAscore
+    from pyascore_amd.device import DevicePlan
+    batch, settings = synth.make_batch("cfg2", n_psm=2, seed=9100)
+    gpu = harness.make_scorer(PyAscore, settings)
+    return gpu, DevicePlan(gpu, batch, peptidoforms=True), torch.device("cuda", 0)
+
+
+_wanted = {}
+
+
+def _want(n, kind):
+    """the records and the yardstick's answer, computed once per case and never changed"""
+    if (n, kind) not in _wanted:
+        r = pl.make(n, kind)
+        want = ref.reduce(r)
+        r.setflags(write=False)
+        want.setflags(write=False)
+        _wanted[(n, kind)] = (r, want)
+    return _wanted[(n, kind)]
+
+
+def _same(got, want, what):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.dtype.itemsize == 48 and got.shape == want.shape, "%s: %d records, want %d" % (what, got.size, want.size)
+    bad = np.flatnonzero(got.view("V48") != want.view("V48"))
+    assert bad.size == 0, "%s: %d records differ, first %d: got %s, want %s" % (what, bad.size, bad[0], got[bad[0]], want[bad[0]])
+
+
+def _up(dev, r):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(r).view(np.uint8).reshape(-1, 48).copy()).to(dev)
+
+
+def _down(records, n):
+    from pyascore_amd.device import peptidoform_records
+    n = n.cpu().numpy()
+    assert int(n[1]) == 0
+    return peptidoform_records(records.cpu().numpy())[:int(n[0])], int(n[0])
+
+
+def _device(ctx, a, b=None, cap=None):
+    gpu, plan, dev = ctx
+    d_a, d_b = _up(dev, a), None if b is None else _up(dev, b)
+    got, n = _down(*plan.peptidoform_reduce(d_a, d_b, cap=cap))
+    assert d_a.cpu().numpy().tobytes() == a.tobytes() and (b is None or d_b.cpu().numpy().tobytes() == b.tobytes()), "the stage wrote into its input"
+    return got, n
+
+
+def _both(ctx, n, kind):
+    r, want = _want(n, kind)
+    _same(ctx[0].peptidoform_reduce(r), want, "host form, %d entries, %s" % (n, kind))
+    got, count = _device(ctx, r)
+    assert count == want.size
+    _same(got, want, "device form, %d entries, %s" % (n, kind))
+    return r, want
+
+
+@pytest.mark.parametrize("kind", pl.KINDS)
+def test_lists_equal_the_yardstick(ctx, kind):
+    for n in pl.SIZES:
+        _both(ctx, n, kind)
+
+
+@pytest.mark.parametrize("kind", pl.KINDS)
+def test_second_scan_level(ctx, kind):
+    _both(ctx, pl.BIG, kind)
+
+
+@pytest.mark.parametrize("kind", ("distinct", "runs", "ties", "ascores", "zeros", "group_ends"))
+def test_permuted_and_split_inputs_give_the_same_bytes(ctx, kind):
+    n = 2 * T + 1
+    r, want = _want(n, kind)
+    perm = r[np.random.default_rng(7).permutation(n)]
+    _same(_device(ctx, perm)[0], want, "permuted")
+    _same(ctx[0].peptidoform_reduce(perm), want, "permuted, host form")
+    for cut in (0, 1, 63, T - 1, T, T + 1, n - 1, n):
+        _same(_device(ctx, r[:cut], r[cut:])[0], want, "split at %d" % cut)
+    _same(ctx[0].peptidoform_reduce(r[:T + 3], r[T + 3:]), want, "split, host form")
+    # a list merged with itself: counts double, nothing else moves
+    twice = _device(ctx, want, want)[0]
+    back = twice.copy()
+    back["n_psm"] //= 2
+    back["n_confident"] //= 2
+    _same(back, want, "a list with itself")
+
+
+def _raw_reduce(ctx, r, cap, shrink_work=0, misalign=0):
+    """pya_peptidoform_reduce with guard bytes around d_out, d_n and d_work; returns rc, the three buffers and their payload slices"""
+    import torch
+    gpu, plan, dev = ctx
+    n = r.size
+    need = int(gpu._lib.pya_peptidoform_workspace_bytes(n))
+    d_a = _up(dev, r)
+    out = torch.full((2 * GUARD + cap * 48,), 0xA5, dtype=torch.uint8, device=dev)
+    cnt = torch.full((2 * GUARD + 8,), 0xA5, dtype=torch.uint8, device=dev)
+    work = torch.full((2 * GUARD + need,), 0xA5, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    rc = gpu._lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr(), n, None, 0, stream, work.data_ptr() + GUARD + misalign, need - shrink_work,
+                                         out.data_ptr() + GUARD, cap, cnt.data_ptr() + GUARD)
+    torch.cuda.synchronize(dev)
+    return rc, out.cpu().numpy(), cnt.cpu().numpy(), work.cpu().numpy()
+
+
+def _guards_intact(buf, payload):
+    return (buf[:GUARD] == 0xA5).all() and (buf[GUARD + payload:] == 0xA5).all()
+
+
+@pytest.mark.parametrize("n,kind", [(T + 1, "distinct"), (2 * T + 1, "runs"), (65, "zeros")])
+def test_guard_bytes_and_cap(ctx, n, kind):
+    r, want = _want(n, kind)
+    rc, out, cnt, work = _raw_reduce(ctx, r, cap=n)
+    assert rc == 0
+    need = work.size - 2 * GUARD
+    assert _guards_intact(out, n * 48) and _guards_intact(cnt, 8) and _guards_intact(work, need)
+    assert cnt[GUARD:GUARD + 8].view(np.uint32).tolist() == [want.size, 0]
+    assert out[GUARD:GUARD + want.size * 48].tobytes() == want.tobytes()
+    assert (out[GUARD + want.size * 48:] == 0xA5).all(), "records behind the list were written"
+    cap = want.size - 1
+    rc, out, cnt, work = _raw_reduce(ctx, r, cap=cap)
+    assert rc == 0 and cnt[GUARD:GUARD + 8].view(np.uint32).tolist() == [want.size, 0]
+    assert out[GUARD:GUARD + cap * 48].tobytes() == want[:cap].tobytes()
+    assert _guards_intact(out, cap * 48) and _guards_intact(cnt, 8) and _guards_intact(work, need)
+    got, count = _device(ctx, r, cap=cap)
+    assert count == want.size and got.size == cap
+
+
+def test_refusals(ctx):
+    import torch
+    gpu, plan, dev = ctx
+    lib = gpu._lib
+    assert lib.pya_peptidoform_workspace_bytes(0) == 0 and lib.pya_peptidoform_workspace_bytes(1) > 0
+    assert lib.pya_peptidoform_workspace_bytes(1 << 31) == 0
+    r, want = _want(T + 1, "distinct")
+    for kw in (dict(shrink_work=1), dict(misalign=4)):
+        rc, out, cnt, work = _raw_reduce(ctx, r, cap=r.size, **kw)
+        assert rc == _lib.PYA_ERR_ARG
+        for buf in (out, cnt, work):
+            assert (buf == 0xA5).all(), "a refused call launched something"
+    d_a, d_n = _up(dev, r), torch.zeros(2, dtype=torch.int32, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    need = int(lib.pya_peptidoform_workspace_bytes(r.size))
+    work, out = torch.empty(need, dtype=torch.uint8, device=dev), torch.empty((r.size, 48), dtype=torch.uint8, device=dev)
+    E = _lib.PYA_ERR_ARG
+    assert lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr(), r.size, None, 0, st, None, need, out.data_ptr(), r.size, d_n.data_ptr()) == E
+    assert lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr(), r.size, None, 0, st, work.data_ptr(), need, None, r.size, d_n.data_ptr()) == E
+    assert lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr(), r.size, None, 0, st, work.data_ptr(), need, out.data_ptr(), r.size, None) == E
+    assert lib.pya_peptidoform_reduce(gpu._h, None, r.size, None, 0, st, work.data_ptr(), need, out.data_ptr(), r.size, d_n.data_ptr()) == E
+    assert lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr(), r.size, None, 5, st, work.data_ptr(), 1 << 40, out.data_ptr(), r.size, d_n.data_ptr()) == E
+    assert lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr() + 8, r.size - 1, None, 0, st, work.data_ptr(), need, out.data_ptr(), r.size, d_n.data_ptr()) == E
+    assert lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr(), 1 << 31, None, 0, st, work.data_ptr(), 1 << 50, out.data_ptr(), r.size, d_n.data_ptr()) == E
+    assert lib.pya_peptidoform_reduce(gpu._h, d_a.data_ptr(), (1 << 31) - 1, d_a.data_ptr(), 1, st, work.data_ptr(), 1 << 50, out.data_ptr(), r.size,
+                                      d_n.data_ptr()) == E
+    assert b"2^31" in lib.pya_last_error(gpu._h)
+    # no entries: valid, nothing launched, d_n zeroed
+    d_n.fill_(7)
+    assert lib.pya_peptidoform_reduce(gpu._h, None, 0, None, 0, st, None, 0, None, 0, d_n.data_ptr()) == 0
+    assert d_n.cpu().numpy().tolist() == [0, 0]
+    # the plan call before the plan's first run
+    sp = torch.zeros((int(plan.site_offsets()[-1]), 2), dtype=torch.float64, device=dev)
+    pp = torch.zeros((plan.n_psm, 16), dtype=torch.uint8, device=dev)
+    grp = torch.zeros(plan.n_psm, dtype=torch.int32, device=dev)
+    with pytest.raises(Exception, match="has not been run"):
+        plan.peptidoforms(sp, pp, grp)
+    out1 = np.zeros(4, DT)
+    count = C.c_uint64()
+    assert lib.pya_last_batch_peptidoforms(gpu._h, out1.ctypes.data_as(C.c_void_p), 4, C.byref(count)) == _lib.PYA_ERR_STATE
+    assert b"PYA_FLAG_PEPTIDOFORMS" in lib.pya_last_error(gpu._h)
+    assert lib.pya_set_peptidoforms(gpu._h, None, 3, 0.75, None) == E
+
+
+# ---- the plan path ----
+def _gpu(settings, **debug):
+    from pyascore_amd import PyAscore
+    gpu = harness.make_scorer(PyAscore, settings)
+    for k, v in debug.items():
+        gpu.set_debug(k, v)
+    return gpu
+
+
+def _ref_of(res, group, thr=THR, psm_id=None, psm_base=0, prev=None):
+    return ref.from_psms(res["best_sig"], res["ascores"], res["site_off"], res["site_probs"], res["psm_probs"], group, thr, psm_id=psm_id,
+                         psm_base=psm_base, prev=prev)
+
+
+def _run_plan(gpu, batch, dev):
+    import torch
+    from pyascore_amd.device import DevicePlan
+    plan = DevicePlan(gpu, batch, peptidoforms=True)
+    plan.run(torch.from_numpy(batch["mz"]).to(dev), torch.from_numpy(batch["intensity"]).to(dev))
+    return plan
+
+
+def _plan_list(plan, dev, group, cap_sig=None, **kw):
+    import torch
+    _, sp, pp = plan.probs() if cap_sig is None else plan.probs(sig_cap=cap_sig)
+    rec, n = plan.peptidoforms(sp, pp, torch.from_numpy(np.ascontiguousarray(group, np.int32)).to(dev), threshold=THR, **kw)
+    return rec, n
+
+
+def _against_yardstick(settings, batch, group, what, skip_invalid=False, cap=0):
+    import torch
+    gpu = _gpu(settings)
+    plain = gpu.score_batch(batch, skip_invalid=skip_invalid, probs=True, site_sig_cap=cap)
+    want = _ref_of(plain, group)
+    got = gpu.score_batch(batch, skip_invalid=skip_invalid, peptidoforms=dict(group=group, threshold=THR), site_sig_cap=cap)
+    for key in ("best_score", "best_sig", "n_sig", "ascores", "alt_mask"):
+        assert got[key].tobytes() == plain[key].tobytes(), (what, key)          # nothing of the run moves
+    _same(got["peptidoforms"], want, what + ", score_batch")
+    both = gpu.score_batch(batch, skip_invalid=skip_invalid, probs=True, peptidoforms=dict(group=group, threshold=THR), site_sig_cap=cap)
+    assert both["site_probs"].tobytes() == plain["site_probs"].tobytes()
+    _same(both["peptidoforms"], want, what + ", beside PYA_FLAG_PROBS")
+    _same(ru.merge_peptidoforms(want), want, what + ", a list is its own merge")
+    assert want["n_psm"].sum() == int(((plain["psm_probs"]["kind"] == pb.SCORED) & (np.asarray(group) >= 0)).sum())
+    return gpu, plain, want
+
+
+def test_cfg2_batch_equals_the_yardstick():
+    import torch
+    batch, settings = synth.make_batch("cfg2", n_psm=300, seed=9310)
+    group = (np.arange(300) % 7).astype(np.int32)
+    gpu, plain, want = _against_yardstick(settings, batch, group, "cfg2")
+    assert (want["n_psm"] > 1).any() and (want["n_isomers"] > 1).any() and want.size < 300, "the seed must give repeats and isomers"
+    dev = torch.device("cuda", 0)
+    plan = _run_plan(gpu, batch, dev)
+    got, n = _down(*_plan_list(plan, dev, group))
+    _same(got, want, "plan")
+    # explicit ids against psm_base
+    ids = (np.arange(300) + 1000).astype(np.uint32)
+    based, _ = _down(*_plan_list(plan, dev, group, psm_base=1000))
+    named, _ = _down(*_plan_list(plan, dev, group, psm_id=torch.from_numpy(ids.astype(np.int64)).to(dev).to(torch.int32)))
+    _same(based, _ref_of(plain, group, psm_base=1000), "psm_base")
+    _same(named, based, "psm_id equals psm_base")
+    rev = (299 - np.arange(300)).astype(np.uint32)
+    got_rev, _ = _down(*_plan_list(plan, dev, group, psm_id=torch.from_numpy(rev.astype(np.int64)).to(dev).to(torch.int32)))
+    _same(got_rev, _ref_of(plain, group, psm_id=rev), "reversed ids")
+    # cap below the list: the prefix, the true count, nothing behind
+    rec, cnt = _plan_list(plan, dev, group, cap=want.size - 1)
+    assert cnt.cpu().numpy().tolist() == [want.size, 0] and rec.shape[0] == want.size - 1
+    from pyascore_amd.device import peptidoform_records
+    _same(peptidoform_records(rec.cpu().numpy()), want[:-1], "cap")
+    # two halves accumulated through prev equal the whole, in either order
+    halves = [(synth.slice_batch(batch, 0, 130), group[:130], 0), (synth.slice_batch(batch, 130, 300), group[130:], 130)]
+    for order in ((0, 1), (1, 0)):
+        prev = None
+        for h in order:
+            p = _run_plan(gpu, halves[h][0], dev)
+            rec, cnt = _plan_list(p, dev, halves[h][1], psm_base=halves[h][2], prev=prev)
+            prev = rec[:int(cnt.cpu().numpy()[0])].contiguous()
+        _same(peptidoform_records(prev.cpu().numpy()), want, "two plans through prev, order %s" % (order,))
+
+
+def test_cfg3_batch_with_mixed_n_of_mod():
+    batch, settings = synth.make_batch("cfg3", n_psm=300, seed=9320)
+    group = (np.arange(300) % 40).astype(np.int32)
+    _, plain, want = _against_yardstick(settings, batch, group, "cfg3")
+    assert len(set(np.asarray(batch["n_of_mod"]).tolist())) > 2 and want.size > 40
+
+
+@pytest.mark.parametrize("case", [c for c in golden_cases() if c.startswith("edge_")])
+def test_edge_goldens(case):
+    settings, batch, _ = harness.load_case(os.path.join(GOLDEN, case + ".npz"))
+    n = int(batch["n_psm"])
+    _against_yardstick(settings, batch, (np.arange(n) % 3).astype(np.int32), case)
+
+
+def test_set_aside_over_and_negative_groups():
+    good, settings = synth.make_batch("cfg2", n_psm=12, seed=9330)
+    psms = []
+    for i in range(good["n_psm"]):
+        kw = synth.unpack_psm(good, i)
+        psms.append(dict(mz=kw["mz_arr"], intensity=kw["int_arr"], peptide=kw["peptide"], n_of_mod=kw["n_of_mod"], max_charge=1))
+    psms[0] = dict(psms[0], peptide="ASGTPEYIDEK", n_of_mod=3)                 # k == n
+    psms[1] = dict(psms[1], peptide="PEPTXIDESK")                              # unknown residue: set aside
+    psms[2] = dict(psms[2], peptide="AGSPEPIDEK", n_of_mod=2)                  # more modifications than sites: not scored
+    psms[3] = dict(psms[3], mz=np.zeros(0), intensity=np.zeros(0))             # empty spectrum: set aside
+    psms[5] = dict(psms[5], peptide="ASGTPEYIDEK", n_of_mod=0)                 # k == 0
+    batch = synth.pack_batch(psms)
+    group = np.array([0, 1, 2, 3, 4, 0, -1, 4, -5, 4, 6, 6], np.int32)
+    gpu, plain, want = _against_yardstick(settings, batch, group, "mixed batch", skip_invalid=True)
+    zero = want[(want["group"] == 0) & (want["sig_bits"] == 0)][0]
+    assert zero["best_min_prob"] == 1.0 and zero["best_min_ascore"] == np.inf and zero["best_psm"] == 5
+    assert not np.isin(want["group"], [1, 2, 3]).any()
+    # a sig_cap pushes PSMs to PYA_SITE_OVER: they contribute nothing
+    batch2, settings2 = synth.make_realistic(60, seed=9940, general=True)
+    n_sig = _gpu(settings2).score_batch(batch2)["n_sig"]
+    cap = int(np.median(n_sig))
+    assert (n_sig > cap).any() and (n_sig <= cap).any()
+    _, plain2, want2 = _against_yardstick(settings2, batch2, (np.arange(60) % 4).astype(np.int32), "cap %d" % cap, cap=cap)
+    assert (plain2["psm_probs"]["kind"] == pb.OVER).any() and want2["n_psm"].sum() == int((plain2["psm_probs"]["kind"] == pb.SCORED).sum())
+
+
+def test_bytes_do_not_depend_on_the_context(monkeypatch):
+    """chunked against uncut, float32 against widened, shared against expanded"""
+    big = synth.make_slice(synth.describe("cfg2", 12_000, seed=9350))
+    settings = synth.describe("cfg2", 1, seed=9350)["settings"]
+    group = (np.arange(12_000) % 1700).astype(np.int32)
+    req = dict(group=group, threshold=THR)
+    gpu = _gpu(settings)
+    monkeypatch.setenv("PYA_NO_CHUNKS", "1")
+    switches.from_env(gpu)
+    plain = gpu.score_batch(big, probs=True)
+    uncut = gpu.score_batch(big, peptidoforms=req)["peptidoforms"]
+    assert gpu._lib.pya_debug_last_chunks(gpu._h) == 1
+    monkeypatch.delenv("PYA_NO_CHUNKS")
+    monkeypatch.setenv("PYA_CHUNK_MB", "2")
+    switches.from_env(gpu)
+    cut = gpu.score_batch(big, peptidoforms=req)["peptidoforms"]
+    assert gpu._lib.pya_debug_last_chunks(gpu._h) > 8
+    slot = np.zeros(int(plain["site_off"][-1]), np.int32)
+    cut_all = gpu.score_batch(big, peptidoforms=req, probs=True, rollup=dict(slot=slot, n_slots=1))
+    monkeypatch.delenv("PYA_CHUNK_MB")
+    switches.from_env(gpu)
+    want = _ref_of(plain, group)
+    assert (want["n_psm"] > 1).any() and (want["n_isomers"] > 1).any()
+    _same(uncut, want, "uncut")
+    _same(cut, want, "chunked")
+    _same(cut_all["peptidoforms"], want, "chunked, beside the probability records and the roll-up")
+    part, g = synth.slice_batch(big, 0, 1500), group[:1500]
+    wide = gpu.score_batch(synth.widen_batch(synth.narrow_batch(part)), peptidoforms=dict(group=g), probs=True)
+    _same(wide["peptidoforms"], _ref_of(wide, g), "widened")
+    _same(gpu.score_batch(synth.narrow_batch(part), peptidoforms=dict(group=g))["peptidoforms"], wide["peptidoforms"], "float32")
+    small_b, _ = synth.make_batch("cfg2", n_psm=60, seed=9351)
+    spectra, psms = [], []
+    for i in range(0, 60, 3):
+        kw = synth.unpack_psm(small_b, i)
+        spectra.append(dict(mz=kw["mz_arr"], intensity=kw["int_arr"]))
+        for j in range(3):
+            kj = synth.unpack_psm(small_b, (i + j) % 12)
+            psms.append(dict(peptide=kj["peptide"], n_of_mod=kj["n_of_mod"], max_charge=1, aux_pos=np.zeros(0, np.uint32),
+                             aux_mass=np.zeros(0, np.float32), spectrum=len(spectra) - 1))
+    for order, what in ((np.arange(60), "shared"), (np.random.default_rng(3).permutation(60), "shuffled shared")):
+        mine = [psms[p] for p in order]
+        shared = synth.pack_shared_batch(spectra, mine)
+        s_group, _, _ = ru.peptide_groups([p["peptide"] for p in mine])
+        flat = gpu.score_batch(synth.expand_shared_batch(shared), probs=True)
+        s_want = _ref_of(flat, s_group)                                       # best_psm: the caller's numbering
+        assert (s_want["n_psm"] >= 2).any()
+        _same(gpu.score_batch(synth.expand_shared_batch(shared), peptidoforms=dict(group=s_group))["peptidoforms"], s_want, what + ", expanded")
+        _same(gpu.score_batch(shared, peptidoforms=dict(group=s_group))["peptidoforms"], s_want, what)
+        typed = synth.narrow_batch(shared)
+        t_want = _ref_of(gpu.score_batch(synth.widen_batch(typed), probs=True), s_group)
+        _same(gpu.score_batch(typed, peptidoforms=dict(group=s_group))["peptidoforms"], t_want, what + ", typed")
+        _same(gpu.score_batch(synth.expand_shared_batch(typed), peptidoforms=dict(group=s_group))["peptidoforms"], t_want, what + ", typed, expanded")
+        ids = (1000 - np.arange(60)).astype(np.uint32)
+        _same(gpu.score_batch(shared, peptidoforms=dict(group=s_group, psm_id=ids))["peptidoforms"], _ref_of(flat, s_group, psm_id=ids),
+              what + ", psm_id")
+
+
+def test_batch_loan_rules():
+    batch, settings = synth.make_batch("cfg2", n_psm=40, seed=9360)
+    gpu = _gpu(settings)
+    group = (np.arange(40) % 5).astype(np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    with pytest.raises(ValueError):
+        gpu.score_batch(batch, peptidoforms=dict(group=group[:-1]))
+    res = gpu.score_batch(batch, peptidoforms=dict(group=group), probs=True)
+    want = _ref_of(res, group)
+    _same(res["peptidoforms"], want, "batch")
+    back, count = np.zeros(want.size, DT), C.c_uint64()
+    assert gpu._lib.pya_last_batch_peptidoforms(gpu._h, vp(back), want.size, C.byref(count)) == 0 and count.value == want.size
+    assert back.tobytes() == want.tobytes()
+    assert gpu._lib.pya_last_batch_peptidoforms(gpu._h, None, 0, C.byref(count)) == 0 and count.value == want.size
+    gpu.score_batch(batch)
+    assert gpu._lib.pya_last_batch_peptidoforms(gpu._h, vp(back), want.size, C.byref(count)) == _lib.PYA_ERR_STATE
+    # a loan of another size
+    assert gpu._lib.pya_set_peptidoforms(gpu._h, vp(group), 39, 0.75, None) == 0
+    arrs = [np.ascontiguousarray(batch[k], t) for k, t in (("peak_off", np.int64), ("pep", np.uint8), ("pep_off", np.int64), ("n_of_mod", np.int32),
+                                                           ("max_charge", np.int32), ("aux_pos", np.uint32), ("aux_mass", np.float32),
+                                                           ("aux_off", np.int64))]
+    b = _lib.Batch(40, *[vp(a) for a in arrs])
+    outs = [np.zeros_like(res[k]) for k in ("best_score", "best_sig", "n_sig", "ascores", "alt_mask")]
+    rs = _lib.Results(res["ascores"].shape[1], *[vp(a) for a in outs])
+    mz, it = np.ascontiguousarray(batch["mz"], np.float64), np.ascontiguousarray(batch["intensity"], np.float64)
+    assert gpu._lib.pya_score_batch(gpu._h, C.byref(b), vp(mz), vp(it), _lib.PYA_FLAG_PEPTIDOFORMS, C.byref(rs)) == _lib.PYA_ERR_ARG
+    assert b"pya_set_peptidoforms" in gpu._lib.pya_last_error(gpu._h)
+    # the flag without a loan (the loan above ended with its call)
+    assert gpu._lib.pya_score_batch(gpu._h, C.byref(b), vp(mz), vp(it), _lib.PYA_FLAG_PEPTIDOFORMS, C.byref(rs)) == _lib.PYA_ERR_ARG
+    # a batch of one takes the plan's launches
+    one = synth.slice_batch(batch, 3, 4)
+    r1 = gpu.score_batch(one, peptidoforms=dict(group=[9]), probs=True)
+    _same(r1["peptidoforms"], _ref_of(r1, np.array([9])), "a batch of one")
+    assert gpu.score_batch(synth.slice_batch(batch, 0, 0), peptidoforms=dict(group=[]))["peptidoforms"].size == 0
