@@ -107,6 +107,9 @@ extern "C" {
                                     /* over the groups lent by pya_set_peptidoforms (pya_last_batch_peptidoforms); the       */
                                     /* library runs the probability stage for itself; pya_plan_create*: as                  */
                                     /* PYA_FLAG_EVIDENCE (pya_plan_peptidoforms)                                            */
+#define PYA_FLAG_MZ_PROFILE 2048u /* pya_score_batch* / pya_score_batch_named: the fragment mass-error profile of the batch as  */
+                                  /* well, into the run slots lent by pya_set_mz_profile (pya_last_batch_mz_profile); it needs  */
+                                  /* no other stage; pya_plan_create*: as PYA_FLAG_EVIDENCE (pya_plan_mz_profile)               */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -393,6 +396,47 @@ typedef struct pya_peptidoform {   /* 48 bytes, three 16-byte stores; records co
     uint32_t n_isomers;            /* distinct sig_bits among the records of this group (same in all of them)  */
 } pya_peptidoform;
 
+/* Fragment mass-error profile.  The third reduction across PSMs, and the one that speaks about a SETTING rather than about a
+ * localisation: per run (file, fraction, instrument -- a slot the caller names per PSM) the distribution of the m/z errors of
+ * the matched fragments the scores counted, in Da and in ppm, resolved over bands of m/z.  The reference has no counterpart.
+ * A PSM CONTRIBUTES when its status is OK, its n_sig > 0 and its slot run[psm] (int32, the caller's) is not negative.  THE
+ * IONS of a contributing PSM are exactly its section-1 ion records, the winner's matched fragments as pya_plan_ions emits them
+ * (site 255): the same match rule -- the lowest rank inside the open window of mz_error, not the nearest peak --, the same
+ * fragments, and two fragments of one m/z are two ions.  Per ion with rank <= max_rank, in double and in this order:
+ *   d    = (double)peak_mz - (double)theo_mz
+ *   p    = d * 1e6 / (double)theo_mz                        one multiplication, then one division
+ *   band = min(PYA_MZP_BANDS - 1, (int)floor((double)theo_mz * inv_band))
+ *   q    = (int)floor(d * inv_da) + PYA_MZP_BINS / 2        counted in da[band][q] when 0 <= q < PYA_MZP_BINS, else in
+ *                                                           out_da[0] (below the axis) or out_da[1] (at or above it)
+ *   the same with p, inv_ppm, ppm[band][q] and out_ppm.
+ * Bins are half-open, [j w, (j + 1) w) around 0: d == 0 lands in bin PYA_MZP_BINS / 2.  inv_da, inv_ppm and inv_band are the
+ * CALLER's doubles, e.g. (PYA_MZP_BINS / 2) / half_width; the device never computes them, there is no multiply-add to contract
+ * and double division is correctly rounded, so a host restatement with the same doubles gives EQUAL counts, not close ones.
+ * Every word of a record is an integer count: THE TABLE IS A FUNCTION OF THE MULTISET OF (slot, ion) PAIRS AND OF NOTHING
+ * ELSE -- not of the order of the PSMs, the route that scored them, shared or typed input, chunk cuts or how the PSMs were
+ * spread over calls.  Two tables merge by adding every word.  Per slot
+ *   sum(da) + out_da[0] + out_da[1] == n_ions, the same for ppm, and
+ *   n_ions + n_rank_skipped == the section-1 ion records of the slot's PSMs.
+ * Counts are 32-bit and are not checked for overflow.  What the profile cannot show: an error outside +-mz_error of the run
+ * (such a peak was never matched), and the nearest peak where a lower-ranked one shares the window; random matches form a flat
+ * floor under the peak.  The use is: run wide, read the profile, re-run narrow.  csrc/mz_profile.hip. */
+#define PYA_MZP_BANDS 8
+#define PYA_MZP_BINS 64
+#define PYA_MZP_CHUNK 128u         /* PSMs per workgroup (the sizes a test of the stage wants to straddle) */
+typedef struct pya_mz_profile {    /* 4 128 bytes; the empty record is all-zero bytes (hipMemsetAsync clears a table) */
+    uint32_t n_psm;                /* contributing PSMs                                                        */
+    uint32_t n_ions;               /* their ions with rank <= max_rank                                         */
+    uint32_t n_rank_skipped;       /* their ions with rank > max_rank                                          */
+    uint32_t out_da[2], out_ppm[2];
+    uint32_t reserved;             /* 0                                                                        */
+    uint32_t da[PYA_MZP_BANDS][PYA_MZP_BINS];
+    uint32_t ppm[PYA_MZP_BANDS][PYA_MZP_BINS];
+} pya_mz_profile;
+typedef struct pya_mz_profile_params {
+    double inv_da, inv_ppm, inv_band;  /* bins per Da, bins per ppm, bands per m/z unit: finite and positive   */
+    uint32_t max_rank, reserved;       /* 0 .. 15: the deepest peak rank counted; 0                            */
+} pya_mz_profile_params;
+
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
  * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
@@ -671,6 +715,18 @@ int pya_set_peptidoforms(pya_handle *h, const int32_t *group, uint64_t n_psm, do
  * min(*n, cap) records into out (out may be NULL with cap == 0: the length alone).  PYA_ERR_STATE when the last batch was
  * scored without the flag. */
 int pya_last_batch_peptidoforms(pya_handle *h, pya_peptidoform *out, uint64_t cap, uint64_t *n);
+/* Lends the library what the NEXT batch call with PYA_FLAG_MZ_PROFILE profiles its PSMs into (pya_mz_profile above):
+ * run[n_psm], one slot per PSM (negative: left out), or NULL: every PSM is of slot 0; host memory that must stay valid until
+ * that call returns; n_slots, the size of the table; params, copied.  Lifetime and refusals are pya_set_peptidoforms's: the loan
+ * ends with the first batch call with the flag that gets as far as its PSMs, a batch of another size or a flag without a loan
+ * is PYA_ERR_ARG.  The batch call uploads a chunk's slice of run with the chunk and runs the stage behind every chunk into one
+ * device table that lives for the call; it needs neither the probability nor the evidence stage.  A slot at or above n_slots:
+ * PYA_ERR_LIMIT.  PYA_ERR_ARG: n_psm or n_slots above 2^31 - 1, NULL params, max_rank >= 16, an inv_* that is not finite and
+ * positive. */
+int pya_set_mz_profile(pya_handle *h, const int32_t *run, uint64_t n_psm, uint64_t n_slots, const pya_mz_profile_params *params);
+/* The table of the last batch call on this handle that was given PYA_FLAG_MZ_PROFILE: out[n_slots], n_slots as lent (anything
+ * else: PYA_ERR_ARG).  PYA_ERR_STATE when the last batch was scored without the flag. */
+int pya_last_batch_mz_profile(pya_handle *h, pya_mz_profile *out, uint64_t n_slots);
 /* The device bytes pya_plan_peptidoforms / pya_peptidoform_reduce need as their workspace for n_entries entries (PSMs of the
  * plan + records of d_prev; records of d_a + d_b): keys double-buffered, the entries, the staged list, digit histograms, tile
  * totals, about 133 bytes per entry; 0 for no entries (and above 2^31 - 1, which the calls refuse). */
@@ -795,6 +851,19 @@ int pya_plan_peptidoforms(pya_plan *plan, const pya_results *d_res, void *hip_st
                           const pya_psm_prob *d_psm_probs, const int32_t *d_group, double threshold, const uint32_t *d_psm_id,
                           uint32_t psm_base, const pya_peptidoform *d_prev, uint64_t n_prev, void *d_work, uint64_t work_bytes,
                           pya_peptidoform *d_out, uint64_t cap, uint32_t *d_n);
+/* Adds the fragment mass errors of this plan's contributing PSMs to d_table[n_slots] (pya_mz_profile above; device memory,
+ * emptied once by a hipMemsetAsync to 0): the stage ACCUMULATES, so the same table may take other plans, other runs and other
+ * calls.  d_run[n_psm] device memory, or NULL: every PSM is of slot 0.  It reads best_sig and n_sig of d_res, the run's status
+ * and its retained tables.  One or two launches of csrc/mz_profile.hip (the PSMs inside the fast limits, the general ones),
+ * stream-ordered, no host synchronisation and no allocation of the caller's inside, waits for the run (its side stream
+ * included) as pya_plan_evidence does, valid until the plan is run again, may be called again.  No write ever lies at or past
+ * d_table + n_slots: a PSM whose slot is at or above n_slots writes nothing, and pya_plan_check reports it (PYA_ERR_LIMIT)
+ * until the call is repeated or the plan is run again.  PYA_ERR_ARG, with nothing launched: max_rank >= 16, an inv_* that is not
+ * finite and positive, n_slots above 2^31 - 1, NULL where an array is needed; PYA_ERR_STATE before the plan's first run;
+ * PYA_ERR_LIMIT under the LDS condition of pya_plan_evidence.  A plan of a handful of PSMs is created with
+ * PYA_FLAG_MZ_PROFILE (or another stage flag): the one-launch kernel leaves no retained tables. */
+int pya_plan_mz_profile(pya_plan *plan, const pya_results *d_res, void *hip_stream, const int32_t *d_run, uint64_t n_slots,
+                        const pya_mz_profile_params *params, pya_mz_profile *d_table);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

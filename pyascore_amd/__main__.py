@@ -11,8 +11,9 @@ candidate residue and the posterior of the reported localisation) and ``--ranked
 with a line per ranked site assignment: the K best localisations of every PSM, in order) and ``--site_table FILE`` with
 ``--site_table_threshold P`` (a site-level table over all PSMs, a line per peptide and position; ``--site_table_flr`` ranks
 its sites and adds false-localisation rates, ``--site_table_decoys LETTERS`` names decoy residues) and
-``--peptidoform_table FILE`` with ``--peptidoform_threshold P`` (a line per peptide and reported site assignment) are the
-additions."""
+``--peptidoform_table FILE`` with ``--peptidoform_threshold P`` (a line per peptide and reported site assignment) and
+``--mz_profile FILE`` (the fragment mass-error profile of the whole file, a line per m/z band, unit and bin, and its summary
+in the log) are the additions."""
 import argparse
 import re
 import sys
@@ -95,6 +96,11 @@ def build_parser():
                         "Isomers), reduced on the device; the main table does not change")
     p.add_argument("--peptidoform_threshold", type=float, default=0.75, metavar="P",
                    help="the smallest site probability from which a PSM counts as Confident in --peptidoform_table (default 0.75)")
+    p.add_argument("--mz_profile", type=str, default=None, metavar="FILE",
+                   help="write the fragment mass-error profile of the whole file to FILE (slot 0): one line per band of m/z, unit "
+                        "(da, ppm) and bin with the number of matched fragments of the reported localisations whose m/z error "
+                        "falls into it, binned on the device, and print its summary; errors are only seen inside +-mz_error, "
+                        "so run wide, read the profile, re-run narrow; the main table does not change")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -158,6 +164,7 @@ def run(args, log=print):
     ranked_rows = [] if args.ranked else None
     site_table_rows = [] if args.site_table else None
     peptidoform_rows = [] if args.peptidoform_table else None
+    profile = [] if args.mz_profile else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -168,7 +175,7 @@ def run(args, log=print):
                               probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth, site_table=site_table_rows,
                               site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
-                              peptidoform_threshold=args.peptidoform_threshold)
+                              peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -179,6 +186,10 @@ def run(args, log=print):
         batch_cli.write_site_table_tsv(site_table_rows, args.site_table, flr=args.site_table_flr)
     if peptidoform_rows is not None:
         batch_cli.write_peptidoform_table_tsv(peptidoform_rows, args.peptidoform_table)
+    if profile is not None:
+        batch_cli.write_mz_profile_tsv(profile[0], profile[1], args.mz_profile)
+        for line in batch_cli.mz_profile_report(profile[0], profile[1]):
+            log("{} -- {}".format(stamp(), line))
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

@@ -18,6 +18,9 @@ PYA_FLAG_PROBS = 128
 PYA_FLAG_RANKED = 256
 PYA_FLAG_ROLLUP = 512
 PYA_FLAG_PEPTIDOFORMS = 1024
+PYA_FLAG_MZ_PROFILE = 2048
+PYA_MZP_BANDS, PYA_MZP_BINS = 8, 64
+PYA_MZP_CHUNK = 128          # PSMs per workgroup of csrc/mz_profile.hip
 PYA_PFORM_TILE = 1024        # entries per workgroup and sort pass of csrc/peptidoforms.hip
 PYA_PFORM_PHASES = 4         # (include/pyascore_debug.h: pya_debug_last_peptidoform_ms)
 PYA_ROLLUP_NO_PSM = 0xFFFFFFFF
@@ -83,7 +86,6 @@ class Ion(C.Structure):
 assert C.sizeof(Ion) == 16, "pya_ion is a 16-byte record"
 ION_DTYPE = [("theo_mz", "<f4"), ("peak_mz", "<f4"), ("size", "<u2"), ("type", "u1"), ("charge", "u1"),
              ("rank", "u1"), ("site", "u1"), ("flags", "u1"), ("reserved", "u1")]
-
 
 
 class Named(C.Structure):
@@ -168,6 +170,17 @@ PEPTIDOFORM_DTYPE = [("sig_bits", "<u8"), ("group", "<u4"), ("n_psm", "<u4"), ("
                      ("best_min_prob", "<f8"), ("best_z", "<f8"), ("best_min_ascore", "<f4"), ("n_isomers", "<u4")]
 FLR_DTYPE = [("rank", "<u4"), ("n_decoy", "<u4"), ("err_sum", "<u8"), ("flr", "<f8"), ("decoy_q", "<f8")]
 
+
+class MzProfileParams(C.Structure):
+    """pya_mz_profile_params: bins per Da, bins per ppm, bands per m/z unit, the deepest peak rank counted"""
+    _fields_ = [("inv_da", C.c_double), ("inv_ppm", C.c_double), ("inv_band", C.c_double), ("max_rank", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(MzProfileParams) == 32, "pya_mz_profile_params is a 32-byte record"
+MZ_PROFILE_DTYPE = [("n_psm", "<u4"), ("n_ions", "<u4"), ("n_rank_skipped", "<u4"), ("out_da", "<u4", (2,)), ("out_ppm", "<u4", (2,)),
+                    ("reserved", "<u4"), ("da", "<u4", (PYA_MZP_BANDS, PYA_MZP_BINS)), ("ppm", "<u4", (PYA_MZP_BANDS, PYA_MZP_BINS))]
+
 PYA_F64, PYA_F32 = 0, 1
 
 
@@ -232,6 +245,9 @@ SYMBOLS = {
     "pya_plan_rollup": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_uint64, C.c_double, _vp, C.c_uint32, _vp]),
     "pya_set_peptidoforms": (C.c_int, [_vp, _vp, C.c_uint64, C.c_double, _vp]),
     "pya_last_batch_peptidoforms": (C.c_int, [_vp, _vp, C.c_uint64, _vp]),
+    "pya_set_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
+    "pya_last_batch_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "pya_plan_mz_profile": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, C.c_uint64, _vp, _vp]),
     "pya_peptidoform_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "pya_peptidoform_reduce": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "pya_peptidoform_reduce_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),

@@ -112,6 +112,36 @@ def _peptidoform_request(req, n_psm):
     return dict(group=np.ascontiguousarray(group, np.int32), threshold=float(req.get("threshold", 0.75)), psm_id=psm_id)
 
 
+def _mz_profile_request(req, n_psm, mz_error, n_top):
+    """``score_batch(mz_profile=...)`` with its defaults resolved: dict(run int32 | None, n_slots, params, c_params)"""
+    from .rollup import mz_profile_params
+    if req is True:
+        req = {}
+    if not isinstance(req, dict):
+        raise ValueError("mz_profile takes a dict: run, n_slots, da_half_width, ppm_half_width, band_width, max_rank")
+    unknown = set(req) - {"run", "n_slots", "da_half_width", "ppm_half_width", "band_width", "max_rank"}
+    if unknown:
+        raise ValueError("mz_profile takes run, n_slots, da_half_width, ppm_half_width, band_width and max_rank; unknown: "
+                         + ", ".join(sorted(unknown)))
+    run = req.get("run")
+    if run is not None:
+        run = np.asarray(run)
+        if run.ndim != 1 or run.size != n_psm or (run.size and run.dtype.kind not in "iu"):
+            raise ValueError("mz_profile: run is one integer per PSM")
+        if run.size and (int(run.max()) > 0x7FFFFFFF or int(run.min()) < -0x80000000):
+            raise ValueError("mz_profile: run does not fit int32")
+        run = np.ascontiguousarray(run, np.int32)
+    n_slots = int(req.get("n_slots", 1))
+    if not 0 <= n_slots <= 0x7FFFFFFF:
+        raise ValueError("mz_profile: n_slots must be in 0 .. 2^31 - 1")
+    da = req.get("da_half_width")
+    rank = req.get("max_rank")
+    params = mz_profile_params(mz_error if da is None else da, req.get("ppm_half_width", 50.0), req.get("band_width", 250.0),
+                               n_top - 1 if rank is None else rank)
+    c_params = _lib.MzProfileParams(params["inv_da"], params["inv_ppm"], params["inv_band"], params["max_rank"], 0)
+    return dict(run=run, n_slots=n_slots, params=params, c_params=c_params)
+
+
 def _rollup_request(rollup, n_psm):
     """``score_batch(rollup=...)`` as contiguous arrays: dict(slot int32, n_slots, threshold, psm_id uint32 | None,
     site_off int64 | None)"""
@@ -199,6 +229,7 @@ class PyAscore:
         self._score_one_addr = C.cast(self._lib.pya_score_one, C.c_void_p).value
         self.device = int(device)
         self._n_top = int(n_top)
+        self._mz_error = float(np.float32(mz_error))     # (as the library holds it: a float32)
         self._last = None            # summary of the last score() call
         self._batch_n = None         # PSMs of the batch retained by score_batch(keep=True)
         self._budget = 0             # set_workspace_budget (0 = the library's default, 6 GiB)
@@ -370,7 +401,7 @@ class PyAscore:
             self._batch_n = 1
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
-                    site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None):
+                    site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -442,6 +473,16 @@ class PyAscore:
         sig_bits, reduced on the device (``group`` is one non-negative int32 per PSM, e.g. from
         ``pyascore_amd.rollup.peptide_groups``; negative: the PSM is left out).  ``best_psm`` is in the caller's numbering.
 
+        ``mz_profile=dict(run=None, n_slots=1, da_half_width=None, ppm_half_width=50.0, band_width=250.0, max_rank=None)`` adds
+        ``mz_profile`` (``pyascore_amd.rollup.MZ_PROFILE_DTYPE``, the 4 128-byte ``pya_mz_profile``, shape ``[n_slots]``): per
+        run slot (``run``: one int32 per PSM, negative: left out; None: everything is slot 0) the m/z errors of the matched
+        fragments of the reported localisations, counted in 64 bins over ``+-da_half_width`` Da (None: the scorer's
+        ``mz_error``) and over ``+-ppm_half_width`` ppm, in 8 bands of ``band_width`` m/z; ``max_rank`` is the deepest peak
+        rank counted (None: ``n_top - 1``, every match); ``mz_profile_params`` is the dict of the three inverse widths and
+        ``max_rank`` the table was binned with (``pyascore_amd.rollup.mz_profile_params``).  ``pyascore_amd.rollup`` has ``mz_profile_summary``, the host
+        restatement ``mz_profile`` and ``merge_mz_profiles``.  The profile only sees errors inside ``+-mz_error`` of this
+        scorer: run wide, read the profile, re-run narrow.
+
         Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
         m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
@@ -450,13 +491,15 @@ class PyAscore:
         ranked_k = None if ranked is None or ranked is False else check_ranked_k(ranked)
         roll = None if rollup is None else _rollup_request(rollup, int(batch["n_psm"]))
         pform = None if peptidoforms is None else _peptidoform_request(peptidoforms, int(batch["n_psm"]))
+        mzp = None if mz_profile is None or mz_profile is False else _mz_profile_request(mz_profile, int(batch["n_psm"]), self._mz_error,
+                                                                                        self._n_top)
         if batch.get("spec_of") is not None:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                         named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup,
-                                        peptidoforms=peptidoforms)
+                                        peptidoforms=peptidoforms, mz_profile=mz_profile)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -480,11 +523,16 @@ class PyAscore:
                 if pform is not None:        # the groups travel with their PSMs, the ids say who they were
                     pform_moved = dict(group=pform["group"][perm], threshold=pform["threshold"],
                                        psm_id=perm.astype(np.uint32) if pform["psm_id"] is None else pform["psm_id"][perm])
+                mzp_moved = None
+                if mzp is not None:          # the run slots travel with their PSMs
+                    mzp_moved = dict(mz_profile if isinstance(mz_profile, dict) else {})
+                    if mzp["run"] is not None:
+                        mzp_moved["run"] = mzp["run"][perm]
                 try:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
                                            site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved,
-                                           peptidoforms=pform_moved)
+                                           peptidoforms=pform_moved, mz_profile=mzp_moved)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
@@ -493,6 +541,8 @@ class PyAscore:
                 res.pop("site_off", None)
                 table = res.pop("rollup", None)         # (per slot, not per PSM)
                 forms = res.pop("peptidoforms", None)   # (per peptidoform)
+                profile = res.pop("mz_profile", None)   # (per run slot)
+                profile_params = res.pop("mz_profile_params", None)
                 per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
                 if moved is not None:
@@ -519,6 +569,8 @@ class PyAscore:
                     res["rollup"] = table
                 if forms is not None:
                     res["peptidoforms"] = forms
+                if profile is not None:
+                    res["mz_profile"], res["mz_profile_params"] = profile, profile_params
                 if res.get("status_message"):
                     res["status_message"] = _renumber_psm(res["status_message"], perm)
                 return res
@@ -578,6 +630,9 @@ class PyAscore:
                 out["rollup"]["best_psm"] = _lib.PYA_ROLLUP_NO_PSM
             if pform is not None:
                 out["peptidoforms"] = np.zeros(0, PEPTIDOFORM_DTYPE)
+            if mzp is not None:
+                out["mz_profile"] = np.zeros(mzp["n_slots"], np.dtype(_lib.MZ_PROFILE_DTYPE))
+                out["mz_profile_params"] = dict(mzp["params"])
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -602,7 +657,8 @@ class PyAscore:
         flags = (_lib.PYA_FLAG_KEEP if keep and not lazy_keep else 0) | (_lib.PYA_FLAG_SKIP_INVALID if skip_invalid else 0) | \
             (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0) | \
-            (_lib.PYA_FLAG_ROLLUP if roll is not None else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if pform is not None else 0)
+            (_lib.PYA_FLAG_ROLLUP if roll is not None else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if pform is not None else 0) | \
+            (_lib.PYA_FLAG_MZ_PROFILE if mzp is not None else 0)
         # for this call; the handle's own settings come back
         cap_before = k_before = None
         if (sites or probs or ranked_k or roll is not None or pform is not None) and site_sig_cap is not None:
@@ -617,6 +673,8 @@ class PyAscore:
                                                                  roll["threshold"], _as_ptr(roll["psm_id"]))
             if not rc and pform is not None:
                 rc = self._lib.pya_set_peptidoforms(self._h, _as_ptr(pform["group"]), n, pform["threshold"], _as_ptr(pform["psm_id"]))
+            if not rc and mzp is not None:
+                rc = self._lib.pya_set_mz_profile(self._h, _as_ptr(mzp["run"]), n, mzp["n_slots"], C.byref(mzp["c_params"]))
             if not rc:
                 rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         finally:
@@ -671,6 +729,12 @@ class PyAscore:
             if rc:
                 self._raise(rc)
             out["peptidoforms"] = out["peptidoforms"][:count.value].copy()
+        if mzp is not None:
+            out["mz_profile"] = np.zeros(mzp["n_slots"], np.dtype(_lib.MZ_PROFILE_DTYPE))
+            rc = self._lib.pya_last_batch_mz_profile(self._h, _as_ptr(out["mz_profile"]), mzp["n_slots"])
+            if rc:
+                self._raise(rc)
+            out["mz_profile_params"] = dict(mzp["params"])
         return out
 
     def peptidoform_reduce(self, a, b=None):

@@ -44,6 +44,8 @@ SITE_TABLE_FLR_COLUMNS = ("Rank", "FLR", "DecoyQ")
 # ``--peptidoform_table FILE``: one line per (peptide, reported site assignment) over all PSMs (pya_peptidoform)
 PEPTIDOFORM_TABLE_COLUMNS = ("Peptide", "Positions", "PSMs", "Confident", "BestScan", "BestMinProb", "BestPosterior", "BestMinAscore",
                              "Isomers")
+# ``--mz_profile FILE``: one line per slot, band, unit and bin of the fragment mass-error profile (pya_mz_profile)
+MZ_PROFILE_COLUMNS = ("Slot", "Band", "Unit", "Bin", "Low", "High", "Count")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -156,7 +158,7 @@ def pack_hits(picked, scans):
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
-             site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75):
+             site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -182,13 +184,19 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``site_table_decoys``: the letters of the modification group that are decoy residues (sites on them count as decoys).
     ``peptidoform_table``: a list that receives one ``peptidoform_table_fields`` row per (unmodified peptide, reported site
     assignment) over ALL scored PSMs (``write_peptidoform_table_tsv``), reduced on the device; ``peptidoform_threshold`` is
-    the "confident" cut on a PSM's smallest site probability; the main table does not change."""
+    the "confident" cut on a PSM's smallest site probability; the main table does not change.
+    ``mz_profile``: a list that receives the fragment mass-error profile of ALL scored PSMs as slot 0: the one-record table
+    (``pyascore_amd.rollup.MZ_PROFILE_DTYPE``) and the parameters it was binned with (``mz_profile_rows``,
+    ``write_mz_profile_tsv``, ``mz_profile_report``); the main table does not change."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
     picked, scans = select_psms(psms, spectra_map, residues, mod_mass, hit_depth, max_fragment_charge,
                                 mod_correction_tol, zero_based, match_save, reported=where)
     if not picked:
+        if mz_profile is not None:           # (no PSM: the empty table, with the parameters a scored batch would have had)
+            none = ascore.score_batch(pack_hits([], []), skip_invalid=True, mz_profile=dict(n_slots=1))
+            mz_profile.extend([none["mz_profile"], none["mz_profile_params"]])
         return []
     batch = pack_hits(picked, scans)
     named = [[sig_bits_of(p["peptide"], q, residues)] for p, q in zip(picked, where)] if reported else None
@@ -202,6 +210,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     if peptidoform_table is not None:
         group, _, form_keys = site_rollup.peptide_groups([p["peptide"] for p in picked])
         stages["peptidoforms"] = dict(group=group, threshold=float(peptidoform_threshold))
+    if mz_profile is not None:
+        stages["mz_profile"] = dict(n_slots=1)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything
@@ -243,6 +253,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         if site_table_flr:
             flr = ascore.rollup_flr(res["rollup"], site_rollup.decoy_classes(keys, decoys=site_table_decoys) if site_table_decoys else None)
         site_table.extend(site_table_fields(row, scans) for row in site_rollup.table(res["rollup"], keys, flr=flr))
+    if mz_profile is not None:
+        mz_profile.extend([res["mz_profile"], res["mz_profile_params"]])
     if peptidoform_table is not None:
         peptidoform_table.extend(peptidoform_table_fields(row, scans)
                                  for row in site_rollup.peptidoform_table(res["peptidoforms"], form_keys, residues=residues))
@@ -328,6 +340,44 @@ def peptidoform_table_fields(row, scans):
     return [row["peptide"], ";".join(str(p) for p in row["sites"]), str(row["n_psm"]), str(row["n_confident"]),
             scans[row["best_psm"]] if row["best_psm"] < len(scans) else "", repr(row["best_min_prob"]), repr(row["best_posterior"]),
             str(np.float32(row["best_min_ascore"])), str(row["n_isomers"])]
+
+
+def mz_profile_rows(table, params):
+    """The ``--mz_profile`` table: one ``MZ_PROFILE_COLUMNS`` row per slot, band, unit and bin of a profile, with the bin's
+    lower and upper edge in the unit (the counts outside an axis are the rows of bin -1 and bin ``MZP_BINS``, band -1)."""
+    rows = []
+    half = site_rollup.MZP_BINS // 2
+    for s, rec in enumerate(np.asarray(table, site_rollup.MZ_PROFILE_DTYPE).reshape(-1)):
+        for unit in ("da", "ppm"):
+            w = 1.0 / params["inv_" + unit]
+            rows.append([s, -1, unit, -1, "-inf", repr(-half * w), int(rec["out_" + unit][0])])
+            for band in range(site_rollup.MZP_BANDS):
+                rows.extend([s, band, unit, q, repr((q - half) * w), repr((q + 1 - half) * w), int(rec[unit][band, q])]
+                            for q in range(site_rollup.MZP_BINS))
+            rows.append([s, -1, unit, site_rollup.MZP_BINS, repr(half * w), "inf", int(rec["out_" + unit][1])])
+    return rows
+
+
+def write_mz_profile_tsv(table, params, path):
+    """The ``--mz_profile`` file: ``mz_profile_rows`` under ``MZ_PROFILE_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(MZ_PROFILE_COLUMNS) + "\n")
+        for row in mz_profile_rows(table, params):
+            out.write("\t".join(str(f) for f in row) + "\n")
+
+
+def mz_profile_report(table, params):
+    """The lines ``--mz_profile`` prints: per slot and unit the ions, the median and the 5 % / 95 % quantiles of the error,
+    the flat floor, and the per-band medians."""
+    lines = []
+    for s, row in enumerate(site_rollup.mz_profile_summary(table, params)):
+        lines.append("mass-error profile, slot %d: %d PSMs, %d ions (%d beyond max_rank)" % (s, row["n_psm"], row["n_ions"], row["n_rank_skipped"]))
+        for unit in ("da", "ppm"):
+            u = row[unit]
+            lines.append("  %-3s median %.6g, 5 %% %.6g, 95 %% %.6g, %d inside (%d below, %d above), floor %.3g per bin; band medians %s"
+                         % (unit, u["median"], u["q05"], u["q95"], u["total"], u["below"], u["above"], u["background"],
+                            " ".join("%.4g" % m for m in u["band_medians"])))
+    return lines
 
 
 def write_peptidoform_table_tsv(peptidoform_rows, path):

@@ -418,6 +418,48 @@ static int pform_end(pya_handle *h) {
     return PYA_OK;
 }
 
+/* PYA_FLAG_MZ_PROFILE: the loan of pya_set_mz_profile becomes the call's; the device table that lives for the call is sized
+ * and emptied here */
+static int mzp_begin(pya_handle *h, pya_handle::MzpLoan *loan, uint64_t n_psm) {
+    *loan = h->mzp_loan;
+    h->mzp_loan = pya_handle::MzpLoan{};                      /* (the loan ends with this call, whatever it returns) */
+    if (!loan->set) return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_MZ_PROFILE without slots: call pya_set_mz_profile before the batch call");
+    if (loan->n_psm != n_psm)
+        return h->fail(PYA_ERR_ARG, -1, "pya_set_mz_profile lent the run slots of %llu PSMs, the batch has %llu", (unsigned long long)loan->n_psm,
+                       (unsigned long long)n_psm);
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->d_mzp.n < loan->n_slots || !h->d_mzp.p) HIPCHK(h, h->d_mzp.alloc((size_t)loan->n_slots));
+    if (loan->n_slots) {                                      /* (before any stream of the call has work: the chunks' streams do not wait for this one) */
+        HIPCHK(h, hipMemsetAsync(h->d_mzp.p, 0, (size_t)loan->n_slots * sizeof(pya_mz_profile), nullptr));
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+    }
+    return PYA_OK;
+}
+
+/* ... the plan's slice of the caller's slots on its way to the device on `st`, in front of the plan's run as the roll-up's
+ * slots are (rollup_upload says why) */
+static int mzp_upload(pya_handle *h, pya_plan *p, const pya_handle::MzpLoan &loan, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0 || !loan.run) return PYA_OK;
+    HIPCHK(h, p->d_mzp_run.alloc((size_t)n));
+    HIPCHK(h, hipMemcpyAsync(p->d_mzp_run.p, loan.run + lo, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    return PYA_OK;
+}
+
+/* ... the stage of the plan behind its run on `st`: it needs no other stage */
+static int mzp_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, const pya_handle::MzpLoan &loan, hipStream_t st) {
+    if (p->n_psm == 0) return PYA_OK;
+    return pya_plan_mz_profile(p, d_out, st, loan.run ? p->d_mzp_run.p : nullptr, loan.n_slots, &loan.params, h->d_mzp.p);
+}
+
+/* ... and the end of the call, when every chunk has been waited for: the table comes to the host */
+static int mzp_end(pya_handle *h, const pya_handle::MzpLoan &loan) {
+    h->mzp_host.assign((size_t)loan.n_slots, pya_mz_profile{});
+    if (loan.n_slots) HIPCHK(h, hipMemcpy(h->mzp_host.data(), h->d_mzp.p, (size_t)loan.n_slots * sizeof(pya_mz_profile), hipMemcpyDeviceToHost));
+    h->mzp_valid = true;
+    return PYA_OK;
+}
+
 /* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
  * counts, [n_q * n_top] scores -- zeroed */
 static int named_host_block(pya_handle *h, uint64_t n_q) {
@@ -488,7 +530,7 @@ static void named_deliver(pya_handle *h, const NamedReq *nq, uint64_t lo, uint64
 static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp,
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
                                const uint8_t *pre_sites, const NamedReq *nq, const pya_handle::RollupLoan &loan,
-                               const pya_handle::PformLoan &pf_loan) {
+                               const pya_handle::PformLoan &pf_loan, const pya_handle::MzpLoan &mzp_loan) {
     const size_t nchunk = cuts.size() - 1;
     const uint64_t n_q = nq ? (uint64_t)nq->q_off[b->n_psm] : 0;
     /* the spectra [first, last) of chunk c: its PSMs' own unless spectra are shared -- then from the first PSM's to the last
@@ -593,6 +635,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if (nq && (rc = named_upload(h, p, nq, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_upload(h, p, mzp_loan, lo, h->run_stream))) return finish(rc);
         rc = pya_plan_run_typed(p, &d_sp, h->run_stream, &d_out);
         if (rc) return finish(rc);
         /* status + results are adjacent in the arena: one asynchronous copy into pinned memory */
@@ -616,6 +659,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_RANKED) && (rc = ranked_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_behind_run(h, p, &d_out, loan, flags, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_behind_run(h, p, &d_out, pf_loan, flags, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_behind_run(h, p, &d_out, mzp_loan, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -658,10 +702,12 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         /* (a slot outside the table: the report of this chunk's roll-up, whose kernels the event above waited for) */
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_report(p, lo))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_collect(h, p, lo))) return finish(rc);
+        if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_report(p, lo))) return finish(rc);
         cur = std::move(next);
     }
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_end(h, loan))) return finish(rc);
     if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_end(h))) return finish(rc);
+    if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_end(h, mzp_loan))) return finish(rc);
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
     h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
     /* (chunks behind the last PSM with records: their offsets stay at the total) */
@@ -685,6 +731,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->ranked_valid = false;
     h->rollup_valid = false;
     h->pform_valid = false;
+    h->mzp_valid = false;
     pya_handle::RollupLoan loan;
     if (flags & PYA_FLAG_ROLLUP) {
         const int rc_ru = rollup_begin(h, &loan);
@@ -694,6 +741,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if (flags & PYA_FLAG_PEPTIDOFORMS) {
         const int rc_pf = pform_begin(h, &pf_loan, b->n_psm);
         if (rc_pf) return rc_pf;
+    }
+    pya_handle::MzpLoan mzp_loan;
+    if (flags & PYA_FLAG_MZ_PROFILE) {
+        const int rc_mzp = mzp_begin(h, &mzp_loan, b->n_psm);
+        if (rc_mzp) return rc_mzp;
     }
     if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
     if (flags & PYA_FLAG_SITES) h->sites_off.assign(b->n_psm + 1, 0);
@@ -711,6 +763,10 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         if (flags & PYA_FLAG_PEPTIDOFORMS) {
             const int rc_pf = pform_end(h);
             if (rc_pf) return rc_pf;
+        }
+        if (flags & PYA_FLAG_MZ_PROFILE) {
+            const int rc_mzp = mzp_end(h, mzp_loan);
+            if (rc_mzp) return rc_mzp;
         }
         return (flags & PYA_FLAG_ROLLUP) ? rollup_end(h, loan) : PYA_OK;
     }
@@ -759,8 +815,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_rk = ranked_host_block(h, b);
         if (rc_rk) return rc_rk;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP or _PEPTIDOFORMS takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS or _MZ_PROFILE takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -803,7 +859,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
             }
             cuts.push_back(b->n_psm);
             h->last_chunks = cuts.size() - 1;
-            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan, pf_loan);
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan, pf_loan, mzp_loan);
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -852,6 +908,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if (nq && (rc = named_upload(h, p, nq, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, 0, nullptr))) return rc;
+    if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_upload(h, p, mzp_loan, 0, nullptr))) return rc;
     rc = pya_plan_run_typed(p, &d_sp, nullptr, &d_out);
     if (rc) return rc;
     if (p->d2h_bytes <= kStageLimit) {
@@ -922,6 +979,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         if ((rc = pform_collect(h, p, 0))) return rc;
         if ((rc = pform_end(h))) return rc;
     }
+    if (flags & PYA_FLAG_MZ_PROFILE) {
+        if ((rc = mzp_behind_run(h, p, &d_out, mzp_loan, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        if ((rc = mzp_report(p, 0))) return rc;
+        if ((rc = mzp_end(h, mzp_loan))) return rc;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -947,6 +1010,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->ranked_valid = false;
     h->rollup_valid = false;
     h->pform_valid = false;
+    h->mzp_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);

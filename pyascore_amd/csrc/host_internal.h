@@ -143,6 +143,9 @@ int pya_launch_rollup(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec,
                       const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id, uint32_t psm_base,
                       const uint64_t *best_sig, const float *ascores, uint32_t max_k, void *d_table, uint32_t *d_over, uint32_t grid[2],
                       hipStream_t stream);
+size_t pya_mz_profile_lds_bytes(uint32_t l_cap);
+int pya_launch_mz_profile(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int32_t *d_run, uint64_t n_slots,
+                          const pya_mz_profile_params *prm, void *d_table, uint32_t *d_over, uint32_t l_cap, hipStream_t stream);
 uint64_t pya_flr_layout_bytes(uint64_t n_slots);
 int pya_launch_flr(const void *d_table, uint64_t n_slots, const uint8_t *d_cls, uint32_t reported_only, void *d_work, void *d_out,
                    uint32_t *d_order, uint32_t *d_n_ranked, hipEvent_t *phase, hipStream_t stream);
@@ -425,6 +428,17 @@ struct pya_handle {
     /* pya_debug_peptidoform_timing: events between the phases of the stage's next calls (include/pyascore_debug.h) */
     bool pform_timed = false, pform_ev_recorded = false;
     hipEvent_t pform_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    /* PYA_FLAG_MZ_PROFILE: what pya_set_mz_profile lent for the next batch call, the device table that lives for the call
+     * (zeroed when the call begins) and the table of the last such call on the host */
+    struct MzpLoan {
+        const int32_t *run = nullptr;
+        uint64_t n_psm = 0, n_slots = 0;
+        pya_mz_profile_params params = {};
+        bool set = false;
+    } mzp_loan;
+    DevBuf<pya_mz_profile> d_mzp;
+    std::vector<pya_mz_profile> mzp_host;
+    bool mzp_valid = false;
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -788,6 +802,12 @@ struct pya_plan {
     DevBuf<int32_t> d_pform_group;
     DevBuf<uint32_t> d_pform_id;
     uint64_t pform_records = 0;
+    /* pya_plan_mz_profile: the report of the last call (PSMs whose slot is at or above n_slots), as for the roll-up; a
+     * pya_score_batch plan's slice of the caller's run slots */
+    DevBuf<uint32_t> d_mzp_over;
+    hipEvent_t ev_mzp = nullptr;
+    bool mzp_asked = false;
+    DevBuf<int32_t> d_mzp_run;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -802,6 +822,7 @@ struct pya_plan {
         if (ev_named) (void)hipEventDestroy(ev_named);
         if (ev_sites) (void)hipEventDestroy(ev_sites);
         if (ev_rollup) (void)hipEventDestroy(ev_rollup);
+        if (ev_mzp) (void)hipEventDestroy(ev_mzp);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
@@ -918,6 +939,10 @@ int pform_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const vo
               double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const uint64_t *best_sig, const float *ascores, uint32_t max_k,
               const void *d_src0, uint64_t n0, const void *d_src1, uint64_t n1, void *d_work, void *d_out, uint64_t cap, uint32_t *d_n, bool run,
               hipStream_t st);
+/* host_mz_profile.cpp: everything the mass-error profile calls refuse, before anything is launched; host_run.cpp: the
+ * report of a plan's last pya_plan_mz_profile (psm_lo as for rollup_report) */
+int mzp_check(pya_handle *h, const char *who, uint64_t n_slots, const pya_mz_profile_params *prm);
+int mzp_report(pya_plan *p, uint64_t psm_lo);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");
@@ -947,6 +972,11 @@ static_assert(sizeof(pya_peptidoform) == 48 && offsetof(pya_peptidoform, group) 
                   offsetof(pya_peptidoform, best_min_prob) == 24 && offsetof(pya_peptidoform, best_z) == 32 &&
                   offsetof(pya_peptidoform, best_min_ascore) == 40 && offsetof(pya_peptidoform, n_isomers) == 44,
               "pya_peptidoform is the three 16-byte stores of peptidoforms.hip");
+static_assert(sizeof(pya_mz_profile) == 4128 && offsetof(pya_mz_profile, n_ions) == 4 && offsetof(pya_mz_profile, n_rank_skipped) == 8 &&
+                  offsetof(pya_mz_profile, out_da) == 12 && offsetof(pya_mz_profile, out_ppm) == 20 && offsetof(pya_mz_profile, reserved) == 28 &&
+                  offsetof(pya_mz_profile, da) == 32 && offsetof(pya_mz_profile, ppm) == 32 + 4 * PYA_MZP_BANDS * PYA_MZP_BINS &&
+                  sizeof(pya_mz_profile_params) == 32 && offsetof(pya_mz_profile_params, max_rank) == 24,
+              "pya_mz_profile is the 1 032 words mz_profile.hip flushes");
 static_assert(sizeof(pya_site_flr) == 32 && offsetof(pya_site_flr, n_decoy) == 4 && offsetof(pya_site_flr, err_sum) == 8 &&
                   offsetof(pya_site_flr, flr) == 16 && offsetof(pya_site_flr, decoy_q) == 24,
               "pya_site_flr is two 16-byte stores of flr.hip");

@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -338,6 +338,7 @@ int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_strea
     p->ions_state = 0;                       /* (counts, offsets and the overflow report belonged to the run before) */
     p->named_asked = false;
     p->rollup_asked = false;
+    p->mzp_asked = false;
     p->dev = d;
     return rc;
 }
@@ -428,6 +429,19 @@ int rollup_report(pya_plan *p, uint64_t psm_lo) {
                    "n_slots of the call; nothing of them was written", over[0], (unsigned long long)first);
 }
 
+/* ... and the last pya_plan_mz_profile of this run: PSMs whose slot is not inside the table of the call */
+int mzp_report(pya_plan *p, uint64_t psm_lo) {
+    pya_handle *h = p->h;
+    if (!p->mzp_asked) return PYA_OK;
+    uint32_t over[2] = {0u, 0u};
+    HIPCHK(h, hipEventSynchronize(p->ev_mzp));
+    HIPCHK(h, hipMemcpy(over, p->d_mzp_over.p, sizeof(over), hipMemcpyDeviceToHost));
+    if (!over[0]) return PYA_OK;
+    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
+    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_mz_profile: %u PSMs (PSM %llu the first) name a run slot at or above the n_slots of "
+                   "the call; nothing of them was written", over[0], (unsigned long long)first);
+}
+
 int pya_plan_check(pya_plan *p) {
     if (!p) return PYA_ERR_ARG;
     pya_handle *h = p->h;
@@ -458,6 +472,8 @@ int pya_plan_check(pya_plan *p) {
     }
     const int rc_ru = rollup_report(p, 0);
     if (rc_ru) return rc_ru;
+    const int rc_mzp = mzp_report(p, 0);
+    if (rc_mzp) return rc_mzp;
     if (p->ions_state != 2) return PYA_OK;
     /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
     HIPCHK(h, hipEventSynchronize(p->ev_ions));
@@ -878,6 +894,47 @@ int pya_plan_peptidoforms(pya_plan *p, const pya_results *r, void *hip_stream, c
     }
     return pform_run(h, p->n_psm ? p->d_site_off.p : nullptr, p->n_psm, d_site_probs, d_psm_probs, d_group, threshold, d_psm_id, psm_base,
                      r->best_sig, r->ascores, r->max_k, d_prev, n_prev, nullptr, 0, d_work, d_out, cap, d_n, run, st);
+}
+
+/* The mass-error profile (csrc/mz_profile.hip): the wait and the two lists of the evidence stage, with the longest peptide of
+ * either list as the only cap -- the kernel keeps no fragment list.  The argument checks are host_mz_profile.cpp's; the report
+ * of slots outside the table goes the way of pya_plan_rollup's. */
+int pya_plan_mz_profile(pya_plan *p, const pya_results *r, void *hip_stream, const int32_t *d_run, uint64_t n_slots,
+                        const pya_mz_profile_params *prm, pya_mz_profile *d_table) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    const int rc_arg = mzp_check(h, "pya_plan_mz_profile", n_slots, prm);
+    if (rc_arg) return rc_arg;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_mz_profile: the plan has not been run");
+    if ((n_slots && !d_table) || !r->best_sig || !r->n_sig) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_mz_profile");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->d_mzp_over.p) HIPCHK(h, p->d_mzp_over.alloc(2));
+    if (!p->ev_mzp) HIPCHK(h, hipEventCreateWithFlags(&p->ev_mzp, hipEventDisableTiming));
+    /* (the LDS condition of pya_plan_evidence, and this kernel's own room, which only a peptide length could exceed) */
+    struct Room {
+        static size_t both(uint32_t l_cap, uint32_t list_cap) {
+            return std::max(pya_evidence_lds_bytes(l_cap, list_cap), pya_mz_profile_lds_bytes(l_cap));
+        }
+    };
+    const int rc = stage_behind_run(p, st, "pya_plan_mz_profile", "evidence", Room::both);
+    if (rc) return rc;
+    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
+    if (p->mzp_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_mzp, 0));
+    HIPCHK(h, hipMemsetAsync(p->d_mzp_over.p, 0, 2 * sizeof(uint32_t), st));
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    int e = pya_launch_mz_profile(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, d_run, n_slots, prm, d_table,
+                                  p->d_mzp_over.p, p->evid_l_cap, st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_mz_profile(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_run, n_slots, prm, d_table, p->d_mzp_over.p, p->gen_l_cap, st);
+    if (e) return h->hip_fail((hipError_t)e, "mass-error profile launch");
+    HIPCHK(h, hipEventRecord(p->ev_mzp, st));
+    p->mzp_asked = true;
+    return PYA_OK;
 }
 
 namespace {

@@ -17,7 +17,7 @@
  * the number of records of every PSM, FILL writes the records at the offsets the scan below made of the counts.  A PSM
  * whose records would pass `cap` writes nothing and is reported through over[] (count, 0xffffffff - the smallest PSM).
  */
-#include "general_core.hip.h"
+#include "ion_match.hip.h"
 
 #define ION_WINNER 255u
 #define ION_LOSS 1u
@@ -30,30 +30,6 @@
  * (size | charge << 16 | loss << 24; bit 31: it survived the walk) */
 __host__ __device__ static inline size_t ions_lds_bytes(uint32_t l_cap, uint32_t list_cap) {
     return ((gen_lds_bytes(l_cap, list_cap) + 15) & ~(size_t)15) + (size_t)list_cap * 3 * 4;
-}
-
-/* gen_match_rank with the table index of the peak: the lowest rank inside the open window and, among equal ranks, the
- * lowest m/z (the table is in m/z order; the reference consumes windows in that order and replaces a match only by a
- * lower rank).  -1: none */
-DEV int ion_match_index(const PeakEntry *e, int n, float f, float err, bool half_check, int *rank) {
-    const float lo = f - err, hi = f + err;
-    int a = 0, b = n;
-    while (a < b) {                                           /* first entry above lo */
-        const int m = (a + b) >> 1;
-        if (e[m].mz > lo) b = m;
-        else a = m + 1;
-    }
-    int best = GEN_NO_MATCH, at = -1;
-    for (int i = a; i < n; i++) {
-        const PeakEntry x = e[i];
-        if (!(x.mz < hi)) break;
-        if ((!half_check || (double)f >= (double)x.mz - 0.5) && (int)x.rank < best) {
-            best = (int)x.rank;
-            at = i;
-        }
-    }
-    *rank = best;
-    return at;
 }
 
 DEV uint4 ion_rec(float theo, float peak, uint32_t size, uint32_t type, uint32_t charge, uint32_t rank, uint32_t site, uint32_t flags) {

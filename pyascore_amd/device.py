@@ -30,10 +30,11 @@ class DevicePlan:
     (``pya_plan_probs``).  ``ranked()`` / ``ranked=True``: the same for the ranked localisations (``pya_plan_ranked``).  ``rollup()`` /
     ``rollup=True``: the probability records rolled into a table of the caller's slots (``pya_plan_rollup``).
     ``peptidoforms()`` / ``peptidoforms=True``: the PSMs collapsed onto one record per (group, best_sig)
-    (``pya_plan_peptidoforms``); ``peptidoform_reduce()`` merges such lists."""
+    (``pya_plan_peptidoforms``); ``peptidoform_reduce()`` merges such lists.  ``mz_profile()`` / ``mz_profile=True``: the
+    fragment mass errors of the reported localisations binned per run slot (``pya_plan_mz_profile``)."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
-                 ranked=False, rollup=False, peptidoforms=False):
+                 ranked=False, rollup=False, peptidoforms=False, mz_profile=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -64,7 +65,8 @@ class DevicePlan:
         flags = (_lib.PYA_FLAG_TIMING if timing else 0) | (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | \
             (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0) | \
-            (_lib.PYA_FLAG_ROLLUP if rollup else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if peptidoforms else 0)
+            (_lib.PYA_FLAG_ROLLUP if rollup else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if peptidoforms else 0) | \
+            (_lib.PYA_FLAG_MZ_PROFILE if mz_profile else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -407,6 +409,31 @@ class DevicePlan:
         work.record_stream(stream)
         return records, n
 
+    def mz_profile(self, params, run=None, n_slots=None, table=None):
+        """Adds the fragment mass errors of the last ``run()`` to ``table`` (``pya_plan_mz_profile``): a ``torch.uint8`` device
+        tensor ``[n_slots, 4128]`` (one ``pya_mz_profile`` per run slot; ``mz_profile_records`` turns a host copy into the
+        structured array), new and zeroed when None -- ``n_slots`` of them, 1 by default.  The stage ACCUMULATES: the same
+        table takes other plans, runs and calls, and an empty table is all-zero bytes.  ``params``:
+        ``pyascore_amd.rollup.mz_profile_params(...)``; ``run``: ``torch.int32`` device tensor ``[n_psm]``, the slot of every
+        PSM (negative: left out), or None: slot 0.  One or two launches on torch's current stream; nothing waits on the host.
+        A slot at or above the table's size writes nothing and is reported by ``check()``.  Returns ``table``."""
+        torch = self._torch
+        if table is None:
+            with torch.cuda.device(self.device):
+                table = torch.zeros((1 if n_slots is None else int(n_slots), MZ_PROFILE_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != MZ_PROFILE_DTYPE.itemsize or not table.is_contiguous() \
+                or not table.is_cuda:
+            raise ValueError("table must be a contiguous uint8 device tensor of shape (n_slots, %d)" % MZ_PROFILE_DTYPE.itemsize)
+        if run is not None and (run.dtype != torch.int32 or tuple(run.shape) != (self.n_psm,) or not run.is_contiguous() or not run.is_cuda):
+            raise ValueError("run must be a contiguous int32 device tensor of %d entries" % self.n_psm)
+        c_params = _lib.MzProfileParams(params["inv_da"], params["inv_ppm"], params["inv_band"], params["max_rank"], 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_plan_mz_profile(self._plan, C.byref(self._res), stream, None if run is None else run.data_ptr(), table.shape[0],
+                                           C.byref(c_params), table.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return table
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -460,6 +487,7 @@ RANKED_DTYPE = np.dtype(_lib.RANKED_DTYPE)
 ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)
 FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)
 PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)
+MZ_PROFILE_DTYPE = np.dtype(_lib.MZ_PROFILE_DTYPE)
 
 
 def evidence_rows(raw):
@@ -527,6 +555,15 @@ def rollup_records(raw):
     if a.ndim != 2 or a.shape[1] != ROLLUP_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, %d)" % ROLLUP_DTYPE.itemsize)
     return a.view(ROLLUP_DTYPE).reshape(a.shape[0])
+
+
+def mz_profile_records(raw):
+    """A host copy of a mass-error profile table (``.cpu().numpy()``, uint8 ``[n_slots, 4128]``) as the structured array
+    ``PyAscore.score_batch(..., mz_profile=...)`` returns in ``mz_profile``; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != MZ_PROFILE_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % MZ_PROFILE_DTYPE.itemsize)
+    return a.view(MZ_PROFILE_DTYPE).reshape(a.shape[0])
 
 
 def peptidoform_records(raw):

@@ -18,6 +18,11 @@ Peptidoforms: ``peptide_groups`` numbers the peptides of a batch for ``score_bat
 returns one record per (peptide, reported site assignment) (``PEPTIDOFORM_DTYPE``, the 48-byte ``pya_peptidoform``);
 ``merge_peptidoforms`` is the host form of ``PyAscore.peptidoform_reduce`` with the same bytes, and ``peptidoform_table``
 turns a list into the rows of a report.
+
+Fragment mass-error profile: ``score_batch(mz_profile=dict(run=..., n_slots=...))`` returns one ``MZ_PROFILE_DTYPE`` record
+(the 4 128-byte ``pya_mz_profile``) per run slot; ``mz_profile_params`` is the only place the three inverse widths are
+computed, ``mz_profile`` restates the stage over ion records with the same IEEE operations (equal counts, not close ones),
+``merge_mz_profiles`` adds tables and ``mz_profile_summary`` reads a tolerance off one.
 """
 import numpy as np
 
@@ -31,6 +36,9 @@ FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)                # pya_site_flr, 32 bytes
 assert FLR_DTYPE.itemsize == 32
 PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)    # pya_peptidoform, 48 bytes
 assert PEPTIDOFORM_DTYPE.itemsize == 48
+MZ_PROFILE_DTYPE = np.dtype(_lib.MZ_PROFILE_DTYPE)  # pya_mz_profile, 4 128 bytes
+assert MZ_PROFILE_DTYPE.itemsize == 4128
+MZP_BANDS, MZP_BINS = _lib.PYA_MZP_BANDS, _lib.PYA_MZP_BINS
 TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
@@ -312,3 +320,127 @@ def peptidoform_table(records, keys, residues=None):
                          best_posterior=1.0 / z if z > 0.0 else 0.0, best_min_ascore=float(rec["best_min_ascore"]),
                          n_isomers=int(rec["n_isomers"])))
     return rows
+
+
+def mz_profile_params(da_half_width, ppm_half_width=50.0, band_width=250.0, max_rank=9):
+    """``dict(inv_da, inv_ppm, inv_band, max_rank)`` of a profile whose Da axis spans ``+-da_half_width``, whose ppm axis spans
+    ``+-ppm_half_width`` (``MZP_BINS`` half-open bins each, 0 at the lower edge of bin ``MZP_BINS / 2``) and whose m/z bands
+    are ``band_width`` wide (the last of the ``MZP_BANDS`` is open-ended): bins per Da, bins per ppm, bands per m/z unit, as
+    the doubles the device and ``mz_profile`` multiply by.  Refuses what the C ABI refuses: a width whose inverse is not a
+    finite positive number, ``max_rank`` outside 0 .. 15."""
+    half = MZP_BINS // 2
+    out = dict(inv_da=half / float(da_half_width) if da_half_width else float("inf"),
+               inv_ppm=half / float(ppm_half_width) if ppm_half_width else float("inf"),
+               inv_band=1.0 / float(band_width) if band_width else float("inf"))
+    for k, v in out.items():
+        if not (np.isfinite(v) and v > 0.0):
+            raise ValueError("mz_profile: %s = %r is not a finite positive number" % (k, v))
+    if int(max_rank) != max_rank or not 0 <= int(max_rank) <= 15:
+        raise ValueError("mz_profile: max_rank must be in 0 .. 15")
+    out["max_rank"] = int(max_rank)
+    return out
+
+
+def _mzp_cell(x):
+    """floor(x) + MZP_BINS / 2 per element, -1 below the axis, MZP_BINS at or above it (csrc/mz_profile.hip: mzp_bin)"""
+    half = MZP_BINS // 2
+    fl = np.floor(x)
+    below = ~(fl >= -float(half))
+    above = ~below & ~(fl < float(half))
+    q = np.where(below | above, 0.0, fl).astype(np.int64) + half
+    return np.where(below, -1, np.where(above, MZP_BINS, q))
+
+
+def mz_profile(ion_off, ions, n_sig, run, n_slots, params):
+    """The table ``score_batch(mz_profile=...)`` returns, from the ion records of the same batch (``score_batch(ions=True)``:
+    ``ion_off``, ``ions``) and its ``n_sig``: the definition of ``pya_mz_profile`` operation for operation, in float64.
+    ``run``: one slot per PSM (negative: left out) or None (slot 0); a contributing PSM whose slot is at or above ``n_slots``
+    is a ValueError (the library answers PYA_ERR_LIMIT).  ``params``: ``mz_profile_params(...)``."""
+    ion_off = np.asarray(ion_off, np.int64)
+    ions = np.asarray(ions, np.dtype(_lib.ION_DTYPE))
+    n_sig = np.asarray(n_sig)
+    n = n_sig.size
+    run = np.zeros(n, np.int64) if run is None else np.asarray(run).astype(np.int64)
+    if ion_off.size != n + 1 or run.shape != (n,):
+        raise ValueError("mz_profile: ion_off has n_psm + 1 entries, run one per PSM")
+    n_slots = int(n_slots)
+    table = np.zeros(n_slots, MZ_PROFILE_DTYPE)
+    contributes = (n_sig > 0) & (run >= 0)
+    if (run[contributes] >= n_slots).any():
+        raise ValueError("mz_profile: PSM %d names run slot %d of %d" % (int(np.flatnonzero(contributes & (run >= n_slots))[0]),
+                                                                       int(run[contributes].max()), n_slots))
+    np.add.at(table["n_psm"], run[contributes], 1)
+    psm_of = np.repeat(np.arange(n), np.diff(ion_off))
+    take = (ions["site"] == _lib.PYA_ION_WINNER) & contributes[psm_of]
+    rec, slot = ions[take], run[psm_of[take]]
+    deep = rec["rank"] > params["max_rank"]
+    np.add.at(table["n_rank_skipped"], slot[deep], 1)
+    rec, slot = rec[~deep], slot[~deep]
+    np.add.at(table["n_ions"], slot, 1)
+    theo, peak = rec["theo_mz"].astype(np.float64), rec["peak_mz"].astype(np.float64)
+    d = peak - theo
+    scaled = d * 1e6
+    p = scaled / theo
+    fb = np.floor(theo * params["inv_band"])
+    band = np.where(~(fb >= 0.0), 0.0, np.where(~(fb < float(MZP_BANDS - 1)), float(MZP_BANDS - 1), fb)).astype(np.int64)
+    for unit, value, inv in (("da", d, params["inv_da"]), ("ppm", p, params["inv_ppm"])):
+        q = _mzp_cell(value * inv)
+        inside = (q >= 0) & (q < MZP_BINS)
+        np.add.at(table[unit], (slot[inside], band[inside], q[inside]), 1)
+        np.add.at(table["out_" + unit], (slot[q < 0], 0), 1)
+        np.add.at(table["out_" + unit], (slot[q >= MZP_BINS], 1), 1)
+    return table
+
+
+def merge_mz_profiles(*tables):
+    """The sum of tables of one shape, word by word (32-bit counts wrap, as on the device): the profile of the PSMs behind
+    all of them."""
+    if not tables:
+        raise ValueError("merge_mz_profiles: no table")
+    parts = [np.ascontiguousarray(t, MZ_PROFILE_DTYPE).reshape(-1) for t in tables]
+    if any(p.size != parts[0].size for p in parts):
+        raise ValueError("merge_mz_profiles: the tables have different numbers of slots")
+    words = np.zeros(parts[0].size * (MZ_PROFILE_DTYPE.itemsize // 4), np.uint32)
+    for p in parts:
+        words += p.view(np.uint32)
+    return words.view(MZ_PROFILE_DTYPE)
+
+
+def _mzp_quantile(hist, q):
+    """where the fraction q of the counts of a 1-D histogram lies, in bins from the lower edge of bin 0, interpolated inside
+    the bin; nan for an empty histogram"""
+    total = float(hist.sum())
+    if total == 0.0:
+        return float("nan")
+    cum = np.cumsum(hist.astype(np.float64))
+    target = q * total
+    j = int(np.searchsorted(cum, target, side="left"))
+    j = min(j, hist.size - 1)
+    while hist[j] == 0:                                  # (target == 0: the first bin that has counts)
+        j += 1
+    before = cum[j] - float(hist[j])
+    return j + (target - before) / float(hist[j])
+
+
+def mz_profile_summary(table, params=None):
+    """One dict per slot: ``n_psm``, ``n_ions``, ``n_rank_skipped`` and per unit (``"da"``, ``"ppm"``) a dict with ``total``
+    (the ions inside the axis), ``below`` / ``above`` (outside it), ``median``, ``q05``, ``q95`` (interpolated inside the bins),
+    ``background`` (the mean count per bin of the two outermost bins on each side: the flat floor random matches leave) and
+    ``band_medians`` (``MZP_BANDS`` values, nan for a band without ions).  With ``params`` (``mz_profile_params``) the
+    positions are in Da and ppm; without, in bins from 0 (bin ``MZP_BINS / 2`` starts at 0.0)."""
+    table = np.asarray(table, MZ_PROFILE_DTYPE).reshape(-1)
+    half = MZP_BINS // 2
+    out = []
+    for rec in table:
+        row = dict(n_psm=int(rec["n_psm"]), n_ions=int(rec["n_ions"]), n_rank_skipped=int(rec["n_rank_skipped"]))
+        for unit in ("da", "ppm"):
+            width = 1.0 if params is None else 1.0 / params["inv_" + unit]
+            bands = rec[unit].astype(np.int64)
+            hist = bands.sum(axis=0)
+            where = lambda h, q: float((_mzp_quantile(h, q) - half) * width)
+            row[unit] = dict(total=int(hist.sum()), below=int(rec["out_" + unit][0]), above=int(rec["out_" + unit][1]),
+                             median=where(hist, 0.5), q05=where(hist, 0.05), q95=where(hist, 0.95),
+                             background=float(hist[[0, 1, MZP_BINS - 2, MZP_BINS - 1]].mean()),
+                             band_medians=[where(b, 0.5) for b in bands])
+        out.append(row)
+    return out
