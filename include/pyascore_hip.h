@@ -110,6 +110,10 @@ extern "C" {
 #define PYA_FLAG_MZ_PROFILE 2048u /* pya_score_batch* / pya_score_batch_named: the fragment mass-error profile of the batch as  */
                                   /* well, into the run slots lent by pya_set_mz_profile (pya_last_batch_mz_profile); it needs  */
                                   /* no other stage; pya_plan_create*: as PYA_FLAG_EVIDENCE (pya_plan_mz_profile)               */
+#define PYA_FLAG_RECALIBRATE 4096u /* pya_score_batch* / pya_score_batch_named: the m/z of every spectrum corrected with the      */
+                                   /* calibration lent by pya_set_recalibration, in the library's own device copy, before the    */
+                                   /* first kernel reads it; refused by pya_score_one, by pya_plan_create* (a plan's user calls  */
+                                   /* pya_recalibrate_spectra on their own arrays) and together with PYA_FLAG_KEEP               */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -437,6 +441,35 @@ typedef struct pya_mz_profile_params {
     uint32_t max_rank, reserved;       /* 0 .. 15: the deepest peak rank counted; 0                            */
 } pya_mz_profile_params;
 
+/* Fragment m/z recalibration: what turns a profile into a correction.  A profile that shows a SYSTEMATIC error -- +30 ppm at low
+ * m/z fading to 0 at high m/z -- makes the narrow re-run useless: the true peaks lie outside the narrow window.  The FIT reads
+ * one systematic error per band of m/z off the ppm axis of a profile, the APPLY corrects the m/z of spectra with it on the
+ * device.  The reference has no counterpart.
+ * THE FIT, per slot and band b, over the band's 64 ppm-axis counts h[0..63], every integer 64-bit:
+ *   floor4 = h[0] + h[1] + h[62] + h[63]             the four outermost bins: the flat floor of random matches, times four
+ *   ex[i]  = max(0, 4 h[i] - floor4),  E = sum ex[i]
+ *   the band is FITTED when E >= 4 min_ions; n_signal[b] = floor(E / 4) (saturating at 2^32 - 1)
+ *   for num in 16, 50, 84: j = the smallest bin with 100 cum[j] >= num E (cum the inclusive sum; ex[j] > 0 follows),
+ *                          pos = j + (double)(num E - 100 (cum[j] - ex[j])) / (double)(100 ex[j])
+ *   ppm[b] = (pos50 - 32) / inv_ppm,  spread_ppm[b] = (float)(0.5 (pos84 - pos16) / inv_ppm)
+ *   a band that is not fitted has spread_ppm 0 and copies ppm from the nearest fitted band, the lower index on a tie; a slot
+ *   without a fitted band is all zero apart from n_signal.
+ * Integer sums, one double division per quantile and one per scaling: a host restatement gives EQUAL bytes
+ * (pyascore_amd.rollup.fit_mz_calibration).
+ * THE APPLY, per peak x of a spectrum whose slot is not negative, in double and in this order (ppm[] the slot's knots, which
+ * sit at the CENTRES of the bands; inv_band the caller's double, bands per m/z unit, as in pya_mz_profile_params):
+ *   u = x inv_band - 0.5,  j = clamp(floor(u), 0, 6),  t = clamp(u - j, 0, 1)
+ *   e = ppm[j] + (ppm[j + 1] - ppm[j]) t,  c = e 1e-6,  x' = x - x c
+ * float32 m/z is widened, corrected and rounded once back to float32.  A value that is not finite or not positive is copied
+ * bit for bit, so the all-zero record leaves every byte as it was.  With |knots| <= PYA_MZC_MAX_PPM the map is increasing: an
+ * ascending spectrum stays non-descending.  csrc/mz_calibrate.hip. */
+#define PYA_MZC_MAX_PPM 1000
+typedef struct pya_mz_calibration {   /* 128 bytes per run slot; the empty record is all-zero bytes = "no correction" */
+    double   ppm[PYA_MZP_BANDS];        /* systematic error (observed - theoretical) at the CENTRE of band b, in ppm */
+    float    spread_ppm[PYA_MZP_BANDS]; /* half of (q84 - q16) of the band's excess, in ppm; 0 where the band was not fitted */
+    uint32_t n_signal[PYA_MZP_BANDS];   /* floor(E / 4): ions above the flat floor; fitted <=> n_signal >= min_ions */
+} pya_mz_calibration;
+
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
  * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
@@ -727,6 +760,40 @@ int pya_set_mz_profile(pya_handle *h, const int32_t *run, uint64_t n_psm, uint64
 /* The table of the last batch call on this handle that was given PYA_FLAG_MZ_PROFILE: out[n_slots], n_slots as lent (anything
  * else: PYA_ERR_ARG).  PYA_ERR_STATE when the last batch was scored without the flag. */
 int pya_last_batch_mz_profile(pya_handle *h, pya_mz_profile *out, uint64_t n_slots);
+/* Fits d_table[n_slots] (device memory, pya_mz_profile) into d_cal[n_slots] (device memory; every byte of every record is
+ * written): one launch of csrc/mz_calibrate.hip on hip_stream, one wavefront per slot, stream-ordered, no host wait and no
+ * allocation.  Of params only inv_ppm is used.  PYA_ERR_ARG, with nothing launched: NULL where an array is needed with
+ * n_slots > 0, n_slots above 2^31 - 1, params that pya_plan_mz_profile would refuse, min_ions == 0.  n_slots == 0 is a no-op. */
+int pya_mz_profile_fit(pya_handle *h, const pya_mz_profile *d_table, uint64_t n_slots, const pya_mz_profile_params *params,
+                       uint32_t min_ions, void *hip_stream, pya_mz_calibration *d_cal);
+/* The same for a table on the host: uploads, runs on the handle's stream, downloads and waits (as pya_rollup_flr_host). */
+int pya_mz_profile_fit_host(pya_handle *h, const pya_mz_profile *table, uint64_t n_slots, const pya_mz_profile_params *params,
+                            uint32_t min_ions, pya_mz_calibration *out);
+/* Corrects the m/z of n_spectra spectra on the device (the APPLY above): d_spectra->mz of d_spectra->mz_type (device memory;
+ * the intensities are not touched and may be NULL), d_peak_off[n_spectra + 1], d_run[n_spectra] the slot of every spectrum
+ * (NULL: slot 0; negative: left as it is), d_cal[n_slots], inv_band (finite and positive), d_mz_out of the same element type
+ * (may equal d_spectra->mz), d_over two words zeroed by the caller.  One launch on hip_stream, stream-ordered, no host wait and
+ * no allocation.  A spectrum whose slot is at or above n_slots, or whose record has a knot that is not finite or exceeds
+ * PYA_MZC_MAX_PPM in magnitude, is copied unchanged and counted in d_over[0], the smallest such spectrum in d_over[1] as
+ * 0xffffffff - spectrum.  No write lies outside d_mz_out[0 .. peak_off[n_spectra]).  PYA_ERR_ARG, with nothing launched: NULL
+ * where an array is needed, an unknown mz_type, n_spectra above 2^32 - 2, n_slots above 2^31 - 1, an inv_band that is not
+ * finite and positive.  n_spectra == 0 is a no-op. */
+int pya_recalibrate_spectra(pya_handle *h, const pya_typed_spectra *d_spectra, const int64_t *d_peak_off, uint64_t n_spectra,
+                            const int32_t *d_run, const pya_mz_calibration *d_cal, uint64_t n_slots, double inv_band, void *hip_stream,
+                            void *d_mz_out, uint32_t *d_over);
+/* Lends the library what the NEXT batch call with PYA_FLAG_RECALIBRATE corrects its spectra with: run[n_psm], one slot per PSM
+ * (negative: the PSM asks for no correction), or NULL: slot 0, host memory that must stay valid until that call returns;
+ * cal[n_slots], host memory, copied; inv_band.  The batch call corrects every chunk's spectra in place in the library's own
+ * device copy on the run stream, before the first kernel that reads them; the caller's arrays are never written.  With shared
+ * spectra a spectrum takes the slot of its PSMs: PSMs of one spectrum that name different non-negative slots are PYA_ERR_ARG
+ * naming the PSM; a spectrum whose PSMs are all negative, or that no PSM refers to, is left alone.  A slot at or above n_slots:
+ * PYA_ERR_LIMIT.  Every result of the flagged batch is bit-equal to the same batch scored without the flag on arrays corrected
+ * by the definition above, whatever the route or the cut into chunks; with PYA_FLAG_MZ_PROFILE the profile is that of the
+ * corrected spectra (the residual errors).  PYA_FLAG_KEEP with this flag is PYA_ERR_ARG.  Lifetime and the remaining refusals
+ * are pya_set_mz_profile's.  PYA_ERR_ARG here: n_psm or n_slots above 2^31 - 1, NULL cal with n_slots > 0, a knot that is not
+ * finite or exceeds PYA_MZC_MAX_PPM in magnitude, an inv_band that is not finite and positive. */
+int pya_set_recalibration(pya_handle *h, const int32_t *run, uint64_t n_psm, const pya_mz_calibration *cal, uint64_t n_slots,
+                          double inv_band);
 /* The device bytes pya_plan_peptidoforms / pya_peptidoform_reduce need as their workspace for n_entries entries (PSMs of the
  * plan + records of d_prev; records of d_a + d_b): keys double-buffered, the entries, the staged list, digit histograms, tile
  * totals, about 133 bytes per entry; 0 for no entries (and above 2^31 - 1, which the calls refuse). */

@@ -13,7 +13,8 @@ with a line per ranked site assignment: the K best localisations of every PSM, i
 its sites and adds false-localisation rates, ``--site_table_decoys LETTERS`` names decoy residues) and
 ``--peptidoform_table FILE`` with ``--peptidoform_threshold P`` (a line per peptide and reported site assignment) and
 ``--mz_profile FILE`` (the fragment mass-error profile of the whole file, a line per m/z band, unit and bin, and its summary
-in the log) are the additions."""
+in the log) and ``--mz_calibration_out FILE`` / ``--mz_calibration FILE`` (fit an m/z calibration to that profile; score with
+the spectra corrected by one) are the additions."""
 import argparse
 import re
 import sys
@@ -101,6 +102,16 @@ def build_parser():
                         "(da, ppm) and bin with the number of matched fragments of the reported localisations whose m/z error "
                         "falls into it, binned on the device, and print its summary; errors are only seen inside +-mz_error, "
                         "so run wide, read the profile, re-run narrow; the main table does not change")
+    p.add_argument("--mz_calibration_out", type=str, default=None, metavar="FILE",
+                   help="profile the run as --mz_profile does, fit the systematic fragment m/z error per band of m/z on the device "
+                        "and write it to FILE: one line per slot and band (band centre, ppm, spread, signal ions, band width); run "
+                        "wide for this, then re-run narrow with --mz_calibration FILE")
+    p.add_argument("--mz_calibration_min_ions", type=int, default=20, metavar="N",
+                   help="the ions above the flat floor a band of m/z needs to be fitted by --mz_calibration_out (default 20); a band "
+                        "with fewer copies its nearest fitted neighbour")
+    p.add_argument("--mz_calibration", type=str, default=None, metavar="FILE",
+                   help="correct the m/z of every spectrum with the calibration in FILE (written by --mz_calibration_out) on the device "
+                        "before it is scored; together with --mz_profile the profile shows the residual errors")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -164,7 +175,12 @@ def run(args, log=print):
     ranked_rows = [] if args.ranked else None
     site_table_rows = [] if args.site_table else None
     peptidoform_rows = [] if args.peptidoform_table else None
-    profile = [] if args.mz_profile else None
+    profile = [] if args.mz_profile or args.mz_calibration_out else None
+    recalibrate = None
+    if args.mz_calibration:
+        from .rollup import read_mz_calibration
+        cal, band_width = read_mz_calibration(args.mz_calibration)
+        recalibrate = dict(calibration=cal, band_width=band_width)
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -175,7 +191,7 @@ def run(args, log=print):
                               probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth, site_table=site_table_rows,
                               site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
-                              peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile)
+                              peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -186,10 +202,13 @@ def run(args, log=print):
         batch_cli.write_site_table_tsv(site_table_rows, args.site_table, flr=args.site_table_flr)
     if peptidoform_rows is not None:
         batch_cli.write_peptidoform_table_tsv(peptidoform_rows, args.peptidoform_table)
-    if profile is not None:
+    if args.mz_profile:
         batch_cli.write_mz_profile_tsv(profile[0], profile[1], args.mz_profile)
         for line in batch_cli.mz_profile_report(profile[0], profile[1]):
             log("{} -- {}".format(stamp(), line))
+    if args.mz_calibration_out:
+        cal = ascore.fit_mz_calibration(profile[0], profile[1], min_ions=args.mz_calibration_min_ions)
+        batch_cli.write_mz_calibration_tsv(cal, 1.0 / profile[1]["inv_band"], args.mz_calibration_out)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     log("{} -- Ascore Completed".format(stamp()))

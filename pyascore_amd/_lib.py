@@ -19,6 +19,8 @@ PYA_FLAG_RANKED = 256
 PYA_FLAG_ROLLUP = 512
 PYA_FLAG_PEPTIDOFORMS = 1024
 PYA_FLAG_MZ_PROFILE = 2048
+PYA_FLAG_RECALIBRATE = 4096
+PYA_MZC_MAX_PPM = 1000       # the largest knot of a pya_mz_calibration, in ppm
 PYA_MZP_BANDS, PYA_MZP_BINS = 8, 64
 PYA_MZP_CHUNK = 128          # PSMs per workgroup of csrc/mz_profile.hip
 PYA_PFORM_TILE = 1024        # entries per workgroup and sort pass of csrc/peptidoforms.hip
@@ -180,6 +182,7 @@ class MzProfileParams(C.Structure):
 assert C.sizeof(MzProfileParams) == 32, "pya_mz_profile_params is a 32-byte record"
 MZ_PROFILE_DTYPE = [("n_psm", "<u4"), ("n_ions", "<u4"), ("n_rank_skipped", "<u4"), ("out_da", "<u4", (2,)), ("out_ppm", "<u4", (2,)),
                     ("reserved", "<u4"), ("da", "<u4", (PYA_MZP_BANDS, PYA_MZP_BINS)), ("ppm", "<u4", (PYA_MZP_BANDS, PYA_MZP_BINS))]
+MZ_CALIBRATION_DTYPE = [("ppm", "<f8", (PYA_MZP_BANDS,)), ("spread_ppm", "<f4", (PYA_MZP_BANDS,)), ("n_signal", "<u4", (PYA_MZP_BANDS,))]
 
 PYA_F64, PYA_F32 = 0, 1
 
@@ -248,6 +251,10 @@ SYMBOLS = {
     "pya_set_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
     "pya_last_batch_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_plan_mz_profile": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, C.c_uint64, _vp, _vp]),
+    "pya_mz_profile_fit": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp]),
+    "pya_mz_profile_fit_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
+    "pya_recalibrate_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_double, _vp, _vp, _vp]),
+    "pya_set_recalibration": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_double]),
     "pya_peptidoform_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "pya_peptidoform_reduce": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "pya_peptidoform_reduce_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),

@@ -142,6 +142,34 @@ def _mz_profile_request(req, n_psm, mz_error, n_top):
     return dict(run=run, n_slots=n_slots, params=params, c_params=c_params)
 
 
+def _recalibrate_request(req, n_psm):
+    """``score_batch(recalibrate=...)`` checked: dict(cal MZ_CALIBRATION_DTYPE, run int32 | None, band_width, inv_band)"""
+    from .rollup import MZ_CALIBRATION_DTYPE, MZC_MAX_PPM
+    if not isinstance(req, dict):
+        raise ValueError("recalibrate takes a dict: calibration, run, band_width")
+    unknown = set(req) - {"calibration", "run", "band_width"}
+    if unknown:
+        raise ValueError("recalibrate takes calibration, run and band_width; unknown: " + ", ".join(sorted(unknown)))
+    if req.get("calibration") is None:
+        raise ValueError("recalibrate: calibration is missing (pyascore_amd.rollup.MZ_CALIBRATION_DTYPE records, one per run slot)")
+    cal = np.ascontiguousarray(req["calibration"], MZ_CALIBRATION_DTYPE).reshape(-1)
+    if not (np.abs(cal["ppm"]) <= float(MZC_MAX_PPM)).all():
+        raise ValueError("recalibrate: a knot of the calibration is not finite or beyond %d ppm" % MZC_MAX_PPM)
+    run = req.get("run")
+    if run is not None:
+        run = np.asarray(run)
+        if run.ndim != 1 or run.size != n_psm or (run.size and run.dtype.kind not in "iu"):
+            raise ValueError("recalibrate: run is one integer per PSM")
+        if run.size and (int(run.max()) > 0x7FFFFFFF or int(run.min()) < -0x80000000):
+            raise ValueError("recalibrate: run does not fit int32")
+        run = np.ascontiguousarray(run, np.int32)
+    band_width = float(req.get("band_width", 250.0))
+    inv_band = 1.0 / band_width if band_width else float("inf")
+    if not (np.isfinite(inv_band) and inv_band > 0.0):
+        raise ValueError("recalibrate: band_width = %r has no finite positive inverse" % band_width)
+    return dict(cal=cal, run=run, band_width=band_width, inv_band=inv_band)
+
+
 def _rollup_request(rollup, n_psm):
     """``score_batch(rollup=...)`` as contiguous arrays: dict(slot int32, n_slots, threshold, psm_id uint32 | None,
     site_off int64 | None)"""
@@ -401,7 +429,8 @@ class PyAscore:
             self._batch_n = 1
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
-                    site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None):
+                    site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
+                    recalibrate=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -483,6 +512,15 @@ class PyAscore:
         restatement ``mz_profile`` and ``merge_mz_profiles``.  The profile only sees errors inside ``+-mz_error`` of this
         scorer: run wide, read the profile, re-run narrow.
 
+        ``recalibrate=dict(calibration=, run=None, band_width=250.0)`` corrects the m/z of every spectrum on the device before
+        it is scored (``PYA_FLAG_RECALIBRATE``): ``calibration`` is one ``pyascore_amd.rollup.MZ_CALIBRATION_DTYPE`` record per
+        run slot (``fit_mz_calibration`` of a profile), ``run`` one slot per PSM (negative: no correction; None: slot 0),
+        ``band_width`` the width of the bands the calibration was fitted over.  Every result is bit-equal to scoring arrays
+        corrected by ``pyascore_amd.rollup.recalibrate``; the caller's arrays are not written.  PSMs that share a spectrum
+        must agree on its slot.  With ``mz_profile=`` the profile is that of the corrected spectra, the residual errors.  Not
+        with ``keep=True`` (the retained records are replayed from the caller's arrays): correct the arrays with
+        ``pyascore_amd.rollup.recalibrate`` first.
+
         Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
         m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
@@ -493,6 +531,10 @@ class PyAscore:
         pform = None if peptidoforms is None else _peptidoform_request(peptidoforms, int(batch["n_psm"]))
         mzp = None if mz_profile is None or mz_profile is False else _mz_profile_request(mz_profile, int(batch["n_psm"]), self._mz_error,
                                                                                         self._n_top)
+        recal = None if recalibrate is None else _recalibrate_request(recalibrate, int(batch["n_psm"]))
+        if recal is not None and keep:
+            raise ValueError("recalibrate does not go with keep=True: correct the arrays with pyascore_amd.rollup.recalibrate and "
+                             "retain the batch without it")
         if batch.get("spec_of") is not None:
             from .synth import expand_shared_batch, spectrum_order, take_psms
             perm, inv = spectrum_order(batch["spec_of"])
@@ -528,11 +570,15 @@ class PyAscore:
                     mzp_moved = dict(mz_profile if isinstance(mz_profile, dict) else {})
                     if mzp["run"] is not None:
                         mzp_moved["run"] = mzp["run"][perm]
+                recal_moved = None
+                if recal is not None:        # ... and so do the slots of the calibration
+                    recal_moved = dict(calibration=recal["cal"], band_width=recal["band_width"],
+                                       run=None if recal["run"] is None else recal["run"][perm])
                 try:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
                                            site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved,
-                                           peptidoforms=pform_moved, mz_profile=mzp_moved)
+                                           peptidoforms=pform_moved, mz_profile=mzp_moved, recalibrate=recal_moved)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
@@ -658,7 +704,7 @@ class PyAscore:
             (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0) | \
             (_lib.PYA_FLAG_ROLLUP if roll is not None else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if pform is not None else 0) | \
-            (_lib.PYA_FLAG_MZ_PROFILE if mzp is not None else 0)
+            (_lib.PYA_FLAG_MZ_PROFILE if mzp is not None else 0) | (_lib.PYA_FLAG_RECALIBRATE if recal is not None else 0)
         # for this call; the handle's own settings come back
         cap_before = k_before = None
         if (sites or probs or ranked_k or roll is not None or pform is not None) and site_sig_cap is not None:
@@ -675,6 +721,9 @@ class PyAscore:
                 rc = self._lib.pya_set_peptidoforms(self._h, _as_ptr(pform["group"]), n, pform["threshold"], _as_ptr(pform["psm_id"]))
             if not rc and mzp is not None:
                 rc = self._lib.pya_set_mz_profile(self._h, _as_ptr(mzp["run"]), n, mzp["n_slots"], C.byref(mzp["c_params"]))
+            if not rc and recal is not None:
+                rc = self._lib.pya_set_recalibration(self._h, _as_ptr(recal["run"]), n, _as_ptr(recal["cal"]), recal["cal"].size,
+                                                     recal["inv_band"])
             if not rc:
                 rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         finally:
@@ -783,6 +832,23 @@ class PyAscore:
         if rc:
             self._raise(rc)
         return off
+
+    def fit_mz_calibration(self, table, params, min_ions=20):
+        """The m/z calibration of a mass-error profile, fitted on the device (``pya_mz_profile_fit_host``): ``table`` is a
+        ``pyascore_amd.rollup.MZ_PROFILE_DTYPE`` array as ``score_batch(mz_profile=...)`` returns it, ``params`` the
+        ``mz_profile_params`` it was binned with, ``min_ions`` the signal ions a band needs to be fitted.  Returns one
+        ``pyascore_amd.rollup.MZ_CALIBRATION_DTYPE`` record per slot; ``pyascore_amd.rollup.fit_mz_calibration`` gives the
+        same bytes on the host."""
+        from .rollup import MZ_CALIBRATION_DTYPE, MZ_PROFILE_DTYPE
+        table = np.ascontiguousarray(table, MZ_PROFILE_DTYPE).reshape(-1)
+        if int(min_ions) != min_ions or not 0 <= int(min_ions) <= 0xFFFFFFFF:
+            raise ValueError("fit_mz_calibration: min_ions must be in 1 .. 2^32 - 1")
+        c_params = _lib.MzProfileParams(params["inv_da"], params["inv_ppm"], params["inv_band"], params["max_rank"], 0)
+        out = np.zeros(table.size, MZ_CALIBRATION_DTYPE)
+        rc = self._lib.pya_mz_profile_fit_host(self._h, _as_ptr(table), table.size, C.byref(c_params), int(min_ions), _as_ptr(out))
+        if rc:
+            self._raise(rc)
+        return out
 
     def rollup_flr(self, table, cls=None, reported_only=False):
         """Site FLR of a roll-up table on the device (``pya_rollup_flr_host``): ``table`` is a ``ROLLUP_DTYPE`` array as

@@ -46,6 +46,8 @@ PEPTIDOFORM_TABLE_COLUMNS = ("Peptide", "Positions", "PSMs", "Confident", "BestS
                              "Isomers")
 # ``--mz_profile FILE``: one line per slot, band, unit and bin of the fragment mass-error profile (pya_mz_profile)
 MZ_PROFILE_COLUMNS = ("Slot", "Band", "Unit", "Bin", "Low", "High", "Count")
+# ``--mz_calibration_out FILE``: one line per slot and band of the m/z calibration fitted to the profile (pya_mz_calibration)
+MZ_CALIBRATION_COLUMNS = ("Slot", "Band", "BandCentre", "Ppm", "SpreadPpm", "SignalIons", "BandWidth")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
 
 
@@ -158,7 +160,8 @@ def pack_hits(picked, scans):
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
-             site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None):
+             site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
+             recalibrate=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -187,7 +190,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     the "confident" cut on a PSM's smallest site probability; the main table does not change.
     ``mz_profile``: a list that receives the fragment mass-error profile of ALL scored PSMs as slot 0: the one-record table
     (``pyascore_amd.rollup.MZ_PROFILE_DTYPE``) and the parameters it was binned with (``mz_profile_rows``,
-    ``write_mz_profile_tsv``, ``mz_profile_report``); the main table does not change."""
+    ``write_mz_profile_tsv``, ``mz_profile_report``); the main table does not change.
+    ``recalibrate``: ``dict(calibration=, band_width=)`` as ``PyAscore.score_batch(recalibrate=...)`` takes it: the m/z of every
+    spectrum is corrected with slot 0 of the calibration on the device before it is scored (``read_mz_calibration`` gives both
+    from the file ``write_mz_calibration_tsv`` wrote); every table is then that of the corrected spectra."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -212,6 +218,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         stages["peptidoforms"] = dict(group=group, threshold=float(peptidoform_threshold))
     if mz_profile is not None:
         stages["mz_profile"] = dict(n_slots=1)
+    if recalibrate is not None:
+        stages["recalibrate"] = dict(recalibrate)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything
@@ -363,6 +371,15 @@ def write_mz_profile_tsv(table, params, path):
     with open(path, "w") as out:
         out.write("\t".join(MZ_PROFILE_COLUMNS) + "\n")
         for row in mz_profile_rows(table, params):
+            out.write("\t".join(str(f) for f in row) + "\n")
+
+
+def write_mz_calibration_tsv(cal, band_width, path):
+    """The ``--mz_calibration_out`` file: ``pyascore_amd.rollup.mz_calibration_rows`` under ``MZ_CALIBRATION_COLUMNS``;
+    ``pyascore_amd.rollup.read_mz_calibration`` reads it back to the same bytes."""
+    with open(path, "w") as out:
+        out.write("\t".join(MZ_CALIBRATION_COLUMNS) + "\n")
+        for row in site_rollup.mz_calibration_rows(cal, band_width):
             out.write("\t".join(str(f) for f in row) + "\n")
 
 

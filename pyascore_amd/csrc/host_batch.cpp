@@ -460,6 +460,56 @@ static int mzp_end(pya_handle *h, const pya_handle::MzpLoan &loan) {
     return PYA_OK;
 }
 
+/* PYA_FLAG_RECALIBRATE: the loan of pya_set_recalibration becomes the call's.  Everything that can be refused is refused here,
+ * before anything is scored: a slot outside the records, PSMs of one spectrum that name different slots.  The slot of every
+ * SPECTRUM of the batch is settled once for the whole call (a spectrum whose PSMs a chunk cut separates travels with both
+ * parts and must be corrected alike in both), and the records go to the device. */
+static int recal_begin(pya_handle *h, pya_handle::RecalLoan *loan, const pya_batch *b, const SpecShare *sh, uint32_t flags) {
+    *loan = std::move(h->recal_loan);
+    h->recal_loan = pya_handle::RecalLoan{};                  /* (the loan ends with this call, whatever it returns) */
+    if (!loan->set) return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_RECALIBRATE without a calibration: call pya_set_recalibration before the batch call");
+    if (loan->n_psm != b->n_psm)
+        return h->fail(PYA_ERR_ARG, -1, "pya_set_recalibration lent the run slots of %llu PSMs, the batch has %llu", (unsigned long long)loan->n_psm,
+                       (unsigned long long)b->n_psm);
+    if (flags & PYA_FLAG_KEEP)
+        return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_RECALIBRATE does not go with PYA_FLAG_KEEP: correct the arrays (pya_recalibrate_spectra) and retain "
+                                        "the batch without the flag");
+    const uint64_t n_spec = sh ? sh->n_spectra : b->n_psm;
+    loan->spec_slot.assign((size_t)n_spec, -1);
+    for (uint64_t i = 0; i < b->n_psm; i++) {
+        const int32_t r = loan->run ? loan->run[i] : 0;
+        if (r < 0) continue;
+        if ((uint64_t)r >= loan->n_slots)
+            return h->fail(PYA_ERR_LIMIT, (int64_t)i, "PSM %llu: run slot %d is at or above the %llu records of pya_set_recalibration",
+                           (unsigned long long)i, r, (unsigned long long)loan->n_slots);
+        int32_t &slot = loan->spec_slot[sh ? sh->spec_of[i] : i];
+        if (slot >= 0 && slot != r)
+            return h->fail(PYA_ERR_ARG, (int64_t)i, "PSM %llu: run slot %d, another PSM of its spectrum names slot %d: a spectrum is corrected once",
+                           (unsigned long long)i, r, slot);
+        slot = r;
+    }
+    if (b->n_psm == 0) return PYA_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, h->d_recal.upload(loan->cal.data(), loan->cal.size(), nullptr));
+    HIPCHK(h, hipStreamSynchronize(nullptr));                 /* (the chunks' streams do not wait for the null stream) */
+    return PYA_OK;
+}
+
+/* ... the plan's spectra [spec_lo, spec_lo + n_spec) corrected in place in the library's device copy on `st`, in front of the
+ * plan's run: the first kernel that reads them is behind this one on the same stream.  (The slots were checked by
+ * recal_begin and the records by pya_set_recalibration, so the kernel's report stays empty.) */
+static int recal_before_run(pya_handle *h, pya_plan *p, const pya_handle::RecalLoan &loan, uint64_t spec_lo, uint32_t mz_type, hipStream_t st) {
+    const uint64_t ns = p->n_spec;
+    if (p->n_psm == 0 || ns == 0) return PYA_OK;
+    HIPCHK(h, p->d_recal_slot.alloc((size_t)ns));
+    HIPCHK(h, p->d_recal_over.alloc(2));
+    HIPCHK(h, hipMemcpyAsync(p->d_recal_slot.p, loan.spec_slot.data() + spec_lo, (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemsetAsync(p->d_recal_over.p, 0, 2 * sizeof(uint32_t), st));
+    const pya_typed_spectra d_sp = {p->d_mz.p, nullptr, mz_type, PYA_F64};
+    return pya_recalibrate_spectra(h, &d_sp, p->d_peak_off.p, ns, p->d_recal_slot.p, h->d_recal.p, loan.n_slots, loan.inv_band, st, p->d_mz.p,
+                                   p->d_recal_over.p);
+}
+
 /* pya_score_batch_named: the handle's pinned block for the records of a call's n_q queries -- [n_q] pya_named, [n_q * n_top]
  * counts, [n_q * n_top] scores -- zeroed */
 static int named_host_block(pya_handle *h, uint64_t n_q) {
@@ -530,7 +580,8 @@ static void named_deliver(pya_handle *h, const NamedReq *nq, uint64_t lo, uint64
 static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShare *sh, const pya_typed_spectra &sp,
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
                                const uint8_t *pre_sites, const NamedReq *nq, const pya_handle::RollupLoan &loan,
-                               const pya_handle::PformLoan &pf_loan, const pya_handle::MzpLoan &mzp_loan) {
+                               const pya_handle::PformLoan &pf_loan, const pya_handle::MzpLoan &mzp_loan,
+                               const pya_handle::RecalLoan &recal_loan) {
     const size_t nchunk = cuts.size() - 1;
     const uint64_t n_q = nq ? (uint64_t)nq->q_off[b->n_psm] : 0;
     /* the spectra [first, last) of chunk c: its PSMs' own unless spectra are shared -- then from the first PSM's to the last
@@ -610,7 +661,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if (b->aux_off) sub.aux_off = b->aux_off + lo;
         IoReq io = {sp, mk, h->io_ring[c & 1].p, h->io_ring[c & 1].p + spec_inten_offset((size_t)np, sp.mz_type), h->run_stream,
                     pre_sites ? pre_sites + lo : nullptr};
-        int rc = plan_create_impl(h, &sub, flags & ~(PYA_FLAG_TIMING | PYA_FLAG_KEEP), &io, sh ? &sub_sh : nullptr, pp);
+        int rc = plan_create_impl(h, &sub, flags & ~(PYA_FLAG_TIMING | PYA_FLAG_KEEP | PYA_FLAG_RECALIBRATE), &io, sh ? &sub_sh : nullptr, pp);
         if (rc) rebase_error(h, lo);
         return rc;
     };
@@ -636,6 +687,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_upload(h, p, mzp_loan, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_RECALIBRATE) && (rc = recal_before_run(h, p, recal_loan, spec_lo(c), sp.mz_type, h->run_stream))) return finish(rc);
         rc = pya_plan_run_typed(p, &d_sp, h->run_stream, &d_out);
         if (rc) return finish(rc);
         /* status + results are adjacent in the arena: one asynchronous copy into pinned memory */
@@ -747,6 +799,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_mzp = mzp_begin(h, &mzp_loan, b->n_psm);
         if (rc_mzp) return rc_mzp;
     }
+    pya_handle::RecalLoan recal_loan;
+    if (flags & PYA_FLAG_RECALIBRATE) {
+        if (b->n_psm && (!b->peak_off || (sh && !sh->spec_of))) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
+        const int rc_rc = recal_begin(h, &recal_loan, b, sh, flags);
+        if (rc_rc) return rc_rc;
+    }
     if (flags & PYA_FLAG_IONS) h->ions_off.assign(b->n_psm + 1, 0);   /* (a PSM no plan reaches has no records) */
     if (flags & PYA_FLAG_SITES) h->sites_off.assign(b->n_psm + 1, 0);
     if (flags & PYA_FLAG_PROBS) h->probs_off.assign(b->n_psm + 1, 0);
@@ -815,8 +873,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_rk = ranked_host_block(h, b);
         if (rc_rk) return rc_rk;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS or _MZ_PROFILE takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS, _MZ_PROFILE or _RECALIBRATE takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_RECALIBRATE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -859,7 +917,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
             }
             cuts.push_back(b->n_psm);
             h->last_chunks = cuts.size() - 1;
-            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan, pf_loan, mzp_loan);
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan, pf_loan, mzp_loan, recal_loan);
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -892,7 +950,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
                 up_err = hipMemcpy(io.d_inten_ext, spec_at(inten, sp.intensity_type, peaks_lo), (size_t)n_peaks * itb, hipMemcpyHostToDevice);
         });
     }
-    int rc = plan_create_impl(h, b, flags & ~PYA_FLAG_TIMING, &io, sh, &p);
+    int rc = plan_create_impl(h, b, flags & ~(PYA_FLAG_TIMING | PYA_FLAG_RECALIBRATE), &io, sh, &p);
     if (uploader.joinable()) uploader.join();
     if (rc) return rc;
     if (up_err != hipSuccess) {
@@ -909,6 +967,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_upload(h, p, mzp_loan, 0, nullptr))) return rc;
+    if ((flags & PYA_FLAG_RECALIBRATE) && (rc = recal_before_run(h, p, recal_loan, 0, sp.mz_type, nullptr))) return rc;
     rc = pya_plan_run_typed(p, &d_sp, nullptr, &d_out);
     if (rc) return rc;
     if (p->d2h_bytes <= kStageLimit) {

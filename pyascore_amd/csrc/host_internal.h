@@ -146,6 +146,9 @@ int pya_launch_rollup(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec,
 size_t pya_mz_profile_lds_bytes(uint32_t l_cap);
 int pya_launch_mz_profile(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int32_t *d_run, uint64_t n_slots,
                           const pya_mz_profile_params *prm, void *d_table, uint32_t *d_over, uint32_t l_cap, hipStream_t stream);
+int pya_launch_mz_fit(const void *d_table, uint64_t n_slots, double inv_ppm, uint32_t min_ions, void *d_cal, hipStream_t stream);
+int pya_launch_mz_apply(const void *d_mz, uint32_t mz_type, const int64_t *d_peak_off, uint64_t n_spectra, const int32_t *d_run,
+                        const void *d_cal, uint64_t n_slots, double inv_band, void *d_out, uint32_t *d_over, hipStream_t stream);
 uint64_t pya_flr_layout_bytes(uint64_t n_slots);
 int pya_launch_flr(const void *d_table, uint64_t n_slots, const uint8_t *d_cls, uint32_t reported_only, void *d_work, void *d_out,
                    uint32_t *d_order, uint32_t *d_n_ranked, hipEvent_t *phase, hipStream_t stream);
@@ -439,6 +442,17 @@ struct pya_handle {
     DevBuf<pya_mz_profile> d_mzp;
     std::vector<pya_mz_profile> mzp_host;
     bool mzp_valid = false;
+    /* PYA_FLAG_RECALIBRATE: what pya_set_recalibration lent for the next batch call (the records are copied); the call's
+     * device copy of the records and, per spectrum of the whole batch, the slot it is corrected with (-1: left alone) */
+    struct RecalLoan {
+        const int32_t *run = nullptr;
+        uint64_t n_psm = 0, n_slots = 0;
+        double inv_band = 0.;
+        std::vector<pya_mz_calibration> cal;
+        std::vector<int32_t> spec_slot;
+        bool set = false;
+    } recal_loan;
+    DevBuf<pya_mz_calibration> d_recal;
     pya_plan *kept = nullptr;                 /* plan of the last PYA_FLAG_KEEP batch */
     /* settings only the general kernel takes: every PSM of the scorer goes there (cfg is rebuilt by every setter) */
     bool all_general() const { return n_top != PYA_NTOP || cfg.n_nl > PYA_FAST_NL; }
@@ -808,6 +822,9 @@ struct pya_plan {
     hipEvent_t ev_mzp = nullptr;
     bool mzp_asked = false;
     DevBuf<int32_t> d_mzp_run;
+    /* PYA_FLAG_RECALIBRATE: a pya_score_batch plan's slice of the spectra's slots and the report words of the apply kernel */
+    DevBuf<int32_t> d_recal_slot;
+    DevBuf<uint32_t> d_recal_over;
     uint64_t n_runs = 0;                 /* pya_plan_run calls so far (which set of hand-over counts is in use) */
     bool ran = false;
     bool quiesced = false;               /* the owner has waited for everything that used the buffers */
@@ -977,6 +994,8 @@ static_assert(sizeof(pya_mz_profile) == 4128 && offsetof(pya_mz_profile, n_ions)
                   offsetof(pya_mz_profile, da) == 32 && offsetof(pya_mz_profile, ppm) == 32 + 4 * PYA_MZP_BANDS * PYA_MZP_BINS &&
                   sizeof(pya_mz_profile_params) == 32 && offsetof(pya_mz_profile_params, max_rank) == 24,
               "pya_mz_profile is the 1 032 words mz_profile.hip flushes");
+static_assert(sizeof(pya_mz_calibration) == 128 && offsetof(pya_mz_calibration, spread_ppm) == 64 && offsetof(pya_mz_calibration, n_signal) == 96,
+              "pya_mz_calibration is the 128-byte record mz_calibrate.hip writes");
 static_assert(sizeof(pya_site_flr) == 32 && offsetof(pya_site_flr, n_decoy) == 4 && offsetof(pya_site_flr, err_sum) == 8 &&
                   offsetof(pya_site_flr, flr) == 16 && offsetof(pya_site_flr, decoy_q) == 24,
               "pya_site_flr is two 16-byte stores of flr.hip");

@@ -209,6 +209,8 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_PEPTIDOFORMS: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_MZ_PROFILE)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_MZ_PROFILE: score the PSM as a batch of one (pya_score_batch)");
+    if (flags & PYA_FLAG_RECALIBRATE)
+        return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_RECALIBRATE: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_ROLLUP)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_ROLLUP: score the PSM as a batch of one (pya_score_batch)");
     if (h->kn.no_tiny) return PYA_ERR_STATE;               /* (route switch of the tests: the kernel-per-stage path) */

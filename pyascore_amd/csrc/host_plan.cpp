@@ -857,7 +857,17 @@ int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const Io
     return PYA_OK;
 }
 
+/* a plan never sees host spectra: its user corrects their own device arrays (pya_recalibrate_spectra) before pya_plan_run_typed */
+static int refuse_recalibrate(pya_handle *h, uint32_t flags, pya_plan **out) {
+    if (!h || !(flags & PYA_FLAG_RECALIBRATE)) return PYA_OK;
+    if (out) *out = nullptr;
+    return h->fail(PYA_ERR_ARG, -1, "pya_plan_create does not take PYA_FLAG_RECALIBRATE: call pya_recalibrate_spectra on the device arrays before "
+                                    "pya_plan_run_typed");
+}
+
 int pya_plan_create(pya_handle *h, const pya_batch *b, uint32_t flags, pya_plan **out) {
+    const int rc_flag = refuse_recalibrate(h, flags, out);
+    if (rc_flag) return rc_flag;
     return plan_create_impl(h, b, flags, nullptr, nullptr, out);
 }
 
@@ -865,6 +875,8 @@ int pya_plan_create_shared(pya_handle *h, const pya_batch *b, const uint32_t *sp
                            pya_plan **out) {
     if (!h || !b || !out) return PYA_ERR_ARG;
     *out = nullptr;
+    const int rc_flag = refuse_recalibrate(h, flags, out);
+    if (rc_flag) return rc_flag;
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);
     if (rc) return rc;
     const SpecShare sh = {spec_of, n_spectra, 0u};

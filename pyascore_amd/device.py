@@ -31,7 +31,9 @@ class DevicePlan:
     ``rollup=True``: the probability records rolled into a table of the caller's slots (``pya_plan_rollup``).
     ``peptidoforms()`` / ``peptidoforms=True``: the PSMs collapsed onto one record per (group, best_sig)
     (``pya_plan_peptidoforms``); ``peptidoform_reduce()`` merges such lists.  ``mz_profile()`` / ``mz_profile=True``: the
-    fragment mass errors of the reported localisations binned per run slot (``pya_plan_mz_profile``)."""
+    fragment mass errors of the reported localisations binned per run slot (``pya_plan_mz_profile``).
+    ``fit_mz_calibration()`` turns such a table into an m/z calibration and ``recalibrate()`` corrects a device m/z tensor with
+    it (``pya_mz_profile_fit``, ``pya_recalibrate_spectra``), so run -> profile -> fit -> correct -> run again needs no host copy."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
                  ranked=False, rollup=False, peptidoforms=False, mz_profile=False):
@@ -434,6 +436,67 @@ class DevicePlan:
             self.scorer._raise(rc)
         return table
 
+    def fit_mz_calibration(self, table, params, min_ions=20, out=None):
+        """The m/z calibration of a profile ``table`` (the ``torch.uint8`` device tensor ``[n_slots, 4128]`` of ``mz_profile()``)
+        as a ``torch.uint8`` device tensor ``[n_slots, 128]``, one ``pya_mz_calibration`` per slot (``pya_mz_profile_fit``;
+        ``mz_calibration_records`` turns a host copy into the structured array).  ``params``: the ``mz_profile_params`` the
+        table was binned with; ``min_ions``: the signal ions a band needs to be fitted.  One launch on torch's current stream;
+        nothing waits on the host.  Returns ``out`` (every byte of it is written)."""
+        torch = self._torch
+        if table.dtype != torch.uint8 or table.dim() != 2 or table.shape[1] != MZ_PROFILE_DTYPE.itemsize or not table.is_contiguous() \
+                or not table.is_cuda:
+            raise ValueError("table must be a contiguous uint8 device tensor of shape (n_slots, %d)" % MZ_PROFILE_DTYPE.itemsize)
+        shape = (table.shape[0], MZ_CALIBRATION_DTYPE.itemsize)
+        if out is None:
+            with torch.cuda.device(self.device):
+                out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous uint8 device tensor of shape %r" % (shape,))
+        c_params = _lib.MzProfileParams(params["inv_da"], params["inv_ppm"], params["inv_band"], params["max_rank"], 0)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_mz_profile_fit(self.scorer._h, table.data_ptr(), table.shape[0], C.byref(c_params), int(min_ions), stream,
+                                          out.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return out
+
+    def recalibrate(self, d_mz, peak_off, cal, run=None, band_width=250.0, out=None):
+        """Corrects the m/z tensor of spectra with a calibration on the device (``pya_recalibrate_spectra``): ``d_mz`` a
+        contiguous float64 or float32 device tensor, ``peak_off`` an ``int64`` device tensor ``[n_spectra + 1]``, ``cal`` the
+        ``torch.uint8`` device tensor ``[n_slots, 128]`` of ``fit_mz_calibration()``, ``run`` an ``int32`` device tensor
+        ``[n_spectra]`` with the slot of every spectrum (negative: left as it is) or None: slot 0, ``band_width`` the width of
+        the bands the calibration was fitted over.  ``out``: a tensor like ``d_mz`` -- ``d_mz`` itself corrects in place --, new
+        when None.  One launch on torch's current stream; nothing waits on the host.  ``pyascore_amd.rollup.recalibrate`` gives
+        the same bytes.  A spectrum whose slot is outside ``cal`` or whose record has a knot that is not finite or beyond 1000 ppm
+        is copied unchanged and counted in ``last_recalibrate_over`` (an ``int32`` device tensor of two words: the count, and
+        0xffffffff minus the first such spectrum).  Returns ``out``."""
+        torch = self._torch
+        if d_mz.dtype not in (torch.float64, torch.float32) or not d_mz.is_cuda or not d_mz.is_contiguous() or d_mz.dim() != 1:
+            raise ValueError("d_mz must be a contiguous one-dimensional float64 or float32 device tensor")
+        if peak_off.dtype != torch.int64 or peak_off.dim() != 1 or peak_off.numel() < 1 or not peak_off.is_contiguous() or not peak_off.is_cuda:
+            raise ValueError("peak_off must be a contiguous int64 device tensor of n_spectra + 1 entries")
+        n_spec = peak_off.numel() - 1
+        if cal.dtype != torch.uint8 or cal.dim() != 2 or cal.shape[1] != MZ_CALIBRATION_DTYPE.itemsize or not cal.is_contiguous() or not cal.is_cuda:
+            raise ValueError("cal must be a contiguous uint8 device tensor of shape (n_slots, %d)" % MZ_CALIBRATION_DTYPE.itemsize)
+        if run is not None and (run.dtype != torch.int32 or tuple(run.shape) != (n_spec,) or not run.is_contiguous() or not run.is_cuda):
+            raise ValueError("run must be a contiguous int32 device tensor of %d entries" % n_spec)
+        if out is None:
+            out = torch.empty_like(d_mz)
+        if out.dtype != d_mz.dtype or tuple(out.shape) != tuple(d_mz.shape) or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous device tensor of the dtype and shape of d_mz")
+        band_width = float(band_width)
+        inv_band = 1.0 / band_width if band_width else float("inf")
+        with torch.cuda.device(self.device):
+            self.last_recalibrate_over = torch.zeros(2, dtype=torch.int32, device=self.device)
+        sp = _lib.TypedSpectra(d_mz.data_ptr(), None, _lib.spectrum_type(d_mz.dtype), _lib.PYA_F64)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_recalibrate_spectra(self.scorer._h, C.byref(sp), peak_off.data_ptr(), n_spec, None if run is None else run.data_ptr(),
+                                               cal.data_ptr(), cal.shape[0], inv_band, stream, out.data_ptr(),
+                                               self.last_recalibrate_over.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return out
+
     def timings_ms(self):
         """(bin_spectra, score_signatures, score_localize, localize) kernel-family durations of the
         last run; synchronises."""
@@ -488,6 +551,7 @@ ROLLUP_DTYPE = np.dtype(_lib.ROLLUP_DTYPE)
 FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)
 PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)
 MZ_PROFILE_DTYPE = np.dtype(_lib.MZ_PROFILE_DTYPE)
+MZ_CALIBRATION_DTYPE = np.dtype(_lib.MZ_CALIBRATION_DTYPE)
 
 
 def evidence_rows(raw):
@@ -564,6 +628,16 @@ def mz_profile_records(raw):
     if a.ndim != 2 or a.shape[1] != MZ_PROFILE_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, %d)" % MZ_PROFILE_DTYPE.itemsize)
     return a.view(MZ_PROFILE_DTYPE).reshape(a.shape[0])
+
+
+def mz_calibration_records(raw):
+    """A host copy of the calibration of ``DevicePlan.fit_mz_calibration()`` (``.cpu().numpy()``, uint8 ``[n_slots, 128]``) as
+    the structured array ``PyAscore.fit_mz_calibration`` returns (``pyascore_amd.rollup.MZ_CALIBRATION_DTYPE``); a view, no
+    copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != MZ_CALIBRATION_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % MZ_CALIBRATION_DTYPE.itemsize)
+    return a.view(MZ_CALIBRATION_DTYPE).reshape(a.shape[0])
 
 
 def peptidoform_records(raw):

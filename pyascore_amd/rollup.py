@@ -23,6 +23,12 @@ Fragment mass-error profile: ``score_batch(mz_profile=dict(run=..., n_slots=...)
 (the 4 128-byte ``pya_mz_profile``) per run slot; ``mz_profile_params`` is the only place the three inverse widths are
 computed, ``mz_profile`` restates the stage over ion records with the same IEEE operations (equal counts, not close ones),
 ``merge_mz_profiles`` adds tables and ``mz_profile_summary`` reads a tolerance off one.
+
+Fragment m/z recalibration: ``fit_mz_calibration`` reads one systematic error per band of m/z off a profile
+(``MZ_CALIBRATION_DTYPE``, the 128-byte ``pya_mz_calibration``) and ``recalibrate`` corrects m/z arrays with it -- the host
+forms of ``PyAscore.fit_mz_calibration`` / ``DevicePlan.fit_mz_calibration`` and of ``DevicePlan.recalibrate`` /
+``score_batch(recalibrate=...)``, with the same bytes; ``mz_calibration_rows`` / ``read_mz_calibration`` are the file of
+``--mz_calibration_out`` / ``--mz_calibration``, ``suggest_mz_error`` a convenience for the narrow re-run.
 """
 import numpy as np
 
@@ -38,6 +44,9 @@ PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)    # pya_peptidoform, 48 by
 assert PEPTIDOFORM_DTYPE.itemsize == 48
 MZ_PROFILE_DTYPE = np.dtype(_lib.MZ_PROFILE_DTYPE)  # pya_mz_profile, 4 128 bytes
 assert MZ_PROFILE_DTYPE.itemsize == 4128
+MZ_CALIBRATION_DTYPE = np.dtype(_lib.MZ_CALIBRATION_DTYPE)  # pya_mz_calibration, 128 bytes
+assert MZ_CALIBRATION_DTYPE.itemsize == 128
+MZC_MAX_PPM = _lib.PYA_MZC_MAX_PPM
 MZP_BANDS, MZP_BINS = _lib.PYA_MZP_BANDS, _lib.PYA_MZP_BINS
 TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
@@ -444,3 +453,145 @@ def mz_profile_summary(table, params=None):
                              band_medians=[where(b, 0.5) for b in bands])
         out.append(row)
     return out
+
+
+def fit_mz_calibration(table, params, min_ions=20):
+    """One ``MZ_CALIBRATION_DTYPE`` record per slot of a profile ``table`` (``MZ_PROFILE_DTYPE``): the definition of
+    ``pya_mz_calibration`` in include/pyascore_hip.h, integer sums and the same IEEE divisions, so the bytes are those of
+    ``pya_mz_profile_fit``.  Per band of m/z the four outermost bins of the ppm axis give the flat floor of random matches;
+    what stands above it is the signal, its median the systematic error ``ppm`` at the band's centre, half of its 16 % .. 84 %
+    width ``spread_ppm``; a band with fewer than ``min_ions`` signal ions copies the nearest fitted band (the lower on a tie).
+    ``params``: ``mz_profile_params(...)`` the table was binned with (``inv_ppm`` is what is used)."""
+    table = np.ascontiguousarray(table, MZ_PROFILE_DTYPE).reshape(-1)
+    inv_ppm = float(params["inv_ppm"])
+    if not (np.isfinite(inv_ppm) and inv_ppm > 0.0):
+        raise ValueError("fit_mz_calibration: inv_ppm = %r is not a finite positive number" % inv_ppm)
+    if int(min_ions) != min_ions or not 1 <= int(min_ions) <= 0xFFFFFFFF:
+        raise ValueError("fit_mz_calibration: min_ions must be in 1 .. 2^32 - 1")
+    min_ions = int(min_ions)
+    out = np.zeros(table.size, MZ_CALIBRATION_DTYPE)
+    half = MZP_BINS // 2
+    for s, rec in enumerate(table):
+        fitted = []
+        for b in range(MZP_BANDS):
+            h = [int(v) for v in rec["ppm"][b]]
+            floor4 = h[0] + h[1] + h[MZP_BINS - 2] + h[MZP_BINS - 1]
+            ex = [max(0, 4 * v - floor4) for v in h]
+            cum, run = [], 0
+            for v in ex:
+                run += v
+                cum.append(run)
+            E = run
+            out["n_signal"][s, b] = min(E // 4, 0xFFFFFFFF)
+            if E < 4 * min_ions:
+                continue
+            pos = {}
+            for num in (16, 50, 84):
+                j = next(i for i in range(MZP_BINS) if 100 * cum[i] >= num * E)
+                pos[num] = float(j) + float(num * E - 100 * (cum[j] - ex[j])) / float(100 * ex[j])
+            out["ppm"][s, b] = (pos[50] - float(half)) / inv_ppm
+            out["spread_ppm"][s, b] = np.float32((0.5 * (pos[84] - pos[16])) / inv_ppm)
+            fitted.append(b)
+        for b in range(MZP_BANDS):
+            if fitted and b not in fitted:
+                out["ppm"][s, b] = out["ppm"][s, min(fitted, key=lambda f: (abs(f - b), f))]
+    return out
+
+
+def _check_calibration(cal):
+    cal = np.ascontiguousarray(cal, MZ_CALIBRATION_DTYPE).reshape(-1)
+    bad = ~(np.abs(cal["ppm"]) <= float(MZC_MAX_PPM))                   # (nan fails the comparison)
+    if bad.any():
+        raise ValueError("calibration slot %d has a knot that is not finite or beyond %d ppm" % (int(np.flatnonzero(bad.any(axis=1))[0]), MZC_MAX_PPM))
+    return cal
+
+
+def recalibrate(mz, peak_off, run, cal, band_width=250.0):
+    """The m/z array of spectra corrected with a calibration: the APPLY of ``pya_mz_calibration``, operation for operation in
+    float64, so the bytes are those of ``pya_recalibrate_spectra``.  ``mz``: float64 or float32 (the result keeps the dtype:
+    float32 is widened, corrected and rounded back once), ``peak_off[n_spectra + 1]``, ``run``: one slot per spectrum
+    (negative: left as it is) or None (slot 0), ``cal``: ``MZ_CALIBRATION_DTYPE`` records.  The knots sit at the centres of the
+    bands and the error is linear between them, constant outside; a value that is not finite or not positive is copied.  A
+    slot outside ``cal`` or a knot that is not finite or beyond ``MZC_MAX_PPM`` is a ValueError.  Returns a new array."""
+    mz = np.asarray(mz)
+    if mz.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("recalibrate: mz is float64 or float32, not %s" % mz.dtype)
+    peak_off = np.asarray(peak_off, np.int64)
+    n_spec = peak_off.size - 1
+    cal = _check_calibration(cal)
+    inv_band = 1.0 / float(band_width) if band_width else float("inf")
+    if not (np.isfinite(inv_band) and inv_band > 0.0):
+        raise ValueError("recalibrate: band_width = %r has no finite positive inverse" % band_width)
+    run = np.zeros(n_spec, np.int64) if run is None else np.asarray(run).astype(np.int64)
+    if run.shape != (n_spec,):
+        raise ValueError("recalibrate: run is one slot per spectrum")
+    if (run >= cal.size).any():
+        raise ValueError("recalibrate: spectrum %d names slot %d of %d" % (int(np.flatnonzero(run >= cal.size)[0]), int(run.max()), cal.size))
+    out = mz.copy()
+    lo, hi = int(peak_off[0]), int(peak_off[-1])
+    slot = np.repeat(run, np.diff(peak_off))
+    x = mz[lo:hi].astype(np.float64)
+    take = (slot >= 0) & (x > 0.0) & (x < np.inf)
+    x, slot = x[take], slot[take]
+    u = x * inv_band - 0.5
+    fl = np.floor(u)
+    top = float(MZP_BANDS - 2)
+    j = np.where(~(fl >= 0.0), 0.0, np.where(~(fl < top), top, fl))
+    rel = u - j
+    t = np.where(~(rel >= 0.0), 0.0, np.where(~(rel < 1.0), 1.0, rel))
+    j = j.astype(np.int64)
+    a, b = cal["ppm"][slot, j], cal["ppm"][slot, j + 1]
+    step = (b - a) * t
+    e = a + step
+    c = e * 1e-6
+    shift = x * c
+    view = out[lo:hi]
+    view[take] = (x - shift).astype(mz.dtype)
+    return out
+
+
+def mz_calibration_rows(cal, band_width=250.0):
+    """The ``--mz_calibration_out`` table: one row ``[slot, band, band centre, ppm, spread, signal ions, band width]`` per slot
+    and band; floats as ``repr``, so ``read_mz_calibration`` gives the same bytes back."""
+    cal = np.ascontiguousarray(cal, MZ_CALIBRATION_DTYPE).reshape(-1)
+    width = float(band_width)
+    return [[s, b, repr((b + 0.5) * width), repr(float(rec["ppm"][b])), repr(float(rec["spread_ppm"][b])), int(rec["n_signal"][b]), repr(width)]
+            for s, rec in enumerate(cal) for b in range(MZP_BANDS)]
+
+
+def read_mz_calibration(path):
+    """``(cal, band_width)`` of a file of ``mz_calibration_rows`` under a header line (``--mz_calibration_out`` writes it):
+    ``MZ_CALIBRATION_DTYPE`` records, one per slot, and the width of the bands they were fitted over."""
+    rows = []
+    with open(path) as f:
+        next(f, None)
+        for line in f:
+            if line.strip():
+                rows.append(line.rstrip("\n").split("\t"))
+    if not rows:
+        return np.zeros(0, MZ_CALIBRATION_DTYPE), 250.0
+    if any(len(r) != 7 for r in rows):
+        raise ValueError("%s: a calibration line has seven columns" % path)
+    widths = {float(r[6]) for r in rows}
+    if len(widths) != 1:
+        raise ValueError("%s: more than one band width" % path)
+    cal = np.zeros(max(int(r[0]) for r in rows) + 1, MZ_CALIBRATION_DTYPE)
+    seen = set()
+    for r in rows:
+        s, b = int(r[0]), int(r[1])
+        if not 0 <= b < MZP_BANDS or s < 0 or (s, b) in seen:
+            raise ValueError("%s: slot %d band %d is out of range or given twice" % (path, s, b))
+        seen.add((s, b))
+        cal["ppm"][s, b], cal["spread_ppm"][s, b], cal["n_signal"][s, b] = float(r[3]), np.float32(float(r[4])), int(r[5])
+    if len(seen) != cal.size * MZP_BANDS:
+        raise ValueError("%s: every slot needs its %d bands" % (path, MZP_BANDS))
+    return cal, widths.pop()
+
+
+def suggest_mz_error(cal, mz_max, k=3.0):
+    """A convenience, not a rule: ``k`` times the largest fitted ``spread_ppm`` at ``mz_max``, in Da -- a tolerance for the
+    narrow re-run on recalibrated spectra that covers ``k`` spreads of the worst band at the highest fragment m/z.  0.0 when
+    nothing was fitted."""
+    cal = np.ascontiguousarray(cal, MZ_CALIBRATION_DTYPE).reshape(-1)
+    worst = float(cal["spread_ppm"].max()) if cal.size else 0.0
+    return float(k) * worst * 1e-6 * float(mz_max)
