@@ -470,6 +470,33 @@ typedef struct pya_mz_calibration {   /* 128 bytes per run slot; the empty recor
     uint32_t n_signal[PYA_MZP_BANDS];   /* floor(E / 4): ions above the flat floor; fitted <=> n_signal >= min_ions */
 } pya_mz_calibration;
 
+/* Deisotoping: the one step in front of a run that REMOVES peaks.  High-resolution MS2 spectra carry isotope envelopes; every
+ * M+1 / M+2 satellite that makes the cut of the ten most intense peaks per 100 m/z takes a slot from a real fragment and offers
+ * one more random match.  The filter is a transform of spectra that runs before a plan exists (a plan reads the peak counts on
+ * the host); no kernel of a run knows of it.  The reference has no counterpart.
+ * THE RULE is local and order-free; every spectrum is handled on its own and the output is a subset of its peaks, bits copied.
+ * A spectrum has ascending m/z x[] and intensities y[] (float32 is widened at the load).  Peak j is REMOVED iff there is a peak
+ * i of the same spectrum and a charge z in 1 .. max_charge with, in double and in this order of operations:
+ *   d = x[j] - x[i],  e = d - spacing[z - 1],  fabs(e) <= tol
+ *   m = x[i] (double)z,  b = ratio0 + ratio_per_mz m,  y[j] <= y[i] b
+ * The parent i may itself be a removed peak (M+2 goes because of M+1): no greedy claiming, no dependence on the order peaks are
+ * visited in.  A comparison with a NaN is false, so a peak with a NaN intensity stays and removes nothing.  spacing[] are the
+ * caller's doubles (the Python helper fills step / z on the host: the kernel divides nothing and a host restatement reads the
+ * same bits, pyascore_amd.rollup.deisotope).  The parameters must satisfy: tol finite and >= 0; ratio0 and ratio_per_mz finite;
+ * 1 <= max_charge <= PYA_DEISO_MAX_CHARGE; reserved == 0; spacing[0 .. max_charge) finite, positive and strictly decreasing;
+ * spacing[max_charge - 1] > 2 tol.  So a parent has a strictly lower m/z, hence a lower index, e is monotone in i, and the
+ * lowest peak of a spectrum is always kept: a spectrum that is not empty stays so.
+ * A spectrum that is NOT ASCENDING -- an adjacent pair without x[k - 1] <= x[k]: a descending pair, or a NaN m/z, which no order
+ * holds -- is copied unchanged and reported. */
+#define PYA_DEISO_MAX_CHARGE 8
+typedef struct pya_deisotope_params {   /* 96 bytes */
+    double tol;                             /* half width of the match on the isotope spacing, in m/z units (Da)            */
+    double ratio0, ratio_per_mz;            /* a satellite is at most (ratio0 + ratio_per_mz x[i] z) times its parent        */
+    double spacing[PYA_DEISO_MAX_CHARGE];   /* the isotope spacing at charge z in [z - 1]; entries at and above max_charge  */
+                                            /* are not read                                                                  */
+    uint32_t max_charge, reserved;          /* 1 .. PYA_DEISO_MAX_CHARGE; 0                                                  */
+} pya_deisotope_params;
+
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
  * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
@@ -794,6 +821,34 @@ int pya_recalibrate_spectra(pya_handle *h, const pya_typed_spectra *d_spectra, c
  * finite or exceeds PYA_MZC_MAX_PPM in magnitude, an inv_band that is not finite and positive. */
 int pya_set_recalibration(pya_handle *h, const int32_t *run, uint64_t n_psm, const pya_mz_calibration *cal, uint64_t n_slots,
                           double inv_band);
+/* The device bytes pya_deisotope_spectra needs as its workspace for n_spectra spectra of n_peaks peaks together: one keep bit
+ * per peak in 64-bit words that no two spectra share, and the tile sums of the offset scan; 8 bytes at the least. */
+uint64_t pya_deisotope_workspace_bytes(uint64_t n_spectra, uint64_t n_peaks);
+/* Deisotopes n_spectra spectra on the device (THE RULE at pya_deisotope_params above; csrc/deisotope.hip): d_in the m/z and
+ * intensity arrays (device memory, laid out by d_peak_off[n_spectra + 1]), d_out arrays of the same element types and the
+ * input's capacity, d_new_off[n_spectra + 1] the offsets of the filtered spectra (d_new_off[0] = 0), d_over two words zeroed
+ * by the caller.  Three passes on hip_stream -- mark and count, an exclusive scan of the counts, fill --, stream-ordered, no
+ * host wait and no allocation; the caller lends d_work (8-byte aligned, work_bytes >= pya_deisotope_workspace_bytes(n_spectra,
+ * d_peak_off[n_spectra])).  The kept peaks of spectrum s are d_out[d_new_off[s] .. d_new_off[s + 1]), in their order, bit for
+ * bit.  A spectrum that is not ascending is copied unchanged and counted in d_over[0], the smallest such spectrum in d_over[1]
+ * as 0xffffffff - spectrum (as pya_recalibrate_spectra reports).  No write lies outside out[0 .. d_new_off[n_spectra]),
+ * d_new_off[0 .. n_spectra], d_over[0 .. 2) and d_work[0 .. work_bytes): the out elements from d_new_off[n_spectra] up to the
+ * input's length stay as they were.  There is no limit on the peaks of a spectrum beyond int64 offsets: a spectrum over the
+ * scorer's 65 535 peaks may come out under it.  The peak count is on the device, so the host can only check the workspace
+ * against pya_deisotope_workspace_bytes(n_spectra, 0); the kernels clip the offsets to the peaks the lent workspace has bits
+ * for, and a spectrum that reaches beyond them is reported in d_over as well.
+ * PYA_ERR_ARG, with nothing launched: NULL where an array is needed, an out array that is an in array, unknown element types
+ * or types that differ between in and out, float32 m/z beside float64 intensities, a workspace that is misaligned or too
+ * small, parameters outside the conditions above, n_spectra above 2^32 - 2.  n_spectra == 0 writes d_new_off[0] = 0 and
+ * nothing else. */
+int pya_deisotope_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64_t *d_peak_off, uint64_t n_spectra,
+                          const pya_deisotope_params *params, void *hip_stream, void *d_work, uint64_t work_bytes,
+                          const pya_typed_spectra *d_out, int64_t *d_new_off, uint32_t *d_over);
+/* The same over HOST arrays: uploads, runs on the handle's stream with a workspace of its own, downloads
+ * out[0 .. new_off[n_spectra]), new_off and over, and waits (as pya_mz_profile_fit_host).  peak_off[0] must not be
+ * negative and the offsets must not descend (PYA_ERR_ARG); the arrays are read from element 0 to peak_off[n_spectra]. */
+int pya_deisotope_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                               const pya_deisotope_params *params, const pya_typed_spectra *out, int64_t *new_off, uint32_t *over);
 /* The device bytes pya_plan_peptidoforms / pya_peptidoform_reduce need as their workspace for n_entries entries (PSMs of the
  * plan + records of d_prev; records of d_a + d_b): keys double-buffered, the entries, the staged list, digit histograms, tile
  * totals, about 133 bytes per entry; 0 for no entries (and above 2^31 - 1, which the calls refuse). */

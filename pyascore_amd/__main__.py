@@ -14,7 +14,8 @@ its sites and adds false-localisation rates, ``--site_table_decoys LETTERS`` nam
 ``--peptidoform_table FILE`` with ``--peptidoform_threshold P`` (a line per peptide and reported site assignment) and
 ``--mz_profile FILE`` (the fragment mass-error profile of the whole file, a line per m/z band, unit and bin, and its summary
 in the log) and ``--mz_calibration_out FILE`` / ``--mz_calibration FILE`` (fit an m/z calibration to that profile; score with
-the spectra corrected by one) are the additions."""
+the spectra corrected by one) and ``--deisotope`` with ``--deisotope_tol DA``, ``--deisotope_charge Z`` and
+``--deisotope_ratio R`` (remove isotope satellites from every spectrum on the device before it is scored) are the additions."""
 import argparse
 import re
 import sys
@@ -112,6 +113,16 @@ def build_parser():
     p.add_argument("--mz_calibration", type=str, default=None, metavar="FILE",
                    help="correct the m/z of every spectrum with the calibration in FILE (written by --mz_calibration_out) on the device "
                         "before it is scored; together with --mz_profile the profile shows the residual errors")
+    p.add_argument("--deisotope", action="store_true",
+                   help="remove isotope satellites from every spectrum on the device before it is scored (and before "
+                        "--mz_calibration corrects it): a peak goes when a peak one isotope spacing / z below it, z = 1 .. "
+                        "--deisotope_charge, is at least as intense (times --deisotope_ratio); one more transfer of the spectra")
+    p.add_argument("--deisotope_tol", type=float, default=0.01, metavar="DA",
+                   help="with --deisotope: how far the distance of two peaks may be from the isotope spacing, in m/z (default 0.01)")
+    p.add_argument("--deisotope_charge", type=int, default=3, metavar="Z",
+                   help="with --deisotope: the largest charge whose spacing is tried, 1 .. 8 (default 3)")
+    p.add_argument("--deisotope_ratio", type=float, default=1.0, metavar="R",
+                   help="with --deisotope: a satellite is at most R times as intense as its parent (default 1.0)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -128,6 +139,9 @@ def validate_args(args):
             raise ValueError("The fragment type inputed, {}, is not allowed.".format(frag))
     if args.max_fragment_charge < 1:
         raise ValueError("The max fragment charge must be greater than or equal to 1")
+    if getattr(args, "deisotope", False):
+        from .rollup import deisotope_params
+        deisotope_params(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio)
 
 
 def parse_args(argv):
@@ -181,6 +195,7 @@ def run(args, log=print):
         from .rollup import read_mz_calibration
         cal, band_width = read_mz_calibration(args.mz_calibration)
         recalibrate = dict(calibration=cal, band_width=band_width)
+    deisotope = dict(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio) if args.deisotope else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -191,7 +206,8 @@ def run(args, log=print):
                               probs=args.probs, ranked=ranked_rows, ranked_depth=args.ranked_depth, site_table=site_table_rows,
                               site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
-                              peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate)
+                              peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
+                              deisotope=deisotope)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:

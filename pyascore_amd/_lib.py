@@ -186,6 +186,17 @@ MZ_CALIBRATION_DTYPE = [("ppm", "<f8", (PYA_MZP_BANDS,)), ("spread_ppm", "<f4", 
 
 PYA_F64, PYA_F32 = 0, 1
 
+PYA_DEISO_MAX_CHARGE = 8
+
+
+class DeisotopeParams(C.Structure):
+    """pya_deisotope_params: the match width, the intensity ratio, the isotope spacing per charge, the largest charge"""
+    _fields_ = [("tol", C.c_double), ("ratio0", C.c_double), ("ratio_per_mz", C.c_double), ("spacing", C.c_double * PYA_DEISO_MAX_CHARGE),
+                ("max_charge", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(DeisotopeParams) == 96, "pya_deisotope_params is a 96-byte record"
+
 
 def spectrum_type(dtype):
     """PYA_F64 / PYA_F32 for a numpy dtype (or its name: 'float64', 'float32'); anything else is no spectrum type."""
@@ -255,6 +266,11 @@ SYMBOLS = {
     "pya_mz_profile_fit_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
     "pya_recalibrate_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_double, _vp, _vp, _vp]),
     "pya_set_recalibration": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, C.c_double]),
+    "pya_deisotope_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "pya_deisotope_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.POINTER(DeisotopeParams), _vp, _vp, C.c_uint64,
+                                        C.POINTER(TypedSpectra), _vp, _vp]),
+    "pya_deisotope_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.POINTER(DeisotopeParams),
+                                             C.POINTER(TypedSpectra), _vp, _vp]),
     "pya_peptidoform_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "pya_peptidoform_reduce": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "pya_peptidoform_reduce_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),

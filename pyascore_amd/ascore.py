@@ -170,6 +170,22 @@ def _recalibrate_request(req, n_psm):
     return dict(cal=cal, run=run, band_width=band_width, inv_band=inv_band)
 
 
+def _deisotope_request(req):
+    """``score_batch(deisotope=...)`` checked: the dict of ``pyascore_amd.rollup.deisotope_params``"""
+    from .rollup import deisotope_params
+    if req is True:
+        req = {}
+    if not isinstance(req, dict):
+        raise ValueError("deisotope takes a dict: tol, max_charge, step, ratio, ratio_per_mz")
+    unknown = set(req) - {"tol", "max_charge", "step", "ratio", "ratio_per_mz"}
+    if unknown:
+        raise ValueError("deisotope takes tol, max_charge, step, ratio and ratio_per_mz; unknown: " + ", ".join(sorted(unknown)))
+    try:
+        return deisotope_params(**req)
+    except TypeError:
+        raise ValueError("deisotope: tol, step, ratio and ratio_per_mz are numbers, max_charge an integer") from None
+
+
 def _rollup_request(rollup, n_psm):
     """``score_batch(rollup=...)`` as contiguous arrays: dict(slot int32, n_slots, threshold, psm_id uint32 | None,
     site_off int64 | None)"""
@@ -430,7 +446,7 @@ class PyAscore:
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
-                    recalibrate=None):
+                    recalibrate=None, deisotope=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -521,11 +537,31 @@ class PyAscore:
         with ``keep=True`` (the retained records are replayed from the caller's arrays): correct the arrays with
         ``pyascore_amd.rollup.recalibrate`` first.
 
+        ``deisotope=dict(tol=0.01, max_charge=3, step=1.0033548378, ratio=1.0, ratio_per_mz=0.0)`` (or True: the defaults)
+        removes isotope satellites from every spectrum before it is scored: the spectra go through ``deisotope_spectra`` once
+        (a batch with ``spec_of``: each shared spectrum once) and the ordinary call then runs on the filtered arrays with
+        everything else unchanged, so every result is bit-equal to scoring the arrays ``pyascore_amd.rollup.deisotope`` returns.
+        That is one extra round trip of the spectra over PCIe.  With ``recalibrate=`` deisotoping comes FIRST: satellites are
+        found on the m/z as given, the kept peaks are then corrected.  ``keep=True`` retains the filtered batch.  The
+        caller's arrays are not written.
+
         Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
         m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
         of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
         float64 intensities."""
+        if deisotope is not None and deisotope is not False:
+            params = _deisotope_request(deisotope)
+            n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
+            peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
+            if peak_off.size != n_spec + 1:
+                raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
+                                 "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
+            f_mz, f_it, f_off, _ = self.deisotope_spectra(batch["mz"], batch["intensity"], peak_off, params)
+            return self.score_batch(dict(batch, mz=f_mz, intensity=f_it, peak_off=f_off), keep=keep, skip_invalid=skip_invalid,
+                                    evidence=evidence, ions=ions, named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs,
+                                    ranked=ranked, rollup=rollup, peptidoforms=peptidoforms, mz_profile=mz_profile,
+                                    recalibrate=recalibrate)
         ranked_k = None if ranked is None or ranked is False else check_ranked_k(ranked)
         roll = None if rollup is None else _rollup_request(rollup, int(batch["n_psm"]))
         pform = None if peptidoforms is None else _peptidoform_request(peptidoforms, int(batch["n_psm"]))
@@ -849,6 +885,40 @@ class PyAscore:
         if rc:
             self._raise(rc)
         return out
+
+    def deisotope_spectra(self, mz, intensity, peak_off, params):
+        """Spectra deisotoped on the device (``pya_deisotope_spectra_host``; the rule is ``pya_deisotope_params``'s in
+        include/pyascore_hip.h): ``mz`` / ``intensity`` float64 or float32 arrays as ``score_batch`` takes them (float32 m/z
+        beside float64 intensities is widened), ``peak_off[n_spectra + 1]``, ``params`` of
+        ``pyascore_amd.rollup.deisotope_params``.  Returns ``(mz, intensity, peak_off, over)``: new arrays with the kept peaks
+        of every spectrum, bit for bit and in order, their offsets, and ``over = (count, first)`` of the spectra that were not
+        ascending and came back unchanged (``first`` is None when there is none).  ``pyascore_amd.rollup.deisotope`` gives the
+        same bytes on the host."""
+        from .rollup import deisotope_c_params
+        c_params = deisotope_c_params(params)
+        mz, intensity = _typed_spectra(mz, intensity)
+        peak_off = np.ascontiguousarray(peak_off, np.int64)
+        if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
+            raise ValueError("deisotope_spectra: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries")
+        if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+            raise ValueError("deisotope_spectra: peak_off must not be negative or descend")
+        lo, hi = int(peak_off[0]), int(peak_off[-1])
+        if mz.size < hi or intensity.size < hi:
+            raise ValueError("peak_off runs past the end of the spectrum arrays")
+        mz, intensity, peak_off = mz[lo:hi], intensity[lo:hi], np.ascontiguousarray(peak_off - lo)
+        n_spec = peak_off.size - 1
+        if hi == lo:                                         # (no peak anywhere: nothing to filter)
+            return mz.copy(), intensity.copy(), np.zeros(n_spec + 1, np.int64), (0, None)
+        out_mz, out_it = np.empty_like(mz), np.empty_like(intensity)
+        new_off, over = np.zeros(n_spec + 1, np.int64), np.zeros(2, np.uint32)
+        t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
+        t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
+        rc = self._lib.pya_deisotope_spectra_host(self._h, C.byref(t_in), _as_ptr(peak_off), n_spec, C.byref(c_params), C.byref(t_out),
+                                                  _as_ptr(new_off), _as_ptr(over))
+        if rc:
+            self._raise(rc)
+        kept = int(new_off[-1])
+        return out_mz[:kept], out_it[:kept], new_off, (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
 
     def rollup_flr(self, table, cls=None, reported_only=False):
         """Site FLR of a roll-up table on the device (``pya_rollup_flr_host``): ``table`` is a ``ROLLUP_DTYPE`` array as

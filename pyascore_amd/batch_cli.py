@@ -161,7 +161,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
-             recalibrate=None):
+             recalibrate=None, deisotope=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -193,7 +193,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``write_mz_profile_tsv``, ``mz_profile_report``); the main table does not change.
     ``recalibrate``: ``dict(calibration=, band_width=)`` as ``PyAscore.score_batch(recalibrate=...)`` takes it: the m/z of every
     spectrum is corrected with slot 0 of the calibration on the device before it is scored (``read_mz_calibration`` gives both
-    from the file ``write_mz_calibration_tsv`` wrote); every table is then that of the corrected spectra."""
+    from the file ``write_mz_calibration_tsv`` wrote); every table is then that of the corrected spectra.
+    ``deisotope``: ``dict(tol=, max_charge=, ratio=)`` as ``PyAscore.score_batch(deisotope=...)`` takes it: isotope satellites are
+    removed from every spectrum on the device before it is scored (and before ``recalibrate`` corrects it); every table is then
+    that of the filtered spectra."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -220,6 +223,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         stages["mz_profile"] = dict(n_slots=1)
     if recalibrate is not None:
         stages["recalibrate"] = dict(recalibrate)
+    if deisotope is not None:
+        from .ascore import _deisotope_request
+        _deisotope_request(deisotope)                      # (a bad request is refused before anything is read or scored)
+        stages["deisotope"] = dict(deisotope)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything

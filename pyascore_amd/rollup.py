@@ -29,6 +29,10 @@ Fragment m/z recalibration: ``fit_mz_calibration`` reads one systematic error pe
 forms of ``PyAscore.fit_mz_calibration`` / ``DevicePlan.fit_mz_calibration`` and of ``DevicePlan.recalibrate`` /
 ``score_batch(recalibrate=...)``, with the same bytes; ``mz_calibration_rows`` / ``read_mz_calibration`` are the file of
 ``--mz_calibration_out`` / ``--mz_calibration``, ``suggest_mz_error`` a convenience for the narrow re-run.
+
+Deisotoping: ``deisotope_params`` checks and fills the parameters of ``pya_deisotope_params`` (the only place ``step / z`` is
+computed) and ``deisotope`` restates the rule over numpy arrays with the same IEEE operations -- the host form of
+``PyAscore.deisotope_spectra`` / ``pyascore_amd.device.deisotope`` / ``score_batch(deisotope=...)``, with the same bytes.
 """
 import numpy as np
 
@@ -48,6 +52,7 @@ MZ_CALIBRATION_DTYPE = np.dtype(_lib.MZ_CALIBRATION_DTYPE)  # pya_mz_calibration
 assert MZ_CALIBRATION_DTYPE.itemsize == 128
 MZC_MAX_PPM = _lib.PYA_MZC_MAX_PPM
 MZP_BANDS, MZP_BINS = _lib.PYA_MZP_BANDS, _lib.PYA_MZP_BINS
+DEISO_MAX_CHARGE = _lib.PYA_DEISO_MAX_CHARGE
 TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
@@ -595,3 +600,117 @@ def suggest_mz_error(cal, mz_max, k=3.0):
     cal = np.ascontiguousarray(cal, MZ_CALIBRATION_DTYPE).reshape(-1)
     worst = float(cal["spread_ppm"].max()) if cal.size else 0.0
     return float(k) * worst * 1e-6 * float(mz_max)
+
+
+def deisotope_params(tol=0.01, max_charge=3, step=1.0033548378, ratio=1.0, ratio_per_mz=0.0):
+    """The parameters of the deisotoping rule (``pya_deisotope_params``) as a dict: ``tol`` the half width of the match on the
+    isotope spacing in m/z units, ``max_charge`` the largest charge tried (1 .. 8), ``spacing`` the tuple ``step / z`` for
+    z = 1 .. max_charge -- computed here, once, so the device and ``deisotope`` read the same bits --, ``ratio0`` and
+    ``ratio_per_mz``: a satellite is at most ``ratio0 + ratio_per_mz * (m/z of the parent) * z`` times as intense as its
+    parent.  ValueError where the library would refuse: a ``tol`` that is not finite or negative, a charge outside 1 .. 8, a
+    ``step`` that is not finite and positive, ``step / max_charge <= 2 tol``, a ratio that is not finite."""
+    tol, step, ratio, ratio_per_mz = float(tol), float(step), float(ratio), float(ratio_per_mz)
+    if int(max_charge) != max_charge or not 1 <= int(max_charge) <= DEISO_MAX_CHARGE:
+        raise ValueError("deisotope: max_charge = %r is not an integer in 1 .. %d" % (max_charge, DEISO_MAX_CHARGE))
+    max_charge = int(max_charge)
+    if not (np.isfinite(tol) and tol >= 0.0):
+        raise ValueError("deisotope: tol = %r is not a finite number >= 0" % tol)
+    if not (np.isfinite(step) and step > 0.0):
+        raise ValueError("deisotope: step = %r is not finite and positive" % step)
+    if not (np.isfinite(ratio) and np.isfinite(ratio_per_mz)):
+        raise ValueError("deisotope: ratio and ratio_per_mz must be finite")
+    return check_deisotope_params(dict(tol=tol, ratio0=ratio, ratio_per_mz=ratio_per_mz, max_charge=max_charge,
+                                       spacing=tuple(step / float(z) for z in range(1, max_charge + 1))))
+
+
+def check_deisotope_params(params):
+    """``params`` (a dict as ``deisotope_params`` makes it, possibly with spacings of the caller's own) checked against the
+    conditions of ``pya_deisotope_params``; returns it with plain Python numbers."""
+    try:
+        out = dict(tol=float(params["tol"]), ratio0=float(params["ratio0"]), ratio_per_mz=float(params["ratio_per_mz"]),
+                   max_charge=int(params["max_charge"]), spacing=tuple(float(v) for v in params["spacing"]))
+    except (KeyError, TypeError):
+        raise ValueError("deisotope: params is the dict of pyascore_amd.rollup.deisotope_params "
+                         "(tol, ratio0, ratio_per_mz, max_charge, spacing)") from None
+    sp, n = out["spacing"], out["max_charge"]
+    if not 1 <= n <= DEISO_MAX_CHARGE or len(sp) < n:
+        raise ValueError("deisotope: max_charge = %d is not in 1 .. %d or has no spacing" % (n, DEISO_MAX_CHARGE))
+    out["spacing"] = sp = sp[:n]
+    if not (np.isfinite(out["tol"]) and out["tol"] >= 0.0):
+        raise ValueError("deisotope: tol = %r is not a finite number >= 0" % out["tol"])
+    if not (np.isfinite(out["ratio0"]) and np.isfinite(out["ratio_per_mz"])):
+        raise ValueError("deisotope: ratio0 and ratio_per_mz must be finite")
+    if not all(np.isfinite(v) and v > 0.0 for v in sp) or any(not sp[z] < sp[z - 1] for z in range(1, n)):
+        raise ValueError("deisotope: spacing must be finite, positive and strictly decreasing")
+    if not sp[n - 1] > 2.0 * out["tol"]:
+        raise ValueError("deisotope: the smallest spacing %r is not above 2 tol = %r" % (sp[n - 1], 2.0 * out["tol"]))
+    return out
+
+
+def deisotope_c_params(params):
+    """``params`` as the ``pya_deisotope_params`` structure the library reads."""
+    p = check_deisotope_params(params)
+    sp = list(p["spacing"]) + [0.0] * (DEISO_MAX_CHARGE - len(p["spacing"]))
+    return _lib.DeisotopeParams(p["tol"], p["ratio0"], p["ratio_per_mz"], (_lib.C.c_double * DEISO_MAX_CHARGE)(*sp), p["max_charge"], 0)
+
+
+def _deisotope_keep(x, y, p):
+    """keep[] of one ascending spectrum (float64 views): the rule, candidates by searchsorted, the exact predicate decides"""
+    n = x.size
+    keep = np.ones(n, bool)
+    if n < 2:
+        return keep
+    tol, idx = p["tol"], np.arange(n)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for z0, sp in enumerate(p["spacing"]):
+            z = float(z0 + 1)
+            t = x - sp
+            slack = 1e-14 * (np.abs(x) + sp + tol)          # (far above the rounding of t and of the predicate: a superset)
+            lo = np.searchsorted(x, t - tol - slack, "left")
+            hi = np.minimum(np.searchsorted(x, t + tol + slack, "right"), idx)
+            cnt = np.maximum(hi - lo, 0)
+            total = int(cnt.sum())
+            if total == 0:
+                continue
+            jj = np.repeat(idx, cnt)
+            ii = np.repeat(lo, cnt) + (np.arange(total) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+            d = x[jj] - x[ii]
+            e = d - sp
+            m = x[ii] * z
+            b = p["ratio0"] + p["ratio_per_mz"] * m
+            ok = (np.fabs(e) <= tol) & (y[jj] <= y[ii] * b)
+            keep[jj[ok]] = False
+    return keep
+
+
+def deisotope(mz, intensity, peak_off, params):
+    """Deisotoped spectra: the rule of ``pya_deisotope_params``, operation for operation in float64, so the bytes are those of
+    ``pya_deisotope_spectra``.  ``mz`` / ``intensity``: float64 or float32 (widened for the decision, the kept elements are
+    copied bit for bit and the dtype stays), ``peak_off[n_spectra + 1]``, ``params`` of ``deisotope_params``.  Peak j of a
+    spectrum goes iff a peak i of it and a charge z have ``|mz[j] - mz[i] - spacing[z - 1]| <= tol`` and ``intensity[j] <=
+    intensity[i] * (ratio0 + ratio_per_mz * mz[i] * z)``; the parent may itself go, the lowest peak always stays.  A spectrum
+    that is not ascending (a descending pair or a NaN m/z) comes back unchanged.  Returns ``(mz, intensity, peak_off, keep)``:
+    new arrays of the kept peaks, their offsets (from 0) and the boolean mask over ``peak_off[0]:peak_off[-1]``."""
+    p = check_deisotope_params(params)
+    mz, intensity = np.asarray(mz), np.asarray(intensity)
+    for name, a in (("mz", mz), ("intensity", intensity)):
+        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
+            raise ValueError("deisotope: %s is a one-dimensional float64 or float32 array" % name)
+    peak_off = np.asarray(peak_off, np.int64)
+    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+        raise ValueError("deisotope: peak_off has n_spectra + 1 offsets that do not descend")
+    lo, hi = int(peak_off[0]), int(peak_off[-1])
+    if mz.size < hi or intensity.size < hi:
+        raise ValueError("deisotope: peak_off runs past the end of the spectrum arrays")
+    x, y = mz[lo:hi].astype(np.float64), intensity[lo:hi].astype(np.float64)
+    keep = np.ones(hi - lo, bool)
+    rel = peak_off - lo
+    for s in range(peak_off.size - 1):
+        a, b = int(rel[s]), int(rel[s + 1])
+        if b - a < 2 or not (x[a:b - 1] <= x[a + 1:b]).all():
+            continue
+        keep[a:b] = _deisotope_keep(x[a:b], y[a:b], p)
+    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+    kept = before[rel[1:]] - before[rel[:-1]]
+    new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+    return mz[lo:hi][keep].copy(), intensity[lo:hi][keep].copy(), new_off, keep
