@@ -497,6 +497,42 @@ typedef struct pya_deisotope_params {   /* 96 bytes */
     uint32_t max_charge, reserved;          /* 1 .. PYA_DEISO_MAX_CHARGE; 0                                                  */
 } pya_deisotope_params;
 
+/* Charge deconvolution: deisotoping, and the fragments that the removed satellites show to be multiply charged reduced to 1+.
+ * The satellites of a peak are the only evidence of its charge; deisotoping alone throws it away and leaves a 2+ or 3+ fragment
+ * at its multiply-charged m/z, where a run with b/y at 1+ never finds it.  Like deisotoping a transform of spectra in front of a
+ * plan (the peak counts change); no kernel of a run knows of it.  The reference has no counterpart.
+ * THE RULE.  Every spectrum is handled on its own; x[], y[], "in double" and R are those of pya_deisotope_params above: for
+ * peaks i, j and a charge z, R(i, j, z) holds iff, in double and in this order of operations,
+ *   d = x[j] - x[i],  e = d - iso.spacing[z - 1],  fabs(e) <= iso.tol
+ *   m = x[i] (double)z,  b = iso.ratio0 + iso.ratio_per_mz m,  y[j] <= y[i] b
+ * so that peak j is removed by deisotoping iff R(i, j, z) for some i and some z in 1 .. iso.max_charge.
+ * KEPT SET: the kept peaks are exactly those deisotoping keeps under iso.
+ * CHARGE: c(i) of kept peak i is the largest z in 2 .. iso.max_charge for which some peak j has R(i, j, z) and
+ * y[j] >= y[i] witness (the product in double); 1 when there is no such z.  The child j is always a removed peak (R removes it);
+ * a child testifies for every z it matches; z = 1 needs no witness.  witness is the least share of the parent's intensity a
+ * child must have to be believed: on spectra whose fragments are all 1+, a chance peak half a spacing above a fragment testifies
+ * to a false 2+, and a real M+1 is seldom that weak.
+ * MOVED VALUE, in double and in this order, then rounded once to the m/z element type:
+ *   t = x[i] (double)c,  u = (double)(c - 1) carrier,  v = t - u
+ * If c >= 2 and the stored (rounded) value is finite and greater than x[i], the peak's m/z becomes it and its charge is c.
+ * Otherwise the peak stays and its charge is reported as 1 (so a peak with x[i] <= carrier never moves).  Intensities are copied
+ * bit for bit, and so is the m/z of every peak that does not move.
+ * carrier is the mass one charge adds.  Its default, PYA_DECHARGE_CARRIER, is the value the scoring kernels themselves add per
+ * charge -- the literal 1.007825 of charge_mz() in csrc/device_common.hip.h and of the walks in csrc/walk_core.hip.h, the
+ * reference's PROTON: the mass of a hydrogen atom to six places, not the proton's 1.00728 --, so that a reduced peak lands where
+ * a run computes the fragment at 1+.
+ * OUTPUT ORDER: the kept peaks of a spectrum ordered by stored m/z as numbers, equal values by raw index (a stable sort of the
+ * kept peaks in raw order).  Moving only raises m/z, so a moved peak precedes every unmoved peak of equal value.
+ * A spectrum that is NOT ASCENDING in pya_deisotope_params' sense is copied unchanged and reported; all its charges are 1.
+ * With iso.max_charge == 1 the output is byte for byte that of pya_deisotope_spectra.
+ * The parameters must satisfy: iso as at pya_deisotope_params; carrier finite and > 0; witness finite and >= 0. */
+#define PYA_DECHARGE_CARRIER 1.007825
+typedef struct pya_decharge_params {   /* 112 bytes */
+    pya_deisotope_params iso;   /* the deisotoping rule, unchanged, with its conditions                                      */
+    double carrier;             /* mass of one charge carrier; finite, > 0                                                   */
+    double witness;             /* a child testifies to a charge only with y[j] >= y[i] witness; finite, >= 0                */
+} pya_decharge_params;
+
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
  * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
@@ -849,6 +885,38 @@ int pya_deisotope_spectra(pya_handle *h, const pya_typed_spectra *d_in, const in
  * negative and the offsets must not descend (PYA_ERR_ARG); the arrays are read from element 0 to peak_off[n_spectra]. */
 int pya_deisotope_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
                                const pya_deisotope_params *params, const pya_typed_spectra *out, int64_t *new_off, uint32_t *over);
+/* The device bytes pya_decharge_spectra needs as its workspace for n_spectra spectra of n_peaks peaks together: per group of 64
+ * peaks a keep word, a moved word, a running count and 64 entries of 16 bytes for the moved peaks (about 16.4 bytes a peak),
+ * per spectrum 32 bytes, and the tile sums of the offset scan. */
+uint64_t pya_decharge_workspace_bytes(uint64_t n_spectra, uint64_t n_peaks);
+/* Charge-deconvolves n_spectra spectra on the device (THE RULE at pya_decharge_params above; csrc/decharge.hip).  The arguments
+ * are those of pya_deisotope_spectra, one for one, and d_charge beside them: one byte per OUTPUT peak with its charge (1 for a
+ * peak that did not move), device memory of the input's capacity, or NULL when it is not wanted.  Three passes on hip_stream --
+ * mark (keep, charge, moved value; counts), an exclusive scan of the kept counts, place (every kept peak computes its position
+ * in the sorted output and writes itself there) --, stream-ordered, no host wait and no allocation; the caller lends d_work
+ * (8-byte aligned, work_bytes >= pya_decharge_workspace_bytes(n_spectra, d_peak_off[n_spectra])).  The peaks of spectrum s are
+ * d_out[d_new_off[s] .. d_new_off[s + 1]), ascending.  d_new_off equals what pya_deisotope_spectra gives under params->iso.  A
+ * spectrum that is not ascending is copied unchanged and counted in d_over[0], the smallest such spectrum in d_over[1] as
+ * 0xffffffff - spectrum.  No write lies outside out[0 .. d_new_off[n_spectra]), d_charge[0 .. d_new_off[n_spectra]),
+ * d_new_off[0 .. n_spectra], d_over[0 .. 2) and d_work[0 .. work_bytes): the out elements from d_new_off[n_spectra] up to the
+ * input's length stay as they were.  The peak count is on the device, so the host can only check the workspace against
+ * pya_decharge_workspace_bytes(n_spectra, 0); the kernels clip the offsets to the peaks the lent workspace has room for (whole
+ * groups of 64), and a spectrum that reaches beyond them is reported in d_over as well.
+ * PYA_ERR_ARG, with nothing launched: everything pya_deisotope_spectra refuses (of params->iso for the parameters), a carrier
+ * that is not finite and positive, a witness that is not finite or negative, a d_charge that is one of the spectrum arrays.
+ * n_spectra == 0 writes d_new_off[0] = 0 and nothing else. */
+int pya_decharge_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64_t *d_peak_off, uint64_t n_spectra,
+                         const pya_decharge_params *params, void *hip_stream, void *d_work, uint64_t work_bytes,
+                         const pya_typed_spectra *d_out, int64_t *d_new_off, uint8_t *d_charge, uint32_t *d_over);
+/* The same over HOST arrays, as pya_deisotope_spectra_host: uploads, runs on the handle's stream with a workspace of its own,
+ * downloads out[0 .. new_off[n_spectra]), charge[0 .. new_off[n_spectra]) (charge may be NULL), new_off and over, and waits.
+ * peak_off[0] must not be negative and the offsets must not descend (PYA_ERR_ARG). */
+int pya_decharge_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                              const pya_decharge_params *params, const pya_typed_spectra *out, int64_t *new_off, uint8_t *charge,
+                              uint32_t *over);
+/* Diagnostic: which of the three passes pya_decharge_spectra launches from now on, in every handle (bit 0 mark, bit 1 scan,
+ * bit 2 place; 7 is the default).  For scripts/decharge_probe.py, which times the passes apart; not thread-safe. */
+void pya_debug_decharge_passes(uint32_t passes);
 /* The device bytes pya_plan_peptidoforms / pya_peptidoform_reduce need as their workspace for n_entries entries (PSMs of the
  * plan + records of d_prev; records of d_a + d_b): keys double-buffered, the entries, the staged list, digit histograms, tile
  * totals, about 133 bytes per entry; 0 for no entries (and above 2^31 - 1, which the calls refuse). */

@@ -15,7 +15,9 @@ its sites and adds false-localisation rates, ``--site_table_decoys LETTERS`` nam
 ``--mz_profile FILE`` (the fragment mass-error profile of the whole file, a line per m/z band, unit and bin, and its summary
 in the log) and ``--mz_calibration_out FILE`` / ``--mz_calibration FILE`` (fit an m/z calibration to that profile; score with
 the spectra corrected by one) and ``--deisotope`` with ``--deisotope_tol DA``, ``--deisotope_charge Z`` and
-``--deisotope_ratio R`` (remove isotope satellites from every spectrum on the device before it is scored) are the additions."""
+``--deisotope_ratio R`` (remove isotope satellites from every spectrum on the device before it is scored) and ``--decharge``
+with ``--decharge_tol DA``, ``--decharge_charge Z``, ``--decharge_ratio R`` and ``--decharge_witness W`` (deisotope, and reduce
+multiply charged fragments to 1+) are the additions."""
 import argparse
 import re
 import sys
@@ -123,6 +125,20 @@ def build_parser():
                    help="with --deisotope: the largest charge whose spacing is tried, 1 .. 8 (default 3)")
     p.add_argument("--deisotope_ratio", type=float, default=1.0, metavar="R",
                    help="with --deisotope: a satellite is at most R times as intense as its parent (default 1.0)")
+    p.add_argument("--decharge", action="store_true",
+                   help="charge-deconvolve every spectrum on the device before it is scored: deisotope it, and move every kept peak "
+                        "whose satellites show a charge z of 2 .. --decharge_charge to its m/z at 1+, so that b/y ions at 1+ find "
+                        "multiply charged fragments; leave --max_fragment_charge at 1 with it; not together with --deisotope "
+                        "(it contains it) or --mz_calibration (correct the spectra first); one more transfer of the spectra")
+    p.add_argument("--decharge_tol", type=float, default=0.01, metavar="DA",
+                   help="with --decharge: how far the distance of two peaks may be from the isotope spacing, in m/z (default 0.01)")
+    p.add_argument("--decharge_charge", type=int, default=3, metavar="Z",
+                   help="with --decharge: the largest charge whose spacing is tried, 1 .. 8 (default 3)")
+    p.add_argument("--decharge_ratio", type=float, default=1.0, metavar="R",
+                   help="with --decharge: a satellite is at most R times as intense as its parent (default 1.0)")
+    p.add_argument("--decharge_witness", type=float, default=0.3, metavar="W",
+                   help="with --decharge: a satellite testifies to a charge only if it is at least W times as intense as its parent "
+                        "(default 0.3, from synthetic spectra)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -142,6 +158,14 @@ def validate_args(args):
     if getattr(args, "deisotope", False):
         from .rollup import deisotope_params
         deisotope_params(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio)
+    if getattr(args, "decharge", False):
+        from .rollup import decharge_params
+        if getattr(args, "deisotope", False):
+            raise ValueError("--decharge contains --deisotope: give one of the two")
+        if getattr(args, "mz_calibration", None):
+            raise ValueError("--decharge moves peaks and --mz_calibration is a function of the measured m/z: write the corrected "
+                             "spectra first, then run with --decharge")
+        decharge_params(tol=args.decharge_tol, max_charge=args.decharge_charge, ratio=args.decharge_ratio, witness=args.decharge_witness)
 
 
 def parse_args(argv):
@@ -196,6 +220,8 @@ def run(args, log=print):
         cal, band_width = read_mz_calibration(args.mz_calibration)
         recalibrate = dict(calibration=cal, band_width=band_width)
     deisotope = dict(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio) if args.deisotope else None
+    decharge = dict(tol=args.decharge_tol, max_charge=args.decharge_charge, ratio=args.decharge_ratio,
+                    witness=args.decharge_witness) if args.decharge else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -207,7 +233,7 @@ def run(args, log=print):
                               site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
                               peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
-                              deisotope=deisotope)
+                              deisotope=deisotope, decharge=decharge)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:

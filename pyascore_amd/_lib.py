@@ -197,6 +197,16 @@ class DeisotopeParams(C.Structure):
 
 assert C.sizeof(DeisotopeParams) == 96, "pya_deisotope_params is a 96-byte record"
 
+PYA_DECHARGE_CARRIER = 1.007825
+
+
+class DechargeParams(C.Structure):
+    """pya_decharge_params: the deisotoping rule, the mass of one charge carrier, the least share of a witness"""
+    _fields_ = [("iso", DeisotopeParams), ("carrier", C.c_double), ("witness", C.c_double)]
+
+
+assert C.sizeof(DechargeParams) == 112, "pya_decharge_params is a 112-byte record"
+
 
 def spectrum_type(dtype):
     """PYA_F64 / PYA_F32 for a numpy dtype (or its name: 'float64', 'float32'); anything else is no spectrum type."""
@@ -271,6 +281,12 @@ SYMBOLS = {
                                         C.POINTER(TypedSpectra), _vp, _vp]),
     "pya_deisotope_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.POINTER(DeisotopeParams),
                                              C.POINTER(TypedSpectra), _vp, _vp]),
+    "pya_decharge_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "pya_decharge_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.POINTER(DechargeParams), _vp, _vp, C.c_uint64,
+                                       C.POINTER(TypedSpectra), _vp, _vp, _vp]),
+    "pya_decharge_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.POINTER(DechargeParams),
+                                            C.POINTER(TypedSpectra), _vp, _vp, _vp]),
+    "pya_debug_decharge_passes": (None, [C.c_uint32]),
     "pya_peptidoform_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "pya_peptidoform_reduce": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "pya_peptidoform_reduce_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),

@@ -186,6 +186,28 @@ def _deisotope_request(req):
         raise ValueError("deisotope: tol, step, ratio and ratio_per_mz are numbers, max_charge an integer") from None
 
 
+_RECALIBRATE_FIRST = ("decharge moves peaks, and a calibration is a function of the measured m/z: correct the spectra first "
+                      "(pya_recalibrate_spectra, DevicePlan.recalibrate or pyascore_amd.rollup.recalibrate), then pass the corrected "
+                      "arrays with decharge=")
+
+
+def _decharge_request(req):
+    """``score_batch(decharge=...)`` checked: the dict of ``pyascore_amd.rollup.decharge_params``"""
+    from .rollup import decharge_params
+    if req is True:
+        req = {}
+    names = ("tol", "max_charge", "step", "ratio", "ratio_per_mz", "carrier", "witness")
+    if not isinstance(req, dict):
+        raise ValueError("decharge takes a dict: " + ", ".join(names))
+    unknown = set(req) - set(names)
+    if unknown:
+        raise ValueError("decharge takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+    try:
+        return decharge_params(**req)
+    except TypeError:
+        raise ValueError("decharge: tol, step, ratio, ratio_per_mz, carrier and witness are numbers, max_charge an integer") from None
+
+
 def _rollup_request(rollup, n_psm):
     """``score_batch(rollup=...)`` as contiguous arrays: dict(slot int32, n_slots, threshold, psm_id uint32 | None,
     site_off int64 | None)"""
@@ -446,7 +468,7 @@ class PyAscore:
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
-                    recalibrate=None, deisotope=None):
+                    recalibrate=None, deisotope=None, decharge=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -545,11 +567,38 @@ class PyAscore:
         found on the m/z as given, the kept peaks are then corrected.  ``keep=True`` retains the filtered batch.  The
         caller's arrays are not written.
 
+        ``decharge=dict(tol=0.01, max_charge=3, step=1.0033548378, ratio=1.0, ratio_per_mz=0.0, carrier=1.007825, witness=0.3)``
+        (or True: the defaults) charge-deconvolves every spectrum before it is scored: deisotoping, and every kept peak whose
+        satellites show a charge of 2 or more moved to its m/z at 1+ (``pya_decharge_params``), so that b/y at 1+ finds
+        multiply charged fragments: leave ``max_fragment_charge`` at 1 with it.  As with ``deisotope=`` the spectra go through
+        ``decharge_spectra`` once (a batch with ``spec_of``: each shared spectrum once) and the ordinary call then runs on the
+        result, so every result is bit-equal to scoring the arrays ``pyascore_amd.rollup.decharge`` returns.  That is one extra
+        round trip of the spectra over PCIe.  ``decharge=`` contains deisotoping: together with ``deisotope=`` it is a
+        ValueError.  Together with ``recalibrate=`` it is a ValueError too: a calibration is a function of the measured m/z
+        and must be applied before peaks move -- correct the spectra first (``pya_recalibrate_spectra``,
+        ``DevicePlan.recalibrate``, ``pyascore_amd.rollup.recalibrate``).  ``keep=True`` retains the transformed batch.  The
+        caller's arrays are not written.
+
         Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
         m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
         of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
         float64 intensities."""
+        if decharge is not None and decharge is not False:
+            if deisotope is not None and deisotope is not False:
+                raise ValueError("decharge= contains deisotoping (its kept peaks are those of deisotope=): pass one of the two")
+            if recalibrate is not None:
+                raise ValueError("decharge= cannot be combined with recalibrate=: " + _RECALIBRATE_FIRST)
+            params = _decharge_request(decharge)
+            n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
+            peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
+            if peak_off.size != n_spec + 1:
+                raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
+                                 "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
+            f_mz, f_it, f_off, _, _ = self.decharge_spectra(batch["mz"], batch["intensity"], peak_off, params)
+            return self.score_batch(dict(batch, mz=f_mz, intensity=f_it, peak_off=f_off), keep=keep, skip_invalid=skip_invalid,
+                                    evidence=evidence, ions=ions, named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs,
+                                    ranked=ranked, rollup=rollup, peptidoforms=peptidoforms, mz_profile=mz_profile)
         if deisotope is not None and deisotope is not False:
             params = _deisotope_request(deisotope)
             n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
@@ -919,6 +968,39 @@ class PyAscore:
             self._raise(rc)
         kept = int(new_off[-1])
         return out_mz[:kept], out_it[:kept], new_off, (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
+
+    def decharge_spectra(self, mz, intensity, peak_off, params):
+        """Spectra charge-deconvolved on the device (``pya_decharge_spectra_host``; the rule is ``pya_decharge_params``'s in
+        include/pyascore_hip.h): arguments as ``deisotope_spectra`` takes them, ``params`` of
+        ``pyascore_amd.rollup.decharge_params``.  Returns ``(mz, intensity, peak_off, charge, over)``: new arrays with the
+        peaks of every spectrum -- those deisotoping keeps, the multiply charged ones moved to 1+, ascending --, their offsets,
+        one ``uint8`` per output peak with its charge (1: not moved), and ``over = (count, first)`` of the spectra that were not
+        ascending and came back unchanged.  ``pyascore_amd.rollup.decharge`` gives the same bytes on the host."""
+        from .rollup import decharge_c_params
+        c_params = decharge_c_params(params)
+        mz, intensity = _typed_spectra(mz, intensity)
+        peak_off = np.ascontiguousarray(peak_off, np.int64)
+        if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
+            raise ValueError("decharge_spectra: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries")
+        if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+            raise ValueError("decharge_spectra: peak_off must not be negative or descend")
+        lo, hi = int(peak_off[0]), int(peak_off[-1])
+        if mz.size < hi or intensity.size < hi:
+            raise ValueError("peak_off runs past the end of the spectrum arrays")
+        mz, intensity, peak_off = mz[lo:hi], intensity[lo:hi], np.ascontiguousarray(peak_off - lo)
+        n_spec = peak_off.size - 1
+        if hi == lo:                                         # (no peak anywhere: nothing to do)
+            return mz.copy(), intensity.copy(), np.zeros(n_spec + 1, np.int64), np.zeros(0, np.uint8), (0, None)
+        out_mz, out_it, charge = np.empty_like(mz), np.empty_like(intensity), np.zeros(mz.size, np.uint8)
+        new_off, over = np.zeros(n_spec + 1, np.int64), np.zeros(2, np.uint32)
+        t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
+        t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
+        rc = self._lib.pya_decharge_spectra_host(self._h, C.byref(t_in), _as_ptr(peak_off), n_spec, C.byref(c_params), C.byref(t_out),
+                                                 _as_ptr(new_off), _as_ptr(charge), _as_ptr(over))
+        if rc:
+            self._raise(rc)
+        kept = int(new_off[-1])
+        return out_mz[:kept], out_it[:kept], new_off, charge[:kept], (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
 
     def rollup_flr(self, table, cls=None, reported_only=False):
         """Site FLR of a roll-up table on the device (``pya_rollup_flr_host``): ``table`` is a ``ROLLUP_DTYPE`` array as

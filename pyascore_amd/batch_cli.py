@@ -161,7 +161,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
-             recalibrate=None, deisotope=None):
+             recalibrate=None, deisotope=None, decharge=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -196,7 +196,10 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     from the file ``write_mz_calibration_tsv`` wrote); every table is then that of the corrected spectra.
     ``deisotope``: ``dict(tol=, max_charge=, ratio=)`` as ``PyAscore.score_batch(deisotope=...)`` takes it: isotope satellites are
     removed from every spectrum on the device before it is scored (and before ``recalibrate`` corrects it); every table is then
-    that of the filtered spectra."""
+    that of the filtered spectra.
+    ``decharge``: ``dict(tol=, max_charge=, ratio=, witness=)`` as ``PyAscore.score_batch(decharge=...)`` takes it: every spectrum is
+    deisotoped and its multiply charged fragments are reduced to 1+ on the device before it is scored; not together with
+    ``deisotope`` or ``recalibrate``."""
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -227,6 +230,12 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         from .ascore import _deisotope_request
         _deisotope_request(deisotope)                      # (a bad request is refused before anything is read or scored)
         stages["deisotope"] = dict(deisotope)
+    if decharge is not None:
+        from .ascore import _decharge_request
+        if deisotope is not None or recalibrate is not None:
+            raise ValueError("decharge cannot be combined with deisotope (it contains it) or with recalibrate (correct the spectra first)")
+        _decharge_request(decharge)
+        stages["decharge"] = dict(decharge)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything

@@ -14,7 +14,7 @@ static const uint64_t kDeisoMaxSpectra = 0xfffffffeull;
  * spectrum's bits in words of its own (deisotope.hip), one more so that no spectra is still a workspace */
 static uint64_t deiso_tile_words(uint64_t n_spectra) { return n_spectra > kDeisoMaxSpectra ? 0 : pya_ions_scan_tiles((uint32_t)n_spectra); }
 
-static const char *deiso_params_fault(const pya_deisotope_params *p) {
+const char *deiso_params_fault(const pya_deisotope_params *p) {
     if (!p) return "params is NULL";
     if (!std::isfinite(p->tol) || !(p->tol >= 0.)) return "tol is not a finite number >= 0";
     if (!std::isfinite(p->ratio0) || !std::isfinite(p->ratio_per_mz)) return "ratio0 or ratio_per_mz is not finite";
@@ -28,8 +28,8 @@ static const char *deiso_params_fault(const pya_deisotope_params *p) {
     return nullptr;
 }
 
-static int deiso_check(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
-                       const pya_deisotope_params *params, const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over) {
+int deiso_check(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                const pya_deisotope_params *params, const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over) {
     if (n_spectra > kDeisoMaxSpectra) return h->fail(PYA_ERR_ARG, -1, "%s: %llu spectra are more than 2^32 - 2", who, (unsigned long long)n_spectra);
     if (const char *why = deiso_params_fault(params)) return h->fail(PYA_ERR_ARG, -1, "%s: %s", who, why);
     if (!in || !out || !new_off) return h->fail(PYA_ERR_ARG, -1, "NULL pointer passed to %s", who);

@@ -960,6 +960,11 @@ int pform_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const vo
  * report of a plan's last pya_plan_mz_profile (psm_lo as for rollup_report) */
 int mzp_check(pya_handle *h, const char *who, uint64_t n_slots, const pya_mz_profile_params *prm);
 int mzp_report(pya_plan *p, uint64_t psm_lo);
+/* host_deisotope.cpp: what is wrong with a set of deisotoping parameters (NULL: nothing), and everything the deisotope calls
+ * refuse about their arrays, before anything is launched; host_decharge.cpp asks the same of its own arguments */
+const char *deiso_params_fault(const pya_deisotope_params *p);
+int deiso_check(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                const pya_deisotope_params *params, const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");

@@ -33,6 +33,11 @@ forms of ``PyAscore.fit_mz_calibration`` / ``DevicePlan.fit_mz_calibration`` and
 Deisotoping: ``deisotope_params`` checks and fills the parameters of ``pya_deisotope_params`` (the only place ``step / z`` is
 computed) and ``deisotope`` restates the rule over numpy arrays with the same IEEE operations -- the host form of
 ``PyAscore.deisotope_spectra`` / ``pyascore_amd.device.deisotope`` / ``score_batch(deisotope=...)``, with the same bytes.
+
+Charge deconvolution: ``decharge_params`` is ``deisotope_params`` with ``carrier`` and ``witness`` beside it
+(``pya_decharge_params``) and ``decharge`` restates that rule -- deisotoping, and every kept peak whose satellites show a charge
+of 2 or more moved to its m/z at 1+, the output sorted -- the host form of ``PyAscore.decharge_spectra`` /
+``pyascore_amd.device.decharge`` / ``score_batch(decharge=...)``, with the same bytes.
 """
 import numpy as np
 
@@ -53,6 +58,7 @@ assert MZ_CALIBRATION_DTYPE.itemsize == 128
 MZC_MAX_PPM = _lib.PYA_MZC_MAX_PPM
 MZP_BANDS, MZP_BINS = _lib.PYA_MZP_BANDS, _lib.PYA_MZP_BINS
 DEISO_MAX_CHARGE = _lib.PYA_DEISO_MAX_CHARGE
+DECHARGE_CARRIER = _lib.PYA_DECHARGE_CARRIER
 TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
@@ -714,3 +720,125 @@ def deisotope(mz, intensity, peak_off, params):
     kept = before[rel[1:]] - before[rel[:-1]]
     new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
     return mz[lo:hi][keep].copy(), intensity[lo:hi][keep].copy(), new_off, keep
+
+
+def decharge_params(tol=0.01, max_charge=3, step=1.0033548378, ratio=1.0, ratio_per_mz=0.0, carrier=DECHARGE_CARRIER, witness=0.3):
+    """The parameters of charge deconvolution (``pya_decharge_params``) as a dict: those of ``deisotope_params`` (same
+    arguments, same checks) and beside them ``carrier``, the mass one charge adds -- by default the 1.007825 the scoring
+    kernels add per charge, so that a reduced peak lands where a run computes the fragment at 1+ --, and ``witness``: a removed
+    satellite testifies to a charge of its parent only when it has at least ``witness`` times the parent's intensity.  The
+    default 0.3 rests on a synthetic measurement (satellites at 0.5 and 0.2 times the parent), not on real
+    isotope envelopes.  ValueError where the library would refuse: what ``deisotope_params`` refuses, a ``carrier`` that is not
+    finite and positive, a ``witness`` that is not finite or negative."""
+    iso = deisotope_params(tol=tol, max_charge=max_charge, step=step, ratio=ratio, ratio_per_mz=ratio_per_mz)
+    return check_decharge_params(dict(iso, carrier=carrier, witness=witness))
+
+
+def check_decharge_params(params):
+    """``params`` (a dict as ``decharge_params`` makes it) checked against the conditions of ``pya_decharge_params``; returns it
+    with plain Python numbers."""
+    try:
+        out = check_deisotope_params(params)
+        out.update(carrier=float(params["carrier"]), witness=float(params["witness"]))
+    except (KeyError, TypeError):
+        raise ValueError("decharge: params is the dict of pyascore_amd.rollup.decharge_params "
+                         "(tol, ratio0, ratio_per_mz, max_charge, spacing, carrier, witness)") from None
+    if not (np.isfinite(out["carrier"]) and out["carrier"] > 0.0):
+        raise ValueError("decharge: carrier = %r is not finite and positive" % out["carrier"])
+    if not (np.isfinite(out["witness"]) and out["witness"] >= 0.0):
+        raise ValueError("decharge: witness = %r is not a finite number >= 0" % out["witness"])
+    return out
+
+
+def decharge_c_params(params):
+    """``params`` as the ``pya_decharge_params`` structure the library reads."""
+    p = check_decharge_params(params)
+    return _lib.DechargeParams(deisotope_c_params(p), p["carrier"], p["witness"])
+
+
+def _decharge_charge(x, y, p):
+    """c[] of one ascending spectrum (float64 views) as if every peak were kept: the largest witnessed z of 2 .. max_charge,
+    else 1; candidates by searchsorted, the exact predicate decides"""
+    n = x.size
+    c = np.ones(n, np.int64)
+    if n < 2:
+        return c
+    tol, idx = p["tol"], np.arange(n)
+    with np.errstate(invalid="ignore", over="ignore"):
+        least = y * p["witness"]
+        for z0, sp in enumerate(p["spacing"]):
+            if z0 == 0:
+                continue
+            z = float(z0 + 1)
+            t = x + sp
+            slack = 1e-14 * (np.abs(x) + sp + tol)          # (far above the rounding of t and of the predicate: a superset)
+            lo = np.maximum(np.searchsorted(x, t - tol - slack, "left"), idx + 1)
+            hi = np.searchsorted(x, t + tol + slack, "right")
+            cnt = np.maximum(hi - lo, 0)
+            total = int(cnt.sum())
+            if total == 0:
+                continue
+            ii = np.repeat(idx, cnt)
+            jj = np.repeat(lo, cnt) + (np.arange(total) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+            d = x[jj] - x[ii]
+            e = d - sp
+            m = x[ii] * z
+            b = p["ratio0"] + p["ratio_per_mz"] * m
+            ok = (np.fabs(e) <= tol) & (y[jj] <= y[ii] * b) & (y[jj] >= least[ii])
+            c[ii[ok]] = z0 + 1                              # (z rises: the largest stays)
+    return c
+
+
+def decharge(mz, intensity, peak_off, params):
+    """Charge-deconvolved spectra: the rule of ``pya_decharge_params``, operation for operation in float64, so the bytes are
+    those of ``pya_decharge_spectra``.  Arguments as ``deisotope`` takes them, ``params`` of ``decharge_params``.  The kept peaks
+    are those ``deisotope`` keeps; a kept peak with a witnessed satellite at spacing / z, z >= 2, moves to ``mz * c -
+    (c - 1) * carrier`` (c the largest such z; rounded once to the dtype of ``mz``) if that is finite and above where it was;
+    every spectrum comes out sorted by m/z, equal values in raw order.  A spectrum that is not ascending comes back unchanged.
+    Returns ``(mz, intensity, peak_off, charge, keep)``: new arrays of the output peaks, their offsets (from 0), one ``uint8``
+    per output peak with its charge (1: not moved, bits of m/z copied), and the boolean mask of the kept peaks over
+    ``peak_off[0]:peak_off[-1]`` of the input."""
+    p = check_decharge_params(params)
+    mz, intensity = np.asarray(mz), np.asarray(intensity)
+    for name, a in (("mz", mz), ("intensity", intensity)):
+        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
+            raise ValueError("decharge: %s is a one-dimensional float64 or float32 array" % name)
+    peak_off = np.asarray(peak_off, np.int64)
+    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+        raise ValueError("decharge: peak_off has n_spectra + 1 offsets that do not descend")
+    lo, hi = int(peak_off[0]), int(peak_off[-1])
+    if mz.size < hi or intensity.size < hi:
+        raise ValueError("decharge: peak_off runs past the end of the spectrum arrays")
+    raw_mz, raw_it = mz[lo:hi], intensity[lo:hi]
+    x, y = raw_mz.astype(np.float64), raw_it.astype(np.float64)
+    keep = np.ones(hi - lo, bool)
+    order = np.arange(hi - lo)                               # raw indices, to become the output order of the kept peaks
+    stored, charge = raw_mz.copy(), np.ones(hi - lo, np.uint8)
+    rel = peak_off - lo
+    for s in range(peak_off.size - 1):
+        a, b = int(rel[s]), int(rel[s + 1])
+        if b - a < 2 or not (x[a:b - 1] <= x[a + 1:b]).all():
+            continue
+        keep[a:b] = _deisotope_keep(x[a:b], y[a:b], p)
+        if p["max_charge"] < 2:
+            continue
+        c = np.where(keep[a:b], _decharge_charge(x[a:b], y[a:b], p), 1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = x[a:b] * c.astype(np.float64)
+            u = (c - 1).astype(np.float64) * p["carrier"]
+            v = t - u
+            new = v.astype(raw_mz.dtype)
+            wide = new.astype(np.float64)
+            moves = (c >= 2) & np.isfinite(wide) & (wide > x[a:b])
+        if not moves.any():
+            continue
+        stored[a:b][moves] = new[moves]
+        charge[a:b][moves] = c[moves]
+        kept = np.flatnonzero(keep[a:b])
+        value = np.where(moves, wide, x[a:b])[kept]
+        order[a:b][kept] = kept[np.argsort(value, kind="stable")] + a
+    pick = order[keep]
+    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+    new_off = np.concatenate([[0], np.cumsum(before[rel[1:]] - before[rel[:-1]])]).astype(np.int64)
+    return stored[pick].copy(), raw_it[pick].copy(), new_off, charge[pick].copy(), keep
+
