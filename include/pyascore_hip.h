@@ -533,6 +533,54 @@ typedef struct pya_decharge_params {   /* 112 bytes */
     double witness;             /* a child testifies to a charge only with y[j] >= y[i] witness; finite, >= 0                */
 } pya_decharge_params;
 
+/* Precursor stripping: the peaks of an MS2 spectrum that are no fragments at all -- the unfragmented precursor, its
+ * neutral-loss forms (precursor - H3PO4 is usually the base peak of a phosphopeptide's CID spectrum), under ETD the
+ * charge-reduced precursors [M + zH]^(z')+, z' < z, and their losses, in TMT runs the reporter region -- removed before a run.
+ * Each of them is the most intense peak of its 100 m/z window: it takes the first of the n_top ranks there, moves every real
+ * fragment of the window one rank down at every depth, and is one more target for a random match.  Like deisotoping a transform
+ * of spectra in front of a plan (the peak counts change); no kernel of a run knows of it.  The reference has no counterpart.
+ * THE RULE.  Every spectrum s is handled on its own, with its precursor prec_mz[s] (double) and prec_z[s] (int32).
+ * NO WINDOWS: a spectrum whose prec_z is outside 1 .. PYA_STRIP_MAX_CHARGE, or whose prec_mz is not finite or not positive,
+ * has no windows; the range cut below still applies to it.
+ * THE WINDOWS: otherwise C = prec_z when reduced, else 1.  For the charge index c = 0 .. C - 1 let z' = prec_z - c; for the
+ * loss index l = 0 .. n_loss, window w = c (n_loss + 1) + l is, in double, every operation rounded on its own, in this order:
+ *   M    = prec_mz (double)prec_z
+ *   cen  = (M - loss[l]) / (double)z'
+ *   span = (double)isotopes (step / (double)z')
+ *   lo   = cen - tol
+ *   hi   = (cen + span) + tol
+ * At most 8 x 8 = 64 windows.  A window whose cen is not finite or not positive is INACTIVE.  loss[0] is always 0.0: window
+ * c (n_loss + 1) is the (charge-reduced) precursor itself.
+ * WHICH PEAKS GO: a peak with m/z x (float32 is widened at the load) is REMOVED iff x < mz_lo, or x > mz_hi, or some active
+ * window has lo <= x && x <= hi.  A comparison with a NaN is false, so a peak with a NaN m/z stays.  Intensities are never
+ * looked at.  The rule is per peak and order-free: a spectrum need not be ascending and there is no "not ascending" path.
+ * The output is the kept peaks in input order, bits copied.
+ * THE REPORT: per spectrum one pya_strip_report.  Bit w of hit is set iff at least one peak of the spectrum lies in active
+ * window w, whether or not the range cut removes that peak too; n_windows is the number of active windows; n_removed the
+ * number of peaks removed by any part of the rule.  "Precursor - 98 seen" is the classic pS/pT-versus-pY hint.
+ * The parameters must satisfy: tol finite and >= 0; step finite and > 0; mz_lo and mz_hi not NaN with mz_lo <= mz_hi (the
+ * defaults -inf and +inf cut nothing); n_loss <= PYA_STRIP_MAX_LOSS; loss[0] == 0.0 and loss[1 .. n_loss] finite and >= 0
+ * (entries above n_loss are not read); reduced 0 or 1; isotopes 0 .. PYA_STRIP_MAX_ISOTOPES; reserved == 0. */
+#define PYA_STRIP_MAX_CHARGE 8
+#define PYA_STRIP_MAX_LOSS 7
+#define PYA_STRIP_MAX_ISOTOPES 4
+#define PYA_STRIP_STEP 1.0033548378
+typedef struct pya_strip_params {   /* 112 bytes */
+    double tol;                             /* half width of a window beyond its centre (and its isotopes), in m/z (Da)      */
+    double step;                            /* the isotope spacing at charge 1; a window reaches isotopes step / z' upwards  */
+    double mz_lo, mz_hi;                    /* the range cut: peaks below mz_lo or above mz_hi go                            */
+    double loss[PYA_STRIP_MAX_LOSS + 1];    /* neutral masses taken off M; [0] is 0.0, [1 .. n_loss] the caller's            */
+    uint32_t n_loss;                        /* 0 .. PYA_STRIP_MAX_LOSS                                                       */
+    uint32_t reduced;                       /* 1: windows at every charge prec_z, prec_z - 1, .. 1 (ETD); 0: at prec_z only  */
+    uint32_t isotopes;                      /* isotope peaks above the centre a window covers, 0 .. PYA_STRIP_MAX_ISOTOPES   */
+    uint32_t reserved;                      /* 0                                                                             */
+} pya_strip_params;
+typedef struct pya_strip_report {   /* 16 bytes per spectrum */
+    uint64_t hit;                           /* bit w: a peak lay in active window w = c (n_loss + 1) + l                     */
+    uint32_t n_removed;                     /* peaks removed, by a window or by the range cut                                */
+    uint32_t n_windows;                     /* active windows                                                                */
+} pya_strip_report;
+
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
  * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
@@ -917,6 +965,37 @@ int pya_decharge_spectra_host(pya_handle *h, const pya_typed_spectra *in, const 
 /* Diagnostic: which of the three passes pya_decharge_spectra launches from now on, in every handle (bit 0 mark, bit 1 scan,
  * bit 2 place; 7 is the default).  For scripts/decharge_probe.py, which times the passes apart; not thread-safe. */
 void pya_debug_decharge_passes(uint32_t passes);
+/* The device bytes pya_strip_spectra needs as its workspace for n_spectra spectra of n_peaks peaks together: what
+ * pya_deisotope_workspace_bytes gives (one keep bit per peak in 64-bit words that no two spectra share, and the tile sums of
+ * the offset scan; 8 bytes at the least). */
+uint64_t pya_strip_workspace_bytes(uint64_t n_spectra, uint64_t n_peaks);
+/* Strips the precursor-derived peaks from n_spectra spectra on the device (THE RULE at pya_strip_params above;
+ * csrc/strip.hip).  The arguments are those of pya_deisotope_spectra, one for one, with the precursors and the report beside
+ * them: d_prec_mz[n_spectra] (double) and d_prec_z[n_spectra] (int32) in device memory, d_report[n_spectra] one
+ * pya_strip_report per spectrum (device memory, 8-byte aligned), or NULL when it is not wanted.  Three passes on hip_stream
+ * -- mark and count (every lane of a wavefront holds one window of the spectrum, every peak is tested against all of them),
+ * an exclusive scan of the counts, deisotoping's fill --, stream-ordered, no host wait and no allocation; the caller lends
+ * d_work (8-byte aligned, work_bytes >= pya_strip_workspace_bytes(n_spectra, d_peak_off[n_spectra])).  The kept peaks of
+ * spectrum s are d_out[d_new_off[s] .. d_new_off[s + 1]), in their order, bit for bit.  No write lies outside
+ * out[0 .. d_new_off[n_spectra]), d_new_off[0 .. n_spectra], d_report[0 .. n_spectra), d_over[0 .. 2) and
+ * d_work[0 .. work_bytes): the out elements from d_new_off[n_spectra] up to the input's length stay as they were.  The peak
+ * count is on the device, so the host can only check the workspace against pya_strip_workspace_bytes(n_spectra, 0); the
+ * kernels clip the offsets to the peaks the lent workspace has bits for, and a spectrum that reaches beyond them is counted
+ * in d_over[0], the smallest such spectrum in d_over[1] as 0xffffffff - spectrum (its report is that of the clipped peaks).
+ * Nothing else is reported in d_over: no spectrum is "not ascending" under this rule.
+ * PYA_ERR_ARG, with nothing launched: everything pya_deisotope_spectra refuses about its arrays, its workspace and n_spectra,
+ * a NULL d_prec_mz or d_prec_z, a d_report that is not 8-byte aligned, parameters outside the conditions above.
+ * n_spectra == 0 writes d_new_off[0] = 0 and nothing else. */
+int pya_strip_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64_t *d_peak_off, uint64_t n_spectra,
+                      const double *d_prec_mz, const int32_t *d_prec_z, const pya_strip_params *params, void *hip_stream,
+                      void *d_work, uint64_t work_bytes, const pya_typed_spectra *d_out, int64_t *d_new_off,
+                      pya_strip_report *d_report, uint32_t *d_over);
+/* The same over HOST arrays, as pya_deisotope_spectra_host: uploads, runs on the handle's stream with a workspace of its own,
+ * downloads out[0 .. new_off[n_spectra]), new_off, report[0 .. n_spectra) (report may be NULL) and over, and waits.
+ * peak_off[0] must not be negative and the offsets must not descend (PYA_ERR_ARG). */
+int pya_strip_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                           const double *prec_mz, const int32_t *prec_z, const pya_strip_params *params,
+                           const pya_typed_spectra *out, int64_t *new_off, pya_strip_report *report, uint32_t *over);
 /* The device bytes pya_plan_peptidoforms / pya_peptidoform_reduce need as their workspace for n_entries entries (PSMs of the
  * plan + records of d_prev; records of d_a + d_b): keys double-buffered, the entries, the staged list, digit histograms, tile
  * totals, about 133 bytes per entry; 0 for no entries (and above 2^31 - 1, which the calls refuse). */

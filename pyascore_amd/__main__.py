@@ -17,7 +17,9 @@ in the log) and ``--mz_calibration_out FILE`` / ``--mz_calibration FILE`` (fit a
 the spectra corrected by one) and ``--deisotope`` with ``--deisotope_tol DA``, ``--deisotope_charge Z`` and
 ``--deisotope_ratio R`` (remove isotope satellites from every spectrum on the device before it is scored) and ``--decharge``
 with ``--decharge_tol DA``, ``--decharge_charge Z``, ``--decharge_ratio R`` and ``--decharge_witness W`` (deisotope, and reduce
-multiply charged fragments to 1+) are the additions."""
+multiply charged fragments to 1+) and ``--strip_precursor`` with ``--strip_tol DA``, ``--strip_losses M1,M2,...``,
+``--strip_reduced``, ``--strip_isotopes N``, ``--strip_mz_min X`` and ``--strip_mz_max X`` (remove the precursor, its
+neutral-loss and charge-reduced forms and the peaks outside an m/z range from every spectrum) are the additions."""
 import argparse
 import re
 import sys
@@ -139,10 +141,45 @@ def build_parser():
     p.add_argument("--decharge_witness", type=float, default=0.3, metavar="W",
                    help="with --decharge: a satellite testifies to a charge only if it is at least W times as intense as its parent "
                         "(default 0.3, from synthetic spectra)")
+    p.add_argument("--strip_precursor", action="store_true",
+                   help="remove the precursor-derived peaks from every spectrum on the device before it is scored, in front of "
+                        "--deisotope / --decharge / --mz_calibration: the peaks within --strip_tol of the spectrum's precursor m/z "
+                        "and of its --strip_losses forms; a spectrum without a precursor m/z or charge keeps them; one more "
+                        "transfer of the spectra")
+    p.add_argument("--strip_tol", type=float, default=None, metavar="DA",
+                   help="with --strip_precursor: the half width of a window around a precursor form, in m/z (default: --mz_error)")
+    p.add_argument("--strip_losses", type=str, default="", metavar="M1,M2,...",
+                   help="with --strip_precursor: up to 7 neutral masses whose loss from the precursor is removed as well, e.g. "
+                        "97.976896,18.010565 (default: none)")
+    p.add_argument("--strip_reduced", action="store_true",
+                   help="with --strip_precursor: also at every charge below the precursor's, down to 1 (the charge-reduced "
+                        "precursors of ETD)")
+    p.add_argument("--strip_isotopes", type=int, default=0, metavar="N",
+                   help="with --strip_precursor: the isotope peaks above each form that its window covers, 0 .. 4 (default 0)")
+    p.add_argument("--strip_mz_min", type=float, default=float("-inf"), metavar="X",
+                   help="with --strip_precursor: peaks below this m/z are removed too (a TMT reporter region: 140)")
+    p.add_argument("--strip_mz_max", type=float, default=float("inf"), metavar="X",
+                   help="with --strip_precursor: peaks above this m/z are removed too")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
     return p
+
+
+def strip_request(args):
+    """The rule of ``--strip_precursor`` as the dict ``batch_cli.localize(strip=...)`` takes (the precursors come from the
+    spectra), checked; None without the flag: the other ``--strip_*`` values are then not looked at."""
+    if not getattr(args, "strip_precursor", False):
+        return None
+    from .rollup import strip_params
+    try:
+        losses = tuple(float(v) for v in args.strip_losses.split(",") if v.strip())
+    except ValueError:
+        raise ValueError("--strip_losses takes neutral masses separated by commas, not %r" % args.strip_losses) from None
+    req = dict(tol=args.strip_tol, losses=losses, reduced=bool(args.strip_reduced), isotopes=args.strip_isotopes, mz_lo=args.strip_mz_min,
+               mz_hi=args.strip_mz_max)
+    strip_params(**dict(req, tol=args.mz_error if args.strip_tol is None else args.strip_tol))
+    return req
 
 
 def validate_args(args):
@@ -158,6 +195,7 @@ def validate_args(args):
     if getattr(args, "deisotope", False):
         from .rollup import deisotope_params
         deisotope_params(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio)
+    strip_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -233,7 +271,7 @@ def run(args, log=print):
                               site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
                               peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
-                              deisotope=deisotope, decharge=decharge)
+                              deisotope=deisotope, decharge=decharge, strip=strip_request(args))
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:

@@ -207,6 +207,31 @@ class DechargeParams(C.Structure):
 
 assert C.sizeof(DechargeParams) == 112, "pya_decharge_params is a 112-byte record"
 
+PYA_STRIP_MAX_CHARGE = 8
+PYA_STRIP_MAX_LOSS = 7
+PYA_STRIP_MAX_ISOTOPES = 4
+PYA_STRIP_STEP = 1.0033548378
+
+
+class StripParams(C.Structure):
+    """pya_strip_params: the half width of a window, the isotope spacing, the range cut, the neutral losses ([0] is 0.0) and
+    how many of them, charge-reduced precursors or not, the isotope peaks a window covers"""
+    _fields_ = [("tol", C.c_double), ("step", C.c_double), ("mz_lo", C.c_double), ("mz_hi", C.c_double),
+                ("loss", C.c_double * (PYA_STRIP_MAX_LOSS + 1)), ("n_loss", C.c_uint32), ("reduced", C.c_uint32), ("isotopes", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(StripParams) == 112, "pya_strip_params is a 112-byte record"
+
+
+class StripReport(C.Structure):
+    """pya_strip_report: which windows of a spectrum held a peak, the peaks removed, the active windows"""
+    _fields_ = [("hit", C.c_uint64), ("n_removed", C.c_uint32), ("n_windows", C.c_uint32)]
+
+
+assert C.sizeof(StripReport) == 16, "pya_strip_report is a 16-byte record"
+STRIP_REPORT_DTYPE = [("hit", "<u8"), ("n_removed", "<u4"), ("n_windows", "<u4")]
+
 
 def spectrum_type(dtype):
     """PYA_F64 / PYA_F32 for a numpy dtype (or its name: 'float64', 'float32'); anything else is no spectrum type."""
@@ -287,6 +312,11 @@ SYMBOLS = {
     "pya_decharge_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.POINTER(DechargeParams),
                                             C.POINTER(TypedSpectra), _vp, _vp, _vp]),
     "pya_debug_decharge_passes": (None, [C.c_uint32]),
+    "pya_strip_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "pya_strip_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.POINTER(StripParams), _vp, _vp, C.c_uint64,
+                                    C.POINTER(TypedSpectra), _vp, _vp, _vp]),
+    "pya_strip_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.POINTER(StripParams),
+                                         C.POINTER(TypedSpectra), _vp, _vp, _vp]),
     "pya_peptidoform_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "pya_peptidoform_reduce": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "pya_peptidoform_reduce_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),

@@ -131,7 +131,8 @@ def select_psms(psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment
             picked.append(dict(mz=spectrum["mz_values"], intensity=spectrum["intensity_values"],
                                peptide=match["peptide"], n_of_mod=n_variable,
                                max_charge=min(max_fragment_charge, psm_charge(match, spectrum) - 1),
-                               aux_pos=const_pos, aux_mass=const_masses))
+                               aux_pos=const_pos, aux_mass=const_masses, precursor_mz=spectrum.get("precursor_mz"),
+                               precursor_charge=spectrum.get("precursor_charge")))
             scans.append(match["scan"])
             if reported is not None:
                 reported.append(reported_positions(residues, mod_mass, match["peptide"], match["mod_positions"], match["mod_masses"],
@@ -157,11 +158,30 @@ def pack_hits(picked, scans):
     return pack_shared_batch(spectra, [dict(p, spectrum=s) for p, s in zip(picked, spec_of)])
 
 
+def hit_precursors(picked, scans):
+    """The precursor m/z (float64) and charge (int32) of every spectrum of ``pack_hits(picked, scans)``, in its order: what
+    ``select_psms`` took from the spectra's ``precursor_mz`` / ``precursor_charge``.  A value that is missing or no number
+    becomes m/z 0 and charge 0: a spectrum without windows (``pya_strip_params``)."""
+    def number(v, kind):
+        try:
+            return kind(v) if v is not None else kind(0)
+        except (TypeError, ValueError, OverflowError):
+            return kind(0)
+
+    prec_mz, prec_z = [], []
+    for i, psm in enumerate(picked):
+        if i and scans[i] == scans[i - 1] and psm["mz"] is picked[i - 1]["mz"] and psm["intensity"] is picked[i - 1]["intensity"]:
+            continue
+        prec_mz.append(number(psm.get("precursor_mz"), float))
+        prec_z.append(min(max(number(psm.get("precursor_charge"), int), -1), 0x7FFFFFFF))
+    return np.asarray(prec_mz, np.float64), np.asarray(prec_z, np.int32)
+
+
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
-             recalibrate=None, deisotope=None, decharge=None):
+             recalibrate=None, deisotope=None, decharge=None, strip=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -199,7 +219,16 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     that of the filtered spectra.
     ``decharge``: ``dict(tol=, max_charge=, ratio=, witness=)`` as ``PyAscore.score_batch(decharge=...)`` takes it: every spectrum is
     deisotoped and its multiply charged fragments are reduced to 1+ on the device before it is scored; not together with
-    ``deisotope`` or ``recalibrate``."""
+    ``deisotope`` or ``recalibrate``.
+    ``strip``: ``dict(tol=, losses=, reduced=, isotopes=, mz_lo=, mz_hi=)`` as ``PyAscore.score_batch(strip=...)`` takes it, without
+    the precursors: they are the spectra's own ``precursor_mz`` / ``precursor_charge`` (``hit_precursors``; a spectrum that lacks
+    one keeps its peaks but for the range cut).  The precursor-derived peaks are removed from every spectrum on the device
+    before anything else is done to it; goes with each of ``deisotope``, ``decharge`` and ``recalibrate``."""
+    if strip is not None:                                  # (a bad request is refused before anything is read or scored)
+        from .ascore import _strip_request
+        if not isinstance(strip, dict) or "precursor_mz" in strip or "precursor_charge" in strip:
+            raise ValueError("strip takes a dict of tol, losses, reduced, isotopes, step, mz_lo and mz_hi: the precursors are the spectra's")
+        _strip_request(dict(strip, precursor_mz=np.zeros(0), precursor_charge=np.zeros(0, np.int32)), getattr(ascore, "_mz_error", 0.0))
     if not isinstance(ascore, PyAscore):
         raise TypeError("ascore must be a pyascore_amd.PyAscore")
     where = [] if reported else None
@@ -236,6 +265,9 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
             raise ValueError("decharge cannot be combined with deisotope (it contains it) or with recalibrate (correct the spectra first)")
         _decharge_request(decharge)
         stages["decharge"] = dict(decharge)
+    if strip is not None:
+        prec_mz, prec_z = hit_precursors(picked, scans)
+        stages["strip"] = dict(strip, precursor_mz=prec_mz, precursor_charge=prec_z)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything

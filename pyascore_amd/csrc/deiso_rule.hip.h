@@ -8,6 +8,12 @@
 #define DEISO_WAVES 4
 #define DEISO_MAX_BLOCKS 2048u
 
+/* the capped grid that strides over n_spectra spectra, DEISO_WAVES of them per workgroup */
+static inline uint32_t deiso_blocks(uint64_t n_spectra) {
+    const uint64_t want = (n_spectra + DEISO_WAVES - 1) / DEISO_WAVES;
+    return (uint32_t)(want < DEISO_MAX_BLOCKS ? want : DEISO_MAX_BLOCKS);
+}
+
 DEV double deiso_widen(double x) { return x; }
 DEV double deiso_widen(float x) { return (double)x; }
 

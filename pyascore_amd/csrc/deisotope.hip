@@ -110,14 +110,29 @@ static void deiso_fill(uint32_t blocks, hipStream_t stream, const void *mz, cons
                        n_spectra, cap_peaks, keep, new_off, (TM *)out_mz, (TI *)out_in);
 }
 
+/* FILL alone, for a caller with keep words and scanned offsets of its own (strip.hip): the launch pya_launch_deisotope ends
+ * with.  d_keep and cap_peaks as there. */
+extern "C" int pya_launch_deiso_fill(const void *d_mz, const void *d_in, uint32_t mz_type, uint32_t in_type, const int64_t *d_peak_off,
+                                     uint64_t n_spectra, int64_t cap_peaks, const uint64_t *d_keep, const int64_t *d_new_off, void *d_out_mz,
+                                     void *d_out_in, hipStream_t stream) {
+    if (n_spectra == 0) return 0;
+    const uint32_t blocks = deiso_blocks(n_spectra);
+    if (mz_type == PYA_F32)
+        deiso_fill<uint32_t, uint32_t>(blocks, stream, d_mz, d_in, d_peak_off, n_spectra, cap_peaks, d_keep, d_new_off, d_out_mz, d_out_in);
+    else if (in_type == PYA_F32)
+        deiso_fill<uint64_t, uint32_t>(blocks, stream, d_mz, d_in, d_peak_off, n_spectra, cap_peaks, d_keep, d_new_off, d_out_mz, d_out_in);
+    else
+        deiso_fill<uint64_t, uint64_t>(blocks, stream, d_mz, d_in, d_peak_off, n_spectra, cap_peaks, d_keep, d_new_off, d_out_mz, d_out_in);
+    return (int)hipGetLastError();
+}
+
 /* d_tiles: room for pya_ions_scan_tiles(n_spectra) words; d_keep: the keep words; cap_peaks: the peaks d_keep has bits for.
  * The types are checked by the caller: (F64, F64), (F64, F32) or (F32, F32).  n_spectra in 1 .. 2^32 - 2. */
 extern "C" int pya_launch_deisotope(const void *d_mz, const void *d_in, uint32_t mz_type, uint32_t in_type, const int64_t *d_peak_off,
                                     uint64_t n_spectra, const pya_deisotope_params *prm, int64_t cap_peaks, uint64_t *d_tiles, uint64_t *d_keep,
                                     void *d_out_mz, void *d_out_in, int64_t *d_new_off, uint32_t *d_over, hipStream_t stream) {
     if (n_spectra == 0) return 0;
-    const uint64_t want = (n_spectra + DEISO_WAVES - 1) / DEISO_WAVES;
-    const uint32_t blocks = (uint32_t)(want < DEISO_MAX_BLOCKS ? want : DEISO_MAX_BLOCKS);
+    const uint32_t blocks = deiso_blocks(n_spectra);
     if (mz_type == PYA_F32)
         deiso_mark<float, float>(blocks, stream, d_mz, d_in, d_peak_off, n_spectra, prm, cap_peaks, d_keep, d_new_off, d_over);
     else if (in_type == PYA_F32)
@@ -128,11 +143,5 @@ extern "C" int pya_launch_deisotope(const void *d_mz, const void *d_in, uint32_t
     if (e) return e;
     e = pya_launch_ions_scan(d_new_off, (uint32_t)n_spectra, d_tiles, stream);
     if (e) return e;
-    if (mz_type == PYA_F32)
-        deiso_fill<uint32_t, uint32_t>(blocks, stream, d_mz, d_in, d_peak_off, n_spectra, cap_peaks, d_keep, d_new_off, d_out_mz, d_out_in);
-    else if (in_type == PYA_F32)
-        deiso_fill<uint64_t, uint32_t>(blocks, stream, d_mz, d_in, d_peak_off, n_spectra, cap_peaks, d_keep, d_new_off, d_out_mz, d_out_in);
-    else
-        deiso_fill<uint64_t, uint64_t>(blocks, stream, d_mz, d_in, d_peak_off, n_spectra, cap_peaks, d_keep, d_new_off, d_out_mz, d_out_in);
-    return (int)hipGetLastError();
+    return pya_launch_deiso_fill(d_mz, d_in, mz_type, in_type, d_peak_off, n_spectra, cap_peaks, d_keep, d_new_off, d_out_mz, d_out_in, stream);
 }

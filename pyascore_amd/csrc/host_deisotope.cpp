@@ -32,6 +32,12 @@ int deiso_check(pya_handle *h, const char *who, const pya_typed_spectra *in, con
                 const pya_deisotope_params *params, const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over) {
     if (n_spectra > kDeisoMaxSpectra) return h->fail(PYA_ERR_ARG, -1, "%s: %llu spectra are more than 2^32 - 2", who, (unsigned long long)n_spectra);
     if (const char *why = deiso_params_fault(params)) return h->fail(PYA_ERR_ARG, -1, "%s: %s", who, why);
+    return deiso_check_arrays(h, who, in, peak_off, n_spectra, out, new_off, over);
+}
+
+int deiso_check_arrays(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                       const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over) {
+    if (n_spectra > kDeisoMaxSpectra) return h->fail(PYA_ERR_ARG, -1, "%s: %llu spectra are more than 2^32 - 2", who, (unsigned long long)n_spectra);
     if (!in || !out || !new_off) return h->fail(PYA_ERR_ARG, -1, "NULL pointer passed to %s", who);
     if ((in->mz_type != PYA_F64 && in->mz_type != PYA_F32) || (in->intensity_type != PYA_F64 && in->intensity_type != PYA_F32))
         return h->fail(PYA_ERR_ARG, -1, "%s: element types %u / %u are neither PYA_F64 nor PYA_F32", who, in->mz_type, in->intensity_type);

@@ -965,6 +965,9 @@ int mzp_report(pya_plan *p, uint64_t psm_lo);
 const char *deiso_params_fault(const pya_deisotope_params *p);
 int deiso_check(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
                 const pya_deisotope_params *params, const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over);
+/* ... the same without the parameters: the array checks alone, for a filter with a rule of its own (host_strip.cpp) */
+int deiso_check_arrays(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                       const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");

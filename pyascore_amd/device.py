@@ -662,6 +662,70 @@ def decharge(scorer, d_mz, d_intensity, peak_off, params, out=None, charge=True)
     return o_mz, o_it, new_off, d_charge, over
 
 
+def strip(scorer, d_mz, d_intensity, peak_off, d_prec_mz, d_prec_z, params, out=None, report=True):
+    """Strips the precursor-derived peaks from spectra that live on the device (``pya_strip_spectra``; the rule is
+    ``pya_strip_params``'s in include/pyascore_hip.h): spectra, ``peak_off`` and ``out`` as ``deisotope`` takes them,
+    ``d_prec_mz`` / ``d_prec_z`` the precursor m/z (float64) and charge (int32) of every spectrum as device tensors or host
+    arrays (a host array is uploaded), ``params`` of ``pyascore_amd.rollup.strip_params``; ``report=False`` leaves the report
+    out (``d_report = NULL``).  Returns ``(d_mz_out, d_intensity_out, d_new_off, d_report, d_over)``: the kept peaks of spectrum
+    s are ``out[d_new_off[s]:d_new_off[s + 1]]`` bit for bit, the elements from ``d_new_off[-1]`` on are not written;
+    ``d_report`` is a ``uint8`` tensor ``[n_spectra, 16]`` (``.cpu().numpy().view(pyascore_amd.rollup.STRIP_REPORT_DTYPE)``),
+    or None; ``d_over`` as ``deisotope`` returns it (two zeros: the workspace is sized here).  Three launches on torch's current
+    stream; nothing waits on the host.  A plan needs the peak counts on the host: read ``d_new_off`` back and build the
+    ``DevicePlan`` with it as ``peak_off``; ``deisotope`` / ``decharge`` take the outputs as they are, with ``d_new_off`` as
+    their ``peak_off``.  ``pyascore_amd.rollup.strip`` gives the same bytes."""
+    import torch
+    from .rollup import strip_c_params
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    c_params = strip_c_params(params)
+    device = torch.device("cuda", scorer.device)
+    for t in (d_mz, d_intensity):
+        if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError("spectra must be contiguous one-dimensional float64 or float32 device tensors")
+    if d_mz.dtype == torch.float32 and d_intensity.dtype == torch.float64:
+        raise ValueError("float32 m/z beside float64 intensities is not supported")
+    if d_mz.numel() != d_intensity.numel():
+        raise ValueError("d_mz and d_intensity have one element per peak each")
+    if not isinstance(peak_off, torch.Tensor):
+        host_off = np.ascontiguousarray(peak_off, np.int64)
+        if host_off.ndim != 1 or host_off.size < 1 or int(host_off[-1]) > d_mz.numel():
+            raise ValueError("peak_off has n_spectra + 1 entries and ends inside the spectrum tensors")
+        peak_off = torch.from_numpy(host_off).to(device)
+    if peak_off.dtype != torch.int64 or peak_off.dim() != 1 or peak_off.numel() < 1 or not peak_off.is_contiguous() or not peak_off.is_cuda:
+        raise ValueError("peak_off must be a contiguous int64 tensor of n_spectra + 1 entries")
+    n_spec = peak_off.numel() - 1
+    if not isinstance(d_prec_mz, torch.Tensor):
+        d_prec_mz = torch.from_numpy(np.ascontiguousarray(d_prec_mz, np.float64)).to(device)
+    if not isinstance(d_prec_z, torch.Tensor):
+        d_prec_z = torch.from_numpy(np.ascontiguousarray(d_prec_z, np.int32)).to(device)
+    for t, dtype in ((d_prec_mz, torch.float64), (d_prec_z, torch.int32)):
+        if t.dtype != dtype or tuple(t.shape) != (n_spec,) or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("d_prec_mz (float64) and d_prec_z (int32) are contiguous device tensors with one entry per spectrum")
+    if out is None:
+        out = (torch.empty_like(d_mz), torch.empty_like(d_intensity))
+    o_mz, o_it = out
+    for o, t in ((o_mz, d_mz), (o_it, d_intensity)):
+        if o.dtype != t.dtype or tuple(o.shape) != tuple(t.shape) or not o.is_contiguous() or not o.is_cuda:
+            raise ValueError("out must be a pair of contiguous device tensors of the dtypes and shapes of the inputs")
+    work_bytes = int(scorer._lib.pya_strip_workspace_bytes(n_spec, d_mz.numel()))
+    with torch.cuda.device(device):
+        work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=device)
+        new_off = torch.empty(n_spec + 1, dtype=torch.int64, device=device)
+        over = torch.zeros(2, dtype=torch.int32, device=device)
+        d_report = torch.empty((n_spec, 16), dtype=torch.uint8, device=device) if report else None
+    t_in = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
+    t_out = _lib.TypedSpectra(o_mz.data_ptr(), o_it.data_ptr(), t_in.mz_type, t_in.intensity_type)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    rc = scorer._lib.pya_strip_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_spec, d_prec_mz.data_ptr(), d_prec_z.data_ptr(),
+                                       C.byref(c_params), stream, work.data_ptr(), work.numel() * 8, C.byref(t_out), new_off.data_ptr(),
+                                       d_report.data_ptr() if report and n_spec else None, over.data_ptr())
+    if rc:
+        scorer._raise(rc)
+    # (the caching allocator keeps `work` for this stream until later work on the stream is done with it)
+    return o_mz, o_it, new_off, d_report, over
+
+
 def evidence_rows(raw):
     """A host copy of ``DevicePlan.evidence()`` (``.cpu().numpy()``, uint8 ``[n_psm, max_k, 16]``) as the structured
     array ``[n_psm, max_k]`` that ``PyAscore.score_batch(..., evidence=True)`` returns; a view, no copy."""

@@ -38,6 +38,12 @@ Charge deconvolution: ``decharge_params`` is ``deisotope_params`` with ``carrier
 (``pya_decharge_params``) and ``decharge`` restates that rule -- deisotoping, and every kept peak whose satellites show a charge
 of 2 or more moved to its m/z at 1+, the output sorted -- the host form of ``PyAscore.decharge_spectra`` /
 ``pyascore_amd.device.decharge`` / ``score_batch(decharge=...)``, with the same bytes.
+
+Precursor stripping: ``strip_params`` checks and fills the parameters of ``pya_strip_params``, ``strip_windows`` gives the
+windows of a precursor and ``strip`` restates the rule -- the peaks inside a window of the precursor, of its neutral-loss forms
+and of its charge-reduced forms, and the peaks outside an m/z range, removed -- the host form of ``PyAscore.strip_spectra`` /
+``pyascore_amd.device.strip`` / ``score_batch(strip=...)``, with the same bytes; ``STRIP_REPORT_DTYPE`` is the 16-byte
+``pya_strip_report`` and ``strip_hits`` reads its ``hit`` word.
 """
 import numpy as np
 
@@ -59,6 +65,11 @@ MZC_MAX_PPM = _lib.PYA_MZC_MAX_PPM
 MZP_BANDS, MZP_BINS = _lib.PYA_MZP_BANDS, _lib.PYA_MZP_BINS
 DEISO_MAX_CHARGE = _lib.PYA_DEISO_MAX_CHARGE
 DECHARGE_CARRIER = _lib.PYA_DECHARGE_CARRIER
+STRIP_REPORT_DTYPE = np.dtype(_lib.STRIP_REPORT_DTYPE)  # pya_strip_report, 16 bytes
+assert STRIP_REPORT_DTYPE.itemsize == 16
+STRIP_MAX_CHARGE, STRIP_MAX_LOSS, STRIP_MAX_ISOTOPES = _lib.PYA_STRIP_MAX_CHARGE, _lib.PYA_STRIP_MAX_LOSS, _lib.PYA_STRIP_MAX_ISOTOPES
+STRIP_STEP = _lib.PYA_STRIP_STEP
+STRIP_WINDOWS = STRIP_MAX_CHARGE * (STRIP_MAX_LOSS + 1)     # 64: one bit of ``hit`` each
 TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
@@ -842,3 +853,156 @@ def decharge(mz, intensity, peak_off, params):
     new_off = np.concatenate([[0], np.cumsum(before[rel[1:]] - before[rel[:-1]])]).astype(np.int64)
     return stored[pick].copy(), raw_it[pick].copy(), new_off, charge[pick].copy(), keep
 
+
+
+def strip_params(tol, losses=(), reduced=False, isotopes=0, step=STRIP_STEP, mz_lo=float("-inf"), mz_hi=float("inf")):
+    """The parameters of precursor stripping (``pya_strip_params``) as a dict: ``tol`` the half width of a window in m/z units,
+    ``loss`` the tuple ``(0.0,) + losses`` -- entry 0 is the precursor itself, the others the neutral masses taken off it (up to
+    7: 97.976896 for H3PO4, 18.010565 for water, ...) --, ``reduced``: windows at every charge from the precursor's down to 1
+    (the charge-reduced precursors of ETD) instead of at the precursor's alone, ``isotopes`` the isotope peaks above its centre
+    a window covers (0 .. 4) at ``step / charge`` each, ``mz_lo`` / ``mz_hi`` the range outside which every peak goes (a TMT
+    reporter region: ``mz_lo=140``).  ValueError where the library would refuse: a ``tol`` that is not finite or negative, a
+    ``step`` that is not finite and positive, a NaN bound or ``mz_lo > mz_hi``, more than 7 losses or one that is not finite or
+    negative, ``isotopes`` outside 0 .. 4."""
+    try:
+        losses = tuple(float(v) for v in losses)
+    except TypeError:
+        raise ValueError("strip: losses is a sequence of neutral masses") from None
+    if isinstance(reduced, (bool, np.bool_)):
+        reduced = int(reduced)
+    return check_strip_params(dict(tol=tol, step=step, mz_lo=mz_lo, mz_hi=mz_hi, loss=(0.0,) + losses, reduced=reduced, isotopes=isotopes))
+
+
+def check_strip_params(params):
+    """``params`` (a dict as ``strip_params`` makes it) checked against the conditions of ``pya_strip_params``; returns it with
+    plain Python numbers."""
+    try:
+        out = dict(tol=float(params["tol"]), step=float(params["step"]), mz_lo=float(params["mz_lo"]), mz_hi=float(params["mz_hi"]),
+                   loss=tuple(float(v) for v in params["loss"]), reduced=params["reduced"], isotopes=params["isotopes"])
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("strip: params is the dict of pyascore_amd.rollup.strip_params "
+                         "(tol, step, mz_lo, mz_hi, loss, reduced, isotopes)") from None
+    if not (np.isfinite(out["tol"]) and out["tol"] >= 0.0):
+        raise ValueError("strip: tol = %r is not a finite number >= 0" % out["tol"])
+    if not (np.isfinite(out["step"]) and out["step"] > 0.0):
+        raise ValueError("strip: step = %r is not finite and positive" % out["step"])
+    if np.isnan(out["mz_lo"]) or np.isnan(out["mz_hi"]) or not out["mz_lo"] <= out["mz_hi"]:
+        raise ValueError("strip: mz_lo = %r and mz_hi = %r are not numbers with mz_lo <= mz_hi" % (out["mz_lo"], out["mz_hi"]))
+    loss = out["loss"]
+    if not 1 <= len(loss) <= STRIP_MAX_LOSS + 1 or loss[0] != 0.0:
+        raise ValueError("strip: loss is (0.0, ...) with at most %d losses behind it" % STRIP_MAX_LOSS)
+    if not all(np.isfinite(v) and v >= 0.0 for v in loss):
+        raise ValueError("strip: every loss is a finite number >= 0")
+    for name, top in (("reduced", 1), ("isotopes", STRIP_MAX_ISOTOPES)):
+        v = out[name]
+        try:
+            ok = int(v) == v and 0 <= int(v) <= top
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("strip: %s = %r is not an integer in 0 .. %d" % (name, v, top))
+        out[name] = int(v)
+    return out
+
+
+def strip_c_params(params):
+    """``params`` as the ``pya_strip_params`` structure the library reads."""
+    p = check_strip_params(params)
+    loss = list(p["loss"]) + [0.0] * (STRIP_MAX_LOSS + 1 - len(p["loss"]))
+    return _lib.StripParams(p["tol"], p["step"], p["mz_lo"], p["mz_hi"], (_lib.C.c_double * (STRIP_MAX_LOSS + 1))(*loss), len(p["loss"]) - 1,
+                            p["reduced"], p["isotopes"], 0)
+
+
+def _strip_precursors(prec_mz, prec_z, what="strip"):
+    pm, pz = np.asarray(prec_mz), np.asarray(prec_z)
+    if pm.dtype.kind not in "fiu" or pz.dtype.kind not in "iu" or pm.shape != pz.shape or pm.ndim > 1:
+        raise ValueError("%s: prec_mz is one number per spectrum and prec_z one integer per spectrum" % what)
+    if pz.size and (pz.min() < -2 ** 31 or pz.max() > 2 ** 31 - 1):
+        raise ValueError("%s: prec_z does not fit an int32" % what)
+    return np.ascontiguousarray(pm, np.float64), np.ascontiguousarray(pz, np.int32)
+
+
+def strip_windows(prec_mz, prec_z, params):
+    """The windows of ``pya_strip_params`` for precursors ``prec_mz`` (float64) / ``prec_z`` (int32), one per spectrum (or one
+    pair of numbers): ``(lo, hi, active)``, float64, float64 and bool of shape ``[n_spectra, 64]`` (``[64]`` for one pair),
+    column ``w = c * (n_loss + 1) + l`` being the window of charge ``prec_z - c`` and ``loss[l]`` -- the header's operations in
+    float64, one rounding each.  ``lo`` / ``hi`` are NaN where ``active`` is False."""
+    p = check_strip_params(params)
+    one = np.ndim(prec_mz) == 0
+    pm, pz = _strip_precursors(prec_mz, prec_z, "strip_windows")
+    pm, pz = pm.reshape(-1), pz.reshape(-1)
+    per = len(p["loss"])
+    w = np.arange(STRIP_WINDOWS)
+    c, l = w // per, w % per
+    loss = np.asarray(p["loss"], np.float64)[l]
+    has = (pz >= 1) & (pz <= STRIP_MAX_CHARGE) & np.isfinite(pm) & (pm > 0.0)
+    n_charge = np.where(has, pz if p["reduced"] else 1, 0)
+    valid = c[None, :] < n_charge[:, None]
+    zr = np.where(valid, pz[:, None] - c[None, :], 1).astype(np.float64)
+    with np.errstate(all="ignore"):
+        m = pm * pz.astype(np.float64)
+        cen = (m[:, None] - loss[None, :]) / zr
+        span = np.float64(p["isotopes"]) * (np.float64(p["step"]) / zr)
+        lo = cen - np.float64(p["tol"])
+        hi = (cen + span) + np.float64(p["tol"])
+        active = valid & np.isfinite(cen) & (cen > 0.0)
+    lo, hi = np.where(active, lo, np.nan), np.where(active, hi, np.nan)
+    return (lo[0], hi[0], active[0]) if one else (lo, hi, active)
+
+
+def strip_hits(report, params):
+    """The ``hit`` word of ``STRIP_REPORT_DTYPE`` records read as a bool array ``[n_spectra, n_charges, n_loss + 1]``:
+    ``[s, c, l]`` says that spectrum s had a peak in the window of charge ``prec_z - c`` and ``loss[l]`` (``l = 0``: the
+    precursor itself).  ``n_charges`` is 8 with ``reduced``, else 1."""
+    p = check_strip_params(params)
+    per = len(p["loss"])
+    n_c = STRIP_MAX_CHARGE if p["reduced"] else 1
+    hit = np.asarray(report, STRIP_REPORT_DTYPE).reshape(-1)["hit"]
+    bits = (hit[:, None] >> np.arange(n_c * per, dtype=np.uint64)[None, :]) & np.uint64(1)
+    return bits.astype(bool).reshape(hit.size, n_c, per)
+
+
+def strip(mz, intensity, peak_off, prec_mz, prec_z, params):
+    """Spectra without their precursor-derived peaks: the rule of ``pya_strip_params``, operation for operation in float64, so
+    the bytes are those of ``pya_strip_spectra``.  ``mz`` / ``intensity``: float64 or float32 (widened for the decision, the
+    kept elements are copied bit for bit and the dtype stays), ``peak_off[n_spectra + 1]``, ``prec_mz`` / ``prec_z`` one
+    precursor m/z and charge per spectrum (a charge outside 1 .. 8 or an m/z that is not finite and positive: no windows),
+    ``params`` of ``strip_params``.  A peak goes iff its m/z lies below ``mz_lo``, above ``mz_hi`` or inside an active window of
+    its spectrum (``strip_windows``), bounds included; a NaN m/z stays; the order of the peaks plays no part.  Returns ``(mz,
+    intensity, peak_off, report)``: new arrays of the kept peaks in input order, their offsets (from 0) and one
+    ``STRIP_REPORT_DTYPE`` record per spectrum (``hit``: bit w set iff a peak lay in active window w; ``n_removed``;
+    ``n_windows``).  ValueError where ``pya_strip_spectra_host`` returns ``PYA_ERR_ARG``."""
+    p = check_strip_params(params)
+    mz, intensity = np.asarray(mz), np.asarray(intensity)
+    for name, a in (("mz", mz), ("intensity", intensity)):
+        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
+            raise ValueError("strip: %s is a one-dimensional float64 or float32 array" % name)
+    peak_off = np.asarray(peak_off, np.int64)
+    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+        raise ValueError("strip: peak_off has n_spectra + 1 offsets that do not descend")
+    first, last = int(peak_off[0]), int(peak_off[-1])
+    if mz.size < last or intensity.size < last:
+        raise ValueError("strip: peak_off runs past the end of the spectrum arrays")
+    n_spec = peak_off.size - 1
+    pm, pz = _strip_precursors(prec_mz, prec_z)
+    if pm.shape != (n_spec,):
+        raise ValueError("strip: prec_mz and prec_z have one entry per spectrum")
+    x = mz[first:last].astype(np.float64)
+    rel = peak_off - first
+    lo, hi, active = strip_windows(pm, pz, p)
+    in_window = np.zeros(x.size, bool)
+    report = np.zeros(n_spec, STRIP_REPORT_DTYPE)
+    report["n_windows"] = active.sum(axis=1)
+    for s in np.flatnonzero(active.any(axis=1) & (np.diff(rel) > 0)):
+        a, b = int(rel[s]), int(rel[s + 1])
+        ws = np.flatnonzero(active[s])
+        xs = x[a:b, None]
+        inside = (lo[s, ws][None, :] <= xs) & (xs <= hi[s, ws][None, :])          # [peaks, active windows]
+        in_window[a:b] = inside.any(axis=1)
+        report["hit"][s] = sum(1 << int(w) for w in ws[inside.any(axis=0)])
+    keep = ~((x < p["mz_lo"]) | (x > p["mz_hi"]) | in_window)
+    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+    kept = before[rel[1:]] - before[rel[:-1]]
+    report["n_removed"] = np.diff(rel) - kept
+    new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+    return mz[first:last][keep].copy(), intensity[first:last][keep].copy(), new_off, report
