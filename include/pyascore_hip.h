@@ -581,6 +581,54 @@ typedef struct pya_strip_report {   /* 16 bytes per spectrum */
     uint32_t n_windows;                     /* active windows                                                                */
 } pya_strip_report;
 
+/* Centroiding (peak picking): the first of the transforms in front of a run.  Everything behind it -- the top-N-per-100-m/z
+ * binning, the match window, deisotoping's tol, the strip windows -- takes one (m/z, intensity) pair for one peak.  A
+ * profile-mode spectrum (msconvert without a peak-picking filter, older QTOF exports, "profile MS2" methods) has 10 to 20
+ * samples per peak: the ranks of a window fill with the flanks of its tallest peaks and every flank sample is one more target
+ * for a random match.  Like deisotoping a transform of spectra in front of a plan (the peak counts change); no kernel of a run
+ * knows of it.  The reference has no counterpart.
+ * THE RULE.  Every spectrum is handled on its own.  x[] is its m/z and y[] its intensities (float32 is widened at the load);
+ * all arithmetic is in double, every operation rounded on its own, in the order written; a comparison with a NaN is false.
+ * CONNECTED: points k - 1 and k are connected iff
+ *   g = x[k] - x[k - 1],  lim = gap0 + gap_per_mz x[k - 1],  g <= lim
+ * APEX: point i is an apex iff y[i] > 0 and y[i] >= min_height, and it has no connected left neighbour or y[i - 1] < y[i], and
+ * it has no connected right neighbour or y[i + 1] <= y[i].  So the first point of a plateau is the apex; a NaN intensity is no
+ * apex and lets neither connected neighbour be one.  Two apexes are never adjacent and connected.
+ * FOOTPRINT [l, r] of apex i: l is the smallest index >= i - half_width such that every step k - 1 -> k, l < k <= i, is
+ * connected and has y[k - 1] < y[k]; r is the largest index <= i + half_width such that every step k -> k + 1, i <= k < r, is
+ * connected and has y[k + 1] <= y[k].  The two comparisons are the apex test's own: a run of equal intensities belongs to the
+ * peak on its LEFT, as a plateau belongs to its first point.  (With <= on both sides the footprints of two neighbours would
+ * share every point of a flat valley, y = 3 1 1 3, and the bound below would not hold.)  A valley point may lie in both
+ * neighbours' footprints: it is then r of the left one and l of the right one, and is added to both.
+ * CENTROID, sequentially for k = l .. r, from sw = 0, s = 0:
+ *   sw = sw + y[k],  d = x[k] - x[i],  p = d y[k],  s = s + p
+ * then
+ *   q = s / sw,  c = x[i] + q,  c = (c >= x[l]) ? c : x[l],  c = (c <= x[r]) ? c : x[r]
+ * (so a NaN becomes x[l]), and c is rounded once to the m/z element type.  When l == r the bits of x[i] are copied instead
+ * (c is x[i] but for the sign of a zero).  The output intensity is y[i] with its bits copied when area == 0, and sw rounded
+ * once to the intensity element type when area == 1.
+ * OUTPUT: one pair per apex, in index order.  It is ascending (not strictly) whenever the input is.  Proof: let i < j be
+ * consecutive apexes with footprints [l_i, r_i] and [l_j, r_j].  (1) r_i < j: otherwise the step j - 1 -> j is one of i's right
+ * flank, connected with y[j] <= y[j - 1], and j with a connected left neighbour needs y[j - 1] < y[j].  (2) r_i <= l_j:
+ * otherwise k = l_j + 1 <= r_i < j, and the step k - 1 -> k lies in i's right flank (y[k] <= y[k - 1]) and in j's left flank
+ * (y[k - 1] < y[k]).  (3) The two selects leave x[l] <= c <= x[r] whatever q is (x[l] <= x[r]: the input ascends), and x[l], x[r]
+ * are values of the element type, so rounding, which is monotone, keeps c inside.  Hence c_i <= x[r_i] <= x[l_j] <= c_j.
+ * PASS-THROUGH: a spectrum in which no two adjacent points are connected comes out as its points with y > 0 && y >= min_height,
+ * every byte copied (l == r everywhere).  So an already centroided spectrum survives the transform, and with min_height == 0
+ * and positive intensities it is unchanged.
+ * A spectrum that is NOT ASCENDING in pya_deisotope_params' sense is copied unchanged and reported.
+ * SELECT: an optional byte per spectrum; a spectrum whose byte is 0 is copied unchanged and is not reported.
+ * The parameters must satisfy: gap0 and gap_per_mz finite, >= 0 and not both 0; min_height finite and >= 0; half_width in
+ * 1 .. PYA_CENTROID_MAX_HALF_WIDTH; area 0 or 1; reserved == 0. */
+#define PYA_CENTROID_MAX_HALF_WIDTH 8
+typedef struct pya_centroid_params {   /* 40 bytes */
+    double gap0, gap_per_mz;                /* two adjacent points are of one peak iff they are at most gap0 + gap_per_mz x apart */
+    double min_height;                      /* an apex is at least this intense (and above 0)                                 */
+    uint32_t half_width;                    /* points on either side of the apex a centroid may take in, 1 .. 8              */
+    uint32_t area;                          /* 0: the output intensity is the apex's; 1: the sum over the footprint          */
+    uint64_t reserved;                      /* 0                                                                             */
+} pya_centroid_params;
+
 /* Ranked localisations.  The site table holds the winner and the runner-up of a PSM, the probabilities a sum over all of its
  * site assignments; this is the list itself: the K best site assignments by PepScore, in order -- the positional isomers a
  * report lists (LuciPHOr-style top-two permutations, MaxQuant-style score differences over all isoforms), "everything within
@@ -996,6 +1044,37 @@ int pya_strip_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64_
 int pya_strip_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
                            const double *prec_mz, const int32_t *prec_z, const pya_strip_params *params,
                            const pya_typed_spectra *out, int64_t *new_off, pya_strip_report *report, uint32_t *over);
+/* The device bytes pya_centroid_spectra needs as its workspace for n_spectra spectra of n_peaks points together: what
+ * pya_deisotope_workspace_bytes gives (one keep bit per point in 64-bit words that no two spectra share, and the tile sums of
+ * the offset scan; 8 bytes at the least).  Centroids are recomputed by the last pass, not stored. */
+uint64_t pya_centroid_workspace_bytes(uint64_t n_spectra, uint64_t n_peaks);
+/* Centroids n_spectra spectra on the device (THE RULE at pya_centroid_params above; csrc/centroid.hip).  The arguments, the
+ * contract and the refusals are those of pya_deisotope_spectra, one for one, with d_select beside them: one byte per spectrum
+ * in device memory (0: the spectrum is copied unchanged), or NULL for all.  Three passes on hip_stream -- mark (the apexes of
+ * every 64 points as one keep word; counts), an exclusive scan of the counts, place (every apex walks its footprint, computes
+ * its centroid and writes the pair at its position) --, stream-ordered, no host wait and no allocation; the caller lends d_work
+ * (8-byte aligned, work_bytes >= pya_centroid_workspace_bytes(n_spectra, d_peak_off[n_spectra])).  The peaks of spectrum s are
+ * d_out[d_new_off[s] .. d_new_off[s + 1]).  A spectrum that is not ascending is copied unchanged and counted in d_over[0], the
+ * smallest such spectrum in d_over[1] as 0xffffffff - spectrum.  No write lies outside out[0 .. d_new_off[n_spectra]),
+ * d_new_off[0 .. n_spectra], d_over[0 .. 2) and d_work[0 .. work_bytes): the out elements from d_new_off[n_spectra] up to the
+ * input's length stay as they were.  There is no limit on the points of a spectrum beyond int64 offsets: a profile spectrum of
+ * 200 000 points may come out under the scorer's 65 535 peaks.  The point count is on the device, so the host can only check
+ * the workspace against pya_centroid_workspace_bytes(n_spectra, 0); the kernels clip the offsets to the points the lent
+ * workspace has bits for, and a spectrum that reaches beyond them is reported in d_over as well.
+ * PYA_ERR_ARG, with nothing launched: everything pya_deisotope_spectra refuses about its arrays, its workspace and n_spectra,
+ * parameters outside the conditions above.  n_spectra == 0 writes d_new_off[0] = 0 and nothing else. */
+int pya_centroid_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64_t *d_peak_off, uint64_t n_spectra,
+                         const uint8_t *d_select, const pya_centroid_params *params, void *hip_stream, void *d_work,
+                         uint64_t work_bytes, const pya_typed_spectra *d_out, int64_t *d_new_off, uint32_t *d_over);
+/* The same over HOST arrays, as pya_deisotope_spectra_host: uploads (select too, when it is not NULL), runs on the handle's
+ * stream with a workspace of its own, downloads out[0 .. new_off[n_spectra]), new_off and over, and waits.  peak_off[0] must
+ * not be negative and the offsets must not descend (PYA_ERR_ARG). */
+int pya_centroid_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                              const uint8_t *select, const pya_centroid_params *params, const pya_typed_spectra *out,
+                              int64_t *new_off, uint32_t *over);
+/* Diagnostic: which of the three passes pya_centroid_spectra launches from now on, in every handle (bit 0 mark, bit 1 scan,
+ * bit 2 place; 7 is the default).  For scripts/centroid_probe.py, which times the passes apart; not thread-safe. */
+void pya_debug_centroid_passes(uint32_t passes);
 /* The device bytes pya_plan_peptidoforms / pya_peptidoform_reduce need as their workspace for n_entries entries (PSMs of the
  * plan + records of d_prev; records of d_a + d_b): keys double-buffered, the entries, the staged list, digit histograms, tile
  * totals, about 133 bytes per entry; 0 for no entries (and above 2^31 - 1, which the calls refuse). */

@@ -19,7 +19,9 @@ the spectra corrected by one) and ``--deisotope`` with ``--deisotope_tol DA``, `
 with ``--decharge_tol DA``, ``--decharge_charge Z``, ``--decharge_ratio R`` and ``--decharge_witness W`` (deisotope, and reduce
 multiply charged fragments to 1+) and ``--strip_precursor`` with ``--strip_tol DA``, ``--strip_losses M1,M2,...``,
 ``--strip_reduced``, ``--strip_isotopes N``, ``--strip_mz_min X`` and ``--strip_mz_max X`` (remove the precursor, its
-neutral-loss and charge-reduced forms and the peaks outside an m/z range from every spectrum) are the additions."""
+neutral-loss and charge-reduced forms and the peaks outside an m/z range from every spectrum) and ``--centroid`` with
+``--centroid_gap DA``, ``--centroid_gap_ppm PPM``, ``--centroid_width W``, ``--centroid_min_height H`` and ``--centroid_area``
+(peak-pick every spectrum the file does not declare centroided, before anything else) are the additions."""
 import argparse
 import re
 import sys
@@ -160,6 +162,21 @@ def build_parser():
                    help="with --strip_precursor: peaks below this m/z are removed too (a TMT reporter region: 140)")
     p.add_argument("--strip_mz_max", type=float, default=float("inf"), metavar="X",
                    help="with --strip_precursor: peaks above this m/z are removed too")
+    p.add_argument("--centroid", action="store_true",
+                   help="centroid (peak-pick) on the device every spectrum that the file does not declare centroided (mzML cvParam "
+                        "MS:1000127, mzXML centroided=\"1\"), in front of --strip_precursor / --deisotope / --decharge / "
+                        "--mz_calibration; a spectrum of isolated peaks passes through unchanged; one more transfer of the spectra")
+    p.add_argument("--centroid_gap", type=float, default=None, metavar="DA",
+                   help="with --centroid: two adjacent samples belong to one peak when they are at most this far apart, in m/z: 2 to "
+                        "3 times the sampling step (needed unless --centroid_gap_ppm is given)")
+    p.add_argument("--centroid_gap_ppm", type=float, default=0.0, metavar="PPM",
+                   help="with --centroid: ... plus this many ppm of the m/z (a TOF's step grows with m/z; default 0)")
+    p.add_argument("--centroid_width", type=int, default=4, metavar="W",
+                   help="with --centroid: the samples on either side of an apex its centroid takes in, 1 .. 8 (default 4)")
+    p.add_argument("--centroid_min_height", type=float, default=0.0, metavar="H",
+                   help="with --centroid: local maxima below this intensity are dropped (default 0)")
+    p.add_argument("--centroid_area", action="store_true",
+                   help="with --centroid: a peak's intensity is the sum over its samples instead of the apex's own")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -182,6 +199,18 @@ def strip_request(args):
     return req
 
 
+def centroid_request(args):
+    """The rule of ``--centroid`` as the dict ``batch_cli.localize(centroid=...)`` takes (which spectra it applies to comes
+    from the spectra), checked; None without the flag: the other ``--centroid_*`` values are then not looked at."""
+    if not getattr(args, "centroid", False):
+        return None
+    from .rollup import centroid_params
+    req = dict(gap=0.0 if args.centroid_gap is None else args.centroid_gap, gap_ppm=args.centroid_gap_ppm, half_width=args.centroid_width,
+               min_height=args.centroid_min_height, area=bool(args.centroid_area))
+    centroid_params(**req)
+    return req
+
+
 def validate_args(args):
     """`__main__.py:48-65`."""
     for aa in args.residues:
@@ -196,6 +225,7 @@ def validate_args(args):
         from .rollup import deisotope_params
         deisotope_params(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio)
     strip_request(args)
+    centroid_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -271,7 +301,8 @@ def run(args, log=print):
                               site_table_threshold=args.site_table_threshold, site_table_flr=args.site_table_flr,
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
                               peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
-                              deisotope=deisotope, decharge=decharge, strip=strip_request(args))
+                              deisotope=deisotope, decharge=decharge, strip=strip_request(args),
+                              centroid=centroid_request(args))
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:

@@ -232,6 +232,18 @@ class StripReport(C.Structure):
 assert C.sizeof(StripReport) == 16, "pya_strip_report is a 16-byte record"
 STRIP_REPORT_DTYPE = [("hit", "<u8"), ("n_removed", "<u4"), ("n_windows", "<u4")]
 
+PYA_CENTROID_MAX_HALF_WIDTH = 8
+
+
+class CentroidParams(C.Structure):
+    """pya_centroid_params: the largest distance of two points of one peak (a constant and a share of the m/z), the least
+    height of an apex, the points on either side a centroid takes in, apex height or summed area"""
+    _fields_ = [("gap0", C.c_double), ("gap_per_mz", C.c_double), ("min_height", C.c_double), ("half_width", C.c_uint32),
+                ("area", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+assert C.sizeof(CentroidParams) == 40, "pya_centroid_params is a 40-byte record"
+
 
 def spectrum_type(dtype):
     """PYA_F64 / PYA_F32 for a numpy dtype (or its name: 'float64', 'float32'); anything else is no spectrum type."""
@@ -317,6 +329,12 @@ SYMBOLS = {
                                     C.POINTER(TypedSpectra), _vp, _vp, _vp]),
     "pya_strip_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.POINTER(StripParams),
                                          C.POINTER(TypedSpectra), _vp, _vp, _vp]),
+    "pya_centroid_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "pya_centroid_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, C.POINTER(CentroidParams), _vp, _vp, C.c_uint64,
+                                       C.POINTER(TypedSpectra), _vp, _vp]),
+    "pya_centroid_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, C.POINTER(CentroidParams),
+                                            C.POINTER(TypedSpectra), _vp, _vp]),
+    "pya_debug_centroid_passes": (None, [C.c_uint32]),
     "pya_peptidoform_workspace_bytes": (C.c_uint64, [C.c_uint64]),
     "pya_peptidoform_reduce": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "pya_peptidoform_reduce_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),

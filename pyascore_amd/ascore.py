@@ -239,6 +239,28 @@ def _strip_request(req, mz_error, n_spec=None):
     return params, prec_mz, prec_z
 
 
+def _centroid_request(req, n_spec=None):
+    """``score_batch(centroid=...)`` checked: ``(params, select)`` -- the dict of ``pyascore_amd.rollup.centroid_params`` and
+    the uint8 ``select`` array (one entry per spectrum; ``n_spec`` entries when it is given) or None"""
+    from .rollup import centroid_params, centroid_select
+    names = ("gap", "gap_ppm", "half_width", "min_height", "area", "select")
+    if not isinstance(req, dict):
+        raise ValueError("centroid takes a dict: " + ", ".join(names))
+    unknown = set(req) - set(names)
+    if unknown:
+        raise ValueError("centroid takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+    if req.get("gap") is None:
+        raise ValueError("centroid needs gap: the largest distance of two samples of one peak, in m/z (2 to 3 sampling steps)")
+    try:
+        params = centroid_params(**{k: v for k, v in req.items() if k != "select"})
+    except TypeError:
+        raise ValueError("centroid: gap, gap_ppm and min_height are numbers, half_width an integer, area a boolean") from None
+    select = req.get("select")
+    if select is not None:
+        select = centroid_select(select, np.size(select) if n_spec is None else n_spec, "centroid")
+    return params, select
+
+
 def _rollup_request(rollup, n_psm):
     """``score_batch(rollup=...)`` as contiguous arrays: dict(slot int32, n_slots, threshold, psm_id uint32 | None,
     site_off int64 | None)"""
@@ -499,7 +521,7 @@ class PyAscore:
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
-                    recalibrate=None, deisotope=None, decharge=None, strip=None):
+                    recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -625,11 +647,36 @@ class PyAscore:
         ``.deisotope``, ``.decharge``), which cost about two device copies of the spectra.  ``keep=True`` retains the transformed batch.  The
         caller's arrays are not written.
 
+        ``centroid=dict(gap=, gap_ppm=0.0, half_width=4, min_height=0.0, area=False, select=None)`` centroids profile-mode spectra
+        before they are scored (``pya_centroid_params``): every local maximum of a run of samples at most ``gap + gap_ppm 1e-6
+        mz`` apart becomes one peak at the intensity-weighted mean m/z of its flanks (``half_width`` samples on either side),
+        with the apex's intensity or, with ``area``, the sum; ``select`` (one boolean per spectrum: per PSM in a private batch,
+        per shared spectrum with ``spec_of``) leaves the spectra it marks False as they are.  An isolated point is copied, so a
+        centroided spectrum passes through.  The spectra go through ``centroid_spectra`` once and the ordinary call then runs
+        on the result with everything else unchanged, so every result is bit-equal to scoring the arrays
+        ``pyascore_amd.rollup.centroid`` returns.  ``centroid=`` comes FIRST, in front of ``strip=``, and goes with each of
+        ``strip=``, ``deisotope=``, ``decharge=`` and ``recalibrate=``: their windows and tolerances are on peaks, not on
+        samples.  Like each of them it is a host form of its own and costs ONE EXTRA PCIe ROUND TRIP of the spectra; a caller
+        whose spectra are resident chains the device forms (``pyascore_amd.device.centroid`` first).  ``keep=True`` retains the
+        transformed batch.  The caller's arrays are not written.
+
         Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
         m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
         of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
         float64 intensities."""
+        if centroid is not None and centroid is not False:
+            n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
+            params, select = _centroid_request(centroid, n_spec)
+            peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
+            if peak_off.size != n_spec + 1:
+                raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
+                                 "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
+            f_mz, f_it, f_off, _ = self.centroid_spectra(batch["mz"], batch["intensity"], peak_off, params, select)
+            return self.score_batch(dict(batch, mz=f_mz, intensity=f_it, peak_off=f_off), keep=keep, skip_invalid=skip_invalid,
+                                    evidence=evidence, ions=ions, named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs,
+                                    ranked=ranked, rollup=rollup, peptidoforms=peptidoforms, mz_profile=mz_profile,
+                                    recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip)
         if strip is not None and strip is not False:
             n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
             params, prec_mz, prec_z = _strip_request(strip, self._mz_error, n_spec)
@@ -1104,6 +1151,43 @@ class PyAscore:
             self._raise(rc)
         kept = int(new_off[-1])
         return out_mz[:kept], out_it[:kept], new_off, report, (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
+
+    def centroid_spectra(self, mz, intensity, peak_off, params, select=None):
+        """Centroided spectra, picked on the device (``pya_centroid_spectra_host``; the rule is ``pya_centroid_params``'s in
+        include/pyascore_hip.h): ``mz`` / ``intensity`` and ``peak_off`` as ``deisotope_spectra`` takes them, ``params`` of
+        ``pyascore_amd.rollup.centroid_params``, ``select`` one boolean per spectrum (False: copied unchanged) or None for
+        all.  Returns ``(mz, intensity, peak_off, over)``: new arrays with one peak per apex of every spectrum, in order, their
+        offsets and ``over = (count, first)``, the number of selected spectra that were not ascending (copied unchanged) and
+        the first of them, ``(0, None)`` when there is none.  ``pyascore_amd.rollup.centroid`` gives the same bytes on the
+        host."""
+        from .rollup import centroid_c_params, centroid_select
+        c_params = centroid_c_params(params)
+        mz, intensity = _typed_spectra(mz, intensity)
+        peak_off = np.ascontiguousarray(peak_off, np.int64)
+        if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
+            raise ValueError("centroid_spectra: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries")
+        if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+            raise ValueError("centroid_spectra: peak_off must not be negative or descend")
+        lo, hi = int(peak_off[0]), int(peak_off[-1])
+        if mz.size < hi or intensity.size < hi:
+            raise ValueError("peak_off runs past the end of the spectrum arrays")
+        mz, intensity, peak_off = mz[lo:hi], intensity[lo:hi], np.ascontiguousarray(peak_off - lo)
+        n_spec = peak_off.size - 1
+        sel = centroid_select(select, n_spec, "centroid_spectra")
+        if n_spec == 0:
+            return mz.copy(), intensity.copy(), np.zeros(1, np.int64), (0, None)
+        out_mz, out_it = np.empty_like(mz), np.empty_like(intensity)
+        new_off, over = np.zeros(n_spec + 1, np.int64), np.zeros(2, np.uint32)
+        if hi == lo:                                         # (no point anywhere: the arrays may have no address to pass)
+            mz, intensity, out_mz, out_it = (np.zeros(1, a.dtype) for a in (mz, intensity, mz, intensity))
+        t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
+        t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
+        rc = self._lib.pya_centroid_spectra_host(self._h, C.byref(t_in), _as_ptr(peak_off), n_spec, None if sel is None else _as_ptr(sel),
+                                                 C.byref(c_params), C.byref(t_out), _as_ptr(new_off), _as_ptr(over))
+        if rc:
+            self._raise(rc)
+        kept = int(new_off[-1])
+        return out_mz[:kept], out_it[:kept], new_off, (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
 
     def rollup_flr(self, table, cls=None, reported_only=False):
         """Site FLR of a roll-up table on the device (``pya_rollup_flr_host``): ``table`` is a ``ROLLUP_DTYPE`` array as

@@ -132,7 +132,7 @@ def select_psms(psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment
                                peptide=match["peptide"], n_of_mod=n_variable,
                                max_charge=min(max_fragment_charge, psm_charge(match, spectrum) - 1),
                                aux_pos=const_pos, aux_mass=const_masses, precursor_mz=spectrum.get("precursor_mz"),
-                               precursor_charge=spectrum.get("precursor_charge")))
+                               precursor_charge=spectrum.get("precursor_charge"), profile=spectrum.get("profile")))
             scans.append(match["scan"])
             if reported is not None:
                 reported.append(reported_positions(residues, mod_mass, match["peptide"], match["mod_positions"], match["mod_masses"],
@@ -177,11 +177,23 @@ def hit_precursors(picked, scans):
     return np.asarray(prec_mz, np.float64), np.asarray(prec_z, np.int32)
 
 
+def hit_profiles(picked, scans):
+    """One boolean per spectrum of ``pack_hits(picked, scans)``, in its order: True unless the file declared the spectrum
+    centroided (``profile`` False, as ``ingest.SpectraParser`` keeps it) -- the ``select`` of ``--centroid``: a spectrum that
+    says nothing is centroided too, which leaves it as it is when it holds centroids already."""
+    select = []
+    for i, psm in enumerate(picked):
+        if i and scans[i] == scans[i - 1] and psm["mz"] is picked[i - 1]["mz"] and psm["intensity"] is picked[i - 1]["intensity"]:
+            continue
+        select.append(psm.get("profile") is not False)
+    return np.asarray(select, bool)
+
+
 def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fragment_charge=5,
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
-             recalibrate=None, deisotope=None, decharge=None, strip=None):
+             recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -223,7 +235,15 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``strip``: ``dict(tol=, losses=, reduced=, isotopes=, mz_lo=, mz_hi=)`` as ``PyAscore.score_batch(strip=...)`` takes it, without
     the precursors: they are the spectra's own ``precursor_mz`` / ``precursor_charge`` (``hit_precursors``; a spectrum that lacks
     one keeps its peaks but for the range cut).  The precursor-derived peaks are removed from every spectrum on the device
-    before anything else is done to it; goes with each of ``deisotope``, ``decharge`` and ``recalibrate``."""
+    before anything else is done to it; goes with each of ``deisotope``, ``decharge`` and ``recalibrate``.
+    ``centroid``: ``dict(gap=, gap_ppm=, half_width=, min_height=, area=)`` as ``PyAscore.score_batch(centroid=...)`` takes it, without
+    ``select``: that is ``hit_profiles`` -- every spectrum the file did not declare centroided (``profile`` of
+    ``ingest.SpectraParser``) is centroided on the device, in front of ``strip`` and everything else."""
+    if centroid is not None:                               # (a bad request is refused before anything is read or scored)
+        from .ascore import _centroid_request
+        if not isinstance(centroid, dict) or "select" in centroid:
+            raise ValueError("centroid takes a dict of gap, gap_ppm, half_width, min_height and area: select is what the spectra declare")
+        _centroid_request(centroid)
     if strip is not None:                                  # (a bad request is refused before anything is read or scored)
         from .ascore import _strip_request
         if not isinstance(strip, dict) or "precursor_mz" in strip or "precursor_charge" in strip:
@@ -268,6 +288,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     if strip is not None:
         prec_mz, prec_z = hit_precursors(picked, scans)
         stages["strip"] = dict(strip, precursor_mz=prec_mz, precursor_charge=prec_z)
+    if centroid is not None:
+        stages["centroid"] = dict(centroid, select=hit_profiles(picked, scans))
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything

@@ -726,6 +726,65 @@ def strip(scorer, d_mz, d_intensity, peak_off, d_prec_mz, d_prec_z, params, out=
     return o_mz, o_it, new_off, d_report, over
 
 
+def centroid(scorer, d_mz, d_intensity, peak_off, params, select=None, out=None):
+    """Centroids profile-mode spectra that live on the device (``pya_centroid_spectra``; the rule is ``pya_centroid_params``'s
+    in include/pyascore_hip.h): spectra, ``peak_off`` and ``out`` as ``deisotope`` takes them, ``params`` of
+    ``pyascore_amd.rollup.centroid_params``, ``select`` one byte per spectrum as a ``uint8`` / ``bool`` device tensor or a
+    host array (uploaded; 0: the spectrum is copied unchanged) or None for all.  Returns ``(d_mz_out, d_intensity_out,
+    d_new_off, d_over)``: the peaks of spectrum s are ``out[d_new_off[s]:d_new_off[s + 1]]``, one per apex, the elements from
+    ``d_new_off[-1]`` on are not written; ``d_over`` as ``deisotope`` returns it (the selected spectra that were not ascending
+    and were copied).  Three launches on torch's current stream; nothing waits on the host.  The first of the transforms:
+    ``strip`` / ``deisotope`` / ``decharge`` take the outputs as they are, with ``d_new_off`` as their ``peak_off``; a plan
+    needs the peak counts on the host.  ``pyascore_amd.rollup.centroid`` gives the same bytes."""
+    import torch
+    from .rollup import centroid_c_params, centroid_select
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    c_params = centroid_c_params(params)
+    device = torch.device("cuda", scorer.device)
+    for t in (d_mz, d_intensity):
+        if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+            raise ValueError("spectra must be contiguous one-dimensional float64 or float32 device tensors")
+    if d_mz.dtype == torch.float32 and d_intensity.dtype == torch.float64:
+        raise ValueError("float32 m/z beside float64 intensities is not supported")
+    if d_mz.numel() != d_intensity.numel():
+        raise ValueError("d_mz and d_intensity have one element per peak each")
+    if not isinstance(peak_off, torch.Tensor):
+        host_off = np.ascontiguousarray(peak_off, np.int64)
+        if host_off.ndim != 1 or host_off.size < 1 or int(host_off[-1]) > d_mz.numel():
+            raise ValueError("peak_off has n_spectra + 1 entries and ends inside the spectrum tensors")
+        peak_off = torch.from_numpy(host_off).to(device)
+    if peak_off.dtype != torch.int64 or peak_off.dim() != 1 or peak_off.numel() < 1 or not peak_off.is_contiguous() or not peak_off.is_cuda:
+        raise ValueError("peak_off must be a contiguous int64 tensor of n_spectra + 1 entries")
+    n_spec = peak_off.numel() - 1
+    if select is not None and not isinstance(select, torch.Tensor):
+        select = torch.from_numpy(centroid_select(select, n_spec, "centroid")).to(device)
+    if select is not None:
+        if select.dtype not in (torch.uint8, torch.bool) or tuple(select.shape) != (n_spec,) or not select.is_contiguous() or not select.is_cuda:
+            raise ValueError("select is a contiguous uint8 or bool device tensor with one entry per spectrum")
+    if out is None:
+        out = (torch.empty_like(d_mz), torch.empty_like(d_intensity))
+    o_mz, o_it = out
+    for o, t in ((o_mz, d_mz), (o_it, d_intensity)):
+        if o.dtype != t.dtype or tuple(o.shape) != tuple(t.shape) or not o.is_contiguous() or not o.is_cuda:
+            raise ValueError("out must be a pair of contiguous device tensors of the dtypes and shapes of the inputs")
+    work_bytes = int(scorer._lib.pya_centroid_workspace_bytes(n_spec, d_mz.numel()))
+    with torch.cuda.device(device):
+        work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=device)
+        new_off = torch.empty(n_spec + 1, dtype=torch.int64, device=device)
+        over = torch.zeros(2, dtype=torch.int32, device=device)
+    t_in = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
+    t_out = _lib.TypedSpectra(o_mz.data_ptr(), o_it.data_ptr(), t_in.mz_type, t_in.intensity_type)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    rc = scorer._lib.pya_centroid_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_spec,
+                                          select.data_ptr() if select is not None and n_spec else None, C.byref(c_params), stream,
+                                          work.data_ptr(), work.numel() * 8, C.byref(t_out), new_off.data_ptr(), over.data_ptr())
+    if rc:
+        scorer._raise(rc)
+    # (the caching allocator keeps `work` and `select` for this stream until later work on the stream is done with them)
+    return o_mz, o_it, new_off, over
+
+
 def evidence_rows(raw):
     """A host copy of ``DevicePlan.evidence()`` (``.cpu().numpy()``, uint8 ``[n_psm, max_k, 16]``) as the structured
     array ``[n_psm, max_k]`` that ``PyAscore.score_batch(..., evidence=True)`` returns; a view, no copy."""

@@ -7,7 +7,7 @@ percolatorTXT, mokapotTXT) -- and :class:`MassCorrector` with nothing but the st
 (``xml.etree`` streaming, ``base64``, ``zlib``, ``csv``) and numpy.  Output records have the
 reference's schema, field for field:
 
-* spectra: ``{scan, ms_level, precursor_mz, precursor_charge, mz_values f64, intensity_values f64}``,
+* spectra: ``{scan, ms_level, precursor_mz, precursor_charge, mz_values f64, intensity_values f64, profile}``,
   sorted by scan (spec_parsers.py:243-282);
 * identifications: ``{scan, charge_state, score, peptide, mod_positions, mod_masses}`` in file order
   within a spectrum, spectra sorted by scan (id_parsers.py:735-815).
@@ -230,17 +230,26 @@ def _as_native(values, width, native_precision):
     return values.astype(np.float32 if native_precision and width == "f4" else np.float64)
 
 
+# what a spectrum's cvParam says of its representation, as the record's "profile": MS:1000128 profile spectrum, MS:1000127
+# centroid spectrum; None where the file says neither
+_SPECTRUM_MODE = {"MS:1000128": True, "MS:1000127": False}
+
+
 class MzMLExtractor:
     """<spectrum> element -> record (spec_parsers.py:49-113).  ``native_precision``: each array keeps the precision its
-    binaryDataArray declares instead of being widened to float64."""
+    binaryDataArray declares instead of being widened to float64.  ``profile``: True for a spectrum the file declares
+    profile-mode (cvParam MS:1000128), False for a centroided one (MS:1000127), None where it says neither."""
 
     def __init__(self, native_precision=False):
         self.native_precision = native_precision
 
     def extract(self, spectrum):
         params = {}
+        profile = None
         for cv in _children(spectrum, "cvParam"):
             params[cv.get("name")] = cv.get("value")
+            if cv.get("accession") in _SPECTRUM_MODE:
+                profile = _SPECTRUM_MODE[cv.get("accession")]
         sid = spectrum.get("id")
         scan = -1
         if sid is not None:
@@ -276,12 +285,13 @@ class MzMLExtractor:
         if "mz" in got and "int" in got:
             mz, inten = got["mz"], got["int"]
         return {"scan": scan, "ms_level": ms_level, "precursor_mz": precursor_mz,
-                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten}
+                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile}
 
 
 class MzXMLExtractor:
     """<scan> element -> record (spec_parsers.py:115-172).  ``native_precision``: both arrays keep the precision the
-    <peaks> element declares (32 unless it says 64) instead of being widened to float64."""
+    <peaks> element declares (32 unless it says 64) instead of being widened to float64.  ``profile``: False where the
+    scan's ``centroided`` attribute is 1, True where it is 0, None without it."""
 
     def __init__(self, native_precision=False):
         self.native_precision = native_precision
@@ -305,8 +315,10 @@ class MzXMLExtractor:
             pairs = _decode(peaks.text.strip(), order + width, peaks.get("compressionType", "none") == "zlib")
             pairs = _as_native(pairs, width, self.native_precision)
             mz, inten = pairs[0::2].copy(), pairs[1::2].copy()
+        centroided = (scan.get("centroided") or "").strip().lower()
+        profile = False if centroided in ("1", "true") else (True if centroided in ("0", "false") else None)
         return {"scan": num, "ms_level": ms_level, "precursor_mz": precursor_mz,
-                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten}
+                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile}
 
 
 def _mzxml_scans(path):

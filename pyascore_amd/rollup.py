@@ -70,7 +70,8 @@ assert STRIP_REPORT_DTYPE.itemsize == 16
 STRIP_MAX_CHARGE, STRIP_MAX_LOSS, STRIP_MAX_ISOTOPES = _lib.PYA_STRIP_MAX_CHARGE, _lib.PYA_STRIP_MAX_LOSS, _lib.PYA_STRIP_MAX_ISOTOPES
 STRIP_STEP = _lib.PYA_STRIP_STEP
 STRIP_WINDOWS = STRIP_MAX_CHARGE * (STRIP_MAX_LOSS + 1)     # 64: one bit of ``hit`` each
-TARGET, DECOY, LEFT_OUT = _lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
+CENTROID_MAX_HALF_WIDTH = _lib.PYA_CENTROID_MAX_HALF_WIDTH
+TARGET, DECOY, LEFT_OUT =_lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
 def _text(peptide):
@@ -1006,3 +1007,138 @@ def strip(mz, intensity, peak_off, prec_mz, prec_z, params):
     report["n_removed"] = np.diff(rel) - kept
     new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
     return mz[first:last][keep].copy(), intensity[first:last][keep].copy(), new_off, report
+
+
+def centroid_params(gap, gap_ppm=0.0, half_width=4, min_height=0.0, area=False):
+    """The parameters of centroiding (``pya_centroid_params``) as a dict: two adjacent points belong to one peak iff they are
+    at most ``gap0 + gap_per_mz * mz`` apart -- ``gap0 = gap`` in m/z units (2 to 3 times the sampling step) and ``gap_per_mz =
+    gap_ppm * 1e-6``, computed here, once, so the device and ``centroid`` read the same bits --, ``half_width`` the points on
+    either side of an apex its centroid may take in (1 .. 8), ``min_height`` the least intensity of an apex, ``area``: the
+    output intensity is the sum over the footprint instead of the apex's own.  ValueError where the library would refuse."""
+    if isinstance(area, (bool, np.bool_)):
+        area = int(area)
+    try:
+        gap_per_mz = float(gap_ppm) * 1e-6
+    except (TypeError, ValueError):
+        raise ValueError("centroid: gap_ppm = %r is not a number" % (gap_ppm,)) from None
+    return check_centroid_params(dict(gap0=gap, gap_per_mz=gap_per_mz, min_height=min_height, half_width=half_width, area=area))
+
+
+def check_centroid_params(params):
+    """``params`` (a dict as ``centroid_params`` makes it) checked against the conditions of ``pya_centroid_params``; returns
+    it with plain Python numbers."""
+    try:
+        out = dict(gap0=float(params["gap0"]), gap_per_mz=float(params["gap_per_mz"]), min_height=float(params["min_height"]),
+                   half_width=params["half_width"], area=params["area"])
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("centroid: params is the dict of pyascore_amd.rollup.centroid_params "
+                         "(gap0, gap_per_mz, min_height, half_width, area)") from None
+    for name in ("gap0", "gap_per_mz", "min_height"):
+        if not (np.isfinite(out[name]) and out[name] >= 0.0):
+            raise ValueError("centroid: %s = %r is not a finite number >= 0" % (name, out[name]))
+    if out["gap0"] == 0.0 and out["gap_per_mz"] == 0.0:
+        raise ValueError("centroid: gap0 and gap_per_mz are both 0")
+    for name, low, top in (("half_width", 1, CENTROID_MAX_HALF_WIDTH), ("area", 0, 1)):
+        v = out[name]
+        try:
+            ok = int(v) == v and low <= int(v) <= top
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("centroid: %s = %r is not an integer in %d .. %d" % (name, v, low, top))
+        out[name] = int(v)
+    return out
+
+
+def centroid_c_params(params):
+    """``params`` as the ``pya_centroid_params`` structure the library reads."""
+    p = check_centroid_params(params)
+    return _lib.CentroidParams(p["gap0"], p["gap_per_mz"], p["min_height"], p["half_width"], p["area"], 0)
+
+
+def centroid_select(select, n_spec, what="centroid"):
+    """``select`` as the uint8 array ``pya_centroid_spectra`` reads (one byte per spectrum, 0: copied unchanged), or None."""
+    if select is None:
+        return None
+    sel = np.asarray(select)
+    if sel.dtype.kind not in "biu" or sel.shape != (n_spec,):
+        raise ValueError("%s: select has one boolean or integer per spectrum" % what)
+    return np.ascontiguousarray(sel != 0, np.uint8)
+
+
+def centroid(mz, intensity, peak_off, params, select=None):
+    """Centroided spectra: the rule of ``pya_centroid_params``, operation for operation in float64, so the bytes are those of
+    ``pya_centroid_spectra``.  ``mz`` / ``intensity``: float64 or float32 (widened for the arithmetic; the dtype stays),
+    ``peak_off[n_spectra + 1]``, ``params`` of ``centroid_params``, ``select`` one boolean per spectrum (False: copied
+    unchanged) or None for all.  Every local maximum of a run of connected points (the first point of a plateau) becomes one
+    peak at the intensity-weighted mean m/z of its monotone flanks, at most ``half_width`` points on either side, summed from
+    the left in the rule's order; an isolated point is copied bit for bit, so centroided spectra pass through.  A spectrum that
+    is not ascending (a descending pair or a NaN m/z) comes back unchanged.  Returns ``(mz, intensity, peak_off, unordered)``:
+    new arrays, their offsets (from 0) and a boolean per spectrum that is True where the spectrum was selected and not
+    ascending (what ``d_over`` counts)."""
+    p = check_centroid_params(params)
+    mz, intensity = np.asarray(mz), np.asarray(intensity)
+    for name, a in (("mz", mz), ("intensity", intensity)):
+        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
+            raise ValueError("centroid: %s is a one-dimensional float64 or float32 array" % name)
+    peak_off = np.asarray(peak_off, np.int64)
+    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+        raise ValueError("centroid: peak_off has n_spectra + 1 offsets that do not descend")
+    first, last = int(peak_off[0]), int(peak_off[-1])
+    if mz.size < last or intensity.size < last:
+        raise ValueError("centroid: peak_off runs past the end of the spectrum arrays")
+    n_spec, n = peak_off.size - 1, last - first
+    sel = centroid_select(select, n_spec)
+    chosen = np.ones(n_spec, bool) if sel is None else sel != 0
+    x, y = mz[first:last].astype(np.float64), intensity[first:last].astype(np.float64)
+    rel = peak_off - first
+    spec = np.repeat(np.arange(n_spec), np.diff(rel))
+    hw = p["half_width"]
+    with np.errstate(all="ignore"):
+        # step[k]: the step k - 1 -> k lies inside one spectrum; conn[k]: ... and is CONNECTED
+        step = np.zeros(n + 1, bool)
+        step[1:n] = spec[1:] == spec[:-1]
+        conn = np.zeros(n + 1, bool)
+        conn[1:n] = step[1:n] & ((x[1:] - x[:-1]) <= (p["gap0"] + p["gap_per_mz"] * x[:-1]))
+        unordered = np.zeros(n_spec, bool)
+        if n > 1:
+            unordered[spec[1:][step[1:n] & ~(x[:-1] <= x[1:])]] = True
+        unordered &= chosen
+        active = (chosen & ~unordered)[spec]
+        y_left, y_right = np.concatenate([[0.0], y[:-1]]), np.concatenate([y[1:], [0.0]])
+        apex = (y > 0.0) & (y >= p["min_height"]) & (~conn[:n] | (y_left < y)) & (~conn[1:] | (y_right <= y))
+        keep = apex | ~active
+        idx = np.flatnonzero(apex & active)
+        # FOOTPRINT
+        l, go = idx.copy(), np.ones(idx.size, bool)
+        for _ in range(hw):
+            go = go & conn[l] & (y[np.maximum(l - 1, 0)] < y[l])
+            l = np.where(go, l - 1, l)
+        r, go = idx.copy(), np.ones(idx.size, bool)
+        for _ in range(hw):
+            go = go & conn[r + 1] & (y[np.minimum(r + 1, n - 1)] <= y[r])
+            r = np.where(go, r + 1, r)
+        # CENTROID: the at most 2 half_width + 1 terms in order, masked
+        sw, s = np.zeros(idx.size), np.zeros(idx.size)
+        for t in range(2 * hw + 1):
+            k = l + t
+            m = k <= r
+            k = np.where(m, k, idx)
+            sw = np.where(m, sw + y[k], sw)
+            d = x[k] - x[idx]
+            s = np.where(m, s + d * y[k], s)
+        q = s / sw
+        c = x[idx] + q
+        c = np.where(c >= x[l], c, x[l])
+        c = np.where(c <= x[r], c, x[r])
+    out_mz, out_it = mz[first:last][keep].copy(), intensity[first:last][keep].copy()
+    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+    pos = before[idx]
+    wide = l != r
+    out_mz[pos[wide]] = c[wide].astype(mz.dtype)
+    if p["area"]:
+        with np.errstate(over="ignore"):
+            out_it[pos] = sw.astype(intensity.dtype)
+    kept = before[rel[1:]] - before[rel[:-1]]
+    new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+    return out_mz, out_it, new_off, unordered
