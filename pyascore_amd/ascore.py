@@ -9,6 +9,7 @@ would abort or read out of bounds on (unknown residue, empty spectrum, ``n_top <
 """
 import ctypes as C
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -27,6 +28,51 @@ def _typed_spectra(mz, intensity):
     it_t = np.float32 if intensity.dtype == np.float32 else np.float64
     mz_t = np.float32 if mz.dtype == np.float32 and it_t == np.float32 else np.float64
     return np.ascontiguousarray(mz, mz_t), np.ascontiguousarray(intensity, it_t)
+
+
+def _n_spectra(batch):
+    """the spectra a batch holds: one per PSM, or the shared ones of a batch with ``spec_of``"""
+    return int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
+
+
+def _batch_peak_off(batch):
+    """the int64 offsets of the spectra of a batch, ``_n_spectra(batch) + 1`` of them"""
+    peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
+    if peak_off.size != _n_spectra(batch) + 1:
+        raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
+                         "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
+    return peak_off
+
+
+def _transform_call(who, mz, intensity, peak_off):
+    """What ``PyAscore.{deisotope,decharge,strip,centroid}_spectra`` (``who``) do alike in front of the library: the spectrum
+    arrays as it takes them, cut to ``peak_off[0]:peak_off[-1]``, the offsets from 0, the arrays it writes and the two
+    ``TypedSpectra``.  ``n_peaks == 0``: ``mz`` / ``intensity`` / ``out_mz`` / ``out_it`` are one-element stand-ins (an empty
+    array may have no address to pass)."""
+    mz, intensity = _typed_spectra(mz, intensity)
+    peak_off = np.ascontiguousarray(peak_off, np.int64)
+    if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
+        raise ValueError("%s: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries" % who)
+    if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+        raise ValueError("%s: peak_off must not be negative or descend" % who)
+    lo, hi = int(peak_off[0]), int(peak_off[-1])
+    if mz.size < hi or intensity.size < hi:
+        raise ValueError("peak_off runs past the end of the spectrum arrays")
+    mz, intensity = (mz[lo:hi], intensity[lo:hi]) if hi > lo else (np.zeros(1, mz.dtype), np.zeros(1, intensity.dtype))
+    out_mz, out_it = np.empty_like(mz), np.empty_like(intensity)
+    t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
+    t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
+    return SimpleNamespace(n_spec=peak_off.size - 1, n_peaks=hi - lo, peak_off=np.ascontiguousarray(peak_off - lo), mz=mz,
+                           intensity=intensity, out_mz=out_mz, out_it=out_it, new_off=np.zeros(peak_off.size, np.int64),
+                           over=np.zeros(2, np.uint32), t_in=t_in, t_out=t_out)
+
+
+def _transform_result(c):
+    """``((mz, intensity, peak_off), over)`` of a ``_transform_call`` the library has answered (or that was not made: no peak
+    is kept): the ``new_off[-1]`` output peaks with their offsets, and ``over = (count, first)``"""
+    kept = int(c.new_off[-1])
+    first = None if not c.over[0] else 0xFFFFFFFF - int(c.over[1])
+    return (c.out_mz[:kept], c.out_it[:kept], c.new_off), (int(c.over[0]), first)
 
 
 def _renumber_psm(message, perm):
@@ -665,57 +711,32 @@ class PyAscore:
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
         of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
         float64 intensities."""
+        def again(done, spectra):
+            """the call itself on what a transform returned, the transform taken out of the request"""
+            rest = dict(keep=keep, skip_invalid=skip_invalid, evidence=evidence, ions=ions, named=named, sites=sites,
+                        site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup, peptidoforms=peptidoforms,
+                        mz_profile=mz_profile, recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip,
+                        centroid=centroid)
+            rest[done] = None
+            return self.score_batch(dict(batch, mz=spectra[0], intensity=spectra[1], peak_off=spectra[2]), **rest)
+
         if centroid is not None and centroid is not False:
-            n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
-            params, select = _centroid_request(centroid, n_spec)
-            peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
-            if peak_off.size != n_spec + 1:
-                raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
-                                 "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
-            f_mz, f_it, f_off, _ = self.centroid_spectra(batch["mz"], batch["intensity"], peak_off, params, select)
-            return self.score_batch(dict(batch, mz=f_mz, intensity=f_it, peak_off=f_off), keep=keep, skip_invalid=skip_invalid,
-                                    evidence=evidence, ions=ions, named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs,
-                                    ranked=ranked, rollup=rollup, peptidoforms=peptidoforms, mz_profile=mz_profile,
-                                    recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip)
+            params, select = _centroid_request(centroid, _n_spectra(batch))
+            return again("centroid", self.centroid_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), params, select))
         if strip is not None and strip is not False:
-            n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
-            params, prec_mz, prec_z = _strip_request(strip, self._mz_error, n_spec)
-            peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
-            if peak_off.size != n_spec + 1:
-                raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
-                                 "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
-            f_mz, f_it, f_off, _, _ = self.strip_spectra(batch["mz"], batch["intensity"], peak_off, prec_mz, prec_z, params)
-            return self.score_batch(dict(batch, mz=f_mz, intensity=f_it, peak_off=f_off), keep=keep, skip_invalid=skip_invalid,
-                                    evidence=evidence, ions=ions, named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs,
-                                    ranked=ranked, rollup=rollup, peptidoforms=peptidoforms, mz_profile=mz_profile,
-                                    recalibrate=recalibrate, deisotope=deisotope, decharge=decharge)
+            params, prec_mz, prec_z = _strip_request(strip, self._mz_error, _n_spectra(batch))
+            return again("strip", self.strip_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), prec_mz, prec_z,
+                                                     params))
         if decharge is not None and decharge is not False:
             if deisotope is not None and deisotope is not False:
                 raise ValueError("decharge= contains deisotoping (its kept peaks are those of deisotope=): pass one of the two")
             if recalibrate is not None:
                 raise ValueError("decharge= cannot be combined with recalibrate=: " + _RECALIBRATE_FIRST)
             params = _decharge_request(decharge)
-            n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
-            peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
-            if peak_off.size != n_spec + 1:
-                raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
-                                 "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
-            f_mz, f_it, f_off, _, _ = self.decharge_spectra(batch["mz"], batch["intensity"], peak_off, params)
-            return self.score_batch(dict(batch, mz=f_mz, intensity=f_it, peak_off=f_off), keep=keep, skip_invalid=skip_invalid,
-                                    evidence=evidence, ions=ions, named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs,
-                                    ranked=ranked, rollup=rollup, peptidoforms=peptidoforms, mz_profile=mz_profile)
+            return again("decharge", self.decharge_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), params))
         if deisotope is not None and deisotope is not False:
             params = _deisotope_request(deisotope)
-            n_spec = int(batch.get("n_spectra", batch["n_psm"])) if batch.get("spec_of") is not None else int(batch["n_psm"])
-            peak_off = np.ascontiguousarray(batch["peak_off"], np.int64)
-            if peak_off.size != n_spec + 1:
-                raise ValueError("offset arrays must have n_psm + 1 entries" if batch.get("spec_of") is None else
-                                 "a shared batch has one spec_of entry per PSM and n_spectra + 1 peak offsets")
-            f_mz, f_it, f_off, _ = self.deisotope_spectra(batch["mz"], batch["intensity"], peak_off, params)
-            return self.score_batch(dict(batch, mz=f_mz, intensity=f_it, peak_off=f_off), keep=keep, skip_invalid=skip_invalid,
-                                    evidence=evidence, ions=ions, named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs,
-                                    ranked=ranked, rollup=rollup, peptidoforms=peptidoforms, mz_profile=mz_profile,
-                                    recalibrate=recalibrate)
+            return again("deisotope", self.deisotope_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), params))
         ranked_k = None if ranked is None or ranked is False else check_ranked_k(ranked)
         roll = None if rollup is None else _rollup_request(rollup, int(batch["n_psm"]))
         pform = None if peptidoforms is None else _peptidoform_request(peptidoforms, int(batch["n_psm"]))
@@ -1050,29 +1071,14 @@ class PyAscore:
         same bytes on the host."""
         from .rollup import deisotope_c_params
         c_params = deisotope_c_params(params)
-        mz, intensity = _typed_spectra(mz, intensity)
-        peak_off = np.ascontiguousarray(peak_off, np.int64)
-        if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
-            raise ValueError("deisotope_spectra: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries")
-        if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-            raise ValueError("deisotope_spectra: peak_off must not be negative or descend")
-        lo, hi = int(peak_off[0]), int(peak_off[-1])
-        if mz.size < hi or intensity.size < hi:
-            raise ValueError("peak_off runs past the end of the spectrum arrays")
-        mz, intensity, peak_off = mz[lo:hi], intensity[lo:hi], np.ascontiguousarray(peak_off - lo)
-        n_spec = peak_off.size - 1
-        if hi == lo:                                         # (no peak anywhere: nothing to filter)
-            return mz.copy(), intensity.copy(), np.zeros(n_spec + 1, np.int64), (0, None)
-        out_mz, out_it = np.empty_like(mz), np.empty_like(intensity)
-        new_off, over = np.zeros(n_spec + 1, np.int64), np.zeros(2, np.uint32)
-        t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
-        t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
-        rc = self._lib.pya_deisotope_spectra_host(self._h, C.byref(t_in), _as_ptr(peak_off), n_spec, C.byref(c_params), C.byref(t_out),
-                                                  _as_ptr(new_off), _as_ptr(over))
-        if rc:
-            self._raise(rc)
-        kept = int(new_off[-1])
-        return out_mz[:kept], out_it[:kept], new_off, (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
+        c = _transform_call("deisotope_spectra", mz, intensity, peak_off)
+        if c.n_peaks:                                        # (no peak anywhere: nothing to filter)
+            rc = self._lib.pya_deisotope_spectra_host(self._h, C.byref(c.t_in), _as_ptr(c.peak_off), c.n_spec, C.byref(c_params),
+                                                      C.byref(c.t_out), _as_ptr(c.new_off), _as_ptr(c.over))
+            if rc:
+                self._raise(rc)
+        spectra, over = _transform_result(c)
+        return spectra + (over,)
 
     def decharge_spectra(self, mz, intensity, peak_off, params):
         """Spectra charge-deconvolved on the device (``pya_decharge_spectra_host``; the rule is ``pya_decharge_params``'s in
@@ -1083,29 +1089,15 @@ class PyAscore:
         ascending and came back unchanged.  ``pyascore_amd.rollup.decharge`` gives the same bytes on the host."""
         from .rollup import decharge_c_params
         c_params = decharge_c_params(params)
-        mz, intensity = _typed_spectra(mz, intensity)
-        peak_off = np.ascontiguousarray(peak_off, np.int64)
-        if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
-            raise ValueError("decharge_spectra: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries")
-        if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-            raise ValueError("decharge_spectra: peak_off must not be negative or descend")
-        lo, hi = int(peak_off[0]), int(peak_off[-1])
-        if mz.size < hi or intensity.size < hi:
-            raise ValueError("peak_off runs past the end of the spectrum arrays")
-        mz, intensity, peak_off = mz[lo:hi], intensity[lo:hi], np.ascontiguousarray(peak_off - lo)
-        n_spec = peak_off.size - 1
-        if hi == lo:                                         # (no peak anywhere: nothing to do)
-            return mz.copy(), intensity.copy(), np.zeros(n_spec + 1, np.int64), np.zeros(0, np.uint8), (0, None)
-        out_mz, out_it, charge = np.empty_like(mz), np.empty_like(intensity), np.zeros(mz.size, np.uint8)
-        new_off, over = np.zeros(n_spec + 1, np.int64), np.zeros(2, np.uint32)
-        t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
-        t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
-        rc = self._lib.pya_decharge_spectra_host(self._h, C.byref(t_in), _as_ptr(peak_off), n_spec, C.byref(c_params), C.byref(t_out),
-                                                 _as_ptr(new_off), _as_ptr(charge), _as_ptr(over))
-        if rc:
-            self._raise(rc)
-        kept = int(new_off[-1])
-        return out_mz[:kept], out_it[:kept], new_off, charge[:kept], (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
+        c = _transform_call("decharge_spectra", mz, intensity, peak_off)
+        charge = np.zeros(c.n_peaks, np.uint8)
+        if c.n_peaks:                                        # (no peak anywhere: nothing to do)
+            rc = self._lib.pya_decharge_spectra_host(self._h, C.byref(c.t_in), _as_ptr(c.peak_off), c.n_spec, C.byref(c_params),
+                                                     C.byref(c.t_out), _as_ptr(c.new_off), _as_ptr(charge), _as_ptr(c.over))
+            if rc:
+                self._raise(rc)
+        spectra, over = _transform_result(c)
+        return spectra + (charge[:spectra[0].size], over)
 
     def strip_spectra(self, mz, intensity, peak_off, precursor_mz, precursor_charge, params):
         """Spectra without their precursor-derived peaks, stripped on the device (``pya_strip_spectra_host``; the rule is
@@ -1118,39 +1110,22 @@ class PyAscore:
         host."""
         from .rollup import STRIP_REPORT_DTYPE, strip_c_params
         c_params = strip_c_params(params)
-        mz, intensity = _typed_spectra(mz, intensity)
-        peak_off = np.ascontiguousarray(peak_off, np.int64)
-        if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
-            raise ValueError("strip_spectra: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries")
-        if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-            raise ValueError("strip_spectra: peak_off must not be negative or descend")
-        lo, hi = int(peak_off[0]), int(peak_off[-1])
-        if mz.size < hi or intensity.size < hi:
-            raise ValueError("peak_off runs past the end of the spectrum arrays")
-        mz, intensity, peak_off = mz[lo:hi], intensity[lo:hi], np.ascontiguousarray(peak_off - lo)
-        n_spec = peak_off.size - 1
+        c = _transform_call("strip_spectra", mz, intensity, peak_off)
         charge = np.asarray(precursor_charge)
         if charge.dtype.kind not in "iu":
             raise ValueError("strip_spectra: precursor_charge is one integer per spectrum")
         prec_mz = np.ascontiguousarray(precursor_mz, np.float64)
         prec_z = np.ascontiguousarray(np.clip(charge, -1, 0x7FFFFFFF), np.int32)
-        if prec_mz.shape != (n_spec,) or prec_z.shape != (n_spec,):
+        if prec_mz.shape != (c.n_spec,) or prec_z.shape != (c.n_spec,):
             raise ValueError("strip_spectra: precursor_mz and precursor_charge have one entry per spectrum")
-        report = np.zeros(n_spec, STRIP_REPORT_DTYPE)
-        if n_spec == 0:
-            return mz.copy(), intensity.copy(), np.zeros(1, np.int64), report, (0, None)
-        out_mz, out_it = np.empty_like(mz), np.empty_like(intensity)
-        new_off, over = np.zeros(n_spec + 1, np.int64), np.zeros(2, np.uint32)
-        if hi == lo:                                         # (no peak anywhere: the arrays may have no address to pass)
-            mz, intensity, out_mz, out_it = (np.zeros(1, a.dtype) for a in (mz, intensity, mz, intensity))
-        t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
-        t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
-        rc = self._lib.pya_strip_spectra_host(self._h, C.byref(t_in), _as_ptr(peak_off), n_spec, _as_ptr(prec_mz), _as_ptr(prec_z),
-                                              C.byref(c_params), C.byref(t_out), _as_ptr(new_off), _as_ptr(report), _as_ptr(over))
-        if rc:
-            self._raise(rc)
-        kept = int(new_off[-1])
-        return out_mz[:kept], out_it[:kept], new_off, report, (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
+        report = np.zeros(c.n_spec, STRIP_REPORT_DTYPE)
+        if c.n_spec:                                         # (spectra without a peak are still a call: the report counts the windows)
+            rc = self._lib.pya_strip_spectra_host(self._h, C.byref(c.t_in), _as_ptr(c.peak_off), c.n_spec, _as_ptr(prec_mz), _as_ptr(prec_z),
+                                                  C.byref(c_params), C.byref(c.t_out), _as_ptr(c.new_off), _as_ptr(report), _as_ptr(c.over))
+            if rc:
+                self._raise(rc)
+        spectra, over = _transform_result(c)
+        return spectra + (report, over)
 
     def centroid_spectra(self, mz, intensity, peak_off, params, select=None):
         """Centroided spectra, picked on the device (``pya_centroid_spectra_host``; the rule is ``pya_centroid_params``'s in
@@ -1162,32 +1137,15 @@ class PyAscore:
         host."""
         from .rollup import centroid_c_params, centroid_select
         c_params = centroid_c_params(params)
-        mz, intensity = _typed_spectra(mz, intensity)
-        peak_off = np.ascontiguousarray(peak_off, np.int64)
-        if mz.ndim != 1 or intensity.ndim != 1 or peak_off.ndim != 1 or peak_off.size < 1:
-            raise ValueError("centroid_spectra: mz, intensity and peak_off are one-dimensional, peak_off has n_spectra + 1 entries")
-        if peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-            raise ValueError("centroid_spectra: peak_off must not be negative or descend")
-        lo, hi = int(peak_off[0]), int(peak_off[-1])
-        if mz.size < hi or intensity.size < hi:
-            raise ValueError("peak_off runs past the end of the spectrum arrays")
-        mz, intensity, peak_off = mz[lo:hi], intensity[lo:hi], np.ascontiguousarray(peak_off - lo)
-        n_spec = peak_off.size - 1
-        sel = centroid_select(select, n_spec, "centroid_spectra")
-        if n_spec == 0:
-            return mz.copy(), intensity.copy(), np.zeros(1, np.int64), (0, None)
-        out_mz, out_it = np.empty_like(mz), np.empty_like(intensity)
-        new_off, over = np.zeros(n_spec + 1, np.int64), np.zeros(2, np.uint32)
-        if hi == lo:                                         # (no point anywhere: the arrays may have no address to pass)
-            mz, intensity, out_mz, out_it = (np.zeros(1, a.dtype) for a in (mz, intensity, mz, intensity))
-        t_in = _lib.TypedSpectra(_as_ptr(mz), _as_ptr(intensity), _lib.spectrum_type(mz.dtype), _lib.spectrum_type(intensity.dtype))
-        t_out = _lib.TypedSpectra(_as_ptr(out_mz), _as_ptr(out_it), t_in.mz_type, t_in.intensity_type)
-        rc = self._lib.pya_centroid_spectra_host(self._h, C.byref(t_in), _as_ptr(peak_off), n_spec, None if sel is None else _as_ptr(sel),
-                                                 C.byref(c_params), C.byref(t_out), _as_ptr(new_off), _as_ptr(over))
-        if rc:
-            self._raise(rc)
-        kept = int(new_off[-1])
-        return out_mz[:kept], out_it[:kept], new_off, (int(over[0]), None if not over[0] else 0xFFFFFFFF - int(over[1]))
+        c = _transform_call("centroid_spectra", mz, intensity, peak_off)
+        sel = centroid_select(select, c.n_spec, "centroid_spectra")
+        if c.n_spec:                                         # (spectra without a point are still a call, as for strip_spectra)
+            rc = self._lib.pya_centroid_spectra_host(self._h, C.byref(c.t_in), _as_ptr(c.peak_off), c.n_spec, _as_ptr(sel), C.byref(c_params),
+                                                     C.byref(c.t_out), _as_ptr(c.new_off), _as_ptr(c.over))
+            if rc:
+                self._raise(rc)
+        spectra, over = _transform_result(c)
+        return spectra + (over,)
 
     def rollup_flr(self, table, cls=None, reported_only=False):
         """Site FLR of a roll-up table on the device (``pya_rollup_flr_host``): ``table`` is a ``ROLLUP_DTYPE`` array as

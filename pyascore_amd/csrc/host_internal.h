@@ -30,6 +30,7 @@
 #include <chrono>
 #include <cstring>
 #include <condition_variable>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -960,14 +961,51 @@ int pform_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const vo
  * report of a plan's last pya_plan_mz_profile (psm_lo as for rollup_report) */
 int mzp_check(pya_handle *h, const char *who, uint64_t n_slots, const pya_mz_profile_params *prm);
 int mzp_report(pya_plan *p, uint64_t psm_lo);
-/* host_deisotope.cpp: what is wrong with a set of deisotoping parameters (NULL: nothing), and everything the deisotope calls
- * refuse about their arrays, before anything is launched; host_decharge.cpp asks the same of its own arguments */
+/* host_deisotope.cpp: what is wrong with a set of deisotoping parameters (NULL: nothing); host_decharge.cpp asks it of the
+ * rule inside its own */
 const char *deiso_params_fault(const pya_deisotope_params *p);
-int deiso_check(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
-                const pya_deisotope_params *params, const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over);
-/* ... the same without the parameters: the array checks alone, for a filter with a rule of its own (host_strip.cpp) */
-int deiso_check_arrays(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
-                       const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over);
+/* host_transform.cpp, the frame of the spectrum transforms (host_deisotope.cpp, host_decharge.cpp, host_strip.cpp,
+ * host_centroid.cpp).  xform_check: everything such a call refuses before anything is launched, in the order of the messages --
+ * more than 2^32 - 2 spectra, `params_fault` (what the stage's *_params_fault found, NULL: nothing), the arrays.
+ * xform_check_work: a workspace that is NULL, misaligned or smaller than `least_bytes`, what the function named `sizer` gives
+ * for no peaks. */
+int xform_check(pya_handle *h, const char *who, const char *params_fault, const pya_typed_spectra *in, const int64_t *peak_off,
+                uint64_t n_spectra, const pya_typed_spectra *out, const int64_t *new_off, const uint32_t *over);
+int xform_check_work(pya_handle *h, const char *who, const char *sizer, uint64_t n_spectra, const void *d_work, uint64_t work_bytes,
+                     uint64_t least_bytes);
+/* the words of a workspace in front of a stage's own: the tile sums of the scan over the spectra (0 beyond the cap, where the
+ * call is refused anyway); and the peaks that keep words behind them -- (n_peaks >> 6) + n_spectra + 1 of them, a spectrum's
+ * bits in words of its own (deisotope.hip) -- have bits for */
+uint64_t xform_tile_words(uint64_t n_spectra);
+int64_t xform_keep_cap(uint64_t n_spectra, uint64_t work_bytes);
+/* the device form without spectra: new_off[0] = 0 on the stream */
+int xform_no_spectra(pya_handle *h, int64_t *d_new_off, hipStream_t st);
+/* a buffer a stage takes beside the spectra: read per spectrum (uploaded), written per spectrum (copied back with new_off) or
+ * per output peak (the first new_off[n_spectra] elements copied back); `host` NULL: not passed, and `dev` stays NULL */
+const size_t kXformMaxSides = 3;     /* (strip: two precursor arrays and the report) */
+struct XformSide {
+    enum Kind { SPECTRUM_IN, SPECTRUM_OUT, PEAK_OUT } kind;
+    void *host;
+    size_t elem_bytes;
+    void *dev;                       /* (set by xform_host before it calls the device form) */
+};
+/* the arguments of a device form that xform_host makes: the device copies, the handle's run stream, the workspace */
+struct XformDevice {
+    const pya_typed_spectra *in, *out;
+    const int64_t *peak_off;
+    hipStream_t stream;
+    void *work;
+    uint64_t work_bytes;
+    int64_t *new_off;
+    uint32_t *over;
+};
+/* the host form of a stage whose own checks have passed: validates peak_off, uploads the spectra, the offsets and the
+ * SPECTRUM_IN sides, allocates the out arrays, the other sides, a workspace of workspace_bytes(n_spectra, n_peaks), new_off and
+ * a zeroed over, calls `device_form`, and copies back new_off, over and the SPECTRUM_OUT sides, then the kept peaks and that
+ * many elements of the PEAK_OUT sides */
+int xform_host(pya_handle *h, const char *who, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+               const pya_typed_spectra *out, int64_t *new_off, uint32_t *over, XformSide *side, size_t n_side,
+               uint64_t (*workspace_bytes)(uint64_t, uint64_t), const std::function<int(const XformDevice &)> &device_form);
 /* host_batch.cpp */
 size_t workspace_budget(const pya_handle *h);
 static_assert(sizeof(pya_evidence) == 16, "pya_evidence is one 16-byte store of evidence.hip");

@@ -554,22 +554,20 @@ MZ_PROFILE_DTYPE = np.dtype(_lib.MZ_PROFILE_DTYPE)
 MZ_CALIBRATION_DTYPE = np.dtype(_lib.MZ_CALIBRATION_DTYPE)
 
 
-def deisotope(scorer, d_mz, d_intensity, peak_off, params, out=None):
-    """Deisotopes spectra that live on the device (``pya_deisotope_spectra``; the rule is ``pya_deisotope_params``'s in
-    include/pyascore_hip.h): ``d_mz`` / ``d_intensity`` contiguous float64 or float32 device tensors (float64 / float64, float64
-    m/z with float32 intensities, or both float32), ``peak_off`` an ``int64`` tensor or array ``[n_spectra + 1]`` (a host array
-    is uploaded), ``params`` of ``pyascore_amd.rollup.deisotope_params``.  ``out``: a pair of tensors like the inputs to write
-    into (not the inputs themselves), new when None.  Returns ``(d_mz_out, d_intensity_out, d_new_off, d_over)``: the kept peaks
-    of spectrum s are ``out[d_new_off[s]:d_new_off[s + 1]]`` bit for bit, the elements from ``d_new_off[-1]`` on are not
-    written; ``d_over`` is an ``int32`` tensor of two words (the spectra that were not ascending and were copied, and
-    0xffffffff minus the first of them).  Three launches on torch's current stream; nothing waits on the host.  A plan needs
-    the peak counts on the host: read ``d_new_off`` back and build the ``DevicePlan`` with it as ``peak_off``.
-    ``pyascore_amd.rollup.deisotope`` gives the same bytes."""
+def _upload(a, dtype, device):
+    """a host array as a contiguous device tensor of ``dtype``"""
     import torch
-    from .rollup import deisotope_c_params
+    return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(device)
+
+
+def _transform_inputs(scorer, c_params_of, params, d_mz, d_intensity, peak_off):
+    """What ``deisotope``, ``decharge``, ``strip`` and ``centroid`` check alike about what they read: the scorer, ``params``
+    (through the stage's ``*_c_params``), the spectrum tensors and ``peak_off`` (a host array is uploaded).  Returns
+    ``(c_params, device, peak_off, n_spec)``."""
+    import torch
     if not isinstance(scorer, PyAscore):
         raise TypeError("scorer must be a pyascore_amd.PyAscore")
-    c_params = deisotope_c_params(params)
+    c_params = c_params_of(params)
     device = torch.device("cuda", scorer.device)
     for t in (d_mz, d_intensity):
         if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
@@ -582,24 +580,49 @@ def deisotope(scorer, d_mz, d_intensity, peak_off, params, out=None):
         host_off = np.ascontiguousarray(peak_off, np.int64)
         if host_off.ndim != 1 or host_off.size < 1 or int(host_off[-1]) > d_mz.numel():
             raise ValueError("peak_off has n_spectra + 1 entries and ends inside the spectrum tensors")
-        peak_off = torch.from_numpy(host_off).to(device)
+        peak_off = _upload(host_off, np.int64, device)
     if peak_off.dtype != torch.int64 or peak_off.dim() != 1 or peak_off.numel() < 1 or not peak_off.is_contiguous() or not peak_off.is_cuda:
         raise ValueError("peak_off must be a contiguous int64 tensor of n_spectra + 1 entries")
-    n_spec = peak_off.numel() - 1
+    return c_params, device, peak_off, peak_off.numel() - 1
+
+
+def _transform_outputs(workspace_bytes, device, d_mz, d_intensity, n_spec, out, side_shape=None):
+    """What they make alike for what they write: ``out`` checked (new when None), the workspace the stage's
+    ``pya_*_workspace_bytes`` asks for, the offsets, the two zeroed words of ``d_over`` and, with ``side_shape``, a ``uint8``
+    tensor of that shape.  Returns ``(o_mz, o_it, t_in, t_out, stream, work, new_off, over, side)``: the two ``TypedSpectra`` of
+    the call and torch's current stream among them."""
+    import torch
     if out is None:
         out = (torch.empty_like(d_mz), torch.empty_like(d_intensity))
     o_mz, o_it = out
     for o, t in ((o_mz, d_mz), (o_it, d_intensity)):
         if o.dtype != t.dtype or tuple(o.shape) != tuple(t.shape) or not o.is_contiguous() or not o.is_cuda:
             raise ValueError("out must be a pair of contiguous device tensors of the dtypes and shapes of the inputs")
-    work_bytes = int(scorer._lib.pya_deisotope_workspace_bytes(n_spec, d_mz.numel()))
     with torch.cuda.device(device):
-        work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=device)
+        work = torch.empty((int(workspace_bytes(n_spec, d_mz.numel())) + 7) // 8, dtype=torch.int64, device=device)
         new_off = torch.empty(n_spec + 1, dtype=torch.int64, device=device)
         over = torch.zeros(2, dtype=torch.int32, device=device)
+        side = None if side_shape is None else torch.empty(side_shape, dtype=torch.uint8, device=device)
     t_in = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
     t_out = _lib.TypedSpectra(o_mz.data_ptr(), o_it.data_ptr(), t_in.mz_type, t_in.intensity_type)
-    stream = torch.cuda.current_stream(device).cuda_stream
+    return o_mz, o_it, t_in, t_out, torch.cuda.current_stream(device).cuda_stream, work, new_off, over, side
+
+
+def deisotope(scorer, d_mz, d_intensity, peak_off, params, out=None):
+    """Deisotopes spectra that live on the device (``pya_deisotope_spectra``; the rule is ``pya_deisotope_params``'s in
+    include/pyascore_hip.h): ``d_mz`` / ``d_intensity`` contiguous float64 or float32 device tensors (float64 / float64, float64
+    m/z with float32 intensities, or both float32), ``peak_off`` an ``int64`` tensor or array ``[n_spectra + 1]`` (a host array
+    is uploaded), ``params`` of ``pyascore_amd.rollup.deisotope_params``.  ``out``: a pair of tensors like the inputs to write
+    into (not the inputs themselves), new when None.  Returns ``(d_mz_out, d_intensity_out, d_new_off, d_over)``: the kept peaks
+    of spectrum s are ``out[d_new_off[s]:d_new_off[s + 1]]`` bit for bit, the elements from ``d_new_off[-1]`` on are not
+    written; ``d_over`` is an ``int32`` tensor of two words (the spectra that were not ascending and were copied, and
+    0xffffffff minus the first of them).  Three launches on torch's current stream; nothing waits on the host.  A plan needs
+    the peak counts on the host: read ``d_new_off`` back and build the ``DevicePlan`` with it as ``peak_off``.
+    ``pyascore_amd.rollup.deisotope`` gives the same bytes."""
+    from .rollup import deisotope_c_params
+    c_params, device, peak_off, n_spec = _transform_inputs(scorer, deisotope_c_params, params, d_mz, d_intensity, peak_off)
+    o_mz, o_it, t_in, t_out, stream, work, new_off, over, _ = _transform_outputs(
+        scorer._lib.pya_deisotope_workspace_bytes, device, d_mz, d_intensity, n_spec, out)
     rc = scorer._lib.pya_deisotope_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_spec, C.byref(c_params), stream, work.data_ptr(),
                                            work.numel() * 8, C.byref(t_out), new_off.data_ptr(), over.data_ptr())
     if rc:
@@ -617,42 +640,10 @@ def decharge(scorer, d_mz, d_intensity, peak_off, params, out=None, charge=True)
     output peak (1: not moved), or None; ``d_over`` as ``deisotope`` returns it.  Three launches on torch's current stream;
     nothing waits on the host.  A plan needs the peak counts on the host: read ``d_new_off`` back and build the ``DevicePlan``
     with it as ``peak_off``; leave ``max_fragment_charge`` at 1.  ``pyascore_amd.rollup.decharge`` gives the same bytes."""
-    import torch
     from .rollup import decharge_c_params
-    if not isinstance(scorer, PyAscore):
-        raise TypeError("scorer must be a pyascore_amd.PyAscore")
-    c_params = decharge_c_params(params)
-    device = torch.device("cuda", scorer.device)
-    for t in (d_mz, d_intensity):
-        if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-            raise ValueError("spectra must be contiguous one-dimensional float64 or float32 device tensors")
-    if d_mz.dtype == torch.float32 and d_intensity.dtype == torch.float64:
-        raise ValueError("float32 m/z beside float64 intensities is not supported")
-    if d_mz.numel() != d_intensity.numel():
-        raise ValueError("d_mz and d_intensity have one element per peak each")
-    if not isinstance(peak_off, torch.Tensor):
-        host_off = np.ascontiguousarray(peak_off, np.int64)
-        if host_off.ndim != 1 or host_off.size < 1 or int(host_off[-1]) > d_mz.numel():
-            raise ValueError("peak_off has n_spectra + 1 entries and ends inside the spectrum tensors")
-        peak_off = torch.from_numpy(host_off).to(device)
-    if peak_off.dtype != torch.int64 or peak_off.dim() != 1 or peak_off.numel() < 1 or not peak_off.is_contiguous() or not peak_off.is_cuda:
-        raise ValueError("peak_off must be a contiguous int64 tensor of n_spectra + 1 entries")
-    n_spec = peak_off.numel() - 1
-    if out is None:
-        out = (torch.empty_like(d_mz), torch.empty_like(d_intensity))
-    o_mz, o_it = out
-    for o, t in ((o_mz, d_mz), (o_it, d_intensity)):
-        if o.dtype != t.dtype or tuple(o.shape) != tuple(t.shape) or not o.is_contiguous() or not o.is_cuda:
-            raise ValueError("out must be a pair of contiguous device tensors of the dtypes and shapes of the inputs")
-    work_bytes = int(scorer._lib.pya_decharge_workspace_bytes(n_spec, d_mz.numel()))
-    with torch.cuda.device(device):
-        work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=device)
-        new_off = torch.empty(n_spec + 1, dtype=torch.int64, device=device)
-        over = torch.zeros(2, dtype=torch.int32, device=device)
-        d_charge = torch.empty(d_mz.numel(), dtype=torch.uint8, device=device) if charge else None
-    t_in = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
-    t_out = _lib.TypedSpectra(o_mz.data_ptr(), o_it.data_ptr(), t_in.mz_type, t_in.intensity_type)
-    stream = torch.cuda.current_stream(device).cuda_stream
+    c_params, device, peak_off, n_spec = _transform_inputs(scorer, decharge_c_params, params, d_mz, d_intensity, peak_off)
+    o_mz, o_it, t_in, t_out, stream, work, new_off, over, d_charge = _transform_outputs(
+        scorer._lib.pya_decharge_workspace_bytes, device, d_mz, d_intensity, n_spec, out, (d_mz.numel(),) if charge else None)
     rc = scorer._lib.pya_decharge_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_spec, C.byref(c_params), stream, work.data_ptr(),
                                           work.numel() * 8, C.byref(t_out), new_off.data_ptr(),
                                           d_charge.data_ptr() if charge and d_charge.numel() else None, over.data_ptr())
@@ -676,47 +667,16 @@ def strip(scorer, d_mz, d_intensity, peak_off, d_prec_mz, d_prec_z, params, out=
     their ``peak_off``.  ``pyascore_amd.rollup.strip`` gives the same bytes."""
     import torch
     from .rollup import strip_c_params
-    if not isinstance(scorer, PyAscore):
-        raise TypeError("scorer must be a pyascore_amd.PyAscore")
-    c_params = strip_c_params(params)
-    device = torch.device("cuda", scorer.device)
-    for t in (d_mz, d_intensity):
-        if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-            raise ValueError("spectra must be contiguous one-dimensional float64 or float32 device tensors")
-    if d_mz.dtype == torch.float32 and d_intensity.dtype == torch.float64:
-        raise ValueError("float32 m/z beside float64 intensities is not supported")
-    if d_mz.numel() != d_intensity.numel():
-        raise ValueError("d_mz and d_intensity have one element per peak each")
-    if not isinstance(peak_off, torch.Tensor):
-        host_off = np.ascontiguousarray(peak_off, np.int64)
-        if host_off.ndim != 1 or host_off.size < 1 or int(host_off[-1]) > d_mz.numel():
-            raise ValueError("peak_off has n_spectra + 1 entries and ends inside the spectrum tensors")
-        peak_off = torch.from_numpy(host_off).to(device)
-    if peak_off.dtype != torch.int64 or peak_off.dim() != 1 or peak_off.numel() < 1 or not peak_off.is_contiguous() or not peak_off.is_cuda:
-        raise ValueError("peak_off must be a contiguous int64 tensor of n_spectra + 1 entries")
-    n_spec = peak_off.numel() - 1
+    c_params, device, peak_off, n_spec = _transform_inputs(scorer, strip_c_params, params, d_mz, d_intensity, peak_off)
     if not isinstance(d_prec_mz, torch.Tensor):
-        d_prec_mz = torch.from_numpy(np.ascontiguousarray(d_prec_mz, np.float64)).to(device)
+        d_prec_mz = _upload(d_prec_mz, np.float64, device)
     if not isinstance(d_prec_z, torch.Tensor):
-        d_prec_z = torch.from_numpy(np.ascontiguousarray(d_prec_z, np.int32)).to(device)
+        d_prec_z = _upload(d_prec_z, np.int32, device)
     for t, dtype in ((d_prec_mz, torch.float64), (d_prec_z, torch.int32)):
         if t.dtype != dtype or tuple(t.shape) != (n_spec,) or not t.is_contiguous() or not t.is_cuda:
             raise ValueError("d_prec_mz (float64) and d_prec_z (int32) are contiguous device tensors with one entry per spectrum")
-    if out is None:
-        out = (torch.empty_like(d_mz), torch.empty_like(d_intensity))
-    o_mz, o_it = out
-    for o, t in ((o_mz, d_mz), (o_it, d_intensity)):
-        if o.dtype != t.dtype or tuple(o.shape) != tuple(t.shape) or not o.is_contiguous() or not o.is_cuda:
-            raise ValueError("out must be a pair of contiguous device tensors of the dtypes and shapes of the inputs")
-    work_bytes = int(scorer._lib.pya_strip_workspace_bytes(n_spec, d_mz.numel()))
-    with torch.cuda.device(device):
-        work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=device)
-        new_off = torch.empty(n_spec + 1, dtype=torch.int64, device=device)
-        over = torch.zeros(2, dtype=torch.int32, device=device)
-        d_report = torch.empty((n_spec, 16), dtype=torch.uint8, device=device) if report else None
-    t_in = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
-    t_out = _lib.TypedSpectra(o_mz.data_ptr(), o_it.data_ptr(), t_in.mz_type, t_in.intensity_type)
-    stream = torch.cuda.current_stream(device).cuda_stream
+    o_mz, o_it, t_in, t_out, stream, work, new_off, over, d_report = _transform_outputs(
+        scorer._lib.pya_strip_workspace_bytes, device, d_mz, d_intensity, n_spec, out, (n_spec, 16) if report else None)
     rc = scorer._lib.pya_strip_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_spec, d_prec_mz.data_ptr(), d_prec_z.data_ptr(),
                                        C.byref(c_params), stream, work.data_ptr(), work.numel() * 8, C.byref(t_out), new_off.data_ptr(),
                                        d_report.data_ptr() if report and n_spec else None, over.data_ptr())
@@ -738,44 +698,14 @@ def centroid(scorer, d_mz, d_intensity, peak_off, params, select=None, out=None)
     needs the peak counts on the host.  ``pyascore_amd.rollup.centroid`` gives the same bytes."""
     import torch
     from .rollup import centroid_c_params, centroid_select
-    if not isinstance(scorer, PyAscore):
-        raise TypeError("scorer must be a pyascore_amd.PyAscore")
-    c_params = centroid_c_params(params)
-    device = torch.device("cuda", scorer.device)
-    for t in (d_mz, d_intensity):
-        if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
-            raise ValueError("spectra must be contiguous one-dimensional float64 or float32 device tensors")
-    if d_mz.dtype == torch.float32 and d_intensity.dtype == torch.float64:
-        raise ValueError("float32 m/z beside float64 intensities is not supported")
-    if d_mz.numel() != d_intensity.numel():
-        raise ValueError("d_mz and d_intensity have one element per peak each")
-    if not isinstance(peak_off, torch.Tensor):
-        host_off = np.ascontiguousarray(peak_off, np.int64)
-        if host_off.ndim != 1 or host_off.size < 1 or int(host_off[-1]) > d_mz.numel():
-            raise ValueError("peak_off has n_spectra + 1 entries and ends inside the spectrum tensors")
-        peak_off = torch.from_numpy(host_off).to(device)
-    if peak_off.dtype != torch.int64 or peak_off.dim() != 1 or peak_off.numel() < 1 or not peak_off.is_contiguous() or not peak_off.is_cuda:
-        raise ValueError("peak_off must be a contiguous int64 tensor of n_spectra + 1 entries")
-    n_spec = peak_off.numel() - 1
+    c_params, device, peak_off, n_spec = _transform_inputs(scorer, centroid_c_params, params, d_mz, d_intensity, peak_off)
     if select is not None and not isinstance(select, torch.Tensor):
-        select = torch.from_numpy(centroid_select(select, n_spec, "centroid")).to(device)
+        select = _upload(centroid_select(select, n_spec, "centroid"), np.uint8, device)
     if select is not None:
         if select.dtype not in (torch.uint8, torch.bool) or tuple(select.shape) != (n_spec,) or not select.is_contiguous() or not select.is_cuda:
             raise ValueError("select is a contiguous uint8 or bool device tensor with one entry per spectrum")
-    if out is None:
-        out = (torch.empty_like(d_mz), torch.empty_like(d_intensity))
-    o_mz, o_it = out
-    for o, t in ((o_mz, d_mz), (o_it, d_intensity)):
-        if o.dtype != t.dtype or tuple(o.shape) != tuple(t.shape) or not o.is_contiguous() or not o.is_cuda:
-            raise ValueError("out must be a pair of contiguous device tensors of the dtypes and shapes of the inputs")
-    work_bytes = int(scorer._lib.pya_centroid_workspace_bytes(n_spec, d_mz.numel()))
-    with torch.cuda.device(device):
-        work = torch.empty((work_bytes + 7) // 8, dtype=torch.int64, device=device)
-        new_off = torch.empty(n_spec + 1, dtype=torch.int64, device=device)
-        over = torch.zeros(2, dtype=torch.int32, device=device)
-    t_in = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
-    t_out = _lib.TypedSpectra(o_mz.data_ptr(), o_it.data_ptr(), t_in.mz_type, t_in.intensity_type)
-    stream = torch.cuda.current_stream(device).cuda_stream
+    o_mz, o_it, t_in, t_out, stream, work, new_off, over, _ = _transform_outputs(
+        scorer._lib.pya_centroid_workspace_bytes, device, d_mz, d_intensity, n_spec, out)
     rc = scorer._lib.pya_centroid_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_spec,
                                           select.data_ptr() if select is not None and n_spec else None, C.byref(c_params), stream,
                                           work.data_ptr(), work.numel() * 8, C.byref(t_out), new_off.data_ptr(), over.data_ptr())

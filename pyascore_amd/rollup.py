@@ -620,6 +620,31 @@ def suggest_mz_error(cal, mz_max, k=3.0):
     return float(k) * worst * 1e-6 * float(mz_max)
 
 
+def _transform_entry(who, mz, intensity, peak_off):
+    """What ``deisotope``, ``decharge``, ``strip`` and ``centroid`` (``who``) refuse about their spectra alike.  Returns
+    ``(raw_mz, raw_it, rel)``: the elements ``peak_off[0]:peak_off[-1]`` of the arrays (views, the dtypes stay) and the offsets
+    into them."""
+    mz, intensity = np.asarray(mz), np.asarray(intensity)
+    for name, a in (("mz", mz), ("intensity", intensity)):
+        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
+            raise ValueError("%s: %s is a one-dimensional float64 or float32 array" % (who, name))
+    peak_off = np.asarray(peak_off, np.int64)
+    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
+        raise ValueError("%s: peak_off has n_spectra + 1 offsets that do not descend" % who)
+    first, last = int(peak_off[0]), int(peak_off[-1])
+    if mz.size < last or intensity.size < last:
+        raise ValueError("%s: peak_off runs past the end of the spectrum arrays" % who)
+    return mz[first:last], intensity[first:last], peak_off - first
+
+
+def _transform_exit(keep, rel):
+    """``(before, kept, new_off)`` of a mask over the peaks: the kept peaks in front of every peak, the kept peaks of every
+    spectrum and their offsets (from 0)"""
+    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+    kept = before[rel[1:]] - before[rel[:-1]]
+    return before, kept, np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+
+
 def deisotope_params(tol=0.01, max_charge=3, step=1.0033548378, ratio=1.0, ratio_per_mz=0.0):
     """The parameters of the deisotoping rule (``pya_deisotope_params``) as a dict: ``tol`` the half width of the match on the
     isotope spacing in m/z units, ``max_charge`` the largest charge tried (1 .. 8), ``spacing`` the tuple ``step / z`` for
@@ -710,28 +735,15 @@ def deisotope(mz, intensity, peak_off, params):
     that is not ascending (a descending pair or a NaN m/z) comes back unchanged.  Returns ``(mz, intensity, peak_off, keep)``:
     new arrays of the kept peaks, their offsets (from 0) and the boolean mask over ``peak_off[0]:peak_off[-1]``."""
     p = check_deisotope_params(params)
-    mz, intensity = np.asarray(mz), np.asarray(intensity)
-    for name, a in (("mz", mz), ("intensity", intensity)):
-        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
-            raise ValueError("deisotope: %s is a one-dimensional float64 or float32 array" % name)
-    peak_off = np.asarray(peak_off, np.int64)
-    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-        raise ValueError("deisotope: peak_off has n_spectra + 1 offsets that do not descend")
-    lo, hi = int(peak_off[0]), int(peak_off[-1])
-    if mz.size < hi or intensity.size < hi:
-        raise ValueError("deisotope: peak_off runs past the end of the spectrum arrays")
-    x, y = mz[lo:hi].astype(np.float64), intensity[lo:hi].astype(np.float64)
-    keep = np.ones(hi - lo, bool)
-    rel = peak_off - lo
-    for s in range(peak_off.size - 1):
+    raw_mz, raw_it, rel = _transform_entry("deisotope", mz, intensity, peak_off)
+    x, y = raw_mz.astype(np.float64), raw_it.astype(np.float64)
+    keep = np.ones(x.size, bool)
+    for s in range(rel.size - 1):
         a, b = int(rel[s]), int(rel[s + 1])
         if b - a < 2 or not (x[a:b - 1] <= x[a + 1:b]).all():
             continue
         keep[a:b] = _deisotope_keep(x[a:b], y[a:b], p)
-    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
-    kept = before[rel[1:]] - before[rel[:-1]]
-    new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
-    return mz[lo:hi][keep].copy(), intensity[lo:hi][keep].copy(), new_off, keep
+    return raw_mz[keep].copy(), raw_it[keep].copy(), _transform_exit(keep, rel)[2], keep
 
 
 def decharge_params(tol=0.01, max_charge=3, step=1.0033548378, ratio=1.0, ratio_per_mz=0.0, carrier=DECHARGE_CARRIER, witness=0.3):
@@ -811,23 +823,12 @@ def decharge(mz, intensity, peak_off, params):
     per output peak with its charge (1: not moved, bits of m/z copied), and the boolean mask of the kept peaks over
     ``peak_off[0]:peak_off[-1]`` of the input."""
     p = check_decharge_params(params)
-    mz, intensity = np.asarray(mz), np.asarray(intensity)
-    for name, a in (("mz", mz), ("intensity", intensity)):
-        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
-            raise ValueError("decharge: %s is a one-dimensional float64 or float32 array" % name)
-    peak_off = np.asarray(peak_off, np.int64)
-    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-        raise ValueError("decharge: peak_off has n_spectra + 1 offsets that do not descend")
-    lo, hi = int(peak_off[0]), int(peak_off[-1])
-    if mz.size < hi or intensity.size < hi:
-        raise ValueError("decharge: peak_off runs past the end of the spectrum arrays")
-    raw_mz, raw_it = mz[lo:hi], intensity[lo:hi]
+    raw_mz, raw_it, rel = _transform_entry("decharge", mz, intensity, peak_off)
     x, y = raw_mz.astype(np.float64), raw_it.astype(np.float64)
-    keep = np.ones(hi - lo, bool)
-    order = np.arange(hi - lo)                               # raw indices, to become the output order of the kept peaks
-    stored, charge = raw_mz.copy(), np.ones(hi - lo, np.uint8)
-    rel = peak_off - lo
-    for s in range(peak_off.size - 1):
+    keep = np.ones(x.size, bool)
+    order = np.arange(x.size)                                # raw indices, to become the output order of the kept peaks
+    stored, charge = raw_mz.copy(), np.ones(x.size, np.uint8)
+    for s in range(rel.size - 1):
         a, b = int(rel[s]), int(rel[s + 1])
         if b - a < 2 or not (x[a:b - 1] <= x[a + 1:b]).all():
             continue
@@ -850,10 +851,7 @@ def decharge(mz, intensity, peak_off, params):
         value = np.where(moves, wide, x[a:b])[kept]
         order[a:b][kept] = kept[np.argsort(value, kind="stable")] + a
     pick = order[keep]
-    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
-    new_off = np.concatenate([[0], np.cumsum(before[rel[1:]] - before[rel[:-1]])]).astype(np.int64)
-    return stored[pick].copy(), raw_it[pick].copy(), new_off, charge[pick].copy(), keep
-
+    return stored[pick].copy(), raw_it[pick].copy(), _transform_exit(keep, rel)[2], charge[pick].copy(), keep
 
 
 def strip_params(tol, losses=(), reduced=False, isotopes=0, step=STRIP_STEP, mz_lo=float("-inf"), mz_hi=float("inf")):
@@ -974,22 +972,12 @@ def strip(mz, intensity, peak_off, prec_mz, prec_z, params):
     ``STRIP_REPORT_DTYPE`` record per spectrum (``hit``: bit w set iff a peak lay in active window w; ``n_removed``;
     ``n_windows``).  ValueError where ``pya_strip_spectra_host`` returns ``PYA_ERR_ARG``."""
     p = check_strip_params(params)
-    mz, intensity = np.asarray(mz), np.asarray(intensity)
-    for name, a in (("mz", mz), ("intensity", intensity)):
-        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
-            raise ValueError("strip: %s is a one-dimensional float64 or float32 array" % name)
-    peak_off = np.asarray(peak_off, np.int64)
-    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-        raise ValueError("strip: peak_off has n_spectra + 1 offsets that do not descend")
-    first, last = int(peak_off[0]), int(peak_off[-1])
-    if mz.size < last or intensity.size < last:
-        raise ValueError("strip: peak_off runs past the end of the spectrum arrays")
-    n_spec = peak_off.size - 1
+    raw_mz, raw_it, rel = _transform_entry("strip", mz, intensity, peak_off)
+    n_spec = rel.size - 1
     pm, pz = _strip_precursors(prec_mz, prec_z)
     if pm.shape != (n_spec,):
         raise ValueError("strip: prec_mz and prec_z have one entry per spectrum")
-    x = mz[first:last].astype(np.float64)
-    rel = peak_off - first
+    x = raw_mz.astype(np.float64)
     lo, hi, active = strip_windows(pm, pz, p)
     in_window = np.zeros(x.size, bool)
     report = np.zeros(n_spec, STRIP_REPORT_DTYPE)
@@ -1002,11 +990,9 @@ def strip(mz, intensity, peak_off, prec_mz, prec_z, params):
         in_window[a:b] = inside.any(axis=1)
         report["hit"][s] = sum(1 << int(w) for w in ws[inside.any(axis=0)])
     keep = ~((x < p["mz_lo"]) | (x > p["mz_hi"]) | in_window)
-    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
-    kept = before[rel[1:]] - before[rel[:-1]]
+    _, kept, new_off = _transform_exit(keep, rel)
     report["n_removed"] = np.diff(rel) - kept
-    new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
-    return mz[first:last][keep].copy(), intensity[first:last][keep].copy(), new_off, report
+    return raw_mz[keep].copy(), raw_it[keep].copy(), new_off, report
 
 
 def centroid_params(gap, gap_ppm=0.0, half_width=4, min_height=0.0, area=False):
@@ -1077,21 +1063,11 @@ def centroid(mz, intensity, peak_off, params, select=None):
     new arrays, their offsets (from 0) and a boolean per spectrum that is True where the spectrum was selected and not
     ascending (what ``d_over`` counts)."""
     p = check_centroid_params(params)
-    mz, intensity = np.asarray(mz), np.asarray(intensity)
-    for name, a in (("mz", mz), ("intensity", intensity)):
-        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 1:
-            raise ValueError("centroid: %s is a one-dimensional float64 or float32 array" % name)
-    peak_off = np.asarray(peak_off, np.int64)
-    if peak_off.ndim != 1 or peak_off.size < 1 or peak_off[0] < 0 or (np.diff(peak_off) < 0).any():
-        raise ValueError("centroid: peak_off has n_spectra + 1 offsets that do not descend")
-    first, last = int(peak_off[0]), int(peak_off[-1])
-    if mz.size < last or intensity.size < last:
-        raise ValueError("centroid: peak_off runs past the end of the spectrum arrays")
-    n_spec, n = peak_off.size - 1, last - first
+    raw_mz, raw_it, rel = _transform_entry("centroid", mz, intensity, peak_off)
+    n_spec, n = rel.size - 1, raw_mz.size
     sel = centroid_select(select, n_spec)
     chosen = np.ones(n_spec, bool) if sel is None else sel != 0
-    x, y = mz[first:last].astype(np.float64), intensity[first:last].astype(np.float64)
-    rel = peak_off - first
+    x, y = raw_mz.astype(np.float64), raw_it.astype(np.float64)
     spec = np.repeat(np.arange(n_spec), np.diff(rel))
     hw = p["half_width"]
     with np.errstate(all="ignore"):
@@ -1131,14 +1107,12 @@ def centroid(mz, intensity, peak_off, params, select=None):
         c = x[idx] + q
         c = np.where(c >= x[l], c, x[l])
         c = np.where(c <= x[r], c, x[r])
-    out_mz, out_it = mz[first:last][keep].copy(), intensity[first:last][keep].copy()
-    before = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+    out_mz, out_it = raw_mz[keep].copy(), raw_it[keep].copy()
+    before, _, new_off = _transform_exit(keep, rel)
     pos = before[idx]
     wide = l != r
-    out_mz[pos[wide]] = c[wide].astype(mz.dtype)
+    out_mz[pos[wide]] = c[wide].astype(raw_mz.dtype)
     if p["area"]:
         with np.errstate(over="ignore"):
-            out_it[pos] = sw.astype(intensity.dtype)
-    kept = before[rel[1:]] - before[rel[:-1]]
-    new_off = np.concatenate([[0], np.cumsum(kept)]).astype(np.int64)
+            out_it[pos] = sw.astype(raw_it.dtype)
     return out_mz, out_it, new_off, unordered
