@@ -114,6 +114,10 @@ extern "C" {
                                    /* calibration lent by pya_set_recalibration, in the library's own device copy, before the    */
                                    /* first kernel reads it; refused by pya_score_one, by pya_plan_create* (a plan's user calls  */
                                    /* pya_recalibrate_spectra on their own arrays) and together with PYA_FLAG_KEEP               */
+#define PYA_FLAG_COVERAGE 8192u /* pya_score_batch* / pya_score_batch_named: the coverage record of every PSM as well           */
+                                /* (pya_last_batch_coverage), taken on the spectra that were scored -- with                    */
+                                /* PYA_FLAG_RECALIBRATE the corrected copy; it needs no other stage; pya_plan_create*: as      */
+                                /* PYA_FLAG_EVIDENCE (pya_plan_coverage)                                                       */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -469,6 +473,48 @@ typedef struct pya_mz_calibration {   /* 128 bytes per run slot; the empty recor
     float    spread_ppm[PYA_MZP_BANDS]; /* half of (q84 - q16) of the band's excess, in ppm; 0 where the band was not fitted */
     uint32_t n_signal[PYA_MZP_BANDS];   /* floor(E / 4): ions above the flat floor; fitted <=> n_signal >= min_ions */
 } pya_mz_calibration;
+
+/* Explained ion current: how much of the spectrum the reported localisation explains.  The PSM quality column of the field
+ * (MS-GF+: ExplainedIonCurrentRatio, NTermIonCurrentRatio, CTermIonCurrentRatio, MS2IonCurrent; MaxQuant: intensity coverage,
+ * peak coverage), and the number that shows on a caller's own spectra whether a transform in front of the run helped.  One
+ * record per PSM, written BEHIND a run; no kernel of a run reads it.  The reference has no counterpart.
+ * THE FRAGMENTS of a scored PSM are exactly its section-1 ion records (pya_ion, site 255): every theoretical fragment of
+ * best_sig -- all ion types of the scorer, charges 1 .. max_charge, loss variants -- that has a retained peak in its window,
+ * matched by the rule of the ion stage.  n_fragments is their number, so it equals the winner's cumulative count at depth
+ * n_top - 1 in pep_scores.
+ * EXPLAINED.  Raw peak i of the PSM's spectrum is explained iff (float)mz[i] equals, bit for bit as a float32 value (a float32
+ * m/z is taken as it is), the peak_mz of at least one fragment; N-terminal-explained if such a fragment has a forward ion type
+ * (b, c: the first types of the configuration), C-terminal-explained if such a fragment has a backward type (y, z, Z).  A peak
+ * can be both.  A NaN m/z is never explained.  TWO RAW PEAKS WITH THE SAME float32 m/z ARE BOTH EXPLAINED when one is: the
+ * price of a definition that does not depend on the order of the raw peaks -- spectra out of m/z order are scored (the exact
+ * binning route) and are covered here.
+ * THE FOUR SUMS are in double, in this order and no other, over the spectrum's peaks by local index: lane l = 0 .. 63
+ * accumulates p[l] = ((0.0 + x[l]) + x[l + 64]) + ..., then s = (((0.0 + p[0]) + p[1]) + ...) + p[63].  In a restricted sum a
+ * peak outside the set contributes + 0.0: added, not skipped.  float32 intensities widen exactly; NaN and infinities propagate
+ * by IEEE.  No multiply-add exists to contract, so a host restatement gives EQUAL bytes (pyascore_amd.rollup.coverage).
+ * SIZES.  A forward fragment of size s covers bond s, a backward one of size s bond L - s (L the peptide's length, bonds
+ * 1 .. L - 1).  nterm_sizes / cterm_sizes count the distinct s with a fragment of that direction, over any type, charge and
+ * loss variant; *_run is the longest run of consecutive s in that set; bonds the size of the union of the covered bonds.
+ * PYA_COV_NONE: the PSM was not scored (status != 0 or n_sig <= 0) or was set aside; every other byte of the record is 0.
+ * The record is a function of the PSM, its spectrum and the scorer: not of the route, shared or typed input or chunk cuts.
+ * csrc/coverage.hip. */
+#define PYA_COV_NONE 0
+#define PYA_COV_SCORED 1
+typedef struct pya_coverage {      /* 64 bytes, four 16-byte stores; records compare as raw bytes */
+    double total_current;          /* sum of the intensities of every raw peak of the PSM's spectrum            */
+    double explained_current;      /* ... of the explained peaks                                                */
+    double nterm_current;          /* ... of the peaks explained by a forward ion type                          */
+    double cterm_current;          /* ... of the peaks explained by a backward ion type                         */
+    uint32_t n_peaks;              /* raw peaks of the spectrum                                                 */
+    uint32_t n_retained;           /* peaks the binning kept (the retained table)                               */
+    uint32_t n_explained;          /* raw peaks that are explained                                              */
+    uint32_t n_fragments;          /* section-1 ion records of the PSM                                          */
+    uint16_t nterm_sizes, cterm_sizes;   /* distinct fragment sizes with a forward / backward fragment          */
+    uint16_t nterm_run, cterm_run;       /* longest run of consecutive sizes among them                         */
+    uint16_t bonds;                /* bonds 1 .. L - 1 covered from either side                                 */
+    uint8_t kind;                  /* PYA_COV_NONE / PYA_COV_SCORED                                             */
+    uint8_t pad[5];                /* 0                                                                         */
+} pya_coverage;
 
 /* Deisotoping: the one step in front of a run that REMOVES peaks.  High-resolution MS2 spectra carry isotope envelopes; every
  * M+1 / M+2 satellite that makes the cut of the ten most intense peaks per 100 m/z takes a slot from a real fragment and offers
@@ -919,6 +965,10 @@ int pya_set_mz_profile(pya_handle *h, const int32_t *run, uint64_t n_psm, uint64
 /* The table of the last batch call on this handle that was given PYA_FLAG_MZ_PROFILE: out[n_slots], n_slots as lent (anything
  * else: PYA_ERR_ARG).  PYA_ERR_STATE when the last batch was scored without the flag. */
 int pya_last_batch_mz_profile(pya_handle *h, pya_mz_profile *out, uint64_t n_slots);
+/* The coverage records (pya_coverage above) of the last batch call on this handle that was given PYA_FLAG_COVERAGE: out[n_psm],
+ * n_psm as in that call (anything else: PYA_ERR_ARG).  PYA_ERR_STATE when the last batch was scored without the flag.  The
+ * record of a PSM that was set aside (PYA_FLAG_SKIP_INVALID) is all zero; records do not depend on the cut into chunks. */
+int pya_last_batch_coverage(pya_handle *h, pya_coverage *out, uint64_t n_psm);
 /* Fits d_table[n_slots] (device memory, pya_mz_profile) into d_cal[n_slots] (device memory; every byte of every record is
  * written): one launch of csrc/mz_calibrate.hip on hip_stream, one wavefront per slot, stream-ordered, no host wait and no
  * allocation.  Of params only inv_ppm is used.  PYA_ERR_ARG, with nothing launched: NULL where an array is needed with
@@ -1212,6 +1262,17 @@ int pya_plan_peptidoforms(pya_plan *plan, const pya_results *d_res, void *hip_st
  * PYA_FLAG_MZ_PROFILE (or another stage flag): the one-launch kernel leaves no retained tables. */
 int pya_plan_mz_profile(pya_plan *plan, const pya_results *d_res, void *hip_stream, const int32_t *d_run, uint64_t n_slots,
                         const pya_mz_profile_params *params, pya_mz_profile *d_table);
+/* Writes the coverage record (pya_coverage above) of every PSM of this plan to d_out[n_psm] (device memory; every byte of it
+ * is written).  d_spectra: the device arrays the last run scored (pya_plan_run_typed's; the float64 pair of pya_plan_run as
+ * PYA_F64 / PYA_F64) -- the stage reads the raw peaks again, beside best_sig and n_sig of d_res, the run's status and its
+ * retained tables.  One or two launches of csrc/coverage.hip (the PSMs inside the fast limits, the general ones),
+ * stream-ordered, no host synchronisation and no allocation of the caller's inside, waits for the run (its side stream
+ * included) as pya_plan_evidence does, valid until the plan is run again, may be called again.  PYA_ERR_ARG, with nothing
+ * launched: NULL where an array is needed, a type pair the run refuses; PYA_ERR_STATE before the plan's first run;
+ * PYA_ERR_LIMIT under the LDS condition of pya_plan_evidence.  A plan of a handful of PSMs is created with PYA_FLAG_COVERAGE
+ * (or another stage flag): the one-launch kernel leaves no retained tables. */
+int pya_plan_coverage(pya_plan *plan, const pya_results *d_res, const pya_typed_spectra *d_spectra, void *hip_stream,
+                      pya_coverage *d_out);
 /* ms per kernel family of the last pya_plan_run (PYA_FLAG_TIMING): bin_spectra, score_signatures,
  * score_localize (the fused kernel, with the localize launch for what it hands over), localize;
  * synchronises.  A batch that has fused PSMs and others runs the fused family on a stream of its own beside

@@ -4,7 +4,8 @@ MI355X scorer: the files are read by :mod:`pyascore_amd.ingest`, every selected 
 batched call (:func:`pyascore_amd.batch_cli.localize`) and the TSV of docs/source/cli.rst:135-180 is
 written.  ``--parameter_file`` takes ``name = value`` lines ('#' starts a comment); options on the
 command line override it.  ``--device`` (HIP ordinal), ``--evidence`` (three more columns: what stands behind every
-Ascore), ``--ions FILE`` (a second table: which ions, one line each) and ``--reported`` (three more columns: the search
+Ascore), ``--ions FILE`` (a second table: which ions, one line each), ``--coverage FILE`` (a table with a line per PSM: the ion
+current of its spectrum and the part the reported localisation explains) and ``--reported`` (three more columns: the search
 engine's own site assignment, scored against the winner) and ``--sites FILE`` (a table with a line per candidate residue, and
 the runner-up localisation in the main one) and ``--probs`` (two more columns: the localisation probability of every
 candidate residue and the posterior of the reported localisation) and ``--ranked FILE`` with ``--ranked_depth K`` (a table
@@ -68,6 +69,11 @@ def build_parser():
     p.add_argument("--ions", type=str, default="", metavar="FILE",
                    help="write the ion table to FILE: one line per matched fragment of the reported localisation and per "
                         "site-determining ion of every site (Scan, Hit, Section, Site, Side, Ion, TheoMz, PeakMz, Rank, Counted)")
+    p.add_argument("--coverage", type=str, default="", metavar="FILE",
+                   help="write the coverage table to FILE: one line per PSM with the ion current of its spectrum, the part the matched "
+                        "fragments of the reported localisation explain (in all, N-terminal, C-terminal), peak, fragment and bond "
+                        "counts, and the four ratios (Scan, Hit, Scored, TotalCurrent, ExplainedCurrent, ..., ExplainedRatio, "
+                        "NTermRatio, CTermRatio, PeakRatio)")
     p.add_argument("--reported", action="store_true",
                    help="append ReportedSequence, ReportedPepScore and ReportedAscore: the site assignment the identification "
                         "file reports, its PepScore, and the ambiguity of the winner against it (0: Ascore kept the site)")
@@ -277,6 +283,7 @@ def run(args, log=print):
         for group, mass in zip(args.neutral_loss_groups.split(","), args.neutral_loss_masses.split(",")):
             ascore.add_neutral_loss(group, float(mass))
     ion_rows = [] if args.ions else None
+    coverage_rows = [] if args.coverage else None
     site_rows = [] if args.sites else None
     ranked_rows = [] if args.ranked else None
     site_table_rows = [] if args.site_table else None
@@ -302,7 +309,7 @@ def run(args, log=print):
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
                               peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
                               deisotope=deisotope, decharge=decharge, strip=strip_request(args),
-                              centroid=centroid_request(args))
+                              centroid=centroid_request(args), coverage=coverage_rows)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -322,6 +329,8 @@ def run(args, log=print):
         batch_cli.write_mz_calibration_tsv(cal, 1.0 / profile[1]["inv_band"], args.mz_calibration_out)
     if ion_rows is not None:
         batch_cli.write_ions_tsv(ion_rows, args.ions)
+    if coverage_rows is not None:
+        batch_cli.write_coverage_tsv(coverage_rows, args.coverage)
     log("{} -- Ascore Completed".format(stamp()))
     return rows
 

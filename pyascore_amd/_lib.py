@@ -20,6 +20,8 @@ PYA_FLAG_ROLLUP = 512
 PYA_FLAG_PEPTIDOFORMS = 1024
 PYA_FLAG_MZ_PROFILE = 2048
 PYA_FLAG_RECALIBRATE = 4096
+PYA_FLAG_COVERAGE = 8192
+PYA_COV_NONE, PYA_COV_SCORED = 0, 1
 PYA_MZC_MAX_PPM = 1000       # the largest knot of a pya_mz_calibration, in ppm
 PYA_MZP_BANDS, PYA_MZP_BINS = 8, 64
 PYA_MZP_CHUNK = 128          # PSMs per workgroup of csrc/mz_profile.hip
@@ -184,6 +186,22 @@ MZ_PROFILE_DTYPE = [("n_psm", "<u4"), ("n_ions", "<u4"), ("n_rank_skipped", "<u4
                     ("reserved", "<u4"), ("da", "<u4", (PYA_MZP_BANDS, PYA_MZP_BINS)), ("ppm", "<u4", (PYA_MZP_BANDS, PYA_MZP_BINS))]
 MZ_CALIBRATION_DTYPE = [("ppm", "<f8", (PYA_MZP_BANDS,)), ("spread_ppm", "<f4", (PYA_MZP_BANDS,)), ("n_signal", "<u4", (PYA_MZP_BANDS,))]
 
+
+class Coverage(C.Structure):
+    """pya_coverage: how much of its spectrum the reported localisation of one PSM explains"""
+    _fields_ = [("total_current", C.c_double), ("explained_current", C.c_double), ("nterm_current", C.c_double),
+                ("cterm_current", C.c_double), ("n_peaks", C.c_uint32), ("n_retained", C.c_uint32), ("n_explained", C.c_uint32),
+                ("n_fragments", C.c_uint32), ("nterm_sizes", C.c_uint16), ("cterm_sizes", C.c_uint16), ("nterm_run", C.c_uint16),
+                ("cterm_run", C.c_uint16), ("bonds", C.c_uint16), ("kind", C.c_uint8), ("pad", C.c_uint8 * 5)]
+
+
+assert C.sizeof(Coverage) == 64 and Coverage.n_peaks.offset == 32 and Coverage.nterm_sizes.offset == 48 and Coverage.bonds.offset == 56 and \
+    Coverage.kind.offset == 58 and Coverage.pad.offset == 59, "pya_coverage is a 64-byte record"
+COVERAGE_DTYPE = [("total_current", "<f8"), ("explained_current", "<f8"), ("nterm_current", "<f8"), ("cterm_current", "<f8"),
+                  ("n_peaks", "<u4"), ("n_retained", "<u4"), ("n_explained", "<u4"), ("n_fragments", "<u4"),
+                  ("nterm_sizes", "<u2"), ("cterm_sizes", "<u2"), ("nterm_run", "<u2"), ("cterm_run", "<u2"), ("bonds", "<u2"),
+                  ("kind", "u1"), ("pad", "u1", (5,))]
+
 PYA_F64, PYA_F32 = 0, 1
 
 PYA_DEISO_MAX_CHARGE = 8
@@ -309,6 +327,8 @@ SYMBOLS = {
     "pya_set_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
     "pya_last_batch_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_plan_mz_profile": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, C.c_uint64, _vp, _vp]),
+    "pya_last_batch_coverage": (C.c_int, [_vp, _vp, C.c_uint64]),
+    "pya_plan_coverage": (C.c_int, [_vp, C.POINTER(Results), C.POINTER(TypedSpectra), _vp, _vp]),
     "pya_mz_profile_fit": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp]),
     "pya_mz_profile_fit_host": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp]),
     "pya_recalibrate_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.c_uint64, C.c_double, _vp, _vp, _vp]),

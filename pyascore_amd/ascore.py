@@ -116,6 +116,7 @@ except ImportError:                   # not built for this interpreter
     _fast = None
 
 EVIDENCE_DTYPE = np.dtype(_lib.EVIDENCE_DTYPE)      # pya_evidence, 16 bytes
+COVERAGE_DTYPE = np.dtype(_lib.COVERAGE_DTYPE)      # pya_coverage, 64 bytes
 SITE_DTYPE = np.dtype(_lib.SITE_DTYPE)              # pya_site, 32 bytes
 SITE_PROB_DTYPE = np.dtype(_lib.SITE_PROB_DTYPE)    # pya_site_prob, 16 bytes
 PSM_PROB_DTYPE = np.dtype(_lib.PSM_PROB_DTYPE)      # pya_psm_prob, 16 bytes
@@ -567,7 +568,7 @@ class PyAscore:
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
-                    recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None):
+                    recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=False):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -706,6 +707,12 @@ class PyAscore:
         whose spectra are resident chains the device forms (``pyascore_amd.device.centroid`` first).  ``keep=True`` retains the
         transformed batch.  The caller's arrays are not written.
 
+        ``coverage=True`` adds ``coverage`` (``COVERAGE_DTYPE``, the 64-byte ``pya_coverage``, shape ``[n]``): per PSM the ion
+        current of its spectrum and the part of it that the matched fragments of the reported localisation explain, in all and
+        from either terminus, beside peak, fragment and bond counts (``pyascore_amd.rollup.coverage_ratios`` makes the ratios,
+        ``pyascore_amd.rollup.coverage`` is the host restatement).  It is taken on the spectra that were scored: with a
+        transform or ``recalibrate=`` on the transformed arrays.  It goes with every other option.
+
         Typed spectra: ``batch["mz"]`` / ``batch["intensity"]`` of dtype float32 go to the device as they are (float64
         m/z with float32 intensities, as mzML holds them, or both float32: 12 or 8 bytes per peak over PCIe instead of 16;
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
@@ -716,7 +723,7 @@ class PyAscore:
             rest = dict(keep=keep, skip_invalid=skip_invalid, evidence=evidence, ions=ions, named=named, sites=sites,
                         site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup, peptidoforms=peptidoforms,
                         mz_profile=mz_profile, recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip,
-                        centroid=centroid)
+                        centroid=centroid, coverage=coverage)
             rest[done] = None
             return self.score_batch(dict(batch, mz=spectra[0], intensity=spectra[1], peak_off=spectra[2]), **rest)
 
@@ -752,7 +759,7 @@ class PyAscore:
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                         named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup,
-                                        peptidoforms=peptidoforms, mz_profile=mz_profile)
+                                        peptidoforms=peptidoforms, mz_profile=mz_profile, coverage=coverage)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -789,7 +796,8 @@ class PyAscore:
                     res = self.score_batch(take_psms(batch, perm), skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
                                            site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved,
-                                           peptidoforms=pform_moved, mz_profile=mzp_moved, recalibrate=recal_moved)
+                                           peptidoforms=pform_moved, mz_profile=mzp_moved, recalibrate=recal_moved,
+                                           coverage=coverage)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
@@ -890,6 +898,8 @@ class PyAscore:
             if mzp is not None:
                 out["mz_profile"] = np.zeros(mzp["n_slots"], np.dtype(_lib.MZ_PROFILE_DTYPE))
                 out["mz_profile_params"] = dict(mzp["params"])
+            if coverage:
+                out["coverage"] = np.zeros(0, COVERAGE_DTYPE)
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -915,7 +925,8 @@ class PyAscore:
             (_lib.PYA_FLAG_EVIDENCE if evidence else 0) | (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0) | \
             (_lib.PYA_FLAG_ROLLUP if roll is not None else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if pform is not None else 0) | \
-            (_lib.PYA_FLAG_MZ_PROFILE if mzp is not None else 0) | (_lib.PYA_FLAG_RECALIBRATE if recal is not None else 0)
+            (_lib.PYA_FLAG_MZ_PROFILE if mzp is not None else 0) | (_lib.PYA_FLAG_RECALIBRATE if recal is not None else 0) | \
+            (_lib.PYA_FLAG_COVERAGE if coverage else 0)
         # for this call; the handle's own settings come back
         cap_before = k_before = None
         if (sites or probs or ranked_k or roll is not None or pform is not None) and site_sig_cap is not None:
@@ -995,6 +1006,11 @@ class PyAscore:
             if rc:
                 self._raise(rc)
             out["mz_profile_params"] = dict(mzp["params"])
+        if coverage:
+            out["coverage"] = np.zeros(n, COVERAGE_DTYPE)
+            rc = self._lib.pya_last_batch_coverage(self._h, _as_ptr(out["coverage"]), n)
+            if rc:
+                self._raise(rc)
         return out
 
     def peptidoform_reduce(self, a, b=None):
@@ -1411,6 +1427,16 @@ class PyAscore:
         return last["ions"].copy()
 
     @property
+    def coverage(self):
+        """How much of its spectrum the last ``score()`` PSM explains: its ``COVERAGE_DTYPE`` record (see
+        ``score_batch(coverage=True)``).  Produced when read, like ``evidence``."""
+        last = self._last
+        if last is None:
+            return np.zeros(1, COVERAGE_DTYPE)[0]
+        self._batch_of_one_records()
+        return last["coverage"].copy()
+
+    @property
     def sites(self):
         """The site table of the last ``score()`` PSM: one ``SITE_DTYPE`` record per modifiable residue (see
         ``score_batch(sites=True)``; no cap on the site assignments).  Produced the first time it is read, by sending that
@@ -1502,7 +1528,7 @@ class PyAscore:
         return dict(named=res["named"], counts=res["named_counts"], scores=res["named_scores"])
 
     def _batch_of_one_records(self):
-        """evidence and ions of score()'s PSM: the arrays it was given, through the batch path as a batch of one"""
+        """evidence, ions and coverage of score()'s PSM: the arrays it was given, through the batch path as a batch of one"""
         last = self._last
         if "evidence" not in last:
             mz, it = _check_f64("mz_arr", last["mz"]), _check_f64("int_arr", last["it"])
@@ -1516,16 +1542,19 @@ class PyAscore:
                            _as_ptr(ap), _as_ptr(am), _as_ptr(off["aux"]))
             r = _lib.Results(k, *[_as_ptr(a) for a in res])
             # (no PYA_FLAG_KEEP: the plan path leaves the staging and the retained records of score()'s PSM alone)
-            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), _lib.PYA_FLAG_EVIDENCE | _lib.PYA_FLAG_IONS,
+            rc = self._lib.pya_score_batch(self._h, C.byref(b), _as_ptr(mz), _as_ptr(it), _lib.PYA_FLAG_EVIDENCE | _lib.PYA_FLAG_IONS | _lib.PYA_FLAG_COVERAGE,
                                            C.byref(r))
-            ev = np.zeros((1, k), EVIDENCE_DTYPE)
+            ev, cov = np.zeros((1, k), EVIDENCE_DTYPE), np.zeros(1, COVERAGE_DTYPE)
             if not rc:
                 rc = self._lib.pya_last_batch_evidence(self._h, _as_ptr(ev), 1, k)
+            if not rc:
+                rc = self._lib.pya_last_batch_coverage(self._h, _as_ptr(cov), 1)
             if rc:
                 self._raise(rc)
             if int(res[1][0]) != int(last["best_sig"]):
                 raise RuntimeError("the arrays passed to score() changed before evidence was read")
             last["ions"] = self._last_batch_ions(1)[1]
+            last["coverage"] = cov[0]
             last["evidence"] = ev[0]
 
     @property

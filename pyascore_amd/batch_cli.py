@@ -49,6 +49,10 @@ MZ_PROFILE_COLUMNS = ("Slot", "Band", "Unit", "Bin", "Low", "High", "Count")
 # ``--mz_calibration_out FILE``: one line per slot and band of the m/z calibration fitted to the profile (pya_mz_calibration)
 MZ_CALIBRATION_COLUMNS = ("Slot", "Band", "BandCentre", "Ppm", "SpreadPpm", "SignalIons", "BandWidth")
 ION_COLUMNS = ("Scan", "Hit", "Section", "Site", "Side", "Ion", "TheoMz", "PeakMz", "Rank", "Counted")
+# ``--coverage FILE``: one line per PSM, the coverage record (pya_coverage) and its four ratios
+COVERAGE_COLUMNS = ("Scan", "Hit", "Scored", "TotalCurrent", "ExplainedCurrent", "NTermCurrent", "CTermCurrent", "Peaks", "RetainedPeaks",
+                    "ExplainedPeaks", "Fragments", "NTermSizes", "CTermSizes", "NTermRun", "CTermRun", "Bonds", "ExplainedRatio",
+                    "NTermRatio", "CTermRatio", "PeakRatio")
 
 
 def process_mods(residues, mod_mass, sequence, positions, masses, mod_correction_tol=1.0,
@@ -193,7 +197,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              mod_correction_tol=1.0, zero_based=False, match_save=False, log=None, evidence=False, ions=None, reported=False,
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
-             recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None):
+             recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -223,6 +227,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``mz_profile``: a list that receives the fragment mass-error profile of ALL scored PSMs as slot 0: the one-record table
     (``pyascore_amd.rollup.MZ_PROFILE_DTYPE``) and the parameters it was binned with (``mz_profile_rows``,
     ``write_mz_profile_tsv``, ``mz_profile_report``); the main table does not change.
+    ``coverage``: a list that receives one ``[scan, hit] + coverage_fields`` row per picked PSM (``write_coverage_tsv``): the
+    coverage record of the PSM on the spectra that were scored, and its four ratios; the main table does not change.
     ``recalibrate``: ``dict(calibration=, band_width=)`` as ``PyAscore.score_batch(recalibrate=...)`` takes it: the m/z of every
     spectrum is corrected with slot 0 of the calibration on the device before it is scored (``read_mz_calibration`` gives both
     from the file ``write_mz_calibration_tsv`` wrote); every table is then that of the corrected spectra.
@@ -273,6 +279,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         stages["peptidoforms"] = dict(group=group, threshold=float(peptidoform_threshold))
     if mz_profile is not None:
         stages["mz_profile"] = dict(n_slots=1)
+    if coverage is not None:
+        stages["coverage"] = True
     if recalibrate is not None:
         stages["recalibrate"] = dict(recalibrate)
     if deisotope is not None:
@@ -336,10 +344,14 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     if peptidoform_table is not None:
         peptidoform_table.extend(peptidoform_table_fields(row, scans)
                                  for row in site_rollup.peptidoform_table(res["peptidoforms"], form_keys, residues=residues))
+    if coverage is not None:
+        cov_ratios = site_rollup.coverage_ratios(res["coverage"])
     rows = []
     hit = 0
     for i, psm in enumerate(picked):
         hit = hit + 1 if i and scans[i] == scans[i - 1] else 1
+        if coverage is not None:
+            coverage.append([scans[i], hit] + coverage_fields(res["coverage"][i], {k: v[i] for k, v in cov_ratios.items()}))
         if ranked is not None:
             ranked.extend([scans[i], hit] + ranked_fields(rk[i, r], rk[i, 0], rk_seqs[i * rk.shape[1] + r])
                           for r in range(int(ranked_lists.lengths(rk[i])[0])))
@@ -553,6 +565,22 @@ def ion_fields(rec):
     return ["winner" if winner_section else "site", "" if winner_section else str(int(rec["site"]) + 1),
             "competitor" if flags & 2 else "winner", ion, str(rec["theo_mz"]), str(rec["peak_mz"]) if matched else "",
             str(int(rec["rank"]) + 1) if matched else "", "1" if flags & 4 else "0"]
+
+
+def coverage_fields(rec, ratios):
+    """One coverage record and its ratios (``pyascore_amd.rollup.coverage_ratios``, one entry each) as the fields behind Scan and
+    Hit of the ``--coverage`` table; a PSM that was not scored has Scored 0 and zeros."""
+    return [str(int(rec["kind"]))] + [repr(float(rec[f])) for f in ("total_current", "explained_current", "nterm_current", "cterm_current")] + \
+        [str(int(rec[f])) for f in ("n_peaks", "n_retained", "n_explained", "n_fragments", "nterm_sizes", "cterm_sizes", "nterm_run",
+                                    "cterm_run", "bonds")] + [repr(float(ratios[k])) for k in ("explained", "nterm", "cterm", "peaks")]
+
+
+def write_coverage_tsv(coverage_rows, path):
+    """The ``--coverage`` table: the rows ``localize(..., coverage=[])`` collected, under ``COVERAGE_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(COVERAGE_COLUMNS) + "\n")
+        for row in coverage_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
 
 
 def write_ions_tsv(ion_rows, path):

@@ -66,6 +66,7 @@ void pya_destroy(pya_handle *h) {
     if (h->sites_host) (void)hipHostFree(h->sites_host);
     if (h->probs_host) (void)hipHostFree(h->probs_host);
     if (h->ranked_host) (void)hipHostFree(h->ranked_host);
+    if (h->cov_host) (void)hipHostFree(h->cov_host);
     for (hipEvent_t ev : h->pform_ev)
         if (ev) (void)hipEventDestroy(ev);
     if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);

@@ -712,6 +712,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_behind_run(h, p, &d_out, loan, flags, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_behind_run(h, p, &d_out, pf_loan, flags, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_behind_run(h, p, &d_out, mzp_loan, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_COVERAGE) && (rc = coverage_behind_run(h, p, &d_out, &d_sp, lo, h->run_stream))) return finish(rc);
         hipEvent_t done = nullptr;                                /* chunk c finished (kernels + copy) */
         e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventRecord(done, h->run_stream);
@@ -761,6 +762,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
     if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_end(h))) return finish(rc);
     if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_end(h, mzp_loan))) return finish(rc);
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
+    h->cov_valid = (flags & PYA_FLAG_COVERAGE) != 0;
     h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
     /* (chunks behind the last PSM with records: their offsets stay at the total) */
     h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
@@ -784,6 +786,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->rollup_valid = false;
     h->pform_valid = false;
     h->mzp_valid = false;
+    h->cov_valid = false;
     pya_handle::RollupLoan loan;
     if (flags & PYA_FLAG_ROLLUP) {
         const int rc_ru = rollup_begin(h, &loan);
@@ -812,6 +815,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         h->evid_n = 0;
         h->evid_k = out->max_k;
         h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
+        h->cov_n = 0;
+        h->cov_valid = (flags & PYA_FLAG_COVERAGE) != 0;
         h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
         h->sites_valid = (flags & PYA_FLAG_SITES) != 0;
         h->probs_valid = (flags & PYA_FLAG_PROBS) != 0;
@@ -859,6 +864,10 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_ev = evidence_host_block(h, b->n_psm, out->max_k);
         if (rc_ev) return rc_ev;
     }
+    if (flags & PYA_FLAG_COVERAGE) {
+        const int rc_cv = coverage_host_block(h, b->n_psm);
+        if (rc_cv) return rc_cv;
+    }
     if (flags & PYA_FLAG_SITES) {
         if (b->pep_off[b->n_psm] < b->pep_off[0]) return h->fail(PYA_ERR_ARG, -1, "pep_off is not monotone");
         const int rc_st = sites_host_block(h, b);
@@ -873,8 +882,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_rk = ranked_host_block(h, b);
         if (rc_rk) return rc_rk;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS, _MZ_PROFILE or _RECALIBRATE takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_RECALIBRATE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS, _MZ_PROFILE, _COVERAGE or _RECALIBRATE takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_RECALIBRATE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -1044,6 +1053,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         if ((rc = mzp_report(p, 0))) return rc;
         if ((rc = mzp_end(h, mzp_loan))) return rc;
     }
+    if (flags & PYA_FLAG_COVERAGE) {
+        if ((rc = coverage_behind_run(h, p, &d_out, &d_sp, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        h->cov_valid = true;
+    }
     lap("d2h");
     if (flags & PYA_FLAG_KEEP) {
         if (h->kept) pya_plan_destroy(h->kept);
@@ -1070,6 +1084,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->rollup_valid = false;
     h->pform_valid = false;
     h->mzp_valid = false;
+    h->cov_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);

@@ -147,6 +147,9 @@ int pya_launch_rollup(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec,
 size_t pya_mz_profile_lds_bytes(uint32_t l_cap);
 int pya_launch_mz_profile(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int32_t *d_run, uint64_t n_slots,
                           const pya_mz_profile_params *prm, void *d_table, uint32_t *d_over, uint32_t l_cap, hipStream_t stream);
+size_t pya_coverage_lds_bytes(uint32_t l_cap, uint32_t peak_cap);
+int pya_launch_coverage(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const uint32_t *d_spec_of, uint32_t types, void *d_out,
+                        uint32_t l_cap, uint32_t peak_cap, hipStream_t stream);
 int pya_launch_mz_fit(const void *d_table, uint64_t n_slots, double inv_ppm, uint32_t min_ions, void *d_cal, hipStream_t stream);
 int pya_launch_mz_apply(const void *d_mz, uint32_t mz_type, const int64_t *d_peak_off, uint64_t n_spectra, const int32_t *d_run,
                         const void *d_cal, uint64_t n_slots, double inv_band, void *d_out, uint32_t *d_over, hipStream_t stream);
@@ -443,6 +446,12 @@ struct pya_handle {
     DevBuf<pya_mz_profile> d_mzp;
     std::vector<pya_mz_profile> mzp_host;
     bool mzp_valid = false;
+    /* PYA_FLAG_COVERAGE: the records of the last batch call, pinned like the evidence rows so that a chunk's records come
+     * back asynchronously behind its results (pya_last_batch_coverage copies them out) */
+    pya_coverage *cov_host = nullptr;
+    size_t cov_cap = 0;                       /* records the block has room for */
+    uint64_t cov_n = 0;                       /* PSMs of the batch they belong to */
+    bool cov_valid = false;                   /* the last batch was scored with the flag */
     /* PYA_FLAG_RECALIBRATE: what pya_set_recalibration lent for the next batch call (the records are copied); the call's
      * device copy of the records and, per spectrum of the whole batch, the slot it is corrected with (-1: left alone) */
     struct RecalLoan {
@@ -823,6 +832,13 @@ struct pya_plan {
     hipEvent_t ev_mzp = nullptr;
     bool mzp_asked = false;
     DevBuf<int32_t> d_mzp_run;
+    /* pya_plan_coverage: the raw peak caps of its two launches (the largest spectrum of a PSM inside the fast limits, of a
+     * general PSM; once per plan), the event behind the last call's kernels (a later call, on whatever stream, writes
+     * behind them) and a pya_score_batch plan's records */
+    bool cov_caps = false, cov_asked = false;
+    uint32_t cov_peak_fast = 1, cov_peak_gen = 1;
+    hipEvent_t ev_cov = nullptr;
+    DevBuf<pya_coverage> d_cov;
     /* PYA_FLAG_RECALIBRATE: a pya_score_batch plan's slice of the spectra's slots and the report words of the apply kernel */
     DevBuf<int32_t> d_recal_slot;
     DevBuf<uint32_t> d_recal_over;
@@ -841,6 +857,7 @@ struct pya_plan {
         if (ev_sites) (void)hipEventDestroy(ev_sites);
         if (ev_rollup) (void)hipEventDestroy(ev_rollup);
         if (ev_mzp) (void)hipEventDestroy(ev_mzp);
+        if (ev_cov) (void)hipEventDestroy(ev_cov);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
@@ -961,6 +978,11 @@ int pform_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const vo
  * report of a plan's last pya_plan_mz_profile (psm_lo as for rollup_report) */
 int mzp_check(pya_handle *h, const char *who, uint64_t n_slots, const pya_mz_profile_params *prm);
 int mzp_report(pya_plan *p, uint64_t psm_lo);
+/* host_coverage.cpp: PYA_FLAG_COVERAGE of the batch calls -- the handle's pinned block for the records of a batch of n PSMs
+ * (zeroed: a PSM no plan reaches has a PYA_COV_NONE record), and the stage behind a plan's kernels on `st` with its records
+ * on their way into the block at PSM `lo` (asynchronous: whoever waits for the chunk's results waits for them too) */
+int coverage_host_block(pya_handle *h, uint64_t n);
+int coverage_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, const pya_typed_spectra *d_sp, uint64_t lo, hipStream_t st);
 /* host_deisotope.cpp: what is wrong with a set of deisotoping parameters (NULL: nothing); host_decharge.cpp asks it of the
  * rule inside its own */
 const char *deiso_params_fault(const pya_deisotope_params *p);

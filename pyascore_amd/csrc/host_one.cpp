@@ -195,6 +195,9 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
     h->rollup_valid = false;
     h->mzp_valid = false;
     h->pform_valid = false;
+    h->cov_valid = false;
+    if (flags & PYA_FLAG_COVERAGE)
+        return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_COVERAGE: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_EVIDENCE)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_EVIDENCE: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_IONS)

@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -934,6 +934,68 @@ int pya_plan_mz_profile(pya_plan *p, const pya_results *r, void *hip_stream, con
     if (e) return h->hip_fail((hipError_t)e, "mass-error profile launch");
     HIPCHK(h, hipEventRecord(p->ev_mzp, st));
     p->mzp_asked = true;
+    return PYA_OK;
+}
+
+namespace {
+/* the raw peak caps of pya_plan_coverage's two launches, for the Room of its stage_behind_run (which hands over l_cap and
+ * list_cap only; the larger of the two caps stands for both lists there, the launches take their own) */
+thread_local uint32_t cov_room_peaks = 1;
+}  // namespace
+
+/* The coverage stage (csrc/coverage.hip): the wait and the two lists of the evidence stage, each launch with the longest
+ * peptide and the largest spectrum of ITS list as caps -- the kernel keeps two bit planes over the retained table, and
+ * retained <= raw.  The raw arrays are the caller's: what the run scored. */
+int pya_plan_coverage(pya_plan *p, const pya_results *r, const pya_typed_spectra *sp, void *hip_stream, pya_coverage *d_out) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_coverage: the plan has not been run");
+    if (!d_out || !sp || !sp->mz || !sp->intensity || !r->best_sig || !r->n_sig)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_coverage");
+    uint32_t types = 0;
+    const int rc_types = spectra_types(h, sp, "pya_plan_coverage", &types);
+    if (rc_types) return rc_types;
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->ev_cov) HIPCHK(h, hipEventCreateWithFlags(&p->ev_cov, hipEventDisableTiming));
+    if (!p->cov_caps) {
+        uint32_t fast = 1, gen = 1;
+        for (uint64_t i = 0; i < p->n_psm; i++) {
+            if (!p->pre_status.empty() && p->pre_status[i]) continue;       /* (set aside: nothing of it is read) */
+            const int64_t np = p->n_peaks(i);
+            uint32_t &cap = (!p->gen.empty() && p->gen[i]) ? gen : fast;
+            cap = std::max(cap, (uint32_t)std::min<int64_t>(std::max<int64_t>(np, 1), 0xffffffffll));
+        }
+        p->cov_peak_fast = fast;
+        p->cov_peak_gen = gen;
+        p->cov_caps = true;
+    }
+    /* (the LDS condition of pya_plan_evidence, and this kernel's own room) */
+    struct Room {
+        static size_t both(uint32_t l_cap, uint32_t list_cap) {
+            return std::max(pya_evidence_lds_bytes(l_cap, list_cap), pya_coverage_lds_bytes(l_cap, cov_room_peaks));
+        }
+    };
+    cov_room_peaks = std::max(p->cov_peak_fast, p->gen_ids.empty() ? 1u : p->cov_peak_gen);
+    const int rc = stage_behind_run(p, st, "pya_plan_coverage", "evidence", Room::both);
+    if (rc) return rc;
+    /* (behind an earlier call's kernels, on whatever stream they were: they may write the same records) */
+    if (p->cov_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_cov, 0));
+    shared_tables(h, p->dev);
+    BatchDev d = p->dev;
+    d.best_sig = r->best_sig;
+    d.n_sig_out = r->n_sig;
+    d.mz = sp->mz;
+    d.inten = sp->intensity;
+    const uint32_t *d_spec_of = p->shared ? p->d_spec_of.p : nullptr;
+    int e = pya_launch_coverage(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, d_spec_of, types, d_out, p->evid_l_cap,
+                                p->cov_peak_fast, st);
+    if (!e && !p->gen_ids.empty())
+        e = pya_launch_coverage(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_spec_of, types, d_out, p->gen_l_cap, p->cov_peak_gen, st);
+    if (e) return h->hip_fail((hipError_t)e, "coverage launch");
+    HIPCHK(h, hipEventRecord(p->ev_cov, st));
+    p->cov_asked = true;
     return PYA_OK;
 }
 

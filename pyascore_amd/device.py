@@ -31,12 +31,13 @@ class DevicePlan:
     ``rollup=True``: the probability records rolled into a table of the caller's slots (``pya_plan_rollup``).
     ``peptidoforms()`` / ``peptidoforms=True``: the PSMs collapsed onto one record per (group, best_sig)
     (``pya_plan_peptidoforms``); ``peptidoform_reduce()`` merges such lists.  ``mz_profile()`` / ``mz_profile=True``: the
-    fragment mass errors of the reported localisations binned per run slot (``pya_plan_mz_profile``).
+    fragment mass errors of the reported localisations binned per run slot (``pya_plan_mz_profile``).  ``coverage()`` /
+    ``coverage=True``: per PSM the ion current of its spectrum and the part the reported localisation explains (``pya_plan_coverage``).
     ``fit_mz_calibration()`` turns such a table into an m/z calibration and ``recalibrate()`` corrects a device m/z tensor with
     it (``pya_mz_profile_fit``, ``pya_recalibrate_spectra``), so run -> profile -> fit -> correct -> run again needs no host copy."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
-                 ranked=False, rollup=False, peptidoforms=False, mz_profile=False):
+                 ranked=False, rollup=False, peptidoforms=False, mz_profile=False, coverage=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -68,7 +69,7 @@ class DevicePlan:
             (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0) | \
             (_lib.PYA_FLAG_ROLLUP if rollup else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if peptidoforms else 0) | \
-            (_lib.PYA_FLAG_MZ_PROFILE if mz_profile else 0)
+            (_lib.PYA_FLAG_MZ_PROFILE if mz_profile else 0) | (_lib.PYA_FLAG_COVERAGE if coverage else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -436,6 +437,27 @@ class DevicePlan:
             self.scorer._raise(rc)
         return table
 
+    def coverage(self, d_mz, d_intensity, out=None):
+        """The coverage records of the last ``run()`` as a ``torch.uint8`` device tensor ``[n_psm, 64]`` (one ``pya_coverage``
+        per PSM; ``coverage_records`` turns a host copy into the structured array).  ``d_mz`` / ``d_intensity``: the tensors
+        that run was given -- the stage reads the raw peaks again.  One or two launches on torch's current stream; nothing
+        waits on the host.  Returns ``out`` (every byte of it is written)."""
+        torch = self._torch
+        for t in (d_mz, d_intensity):
+            if t.dtype not in (torch.float64, torch.float32) or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("spectra must be the contiguous device tensors the plan was run with")
+        shape = (self.n_psm, COVERAGE_DTYPE.itemsize)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("out must be a contiguous uint8 device tensor of shape %r" % (shape,))
+        sp = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_plan_coverage(self._plan, C.byref(self._res), C.byref(sp), stream, out.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return out
+
     def fit_mz_calibration(self, table, params, min_ions=20, out=None):
         """The m/z calibration of a profile ``table`` (the ``torch.uint8`` device tensor ``[n_slots, 4128]`` of ``mz_profile()``)
         as a ``torch.uint8`` device tensor ``[n_slots, 128]``, one ``pya_mz_calibration`` per slot (``pya_mz_profile_fit``;
@@ -552,6 +574,7 @@ FLR_DTYPE = np.dtype(_lib.FLR_DTYPE)
 PEPTIDOFORM_DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)
 MZ_PROFILE_DTYPE = np.dtype(_lib.MZ_PROFILE_DTYPE)
 MZ_CALIBRATION_DTYPE = np.dtype(_lib.MZ_CALIBRATION_DTYPE)
+COVERAGE_DTYPE = np.dtype(_lib.COVERAGE_DTYPE)
 
 
 def _upload(a, dtype, device):
@@ -780,6 +803,15 @@ def rollup_records(raw):
     if a.ndim != 2 or a.shape[1] != ROLLUP_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n, %d)" % ROLLUP_DTYPE.itemsize)
     return a.view(ROLLUP_DTYPE).reshape(a.shape[0])
+
+
+def coverage_records(raw):
+    """A host copy of the records of ``DevicePlan.coverage()`` (``.cpu().numpy()``, uint8 ``[n, 64]``) as the structured
+    array ``PyAscore.score_batch(..., coverage=True)`` returns; a view, no copy."""
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != COVERAGE_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % COVERAGE_DTYPE.itemsize)
+    return a.view(COVERAGE_DTYPE).reshape(a.shape[0])
 
 
 def mz_profile_records(raw):

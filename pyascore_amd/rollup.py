@@ -44,6 +44,10 @@ windows of a precursor and ``strip`` restates the rule -- the peaks inside a win
 and of its charge-reduced forms, and the peaks outside an m/z range, removed -- the host form of ``PyAscore.strip_spectra`` /
 ``pyascore_amd.device.strip`` / ``score_batch(strip=...)``, with the same bytes; ``STRIP_REPORT_DTYPE`` is the 16-byte
 ``pya_strip_report`` and ``strip_hits`` reads its ``hit`` word.
+
+Explained ion current: ``score_batch(coverage=True)`` returns one ``COVERAGE_DTYPE`` record (the 64-byte ``pya_coverage``) per
+PSM; ``coverage`` restates the stage over section-1 ion records and the raw arrays with the sums in the definition's order
+(equal bytes, not close ones) and ``coverage_ratios`` turns records into the four ratios a report shows.
 """
 import numpy as np
 
@@ -61,6 +65,8 @@ MZ_PROFILE_DTYPE = np.dtype(_lib.MZ_PROFILE_DTYPE)  # pya_mz_profile, 4 128 byte
 assert MZ_PROFILE_DTYPE.itemsize == 4128
 MZ_CALIBRATION_DTYPE = np.dtype(_lib.MZ_CALIBRATION_DTYPE)  # pya_mz_calibration, 128 bytes
 assert MZ_CALIBRATION_DTYPE.itemsize == 128
+COVERAGE_DTYPE = np.dtype(_lib.COVERAGE_DTYPE)      # pya_coverage, 64 bytes
+assert COVERAGE_DTYPE.itemsize == 64
 MZC_MAX_PPM = _lib.PYA_MZC_MAX_PPM
 MZP_BANDS, MZP_BINS = _lib.PYA_MZP_BANDS, _lib.PYA_MZP_BINS
 DEISO_MAX_CHARGE = _lib.PYA_DEISO_MAX_CHARGE
@@ -422,6 +428,94 @@ def mz_profile(ion_off, ions, n_sig, run, n_slots, params):
         np.add.at(table["out_" + unit], (slot[q < 0], 0), 1)
         np.add.at(table["out_" + unit], (slot[q >= MZP_BINS], 1), 1)
     return table
+
+
+def _lane_sum(values):
+    """The sum of ``pya_coverage``: 64 partials, element k into partial k mod 64 from 0.0 in index order, the partials then
+    added in order from 0.0 -- plain Python floats (IEEE double), two explicit loops."""
+    part = [0.0] * 64
+    for k, v in enumerate(values):
+        part[k & 63] = part[k & 63] + v
+    s = 0.0
+    for lane in range(64):
+        s = s + part[lane]
+    return s
+
+
+def _longest_run(sizes):
+    best = run = 0
+    prev = None
+    for s in sorted(sizes):
+        run = run + 1 if prev is not None and s == prev + 1 else 1
+        best = max(best, run)
+        prev = s
+    return best
+
+
+def coverage(ion_off, ions, mz, intensity, peak_off, pep_len, forward_types, scored, spec_of=None, n_retained=None):
+    """The records ``score_batch(coverage=True)`` returns, from the ion records of the same batch (``score_batch(ions=True)``:
+    ``ion_off``, ``ions``; only section 1, ``site`` 255, is read) and the raw arrays that were scored: the definition of
+    ``pya_coverage`` restated, the four sums in its order with explicit loops.  ``pep_len``: the peptide length of every PSM;
+    ``forward_types``: the forward ion types of the scorer, e.g. ``"b"`` or ``"bc"``; ``scored``: one boolean per PSM (status 0
+    and ``n_sig > 0``), the others get the all-zero record; ``spec_of``: the spectrum of every PSM of a shared batch;
+    ``n_retained``: the peaks the binning kept per PSM, which neither the ion records nor the raw arrays tell (None: the field
+    stays 0)."""
+    ion_off = np.asarray(ion_off, np.int64)
+    ions = np.asarray(ions, np.dtype(_lib.ION_DTYPE))
+    peak_off = np.asarray(peak_off, np.int64)
+    scored = np.asarray(scored, bool)
+    n = scored.size
+    pep_len = np.asarray(pep_len, np.int64)
+    if ion_off.size != n + 1 or pep_len.shape != (n,):
+        raise ValueError("coverage: ion_off has n_psm + 1 entries, pep_len and scored one per PSM")
+    mz, intensity = np.asarray(mz), np.asarray(intensity)
+    fwd_codes = [ord(c) for c in forward_types]
+    out = np.zeros(n, COVERAGE_DTYPE)
+    for i in range(n):
+        if not scored[i]:
+            continue
+        s = i if spec_of is None else int(spec_of[i])
+        a, b = int(peak_off[s]), int(peak_off[s + 1])
+        x = mz[a:b].astype(np.float32)                      # (a float32 m/z is taken as it is)
+        y = intensity[a:b].astype(np.float64).tolist()      # (float32 widens exactly)
+        rec = ions[ion_off[i]:ion_off[i + 1]]
+        rec = rec[rec["site"] == _lib.PYA_ION_WINNER]
+        is_fwd = np.isin(rec["type"], fwd_codes)
+        in_fwd = np.isin(x, rec["peak_mz"][is_fwd]).tolist()        # (float32 equality: a NaN equals nothing)
+        in_bwd = np.isin(x, rec["peak_mz"][~is_fwd]).tolist()
+        r = out[i]
+        r["total_current"] = _lane_sum(y)
+        r["explained_current"] = _lane_sum([v if f or k else 0.0 for v, f, k in zip(y, in_fwd, in_bwd)])
+        r["nterm_current"] = _lane_sum([v if f else 0.0 for v, f in zip(y, in_fwd)])
+        r["cterm_current"] = _lane_sum([v if k else 0.0 for v, k in zip(y, in_bwd)])
+        r["n_peaks"] = b - a
+        r["n_retained"] = 0 if n_retained is None else int(n_retained[i])
+        r["n_explained"] = sum(1 for f, k in zip(in_fwd, in_bwd) if f or k)
+        r["n_fragments"] = rec.size
+        L = int(pep_len[i])
+        f_sizes = set(rec["size"][is_fwd].tolist())
+        b_sizes = set(rec["size"][~is_fwd].tolist())
+        r["nterm_sizes"], r["cterm_sizes"] = len(f_sizes), len(b_sizes)
+        r["nterm_run"], r["cterm_run"] = _longest_run(f_sizes), _longest_run(b_sizes)
+        r["bonds"] = len(f_sizes | set(L - t for t in b_sizes))
+        r["kind"] = _lib.PYA_COV_SCORED
+    return out
+
+
+def coverage_ratios(rec):
+    """``dict(explained, nterm, cterm, peaks)`` of coverage records, one float64 per record: explained / total, N-terminal /
+    total and C-terminal / total ion current, explained peaks / retained peaks -- 0 where the denominator is 0."""
+    rec = np.asarray(rec, COVERAGE_DTYPE)
+    total, kept = rec["total_current"], rec["n_retained"].astype(np.float64)
+
+    def over(num, den):
+        out = np.zeros(rec.shape, np.float64)
+        ok = den != 0
+        with np.errstate(invalid="ignore", over="ignore"):
+            out[ok] = num[ok] / den[ok]
+        return out
+    return dict(explained=over(rec["explained_current"], total), nterm=over(rec["nterm_current"], total),
+                cterm=over(rec["cterm_current"], total), peaks=over(rec["n_explained"].astype(np.float64), kept))
 
 
 def merge_mz_profiles(*tables):
