@@ -3,9 +3,8 @@
  * run reads anything written here.  The reference has no counterpart.
  *
  * A workgroup is one wavefront and takes one PSM.  Three phases:
- *   1  section 1 of the ion stage (ions.hip) without the emission, as mz_profile.hip walks it: gen_setup_residues, the
- *      winner's two prefix tables, the lanes over 64 consecutive prefixes x loss variants x ion types x charges,
- *      ion_match_index.  A match ORs bit `at` (the table index of its peak) into one of two bit planes over the retained
+ *   1  the winner's matched fragments, the walk the ion stage's section 1 and mz_profile.hip take: gen_setup_residues, then
+ *      ion_walk_winner (ion_match.hip.h).  A match ORs bit `at` (the table index of its peak) into one of two bit planes over the retained
  *      table -- forward types, backward types -- and bit `size` into one of two size planes, all in LDS (ds_or).
  *   2  the lanes stride the RAW peaks of the PSM's spectrum: (float)mz is looked up in the retained table (lower bound, then
  *      the run of equal entries), the plane bits of those entries say explained / N-terminal / C-terminal, and the intensity
@@ -39,7 +38,7 @@ __host__ __device__ static inline uint32_t cov_plane_words(uint32_t peak_cap) { 
 
 /* the general carve without lists | two size planes | 4 x 64 partial sums | two planes over the retained table */
 __host__ __device__ static inline size_t cov_lds_bytes(uint32_t l_cap, uint32_t peak_cap) {
-    return ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15) + 2 * COV_SIZE_WORDS * 4 + 4 * 64 * 8 + 2 * (size_t)cov_plane_words(peak_cap) * 4;
+    return gen_own_off(l_cap, 0) + 2 * COV_SIZE_WORDS * 4 + 4 * 64 * 8 + 2 * (size_t)cov_plane_words(peak_cap) * 4;
 }
 
 /* the longest run of consecutive set bits among bits 1 .. hi of a size plane, and how many are set (one lane) */
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(64) void pya_coverage_kernel(BatchDev b, const CovA
     const uint32_t l_cap = a.l_cap;
     const GenLds g = gen_carve(lds_raw, l_cap, 0);
     const uint32_t lc = (l_cap + 3u) & ~3u;
-    uint32_t *size_pl = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15));    /* [2][COV_SIZE_WORDS] */
+    uint32_t *size_pl = (uint32_t *)(lds_raw + gen_own_off(l_cap, 0));    /* [2][COV_SIZE_WORDS] */
     double *part = (double *)(size_pl + 2 * COV_SIZE_WORDS);                                        /* [4][64] */
     uint32_t *peak_pl = (uint32_t *)(part + 4 * 64);                                                /* [2][pw] */
     const uint32_t pw = cov_plane_words(a.peak_cap);
@@ -96,46 +95,14 @@ __global__ __launch_bounds__(64) void pya_coverage_kernel(BatchDev b, const CovA
     if (L >= 1 && (uint32_t)L <= l_cap && L <= PYA_MAX_PEPTIDE_LEN) n_sites = gen_setup_residues(b, cfg, g, psm, pep0, L);
     const bool walked = n_sites >= 0 && n_sites <= GEN_MAX_SITES;   /* (otherwise: not reached by a scored PSM; no fragments) */
     if (walked) {
-        const float err = cfg->mz_error;
-        const bool half_check = err > 0.49f;
-        const int T = cfg->n_types, n_fwd = cfg->n_fwd;
-        const uint64_t types64 = load_types64(cfg);
-        const int n_uniq = cfg->n_nl ? cfg->n_uniq : 1;
-        const int zmax = b.max_charge[psm];
-        const uint64_t best_bits = b.best_sig[psm];
-        /* both directions of the winner at once, slot 0 forward, slot 1 backward (ions.hip, section 1) */
-        if (lane < 2) gen_prefix_table(g, cfg, best_bits, L, lane, lane, lc);
-        gen_sync();
-        for (int dir = 0; dir < 2; dir++) {
-            const int t0 = dir ? n_fwd : 0, t1 = dir ? T : n_fwd;
-            for (int s0 = 0; s0 + 1 < L && t0 < t1; s0 += 64) {
-                const int step = s0 + lane;
-                const bool live = step + 1 < L;
-                const float running = live ? g.run[dir * lc + step] : 0.f;
-                const uint64_t pm = live ? g.pm[dir * lc + step] : 0ull;
-                const uint32_t size = (uint32_t)(step + 1);
-                for (int v = 0; v < n_uniq; v++) {
-                    const bool has = (pm >> v) & 1ull;
-                    if (!__ballot(has)) continue;
-                    const float x = running - (cfg->n_nl ? g.uniq[v] : 0.f);
-                    for (int t = t0; t < t1; t++) {
-                        double A, B;
-                        type_constants((uint8_t)type_at(types64, t), &A, &B);
-                        const double m = ((double)x + A) - B;
-                        for (int z = 1; z <= zmax; z++) {
-                            const float f = charge_mz(m, z);
-                            int rk = GEN_NO_MATCH;
-                            const int at = has ? ion_match_index(tab, R, f, err, half_check, &rk) : -1;
-                            if (at >= 0) {
-                                if (((uint32_t)at >> 5) < r_words) atomicOr(&peak_pl[dir * pw + ((uint32_t)at >> 5)], 1u << ((uint32_t)at & 31u));
-                                if (size < 32u * COV_SIZE_WORDS) atomicOr(&size_pl[dir * COV_SIZE_WORDS + (size >> 5)], 1u << (size & 31u));
-                            }
-                            n_frag += (uint32_t)__popcll(__ballot(at >= 0));
-                        }
-                    }
-                }
+        ion_walk_winner(g, cfg, b.best_sig[psm], L, b.max_charge[psm], lc, tab, R, [&](int dir, int step, int, uint32_t, int, float, int at, int) {
+            const uint32_t size = (uint32_t)(step + 1);
+            if (at >= 0) {
+                if (((uint32_t)at >> 5) < r_words) atomicOr(&peak_pl[dir * pw + ((uint32_t)at >> 5)], 1u << ((uint32_t)at & 31u));
+                if (size < 32u * COV_SIZE_WORDS) atomicOr(&size_pl[dir * COV_SIZE_WORDS + (size >> 5)], 1u << (size & 31u));
             }
-        }
+            n_frag += (uint32_t)__popcll(__ballot(at >= 0));
+        });
     }
     gen_sync();
 

@@ -8,9 +8,10 @@
  *                                              of the site (cpp/Ascore.cpp:212-250, the test at :240)
  *   depth scores and PepScore of the winner    cpp/Ascore.cpp:53-139: one site assignment per lane -- lane 0 the winner,
  *   and of every competitor of the site        lane i the i-th competitor in position order -- counted into an LDS
- *                                              histogram (a column per lane), scored from the host-built table
+ *                                              histogram (a column per lane) by gen_walk_assignment, scored from the
+ *                                              host-built table by gen_pep_score (general_core.hip.h)
  *   a tie with the winner                      cpp/Ascore.cpp:159-161: PYA_EV_TIED, no ion is looked at
- *   the depth of the pair                      cpp/Ascore.cpp:164-172, every lane its own
+ *   the depth of the pair                      gen_pair_depth (cpp/Ascore.cpp:164-172), every lane its own
  *   site-determining ions, their matches       gen_ascore_pair (general_core.hip.h): both lists, ranked, the greedy walk
  *                                              of cpp/ModifiedPeptide.cpp:259-320 -- it ends with the four tallies on
  *                                              lane 0, one competitor after the other; the smallest Ascore, and among
@@ -28,7 +29,7 @@
 /* behind the general route's LDS: hist[PYA_NTOP_MAX][64] counts per depth, a column per lane (later the lanes' depth
  * scores), rows[64] the records of the PSM, site_res[64] the residue of the j-th modifiable one */
 __host__ __device__ static inline size_t ev_lds_bytes(uint32_t l_cap, uint32_t list_cap) {
-    return ((gen_lds_bytes(l_cap, list_cap) + 15) & ~(size_t)15) + PYA_NTOP_MAX * 64 * 4 + 64 * 16 + 64 * 2;
+    return gen_own_off(l_cap, list_cap) + PYA_NTOP_MAX * 64 * 4 + 64 * 16 + 64 * 2;
 }
 
 DEV uint4 ev_row(float comp_score, uint32_t comp_pos, uint32_t depth, uint32_t kind, uint32_t ref_m, uint32_t ref_p,
@@ -47,7 +48,7 @@ __global__ __launch_bounds__(64) void pya_evidence_kernel(BatchDev b, const uint
     const DevConfig *cfg = b.cfg;
     const GenLds g = gen_carve(lds_raw, l_cap, list_cap);
     const uint32_t lc = (l_cap + 3u) & ~3u;
-    uint32_t *hist = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, list_cap) + 15) & ~(size_t)15));
+    uint32_t *hist = (uint32_t *)(lds_raw + gen_own_off(l_cap, list_cap));
     float *scf = (float *)hist;
     uint4 *rows = (uint4 *)(hist + PYA_NTOP_MAX * 64);
     uint16_t *site_res = (uint16_t *)(rows + 64);
@@ -78,10 +79,6 @@ __global__ __launch_bounds__(64) void pya_evidence_kernel(BatchDev b, const uint
     const uint64_t best_bits = b.best_sig[psm];
     const PeakEntry *tab = b.ret + b.ret_off[psm];
     const int R = (int)b.ret_n[psm];
-    const float err = cfg->mz_error;
-    const bool half_check = err > 0.49f;
-    const int T = cfg->n_types, n_fwd = cfg->n_fwd;
-    const uint64_t types64 = load_types64(cfg);
     const int ntop = cfg->n_top;
 
     for (int a = 0; a < k && a < (int)max_k && a < 64; a++) {
@@ -102,78 +99,20 @@ __global__ __launch_bounds__(64) void pya_evidence_kernel(BatchDev b, const uint
         }
         for (int d = 0; d < PYA_NTOP_MAX; d++) hist[d * 64 + lane] = 0u;
 
-        /* ---- counts (Ascore.cpp:53-121), as the general kernel takes them ---- */
-        uint32_t nfrag = 0;
-        if (active) {
-            for (int dir = 0; dir < 2; dir++) {
-                const int t0 = dir ? n_fwd : 0, t1 = dir ? T : n_fwd;
-                if (t0 == t1) continue;
-                float running = 0.f;
-                uint32_t st = 0;
-                uint64_t pm_now = 1ull;
-                for (int step = 0; step + 1 < L; step++) {
-                    const int ri = dir ? L - 1 - step : step;
-                    const bool mod = gen_modified(g, bits, ri);
-                    running = (mod ? g.m1[ri] : g.m0[ri]) + running;
-                    if (cfg->n_nl) {
-                        const uint32_t cls = mod ? g.nl1[ri] : g.nl0[ri];
-                        if (cls) {
-                            const uint32_t st2 = nl_bump(st, cls);
-                            if (st2 != st) pm_now = gen_present(g, cfg->n_cand, st2);
-                            st = st2;
-                        }
-                    }
-                    uint64_t pm = pm_now;
-                    while (pm) {
-                        const int v = __builtin_ctzll(pm);
-                        pm &= pm - 1;
-                        const float x = running - (cfg->n_nl ? g.uniq[v] : 0.f);
-                        for (int t = t0; t < t1; t++) {
-                            double A, B;
-                            type_constants(type_at(types64, t), &A, &B);
-                            const double m = ((double)x + A) - B;
-                            for (int z = 1; z <= zmax; z++) {
-                                const int rk = gen_match_rank(tab, R, charge_mz(m, z), err, half_check);
-                                if (rk < ntop) hist[rk * 64 + lane]++;
-                                nfrag++;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        /* ---- depth scores and PepScore (Ascore.cpp:123-139): the lane's column turns from counts into scores ---- */
-        const bool in_table = nfrag <= b.lut_n_max;
+        /* ---- counts (gen_walk_assignment), then depth scores and PepScore (gen_pep_score): the lane's column turns from
+         * counts into scores ---- */
         float ws = -1.f;
-        if (active && in_table) {
-            double sum = 0.;
-            uint32_t acc = 0;
-            const float *row = b.lut + b.lut_off[nfrag];
-            for (int d = 0; d < ntop; d++) {
-                acc += hist[d * 64 + lane];
-                const float sc = row[(uint32_t)d * (nfrag + 1) + acc];
-                scf[d * 64 + lane] = sc;
-                if (d < PYA_NTOP) {
-                    const float prod = cfg->weights[d] * sc;      /* float product ... */
-                    sum = sum + (double)prod;                     /* ... double sum    */
-                }
-            }
-            ws = (float)sum;
+        bool in_table = true;
+        if (active) {
+            const uint32_t nfrag = gen_walk_assignment(g, cfg, bits, L, zmax, tab, R, [&](int rk) {
+                if (rk < ntop) hist[rk * 64 + lane]++;
+            });
+            in_table = gen_pep_score(b, cfg, hist + lane, 64, nfrag, &ws, nullptr, scf + lane);
         }
         gen_sync();
-        if (__any(active && !in_table)) continue;                   /* (the run would have rejected the PSM: not reached) */
-        /* ---- the depth of every pair (Ascore.cpp:164-172) ---- */
-        int depth = 0;
-        {
-            float bestd = 0.f;
-            for (int d = 0; d < ntop; d++) {
-                const float diff = scf[d * 64] - scf[d * 64 + lane];
-                if (diff > bestd) {
-                    bestd = diff;
-                    depth = d;
-                }
-            }
-        }
+        if (__any(!in_table)) continue;                             /* (the run would have rejected the PSM: not reached) */
+        /* ---- the depth of every pair, every lane its own against the winner's column ---- */
+        const int depth = gen_pair_depth(scf, scf + lane, 64, ntop);
         const float best_ws = __shfl(ws, 0, 64), comp_ws = __shfl(ws, 1, 64);
         const int first_bit = __builtin_ctzll(alt);
         if ((double)__builtin_fabsf(best_ws - comp_ws) < 1e-6) {   /* Ascore.cpp:159-161 */

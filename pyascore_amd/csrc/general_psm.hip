@@ -61,10 +61,6 @@ __global__ __launch_bounds__(64) void pya_general_psm_kernel(BatchDev b, const u
     const int64_t s0 = b.sig_off[psm];
     const PeakEntry *tab = b.ret + b.ret_off[psm];
     const int R = (int)b.ret_n[psm];
-    const float err = cfg->mz_error;
-    const bool half_check = err > 0.49f;
-    const int T = cfg->n_types, n_fwd = cfg->n_fwd;
-    const uint64_t types64 = load_types64(cfg);
     const int ntop = cfg->n_top;                               /* 10..PYA_NTOP_MAX */
     const uint32_t rec_words = (uint32_t)(ntop + 1) / 2u + 1u;    /* count record: ntop 16-bit counts + the fragment total (host_internal.h: rec_words) */
 
@@ -79,67 +75,16 @@ __global__ __launch_bounds__(64) void pya_general_psm_kernel(BatchDev b, const u
         uint32_t cnt[PYA_NTOP_MAX];
 #pragma unroll
         for (int d = 0; d < PYA_NTOP_MAX; d++) cnt[d] = 0;
-        uint32_t nfrag = 0;
-        for (int dir = 0; dir < 2; dir++) {
-            const int t0 = dir ? n_fwd : 0, t1 = dir ? T : n_fwd;
-            if (t0 == t1) continue;
-            float running = 0.f;
-            uint32_t st = 0;
-            uint64_t pm_now = 1ull;
-            for (int step = 0; step + 1 < L; step++) {
-                const int ri = dir ? L - 1 - step : step;
-                const bool mod = gen_modified(g, bits, ri);
-                running = (mod ? g.m1[ri] : g.m0[ri]) + running;
-                if (cfg->n_nl) {
-                    const uint32_t cls = mod ? g.nl1[ri] : g.nl0[ri];
-                    if (cls) {
-                        const uint32_t st2 = nl_bump(st, cls);
-                        if (st2 != st) pm_now = gen_present(g, cfg->n_cand, st2);
-                        st = st2;
-                    }
-                }
-                uint64_t pm = pm_now;
-                while (pm) {
-                    const int v = __builtin_ctzll(pm);
-                    pm &= pm - 1;
-                    const float x = running - (cfg->n_nl ? g.uniq[v] : 0.f);
-                    for (int t = t0; t < t1; t++) {
-                        double A, B;
-                        type_constants(type_at(types64, t), &A, &B);
-                        const double m = ((double)x + A) - B;
-                        for (int z = 1; z <= zmax; z++) {
-                            const int rk = gen_match_rank(tab, R, charge_mz(m, z), err, half_check);
-                            if (rk < ntop) cnt[rk]++;
-                            nfrag++;
-                        }
-                    }
-                }
-            }
-        }
-        uint32_t cum[PYA_NTOP_MAX], acc = 0;
-#pragma unroll
-        for (int d = 0; d < PYA_NTOP_MAX; d++) {
-            acc += cnt[d];
-            cum[d] = acc;
-        }
-        float ws = -1.f;
-        if (nfrag <= b.lut_n_max) {
-            double sum = 0.;
-#pragma unroll
-            for (int d = 0; d < PYA_NTOP; d++) {
-                const float sc = b.lut[b.lut_off[nfrag] + (uint32_t)d * (nfrag + 1) + cum[d]];   /* (the first ten depths are weighted) */
-                const float prod = cfg->weights[d] * sc;          /* float product ... */
-                sum = sum + (double)prod;                         /* ... double sum    */
-            }
-            ws = (float)sum;
-        } else {
-            fail = 1;
-        }
+        const uint32_t nfrag = gen_walk_assignment(g, cfg, bits, L, zmax, tab, R, [&](int rk) {
+            if (rk < ntop) cnt[rk]++;
+        });
+        float ws;                                              /* (the counts turn cumulative where they stand, in registers) */
+        if (!gen_pep_score(b, cfg, cnt, 1, nfrag, &ws, cnt)) fail = 1;
         b.ws[s0 + s] = ws;
         uint32_t *r6 = b.rec + (size_t)(s0 + s) * rec_words;
 #pragma unroll
         for (int d = 0; d < PYA_NTOP_MAX; d += 2)
-            if (d < ntop) r6[d >> 1] = cum[d] | ((d + 1 < ntop ? cum[d + 1] : 0u) << 16);
+            if (d < ntop) r6[d >> 1] = cnt[d] | ((d + 1 < ntop ? cnt[d + 1] : 0u) << 16);
         r6[rec_words - 1] = nfrag;
     }
     if (__any(fail)) {
@@ -265,17 +210,7 @@ __global__ __launch_bounds__(64) void pya_general_psm_kernel(BatchDev b, const u
             }
         }
         gen_sync();
-        int depth = 0;
-        {
-            float bestd = 0.f;
-            for (int d = 0; d < ntop; d++) {
-                const float diff = g.sc[d] - g.sc[PYA_NTOP_MAX + d];
-                if (diff > bestd) {
-                    bestd = diff;
-                    depth = d;
-                }
-            }
-        }
+        const int depth = gen_pair_depth(g.sc, g.sc + PYA_NTOP_MAX, 1, ntop);
         float asc = 0.f;
         if (gen_ascore_pair(b, cfg, g, best_bits, pe.bits, depth, L, zmax, lc, list_cap, tab, R, &asc)) fail = 1;
         else if (lane == 0) g.site_asc[a] = asc < g.site_asc[a] ? asc : g.site_asc[a];
@@ -321,17 +256,7 @@ __global__ __launch_bounds__(64) void pya_general_ambiguity_kernel(BatchDev b, u
     const int64_t pep0 = b.pep_off[psm];
     const int L = (int)(b.pep_off[psm + 1] - pep0);
     (void)gen_setup_residues(b, cfg, g, psm, pep0, L);
-    int depth = 0;
-    {
-        float bestd = 0.f;                                          /* Ascore.cpp:164-172 */
-        for (int d = 0; d < (int)n_scores; d++) {
-            const float diff = scores[d] - scores[n_scores + d];
-            if (diff > bestd) {
-                bestd = diff;
-                depth = d;
-            }
-        }
-    }
+    const int depth = gen_pair_depth(scores, scores + n_scores, 1, (int)n_scores);
     float asc = 0.f;
     const int fail = gen_ascore_pair(b, cfg, g, ref_bits, oth_bits, depth, L, b.max_charge[psm], lc, list_cap,
                                      b.ret + b.ret_off[psm], (int)b.ret_n[psm], &asc);

@@ -5,9 +5,9 @@
  * they lie, best_sig, status -- and the evidence rows of the same results (competitor and depth of every counted column):
  *   section 1, the winner's annotation         every fragment Ascore::accumulateCounts visits for the best localisation
  *                                              (cpp/Ascore.cpp:53-121) that has a retained peak in its window
- *                                              (ModifiedPeptide::consumePeak, cpp/ModifiedPeptide.cpp:126-142): the walk of
- *                                              the evidence kernel's counting loop with the lanes over 64 consecutive
- *                                              prefixes, the table INDEX of the match, records placed by ballot / mask_rank
+ *                                              (ModifiedPeptide::consumePeak, cpp/ModifiedPeptide.cpp:126-142):
+ *                                              ion_walk_winner (ion_match.hip.h), the lanes over 64 consecutive prefixes,
+ *                                              the table INDEX of the match, records placed by ballot / mask_rank
  *   section 2, site-determining ions           for every PYA_EV_COUNTED column the two lists that survive the greedy walk
  *                                              (cpp/ModifiedPeptide.cpp:259-320) of the winner against that row's
  *                                              competitor: the pair routine of general_core.hip.h with every ion's identity
@@ -29,46 +29,12 @@
 /* behind the general route's LDS, per list entry: the identity of the unsorted ion and of the sorted ion of either list
  * (size | charge << 16 | loss << 24; bit 31: it survived the walk) */
 __host__ __device__ static inline size_t ions_lds_bytes(uint32_t l_cap, uint32_t list_cap) {
-    return ((gen_lds_bytes(l_cap, list_cap) + 15) & ~(size_t)15) + (size_t)list_cap * 3 * 4;
+    return gen_own_off(l_cap, list_cap) + (size_t)list_cap * 3 * 4;
 }
 
 DEV uint4 ion_rec(float theo, float peak, uint32_t size, uint32_t type, uint32_t charge, uint32_t rank, uint32_t site, uint32_t flags) {
     return make_uint4(__float_as_uint(theo), __float_as_uint(peak), (size & 0xffffu) | (type & 0xffu) << 16 | (charge & 0xffu) << 24,
                       (rank & 0xffu) | (site & 0xffu) << 8 | (flags & 0xffu) << 16);
-}
-
-/* gen_fill_list with the identity of every ion beside its m/z */
-DEV void ion_fill_list(const GenLds &g, const DevConfig *cfg, int L, int zmax, int slot, uint32_t lc, double A, double B, float *out,
-                       uint32_t *ident) {
-    for (int step = lane_id(); step + 1 < L; step += 64) {
-        const float running = g.run[slot * lc + step];
-        uint64_t pm = g.pm[slot * lc + step];
-        uint32_t at = g.cpre[slot * lc + step] * (uint32_t)zmax;
-        while (pm) {
-            const int v = __builtin_ctzll(pm);
-            pm &= pm - 1;
-            const float x = running - (cfg->n_nl ? g.uniq[v] : 0.f);
-            const double m = ((double)x + A) - B;
-            for (int z = 1; z <= zmax; z++) {
-                ident[at] = (uint32_t)(step + 1) | (uint32_t)z << 16 | (v ? 1u << 24 : 0u);
-                out[at++] = charge_mz(m, z);
-            }
-        }
-    }
-}
-
-/* gen_rank_sort, the identities moved with the values (equal m/z keep the order of the fill: size, loss sum, charge) */
-DEV void ion_rank_sort(const float *in, const uint32_t *ident, float *out, uint32_t *ident_out, int n) {
-    for (int i = lane_id(); i < n; i += 64) {
-        const float x = in[i];
-        int pos = 0;
-        for (int j = 0; j < n; j++) {
-            const float y = in[j];
-            pos += (y < x || (y == x && j < i)) ? 1 : 0;
-        }
-        out[pos] = x;
-        ident_out[pos] = ident[i];
-    }
 }
 
 /* the survivors of one sorted list, in m/z order, from `at` on (never at or past `end`); returns how many there were */
@@ -107,61 +73,37 @@ DEV void ion_pair_emit(const DevConfig *cfg, const GenLds &g, uint32_t *ident_u,
     for (int t = 0; t < T; t++) {
         const int dir = t < n_fwd ? 0 : 1;
         if (dir != tables_dir) {
-            gen_sync();
-            uint32_t n = 0;
-            if (lane < 2) n = gen_prefix_table(g, cfg, lane ? oth_bits : ref_bits, L, dir, lane, lc);
-            npairs_a = (uint32_t)__shfl((int)n, 0, 64);
-            npairs_b = (uint32_t)__shfl((int)n, 1, 64);
+            gen_pair_tables(g, cfg, ref_bits, oth_bits, L, dir, lc, &npairs_a, &npairs_b);
             tables_dir = dir;
-            gen_sync();
         }
         const int na = (int)npairs_a * zmax, nb = (int)npairs_b * zmax;
         if ((uint32_t)na > list_cap || (uint32_t)nb > list_cap) return;   /* (the evidence row would not be a counted one: not reached) */
         const uint32_t type = type_at(types64, t);
         double A, B;
         type_constants((uint8_t)type, &A, &B);
-        ion_fill_list(g, cfg, L, zmax, 0, lc, A, B, g.la, ident_u);
+        gen_fill_list(g, cfg, L, zmax, 0, lc, A, B, g.la, ident_u);
         gen_sync();
-        ion_rank_sort(g.la, ident_u, g.sa, ident_a, na);
+        gen_rank_sort(g.la, g.sa, na, ident_u, ident_a);
         gen_sync();
-        ion_fill_list(g, cfg, L, zmax, 1, lc, A, B, g.lb, ident_u);
+        gen_fill_list(g, cfg, L, zmax, 1, lc, A, B, g.lb, ident_u);
         gen_sync();
-        ion_rank_sort(g.lb, ident_u, g.sb, ident_b, nb);
+        gen_rank_sort(g.lb, g.sb, nb, ident_u, ident_b);
         gen_sync();
         /* the match of every sorted ion: its rank beside it, the peak's m/z where the unsorted value was */
         for (int i = lane; i < na; i += 64) {
             int rk;
-            const int at = ion_match_index(tab, R, g.sa[i], err, half_check, &rk);
+            const int at = gen_match_index(tab, R, g.sa[i], err, half_check, &rk);
             g.ha[i] = (uint8_t)rk;
             g.la[i] = at >= 0 ? tab[at].mz : 0.f;
         }
         for (int i = lane; i < nb; i += 64) {
             int rk;
-            const int at = ion_match_index(tab, R, g.sb[i], err, half_check, &rk);
+            const int at = gen_match_index(tab, R, g.sb[i], err, half_check, &rk);
             g.hb[i] = (uint8_t)rk;
             g.lb[i] = at >= 0 ? tab[at].mz : 0.f;
         }
         gen_sync();
-        if (lane == 0) {                                    /* the greedy walk (ModifiedPeptide.cpp:291-316) */
-            int ia = 0, ib = 0;
-            while (ia < na || ib < nb) {
-                if (ib == nb) {
-                    ident_a[ia++] |= ION_SURVIVES;
-                } else if (ia == na) {
-                    ident_b[ib++] |= ION_SURVIVES;
-                } else {
-                    const float xa = g.sa[ia], xb = g.sb[ib];
-                    if (__builtin_fabsf(xa - xb) < err) {
-                        ia++;
-                        ib++;
-                    } else if (xa < xb) {
-                        ident_a[ia++] |= ION_SURVIVES;
-                    } else {
-                        ident_b[ib++] |= ION_SURVIVES;
-                    }
-                }
-            }
-        }
+        if (lane == 0) gen_greedy_walk(g.sa, na, g.sb, nb, err, [&](int side, int i) { (side ? ident_b : ident_a)[i] |= ION_SURVIVES; });
         gen_sync();
         at_ref += ion_write_list(out, at_ref, end_ref, g.sa, g.la, ident_a, g.ha, na, type, site, 0u, depth);
         at_oth += ion_write_list(out, at_oth, end_oth, g.sb, g.lb, ident_b, g.hb, nb, type, site, ION_COMP, depth);
@@ -180,7 +122,7 @@ __global__ __launch_bounds__(64) void pya_ions_kernel(BatchDev b, const uint32_t
     const DevConfig *cfg = b.cfg;
     const GenLds g = gen_carve(lds_raw, l_cap, list_cap);
     const uint32_t lc = (l_cap + 3u) & ~3u;
-    uint32_t *ident_u = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, list_cap) + 15) & ~(size_t)15));
+    uint32_t *ident_u = (uint32_t *)(lds_raw + gen_own_off(l_cap, list_cap));
     uint32_t *ident_a = ident_u + list_cap, *ident_b = ident_a + list_cap;
 
     /* no records: not scored (set aside, rejected by a kernel, no site assignment) */
@@ -213,11 +155,6 @@ __global__ __launch_bounds__(64) void pya_ions_kernel(BatchDev b, const uint32_t
     const uint64_t best_bits = b.best_sig[psm];
     const PeakEntry *tab = b.ret + b.ret_off[psm];
     const int R = (int)b.ret_n[psm];
-    const float err = cfg->mz_error;
-    const bool half_check = err > 0.49f;
-    const int T = cfg->n_types, n_fwd = cfg->n_fwd;
-    const uint64_t types64 = load_types64(cfg);
-    const int n_uniq = cfg->n_nl ? cfg->n_uniq : 1;
     const bool pairs = k > 0 && k < n_sites;                        /* (an unambiguous PSM has no section 2) */
 
     /* section 2 is as long as its counted rows say */
@@ -230,42 +167,17 @@ __global__ __launch_bounds__(64) void pya_ions_kernel(BatchDev b, const uint32_t
     if (FILL && end - base < n2) return;                            /* (offsets that are not this count's: not reached) */
     const uint64_t end1 = end - n2;
 
-    /* ---- section 1: both directions of the winner at once, slot 0 forward, slot 1 backward ---- */
-    if (lane < 2) gen_prefix_table(g, cfg, best_bits, L, lane, lane, lc);
-    gen_sync();
+    /* ---- section 1: the winner's matched fragments in the order of ion_walk_winner, placed by ballot / mask_rank ---- */
     uint64_t n1 = 0;
-    for (int dir = 0; dir < 2; dir++) {
-        const int t0 = dir ? n_fwd : 0, t1 = dir ? T : n_fwd;
-        for (int s0 = 0; s0 + 1 < L && t0 < t1; s0 += 64) {
-            const int step = s0 + lane;
-            const bool live = step + 1 < L;
-            const float running = live ? g.run[dir * lc + step] : 0.f;
-            const uint64_t pm = live ? g.pm[dir * lc + step] : 0ull;
-            for (int v = 0; v < n_uniq; v++) {
-                const bool has = (pm >> v) & 1ull;
-                if (!__ballot(has)) continue;
-                const float x = running - (cfg->n_nl ? g.uniq[v] : 0.f);
-                for (int t = t0; t < t1; t++) {
-                    const uint32_t type = type_at(types64, t);
-                    double A, B;
-                    type_constants((uint8_t)type, &A, &B);
-                    const double m = ((double)x + A) - B;
-                    for (int z = 1; z <= zmax; z++) {
-                        const float f = charge_mz(m, z);
-                        int rk = GEN_NO_MATCH;
-                        const int at = has ? ion_match_index(tab, R, f, err, half_check, &rk) : -1;
-                        const uint64_t hit = __ballot(at >= 0);
-                        if (FILL) {
-                            const uint64_t pos = base + n1 + (uint64_t)mask_rank(hit);
-                            if (at >= 0 && pos < end1)
-                                out[pos] = ion_rec(f, tab[at].mz, (uint32_t)(step + 1), type, (uint32_t)z, (uint32_t)rk, ION_WINNER, v ? ION_LOSS : 0u);
-                        }
-                        n1 += (uint64_t)__popcll(hit);
-                    }
-                }
-            }
+    ion_walk_winner(g, cfg, best_bits, L, zmax, lc, tab, R, [&](int, int step, int v, uint32_t type, int z, float f, int at, int rk) {
+        const uint64_t hit = __ballot(at >= 0);
+        if (FILL) {
+            const uint64_t pos = base + n1 + (uint64_t)mask_rank(hit);
+            if (at >= 0 && pos < end1)
+                out[pos] = ion_rec(f, tab[at].mz, (uint32_t)(step + 1), type, (uint32_t)z, (uint32_t)rk, ION_WINNER, v ? ION_LOSS : 0u);
         }
-    }
+        n1 += (uint64_t)__popcll(hit);
+    });
     if (!FILL) {
         if (lane == 0) off[psm] = (int64_t)(n1 + n2);
         return;

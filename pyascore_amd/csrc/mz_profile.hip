@@ -2,9 +2,9 @@
  * binned in Da and in ppm over bands of m/z, into one table per caller-named run slot (pya_mz_profile, include/pyascore_hip.h).
  * Launched BEHIND a run like evidence.hip; no kernel of a run reads anything written here.  The reference has no counterpart.
  *
- * The ions are section 1 of the ion stage (ions.hip) without the emission: gen_setup_residues, the winner's two prefix
- * tables, the lanes over 64 consecutive prefixes x loss variants x ion types x charges, ion_match_index.  Neither evidence
- * rows nor fragment lists are needed, so the LDS is the general carve with list_cap 0 plus ONE slot's table.
+ * The ions are those of the ion stage's section 1 (ions.hip), without the emission: gen_setup_residues, then
+ * ion_walk_winner (ion_match.hip.h).  Neither evidence rows nor fragment lists are needed, so the LDS is the general carve
+ * with list_cap 0 plus ONE slot's table.
  *
  * A workgroup is one wavefront and takes PYA_MZP_CHUNK consecutive PSMs of its list, one after the other.  A matched ion is
  * two LDS atomic adds (its Da cell, its ppm cell).  The table in LDS belongs to the slot of the PSMs since the last flush:
@@ -43,7 +43,7 @@ struct MzpArgs {
 };
 
 __host__ __device__ static inline size_t mzp_lds_bytes(uint32_t l_cap) {
-    return ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15) + sizeof(pya_mz_profile);
+    return gen_own_off(l_cap, 0) + sizeof(pya_mz_profile);
 }
 
 /* the cell of x on an axis of PYA_MZP_BINS half-open bins around 0: floor(x) + BINS / 2, -1 below the axis, BINS at or above it */
@@ -91,15 +91,9 @@ __global__ __launch_bounds__(64) void pya_mz_profile_kernel(BatchDev b, const Mz
     const uint32_t l_cap = a.l_cap;
     const GenLds g = gen_carve(lds_raw, l_cap, 0);
     const uint32_t lc = (l_cap + 3u) & ~3u;
-    uint32_t *hist = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15));
+    uint32_t *hist = (uint32_t *)(lds_raw + gen_own_off(l_cap, 0));
     for (uint32_t i = (uint32_t)lane; i < MZP_WORDS; i += 64) hist[i] = 0u;
     gen_sync();
-
-    const float err = cfg->mz_error;
-    const bool half_check = err > 0.49f;
-    const int T = cfg->n_types, n_fwd = cfg->n_fwd;
-    const uint64_t types64 = load_types64(cfg);
-    const int n_uniq = cfg->n_nl ? cfg->n_uniq : 1;
 
     const uint64_t first = (uint64_t)blockIdx.x * PYA_MZP_CHUNK;
     const uint64_t last = first + PYA_MZP_CHUNK < a.n_ids ? first + PYA_MZP_CHUNK : a.n_ids;
@@ -129,37 +123,12 @@ __global__ __launch_bounds__(64) void pya_mz_profile_kernel(BatchDev b, const Mz
             const uint64_t best_bits = b.best_sig[psm];
             const PeakEntry *tab = b.ret + b.ret_off[psm];
             const int R = (int)b.ret_n[psm];
-            /* both directions of the winner at once, slot 0 forward, slot 1 backward (ions.hip, section 1) */
-            if (lane < 2) gen_prefix_table(g, cfg, best_bits, L, lane, lane, lc);
-            gen_sync();
-            for (int dir = 0; dir < 2; dir++) {
-                const int t0 = dir ? n_fwd : 0, t1 = dir ? T : n_fwd;
-                for (int s0 = 0; s0 + 1 < L && t0 < t1; s0 += 64) {
-                    const int step = s0 + lane;
-                    const bool live = step + 1 < L;
-                    const float running = live ? g.run[dir * lc + step] : 0.f;
-                    const uint64_t pm = live ? g.pm[dir * lc + step] : 0ull;
-                    for (int v = 0; v < n_uniq; v++) {
-                        const bool has = (pm >> v) & 1ull;
-                        if (!__ballot(has)) continue;
-                        const float x = running - (cfg->n_nl ? g.uniq[v] : 0.f);
-                        for (int t = t0; t < t1; t++) {
-                            double A, B;
-                            type_constants((uint8_t)type_at(types64, t), &A, &B);
-                            const double m = ((double)x + A) - B;
-                            for (int z = 1; z <= zmax; z++) {
-                                const float f = charge_mz(m, z);
-                                int rk = GEN_NO_MATCH;
-                                const int at = has ? ion_match_index(tab, R, f, err, half_check, &rk) : -1;
-                                const bool counted = at >= 0 && (uint32_t)rk <= a.max_rank;
-                                if (counted) mzp_count(hist, a, f, tab[at].mz);
-                                n_ions += (uint32_t)__popcll(__ballot(counted));
-                                n_skipped += (uint32_t)__popcll(__ballot(at >= 0 && !counted));
-                            }
-                        }
-                    }
-                }
-            }
+            ion_walk_winner(g, cfg, best_bits, L, zmax, lc, tab, R, [&](int, int, int, uint32_t, int, float f, int at, int rk) {
+                const bool counted = at >= 0 && (uint32_t)rk <= a.max_rank;
+                if (counted) mzp_count(hist, a, f, tab[at].mz);
+                n_ions += (uint32_t)__popcll(__ballot(counted));
+                n_skipped += (uint32_t)__popcll(__ballot(at >= 0 && !counted));
+            });
             gen_sync();                                             /* (the next PSM's set-up overwrites the tables) */
         }
         if (lane == 0) {                                            /* (one wavefront: nobody else adds to these words) */

@@ -14,7 +14,7 @@
  *                                              m/z arithmetic of a fragment is the general kernel's, so the order of the
  *                                              lookups changes no bit.
  *   a tie with the winner                      cpp/Ascore.cpp:159-161: PYA_NAMED_TIED, no ion is looked at
- *   the depth of the pair                      cpp/Ascore.cpp:164-172, every lane its own column against column 0
+ *   the depth of the pair                      gen_pair_depth (cpp/Ascore.cpp:164-172), every lane its own column against column 0
  *   site-determining ions, their matches       gen_ascore_pair as it is, for any number of moved modifications
  * Queries go through in slices: column 0 is the winner, counted once per PSM, columns 1 .. 63 the slice's queries.
  * The code is the general route's, so one body serves the PSMs inside the fast kernels' limits and the plan's general list,
@@ -34,7 +34,7 @@
 /* behind the general route's LDS: hist[PYA_NTOP_MAX][64] counts per depth, a column per signature (cumulative once the
  * column is scored), scf[PYA_NTOP_MAX][64] the columns' depth scores, col_of[64] the column a slice's record reads */
 __host__ __device__ static inline size_t nm_lds_bytes(uint32_t l_cap, uint32_t list_cap) {
-    return ((gen_lds_bytes(l_cap, list_cap) + 15) & ~(size_t)15) + 2 * PYA_NTOP_MAX * 64 * 4 + 64;
+    return gen_own_off(l_cap, list_cap) + 2 * PYA_NTOP_MAX * 64 * 4 + 64;
 }
 
 /* ids == NULL: block i takes PSM i */
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(64) void pya_named_kernel(BatchDev b, const uint32_
     const DevConfig *cfg = b.cfg;
     const GenLds g = gen_carve(lds_raw, l_cap, list_cap);
     const uint32_t lc = (l_cap + 3u) & ~3u;
-    uint32_t *hist = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, list_cap) + 15) & ~(size_t)15));
+    uint32_t *hist = (uint32_t *)(lds_raw + gen_own_off(l_cap, list_cap));
     float *scf = (float *)(hist + PYA_NTOP_MAX * 64);
     uint8_t *col_of = (uint8_t *)(scf + PYA_NTOP_MAX * 64);
     const int ntop = cfg->n_top;
@@ -146,25 +146,9 @@ __global__ __launch_bounds__(64) void pya_named_kernel(BatchDev b, const uint32_
             if (lane == cb) nfrag = nf_b;
         }
         gen_sync();
-        /* ---- depth scores and PepScore (Ascore.cpp:123-139): the column's counts become cumulative, scf takes the scores ---- */
-        const bool in_table = nfrag <= b.lut_n_max;
+        /* ---- depth scores and PepScore (gen_pep_score): the column's counts become cumulative, scf takes the scores ---- */
         float ws = -1.f;
-        if (count_me && in_table) {
-            double sum = 0.;
-            uint32_t acc = 0;
-            const float *row = b.lut + b.lut_off[nfrag];
-            for (int d = 0; d < ntop; d++) {
-                acc += hist[d * 64 + lane];
-                hist[d * 64 + lane] = acc;
-                const float sc = row[(uint32_t)d * (nfrag + 1) + acc];
-                scf[d * 64 + lane] = sc;
-                if (d < PYA_NTOP) {
-                    const float prod = cfg->weights[d] * sc;      /* float product ... */
-                    sum = sum + (double)prod;                     /* ... double sum    */
-                }
-            }
-            ws = (float)sum;
-        }
+        const bool in_table = !count_me || gen_pep_score(b, cfg, hist + lane, 64, nfrag, &ws, hist + lane, scf + lane);
         if (first) {
             win_nfrag = (uint32_t)__shfl((int)nfrag, 0, 64);
             win_ws = __shfl(ws, 0, 64);
@@ -181,14 +165,7 @@ __global__ __launch_bounds__(64) void pya_named_kernel(BatchDev b, const uint32_
         /* ---- the depth of every pair (Ascore.cpp:164-172), the tie (:159-161) ---- */
         int depth = 0;
         if (kind == NM_COUNTED) {
-            float bestd = 0.f;
-            for (int d = 0; d < ntop; d++) {
-                const float diff = scf[d * 64] - scf[d * 64 + lane];
-                if (diff > bestd) {
-                    bestd = diff;
-                    depth = d;
-                }
-            }
+            depth = gen_pair_depth(scf, scf + lane, 64, ntop);
             if ((double)__builtin_fabsf(win_ws - ws) < 1e-6) {
                 kind = NM_TIED;
                 depth = 0;

@@ -9,7 +9,7 @@
  *   1. scores the slice            two front ends with the same float32 PepScores (the bits of the pep_scores records):
  *        count nodes                 probs_cnt.hip.h: the tables once per PSM, then k table reads per assignment, for a PSM
  *                                    under score_cnt.hip's conditions;
- *        general                     the lane-per-signature count loop of sites.hip on general_core.hip.h (a binary search
+ *        general                     the lane-per-signature walk (gen_walk_assignment, general_core.hip.h: a binary search
  *                                    per fragment), for everything else and for every PSM under PYA_NO_PROB_CNT;
  *   2. weights                     w = exp2(((double)s - (double)best_score) * C) per lane, (w, bits) into LDS;
  *   3. reduces                     lane r owns residue r and walks the slice's 64 pairs IN INDEX ORDER with broadcast LDS
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(64) void pya_probs_kernel(BatchDev b, const uint32_
         ok = pc_setup(b, psm, lds_raw, caps, ret0, R, k, n_rec, pc);
     } else if (ok) {
         g = gen_carve(lds_raw, l_cap, 0);
-        hist = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15));
+        hist = (uint32_t *)(lds_raw + gen_own_off(l_cap, 0));
         ok = gen_setup_residues(b, cfg, g, psm, pep0, L) == n_rec;
     }
     /* (the host's offsets are made of the same count, and it launches the tables alone only where its own copy of pc_fits

@@ -96,7 +96,7 @@ __global__ __launch_bounds__(64) void pya_ranked_kernel(BatchDev b, const uint32
         ok = pc_setup(b, psm, lds_raw, caps, ret0, R, k, n_rec, pc);
     } else if (ok) {
         g = gen_carve(lds_raw, l_cap, 0);
-        hist = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15));
+        hist = (uint32_t *)(lds_raw + gen_own_off(l_cap, 0));
         ok = gen_setup_residues(b, cfg, g, psm, pep0, L) == n_rec;
     }
     /* (the host launches the tables alone only where its own copy of pc_fits passed every scored PSM of the list --

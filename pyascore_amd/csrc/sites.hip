@@ -6,7 +6,8 @@
  * retained peak tables where they lie, best_sig, n_sig, status, the host-built score table, the shape's signature list
  * (order_tab + order_off[psm], the list every route scores from) -- and repeats the reference's own steps for EVERY site
  * assignment of the PSM:
- *   the score container of a signature         cpp/Ascore.cpp:53-139, as evidence.hip takes it for the competitors of a site:
+ *   the score container of a signature         cpp/Ascore.cpp:53-139, pb_gen_score (slice_score.hip.h) on the one walk and
+ *                                              PepScore chain of general_core.hip.h:
  *                                              lane c of a slice owns signature base + c whole -- the float32 running sum
  *                                              (whose order fixes the bits), the neutral-loss state, every lookup of its
  *                                              fragments, its own column of a histogram [depth][64] in LDS.  All 64 lanes
@@ -26,7 +27,7 @@
  * The records of a PSM lie at site_off[psm] .. site_off[psm + 1], offsets the host made from its pre-pass: a PSM writes
  * exactly that range, whatever it finds.
  */
-#include "general_core.hip.h"
+#include "slice_score.hip.h"
 
 #define ST_NONE 0u
 #define ST_SCORED 1u
@@ -39,7 +40,7 @@
 /* behind the general route's LDS without its lists: hist[PYA_NTOP_MAX][64] counts per depth, a column per lane, s_bits[64] /
  * s_score[64] the slice's signatures and PepScores, site_res[64] the residue of the j-th modifiable one */
 __host__ __device__ static inline size_t st_lds_bytes(uint32_t l_cap) {
-    return ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15) + PYA_NTOP_MAX * 64 * 4 + 64 * 8 + 64 * 4 + 64 * 2;
+    return pb_gen_bytes(l_cap) + 64 * 8 + 64 * 4 + 64 * 2;
 }
 
 /* (max, arg, ties) of one of a residue's two sets, a register each */
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(64) void pya_sites_kernel(BatchDev b, const uint32_
     const int n_rec = (int)(n_rec64 < 64 ? n_rec64 : 64);
     const DevConfig *cfg = b.cfg;
     const GenLds g = gen_carve(lds_raw, l_cap, 0);
-    uint32_t *hist = (uint32_t *)(lds_raw + ((gen_lds_bytes(l_cap, 0) + 15) & ~(size_t)15));
+    uint32_t *hist = (uint32_t *)(lds_raw + gen_own_off(l_cap, 0));
     uint64_t *s_bits = (uint64_t *)(hist + PYA_NTOP_MAX * 64);
     float *s_score = (float *)(s_bits + 64);
     uint16_t *site_res = (uint16_t *)(s_score + 64);
@@ -119,11 +120,6 @@ __global__ __launch_bounds__(64) void pya_sites_kernel(BatchDev b, const uint32_
     const uint64_t *order = b.order_tab + b.order_off[psm];
     const PeakEntry *tab = b.ret + b.ret_off[psm];
     const int R = (int)b.ret_n[psm];
-    const float err = cfg->mz_error;
-    const bool half_check = err > 0.49f;
-    const int T = cfg->n_types, n_fwd = cfg->n_fwd;
-    const uint64_t types64 = load_types64(cfg);
-    const int ntop = cfg->n_top;
 
     StBest with = {-1.f, 0ull, 0u, false}, without = {-1.f, 0ull, 0u, false};
     bool bad = false;
@@ -132,66 +128,9 @@ __global__ __launch_bounds__(64) void pya_sites_kernel(BatchDev b, const uint32_
         const int n_slice = (int)(left < 64u ? left : 64u);
         const bool active = lane < n_slice;
         const uint64_t bits = active ? order[base + (uint32_t)lane] : 0ull;
-        for (int d = 0; d < PYA_NTOP_MAX; d++) hist[d * 64 + lane] = 0u;
-
-        /* ---- counts (Ascore.cpp:53-121), as the general kernel takes them: the lane's signature, its own column ---- */
-        uint32_t nfrag = 0;
-        if (active) {
-            for (int dir = 0; dir < 2; dir++) {
-                const int t0 = dir ? n_fwd : 0, t1 = dir ? T : n_fwd;
-                if (t0 == t1) continue;
-                float running = 0.f;
-                uint32_t st = 0;
-                uint64_t pm_now = 1ull;
-                for (int step = 0; step + 1 < L; step++) {
-                    const int ri = dir ? L - 1 - step : step;
-                    const bool mod = gen_modified(g, bits, ri);
-                    running = (mod ? g.m1[ri] : g.m0[ri]) + running;
-                    if (cfg->n_nl) {
-                        const uint32_t cls = mod ? g.nl1[ri] : g.nl0[ri];
-                        if (cls) {
-                            const uint32_t st2 = nl_bump(st, cls);
-                            if (st2 != st) pm_now = gen_present(g, cfg->n_cand, st2);
-                            st = st2;
-                        }
-                    }
-                    uint64_t pm = pm_now;
-                    while (pm) {
-                        const int v = __builtin_ctzll(pm);
-                        pm &= pm - 1;
-                        const float x = running - (cfg->n_nl ? g.uniq[v] : 0.f);
-                        for (int t = t0; t < t1; t++) {
-                            double A, B;
-                            type_constants(type_at(types64, t), &A, &B);
-                            const double m = ((double)x + A) - B;
-                            for (int z = 1; z <= zmax; z++) {
-                                const int rk = gen_match_rank(tab, R, charge_mz(m, z), err, half_check);
-                                if (rk < ntop) hist[rk * 64 + lane]++;
-                                nfrag++;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        /* ---- depth scores and PepScore (Ascore.cpp:123-139): the chain that fills pya_named.pep_score ---- */
-        const bool in_table = nfrag <= b.lut_n_max;
-        float ws = -1.f;
-        if (active && in_table) {
-            double sum = 0.;
-            uint32_t acc = 0;
-            const float *row = b.lut + b.lut_off[nfrag];
-            for (int d = 0; d < ntop; d++) {
-                acc += hist[d * 64 + lane];
-                const float sc = row[(uint32_t)d * (nfrag + 1) + acc];
-                if (d < PYA_NTOP) {
-                    const float prod = cfg->weights[d] * sc;      /* float product ... */
-                    sum = sum + (double)prod;                     /* ... double sum    */
-                }
-            }
-            ws = (float)sum;
-        }
-        bad = bad || __any(active && !in_table);                    /* (the run would have rejected the PSM: not reached) */
+        /* ---- counts and PepScore (Ascore.cpp:53-139): the lane's signature, its own column; the chain that fills
+         * pya_named.pep_score ---- */
+        const float ws = pb_gen_score(b, cfg, g, hist, tab, R, L, zmax, bits, active, &bad);
         s_bits[lane] = bits;
         s_score[lane] = ws;
         gen_sync();
