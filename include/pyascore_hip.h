@@ -627,6 +627,57 @@ typedef struct pya_strip_report {   /* 16 bytes per spectrum */
     uint32_t n_windows;                     /* active windows                                                                */
 } pya_strip_report;
 
+/* Marker ions: the intensities of reporter and diagnostic ions per spectrum -- the isobaric-label reporters a site is
+ * quantified with, the pY immonium ion, the precursor's - H3PO4 and - HPO3 peaks -- read off the peaks pya_strip_params is there
+ * to remove.  A READ-ONLY stage: it looks up at most PYA_MARKER_MAX_TARGETS target windows per spectrum and writes records; the
+ * spectra and their peak counts stay as they are, so there is no workspace, no scan and no fill, and no kernel of a run knows
+ * of it.  The reference has no counterpart.
+ * THE RULE.  Every spectrum s is handled on its own; x is the m/z of a peak and y its intensity (float32 is widened at the
+ * load); all arithmetic is in double, every operation rounded on its own, in the order written; a comparison with a NaN is
+ * false.
+ * THE CENTRE c of target t: a FIXED target (bit t of loss_mask clear) has c = value[t] and is always active.  A LOSS target
+ * (bit t set) applies only to a spectrum with a usable precursor -- strip's test: prec_z[s] in 1 .. PYA_STRIP_MAX_CHARGE,
+ * prec_mz[s] finite and > 0 --, where
+ *   c = (prec_mz (double)prec_z - value[t]) / (double)prec_z
+ * and the target is ACTIVE iff c is finite and > 0.  Without a usable precursor a loss target is inactive.
+ * THE WINDOW of an active target:
+ *   w  = tol + (tol_ppm 1e-6) c
+ *   lo = c - w,  hi = c + w
+ * A peak is INSIDE iff lo <= x && x <= hi; a NaN m/z is never inside.  n_peaks of the record counts every peak inside.
+ * THE PICK: a peak inside is ELIGIBLE iff y == y.  Among the eligible peaks the larger y wins; with equal y the smaller
+ * fabs(x - c); with that equal too the smaller x.  That is a total order up to peaks with equal (x, y), so the record does not
+ * depend on the order of the peaks.  The record holds x + 0.0 and y + 0.0 of the pick (no -0.0 reaches a record) and 0.0 / 0.0
+ * when no peak is eligible.  A peak inside the windows of two targets counts for both and may be picked by both.
+ * PER SPECTRUM: tic is the sum of (y == y ? y : 0.0) over the peaks: 64 partials from 0.0, peak k (counted from the spectrum's
+ * first) into partial k mod 64 in index order, the partials then added in order from 0.0 (pya_coverage's sum).  base_peak is
+ * the largest y with y == y of the whole spectrum, + 0.0; 0.0 when there is none.  n_peaks is the (clipped) peak count, n_active
+ * the number of active targets, bit t of hit is set iff target t picked a peak.
+ * An INACTIVE target's record is all zero; every record of a call is written.
+ * The parameters must satisfy: tol and tol_ppm finite and >= 0; n_targets in 1 .. PYA_MARKER_MAX_TARGETS; no bit of loss_mask
+ * at or above n_targets; value[t], t < n_targets, finite, > 0 for a fixed target and >= 0 for a loss target (entries from
+ * n_targets on are not looked at); reserved == 0. */
+#define PYA_MARKER_MAX_TARGETS 64
+typedef struct pya_marker_params {     /* 544 bytes */
+    double tol;                                    /* half width of a window in m/z (Da); finite, >= 0                       */
+    double tol_ppm;                                /* and in ppm of the centre, added to it; finite, >= 0                    */
+    double value[PYA_MARKER_MAX_TARGETS];          /* fixed target: its m/z; loss target: the neutral mass off the precursor */
+    uint64_t loss_mask;                            /* bit t: target t is relative to the precursor; no bit >= n_targets      */
+    uint32_t n_targets;                            /* 1 .. PYA_MARKER_MAX_TARGETS                                            */
+    uint32_t reserved;                             /* 0                                                                      */
+} pya_marker_params;
+typedef struct pya_marker {            /* 24 bytes per (spectrum, target), at [s * n_targets + t] */
+    double mz, intensity;                          /* the picked peak, widened; 0.0 / 0.0 when none                          */
+    uint32_t n_peaks;                              /* peaks of the spectrum inside the window                                */
+    uint32_t flags;                                /* bit 0: the target is active for this spectrum; bit 1: a peak was picked */
+} pya_marker;
+#define PYA_MARKER_ACTIVE 1u
+#define PYA_MARKER_PICKED 2u
+typedef struct pya_marker_spectrum {   /* 32 bytes per spectrum */
+    double tic, base_peak;                         /* the ion current and the largest intensity of the spectrum              */
+    uint64_t hit;                                  /* bit t: target t picked a peak                                          */
+    uint32_t n_peaks, n_active;                    /* peaks of the spectrum; active targets                                  */
+} pya_marker_spectrum;
+
 /* Centroiding (peak picking): the first of the transforms in front of a run.  Everything behind it -- the top-N-per-100-m/z
  * binning, the match window, deisotoping's tol, the strip windows -- takes one (m/z, intensity) pair for one peak.  A
  * profile-mode spectrum (msconvert without a peak-picking filter, older QTOF exports, "profile MS2" methods) has 10 to 20
@@ -1094,6 +1145,28 @@ int pya_strip_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64_
 int pya_strip_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
                            const double *prec_mz, const int32_t *prec_z, const pya_strip_params *params,
                            const pya_typed_spectra *out, int64_t *new_off, pya_strip_report *report, uint32_t *over);
+/* Looks up the marker ions of n_spectra spectra on the device (THE RULE at pya_marker_params above; csrc/markers.hip).  d_in,
+ * d_peak_off and n_spectra as pya_deisotope_spectra takes them; n_peaks: the elements the arrays of d_in hold -- the offsets
+ * are clipped to it, as the transforms clip theirs to their workspace, so nothing beyond it is read whatever the offsets say;
+ * d_prec_mz[n_spectra] (double) and d_prec_z[n_spectra] (int32) in device memory, both of which may be NULL iff
+ * params->loss_mask == 0.  d_markers[n_spectra * params->n_targets]: one pya_marker per (spectrum, target), at
+ * [s * n_targets + t]; d_spectra[n_spectra]: one pya_marker_spectrum per spectrum, or NULL when it is not wanted (both device
+ * memory, 8-byte aligned); d_over[2] (zeroed by the caller): the spectra whose offsets were clipped are counted in d_over[0],
+ * the smallest of them in d_over[1] as 0xffffffff - spectrum (its records are those of the clipped peaks).  One launch on
+ * hip_stream, stream-ordered, no host wait, no allocation and no workspace.  The spectra are only read; no write lies
+ * outside d_markers[0 .. n_spectra * n_targets), d_spectra[0 .. n_spectra) and d_over[0 .. 2).
+ * PYA_ERR_ARG, with nothing launched: element types that are neither PYA_F64 nor PYA_F32, float32 m/z beside float64
+ * intensities, more than 2^32 - 2 spectra, a NULL array, parameters outside the conditions above, a NULL precursor array
+ * while loss_mask != 0, records that are not 8-byte aligned.  n_spectra == 0 is a call that writes nothing. */
+int pya_marker_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64_t *d_peak_off, uint64_t n_spectra,
+                       uint64_t n_peaks, const double *d_prec_mz, const int32_t *d_prec_z, const pya_marker_params *params,
+                       void *hip_stream, pya_marker *d_markers, pya_marker_spectrum *d_spectra, uint32_t *d_over);
+/* The same over HOST arrays: uploads the spectra once, runs on the handle's stream, downloads only the records -- markers,
+ * spectra (may be NULL) and over -- and waits.  peak_off[0] must not be negative and the offsets must not descend
+ * (PYA_ERR_ARG); n_peaks is peak_off[n_spectra]. */
+int pya_marker_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
+                            const double *prec_mz, const int32_t *prec_z, const pya_marker_params *params,
+                            pya_marker *markers, pya_marker_spectrum *spectra, uint32_t *over);
 /* The device bytes pya_centroid_spectra needs as its workspace for n_spectra spectra of n_peaks points together: what
  * pya_deisotope_workspace_bytes gives (one keep bit per point in 64-bit words that no two spectra share, and the tile sums of
  * the offset scan; 8 bytes at the least).  Centroids are recomputed by the last pass, not stored. */

@@ -22,7 +22,9 @@ multiply charged fragments to 1+) and ``--strip_precursor`` with ``--strip_tol D
 ``--strip_reduced``, ``--strip_isotopes N``, ``--strip_mz_min X`` and ``--strip_mz_max X`` (remove the precursor, its
 neutral-loss and charge-reduced forms and the peaks outside an m/z range from every spectrum) and ``--centroid`` with
 ``--centroid_gap DA``, ``--centroid_gap_ppm PPM``, ``--centroid_width W``, ``--centroid_min_height H`` and ``--centroid_area``
-(peak-pick every spectrum the file does not declare centroided, before anything else) are the additions."""
+(peak-pick every spectrum the file does not declare centroided, before anything else) and ``--markers FILE`` with
+``--marker_mz M1,M2,...``, ``--marker_losses L1,...``, ``--marker_tol DA`` and ``--marker_tol_ppm PPM`` (a table with a line per PSM:
+the intensities of reporter and diagnostic ions in its spectrum, read before anything is stripped) are the additions."""
 import argparse
 import re
 import sys
@@ -183,6 +185,21 @@ def build_parser():
                    help="with --centroid: local maxima below this intensity are dropped (default 0)")
     p.add_argument("--centroid_area", action="store_true",
                    help="with --centroid: a peak's intensity is the sum over its samples instead of the apex's own")
+    p.add_argument("--markers", type=str, default="", metavar="FILE",
+                   help="write the marker-ion table to FILE: one line per PSM with the ion current and the base peak of its spectrum "
+                        "and, per target of --marker_mz / --marker_losses, the m/z and the intensity of the most intense peak within "
+                        "the tolerance and the peaks inside it; read off the spectra before --strip_precursor cuts them; one more "
+                        "upload of the spectra")
+    p.add_argument("--marker_mz", type=str, default="", metavar="M1,M2,...",
+                   help="with --markers: the m/z of the fixed targets (reporter ions, immonium ions); up to 64 targets with "
+                        "--marker_losses together (default: none)")
+    p.add_argument("--marker_losses", type=str, default="", metavar="L1,L2,...",
+                   help="with --markers: neutral masses whose loss from the spectrum's precursor is a target, e.g. 97.976896 "
+                        "(default: none)")
+    p.add_argument("--marker_tol", type=float, default=None, metavar="DA",
+                   help="with --markers: the half width of a target's window in m/z (default: --mz_error)")
+    p.add_argument("--marker_tol_ppm", type=float, default=0.0, metavar="PPM",
+                   help="with --markers: ... plus this many ppm of the target's m/z (default 0)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -202,6 +219,23 @@ def strip_request(args):
     req = dict(tol=args.strip_tol, losses=losses, reduced=bool(args.strip_reduced), isotopes=args.strip_isotopes, mz_lo=args.strip_mz_min,
                mz_hi=args.strip_mz_max)
     strip_params(**dict(req, tol=args.mz_error if args.strip_tol is None else args.strip_tol))
+    return req
+
+
+def markers_request(args):
+    """The rule of ``--markers`` as the dict ``batch_cli.localize(markers=...)`` takes (the precursors come from the spectra),
+    checked; None without the option: the other ``--marker_*`` values are then not looked at."""
+    if not getattr(args, "markers", ""):
+        return None
+    from .rollup import marker_params
+    lists = {}
+    for name in ("marker_mz", "marker_losses"):
+        try:
+            lists[name] = tuple(float(v) for v in getattr(args, name).split(",") if v.strip())
+        except ValueError:
+            raise ValueError("--%s takes numbers separated by commas, not %r" % (name, getattr(args, name))) from None
+    req = dict(mz=lists["marker_mz"], losses=lists["marker_losses"], tol=args.marker_tol, tol_ppm=args.marker_tol_ppm)
+    marker_params(**dict(req, tol=args.mz_error if args.marker_tol is None else args.marker_tol))
     return req
 
 
@@ -232,6 +266,7 @@ def validate_args(args):
         deisotope_params(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio)
     strip_request(args)
     centroid_request(args)
+    markers_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -297,6 +332,8 @@ def run(args, log=print):
     deisotope = dict(tol=args.deisotope_tol, max_charge=args.deisotope_charge, ratio=args.deisotope_ratio) if args.deisotope else None
     decharge = dict(tol=args.decharge_tol, max_charge=args.decharge_charge, ratio=args.decharge_ratio,
                     witness=args.decharge_witness) if args.decharge else None
+    markers = markers_request(args)
+    marker_rows = [] if markers is not None else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -309,7 +346,8 @@ def run(args, log=print):
                               site_table_decoys=args.site_table_decoys, peptidoform_table=peptidoform_rows,
                               peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
                               deisotope=deisotope, decharge=decharge, strip=strip_request(args),
-                              centroid=centroid_request(args), coverage=coverage_rows)
+                              centroid=centroid_request(args), coverage=coverage_rows, markers=markers,
+                              marker_rows=marker_rows)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -331,6 +369,8 @@ def run(args, log=print):
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     if coverage_rows is not None:
         batch_cli.write_coverage_tsv(coverage_rows, args.coverage)
+    if marker_rows is not None:
+        batch_cli.write_markers_tsv(marker_rows, args.markers, mz=markers["mz"], losses=markers["losses"])
     log("{} -- Ascore Completed".format(stamp()))
     return rows
 

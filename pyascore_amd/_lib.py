@@ -250,6 +250,39 @@ class StripReport(C.Structure):
 assert C.sizeof(StripReport) == 16, "pya_strip_report is a 16-byte record"
 STRIP_REPORT_DTYPE = [("hit", "<u8"), ("n_removed", "<u4"), ("n_windows", "<u4")]
 
+PYA_MARKER_MAX_TARGETS = 64
+PYA_MARKER_ACTIVE = 1
+PYA_MARKER_PICKED = 2
+
+
+class MarkerParams(C.Structure):
+    """pya_marker_params: the half width of a window in Da and in ppm of its centre, the value of every target (a fixed m/z, or
+    the neutral mass taken off the precursor), which targets are relative to the precursor, and how many targets there are"""
+    _fields_ = [("tol", C.c_double), ("tol_ppm", C.c_double), ("value", C.c_double * PYA_MARKER_MAX_TARGETS), ("loss_mask", C.c_uint64),
+                ("n_targets", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(MarkerParams) == 544, "pya_marker_params is a 544-byte record"
+
+
+class Marker(C.Structure):
+    """pya_marker: the peak a target picked in a spectrum, the peaks inside its window, whether it was active and picked"""
+    _fields_ = [("mz", C.c_double), ("intensity", C.c_double), ("n_peaks", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(Marker) == 24, "pya_marker is a 24-byte record"
+MARKER_DTYPE = [("mz", "<f8"), ("intensity", "<f8"), ("n_peaks", "<u4"), ("flags", "<u4")]
+
+
+class MarkerSpectrum(C.Structure):
+    """pya_marker_spectrum: the ion current and the base peak of a spectrum, which targets picked a peak, the peaks of the
+    spectrum and its active targets"""
+    _fields_ = [("tic", C.c_double), ("base_peak", C.c_double), ("hit", C.c_uint64), ("n_peaks", C.c_uint32), ("n_active", C.c_uint32)]
+
+
+assert C.sizeof(MarkerSpectrum) == 32, "pya_marker_spectrum is a 32-byte record"
+MARKER_SPECTRUM_DTYPE = [("tic", "<f8"), ("base_peak", "<f8"), ("hit", "<u8"), ("n_peaks", "<u4"), ("n_active", "<u4")]
+
 PYA_CENTROID_MAX_HALF_WIDTH = 8
 
 
@@ -349,6 +382,9 @@ SYMBOLS = {
                                     C.POINTER(TypedSpectra), _vp, _vp, _vp]),
     "pya_strip_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.POINTER(StripParams),
                                          C.POINTER(TypedSpectra), _vp, _vp, _vp]),
+    "pya_marker_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.POINTER(MarkerParams), _vp, _vp, _vp,
+                                     _vp]),
+    "pya_marker_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.POINTER(MarkerParams), _vp, _vp, _vp]),
     "pya_centroid_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "pya_centroid_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, C.POINTER(CentroidParams), _vp, _vp, C.c_uint64,
                                        C.POINTER(TypedSpectra), _vp, _vp]),

@@ -738,6 +738,71 @@ def centroid(scorer, d_mz, d_intensity, peak_off, params, select=None, out=None)
     return o_mz, o_it, new_off, over
 
 
+def markers(scorer, d_mz, d_intensity, peak_off, params, d_prec_mz=None, d_prec_z=None, out=None):
+    """Looks up the marker ions of spectra that live on the device (``pya_marker_spectra``; the rule is ``pya_marker_params``'s
+    in include/pyascore_hip.h): spectra and ``peak_off`` as ``deisotope`` takes them, ``params`` of
+    ``pyascore_amd.rollup.marker_params``, ``d_prec_mz`` / ``d_prec_z`` the precursor m/z (float64) and charge (int32) of every
+    spectrum as device tensors or host arrays (a host array is uploaded), needed iff ``params`` has loss targets.  ``out``: a
+    pair of contiguous ``uint8`` device tensors ``[n_spectra, n_targets, 24]`` and ``[n_spectra, 32]`` to write into, new when
+    None.  Returns ``(d_markers, d_spectra, d_over)``: the two record tensors (``marker_records`` / ``marker_spectrum_records``
+    read host copies of them) and ``d_over`` as ``deisotope`` returns it (the spectra whose offsets reach beyond the tensors).
+    READ-ONLY: the spectra are not written and nothing needs the result on the host, so the call sits anywhere in a chain of
+    device forms -- in front of ``strip``, to see the peaks it cuts.  One launch on torch's current stream; nothing waits on
+    the host.  ``pyascore_amd.rollup.markers`` gives the same bytes."""
+    import torch
+    from .rollup import MARKER_DTYPE, MARKER_SPECTRUM_DTYPE, marker_c_params
+    c_params, device, peak_off, n_spec = _transform_inputs(scorer, marker_c_params, params, d_mz, d_intensity, peak_off)
+    if (d_prec_mz is None) != (d_prec_z is None) or (d_prec_mz is None and c_params.loss_mask):
+        raise ValueError("d_prec_mz and d_prec_z come together, and loss targets need both")
+    if d_prec_mz is not None:
+        if not isinstance(d_prec_mz, torch.Tensor):
+            d_prec_mz = _upload(d_prec_mz, np.float64, device)
+        if not isinstance(d_prec_z, torch.Tensor):
+            d_prec_z = _upload(d_prec_z, np.int32, device)
+        for t, dtype in ((d_prec_mz, torch.float64), (d_prec_z, torch.int32)):
+            if t.dtype != dtype or tuple(t.shape) != (n_spec,) or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("d_prec_mz (float64) and d_prec_z (int32) are contiguous device tensors with one entry per spectrum")
+    shapes = (n_spec, int(c_params.n_targets), MARKER_DTYPE.itemsize), (n_spec, MARKER_SPECTRUM_DTYPE.itemsize)
+    with torch.cuda.device(device):
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=torch.uint8, device=device) for shape in shapes)
+        over = torch.zeros(2, dtype=torch.int32, device=device)
+    d_markers, d_spectra = out
+    for o, shape in zip(out, shapes):
+        if o.dtype != torch.uint8 or tuple(o.shape) != shape or not o.is_contiguous() or not o.is_cuda:
+            raise ValueError("out must be a pair of contiguous uint8 device tensors of shapes %r and %r" % shapes)
+    t_in = _lib.TypedSpectra(d_mz.data_ptr(), d_intensity.data_ptr(), _lib.spectrum_type(d_mz.dtype), _lib.spectrum_type(d_intensity.dtype))
+    rc = scorer._lib.pya_marker_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_spec, d_mz.numel(),
+                                        None if d_prec_mz is None or not n_spec else d_prec_mz.data_ptr(),
+                                        None if d_prec_z is None or not n_spec else d_prec_z.data_ptr(), C.byref(c_params),
+                                        torch.cuda.current_stream(device).cuda_stream, d_markers.data_ptr() if n_spec else None,
+                                        d_spectra.data_ptr() if n_spec else None, over.data_ptr())
+    if rc:
+        scorer._raise(rc)
+    # (the caching allocator keeps uploaded precursors for this stream until later work on the stream is done with them)
+    return d_markers, d_spectra, over
+
+
+def marker_records(raw):
+    """A host copy of the first tensor of ``markers`` (``.cpu().numpy()``, uint8 ``[n_spectra, n_targets, 24]``) as the
+    structured array ``PyAscore.score_batch(..., markers=...)`` returns in ``markers``; a view, no copy."""
+    from .rollup import MARKER_DTYPE
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 3 or a.shape[2] != MARKER_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n_spectra, n_targets, %d)" % MARKER_DTYPE.itemsize)
+    return a.view(MARKER_DTYPE).reshape(a.shape[0], a.shape[1])
+
+
+def marker_spectrum_records(raw):
+    """A host copy of the second tensor of ``markers`` (``.cpu().numpy()``, uint8 ``[n_spectra, 32]``) as the structured
+    array ``PyAscore.score_batch(..., markers=...)`` returns in ``marker_spectra``; a view, no copy."""
+    from .rollup import MARKER_SPECTRUM_DTYPE
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != MARKER_SPECTRUM_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % MARKER_SPECTRUM_DTYPE.itemsize)
+    return a.view(MARKER_SPECTRUM_DTYPE).reshape(a.shape[0])
+
+
 def evidence_rows(raw):
     """A host copy of ``DevicePlan.evidence()`` (``.cpu().numpy()``, uint8 ``[n_psm, max_k, 16]``) as the structured
     array ``[n_psm, max_k]`` that ``PyAscore.score_batch(..., evidence=True)`` returns; a view, no copy."""

@@ -48,6 +48,13 @@ and of its charge-reduced forms, and the peaks outside an m/z range, removed -- 
 Explained ion current: ``score_batch(coverage=True)`` returns one ``COVERAGE_DTYPE`` record (the 64-byte ``pya_coverage``) per
 PSM; ``coverage`` restates the stage over section-1 ion records and the raw arrays with the sums in the definition's order
 (equal bytes, not close ones) and ``coverage_ratios`` turns records into the four ratios a report shows.
+
+Marker ions: ``marker_params`` checks and fills the parameters of ``pya_marker_params`` (fixed targets -- reporter and
+immonium m/z -- first, precursor losses behind them), ``marker_windows`` gives the windows of a precursor and ``markers`` restates
+the read-only rule -- per (spectrum, target) the most intense peak inside the window, per spectrum the ion current and the base
+peak -- the host form of ``PyAscore.marker_spectra`` / ``pyascore_amd.device.markers`` / ``score_batch(markers=...)``, with the
+same bytes; ``MARKER_DTYPE`` / ``MARKER_SPECTRUM_DTYPE`` are the 24-byte ``pya_marker`` and the 32-byte ``pya_marker_spectrum``
+and ``marker_matrix`` is what a quantification step takes.
 """
 import numpy as np
 
@@ -77,6 +84,11 @@ STRIP_MAX_CHARGE, STRIP_MAX_LOSS, STRIP_MAX_ISOTOPES = _lib.PYA_STRIP_MAX_CHARGE
 STRIP_STEP = _lib.PYA_STRIP_STEP
 STRIP_WINDOWS = STRIP_MAX_CHARGE * (STRIP_MAX_LOSS + 1)     # 64: one bit of ``hit`` each
 CENTROID_MAX_HALF_WIDTH = _lib.PYA_CENTROID_MAX_HALF_WIDTH
+MARKER_DTYPE = np.dtype(_lib.MARKER_DTYPE)          # pya_marker, 24 bytes
+MARKER_SPECTRUM_DTYPE = np.dtype(_lib.MARKER_SPECTRUM_DTYPE)    # pya_marker_spectrum, 32 bytes
+assert MARKER_DTYPE.itemsize == 24 and MARKER_SPECTRUM_DTYPE.itemsize == 32
+MARKER_MAX_TARGETS = _lib.PYA_MARKER_MAX_TARGETS
+MARKER_ACTIVE, MARKER_PICKED = _lib.PYA_MARKER_ACTIVE, _lib.PYA_MARKER_PICKED
 TARGET, DECOY, LEFT_OUT =_lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
@@ -1087,6 +1099,150 @@ def strip(mz, intensity, peak_off, prec_mz, prec_z, params):
     _, kept, new_off = _transform_exit(keep, rel)
     report["n_removed"] = np.diff(rel) - kept
     return raw_mz[keep].copy(), raw_it[keep].copy(), new_off, report
+
+
+def marker_params(mz=(), losses=(), tol=0.0, tol_ppm=0.0):
+    """The parameters of the marker-ion stage (``pya_marker_params``) as a dict: ``value`` the tuple of the fixed targets ``mz``
+    (reporter ions, immonium ions: their m/z) FIRST and the ``losses`` (neutral masses taken off the precursor: 97.976896 for
+    H3PO4, 79.966331 for HPO3) behind them, ``loss_mask`` with bit t set for every loss target, ``tol`` the half width of a window
+    in m/z units and ``tol_ppm`` in ppm of its centre, added to it.  At most 64 targets together and at least one.  ValueError
+    where the library would refuse: a ``tol`` or ``tol_ppm`` that is not finite or negative, a fixed m/z that is not finite and
+    positive, a loss that is not finite or negative, no target or more than 64."""
+    try:
+        mz, losses = tuple(float(v) for v in mz), tuple(float(v) for v in losses)
+    except TypeError:
+        raise ValueError("markers: mz and losses are sequences of numbers") from None
+    n = len(mz) + len(losses)
+    return check_marker_params(dict(tol=tol, tol_ppm=tol_ppm, value=mz + losses, loss_mask=((1 << n) - 1) ^ ((1 << len(mz)) - 1)))
+
+
+def check_marker_params(params):
+    """``params`` (a dict as ``marker_params`` makes it) checked against the conditions of ``pya_marker_params``; returns it
+    with plain Python numbers."""
+    try:
+        out = dict(tol=float(params["tol"]), tol_ppm=float(params["tol_ppm"]), value=tuple(float(v) for v in params["value"]),
+                   loss_mask=params["loss_mask"])
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("markers: params is the dict of pyascore_amd.rollup.marker_params (tol, tol_ppm, value, loss_mask)") from None
+    for name in ("tol", "tol_ppm"):
+        if not (np.isfinite(out[name]) and out[name] >= 0.0):
+            raise ValueError("markers: %s = %r is not a finite number >= 0" % (name, out[name]))
+    n = len(out["value"])
+    if not 1 <= n <= MARKER_MAX_TARGETS:
+        raise ValueError("markers: %d targets are not 1 .. %d" % (n, MARKER_MAX_TARGETS))
+    mask = out["loss_mask"]
+    try:
+        ok = int(mask) == mask and 0 <= int(mask) < (1 << n)
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("markers: loss_mask = %r is not an integer with a bit per loss target and none at or above %d" % (mask, n))
+    out["loss_mask"] = mask = int(mask)
+    for t, v in enumerate(out["value"]):
+        if (mask >> t) & 1:
+            if not (np.isfinite(v) and v >= 0.0):
+                raise ValueError("markers: the loss %r of target %d is not a finite number >= 0" % (v, t))
+        elif not (np.isfinite(v) and v > 0.0):
+            raise ValueError("markers: the m/z %r of target %d is not finite and positive" % (v, t))
+    return out
+
+
+def marker_c_params(params):
+    """``params`` as the ``pya_marker_params`` structure the library reads."""
+    p = check_marker_params(params)
+    value = list(p["value"]) + [0.0] * (MARKER_MAX_TARGETS - len(p["value"]))
+    return _lib.MarkerParams(p["tol"], p["tol_ppm"], (_lib.C.c_double * MARKER_MAX_TARGETS)(*value), p["loss_mask"], len(p["value"]), 0)
+
+
+def marker_windows(prec_mz, prec_z, params):
+    """The windows of ``pya_marker_params`` for precursors ``prec_mz`` (float64) / ``prec_z`` (int32), one per spectrum (or one
+    pair of numbers): ``(centre, lo, hi, active)``, three float64 arrays and a bool array of shape ``[n_spectra, n_targets]``
+    (``[n_targets]`` for one pair) -- the header's operations in float64, one rounding each.  A fixed target is active
+    everywhere; a loss target where the precursor is usable (a charge in 1 .. 8, an m/z that is finite and positive) and its
+    centre finite and positive.  ``centre`` / ``lo`` / ``hi`` are NaN where ``active`` is False."""
+    p = check_marker_params(params)
+    one = np.ndim(prec_mz) == 0
+    pm, pz = _strip_precursors(prec_mz, prec_z, "marker_windows")
+    pm, pz = pm.reshape(-1), pz.reshape(-1)
+    value = np.asarray(p["value"], np.float64)
+    is_loss = ((p["loss_mask"] >> np.arange(value.size, dtype=object)) & 1).astype(bool)
+    has = (pz >= 1) & (pz <= STRIP_MAX_CHARGE) & np.isfinite(pm) & (pm > 0.0)
+    zd = np.where(has, pz, 1).astype(np.float64)
+    with np.errstate(all="ignore"):
+        rel = ((pm * zd)[:, None] - value[None, :]) / zd[:, None]
+        cen = np.where(is_loss[None, :], rel, value[None, :])
+        active = np.where(is_loss[None, :], has[:, None] & np.isfinite(rel) & (rel > 0.0), True)
+        w = np.float64(p["tol"]) + np.float64(p["tol_ppm"] * 1e-6) * cen
+        lo, hi = cen - w, cen + w
+    cen, lo, hi = np.where(active, cen, np.nan), np.where(active, lo, np.nan), np.where(active, hi, np.nan)
+    return (cen[0], lo[0], hi[0], active[0]) if one else (cen, lo, hi, active)
+
+
+def markers(mz, intensity, peak_off, params, prec_mz=None, prec_z=None):
+    """The marker ions of spectra: the rule of ``pya_marker_params``, operation for operation in float64 and plain Python
+    floats, so the bytes are those of ``pya_marker_spectra``.  ``mz`` / ``intensity``: float64 or float32 (widened),
+    ``peak_off[n_spectra + 1]``, ``params`` of ``marker_params``, ``prec_mz`` / ``prec_z`` one precursor m/z and charge per
+    spectrum -- needed iff ``params`` has loss targets.  Per (spectrum, target) the record of the peak the target picks: among
+    the peaks with ``lo <= x <= hi`` whose intensity is a number the most intense, then the one nearest the centre, then the one
+    at the smaller m/z -- an order-free definition --, with the count of ALL peaks inside; per spectrum the ion current (NaN
+    intensities left out; summed in the order of ``pya_coverage``'s sums), the base peak, the peak count, the active targets
+    and the ``hit`` word.  Returns ``(markers, spectra)``: ``MARKER_DTYPE[n_spectra, n_targets]`` and
+    ``MARKER_SPECTRUM_DTYPE[n_spectra]``.  The spectra are only read.  ValueError where ``pya_marker_spectra_host`` returns
+    ``PYA_ERR_ARG``."""
+    p = check_marker_params(params)
+    raw_mz, raw_it, rel = _transform_entry("markers", mz, intensity, peak_off)
+    n_spec, n_t = rel.size - 1, len(p["value"])
+    if prec_mz is None or prec_z is None:
+        if p["loss_mask"]:
+            raise ValueError("markers: loss targets need prec_mz and prec_z, one entry per spectrum")
+        pm, pz = np.full(n_spec, np.nan), np.zeros(n_spec, np.int32)
+    else:
+        pm, pz = _strip_precursors(prec_mz, prec_z, "markers")
+        if pm.shape != (n_spec,):
+            raise ValueError("markers: prec_mz and prec_z have one entry per spectrum")
+    cen, lo, hi, active = marker_windows(pm, pz, p)
+    x, y = raw_mz.astype(np.float64), raw_it.astype(np.float64)
+    rec = np.zeros((n_spec, n_t), MARKER_DTYPE)
+    spec = np.zeros(n_spec, MARKER_SPECTRUM_DTYPE)
+    rec["flags"] = np.where(active, MARKER_ACTIVE, 0)
+    spec["n_peaks"] = np.diff(rel)
+    spec["n_active"] = active.sum(axis=1)
+    for s in np.flatnonzero(np.diff(rel) > 0):
+        xs, ys = x[rel[s]:rel[s + 1]], y[rel[s]:rel[s + 1]]
+        num = ys == ys
+        spec["tic"][s] = _lane_sum(np.where(num, ys, 0.0).tolist())
+        if num.any():
+            spec["base_peak"][s] = ys[num].max() + 0.0
+        ts = np.flatnonzero(active[s])
+        inside = (lo[s, ts][None, :] <= xs[:, None]) & (xs[:, None] <= hi[s, ts][None, :])        # [peaks, active targets]
+        hit = 0
+        for k in np.flatnonzero(inside.any(axis=0)):
+            t = int(ts[k])
+            rec["n_peaks"][s, t] = inside[:, k].sum()
+            at = np.flatnonzero(inside[:, k] & num)
+            if not at.size:
+                continue
+            top = ys[at].max()
+            at = at[ys[at] == top]
+            d = np.abs(xs[at] - cen[s, t])
+            at = at[d == d.min()]
+            rec["mz"][s, t] = xs[at].min() + 0.0
+            rec["intensity"][s, t] = top + 0.0
+            rec["flags"][s, t] |= MARKER_PICKED
+            hit |= 1 << t
+        spec["hit"][s] = np.uint64(hit)
+    return rec, spec
+
+
+def marker_matrix(records, field="intensity"):
+    """``MARKER_DTYPE`` records ``[n_spectra, n_targets]`` as a float64 array of the same shape: ``field`` (``"intensity"``,
+    ``"mz"`` or ``"n_peaks"``) of every target that picked a peak, NaN where none was picked -- what a quantification step
+    takes (the rows of the PSMs behind a roll-up slot are summed or averaged by the caller, in an order of the caller's)."""
+    if field not in ("intensity", "mz", "n_peaks"):
+        raise ValueError("marker_matrix: field is 'intensity', 'mz' or 'n_peaks'")
+    records = np.asarray(records, MARKER_DTYPE)
+    picked = (records["flags"] & MARKER_PICKED) != 0
+    return np.where(picked, records[field].astype(np.float64), np.nan)
 
 
 def centroid_params(gap, gap_ppm=0.0, half_width=4, min_height=0.0, area=False):
