@@ -67,17 +67,24 @@ def tree_digest():
 
 
 def _deps_of(obj):
-    """The files of this repository the compiler read for `obj` (from its -MD output), or None."""
+    """The files of this repository the compiler read for `obj` (from its -MD output), or None.  The list names them by the
+    absolute paths of the tree the object was compiled in; the rule's target, the object itself, tells where that tree lay, so
+    a built tree that was copied or moved since still finds its files (and their bytes are what is compared, as before)."""
     try:
         with open(obj + ".d") as f:
             text = f.read()
     except OSError:
         return None
     words = text.replace("\\\n", " ").split()
+    tail = os.sep + os.path.relpath(obj, ROOT)
+    target = words[0][:-1] if words and words[0].endswith(":") else ""
+    built_in = target[:-len(tail)] if target.endswith(tail) else ROOT
     deps = set()
     for w in words:
         if w.endswith(":"):
             continue
+        if built_in != ROOT and w.startswith(built_in + os.sep):
+            w = ROOT + w[len(built_in):]
         p = os.path.realpath(w)
         if p.startswith(ROOT + os.sep):
             deps.add(p)

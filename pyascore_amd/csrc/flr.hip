@@ -1,56 +1,32 @@
 /* flr.hip -- false-localisation rates over a roll-up table: a global sort of the slots by best_prob and scans over the
  * sorted order, on the table where rollup.hip left it.  The definition is in include/pyascore_hip.h (pya_site_flr); the
  * reference has no counterpart.  The first kernels of this tree that are neither "one PSM per wavefront" nor a scatter of
- * atomics: every launch is a grid over tiles of FL_TILE slots, and KERNEL BOUNDARIES ARE THE ONLY GRID-WIDE SYNCHRONISATION --
+ * atomics: every launch is a grid over tiles of TS_TILE slots, and KERNEL BOUNDARIES ARE THE ONLY GRID-WIDE SYNCHRONISATION --
  * no kernel waits on another workgroup (no look-back, no flag, no cooperative launch), so nothing here can hang a card whose
  * workgroups are not co-resident.  Everything is launched on the caller's stream into the caller's workspace; nothing is
- * allocated and the host waits for nothing.
+ * allocated and the host waits for nothing.  The tile geometry, the block scan, the multi-level scan and the radix sort are
+ * tile_sort.hip.h's, shared with peptidoforms.hip; what a pass and a scan level do is described there.
  *
  *   keys      one thread per slot: key = ~bits(best_prob) of a ranked slot, all-ones otherwise; payload = the slot index, bit
  *             31 set for an unranked slot (n_slots <= 2^31 - 1 leaves the bit free).  p = +0.0 of a ranked slot has the
  *             all-ones key as well, which is why the unranked tail is split off by a pass of its own on that bit and not by
  *             the key.  Counts the ranked slots and the class bytes that are none of 0 / 1 / 2.
- *   sort      a stable LSD radix sort of (key, payload): FL_PASSES = 9 passes, eight over the bytes of the key from the
- *             lowest, the last over payload bit 31.  No pass is skipped.  A pass is three steps:
- *               histogram  per tile, 256 digit counts in LDS -> hist[digit * n_tiles + tile];
- *               scan       the exclusive prefix sum of that array as it lies (digit-major: every smaller digit of every tile,
- *                          then the same digit of the earlier tiles) is the place of a tile's first key of a digit;
- *               scatter    a wave owns 256 consecutive keys of the tile, 64 at a time; the lanes that hold one digit find
- *                          each other with eight ballots, a lane's rank among them is v_mbcnt of that mask, and the wave's
- *                          running count per digit lives in LDS (one wave touches one row: no atomics).  Ranks are in index
- *                          order, so the pass is stable.
+ *   sort      ts_sort over FlKey: (key, payload) in two arrays, FlKey::passes = 9 passes, eight over the bytes of the key from
+ *             the lowest, the last over payload bit 31.
  *   records   over the sorted order: tile sums of (1, decoy, err) -> exclusive scan; then the values at the END of a tie group
  *             reach its members and the running minimum of the decoy ratio reaches every better site by ONE backward scan --
  *             rank strictly rises from one group end to the next, so "the nearest group end at or behind me" is the element
  *             with the smallest rank, a commutative min, and the ratio takes a plain min beside it.  Tile minima -> exclusive
  *             scan (stored back to front) -> the last kernel recomputes both in-tile scans and writes the record of every
  *             slot (zero bytes for an unranked one) and the order.
- * Every multi-workgroup scan is reduce-then-scan with one set of three kernels (fl_reduce / fl_scan_block / fl_apply, 256
- * entries per workgroup) over as many levels as the length needs: 256 * n_tiles histogram entries are two levels from the
- * second tile and three from the 257th.
  * Sums are integers (err is the 2^32-scaled error truncated to a uint64), so no result depends on the order of anything.
  * No write lies outside d_out[0 .. n), d_order[0 .. n), d_n_ranked[0 .. 2) and the workspace bytes fl_layout() counts: every
  * scatter and record store is guarded by its index, and a payload indexes d_out only below n. */
-#include "device_common.hip.h"
-#include "../../include/pyascore_hip.h"
+#include "tile_sort.hip.h"
 
-#define FL_THREADS 256
-#define FL_ITEMS 4
-#define FL_TILE (FL_THREADS * FL_ITEMS)
-#define FL_WAVE_SPAN (64 * FL_ITEMS)          /* consecutive keys of a tile one wave owns */
-#define FL_BINS 256
-#define FL_PASSES 9
 #define FL_UNRANKED 0x80000000u
-static_assert(FL_TILE == PYA_FLR_TILE, "the tile size the header exports");
-static_assert(FL_BINS == FL_THREADS, "one digit per thread where a tile's counts are combined");
 
-/* ---- what is scanned: a type, an identity, a commutative and associative operator ---- */
-struct FlAddU32 {
-    typedef uint32_t T;
-    static DEV T identity() { return 0u; }
-    static DEV T op(T a, T b) { return a + b; }
-    static DEV T shfl_up(T v, int o) { return __shfl_up(v, o, 64); }
-};
+/* ---- what is scanned (both operators commute) ---- */
 /* (1, decoy, err) of the ranked slots: n = count (low word) | decoys (high word), neither reaches 2^31 */
 struct FlSum {
     uint64_t n, err;
@@ -59,7 +35,6 @@ struct FlAddSum {
     typedef FlSum T;
     static DEV T identity() { return FlSum{0ull, 0ull}; }
     static DEV T op(T a, T b) { return FlSum{a.n + b.n, a.err + b.err}; }
-    static DEV T shfl_up(T v, int o) { return FlSum{__shfl_up(v.n, o, 64), __shfl_up(v.err, o, 64)}; }
 };
 /* a group end: key = rank << 32 | n_decoy of the cut, err its error sum, q its decoy ratio; anything else is the identity.
  * op keeps (key, err) of the smaller key -- the nearest end -- and the smaller q */
@@ -74,115 +49,12 @@ struct FlNearestEnd {
         const bool first = a.key <= b.key;
         return FlEnd{first ? a.key : b.key, first ? a.err : b.err, b.q < a.q ? b.q : a.q};
     }
-    static DEV T shfl_up(T v, int o) { return FlEnd{__shfl_up(v.key, o, 64), __shfl_up(v.err, o, 64), __shfl_up(v.q, o, 64)}; }
 };
 
-/* inclusive scan over the 256 threads of a workgroup, thread order; every thread takes part.  lds: 4 entries.  *total: the
- * workgroup's. */
-template <typename S>
-DEV typename S::T fl_block_scan(typename S::T v, typename S::T *lds, typename S::T *total) {
-    typedef typename S::T T;
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = S::shfl_up(v, o);
-        if (lane >= o) v = S::op(y, v);
-    }
-    __syncthreads();                                      /* (lds may still be read from the call before) */
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    T before = S::identity(), all = S::identity();
-#pragma unroll
-    for (int w = 0; w < FL_THREADS / 64; w++) {
-        const T x = lds[w];
-        if (w < wave) before = S::op(before, x);
-        all = S::op(all, x);
-    }
-    *total = all;
-    return S::op(before, v);
-}
-
-/* sums[b] = the entries b * 256 .. of in[n] combined */
-template <typename S>
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_reduce_kernel(const typename S::T *in, uint64_t n, typename S::T *sums) {
-    typedef typename S::T T;
-    __shared__ T lds[FL_THREADS / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * FL_THREADS + threadIdx.x;
-    T total;
-    fl_block_scan<S>(i < n ? in[i] : S::identity(), lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-/* data[n], n <= 256, one workgroup: the exclusive scan in place */
-template <typename S>
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_scan_block_kernel(typename S::T *data, uint32_t n) {
-    typedef typename S::T T;
-    __shared__ T lds[FL_THREADS / 64];
-    const uint32_t i = threadIdx.x;
-    const T v = i < n ? data[i] : S::identity();
-    T total;
-    const T incl = fl_block_scan<S>(v, lds, &total);
-    /* exclusive = everything before me: the inclusive value of the thread before */
-    const T prev = S::shfl_up(incl, 1);
-    __syncthreads();
-    if ((i & 63u) == 63u) lds[i >> 6] = incl;
-    __syncthreads();
-    T ex = (i & 63u) ? prev : (i ? lds[(i >> 6) - 1] : S::identity());
-    if (i < n) data[i] = ex;
-}
-/* data[n] in place: the exclusive scan of every run of 256 entries, started from offs[block] (the scanned sums) */
-template <typename S>
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_apply_kernel(typename S::T *data, uint64_t n, const typename S::T *offs) {
-    typedef typename S::T T;
-    __shared__ T lds[FL_THREADS / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * FL_THREADS + threadIdx.x;
-    const T v = i < n ? data[i] : S::identity();
-    T total;
-    const T incl = fl_block_scan<S>(v, lds, &total);
-    const T prev = S::shfl_up(incl, 1);
-    __syncthreads();
-    if ((threadIdx.x & 63u) == 63u) lds[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    const T ex = (threadIdx.x & 63u) ? prev : (threadIdx.x ? lds[(threadIdx.x >> 6) - 1] : S::identity());
-    if (i < n) data[i] = S::op(offs[blockIdx.x], ex);
-}
-
-/* the number of entries of level l + 1 over a level of n entries */
-static inline uint64_t fl_up(uint64_t n) { return (n + FL_THREADS - 1) / FL_THREADS; }
-/* entries of every level of a scan over n entries together: n + ceil(n / 256) + ... down to a level of at most 256 */
-static uint64_t fl_levels_total(uint64_t n) {
-    uint64_t total = n;
-    while (n > FL_THREADS) {
-        n = fl_up(n);
-        total += n;
-    }
-    return total;
-}
-/* the exclusive scan of data[n] in place; the levels above it follow it in memory (fl_levels_total entries in all) */
-template <typename S>
-static hipError_t fl_scan(typename S::T *data, uint64_t n, hipStream_t st) {
-    typedef typename S::T T;
-    T *level[8];
-    uint64_t len[8];
-    int top = 0;
-    level[0] = data;
-    len[0] = n;
-    while (len[top] > FL_THREADS) {
-        level[top + 1] = level[top] + len[top];
-        len[top + 1] = fl_up(len[top]);
-        top++;                                            /* (2^39 entries would be five levels) */
-    }
-    for (int l = 0; l < top; l++)
-        hipLaunchKernelGGL(pya_flr_reduce_kernel<S>, dim3((uint32_t)len[l + 1]), dim3(FL_THREADS), 0, st, (const T *)level[l], len[l], level[l + 1]);
-    hipLaunchKernelGGL(pya_flr_scan_block_kernel<S>, dim3(1), dim3(FL_THREADS), 0, st, level[top], (uint32_t)len[top]);
-    for (int l = top - 1; l >= 0; l--)
-        hipLaunchKernelGGL(pya_flr_apply_kernel<S>, dim3((uint32_t)len[l + 1]), dim3(FL_THREADS), 0, st, level[l], len[l], (const T *)level[l + 1]);
-    return hipGetLastError();
-}
-
 /* ---- keys ---- */
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_keys_kernel(const uint4 *table, const uint8_t *cls, uint32_t n, uint32_t reported_only,
+__global__ void __launch_bounds__(TS_THREADS) pya_flr_keys_kernel(const uint4 *table, const uint8_t *cls, uint32_t n, uint32_t reported_only,
                                                                   uint64_t *keys, uint32_t *pay, uint32_t *n_ranked) {
-    const uint32_t s = blockIdx.x * FL_THREADS + threadIdx.x;
+    const uint32_t s = blockIdx.x * TS_THREADS + threadIdx.x;
     const bool in = s < n;
     bool ranked = false, bad = false;
     uint64_t bits = 0;
@@ -203,93 +75,27 @@ __global__ void __launch_bounds__(FL_THREADS) pya_flr_keys_kernel(const uint4 *t
     }
 }
 
-/* ---- sort ---- */
-DEV uint32_t fl_digit(uint64_t key, uint32_t pay, int pass) {
-    return pass < 8 ? (uint32_t)(key >> (8 * pass)) & 0xffu : pay >> 31;
-}
-/* the lanes of the wave that are `in` and hold digit d (every lane calls this) */
-DEV uint64_t fl_same_digit(uint32_t d, bool in) {
-    uint64_t m = __ballot(in);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t v = __ballot(bit);
-        m &= bit ? v : ~v;
+/* ---- sort: the key policy ---- */
+struct FlKey {
+    struct E {
+        uint64_t key;
+        uint32_t pay;
+    };
+    struct Buf {
+        uint64_t *keys;
+        uint32_t *pay;
+    };
+    static const int passes = 9;
+    static DEV E none() { return E{0ull, 0u}; }
+    static DEV uint32_t digit(const E &e, int pass) { return pass < 8 ? (uint32_t)(e.key >> (8 * pass)) & 0xffu : e.pay >> 31; }
+    static DEV E load(const Buf &b, uint32_t i) { return E{b.keys[i], b.pay[i]}; }
+    /* only the last pass reads the payload: the other eight histograms move 8 bytes per slot, not 12 */
+    static DEV E load_digit(const Buf &b, uint32_t i, int pass) { return E{b.keys[i], pass == 8 ? b.pay[i] : 0u}; }
+    static DEV void store(const Buf &b, uint32_t i, const E &e) {
+        b.keys[i] = e.key;
+        b.pay[i] = e.pay;
     }
-    return m;
-}
-
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_hist_kernel(const uint64_t *keys, const uint32_t *pay, uint32_t n, uint32_t n_tiles, int pass,
-                                                                  uint32_t *hist) {
-    __shared__ uint32_t cnt[FL_BINS];
-    cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * FL_TILE + (threadIdx.x >> 6) * FL_WAVE_SPAN + (uint32_t)lane_id();
-#pragma unroll
-    for (int r = 0; r < FL_ITEMS; r++) {
-        const uint32_t i = base + r * 64;
-        const bool in = i < n;
-        const uint32_t d = in ? fl_digit(keys[i], pass == 8 ? pay[i] : 0u, pass) : 0u;
-        const uint64_t m = fl_same_digit(d, in);
-        if (in && mask_rank(m) == 0) atomicAdd(&cnt[d], (uint32_t)__popcll(m));
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * n_tiles + blockIdx.x] = cnt[threadIdx.x];
-}
-
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_scatter_kernel(const uint64_t *keys, const uint32_t *pay, uint32_t n, uint32_t n_tiles, int pass,
-                                                                     const uint32_t *offs, uint64_t *keys_out, uint32_t *pay_out) {
-    __shared__ uint32_t cnt[FL_THREADS / 64][FL_BINS];    /* a wave's running count of every digit, then the waves' before it */
-    __shared__ uint32_t first[FL_BINS];                   /* where the tile's first key of a digit goes */
-    const int wave = (int)(threadIdx.x >> 6);
-#pragma unroll
-    for (int w = 0; w < FL_THREADS / 64; w++) cnt[w][threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * FL_TILE + (uint32_t)wave * FL_WAVE_SPAN + (uint32_t)lane_id();
-    uint64_t k[FL_ITEMS];
-    uint32_t p[FL_ITEMS], d[FL_ITEMS], rk[FL_ITEMS];
-#pragma unroll
-    for (int r = 0; r < FL_ITEMS; r++) {
-        const uint32_t i = base + r * 64;
-        const bool in = i < n;
-        k[r] = in ? keys[i] : 0ull;
-        p[r] = in ? pay[i] : 0u;
-    }
-#pragma unroll
-    for (int r = 0; r < FL_ITEMS; r++) {
-        const bool in = base + r * 64 < n;
-        d[r] = in ? fl_digit(k[r], p[r], pass) : 0u;
-        const uint64_t m = fl_same_digit(d[r], in);
-        const uint32_t mine = (uint32_t)mask_rank(m);
-        const uint32_t seen = cnt[wave][d[r]];            /* the row is this wave's alone, and a wave's LDS traffic is in order */
-        rk[r] = seen + mine;
-        wave_lds_sync();
-        if (in && mine == 0u) cnt[wave][d[r]] = seen + (uint32_t)__popcll(m);
-        wave_lds_sync();
-    }
-    __syncthreads();
-    {
-        uint32_t run = 0u;
-#pragma unroll
-        for (int w = 0; w < FL_THREADS / 64; w++) {
-            const uint32_t c = cnt[w][threadIdx.x];
-            cnt[w][threadIdx.x] = run;
-            run += c;
-        }
-        first[threadIdx.x] = offs[(size_t)threadIdx.x * n_tiles + blockIdx.x];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < FL_ITEMS; r++) {
-        if (base + r * 64 < n) {
-            const uint32_t dst = first[d[r]] + cnt[wave][d[r]] + rk[r];
-            if (dst < n) {
-                keys_out[dst] = k[r];
-                pay_out[dst] = p[r];
-            }
-        }
-    }
-}
+};
 
 /* ---- records ---- */
 struct FlRecArgs {
@@ -320,49 +126,48 @@ DEV FlSum fl_element(const FlRecArgs &a, uint32_t i, uint64_t *key, uint32_t *pa
     return FlSum{1ull | decoy << 32, fl_err(~*key)};
 }
 
-/* A thread holds FL_ITEMS CONSECUTIVE positions here (tile * FL_TILE + thread * FL_ITEMS + j): its own run is scanned in
- * registers, the threads' totals by fl_block_scan. */
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_tile_sums_kernel(const FlRecArgs a) {
-    __shared__ FlSum lds[FL_THREADS / 64];
-    const uint32_t i0 = blockIdx.x * FL_TILE + threadIdx.x * FL_ITEMS;
+/* A thread holds TS_ITEMS CONSECUTIVE positions here (tile * TS_TILE + thread * TS_ITEMS + j): its own run is scanned in
+ * registers, the threads' totals by ts_block_scan. */
+__global__ void __launch_bounds__(TS_THREADS) pya_flr_tile_sums_kernel(const FlRecArgs a) {
+    __shared__ FlSum lds[TS_THREADS / 64];
+    const uint32_t i0 = blockIdx.x * TS_TILE + threadIdx.x * TS_ITEMS;
     FlSum mine = FlAddSum::identity();
 #pragma unroll
-    for (int j = 0; j < FL_ITEMS; j++) {
+    for (int j = 0; j < TS_ITEMS; j++) {
         uint64_t key;
         uint32_t pay;
         mine = FlAddSum::op(mine, fl_element(a, i0 + j, &key, &pay));
     }
     FlSum total;
-    fl_block_scan<FlAddSum>(mine, lds, &total);
+    ts_block_scan<FlAddSum>(mine, lds, &total);
     if (threadIdx.x == 0) a.sums[blockIdx.x] = total;
 }
 
-/* the inclusive sums at the thread's FL_ITEMS positions and the group ends among them (identity elsewhere) */
+/* the inclusive sums at the thread's TS_ITEMS positions and the group ends among them (identity elsewhere) */
 DEV void fl_tile_ends(const FlRecArgs &a, FlSum *lds, uint32_t *pay, FlEnd *e) {
-    const uint32_t i0 = blockIdx.x * FL_TILE + threadIdx.x * FL_ITEMS;
-    uint64_t key[FL_ITEMS + 1];
+    const uint32_t i0 = blockIdx.x * TS_TILE + threadIdx.x * TS_ITEMS;
+    uint64_t key[TS_ITEMS + 1];
     uint32_t next_pay;
-    FlSum v[FL_ITEMS], mine = FlAddSum::identity();
+    FlSum v[TS_ITEMS], mine = FlAddSum::identity();
 #pragma unroll
-    for (int j = 0; j < FL_ITEMS; j++) {
+    for (int j = 0; j < TS_ITEMS; j++) {
         v[j] = fl_element(a, i0 + j, &key[j], &pay[j]);
         mine = FlAddSum::op(mine, v[j]);
         v[j] = mine;
     }
     /* the position behind the thread's last: of another thread or another tile */
-    key[FL_ITEMS] = ~0ull;
+    key[TS_ITEMS] = ~0ull;
     next_pay = FL_UNRANKED;
-    if (i0 + FL_ITEMS < a.n) {
-        key[FL_ITEMS] = a.keys[i0 + FL_ITEMS];
-        next_pay = a.pay[i0 + FL_ITEMS];
+    if (i0 + TS_ITEMS < a.n) {
+        key[TS_ITEMS] = a.keys[i0 + TS_ITEMS];
+        next_pay = a.pay[i0 + TS_ITEMS];
     }
     FlSum total;
-    const FlSum incl = fl_block_scan<FlAddSum>(mine, lds, &total);
-    const FlSum before = FlAddSum::op(a.sums[blockIdx.x], FlSum{incl.n - mine.n, incl.err - mine.err});
+    const FlSum before = FlAddSum::op(a.sums[blockIdx.x], ts_block_scan<FlAddSum>(mine, lds, &total));
 #pragma unroll
-    for (int j = 0; j < FL_ITEMS; j++) {
+    for (int j = 0; j < TS_ITEMS; j++) {
         const bool ranked = !(pay[j] & FL_UNRANKED);
-        const bool next_ranked = !((j + 1 < FL_ITEMS ? pay[j + 1] : next_pay) & FL_UNRANKED);
+        const bool next_ranked = !((j + 1 < TS_ITEMS ? pay[j + 1] : next_pay) & FL_UNRANKED);
         e[j] = FlNearestEnd::identity();
         if (ranked && (!next_ranked || key[j + 1] != key[j])) {
             const FlSum c = FlAddSum::op(before, v[j]);
@@ -374,45 +179,45 @@ DEV void fl_tile_ends(const FlRecArgs &a, FlSum *lds, uint32_t *pay, FlEnd *e) {
     }
 }
 
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_tile_ends_kernel(const FlRecArgs a) {
-    __shared__ FlSum lds[FL_THREADS / 64];
-    __shared__ FlEnd lds_e[FL_THREADS / 64];
-    uint32_t pay[FL_ITEMS];
-    FlEnd e[FL_ITEMS], mine = FlNearestEnd::identity();
+__global__ void __launch_bounds__(TS_THREADS) pya_flr_tile_ends_kernel(const FlRecArgs a) {
+    __shared__ FlSum lds[TS_THREADS / 64];
+    __shared__ FlEnd lds_e[TS_THREADS / 64];
+    uint32_t pay[TS_ITEMS];
+    FlEnd e[TS_ITEMS], mine = FlNearestEnd::identity();
     fl_tile_ends(a, lds, pay, e);
 #pragma unroll
-    for (int j = 0; j < FL_ITEMS; j++) mine = FlNearestEnd::op(mine, e[j]);
+    for (int j = 0; j < TS_ITEMS; j++) mine = FlNearestEnd::op(mine, e[j]);
     FlEnd total;
-    fl_block_scan<FlNearestEnd>(mine, lds_e, &total);
+    ts_block_scan<FlNearestEnd>(mine, lds_e, &total);
     if (threadIdx.x == 0) a.ends[a.n_tiles - 1u - blockIdx.x] = total;
 }
 
-__global__ void __launch_bounds__(FL_THREADS) pya_flr_records_kernel(const FlRecArgs a) {
-    __shared__ FlSum lds[FL_THREADS / 64];
-    __shared__ FlEnd lds_e[FL_THREADS / 64];
-    __shared__ FlEnd rev[FL_THREADS];
-    uint32_t pay[FL_ITEMS];
-    FlEnd e[FL_ITEMS];
+__global__ void __launch_bounds__(TS_THREADS) pya_flr_records_kernel(const FlRecArgs a) {
+    __shared__ FlSum lds[TS_THREADS / 64];
+    __shared__ FlEnd lds_e[TS_THREADS / 64];
+    __shared__ FlEnd rev[TS_THREADS];
+    uint32_t pay[TS_ITEMS];
+    FlEnd e[TS_ITEMS];
     fl_tile_ends(a, lds, pay, e);
     /* backward: the thread's own positions from its last to its first, the threads in reverse order */
     FlEnd mine = FlNearestEnd::identity();
 #pragma unroll
-    for (int j = FL_ITEMS - 1; j >= 0; j--) {
+    for (int j = TS_ITEMS - 1; j >= 0; j--) {
         mine = FlNearestEnd::op(mine, e[j]);
         e[j] = mine;                                       /* ends at positions j .. of this thread */
     }
-    rev[FL_THREADS - 1u - threadIdx.x] = mine;
+    rev[TS_THREADS - 1u - threadIdx.x] = mine;
     __syncthreads();
     FlEnd total;
-    const FlEnd incl = fl_block_scan<FlNearestEnd>(rev[threadIdx.x], lds_e, &total);
+    /* the exclusive value of thread t is every end behind thread TS_THREADS - 1 - t in this tile: it goes back to that thread
+     * through rev[t], which no other thread touches between the two barriers */
+    rev[threadIdx.x] = ts_block_scan<FlNearestEnd>(rev[threadIdx.x], lds_e, &total);
     __syncthreads();
-    rev[threadIdx.x] = incl;                               /* rev[t]: the ends of the threads FL_THREADS - 1 - t .. of the tile */
-    __syncthreads();
-    FlEnd behind = a.ends[a.n_tiles - 1u - blockIdx.x];    /* the ends of every later tile */
-    if (threadIdx.x + 1u < FL_THREADS) behind = FlNearestEnd::op(behind, rev[FL_THREADS - 2u - threadIdx.x]);
-    const uint32_t i0 = blockIdx.x * FL_TILE + threadIdx.x * FL_ITEMS;
+    /* the ends of every later tile, then of the later threads of this one */
+    const FlEnd behind = FlNearestEnd::op(a.ends[a.n_tiles - 1u - blockIdx.x], rev[TS_THREADS - 1u - threadIdx.x]);
+    const uint32_t i0 = blockIdx.x * TS_TILE + threadIdx.x * TS_ITEMS;
 #pragma unroll
-    for (int j = 0; j < FL_ITEMS; j++) {
+    for (int j = 0; j < TS_ITEMS; j++) {
         const uint32_t i = i0 + j;
         if (i >= a.n) continue;
         const uint32_t slot = pay[j] & ~FL_UNRANKED;
@@ -437,25 +242,24 @@ struct FlLayout {
     uint64_t keys[2], pay[2], hist, sums, ends, bytes;
     uint32_t n_tiles;
 };
-static uint64_t fl_round(uint64_t b) { return (b + 255u) & ~(uint64_t)255u; }
 static FlLayout fl_layout(uint64_t n) {
     FlLayout L;
-    L.n_tiles = (uint32_t)((n + FL_TILE - 1) / FL_TILE);
+    L.n_tiles = (uint32_t)((n + TS_TILE - 1) / TS_TILE);
     uint64_t at = 0;
     for (int b = 0; b < 2; b++) {
         L.keys[b] = at;
-        at += fl_round(n * sizeof(uint64_t));
+        at += ts_round(n * sizeof(uint64_t));
     }
     for (int b = 0; b < 2; b++) {
         L.pay[b] = at;
-        at += fl_round(n * sizeof(uint32_t));
+        at += ts_round(n * sizeof(uint32_t));
     }
     L.hist = at;
-    at += fl_round(fl_levels_total((uint64_t)FL_BINS * L.n_tiles) * sizeof(uint32_t));
+    at += ts_round(ts_levels_total((uint64_t)TS_BINS * L.n_tiles) * sizeof(uint32_t));
     L.sums = at;
-    at += fl_round(fl_levels_total(L.n_tiles) * sizeof(FlSum));
+    at += ts_round(ts_levels_total(L.n_tiles) * sizeof(FlSum));
     L.ends = at;
-    at += fl_round(fl_levels_total(L.n_tiles) * sizeof(FlEnd));
+    at += ts_round(ts_levels_total(L.n_tiles) * sizeof(FlEnd));
     L.bytes = n ? at : 0;
     return L;
 }
@@ -471,40 +275,25 @@ extern "C" int pya_launch_flr(const void *d_table, uint64_t n_slots, const uint8
     const uint32_t n = (uint32_t)n_slots;
     const FlLayout L = fl_layout(n_slots);
     unsigned char *w = (unsigned char *)d_work;
-    uint64_t *keys[2] = {(uint64_t *)(w + L.keys[0]), (uint64_t *)(w + L.keys[1])};
-    uint32_t *pay[2] = {(uint32_t *)(w + L.pay[0]), (uint32_t *)(w + L.pay[1])};
-    uint32_t *hist = (uint32_t *)(w + L.hist);
-    const uint32_t threads_blocks = (n + FL_THREADS - 1) / FL_THREADS;
+    const FlKey::Buf buf[2] = {{(uint64_t *)(w + L.keys[0]), (uint32_t *)(w + L.pay[0])}, {(uint64_t *)(w + L.keys[1]), (uint32_t *)(w + L.pay[1])}};
+    const uint32_t threads_blocks = (n + TS_THREADS - 1) / TS_THREADS;
     hipError_t e;
     int ph = 0;
-#define FL_PHASE()                                                                \
-    do {                                                                          \
-        if (phase && (e = hipEventRecord(phase[ph++], st)) != hipSuccess) return (int)e; \
-    } while (0)
-    FL_PHASE();
-    hipLaunchKernelGGL(pya_flr_keys_kernel, dim3(threads_blocks), dim3(FL_THREADS), 0, st, (const uint4 *)d_table, d_cls, n, reported_only, keys[0],
-                       pay[0], d_n_ranked);
+    TS_PHASE();
+    hipLaunchKernelGGL(pya_flr_keys_kernel, dim3(threads_blocks), dim3(TS_THREADS), 0, st, (const uint4 *)d_table, d_cls, n, reported_only, buf[0].keys,
+                       buf[0].pay, d_n_ranked);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    int cur = 0;
-    for (int pass = 0; pass < FL_PASSES; pass++) {
-        FL_PHASE();
-        hipLaunchKernelGGL(pya_flr_hist_kernel, dim3(L.n_tiles), dim3(FL_THREADS), 0, st, (const uint64_t *)keys[cur], (const uint32_t *)pay[cur], n,
-                           L.n_tiles, pass, hist);
-        if ((e = fl_scan<FlAddU32>(hist, (uint64_t)FL_BINS * L.n_tiles, st)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(pya_flr_scatter_kernel, dim3(L.n_tiles), dim3(FL_THREADS), 0, st, (const uint64_t *)keys[cur], (const uint32_t *)pay[cur], n,
-                           L.n_tiles, pass, (const uint32_t *)hist, keys[cur ^ 1], pay[cur ^ 1]);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        cur ^= 1;
-    }
-    FL_PHASE();
-    const FlRecArgs a = {keys[cur], pay[cur], d_cls, n, L.n_tiles, (FlSum *)(w + L.sums), (FlEnd *)(w + L.ends), (uint4 *)d_out, d_order};
-    hipLaunchKernelGGL(pya_flr_tile_sums_kernel, dim3(L.n_tiles), dim3(FL_THREADS), 0, st, a);
-    if ((e = fl_scan<FlAddSum>(a.sums, L.n_tiles, st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pya_flr_tile_ends_kernel, dim3(L.n_tiles), dim3(FL_THREADS), 0, st, a);
-    if ((e = fl_scan<FlNearestEnd>(a.ends, L.n_tiles, st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pya_flr_records_kernel, dim3(L.n_tiles), dim3(FL_THREADS), 0, st, a);
+    int cur;
+    if ((e = ts_sort<FlKey>(buf, n, (uint32_t *)(w + L.hist), phase ? phase + ph : nullptr, st, &cur)) != hipSuccess) return (int)e;
+    ph += FlKey::passes;
+    TS_PHASE();
+    const FlRecArgs a = {buf[cur].keys, buf[cur].pay, d_cls, n, L.n_tiles, (FlSum *)(w + L.sums), (FlEnd *)(w + L.ends), (uint4 *)d_out, d_order};
+    hipLaunchKernelGGL(pya_flr_tile_sums_kernel, dim3(L.n_tiles), dim3(TS_THREADS), 0, st, a);
+    if ((e = ts_scan<FlAddSum>(a.sums, L.n_tiles, st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pya_flr_tile_ends_kernel, dim3(L.n_tiles), dim3(TS_THREADS), 0, st, a);
+    if ((e = ts_scan<FlNearestEnd>(a.ends, L.n_tiles, st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pya_flr_records_kernel, dim3(L.n_tiles), dim3(TS_THREADS), 0, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    FL_PHASE();
-#undef FL_PHASE
+    TS_PHASE();
     return 0;
 }

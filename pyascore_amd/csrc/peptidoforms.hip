@@ -2,16 +2,17 @@
  * and the records of earlier lists.  The definition is in include/pyascore_hip.h (pya_peptidoform); the reference has no
  * counterpart.  The second reduction over PSMs of this tree, and unlike rollup.hip its keys are sparse and known only after
  * scoring, so it is sort-and-segment-reduce, not a scatter of atomics.  As in flr.hip every launch is a grid over tiles of
- * PF_TILE entries and KERNEL BOUNDARIES ARE THE ONLY GRID-WIDE SYNCHRONISATION: no kernel waits on another workgroup.
+ * TS_TILE entries and KERNEL BOUNDARIES ARE THE ONLY GRID-WIDE SYNCHRONISATION: no kernel waits on another workgroup.
  * Everything is launched on the caller's stream into the caller's workspace; nothing is allocated and the host waits for
- * nothing.  The stage has a sort and scans of its own (flr.hip's are left as they are).
+ * nothing.  The tile geometry, the block scan, the multi-level scan and the radix sort are tile_sort.hip.h's, shared with
+ * flr.hip; what a pass and a scan level do is described there.
  *
  *   entries   one thread per PSM / per input record: a 48-byte entry (a pya_peptidoform with n_psm == 1 for a PSM) and a
  *             16-byte key (sig_bits low, sig_bits high, group, entry index; bit 31 of the index word set for an entry that
  *             contributes nothing -- n_entries <= 2^31 - 1 leaves the bit free).
- *   sort      a stable LSD radix sort of the keys: PF_PASSES = 13 passes, twelve over the bytes of sig_bits and group from
- *             the lowest, the last over the "nothing" bit, which sends those entries behind every other whatever key they
- *             carry.  No pass is skipped.  A pass is histogram / scan / scatter as flr.hip describes them.
+ *   sort      ts_sort over PfKey: the keys in one array, PfKey::passes = 13 passes, twelve over the bytes of sig_bits and group
+ *             from the lowest, the last over the "nothing" bit, which sends those entries behind every other whatever key they
+ *             carry.
  *   reduce    over the sorted order, a SEGMENTED scan: an element is (value, heads, group heads, flag) with flag set on the
  *             first entry of a key; op(a, b) keeps b's value when b carries a flag and merges the two otherwise.  The value
  *             merge is counts that add, a max / min over bit patterns and a min over ids, so any tree gives the same bytes.
@@ -20,34 +21,18 @@
  *             of its group where n_isomers will go; the first entry of a group stores the number of its first record.
  *   finish    one thread per record below min(count, cap): n_isomers = first record of the next group - first of its own,
  *             three 16-byte stores into d_out.
- * Every multi-workgroup scan is reduce-then-scan (pf_reduce / pf_scan_block / pf_apply, 256 entries per workgroup) over as
- * many levels as the length needs.
  * No write lies outside d_out[0 .. cap), d_n[0 .. 2) and the workspace bytes pf_layout() counts: every scatter, staging and
  * record store is guarded by its index. */
-#include "device_common.hip.h"
-#include "../../include/pyascore_hip.h"
+#include "tile_sort.hip.h"
 
-#define PF_THREADS 256
-#define PF_ITEMS 4
-#define PF_TILE (PF_THREADS * PF_ITEMS)
-#define PF_WAVE_SPAN (64 * PF_ITEMS)          /* consecutive keys of a tile one wave owns */
-#define PF_BINS 256
-#define PF_PASSES 13
 #define PF_NOTHING 0x80000000u
 #define PF_SCORED 1u                          /* PYA_SITE_SCORED */
-static_assert(PF_TILE == PYA_PFORM_TILE, "the tile size the header exports");
-static_assert(PF_BINS == PF_THREADS, "one digit per thread where a tile's counts are combined");
 
 /* the order-preserving image of a float's bits under -NaN < -inf < ... < -0 < +0 < ... < +inf < +NaN, and back */
 DEV uint32_t pf_akey(uint32_t b) { return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }
 DEV uint32_t pf_abits(uint32_t k) { return k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu); }
 
 /* ---- what is scanned ---- */
-struct PfAddU32 {
-    typedef uint32_t T;
-    static DEV T identity() { return 0u; }
-    static DEV T op(T a, T b) { return a + b; }
-};
 /* the fields of a record that are reduced: counts, max prob bits with the smallest id that has them, min z bits, max Ascore key */
 struct PfVal {
     uint64_t prob, z;
@@ -83,109 +68,6 @@ struct PfSegmented {
 };
 static_assert(sizeof(PfState) == 48, "twelve words per scan element");
 
-template <typename T>
-DEV T pf_shfl_up(const T &v, int o) {
-    union U {
-        T t;
-        uint32_t w[sizeof(T) / 4];
-        DEV U() {}
-    } a, r;
-    a.t = v;
-#pragma unroll
-    for (unsigned k = 0; k < sizeof(T) / 4; k++) r.w[k] = __shfl_up(a.w[k], o, 64);
-    return r.t;
-}
-
-/* EXCLUSIVE scan over the 256 threads of a workgroup in thread order (op need not commute); every thread takes part.
- * lds: 4 entries.  *total: the workgroup's. */
-template <typename S>
-DEV typename S::T pf_block_scan(typename S::T v, typename S::T *lds, typename S::T *total) {
-    typedef typename S::T T;
-    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = pf_shfl_up(v, o);
-        if (lane >= o) v = S::op(y, v);
-    }
-    T ex = pf_shfl_up(v, 1);
-    if (lane == 0) ex = S::identity();
-    __syncthreads();                                      /* (lds may still be read from the call before) */
-    if (lane == 63) lds[wave] = v;
-    __syncthreads();
-    T before = S::identity(), all = S::identity();
-#pragma unroll
-    for (int w = 0; w < PF_THREADS / 64; w++) {
-        const T x = lds[w];
-        if (w < wave) before = S::op(before, x);
-        all = S::op(all, x);
-    }
-    *total = all;
-    return S::op(before, ex);
-}
-
-/* sums[b] = the entries b * 256 .. of in[n] combined */
-template <typename S>
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_reduce_kernel(const typename S::T *in, uint64_t n, typename S::T *sums) {
-    typedef typename S::T T;
-    __shared__ T lds[PF_THREADS / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * PF_THREADS + threadIdx.x;
-    T total;
-    pf_block_scan<S>(i < n ? in[i] : S::identity(), lds, &total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-/* data[n], n <= 256, one workgroup: the exclusive scan in place */
-template <typename S>
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_scan_block_kernel(typename S::T *data, uint32_t n) {
-    typedef typename S::T T;
-    __shared__ T lds[PF_THREADS / 64];
-    const uint32_t i = threadIdx.x;
-    T total;
-    const T ex = pf_block_scan<S>(i < n ? data[i] : S::identity(), lds, &total);
-    if (i < n) data[i] = ex;
-}
-/* data[n] in place: the exclusive scan of every run of 256 entries, started from offs[block] (the scanned sums) */
-template <typename S>
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_apply_kernel(typename S::T *data, uint64_t n, const typename S::T *offs) {
-    typedef typename S::T T;
-    __shared__ T lds[PF_THREADS / 64];
-    const uint64_t i = (uint64_t)blockIdx.x * PF_THREADS + threadIdx.x;
-    T total;
-    const T ex = pf_block_scan<S>(i < n ? data[i] : S::identity(), lds, &total);
-    if (i < n) data[i] = S::op(offs[blockIdx.x], ex);
-}
-
-static inline uint64_t pf_up(uint64_t n) { return (n + PF_THREADS - 1) / PF_THREADS; }
-/* entries of every level of a scan over n entries together: n + ceil(n / 256) + ... down to a level of at most 256 */
-static uint64_t pf_levels_total(uint64_t n) {
-    uint64_t total = n;
-    while (n > PF_THREADS) {
-        n = pf_up(n);
-        total += n;
-    }
-    return total;
-}
-/* the exclusive scan of data[n] in place; the levels above it follow it in memory (pf_levels_total entries in all) */
-template <typename S>
-static hipError_t pf_scan(typename S::T *data, uint64_t n, hipStream_t st) {
-    typedef typename S::T T;
-    T *level[8];
-    uint64_t len[8];
-    int top = 0;
-    level[0] = data;
-    len[0] = n;
-    while (len[top] > PF_THREADS) {
-        level[top + 1] = level[top] + len[top];
-        len[top + 1] = pf_up(len[top]);
-        top++;
-    }
-    for (int l = 0; l < top; l++)
-        hipLaunchKernelGGL(pya_pform_reduce_kernel<S>, dim3((uint32_t)len[l + 1]), dim3(PF_THREADS), 0, st, (const T *)level[l], len[l], level[l + 1]);
-    hipLaunchKernelGGL(pya_pform_scan_block_kernel<S>, dim3(1), dim3(PF_THREADS), 0, st, level[top], (uint32_t)len[top]);
-    for (int l = top - 1; l >= 0; l--)
-        hipLaunchKernelGGL(pya_pform_apply_kernel<S>, dim3((uint32_t)len[l + 1]), dim3(PF_THREADS), 0, st, level[l], len[l], (const T *)level[l + 1]);
-    return hipGetLastError();
-}
-
 /* ---- entries ---- */
 struct PfPsmArgs {
     const int64_t *site_off;          /* [n_psm + 1] */
@@ -201,8 +83,8 @@ struct PfPsmArgs {
     uint32_t n_psm, psm_base, max_k;
 };
 
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_psm_entries_kernel(const PfPsmArgs a) {
-    const uint32_t i = blockIdx.x * PF_THREADS + threadIdx.x;
+__global__ void __launch_bounds__(TS_THREADS) pya_pform_psm_entries_kernel(const PfPsmArgs a) {
+    const uint32_t i = blockIdx.x * TS_THREADS + threadIdx.x;
     if (i >= a.n_psm) return;
     const uint4 pp = a.psm_probs[i];
     const int32_t g = a.group[i];
@@ -244,8 +126,8 @@ __global__ void __launch_bounds__(PF_THREADS) pya_pform_psm_entries_kernel(const
 }
 
 /* records src[n] as the entries base .. base + n of the call */
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_rec_entries_kernel(const uint4 *src, uint32_t n, uint32_t base, uint4 *entries, uint4 *keys) {
-    const uint32_t i = blockIdx.x * PF_THREADS + threadIdx.x;
+__global__ void __launch_bounds__(TS_THREADS) pya_pform_rec_entries_kernel(const uint4 *src, uint32_t n, uint32_t base, uint4 *entries, uint4 *keys) {
+    const uint32_t i = blockIdx.x * TS_THREADS + threadIdx.x;
     if (i >= n) return;
     const uint4 q0 = src[(size_t)i * 3], q1 = src[(size_t)i * 3 + 1], q2 = src[(size_t)i * 3 + 2];
     const uint32_t e = base + i;
@@ -255,85 +137,20 @@ __global__ void __launch_bounds__(PF_THREADS) pya_pform_rec_entries_kernel(const
     keys[e] = q0.w ? make_uint4(q0.x, q0.y, q0.z, e) : make_uint4(0u, 0u, 0u, e | PF_NOTHING);
 }
 
-/* ---- sort ---- */
-DEV uint32_t pf_digit(const uint4 &k, int pass) {
-    const uint32_t w = pass < 4 ? k.x : (pass < 8 ? k.y : k.z);
-    return pass < 12 ? (w >> (8 * (pass & 3))) & 0xffu : k.w >> 31;
-}
-/* the lanes of the wave that are `in` and hold digit d (every lane calls this) */
-DEV uint64_t pf_same_digit(uint32_t d, bool in) {
-    uint64_t m = __ballot(in);
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t v = __ballot(bit);
-        m &= bit ? v : ~v;
+/* ---- sort: the key policy ---- */
+struct PfKey {
+    typedef uint4 E;
+    typedef uint4 *Buf;
+    static const int passes = 13;
+    static DEV E none() { return make_uint4(0u, 0u, 0u, 0u); }
+    static DEV uint32_t digit(const E &k, int pass) {
+        const uint32_t w = pass < 4 ? k.x : (pass < 8 ? k.y : k.z);
+        return pass < 12 ? (w >> (8 * (pass & 3))) & 0xffu : k.w >> 31;
     }
-    return m;
-}
-
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_hist_kernel(const uint4 *keys, uint32_t n, uint32_t n_tiles, int pass, uint32_t *hist) {
-    __shared__ uint32_t cnt[PF_BINS];
-    cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * PF_TILE + (threadIdx.x >> 6) * PF_WAVE_SPAN + (uint32_t)lane_id();
-#pragma unroll
-    for (int r = 0; r < PF_ITEMS; r++) {
-        const uint32_t i = base + r * 64;
-        const bool in = i < n;
-        const uint32_t d = in ? pf_digit(keys[i], pass) : 0u;
-        const uint64_t m = pf_same_digit(d, in);
-        if (in && mask_rank(m) == 0) atomicAdd(&cnt[d], (uint32_t)__popcll(m));
-    }
-    __syncthreads();
-    hist[(size_t)threadIdx.x * n_tiles + blockIdx.x] = cnt[threadIdx.x];
-}
-
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_scatter_kernel(const uint4 *keys, uint32_t n, uint32_t n_tiles, int pass, const uint32_t *offs,
-                                                                       uint4 *keys_out) {
-    __shared__ uint32_t cnt[PF_THREADS / 64][PF_BINS];    /* a wave's running count of every digit, then the waves' before it */
-    __shared__ uint32_t first[PF_BINS];                   /* where the tile's first key of a digit goes */
-    const int wave = (int)(threadIdx.x >> 6);
-#pragma unroll
-    for (int w = 0; w < PF_THREADS / 64; w++) cnt[w][threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * PF_TILE + (uint32_t)wave * PF_WAVE_SPAN + (uint32_t)lane_id();
-    uint4 k[PF_ITEMS];
-    uint32_t d[PF_ITEMS], rk[PF_ITEMS];
-#pragma unroll
-    for (int r = 0; r < PF_ITEMS; r++) k[r] = base + r * 64 < n ? keys[base + r * 64] : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int r = 0; r < PF_ITEMS; r++) {
-        const bool in = base + r * 64 < n;
-        d[r] = in ? pf_digit(k[r], pass) : 0u;
-        const uint64_t m = pf_same_digit(d[r], in);
-        const uint32_t mine = (uint32_t)mask_rank(m);
-        const uint32_t seen = cnt[wave][d[r]];            /* the row is this wave's alone, and a wave's LDS traffic is in order */
-        rk[r] = seen + mine;
-        wave_lds_sync();
-        if (in && mine == 0u) cnt[wave][d[r]] = seen + (uint32_t)__popcll(m);
-        wave_lds_sync();
-    }
-    __syncthreads();
-    {
-        uint32_t run = 0u;
-#pragma unroll
-        for (int w = 0; w < PF_THREADS / 64; w++) {
-            const uint32_t c = cnt[w][threadIdx.x];
-            cnt[w][threadIdx.x] = run;
-            run += c;
-        }
-        first[threadIdx.x] = offs[(size_t)threadIdx.x * n_tiles + blockIdx.x];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < PF_ITEMS; r++) {
-        if (base + r * 64 < n) {
-            const uint32_t dst = first[d[r]] + cnt[wave][d[r]] + rk[r];
-            if (dst < n) keys_out[dst] = k[r];
-        }
-    }
-}
+    static DEV E load(Buf b, uint32_t i) { return b[i]; }
+    static DEV E load_digit(Buf b, uint32_t i, int) { return b[i]; }
+    static DEV void store(Buf b, uint32_t i, const E &e) { b[i] = e; }
+};
 
 /* ---- reduce ---- */
 struct PfRedArgs {
@@ -346,20 +163,20 @@ struct PfRedArgs {
     uint32_t *d_n;
 };
 
-/* A thread holds PF_ITEMS CONSECUTIVE sorted positions (tile * PF_TILE + thread * PF_ITEMS + j).  key[0] is the position
- * before its first, key[PF_ITEMS + 1] the one behind its last (the "nothing" key outside 0 .. n); s[j]: the positions as scan
+/* A thread holds TS_ITEMS CONSECUTIVE sorted positions (tile * TS_TILE + thread * TS_ITEMS + j).  key[0] is the position
+ * before its first, key[TS_ITEMS + 1] the one behind its last (the "nothing" key outside 0 .. n); s[j]: the positions as scan
  * elements, combined from the thread's first; returns the thread's total. */
 DEV PfState pf_thread_items(const PfRedArgs &a, uint4 *key, PfState *s) {
-    const uint32_t i0 = blockIdx.x * PF_TILE + threadIdx.x * PF_ITEMS;
+    const uint32_t i0 = blockIdx.x * TS_TILE + threadIdx.x * TS_ITEMS;
 #pragma unroll
-    for (int j = 0; j < PF_ITEMS + 2; j++) {
+    for (int j = 0; j < TS_ITEMS + 2; j++) {
         const uint32_t i = i0 + (uint32_t)j - 1u;          /* (i0 == 0, j == 0 wraps to 0xffffffff >= n) */
         key[j] = make_uint4(0u, 0u, 0u, PF_NOTHING);
         if (i < a.n) key[j] = a.keys[i];
     }
     PfState run = PfSegmented::identity();
 #pragma unroll
-    for (int j = 0; j < PF_ITEMS; j++) {
+    for (int j = 0; j < TS_ITEMS; j++) {
         const uint4 k = key[j + 1], p = key[j];
         PfState e = PfSegmented::identity();
         const uint32_t idx = k.w;
@@ -383,24 +200,24 @@ DEV PfState pf_thread_items(const PfRedArgs &a, uint4 *key, PfState *s) {
     return run;
 }
 
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_tile_totals_kernel(const PfRedArgs a) {
-    __shared__ PfState lds[PF_THREADS / 64];
-    uint4 key[PF_ITEMS + 2];
-    PfState s[PF_ITEMS], total;
+__global__ void __launch_bounds__(TS_THREADS) pya_pform_tile_totals_kernel(const PfRedArgs a) {
+    __shared__ PfState lds[TS_THREADS / 64];
+    uint4 key[TS_ITEMS + 2];
+    PfState s[TS_ITEMS], total;
     const PfState mine = pf_thread_items(a, key, s);
-    pf_block_scan<PfSegmented>(mine, lds, &total);
+    ts_block_scan<PfSegmented>(mine, lds, &total);
     if (threadIdx.x == 0) a.tiles[blockIdx.x] = total;
 }
 
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_stage_kernel(const PfRedArgs a) {
-    __shared__ PfState lds[PF_THREADS / 64];
-    uint4 key[PF_ITEMS + 2];
-    PfState s[PF_ITEMS], total;
+__global__ void __launch_bounds__(TS_THREADS) pya_pform_stage_kernel(const PfRedArgs a) {
+    __shared__ PfState lds[TS_THREADS / 64];
+    uint4 key[TS_ITEMS + 2];
+    PfState s[TS_ITEMS], total;
     const PfState mine = pf_thread_items(a, key, s);
-    const PfState ex = pf_block_scan<PfSegmented>(mine, lds, &total);
+    const PfState ex = ts_block_scan<PfSegmented>(mine, lds, &total);
     const PfState before = PfSegmented::op(a.tiles[blockIdx.x], ex);
 #pragma unroll
-    for (int j = 0; j < PF_ITEMS; j++) {
+    for (int j = 0; j < TS_ITEMS; j++) {
         const uint4 k = key[j + 1], p = key[j], nx = key[j + 2];
         if (k.w & PF_NOTHING) continue;
         const PfState c = PfSegmented::op(before, s[j]);
@@ -421,9 +238,9 @@ __global__ void __launch_bounds__(PF_THREADS) pya_pform_stage_kernel(const PfRed
 }
 
 /* ---- finish ---- */
-__global__ void __launch_bounds__(PF_THREADS) pya_pform_finish_kernel(const uint4 *staged, const uint32_t *grp_first, const uint32_t *d_n, uint32_t n,
+__global__ void __launch_bounds__(TS_THREADS) pya_pform_finish_kernel(const uint4 *staged, const uint32_t *grp_first, const uint32_t *d_n, uint32_t n,
                                                                       uint64_t cap, uint4 *out) {
-    const uint32_t j = blockIdx.x * PF_THREADS + threadIdx.x;
+    const uint32_t j = blockIdx.x * TS_THREADS + threadIdx.x;
     if (j >= n || j >= d_n[0] || (uint64_t)j >= cap) return;
     const uint4 q0 = staged[(size_t)j * 3], q1 = staged[(size_t)j * 3 + 1];
     uint4 q2 = staged[(size_t)j * 3 + 2];
@@ -439,25 +256,24 @@ struct PfLayout {
     uint64_t keys[2], entries, staged, grp_first, hist, tiles, bytes;
     uint32_t n_tiles;
 };
-static uint64_t pf_round(uint64_t b) { return (b + 255u) & ~(uint64_t)255u; }
 static PfLayout pf_layout(uint64_t n) {
     PfLayout L;
-    L.n_tiles = (uint32_t)((n + PF_TILE - 1) / PF_TILE);
+    L.n_tiles = (uint32_t)((n + TS_TILE - 1) / TS_TILE);
     uint64_t at = 0;
     for (int b = 0; b < 2; b++) {
         L.keys[b] = at;
-        at += pf_round(n * sizeof(uint4));
+        at += ts_round(n * sizeof(uint4));
     }
     L.entries = at;
-    at += pf_round(n * 3 * sizeof(uint4));
+    at += ts_round(n * 3 * sizeof(uint4));
     L.staged = at;
-    at += pf_round(n * 3 * sizeof(uint4));
+    at += ts_round(n * 3 * sizeof(uint4));
     L.grp_first = at;
-    at += pf_round((n + 1) * sizeof(uint32_t));
+    at += ts_round((n + 1) * sizeof(uint32_t));
     L.hist = at;
-    at += pf_round(pf_levels_total((uint64_t)PF_BINS * L.n_tiles) * sizeof(uint32_t));
+    at += ts_round(ts_levels_total((uint64_t)TS_BINS * L.n_tiles) * sizeof(uint32_t));
     L.tiles = at;
-    at += pf_round(pf_levels_total(L.n_tiles) * sizeof(PfState));
+    at += ts_round(ts_levels_total(L.n_tiles) * sizeof(PfState));
     L.bytes = n ? at : 0;
     return L;
 }
@@ -480,54 +296,41 @@ extern "C" int pya_launch_pform(const int64_t *d_site_off, uint64_t n_psm, const
     const uint32_t n = (uint32_t)total;
     const PfLayout L = pf_layout(total);
     unsigned char *w = (unsigned char *)d_work;
-    uint4 *keys[2] = {(uint4 *)(w + L.keys[0]), (uint4 *)(w + L.keys[1])};
+    uint4 *const keys[2] = {(uint4 *)(w + L.keys[0]), (uint4 *)(w + L.keys[1])};
     uint4 *entries = (uint4 *)(w + L.entries);
-    uint32_t *hist = (uint32_t *)(w + L.hist);
     hipError_t e;
     int ph = 0;
-#define PF_PHASE()                                                                \
-    do {                                                                          \
-        if (phase && (e = hipEventRecord(phase[ph++], st)) != hipSuccess) return (int)e; \
-    } while (0)
-    PF_PHASE();
+    TS_PHASE();
     uint32_t base = 0;
     if (n_psm) {
         const PfPsmArgs p = {d_site_off, (const uint2 *)d_site_probs, (const uint4 *)d_psm_probs, d_group, d_psm_id, best_sig, (const uint32_t *)ascores,
                              entries, keys[0], d_n, threshold, (uint32_t)n_psm, psm_base, max_k};
-        hipLaunchKernelGGL(pya_pform_psm_entries_kernel, dim3(((uint32_t)n_psm + PF_THREADS - 1) / PF_THREADS), dim3(PF_THREADS), 0, st, p);
+        hipLaunchKernelGGL(pya_pform_psm_entries_kernel, dim3(((uint32_t)n_psm + TS_THREADS - 1) / TS_THREADS), dim3(TS_THREADS), 0, st, p);
         base = (uint32_t)n_psm;
     }
     for (int s = 0; s < 2; s++) {
         if (!n_src[s]) continue;
-        hipLaunchKernelGGL(pya_pform_rec_entries_kernel, dim3((uint32_t)((n_src[s] + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, st,
+        hipLaunchKernelGGL(pya_pform_rec_entries_kernel, dim3((uint32_t)((n_src[s] + TS_THREADS - 1) / TS_THREADS)), dim3(TS_THREADS), 0, st,
                            (const uint4 *)d_src[s], (uint32_t)n_src[s], base, entries, keys[0]);
         base += (uint32_t)n_src[s];
     }
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    PF_PHASE();
-    int cur = 0;
-    for (int pass = 0; pass < PF_PASSES; pass++) {
-        hipLaunchKernelGGL(pya_pform_hist_kernel, dim3(L.n_tiles), dim3(PF_THREADS), 0, st, (const uint4 *)keys[cur], n, L.n_tiles, pass, hist);
-        if ((e = pf_scan<PfAddU32>(hist, (uint64_t)PF_BINS * L.n_tiles, st)) != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(pya_pform_scatter_kernel, dim3(L.n_tiles), dim3(PF_THREADS), 0, st, (const uint4 *)keys[cur], n, L.n_tiles, pass,
-                           (const uint32_t *)hist, keys[cur ^ 1]);
-        if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        cur ^= 1;
-    }
-    PF_PHASE();
+    TS_PHASE();
+    int cur;
+    if ((e = ts_sort<PfKey>(keys, n, (uint32_t *)(w + L.hist), nullptr, st, &cur)) != hipSuccess) return (int)e;
+    TS_PHASE();
     const PfRedArgs a = {keys[cur], entries, n, L.n_tiles, (PfState *)(w + L.tiles), (uint4 *)(w + L.staged), (uint32_t *)(w + L.grp_first), d_n};
-    hipLaunchKernelGGL(pya_pform_tile_totals_kernel, dim3(L.n_tiles), dim3(PF_THREADS), 0, st, a);
-    if ((e = pf_scan<PfSegmented>(a.tiles, L.n_tiles, st)) != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(pya_pform_stage_kernel, dim3(L.n_tiles), dim3(PF_THREADS), 0, st, a);
+    hipLaunchKernelGGL(pya_pform_tile_totals_kernel, dim3(L.n_tiles), dim3(TS_THREADS), 0, st, a);
+    if ((e = ts_scan<PfSegmented>(a.tiles, L.n_tiles, st)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pya_pform_stage_kernel, dim3(L.n_tiles), dim3(TS_THREADS), 0, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-    PF_PHASE();
+    TS_PHASE();
     if (cap) {
         const uint64_t m = total < cap ? total : cap;
-        hipLaunchKernelGGL(pya_pform_finish_kernel, dim3((uint32_t)((m + PF_THREADS - 1) / PF_THREADS)), dim3(PF_THREADS), 0, st,
+        hipLaunchKernelGGL(pya_pform_finish_kernel, dim3((uint32_t)((m + TS_THREADS - 1) / TS_THREADS)), dim3(TS_THREADS), 0, st,
                            (const uint4 *)a.staged, (const uint32_t *)a.grp_first, (const uint32_t *)d_n, n, cap, (uint4 *)d_out);
         if ((e = hipGetLastError()) != hipSuccess) return (int)e;
     }
-    PF_PHASE();
-#undef PF_PHASE
+    TS_PHASE();
     return 0;
 }

@@ -93,6 +93,32 @@ def test_every_object_was_compiled_from_the_files_in_the_tree(lib):
     assert not unused, "in the tree digest but read by no compile: %s" % unused
 
 
+def test_object_records_hold_in_a_copy_of_the_built_tree(lib, tmp_path):
+    """The compiler's dependency lists name files by the absolute paths of the tree the objects were compiled in; a copy of
+    a built tree somewhere else must still find them, in the copy, and judge by their bytes."""
+    import importlib.util
+    import shutil
+    from pyascore_amd import build
+    obj = os.path.join(build.CSRC, "host_flr.cpp.o")
+    deps = build._deps_of(obj)
+    assert len(deps) > 1
+    for p in deps + [obj + ".d", obj + ".flags", build.__file__]:
+        dst = tmp_path / os.path.relpath(p, build.ROOT)
+        dst.parent.mkdir(parents=True, exist_ok=True)
+        shutil.copy(p, dst)
+    spec = importlib.util.spec_from_file_location("moved_build", str(tmp_path / "pyascore_amd" / "build.py"))
+    moved = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(moved)
+    there = os.path.join(moved.CSRC, "host_flr.cpp.o")
+    assert moved.ROOT == os.path.realpath(str(tmp_path)) and there != obj
+    got = moved._deps_of(there)
+    assert [os.path.relpath(p, moved.ROOT) for p in got] == [os.path.relpath(p, build.ROOT) for p in deps]
+    assert open(there + ".flags").read().split("\n")[1] == moved._digest(got)
+    with open(os.path.join(moved.CSRC, "host_flr.cpp"), "a") as f:      # a changed file is still a stale object
+        f.write("\n")
+    assert open(there + ".flags").read().split("\n")[1] != moved._digest(moved._deps_of(there))
+
+
 def test_fails_loudly_without_device(lib):
     import torch
     if torch.cuda.is_available():

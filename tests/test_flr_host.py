@@ -164,3 +164,7 @@ def test_workspace_size_without_a_device():
         b = lib.pya_flr_workspace_bytes(n)
         assert 24 * n <= b <= 32 * n + 16384, (n, b)
     assert lib.pya_flr_workspace_bytes(10 ** 7) < 26 * 10 ** 7
+    # the caller lends the workspace, so its size is public: the values of the library before the sort and the scans moved
+    # into csrc/tile_sort.hip.h (one, two and three scan levels under the histogram)
+    want = {1: 2560, T: 26112, T + 1: 28416, 256 * T + 1: 6567680, 10 ** 7: 250432256}
+    assert {n: lib.pya_flr_workspace_bytes(n) for n in want} == want

@@ -72,3 +72,14 @@ def test_request_checks():
                 dict(group=[0, 1, 2], psm_id=[1, 2]), [0, 1, 2]):
         with pytest.raises(ValueError):
             _peptidoform_request(bad, 3)
+
+
+def test_workspace_size_without_a_device():
+    """The caller lends the workspace, so its size is public: the values of the library before the sort and the scans moved
+    into csrc/tile_sort.hip.h (one, two and three scan levels under the histogram, one and two under the tile totals)."""
+    from pyascore_amd import build
+    build.build()
+    lib = _lib.load()
+    T = _lib.PYA_PFORM_TILE
+    want = {0: 0, 1: 2560, T: 136704, T + 1: 139008, 256 * T + 1: 34881280, 10 ** 7: 1330510848}
+    assert {n: lib.pya_peptidoform_workspace_bytes(n) for n in want} == want
