@@ -118,6 +118,10 @@ extern "C" {
                                 /* (pya_last_batch_coverage), taken on the spectra that were scored -- with                    */
                                 /* PYA_FLAG_RECALIBRATE the corrected copy; it needs no other stage; pya_plan_create*: as      */
                                 /* PYA_FLAG_EVIDENCE (pya_plan_coverage)                                                       */
+#define PYA_FLAG_QUANT 16384u /* pya_score_batch* / pya_score_batch_named: the site quantification of the batch as well, over the */
+                              /* slots of the same call's PYA_FLAG_ROLLUP (without it: PYA_ERR_ARG) and the channel matrix lent   */
+                              /* by pya_set_site_quant (pya_last_batch_site_quant); pya_plan_create*: as PYA_FLAG_EVIDENCE        */
+                              /* (pya_plan_site_quant)                                                                            */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -339,6 +343,50 @@ typedef struct pya_site_rollup {   /* 32 bytes; records compare as raw bytes */
     float best_ascore;             /* max Ascore over those n_in_best records; 0 when n_in_best == 0           */
     uint32_t reserved;             /* 0                                                                        */
 } pya_site_rollup;
+
+/* Site quantification: the roll-up's slots joined with the channel intensities of a labelled experiment (TMT / iTRAQ reporters,
+ * pya_marker above or any matrix of the caller's) -- per slot and channel the summed intensity of the PSMs that place the
+ * modification on the site confidently.  The reference has no counterpart.  Input: the residue records of the probability
+ * stage and best_sig of the results; slot[site_off[n_psm]] exactly as the roll-up takes it; a channel matrix
+ * values[n_rows * n_channels], doubles, row-major, one row per spectrum (or whatever the caller keys rows by); row[n_psm], the
+ * row of every PSM (int32; NULL: PSM i has row row_base + i; negative: the PSM has no channel data and is left out).
+ * A residue record r of PSM p CONTRIBUTES iff the roll-up's rule holds (pya_psm_prob.kind == PYA_SITE_SCORED, slot in
+ * [0, n_slots)), bit r of best_sig[p] is set, with_prob >= threshold (compared as doubles) and the PSM's row is in
+ * [0, n_rows).  A negative slot or a negative row contributes nothing, silently.  A record that meets every other condition
+ * and whose slot is at or above n_slots, or whose row is at or above n_rows, writes nothing and is reported by pya_plan_check
+ * (PYA_ERR_LIMIT), as the roll-up reports its slots.  Two records of one PSM may name one slot: both contribute.
+ * A value v is USABLE iff v == v && v > 0.0: NaN, zeros and negatives are "no reading".  Its QUANTUM q(v): t = v * 2^scale_log2,
+ * one double multiplication by an exactly representable power of two; t >= 281474976710656.0 (2^48, +inf included): q = 2^48
+ * and the reading is SATURATED; otherwise q = (uint64_t)t, by truncation (it may be 0: the reading still counts).  A
+ * contributing record is COMPLETE when all n_channels values of its row are usable.
+ * Per slot, head.n_records counts the contributing records and head.n_complete the complete ones among them.  Per cell
+ * [slot * n_channels + c], over the contributing records whose value in channel c is usable -- with PYA_QUANT_COMPLETE_ONLY:
+ * over the complete records only --: sum is the sum of q, n their number, n_saturated the saturated readings among them.
+ * THE TABLE IS A FUNCTION OF THE MULTISET OF CONTRIBUTING RECORDS (slot, the row's values) AND OF NOTHING ELSE: every field is
+ * an integer sum.  It does not depend on the order of the atomics, on how the records were grouped before they reached memory,
+ * on the route that scored a PSM, on shared or typed input, on chunk cuts, or on whether the PSMs came in one call or were
+ * accumulated over several plans, calls and files.  Two tables over the same slots and channels MERGE BY ADDING EVERY FIELD.
+ * The empty table is all-zero bytes (hipMemsetAsync clears it).  Counts are 32-bit and sums 64-bit, neither checked for
+ * overflow: a reading is at most 2^48, so a sum stays below 2^64 for up to 65 535 contributing records per slot.
+ * csrc/site_quant.hip; the library is built without fast-math. */
+#define PYA_QUANT_COMPLETE_ONLY 1u /* pya_site_quant_params.flags: only complete records are summed */
+#define PYA_QUANT_MAX_CHANNELS 64
+typedef struct pya_site_quant_params {  /* 24 bytes */
+    double threshold;              /* a record contributes when with_prob >= threshold (not a NaN)              */
+    int32_t scale_log2;            /* -64 .. 64: a quantum is 2^-scale_log2 intensity units                     */
+    uint32_t n_channels;           /* 1 .. PYA_QUANT_MAX_CHANNELS: the columns of values and of the table       */
+    uint32_t flags;                /* PYA_QUANT_COMPLETE_ONLY or 0                                              */
+    uint32_t reserved;             /* 0                                                                        */
+} pya_site_quant_params;
+typedef struct pya_site_quant_head {   /* 8 bytes per slot; one 64-bit add */
+    uint32_t n_records;            /* contributing records                                                     */
+    uint32_t n_complete;           /* ... of them whose row has a usable value in every channel                */
+} pya_site_quant_head;
+typedef struct pya_site_quant {    /* 16 bytes per (slot, channel), at [slot * n_channels + c]; two 64-bit adds */
+    uint64_t sum;                  /* sum of q over the summed records with a usable value in this channel     */
+    uint32_t n;                    /* their number                                                             */
+    uint32_t n_saturated;          /* ... of them with q = 2^48                                                */
+} pya_site_quant;
 
 /* Site FLR.  The roll-up says how good every site's best localisation is; this says which sites may be reported at a given
  * false-localisation rate: the slots sorted by best_prob, the expected errors 1 - p accumulated down the list and, with decoy
@@ -1016,6 +1064,21 @@ int pya_set_mz_profile(pya_handle *h, const int32_t *run, uint64_t n_psm, uint64
 /* The table of the last batch call on this handle that was given PYA_FLAG_MZ_PROFILE: out[n_slots], n_slots as lent (anything
  * else: PYA_ERR_ARG).  PYA_ERR_STATE when the last batch was scored without the flag. */
 int pya_last_batch_mz_profile(pya_handle *h, pya_mz_profile *out, uint64_t n_slots);
+/* Lends the library what the NEXT batch call with PYA_FLAG_QUANT quantifies its sites with (pya_site_quant above):
+ * values[n_rows * params->n_channels] and row[n_psm] (or NULL: PSM i of the batch has row i), host memory that must stay valid
+ * until that call returns; params, copied.  The slots and n_slots are those of the same call's PYA_FLAG_ROLLUP
+ * (pya_set_rollup): the flag without PYA_FLAG_ROLLUP is PYA_ERR_ARG with a message.  Lifetime and refusals are
+ * pya_set_mz_profile's: the loan ends with the first batch call with the flag that gets as far as its PSMs, a batch of another
+ * size or a flag without a loan is PYA_ERR_ARG.  The batch call uploads the matrix once, a chunk's slice of row with the chunk,
+ * and runs the stage behind every chunk's roll-up into one device table that lives for the call.  A row at or above n_rows:
+ * PYA_ERR_LIMIT.  PYA_ERR_ARG: n_psm or n_rows above 2^31 - 1, NULL params, NULL values with n_rows != 0, scale_log2 outside
+ * -64 .. 64, n_channels outside 1 .. 64, unknown flag bits, a threshold that is a NaN, reserved != 0. */
+int pya_set_site_quant(pya_handle *h, const double *values, uint64_t n_rows, const int32_t *row, uint64_t n_psm,
+                       const pya_site_quant_params *params);
+/* The table of the last batch call on this handle that was given PYA_FLAG_QUANT: head[n_slots] and cell[n_slots * n_channels],
+ * n_slots and n_channels as lent (anything else: PYA_ERR_ARG, as is a NULL array for a table that has slots).  PYA_ERR_STATE
+ * when the last batch was scored without the flag. */
+int pya_last_batch_site_quant(pya_handle *h, pya_site_quant_head *head, pya_site_quant *cell, uint64_t n_slots, uint32_t n_channels);
 /* The coverage records (pya_coverage above) of the last batch call on this handle that was given PYA_FLAG_COVERAGE: out[n_psm],
  * n_psm as in that call (anything else: PYA_ERR_ARG).  PYA_ERR_STATE when the last batch was scored without the flag.  The
  * record of a PSM that was set aside (PYA_FLAG_SKIP_INVALID) is all zero; records do not depend on the cut into chunks. */
@@ -1167,6 +1230,15 @@ int pya_marker_spectra(pya_handle *h, const pya_typed_spectra *d_in, const int64
 int pya_marker_spectra_host(pya_handle *h, const pya_typed_spectra *in, const int64_t *peak_off, uint64_t n_spectra,
                             const double *prec_mz, const int32_t *prec_z, const pya_marker_params *params,
                             pya_marker *markers, pya_marker_spectrum *spectra, uint32_t *over);
+/* Turns the marker records d_markers[n_spectra * n_targets] (device memory, as pya_marker_spectra wrote them) into the channel
+ * matrix pya_plan_site_quant takes: d_values[n_spectra * popcount(channel_mask)] (device memory, doubles, row-major), the
+ * channels being the targets whose bit of channel_mask is set, in ascending order -- the picked intensity, or a NaN where
+ * PYA_MARKER_PICKED is clear.  One launch of csrc/site_quant.hip on hip_stream, stream-ordered, no host wait, no allocation;
+ * the records are only read and no write lies outside d_values[0 .. n_spectra * popcount(channel_mask)).  PYA_ERR_ARG, with
+ * nothing launched: n_targets outside 1 .. PYA_MARKER_MAX_TARGETS, an empty channel_mask or one with a bit at or above
+ * n_targets, more than 2^32 - 2 spectra, a NULL array.  n_spectra == 0 is a call that writes nothing. */
+int pya_marker_values(pya_handle *h, const pya_marker *d_markers, uint64_t n_spectra, uint32_t n_targets, uint64_t channel_mask,
+                      void *hip_stream, double *d_values);
 /* The device bytes pya_centroid_spectra needs as its workspace for n_spectra spectra of n_peaks points together: what
  * pya_deisotope_workspace_bytes gives (one keep bit per point in 64-bit words that no two spectra share, and the tile sums of
  * the offset scan; 8 bytes at the least).  Centroids are recomputed by the last pass, not stored. */
@@ -1304,6 +1376,22 @@ int pya_plan_ranked(pya_plan *plan, const pya_results *d_res, void *hip_stream, 
 int pya_plan_rollup(pya_plan *plan, const pya_results *d_res, void *hip_stream, const pya_site_prob *d_site_probs,
                     const pya_psm_prob *d_psm_probs, const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id,
                     uint32_t psm_base, pya_site_rollup *d_table);
+/* Adds the channel intensities of this plan's contributing records to the table d_head[n_slots] / d_cell[n_slots *
+ * params->n_channels] (pya_site_quant above; device memory, emptied once by a hipMemsetAsync to 0): the stage ACCUMULATES, so
+ * the same table may take other plans, other runs and other calls.  d_site_probs / d_psm_probs and d_slot as for
+ * pya_plan_rollup; d_values[n_rows * n_channels] device memory; d_row[n_psm] device memory, or NULL: PSM i has row
+ * row_base + i.  It reads best_sig of d_res.  One launch of csrc/site_quant.hip, stream-ordered, no host synchronisation, no
+ * allocation of the caller's and no workspace; waits for the run as pya_plan_rollup does, valid until the plan is run again,
+ * may be called again.  No write ever lies outside d_head[0 .. n_slots) and d_cell[0 .. n_slots * n_channels): a record that
+ * would contribute but whose slot is at or above n_slots or whose row is at or above n_rows writes nothing, and pya_plan_check
+ * reports it (PYA_ERR_LIMIT) until the call is repeated or the plan is run again.  PYA_ERR_ARG, with nothing launched:
+ * parameters outside the conditions of pya_set_site_quant, n_slots or n_rows above 2^31 - 1, NULL where an array is needed;
+ * PYA_ERR_STATE before the plan's first run.  A plan of a handful of PSMs is created with PYA_FLAG_QUANT (or another stage
+ * flag), as for pya_plan_rollup. */
+int pya_plan_site_quant(pya_plan *plan, const pya_results *d_res, void *hip_stream, const pya_site_prob *d_site_probs,
+                        const pya_psm_prob *d_psm_probs, const int32_t *d_slot, uint64_t n_slots, const double *d_values,
+                        uint64_t n_rows, const int32_t *d_row, uint32_t row_base, const pya_site_quant_params *params,
+                        pya_site_quant_head *d_head, pya_site_quant *d_cell);
 /* The peptidoform list (pya_peptidoform above) over this plan's contributing PSMs and the n_prev records of an earlier list
  * d_prev (only read, must not alias d_out; NULL with n_prev == 0): bytewise what one call over all the PSMs behind both would
  * give.  d_site_probs / d_psm_probs as for pya_plan_rollup; d_group[n_psm] device memory; d_psm_id[n_psm] device memory, or

@@ -24,7 +24,9 @@ neutral-loss and charge-reduced forms and the peaks outside an m/z range from ev
 ``--centroid_gap DA``, ``--centroid_gap_ppm PPM``, ``--centroid_width W``, ``--centroid_min_height H`` and ``--centroid_area``
 (peak-pick every spectrum the file does not declare centroided, before anything else) and ``--markers FILE`` with
 ``--marker_mz M1,M2,...``, ``--marker_losses L1,...``, ``--marker_tol DA`` and ``--marker_tol_ppm PPM`` (a table with a line per PSM:
-the intensities of reporter and diagnostic ions in its spectrum, read before anything is stripped) are the additions."""
+the intensities of reporter and diagnostic ions in its spectrum, read before anything is stripped) and ``--site_quant FILE`` with
+``--site_quant_threshold P``, ``--site_quant_scale E`` and ``--site_quant_complete`` (a line per site of ``--site_table``: the
+intensities of the ``--marker_mz`` targets summed over the PSMs that localise the modification there) are the additions."""
 import argparse
 import re
 import sys
@@ -200,6 +202,16 @@ def build_parser():
                    help="with --markers: the half width of a target's window in m/z (default: --mz_error)")
     p.add_argument("--marker_tol_ppm", type=float, default=0.0, metavar="PPM",
                    help="with --markers: ... plus this many ppm of the target's m/z (default 0)")
+    p.add_argument("--site_quant", type=str, default="", metavar="FILE",
+                   help="write the site quantification to FILE: one line per site of --site_table with a contributing PSM, the "
+                        "intensities of the --marker_mz targets summed on the device over the PSMs that place the modification on "
+                        "the site with at least --site_quant_threshold; needs --site_table and --marker_mz")
+    p.add_argument("--site_quant_threshold", type=float, default=0.75, metavar="P",
+                   help="with --site_quant: the localisation probability from which a PSM's reading is summed (default 0.75)")
+    p.add_argument("--site_quant_scale", type=int, default=10, metavar="E",
+                   help="with --site_quant: readings are summed as integers in units of 2^-E (default 10; -64 .. 64)")
+    p.add_argument("--site_quant_complete", action="store_true",
+                   help="with --site_quant: only PSMs with a reading in every channel are summed")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -222,10 +234,27 @@ def strip_request(args):
     return req
 
 
+def site_quant_request(args):
+    """``--site_quant`` as the dict ``batch_cli.localize(site_quant=...)`` takes, checked; None without the option: the other
+    ``--site_quant_*`` values are then not looked at."""
+    if not getattr(args, "site_quant", ""):
+        return None
+    from .rollup import site_quant_params
+    if not args.site_table:
+        raise ValueError("--site_quant sums over the sites of --site_table: give --site_table FILE as well")
+    channels = [v for v in args.marker_mz.split(",") if v.strip()]
+    if not channels:
+        raise ValueError("--site_quant sums the intensities of the --marker_mz targets: give --marker_mz M1,M2,... as well")
+    req = dict(threshold=args.site_quant_threshold, scale_log2=args.site_quant_scale, complete_only=bool(args.site_quant_complete))
+    site_quant_params(n_channels=min(len(channels), 64), **req)
+    return req
+
+
 def markers_request(args):
     """The rule of ``--markers`` as the dict ``batch_cli.localize(markers=...)`` takes (the precursors come from the spectra),
-    checked; None without the option: the other ``--marker_*`` values are then not looked at."""
-    if not getattr(args, "markers", ""):
+    checked; None without the option (and without ``--site_quant``, which reads the same targets): the other ``--marker_*``
+    values are then not looked at."""
+    if not getattr(args, "markers", "") and not getattr(args, "site_quant", ""):
         return None
     from .rollup import marker_params
     lists = {}
@@ -267,6 +296,7 @@ def validate_args(args):
     strip_request(args)
     centroid_request(args)
     markers_request(args)
+    site_quant_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -334,6 +364,8 @@ def run(args, log=print):
                     witness=args.decharge_witness) if args.decharge else None
     markers = markers_request(args)
     marker_rows = [] if markers is not None else None
+    site_quant = site_quant_request(args)
+    site_quant_rows = [] if site_quant is not None else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -347,7 +379,7 @@ def run(args, log=print):
                               peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
                               deisotope=deisotope, decharge=decharge, strip=strip_request(args),
                               centroid=centroid_request(args), coverage=coverage_rows, markers=markers,
-                              marker_rows=marker_rows)
+                              marker_rows=marker_rows, site_quant=site_quant, site_quant_rows=site_quant_rows)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -369,7 +401,9 @@ def run(args, log=print):
         batch_cli.write_ions_tsv(ion_rows, args.ions)
     if coverage_rows is not None:
         batch_cli.write_coverage_tsv(coverage_rows, args.coverage)
-    if marker_rows is not None:
+    if site_quant_rows is not None:
+        batch_cli.write_site_quant_tsv(site_quant_rows, args.site_quant, mz=markers["mz"])
+    if marker_rows is not None and args.markers:
         batch_cli.write_markers_tsv(marker_rows, args.markers, mz=markers["mz"], losses=markers["losses"])
     log("{} -- Ascore Completed".format(stamp()))
     return rows

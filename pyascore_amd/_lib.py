@@ -21,6 +21,9 @@ PYA_FLAG_PEPTIDOFORMS = 1024
 PYA_FLAG_MZ_PROFILE = 2048
 PYA_FLAG_RECALIBRATE = 4096
 PYA_FLAG_COVERAGE = 8192
+PYA_FLAG_QUANT = 16384
+PYA_QUANT_COMPLETE_ONLY = 1
+PYA_QUANT_MAX_CHANNELS = 64
 PYA_COV_NONE, PYA_COV_SCORED = 0, 1
 PYA_MZC_MAX_PPM = 1000       # the largest knot of a pya_mz_calibration, in ppm
 PYA_MZP_BANDS, PYA_MZP_BINS = 8, 64
@@ -161,6 +164,20 @@ class SiteFlr(C.Structure):
 
 
 assert C.sizeof(SiteFlr) == 32, "pya_site_flr is a 32-byte record"
+
+
+class SiteQuantParams(C.Structure):
+    """pya_site_quant_params: the probability a record needs to contribute, the power of two a reading is scaled by, the
+    channels of the matrix and the table, PYA_QUANT_COMPLETE_ONLY or 0"""
+    _fields_ = [("threshold", C.c_double), ("scale_log2", C.c_int32), ("n_channels", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(SiteQuantParams) == 24, "pya_site_quant_params is a 24-byte record"
+SITE_QUANT_HEAD_DTYPE = [("n_records", "<u4"), ("n_complete", "<u4")]
+SITE_QUANT_DTYPE = [("sum", "<u8"), ("n", "<u4"), ("n_saturated", "<u4")]
+
+
 class Peptidoform(C.Structure):
     """pya_peptidoform: one localised peptidoform -- a peptide (the caller's group) with one site assignment: how many PSMs
     report it, how many confidently, the best of their minimum site probabilities and who has it, the best posterior
@@ -360,6 +377,10 @@ SYMBOLS = {
     "pya_set_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _vp]),
     "pya_last_batch_mz_profile": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_plan_mz_profile": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, C.c_uint64, _vp, _vp]),
+    "pya_set_site_quant": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
+    "pya_last_batch_site_quant": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32]),
+    "pya_plan_site_quant": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "pya_marker_values": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp]),
     "pya_last_batch_coverage": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_plan_coverage": (C.c_int, [_vp, C.POINTER(Results), C.POINTER(TypedSpectra), _vp, _vp]),
     "pya_mz_profile_fit": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp]),

@@ -371,6 +371,41 @@ def _rollup_request(rollup, n_psm):
                 psm_id=psm_id, site_off=site_off)
 
 
+def _quant_request(req, n_psm, have_rollup):
+    """``score_batch(quant=...)`` checked: dict(values float64 [n_rows, n_channels], row int32 | None, params, c_params) --
+    ``params`` the dict of ``pyascore_amd.rollup.site_quant_params``"""
+    from .rollup import site_quant_c_params, site_quant_params
+    names = ("values", "row", "threshold", "scale_log2", "complete_only")
+    if not isinstance(req, dict):
+        raise ValueError("quant takes a dict: " + ", ".join(names))
+    unknown = set(req) - set(names)
+    if unknown:
+        raise ValueError("quant takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+    if not have_rollup:
+        raise ValueError("quant needs rollup= in the same call: the channel sums go to the slots of the roll-up")
+    if req.get("values") is None:
+        raise ValueError("quant: values is missing (a float64 matrix, one row per spectrum and one column per channel); only beside "
+                         "markers= it may be None -- the channels are then the fixed targets of markers=")
+    try:
+        values = np.ascontiguousarray(req["values"], np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("quant: values is a matrix of numbers") from None
+    if values.ndim != 2:
+        raise ValueError("quant: values is a matrix, one row per spectrum and one column per channel")
+    if values.shape[0] > 0x7FFFFFFF:
+        raise ValueError("quant: values has more than 2^31 - 1 rows")
+    row = req.get("row")
+    if row is not None:
+        row = np.asarray(row)
+        if row.ndim != 1 or row.size != n_psm or (row.size and row.dtype.kind not in "iu"):
+            raise ValueError("quant: row is one integer per PSM")
+        if row.size and (int(row.max()) > 0x7FFFFFFF or int(row.min()) < -0x80000000):
+            raise ValueError("quant: row does not fit int32")
+        row = np.ascontiguousarray(row, np.int32)
+    params = site_quant_params(req.get("threshold", 0.75), req.get("scale_log2", 10), values.shape[1], req.get("complete_only", False))
+    return dict(values=values, row=row, params=params, c_params=site_quant_c_params(params))
+
+
 class _Last(dict):
     """What the last score() call left: the scalars as they came back, the arrays made from the raw bytes the first
     time something reads them (a loop that only reads best_score never builds them)."""
@@ -604,7 +639,8 @@ class PyAscore:
 
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
-                    recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=False, markers=None):
+                    recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=False, markers=None,
+                    quant=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -758,6 +794,17 @@ class PyAscore:
         uses ``pyascore_amd.device.markers``.  ``pyascore_amd.rollup.markers`` gives the same bytes on the host and
         ``pyascore_amd.rollup.marker_matrix`` the intensities as a matrix.
 
+        ``quant=dict(values=, row=None, threshold=0.75, scale_log2=10, complete_only=False)`` -- beside ``rollup=``, whose slots it
+        uses; without it a ValueError -- adds ``quant_head`` (``pyascore_amd.rollup.SITE_QUANT_HEAD_DTYPE``, shape ``[n_slots]``),
+        ``quant`` (``SITE_QUANT_DTYPE``, shape ``[n_slots, n_channels]``) and ``quant_params``: per slot and channel the summed
+        reading of the PSMs that place the modification on the site with ``with_prob >= threshold`` (``PYA_FLAG_QUANT``,
+        ``pya_site_quant``).  ``values``: float64 ``[n_rows, n_channels]``, one row per spectrum; ``row``: the row of every PSM
+        (negative: left out), None: PSM i has row i.  With ``values=None`` beside ``markers=`` the channels are the fixed targets of
+        ``markers=``, the matrix ``marker_matrix`` of that call's records and ``row`` the batch's ``spec_of`` (the PSM index
+        without one).  The sums are integers in units of ``2^-scale_log2`` (``pyascore_amd.rollup.site_quant_sums`` turns them
+        into intensities), so the table does not depend on chunk cuts, route or order, and tables of several calls merge by
+        adding (``merge_site_quant``); ``pyascore_amd.rollup.site_quant`` gives the same bytes on the host.
+
         ``coverage=True`` adds ``coverage`` (``COVERAGE_DTYPE``, the 64-byte ``pya_coverage``, shape ``[n]``): per PSM the ion
         current of its spectrum and the part of it that the matched fragments of the reported localisation explain, in all and
         from either terminus, beside peak, fragment and bond counts (``pyascore_amd.rollup.coverage_ratios`` makes the ratios,
@@ -769,12 +816,13 @@ class PyAscore:
         ``pya_score_batch_typed``).  float32 -> float64 is exact and the kernels widen at the load, so the results are those
         of the widened arrays, bit for bit.  Any other dtype is converted to float64, as is a float32 m/z array beside
         float64 intensities."""
-        def again(done, spectra):
+        def again(done, spectra, **changed):
             """the call itself on what a transform returned, the transform taken out of the request"""
             rest = dict(keep=keep, skip_invalid=skip_invalid, evidence=evidence, ions=ions, named=named, sites=sites,
                         site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup, peptidoforms=peptidoforms,
                         mz_profile=mz_profile, recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip,
-                        centroid=centroid, coverage=coverage, markers=markers)
+                        centroid=centroid, coverage=coverage, markers=markers, quant=quant)
+            rest.update(changed)
             rest[done] = None
             return self.score_batch(dict(batch, mz=spectra[0], intensity=spectra[1], peak_off=spectra[2]), **rest)
 
@@ -784,7 +832,19 @@ class PyAscore:
         if markers is not None and markers is not False:
             params, prec_mz, prec_z = _markers_request(markers, self._mz_error, _n_spectra(batch))
             records, spectra, _ = self.marker_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), params, prec_mz, prec_z)
-            res = again("markers", (batch["mz"], batch["intensity"], batch["peak_off"]))
+            changed = {}
+            if isinstance(quant, dict) and quant.get("values") is None:
+                # the channels: the fixed targets of markers=; the rows: the spectra
+                from .rollup import marker_matrix
+                fixed = [t for t in range(len(params["value"])) if not (params["loss_mask"] >> t) & 1]
+                if not fixed:
+                    raise ValueError("quant: markers= has no fixed target to take as a channel")
+                values = np.ascontiguousarray(marker_matrix(records)[:, fixed])
+                row = quant.get("row")
+                if row is None and batch.get("spec_of") is not None:
+                    row = np.asarray(batch["spec_of"]).astype(np.int32)
+                changed["quant"] = dict(quant, values=values, row=row)
+            res = again("markers", (batch["mz"], batch["intensity"], batch["peak_off"]), **changed)
             res["markers"], res["marker_spectra"] = records, spectra
             return res
         if strip is not None and strip is not False:
@@ -807,6 +867,7 @@ class PyAscore:
         mzp = None if mz_profile is None or mz_profile is False else _mz_profile_request(mz_profile, int(batch["n_psm"]), self._mz_error,
                                                                                         self._n_top)
         recal = None if recalibrate is None else _recalibrate_request(recalibrate, int(batch["n_psm"]))
+        qu = None if quant is None or quant is False else _quant_request(quant, int(batch["n_psm"]), roll is not None)
         if recal is not None and keep:
             raise ValueError("recalibrate does not go with keep=True: correct the arrays with pyascore_amd.rollup.recalibrate and "
                              "retain the batch without it")
@@ -816,7 +877,7 @@ class PyAscore:
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                         named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup,
-                                        peptidoforms=peptidoforms, mz_profile=mz_profile, coverage=coverage)
+                                        peptidoforms=peptidoforms, mz_profile=mz_profile, coverage=coverage, quant=quant)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -845,6 +906,9 @@ class PyAscore:
                     mzp_moved = dict(mz_profile if isinstance(mz_profile, dict) else {})
                     if mzp["run"] is not None:
                         mzp_moved["run"] = mzp["run"][perm]
+                quant_moved = None
+                if qu is not None:           # the rows travel with their PSMs
+                    quant_moved = dict(quant, values=qu["values"], row=perm.astype(np.int32) if qu["row"] is None else qu["row"][perm])
                 recal_moved = None
                 if recal is not None:        # ... and so do the slots of the calibration
                     recal_moved = dict(calibration=recal["cal"], band_width=recal["band_width"],
@@ -854,7 +918,7 @@ class PyAscore:
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
                                            site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved,
                                            peptidoforms=pform_moved, mz_profile=mzp_moved, recalibrate=recal_moved,
-                                           coverage=coverage)
+                                           coverage=coverage, quant=quant_moved)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
@@ -865,6 +929,7 @@ class PyAscore:
                 forms = res.pop("peptidoforms", None)   # (per peptidoform)
                 profile = res.pop("mz_profile", None)   # (per run slot)
                 profile_params = res.pop("mz_profile_params", None)
+                per_slot = {k: res.pop(k) for k in ("quant_head", "quant", "quant_params") if k in res}   # (per roll-up slot)
                 per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
                 if moved is not None:
@@ -893,6 +958,7 @@ class PyAscore:
                     res["peptidoforms"] = forms
                 if profile is not None:
                     res["mz_profile"], res["mz_profile_params"] = profile, profile_params
+                res.update(per_slot)
                 if res.get("status_message"):
                     res["status_message"] = _renumber_psm(res["status_message"], perm)
                 return res
@@ -957,6 +1023,10 @@ class PyAscore:
                 out["mz_profile_params"] = dict(mzp["params"])
             if coverage:
                 out["coverage"] = np.zeros(0, COVERAGE_DTYPE)
+            if qu is not None:
+                from .rollup import empty_site_quant
+                out["quant_head"], out["quant"] = empty_site_quant(roll["n_slots"], qu["params"]["n_channels"])
+                out["quant_params"] = dict(qu["params"])
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -983,7 +1053,7 @@ class PyAscore:
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0) | \
             (_lib.PYA_FLAG_ROLLUP if roll is not None else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if pform is not None else 0) | \
             (_lib.PYA_FLAG_MZ_PROFILE if mzp is not None else 0) | (_lib.PYA_FLAG_RECALIBRATE if recal is not None else 0) | \
-            (_lib.PYA_FLAG_COVERAGE if coverage else 0)
+            (_lib.PYA_FLAG_COVERAGE if coverage else 0) | (_lib.PYA_FLAG_QUANT if qu is not None else 0)
         # for this call; the handle's own settings come back
         cap_before = k_before = None
         if (sites or probs or ranked_k or roll is not None or pform is not None) and site_sig_cap is not None:
@@ -1003,6 +1073,9 @@ class PyAscore:
             if not rc and recal is not None:
                 rc = self._lib.pya_set_recalibration(self._h, _as_ptr(recal["run"]), n, _as_ptr(recal["cal"]), recal["cal"].size,
                                                      recal["inv_band"])
+            if not rc and qu is not None:
+                rc = self._lib.pya_set_site_quant(self._h, _as_ptr(qu["values"]), qu["values"].shape[0], _as_ptr(qu["row"]), n,
+                                                  C.byref(qu["c_params"]))
             if not rc:
                 rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         finally:
@@ -1063,6 +1136,14 @@ class PyAscore:
             if rc:
                 self._raise(rc)
             out["mz_profile_params"] = dict(mzp["params"])
+        if qu is not None:
+            from .rollup import empty_site_quant
+            out["quant_head"], out["quant"] = empty_site_quant(roll["n_slots"], qu["params"]["n_channels"])
+            rc = self._lib.pya_last_batch_site_quant(self._h, _as_ptr(out["quant_head"]), _as_ptr(out["quant"]), roll["n_slots"],
+                                                     qu["params"]["n_channels"])
+            if rc:
+                self._raise(rc)
+            out["quant_params"] = dict(qu["params"])
         if coverage:
             out["coverage"] = np.zeros(n, COVERAGE_DTYPE)
             rc = self._lib.pya_last_batch_coverage(self._h, _as_ptr(out["coverage"]), n)

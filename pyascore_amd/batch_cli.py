@@ -198,7 +198,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
              recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=None, markers=None,
-             marker_rows=None):
+             marker_rows=None, site_quant=None, site_quant_rows=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -249,7 +249,17 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``markers``: ``dict(mz=, losses=, tol=, tol_ppm=)`` as ``PyAscore.score_batch(markers=...)`` takes it, without the precursors:
     they are the spectra's own (``hit_precursors``), as for ``strip``.  ``marker_rows``: the list that then receives one
     ``[scan] + marker_fields`` row per picked PSM (``write_markers_tsv``): the ion current and the base peak of its spectrum and
-    the peak every target picked in it, read-only and on the spectra ``strip`` is about to cut; the main table does not change."""
+    the peak every target picked in it, read-only and on the spectra ``strip`` is about to cut; the main table does not change.
+    ``site_quant``: ``dict(threshold=, scale_log2=, complete_only=)`` as ``PyAscore.score_batch(quant=...)`` takes it, without a
+    matrix: the channels are the fixed targets of ``markers``, the rows the spectra, the slots those of ``site_table`` -- it
+    needs both.  ``site_quant_rows``: the list that then receives one ``site_quant_fields`` row per site with a contributing
+    record (``write_site_quant_tsv``); no other table changes."""
+    if site_quant is not None:                             # (a bad request is refused before anything is read or scored)
+        if not isinstance(site_quant, dict) or set(site_quant) - {"threshold", "scale_log2", "complete_only"} or site_quant_rows is None:
+            raise ValueError("site_quant takes a dict of threshold, scale_log2 and complete_only beside a list site_quant_rows")
+        if site_table is None or not isinstance(markers, dict) or not tuple(markers.get("mz", ())):
+            raise ValueError("site_quant needs site_table (its slots) and markers with fixed targets mz (its channels)")
+        site_rollup.site_quant_params(n_channels=len(tuple(markers["mz"])), **site_quant)
     if markers is not None:                                # (a bad request is refused before anything is read or scored)
         from .ascore import _markers_request
         if not isinstance(markers, dict) or "precursor_mz" in markers or "precursor_charge" in markers or marker_rows is None:
@@ -311,6 +321,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     if markers is not None:
         prec_mz, prec_z = hit_precursors(picked, scans)
         stages["markers"] = dict(markers, precursor_mz=prec_mz, precursor_charge=prec_z)
+    if site_quant is not None:
+        stages["quant"] = dict(site_quant, values=None)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything
@@ -352,6 +364,9 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         if site_table_flr:
             flr = ascore.rollup_flr(res["rollup"], site_rollup.decoy_classes(keys, decoys=site_table_decoys) if site_table_decoys else None)
         site_table.extend(site_table_fields(row, scans) for row in site_rollup.table(res["rollup"], keys, flr=flr))
+    if site_quant is not None:
+        sums = site_rollup.site_quant_sums(res["quant_head"], res["quant"], res["quant_params"])
+        site_quant_rows.extend(site_quant_fields(keys[s], res["quant_head"][s], sums[s]) for s in np.flatnonzero(res["quant_head"]["n_records"]))
     if mz_profile is not None:
         mz_profile.extend([res["mz_profile"], res["mz_profile_params"]])
     if peptidoform_table is not None:
@@ -434,6 +449,31 @@ def write_site_table_tsv(site_table_rows, path, flr=False):
     with open(path, "w") as out:
         out.write("\t".join(SITE_TABLE_COLUMNS + (SITE_TABLE_FLR_COLUMNS if wide else ())) + "\n")
         for row in site_table_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
+
+
+def site_quant_columns(mz=()):
+    """The header of the ``--site_quant`` table: Peptide, Position, Residue, Records, Complete, then the sum of every channel under
+    the name of its target, ``mz<value>``, in the order of ``--marker_mz``."""
+    return ("Peptide", "Position", "Residue", "Records", "Complete") + tuple("mz%r" % float(v) for v in mz)
+
+
+def site_quant_fields(key, head, sums):
+    """One slot of the site quantification (``pya_site_quant``) keyed by (peptide, position) as the fields of the ``--site_quant``
+    table: Peptide, Position (1-based), Residue, Records -- the records that place the modification on the site at or above the
+    threshold --, Complete -- those of them with a reading in every channel --, then per channel the summed intensity (``repr``),
+    empty where no reading was summed."""
+    peptide, pos = key
+    return [peptide, str(pos), peptide[pos - 1] if 1 <= pos <= len(peptide) else "?", str(int(head["n_records"])), str(int(head["n_complete"]))] + \
+        ["" if v != v else repr(float(v)) for v in sums]
+
+
+def write_site_quant_tsv(site_quant_rows, path, mz=()):
+    """The ``--site_quant`` table: the rows ``localize(..., site_quant=dict(...), site_quant_rows=[])`` collected, under
+    ``site_quant_columns(mz)``."""
+    with open(path, "w") as out:
+        out.write("\t".join(site_quant_columns(mz)) + "\n")
+        for row in site_quant_rows:
             out.write("\t".join("%s" % f for f in row) + "\n")
 
 

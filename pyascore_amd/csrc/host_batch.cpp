@@ -460,6 +460,64 @@ static int mzp_end(pya_handle *h, const pya_handle::MzpLoan &loan) {
     return PYA_OK;
 }
 
+/* PYA_FLAG_QUANT: the loan of pya_set_site_quant becomes the call's; the matrix goes to the device once, the device table that
+ * lives for the call is sized by the roll-up's n_slots and emptied here */
+static int quant_begin(pya_handle *h, pya_handle::QuantLoan *loan, uint64_t n_psm, uint32_t flags, const pya_handle::RollupLoan &ru) {
+    *loan = h->quant_loan;
+    h->quant_loan = pya_handle::QuantLoan{};                  /* (the loan ends with this call, whatever it returns) */
+    if (!(flags & PYA_FLAG_ROLLUP))
+        return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_QUANT without PYA_FLAG_ROLLUP: the quantification uses the slots of the same call's roll-up");
+    if (!loan->set) return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_QUANT without a matrix: call pya_set_site_quant before the batch call");
+    if (loan->n_psm != n_psm)
+        return h->fail(PYA_ERR_ARG, -1, "pya_set_site_quant lent the rows of %llu PSMs, the batch has %llu", (unsigned long long)loan->n_psm,
+                       (unsigned long long)n_psm);
+    const size_t n_ch = loan->params.n_channels, n_cell = (size_t)ru.n_slots * n_ch, n_val = (size_t)loan->n_rows * n_ch;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->d_quant_head.n < ru.n_slots || !h->d_quant_head.p) HIPCHK(h, h->d_quant_head.alloc((size_t)ru.n_slots));
+    if (h->d_quant_cell.n < n_cell || !h->d_quant_cell.p) HIPCHK(h, h->d_quant_cell.alloc(n_cell));
+    if (h->d_quant_values.n < n_val || !h->d_quant_values.p) HIPCHK(h, h->d_quant_values.alloc(n_val));
+    /* (before any stream of the call has work: the chunks' streams do not wait for this one) */
+    if (ru.n_slots) {
+        HIPCHK(h, hipMemsetAsync(h->d_quant_head.p, 0, (size_t)ru.n_slots * sizeof(pya_site_quant_head), nullptr));
+        HIPCHK(h, hipMemsetAsync(h->d_quant_cell.p, 0, n_cell * sizeof(pya_site_quant), nullptr));
+    }
+    if (n_val && n_psm) HIPCHK(h, hipMemcpyAsync(h->d_quant_values.p, loan->values, n_val * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    HIPCHK(h, hipStreamSynchronize(nullptr));
+    return PYA_OK;
+}
+
+/* ... the plan's slice of the caller's rows on its way to the device on `st`, in front of the plan's run as the roll-up's
+ * slots are (rollup_upload says why) */
+static int quant_upload(pya_handle *h, pya_plan *p, const pya_handle::QuantLoan &loan, uint64_t lo, hipStream_t st) {
+    const uint64_t n = p->n_psm;
+    if (n == 0 || !loan.row) return PYA_OK;
+    HIPCHK(h, p->d_quant_row.alloc((size_t)n));
+    HIPCHK(h, hipMemcpyAsync(p->d_quant_row.p, loan.row + lo, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    return PYA_OK;
+}
+
+/* ... the stage of the plan behind its roll-up on `st`: the probability records and the slots are the roll-up's */
+static int quant_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out, const pya_handle::QuantLoan &loan,
+                            const pya_handle::RollupLoan &ru, uint64_t lo, hipStream_t st) {
+    if (p->n_psm == 0 || p->d_rollup_slot.n == 0) return PYA_OK;     /* (rollup_upload: the plan's residue records) */
+    return pya_plan_site_quant(p, d_out, st, p->d_prob_sites.p, p->d_prob_psms.p, p->d_rollup_slot.p, ru.n_slots, h->d_quant_values.p, loan.n_rows,
+                               loan.row ? p->d_quant_row.p : nullptr, (uint32_t)lo, &loan.params, h->d_quant_head.p, h->d_quant_cell.p);
+}
+
+/* ... and the end of the call, when every chunk has been waited for: the table comes to the host */
+static int quant_end(pya_handle *h, const pya_handle::QuantLoan &loan, const pya_handle::RollupLoan &ru) {
+    const size_t n_cell = (size_t)ru.n_slots * loan.params.n_channels;
+    h->quant_head_host.assign((size_t)ru.n_slots, pya_site_quant_head{});
+    h->quant_cell_host.assign(n_cell, pya_site_quant{});
+    if (ru.n_slots) {
+        HIPCHK(h, hipMemcpy(h->quant_head_host.data(), h->d_quant_head.p, (size_t)ru.n_slots * sizeof(pya_site_quant_head), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(h->quant_cell_host.data(), h->d_quant_cell.p, n_cell * sizeof(pya_site_quant), hipMemcpyDeviceToHost));
+    }
+    h->quant_channels = loan.params.n_channels;
+    h->quant_valid = true;
+    return PYA_OK;
+}
+
 /* PYA_FLAG_RECALIBRATE: the loan of pya_set_recalibration becomes the call's.  Everything that can be refused is refused here,
  * before anything is scored: a slot outside the records, PSMs of one spectrum that name different slots.  The slot of every
  * SPECTRUM of the batch is settled once for the whole call (a spectrum whose PSMs a chunk cut separates travels with both
@@ -581,7 +639,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
                                uint32_t flags, const pya_results *out, const std::vector<uint64_t> &cuts,
                                const uint8_t *pre_sites, const NamedReq *nq, const pya_handle::RollupLoan &loan,
                                const pya_handle::PformLoan &pf_loan, const pya_handle::MzpLoan &mzp_loan,
-                               const pya_handle::RecalLoan &recal_loan) {
+                               const pya_handle::RecalLoan &recal_loan, const pya_handle::QuantLoan &quant_loan) {
     const size_t nchunk = cuts.size() - 1;
     const uint64_t n_q = nq ? (uint64_t)nq->q_off[b->n_psm] : 0;
     /* the spectra [first, last) of chunk c: its PSMs' own unless spectra are shared -- then from the first PSM's to the last
@@ -687,6 +745,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_upload(h, p, mzp_loan, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_QUANT) && (rc = quant_upload(h, p, quant_loan, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_RECALIBRATE) && (rc = recal_before_run(h, p, recal_loan, spec_lo(c), sp.mz_type, h->run_stream))) return finish(rc);
         rc = pya_plan_run_typed(p, &d_sp, h->run_stream, &d_out);
         if (rc) return finish(rc);
@@ -710,6 +769,7 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_PROBS) && (rc = probs_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_RANKED) && (rc = ranked_behind_run(h, p, &d_out, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_behind_run(h, p, &d_out, loan, flags, lo, h->run_stream))) return finish(rc);
+        if ((flags & PYA_FLAG_QUANT) && (rc = quant_behind_run(h, p, &d_out, quant_loan, loan, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_behind_run(h, p, &d_out, pf_loan, flags, lo, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_behind_run(h, p, &d_out, mzp_loan, h->run_stream))) return finish(rc);
         if ((flags & PYA_FLAG_COVERAGE) && (rc = coverage_behind_run(h, p, &d_out, &d_sp, lo, h->run_stream))) return finish(rc);
@@ -756,11 +816,13 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_report(p, lo))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_collect(h, p, lo))) return finish(rc);
         if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_report(p, lo))) return finish(rc);
+        if ((flags & PYA_FLAG_QUANT) && (rc = quant_report(p, lo))) return finish(rc);
         cur = std::move(next);
     }
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_end(h, loan))) return finish(rc);
     if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_end(h))) return finish(rc);
     if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_end(h, mzp_loan))) return finish(rc);
+    if ((flags & PYA_FLAG_QUANT) && (rc = quant_end(h, quant_loan, loan))) return finish(rc);
     h->evid_valid = (flags & PYA_FLAG_EVIDENCE) != 0;
     h->cov_valid = (flags & PYA_FLAG_COVERAGE) != 0;
     h->ions_valid = (flags & PYA_FLAG_IONS) != 0;
@@ -786,6 +848,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->rollup_valid = false;
     h->pform_valid = false;
     h->mzp_valid = false;
+    h->quant_valid = false;
     h->cov_valid = false;
     pya_handle::RollupLoan loan;
     if (flags & PYA_FLAG_ROLLUP) {
@@ -801,6 +864,11 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if (flags & PYA_FLAG_MZ_PROFILE) {
         const int rc_mzp = mzp_begin(h, &mzp_loan, b->n_psm);
         if (rc_mzp) return rc_mzp;
+    }
+    pya_handle::QuantLoan quant_loan;
+    if (flags & PYA_FLAG_QUANT) {
+        const int rc_qu = quant_begin(h, &quant_loan, b->n_psm, flags, loan);
+        if (rc_qu) return rc_qu;
     }
     pya_handle::RecalLoan recal_loan;
     if (flags & PYA_FLAG_RECALIBRATE) {
@@ -830,6 +898,10 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         if (flags & PYA_FLAG_MZ_PROFILE) {
             const int rc_mzp = mzp_end(h, mzp_loan);
             if (rc_mzp) return rc_mzp;
+        }
+        if (flags & PYA_FLAG_QUANT) {
+            const int rc_qu = quant_end(h, quant_loan, loan);
+            if (rc_qu) return rc_qu;
         }
         return (flags & PYA_FLAG_ROLLUP) ? rollup_end(h, loan) : PYA_OK;
     }
@@ -882,8 +954,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_rk = ranked_host_block(h, b);
         if (rc_rk) return rc_rk;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS, _MZ_PROFILE, _COVERAGE or _RECALIBRATE takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_RECALIBRATE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS, _MZ_PROFILE, _COVERAGE, _QUANT or _RECALIBRATE takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_QUANT | PYA_FLAG_RECALIBRATE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -926,7 +998,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
             }
             cuts.push_back(b->n_psm);
             h->last_chunks = cuts.size() - 1;
-            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan, pf_loan, mzp_loan, recal_loan);
+            if (cuts.size() > 2) return score_batch_chunked(h, b, sh, sp, flags, out, cuts, cost.sites.data(), nq, loan, pf_loan, mzp_loan, recal_loan, quant_loan);
         }
     }
     const bool host_timing = h->kn.host_timing;
@@ -976,6 +1048,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_upload(h, p, loan, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_upload(h, p, pf_loan, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_upload(h, p, mzp_loan, 0, nullptr))) return rc;
+    if ((flags & PYA_FLAG_QUANT) && (rc = quant_upload(h, p, quant_loan, 0, nullptr))) return rc;
     if ((flags & PYA_FLAG_RECALIBRATE) && (rc = recal_before_run(h, p, recal_loan, 0, sp.mz_type, nullptr))) return rc;
     rc = pya_plan_run_typed(p, &d_sp, nullptr, &d_out);
     if (rc) return rc;
@@ -1041,6 +1114,12 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         if ((rc = rollup_report(p, 0))) return rc;
         if ((rc = rollup_end(h, loan))) return rc;
     }
+    if (flags & PYA_FLAG_QUANT) {
+        if ((rc = quant_behind_run(h, p, &d_out, quant_loan, loan, 0, nullptr))) return rc;
+        HIPCHK(h, hipStreamSynchronize(nullptr));
+        if ((rc = quant_report(p, 0))) return rc;
+        if ((rc = quant_end(h, quant_loan, loan))) return rc;
+    }
     if (flags & PYA_FLAG_PEPTIDOFORMS) {
         if ((rc = pform_behind_run(h, p, &d_out, pf_loan, flags, 0, nullptr))) return rc;
         HIPCHK(h, hipStreamSynchronize(nullptr));
@@ -1084,6 +1163,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->rollup_valid = false;
     h->pform_valid = false;
     h->mzp_valid = false;
+    h->quant_valid = false;
     h->cov_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");

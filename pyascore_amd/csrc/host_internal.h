@@ -144,6 +144,12 @@ int pya_launch_rollup(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec,
                       const int32_t *d_slot, uint64_t n_slots, double threshold, const uint32_t *d_psm_id, uint32_t psm_base,
                       const uint64_t *best_sig, const float *ascores, uint32_t max_k, void *d_table, uint32_t *d_over, uint32_t grid[2],
                       hipStream_t stream);
+int pya_launch_site_quant(const int64_t *d_site_off, uint64_t n_psm, uint64_t n_rec, const void *d_site_probs, const void *d_psm_probs,
+                          const int32_t *d_slot, uint64_t n_slots, const double *d_values, uint64_t n_rows, const int32_t *d_row, uint32_t row_base,
+                          const pya_site_quant_params *prm, double scale, const uint64_t *best_sig, void *d_head, void *d_cell, uint32_t *d_over,
+                          hipStream_t stream);
+int pya_launch_marker_values(const pya_marker *d_markers, uint64_t n_spectra, uint32_t n_targets, uint64_t mask, double *d_values,
+                             hipStream_t stream);
 size_t pya_mz_profile_lds_bytes(uint32_t l_cap);
 int pya_launch_mz_profile(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, const int32_t *d_run, uint64_t n_slots,
                           const pya_mz_profile_params *prm, void *d_table, uint32_t *d_over, uint32_t l_cap, hipStream_t stream);
@@ -446,6 +452,22 @@ struct pya_handle {
     DevBuf<pya_mz_profile> d_mzp;
     std::vector<pya_mz_profile> mzp_host;
     bool mzp_valid = false;
+    /* PYA_FLAG_QUANT: what pya_set_site_quant lent for the next batch call, the device copy of the matrix and the device
+     * table that live for the call (the table zeroed when the call begins) and the table of the last such call on the host */
+    struct QuantLoan {
+        const double *values = nullptr;
+        const int32_t *row = nullptr;
+        uint64_t n_rows = 0, n_psm = 0;
+        pya_site_quant_params params = {};
+        bool set = false;
+    } quant_loan;
+    DevBuf<double> d_quant_values;
+    DevBuf<pya_site_quant_head> d_quant_head;
+    DevBuf<pya_site_quant> d_quant_cell;
+    std::vector<pya_site_quant_head> quant_head_host;
+    std::vector<pya_site_quant> quant_cell_host;
+    uint32_t quant_channels = 0;
+    bool quant_valid = false;
     /* PYA_FLAG_COVERAGE: the records of the last batch call, pinned like the evidence rows so that a chunk's records come
      * back asynchronously behind its results (pya_last_batch_coverage copies them out) */
     pya_coverage *cov_host = nullptr;
@@ -832,6 +854,12 @@ struct pya_plan {
     hipEvent_t ev_mzp = nullptr;
     bool mzp_asked = false;
     DevBuf<int32_t> d_mzp_run;
+    /* pya_plan_site_quant: the report of the last call (records whose slot or row is outside the call's table or matrix), as
+     * for the roll-up; a pya_score_batch plan's slice of the caller's rows */
+    DevBuf<uint32_t> d_quant_over;
+    hipEvent_t ev_quant = nullptr;
+    bool quant_asked = false;
+    DevBuf<int32_t> d_quant_row;
     /* pya_plan_coverage: the raw peak caps of its two launches (the largest spectrum of a PSM inside the fast limits, of a
      * general PSM; once per plan), the event behind the last call's kernels (a later call, on whatever stream, writes
      * behind them) and a pya_score_batch plan's records */
@@ -857,6 +885,7 @@ struct pya_plan {
         if (ev_sites) (void)hipEventDestroy(ev_sites);
         if (ev_rollup) (void)hipEventDestroy(ev_rollup);
         if (ev_mzp) (void)hipEventDestroy(ev_mzp);
+        if (ev_quant) (void)hipEventDestroy(ev_quant);
         if (ev_cov) (void)hipEventDestroy(ev_cov);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
@@ -978,6 +1007,10 @@ int pform_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const vo
  * report of a plan's last pya_plan_mz_profile (psm_lo as for rollup_report) */
 int mzp_check(pya_handle *h, const char *who, uint64_t n_slots, const pya_mz_profile_params *prm);
 int mzp_report(pya_plan *p, uint64_t psm_lo);
+/* host_site_quant.cpp: everything the site quantification calls refuse, before anything is launched; host_run.cpp: the report
+ * of a plan's last pya_plan_site_quant (psm_lo as for rollup_report) */
+int quant_check(pya_handle *h, const char *who, uint64_t n_slots, uint64_t n_rows, const pya_site_quant_params *prm);
+int quant_report(pya_plan *p, uint64_t psm_lo);
 /* host_coverage.cpp: PYA_FLAG_COVERAGE of the batch calls -- the handle's pinned block for the records of a batch of n PSMs
  * (zeroed: a PSM no plan reaches has a PYA_COV_NONE record), and the stage behind a plan's kernels on `st` with its records
  * on their way into the block at PSM `lo` (asynchronous: whoever waits for the chunk's results waits for them too) */
@@ -1064,6 +1097,11 @@ static_assert(sizeof(pya_mz_profile) == 4128 && offsetof(pya_mz_profile, n_ions)
               "pya_mz_profile is the 1 032 words mz_profile.hip flushes");
 static_assert(sizeof(pya_mz_calibration) == 128 && offsetof(pya_mz_calibration, spread_ppm) == 64 && offsetof(pya_mz_calibration, n_signal) == 96,
               "pya_mz_calibration is the 128-byte record mz_calibrate.hip writes");
+static_assert(sizeof(pya_site_quant_params) == 24 && offsetof(pya_site_quant_params, scale_log2) == 8 &&
+                  offsetof(pya_site_quant_params, n_channels) == 12 && offsetof(pya_site_quant_params, flags) == 16 &&
+                  sizeof(pya_site_quant_head) == 8 && offsetof(pya_site_quant_head, n_complete) == 4 && sizeof(pya_site_quant) == 16 &&
+                  offsetof(pya_site_quant, n) == 8 && offsetof(pya_site_quant, n_saturated) == 12,
+              "pya_site_quant_head is one and pya_site_quant two of the 64-bit words site_quant.hip adds to");
 static_assert(sizeof(pya_site_flr) == 32 && offsetof(pya_site_flr, n_decoy) == 4 && offsetof(pya_site_flr, err_sum) == 8 &&
                   offsetof(pya_site_flr, flr) == 16 && offsetof(pya_site_flr, decoy_q) == 24,
               "pya_site_flr is two 16-byte stores of flr.hip");

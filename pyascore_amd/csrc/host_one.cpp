@@ -194,6 +194,7 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
     h->ranked_valid = false;
     h->rollup_valid = false;
     h->mzp_valid = false;
+    h->quant_valid = false;
     h->pform_valid = false;
     h->cov_valid = false;
     if (flags & PYA_FLAG_COVERAGE)
@@ -210,6 +211,8 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_RANKED: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_PEPTIDOFORMS)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_PEPTIDOFORMS: score the PSM as a batch of one (pya_score_batch)");
+    if (flags & PYA_FLAG_QUANT)
+        return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_QUANT: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_MZ_PROFILE)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_MZ_PROFILE: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_RECALIBRATE)

@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_QUANT | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -339,6 +339,7 @@ int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_strea
     p->named_asked = false;
     p->rollup_asked = false;
     p->mzp_asked = false;
+    p->quant_asked = false;
     p->dev = d;
     return rc;
 }
@@ -442,6 +443,19 @@ int mzp_report(pya_plan *p, uint64_t psm_lo) {
                    "the call; nothing of them was written", over[0], (unsigned long long)first);
 }
 
+/* ... and the last pya_plan_site_quant of this run: records whose slot or row is not inside the table or the matrix of the call */
+int quant_report(pya_plan *p, uint64_t psm_lo) {
+    pya_handle *h = p->h;
+    if (!p->quant_asked) return PYA_OK;
+    uint32_t over[2] = {0u, 0u};
+    HIPCHK(h, hipEventSynchronize(p->ev_quant));
+    HIPCHK(h, hipMemcpy(over, p->d_quant_over.p, sizeof(over), hipMemcpyDeviceToHost));
+    if (!over[0]) return PYA_OK;
+    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
+    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_site_quant: %u residue records (PSM %llu the first) name a slot at or above the "
+                   "n_slots or a row at or above the n_rows of the call; nothing of them was written", over[0], (unsigned long long)first);
+}
+
 int pya_plan_check(pya_plan *p) {
     if (!p) return PYA_ERR_ARG;
     pya_handle *h = p->h;
@@ -474,6 +488,8 @@ int pya_plan_check(pya_plan *p) {
     if (rc_ru) return rc_ru;
     const int rc_mzp = mzp_report(p, 0);
     if (rc_mzp) return rc_mzp;
+    const int rc_qu = quant_report(p, 0);
+    if (rc_qu) return rc_qu;
     if (p->ions_state != 2) return PYA_OK;
     /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
     HIPCHK(h, hipEventSynchronize(p->ev_ions));
@@ -858,6 +874,43 @@ int pya_plan_rollup(pya_plan *p, const pya_results *r, void *hip_stream, const p
     h->last_rollup_records = n_rec;
     HIPCHK(h, hipEventRecord(p->ev_rollup, st));
     p->rollup_asked = true;
+    return PYA_OK;
+}
+
+/* The site quantification (csrc/site_quant.hip): the roll-up's wait for the run and its offsets, one launch into the caller's
+ * table; the argument checks are host_site_quant.cpp's, the report of slots and rows outside goes the way of pya_plan_rollup's. */
+int pya_plan_site_quant(pya_plan *p, const pya_results *r, void *hip_stream, const pya_site_prob *d_site_probs, const pya_psm_prob *d_psm_probs,
+                        const int32_t *d_slot, uint64_t n_slots, const double *d_values, uint64_t n_rows, const int32_t *d_row, uint32_t row_base,
+                        const pya_site_quant_params *prm, pya_site_quant_head *d_head, pya_site_quant *d_cell) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    const int rc_arg = quant_check(h, "pya_plan_site_quant", n_slots, n_rows, prm);
+    if (rc_arg) return rc_arg;
+    if (p->n_psm == 0) return PYA_OK;
+    if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_site_quant: the plan has not been run");
+    site_offsets(p);
+    const uint64_t n_rec = (uint64_t)p->site_off[p->n_psm];
+    if (!d_psm_probs || (n_rec && (!d_site_probs || !d_slot)) || (n_slots && (!d_head || !d_cell)) || (n_rows && !d_values) || !r->best_sig)
+        return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_site_quant");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!p->d_quant_over.p) HIPCHK(h, p->d_quant_over.alloc(2));
+    if (!p->ev_quant) HIPCHK(h, hipEventCreateWithFlags(&p->ev_quant, hipEventDisableTiming));
+    if (st != p->last_stream) {                                 /* (behind the run, as pya_plan_rollup waits for it) */
+        if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
+        HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
+    }
+    const int rc_off = site_offsets_on_device(p, st);
+    if (rc_off) return rc_off;
+    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
+    if (p->quant_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_quant, 0));
+    HIPCHK(h, hipMemsetAsync(p->d_quant_over.p, 0, 2 * sizeof(uint32_t), st));
+    const int e = pya_launch_site_quant(p->d_site_off.p, p->n_psm, n_rec, d_site_probs, d_psm_probs, d_slot, n_slots, d_values, n_rows, d_row,
+                                        row_base, prm, std::ldexp(1.0, prm->scale_log2), r->best_sig, d_head, d_cell, p->d_quant_over.p, st);
+    if (e) return h->hip_fail((hipError_t)e, "site quantification launch");
+    HIPCHK(h, hipEventRecord(p->ev_quant, st));
+    p->quant_asked = true;
     return PYA_OK;
 }
 

@@ -33,11 +33,13 @@ class DevicePlan:
     (``pya_plan_peptidoforms``); ``peptidoform_reduce()`` merges such lists.  ``mz_profile()`` / ``mz_profile=True``: the
     fragment mass errors of the reported localisations binned per run slot (``pya_plan_mz_profile``).  ``coverage()`` /
     ``coverage=True``: per PSM the ion current of its spectrum and the part the reported localisation explains (``pya_plan_coverage``).
+    ``site_quant()`` / ``quant=True``: the channel intensities of a device matrix summed per roll-up slot over the confidently
+    localised records (``pya_plan_site_quant``; ``pyascore_amd.device.marker_values`` makes the matrix from marker records).
     ``fit_mz_calibration()`` turns such a table into an m/z calibration and ``recalibrate()`` corrects a device m/z tensor with
     it (``pya_mz_profile_fit``, ``pya_recalibrate_spectra``), so run -> profile -> fit -> correct -> run again needs no host copy."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
-                 ranked=False, rollup=False, peptidoforms=False, mz_profile=False, coverage=False):
+                 ranked=False, rollup=False, peptidoforms=False, mz_profile=False, coverage=False, quant=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -69,7 +71,8 @@ class DevicePlan:
             (_lib.PYA_FLAG_IONS if ions else 0) | (_lib.PYA_FLAG_NAMED if named else 0) | (_lib.PYA_FLAG_SITES if sites else 0) | \
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0) | \
             (_lib.PYA_FLAG_ROLLUP if rollup else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if peptidoforms else 0) | \
-            (_lib.PYA_FLAG_MZ_PROFILE if mz_profile else 0) | (_lib.PYA_FLAG_COVERAGE if coverage else 0)
+            (_lib.PYA_FLAG_MZ_PROFILE if mz_profile else 0) | (_lib.PYA_FLAG_COVERAGE if coverage else 0) | \
+            (_lib.PYA_FLAG_QUANT if quant else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -311,6 +314,50 @@ class DevicePlan:
         rc = self._lib.pya_plan_rollup(self._plan, C.byref(self._res), stream, site_probs.data_ptr(), psm_probs.data_ptr(), slot.data_ptr(),
                                        table.shape[0], float(threshold), None if psm_id is None else psm_id.data_ptr(), int(psm_base),
                                        table.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        return table
+
+    def site_quant(self, site_probs, psm_probs, slot, values, params, n_slots=None, row=None, row_base=0, table=None):
+        """Adds the channel intensities of the contributing records of the last ``run()`` to ``table``
+        (``pya_plan_site_quant``): a pair of ``torch.uint8`` device tensors ``[n_slots, 8]`` and ``[n_slots, n_channels, 16]``
+        (one ``pya_site_quant_head`` per slot, one ``pya_site_quant`` per slot and channel; ``site_quant_records`` turns host
+        copies into the structured arrays), new and zeroed when None -- ``n_slots`` of them.  The stage ACCUMULATES: the same
+        table takes other plans, runs and calls, and an empty table is all-zero bytes.  ``site_probs`` / ``psm_probs``: the
+        two tensors of ``probs()``; ``slot`` as for ``rollup()``; ``values``: contiguous ``torch.float64`` device tensor
+        ``[n_rows, n_channels]``; ``params``: ``pyascore_amd.rollup.site_quant_params(...)``; ``row``: ``torch.int32`` device
+        tensor ``[n_psm]``, the row of every PSM (negative: left out), or None: PSM i has row ``row_base + i``.  One launch on
+        torch's current stream; nothing waits on the host.  A record that would contribute but names a slot or a row outside
+        the table or the matrix writes nothing and is reported by ``check()``.  Returns ``table``."""
+        from .rollup import site_quant_c_params
+        torch = self._torch
+        c_params = site_quant_c_params(params)
+        n_ch = int(c_params.n_channels)
+        n_rec = int(self.site_offsets()[-1])
+        if table is None:
+            if n_slots is None:
+                raise ValueError("site_quant needs a table or n_slots")
+            with torch.cuda.device(self.device):
+                table = (torch.zeros((int(n_slots), 8), dtype=torch.uint8, device=self.device),
+                         torch.zeros((int(n_slots), n_ch, 16), dtype=torch.uint8, device=self.device))
+        head, cell = table
+        if head.dtype != torch.uint8 or head.dim() != 2 or head.shape[1] != 8 or not head.is_contiguous() or not head.is_cuda \
+                or cell.dtype != torch.uint8 or tuple(cell.shape) != (head.shape[0], n_ch, 16) or not cell.is_contiguous() or not cell.is_cuda:
+            raise ValueError("table must be a pair of contiguous uint8 device tensors of shapes (n_slots, 8) and (n_slots, %d, 16)" % n_ch)
+        if slot.dtype != torch.int32 or tuple(slot.shape) != (n_rec,) or not slot.is_contiguous() or not slot.is_cuda:
+            raise ValueError("slot must be a contiguous int32 device tensor of %d entries" % n_rec)
+        if site_probs.dtype != torch.float64 or tuple(site_probs.shape) != (n_rec, 2) or not site_probs.is_contiguous() or not site_probs.is_cuda \
+                or psm_probs.dtype != torch.uint8 or tuple(psm_probs.shape) != (self.n_psm, 16) or not psm_probs.is_contiguous() or not psm_probs.is_cuda:
+            raise ValueError("site_probs and psm_probs must be the tensors of probs()")
+        if values.dtype != torch.float64 or values.dim() != 2 or values.shape[1] != n_ch or not values.is_contiguous() or not values.is_cuda:
+            raise ValueError("values must be a contiguous float64 device tensor of shape (n_rows, %d)" % n_ch)
+        if row is not None and (row.dtype != torch.int32 or tuple(row.shape) != (self.n_psm,) or not row.is_contiguous() or not row.is_cuda):
+            raise ValueError("row must be a contiguous int32 device tensor of %d entries" % self.n_psm)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.pya_plan_site_quant(self._plan, C.byref(self._res), stream, site_probs.data_ptr(), psm_probs.data_ptr(), slot.data_ptr(),
+                                           head.shape[0], values.data_ptr() if values.shape[0] else None, values.shape[0],
+                                           None if row is None else row.data_ptr(), int(row_base), C.byref(c_params),
+                                           head.data_ptr() if head.shape[0] else None, cell.data_ptr() if head.shape[0] else None)
         if rc:
             self.scorer._raise(rc)
         return table
@@ -781,6 +828,50 @@ def markers(scorer, d_mz, d_intensity, peak_off, params, d_prec_mz=None, d_prec_
         scorer._raise(rc)
     # (the caching allocator keeps uploaded precursors for this stream until later work on the stream is done with them)
     return d_markers, d_spectra, over
+
+
+def marker_values(scorer, d_markers, channel_mask=None, out=None):
+    """Marker records that live on the device as the channel matrix ``DevicePlan.site_quant`` takes (``pya_marker_values``):
+    ``d_markers`` the first tensor of ``markers`` (uint8 ``[n_spectra, n_targets, 24]``), ``channel_mask`` an integer with one
+    bit per target that becomes a channel (None: every target), in ascending order.  Returns a ``torch.float64`` device tensor
+    ``[n_spectra, popcount(channel_mask)]``: the picked intensity, NaN where the target picked no peak -- the columns of
+    ``pyascore_amd.rollup.marker_matrix`` the mask names, with the same bytes.  ``out``: such a tensor to write into.  One launch
+    on torch's current stream; nothing waits on the host."""
+    import torch
+    from .rollup import MARKER_DTYPE
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    if d_markers.dtype != torch.uint8 or d_markers.dim() != 3 or d_markers.shape[2] != MARKER_DTYPE.itemsize or not d_markers.is_contiguous() \
+            or not d_markers.is_cuda:
+        raise ValueError("d_markers must be a contiguous uint8 device tensor of shape (n_spectra, n_targets, %d)" % MARKER_DTYPE.itemsize)
+    n_spec, n_t = int(d_markers.shape[0]), int(d_markers.shape[1])
+    mask = (1 << n_t) - 1 if channel_mask is None else int(channel_mask)
+    if not 1 <= n_t <= 64 or mask <= 0 or mask >> n_t:
+        raise ValueError("channel_mask must name at least one of the %d targets and none beyond them" % n_t)
+    shape = (n_spec, bin(mask).count("1"))
+    device = d_markers.device
+    if out is None:
+        with torch.cuda.device(device):
+            out = torch.empty(shape, dtype=torch.float64, device=device)
+    if out.dtype != torch.float64 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("out must be a contiguous float64 device tensor of shape %r" % (shape,))
+    rc = scorer._lib.pya_marker_values(scorer._h, d_markers.data_ptr() if n_spec else None, n_spec, n_t, mask,
+                                       torch.cuda.current_stream(device).cuda_stream, out.data_ptr() if n_spec else None)
+    if rc:
+        scorer._raise(rc)
+    return out
+
+
+def site_quant_records(raw):
+    """Host copies of the table of ``DevicePlan.site_quant`` (``.cpu().numpy()`` of the pair: uint8 ``[n_slots, 8]`` and
+    ``[n_slots, n_channels, 16]``) as the structured arrays ``PyAscore.score_batch(..., quant=...)`` returns in ``quant_head``
+    and ``quant``; views, no copy."""
+    from .rollup import SITE_QUANT_DTYPE, SITE_QUANT_HEAD_DTYPE
+    head, cell = (np.ascontiguousarray(a, np.uint8) for a in raw)
+    if head.ndim != 2 or head.shape[1] != SITE_QUANT_HEAD_DTYPE.itemsize or cell.ndim != 3 or cell.shape[2] != SITE_QUANT_DTYPE.itemsize \
+            or cell.shape[0] != head.shape[0]:
+        raise ValueError("expected uint8 arrays of shapes (n_slots, 8) and (n_slots, n_channels, 16)")
+    return head.view(SITE_QUANT_HEAD_DTYPE).reshape(head.shape[0]), cell.view(SITE_QUANT_DTYPE).reshape(cell.shape[0], cell.shape[1])
 
 
 def marker_records(raw):

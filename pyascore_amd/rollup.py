@@ -55,6 +55,12 @@ the read-only rule -- per (spectrum, target) the most intense peak inside the wi
 peak -- the host form of ``PyAscore.marker_spectra`` / ``pyascore_amd.device.markers`` / ``score_batch(markers=...)``, with the
 same bytes; ``MARKER_DTYPE`` / ``MARKER_SPECTRUM_DTYPE`` are the 24-byte ``pya_marker`` and the 32-byte ``pya_marker_spectrum``
 and ``marker_matrix`` is what a quantification step takes.
+
+Site quantification: ``score_batch(rollup=..., quant=...)`` returns per roll-up slot and channel the summed intensity of the PSMs
+that place the modification on the site confidently (``SITE_QUANT_HEAD_DTYPE`` / ``SITE_QUANT_DTYPE``, the 8-byte
+``pya_site_quant_head`` and the 16-byte ``pya_site_quant``); ``site_quant_params`` checks and fills the parameters,
+``site_quant`` restates the stage over the probability records with integer sums (equal bytes), ``merge_site_quant`` adds tables
+and ``site_quant_sums`` turns one into intensities.
 """
 import numpy as np
 
@@ -89,6 +95,10 @@ MARKER_SPECTRUM_DTYPE = np.dtype(_lib.MARKER_SPECTRUM_DTYPE)    # pya_marker_spe
 assert MARKER_DTYPE.itemsize == 24 and MARKER_SPECTRUM_DTYPE.itemsize == 32
 MARKER_MAX_TARGETS = _lib.PYA_MARKER_MAX_TARGETS
 MARKER_ACTIVE, MARKER_PICKED = _lib.PYA_MARKER_ACTIVE, _lib.PYA_MARKER_PICKED
+SITE_QUANT_HEAD_DTYPE = np.dtype(_lib.SITE_QUANT_HEAD_DTYPE)   # pya_site_quant_head, 8 bytes
+SITE_QUANT_DTYPE = np.dtype(_lib.SITE_QUANT_DTYPE)             # pya_site_quant, 16 bytes
+assert SITE_QUANT_HEAD_DTYPE.itemsize == 8 and SITE_QUANT_DTYPE.itemsize == 16
+QUANT_MAX_CHANNELS = _lib.PYA_QUANT_MAX_CHANNELS
 TARGET, DECOY, LEFT_OUT =_lib.PYA_FLR_TARGET, _lib.PYA_FLR_DECOY, _lib.PYA_FLR_LEFT_OUT
 
 
@@ -1366,3 +1376,143 @@ def centroid(mz, intensity, peak_off, params, select=None):
         with np.errstate(over="ignore"):
             out_it[pos] = sw.astype(raw_it.dtype)
     return out_mz, out_it, new_off, unordered
+
+
+def site_quant_params(threshold=0.75, scale_log2=10, n_channels=None, complete_only=False):
+    """The parameters of the site quantification (``pya_site_quant_params``) as a dict: ``threshold`` the localisation
+    probability a record needs to contribute, ``scale_log2`` the power of two a reading is multiplied by before it is
+    truncated to an integer -- the default 10 is a choice, not a measurement: about 1e-3 intensity units of resolution and
+    2^38 per reading before it saturates --, ``n_channels`` the columns of the matrix (1 .. 64), ``complete_only`` whether only
+    records with a usable value in every channel are summed.  ValueError where the library would refuse."""
+    if n_channels is None:
+        raise ValueError("site_quant: n_channels is missing (the columns of the channel matrix, 1 .. %d)" % QUANT_MAX_CHANNELS)
+    return check_site_quant_params(dict(threshold=threshold, scale_log2=scale_log2, n_channels=n_channels, complete_only=complete_only))
+
+
+def check_site_quant_params(params):
+    """``params`` (a dict as ``site_quant_params`` makes it) checked against the conditions of ``pya_site_quant_params``;
+    returns it with plain Python numbers."""
+    try:
+        out = dict(threshold=float(params["threshold"]), scale_log2=params["scale_log2"], n_channels=params["n_channels"],
+                   complete_only=params["complete_only"])
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("site_quant: params is the dict of pyascore_amd.rollup.site_quant_params (threshold, scale_log2, n_channels, "
+                         "complete_only)") from None
+    if out["threshold"] != out["threshold"]:
+        raise ValueError("site_quant: threshold is not a number")
+    for name, lo, hi in (("scale_log2", -64, 64), ("n_channels", 1, QUANT_MAX_CHANNELS)):
+        v = out[name]
+        try:
+            ok = not isinstance(v, bool) and int(v) == v and lo <= int(v) <= hi
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("site_quant: %s = %r is not an integer in %d .. %d" % (name, v, lo, hi))
+        out[name] = int(v)
+    if not isinstance(out["complete_only"], (bool, np.bool_)):
+        raise ValueError("site_quant: complete_only = %r is not a boolean" % (out["complete_only"],))
+    out["complete_only"] = bool(out["complete_only"])
+    return out
+
+
+def site_quant_c_params(params):
+    """``params`` as the ``pya_site_quant_params`` structure the library reads."""
+    p = check_site_quant_params(params)
+    return _lib.SiteQuantParams(p["threshold"], p["scale_log2"], p["n_channels"], _lib.PYA_QUANT_COMPLETE_ONLY if p["complete_only"] else 0, 0)
+
+
+def empty_site_quant(n_slots, n_channels):
+    """``(head, cell)`` of an empty table: ``SITE_QUANT_HEAD_DTYPE[n_slots]`` and ``SITE_QUANT_DTYPE[n_slots, n_channels]``,
+    all zero."""
+    return np.zeros(int(n_slots), SITE_QUANT_HEAD_DTYPE), np.zeros((int(n_slots), int(n_channels)), SITE_QUANT_DTYPE)
+
+
+def _site_quant_table(table, what):
+    head = np.ascontiguousarray(table[0], SITE_QUANT_HEAD_DTYPE)
+    cell = np.ascontiguousarray(table[1], SITE_QUANT_DTYPE)
+    if head.ndim != 1 or cell.ndim != 2 or cell.shape[0] != head.size:
+        raise ValueError("%s: a table is (head[n_slots], cell[n_slots, n_channels])" % what)
+    return head, cell
+
+
+def site_quant(site_probs, psm_probs, site_off, best_sig, slot, n_slots, values, row, params, into=None):
+    """The table ``score_batch(quant=...)`` returns, from the probability records of the same batch (``score_batch(probs=True)``:
+    ``site_probs``, ``psm_probs``, ``site_off``) and its ``best_sig``: the definition of ``pya_site_quant`` restated in numpy,
+    with the same bytes.  ``slot``: one per residue record as for ``rollup=``; ``values``: float64 ``[n_rows, n_channels]``;
+    ``row``: the row of every PSM (negative: left out) or None (PSM i has row i); ``params``: ``site_quant_params(...)``;
+    ``into``: a ``(head, cell)`` to accumulate into (it is copied), None: the empty table.  A record that would contribute but
+    names a slot at or above ``n_slots`` or a row at or above ``n_rows`` is a ValueError (the library answers PYA_ERR_LIMIT).
+    Returns ``(head, cell)``: ``SITE_QUANT_HEAD_DTYPE[n_slots]``, ``SITE_QUANT_DTYPE[n_slots, n_channels]``."""
+    p = check_site_quant_params(params)
+    n_ch, n_slots = p["n_channels"], int(n_slots)
+    site_off = np.asarray(site_off, np.int64)
+    n = site_off.size - 1
+    site_probs = np.asarray(site_probs, np.dtype(_lib.SITE_PROB_DTYPE))
+    psm_probs = np.asarray(psm_probs, np.dtype(_lib.PSM_PROB_DTYPE))
+    best_sig = np.asarray(best_sig).astype(np.uint64)
+    slot = np.asarray(slot).astype(np.int64)
+    values = np.ascontiguousarray(values, np.float64)
+    if values.ndim != 2 or values.shape[1] != n_ch:
+        raise ValueError("site_quant: values is a float64 matrix with %d columns" % n_ch)
+    n_rec = int(site_off[-1]) if n >= 0 else 0
+    if n < 0 or site_probs.shape != (n_rec,) or psm_probs.shape != (n,) or best_sig.shape != (n,) or slot.shape != (n_rec,):
+        raise ValueError("site_quant: site_off has n_psm + 1 entries, psm_probs and best_sig one per PSM, site_probs and slot one per residue record")
+    row = np.arange(n, dtype=np.int64) if row is None else np.asarray(row).astype(np.int64)
+    if row.shape != (n,):
+        raise ValueError("site_quant: row has one entry per PSM")
+    head, cell = empty_site_quant(n_slots, n_ch) if into is None else tuple(a.copy() for a in _site_quant_table(into, "site_quant"))
+    if head.shape != (n_slots,) or cell.shape != (n_slots, n_ch):
+        raise ValueError("site_quant: into is a table of other slots or channels")
+    owner = np.repeat(np.arange(n), np.diff(site_off))
+    r = np.arange(n_rec, dtype=np.int64) - site_off[owner]
+    in_best = (r < 64) & (((best_sig[owner] >> np.minimum(r, 63).astype(np.uint64)) & np.uint64(1)) != 0)
+    rw = row[owner]
+    with np.errstate(invalid="ignore"):
+        cand = (slot >= 0) & (psm_probs["kind"][owner] == _lib.PYA_SITE_SCORED) & in_best & (site_probs["with_prob"] >= p["threshold"]) & (rw >= 0)
+    outside = cand & ((slot >= n_slots) | (rw >= values.shape[0]))
+    if outside.any():
+        first = int(np.flatnonzero(outside)[0])
+        raise ValueError("site_quant: residue record %d (PSM %d) names slot %d of %d, row %d of %d"
+                         % (first, int(owner[first]), int(slot[first]), n_slots, int(rw[first]), values.shape[0]))
+    s, v = slot[cand], values[rw[cand]]
+    usable = (v == v) & (v > 0.0)
+    complete = usable.all(axis=1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = v * 2.0 ** p["scale_log2"]
+    saturated = usable & (t >= 281474976710656.0)
+    q = np.where(usable & ~saturated, t, 0.0).astype(np.uint64)
+    q[saturated] = np.uint64(1 << 48)
+    summed = usable & complete[:, None] if p["complete_only"] else usable
+    np.add.at(head["n_records"], s, 1)
+    np.add.at(head["n_complete"], s[complete], 1)
+    at = np.nonzero(summed)
+    np.add.at(cell["sum"], (s[at[0]], at[1]), q[at])
+    np.add.at(cell["n"], (s[at[0]], at[1]), 1)
+    at = np.nonzero(summed & saturated)
+    np.add.at(cell["n_saturated"], (s[at[0]], at[1]), 1)
+    return head, cell
+
+
+def merge_site_quant(*tables):
+    """The sum of ``(head, cell)`` tables over the same slots and channels, field by field (counts and sums wrap as on the
+    device): the table of the records behind all of them."""
+    if not tables:
+        raise ValueError("merge_site_quant: no table")
+    parts = [_site_quant_table(t, "merge_site_quant") for t in tables]
+    if any(h.shape != parts[0][0].shape or c.shape != parts[0][1].shape for h, c in parts):
+        raise ValueError("merge_site_quant: the tables have different slots or channels")
+    head, cell = parts[0][0].copy(), parts[0][1].copy()
+    for h, c in parts[1:]:
+        for f in ("n_records", "n_complete"):
+            head[f] += h[f]
+        for f in ("sum", "n", "n_saturated"):
+            cell[f] += c[f]
+    return head, cell
+
+
+def site_quant_sums(head, cell, params):
+    """The channel sums of a table in intensity units: float64 ``[n_slots, n_channels]``, ``sum / 2^scale_log2``, NaN where no
+    reading was summed (``n == 0``)."""
+    p = check_site_quant_params(params)
+    head, cell = _site_quant_table((head, cell), "site_quant_sums")
+    return np.where(cell["n"] != 0, cell["sum"].astype(np.float64) * 2.0 ** -p["scale_log2"], np.nan)
