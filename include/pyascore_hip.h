@@ -122,6 +122,10 @@ extern "C" {
                               /* slots of the same call's PYA_FLAG_ROLLUP (without it: PYA_ERR_ARG) and the channel matrix lent   */
                               /* by pya_set_site_quant (pya_last_batch_site_quant); pya_plan_create*: as PYA_FLAG_EVIDENCE        */
                               /* (pya_plan_site_quant)                                                                            */
+#define PYA_FLAG_PFORM_QUANT 32768u /* pya_score_batch* / pya_score_batch_named: the peptidoform quantification of the batch as well, */
+                                    /* row-aligned with the list of the same call's PYA_FLAG_PEPTIDOFORMS (without it: PYA_ERR_ARG)  */
+                                    /* over the channel matrix lent by pya_set_peptidoform_quant (pya_last_batch_peptidoform_quant);  */
+                                    /* pya_plan_create*: as PYA_FLAG_EVIDENCE (pya_plan_peptidoform_quant)                            */
 
 /* per-PSM codes of pya_last_batch_status */
 #define PYA_PSM_OK 0
@@ -451,6 +455,39 @@ typedef struct pya_peptidoform {   /* 48 bytes, three 16-byte stores; records co
     float best_min_ascore;         /* max over the PSMs of min_ascore, under the roll-up's total order of bits */
     uint32_t n_isomers;            /* distinct sig_bits among the records of this group (same in all of them)  */
 } pya_peptidoform;
+
+/* Peptidoform quantification: the peptidoform list joined with the channel intensities of a labelled experiment -- per
+ * modification-specific peptide and channel the summed intensity of the PSMs that report it confidently.  A site table adds
+ * the intensities of species that are regulated independently (a doubly modified peptide and its singly modified forms share
+ * sites); this one does not.  The reference has no counterpart.  THE RESULT IS A PAIR: a peptidoform list, pya_peptidoform[n],
+ * byte for byte what pya_plan_peptidoforms gives for the same inputs, and a table ROW-ALIGNED with it, pya_site_quant_head
+ * head[n] and pya_site_quant cell[n * n_channels]: row j belongs to list record j.  No new record types: the two structs and
+ * pya_site_quant_params are the site quantification's.  Input: what pya_plan_peptidoforms takes (probability records,
+ * best_sig, ascores, group, psm_id, the list's threshold, an earlier list), what pya_plan_site_quant takes for the channels
+ * (values[n_rows * n_channels], row[n_psm] or NULL with row_base, params), and optionally the table of the earlier list.
+ * A PSM CONTRIBUTES TO THE TABLE iff it contributes to the list (kind == PYA_SITE_SCORED, group not negative, best_sig inside
+ * the plan's residue records and max_k), its min_prob -- the same bits the list stage computes -- satisfies min_prob >=
+ * params->threshold compared as doubles, and its row is in [0, n_rows).  A negative row is left out silently.  A row at or
+ * above n_rows writes nothing to the table and is reported by pya_plan_check (PYA_ERR_LIMIT), as the site quantification
+ * reports it; the PSM is still in the list.  params->threshold is the table's own and independent of the list's threshold.
+ * Usable value, quantum q(v), saturation at 2^48, COMPLETE and PYA_QUANT_COMPLETE_ONLY are pya_site_quant's above, word for
+ * word (csrc/quant_rule.hip.h is the one place both stages take them from).  Per list record, head.n_records counts the
+ * contributing PSMs of that key and head.n_complete the complete ones, plus the same fields of the earlier table's row for
+ * the same key.  Per cell, sum, n and n_saturated over those PSMs with a usable value in the channel -- with
+ * PYA_QUANT_COMPLETE_ONLY over the complete ones only --, plus the earlier table's cell for the same key.  A record of the
+ * list none of whose PSMs contributes to the table has an all-zero row.
+ * THE PAIR IS A FUNCTION OF THE MULTISET OF CONTRIBUTING TUPLES (group, sig, min_prob, z, min_ascore, psm_id, the row's
+ * values) AND OF NOTHING ELSE: the list is, and every field of the table is an integer sum.  It does not depend on the order of
+ * the PSMs, on the route that scored a PSM, on shared or typed input, on chunk cuts, or on how the PSMs were spread over calls.
+ * A pair fed back as the earlier list and table together with more PSMs gives the bytes of one call over all of them.  Two
+ * pairs merge by pya_peptidoform_quant_reduce: the keys' union, rows of equal keys added field by field.  A record with
+ * n_psm == 0 in an input list is skipped, as the list stage skips it, and its table row with it.  THE CALLER KEEPS
+ * params->threshold, scale_log2, n_channels and flags THE SAME across everything that is merged or fed forward: the table does
+ * not record them.  Counts are 32-bit and sums 64-bit, neither checked for overflow.
+ * cap: d_n[0] is the true length of the list; rows [0, min(length, cap)) of list and table are written; the call clears
+ * head[0 .. cap) and cell[0 .. cap * n_channels) itself on the stream, so rows behind the list are zero bytes; a key whose
+ * place in the list is at or above cap writes nothing; the result for a smaller cap is the byte prefix of the result for a
+ * larger one.  csrc/pform_quant.hip; the library is built without fast-math. */
 
 /* Fragment mass-error profile.  The third reduction across PSMs, and the one that speaks about a SETTING rather than about a
  * localisation: per run (file, fraction, instrument -- a slot the caller names per PSM) the distribution of the m/z errors of
@@ -1079,6 +1116,20 @@ int pya_set_site_quant(pya_handle *h, const double *values, uint64_t n_rows, con
  * n_slots and n_channels as lent (anything else: PYA_ERR_ARG, as is a NULL array for a table that has slots).  PYA_ERR_STATE
  * when the last batch was scored without the flag. */
 int pya_last_batch_site_quant(pya_handle *h, pya_site_quant_head *head, pya_site_quant *cell, uint64_t n_slots, uint32_t n_channels);
+/* Lends the library what the NEXT batch call with PYA_FLAG_PFORM_QUANT quantifies its peptidoforms with (peptidoform
+ * quantification above): values[n_rows * params->n_channels] and row[n_psm] (or NULL: PSM i of the batch has row i), host
+ * memory that must stay valid until that call returns; params, copied.  The list is that of the same call's
+ * PYA_FLAG_PEPTIDOFORMS (pya_set_peptidoforms): the flag without PYA_FLAG_PEPTIDOFORMS is PYA_ERR_ARG with a message.  Lifetime
+ * and refusals are pya_set_site_quant's.  The batch call uploads the matrix once, a chunk's slice of row with the chunk, and
+ * feeds every chunk's pair into the next chunk's call as the earlier list and table, as it does for the list alone; with the
+ * flag pya_last_batch_peptidoforms returns exactly what it returns without it.  A row at or above n_rows: PYA_ERR_LIMIT. */
+int pya_set_peptidoform_quant(pya_handle *h, const double *values, uint64_t n_rows, const int32_t *row, uint64_t n_psm,
+                              const pya_site_quant_params *params);
+/* The table of the last batch call on this handle that was given PYA_FLAG_PFORM_QUANT, row-aligned with the list of
+ * pya_last_batch_peptidoforms: head[n] and cell[n * n_channels], n the length of that list and n_channels as lent (anything
+ * else: PYA_ERR_ARG, as is a NULL array for a table that has rows).  PYA_ERR_STATE when the last batch was scored without the
+ * flag. */
+int pya_last_batch_peptidoform_quant(pya_handle *h, pya_site_quant_head *head, pya_site_quant *cell, uint64_t n, uint32_t n_channels);
 /* The coverage records (pya_coverage above) of the last batch call on this handle that was given PYA_FLAG_COVERAGE: out[n_psm],
  * n_psm as in that call (anything else: PYA_ERR_ARG).  PYA_ERR_STATE when the last batch was scored without the flag.  The
  * record of a PSM that was set aside (PYA_FLAG_SKIP_INVALID) is all zero; records do not depend on the cut into chunks. */
@@ -1289,6 +1340,29 @@ int pya_peptidoform_reduce(pya_handle *h, const pya_peptidoform *d_a, uint64_t n
  * downloads.  *n: the length of the list; the first min(*n, cap) records into out. */
 int pya_peptidoform_reduce_host(pya_handle *h, const pya_peptidoform *a, uint64_t n_a, const pya_peptidoform *b, uint64_t n_b,
                                 pya_peptidoform *out, uint64_t cap, uint64_t *n);
+/* The device bytes pya_plan_peptidoform_quant / pya_peptidoform_quant_reduce need as their workspace: never less than
+ * pya_peptidoform_workspace_bytes(n_entries) (today exactly that: the table stage keeps nothing in the workspace). */
+uint64_t pya_peptidoform_quant_workspace_bytes(uint64_t n_entries, uint32_t n_channels);
+/* The merge of two pairs (peptidoform quantification above) over DEVICE arrays: the list as pya_peptidoform_reduce gives it for
+ * d_a[n_a] and d_b[n_b], and d_head[cap] / d_cell[cap * n_channels] row-aligned with it: per key the rows of d_a_head /
+ * d_a_cell and d_b_head / d_b_cell of the records with that key, added field by field.  The head and cells of a side may both
+ * be NULL: that side counts as having an all-zero table (exactly one of them NULL: PYA_ERR_ARG).  Records with n_psm == 0 are
+ * skipped and their rows with them.  The call clears d_head[0 .. cap) and d_cell[0 .. cap * n_channels) itself; the outputs
+ * must not alias an input.  Otherwise pya_peptidoform_reduce's contract: stream-ordered, no host synchronisation, no
+ * allocation; work_bytes >= pya_peptidoform_quant_workspace_bytes(n_a + n_b, n_channels); cells 16-byte, heads 8-byte aligned.
+ * No write lies outside d_out[0 .. cap), d_head[0 .. cap), d_cell[0 .. cap * n_channels), d_n[0 .. 2) and the workspace.
+ * PYA_ERR_ARG, with nothing launched: pya_peptidoform_reduce's refusals, n_channels outside 1 .. 64. */
+int pya_peptidoform_quant_reduce(pya_handle *h, const pya_peptidoform *d_a, const pya_site_quant_head *d_a_head, const pya_site_quant *d_a_cell,
+                                 uint64_t n_a, const pya_peptidoform *d_b, const pya_site_quant_head *d_b_head, const pya_site_quant *d_b_cell,
+                                 uint64_t n_b, uint32_t n_channels, void *hip_stream, void *d_work, uint64_t work_bytes, pya_peptidoform *d_out,
+                                 pya_site_quant_head *d_head, pya_site_quant *d_cell, uint64_t cap, uint32_t *d_n);
+/* The same for HOST arrays: uploads, runs pya_peptidoform_quant_reduce on the handle's stream with a workspace of its own and
+ * downloads.  *n: the length of the list; the first min(*n, cap) rows into out, head and cell; the rows behind them up to
+ * min(cap, n_a + n_b) are zeroed. */
+int pya_peptidoform_quant_reduce_host(pya_handle *h, const pya_peptidoform *a, const pya_site_quant_head *a_head, const pya_site_quant *a_cell,
+                                      uint64_t n_a, const pya_peptidoform *b, const pya_site_quant_head *b_head, const pya_site_quant *b_cell,
+                                      uint64_t n_b, uint32_t n_channels, pya_peptidoform *out, pya_site_quant_head *head, pya_site_quant *cell,
+                                      uint64_t cap, uint64_t *n);
 
 /* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
@@ -1410,6 +1484,24 @@ int pya_plan_peptidoforms(pya_plan *plan, const pya_results *d_res, void *hip_st
                           const pya_psm_prob *d_psm_probs, const int32_t *d_group, double threshold, const uint32_t *d_psm_id,
                           uint32_t psm_base, const pya_peptidoform *d_prev, uint64_t n_prev, void *d_work, uint64_t work_bytes,
                           pya_peptidoform *d_out, uint64_t cap, uint32_t *d_n);
+/* The pair of the peptidoform quantification (above) over this plan's contributing PSMs and an earlier pair: pya_plan_peptidoforms'
+ * contract, extended.  d_out[cap] / d_n and everything up to n_prev as in that call, with the same bytes as its result;
+ * d_prev_head[n_prev] / d_prev_cell[n_prev * n_channels], the table of d_prev, may both be NULL: the earlier list then counts as
+ * having an all-zero table (exactly one of them NULL: PYA_ERR_ARG).  d_values / n_rows / d_row / row_base / params as for
+ * pya_plan_site_quant.  d_head[cap] / d_cell[cap * n_channels] take the table; the call clears both on the stream before it
+ * adds to them.  The list by the launches of csrc/peptidoforms.hip, one launch of csrc/pform_quant.hip behind them on the same
+ * stream, inside the caller's workspace (work_bytes >= pya_peptidoform_quant_workspace_bytes(n_psm + n_prev, n_channels)): no
+ * host synchronisation, no allocation of the caller's.  No write lies outside d_out[0 .. cap), d_head[0 .. cap), d_cell[0 ..
+ * cap * n_channels), d_n[0 .. 2) and the workspace.  A PSM that would contribute and whose row is at or above n_rows writes
+ * nothing to the table, and pya_plan_check reports it (PYA_ERR_LIMIT) until the call is repeated or the plan is run again.
+ * PYA_ERR_ARG, with nothing launched: what pya_plan_peptidoforms and pya_set_site_quant refuse; PYA_ERR_STATE before the plan's
+ * first run. */
+int pya_plan_peptidoform_quant(pya_plan *plan, const pya_results *d_res, void *hip_stream, const pya_site_prob *d_site_probs,
+                               const pya_psm_prob *d_psm_probs, const int32_t *d_group, double threshold, const uint32_t *d_psm_id,
+                               uint32_t psm_base, const pya_peptidoform *d_prev, const pya_site_quant_head *d_prev_head,
+                               const pya_site_quant *d_prev_cell, uint64_t n_prev, const double *d_values, uint64_t n_rows, const int32_t *d_row,
+                               uint32_t row_base, const pya_site_quant_params *params, void *d_work, uint64_t work_bytes, pya_peptidoform *d_out,
+                               pya_site_quant_head *d_head, pya_site_quant *d_cell, uint64_t cap, uint32_t *d_n);
 /* Adds the fragment mass errors of this plan's contributing PSMs to d_table[n_slots] (pya_mz_profile above; device memory,
  * emptied once by a hipMemsetAsync to 0): the stage ACCUMULATES, so the same table may take other plans, other runs and other
  * calls.  d_run[n_psm] device memory, or NULL: every PSM is of slot 0.  It reads best_sig and n_sig of d_res, the run's status

@@ -26,7 +26,10 @@ neutral-loss and charge-reduced forms and the peaks outside an m/z range from ev
 ``--marker_mz M1,M2,...``, ``--marker_losses L1,...``, ``--marker_tol DA`` and ``--marker_tol_ppm PPM`` (a table with a line per PSM:
 the intensities of reporter and diagnostic ions in its spectrum, read before anything is stripped) and ``--site_quant FILE`` with
 ``--site_quant_threshold P``, ``--site_quant_scale E`` and ``--site_quant_complete`` (a line per site of ``--site_table``: the
-intensities of the ``--marker_mz`` targets summed over the PSMs that localise the modification there) are the additions."""
+intensities of the ``--marker_mz`` targets summed over the PSMs that localise the modification there) and ``--peptidoform_quant FILE``
+with ``--peptidoform_quant_threshold P``, ``--peptidoform_quant_scale E`` and ``--peptidoform_quant_complete`` (a line per peptidoform:
+the columns of ``--peptidoform_table``, then the same intensities summed over the PSMs that report the assignment; it needs
+``--marker_mz``) are the additions."""
 import argparse
 import re
 import sys
@@ -212,6 +215,16 @@ def build_parser():
                    help="with --site_quant: readings are summed as integers in units of 2^-E (default 10; -64 .. 64)")
     p.add_argument("--site_quant_complete", action="store_true",
                    help="with --site_quant: only PSMs with a reading in every channel are summed")
+    p.add_argument("--peptidoform_quant", type=str, default="", metavar="FILE",
+                   help="write the peptidoform quantification to FILE: one line per peptidoform, the columns of --peptidoform_table, then "
+                        "the intensities of the --marker_mz targets summed on the device over the PSMs that report the assignment with "
+                        "a smallest site probability of at least --peptidoform_quant_threshold; needs --marker_mz (fixed targets)")
+    p.add_argument("--peptidoform_quant_threshold", type=float, default=0.75, metavar="P",
+                   help="with --peptidoform_quant: the smallest site probability from which a PSM's reading is summed (default 0.75)")
+    p.add_argument("--peptidoform_quant_scale", type=int, default=10, metavar="E",
+                   help="with --peptidoform_quant: readings are summed as integers in units of 2^-E (default 10; -64 .. 64)")
+    p.add_argument("--peptidoform_quant_complete", action="store_true",
+                   help="with --peptidoform_quant: only PSMs with a reading in every channel are summed")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -250,11 +263,30 @@ def site_quant_request(args):
     return req
 
 
+def peptidoform_quant_request(args):
+    """``--peptidoform_quant`` as the dict ``batch_cli.localize(peptidoform_quant=...)`` takes, checked; None without the option:
+    the other ``--peptidoform_quant_*`` values are then not looked at."""
+    if not getattr(args, "peptidoform_quant", ""):
+        return None
+    from .rollup import site_quant_params
+    channels = [v for v in args.marker_mz.split(",") if v.strip()]
+    if not channels:
+        raise ValueError("--peptidoform_quant sums the intensities of the fixed --marker_mz targets (--marker_losses are no channels): "
+                         "give --marker_mz M1,M2,... as well")
+    req = dict(threshold=args.peptidoform_quant_threshold, scale_log2=args.peptidoform_quant_scale,
+               complete_only=bool(args.peptidoform_quant_complete))
+    try:
+        site_quant_params(n_channels=min(len(channels), 64), **req)
+    except ValueError as e:
+        raise ValueError("--peptidoform_quant_scale / --peptidoform_quant_threshold: %s" % e) from None
+    return req
+
+
 def markers_request(args):
     """The rule of ``--markers`` as the dict ``batch_cli.localize(markers=...)`` takes (the precursors come from the spectra),
-    checked; None without the option (and without ``--site_quant``, which reads the same targets): the other ``--marker_*``
-    values are then not looked at."""
-    if not getattr(args, "markers", "") and not getattr(args, "site_quant", ""):
+    checked; None without the option (and without ``--site_quant`` / ``--peptidoform_quant``, which read the same targets): the
+    other ``--marker_*`` values are then not looked at."""
+    if not getattr(args, "markers", "") and not getattr(args, "site_quant", "") and not getattr(args, "peptidoform_quant", ""):
         return None
     from .rollup import marker_params
     lists = {}
@@ -297,6 +329,7 @@ def validate_args(args):
     centroid_request(args)
     markers_request(args)
     site_quant_request(args)
+    peptidoform_quant_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -366,6 +399,8 @@ def run(args, log=print):
     marker_rows = [] if markers is not None else None
     site_quant = site_quant_request(args)
     site_quant_rows = [] if site_quant is not None else None
+    pform_quant = peptidoform_quant_request(args)
+    pform_quant_rows = [] if pform_quant is not None else None
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -379,7 +414,8 @@ def run(args, log=print):
                               peptidoform_threshold=args.peptidoform_threshold, mz_profile=profile, recalibrate=recalibrate,
                               deisotope=deisotope, decharge=decharge, strip=strip_request(args),
                               centroid=centroid_request(args), coverage=coverage_rows, markers=markers,
-                              marker_rows=marker_rows, site_quant=site_quant, site_quant_rows=site_quant_rows)
+                              marker_rows=marker_rows, site_quant=site_quant, site_quant_rows=site_quant_rows,
+                              peptidoform_quant=pform_quant, peptidoform_quant_rows=pform_quant_rows)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -403,6 +439,8 @@ def run(args, log=print):
         batch_cli.write_coverage_tsv(coverage_rows, args.coverage)
     if site_quant_rows is not None:
         batch_cli.write_site_quant_tsv(site_quant_rows, args.site_quant, mz=markers["mz"])
+    if pform_quant_rows is not None:
+        batch_cli.write_peptidoform_quant_tsv(pform_quant_rows, args.peptidoform_quant, mz=markers["mz"])
     if marker_rows is not None and args.markers:
         batch_cli.write_markers_tsv(marker_rows, args.markers, mz=markers["mz"], losses=markers["losses"])
     log("{} -- Ascore Completed".format(stamp()))

@@ -22,6 +22,7 @@ PYA_FLAG_MZ_PROFILE = 2048
 PYA_FLAG_RECALIBRATE = 4096
 PYA_FLAG_COVERAGE = 8192
 PYA_FLAG_QUANT = 16384
+PYA_FLAG_PFORM_QUANT = 32768
 PYA_QUANT_COMPLETE_ONLY = 1
 PYA_QUANT_MAX_CHANNELS = 64
 PYA_COV_NONE, PYA_COV_SCORED = 0, 1
@@ -381,6 +382,16 @@ SYMBOLS = {
     "pya_last_batch_site_quant": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32]),
     "pya_plan_site_quant": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp]),
     "pya_marker_values": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "pya_set_peptidoform_quant": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
+    "pya_last_batch_peptidoform_quant": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32]),
+    "pya_peptidoform_quant_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),
+    "pya_peptidoform_quant_reduce": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint64,
+                                               _vp, _vp, _vp, C.c_uint64, _vp]),
+    "pya_peptidoform_quant_reduce_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp,
+                                                    C.c_uint64, _vp]),
+    "pya_plan_peptidoform_quant": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_double, _vp, C.c_uint32, _vp, _vp, _vp,
+                                             C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_uint64,
+                                             _vp]),
     "pya_last_batch_coverage": (C.c_int, [_vp, _vp, C.c_uint64]),
     "pya_plan_coverage": (C.c_int, [_vp, C.POINTER(Results), C.POINTER(TypedSpectra), _vp, _vp]),
     "pya_mz_profile_fit": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp]),

@@ -371,36 +371,52 @@ def _rollup_request(rollup, n_psm):
                 psm_id=psm_id, site_off=site_off)
 
 
-def _quant_request(req, n_psm, have_rollup):
-    """``score_batch(quant=...)`` checked: dict(values float64 [n_rows, n_channels], row int32 | None, params, c_params) --
-    ``params`` the dict of ``pyascore_amd.rollup.site_quant_params``"""
+def _marker_channels(name, req, params, records, spec_of):
+    """``quant=`` / ``peptidoform_quant=`` with ``values=None`` beside ``markers=``, filled in: the channels are the fixed targets
+    of ``markers=`` (its marker records ``records``), the rows the spectra"""
+    from .rollup import marker_matrix
+    fixed = [t for t in range(len(params["value"])) if not (params["loss_mask"] >> t) & 1]
+    if not fixed:
+        raise ValueError(name + ": markers= has no fixed target to take as a channel")
+    row = req.get("row")
+    if row is None and spec_of is not None:
+        row = np.asarray(spec_of).astype(np.int32)
+    return dict(req, values=np.ascontiguousarray(marker_matrix(records)[:, fixed]), row=row)
+
+
+def _quant_request(req, n_psm, have_rollup, name="quant"):
+    """``score_batch(quant=...)`` checked -- under the name ``peptidoform_quant`` that option, whose companion is
+    ``peptidoforms=`` --: dict(values float64 [n_rows, n_channels], row int32 | None, params, c_params), ``params`` the dict of
+    ``pyascore_amd.rollup.site_quant_params``"""
     from .rollup import site_quant_c_params, site_quant_params
     names = ("values", "row", "threshold", "scale_log2", "complete_only")
     if not isinstance(req, dict):
-        raise ValueError("quant takes a dict: " + ", ".join(names))
+        raise ValueError(name + " takes a dict: " + ", ".join(names))
     unknown = set(req) - set(names)
     if unknown:
-        raise ValueError("quant takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+        raise ValueError(name + " takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+    if not have_rollup and name == "peptidoform_quant":
+        raise ValueError("peptidoform_quant needs peptidoforms= in the same call: the table is row-aligned with its list")
     if not have_rollup:
         raise ValueError("quant needs rollup= in the same call: the channel sums go to the slots of the roll-up")
     if req.get("values") is None:
-        raise ValueError("quant: values is missing (a float64 matrix, one row per spectrum and one column per channel); only beside "
+        raise ValueError(name + ": values is missing (a float64 matrix, one row per spectrum and one column per channel); only beside "
                          "markers= it may be None -- the channels are then the fixed targets of markers=")
     try:
         values = np.ascontiguousarray(req["values"], np.float64)
     except (TypeError, ValueError):
-        raise ValueError("quant: values is a matrix of numbers") from None
+        raise ValueError(name + ": values is a matrix of numbers") from None
     if values.ndim != 2:
-        raise ValueError("quant: values is a matrix, one row per spectrum and one column per channel")
+        raise ValueError(name + ": values is a matrix, one row per spectrum and one column per channel")
     if values.shape[0] > 0x7FFFFFFF:
-        raise ValueError("quant: values has more than 2^31 - 1 rows")
+        raise ValueError(name + ": values has more than 2^31 - 1 rows")
     row = req.get("row")
     if row is not None:
         row = np.asarray(row)
         if row.ndim != 1 or row.size != n_psm or (row.size and row.dtype.kind not in "iu"):
-            raise ValueError("quant: row is one integer per PSM")
+            raise ValueError(name + ": row is one integer per PSM")
         if row.size and (int(row.max()) > 0x7FFFFFFF or int(row.min()) < -0x80000000):
-            raise ValueError("quant: row does not fit int32")
+            raise ValueError(name + ": row does not fit int32")
         row = np.ascontiguousarray(row, np.int32)
     params = site_quant_params(req.get("threshold", 0.75), req.get("scale_log2", 10), values.shape[1], req.get("complete_only", False))
     return dict(values=values, row=row, params=params, c_params=site_quant_c_params(params))
@@ -640,7 +656,7 @@ class PyAscore:
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
                     recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=False, markers=None,
-                    quant=None):
+                    quant=None, peptidoform_quant=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -805,6 +821,17 @@ class PyAscore:
         into intensities), so the table does not depend on chunk cuts, route or order, and tables of several calls merge by
         adding (``merge_site_quant``); ``pyascore_amd.rollup.site_quant`` gives the same bytes on the host.
 
+        ``peptidoform_quant=dict(values=, row=None, threshold=0.75, scale_log2=10, complete_only=False)`` -- beside
+        ``peptidoforms=``, whose list it is row-aligned with; without it a ValueError -- adds ``peptidoform_quant_head``
+        (``SITE_QUANT_HEAD_DTYPE``, shape ``[n_list]``), ``peptidoform_quant`` (``SITE_QUANT_DTYPE``, shape ``[n_list,
+        n_channels]``) and ``peptidoform_quant_params``: per peptidoform and channel the summed reading of the PSMs that
+        contribute to the list with ``min_prob >= threshold`` (``PYA_FLAG_PFORM_QUANT``, the peptidoform quantification of
+        ``include/pyascore_hip.h``).  ``values``, ``row`` and the parameters are those of ``quant=``; ``values=None`` beside
+        ``markers=`` takes the fixed targets of that call.  ``peptidoforms`` is exactly what the call returns without the
+        option; it goes together with ``rollup=`` / ``quant=`` in one call.  Two pairs merge by
+        ``peptidoform_quant_reduce`` or ``pyascore_amd.rollup.merge_peptidoform_quant``; ``pyascore_amd.rollup.peptidoform_quant``
+        gives the same bytes on the host.
+
         ``coverage=True`` adds ``coverage`` (``COVERAGE_DTYPE``, the 64-byte ``pya_coverage``, shape ``[n]``): per PSM the ion
         current of its spectrum and the part of it that the matched fragments of the reported localisation explain, in all and
         from either terminus, beside peak, fragment and bond counts (``pyascore_amd.rollup.coverage_ratios`` makes the ratios,
@@ -821,7 +848,8 @@ class PyAscore:
             rest = dict(keep=keep, skip_invalid=skip_invalid, evidence=evidence, ions=ions, named=named, sites=sites,
                         site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup, peptidoforms=peptidoforms,
                         mz_profile=mz_profile, recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip,
-                        centroid=centroid, coverage=coverage, markers=markers, quant=quant)
+                        centroid=centroid, coverage=coverage, markers=markers, quant=quant,
+                        peptidoform_quant=peptidoform_quant)
             rest.update(changed)
             rest[done] = None
             return self.score_batch(dict(batch, mz=spectra[0], intensity=spectra[1], peak_off=spectra[2]), **rest)
@@ -833,17 +861,9 @@ class PyAscore:
             params, prec_mz, prec_z = _markers_request(markers, self._mz_error, _n_spectra(batch))
             records, spectra, _ = self.marker_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), params, prec_mz, prec_z)
             changed = {}
-            if isinstance(quant, dict) and quant.get("values") is None:
-                # the channels: the fixed targets of markers=; the rows: the spectra
-                from .rollup import marker_matrix
-                fixed = [t for t in range(len(params["value"])) if not (params["loss_mask"] >> t) & 1]
-                if not fixed:
-                    raise ValueError("quant: markers= has no fixed target to take as a channel")
-                values = np.ascontiguousarray(marker_matrix(records)[:, fixed])
-                row = quant.get("row")
-                if row is None and batch.get("spec_of") is not None:
-                    row = np.asarray(batch["spec_of"]).astype(np.int32)
-                changed["quant"] = dict(quant, values=values, row=row)
+            for name, req in (("quant", quant), ("peptidoform_quant", peptidoform_quant)):
+                if isinstance(req, dict) and req.get("values") is None:
+                    changed[name] = _marker_channels(name, req, params, records, batch.get("spec_of"))
             res = again("markers", (batch["mz"], batch["intensity"], batch["peak_off"]), **changed)
             res["markers"], res["marker_spectra"] = records, spectra
             return res
@@ -868,6 +888,8 @@ class PyAscore:
                                                                                         self._n_top)
         recal = None if recalibrate is None else _recalibrate_request(recalibrate, int(batch["n_psm"]))
         qu = None if quant is None or quant is False else _quant_request(quant, int(batch["n_psm"]), roll is not None)
+        pfq = None if peptidoform_quant is None or peptidoform_quant is False else \
+            _quant_request(peptidoform_quant, int(batch["n_psm"]), pform is not None, "peptidoform_quant")
         if recal is not None and keep:
             raise ValueError("recalibrate does not go with keep=True: correct the arrays with pyascore_amd.rollup.recalibrate and "
                              "retain the batch without it")
@@ -877,7 +899,8 @@ class PyAscore:
             if perm is not None and keep:
                 return self.score_batch(expand_shared_batch(batch), keep=True, skip_invalid=skip_invalid, evidence=evidence, ions=ions,
                                         named=named, sites=sites, site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup,
-                                        peptidoforms=peptidoforms, mz_profile=mz_profile, coverage=coverage, quant=quant)
+                                        peptidoforms=peptidoforms, mz_profile=mz_profile, coverage=coverage, quant=quant,
+                                        peptidoform_quant=peptidoform_quant)
             if perm is not None:
                 moved = None
                 if named is not None:        # the queries travel with their PSMs, the records come back to the caller's order
@@ -909,6 +932,10 @@ class PyAscore:
                 quant_moved = None
                 if qu is not None:           # the rows travel with their PSMs
                     quant_moved = dict(quant, values=qu["values"], row=perm.astype(np.int32) if qu["row"] is None else qu["row"][perm])
+                pfq_moved = None
+                if pfq is not None:
+                    pfq_moved = dict(peptidoform_quant, values=pfq["values"],
+                                     row=perm.astype(np.int32) if pfq["row"] is None else pfq["row"][perm])
                 recal_moved = None
                 if recal is not None:        # ... and so do the slots of the calibration
                     recal_moved = dict(calibration=recal["cal"], band_width=recal["band_width"],
@@ -918,7 +945,7 @@ class PyAscore:
                                            named=None if moved is None else (moved[0], moved[1]), sites=sites,
                                            site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=roll_moved,
                                            peptidoforms=pform_moved, mz_profile=mzp_moved, recalibrate=recal_moved,
-                                           coverage=coverage, quant=quant_moved)
+                                           coverage=coverage, quant=quant_moved, peptidoform_quant=pfq_moved)
                 except ValueError as e:
                     raise ValueError(_renumber_psm(str(e), perm)) from None
                 csr = (res.pop("ion_off"), res.pop("ions")) if ions else None
@@ -929,7 +956,8 @@ class PyAscore:
                 forms = res.pop("peptidoforms", None)   # (per peptidoform)
                 profile = res.pop("mz_profile", None)   # (per run slot)
                 profile_params = res.pop("mz_profile_params", None)
-                per_slot = {k: res.pop(k) for k in ("quant_head", "quant", "quant_params") if k in res}   # (per roll-up slot)
+                per_slot = {k: res.pop(k) for k in ("quant_head", "quant", "quant_params", "peptidoform_quant_head", "peptidoform_quant",
+                                                    "peptidoform_quant_params") if k in res}   # (per roll-up slot, per peptidoform)
                 per_query = {k: res.pop(k) for k in ("named_off", "named", "named_counts", "named_scores") if k in res}
                 res = {k: (v[inv] if isinstance(v, np.ndarray) else v) for k, v in res.items()}
                 if moved is not None:
@@ -1027,6 +1055,10 @@ class PyAscore:
                 from .rollup import empty_site_quant
                 out["quant_head"], out["quant"] = empty_site_quant(roll["n_slots"], qu["params"]["n_channels"])
                 out["quant_params"] = dict(qu["params"])
+            if pfq is not None:
+                from .rollup import empty_site_quant
+                out["peptidoform_quant_head"], out["peptidoform_quant"] = empty_site_quant(0, pfq["params"]["n_channels"])
+                out["peptidoform_quant_params"] = dict(pfq["params"])
             return out
         b = _lib.Batch(n, _as_ptr(arrs["peak_off"]), _as_ptr(arrs["pep"]), _as_ptr(arrs["pep_off"]),
                        _as_ptr(arrs["n_of_mod"]), _as_ptr(arrs["max_charge"]), _as_ptr(arrs["aux_pos"]),
@@ -1053,7 +1085,8 @@ class PyAscore:
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked_k else 0) | \
             (_lib.PYA_FLAG_ROLLUP if roll is not None else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if pform is not None else 0) | \
             (_lib.PYA_FLAG_MZ_PROFILE if mzp is not None else 0) | (_lib.PYA_FLAG_RECALIBRATE if recal is not None else 0) | \
-            (_lib.PYA_FLAG_COVERAGE if coverage else 0) | (_lib.PYA_FLAG_QUANT if qu is not None else 0)
+            (_lib.PYA_FLAG_COVERAGE if coverage else 0) | (_lib.PYA_FLAG_QUANT if qu is not None else 0) | \
+            (_lib.PYA_FLAG_PFORM_QUANT if pfq is not None else 0)
         # for this call; the handle's own settings come back
         cap_before = k_before = None
         if (sites or probs or ranked_k or roll is not None or pform is not None) and site_sig_cap is not None:
@@ -1076,6 +1109,9 @@ class PyAscore:
             if not rc and qu is not None:
                 rc = self._lib.pya_set_site_quant(self._h, _as_ptr(qu["values"]), qu["values"].shape[0], _as_ptr(qu["row"]), n,
                                                   C.byref(qu["c_params"]))
+            if not rc and pfq is not None:
+                rc = self._lib.pya_set_peptidoform_quant(self._h, _as_ptr(pfq["values"]), pfq["values"].shape[0], _as_ptr(pfq["row"]), n,
+                                                         C.byref(pfq["c_params"]))
             if not rc:
                 rc = self._score_batch_call(b, spec_of, n_spec, mz, it, flags, r, nq)
         finally:
@@ -1130,6 +1166,15 @@ class PyAscore:
             if rc:
                 self._raise(rc)
             out["peptidoforms"] = out["peptidoforms"][:count.value].copy()
+        if pfq is not None:
+            from .rollup import empty_site_quant
+            n_list, n_ch = out["peptidoforms"].size, pfq["params"]["n_channels"]
+            out["peptidoform_quant_head"], out["peptidoform_quant"] = empty_site_quant(n_list, n_ch)
+            rc = self._lib.pya_last_batch_peptidoform_quant(self._h, _as_ptr(out["peptidoform_quant_head"]),
+                                                            _as_ptr(out["peptidoform_quant"]), n_list, n_ch)
+            if rc:
+                self._raise(rc)
+            out["peptidoform_quant_params"] = dict(pfq["params"])
         if mzp is not None:
             out["mz_profile"] = np.zeros(mzp["n_slots"], np.dtype(_lib.MZ_PROFILE_DTYPE))
             rc = self._lib.pya_last_batch_mz_profile(self._h, _as_ptr(out["mz_profile"]), mzp["n_slots"])
@@ -1164,6 +1209,46 @@ class PyAscore:
         if rc:
             self._raise(rc)
         return out[:count.value].copy()
+
+    def peptidoform_quant_reduce(self, a, b):
+        """The merge of two peptidoform quantification pairs on the device (``pya_peptidoform_quant_reduce_host``): ``a`` and
+        ``b`` are ``(list, head, cell)`` triples -- ``PEPTIDOFORM_DTYPE`` records, ``SITE_QUANT_HEAD_DTYPE`` ``[n]`` and
+        ``SITE_QUANT_DTYPE`` ``[n, n_channels]`` --, a pair whose ``head`` and ``cell`` are None counts as having an all-zero
+        table.  Returns the triple of the merged pair: the keys' union in list order, rows of equal keys added field by field.
+        ``pyascore_amd.rollup.merge_peptidoform_quant`` gives the same bytes on the host."""
+        from .rollup import SITE_QUANT_DTYPE, SITE_QUANT_HEAD_DTYPE
+        sides, n_ch = [], None
+        for name, pair in (("a", a), ("b", b)):
+            if pair is None:
+                pair = (np.zeros(0, PEPTIDOFORM_DTYPE), None, None)
+            if len(pair) != 3:
+                raise ValueError("peptidoform_quant_reduce: %s is a (list, head, cell) triple" % name)
+            lst = np.ascontiguousarray(pair[0], PEPTIDOFORM_DTYPE).reshape(-1)
+            if (pair[1] is None) != (pair[2] is None):
+                raise ValueError("peptidoform_quant_reduce: head and cell of %s are both given or both None" % name)
+            head = cell = None
+            if pair[1] is not None:
+                head = np.ascontiguousarray(pair[1], SITE_QUANT_HEAD_DTYPE).reshape(-1)
+                cell = np.ascontiguousarray(pair[2], SITE_QUANT_DTYPE)
+                if head.size != lst.size or cell.ndim != 2 or cell.shape[0] != lst.size:
+                    raise ValueError("peptidoform_quant_reduce: the table of %s is not row-aligned with its list" % name)
+                if n_ch is not None and cell.shape[1] != n_ch:
+                    raise ValueError("peptidoform_quant_reduce: the two tables have different channel counts")
+                n_ch = cell.shape[1]
+            sides.append((lst, head, cell))
+        if n_ch is None:
+            raise ValueError("peptidoform_quant_reduce: neither side has a table to take the channel count from")
+        total = sides[0][0].size + sides[1][0].size
+        out, count = np.zeros(total, PEPTIDOFORM_DTYPE), C.c_uint64(0)
+        head, cell = np.zeros(total, SITE_QUANT_HEAD_DTYPE), np.zeros((total, n_ch), SITE_QUANT_DTYPE)
+        (la, ha, ca), (lb, hb, cb) = sides
+        rc = self._lib.pya_peptidoform_quant_reduce_host(self._h, _as_ptr(la), _as_ptr(ha), _as_ptr(ca), la.size, _as_ptr(lb), _as_ptr(hb),
+                                                         _as_ptr(cb), lb.size, n_ch, _as_ptr(out), _as_ptr(head), _as_ptr(cell), total,
+                                                         C.byref(count))
+        if rc:
+            self._raise(rc)
+        m = count.value
+        return out[:m].copy(), head[:m].copy(), cell[:m].copy()
 
     def site_offsets(self, batch, skip_invalid=False):
         """``site_off`` (int64 ``[n_psm + 1]``) of a batch BEFORE it is scored: where the residue records of every PSM will

@@ -198,7 +198,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
              recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=None, markers=None,
-             marker_rows=None, site_quant=None, site_quant_rows=None):
+             marker_rows=None, site_quant=None, site_quant_rows=None, peptidoform_quant=None, peptidoform_quant_rows=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -253,7 +253,18 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``site_quant``: ``dict(threshold=, scale_log2=, complete_only=)`` as ``PyAscore.score_batch(quant=...)`` takes it, without a
     matrix: the channels are the fixed targets of ``markers``, the rows the spectra, the slots those of ``site_table`` -- it
     needs both.  ``site_quant_rows``: the list that then receives one ``site_quant_fields`` row per site with a contributing
-    record (``write_site_quant_tsv``); no other table changes."""
+    record (``write_site_quant_tsv``); no other table changes.
+    ``peptidoform_quant``: ``dict(threshold=, scale_log2=, complete_only=)`` as ``PyAscore.score_batch(peptidoform_quant=...)``
+    takes it, without a matrix: the channels are the fixed targets ``mz`` of ``markers``, which it needs (``losses`` are no
+    channels).  ``peptidoform_quant_rows``: the list that then receives one ``peptidoform_quant_fields`` row per peptidoform
+    (``write_peptidoform_quant_tsv``); the list is the one ``peptidoform_table`` gets, with ``peptidoform_threshold``."""
+    if peptidoform_quant is not None:                      # (a bad request is refused before anything is read or scored)
+        if not isinstance(peptidoform_quant, dict) or set(peptidoform_quant) - {"threshold", "scale_log2", "complete_only"} \
+                or peptidoform_quant_rows is None:
+            raise ValueError("peptidoform_quant takes a dict of threshold, scale_log2 and complete_only beside a list peptidoform_quant_rows")
+        if not isinstance(markers, dict) or not tuple(markers.get("mz", ())):
+            raise ValueError("peptidoform_quant needs markers with fixed targets mz (its channels)")
+        site_rollup.site_quant_params(n_channels=len(tuple(markers["mz"])), **peptidoform_quant)
     if site_quant is not None:                             # (a bad request is refused before anything is read or scored)
         if not isinstance(site_quant, dict) or set(site_quant) - {"threshold", "scale_log2", "complete_only"} or site_quant_rows is None:
             raise ValueError("site_quant takes a dict of threshold, scale_log2 and complete_only beside a list site_quant_rows")
@@ -294,7 +305,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
                   ranked=ranked_depth if ranked is not None else None)
     keys = None
     form_keys = None
-    if peptidoform_table is not None:
+    if peptidoform_table is not None or peptidoform_quant is not None:
         group, _, form_keys = site_rollup.peptide_groups([p["peptide"] for p in picked])
         stages["peptidoforms"] = dict(group=group, threshold=float(peptidoform_threshold))
     if mz_profile is not None:
@@ -323,6 +334,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         stages["markers"] = dict(markers, precursor_mz=prec_mz, precursor_charge=prec_z)
     if site_quant is not None:
         stages["quant"] = dict(site_quant, values=None)
+    if peptidoform_quant is not None:
+        stages["peptidoform_quant"] = dict(peptidoform_quant, values=None)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything
@@ -372,6 +385,11 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     if peptidoform_table is not None:
         peptidoform_table.extend(peptidoform_table_fields(row, scans)
                                  for row in site_rollup.peptidoform_table(res["peptidoforms"], form_keys, residues=residues))
+    if peptidoform_quant is not None:
+        sums = site_rollup.site_quant_sums(res["peptidoform_quant_head"], res["peptidoform_quant"], res["peptidoform_quant_params"])
+        forms = site_rollup.peptidoform_table(res["peptidoforms"], form_keys, residues=residues)
+        peptidoform_quant_rows.extend(peptidoform_quant_fields(row, scans, res["peptidoform_quant_head"][j], sums[j])
+                                      for j, row in enumerate(forms))
     if coverage is not None:
         cov_ratios = site_rollup.coverage_ratios(res["coverage"])
     rows = []
@@ -486,6 +504,30 @@ def peptidoform_table_fields(row, scans):
     return [row["peptide"], ";".join(str(p) for p in row["sites"]), str(row["n_psm"]), str(row["n_confident"]),
             scans[row["best_psm"]] if row["best_psm"] < len(scans) else "", repr(row["best_min_prob"]), repr(row["best_posterior"]),
             str(np.float32(row["best_min_ascore"])), str(row["n_isomers"])]
+
+
+def peptidoform_quant_columns(mz=()):
+    """The header of the ``--peptidoform_quant`` table: the columns of ``--peptidoform_table``, Records, Complete, then the sum of
+    every channel under the name of its target, ``mz<value>``, in the order of ``--marker_mz``."""
+    return tuple(PEPTIDOFORM_TABLE_COLUMNS) + ("Records", "Complete") + tuple("mz%r" % float(v) for v in mz)
+
+
+def peptidoform_quant_fields(row, scans, head, sums):
+    """One peptidoform with its row of the peptidoform quantification as the fields of the ``--peptidoform_quant`` table: those
+    of ``peptidoform_table_fields``, Records -- the PSMs whose smallest site probability is at or above the quant threshold --,
+    Complete -- those of them with a reading in every channel --, then per channel the summed intensity (``repr``), empty where no
+    reading was summed."""
+    return peptidoform_table_fields(row, scans) + [str(int(head["n_records"])), str(int(head["n_complete"]))] + \
+        ["" if v != v else repr(float(v)) for v in sums]
+
+
+def write_peptidoform_quant_tsv(peptidoform_quant_rows, path, mz=()):
+    """The ``--peptidoform_quant`` table: the rows ``localize(..., peptidoform_quant=dict(...), peptidoform_quant_rows=[])``
+    collected, under ``peptidoform_quant_columns(mz)``."""
+    with open(path, "w") as out:
+        out.write("\t".join(peptidoform_quant_columns(mz)) + "\n")
+        for row in peptidoform_quant_rows:
+            out.write("\t".join("%s" % f for f in row) + "\n")
 
 
 def mz_profile_rows(table, params):

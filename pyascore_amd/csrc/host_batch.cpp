@@ -356,6 +356,33 @@ static int pform_begin(pya_handle *h, pya_handle::PformLoan *loan, uint64_t n_ps
     return PYA_OK;
 }
 
+/* PYA_FLAG_PFORM_QUANT: the loan of pya_set_peptidoform_quant becomes the call's (h->pfq_call; pfq_active says that the
+ * peptidoform hooks below carry a table); the matrix goes to the device once, the two device tables that travel with the two
+ * lists are sized here.  Behind pform_begin. */
+static int pfq_begin(pya_handle *h, uint64_t n_psm, uint32_t flags) {
+    h->pfq_call = h->pfq_loan;
+    h->pfq_loan = pya_handle::QuantLoan{};                    /* (the loan ends with this call, whatever it returns) */
+    const pya_handle::QuantLoan &loan = h->pfq_call;
+    if (!(flags & PYA_FLAG_PEPTIDOFORMS))
+        return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_PFORM_QUANT without PYA_FLAG_PEPTIDOFORMS: the table is row-aligned with the same call's list");
+    if (!loan.set) return h->fail(PYA_ERR_ARG, -1, "PYA_FLAG_PFORM_QUANT without a matrix: call pya_set_peptidoform_quant before the batch call");
+    if (loan.n_psm != n_psm)
+        return h->fail(PYA_ERR_ARG, -1, "pya_set_peptidoform_quant lent the rows of %llu PSMs, the batch has %llu", (unsigned long long)loan.n_psm,
+                       (unsigned long long)n_psm);
+    const size_t n_ch = loan.params.n_channels, n_cell = (size_t)n_psm * n_ch, n_val = (size_t)loan.n_rows * n_ch;
+    HIPCHK(h, hipSetDevice(h->device));
+    for (auto &d : h->d_pfq_head)
+        if (d.n < n_psm || !d.p) HIPCHK(h, d.alloc((size_t)n_psm));
+    for (auto &d : h->d_pfq_cell)
+        if (d.n < n_cell || !d.p) HIPCHK(h, d.alloc(n_cell));
+    if (h->d_pfq_values.n < n_val || !h->d_pfq_values.p) HIPCHK(h, h->d_pfq_values.alloc(n_val));
+    /* (before any stream of the call has work: the chunks' streams do not wait for this one) */
+    if (n_val && n_psm) HIPCHK(h, hipMemcpyAsync(h->d_pfq_values.p, loan.values, n_val * sizeof(double), hipMemcpyHostToDevice, nullptr));
+    HIPCHK(h, hipStreamSynchronize(nullptr));
+    h->pfq_active = true;
+    return PYA_OK;
+}
+
 /* ... the plan's slice of the caller's groups and ids on its way to the device on `st`, in front of the plan's run as the
  * roll-up's slots are (rollup_upload says why), and the workspace for the plan's PSMs and the list so far, which the host
  * knows: the chunk before has been waited for */
@@ -374,6 +401,10 @@ static int pform_upload(pya_handle *h, pya_plan *p, const pya_handle::PformLoan 
     }
     const uint64_t need = pya_peptidoform_workspace_bytes(n + h->pform_len);
     if (h->d_pform_work.n < need || !h->d_pform_work.p) HIPCHK(h, h->d_pform_work.alloc((size_t)need));
+    if (h->pfq_active && h->pfq_call.row) {                   /* (the plan's slice of the caller's rows, as quant_upload sends them) */
+        HIPCHK(h, p->d_pfq_row.alloc((size_t)n));
+        HIPCHK(h, hipMemcpyAsync(p->d_pfq_row.p, h->pfq_call.row + lo, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
     return PYA_OK;
 }
 
@@ -390,9 +421,21 @@ static int pform_behind_run(pya_handle *h, pya_plan *p, const pya_results *d_out
         if (rc) return rc;
     }
     const int cur = h->pform_cur;
-    const int rc = pya_plan_peptidoforms(p, d_out, st, p->d_prob_sites.p, p->d_prob_psms.p, p->d_pform_group.p, loan.threshold,
-                                         loan.psm_id ? p->d_pform_id.p : nullptr, (uint32_t)lo, h->d_pform[cur].p, h->pform_len, h->d_pform_work.p,
-                                         h->d_pform_work.n, h->d_pform[cur ^ 1].p, h->d_pform[cur ^ 1].n, h->d_pform_n.p);
+    /* (with PYA_FLAG_PFORM_QUANT the same list by the same launches, and the table of the list so far goes in beside it) */
+    const pya_handle::QuantLoan &q = h->pfq_call;
+    /* (the rows all three arrays of the result have room for; a list cannot be longer than the batch has PSMs) */
+    /* ... and no more than this call's list can have, since the call clears that many rows of the table */
+    const uint64_t pfq_cap = !h->pfq_active ? 0 : std::min<uint64_t>(std::min<uint64_t>(std::min<uint64_t>(h->d_pform[cur ^ 1].n, h->d_pfq_head[cur ^ 1].n),
+                                                                                        h->d_pfq_cell[cur ^ 1].n / q.params.n_channels), n + h->pform_len);
+    const int rc = h->pfq_active
+        ? pya_plan_peptidoform_quant(p, d_out, st, p->d_prob_sites.p, p->d_prob_psms.p, p->d_pform_group.p, loan.threshold,
+                                     loan.psm_id ? p->d_pform_id.p : nullptr, (uint32_t)lo, h->d_pform[cur].p, h->d_pfq_head[cur].p,
+                                     h->d_pfq_cell[cur].p, h->pform_len, h->d_pfq_values.p, q.n_rows, q.row ? p->d_pfq_row.p : nullptr, (uint32_t)lo,
+                                     &q.params, h->d_pform_work.p, h->d_pform_work.n, h->d_pform[cur ^ 1].p, h->d_pfq_head[cur ^ 1].p,
+                                     h->d_pfq_cell[cur ^ 1].p, pfq_cap, h->d_pform_n.p)
+        : pya_plan_peptidoforms(p, d_out, st, p->d_prob_sites.p, p->d_prob_psms.p, p->d_pform_group.p, loan.threshold,
+                                loan.psm_id ? p->d_pform_id.p : nullptr, (uint32_t)lo, h->d_pform[cur].p, h->pform_len, h->d_pform_work.p,
+                                h->d_pform_work.n, h->d_pform[cur ^ 1].p, h->d_pform[cur ^ 1].n, h->d_pform_n.p);
     if (rc) return rc;
     h->pform_cur = cur ^ 1;
     HIPCHK(h, hipMemcpyAsync(h->pform_n_host, h->d_pform_n.p, sizeof h->pform_n_host, hipMemcpyDeviceToHost, st));
@@ -406,7 +449,7 @@ static int pform_collect(pya_handle *h, pya_plan *p, uint64_t lo) {
     if (h->pform_n_host[1])
         return h->fail(PYA_ERR_STATE, (int64_t)lo, "peptidoforms: %u PSMs from %llu have a best_sig that does not fit their residue records",
                        h->pform_n_host[1], (unsigned long long)lo);
-    return PYA_OK;
+    return h->pfq_active ? pfq_report(p, lo) : PYA_OK;
 }
 
 /* ... and the end of the call: the list comes to the host */
@@ -415,6 +458,19 @@ static int pform_end(pya_handle *h) {
     if (h->pform_len)
         HIPCHK(h, hipMemcpy(h->pform_host.data(), h->d_pform[h->pform_cur].p, (size_t)h->pform_len * sizeof(pya_peptidoform), hipMemcpyDeviceToHost));
     h->pform_valid = true;
+    if (h->pfq_active) {                                      /* (the table of that list, row-aligned with it) */
+        const size_t n_ch = h->pfq_call.params.n_channels;
+        h->pfq_head_host.assign((size_t)h->pform_len, pya_site_quant_head{});
+        h->pfq_cell_host.assign((size_t)h->pform_len * n_ch, pya_site_quant{});
+        if (h->pform_len) {
+            HIPCHK(h, hipMemcpy(h->pfq_head_host.data(), h->d_pfq_head[h->pform_cur].p, (size_t)h->pform_len * sizeof(pya_site_quant_head),
+                                hipMemcpyDeviceToHost));
+            HIPCHK(h, hipMemcpy(h->pfq_cell_host.data(), h->d_pfq_cell[h->pform_cur].p, (size_t)h->pform_len * n_ch * sizeof(pya_site_quant),
+                                hipMemcpyDeviceToHost));
+        }
+        h->pfq_channels = (uint32_t)n_ch;
+        h->pfq_valid = true;
+    }
     return PYA_OK;
 }
 
@@ -850,6 +906,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     h->mzp_valid = false;
     h->quant_valid = false;
     h->cov_valid = false;
+    h->pfq_valid = false;
+    h->pfq_active = false;
     pya_handle::RollupLoan loan;
     if (flags & PYA_FLAG_ROLLUP) {
         const int rc_ru = rollup_begin(h, &loan);
@@ -859,6 +917,10 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if (flags & PYA_FLAG_PEPTIDOFORMS) {
         const int rc_pf = pform_begin(h, &pf_loan, b->n_psm);
         if (rc_pf) return rc_pf;
+    }
+    if (flags & PYA_FLAG_PFORM_QUANT) {
+        const int rc_pfq = pfq_begin(h, b->n_psm, flags);
+        if (rc_pfq) return rc_pfq;
     }
     pya_handle::MzpLoan mzp_loan;
     if (flags & PYA_FLAG_MZ_PROFILE) {
@@ -954,8 +1016,8 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
         const int rc_rk = ranked_host_block(h, b);
         if (rc_rk) return rc_rk;
     }
-    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS, _MZ_PROFILE, _COVERAGE, _QUANT or _RECALIBRATE takes the plan's launches: the one-PSM kernel stays as it is) */
-    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_QUANT | PYA_FLAG_RECALIBRATE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
+    /* (a batch of one with PYA_FLAG_EVIDENCE, _IONS, _SITES, _PROBS, _RANKED, _ROLLUP, _PEPTIDOFORMS, _MZ_PROFILE, _COVERAGE, _QUANT, _PFORM_QUANT or _RECALIBRATE takes the plan's launches: the one-PSM kernel stays as it is) */
+    if (b->n_psm == 1 && !sh && !(flags & (PYA_FLAG_SKIP_INVALID | PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_QUANT | PYA_FLAG_PFORM_QUANT | PYA_FLAG_RECALIBRATE)) && !nq && !one_view_live && types == PYA_SPEC_F64_F64) {
         /* a batch of one is PyAscore.score: the low-latency path (it declines what it has no room for; float64 only) */
         const bool has_aux1 = b->aux_off && b->aux_pos && b->aux_mass;
         const int64_t a0 = has_aux1 ? b->aux_off[0] : 0, a1 = has_aux1 ? b->aux_off[1] : 0;
@@ -1165,6 +1227,7 @@ static int score_batch_shared(pya_handle *h, const pya_batch *b, const uint32_t 
     h->mzp_valid = false;
     h->quant_valid = false;
     h->cov_valid = false;
+    h->pfq_valid = false;
     if (b->n_psm == 0) return score_batch_impl(h, b, nullptr, sp, flags, out, nq);
     if (!b->peak_off) return h->fail(PYA_ERR_ARG, -1, "NULL array in batch");
     const int rc = check_spec_of(h, b->n_psm, spec_of, n_spectra);

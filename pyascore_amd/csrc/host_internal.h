@@ -167,6 +167,11 @@ int pya_launch_pform(const int64_t *d_site_off, uint64_t n_psm, const void *d_si
                      double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const uint64_t *best_sig, const float *ascores, uint32_t max_k,
                      const void *d_src0, uint64_t n0, const void *d_src1, uint64_t n1, void *d_work, void *d_out, uint64_t cap, uint32_t *d_n,
                      hipEvent_t *phase, hipStream_t stream);
+int pya_launch_pform_quant(const int64_t *d_site_off, uint64_t n_psm, const void *d_site_probs, const void *d_psm_probs, const int32_t *d_group,
+                           const uint64_t *best_sig, uint32_t max_k, const void *d_src0, const void *d_head0, const void *d_cell0, uint64_t n0,
+                           const void *d_src1, const void *d_head1, const void *d_cell1, uint64_t n1, const double *d_values, uint64_t n_rows,
+                           const int32_t *d_row, uint32_t row_base, const pya_site_quant_params *prm, double scale, const void *d_list,
+                           const uint32_t *d_n, void *d_head, void *d_cell, uint64_t cap, uint32_t *d_over, hipStream_t stream);
 int pya_launch_localize_redo(const BatchDev *b, const uint32_t *d_count, const uint32_t *d_ids, uint32_t n_max,
                              uint32_t push_cap, uint32_t n_cap, uint32_t pos_cap, uint32_t pool_cap, uint32_t sb,
                              uint32_t gtp, hipStream_t stream);
@@ -468,6 +473,19 @@ struct pya_handle {
     std::vector<pya_site_quant> quant_cell_host;
     uint32_t quant_channels = 0;
     bool quant_valid = false;
+    /* PYA_FLAG_PFORM_QUANT: what pya_set_peptidoform_quant lent for the next batch call and, while such a call runs, the loan
+     * as the call's own (pfq_active); the device copy of the matrix, the two device tables that travel with the two lists of
+     * PYA_FLAG_PEPTIDOFORMS (d_pfq_head[i] / d_pfq_cell[i] is row-aligned with d_pform[i]) and the table of the last such
+     * call on the host, row-aligned with pform_host */
+    QuantLoan pfq_loan, pfq_call;
+    bool pfq_active = false;
+    DevBuf<double> d_pfq_values;
+    DevBuf<pya_site_quant_head> d_pfq_head[2];
+    DevBuf<pya_site_quant> d_pfq_cell[2];
+    std::vector<pya_site_quant_head> pfq_head_host;
+    std::vector<pya_site_quant> pfq_cell_host;
+    uint32_t pfq_channels = 0;
+    bool pfq_valid = false;
     /* PYA_FLAG_COVERAGE: the records of the last batch call, pinned like the evidence rows so that a chunk's records come
      * back asynchronously behind its results (pya_last_batch_coverage copies them out) */
     pya_coverage *cov_host = nullptr;
@@ -860,6 +878,12 @@ struct pya_plan {
     hipEvent_t ev_quant = nullptr;
     bool quant_asked = false;
     DevBuf<int32_t> d_quant_row;
+    /* pya_plan_peptidoform_quant: the report of the last call (PSMs whose row is at or above the call's n_rows), as for the
+     * site quantification; a pya_score_batch plan's slice of the caller's rows */
+    DevBuf<uint32_t> d_pfq_over;
+    hipEvent_t ev_pfq = nullptr;
+    bool pfq_asked = false;
+    DevBuf<int32_t> d_pfq_row;
     /* pya_plan_coverage: the raw peak caps of its two launches (the largest spectrum of a PSM inside the fast limits, of a
      * general PSM; once per plan), the event behind the last call's kernels (a later call, on whatever stream, writes
      * behind them) and a pya_score_batch plan's records */
@@ -886,6 +910,7 @@ struct pya_plan {
         if (ev_rollup) (void)hipEventDestroy(ev_rollup);
         if (ev_mzp) (void)hipEventDestroy(ev_mzp);
         if (ev_quant) (void)hipEventDestroy(ev_quant);
+        if (ev_pfq) (void)hipEventDestroy(ev_pfq);
         if (ev_cov) (void)hipEventDestroy(ev_cov);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
@@ -1011,6 +1036,17 @@ int mzp_report(pya_plan *p, uint64_t psm_lo);
  * of a plan's last pya_plan_site_quant (psm_lo as for rollup_report) */
 int quant_check(pya_handle *h, const char *who, uint64_t n_slots, uint64_t n_rows, const pya_site_quant_params *prm);
 int quant_report(pya_plan *p, uint64_t psm_lo);
+/* host_pform_quant.cpp: what the peptidoform quantification calls refuse beyond pform_check and quant_check (the tables of
+ * the call and of the earlier lists), and the stage on `st`: the list by pform_run, then csrc/pform_quant.hip behind it;
+ * host_run.cpp: the report of a plan's last pya_plan_peptidoform_quant (psm_lo as for rollup_report) */
+int pfq_check(pya_handle *h, const char *who, const void *d_head0, const void *d_cell0, const void *d_head1, const void *d_cell1,
+              const void *d_head, const void *d_cell, uint64_t cap);
+int pfq_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const void *d_site_probs, const void *d_psm_probs, const int32_t *d_group,
+            double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const uint64_t *best_sig, const float *ascores, uint32_t max_k,
+            const void *d_src0, const void *d_head0, const void *d_cell0, uint64_t n0, const void *d_src1, const void *d_head1, const void *d_cell1,
+            uint64_t n1, const double *d_values, uint64_t n_rows, const int32_t *d_row, uint32_t row_base, const pya_site_quant_params *prm,
+            void *d_work, void *d_out, void *d_head, void *d_cell, uint64_t cap, uint32_t *d_n, uint32_t *d_over, bool run, hipStream_t st);
+int pfq_report(pya_plan *p, uint64_t psm_lo);
 /* host_coverage.cpp: PYA_FLAG_COVERAGE of the batch calls -- the handle's pinned block for the records of a batch of n PSMs
  * (zeroed: a PSM no plan reaches has a PYA_COV_NONE record), and the stage behind a plan's kernels on `st` with its records
  * on their way into the block at PSM `lo` (asynchronous: whoever waits for the chunk's results waits for them too) */

@@ -196,6 +196,7 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
     h->mzp_valid = false;
     h->quant_valid = false;
     h->pform_valid = false;
+    h->pfq_valid = false;
     h->cov_valid = false;
     if (flags & PYA_FLAG_COVERAGE)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_COVERAGE: score the PSM as a batch of one (pya_score_batch)");
@@ -213,6 +214,8 @@ extern "C" int pya_score_one(pya_handle *h, const double *mz, const double *inte
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_PEPTIDOFORMS: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_QUANT)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_QUANT: score the PSM as a batch of one (pya_score_batch)");
+    if (flags & PYA_FLAG_PFORM_QUANT)
+        return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_PFORM_QUANT: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_MZ_PROFILE)
         return h->fail(PYA_ERR_ARG, -1, "pya_score_one does not take PYA_FLAG_MZ_PROFILE: score the PSM as a batch of one (pya_score_batch)");
     if (flags & PYA_FLAG_RECALIBRATE)

@@ -73,7 +73,7 @@ int run_tiny(pya_plan *p, const BatchDev &d, uint32_t types, hipStream_t st, boo
     *done = false;
     /* (the tiny kernel bins per PSM from the PSM's own float64 peaks: a shared batch and a batch with float32 arrays,
      * however small, take the plan's launches) */
-    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_QUANT | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
+    if ((p->flags & (PYA_FLAG_TIMING | PYA_FLAG_EVIDENCE | PYA_FLAG_IONS | PYA_FLAG_NAMED | PYA_FLAG_ROLLUP | PYA_FLAG_PEPTIDOFORMS | PYA_FLAG_MZ_PROFILE | PYA_FLAG_COVERAGE | PYA_FLAG_QUANT | PYA_FLAG_PFORM_QUANT | PYA_FLAG_SITES | PYA_FLAG_PROBS | PYA_FLAG_RANKED)) || p->n_psm > (uint64_t)h->kn.tiny_max || p->n_skipped != 0 || h->kn.no_tiny || !p->gen_ids.empty() ||
         p->shared || types != PYA_SPEC_F64_F64)
         return PYA_OK;
     /* caps that cover every PSM of the batch (the PSMs the fused kernel would take are accounted in their own bucket: its
@@ -340,6 +340,7 @@ int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_strea
     p->rollup_asked = false;
     p->mzp_asked = false;
     p->quant_asked = false;
+    p->pfq_asked = false;
     p->dev = d;
     return rc;
 }
@@ -456,6 +457,19 @@ int quant_report(pya_plan *p, uint64_t psm_lo) {
                    "n_slots or a row at or above the n_rows of the call; nothing of them was written", over[0], (unsigned long long)first);
 }
 
+/* ... and the last pya_plan_peptidoform_quant of this run: PSMs whose row is not inside the matrix of the call */
+int pfq_report(pya_plan *p, uint64_t psm_lo) {
+    pya_handle *h = p->h;
+    if (!p->pfq_asked) return PYA_OK;
+    uint32_t over[2] = {0u, 0u};
+    HIPCHK(h, hipEventSynchronize(p->ev_pfq));
+    HIPCHK(h, hipMemcpy(over, p->d_pfq_over.p, sizeof(over), hipMemcpyDeviceToHost));
+    if (!over[0]) return PYA_OK;
+    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
+    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_peptidoform_quant: %u PSMs (PSM %llu the first) name a row at or above the n_rows of "
+                   "the call; nothing of them was written to the table", over[0], (unsigned long long)first);
+}
+
 int pya_plan_check(pya_plan *p) {
     if (!p) return PYA_ERR_ARG;
     pya_handle *h = p->h;
@@ -490,6 +504,8 @@ int pya_plan_check(pya_plan *p) {
     if (rc_mzp) return rc_mzp;
     const int rc_qu = quant_report(p, 0);
     if (rc_qu) return rc_qu;
+    const int rc_pfq = pfq_report(p, 0);
+    if (rc_pfq) return rc_pfq;
     if (p->ions_state != 2) return PYA_OK;
     /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
     HIPCHK(h, hipEventSynchronize(p->ev_ions));
@@ -947,6 +963,59 @@ int pya_plan_peptidoforms(pya_plan *p, const pya_results *r, void *hip_stream, c
     }
     return pform_run(h, p->n_psm ? p->d_site_off.p : nullptr, p->n_psm, d_site_probs, d_psm_probs, d_group, threshold, d_psm_id, psm_base,
                      r->best_sig, r->ascores, r->max_k, d_prev, n_prev, nullptr, 0, d_work, d_out, cap, d_n, run, st);
+}
+
+/* The peptidoform quantification (csrc/pform_quant.hip): pya_plan_peptidoforms' checks, wait and offsets, the list by the same
+ * launches, the table behind them; the report of rows outside the matrix goes the way of pya_plan_site_quant's. */
+int pya_plan_peptidoform_quant(pya_plan *p, const pya_results *r, void *hip_stream, const pya_site_prob *d_site_probs, const pya_psm_prob *d_psm_probs,
+                               const int32_t *d_group, double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const pya_peptidoform *d_prev,
+                               const pya_site_quant_head *d_prev_head, const pya_site_quant *d_prev_cell, uint64_t n_prev, const double *d_values,
+                               uint64_t n_rows, const int32_t *d_row, uint32_t row_base, const pya_site_quant_params *prm, void *d_work,
+                               uint64_t work_bytes, pya_peptidoform *d_out, pya_site_quant_head *d_head, pya_site_quant *d_cell, uint64_t cap,
+                               uint32_t *d_n) {
+    if (!p || !r) return PYA_ERR_ARG;
+    pya_handle *h = p->h;
+    const char *who = "pya_plan_peptidoform_quant";
+    int rc = quant_check(h, who, 0, n_rows, prm);
+    if (rc) return rc;
+    bool run;
+    if ((rc = pform_check(h, who, p->n_psm, d_prev, n_prev, d_work, work_bytes, d_out, cap, d_n, &run))) return rc;
+    if ((rc = pfq_check(h, who, d_prev_head, d_prev_cell, nullptr, nullptr, d_head, d_cell, cap))) return rc;
+    uint64_t n_rec = 0;
+    if (p->n_psm) {
+        if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "%s: the plan has not been run", who);
+        site_offsets(p);
+        n_rec = (uint64_t)p->site_off[p->n_psm];
+        if (!d_psm_probs || !d_group || (n_rec && !d_site_probs) || !r->best_sig || !r->ascores || (n_rows && !d_values))
+            return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to %s", who);
+        if (r->max_k < p->max_k)
+            return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)", r->max_k, p->max_k);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (p->n_psm) {
+        if (!p->d_pfq_over.p) HIPCHK(h, p->d_pfq_over.alloc(2));
+        if (!p->ev_pfq) HIPCHK(h, hipEventCreateWithFlags(&p->ev_pfq, hipEventDisableTiming));
+        if (st != p->last_stream) {                             /* (behind the run, as pya_plan_rollup waits for it) */
+            if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
+            HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
+            HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
+        }
+        const int rc_off = site_offsets_on_device(p, st);
+        if (rc_off) return rc_off;
+        /* (behind an earlier call's kernel, on whatever stream it was: it reports into the same two words) */
+        if (p->pfq_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_pfq, 0));
+        HIPCHK(h, hipMemsetAsync(p->d_pfq_over.p, 0, 2 * sizeof(uint32_t), st));
+    }
+    rc = pfq_run(h, p->n_psm ? p->d_site_off.p : nullptr, p->n_psm, d_site_probs, d_psm_probs, d_group, threshold, d_psm_id, psm_base, r->best_sig,
+                 r->ascores, r->max_k, d_prev, d_prev_head, d_prev_cell, n_prev, nullptr, nullptr, nullptr, 0, d_values, n_rows, d_row, row_base, prm,
+                 d_work, d_out, d_head, d_cell, cap, d_n, p->n_psm ? p->d_pfq_over.p : nullptr, run, st);
+    if (rc) return rc;
+    if (p->n_psm) {
+        HIPCHK(h, hipEventRecord(p->ev_pfq, st));
+        p->pfq_asked = true;
+    }
+    return PYA_OK;
 }
 
 /* The mass-error profile (csrc/mz_profile.hip): the wait and the two lists of the evidence stage, with the longest peptide of

@@ -30,13 +30,12 @@
  * as 0xffffffff - psm) and nothing of it is written; a row below n_rows is the only index values is read at.
  *
  * pya_marker_values_kernel, the second kernel: marker records to a channel matrix, one thread per element. */
-#include "device_common.hip.h"
+#include "quant_rule.hip.h"
 #include "../../include/pyascore_hip.h"
 
 #define SQ_SCORED 1u                  /* PYA_SITE_SCORED */
 #define SQ_THREADS 256
 #define SQ_UNROLL 4                   /* rows in flight per lane in step 3 */
-#define SQ_SAT 281474976710656.0      /* 2^48 */
 
 struct SqArgs {
     const int64_t *site_off;          /* [n_psm + 1] */
@@ -114,16 +113,13 @@ __global__ void __launch_bounds__(SQ_THREADS) pya_site_quant_kernel(const SqArgs
 #pragma unroll
             for (int u = 0; u < SQ_UNROLL; u++) {
                 if (!have[u]) break;
-                const bool usable = mine && v[u] == v[u] && v[u] > 0.0;
+                const bool usable = mine && qr_usable(v[u]);
                 const bool complete = (uint32_t)__popcll(__ballot(usable)) == a.n_ch;
                 n_complete += complete ? 1u : 0u;
                 if (usable && (complete || !a.complete_only)) {
-                    const double t = v[u] * a.scale;
-                    if (t >= SQ_SAT) {
-                        sum += 1ull << 48;
-                        n_sat++;
-                    } else
-                        sum += (uint64_t)t;
+                    bool sat;
+                    sum += qr_quantum(v[u], a.scale, &sat);
+                    n_sat += sat ? 1u : 0u;
                     n++;
                 }
             }

@@ -39,7 +39,7 @@ class DevicePlan:
     it (``pya_mz_profile_fit``, ``pya_recalibrate_spectra``), so run -> profile -> fit -> correct -> run again needs no host copy."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
-                 ranked=False, rollup=False, peptidoforms=False, mz_profile=False, coverage=False, quant=False):
+                 ranked=False, rollup=False, peptidoforms=False, mz_profile=False, coverage=False, quant=False, peptidoform_quant=False):
         import torch
         if not isinstance(scorer, PyAscore):
             raise TypeError("scorer must be a pyascore_amd.PyAscore")
@@ -72,7 +72,7 @@ class DevicePlan:
             (_lib.PYA_FLAG_PROBS if probs else 0) | (_lib.PYA_FLAG_RANKED if ranked else 0) | \
             (_lib.PYA_FLAG_ROLLUP if rollup else 0) | (_lib.PYA_FLAG_PEPTIDOFORMS if peptidoforms else 0) | \
             (_lib.PYA_FLAG_MZ_PROFILE if mz_profile else 0) | (_lib.PYA_FLAG_COVERAGE if coverage else 0) | \
-            (_lib.PYA_FLAG_QUANT if quant else 0)
+            (_lib.PYA_FLAG_QUANT if quant else 0) | (_lib.PYA_FLAG_PFORM_QUANT if peptidoform_quant else 0)
         if batch.get("spec_of") is not None:
             # shared spectra (synth.pack_shared_batch): peak_off describes the spectra, spec_of names every PSM's
             spec_of = m["spec_of"] = np.ascontiguousarray(batch["spec_of"], np.uint32)
@@ -458,6 +458,106 @@ class DevicePlan:
             self.scorer._raise(rc)
         work.record_stream(stream)
         return records, n
+
+    def _pfq_table(self, pair, what, n_ch):
+        """an input pair ``(records, head, cell)`` (head and cell None: an all-zero table) checked: (records, n, head, cell)"""
+        torch = self._torch
+        if pair is None:
+            return None, 0, None, None
+        if len(pair) != 3:
+            raise ValueError("%s must be a (records, head, cell) triple" % what)
+        records, n = self._pform_records(pair[0], what)
+        head, cell = pair[1], pair[2]
+        if (head is None) != (cell is None):
+            raise ValueError("%s: head and cell are both given or both None" % what)
+        if head is not None and (head.dtype != torch.uint8 or tuple(head.shape) != (n, 8) or not head.is_contiguous() or not head.is_cuda
+                                 or cell.dtype != torch.uint8 or tuple(cell.shape) != (n, n_ch, 16) or not cell.is_contiguous()
+                                 or not cell.is_cuda):
+            raise ValueError("%s: the table must be contiguous uint8 device tensors of shapes (%d, 8) and (%d, %d, 16)" % (what, n, n, n_ch))
+        return records, n, head, cell
+
+    def _pfq_buffers(self, n_entries, n_ch, cap):
+        torch = self._torch
+        cap = n_entries if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError("cap must not be negative")
+        work_bytes = int(self._lib.pya_peptidoform_quant_workspace_bytes(n_entries, n_ch))
+        with torch.cuda.device(self.device):
+            work = torch.empty(max(work_bytes, 1), dtype=torch.uint8, device=self.device)
+            records = torch.empty((cap, 48), dtype=torch.uint8, device=self.device)
+            head = torch.empty((cap, 8), dtype=torch.uint8, device=self.device)
+            cell = torch.empty((cap, n_ch, 16), dtype=torch.uint8, device=self.device)
+            n = torch.empty(2, dtype=torch.int32, device=self.device)
+        return work, work_bytes, records, head, cell, cap, n
+
+    def peptidoform_quant(self, site_probs, psm_probs, group, values, params, threshold=0.75, psm_id=None, psm_base=0, row=None, row_base=0,
+                          prev=None, cap=None):
+        """The peptidoform quantification of the last ``run()`` (``pya_plan_peptidoform_quant``): the list ``peptidoforms()``
+        gives for the same arguments, byte for byte, and row-aligned with it the channel sums of the PSMs that contribute to
+        the list with ``min_prob >= params["threshold"]``.  ``site_probs`` / ``psm_probs`` / ``group`` / ``threshold`` /
+        ``psm_id`` / ``psm_base`` as for ``peptidoforms()``; ``values`` / ``params`` / ``row`` / ``row_base`` as for
+        ``site_quant()``; ``prev``: an earlier pair ``(records, head, cell)`` of device tensors (only read; head and cell None:
+        an all-zero table) -- the result is then the pair over the PSMs behind both; ``cap``: the room of the result.  Returns
+        device tensors ``(records, head, cell, n)``: ``torch.uint8 [cap, 48]``, ``[cap, 8]``, ``[cap, n_channels, 16]`` (rows
+        behind the list are zero bytes in the table) and ``torch.int32 [2]`` as for ``peptidoforms()``.  Everything is launched
+        on torch's current stream and nothing waits on the host; a PSM whose row lies at or above ``n_rows`` writes nothing to
+        the table and is reported by ``check()``."""
+        from .rollup import site_quant_c_params
+        torch = self._torch
+        c_params = site_quant_c_params(params)
+        n_ch = int(c_params.n_channels)
+        n_rec = int(self.site_offsets()[-1])
+        if group.dtype != torch.int32 or tuple(group.shape) != (self.n_psm,) or not group.is_contiguous() or not group.is_cuda:
+            raise ValueError("group must be a contiguous int32 device tensor of %d entries" % self.n_psm)
+        if site_probs.dtype != torch.float64 or tuple(site_probs.shape) != (n_rec, 2) or not site_probs.is_contiguous() or not site_probs.is_cuda \
+                or psm_probs.dtype != torch.uint8 or tuple(psm_probs.shape) != (self.n_psm, 16) or not psm_probs.is_contiguous() or not psm_probs.is_cuda:
+            raise ValueError("site_probs and psm_probs must be the tensors of probs()")
+        if psm_id is not None and (psm_id.element_size() != 4 or psm_id.is_floating_point() or tuple(psm_id.shape) != (self.n_psm,)
+                                   or not psm_id.is_contiguous() or not psm_id.is_cuda):
+            raise ValueError("psm_id must be a contiguous 32-bit integer device tensor of %d entries" % self.n_psm)
+        if values.dtype != torch.float64 or values.dim() != 2 or values.shape[1] != n_ch or not values.is_contiguous() or not values.is_cuda:
+            raise ValueError("values must be a contiguous float64 device tensor of shape (n_rows, %d)" % n_ch)
+        if row is not None and (row.dtype != torch.int32 or tuple(row.shape) != (self.n_psm,) or not row.is_contiguous() or not row.is_cuda):
+            raise ValueError("row must be a contiguous int32 device tensor of %d entries" % self.n_psm)
+        prev, n_prev, p_head, p_cell = self._pfq_table(prev, "prev", n_ch)
+        work, work_bytes, records, head, cell, cap, n = self._pfq_buffers(self.n_psm + n_prev, n_ch, cap)
+        stream = torch.cuda.current_stream(self.device)
+        ptr = lambda t: None if t is None or not t.numel() else t.data_ptr()  # noqa: E731
+        rc = self._lib.pya_plan_peptidoform_quant(self._plan, C.byref(self._res), stream.cuda_stream, site_probs.data_ptr(), psm_probs.data_ptr(),
+                                                  group.data_ptr(), float(threshold), None if psm_id is None else psm_id.data_ptr(),
+                                                  int(psm_base), ptr(prev), ptr(p_head), ptr(p_cell), n_prev, ptr(values), values.shape[0],
+                                                  None if row is None else row.data_ptr(), int(row_base), C.byref(c_params), work.data_ptr(),
+                                                  work_bytes, ptr(records), ptr(head), ptr(cell), cap, n.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        work.record_stream(stream)                 # (the caching allocator must not hand the workspace on before the stream is past it)
+        return records, head, cell, n
+
+    def peptidoform_quant_reduce(self, a, b=None, n_channels=None, cap=None):
+        """The merge of two peptidoform quantification pairs on the device (``pya_peptidoform_quant_reduce``): ``a`` and ``b``
+        are ``(records, head, cell)`` triples of device tensors as ``peptidoform_quant()`` returns them cut to their length (any
+        order, keys may repeat, records with ``n_psm == 0`` are skipped with their rows; head and cell None: an all-zero table).
+        ``n_channels`` is needed only when neither side has a table.  Returns ``(records, head, cell, n)`` as
+        ``peptidoform_quant()`` does; the inputs are only read."""
+        torch = self._torch
+        n_ch = n_channels
+        for pair in (a, b):
+            if pair is not None and len(pair) == 3 and pair[2] is not None and pair[2].dim() == 3:
+                n_ch = int(pair[2].shape[1])
+        if n_ch is None:
+            raise ValueError("peptidoform_quant_reduce: neither side has a table; pass n_channels")
+        ra, n_a, ha, ca = self._pfq_table(a, "a", n_ch)
+        rb, n_b, hb, cb = self._pfq_table(b, "b", n_ch)
+        work, work_bytes, records, head, cell, cap, n = self._pfq_buffers(n_a + n_b, n_ch, cap)
+        stream = torch.cuda.current_stream(self.device)
+        ptr = lambda t: None if t is None or not t.numel() else t.data_ptr()  # noqa: E731
+        rc = self._lib.pya_peptidoform_quant_reduce(self.scorer._h, ptr(ra), ptr(ha), ptr(ca), n_a, ptr(rb), ptr(hb), ptr(cb), n_b, int(n_ch),
+                                                    stream.cuda_stream, work.data_ptr(), work_bytes, ptr(records), ptr(head), ptr(cell), cap,
+                                                    n.data_ptr())
+        if rc:
+            self.scorer._raise(rc)
+        work.record_stream(stream)
+        return records, head, cell, n
 
     def mz_profile(self, params, run=None, n_slots=None, table=None):
         """Adds the fragment mass errors of the last ``run()`` to ``table`` (``pya_plan_mz_profile``): a ``torch.uint8`` device

@@ -61,6 +61,11 @@ that place the modification on the site confidently (``SITE_QUANT_HEAD_DTYPE`` /
 ``pya_site_quant_head`` and the 16-byte ``pya_site_quant``); ``site_quant_params`` checks and fills the parameters,
 ``site_quant`` restates the stage over the probability records with integer sums (equal bytes), ``merge_site_quant`` adds tables
 and ``site_quant_sums`` turns one into intensities.
+
+Peptidoform quantification: ``score_batch(peptidoforms=..., peptidoform_quant=...)`` returns the peptidoform list and, row-aligned
+with it, the same head / cell records per peptidoform and channel; ``peptidoform_quant`` restates the pair over the probability
+records (the list through ``merge_peptidoforms``, integer sums, equal bytes), ``merge_peptidoform_quant`` merges pairs and
+``site_quant_sums`` turns the table into intensities.
 """
 import numpy as np
 
@@ -1512,7 +1517,179 @@ def merge_site_quant(*tables):
 
 def site_quant_sums(head, cell, params):
     """The channel sums of a table in intensity units: float64 ``[n_slots, n_channels]``, ``sum / 2^scale_log2``, NaN where no
-    reading was summed (``n == 0``)."""
+    reading was summed (``n == 0``).  The head / cell arrays of a peptidoform quantification (``peptidoform_quant``,
+    ``score_batch(peptidoform_quant=...)``) are tables of the same records: they go through unchanged, one row per peptidoform."""
     p = check_site_quant_params(params)
     head, cell = _site_quant_table((head, cell), "site_quant_sums")
     return np.where(cell["n"] != 0, cell["sum"].astype(np.float64) * 2.0 ** -p["scale_log2"], np.nan)
+
+
+def _pfq_place(records):
+    """(group, sig_bits) -> row of a peptidoform list"""
+    return {(int(g), int(b)): j for j, (g, b) in enumerate(zip(records["group"].tolist(), records["sig_bits"].tolist()))}
+
+
+def _pfq_pair(pair, what):
+    """a pair as (list, head, cell); head and cell None: an all-zero table"""
+    if len(pair) != 3:
+        raise ValueError("%s: a pair is (list, head, cell)" % what)
+    records = np.ascontiguousarray(pair[0], PEPTIDOFORM_DTYPE).reshape(-1)
+    if (pair[1] is None) != (pair[2] is None):
+        raise ValueError("%s: head and cell of a pair are both given or both None" % what)
+    if pair[1] is None:
+        return records, None, None
+    head, cell = _site_quant_table((pair[1], pair[2]), what)
+    if head.size != records.size:
+        raise ValueError("%s: the table of a pair is not row-aligned with its list" % what)
+    return records, head, cell
+
+
+def _pfq_add_rows(place, head, cell, pair):
+    """the rows of ``pair`` (records with n_psm != 0) added to the rows of their keys; a key without a place (behind cap) is left out"""
+    records, h, c = pair
+    if h is None:
+        return
+    keep = np.flatnonzero(records["n_psm"] != 0)
+    at = np.array([place.get((int(records["group"][j]), int(records["sig_bits"][j])), -1) for j in keep], np.int64)
+    keep, at = keep[at >= 0], at[at >= 0]
+    for f in ("n_records", "n_complete"):
+        np.add.at(head[f], at, h[f][keep])
+    for f in ("sum", "n", "n_saturated"):
+        np.add.at(cell[f], at, c[f][keep])
+
+
+def _pfq_min_prob(site_probs, psm_probs, site_off, sig, group):
+    """(in_list, min_prob, k) per PSM: whether the PSM contributes to the peptidoform list, the smallest with_prob over the
+    residues of its best_sig as bit patterns (1.0 for best_sig == 0; of no meaning where not in_list) and their number"""
+    n = site_off.size - 1
+    in_list = (psm_probs["kind"] == _lib.PYA_SITE_SCORED) & (group >= 0)
+    sig = np.where(in_list, sig, np.uint64(0))
+    n_res = np.diff(site_off)
+    pbits = np.ascontiguousarray(site_probs["with_prob"]).view(np.uint64)
+    prob = np.where(sig != 0, np.uint64(0xFFFFFFFFFFFFFFFF), np.float64(1.0).view(np.uint64))
+    k = np.zeros(n, np.int64)
+    for r in range(64):
+        has = ((sig >> np.uint64(r)) & np.uint64(1)) != 0
+        if not has.any():
+            continue
+        if (n_res[has] <= r).any():
+            raise ValueError("peptidoform_quant: PSM %d has a best_sig that does not fit its residue records" % int(np.flatnonzero(has & (n_res <= r))[0]))
+        prob[has] = np.minimum(prob[has], pbits[site_off[:-1][has] + r])
+        k += has
+    return in_list, prob.view(np.float64), k
+
+
+def peptidoform_min_prob(site_probs, psm_probs, site_off, best_sig, group):
+    """``min_prob`` of every PSM as the peptidoform stages compute it (float64 ``[n_psm]``; NaN for a PSM that does not
+    contribute to the list): what ``peptidoform_quant``'s threshold is compared with -- its median makes about half of the
+    listed PSMs contribute."""
+    site_off = np.asarray(site_off, np.int64)
+    in_list, min_prob, _ = _pfq_min_prob(np.asarray(site_probs, np.dtype(_lib.SITE_PROB_DTYPE)), np.asarray(psm_probs, np.dtype(_lib.PSM_PROB_DTYPE)),
+                                         site_off, np.asarray(best_sig).astype(np.uint64), np.asarray(group).astype(np.int64))
+    return np.where(in_list, min_prob, np.nan)
+
+
+def peptidoform_quant(site_probs, psm_probs, site_off, best_sig, ascores, group, values, row, params, threshold=0.75, psm_id=None,
+                      psm_base=0, prev=None, cap=None):
+    """The pair ``score_batch(peptidoforms=dict(group=, threshold=, psm_id=), peptidoform_quant=...)`` returns, from the
+    probability records of the same batch (``score_batch(probs=True)``: ``site_probs``, ``psm_probs``, ``site_off``), its
+    ``best_sig`` and ``ascores``: the peptidoform quantification of ``include/pyascore_hip.h`` restated in numpy, with the same
+    bytes.  The list goes through ``merge_peptidoforms`` (every contributing PSM a record with ``n_psm == 1``), the table is
+    row-aligned with it.  ``values`` / ``row`` / ``params`` as for ``site_quant``; ``threshold`` is the list's ("confident"),
+    ``params["threshold"]`` the table's; ``prev``: an earlier pair ``(list, head, cell)`` (head and cell None: an all-zero table) --
+    the result is then the pair over the PSMs behind both; ``cap``: only the first ``cap`` rows are kept, a key behind them adds
+    nothing.  A PSM that would contribute but names a row at or above ``n_rows`` is a ValueError (the library answers
+    PYA_ERR_LIMIT), as is a ``best_sig`` that does not fit the residue records.  Returns ``(list, head, cell)``:
+    ``PEPTIDOFORM_DTYPE[n]``, ``SITE_QUANT_HEAD_DTYPE[n]``, ``SITE_QUANT_DTYPE[n, n_channels]``."""
+    p = check_site_quant_params(params)
+    n_ch = p["n_channels"]
+    site_off = np.asarray(site_off, np.int64)
+    n = site_off.size - 1
+    site_probs = np.asarray(site_probs, np.dtype(_lib.SITE_PROB_DTYPE))
+    psm_probs = np.asarray(psm_probs, np.dtype(_lib.PSM_PROB_DTYPE))
+    sig = np.asarray(best_sig).astype(np.uint64)
+    group = np.asarray(group).astype(np.int64)
+    ascores = np.ascontiguousarray(ascores, np.float32)
+    values = np.ascontiguousarray(values, np.float64)
+    if values.ndim != 2 or values.shape[1] != n_ch:
+        raise ValueError("peptidoform_quant: values is a float64 matrix with %d columns" % n_ch)
+    n_rec = int(site_off[-1]) if n >= 0 else 0
+    if n < 0 or site_probs.shape != (n_rec,) or psm_probs.shape != (n,) or sig.shape != (n,) or group.shape != (n,) or ascores.ndim != 2 \
+            or ascores.shape[0] != n:
+        raise ValueError("peptidoform_quant: site_off has n_psm + 1 entries, psm_probs, best_sig, group and the rows of ascores one per "
+                         "PSM, site_probs one per residue record")
+    row = np.arange(n, dtype=np.int64) if row is None else np.asarray(row).astype(np.int64)
+    if row.shape != (n,):
+        raise ValueError("peptidoform_quant: row has one entry per PSM")
+    ident = (np.arange(n, dtype=np.int64) + int(psm_base)) if psm_id is None else np.asarray(psm_id).astype(np.int64)
+    in_list, min_prob, k = _pfq_min_prob(site_probs, psm_probs, site_off, sig, group)
+    sig = np.where(in_list, sig, np.uint64(0))
+    max_k = ascores.shape[1]
+    if (k > max_k).any():
+        raise ValueError("peptidoform_quant: PSM %d has more modified residues than ascores has columns" % int(np.flatnonzero(k > max_k)[0]))
+    akey = np.where(np.arange(max_k)[None, :] < k[:, None], _ascore_key(ascores).reshape(n, max_k), 0xFFFFFFFF).min(axis=1, initial=0xFFFFFFFF)
+    akey = np.where(k == 0, int(_ascore_key(np.float32([np.inf]))[0]), akey)
+    psms = np.zeros(n, PEPTIDOFORM_DTYPE)
+    psms["sig_bits"], psms["group"], psms["n_psm"] = sig, np.where(in_list, group, 0).astype(np.uint32), 1
+    with np.errstate(invalid="ignore"):
+        psms["n_confident"] = min_prob >= float(threshold)
+        quantified = in_list & (min_prob >= p["threshold"]) & (row >= 0)
+    psms["best_psm"] = ident.astype(np.uint32)
+    psms["best_min_prob"], psms["best_z"] = min_prob, psm_probs["z"]
+    psms["best_min_ascore"] = np.where(akey >> 31 != 0, akey - 0x80000000, 0xFFFFFFFF - akey).astype(np.uint32).view(np.float32)
+    psms["n_psm"][~in_list] = 0
+    before = None if prev is None else _pfq_pair(prev, "peptidoform_quant")
+    if before is not None and before[2] is not None and before[2].shape[1] != n_ch:
+        raise ValueError("peptidoform_quant: prev is a table of other channels")
+    records = merge_peptidoforms(psms, None if before is None else before[0])
+    if cap is not None:
+        records = records[:int(cap)]
+    outside = quantified & (row >= values.shape[0])
+    if outside.any():
+        first = int(np.flatnonzero(outside)[0])
+        raise ValueError("peptidoform_quant: PSM %d names row %d of %d" % (first, int(row[first]), values.shape[0]))
+    head, cell = empty_site_quant(records.size, n_ch)
+    place = _pfq_place(records)
+    who = np.flatnonzero(quantified)
+    at = np.array([place.get((int(psms["group"][i]), int(sig[i])), -1) for i in who], np.int64)
+    who, at = who[at >= 0], at[at >= 0]
+    v = values[row[who]].reshape(who.size, n_ch)
+    usable = (v == v) & (v > 0.0)
+    complete = usable.all(axis=1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = v * 2.0 ** p["scale_log2"]
+    saturated = usable & (t >= 281474976710656.0)
+    q = np.where(usable & ~saturated, t, 0.0).astype(np.uint64)
+    q[saturated] = np.uint64(1 << 48)
+    summed = usable & complete[:, None] if p["complete_only"] else usable
+    np.add.at(head["n_records"], at, 1)
+    np.add.at(head["n_complete"], at[complete], 1)
+    hit = np.nonzero(summed)
+    np.add.at(cell["sum"], (at[hit[0]], hit[1]), q[hit])
+    np.add.at(cell["n"], (at[hit[0]], hit[1]), 1)
+    hit = np.nonzero(summed & saturated)
+    np.add.at(cell["n_saturated"], (at[hit[0]], hit[1]), 1)
+    if before is not None:
+        _pfq_add_rows(place, head, cell, before)
+    return records, head, cell
+
+
+def merge_peptidoform_quant(*pairs, cap=None):
+    """The merge of peptidoform quantification pairs ``(list, head, cell)`` over the same channels: the keys' union through
+    ``merge_peptidoforms``, the rows of equal keys added field by field (counts and sums wrap as on the device); records with
+    ``n_psm == 0`` are skipped and their rows with them; a pair whose head and cell are None has an all-zero table.  The host
+    form of ``PyAscore.peptidoform_quant_reduce`` / ``pya_peptidoform_quant_reduce``, with the same bytes."""
+    if not pairs:
+        raise ValueError("merge_peptidoform_quant: no pair")
+    parts = [_pfq_pair(t, "merge_peptidoform_quant") for t in pairs]
+    widths = {c.shape[1] for _, _, c in parts if c is not None}
+    if len(widths) != 1:
+        raise ValueError("merge_peptidoform_quant: the tables have different channel counts, or no pair has a table")
+    records = merge_peptidoforms(np.concatenate([r for r, _, _ in parts]))
+    if cap is not None:
+        records = records[:int(cap)]
+    head, cell = empty_site_quant(records.size, widths.pop())
+    place = _pfq_place(records)
+    for part in parts:
+        _pfq_add_rows(place, head, cell, part)
+    return records, head, cell
