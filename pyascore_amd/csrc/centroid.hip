@@ -74,10 +74,7 @@ __global__ __launch_bounds__(64 * DEISO_WAVES) void pya_centroid_mark_kernel(con
         }
         if (lane == 0) {
             new_off[s] = (int64_t)kept;
-            if (bad || clipped) {
-                atomicAdd(&over[0], 1u);
-                atomicMax(&over[1], 0xffffffffu - (uint32_t)s);
-            }
+            if (bad || clipped) report_over(over, (uint32_t)s);
         }
     }
 }

@@ -127,10 +127,7 @@ __global__ __launch_bounds__(64 * DEISO_WAVES) void pya_dechg_mark_kernel(const 
         if (lane == 0) {
             new_off[s] = (int64_t)kept;
             n_moved[s] = n_mv;
-            if (bad || clipped) {
-                atomicAdd(&over[0], 1u);
-                atomicMax(&over[1], 0xffffffffu - (uint32_t)s);
-            }
+            if (bad || clipped) report_over(over, (uint32_t)s);
         }
     }
 }

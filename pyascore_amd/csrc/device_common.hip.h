@@ -210,6 +210,31 @@ DEV uint32_t xcd_slot(uint32_t b, uint32_t n) {
 #endif
 }
 
+/* The two report words of a stage that writes nothing of an item outside the caller's room: over[0] counts such items,
+ * over[1] keeps the smallest id among them as 0xffffffff - id (a max, so that the words' zero state means "none").  The host
+ * clears the words before the launch.  Whether a kernel reports at all (a NULL pointer, a template flag, one lane of a
+ * wavefront) is the caller's to test. */
+DEV void report_over(uint32_t *over, uint32_t id) {
+    atomicAdd(&over[0], 1u);
+    atomicMax(&over[1], 0xffffffffu - id);
+}
+
+/* The PSM of residue record `rec` of the site stage's offsets site_off[n_psm + 1] (rollup.hip, site_quant.hip): the first i
+ * with site_off[i + 1] > rec, by a binary search (17 steps for 100 000 PSMs, all in L2), and r, the record's place among the
+ * PSM's modifiable residues.  False when the record has nothing to give: psm_probs (pya_psm_prob as 4 x uint32: kind is the
+ * low byte of word 3) does not say PYA_SITE_SCORED. */
+DEV bool record_psm(const int64_t *site_off, uint32_t n_psm, const uint32_t *psm_probs, uint64_t rec, uint32_t &psm, uint64_t &r) {
+    uint32_t lo = 0, hi = n_psm - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((uint64_t)site_off[mid + 1] <= rec) lo = mid + 1; else hi = mid;
+    }
+    psm = lo;
+    r = rec - (uint64_t)site_off[lo];
+    if (r > 63u) return false;                               /* (offsets that are not the plan's) */
+    return (psm_probs[(size_t)lo * 4 + 3] & 0xffu) == 1u /* PYA_SITE_SCORED */;
+}
+
 /* LDS traffic of one wave is in order, but the compiler must not move LDS accesses across the
  * points where lanes exchange data through LDS.  The fences name the LDS address space only: a
  * fence over all address spaces makes the compiler drain the vector-memory counter as well

@@ -449,7 +449,7 @@ static int pform_collect(pya_handle *h, pya_plan *p, uint64_t lo) {
     if (h->pform_n_host[1])
         return h->fail(PYA_ERR_STATE, (int64_t)lo, "peptidoforms: %u PSMs from %llu have a best_sig that does not fit their residue records",
                        h->pform_n_host[1], (unsigned long long)lo);
-    return h->pfq_active ? pfq_report(p, lo) : PYA_OK;
+    return h->pfq_active ? over_report(p, OVER_PFQ, lo) : PYA_OK;
 }
 
 /* ... and the end of the call: the list comes to the host */
@@ -869,10 +869,10 @@ static int score_batch_chunked(pya_handle *h, const pya_batch *b, const SpecShar
         std::memcpy(out->alt_mask + lo * mk, sg + (p->o_alt - o), n * mk * sizeof(uint64_t));
         if (nq) named_deliver(h, nq, lo, lo + n, n_q);
         /* (a slot outside the table: the report of this chunk's roll-up, whose kernels the event above waited for) */
-        if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_report(p, lo))) return finish(rc);
+        if ((flags & PYA_FLAG_ROLLUP) && (rc = over_report(p, OVER_ROLLUP, lo))) return finish(rc);
         if ((flags & PYA_FLAG_PEPTIDOFORMS) && (rc = pform_collect(h, p, lo))) return finish(rc);
-        if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = mzp_report(p, lo))) return finish(rc);
-        if ((flags & PYA_FLAG_QUANT) && (rc = quant_report(p, lo))) return finish(rc);
+        if ((flags & PYA_FLAG_MZ_PROFILE) && (rc = over_report(p, OVER_MZP, lo))) return finish(rc);
+        if ((flags & PYA_FLAG_QUANT) && (rc = over_report(p, OVER_QUANT, lo))) return finish(rc);
         cur = std::move(next);
     }
     if ((flags & PYA_FLAG_ROLLUP) && (rc = rollup_end(h, loan))) return finish(rc);
@@ -1173,13 +1173,13 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if (flags & PYA_FLAG_ROLLUP) {
         if ((rc = rollup_behind_run(h, p, &d_out, loan, flags, 0, nullptr))) return rc;
         HIPCHK(h, hipStreamSynchronize(nullptr));
-        if ((rc = rollup_report(p, 0))) return rc;
+        if ((rc = over_report(p, OVER_ROLLUP, 0))) return rc;
         if ((rc = rollup_end(h, loan))) return rc;
     }
     if (flags & PYA_FLAG_QUANT) {
         if ((rc = quant_behind_run(h, p, &d_out, quant_loan, loan, 0, nullptr))) return rc;
         HIPCHK(h, hipStreamSynchronize(nullptr));
-        if ((rc = quant_report(p, 0))) return rc;
+        if ((rc = over_report(p, OVER_QUANT, 0))) return rc;
         if ((rc = quant_end(h, quant_loan, loan))) return rc;
     }
     if (flags & PYA_FLAG_PEPTIDOFORMS) {
@@ -1191,7 +1191,7 @@ static int score_batch_impl(pya_handle *h, const pya_batch *b, const SpecShare *
     if (flags & PYA_FLAG_MZ_PROFILE) {
         if ((rc = mzp_behind_run(h, p, &d_out, mzp_loan, nullptr))) return rc;
         HIPCHK(h, hipStreamSynchronize(nullptr));
-        if ((rc = mzp_report(p, 0))) return rc;
+        if ((rc = over_report(p, OVER_MZP, 0))) return rc;
         if ((rc = mzp_end(h, mzp_loan))) return rc;
     }
     if (flags & PYA_FLAG_COVERAGE) {

@@ -559,6 +559,46 @@ struct pya_handle {
         if (e_ != hipSuccess) return (h)->hip_fail(e_, #call); \
     } while (0)
 
+/* The out-of-range report of a stage behind a run (device_common.hip.h: report_over): the two device words -- how many items
+ * the last call wrote nothing of, and 0xffffffff - the smallest id among them --, the event behind that call's kernels, and
+ * whether the last run has been asked at all.  Every call of the stage reports into the same two words, so a later call, on
+ * whatever stream, waits for the earlier call's kernels before it clears them: the words are those of the LAST call. */
+struct OverReport {
+    DevBuf<uint32_t> d_over;
+    hipEvent_t ev = nullptr;
+    bool asked = false;
+    ~OverReport() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    /* before the stage's launches on `st` */
+    int begin(pya_handle *h, hipStream_t st) {
+        if (!d_over.p) HIPCHK(h, d_over.alloc(2));
+        if (!ev) HIPCHK(h, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        if (asked) HIPCHK(h, hipStreamWaitEvent(st, ev, 0));
+        HIPCHK(h, hipMemsetAsync(d_over.p, 0, 2 * sizeof(uint32_t), st));
+        return PYA_OK;
+    }
+    /* ... and behind them */
+    int end(pya_handle *h, hipStream_t st) {
+        HIPCHK(h, hipEventRecord(ev, st));
+        asked = true;
+        return PYA_OK;
+    }
+    /* waits for the last call's kernels; *count == 0: nothing was outside, or nothing was asked */
+    int read(pya_handle *h, uint32_t *count, uint32_t *first_id) {
+        uint32_t over[2] = {0u, 0u};
+        if (asked) {
+            HIPCHK(h, hipEventSynchronize(ev));
+            HIPCHK(h, hipMemcpy(over, d_over.p, sizeof(over), hipMemcpyDeviceToHost));
+        }
+        *count = over[0];
+        *first_id = 0xffffffffu - over[1];
+        return PYA_OK;
+    }
+};
+/* the stages of a plan that keep one (pya_plan::over), in the order pya_plan_check reports them */
+enum { OVER_NAMED, OVER_ROLLUP, OVER_MZP, OVER_QUANT, OVER_PFQ, OVER_COUNT };
+
 struct Bucket {
     std::vector<uint32_t> ids;          /* every PSM of the bucket (score_signatures launch), plain ones first */
     std::vector<uint32_t> general_ids;  /* filled while scanning; appended to ids afterwards */
@@ -823,12 +863,13 @@ struct pya_plan {
     hipEvent_t ev_ions = nullptr;
     uint32_t ions_max_k = 0;
     int ions_state = 0;
-    /* pya_plan_named: the report of the last call (PSMs whose query range is not inside the output: count, 0xffffffff -
-     * the smallest), the event pya_plan_check waits for, whether the last run has been asked; a pya_score_batch_named plan's
-     * slice of the queries (host offsets rebased to the chunk: they outlive the asynchronous upload) and its records */
-    DevBuf<uint32_t> d_named_over;
-    hipEvent_t ev_named = nullptr;
-    bool named_asked = false;
+    /* the out-of-range reports of the last calls behind this run: PSMs whose query range is not inside the output
+     * (pya_plan_named), records whose slot is at or above n_slots (pya_plan_rollup), PSMs whose run slot is (pya_plan_mz_profile),
+     * records whose slot or row is outside the call's table or matrix (pya_plan_site_quant), PSMs whose row is at or above
+     * n_rows (pya_plan_peptidoform_quant) */
+    OverReport over[OVER_COUNT];
+    /* a pya_score_batch_named plan's slice of the queries (host offsets rebased to the chunk: they outlive the asynchronous
+     * upload) and its records */
     std::vector<int64_t> named_q_off;
     DevBuf<int64_t> d_named_q_off;
     DevBuf<uint64_t> d_named_q_bits;
@@ -854,35 +895,18 @@ struct pya_plan {
     DevBuf<pya_site_prob> d_prob_sites;
     DevBuf<pya_psm_prob> d_prob_psms;
     DevBuf<pya_ranked> d_ranked;         /* pya_plan_ranked: the records of a pya_score_batch plan */
-    /* pya_plan_rollup: the report of the last call (records whose slot is at or above n_slots: count, 0xffffffff - the
-     * smallest PSM), the event pya_plan_check waits for, whether the last run has been asked; a pya_score_batch plan's slice
-     * of the caller's slots and ids */
-    DevBuf<uint32_t> d_rollup_over;
-    hipEvent_t ev_rollup = nullptr;
-    bool rollup_asked = false;
+    /* pya_plan_rollup: a pya_score_batch plan's slice of the caller's slots and ids */
     DevBuf<int32_t> d_rollup_slot;
     DevBuf<uint32_t> d_rollup_id;
     /* a pya_score_batch plan's slice of the caller's groups and ids (PYA_FLAG_PEPTIDOFORMS), and its residue records */
     DevBuf<int32_t> d_pform_group;
     DevBuf<uint32_t> d_pform_id;
     uint64_t pform_records = 0;
-    /* pya_plan_mz_profile: the report of the last call (PSMs whose slot is at or above n_slots), as for the roll-up; a
-     * pya_score_batch plan's slice of the caller's run slots */
-    DevBuf<uint32_t> d_mzp_over;
-    hipEvent_t ev_mzp = nullptr;
-    bool mzp_asked = false;
+    /* pya_plan_mz_profile: a pya_score_batch plan's slice of the caller's run slots */
     DevBuf<int32_t> d_mzp_run;
-    /* pya_plan_site_quant: the report of the last call (records whose slot or row is outside the call's table or matrix), as
-     * for the roll-up; a pya_score_batch plan's slice of the caller's rows */
-    DevBuf<uint32_t> d_quant_over;
-    hipEvent_t ev_quant = nullptr;
-    bool quant_asked = false;
+    /* pya_plan_site_quant: a pya_score_batch plan's slice of the caller's rows */
     DevBuf<int32_t> d_quant_row;
-    /* pya_plan_peptidoform_quant: the report of the last call (PSMs whose row is at or above the call's n_rows), as for the
-     * site quantification; a pya_score_batch plan's slice of the caller's rows */
-    DevBuf<uint32_t> d_pfq_over;
-    hipEvent_t ev_pfq = nullptr;
-    bool pfq_asked = false;
+    /* pya_plan_peptidoform_quant: a pya_score_batch plan's slice of the caller's rows */
     DevBuf<int32_t> d_pfq_row;
     /* pya_plan_coverage: the raw peak caps of its two launches (the largest spectrum of a PSM inside the fast limits, of a
      * general PSM; once per plan), the event behind the last call's kernels (a later call, on whatever stream, writes
@@ -905,12 +929,7 @@ struct pya_plan {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (ev_evid) (void)hipEventDestroy(ev_evid);
         if (ev_ions) (void)hipEventDestroy(ev_ions);
-        if (ev_named) (void)hipEventDestroy(ev_named);
         if (ev_sites) (void)hipEventDestroy(ev_sites);
-        if (ev_rollup) (void)hipEventDestroy(ev_rollup);
-        if (ev_mzp) (void)hipEventDestroy(ev_mzp);
-        if (ev_quant) (void)hipEventDestroy(ev_quant);
-        if (ev_pfq) (void)hipEventDestroy(ev_pfq);
         if (ev_cov) (void)hipEventDestroy(ev_cov);
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
@@ -1019,7 +1038,9 @@ struct SpecShare {
 int check_spec_of(pya_handle *h, uint64_t n_psm, const uint32_t *spec_of, uint64_t n_spectra);
 int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const IoReq *io, const SpecShare *sh, pya_plan **out);
 int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid = false);
-int rollup_report(pya_plan *p, uint64_t psm_lo);
+/* host_run.cpp: what the last call of stage `which` (OVER_*) behind this run wrote nothing of, as that stage's PYA_ERR_LIMIT;
+ * psm_lo: what the plan's first PSM is called in the message, a chunk's place in its batch */
+int over_report(pya_plan *p, int which, uint64_t psm_lo);
 /* host_peptidoforms.cpp: everything the peptidoform calls refuse, before anything is launched (*run: there are entries), and
  * the stage on `st` behind it: d_n zeroed, then the launches of csrc/peptidoforms.hip */
 int pform_check(pya_handle *h, const char *who, uint64_t n_first, const void *d_second, uint64_t n_second, const void *d_work, uint64_t work_bytes,
@@ -1028,17 +1049,12 @@ int pform_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const vo
               double threshold, const uint32_t *d_psm_id, uint32_t psm_base, const uint64_t *best_sig, const float *ascores, uint32_t max_k,
               const void *d_src0, uint64_t n0, const void *d_src1, uint64_t n1, void *d_work, void *d_out, uint64_t cap, uint32_t *d_n, bool run,
               hipStream_t st);
-/* host_mz_profile.cpp: everything the mass-error profile calls refuse, before anything is launched; host_run.cpp: the
- * report of a plan's last pya_plan_mz_profile (psm_lo as for rollup_report) */
+/* host_mz_profile.cpp: everything the mass-error profile calls refuse, before anything is launched */
 int mzp_check(pya_handle *h, const char *who, uint64_t n_slots, const pya_mz_profile_params *prm);
-int mzp_report(pya_plan *p, uint64_t psm_lo);
-/* host_site_quant.cpp: everything the site quantification calls refuse, before anything is launched; host_run.cpp: the report
- * of a plan's last pya_plan_site_quant (psm_lo as for rollup_report) */
+/* host_site_quant.cpp: everything the site quantification calls refuse, before anything is launched */
 int quant_check(pya_handle *h, const char *who, uint64_t n_slots, uint64_t n_rows, const pya_site_quant_params *prm);
-int quant_report(pya_plan *p, uint64_t psm_lo);
 /* host_pform_quant.cpp: what the peptidoform quantification calls refuse beyond pform_check and quant_check (the tables of
- * the call and of the earlier lists), and the stage on `st`: the list by pform_run, then csrc/pform_quant.hip behind it;
- * host_run.cpp: the report of a plan's last pya_plan_peptidoform_quant (psm_lo as for rollup_report) */
+ * the call and of the earlier lists), and the stage on `st`: the list by pform_run, then csrc/pform_quant.hip behind it */
 int pfq_check(pya_handle *h, const char *who, const void *d_head0, const void *d_cell0, const void *d_head1, const void *d_cell1,
               const void *d_head, const void *d_cell, uint64_t cap);
 int pfq_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const void *d_site_probs, const void *d_psm_probs, const int32_t *d_group,
@@ -1046,7 +1062,6 @@ int pfq_run(pya_handle *h, const int64_t *d_site_off, uint64_t n_psm, const void
             const void *d_src0, const void *d_head0, const void *d_cell0, uint64_t n0, const void *d_src1, const void *d_head1, const void *d_cell1,
             uint64_t n1, const double *d_values, uint64_t n_rows, const int32_t *d_row, uint32_t row_base, const pya_site_quant_params *prm,
             void *d_work, void *d_out, void *d_head, void *d_cell, uint64_t cap, uint32_t *d_n, uint32_t *d_over, bool run, hipStream_t st);
-int pfq_report(pya_plan *p, uint64_t psm_lo);
 /* host_coverage.cpp: PYA_FLAG_COVERAGE of the batch calls -- the handle's pinned block for the records of a batch of n PSMs
  * (zeroed: a PSM no plan reaches has a PYA_COV_NONE record), and the stage behind a plan's kernels on `st` with its records
  * on their way into the block at PSM `lo` (asynchronous: whoever waits for the chunk's results waits for them too) */

@@ -336,11 +336,7 @@ int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_strea
     p->last_stream = st;
     p->ran = true;
     p->ions_state = 0;                       /* (counts, offsets and the overflow report belonged to the run before) */
-    p->named_asked = false;
-    p->rollup_asked = false;
-    p->mzp_asked = false;
-    p->quant_asked = false;
-    p->pfq_asked = false;
+    for (OverReport &o : p->over) o.asked = false;
     p->dev = d;
     return rc;
 }
@@ -417,57 +413,25 @@ int check_status(pya_handle *h, const int32_t *st, uint64_t n, bool skip_invalid
     return PYA_OK;
 }
 
-/* the last pya_plan_rollup of this run: records whose slot is not inside the table of the call (psm_lo: what the plan's
- * first PSM is called in the message, a chunk's place in its batch) */
-int rollup_report(pya_plan *p, uint64_t psm_lo) {
-    pya_handle *h = p->h;
-    if (!p->rollup_asked) return PYA_OK;
-    uint32_t over[2] = {0u, 0u};
-    HIPCHK(h, hipEventSynchronize(p->ev_rollup));
-    HIPCHK(h, hipMemcpy(over, p->d_rollup_over.p, sizeof(over), hipMemcpyDeviceToHost));
-    if (!over[0]) return PYA_OK;
-    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
-    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_rollup: %u residue records (PSM %llu the first) name a slot at or above the "
-                   "n_slots of the call; nothing of them was written", over[0], (unsigned long long)first);
-}
-
-/* ... and the last pya_plan_mz_profile of this run: PSMs whose slot is not inside the table of the call */
-int mzp_report(pya_plan *p, uint64_t psm_lo) {
-    pya_handle *h = p->h;
-    if (!p->mzp_asked) return PYA_OK;
-    uint32_t over[2] = {0u, 0u};
-    HIPCHK(h, hipEventSynchronize(p->ev_mzp));
-    HIPCHK(h, hipMemcpy(over, p->d_mzp_over.p, sizeof(over), hipMemcpyDeviceToHost));
-    if (!over[0]) return PYA_OK;
-    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
-    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_mz_profile: %u PSMs (PSM %llu the first) name a run slot at or above the n_slots of "
-                   "the call; nothing of them was written", over[0], (unsigned long long)first);
-}
-
-/* ... and the last pya_plan_site_quant of this run: records whose slot or row is not inside the table or the matrix of the call */
-int quant_report(pya_plan *p, uint64_t psm_lo) {
-    pya_handle *h = p->h;
-    if (!p->quant_asked) return PYA_OK;
-    uint32_t over[2] = {0u, 0u};
-    HIPCHK(h, hipEventSynchronize(p->ev_quant));
-    HIPCHK(h, hipMemcpy(over, p->d_quant_over.p, sizeof(over), hipMemcpyDeviceToHost));
-    if (!over[0]) return PYA_OK;
-    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
-    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_site_quant: %u residue records (PSM %llu the first) name a slot at or above the "
-                   "n_slots or a row at or above the n_rows of the call; nothing of them was written", over[0], (unsigned long long)first);
-}
-
-/* ... and the last pya_plan_peptidoform_quant of this run: PSMs whose row is not inside the matrix of the call */
-int pfq_report(pya_plan *p, uint64_t psm_lo) {
-    pya_handle *h = p->h;
-    if (!p->pfq_asked) return PYA_OK;
-    uint32_t over[2] = {0u, 0u};
-    HIPCHK(h, hipEventSynchronize(p->ev_pfq));
-    HIPCHK(h, hipMemcpy(over, p->d_pfq_over.p, sizeof(over), hipMemcpyDeviceToHost));
-    if (!over[0]) return PYA_OK;
-    const uint64_t first = psm_lo + (0xffffffffu - over[1]);
-    return h->fail(PYA_ERR_LIMIT, (int64_t)first, "pya_plan_peptidoform_quant: %u PSMs (PSM %llu the first) name a row at or above the n_rows of "
-                   "the call; nothing of them was written to the table", over[0], (unsigned long long)first);
+/* The last call of stage `which` behind this run: what it wrote nothing of, because it was not inside the room of the call
+ * (the query range of a PSM; the slot of a record, of a PSM's run; the slot or the row of a record; the row of a PSM). */
+int over_report(pya_plan *p, int which, uint64_t psm_lo) {
+    static const char *const kText[OVER_COUNT] = {
+        "pya_plan_named: the query ranges of %u PSMs (PSM %llu the first) are not inside the n_q records of the call; nothing of them was "
+        "written",
+        "pya_plan_rollup: %u residue records (PSM %llu the first) name a slot at or above the n_slots of the call; nothing of them was "
+        "written",
+        "pya_plan_mz_profile: %u PSMs (PSM %llu the first) name a run slot at or above the n_slots of the call; nothing of them was written",
+        "pya_plan_site_quant: %u residue records (PSM %llu the first) name a slot at or above the n_slots or a row at or above the n_rows "
+        "of the call; nothing of them was written",
+        "pya_plan_peptidoform_quant: %u PSMs (PSM %llu the first) name a row at or above the n_rows of the call; nothing of them was "
+        "written to the table",
+    };
+    uint32_t count = 0u, id = 0u;
+    const int rc = p->over[which].read(p->h, &count, &id);
+    if (rc || !count) return rc;
+    const uint64_t first = psm_lo + id;
+    return p->h->fail(PYA_ERR_LIMIT, (int64_t)first, kText[which], count, (unsigned long long)first);
 }
 
 int pya_plan_check(pya_plan *p) {
@@ -489,25 +453,11 @@ int pya_plan_check(pya_plan *p) {
     if (skip) h->last_status = st;
     const int rc = check_status(h, st.data(), p->n_psm, skip);
     if (rc) return rc;
-    uint32_t over[2] = {0u, 0u};
-    if (p->named_asked) {
-        /* the last pya_plan_named of this run: PSMs whose query range is not inside the output of the call */
-        HIPCHK(h, hipEventSynchronize(p->ev_named));
-        HIPCHK(h, hipMemcpy(over, p->d_named_over.p, sizeof(over), hipMemcpyDeviceToHost));
-        if (over[0])
-            return h->fail(PYA_ERR_LIMIT, (int64_t)(0xffffffffu - over[1]), "pya_plan_named: the query ranges of %u PSMs (PSM %u the first) "
-                           "are not inside the n_q records of the call; nothing of them was written", over[0], 0xffffffffu - over[1]);
-    }
-    const int rc_ru = rollup_report(p, 0);
-    if (rc_ru) return rc_ru;
-    const int rc_mzp = mzp_report(p, 0);
-    if (rc_mzp) return rc_mzp;
-    const int rc_qu = quant_report(p, 0);
-    if (rc_qu) return rc_qu;
-    const int rc_pfq = pfq_report(p, 0);
-    if (rc_pfq) return rc_pfq;
+    for (int which = 0; which < OVER_COUNT; which++)     /* (named, rollup, mzp, quant, pfq: the order of the enum) */
+        if (const int rc_over = over_report(p, which, 0)) return rc_over;
     if (p->ions_state != 2) return PYA_OK;
     /* the last pya_plan_ions of this run: PSMs whose records would have passed the caller's cap */
+    uint32_t over[2] = {0u, 0u};
     HIPCHK(h, hipEventSynchronize(p->ev_ions));
     HIPCHK(h, hipMemcpy(over, p->d_ions_over.p, sizeof(over), hipMemcpyDeviceToHost));
     if (over[0])
@@ -517,6 +467,17 @@ int pya_plan_check(pya_plan *p) {
 }
 
 namespace {
+/* Makes `st` wait for the last run.  The run's own stream has joined the side stream already (pya_plan_run_typed); another
+ * stream waits for an event recorded behind it. */
+int wait_for_run(pya_plan *p, hipStream_t st) {
+    pya_handle *h = p->h;
+    if (st == p->last_stream) return PYA_OK;
+    if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
+    HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
+    HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
+    return PYA_OK;
+}
+
 /* What a stage behind a run does before it launches.  Two launches: one for the PSMs inside the fast limits, sized by THEIR
  * longest peptide and fragment list, one for the plan's general PSMs with the general kernel's caps (a single 400-residue
  * peptide must not set the LDS, hence the occupancy, of a batch of 20-mers).  This sets the caps of the first (once per plan
@@ -551,13 +512,7 @@ int stage_behind_run(pya_plan *p, hipStream_t st, const char *who, const char *k
     if (lds_bytes(p->evid_l_cap, p->evid_list_cap) > kMaxLds || (!p->gen_ids.empty() && lds_bytes(p->gen_l_cap, p->gen_list_cap) > kMaxLds))
         return h->fail(PYA_ERR_LIMIT, -1, "%s: %u fragments per ion type exceed the %s kernel's room", who,
                        std::max(p->evid_list_cap, p->gen_ids.empty() ? 0u : p->gen_list_cap), kernel);
-    /* behind the run: its stream has joined the side stream already (pya_plan_run_typed); another stream waits for it */
-    if (st != p->last_stream) {
-        if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
-        HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
-        HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
-    }
-    return PYA_OK;
+    return wait_for_run(p, st);
 }
 }  // namespace
 
@@ -603,27 +558,21 @@ int pya_plan_named(pya_plan *p, const pya_results *r, void *hip_stream, const in
         return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_named");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!p->d_named_over.p) HIPCHK(h, p->d_named_over.alloc(2));
-    if (!p->ev_named) HIPCHK(h, hipEventCreateWithFlags(&p->ev_named, hipEventDisableTiming));
-    const int rc = stage_behind_run(p, st, "pya_plan_named", "named", pya_named_lds_bytes);
-    if (rc) return rc;
-    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
-    if (p->named_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_named, 0));
-    HIPCHK(h, hipMemsetAsync(p->d_named_over.p, 0, 2 * sizeof(uint32_t), st));
+    OverReport &over = p->over[OVER_NAMED];
+    int rc = stage_behind_run(p, st, "pya_plan_named", "named", pya_named_lds_bytes);
+    if (rc || (rc = over.begin(h, st))) return rc;
     shared_tables(h, p->dev);
     BatchDev d = p->dev;
     d.best_score = r->best_score;
     d.best_sig = r->best_sig;
     d.n_sig_out = r->n_sig;
     int e = pya_launch_named(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, d_q_off, d_q_bits, n_q, d_out, d_counts,
-                             d_scores, p->d_named_over.p, p->evid_l_cap, p->evid_list_cap, st);
+                             d_scores, over.d_over.p, p->evid_l_cap, p->evid_list_cap, st);
     if (!e && !p->gen_ids.empty())
         e = pya_launch_named(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_q_off, d_q_bits, n_q, d_out, d_counts, d_scores,
-                             p->d_named_over.p, p->gen_l_cap, p->gen_list_cap, st);
+                             over.d_over.p, p->gen_l_cap, p->gen_list_cap, st);
     if (e) return h->hip_fail((hipError_t)e, "named launch");
-    HIPCHK(h, hipEventRecord(p->ev_named, st));
-    p->named_asked = true;
-    return PYA_OK;
+    return over.end(h, st);
 }
 
 /* The site stage (csrc/sites.hip).  The offsets are the pre-pass's: a PSM has as many records as modifiable residues, a PSM
@@ -872,25 +821,14 @@ int pya_plan_rollup(pya_plan *p, const pya_results *r, void *hip_stream, const p
         return h->fail(PYA_ERR_ARG, -1, "results.max_k (%u) is smaller than the largest n_of_mod (%u)", r->max_k, p->max_k);
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!p->d_rollup_over.p) HIPCHK(h, p->d_rollup_over.alloc(2));
-    if (!p->ev_rollup) HIPCHK(h, hipEventCreateWithFlags(&p->ev_rollup, hipEventDisableTiming));
-    if (st != p->last_stream) {                                 /* (behind the run, as stage_behind_run waits for it) */
-        if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
-        HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
-        HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
-    }
-    const int rc_off = site_offsets_on_device(p, st);
-    if (rc_off) return rc_off;
-    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
-    if (p->rollup_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_rollup, 0));
-    HIPCHK(h, hipMemsetAsync(p->d_rollup_over.p, 0, 2 * sizeof(uint32_t), st));
+    OverReport &over = p->over[OVER_ROLLUP];
+    int rc;
+    if ((rc = wait_for_run(p, st)) || (rc = site_offsets_on_device(p, st)) || (rc = over.begin(h, st))) return rc;
     const int e = pya_launch_rollup(p->d_site_off.p, p->n_psm, n_rec, d_site_probs, d_psm_probs, d_slot, n_slots, threshold, d_psm_id, psm_base,
-                                    r->best_sig, r->ascores, r->max_k, d_table, p->d_rollup_over.p, h->last_rollup_grid, st);
+                                    r->best_sig, r->ascores, r->max_k, d_table, over.d_over.p, h->last_rollup_grid, st);
     if (e) return h->hip_fail((hipError_t)e, "roll-up launch");
     h->last_rollup_records = n_rec;
-    HIPCHK(h, hipEventRecord(p->ev_rollup, st));
-    p->rollup_asked = true;
-    return PYA_OK;
+    return over.end(h, st);
 }
 
 /* The site quantification (csrc/site_quant.hip): the roll-up's wait for the run and its offsets, one launch into the caller's
@@ -910,24 +848,13 @@ int pya_plan_site_quant(pya_plan *p, const pya_results *r, void *hip_stream, con
         return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_site_quant");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!p->d_quant_over.p) HIPCHK(h, p->d_quant_over.alloc(2));
-    if (!p->ev_quant) HIPCHK(h, hipEventCreateWithFlags(&p->ev_quant, hipEventDisableTiming));
-    if (st != p->last_stream) {                                 /* (behind the run, as pya_plan_rollup waits for it) */
-        if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
-        HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
-        HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
-    }
-    const int rc_off = site_offsets_on_device(p, st);
-    if (rc_off) return rc_off;
-    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
-    if (p->quant_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_quant, 0));
-    HIPCHK(h, hipMemsetAsync(p->d_quant_over.p, 0, 2 * sizeof(uint32_t), st));
+    OverReport &over = p->over[OVER_QUANT];
+    int rc;
+    if ((rc = wait_for_run(p, st)) || (rc = site_offsets_on_device(p, st)) || (rc = over.begin(h, st))) return rc;
     const int e = pya_launch_site_quant(p->d_site_off.p, p->n_psm, n_rec, d_site_probs, d_psm_probs, d_slot, n_slots, d_values, n_rows, d_row,
-                                        row_base, prm, std::ldexp(1.0, prm->scale_log2), r->best_sig, d_head, d_cell, p->d_quant_over.p, st);
+                                        row_base, prm, std::ldexp(1.0, prm->scale_log2), r->best_sig, d_head, d_cell, over.d_over.p, st);
     if (e) return h->hip_fail((hipError_t)e, "site quantification launch");
-    HIPCHK(h, hipEventRecord(p->ev_quant, st));
-    p->quant_asked = true;
-    return PYA_OK;
+    return over.end(h, st);
 }
 
 /* The peptidoform stage (csrc/peptidoforms.hip): like the roll-up it takes nothing of stage_behind_run but the wait for the
@@ -953,13 +880,8 @@ int pya_plan_peptidoforms(pya_plan *p, const pya_results *r, void *hip_stream, c
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
     if (p->n_psm) {
-        if (st != p->last_stream) {                             /* (behind the run, as pya_plan_rollup waits for it) */
-            if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
-            HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
-            HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
-        }
-        const int rc_off = site_offsets_on_device(p, st);
-        if (rc_off) return rc_off;
+        int rc_run;
+        if ((rc_run = wait_for_run(p, st)) || (rc_run = site_offsets_on_device(p, st))) return rc_run;
     }
     return pform_run(h, p->n_psm ? p->d_site_off.p : nullptr, p->n_psm, d_site_probs, d_psm_probs, d_group, threshold, d_psm_id, psm_base,
                      r->best_sig, r->ascores, r->max_k, d_prev, n_prev, nullptr, 0, d_work, d_out, cap, d_n, run, st);
@@ -993,29 +915,13 @@ int pya_plan_peptidoform_quant(pya_plan *p, const pya_results *r, void *hip_stre
     }
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (p->n_psm) {
-        if (!p->d_pfq_over.p) HIPCHK(h, p->d_pfq_over.alloc(2));
-        if (!p->ev_pfq) HIPCHK(h, hipEventCreateWithFlags(&p->ev_pfq, hipEventDisableTiming));
-        if (st != p->last_stream) {                             /* (behind the run, as pya_plan_rollup waits for it) */
-            if (!p->ev_evid) HIPCHK(h, hipEventCreateWithFlags(&p->ev_evid, hipEventDisableTiming));
-            HIPCHK(h, hipEventRecord(p->ev_evid, p->last_stream));
-            HIPCHK(h, hipStreamWaitEvent(st, p->ev_evid, 0));
-        }
-        const int rc_off = site_offsets_on_device(p, st);
-        if (rc_off) return rc_off;
-        /* (behind an earlier call's kernel, on whatever stream it was: it reports into the same two words) */
-        if (p->pfq_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_pfq, 0));
-        HIPCHK(h, hipMemsetAsync(p->d_pfq_over.p, 0, 2 * sizeof(uint32_t), st));
-    }
+    OverReport &over = p->over[OVER_PFQ];                       /* (of the PSMs: a call without them reports nothing) */
+    if (p->n_psm && ((rc = wait_for_run(p, st)) || (rc = site_offsets_on_device(p, st)) || (rc = over.begin(h, st)))) return rc;
     rc = pfq_run(h, p->n_psm ? p->d_site_off.p : nullptr, p->n_psm, d_site_probs, d_psm_probs, d_group, threshold, d_psm_id, psm_base, r->best_sig,
                  r->ascores, r->max_k, d_prev, d_prev_head, d_prev_cell, n_prev, nullptr, nullptr, nullptr, 0, d_values, n_rows, d_row, row_base, prm,
-                 d_work, d_out, d_head, d_cell, cap, d_n, p->n_psm ? p->d_pfq_over.p : nullptr, run, st);
-    if (rc) return rc;
-    if (p->n_psm) {
-        HIPCHK(h, hipEventRecord(p->ev_pfq, st));
-        p->pfq_asked = true;
-    }
-    return PYA_OK;
+                 d_work, d_out, d_head, d_cell, cap, d_n, p->n_psm ? over.d_over.p : nullptr, run, st);
+    if (rc || !p->n_psm) return rc;
+    return over.end(h, st);
 }
 
 /* The mass-error profile (csrc/mz_profile.hip): the wait and the two lists of the evidence stage, with the longest peptide of
@@ -1032,31 +938,25 @@ int pya_plan_mz_profile(pya_plan *p, const pya_results *r, void *hip_stream, con
     if ((n_slots && !d_table) || !r->best_sig || !r->n_sig) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_mz_profile");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
-    if (!p->d_mzp_over.p) HIPCHK(h, p->d_mzp_over.alloc(2));
-    if (!p->ev_mzp) HIPCHK(h, hipEventCreateWithFlags(&p->ev_mzp, hipEventDisableTiming));
+    OverReport &over = p->over[OVER_MZP];
     /* (the LDS condition of pya_plan_evidence, and this kernel's own room, which only a peptide length could exceed) */
     struct Room {
         static size_t both(uint32_t l_cap, uint32_t list_cap) {
             return std::max(pya_evidence_lds_bytes(l_cap, list_cap), pya_mz_profile_lds_bytes(l_cap));
         }
     };
-    const int rc = stage_behind_run(p, st, "pya_plan_mz_profile", "evidence", Room::both);
-    if (rc) return rc;
-    /* (behind an earlier call's kernels, on whatever stream they were: they report into the same two words) */
-    if (p->mzp_asked) HIPCHK(h, hipStreamWaitEvent(st, p->ev_mzp, 0));
-    HIPCHK(h, hipMemsetAsync(p->d_mzp_over.p, 0, 2 * sizeof(uint32_t), st));
+    int rc = stage_behind_run(p, st, "pya_plan_mz_profile", "evidence", Room::both);
+    if (rc || (rc = over.begin(h, st))) return rc;
     shared_tables(h, p->dev);
     BatchDev d = p->dev;
     d.best_sig = r->best_sig;
     d.n_sig_out = r->n_sig;
     int e = pya_launch_mz_profile(&d, p->gen_ids.empty() ? nullptr : p->d_evid_ids.p, p->evid_n_fast, d_run, n_slots, prm, d_table,
-                                  p->d_mzp_over.p, p->evid_l_cap, st);
+                                  over.d_over.p, p->evid_l_cap, st);
     if (!e && !p->gen_ids.empty())
-        e = pya_launch_mz_profile(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_run, n_slots, prm, d_table, p->d_mzp_over.p, p->gen_l_cap, st);
+        e = pya_launch_mz_profile(&d, p->d_gen_ids.p, (uint32_t)p->gen_ids.size(), d_run, n_slots, prm, d_table, over.d_over.p, p->gen_l_cap, st);
     if (e) return h->hip_fail((hipError_t)e, "mass-error profile launch");
-    HIPCHK(h, hipEventRecord(p->ev_mzp, st));
-    p->mzp_asked = true;
-    return PYA_OK;
+    return over.end(h, st);
 }
 
 namespace {

@@ -141,10 +141,7 @@ __global__ __launch_bounds__(64) void pya_ions_kernel(BatchDev b, const uint32_t
         end = (uint64_t)off[psm + 1];
         if (end == base) return;
         if (end > cap || end < base) {                              /* nothing of the PSM is written */
-            if (lane == 0) {
-                atomicAdd(&over[0], 1u);
-                atomicMax(&over[1], 0xffffffffu - psm);
-            }
+            if (lane == 0) report_over(over, psm);
             return;
         }
     }

@@ -156,10 +156,7 @@ __global__ __launch_bounds__(64 * DEISO_WAVES) void pya_markers_kernel(const TM 
                 r.n_active = (uint32_t)__builtin_popcountll(act);
                 spectra[s] = r;
             }
-            if (clipped) {
-                atomicAdd(&over[0], 1u);
-                atomicMax(&over[1], 0xffffffffu - (uint32_t)s);
-            }
+            if (clipped) report_over(over, (uint32_t)s);
         }
     }
 }

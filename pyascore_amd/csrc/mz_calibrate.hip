@@ -160,10 +160,7 @@ __global__ __launch_bounds__(64 * MZC_WAVES) void pya_mz_apply_kernel(const T *m
         }
         if (bad) {
             apply = false;
-            if (lane == 0) {
-                atomicAdd(&over[0], 1u);
-                atomicMax(&over[1], 0xffffffffu - (uint32_t)s);
-            }
+            if (lane == 0) report_over(over, (uint32_t)s);
         }
         if (!apply && out == mz) continue;                             /* in place: the bytes stay */
         for (int64_t i = p0 + lane; i < p1; i += 64) {

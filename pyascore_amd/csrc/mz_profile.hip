@@ -104,10 +104,7 @@ __global__ __launch_bounds__(64) void pya_mz_profile_kernel(BatchDev b, const Mz
         const int32_t slot = a.run ? a.run[psm] : 0;
         if (N <= 0 || slot < 0) continue;
         if ((uint64_t)slot >= a.n_slots) {
-            if (lane == 0) {
-                atomicAdd(&a.over[0], 1u);
-                atomicMax(&a.over[1], 0xffffffffu - psm);
-            }
+            if (lane == 0) report_over(a.over, psm);
             continue;
         }
         if (held >= 0 && held != (int64_t)slot) mzp_flush(hist, a.table, (uint64_t)held);

@@ -48,10 +48,7 @@ __global__ __launch_bounds__(64) void pya_named_kernel(BatchDev b, const uint32_
     if (q1 == q0) return;                                            /* (the common PSM of a sparse query list) */
     const int lane = lane_id();
     if (q0 < 0 || q1 < q0 || (uint64_t)q1 > n_q) {                   /* nothing of the PSM is written */
-        if (lane == 0) {
-            atomicAdd(&over[0], 1u);
-            atomicMax(&over[1], 0xffffffffu - psm);
-        }
+        if (lane == 0) report_over(over, psm);
         return;
     }
     const DevConfig *cfg = b.cfg;

@@ -16,23 +16,20 @@
  *      over two lists is the same code.  The price: a wavefront aggregates only what lies in 64 CONSECUTIVE entries, so the
  *      PSMs of one peptidoform scattered over a batch reach memory as one atomic each instead of one per key; the walk
  *      would merge them first.  The upper search steps hit the same few list records from every lane and stay in cache.
- *   2  the contributing lanes that share a position find each other in a wave-uniform loop: the position of the first lane
- *      still to do by v_readlane, a ballot of equality.
- *   3  lane = channel.  For each group the lanes walk the group's entries, four loads in flight together: a PSM's row is one
- *      coalesced load of values[row * n_channels + lane], quantised here; an earlier record's cell is one 16-byte load,
- *      integers already, added as they are, and its head is added to the group's.
- *   4  one 64-bit atomic add per (group, channel) to sum, one of n | n_saturated << 32 behind it, one of n_records |
- *      n_complete << 32 to the head from lane 0; a part that is zero adds nothing.
- * No write lies outside head[0 .. cap) and cell[0 .. cap * n_channels): a position comes out of the search below
- * min(d_n[0], cap), a channel lane is below n_channels.  values is read at rows below n_rows only, an earlier table at records
- * below its n only.  A PSM that would contribute but whose row is at or above n_rows is counted in over[0] (the smallest such
- * PSM kept in over[1] as 0xffffffff - psm) and nothing of it is written.  The launcher clears the table on the stream first. */
-#include "quant_rule.hip.h"
+ *   2 to 4  quant_wave.hip.h, with the list position as the key.  An entry is a reading or an earlier record's cell and head:
+ *      a PSM's row is one coalesced load of values[row * n_channels + lane], quantised there; an earlier record's cell is one
+ *      16-byte load, integers already, added as they are, and its head is added to the group's.
+ * No write lies outside head[0 .. cap) and cell[0 .. cap * n_channels): a lane is active only with a position that pq_find
+ * returned, and pq_find's own last lines return a position below m = min(d_n[0], cap) or -1 -- so the reduce does not test
+ * the position against m again --; a channel lane is below n_channels.  values is read at rows below n_rows only, an earlier
+ * table at records below its n only.  A PSM that would contribute but whose row is at or above n_rows is counted in over[0]
+ * (the smallest such PSM kept in over[1] as 0xffffffff - psm) and nothing of it is written.  The launcher clears the table on
+ * the stream first. */
+#include "quant_wave.hip.h"
 #include "../../include/pyascore_hip.h"
 
 #define PQ_SCORED 1u                  /* PYA_SITE_SCORED */
 #define PQ_THREADS 256
-#define PQ_UNROLL 4                   /* entries in flight per lane in step 3 */
 
 struct PqArgs {
     const int64_t *site_off;          /* [n_psm + 1] */
@@ -76,10 +73,7 @@ DEV bool pq_psm(const PqArgs &a, uint32_t i, uint32_t &g, uint64_t &sig, uint32_
     const int64_t rw = a.row ? (int64_t)a.row[i] : (int64_t)a.row_base + (int64_t)i;
     if (rw < 0) return false;
     if ((uint64_t)rw >= a.n_rows) {
-        if (a.over) {
-            atomicAdd(&a.over[0], 1u);
-            atomicMax(&a.over[1], 0xffffffffu - i);
-        }
+        if (a.over) report_over(a.over, i);
         return false;
     }
     g = (uint32_t)gi;
@@ -101,9 +95,16 @@ DEV int32_t pq_find(const uint4 *list, uint32_t m, uint32_t g, uint64_t sig) {
     return (q.z == g && ((uint64_t)q.y << 32 | q.x) == sig) ? (int32_t)lo : -1;
 }
 
+/* this lane's part of one entry of a group: a PSM's reading of the lane's channel (kind 0: the double's bits in c.x, c.y), or an
+ * earlier record's cell of that channel and its head (kind 1 / 2); kind is wave-uniform */
+struct PqEntry {
+    uint4 c;
+    unsigned long long hd;
+    uint32_t kind;
+};
+
 __global__ void __launch_bounds__(PQ_THREADS) pya_pform_quant_kernel(const PqArgs a) {
     const uint64_t e = (uint64_t)blockIdx.x * PQ_THREADS + threadIdx.x;
-    const int lane = lane_id();
     const uint64_t len = a.d_n[0];
     const uint32_t m = (uint32_t)(len < a.cap ? len : a.cap);
     int32_t pos = -1;
@@ -127,74 +128,39 @@ __global__ void __launch_bounds__(PQ_THREADS) pya_pform_quant_kernel(const PqArg
         }
         if (have && m) pos = pq_find(a.list, m, g, sig);
     }
-    const bool active = pos >= 0;
     /* (from here on the control flow is wave-uniform: no lane has left) */
-    const bool mine = (uint32_t)lane < a.n_ch;               /* this lane is a channel */
-    uint64_t todo = __ballot(active);
-    while (todo) {
-        const int lead = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
-        const int32_t gp = __builtin_amdgcn_readlane(pos, lead);
-        uint64_t grp = __ballot(active && pos == gp);
-        todo &= ~grp;
-        uint64_t sum = 0;
-        uint32_t n = 0, n_sat = 0, n_records = 0, n_complete = 0;
-        while (grp) {
-            uint4 c[PQ_UNROLL];
-            unsigned long long hd[PQ_UNROLL];
-            uint32_t kd[PQ_UNROLL];
-            bool have[PQ_UNROLL];
-#pragma unroll
-            for (int u = 0; u < PQ_UNROLL; u++) {
-                have[u] = grp != 0ull;
-                const int j = __builtin_amdgcn_readfirstlane(have[u] ? (int)__builtin_ctzll(grp) : 0);
-                grp &= grp - 1ull;                           /* (0 stays 0) */
-                kd[u] = (uint32_t)__builtin_amdgcn_readlane((int)kind, j);
-                const uint32_t rj = (uint32_t)__builtin_amdgcn_readlane((int)ref, j);
-                c[u] = make_uint4(0u, 0u, 0u, 0u);
-                hd[u] = 0ull;
-                if (have[u] && kd[u] == 0u) {
-                    if (mine) {
-                        const uint2 v = a.values[(size_t)rj * a.n_ch + (uint32_t)lane];
-                        c[u].x = v.x;
-                        c[u].y = v.y;
-                    }
-                } else if (have[u]) {
-                    if (mine) c[u] = (kd[u] == 1u ? a.src_cell0 : a.src_cell1)[(size_t)rj * a.n_ch + (uint32_t)lane];
-                    hd[u] = (kd[u] == 1u ? a.src_head0 : a.src_head1)[rj];
+    qw_reduce(
+        pos >= 0, (uint32_t)pos, a.n_ch, a.head, a.cell,
+        [&](int j, bool have) {
+            PqEntry e = {make_uint4(0u, 0u, 0u, 0u), 0ull, (uint32_t)__builtin_amdgcn_readlane((int)kind, j)};
+            const uint32_t rj = (uint32_t)__builtin_amdgcn_readlane((int)ref, j);
+            const bool mine = qw_channel(a.n_ch);
+            const size_t at = (size_t)rj * a.n_ch + (uint32_t)lane_id();
+            if (have && e.kind == 0u) {
+                if (mine) {
+                    const uint2 v = a.values[at];
+                    e.c.x = v.x;
+                    e.c.y = v.y;
                 }
+            } else if (have) {
+                if (mine) e.c = (e.kind == 1u ? a.src_cell0 : a.src_cell1)[at];
+                /* (a uniform address: the compiler takes the head into scalar registers at once, so an earlier record's two
+                 * loads are waited for before the next entry's are issued.  Readings, the common entry, stay in flight together) */
+                e.hd = (e.kind == 1u ? a.src_head0 : a.src_head1)[rj];
             }
-#pragma unroll
-            for (int u = 0; u < PQ_UNROLL; u++) {
-                if (!have[u]) break;
-                if (kd[u] == 0u) {
-                    const double v = __longlong_as_double((long long)((uint64_t)c[u].y << 32 | c[u].x));
-                    const bool usable = mine && qr_usable(v);
-                    const bool complete = (uint32_t)__popcll(__ballot(usable)) == a.n_ch;
-                    n_records++;
-                    n_complete += complete ? 1u : 0u;
-                    if (usable && (complete || !a.complete_only)) {
-                        bool sat;
-                        sum += qr_quantum(v, a.scale, &sat);
-                        n_sat += sat ? 1u : 0u;
-                        n++;
-                    }
-                } else {
-                    sum += (uint64_t)c[u].y << 32 | c[u].x;
-                    n += c[u].z;
-                    n_sat += c[u].w;
-                    n_records += (uint32_t)hd[u];
-                    n_complete += (uint32_t)(hd[u] >> 32);
-                }
+            return e;
+        },
+        [&](QwAcc &c, const PqEntry &e) {
+            if (e.kind == 0u) {
+                qw_add_reading(c, __longlong_as_double((long long)((uint64_t)e.c.y << 32 | e.c.x)), a.n_ch, a.scale, a.complete_only);
+            } else {
+                c.sum += (uint64_t)e.c.y << 32 | e.c.x;
+                c.n += e.c.z;
+                c.n_saturated += e.c.w;
+                c.n_records += (uint32_t)e.hd;
+                c.n_complete += (uint32_t)(e.hd >> 32);
             }
-        }
-        if (mine && (uint32_t)gp < m) {
-            unsigned long long *c = a.cell + ((size_t)(uint32_t)gp * a.n_ch + (uint32_t)lane) * 2;
-            if (sum) atomicAdd(c, (unsigned long long)sum);
-            if (n | n_sat) atomicAdd(c + 1, (unsigned long long)n | (unsigned long long)n_sat << 32);
-        }
-        if (lane == 0 && (uint32_t)gp < m && (n_records | n_complete))
-            atomicAdd(a.head + (uint32_t)gp, (unsigned long long)n_records | (unsigned long long)n_complete << 32);
-    }
+        });
 }
 
 /* Behind pya_launch_pform on `st`: d_list[cap] / d_n as that call leaves them; the entries are the n_psm PSMs of the plan (0:

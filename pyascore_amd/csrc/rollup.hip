@@ -30,12 +30,11 @@
  * do not disturb their neighbours, and the end of kernel 1 writes them back and the start of kernel 2 invalidates the caches
  * before kernel 2's atomics and loads see the word.  So nothing here depends on where a workgroup runs.
  * An Ascore with the bits of RU_NO_ASCORE (a NaN) cannot be told from the seed; it is the minimum of the order anyway.
- * A record finds its PSM by a binary search of the site offsets (17 steps for 100 000 PSMs, all in L2).
+ * A record finds its PSM by a binary search of the site offsets (device_common.hip.h: record_psm).
  * No write lies outside table[0 .. n_slots): a slot at or above n_slots is counted in over[0] (and the smallest such PSM kept
  * in over[1] as 0xffffffff - psm) and nothing of it is written. */
 #include "device_common.hip.h"
 
-#define RU_SCORED 1u                  /* PYA_SITE_SCORED */
 #define RU_NO_PSM 0xffffffffu
 #define RU_NO_ASCORE 0xffffffffu
 #define RU_THREADS 256
@@ -74,21 +73,11 @@ template <bool REPORT>
 DEV bool ru_record(const RuArgs &a, uint64_t rec, RuRec &o) {
     const int32_t s = a.slot[rec];
     if (s < 0) return false;
-    /* the PSM: the first i with site_off[i + 1] > rec */
-    uint32_t lo = 0, hi = a.n_psm - 1u;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((uint64_t)a.site_off[mid + 1] <= rec) lo = mid + 1; else hi = mid;
-    }
-    const uint32_t psm = lo;
-    const uint64_t r = rec - (uint64_t)a.site_off[psm];
-    if (r > 63u) return false;                               /* (offsets that are not the plan's) */
-    if ((a.psm_probs[(size_t)psm * 4 + 3] & 0xffu) != RU_SCORED) return false;
+    uint32_t psm;
+    uint64_t r;
+    if (!record_psm(a.site_off, a.n_psm, a.psm_probs, rec, psm, r)) return false;
     if ((uint64_t)s >= a.n_slots) {
-        if (REPORT) {
-            atomicAdd(&a.over[0], 1u);
-            atomicMax(&a.over[1], 0xffffffffu - psm);
-        }
+        if (REPORT) report_over(a.over, psm);
         return false;
     }
     o.w = a.table + (size_t)s * 4;

@@ -11,31 +11,23 @@
  * wavefront aggregates before it reaches memory:
  *   1  lane = record.  A wavefront takes 64 consecutive residue records.  Each lane finds its PSM by the roll-up's binary search
  *      of the site offsets and decides whether the record contributes, its slot and its row.
- *   2  the contributing lanes that share a slot find each other in a wave-uniform loop: the slot of the first lane still to
- *      do by v_readlane, a ballot of equality.  At most 64 turns, one per distinct slot of the wavefront.
- *   3  lane = channel.  For each group the lanes walk the group's records -- the row of record j by v_readlane, j from the
- *      group's mask, uniform -- with one coalesced load of values[row * n_channels + lane] each, four records' loads in flight
- *      together, and accumulate q, n and n_saturated in registers.  A ballot of "usable" says whether the record is complete.
- *   4  one 64-bit atomic add per (group, channel) to sum, one of n | n_saturated << 32 to the aligned pair behind it (a channel
- *      that summed nothing adds nothing), and one of n_records | n_complete << 32 to the head from lane 0.
+ *   2 to 4  quant_wave.hip.h, with the slot as the key: the lanes of one slot find each other, the lanes as channels walk the
+ *      group's rows -- an entry is a reading, one coalesced load of values[row * n_channels + lane] -- and one atomic per
+ *      (group, channel) and one for the head reach memory.
  * With n_channels below 64 the lanes at and above it idle in step 3: for 3 channels that is most of the wavefront, and the
  * walk is then bound by the latency of a row's load, not by the lanes.  It is kept: step 3 costs a load per contributing record
  * however the lanes are used, and the atomics -- the part that serialises on hot slots -- are already one per (group, channel).
- * No LDS, no workspace.  Everything that reaches memory is a device-scope atomic add of a vector lane (the eight L2s do not
- * matter to it: an atomic is performed at device scope whichever XCD issues it); the table is never LOADED here, so the
- * question rollup.hip's header answers about plain loads beside atomics does not arise.  values, the records and the slots
- * are only read, and nothing of this launch writes them.
+ * The table is never LOADED here, so the question rollup.hip's header answers about plain loads beside atomics does not
+ * arise.  values, the records and the slots are only read, and nothing of this launch writes them.
  * No write lies outside head[0 .. n_slots) and cell[0 .. n_slots * n_channels): a record that would contribute but whose slot
  * is at or above n_slots or whose row is at or above n_rows is counted in over[0] (and the smallest such PSM kept in over[1]
  * as 0xffffffff - psm) and nothing of it is written; a row below n_rows is the only index values is read at.
  *
  * pya_marker_values_kernel, the second kernel: marker records to a channel matrix, one thread per element. */
-#include "quant_rule.hip.h"
+#include "quant_wave.hip.h"
 #include "../../include/pyascore_hip.h"
 
-#define SQ_SCORED 1u                  /* PYA_SITE_SCORED */
 #define SQ_THREADS 256
-#define SQ_UNROLL 4                   /* rows in flight per lane in step 3 */
 
 struct SqArgs {
     const int64_t *site_off;          /* [n_psm + 1] */
@@ -57,24 +49,16 @@ struct SqArgs {
 DEV bool sq_record(const SqArgs &a, uint64_t rec, int32_t &slot, int32_t &row) {
     const int32_t s = a.slot[rec];
     if (s < 0) return false;
-    /* the PSM: the first i with site_off[i + 1] > rec */
-    uint32_t lo = 0, hi = a.n_psm - 1u;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if ((uint64_t)a.site_off[mid + 1] <= rec) lo = mid + 1; else hi = mid;
-    }
-    const uint32_t psm = lo;
-    const uint64_t r = rec - (uint64_t)a.site_off[psm];
-    if (r > 63u) return false;                               /* (offsets that are not the plan's) */
-    if ((a.psm_probs[(size_t)psm * 4 + 3] & 0xffu) != SQ_SCORED) return false;
+    uint32_t psm;
+    uint64_t r;
+    if (!record_psm(a.site_off, a.n_psm, a.psm_probs, rec, psm, r)) return false;
     if (!((a.best_sig[psm] >> r) & 1ull)) return false;
     const uint2 pb = a.site_probs[rec * 2];
     if (!(__longlong_as_double((long long)((uint64_t)pb.y << 32 | pb.x)) >= a.threshold)) return false;
     const int64_t rw = a.row ? (int64_t)a.row[psm] : (int64_t)a.row_base + (int64_t)psm;
     if (rw < 0) return false;
     if ((uint64_t)s >= a.n_slots || (uint64_t)rw >= a.n_rows) {
-        atomicAdd(&a.over[0], 1u);
-        atomicMax(&a.over[1], 0xffffffffu - psm);
+        report_over(a.over, psm);
         return false;
     }
     slot = s;
@@ -84,53 +68,17 @@ DEV bool sq_record(const SqArgs &a, uint64_t rec, int32_t &slot, int32_t &row) {
 
 __global__ void __launch_bounds__(SQ_THREADS) pya_site_quant_kernel(const SqArgs a) {
     const uint64_t rec = (uint64_t)blockIdx.x * SQ_THREADS + threadIdx.x;
-    const int lane = lane_id();
     int32_t slot = -1, row = -1;
     bool active = false;
     if (rec < a.n_rec) active = sq_record(a, rec, slot, row);
     /* (from here on the control flow is wave-uniform: no lane has left) */
-    const bool mine = (uint32_t)lane < a.n_ch;               /* this lane is a channel */
-    uint64_t todo = __ballot(active);
-    while (todo) {
-        const int lead = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(todo));
-        const int32_t gs = __builtin_amdgcn_readlane(slot, lead);
-        uint64_t grp = __ballot(active && slot == gs);
-        todo &= ~grp;
-        const uint32_t n_records = (uint32_t)__popcll(grp);
-        uint64_t sum = 0;
-        uint32_t n = 0, n_sat = 0, n_complete = 0;
-        while (grp) {
-            double v[SQ_UNROLL];
-            bool have[SQ_UNROLL];
-#pragma unroll
-            for (int u = 0; u < SQ_UNROLL; u++) {
-                have[u] = grp != 0ull;
-                const int j = __builtin_amdgcn_readfirstlane(have[u] ? (int)__builtin_ctzll(grp) : 0);
-                grp &= grp - 1ull;                           /* (0 stays 0) */
-                const int32_t rj = __builtin_amdgcn_readlane(row, j);
-                v[u] = have[u] && mine ? a.values[(size_t)(uint32_t)rj * a.n_ch + (uint32_t)lane] : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < SQ_UNROLL; u++) {
-                if (!have[u]) break;
-                const bool usable = mine && qr_usable(v[u]);
-                const bool complete = (uint32_t)__popcll(__ballot(usable)) == a.n_ch;
-                n_complete += complete ? 1u : 0u;
-                if (usable && (complete || !a.complete_only)) {
-                    bool sat;
-                    sum += qr_quantum(v[u], a.scale, &sat);
-                    n_sat += sat ? 1u : 0u;
-                    n++;
-                }
-            }
-        }
-        if (mine && n) {
-            unsigned long long *c = a.cell + ((size_t)(uint32_t)gs * a.n_ch + (uint32_t)lane) * 2;
-            atomicAdd(c, (unsigned long long)sum);
-            atomicAdd(c + 1, (unsigned long long)n | (unsigned long long)n_sat << 32);
-        }
-        if (lane == 0) atomicAdd(a.head + (uint32_t)gs, (unsigned long long)n_records | (unsigned long long)n_complete << 32);
-    }
+    qw_reduce(
+        active, (uint32_t)slot, a.n_ch, a.head, a.cell,
+        [&](int j, bool have) {                              /* the reading of record j's row */
+            const uint32_t rj = (uint32_t)__builtin_amdgcn_readlane(row, j);
+            return have && qw_channel(a.n_ch) ? a.values[(size_t)rj * a.n_ch + (uint32_t)lane_id()] : 0.0;
+        },
+        [&](QwAcc &c, double v) { qw_add_reading(c, v, a.n_ch, a.scale, a.complete_only); });
 }
 
 /* element i of the matrix: spectrum i / n_ch, the (i % n_ch)-th set bit of the mask as its target */

@@ -91,10 +91,7 @@ __global__ __launch_bounds__(64 * DEISO_WAVES) void pya_strip_mark_kernel(const 
                 r.n_windows = (uint32_t)__builtin_popcountll(act);
                 report[s] = r;
             }
-            if (clipped) {
-                atomicAdd(&over[0], 1u);
-                atomicMax(&over[1], 0xffffffffu - (uint32_t)s);
-            }
+            if (clipped) report_over(over, (uint32_t)s);
         }
     }
 }

@@ -175,6 +175,51 @@ def test_all_psms_on_one_peptidoform():
         pc.same(_pair(got), want, "%d PSMs on one peptidoform" % n)
 
 
+def test_psms_and_an_earlier_record_share_one_group():
+    """8 PSMs on one peptidoform (built as above), 3 channels; the plan's call without an earlier pair, then the same call with
+    the first call's pair as prev.  Wavefront 0 of the second launch holds 8 PSM lanes and 1 record lane on one list position:
+    ONE group of 9 that mixes both kinds of entry, walked four at a time with a tail of 1.  The merge of the yardstick: 16
+    records behind the one list record, every sum doubled."""
+    import torch
+    src, settings = synth.make_batch("cfg2", n_psm=24, seed=9830)
+    one, _ = synth.make_batch("cfg2", n_psm=1, seed=9831, n_sites=2, n_mod=2)
+    kw1 = synth.unpack_psm(one, 0)
+    gpu = _gpu(settings)
+    psms = []
+    for i in range(24):
+        kw = synth.unpack_psm(src, i)
+        psms.append(dict(mz=kw["mz_arr"], intensity=kw["int_arr"], peptide=kw1["peptide"], n_of_mod=2, max_charge=1))
+    every = gpu.score_batch(synth.pack_batch(psms), probs=True)
+    scored = np.flatnonzero(every["psm_probs"]["kind"] == pc.SCORED)
+    assert scored.size >= 8
+    n, n_ch = 8, 3
+    batch = synth.pack_batch([psms[i] for i in scored[:n]])
+    res = gpu.score_batch(batch, probs=True)
+    assert (res["psm_probs"]["kind"] == pc.SCORED).all()
+    group = np.zeros(n, np.int32)
+    values = pc.matrix(n, n, n_ch)
+    p = ru.site_quant_params(threshold=0.5, scale_log2=SCALE, n_channels=n_ch)
+    dev = torch.device("cuda", 0)
+    plan = _run_plan(gpu, batch, dev)
+    _, sp, pp = plan.probs()
+    d_group, d_values = torch.from_numpy(group).to(dev), torch.from_numpy(values).to(dev)
+    first = plan.peptidoform_quant(sp, pp, d_group, d_values, p, threshold=LIST_THR)
+    plan.check()
+    f_pair, f_n = _down(*first)
+    assert f_n == 1 and f_pair[0].size == 1                                           # the list has exactly one record
+    once = _ref(res, group, values, None, 0.5)
+    assert int(once[1]["n_records"][0]) == n and once[2]["sum"].any()
+    pc.same(f_pair, once, "8 PSMs on one peptidoform, no earlier pair")
+    d_first = tuple(t[:f_n].contiguous() for t in first[:3])
+    got, count = _down(*plan.peptidoform_quant(sp, pp, d_group, d_values, p, threshold=LIST_THR, prev=d_first))
+    plan.check()
+    twice = _ref(res, group, values, None, 0.5, prev=f_pair)
+    assert count == 1 and twice[0].size == 1 and int(twice[1]["n_records"][0]) == 2 * n
+    for field in ("sum", "n", "n_saturated"):
+        assert (twice[2][field] == 2 * once[2][field]).all(), field
+    pc.same(got, twice, "8 PSMs and their own earlier record in one group")
+
+
 # ---- the reduce calls on synthetic pairs ----
 @pytest.fixture(scope="module")
 def ctx():

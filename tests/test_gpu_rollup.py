@@ -370,6 +370,40 @@ def DevicePlanNotRun(gpu, batch):
     return DevicePlan(gpu, batch, rollup=True)
 
 
+def test_the_report_is_the_last_call_s_on_whatever_stream():
+    """one plan asked on two streams in turn, with nothing between them that orders the streams: the second call waits for the
+    first call's report event before it clears the two words, so check() sees the words of the LAST call -- nothing to report
+    after (outside, inside), the roll-up's error after (inside, outside) -- and the tables are what the calls give alone"""
+    import torch
+    from pyascore_amd.device import rollup_records
+    batch, settings = synth.make_batch("cfg2", n_psm=200, seed=9990)
+    batch, peptides = _repeats(batch)
+    gpu = _gpu(settings)
+    res = gpu.score_batch(batch, probs=True)
+    slot, n_slots, _ = ru.peptide_slots(peptides, res["site_off"], residues=settings["mod_group"])
+    want = _ref(res, slot, n_slots)
+    dev = torch.device("cuda", 0)
+    plan = _plan(gpu, batch, dev)
+    _, sp, pp = plan.probs()
+    d_slot = torch.from_numpy(slot).to(dev)
+    outside = torch.full_like(d_slot, n_slots)
+    streams = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    for calls, fails in (((outside, d_slot), False), ((d_slot, outside), True)):
+        tables = plan.rollup_clear(n_slots), plan.rollup_clear(n_slots)
+        torch.cuda.synchronize()                                               # (the inputs are there; from here on only the library orders)
+        for st, d, table in zip(streams, calls, tables):
+            with torch.cuda.stream(st):
+                plan.rollup(sp, pp, d, table)
+        if fails:
+            with pytest.raises(ValueError, match="pya_plan_rollup"):
+                plan.check()
+        else:
+            plan.check()
+        torch.cuda.synchronize()
+        for d, table in zip(calls, tables):
+            _same_bytes(rollup_records(table.cpu().numpy()), ru.empty(n_slots) if d is outside else want, "outside" if d is outside else "inside")
+
+
 def test_a_handful_and_a_batch_of_one():
     batch, settings = synth.make_batch("cfg2", n_psm=300, seed=9995)
     batch, peptides = _repeats(batch)

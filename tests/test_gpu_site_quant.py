@@ -473,6 +473,43 @@ def test_limits_and_guards():
     assert rc == _lib.PYA_ERR_ARG and b"PYA_FLAG_QUANT" in gpu._lib.pya_last_error(gpu._h)
 
 
+def test_two_reports_in_one_run_and_none_after_it():
+    """the 200-PSM plan above: a roll-up call and a site-quantification call of one run both have something to report, and
+    check() names the roll-up, the first in its order; the reports belong to their run -- after the next run, with no stage
+    asked, check() passes --, and a good call behind that run gives the yardstick's table"""
+    import torch
+    from pyascore_amd.device import DevicePlan, rollup_records, site_quant_records
+    batch, settings = synth.make_batch("cfg2", n_psm=200, seed=9770)
+    batch, peptides = _repeats(batch)
+    gpu = _gpu(settings)
+    res = gpu.score_batch(batch, probs=True)
+    thr = _threshold(res)
+    slot, n_slots, _ = ru.peptide_slots(peptides, res["site_off"], residues=settings["mod_group"])
+    values = _matrix(17, 200, 3)
+    want = _ref(res, slot, n_slots, values, None, thr)
+    dev = torch.device("cuda", 0)
+    d_mz, d_in = torch.from_numpy(batch["mz"]).to(dev), torch.from_numpy(batch["intensity"]).to(dev)
+    plan = DevicePlan(gpu, batch, quant=True)
+    plan.run(d_mz, d_in)
+    _, sp, pp = plan.probs()
+    p = ru.site_quant_params(threshold=thr, scale_log2=SCALE, n_channels=3)
+    d_slot, d_values = torch.from_numpy(slot).to(dev), torch.from_numpy(values).to(dev)
+    host = lambda t: site_quant_records((t[0].cpu().numpy(), t[1].cpu().numpy()))   # noqa: E731
+    rolled = plan.rollup_clear(n_slots)
+    plan.rollup(sp, pp, torch.full_like(d_slot, n_slots), rolled)                   # every slot outside
+    table = plan.site_quant(sp, pp, d_slot, d_values, p, n_slots=n_slots, row_base=200)   # every row outside
+    with pytest.raises(ValueError, match="pya_plan_rollup"):
+        plan.check()
+    assert rollup_records(rolled.cpu().numpy()).tobytes() == ru.empty(n_slots).tobytes()
+    _same(host(table), ru.empty_site_quant(n_slots, 3), "a call whose rows are all outside")
+    plan.run(d_mz, d_in)                                                             # the next run: nothing of it has been asked
+    plan.check()
+    _, sp, pp = plan.probs()
+    plan.site_quant(sp, pp, d_slot, d_values, p, table=table)
+    plan.check()
+    _same(host(table), want, "a good call behind the second run")
+
+
 def test_set_aside_and_unscored_psms():
     good, settings = synth.make_batch("cfg2", n_psm=12, seed=9930)
     psms = []

@@ -289,9 +289,12 @@ def test_header_and_bindings_declare_the_interface():
     csrc = os.path.join(ROOT, "pyascore_amd", "csrc")
     rule = open(os.path.join(csrc, "quant_rule.hip.h")).read()
     assert "281474976710656.0" in rule
-    for name in ("site_quant.hip", "pform_quant.hip"):                              # the quantum rule exists once
+    wave = open(os.path.join(csrc, "quant_wave.hip.h")).read()                      # the quantum rule exists once, and so does the
+    assert '#include "quant_rule.hip.h"' in wave and "281474976710656" not in wave and "qr_quantum(" in wave   # wave reduce that applies it
+    for name in ("site_quant.hip", "pform_quant.hip"):
         body = open(os.path.join(csrc, name)).read()
-        assert '#include "quant_rule.hip.h"' in body and "281474976710656" not in body and "qr_quantum(" in body, name
+        assert '#include "quant_wave.hip.h"' in body and "281474976710656" not in body and "qw_reduce(" in body, name
+        assert "qr_quantum(" not in body and "__ballot(" not in body, name
 
 
 @pytest.mark.parametrize("n_mod", [None, 1])
