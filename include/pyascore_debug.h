@@ -39,6 +39,12 @@ int pya_set_debug(pya_handle *h, const char *key, const char *value);
  * No reference counterpart. */
 int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]);
 
+/* The handle's device tables as they are now: out[0] entries of the signature order table that are on the device, out[1] rows
+ * of the score table that are, out[2] uploads of the DevConfig so far, out[3] the device address of the score table as an
+ * integer (a table that grows is uploaded into a new allocation).  The tests of live plans read from it that a table grew and
+ * moved between two runs of one plan, and that a refused call uploaded nothing.  No reference counterpart. */
+int pya_debug_table_sizes(const pya_handle *h, uint64_t out[4]);
+
 /* Plans the last pya_score_batch / pya_score_batch_shared / pya_score_batch_typed call on the handle was cut into (1: one
  * plan, not pipelined; 0: no call yet).  The tests read from it that a budget cuts a float32 batch into no more chunks than
  * the same batch widened.  No reference counterpart. */

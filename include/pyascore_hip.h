@@ -887,6 +887,10 @@ typedef struct pya_results {
 
 int pya_create(const pya_config *cfg, pya_handle **out);
 void pya_destroy(pya_handle *h);
+/* PyAscore.add_neutral_loss.  Changes what every later call scores under -- and ENDS THE LAUNCHING LIFE of every plan the
+ * handle has made so far, the retained batch of a PYA_FLAG_KEEP call included (see pya_plan_create): the handle's settings
+ * generation goes up with every call, a repeated identical one and one that fails with PYA_ERR_LIMIT too.  Results already
+ * produced stay readable (pya_get_pep_scores*, pya_plan_check, the timing ring): they are those of the old settings. */
 int pya_add_neutral_loss(pya_handle *h, const char *group, float mass);
 /* PyAscore.score for ONE PSM with the lowest latency (Ascore.pyx:103-152; the reference's own command line
  * calls it once per PSM, pyascore/__main__.py:129-164): no plan, no copies -- the spectrum is staged in pinned
@@ -1364,7 +1368,18 @@ int pya_peptidoform_quant_reduce_host(pya_handle *h, const pya_peptidoform *a, c
                                       uint64_t n_b, uint32_t n_channels, pya_peptidoform *out, pya_site_quant_head *head, pya_site_quant *cell,
                                       uint64_t cap, uint64_t *n);
 
-/* device-resident path: plan once (host pre-pass, tables, workspace), run many times */
+/* device-resident path: plan once (host pre-pass, tables, workspace), run many times.
+ * LIFETIME.  A plan belongs to the handle and to the SETTINGS it was made under: its routes, launch caps, LDS carves and its
+ * score-table need are fixed then.  It stays valid while the handle makes other plans, scores other batches or single PSMs,
+ * and while the handle's own device tables grow and move (a run asks for them anew).  After pya_add_neutral_loss on the
+ * handle every call that would LAUNCH over the plan -- pya_plan_run, pya_plan_run_typed, pya_plan_evidence,
+ * pya_plan_ions_count, pya_plan_ions, pya_plan_named, pya_plan_sites, pya_plan_probs, pya_plan_ranked, pya_plan_rollup,
+ * pya_plan_site_quant, pya_plan_peptidoforms, pya_plan_peptidoform_quant, pya_plan_mz_profile, pya_plan_coverage, and
+ * pya_calculate_ambiguity over a retained batch -- returns PYA_ERR_STATE ("settings changed since the plan was made") with
+ * nothing enqueued; the library does not rebuild a plan behind its caller's back.  Make a new plan.  What only reads back
+ * (pya_plan_check, pya_plan_timings*, pya_plan_workspace_bytes, pya_plan_site_offsets, pya_get_pep_scores*) and
+ * pya_plan_destroy stay valid.  The debug switches of pyascore_debug.h and the sizes (workspace budget, ranked list length,
+ * site cap) do not end a plan's life. */
 int pya_plan_create(pya_handle *h, const pya_batch *batch, uint32_t flags, pya_plan **out);
 /* the same for a batch whose PSMs share spectra (pya_score_batch_shared: batch->peak_off describes n_spectra spectra,
  * spec_of[i] names PSM i's; the reference's hit_depth loop, pyascore/__main__.py).  pya_plan_run and every other pya_plan_*

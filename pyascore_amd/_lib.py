@@ -332,6 +332,7 @@ SYMBOLS = {
     "pya_set_debug": (C.c_int, [_vp, C.c_char_p, C.c_char_p]),          # include/pyascore_debug.h (test-only)
     "pya_debug_wave_ops": (C.c_int, [_vp, _vp, _vp]),         # (test-only)
     "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
+    "pya_debug_table_sizes": (C.c_int, [_vp, _vp]),           # (test-only)
     "pya_debug_last_probs_launch": (C.c_int, [_vp, _vp, _vp]),        # (test-only)
     "pya_debug_last_ranked_launch": (C.c_int, [_vp, _vp, _vp]),       # (test-only)
     "pya_debug_last_rollup_launch": (C.c_int, [_vp, _vp, _vp]),       # (test-only)

@@ -505,7 +505,10 @@ class PyAscore:
     # ------------------------------------------------------------------------------------------
     def add_neutral_loss(self, group, mass):
         """Add a neutral loss ion to any fragment containing specified amino acids
-        (Ascore.pyx:81-99).  Upper case = unmodified residue, lower case = modified residue."""
+        (Ascore.pyx:81-99).  Upper case = unmodified residue, lower case = modified residue.  Every later call scores
+        under the new settings; what was made under the old ones -- a ``DevicePlan``, the retained batch of ``score_batch(...,
+        keep=True)``, the records of the last ``score()`` PSM -- can still be READ (``batch_pep_scores``, ``pep_scores``) but
+        no longer launched over: ``DevicePlan.run`` and its stages and ``calculate_ambiguity`` raise ``RuntimeError``."""
         if not isinstance(group, str):
             raise TypeError("Argument 'group' has incorrect type (expected str)")
         self._ensure_kept()      # (the last score() PSM's records, if they are still to be produced: under the old settings)

@@ -98,6 +98,7 @@ int pya_add_neutral_loss(pya_handle *h, const char *group, float mass) {
     for (const char *c = group; *c; c++) h->nl[*c] = mass;     /* ModifiedPeptide.cpp:99-103 */
     h->cfg_dirty = true;
     h->one.have_last = false;        /* (a replay of the last pya_score_one PSM would score it under the new settings) */
+    h->settings_gen++;               /* every call, an identical or a refused one too: plans made before it do not launch again */
     int rc = build_dev_config(h);
     if (rc) {
         h->nl = saved;
@@ -417,6 +418,7 @@ int pya_calculate_ambiguity(pya_handle *h, uint64_t psm, uint64_t ref_bits, cons
     if (!h || !ref_scores || !other_scores || !out) return PYA_ERR_ARG;
     pya_plan *p = h->kept;
     if (!p) return h->fail(PYA_ERR_STATE, -1, "no batch retained: call pya_score_batch with PYA_FLAG_KEEP first");
+    if (const int rc_gen = plan_settings_stale(p, "pya_calculate_ambiguity")) return rc_gen;   /* (the retained batch is a plan) */
     if (psm >= p->n_psm) return h->fail(PYA_ERR_ARG, -1, "PSM index out of range");
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t L = p->pep_off[psm + 1] - p->pep_off[psm];
@@ -451,6 +453,15 @@ int pya_calculate_ambiguity(pya_handle *h, uint64_t psm, uint64_t ref_bits, cons
     HIPCHK(h, hipMemcpy(res, d_out.p, sizeof res, hipMemcpyDeviceToHost));
     if (res[1] != 0.f) return h->fail(PYA_ERR_LIMIT, (int64_t)psm, "trial count outside the score table");
     *out = res[0];
+    return PYA_OK;
+}
+
+int pya_debug_table_sizes(const pya_handle *h, uint64_t out[4]) {
+    if (!h || !out) return PYA_ERR_ARG;
+    out[0] = (uint64_t)h->order_uploaded;
+    out[1] = (uint64_t)h->lut_uploaded_n;
+    out[2] = h->cfg_uploads;
+    out[3] = (uint64_t)(uintptr_t)h->d_lut.p;
     return PYA_OK;
 }
 

@@ -313,6 +313,26 @@ struct pya_handle {
     DevConfig cfg;
     bool cfg_dirty = true;
     DevBuf<DevConfig> d_cfg;
+    /* The settings generation: bumped by everything that changes what a plan was sized under.  A plan records the value it was
+     * made under (pya_plan::settings_gen) and every entry point that launches over a plan refuses with PYA_ERR_STATE when the
+     * two differ (plan_settings_stale, below).
+     *   bumps:       pya_add_neutral_loss -- a plan's routes (plain_types -> fused / count-node / lean lists), its caps (per_type,
+     *                pair_cap, list_cap = f(n_uniq)), hash_ok(max_k, n_nl) and its score-table need were fixed under the old
+     *                DevConfig, while the launch sizing of a run reads h->cfg as it is then.  Every call bumps, a repeated
+     *                identical one too: the setter does not compare.
+     *   does not:    pya_set_debug / pya_reload_env.  The switches a plan is BUILT under are copied into it or spent when it
+     *                is made (PYA_SB, PYA_GTP, PYA_HASH_PP: Bucket::take_knobs; PYA_NO_FORK: pya_plan::fork; PYA_STAMPS,
+     *                PYA_DEBUG's kernel bits: BatchDev; PYA_NO_PLAIN, PYA_NO_FUSED, PYA_NO_BIG, PYA_NO_BIG_INLINE, PYA_PLAIN_MIN,
+     *                PYA_BIG_MIN_N, PYA_ONE_PEAK_CLASS, PYA_PEAK_CLASSES, PYA_ONE_LDS_CLASS: the id lists).  The ones a RUN
+     *                reads (PYA_NO_CNT, PYA_DEBUG bit 0x8000, PYA_NO_NODES, PYA_NODE_CAP, PYA_NO_PREFIX, PYA_NO_TINY,
+     *                PYA_TINY_MAX, PYA_BIN_SELECT_MIN, PYA_BIN_SELECT_SCAP, PYA_SORT_ROOM, PYA_SORT_ROOM_MAX, PYA_NO_LOC_HASH,
+     *                PYA_NO_PROB_CNT) each choose between kernels that the same call sizes, LDS included, from the plan's bucket
+     *                caps, which no switch enters; nothing of the arena depends on them.  PYA_HOST_TIMING prints.
+     *                PYA_SLOW_NULL_STREAM, PYA_NO_UPLOAD_THREAD, PYA_NO_CHUNKS, PYA_CHUNK_MB, PYA_WORKSPACE_MB and
+     *                pya_set_workspace_budget, pya_set_ranked_k, pya_set_site_sig_cap are read by pya_score_one / the batch
+     *                calls, which make their own plans per call. */
+    uint64_t settings_gen = 0;
+    uint64_t cfg_uploads = 0;                 /* uploads of d_cfg so far (pya_debug_table_sizes) */
 
     std::vector<float> lut;
     std::vector<uint32_t> lut_off;
@@ -705,6 +725,7 @@ struct Bucket {
 
 struct pya_plan {
     pya_handle *h = nullptr;
+    uint64_t settings_gen = 0;           /* pya_handle::settings_gen when the plan was made */
     uint32_t flags = 0;
     uint64_t n_psm = 0;
     int64_t total_peaks = 0, total_sigs = 0;
@@ -934,6 +955,14 @@ struct pya_plan {
     }
     uint64_t workspace_bytes() const { return arena.bytes(); }
 };
+
+/* Asked by every entry point that launches over a plan, before anything is enqueued: PYA_ERR_STATE when a setting the plan
+ * was sized under has changed since (pya_handle::settings_gen).  Read-backs of what a run has produced do not ask. */
+inline int plan_settings_stale(pya_plan *p, const char *who) {
+    if (p->settings_gen == p->h->settings_gen) return PYA_OK;
+    return p->h->fail(PYA_ERR_STATE, -1, "%s: settings changed since the plan was made (pya_add_neutral_loss): its routes and caps belong "
+                                         "to the old settings; make a new plan", who);
+}
 
 /* ---- functions shared between the host files ---- */
 /* host_tables.cpp: configuration -> DevConfig, score table, pre-sort order tables */

@@ -154,6 +154,7 @@ int one_run(pya_handle *h, bool keep, uint32_t max_k) {
         if (!o.view) o.view = new pya_plan;
         pya_plan *p = o.view;
         p->h = h;
+        p->settings_gen = h->settings_gen;
         p->flags = PYA_FLAG_KEEP;
         p->n_psm = 1;
         p->peak_cap = cap;

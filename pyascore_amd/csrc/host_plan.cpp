@@ -813,6 +813,7 @@ int plan_create_impl(pya_handle *h, const pya_batch *b, uint32_t flags, const Io
     Lap lap{h->kn.host_timing};
     std::unique_ptr<pya_plan> p(new pya_plan);
     p->h = h;
+    p->settings_gen = h->settings_gen;                       /* (sync_config above: the device has this generation's DevConfig) */
     for (Bucket &bk : p->buckets) bk.take_knobs(h->kn);      /* (PYA_SB / PYA_GTP / PYA_HASH_PP of THIS handle) */
     p->fusedb.take_knobs(h->kn);
     p->bigloc.take_knobs(h->kn);

@@ -279,6 +279,7 @@ int pya_plan_run(pya_plan *p, const double *d_mz, const double *d_inten, void *h
 int pya_plan_run_typed(pya_plan *p, const pya_typed_spectra *sp, void *hip_stream, const pya_results *o) {
     if (!p || !o) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_run")) return rc_gen;
     if (p->n_psm == 0) return PYA_OK;
     if (!sp) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_run");
     uint32_t types = 0;
@@ -520,6 +521,7 @@ int stage_behind_run(pya_plan *p, hipStream_t st, const char *who, const char *k
 int pya_plan_evidence(pya_plan *p, const pya_results *r, void *hip_stream, pya_evidence *d_out) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_evidence")) return rc_gen;
     if (p->n_psm == 0) return PYA_OK;
     if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_evidence: the plan has not been run");
     if (!d_out || !r->best_score || !r->best_sig || !r->n_sig || !r->ascores || !r->alt_mask)
@@ -552,6 +554,7 @@ int pya_plan_named(pya_plan *p, const pya_results *r, void *hip_stream, const in
                    pya_named *d_out, int32_t *d_counts, float *d_scores) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_named")) return rc_gen;
     if (p->n_psm == 0 || n_q == 0) return PYA_OK;
     if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_named: the plan has not been run");
     if (!d_q_off || !d_q_bits || !d_out || !r->best_score || !r->best_sig || !r->n_sig)
@@ -612,6 +615,7 @@ int pya_plan_site_offsets(const pya_plan *plan, int64_t *site_off) {
 int pya_plan_sites(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t sig_cap, pya_site *d_out) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_sites")) return rc_gen;
     if (p->n_psm == 0) return PYA_OK;
     if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_sites: the plan has not been run");
     site_offsets(p);
@@ -710,6 +714,7 @@ static void prob_front_ends(pya_plan *p, PcCaps caps[2], uint32_t sw[2]) {
 int pya_plan_probs(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t sig_cap, pya_site_prob *d_sites, pya_psm_prob *d_psms) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_probs")) return rc_gen;
     if (p->n_psm == 0) return PYA_OK;
     if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_probs: the plan has not been run");
     site_offsets(p);
@@ -759,6 +764,7 @@ int pya_plan_probs(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t
 int pya_plan_ranked(pya_plan *p, const pya_results *r, void *hip_stream, uint32_t top_k, uint32_t sig_cap, pya_ranked *d_out) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_ranked")) return rc_gen;
     if (top_k < 1u || top_k > PYA_MAX_RANKED)
         return h->fail(PYA_ERR_ARG, -1, "pya_plan_ranked: top_k %u is not in 1 .. %d", top_k, PYA_MAX_RANKED);
     if (p->n_psm == 0) return PYA_OK;
@@ -810,6 +816,7 @@ int pya_plan_rollup(pya_plan *p, const pya_results *r, void *hip_stream, const p
                     pya_site_rollup *d_table) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_rollup")) return rc_gen;
     if (n_slots > 0x7fffffffull) return h->fail(PYA_ERR_ARG, -1, "pya_plan_rollup: %llu slots are more than an int32 slot can name", (unsigned long long)n_slots);
     if (p->n_psm == 0) return PYA_OK;
     if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_rollup: the plan has not been run");
@@ -838,6 +845,7 @@ int pya_plan_site_quant(pya_plan *p, const pya_results *r, void *hip_stream, con
                         const pya_site_quant_params *prm, pya_site_quant_head *d_head, pya_site_quant *d_cell) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_site_quant")) return rc_gen;
     const int rc_arg = quant_check(h, "pya_plan_site_quant", n_slots, n_rows, prm);
     if (rc_arg) return rc_arg;
     if (p->n_psm == 0) return PYA_OK;
@@ -864,6 +872,7 @@ int pya_plan_peptidoforms(pya_plan *p, const pya_results *r, void *hip_stream, c
                           uint64_t n_prev, void *d_work, uint64_t work_bytes, pya_peptidoform *d_out, uint64_t cap, uint32_t *d_n) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_peptidoforms")) return rc_gen;
     bool run;
     const int rc = pform_check(h, "pya_plan_peptidoforms", p->n_psm, d_prev, n_prev, d_work, work_bytes, d_out, cap, d_n, &run);
     if (rc) return rc;
@@ -897,6 +906,7 @@ int pya_plan_peptidoform_quant(pya_plan *p, const pya_results *r, void *hip_stre
                                uint32_t *d_n) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_peptidoform_quant")) return rc_gen;
     const char *who = "pya_plan_peptidoform_quant";
     int rc = quant_check(h, who, 0, n_rows, prm);
     if (rc) return rc;
@@ -931,6 +941,7 @@ int pya_plan_mz_profile(pya_plan *p, const pya_results *r, void *hip_stream, con
                         const pya_mz_profile_params *prm, pya_mz_profile *d_table) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_mz_profile")) return rc_gen;
     const int rc_arg = mzp_check(h, "pya_plan_mz_profile", n_slots, prm);
     if (rc_arg) return rc_arg;
     if (p->n_psm == 0) return PYA_OK;
@@ -971,6 +982,7 @@ thread_local uint32_t cov_room_peaks = 1;
 int pya_plan_coverage(pya_plan *p, const pya_results *r, const pya_typed_spectra *sp, void *hip_stream, pya_coverage *d_out) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_coverage")) return rc_gen;
     if (p->n_psm == 0) return PYA_OK;
     if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_coverage: the plan has not been run");
     if (!d_out || !sp || !sp->mz || !sp->intensity || !r->best_sig || !r->n_sig)
@@ -1051,6 +1063,7 @@ int ions_launches(pya_plan *p, const BatchDev &d, int64_t *d_off, pya_ion *d_out
 int pya_plan_ions_count(pya_plan *p, const pya_results *r, void *hip_stream, int64_t *d_ion_off) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_ions_count")) return rc_gen;
     if (!d_ion_off) return h->fail(PYA_ERR_ARG, -1, "NULL device pointer passed to pya_plan_ions_count");
     HIPCHK(h, hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)hip_stream;
@@ -1086,6 +1099,7 @@ int pya_plan_ions_count(pya_plan *p, const pya_results *r, void *hip_stream, int
 int pya_plan_ions(pya_plan *p, const pya_results *r, void *hip_stream, const int64_t *d_ion_off, pya_ion *d_out, uint64_t cap) {
     if (!p || !r) return PYA_ERR_ARG;
     pya_handle *h = p->h;
+    if (const int rc_gen = plan_settings_stale(p, "pya_plan_ions")) return rc_gen;
     if (p->n_psm == 0) return PYA_OK;
     if (!p->ran) return h->fail(PYA_ERR_STATE, -1, "pya_plan_ions: the plan has not been run");
     if (p->ions_state == 0) return h->fail(PYA_ERR_STATE, -1, "pya_plan_ions: pya_plan_ions_count has not been called for this run");

@@ -166,13 +166,23 @@ int build_dev_config(pya_handle *h) {
     return PYA_OK;
 }
 
+/* The handle's device tables (d_cfg, d_lut, d_lut_off, d_order, d_inv) are replaced by a NEW allocation when they change, and
+ * live plans read them at every run through shared_tables().  A run enqueued on any stream, blocking or not, may still be
+ * reading the old allocation: the device is drained before it is released.  (hipFree waits as well; the lifetime of a table
+ * other plans read is not left to that.) */
+static hipError_t quiesce_before_reupload(const void *old) {
+    return old ? hipDeviceSynchronize() : hipSuccess;
+}
+
 int sync_config(pya_handle *h) {
     if (!h->cfg_dirty) return PYA_OK;
     int rc = build_dev_config(h);
     if (rc) return rc;
+    HIPCHK(h, quiesce_before_reupload(h->d_cfg.p));
     HIPCHK(h, h->d_cfg.upload(&h->cfg, 1));
     HIPCHK(h, hipDeviceSynchronize());
     h->cfg_dirty = false;
+    h->cfg_uploads++;
     return PYA_OK;
 }
 
@@ -186,6 +196,7 @@ int ensure_lut(pya_handle *h, uint32_t n_max) {
     for (size_t n = 0; n < h->lut_off.size(); n++)             /* the kernels compute row offsets */
         if (h->lut_off[n] != h->n_top * (uint32_t)n * ((uint32_t)n + 1u) / 2u)
             return h->fail(PYA_ERR_STATE, -1, "score table rows are not dense");
+    HIPCHK(h, quiesce_before_reupload(h->d_lut.p));
     HIPCHK(h, h->d_lut.upload(h->lut.data(), h->lut.size()));
     HIPCHK(h, h->d_lut_off.upload(h->lut_off.data(), h->lut_off.size()));
     HIPCHK(h, hipDeviceSynchronize());
@@ -277,6 +288,7 @@ uint32_t next_pow2(uint32_t v) {
 
 int upload_shared_tables(pya_handle *h) {
     if (h->order_uploaded == h->order_tab.size() && h->d_order.p) return PYA_OK;
+    HIPCHK(h, quiesce_before_reupload(h->d_order.p));
     HIPCHK(h, h->d_order.upload(h->order_tab.data(), h->order_tab.size()));
     HIPCHK(h, h->d_inv.upload(h->inv_tab.data(), h->inv_tab.size()));
     if (!h->d_binom.p) {

@@ -36,7 +36,11 @@ class DevicePlan:
     ``site_quant()`` / ``quant=True``: the channel intensities of a device matrix summed per roll-up slot over the confidently
     localised records (``pya_plan_site_quant``; ``pyascore_amd.device.marker_values`` makes the matrix from marker records).
     ``fit_mz_calibration()`` turns such a table into an m/z calibration and ``recalibrate()`` corrects a device m/z tensor with
-    it (``pya_mz_profile_fit``, ``pya_recalibrate_spectra``), so run -> profile -> fit -> correct -> run again needs no host copy."""
+    it (``pya_mz_profile_fit``, ``pya_recalibrate_spectra``), so run -> profile -> fit -> correct -> run again needs no host copy.
+
+    A plan belongs to the settings it was made under: after ``scorer.add_neutral_loss`` its ``run()`` and every stage method
+    raise ``RuntimeError`` ("settings changed since the plan was made") with nothing enqueued -- make a new plan.  ``check()``,
+    ``site_offsets()``, the timings and the result tensors of the runs so far stay valid."""
 
     def __init__(self, scorer, batch, timing=False, max_k=None, evidence=False, ions=False, named=False, sites=False, probs=False,
                  ranked=False, rollup=False, peptidoforms=False, mz_profile=False, coverage=False, quant=False, peptidoform_quant=False):
