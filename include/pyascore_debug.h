@@ -23,7 +23,8 @@ extern "C" {
  *     PYA_NO_LOC_HASH PYA_NO_NODES PYA_NO_CNT PYA_NO_PROB_CNT (the probability stage scores every PSM with its
  *     general front end, csrc/probs.hip) PYA_HOST_TIMING PYA_STAMPS PYA_SLOW_NULL_STREAM PYA_NO_FORK (r06: the
  *     fused family behind the scoring kernels on the caller's stream instead of beside them on the plan's side stream)
- *   numbers: PYA_DEBUG (bit set, common.h) PYA_PLAIN_MIN PYA_BIG_MIN_N PYA_TINY_MAX PYA_SORT_ROOM_MAX PYA_SB PYA_GTP
+ *   numbers: PYA_DEBUG (bit set, common.h; 0x08000000 = no split walk: the fused score-localize body walks every PSM
+ *     on its walker lanes alone, for A/B runs and tests/test_gpu_split_walk.py) PYA_PLAIN_MIN PYA_BIG_MIN_N PYA_TINY_MAX PYA_SORT_ROOM_MAX PYA_SB PYA_GTP
  *     PYA_HASH_PP PYA_NODE_CAP PYA_CHUNK_MB PYA_WORKSPACE_MB
  *     PYA_BIN_SELECT_MIN (r06: peak classes above this many peaks are binned by selection, csrc/bin_select.hip.h; default 640,
  *     0 = every class, a huge value = none) PYA_BIN_SELECT_SCAP (survivor slots per spectrum there; default 768) */

@@ -234,6 +234,97 @@ DEV CumCounts walk_record(const float2 *resd, const uint4 *lut, const PeakTable 
     return cum;
 }
 
+/* walk_record_steps for charge 1 with two consecutive steps of a lane per iteration: the second running sum needs the first
+ * and one addition, so both lookups are in flight together (walk_core.hip.h, walk_both_steps, does the same with a lane's two
+ * directions); the two rank bytes are stored after both, because a byte store between them would keep the second lookup's
+ * reads behind it */
+template <bool BZ>
+DEV void walk_record_pairs(const float2 *&rp, int rstride, StepBits &bits, float &running, const uint4 *lut, CumCounts &cum,
+                           const PeakTable &tab, double A, double B, uint8_t *&ro, int stride, int count) {
+    int i = 0;
+    for (; i + 2 <= count; i += 2, rp += 2 * rstride, ro += 2 * stride) {
+        const float2 ma = rp[0], mb = rp[rstride];
+        const float ra = (bits.next() ? ma.y : ma.x) + running;              /* ModifiedPeptide.cpp:385-389 */
+        const float rb = (bits.next() ? mb.y : mb.x) + ra;
+        running = rb;
+        const double da = BZ ? (double)ra + A : ((double)ra + A) - B, db = BZ ? (double)rb + A : ((double)rb + A) - B;
+        const Look ka = look4(tab, charge_mz(da, 1)), kb = look4(tab, charge_mz(db, 1));
+        int rka = ka.best, rkb = kb.best;
+        if (ka.more()) rka = look_rest(tab, ka);
+        if (kb.more()) rkb = look_rest(tab, kb);
+        cum.add(lut[rka]);
+        cum.add(lut[rkb]);
+        ro[0] = (uint8_t)rka;
+        ro[stride] = (uint8_t)rkb;
+    }
+    if (i < count) walk_record_steps<BZ>(rp, rstride, bits, running, lut, cum, tab, 1, A, B, ro, stride, 1);
+}
+
+/* The split walk (charge 1, both directions, at most 21 site assignments, mz_error <= 0.49): in the layout of lanes 0..31
+ * forward and 32..63 backward, a PSM of N site assignments leaves 64 - 2 N lanes without a walker, and they would run every
+ * instruction of the L - 1 steps for nothing.  With 3 N <= 64, N of them become helpers, one per site assignment: helper h
+ * walks the first x = (L - 1) / 3 steps of assignment h forward, then its first x steps backward, and records their ranks in
+ * the rows and columns the two walkers of h would have used; the walkers look up steps x .. L - 2 only.  The wavefront then
+ * runs L - 1 - x lookup steps instead of L - 1.
+ * A fragment's m/z depends on the float32 running sum built residue by residue from the terminus, so a walker first adds up
+ * its steps 0 .. x - 1 without looking anything up (the loop of walk_sums_only) and a helper starts at 0: every sum is built
+ * by the sequence of additions walk_record makes.
+ * `dir`, `w`: direction and column of a walker; a helper passes 0 and its assignment's forward column (its backward column is
+ * N further on).  `resmask`: the lane's site assignment (a helper's: the one it serves).  A helper's counts are its own: the
+ * caller adds them to the forward walker's.  The steps past 2 x (at most two) run on the walkers alone.  The steps go two
+ * at a time (walk_record_pairs); a run of steps ends where a lane changes its mask word or a helper turns round. */
+template <bool BZ>
+DEV CumCounts walk_record_split(const float2 *resd, const uint4 *lut, const PeakTable &tab, int L, int x, uint64_t resmask, int dir,
+                                bool helper, double Af, double Bf, double Ab, double Bb, uint8_t *rkl, int stride, int w, int N) {
+    const int n = L - 1;
+    const uint64_t fwd_m = __brevll(resmask), back_m = resmask << (64 - L);    /* MSB first: bit 63 = step 0 of the direction */
+    uint64_t M = dir ? back_m : fwd_m;
+    const float2 *rp = resd + (dir ? n : 0);
+    int rstride = dir ? -1 : 1;
+    double A = dir ? Ab : Af, B = dir ? Bb : Bf;
+    float running = 0.f;
+    if (!helper) {                                           /* a walker's sum over the steps its helper looks up */
+        StepBits pre = {(uint32_t)(M >> 32)};                /* (x <= 21 steps: one mask word) */
+        int i = 0;
+        for (; i + 4 <= x; i += 4, rp += 4 * rstride) {      /* (four reads on their way together) */
+            const float2 m0 = rp[0], m1 = rp[rstride], m2 = rp[2 * rstride], m3 = rp[3 * rstride];
+            running = (pre.next() ? m0.y : m0.x) + running;
+            running = (pre.next() ? m1.y : m1.x) + running;
+            running = (pre.next() ? m2.y : m2.x) + running;
+            running = (pre.next() ? m3.y : m3.x) + running;
+        }
+        for (; i < x; i++, rp += rstride) {
+            const float2 mm = *rp;
+            running = (pre.next() ? mm.y : mm.x) + running;
+        }
+        M <<= x;                                             /* bit 63 = step x */
+    }
+    StepBits bits = {(uint32_t)(M >> 32)};
+    uint8_t *ro = rkl + (helper ? 0 : x * stride) + w;
+    CumCounts cum = {0u, 0u, 0u};
+    /* a walker's steps x .. 2 x - 1 (x < 32: one mask word), a helper's forward steps */
+    walk_record_pairs<BZ>(rp, rstride, bits, running, lut, cum, tab, A, B, ro, stride, x);
+    if (helper) {                                            /* a helper turns round: column N + h, rows 0 .. x - 1 */
+        rp = resd + n;
+        rstride = -1;
+        bits.w = (uint32_t)(back_m >> 32);
+        running = 0.f;
+        A = Ab;
+        B = Bb;
+        ro = rkl + N + w;
+    }
+    const int T = n - x;                                     /* lookup steps of a walker; a helper has 2 x <= T */
+    for (int done = x; done < T;) {
+        if (done == 32 && !helper) bits.w = (uint32_t)M;     /* a walker's mask words change after 32 steps */
+        int next = done < 2 * x ? 2 * x : T;
+        if (done < 32 && next > 32) next = 32;
+        if (!(helper && done >= 2 * x))
+            walk_record_pairs<BZ>(rp, rstride, bits, running, lut, cum, tab, A, B, ro, stride, next - done);
+        done = next;
+    }
+    return cum;
+}
+
 /* the same walk without lookups: fragment m/z of one signature and direction to out[z-1][step] */
 DEV void walk_mz_only(const float2 *resd, int L, int zmax, uint64_t resmask, int dir, double A, double B, float *out) {
     const uint64_t tmask = dir ? (__brevll(resmask) >> (64 - L)) : resmask;
@@ -370,8 +461,13 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
     const int s = (BOTH && !two_pass) ? (lane & 31) : lane;
     const int dir = BOTH ? (two_pass ? 0 : (lane >> 5)) : (cfg->n_fwd > 0 ? 0 : 1);
     const bool active = s < N;
+    /* the split walk (walk_record_split): of the lanes without a walker, N..31 and 32 + N..63, the first N are helpers,
+     * helper lane N + h or 2 N + h for site assignment h.  PYA_DEBUG bit 0x08000000: no split walk. */
+    const bool split = BOTH && !ZM && !WIDE && 3 * N <= 64 && L - 1 >= 6 && !(cfg->mz_error > 0.49f) && !(b.debug & 0x08000000u);
+    const int hs = lane - (lane < 32 ? N : 2 * N);
+    const bool helper = split && !active && hs < N;
     const uint32_t letter = lane < L ? (uint32_t)b.pep[pep0 + lane] : (uint32_t)'A';
-    const uint64_t bits = active ? order[s] : 0ull;
+    const uint64_t bits = active ? order[s] : (helper ? order[hs] : 0ull);   /* (a helper's: read by its walk alone) */
     uint32_t aux_pos = 0;
     float aux_mass = 0.f;
     if (lane < n_aux) {
@@ -453,8 +549,24 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
     const bool wide = !__any(lane < L && !(m0 > wide_min && m1 > wide_min));
     wave_lds_sync();
     STAMP_T(b, 40, false);
-    CumCounts cum = walk_record(f.resd, f.cum_lut, tab, L, zmax, resmask, dir, dir ? Ab : Af, dir ? Bb : Bf, Bf == 0. && Bb == 0.,
-                                f.rkl, (int)stride, w);
+    CumCounts cum;
+    if (split) {
+        const int sd = helper ? 0 : dir, sw = helper ? hs : w, x = Lm1 / 3;
+        cum = (Bf == 0. && Bb == 0.)
+                  ? walk_record_split<true>(f.resd, f.cum_lut, tab, L, x, resmask, sd, helper, Af, Bf, Ab, Bb, f.rkl, (int)stride, sw, N)
+                  : walk_record_split<false>(f.resd, f.cum_lut, tab, L, x, resmask, sd, helper, Af, Bf, Ab, Bb, f.rkl, (int)stride, sw, N);
+        /* the helper's counts to the forward walker of its site assignment (integers: the order of the sums is free) */
+        const int from = s + N < 32 ? s + N : s + 2 * N;
+        const uint32_t ha = __shfl(cum.a, from, 64), hb = __shfl(cum.b, from, 64), hc = __shfl(cum.c, from, 64);
+        if (active && lane < 32) {
+            cum.a += ha;
+            cum.b += hb;
+            cum.c += hc;
+        }
+    } else {
+        cum = walk_record(f.resd, f.cum_lut, tab, L, zmax, resmask, dir, dir ? Ab : Af, dir ? Bb : Bf, Bf == 0. && Bb == 0., f.rkl,
+                          (int)stride, w);
+    }
     if (two_pass) {                                         /* ... and the same lane's backward walk (column N + s) */
         const CumCounts back = walk_record(f.resd, f.cum_lut, tab, L, zmax, resmask, 1, Ab, Bb, Bf == 0. && Bb == 0., f.rkl, (int)stride,
                                            active ? N + s : (int)stride - 1);
