@@ -24,7 +24,8 @@ extern "C" {
  *     general front end, csrc/probs.hip) PYA_HOST_TIMING PYA_STAMPS PYA_SLOW_NULL_STREAM PYA_NO_FORK (r06: the
  *     fused family behind the scoring kernels on the caller's stream instead of beside them on the plan's side stream)
  *   numbers: PYA_DEBUG (bit set, common.h; 0x08000000 = no split walk: the fused score-localize body walks every PSM
- *     on its walker lanes alone, for A/B runs and tests/test_gpu_split_walk.py) PYA_PLAIN_MIN PYA_BIG_MIN_N PYA_TINY_MAX PYA_SORT_ROOM_MAX PYA_SB PYA_GTP
+ *     on its walker lanes alone, for A/B runs and tests/test_gpu_split_walk.py; 0x04000000 = no span count: it pairs the
+ *     span ions of every PSM by their m/z lists, for A/B runs and tests/test_gpu_span_count.py) PYA_PLAIN_MIN PYA_BIG_MIN_N PYA_TINY_MAX PYA_SORT_ROOM_MAX PYA_SB PYA_GTP
  *     PYA_HASH_PP PYA_NODE_CAP PYA_CHUNK_MB PYA_WORKSPACE_MB
  *     PYA_BIN_SELECT_MIN (r06: peak classes above this many peaks are binned by selection, csrc/bin_select.hip.h; default 640,
  *     0 = every class, a huge value = none) PYA_BIN_SELECT_SCAP (survivor slots per spectrum there; default 768) */
@@ -45,6 +46,16 @@ int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]);
  * integer (a table that grows is uploaded into a new allocation).  The tests of live plans read from it that a table grew and
  * moved between two runs of one plan, and that a refused call uploaded nothing.  No reference counterpart. */
 int pya_debug_table_sizes(const pya_handle *h, uint64_t out[4]);
+
+/* Whether the fused score-localize kernel counts the site-determining ions of this PSM's spans instead of pairing them by
+ * their m/z lists (csrc/span_guard.h), restated on the host in the kernel's float32 / float64 operations from the handle's
+ * mod_group, mod_mass and mz_error, the peptide (len <= 64 letters) and its fixed modifications (aux_pos, aux_mass as in a
+ * pya_batch: position 0 = the N-terminus, else residue aux_pos - 1).  Returns 1 (counted), 0 (paired) or PYA_ERR_ARG.  It is
+ * the decision per PSM: a launch with fragment charges above 1 and PYA_DEBUG bits 2048 / 0x04000000 pair every PSM.  out (may be
+ * NULL): [0] E = mz_error + the PSM's rounding margin, [1], [2] the interval every modifiable residue's mass delta must lie in.
+ * The tests place inputs on a chosen side of the guard with it; the results are the same on both.  No reference counterpart. */
+int pya_debug_span_guard(const pya_handle *h, const char *peptide, uint64_t len, const uint32_t *aux_pos, const float *aux_mass,
+                         uint64_t n_aux, double out[3]);
 
 /* Plans the last pya_score_batch / pya_score_batch_shared / pya_score_batch_typed call on the handle was cut into (1: one
  * plan, not pipelined; 0: no call yet).  The tests read from it that a budget cuts a float32 batch into no more chunks than

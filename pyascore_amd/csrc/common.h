@@ -144,7 +144,8 @@ struct BatchDev {
      * neighbour through the exact run walk too (no closed form for {ion, winner's ion outside the span, its twin}), 0x10000000
      * score_big leaves no candidate records (the PepScores of all site assignments go to the workspace, the finishing kernel
      * ranks, gathers and recounts: the r05 route), 0x08000000 no split walk in the fused kernel (fused_core.hip.h,
-     * walk_record_split: every PSM walks all its steps on its walker lanes, no helper lanes).  Ablation: 2 the hash route
+     * walk_record_split: every PSM walks all its steps on its walker lanes, no helper lanes), 0x04000000 no span count in the
+     * fused kernel (span_guard.h: every PSM's span ions are paired by their m/z lists).  Ablation: 2 the hash route
      * looks no surviving ion up.
      * Bits 16..31: truncation point of the diagnostic build (device_common.hip.h, STAMP_T). */
     uint32_t debug;

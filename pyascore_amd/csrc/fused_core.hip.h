@@ -13,7 +13,9 @@
  * LDS) while it scores; once the winner and its single-move competitors are known, only THEIR
  * fragment m/z are re-derived (a walk without lookups: the float32 running sums) and the
  * site-determining ions become a comparison of those few lists and a count over recorded ranks:
- * no lookup, nothing through HBM but the inputs and the 64-byte result.
+ * no lookup, nothing through HBM but the inputs and the 64-byte result.  Where the residue masses rule out that a span ion of
+ * one list meets an ion of the other (span_guard.h: phospho-sized deltas on ordinary residues, charge 1) not even the lists
+ * are built: the count over the recorded ranks is all that is left.
  *
  * This kernel's speed follows its occupancy (measured: its time is inversely proportional to the
  * wavefronts resident per CU up to the VALU issue limit -- every wavefront is a chain of dependent
@@ -38,6 +40,7 @@
 #define PYA_FUSED_CORE_H
 #include "score_core.hip.h"
 #include "localize_core.hip.h"
+#include "span_guard.h"
 
 #define FUSED_ROUND 3                /* competitors localised together (plus the winner) */
 
@@ -503,6 +506,7 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
     /* ---- residues (ModifiedPeptide.cpp:24-79) from the letter and the LDS table ---- */
     float m0, m1;
     uint64_t site_mask;
+    bool modifiable_lane;
     {
         const bool in = lane < L;
         const uint32_t li = (letter - 'A') & 31u;
@@ -530,6 +534,7 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
             }
         }
         site_mask = __ballot(modifiable);
+        modifiable_lane = modifiable;
         if (in) f.resd[lane] = make_float2(m0, m1);
         if (modifiable) f.site_pos[mask_rank(site_mask)] = (uint8_t)lane;
     }
@@ -547,6 +552,14 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
      * in the other list */
     const float wide_min = 2.f * cfg->mz_error + 0.02f;
     const bool wide = !__any(lane < L && !(m0 > wide_min && m1 > wide_min));
+    /* the span count (span_guard.h): no ion of a span can have a partner, so a round counts instead of comparing m/z lists.
+     * Charge 1 only; PYA_DEBUG bit 0x04000000 switches it off. */
+    bool no_cross = false;
+    if (!ZM && presorted && wide && !(b.debug & (2048u | 0x04000000u))) {      /* (wave-uniform) */
+        const float heaviest = wave_max_f32(lane < L ? (m0 > m1 ? m0 : m1) : 0.f);
+        const SpanGuard g = span_guard_make(cfg->mz_error, cfg->mod_mass, L, heaviest);
+        no_cross = g.ok && !__any(lane < L && span_guard_residue_fails(g, m0, m1, modifiable_lane));
+    }
     wave_lds_sync();
     STAMP_T(b, 40, false);
     CumCounts cum;
@@ -702,7 +715,7 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
         const int S = 1 + nc;
         /* fragment m/z of the winner (first round only) and of the round's competitors: one lane per
          * (signature, direction), the walk of walk_record without its lookups */
-        if (lane < S * ndir && (e0 == 0 || lane >= ndir)) {
+        if (!no_cross && lane < S * ndir && (e0 == 0 || lane >= ndir)) {       /* (no_cross: no list is read) */
             const int sg = lane / ndir, d = lane - sg * ndir;
             const uint64_t sb = sg == 0 ? best_bits : f.pushed[e0 + sg - 1].bits;
             const int dd = BOTH ? d : (cfg->n_fwd > 0 ? 0 : 1);
@@ -710,7 +723,7 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
                                  f.selm + (size_t)lane * ent_cap);
             else walk_sums_only(f.resd, L, deposit_sites(sb, site_mask), dd, f.selm + (size_t)lane * ent_cap);
         }
-        if (!ZM) {
+        if (!ZM && !no_cross) {
             /* charge 1: the few lanes above leave the running sums; every lane turns a share of them into m/z
              * (ModifiedPeptide.cpp:570-591), instead of the few doing the float64 arithmetic step by step */
             wave_lds_sync();
@@ -789,7 +802,36 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
          * same argument): one binary search per ion, no replay. */
         const bool zm_clusters = ZM && !(b.debug & 2048);
         int items = items_all;
-        if (spans) {
+        if (!ZM && no_cross && !(b.debug & 1)) {
+            /* The span count (span_guard.h): no ion of a span has a partner, so every one of them is site-determining --
+             * c_tr is the span's length, c_cnt the ions of the span whose recorded rank is within the depth.  No fragment
+             * m/z is built or compared.  G lanes per (task, side), each over every G-th step of the span; their counts
+             * meet in the first by DPP (every lane is active here: the branch is wave-uniform).  The span table of the
+             * pairing (t_lo, t_off) is not built: only the pairing's item loop reads it, and that loop does not run. */
+            constexpr int G = 4;                             /* a quad: FUSED_ROUND x ndir x 2 x G <= 48 lanes, the sum by two quad_perm moves */
+            const int ts = lane / G, q = lane & (G - 1), task = ts >> 1, side = ts & 1;
+            const int c = BOTH ? task >> 1 : task, d = BOTH ? task & 1 : 0;
+            int n = 0, len = 0;
+            if (c < nc) {
+                const PushedEntry pe = f.pushed[e0 + c];
+                const uint64_t diff = best_bits ^ pe.bits;                          /* site indices */
+                const int r_lo = (int)f.site_pos[__builtin_ctzll(diff)];
+                const int r_hi = (int)f.site_pos[63 - __builtin_clzll(diff)];
+                const int dd = BOTH ? d : (cfg->n_fwd > 0 ? 0 : 1);
+                const int lo = dd ? L - 1 - r_hi : r_lo, hi = dd ? L - 1 - r_lo : r_hi;
+                const uint8_t *col = f.rkl + (d * N + (int)(side ? pe.idx : best_i));
+                const int depth = f.c_depth[c];
+#pragma unroll 1                                             /* (a handful of trips; unrolled it costs the walk registers) */
+                for (int i = lo + q; i < hi; i += G) n += (int)col[(size_t)i * stride] <= depth ? 1 : 0;
+                len = hi - lo;
+            }
+            n += __builtin_amdgcn_update_dpp(0, n, 0xB1, 0xf, 0xf, false);          /* quad_perm [1,0,3,2] */
+            n += __builtin_amdgcn_update_dpp(0, n, 0x4E, 0xf, 0xf, false);          /* quad_perm [2,3,0,1] */
+            if (c < nc && q == 0) {
+                f.c_tr[ts] = (uint32_t)len;
+                f.c_cnt[ts] = (uint32_t)n;
+            }
+        } else if (spans) {
             const int ntask = nc * ndir;
             if (lane < ntask) {
                 const int c = lane / ndir, d = lane - c * ndir;
@@ -813,7 +855,7 @@ DEV bool fused_body(const BatchDev &b, uint32_t psm, unsigned char *lds_raw, uin
             items = (int)acc;
             wave_lds_sync();
         }
-        if (!(b.debug & 1) && !zm_clusters)
+        if (!(b.debug & 1) && !zm_clusters && !no_cross)
         for (int base = 0; base < items; base += 64) {
             const int e = base + lane;
             if (e < items) {

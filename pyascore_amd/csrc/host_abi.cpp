@@ -2,6 +2,7 @@
  * strings, retained records, ambiguity. */
 #include "host_internal.h"
 #include "../../include/pyascore_debug.h"
+#include "span_guard.h"
 
 extern "C" {
 
@@ -463,6 +464,48 @@ int pya_debug_table_sizes(const pya_handle *h, uint64_t out[4]) {
     out[2] = h->cfg_uploads;
     out[3] = (uint64_t)(uintptr_t)h->d_lut.p;
     return PYA_OK;
+}
+
+/* The fused body's decision for one PSM, restated (span_guard.h; fused_core.hip.h: residues, presorted, wide, no_cross): the
+ * residue states as the kernel builds them -- table mass, + mod_mass, the fixed modifications added to both in list order,
+ * all in float32 -- and the same guard functions. */
+int pya_debug_span_guard(const pya_handle *h, const char *peptide, uint64_t len, const uint32_t *aux_pos, const float *aux_mass,
+                         uint64_t n_aux, double out[3]) {
+    if (!h || !peptide || len < 1 || len > 64 || (n_aux && (!aux_pos || !aux_mass))) return PYA_ERR_ARG;
+    const int L = (int)len;
+    const bool allow_n = h->mod_group.find('n') != std::string::npos, allow_c = h->mod_group.find('c') != std::string::npos;
+    float m0[64], m1[64];
+    bool modifiable[64];
+    for (int r = 0; r < L; r++) {
+        const char up = peptide[r];
+        if (up < 'A' || up > 'Z') return PYA_ERR_ARG;
+        m0[r] = std_residue_mass(up);
+        m1[r] = m0[r] + h->mod_mass;
+        modifiable[r] = h->mod_group.find(up) != std::string::npos || (allow_n && r == 0) || (allow_c && r == L - 1);
+    }
+    for (uint64_t j = 0; j < n_aux; j++) {
+        const uint64_t idx = aux_pos[j] > 0 ? aux_pos[j] - 1 : 0;
+        if (idx >= len) return PYA_ERR_ARG;
+        m0[idx] += aux_mass[j];
+        m1[idx] += aux_mass[j];
+    }
+    const float wide_min = 2.f * h->mz_error + 0.02f;
+    bool pre = true;                                         /* presorted and wide */
+    float heaviest = 0.f;
+    for (int r = 0; r < L; r++) {
+        pre = pre && m0[r] > 0.f && m1[r] > 0.f && m0[r] > wide_min && m1[r] > wide_min;
+        const float top = m0[r] > m1[r] ? m0[r] : m1[r];
+        heaviest = top > heaviest ? top : heaviest;
+    }
+    const SpanGuard g = span_guard_make(h->mz_error, h->mod_mass, L, heaviest);
+    bool ok = pre && g.ok;
+    for (int r = 0; r < L; r++) ok = ok && !span_guard_residue_fails(g, m0[r], m1[r], modifiable[r]);
+    if (out) {
+        out[0] = g.E;
+        out[1] = g.d_min;
+        out[2] = g.d_max;
+    }
+    return ok ? 1 : 0;
 }
 
 int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]) {

@@ -99,7 +99,7 @@ int one_run(pya_handle *h, bool keep, uint32_t max_k) {
     shared_tables(h, d);
     d.max_k = max_k;
     d.keep = keep ? 1u : 0u;
-    d.debug = h->kn.debug & (0xffffu | 0x08000000u);        /* (0x08000000: no split walk, fused_core.hip.h) */
+    d.debug = h->kn.debug & (0xffffu | 0x08000000u | 0x04000000u);   /* (no split walk, no span count: fused_core.hip.h) */
     /* caps of this one PSM (the rules of the plan's buckets, for a bucket of one) */
     const uint32_t L = m.L, z = (uint32_t)m.max_charge, k = (uint32_t)m.n_of_mod, ns = m.n_sites, N = m.n_sig;
     Bucket bk;
