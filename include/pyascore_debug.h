@@ -57,6 +57,14 @@ int pya_debug_table_sizes(const pya_handle *h, uint64_t out[4]);
 int pya_debug_span_guard(const pya_handle *h, const char *peptide, uint64_t len, const uint32_t *aux_pos, const float *aux_mass,
                          uint64_t n_aux, double out[3]);
 
+/* The composite keys the common-case binning kernels rank the peaks of a spectrum by (csrc/bin_key.h: a float32 with the window
+ * in its exponent and 23 bits of intensity in its mantissa), computed on the host with that header's own operations:
+ * keys[i] for intensity[i] in window[i] (< 64), the key base taken from the largest intensity of the array as a spectrum's most
+ * intense peak gives it (*key_base, may be NULL).  PYA_ERR_ARG: n == 0, a NULL array, a window of 64 or more, an intensity that
+ * is negative, infinite or NaN (no spectrum with such a peak takes the fast path).  Needs no handle and no device.  The tests
+ * place intensities a chosen number of key steps apart with it.  No reference counterpart. */
+int pya_debug_bin_keys(const double *intensity, const uint32_t *window, uint64_t n, uint32_t *keys, uint32_t *key_base);
+
 /* Plans the last pya_score_batch / pya_score_batch_shared / pya_score_batch_typed call on the handle was cut into (1: one
  * plan, not pipelined; 0: no call yet).  The tests read from it that a budget cuts a float32 batch into no more chunks than
  * the same batch widened.  No reference counterpart. */

@@ -334,6 +334,7 @@ SYMBOLS = {
     "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
     "pya_debug_table_sizes": (C.c_int, [_vp, _vp]),           # (test-only)
     "pya_debug_span_guard": (C.c_int, [_vp, C.c_char_p, C.c_uint64, _vp, _vp, C.c_uint64, _vp]),   # (test-only)
+    "pya_debug_bin_keys": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),             # (test-only)
     "pya_debug_last_probs_launch": (C.c_int, [_vp, _vp, _vp]),        # (test-only)
     "pya_debug_last_ranked_launch": (C.c_int, [_vp, _vp, _vp]),       # (test-only)
     "pya_debug_last_rollup_launch": (C.c_int, [_vp, _vp, _vp]),       # (test-only)

@@ -3,6 +3,7 @@
 #ifndef PYA_BIN_CORE_H
 #define PYA_BIN_CORE_H
 #include "device_common.hip.h"
+#include "bin_key.h"
 
 
 /* ---------------------------------------------------------------------------------------
@@ -172,8 +173,24 @@ DEV void run_exact_ranks(const R &r, int len, uint8_t *rank_out, int ntop) {
 #ifndef BIN_BLOCK
 #define BIN_BLOCK 6
 #endif
-#define PYA_BIN_FAST_WINDOWS 64    /* window ids the composite key has room for */
-#define PYA_BIN_KEY_BITS 25        /* intensity bits of the composite key: 5 exponent + 20 mantissa bits below the largest */
+/* (the composite key, its window field and PYA_BIN_FAST_WINDOWS / PYA_BIN_KEY_BITS: bin_key.h) */
+
+/* The rank count of the ranking sweeps (bin_fast below, bin_select.hip.h): acc += 1.0 for each of the two mates `o` whose key
+ * is above `me` (both lanes of me2 hold it), 0.0 otherwise -- a clamped float difference (bin_key.h says why it is exactly
+ * 0 or 1) and a float add, two packed instructions per two mates.  Counts stay exact far beyond any window length (2^24).
+ * Written as instructions: the packed form was measured against v_sub_f32 ... clamp + v_add_f32 per mate
+ * (profiles/bin_float_keys: 4.1 against 4.3 cycles per mate), and the vectoriser is not to re-decide it. */
+typedef float bin_f2 __attribute__((ext_vector_type(2)));
+DEV void bin_count2(bin_f2 &acc, const bin_f2 o, const bin_f2 me2) {
+    bin_f2 d;
+    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1] clamp" : "=v"(d) : "v"(o), "v"(me2));
+    asm("v_pk_add_f32 %0, %0, %1" : "+v"(acc) : "v"(d));
+}
+/* the count of a chunk from its two accumulators: whole numbers below 2^24, so every sum is exact */
+DEV uint32_t bin_count_total(bin_f2 c0, const bin_f2 c1) {
+    asm("v_pk_add_f32 %0, %0, %1" : "+v"(c0) : "v"(c1));
+    return (uint32_t)(c0.x + c0.y);
+}
 
 /* whole-wave DPP shifts (GFX9): lane i takes the value of lane i - 1 / i + 1; lane 0 / 63 take `edge`.  One
  * vector move where __shfl_up / __shfl_down are an LDS permute with its address arithmetic.
@@ -214,7 +231,8 @@ DEV double lane_next_f64_or_zero(double x) {
 }
 
 /* The common case.  LDS (PYA_BIN_FAST_BYTES):
- *   ckey u32[2 cap]  one composite key per peak, (63 - window) << 25 | intensity key, then zeros for the longest window
+ *   ckey u32[2 cap]  one composite key per peak (bin_key.h: window in the exponent, intensity key in the mantissa of a
+ *                    float32), then zeros for the longest window
  *   mzf  f32[cap]    float m/z per peak; the retained m/z are compacted into it in place
  *   rank u8 [cap]    ranks of the retained peaks (output)
  *   wtab u16[65 + 64] last peak of every window (and a slot for "the window before the first"), first peak of every window
@@ -224,10 +242,10 @@ DEV double lane_next_f64_or_zero(double x) {
  * longest run of the spectrum has peaks -- the same trip count for every lane, no per-lane bounds: what follows a run
  * in LDS belongs to later windows (or is the zero padding), and the window field makes all of that compare below
  * every peak of this run.  The intensity key is the high word of the float64 intensity (sign 0, order-preserving)
- * minus a base that leaves room for 2^32 of dynamic range below the spectrum's most intense peak; "more intense" is
- * then the sign of a 32-bit difference: subtract, shift, add -- three instructions of the cheap class per mate
- * (profiles/r03_valu_ceiling.md) where a float64 compare with its masks took four of the expensive one.
- * Keys that are equal (intensities that agree in 20 mantissa bits, or lie 2^32 below the maximum) make the counts of a
+ * minus a base that leaves room for 2^32 of dynamic range below the spectrum's most intense peak, less its two lowest bits;
+ * "more intense" is then a float difference of two keys clamped to [0, 1] (bin_count2 above) where a float64 compare with
+ * its masks took four instructions of the expensive class.
+ * Keys that are equal (intensities that agree in 18 mantissa bits, or lie 2^32 below the maximum) make the counts of a
  * window fall short of len (len - 1) / 2, which the deficit notices; only for a peak that ranks inside the top n_top
  * does it matter: those are then ordered by their whole intensities, and if these are equal too the spectrum is handed
  * over (std::nth_element decides between equal intensities).
@@ -330,7 +348,6 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
         return (uint32_t)w;
     };
     constexpr uint32_t U = BIN_BLOCK;
-    constexpr uint32_t KMAX = (1u << PYA_BIN_KEY_BITS) - 1u;
     w_first[lane] = 0xffffu;                                  /* (no peak) */
     /* only the high word of an intensity is needed here (the keys; sign, infinity and NaN show in it too) */
     uint32_t maxhw = 0;
@@ -373,7 +390,7 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
                 m = hw[u] > m ? hw[u] : m;
             }
             m = wave_max_u32(m);
-            keybase = m > KMAX ? m - KMAX : 0u;
+            keybase = bin_key_base(m);
         }
 #pragma unroll
         for (uint32_t u = 0; u < U; u++) {
@@ -390,9 +407,8 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
                 const uint32_t w = window_of(x);
                 const uint32_t pw = lane_prev_u32(w, carry_w);
                 carry_w = (uint32_t)__builtin_amdgcn_readlane((int)w, 63);    /* (ends as the window of the last peak) */
-                const uint32_t k = (hw[u] > keybase ? hw[u] : keybase) - keybase;
                 if (in) {
-                    ckey[i] = ((63u - w) << PYA_BIN_KEY_BITS) | k;
+                    ckey[i] = bin_key_bits(hw[u], keybase, w);
                     s_mzf[i] = (float)x;
                     if (pw != w) {                                /* a window starts here, the one before has ended */
                         w_last[pw] = (uint16_t)(i - 1u);
@@ -434,22 +450,30 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
         const bool in = i < P;
         const uint32_t ic = in ? i : P - 1u;                 /* (past the end: the last peak again, left out below) */
         const uint32_t me = ckey[ic];
-        const uint32_t lo = (uint32_t)w_first[63u - (me >> PYA_BIN_KEY_BITS)];
+        const uint32_t lo = (uint32_t)w_first[bin_key_window(me)];
         const float mzf = s_mzf[ic];
         const uint32_t *src = ckey + lo;
-        uint32_t c0 = 0, c1 = 0;
-        const uint32_t tc = per_chunk ? (((uint32_t)__builtin_amdgcn_readfirstlane((int)cmax[base >> 6]) + 3u) & ~3u) : trips;
-        if (!(b.debug & 32))
-#pragma unroll 2
-        for (uint32_t t = 0; t < tc; t += 4) {                /* (trips is a multiple of 8, a chunk's own count of 4) */
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q += 2) {
-                const uint32_t o0 = src[t + q], o1 = src[t + q + 1];
-                c0 += (me - o0) >> 31;                       /* keys are below 2^31: the sign says "more intense" */
-                c1 += (me - o1) >> 31;
-            }
+        const bin_f2 me2 = {__uint_as_float(me), __uint_as_float(me)};
+        bin_f2 c0 = {0.f, 0.f}, c1 = {0.f, 0.f};
+        const uint32_t tc = (b.debug & 32) ? 0u : per_chunk ? (((uint32_t)__builtin_amdgcn_readfirstlane((int)cmax[base >> 6]) + 3u) & ~3u) : trips;
+        /* four mates a step, two steps a trip (unrolled by hand: the compiler unrolls no loop around inline asm); tc is
+         * a multiple of 4, so an odd step goes first */
+        auto step4 = [&](uint32_t t) {
+            const bin_f2 o0 = {__uint_as_float(src[t]), __uint_as_float(src[t + 1])};
+            const bin_f2 o1 = {__uint_as_float(src[t + 2]), __uint_as_float(src[t + 3])};
+            bin_count2(c0, o0, me2);
+            bin_count2(c1, o1, me2);
+        };
+        uint32_t t = 0;
+        if (tc & 4u) {
+            step4(0);
+            t = 4;
         }
-        const uint32_t cnt = c0 + c1;
+        for (; t < tc; t += 8) {
+            step4(t);
+            step4(t + 4);
+        }
+        const uint32_t cnt = bin_count_total(c0, c1);
         deficit += in ? (int)cnt - (int)(i - lo) : 0;        /* 0 over a window whose keys all differ */
         const bool keep = in && cnt < (uint32_t)ntop;
         const uint64_t m = __ballot(keep);
@@ -477,7 +501,7 @@ DEV int bin_fast(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t c
             const uint32_t i = base + (uint32_t)lane;
             const bool in = i < P;
             const uint32_t me = in ? ckey[i] : 0u;
-            const uint32_t w = 63u - (me >> PYA_BIN_KEY_BITS);
+            const uint32_t w = in ? bin_key_window(me) : 0u;
             const uint32_t lo = in ? (uint32_t)w_first[w] : 0u;
             const uint32_t *src = ckey + lo;
             uint32_t cnt = 0, eq = 0;

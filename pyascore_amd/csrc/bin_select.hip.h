@@ -5,7 +5,7 @@
  * per raw peak: right for the ~17 peaks per window of a sparse spectrum (cfg2: 323 peaks), 20 x the time per peak at 4 000
  * peaks (214 per window; r06 bench legs dense1500 / dense4000).  Here:
  *   pass 0  order / sign / finiteness checks and the largest intensity (the key base), as bin_fast makes them;
- *   pass 1  a histogram per window over the top 6 bits of the 25-bit intensity key (half an octave per bucket): LDS atomics,
+ *   pass 1  a histogram per window over the top 6 bits of the 23-bit intensity key (half an octave per bucket): LDS atomics,
  *           64 windows x 64 buckets of 16 bits;
  *   thresholds  per window the highest bucket b with  #{peaks of the window in buckets >= b} >= n_top  (0 when the window has
  *           fewer peaks): every peak of the window's top n_top lies in a bucket >= b, and so does every peak MORE INTENSE
@@ -94,8 +94,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
         return (uint32_t)w;
     };
     constexpr uint32_t U = BIN_BLOCK;
-    constexpr uint32_t KMAX = (1u << PYA_BIN_KEY_BITS) - 1u;
-    constexpr uint32_t DSHIFT = PYA_BIN_KEY_BITS - 6;
+    constexpr uint32_t DSHIFT = PYA_BIN_KEY_BITS - 6;        /* (the six bits the 25-bit keys gave: (k25 >> 2) >> 17 = k25 >> 19) */
 
     /* ---- pass 0: checks and the key base.  Blocks of 64 U peaks, all loads of a block in flight together ---- */
     for (uint32_t i = (uint32_t)lane; i < PYA_BIN_SEL_HIST_BYTES / 4; i += 64) hist[i] = 0u;
@@ -129,7 +128,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
     }
     if (__any(bad) || n_bins > PYA_BIN_FAST_WINDOWS || (b.debug & 128)) return PYA_BIN_REDO;
     maxhw = wave_max_u32(maxhw);
-    const uint32_t keybase = maxhw > KMAX ? maxhw - KMAX : 0u;
+    const uint32_t keybase = bin_key_base(maxhw);
     wave_lds_sync();
     STAMP_T(b, 2, -1);
 
@@ -150,7 +149,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
             const uint32_t i = base + u * 64 + (uint32_t)lane;
             if (base + u * 64 < P) {
                 const uint32_t w = window_of(v[u]);
-                const uint32_t k = (hw[u] > keybase ? hw[u] : keybase) - keybase;
+                const uint32_t k = bin_key_intensity(hw[u], keybase);
                 const uint32_t d = k >> DSHIFT;
                 if (i < P) atomicAdd(&hist[w * 32u + (d >> 1)], 1u << ((d & 1u) * 16u));
             }
@@ -199,7 +198,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
                 const uint32_t i = base + u * 64 + (uint32_t)lane;
                 if (base + u * 64 < P) {
                     const uint32_t w = window_of(v[u]);
-                    const uint32_t k = (hw[u] > keybase ? hw[u] : keybase) - keybase;
+                    const uint32_t k = bin_key_intensity(hw[u], keybase);
                     const uint32_t sub = (k >> DSHIFT2) & 63u;
                     if (i < P && (k >> DSHIFT) == (uint32_t)thr[w]) atomicAdd(&hist[w * 32u + (sub >> 1)], 1u << ((sub & 1u) * 16u));
                 }
@@ -238,13 +237,13 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
             const uint32_t i = base + u * 64 + (uint32_t)lane;
             if (base + u * 64 < P) {
                 const uint32_t w = window_of(v[u]);
-                const uint32_t k = (hw[u] > keybase ? hw[u] : keybase) - keybase;
+                const uint32_t k = bin_key_intensity(hw[u], keybase);
                 /* the top 12 key bits against (threshold bucket, threshold sub-bucket): one compare */
                 const bool sv = i < P && (k >> (DSHIFT - 6)) >= (((uint32_t)thr[w] << 6) | (uint32_t)thr2[w]);
                 const uint64_t m = __ballot(sv);
                 const uint32_t pos = S + lanes_below(m);
                 if (sv && pos < scap) {
-                    ckey[pos] = ((63u - w) << PYA_BIN_KEY_BITS) | k;
+                    ckey[pos] = bin_key_bits(hw[u], keybase, w);
                     s_mzf[pos] = (float)v[u];
                     s_idx[pos] = (uint16_t)i;
                 }
@@ -261,7 +260,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
     for (uint32_t base = 0; base < S; base += 64) {
         const uint32_t i = base + (uint32_t)lane;
         const bool in = i < S;
-        const uint32_t w = 63u - (ckey[in ? i : S - 1u] >> PYA_BIN_KEY_BITS);
+        const uint32_t w = bin_key_window(ckey[in ? i : S - 1u]);
         const uint32_t pw = lane_prev_u32(w, carry_w);
         carry_w = (uint32_t)__builtin_amdgcn_readlane((int)w, 63);
         if (in && pw != w) {
@@ -292,21 +291,30 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
         const bool in = i < S;
         const uint32_t ic = in ? i : S - 1u;
         const uint32_t me = ckey[ic];
-        const uint32_t lo = (uint32_t)w_first[63u - (me >> PYA_BIN_KEY_BITS)];
+        const uint32_t lo = (uint32_t)w_first[bin_key_window(me)];
         const float mzf = s_mzf[ic];
         const uint32_t *src = ckey + lo;
-        uint32_t c0 = 0, c1 = 0;
+        const bin_f2 me2 = {__uint_as_float(me), __uint_as_float(me)};
+        bin_f2 c0 = {0.f, 0.f}, c1 = {0.f, 0.f};
         const uint32_t tc = per_chunk ? (((uint32_t)__builtin_amdgcn_readfirstlane((int)cmax[base >> 6]) + 3u) & ~3u) : trips;
-#pragma unroll 2
-        for (uint32_t t = 0; t < tc; t += 4) {
-#pragma unroll
-            for (uint32_t q = 0; q < 4; q += 2) {
-                const uint32_t o0 = src[t + q], o1 = src[t + q + 1];
-                c0 += (me - o0) >> 31;
-                c1 += (me - o1) >> 31;
-            }
+        /* four mates a step, two steps a trip (unrolled by hand: the compiler unrolls no loop around inline asm); tc is
+         * a multiple of 4, so an odd step goes first */
+        auto step4 = [&](uint32_t t) {
+            const bin_f2 o0 = {__uint_as_float(src[t]), __uint_as_float(src[t + 1])};
+            const bin_f2 o1 = {__uint_as_float(src[t + 2]), __uint_as_float(src[t + 3])};
+            bin_count2(c0, o0, me2);
+            bin_count2(c1, o1, me2);
+        };
+        uint32_t t = 0;
+        if (tc & 4u) {
+            step4(0);
+            t = 4;
         }
-        const uint32_t cnt = c0 + c1;
+        for (; t < tc; t += 8) {
+            step4(t);
+            step4(t + 4);
+        }
+        const uint32_t cnt = bin_count_total(c0, c1);
         deficit += in ? (int)cnt - (int)(i - lo) : 0;
         const bool keep = in && cnt < (uint32_t)ntop;
         const uint64_t m = __ballot(keep);
@@ -326,7 +334,7 @@ DEV int bin_select(const BatchDev &b, uint32_t psm, unsigned char *lds, uint32_t
             const uint32_t i = base + (uint32_t)lane;
             const bool in = i < S;
             const uint32_t me = in ? ckey[i] : 0u;
-            const uint32_t w = 63u - (me >> PYA_BIN_KEY_BITS);
+            const uint32_t w = in ? bin_key_window(me) : 0u;
             const uint32_t lo = in ? (uint32_t)w_first[w] : 0u;
             const uint32_t *src = ckey + lo;
             uint32_t cnt = 0, eq = 0;

@@ -3,6 +3,7 @@
 #include "host_internal.h"
 #include "../../include/pyascore_debug.h"
 #include "span_guard.h"
+#include "bin_key.h"
 
 extern "C" {
 
@@ -506,6 +507,28 @@ int pya_debug_span_guard(const pya_handle *h, const char *peptide, uint64_t len,
         out[2] = g.d_max;
     }
     return ok ? 1 : 0;
+}
+
+/* The composite keys of the common-case binning bodies (bin_key.h), by the header's own functions: the key base from the
+ * largest high word of the array, as a spectrum's most intense peak gives it. */
+int pya_debug_bin_keys(const double *intensity, const uint32_t *window, uint64_t n, uint32_t *keys, uint32_t *key_base) {
+    if (n < 1 || !intensity || !window || !keys) return PYA_ERR_ARG;
+    uint32_t maxhw = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t bits;
+        std::memcpy(&bits, &intensity[i], 8);
+        const uint32_t hw = (uint32_t)(bits >> 32);
+        if (hw >= 0x7ff00000u || window[i] >= PYA_BIN_FAST_WINDOWS) return PYA_ERR_ARG;   /* negative, infinite, NaN: no fast path */
+        maxhw = hw > maxhw ? hw : maxhw;
+    }
+    const uint32_t base = bin_key_base(maxhw);
+    for (uint64_t i = 0; i < n; i++) {
+        uint64_t bits;
+        std::memcpy(&bits, &intensity[i], 8);
+        keys[i] = bin_key_bits((uint32_t)(bits >> 32), base, window[i]);
+    }
+    if (key_base) *key_base = base;
+    return PYA_OK;
 }
 
 int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]) {

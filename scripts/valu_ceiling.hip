@@ -227,6 +227,15 @@
 #define F_LSHR_B64(k) "v_lshrrev_b64 %[r" #k "], %[ci], %[r" #k "]\n"
 #define F_MAD_U64(k) "v_mad_u64_u32 %[r" #k "], vcc, %[ci], %[ci], %[r" #k "]\n"
 #define F_PK_ADD_F32(k) "v_pk_add_f32 %[r" #k "], %[r" #k "], %[c]\n"
+/* the binning kernel's rank count per mate (bin_core.hip.h): float keys with the window in the exponent, "more intense" as a
+ * clamped difference.  bk_pk_sub_clamp / bk_sub_f32_e64_clamp: the two instructions alone (the second one is a VOP2 opcode in
+ * VOP3 encoding); bk_form_c (two packed instructions per two mates), bk_form_d (two per mate) and bk_form_int (the integer
+ * count they replace: subtract, shift, add) with the dependence of the count on the difference */
+#define F_BK_PK_SUB_CLAMP(k) "v_pk_add_f32 %[r" #k "], %[r" #k "], %[c] neg_lo:[0,1] neg_hi:[0,1] clamp\n"
+#define F_BK_SUB_F32_E64_CLAMP(k) "v_sub_f32_e64 %[r" #k "], %[r" #k "], %[c] clamp\n"
+#define F_BK_FORM_C(k) "v_pk_add_f32 %[r" #k "], %[r" #k "], %[c] neg_lo:[0,1] neg_hi:[0,1] clamp\nv_pk_add_f32 %[r" #k "], %[r" #k "], %[c]\n"
+#define F_BK_FORM_D(k) "v_sub_f32_e64 %[q" #k "], %[c], %[r" #k "] clamp\nv_add_f32 %[r" #k "], %[r" #k "], %[q" #k "]\n"
+#define F_BK_FORM_INT(k) "v_sub_u32 %[q" #k "], %[c], %[r" #k "]\nv_lshrrev_b32 %[q" #k "], 31, %[q" #k "]\nv_add_u32 %[r" #k "], %[r" #k "], %[q" #k "]\n"
 #define F_PK_MOV(k) "v_pk_mov_b32 %[r" #k "], %[r" #k "], %[c]\n"
 /* LDS (address in ci; conflict-free: lane * 4 / * 8 / * 16 bytes) */
 #define F_DS_READ_B32(k) "ds_read_b32 %[r" #k "], %[ci]\n"
@@ -319,6 +328,11 @@ K3(lshl_b64, uint64_t, F_LSHL_B64, NOW)
 K3(lshr_b64, uint64_t, F_LSHR_B64, NOW)
 K3(mad_u64_u32, uint64_t, F_MAD_U64, NOW)
 K3(pk_add_f32, uint64_t, F_PK_ADD_F32, NOW)
+K3(bk_pk_sub_clamp, uint64_t, F_BK_PK_SUB_CLAMP, NOW)
+K3(bk_sub_f32_e64_clamp, float, F_BK_SUB_F32_E64_CLAMP, NOW)
+K3(bk_form_c, uint64_t, F_BK_FORM_C, NOW)
+K3(bk_form_d, float, F_BK_FORM_D, NOW)
+K3(bk_form_int, uint32_t, F_BK_FORM_INT, NOW)
 K3(ds_read_b32, uint32_t, F_DS_READ_B32, LGKM)
 K3(ds_read_b64, uint64_t, F_DS_READ_B64, LGKM)
 K3(ds_add_u32, uint32_t, F_DS_ADD_U32, LGKM)
@@ -468,6 +482,7 @@ static const Entry kEntries[] = {
     E3(readlane, 0, 1) E3(readfirstlane, 0, 1) E3(dpp_mov, 0, 1) E3(dpp_add, 0, 1) E3(mbcnt, 0, 1) E3(bcnt, 0, 1) E3(ffbl, 0, 1)
     E3(add_f64, 3, 1) E3(mul_f64, 3, 1) E3(fma_f64, 3, 1) E3(cmp_f64, 3, 1) E3(floor_f64, 3, 1) E3(lshl_b64, 2, 1)
     E3(lshr_b64, 2, 1) E3(mad_u64_u32, 2, 1) E3(pk_add_f32, 2, 1)
+    E3(bk_pk_sub_clamp, 2, 1) E3(bk_sub_f32_e64_clamp, 1, 1) E3(bk_form_c, 2, 2) E3(bk_form_d, 1, 2) E3(bk_form_int, 0, 3)
     E3(ds_read_b32, 0, 1) E3(ds_read_b64, 2, 1) E3(ds_add_u32, 0, 1) E3(ds_add_rtn_u32, 0, 1) E3(ds_write_b8, 0, 1)
     E3(ds_write_b32, 0, 1) E3(ds_bpermute, 0, 1) E3(ds_swizzle, 0, 1) E3(s_add_x4, 0, 4) E3(s_mix_x4, 0, 4)
     {"cvt_f64_f32+cvt_f32_f64", "0", (const void *)k_cvt_f64_f32_S0, 1, 1},
