@@ -489,6 +489,36 @@ typedef struct pya_peptidoform {   /* 48 bytes, three 16-byte stores; records co
  * place in the list is at or above cap writes nothing; the result for a smaller cap is the byte prefix of the result for a
  * larger one.  csrc/pform_quant.hip; the library is built without fast-math. */
 
+/* Channel correction: what stands between the raw reporter intensities of a labelled experiment and sums that are reported --
+ * the isotope impurities of the reagent lot taken out per spectrum, and the columns brought to equal totals because the
+ * channels were not loaded with equal amounts.  Both act on the channel matrix values[n_rows * n_channels] (doubles, row-major,
+ * n_channels 1 .. PYA_QUANT_MAX_CHANNELS: what pya_marker_values writes and pya_plan_site_quant reads) BEFORE the tables sum it;
+ * afterwards they cannot be done, because a sum of clamped values is not the clamp of a sum, the quanta are truncated per reading
+ * and a "no reading" must stay one.  The reference has no counterpart.  Usable value and quantum q(v) are pya_site_quant's
+ * above, word for word (csrc/quant_rule.hip.h is the one place the stages take them from).  With C = n_channels:
+ * APPLY (pya_channel_correct), with a matrix m[C * C] (row-major: the inverse of the lot's spill matrix S, observed = S true;
+ * the caller inverts) or a factor f[C] or both.  For every row v[0 .. C) and channel c:
+ *   u[j]   = usable(v[j]) ? v[j] : +0.0
+ *   v[c] not usable:  out[c] = v[c], bits copied -- a missing reading stays the missing reading it was, a zero stays a zero;
+ *   otherwise         x = +0.0; for j = 0 .. C - 1 ascending: x = x + m[c * C + j] * u[j]    (with a matrix: one rounded double
+ *                                                     multiplication and one rounded double addition per term, never fused)
+ *                     x = v[c]                                                               (without a matrix)
+ *                     x = x * f[c]                                                           (with a factor: one multiplication)
+ *                     out[c] = (x == x && x > 0.0) ? x : +0.0
+ * A corrected reading that is not positive is clamped to +0.0, which the quant stages take as "no reading" and the caller can
+ * tell from a NaN; so is the NaN of inf * 0.  THE STAGE HAS ONE DEFINED ORDER OF ARITHMETIC, so its bytes are those of a host
+ * restatement with the same doubles: no matrix instruction (v_mfma_f64_* fuses and reorders), no butterfly sum, no atomics.
+ * SUMS (pya_channel_sums): one table row, pya_site_quant cell[C] -- per channel, over the selected rows (select[row] != 0, or
+ * all) with a usable value in the channel: sum of q, n their number, n_saturated the saturated ones.  The result is ADDED into
+ * cell; the empty row is zero bytes, so it accumulates over calls and files and rows merge by adding.  Integer sums: the bytes
+ * depend on no order.
+ * FACTORS (pya_channel_factors): M the largest sum of the C cells; f[c] = sum[c] == 0 ? 1.0 : (double)M / (double)sum[c], both
+ * conversions to nearest and one correctly rounded division.  Every column's total is brought to the largest one -- an
+ * order-free integer, and ratios between channels do not depend on the target.
+ * csrc/channel_correct.hip; the library is built without fast-math. */
+#define PYA_CHANNEL_NORMALIZE 1u   /* pya_channel_correct_host flags: equal column totals after the matrix pass */
+#define PYA_CHANNEL_TILE 128u      /* rows per workgroup of the apply kernel (the sizes a test of the stage wants to straddle) */
+
 /* Fragment mass-error profile.  The third reduction across PSMs, and the one that speaks about a SETTING rather than about a
  * localisation: per run (file, fraction, instrument -- a slot the caller names per PSM) the distribution of the m/z errors of
  * the matched fragments the scores counted, in Da and in ppm, resolved over bands of m/z.  The reference has no counterpart.
@@ -1294,6 +1324,38 @@ int pya_marker_spectra_host(pya_handle *h, const pya_typed_spectra *in, const in
  * n_targets, more than 2^32 - 2 spectra, a NULL array.  n_spectra == 0 is a call that writes nothing. */
 int pya_marker_values(pya_handle *h, const pya_marker *d_markers, uint64_t n_spectra, uint32_t n_targets, uint64_t channel_mask,
                       void *hip_stream, double *d_values);
+/* Applies a correction to the channel matrix d_values[n_rows * n_channels] (APPLY of the channel correction above;
+ * csrc/channel_correct.hip): d_matrix[n_channels * n_channels] (row-major) or NULL, d_factor[n_channels] or NULL, not both
+ * NULL; d_out[n_rows * n_channels] takes the result (all device memory, doubles, 8-byte aligned).  d_out == d_values, exactly
+ * in place, is allowed: a row is read whole by the lanes that write it before they write; any other overlap is the caller's
+ * error.  One launch on hip_stream, stream-ordered, no host wait, no allocation and no workspace; 64-bit index arithmetic; the
+ * inputs are only read and no write lies outside d_out[0 .. n_rows * n_channels).  PYA_ERR_ARG, with nothing launched:
+ * n_channels outside 1 .. PYA_QUANT_MAX_CHANNELS, d_matrix and d_factor both NULL, more than 2^32 - 2 rows, a NULL or not
+ * 8-byte aligned array.  n_rows == 0 is a call that writes nothing. */
+int pya_channel_correct(pya_handle *h, const double *d_values, uint64_t n_rows, uint32_t n_channels, const double *d_matrix,
+                        const double *d_factor, void *hip_stream, double *d_out);
+/* Adds the column sums of d_values[n_rows * n_channels] into the table row d_cell[n_channels] (SUMS of the channel correction
+ * above): d_select[n_rows], one byte per row (0: the row is left out), or NULL for all rows; scale_log2 as
+ * pya_site_quant_params has it.  The caller clears d_cell (hipMemsetAsync to 0) before the first call.  One launch,
+ * stream-ordered, no host wait, no allocation and no workspace; everything that reaches memory is a 64-bit integer atomic add
+ * to d_cell[0 .. n_channels).  PYA_ERR_ARG, with nothing launched: n_channels outside 1 .. PYA_QUANT_MAX_CHANNELS, scale_log2
+ * outside -64 .. 64, more than 2^32 - 2 rows, a NULL array that is needed, d_values or d_cell not 8-byte aligned.  n_rows == 0
+ * is a call that writes nothing. */
+int pya_channel_sums(pya_handle *h, const double *d_values, uint64_t n_rows, uint32_t n_channels, const uint8_t *d_select,
+                     int32_t scale_log2, void *hip_stream, pya_site_quant *d_cell);
+/* The loading factors d_factor[n_channels] of a table row d_cell[n_channels] (FACTORS of the channel correction above): one
+ * wavefront on hip_stream, so that a resident chain -- sums, factors, apply -- has no host wait.  d_cell is only read.
+ * PYA_ERR_ARG, with nothing launched: n_channels outside 1 .. PYA_QUANT_MAX_CHANNELS, a NULL or not 8-byte aligned array. */
+int pya_channel_factors(pya_handle *h, const pya_site_quant *d_cell, uint32_t n_channels, void *hip_stream, double *d_factor);
+/* The chain over HOST arrays: one upload (values, matrix and select where given), pya_channel_correct with the matrix if one is
+ * given, pya_channel_sums over the result into a cleared row, and with PYA_CHANNEL_NORMALIZE in flags pya_channel_factors and
+ * pya_channel_correct with the factor alone, in place; one download of out[n_rows * n_channels], cell[n_channels] (the sums
+ * BEFORE the factor; may be NULL without PYA_CHANNEL_NORMALIZE) and, with PYA_CHANNEL_NORMALIZE, factor[n_channels]; waits.
+ * With both steps the result is clamp(clamp(M u) f): two applications of the rule, not a third rule.  out == values is
+ * allowed.  PYA_ERR_ARG: what the three calls refuse, matrix NULL without PYA_CHANNEL_NORMALIZE, unknown flag bits. */
+int pya_channel_correct_host(pya_handle *h, const double *values, uint64_t n_rows, uint32_t n_channels, const double *matrix,
+                             const uint8_t *select, int32_t scale_log2, uint32_t flags, double *out, pya_site_quant *cell,
+                             double *factor);
 /* The device bytes pya_centroid_spectra needs as its workspace for n_spectra spectra of n_peaks points together: what
  * pya_deisotope_workspace_bytes gives (one keep bit per point in 64-bit words that no two spectra share, and the tile sums of
  * the offset scan; 8 bytes at the least).  Centroids are recomputed by the last pass, not stored. */

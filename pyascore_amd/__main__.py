@@ -29,7 +29,8 @@ the intensities of reporter and diagnostic ions in its spectrum, read before any
 intensities of the ``--marker_mz`` targets summed over the PSMs that localise the modification there) and ``--peptidoform_quant FILE``
 with ``--peptidoform_quant_threshold P``, ``--peptidoform_quant_scale E`` and ``--peptidoform_quant_complete`` (a line per peptidoform:
 the columns of ``--peptidoform_table``, then the same intensities summed over the PSMs that report the assignment; it needs
-``--marker_mz``) are the additions."""
+``--marker_mz``) and ``--channel_spill FILE`` and ``--channel_normalize`` (the reporter intensities corrected for the reagent lot's
+isotope impurities and brought to equal channel totals before either table sums them) are the additions."""
 import argparse
 import re
 import sys
@@ -225,6 +226,14 @@ def build_parser():
                    help="with --peptidoform_quant: readings are summed as integers in units of 2^-E (default 10; -64 .. 64)")
     p.add_argument("--peptidoform_quant_complete", action="store_true",
                    help="with --peptidoform_quant: only PSMs with a reading in every channel are summed")
+    p.add_argument("--channel_spill", type=str, default="", metavar="FILE",
+                   help="with --site_quant / --peptidoform_quant: correct the reporter intensities for the isotope impurities of the "
+                        "reagent lot before they are summed; FILE holds tab-separated lines from, to, fraction -- that fraction of "
+                        "channel from's reporter shows up in channel to (-1: in no channel) --, the channels numbered from 0 in "
+                        "--marker_mz order")
+    p.add_argument("--channel_normalize", action="store_true",
+                   help="with --site_quant / --peptidoform_quant: bring the channels to equal totals over all spectra (after "
+                        "--channel_spill) before they are summed")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -282,6 +291,27 @@ def peptidoform_quant_request(args):
     return req
 
 
+def channels_request(args):
+    """``--channel_spill`` / ``--channel_normalize`` as the dict ``batch_cli.localize(channels=...)`` takes, the spill file read and
+    inverted, checked; None without either option."""
+    spill, normalize = getattr(args, "channel_spill", ""), bool(getattr(args, "channel_normalize", False))
+    if not spill and not normalize:
+        return None
+    if not getattr(args, "site_quant", "") and not getattr(args, "peptidoform_quant", ""):
+        raise ValueError("--channel_spill / --channel_normalize correct what --site_quant and --peptidoform_quant sum: give one of them")
+    from .rollup import channel_matrix, read_channel_spill
+    n_ch = len([v for v in args.marker_mz.split(",") if v.strip()])
+    req = dict(normalize=normalize)
+    if spill:
+        try:
+            req["matrix"] = channel_matrix(read_channel_spill(spill, n_ch))
+        except OSError as e:
+            raise ValueError("--channel_spill: %s" % e) from None
+        except ValueError as e:
+            raise ValueError("--channel_spill %s" % e) from None
+    return req
+
+
 def markers_request(args):
     """The rule of ``--markers`` as the dict ``batch_cli.localize(markers=...)`` takes (the precursors come from the spectra),
     checked; None without the option (and without ``--site_quant`` / ``--peptidoform_quant``, which read the same targets): the
@@ -330,6 +360,7 @@ def validate_args(args):
     markers_request(args)
     site_quant_request(args)
     peptidoform_quant_request(args)
+    channels_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -415,7 +446,8 @@ def run(args, log=print):
                               deisotope=deisotope, decharge=decharge, strip=strip_request(args),
                               centroid=centroid_request(args), coverage=coverage_rows, markers=markers,
                               marker_rows=marker_rows, site_quant=site_quant, site_quant_rows=site_quant_rows,
-                              peptidoform_quant=pform_quant, peptidoform_quant_rows=pform_quant_rows)
+                              peptidoform_quant=pform_quant, peptidoform_quant_rows=pform_quant_rows,
+                              channels=channels_request(args))
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:

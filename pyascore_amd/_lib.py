@@ -25,6 +25,8 @@ PYA_FLAG_QUANT = 16384
 PYA_FLAG_PFORM_QUANT = 32768
 PYA_QUANT_COMPLETE_ONLY = 1
 PYA_QUANT_MAX_CHANNELS = 64
+PYA_CHANNEL_NORMALIZE = 1
+PYA_CHANNEL_TILE = 128       # rows per workgroup of csrc/channel_correct.hip
 PYA_COV_NONE, PYA_COV_SCORED = 0, 1
 PYA_MZC_MAX_PPM = 1000       # the largest knot of a pya_mz_calibration, in ppm
 PYA_MZP_BANDS, PYA_MZP_BINS = 8, 64
@@ -385,6 +387,10 @@ SYMBOLS = {
     "pya_last_batch_site_quant": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32]),
     "pya_plan_site_quant": (C.c_int, [_vp, C.POINTER(Results), _vp, _vp, _vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp, C.c_uint32, _vp, _vp, _vp]),
     "pya_marker_values": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp]),
+    "pya_channel_correct": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, _vp, _vp]),
+    "pya_channel_sums": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_int32, _vp, _vp]),
+    "pya_channel_factors": (C.c_int, [_vp, _vp, C.c_uint32, _vp, _vp]),
+    "pya_channel_correct_host": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp, C.c_int32, C.c_uint32, _vp, _vp, _vp]),
     "pya_set_peptidoform_quant": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_uint64, _vp]),
     "pya_last_batch_peptidoform_quant": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint32]),
     "pya_peptidoform_quant_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint32]),

@@ -384,6 +384,62 @@ def _marker_channels(name, req, params, records, spec_of):
     return dict(req, values=np.ascontiguousarray(marker_matrix(records)[:, fixed]), row=row)
 
 
+def _channels_request(name, req, markers=None):
+    """The ``channels=`` entry of ``score_batch(quant=...)`` / ``peptidoform_quant=`` checked, against ``values`` where the
+    request holds them already and against the fixed targets of ``markers`` (the ``markers=`` request) where they come from
+    there, so that a matrix of another shape is refused before any device work: None when there is none, else dict(matrix float64
+    [n_channels, n_channels] | None, normalize bool, select uint8 [n_rows] | None)"""
+    from .rollup import QUANT_MAX_CHANNELS, check_channel_matrix
+    if not isinstance(req, dict) or req.get("channels") is None:
+        return None
+    ch = req["channels"]
+    what = name + ": channels"
+    names = ("matrix", "normalize", "select")
+    if not isinstance(ch, dict):
+        raise ValueError(what + " takes a dict: " + ", ".join(names))
+    unknown = set(ch) - set(names)
+    if unknown:
+        raise ValueError(what + " takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+    normalize = ch.get("normalize", False)
+    if not isinstance(normalize, (bool, np.bool_)):
+        raise ValueError(what + ": normalize = %r is not a boolean" % (normalize,))
+    matrix, select = ch.get("matrix"), ch.get("select")
+    if matrix is None and not normalize:
+        raise ValueError(what + " names neither a matrix nor normalize=True")
+    if select is not None and not normalize:
+        raise ValueError(what + ": select names the rows the loading factors are taken from; it needs normalize=True")
+    shape = None
+    if req.get("values") is not None:
+        try:
+            shape = np.shape(req["values"])
+        except (TypeError, ValueError):
+            shape = None
+        if shape is None or len(shape) != 2:
+            raise ValueError(name + ": values is a matrix, one row per spectrum and one column per channel")
+    if matrix is not None:
+        try:
+            matrix = np.ascontiguousarray(matrix, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(what + ": matrix is a square matrix of numbers") from None
+        if matrix.ndim != 2 or matrix.shape[0] != matrix.shape[1] or not 1 <= matrix.shape[0] <= QUANT_MAX_CHANNELS:
+            raise ValueError(what + ": matrix is a square matrix of 1 .. %d channels" % QUANT_MAX_CHANNELS)
+        if shape is not None:
+            matrix = check_channel_matrix(matrix, shape[1], what)
+        elif isinstance(markers, dict):
+            try:
+                n_fixed = len(tuple(markers.get("mz", ())))
+            except TypeError:
+                n_fixed = 0                                  # (markers= itself is refused where it is checked)
+            if n_fixed:
+                matrix = check_channel_matrix(matrix, n_fixed, what)
+    if select is not None:
+        select = np.asarray(select)
+        if select.ndim != 1 or (shape is not None and select.size != shape[0]) or (select.size and select.dtype.kind not in "biu"):
+            raise ValueError(what + ": select is one boolean per row of values")
+        select = np.ascontiguousarray(select != 0, np.uint8)
+    return dict(matrix=matrix, normalize=bool(normalize), select=select)
+
+
 def _quant_request(req, n_psm, have_rollup, name="quant"):
     """``score_batch(quant=...)`` checked -- under the name ``peptidoform_quant`` that option, whose companion is
     ``peptidoforms=`` --: dict(values float64 [n_rows, n_channels], row int32 | None, params, c_params), ``params`` the dict of
@@ -824,6 +880,19 @@ class PyAscore:
         into intensities), so the table does not depend on chunk cuts, route or order, and tables of several calls merge by
         adding (``merge_site_quant``); ``pyascore_amd.rollup.site_quant`` gives the same bytes on the host.
 
+        ``channels=dict(matrix=None, normalize=False, select=None)`` inside ``quant=`` (and, the same key, inside
+        ``peptidoform_quant=``) corrects the channel matrix before it is summed (the channel correction of
+        ``include/pyascore_hip.h``): ``matrix`` float64 ``[n_channels, n_channels]``, the inverse of the reagent lot's spill
+        matrix (``pyascore_amd.rollup.channel_matrix``), takes the isotope impurities out of every row; ``normalize=True`` then
+        brings the column totals -- over the rows ``select`` names, one boolean per row, None: all -- to the largest one.  The
+        matrix (given, or made from ``markers=``) goes through ``correct_channels`` first: ONE EXTRA ROUND TRIP OF THE MATRIX to
+        the device and back, before the batch call uploads it again (one for both options where they name the same matrix
+        and the same ``channels=``, one each otherwise).  Adds ``quant_channel_sums`` (``SITE_QUANT_DTYPE``, shape
+        ``[n_channels]``: the column sums behind the factors) and ``quant_channel_factors`` (float64 ``[n_channels]``, None
+        without ``normalize``) -- under ``peptidoform_quant_channel_...`` for that option; every other result is what the
+        call gives for ``values=`` the corrected matrix.  Unknown keys and a matrix of another shape are a ValueError before
+        anything is scored.
+
         ``peptidoform_quant=dict(values=, row=None, threshold=0.75, scale_log2=10, complete_only=False)`` -- beside
         ``peptidoforms=``, whose list it is row-aligned with; without it a ValueError -- adds ``peptidoform_quant_head``
         (``SITE_QUANT_HEAD_DTYPE``, shape ``[n_list]``), ``peptidoform_quant`` (``SITE_QUANT_DTYPE``, shape ``[n_list,
@@ -854,9 +923,12 @@ class PyAscore:
                         centroid=centroid, coverage=coverage, markers=markers, quant=quant,
                         peptidoform_quant=peptidoform_quant)
             rest.update(changed)
-            rest[done] = None
+            if done is not None:
+                rest[done] = None
             return self.score_batch(dict(batch, mz=spectra[0], intensity=spectra[1], peak_off=spectra[2]), **rest)
 
+        channel_reqs = {name: _channels_request(name, req, markers)
+                        for name, req in (("quant", quant), ("peptidoform_quant", peptidoform_quant))}
         if centroid is not None and centroid is not False:
             params, select = _centroid_request(centroid, _n_spectra(batch))
             return again("centroid", self.centroid_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), params, select))
@@ -869,6 +941,27 @@ class PyAscore:
                     changed[name] = _marker_channels(name, req, params, records, batch.get("spec_of"))
             res = again("markers", (batch["mz"], batch["intensity"], batch["peak_off"]), **changed)
             res["markers"], res["marker_spectra"] = records, spectra
+            return res
+        if any(ch is not None for ch in channel_reqs.values()):
+            # (behind markers=: the matrix is there by now; in front of everything that scores)
+            changed, extra, done = {}, {}, []
+            for name, req, have in (("quant", quant, rollup is not None), ("peptidoform_quant", peptidoform_quant, peptidoforms is not None)):
+                ch = channel_reqs[name]
+                if ch is None:
+                    continue
+                plain = {k: v for k, v in req.items() if k != "channels"}
+                checked = _quant_request(plain, int(batch["n_psm"]), have, name)
+                key = (checked["values"].shape, checked["values"].tobytes(), None if ch["matrix"] is None else ch["matrix"].tobytes(),
+                       ch["normalize"], None if ch["select"] is None else ch["select"].tobytes(), checked["params"]["scale_log2"])
+                # (both options over one matrix with one request, as beside markers=: one round trip serves both)
+                result = next((r for k, r in done if k == key), None)
+                if result is None:
+                    result = self.correct_channels(checked["values"], ch["matrix"], ch["normalize"], ch["select"], checked["params"]["scale_log2"])
+                    done.append((key, result))
+                changed[name] = dict(plain, values=result[0])
+                extra[name + "_channel_sums"], extra[name + "_channel_factors"] = result[1], result[2]
+            res = again(None, (batch["mz"], batch["intensity"], batch["peak_off"]), **changed)      # (no transform served: the same spectra)
+            res.update(extra)
             return res
         if strip is not None and strip is not False:
             params, prec_mz, prec_z = _strip_request(strip, self._mz_error, _n_spectra(batch))
@@ -1368,6 +1461,43 @@ class PyAscore:
                 self._raise(rc)
         spectra, over = _transform_result(c)
         return spectra + (report, over)
+
+    def correct_channels(self, values, matrix=None, normalize=False, select=None, scale_log2=10):
+        """A channel matrix corrected on the device (``pya_channel_correct_host``; the rule is the channel correction's in
+        include/pyascore_hip.h): ``values`` float64 ``[n_rows, n_channels]`` (reporter intensities, NaN where there is none),
+        ``matrix`` ``[n_channels, n_channels]`` the inverse of the lot's spill matrix (``pyascore_amd.rollup.channel_matrix``) or
+        None, ``normalize`` whether the column totals are then made equal, over the rows ``select`` names (one boolean per row;
+        None: all), ``scale_log2`` the quantum of the sums as ``quant=`` has it.  Returns ``(values, cell, factors)``: the
+        corrected matrix (new), ``pyascore_amd.rollup.SITE_QUANT_DTYPE[n_channels]`` the column sums after the matrix and before
+        the factors, and the factors float64 ``[n_channels]`` (None without ``normalize``).  One upload, one download.
+        ``pyascore_amd.rollup.correct_channels`` / ``channel_sums`` / ``channel_factors`` give the same bytes on the host."""
+        from .rollup import QUANT_MAX_CHANNELS, SITE_QUANT_DTYPE, check_channel_matrix, check_site_quant_params
+        v = np.ascontiguousarray(values, np.float64)
+        if v.ndim != 2 or not 1 <= v.shape[1] <= QUANT_MAX_CHANNELS or v.shape[0] > 0xFFFFFFFE:
+            raise ValueError("correct_channels: values is a float64 matrix, one row per spectrum and 1 .. %d channels" % QUANT_MAX_CHANNELS)
+        n_rows, n_ch = v.shape
+        if not isinstance(normalize, (bool, np.bool_)):
+            raise ValueError("correct_channels: normalize = %r is not a boolean" % (normalize,))
+        if matrix is None and not normalize:
+            raise ValueError("correct_channels: neither a matrix nor normalize=True")
+        m = None if matrix is None else check_channel_matrix(matrix, n_ch)
+        scale_log2 = check_site_quant_params(dict(threshold=0.0, scale_log2=scale_log2, n_channels=n_ch, complete_only=False))["scale_log2"]
+        sel = None
+        if select is not None:
+            sel = np.asarray(select)
+            if sel.shape != (n_rows,) or (sel.size and sel.dtype.kind not in "biu"):
+                raise ValueError("correct_channels: select is one boolean per row")
+            sel = np.ascontiguousarray(sel != 0, np.uint8)
+        out = np.empty_like(v)
+        cell = np.zeros(n_ch, SITE_QUANT_DTYPE)
+        factors = np.ones(n_ch, np.float64) if normalize else None
+        rc = self._lib.pya_channel_correct_host(self._h, _as_ptr(v) if n_rows else None, n_rows, n_ch, None if m is None else _as_ptr(m),
+                                                None if sel is None or not n_rows else _as_ptr(sel), scale_log2,
+                                                _lib.PYA_CHANNEL_NORMALIZE if normalize else 0, _as_ptr(out) if n_rows else None,
+                                                _as_ptr(cell), None if factors is None else _as_ptr(factors))
+        if rc:
+            self._raise(rc)
+        return out, cell, factors
 
     def marker_spectra(self, mz, intensity, peak_off, params, precursor_mz=None, precursor_charge=None):
         """The marker ions of spectra, looked up on the device (``pya_marker_spectra_host``; the rule is ``pya_marker_params``'s

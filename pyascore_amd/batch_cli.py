@@ -198,7 +198,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
              recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=None, markers=None,
-             marker_rows=None, site_quant=None, site_quant_rows=None, peptidoform_quant=None, peptidoform_quant_rows=None):
+             marker_rows=None, site_quant=None, site_quant_rows=None, peptidoform_quant=None, peptidoform_quant_rows=None, channels=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -257,7 +257,19 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``peptidoform_quant``: ``dict(threshold=, scale_log2=, complete_only=)`` as ``PyAscore.score_batch(peptidoform_quant=...)``
     takes it, without a matrix: the channels are the fixed targets ``mz`` of ``markers``, which it needs (``losses`` are no
     channels).  ``peptidoform_quant_rows``: the list that then receives one ``peptidoform_quant_fields`` row per peptidoform
-    (``write_peptidoform_quant_tsv``); the list is the one ``peptidoform_table`` gets, with ``peptidoform_threshold``."""
+    (``write_peptidoform_quant_tsv``); the list is the one ``peptidoform_table`` gets, with ``peptidoform_threshold``.
+    ``channels``: ``dict(matrix=, normalize=)`` as the ``channels=`` entry of ``PyAscore.score_batch(quant=...)`` takes it, without
+    ``select``: the reporter matrix is corrected for the lot's isotope impurities (``matrix``, of as many channels as ``markers``
+    has fixed targets) and / or brought to equal column totals before ``site_quant`` and ``peptidoform_quant`` sum it; it needs
+    one of the two."""
+    if channels is not None:                               # (a bad request is refused before anything is read or scored)
+        from .ascore import _channels_request
+        if site_quant is None and peptidoform_quant is None:
+            raise ValueError("channels corrects the matrix site_quant and peptidoform_quant sum: it needs one of them")
+        if not isinstance(channels, dict) or "select" in channels or not isinstance(markers, dict):
+            raise ValueError("channels takes a dict of matrix and normalize beside markers")
+        n_ch = len(tuple(markers.get("mz", ())))
+        _channels_request("channels", dict(values=np.zeros((0, n_ch)), channels=channels))
     if peptidoform_quant is not None:                      # (a bad request is refused before anything is read or scored)
         if not isinstance(peptidoform_quant, dict) or set(peptidoform_quant) - {"threshold", "scale_log2", "complete_only"} \
                 or peptidoform_quant_rows is None:
@@ -332,10 +344,11 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     if markers is not None:
         prec_mz, prec_z = hit_precursors(picked, scans)
         stages["markers"] = dict(markers, precursor_mz=prec_mz, precursor_charge=prec_z)
+    corrected = {} if channels is None else dict(channels=dict(channels))
     if site_quant is not None:
-        stages["quant"] = dict(site_quant, values=None)
+        stages["quant"] = dict(site_quant, values=None, **corrected)
     if peptidoform_quant is not None:
-        stages["peptidoform_quant"] = dict(peptidoform_quant, values=None)
+        stages["peptidoform_quant"] = dict(peptidoform_quant, values=None, **corrected)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything

@@ -966,6 +966,113 @@ def marker_values(scorer, d_markers, channel_mask=None, out=None):
     return out
 
 
+def _channel_tensor(t, shape, dtype, what):
+    if t.dtype != dtype or (shape is not None and tuple(t.shape) != shape) or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError("%s must be a contiguous %s device tensor%s" % (what, str(dtype).replace("torch.", ""),
+                                                                         "" if shape is None else " of shape %r" % (shape,)))
+    return t
+
+
+def correct_channels(scorer, d_values, matrix=None, factor=None, out=None):
+    """APPLY of the channel correction on a matrix that lives on the device (``pya_channel_correct``; the rule is in
+    include/pyascore_hip.h): ``d_values`` a contiguous ``torch.float64`` device tensor ``[n_rows, n_channels]`` (what
+    ``marker_values`` returns), ``matrix`` ``[n_channels, n_channels]`` and ``factor`` ``[n_channels]`` float64 device tensors or
+    host arrays (a host array is uploaded) or None, not both None.  ``out``: such a tensor as ``d_values`` to write into -- it
+    may be ``d_values`` itself: in place --, new when None.  Returns it.  One launch on torch's current stream; nothing waits on
+    the host.  ``pyascore_amd.rollup.correct_channels`` gives the same bytes."""
+    import torch
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    if d_values.dim() != 2 or not 1 <= d_values.shape[1] <= 64:
+        raise ValueError("d_values must be a float64 device tensor of shape (n_rows, n_channels), n_channels in 1 .. 64")
+    _channel_tensor(d_values, None, torch.float64, "d_values")
+    n_rows, n_ch = int(d_values.shape[0]), int(d_values.shape[1])
+    device = d_values.device
+    if matrix is None and factor is None:
+        raise ValueError("correct_channels: neither a matrix nor a factor")
+    if matrix is not None:
+        if not isinstance(matrix, torch.Tensor):
+            matrix = _upload(matrix, np.float64, device)
+        _channel_tensor(matrix, (n_ch, n_ch), torch.float64, "matrix")
+    if factor is not None:
+        if not isinstance(factor, torch.Tensor):
+            factor = _upload(factor, np.float64, device)
+        _channel_tensor(factor, (n_ch,), torch.float64, "factor")
+    if out is None:
+        with torch.cuda.device(device):
+            out = torch.empty((n_rows, n_ch), dtype=torch.float64, device=device)
+    _channel_tensor(out, (n_rows, n_ch), torch.float64, "out")
+    rc = scorer._lib.pya_channel_correct(scorer._h, d_values.data_ptr() if n_rows else None, n_rows, n_ch,
+                                         None if matrix is None else matrix.data_ptr(), None if factor is None else factor.data_ptr(),
+                                         torch.cuda.current_stream(device).cuda_stream, out.data_ptr() if n_rows else None)
+    if rc:
+        scorer._raise(rc)
+    return out
+
+
+def channel_sums(scorer, d_values, select=None, scale_log2=10, out=None):
+    """SUMS of the channel correction over a device matrix (``pya_channel_sums``): ``d_values`` as ``correct_channels`` takes
+    it, ``select`` a ``torch.uint8`` device tensor ``[n_rows]`` (0: the row is left out) or a host array of booleans or None for
+    all rows.  ``out``: a contiguous ``torch.uint8`` device tensor ``[n_channels, 16]``, one ``pya_site_quant`` per channel, to
+    ADD into; None: a new zeroed one.  Returns it (``channel_sum_records`` reads a host copy).  One launch on torch's current
+    stream; nothing waits on the host.  ``pyascore_amd.rollup.channel_sums`` gives the same bytes."""
+    import torch
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    if d_values.dim() != 2 or not 1 <= d_values.shape[1] <= 64:
+        raise ValueError("d_values must be a float64 device tensor of shape (n_rows, n_channels), n_channels in 1 .. 64")
+    _channel_tensor(d_values, None, torch.float64, "d_values")
+    n_rows, n_ch = int(d_values.shape[0]), int(d_values.shape[1])
+    device = d_values.device
+    if select is not None:
+        if not isinstance(select, torch.Tensor):
+            select = _upload(np.asarray(select) != 0, np.uint8, device)
+        _channel_tensor(select, (n_rows,), torch.uint8, "select")
+    if out is None:
+        with torch.cuda.device(device):
+            out = torch.zeros((n_ch, 16), dtype=torch.uint8, device=device)
+    _channel_tensor(out, (n_ch, 16), torch.uint8, "out")
+    rc = scorer._lib.pya_channel_sums(scorer._h, d_values.data_ptr() if n_rows else None, n_rows, n_ch,
+                                      None if select is None or not n_rows else select.data_ptr(), int(scale_log2),
+                                      torch.cuda.current_stream(device).cuda_stream, out.data_ptr())
+    if rc:
+        scorer._raise(rc)
+    return out
+
+
+def channel_factors(scorer, d_cell, out=None):
+    """FACTORS of the channel correction (``pya_channel_factors``): ``d_cell`` the tensor of ``channel_sums`` (uint8
+    ``[n_channels, 16]``); returns a ``torch.float64`` device tensor ``[n_channels]``, ``out`` when given.  One launch of one
+    wavefront on torch's current stream; nothing waits on the host, so sums, factors and the second ``correct_channels`` chain
+    without a host read.  ``pyascore_amd.rollup.channel_factors`` gives the same bytes."""
+    import torch
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    if d_cell.dim() != 2 or not 1 <= d_cell.shape[0] <= 64:
+        raise ValueError("d_cell must be a uint8 device tensor of shape (n_channels, 16), n_channels in 1 .. 64")
+    n_ch = int(d_cell.shape[0])
+    _channel_tensor(d_cell, (n_ch, 16), torch.uint8, "d_cell")
+    device = d_cell.device
+    if out is None:
+        with torch.cuda.device(device):
+            out = torch.empty(n_ch, dtype=torch.float64, device=device)
+    _channel_tensor(out, (n_ch,), torch.float64, "out")
+    rc = scorer._lib.pya_channel_factors(scorer._h, d_cell.data_ptr(), n_ch, torch.cuda.current_stream(device).cuda_stream, out.data_ptr())
+    if rc:
+        scorer._raise(rc)
+    return out
+
+
+def channel_sum_records(raw):
+    """A host copy of the tensor of ``channel_sums`` (``.cpu().numpy()``, uint8 ``[n_channels, 16]``) as the structured array
+    ``pyascore_amd.rollup.channel_sums`` returns (``SITE_QUANT_DTYPE[n_channels]``); a view, no copy."""
+    from .rollup import SITE_QUANT_DTYPE
+    cell = np.ascontiguousarray(raw, np.uint8)
+    if cell.ndim != 2 or cell.shape[1] != SITE_QUANT_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n_channels, 16)")
+    return cell.view(SITE_QUANT_DTYPE).reshape(cell.shape[0])
+
+
 def site_quant_records(raw):
     """Host copies of the table of ``DevicePlan.site_quant`` (``.cpu().numpy()`` of the pair: uint8 ``[n_slots, 8]`` and
     ``[n_slots, n_channels, 16]``) as the structured arrays ``PyAscore.score_batch(..., quant=...)`` returns in ``quant_head``

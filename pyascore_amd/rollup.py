@@ -1693,3 +1693,191 @@ def merge_peptidoform_quant(*pairs, cap=None):
     for part in parts:
         _pfq_add_rows(place, head, cell, part)
     return records, head, cell
+
+
+CHANNEL_TILE = _lib.PYA_CHANNEL_TILE                # rows per workgroup of csrc/channel_correct.hip
+
+
+def channel_spill(n_channels, entries):
+    """The spill matrix ``S`` of a reagent lot, float64 ``[n_channels, n_channels]`` with ``observed = S @ true``, from
+    ``(from, to, fraction)`` triples: ``fraction`` of channel ``from``'s reporter shows up in channel ``to`` (``S[to, from]``);
+    ``to = -1``: it leaves to no channel (an isotope peak outside the plex).  The diagonal is 1 minus what leaves.  The numbers
+    are the caller's, from the lot's sheet: no presets are shipped.  ValueError for a channel outside the plex, ``from == to``, a
+    fraction that is not finite or negative, a triple named twice, or a channel that loses everything."""
+    try:
+        n = int(n_channels)
+        ok = n == n_channels and not isinstance(n_channels, bool) and 1 <= n <= QUANT_MAX_CHANNELS
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError("channel_spill: n_channels = %r is not an integer in 1 .. %d" % (n_channels, QUANT_MAX_CHANNELS))
+    s = np.zeros((n, n), np.float64)
+    leaves = [0.0] * n
+    seen = set()
+    for entry in entries:
+        try:
+            a, b, frac = entry
+            a, b, frac = int(a), int(b), float(frac)
+        except (TypeError, ValueError):
+            raise ValueError("channel_spill: an entry is (from, to, fraction), not %r" % (entry,)) from None
+        if not 0 <= a < n or not -1 <= b < n or a == b:
+            raise ValueError("channel_spill: entry %r names a channel outside 0 .. %d (to may be -1), or from == to" % (entry, n - 1))
+        if not np.isfinite(frac) or frac < 0.0:
+            raise ValueError("channel_spill: the fraction of entry %r is not a finite number >= 0" % (entry,))
+        if b >= 0 and (a, b) in seen:
+            raise ValueError("channel_spill: (%d, %d) is named twice" % (a, b))
+        seen.add((a, b))
+        leaves[a] += frac
+        if b >= 0:
+            s[b, a] = frac
+    for c in range(n):
+        if not leaves[c] < 1.0:
+            raise ValueError("channel_spill: channel %d loses %g of itself" % (c, leaves[c]))
+        s[c, c] = 1.0 - leaves[c]
+    return s
+
+
+def channel_matrix(spill):
+    """The correction matrix of ``correct_channels``: the inverse of the spill matrix ``S`` (``channel_spill``), by
+    ``numpy.linalg.inv`` in float64.  ValueError for a matrix that is not square, not finite, larger than the channel limit, or
+    whose condition number (2-norm) is above 1e6: such a lot sheet does not determine the true intensities."""
+    try:
+        s = np.array(spill, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("channel_matrix: spill is a square matrix of numbers") from None
+    if s.ndim != 2 or s.shape[0] != s.shape[1] or not 1 <= s.shape[0] <= QUANT_MAX_CHANNELS:
+        raise ValueError("channel_matrix: spill is a square matrix of 1 .. %d channels" % QUANT_MAX_CHANNELS)
+    if not np.isfinite(s).all():
+        raise ValueError("channel_matrix: spill has entries that are not finite")
+    try:
+        cond = float(np.linalg.cond(s))
+        inv = np.linalg.inv(s)
+    except np.linalg.LinAlgError:
+        raise ValueError("channel_matrix: spill is singular") from None
+    if not cond <= 1e6 or not np.isfinite(inv).all():
+        raise ValueError("channel_matrix: the condition number of spill, %g, is above 1e6" % cond)
+    return np.ascontiguousarray(inv)
+
+
+def _channel_values(values, what):
+    v = np.ascontiguousarray(values, np.float64)
+    if v.ndim != 2 or not 1 <= v.shape[1] <= QUANT_MAX_CHANNELS:
+        raise ValueError("%s: values is a float64 matrix, one row per spectrum and 1 .. %d channels" % (what, QUANT_MAX_CHANNELS))
+    return v
+
+
+def check_channel_matrix(matrix, n_channels, what="correct_channels"):
+    """``matrix`` as the contiguous float64 ``[n_channels, n_channels]`` array the library reads; ValueError for another shape"""
+    try:
+        m = np.ascontiguousarray(matrix, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: matrix is a square matrix of numbers" % what) from None
+    if m.shape != (n_channels, n_channels):
+        raise ValueError("%s: matrix has shape %r, not (%d, %d)" % (what, m.shape, n_channels, n_channels))
+    return m
+
+
+def correct_channels(values, matrix=None, factor=None):
+    """APPLY of the channel correction (``pya_channel_correct`` in include/pyascore_hip.h) restated in numpy, with the same
+    bytes: ``values`` float64 ``[n_rows, n_channels]``, ``matrix`` ``[n_channels, n_channels]`` (``channel_matrix``) or None,
+    ``factor`` ``[n_channels]`` (``channel_factors``) or None, not both None.  Vectorised over the rows only: the chain over the
+    channels runs in the rule's order, one multiplication and one addition per term.  Returns a new matrix."""
+    v = _channel_values(values, "correct_channels")
+    n_ch = v.shape[1]
+    if matrix is None and factor is None:
+        raise ValueError("correct_channels: neither a matrix nor a factor")
+    usable = (v == v) & (v > 0.0)
+    with np.errstate(all="ignore"):
+        if matrix is not None:
+            m = check_channel_matrix(matrix, n_ch)
+            u = np.where(usable, v, 0.0)
+            x = np.empty_like(v)
+            for c in range(n_ch):
+                acc = np.zeros(v.shape[0], np.float64)
+                for j in range(n_ch):
+                    t = m[c, j] * u[:, j]
+                    acc = acc + t
+                x[:, c] = acc
+        else:
+            x = v.copy()
+        if factor is not None:
+            f = np.ascontiguousarray(factor, np.float64)
+            if f.shape != (n_ch,):
+                raise ValueError("correct_channels: factor has one entry per channel")
+            x = x * f[None, :]
+        x = np.where((x == x) & (x > 0.0), x, 0.0)
+    out = v.copy()
+    out[usable] = x[usable]
+    return out
+
+
+def channel_sums(values, select=None, scale_log2=10, into=None):
+    """SUMS of the channel correction (``pya_channel_sums``) restated in numpy: the table row ``SITE_QUANT_DTYPE[n_channels]``
+    of the column sums of ``values`` over the rows ``select`` names (one byte or bool per row; None: all), added to ``into``
+    (it is copied; None: the empty row)."""
+    v = _channel_values(values, "channel_sums")
+    p = check_site_quant_params(dict(threshold=0.0, scale_log2=scale_log2, n_channels=v.shape[1], complete_only=False))
+    cell = np.zeros(v.shape[1], SITE_QUANT_DTYPE) if into is None else np.array(into, SITE_QUANT_DTYPE)
+    if cell.shape != (v.shape[1],):
+        raise ValueError("channel_sums: into is a row of one cell per channel")
+    if select is not None:
+        select = np.asarray(select)
+        if select.shape != (v.shape[0],):
+            raise ValueError("channel_sums: select has one entry per row")
+        v = v[select != 0]
+    usable = (v == v) & (v > 0.0)
+    with np.errstate(over="ignore", invalid="ignore"):
+        t = v * 2.0 ** p["scale_log2"]
+    saturated = usable & (t >= 281474976710656.0)
+    q = np.where(usable & ~saturated, t, 0.0).astype(np.uint64)
+    q[saturated] = np.uint64(1 << 48)
+    cell["sum"] += q.sum(axis=0, dtype=np.uint64)
+    cell["n"] += usable.sum(axis=0).astype(np.uint32)
+    cell["n_saturated"] += saturated.sum(axis=0).astype(np.uint32)
+    return cell
+
+
+def channel_factors(cell):
+    """FACTORS of the channel correction (``pya_channel_factors``) restated in numpy: float64 ``[n_channels]``, the largest
+    ``sum`` of the row over each ``sum`` (1.0 for an empty column), both converted to the nearest double and divided once."""
+    cell = np.ascontiguousarray(cell, SITE_QUANT_DTYPE)
+    if cell.ndim != 1 or not 1 <= cell.size <= QUANT_MAX_CHANNELS:
+        raise ValueError("channel_factors: cell is a row of 1 .. %d cells" % QUANT_MAX_CHANNELS)
+    s = cell["sum"]
+    top = np.full(s.shape, s.max(), np.uint64).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(s == 0, 1.0, top / s.astype(np.float64))
+
+
+def _is_number(text):
+    try:
+        float(text)
+    except ValueError:
+        return False
+    return True
+
+
+def read_channel_spill(path, n_channels):
+    """The spill matrix (``channel_spill``) of a tab-separated file of ``from``, ``to``, ``fraction`` lines, the channels
+    numbered from 0 in the order the caller's channels have; blank lines, lines that start with ``#`` and one header line whose
+    first field is no number are skipped.  ValueError (with the line) for anything else."""
+    entries, header = [], False
+    with open(path) as f:
+        for n, line in enumerate(f, 1):
+            text = line.strip()
+            if not text or text.startswith("#"):
+                continue
+            fields = text.split("\t")
+            try:
+                if len(fields) != 3:
+                    raise ValueError
+                entries.append((int(fields[0]), int(fields[1]), float(fields[2])))
+            except ValueError:
+                if not entries and not header and len(fields) == 3 and not _is_number(fields[0]):
+                    header = True
+                    continue
+                raise ValueError("%s line %d: expected from<TAB>to<TAB>fraction, got %r" % (path, n, text)) from None
+    try:
+        return channel_spill(n_channels, entries)
+    except ValueError as e:
+        raise ValueError("%s: %s" % (path, e)) from None
