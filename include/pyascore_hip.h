@@ -793,6 +793,68 @@ typedef struct pya_marker_spectrum {   /* 32 bytes per spectrum */
     uint32_t n_peaks, n_active;                    /* peaks of the spectrum; active targets                                  */
 } pya_marker_spectrum;
 
+/* Precursor purity: the share of an MS2 scan's isolation window that belonged to the identified precursor, read off the survey
+ * (MS1) scan in front of it -- MaxQuant's PIF, Proteome Discoverer's "isolation interference".  A reporter reading is only as
+ * good as that share: what else was isolated adds its own signal to every channel and compresses the ratios.  A READ-ONLY
+ * stage over the survey spectra, as the marker stage is over the MS2 spectra: records out, no workspace, and no kernel of a
+ * run knows of it.  The reference has no counterpart.
+ * THE RULE.  n_survey survey spectra (pya_typed_spectra + int64 offsets) and n_query queries, one per MS2 spectrum, row-aligned
+ * with the matrix pya_marker_values writes.  Per query q: survey[q] (int64, the survey spectrum to read), prec_mz[q] (double),
+ * prec_z[q] (int32), win_lo[q] and win_hi[q] (double, the ABSOLUTE m/z bounds of the isolation window).  All arithmetic is in
+ * double, every operation rounded on its own, in the order written; a comparison with a NaN is false; float32 is widened at
+ * the load.
+ * INACTIVE: a query with survey[q] < 0, or whose precursor fails strip's test (prec_z in 1 .. PYA_STRIP_MAX_CHARGE, prec_mz
+ * finite and > 0), or for which win_lo <= win_hi is false, or one of whose bounds is not finite.  Its record is all zero and
+ * nothing is read for it.
+ * survey[q] >= n_survey: the record is all zero and the query is reported through d_over as a clipped spectrum is (counted in
+ * d_over[0], the smallest such q in d_over[1] as 0xffffffff - q); nothing is read.  An active query whose survey spectrum's
+ * offsets had to be clipped to the elements the arrays hold is reported the same way; its record is that of the clipped peaks.
+ * THE CENTRES of an active query:
+ *   d = step / (double)prec_z
+ *   for i = -below .. isotopes:
+ *     c_i  = prec_mz + (double)i d
+ *     w_i  = tol + (tol_ppm 1e-6) c_i
+ *     lo_i = c_i - w_i,  hi_i = c_i + w_i
+ * THE PEAKS: peak (x, y) of the survey spectrum, in index order, is
+ *   INSIDE    iff win_lo <= x && x <= win_hi
+ *   ELIGIBLE  iff inside and y > 0.0
+ *   PRECURSOR iff eligible and lo_i <= x && x <= hi_i for some i.
+ * A centre outside the isolation window gets nothing; a peak in two centre windows counts once.
+ * THE RECORD: window is the sum of y over the eligible peaks and precursor the sum of y over the precursor peaks, each
+ * SEQUENTIAL from 0.0 in index order -- the two sums have ONE defined order, the survey spectrum's own.  other_mz /
+ * other_intensity: the most intense eligible peak that is no precursor peak; the larger y wins, then the smaller x -- total up
+ * to equal (x, y) --, stored + 0.0, and 0.0 / 0.0 when there is none.  n_window and n_precursor count the eligible and the
+ * precursor peaks; bit i + below of iso_hit is set iff centre i holds an eligible peak; flags is PYA_PURITY_ACTIVE, with
+ * PYA_PURITY_SEEN iff n_precursor > 0.  The ratio is not stored: precursor / window where window > 0.  Every record of a call
+ * is written.
+ * The parameters must satisfy: tol and tol_ppm finite and >= 0; step finite and > 0; below 0 .. 4;
+ * n_c = below + 1 + isotopes in 1 .. PYA_PURITY_MAX_CENTRES; reserved == 0.  The defaults of the Python layer (tol 0, tol_ppm
+ * 10, isotopes 3, below 0, step PYA_STRIP_STEP) are choices, not measurements.
+ * THE GATE (pya_purity_gate): threshold finite in [0, 1], keep_unknown 0 or 1.  Row r is KNOWN iff its record is ACTIVE and
+ * window > 0.0.  It PASSES iff known ? precursor >= threshold window : keep_unknown -- one multiplication, no division.
+ * select[r] = 1 / 0; in the matrix a passing row's readings have their bits copied and a failing row's readings become the NaN
+ * pya_marker_values writes for "no reading" (0x7ff8000000000000). */
+#define PYA_PURITY_MAX_CENTRES 16
+#define PYA_PURITY_MAX_BELOW 4
+typedef struct pya_purity_params {     /* 40 bytes */
+    double tol;                                    /* half width of a centre's window in m/z (Da); finite, >= 0              */
+    double tol_ppm;                                /* and in ppm of the centre, added to it; finite, >= 0                    */
+    double step;                                   /* the isotope spacing at charge 1 (PYA_STRIP_STEP); finite, > 0          */
+    uint32_t below;                                /* isotope positions under the selected m/z, 0 .. PYA_PURITY_MAX_BELOW    */
+    uint32_t isotopes;                             /* positions above it; below + 1 + isotopes <= PYA_PURITY_MAX_CENTRES     */
+    uint32_t reserved[2];                          /* 0                                                                      */
+} pya_purity_params;
+typedef struct pya_purity {            /* 48 bytes per query */
+    double window;                                 /* sum of y over the eligible peaks, in index order                       */
+    double precursor;                              /* sum of y over the precursor peaks, in index order                      */
+    double other_mz, other_intensity;              /* the most intense eligible peak that is no precursor peak; 0.0 / 0.0    */
+    uint32_t n_window, n_precursor;                /* eligible peaks; precursor peaks                                        */
+    uint32_t iso_hit;                              /* bit i + below: centre i holds an eligible peak                         */
+    uint32_t flags;                                /* PYA_PURITY_ACTIVE; PYA_PURITY_SEEN iff n_precursor > 0                 */
+} pya_purity;
+#define PYA_PURITY_ACTIVE 1u
+#define PYA_PURITY_SEEN 2u
+
 /* Centroiding (peak picking): the first of the transforms in front of a run.  Everything behind it -- the top-N-per-100-m/z
  * binning, the match window, deisotoping's tol, the strip windows -- takes one (m/z, intensity) pair for one peak.  A
  * profile-mode spectrum (msconvert without a peak-picking filter, older QTOF exports, "profile MS2" methods) has 10 to 20
@@ -1324,6 +1386,42 @@ int pya_marker_spectra_host(pya_handle *h, const pya_typed_spectra *in, const in
  * n_targets, more than 2^32 - 2 spectra, a NULL array.  n_spectra == 0 is a call that writes nothing. */
 int pya_marker_values(pya_handle *h, const pya_marker *d_markers, uint64_t n_spectra, uint32_t n_targets, uint64_t channel_mask,
                       void *hip_stream, double *d_values);
+/* The precursor purity of n_query queries over n_survey survey spectra on the device (THE RULE at pya_purity_params above;
+ * csrc/purity.hip).  d_survey_spectra, d_survey_off[n_survey + 1] and n_survey as pya_marker_spectra takes its spectra;
+ * n_survey_peaks: the elements the arrays hold -- the offsets are clipped to it, so nothing beyond it is read whatever they
+ * say; d_survey[n_query] (int64), d_prec_mz[n_query] (double), d_prec_z[n_query] (int32), d_win_lo[n_query] and
+ * d_win_hi[n_query] (double) in device memory; d_purity[n_query]: one pya_purity per query (device memory, 8-byte aligned);
+ * d_over[2] (zeroed by the caller): the queries with survey[q] >= n_survey or a clipped survey spectrum are counted in
+ * d_over[0], the smallest of them in d_over[1] as 0xffffffff - q.  One launch on hip_stream, one wavefront per query,
+ * stream-ordered, no host wait, no allocation and no workspace.  The inputs are only read; no write lies outside
+ * d_purity[0 .. n_query) and d_over[0 .. 2).
+ * PYA_ERR_ARG, with nothing launched: more than 2^32 - 2 queries or survey spectra, parameters outside the conditions above,
+ * element types that are neither PYA_F64 nor PYA_F32, float32 m/z beside float64 intensities, a NULL array, records that are
+ * not 8-byte aligned.  n_query == 0 is a call that writes nothing; n_survey == 0 is allowed (the survey arrays may then be
+ * NULL but for the offsets: every query is inactive or out of range). */
+int pya_purity_spectra(pya_handle *h, const pya_typed_spectra *d_survey_spectra, const int64_t *d_survey_off, uint64_t n_survey,
+                       uint64_t n_survey_peaks, const int64_t *d_survey, const double *d_prec_mz, const int32_t *d_prec_z,
+                       const double *d_win_lo, const double *d_win_hi, uint64_t n_query, const pya_purity_params *params,
+                       void *hip_stream, pya_purity *d_purity, uint32_t *d_over);
+/* The same over HOST arrays: uploads the survey spectra and the queries once, runs on the handle's stream, downloads only the
+ * records and over, and waits.  survey_off[0] must not be negative and the offsets must not descend (PYA_ERR_ARG);
+ * n_survey_peaks is survey_off[n_survey]. */
+int pya_purity_spectra_host(pya_handle *h, const pya_typed_spectra *survey_spectra, const int64_t *survey_off, uint64_t n_survey,
+                            const int64_t *survey, const double *prec_mz, const int32_t *prec_z, const double *win_lo,
+                            const double *win_hi, uint64_t n_query, const pya_purity_params *params, pya_purity *purity,
+                            uint32_t *over);
+/* THE GATE of the precursor purity over the records d_purity[n_rows] (device memory, as pya_purity_spectra wrote them):
+ * d_select[n_rows] (uint8, or NULL) takes 1 for a passing row and 0 otherwise; with n_channels in 1 .. PYA_QUANT_MAX_CHANNELS
+ * d_out[n_rows * n_channels] takes d_values[n_rows * n_channels] (doubles, 8-byte aligned) with the readings of a passing row
+ * copied bit for bit and those of a failing row set to the NaN of pya_marker_values.  d_out == d_values, exactly in place, is
+ * allowed; any other overlap is the caller's error.  n_channels == 0 asks for d_select alone (d_values and d_out are not
+ * looked at).  One launch on hip_stream, stream-ordered, no host wait, no allocation; the records are only read and no write
+ * lies outside d_out[0 .. n_rows * n_channels) and d_select[0 .. n_rows).  PYA_ERR_ARG, with nothing launched: n_channels
+ * above PYA_QUANT_MAX_CHANNELS, more than 2^32 - 2 rows, a threshold that is NaN or outside [0, 1], keep_unknown neither 0
+ * nor 1, nothing to write (n_channels == 0 and d_select NULL), a NULL array that is needed, records or matrices that are not
+ * 8-byte aligned.  n_rows == 0 is a call that writes nothing. */
+int pya_purity_gate(pya_handle *h, const pya_purity *d_purity, uint64_t n_rows, double threshold, uint32_t keep_unknown,
+                    const double *d_values, uint32_t n_channels, double *d_out, uint8_t *d_select, void *hip_stream);
 /* Applies a correction to the channel matrix d_values[n_rows * n_channels] (APPLY of the channel correction above;
  * csrc/channel_correct.hip): d_matrix[n_channels * n_channels] (row-major) or NULL, d_factor[n_channels] or NULL, not both
  * NULL; d_out[n_rows * n_channels] takes the result (all device memory, doubles, 8-byte aligned).  d_out == d_values, exactly

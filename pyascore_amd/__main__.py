@@ -30,7 +30,10 @@ intensities of the ``--marker_mz`` targets summed over the PSMs that localise th
 with ``--peptidoform_quant_threshold P``, ``--peptidoform_quant_scale E`` and ``--peptidoform_quant_complete`` (a line per peptidoform:
 the columns of ``--peptidoform_table``, then the same intensities summed over the PSMs that report the assignment; it needs
 ``--marker_mz``) and ``--channel_spill FILE`` and ``--channel_normalize`` (the reporter intensities corrected for the reagent lot's
-isotope impurities and brought to equal channel totals before either table sums them) are the additions."""
+isotope impurities and brought to equal channel totals before either table sums them) and ``--purity FILE`` with ``--purity_tol``,
+``--purity_tol_ppm``, ``--purity_isotopes``, ``--purity_below``, ``--purity_window LO,HI``, ``--purity_threshold P`` and
+``--purity_drop_unknown`` (per PSM the share of its isolation window that was its precursor, read off the survey scans of the
+spectrum file; with a threshold the impure spectra are left out of both quantification tables) are the additions."""
 import argparse
 import re
 import sys
@@ -234,6 +237,28 @@ def build_parser():
     p.add_argument("--channel_normalize", action="store_true",
                    help="with --site_quant / --peptidoform_quant: bring the channels to equal totals over all spectra (after "
                         "--channel_spill) before they are summed")
+    p.add_argument("--purity", type=str, default="", metavar="FILE",
+                   help="write the precursor-purity table to FILE: one line per PSM with the survey (MS1) scan in front of its "
+                        "spectrum, the bounds of its isolation window, the intensity inside the window there, the part of it at the "
+                        "precursor's m/z and isotope positions, their ratio, the peak counts, which isotope positions held a peak "
+                        "and the most intense other peak (the survey scans are a second read of the spectrum file)")
+    p.add_argument("--purity_tol", type=float, default=0.0, metavar="DA",
+                   help="with --purity: the half width of the window around an isotope position in m/z (default 0)")
+    p.add_argument("--purity_tol_ppm", type=float, default=10.0, metavar="PPM",
+                   help="with --purity: ... plus this many ppm of the position's m/z (default 10)")
+    p.add_argument("--purity_isotopes", type=int, default=3, metavar="N",
+                   help="with --purity: isotope positions above the precursor's m/z that count as the precursor (default 3)")
+    p.add_argument("--purity_below", type=int, default=0, metavar="N",
+                   help="with --purity: isotope positions under the precursor's m/z that count as the precursor, 0 .. 4 (default 0)")
+    p.add_argument("--purity_window", type=str, default="", metavar="LO,HI",
+                   help="with --purity: the offsets of the isolation window under and above the precursor's m/z, used where the "
+                        "spectrum file declares none (default: such a spectrum has no purity)")
+    p.add_argument("--purity_threshold", type=float, default=None, metavar="P",
+                   help="with --purity beside --site_quant / --peptidoform_quant: leave out the reporter readings of every spectrum "
+                        "whose precursor made up less than P of its isolation window")
+    p.add_argument("--purity_drop_unknown", action="store_true",
+                   help="with --purity_threshold: also leave out the spectra whose purity is not known (no survey scan, no window, "
+                        "an empty window)")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -330,6 +355,35 @@ def markers_request(args):
     return req
 
 
+def purity_request(args):
+    """``--purity`` as the dict ``batch_cli.localize(purity=...)`` takes, without the survey records (``run`` reads them),
+    checked; None without the option: the other ``--purity_*`` values are then not looked at -- but for ``--purity_threshold``,
+    which is refused without it."""
+    if not getattr(args, "purity", ""):
+        if getattr(args, "purity_threshold", None) is not None or getattr(args, "purity_drop_unknown", False):
+            raise ValueError("--purity_threshold / --purity_drop_unknown gate on the table of --purity: give --purity FILE as well")
+        return None
+    from . import batch_cli
+    req = dict(tol=args.purity_tol, tol_ppm=args.purity_tol_ppm, isotopes=args.purity_isotopes, below=args.purity_below)
+    if args.purity_window:
+        try:
+            req["window"] = tuple(float(v) for v in args.purity_window.split(","))
+        except ValueError:
+            raise ValueError("--purity_window takes two offsets LO,HI, not %r" % args.purity_window) from None
+        if len(req["window"]) != 2:
+            raise ValueError("--purity_window takes two offsets LO,HI, not %r" % args.purity_window)
+    if args.purity_threshold is not None:
+        req["threshold"] = args.purity_threshold
+        req["keep_unknown"] = not args.purity_drop_unknown
+    elif args.purity_drop_unknown:
+        raise ValueError("--purity_drop_unknown goes with --purity_threshold")
+    try:
+        batch_cli.purity_request(dict(req, survey=()), [], bool(getattr(args, "site_quant", "") or getattr(args, "peptidoform_quant", "")))
+    except ValueError as e:
+        raise ValueError("--purity: %s" % e) from None
+    return req
+
+
 def centroid_request(args):
     """The rule of ``--centroid`` as the dict ``batch_cli.localize(centroid=...)`` takes (which spectra it applies to comes
     from the spectra), checked; None without the flag: the other ``--centroid_*`` values are then not looked at."""
@@ -361,6 +415,7 @@ def validate_args(args):
     site_quant_request(args)
     peptidoform_quant_request(args)
     channels_request(args)
+    purity_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -432,6 +487,11 @@ def run(args, log=print):
     site_quant_rows = [] if site_quant is not None else None
     pform_quant = peptidoform_quant_request(args)
     pform_quant_rows = [] if pform_quant is not None else None
+    purity = purity_request(args)
+    purity_rows = [] if purity is not None else None
+    if purity is not None:
+        log("{} -- Reading survey scans from: {}".format(stamp(), args.spec_file))
+        purity["survey"] = ingest.SpectraParser(args.spec_file, args.spec_file_type, ms_level=1, native_precision=True).to_list()
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -447,7 +507,7 @@ def run(args, log=print):
                               centroid=centroid_request(args), coverage=coverage_rows, markers=markers,
                               marker_rows=marker_rows, site_quant=site_quant, site_quant_rows=site_quant_rows,
                               peptidoform_quant=pform_quant, peptidoform_quant_rows=pform_quant_rows,
-                              channels=channels_request(args))
+                              channels=channels_request(args), purity=purity, purity_rows=purity_rows)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -473,6 +533,8 @@ def run(args, log=print):
         batch_cli.write_site_quant_tsv(site_quant_rows, args.site_quant, mz=markers["mz"])
     if pform_quant_rows is not None:
         batch_cli.write_peptidoform_quant_tsv(pform_quant_rows, args.peptidoform_quant, mz=markers["mz"])
+    if purity_rows is not None:
+        batch_cli.write_purity_tsv(purity_rows, args.purity)
     if marker_rows is not None and args.markers:
         batch_cli.write_markers_tsv(marker_rows, args.markers, mz=markers["mz"], losses=markers["losses"])
     log("{} -- Ascore Completed".format(stamp()))

@@ -303,6 +303,33 @@ class MarkerSpectrum(C.Structure):
 assert C.sizeof(MarkerSpectrum) == 32, "pya_marker_spectrum is a 32-byte record"
 MARKER_SPECTRUM_DTYPE = [("tic", "<f8"), ("base_peak", "<f8"), ("hit", "<u8"), ("n_peaks", "<u4"), ("n_active", "<u4")]
 
+PYA_PURITY_MAX_CENTRES = 16
+PYA_PURITY_MAX_BELOW = 4
+PYA_PURITY_ACTIVE = 1
+PYA_PURITY_SEEN = 2
+
+
+class PurityParams(C.Structure):
+    """pya_purity_params: the half width of a centre's window in Da and in ppm of the centre, the isotope spacing at charge 1,
+    the isotope positions under and above the selected m/z"""
+    _fields_ = [("tol", C.c_double), ("tol_ppm", C.c_double), ("step", C.c_double), ("below", C.c_uint32), ("isotopes", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+assert C.sizeof(PurityParams) == 40, "pya_purity_params is a 40-byte record"
+
+
+class Purity(C.Structure):
+    """pya_purity: the eligible and the precursor intensity of an isolation window, the most intense other peak, the counts,
+    which centres held a peak, whether the query was active and its precursor seen"""
+    _fields_ = [("window", C.c_double), ("precursor", C.c_double), ("other_mz", C.c_double), ("other_intensity", C.c_double),
+                ("n_window", C.c_uint32), ("n_precursor", C.c_uint32), ("iso_hit", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(Purity) == 48, "pya_purity is a 48-byte record"
+PURITY_DTYPE = [("window", "<f8"), ("precursor", "<f8"), ("other_mz", "<f8"), ("other_intensity", "<f8"), ("n_window", "<u4"),
+                ("n_precursor", "<u4"), ("iso_hit", "<u4"), ("flags", "<u4")]
+
 PYA_CENTROID_MAX_HALF_WIDTH = 8
 
 
@@ -426,6 +453,11 @@ SYMBOLS = {
     "pya_marker_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.c_uint64, _vp, _vp, C.POINTER(MarkerParams), _vp, _vp, _vp,
                                      _vp]),
     "pya_marker_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, C.POINTER(MarkerParams), _vp, _vp, _vp]),
+    "pya_purity_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                     C.POINTER(PurityParams), _vp, _vp, _vp]),
+    "pya_purity_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                          C.POINTER(PurityParams), _vp, _vp]),
+    "pya_purity_gate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_double, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
     "pya_centroid_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "pya_centroid_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, C.POINTER(CentroidParams), _vp, _vp, C.c_uint64,
                                        C.POINTER(TypedSpectra), _vp, _vp]),

@@ -322,6 +322,40 @@ def _markers_request(req, mz_error, n_spec=None):
     return params, prec_mz, prec_z
 
 
+def _purity_request(req, n_spec=None, have_quant=True):
+    """``score_batch(purity=...)`` checked: ``(params, spectra, queries, gate)`` -- the dict of
+    ``pyascore_amd.rollup.purity_params``, ``(ms1_mz, ms1_intensity, ms1_peak_off)`` as given, the five query arrays of
+    ``pyascore_amd.rollup.purity_queries`` (``n_spec`` entries each when it is given) and ``(threshold, keep_unknown)`` or None"""
+    from .rollup import check_purity_gate, purity_params, purity_queries
+    rule_names = ("tol", "tol_ppm", "isotopes", "below", "step")
+    names = ("ms1_mz", "ms1_intensity", "ms1_peak_off", "survey", "precursor_mz", "precursor_charge", "window_lo", "window_hi") + rule_names + \
+        ("gate",)
+    if not isinstance(req, dict):
+        raise ValueError("purity takes a dict: " + ", ".join(names))
+    unknown = set(req) - set(names)
+    if unknown:
+        raise ValueError("purity takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+    missing = [k for k in names[:8] if req.get(k) is None]
+    if missing:
+        raise ValueError("purity needs " + ", ".join(missing))
+    try:
+        params = purity_params(**{k: req[k] for k in rule_names if req.get(k) is not None})
+    except TypeError:
+        raise ValueError("purity: tol, tol_ppm and step are numbers, isotopes and below integers") from None
+    queries = purity_queries(req["survey"], req["precursor_mz"], req["precursor_charge"], req["window_lo"], req["window_hi"])
+    if n_spec is not None and queries[0].size != n_spec:
+        raise ValueError("purity: survey, precursor_mz, precursor_charge, window_lo and window_hi have one entry per spectrum (per PSM in a "
+                         "batch without spec_of)")
+    gate = req.get("gate")
+    if gate is not None:
+        if not isinstance(gate, dict) or set(gate) - {"threshold", "keep_unknown"} or gate.get("threshold") is None:
+            raise ValueError("purity: gate takes a dict: threshold, keep_unknown")
+        gate = check_purity_gate(gate["threshold"], gate.get("keep_unknown", True), "purity: gate")
+        if not have_quant:
+            raise ValueError("purity: gate needs quant= or peptidoform_quant= in the same call: it is their matrix that is gated")
+    return params, (req["ms1_mz"], req["ms1_intensity"], req["ms1_peak_off"]), queries, gate
+
+
 def _centroid_request(req, n_spec=None):
     """``score_batch(centroid=...)`` checked: ``(params, select)`` -- the dict of ``pyascore_amd.rollup.centroid_params`` and
     the uint8 ``select`` array (one entry per spectrum; ``n_spec`` entries when it is given) or None"""
@@ -715,7 +749,7 @@ class PyAscore:
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
                     recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=False, markers=None,
-                    quant=None, peptidoform_quant=None):
+                    quant=None, peptidoform_quant=None, purity=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -904,6 +938,19 @@ class PyAscore:
         ``peptidoform_quant_reduce`` or ``pyascore_amd.rollup.merge_peptidoform_quant``; ``pyascore_amd.rollup.peptidoform_quant``
         gives the same bytes on the host.
 
+        ``purity=dict(ms1_mz=, ms1_intensity=, ms1_peak_off=, survey=, precursor_mz=, precursor_charge=, window_lo=, window_hi=,
+        tol=0.0, tol_ppm=10.0, isotopes=3, below=0, step=, gate=None)`` adds ``purity`` (``pyascore_amd.rollup.PURITY_DTYPE``, the
+        48-byte ``pya_purity``, shape ``[n_spectra]``): per spectrum the intensity of its isolation window in the survey (MS1)
+        spectrum ``survey`` names and the part of it at the selected m/z and its isotope positions (``pya_purity_params``;
+        ``pyascore_amd.rollup.survey_index`` finds ``survey``, ``purity_ratio`` divides).  One entry per spectrum, as ``markers=``
+        has its precursors.  It is handled behind ``markers=`` and in front of ``channels=``: without ``gate`` every other result
+        of the call is bit-equal with and without it.  ``gate=dict(threshold=, keep_unknown=True)`` also adds ``purity_pass``
+        (uint8 ``[n_spectra]``) and sends the matrix of ``quant=`` / ``peptidoform_quant=`` -- given, or made from ``markers=``;
+        one row per spectrum -- through ``pyascore_amd.rollup.purity_gate`` on the host, where the matrix is at that point: the
+        readings of a failing spectrum become NaN, and ``purity_pass`` is ANDed into the ``select`` of a ``channels=`` that
+        normalizes.  A ``gate`` without ``quant=`` / ``peptidoform_quant=`` is a ValueError.  A caller whose spectra are resident
+        uses ``pyascore_amd.device.purity`` / ``purity_gate``; ``pyascore_amd.rollup.purity`` gives the same bytes on the host.
+
         ``coverage=True`` adds ``coverage`` (``COVERAGE_DTYPE``, the 64-byte ``pya_coverage``, shape ``[n]``): per PSM the ion
         current of its spectrum and the part of it that the matched fragments of the reported localisation explain, in all and
         from either terminus, beside peak, fragment and bond counts (``pyascore_amd.rollup.coverage_ratios`` makes the ratios,
@@ -921,7 +968,7 @@ class PyAscore:
                         site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup, peptidoforms=peptidoforms,
                         mz_profile=mz_profile, recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip,
                         centroid=centroid, coverage=coverage, markers=markers, quant=quant,
-                        peptidoform_quant=peptidoform_quant)
+                        peptidoform_quant=peptidoform_quant, purity=purity)
             rest.update(changed)
             if done is not None:
                 rest[done] = None
@@ -929,6 +976,9 @@ class PyAscore:
 
         channel_reqs = {name: _channels_request(name, req, markers)
                         for name, req in (("quant", quant), ("peptidoform_quant", peptidoform_quant))}
+        if purity is not None and purity is not False:
+            # (refused before anything is launched, whatever stands in front of it)
+            purity_req = _purity_request(purity, _n_spectra(batch), isinstance(quant, dict) or isinstance(peptidoform_quant, dict))
         if centroid is not None and centroid is not False:
             params, select = _centroid_request(centroid, _n_spectra(batch))
             return again("centroid", self.centroid_spectra(batch["mz"], batch["intensity"], _batch_peak_off(batch), params, select))
@@ -941,6 +991,36 @@ class PyAscore:
                     changed[name] = _marker_channels(name, req, params, records, batch.get("spec_of"))
             res = again("markers", (batch["mz"], batch["intensity"], batch["peak_off"]), **changed)
             res["markers"], res["marker_spectra"] = records, spectra
+            return res
+        if purity is not None and purity is not False:
+            # (behind markers=: the matrix is there by now; in front of channels=, which corrects what the gate leaves)
+            from .rollup import purity_gate
+            params, survey_spectra, queries, gate = purity_req
+            records, _ = self.precursor_purity(*survey_spectra, *queries, params)
+            changed, extra = {}, {"purity": records}
+            if gate is not None:
+                passed, _ = purity_gate(records, *gate)
+                extra["purity_pass"] = passed
+                for name, req in (("quant", quant), ("peptidoform_quant", peptidoform_quant)):
+                    if not isinstance(req, dict):
+                        continue
+                    if req.get("values") is None:
+                        raise ValueError(name + ": values is missing (a float64 matrix, one row per spectrum and one column per channel)")
+                    try:
+                        values = np.ascontiguousarray(req["values"], np.float64)
+                    except (TypeError, ValueError):
+                        raise ValueError(name + ": values is a matrix of numbers") from None
+                    if values.ndim != 2 or values.shape[0] != records.size:
+                        raise ValueError(name + ": beside a purity gate values has one row per spectrum, as the purity records have")
+                    req = dict(req, values=purity_gate(records, *gate, values=values)[1])
+                    ch = channel_reqs[name]
+                    if ch is not None and ch["normalize"]:
+                        if ch["select"] is not None and ch["select"].size != passed.size:
+                            raise ValueError(name + ": channels: select is one boolean per row of values")
+                        req["channels"] = dict(req["channels"], select=passed if ch["select"] is None else passed & ch["select"])
+                    changed[name] = req
+            res = again("purity", (batch["mz"], batch["intensity"], batch["peak_off"]), **changed)
+            res.update(extra)
             return res
         if any(ch is not None for ch in channel_reqs.values()):
             # (behind markers=: the matrix is there by now; in front of everything that scores)
@@ -1531,6 +1611,54 @@ class PyAscore:
             if rc:
                 self._raise(rc)
         return records, spectra, (int(c.over[0]), None if not c.over[0] else 0xFFFFFFFF - int(c.over[1]))
+
+    def precursor_purity(self, ms1_mz, ms1_intensity, ms1_peak_off, survey, precursor_mz, precursor_charge, window_lo, window_hi, params):
+        """The precursor purity of isolation windows, read off survey spectra on the device (``pya_purity_spectra_host``; the rule
+        is ``pya_purity_params``'s in include/pyascore_hip.h): ``ms1_mz`` / ``ms1_intensity`` / ``ms1_peak_off`` the survey (MS1)
+        spectra as ``deisotope_spectra`` takes spectra; per query (one per MS2 spectrum) ``survey`` the index of its survey
+        spectrum (negative: none), ``precursor_mz`` / ``precursor_charge`` and ``window_lo`` / ``window_hi``, the absolute m/z
+        bounds of the isolation window; ``params`` of ``pyascore_amd.rollup.purity_params``.  Returns ``(records, over)``:
+        ``pyascore_amd.rollup.PURITY_DTYPE[n_query]`` and ``over = (count, first)`` for the queries whose ``survey`` lies beyond
+        the survey spectra (zero records), ``(0, None)`` when there is none.  The survey spectra and the queries are uploaded
+        once and only the records come back.  ``pyascore_amd.rollup.purity`` gives the same bytes on the host."""
+        from .rollup import PURITY_DTYPE, purity_c_params, purity_queries
+        c_params = purity_c_params(params)
+        c = _transform_call("precursor_purity", ms1_mz, ms1_intensity, ms1_peak_off)
+        sv, pm, pz, wl, wh = purity_queries(survey, precursor_mz, precursor_charge, window_lo, window_hi, "precursor_purity")
+        if sv.size > 0xFFFFFFFE:
+            raise ValueError("precursor_purity: more than 2^32 - 2 queries")
+        records = np.zeros(sv.size, PURITY_DTYPE)
+        if sv.size:
+            rc = self._lib.pya_purity_spectra_host(self._h, C.byref(c.t_in), _as_ptr(c.peak_off), c.n_spec, _as_ptr(sv), _as_ptr(pm), _as_ptr(pz),
+                                                   _as_ptr(wl), _as_ptr(wh), sv.size, C.byref(c_params), _as_ptr(records), _as_ptr(c.over))
+            if rc:
+                self._raise(rc)
+        return records, (int(c.over[0]), None if not c.over[0] else 0xFFFFFFFF - int(c.over[1]))
+
+    def purity_gate(self, records, threshold, keep_unknown=True, values=None):
+        """THE GATE of the precursor purity on the device (``pya_purity_gate``): ``records`` ``PURITY_DTYPE[n_rows]``,
+        ``threshold`` in 0 .. 1, ``values`` float64 ``[n_rows, n_channels]`` or None.  Returns ``(select, values)`` as
+        ``pyascore_amd.rollup.purity_gate`` does, with the same bytes: one upload, one launch, one download -- the host
+        function is the cheaper one for host arrays; this form is there for parity with the resident chain
+        (``pyascore_amd.device.purity_gate``)."""
+        import torch
+        from . import device as dev
+        from .rollup import PURITY_DTYPE, check_purity_gate
+        t, keep = check_purity_gate(threshold, keep_unknown)
+        rec = np.ascontiguousarray(records, PURITY_DTYPE)
+        if rec.ndim != 1:
+            raise ValueError("purity_gate: records is one PURITY_DTYPE record per row")
+        device = torch.device("cuda", self.device)
+        d_rec = torch.from_numpy(rec.view(np.uint8).reshape(rec.size, PURITY_DTYPE.itemsize)).to(device)
+        d_values = None
+        if values is not None:
+            v = np.ascontiguousarray(values, np.float64)
+            if v.ndim != 2 or v.shape[0] != rec.size:
+                raise ValueError("purity_gate: values is a float64 matrix with one row per record")
+            d_values = torch.from_numpy(v).to(device)
+        out, select = dev.purity_gate(self, d_rec, t, keep, d_values, select=True)
+        torch.cuda.synchronize(device)
+        return select.cpu().numpy(), None if out is None else out.cpu().numpy()
 
     def centroid_spectra(self, mz, intensity, peak_off, params, select=None):
         """Centroided spectra, picked on the device (``pya_centroid_spectra_host``; the rule is ``pya_centroid_params``'s in

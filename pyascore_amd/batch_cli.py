@@ -198,7 +198,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              sites=None, probs=False, ranked=None, ranked_depth=5, site_table=None, site_table_threshold=0.75,
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
              recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=None, markers=None,
-             marker_rows=None, site_quant=None, site_quant_rows=None, peptidoform_quant=None, peptidoform_quant_rows=None, channels=None):
+             marker_rows=None, site_quant=None, site_quant_rows=None, peptidoform_quant=None, peptidoform_quant_rows=None, channels=None,
+             purity=None, purity_rows=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -261,7 +262,17 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     ``channels``: ``dict(matrix=, normalize=)`` as the ``channels=`` entry of ``PyAscore.score_batch(quant=...)`` takes it, without
     ``select``: the reporter matrix is corrected for the lot's isotope impurities (``matrix``, of as many channels as ``markers``
     has fixed targets) and / or brought to equal column totals before ``site_quant`` and ``peptidoform_quant`` sum it; it needs
-    one of the two."""
+    one of the two.
+    ``purity``: ``dict(survey=, tol=, tol_ppm=, isotopes=, below=, window=None, threshold=None, keep_unknown=True)``: ``survey`` the
+    MS1 records of the spectrum file (``ingest.SpectraParser(..., ms_level=1).to_list()``), the rule as
+    ``pyascore_amd.rollup.purity_params`` takes it, ``window`` the ``(lower, upper)`` offsets around the precursor m/z used where
+    a spectrum's record declares no ``isolation``; the survey scan of a spectrum is its ``parent_scan`` where the file names one,
+    else the last survey scan in front of it (``pyascore_amd.rollup.survey_index``).  ``purity_rows``: the list that then
+    receives one ``[scan] + purity_fields`` row per picked PSM (``write_purity_tsv``).  With ``threshold`` the gate of
+    ``PyAscore.score_batch(purity=dict(gate=...))`` is applied to what ``site_quant`` / ``peptidoform_quant`` sum; it needs one of
+    them."""
+    if purity is not None:                                 # (a bad request is refused before anything is read or scored)
+        purity_rule, purity_window, purity_gate = purity_request(purity, purity_rows, site_quant is not None or peptidoform_quant is not None)
     if channels is not None:                               # (a bad request is refused before anything is read or scored)
         from .ascore import _channels_request
         if site_quant is None and peptidoform_quant is None:
@@ -344,6 +355,8 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     if markers is not None:
         prec_mz, prec_z = hit_precursors(picked, scans)
         stages["markers"] = dict(markers, precursor_mz=prec_mz, precursor_charge=prec_z)
+    if purity is not None:
+        stages["purity"] = purity_stage(picked, scans, spectra_map, purity["survey"], purity_rule, purity_window, purity_gate)
     corrected = {} if channels is None else dict(channels=dict(channels))
     if site_quant is not None:
         stages["quant"] = dict(site_quant, values=None, **corrected)
@@ -414,6 +427,12 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         if markers is not None:                  # (the records are per spectrum: the hits of a scan share its row)
             spec = i if batch.get("spec_of") is None else int(batch["spec_of"][i])
             marker_rows.append([scans[i]] + marker_fields(res["markers"][spec], res["marker_spectra"][spec]))
+        if purity is not None:                   # (per spectrum, as the marker records)
+            spec = i if batch.get("spec_of") is None else int(batch["spec_of"][i])
+            q = stages["purity"]
+            survey_scan = int(purity["survey"][int(q["survey"][spec])]["scan"]) if q["survey"][spec] >= 0 else ""
+            purity_rows.append([scans[i], survey_scan, float(q["window_lo"][spec]), float(q["window_hi"][spec])] +
+                               purity_fields(res["purity"][spec]))
         if ranked is not None:
             ranked.extend([scans[i], hit] + ranked_fields(rk[i, r], rk[i, 0], rk_seqs[i * rk.shape[1] + r])
                           for r in range(int(ranked_lists.lengths(rk[i])[0])))
@@ -692,6 +711,93 @@ def write_coverage_tsv(coverage_rows, path):
         out.write("\t".join(COVERAGE_COLUMNS) + "\n")
         for row in coverage_rows:
             out.write("\t".join("%s" % f for f in row) + "\n")
+
+
+def purity_request(purity, purity_rows, have_quant):
+    """``localize(purity=...)`` checked: ``(rule, window, gate)`` -- the dict of ``pyascore_amd.rollup.purity_params``, the
+    ``(lower, upper)`` offsets or None, and ``dict(threshold=, keep_unknown=)`` or None"""
+    names = ("survey", "tol", "tol_ppm", "isotopes", "below", "step", "window", "threshold", "keep_unknown")
+    if not isinstance(purity, dict) or set(purity) - set(names) or purity.get("survey") is None or purity_rows is None:
+        raise ValueError("purity takes a dict of " + ", ".join(names) + " beside a list purity_rows; survey is the MS1 records")
+    try:
+        rule = site_rollup.purity_params(**{k: purity[k] for k in ("tol", "tol_ppm", "isotopes", "below", "step") if purity.get(k) is not None})
+    except TypeError:
+        raise ValueError("purity: tol, tol_ppm and step are numbers, isotopes and below integers") from None
+    window = purity.get("window")
+    if window is not None:
+        try:
+            window = tuple(float(v) for v in window)
+        except (TypeError, ValueError):
+            window = ()
+        if len(window) != 2 or not all(np.isfinite(v) and v >= 0.0 for v in window):
+            raise ValueError("purity: window is a pair of offsets (lower, upper), finite and >= 0")
+    gate = None
+    if purity.get("threshold") is not None:
+        t, keep = site_rollup.check_purity_gate(purity["threshold"], purity.get("keep_unknown", True), "purity")
+        if not have_quant:
+            raise ValueError("purity: threshold gates what site_quant and peptidoform_quant sum: it needs one of them")
+        gate = dict(threshold=t, keep_unknown=keep)
+    elif purity.get("keep_unknown", True) is not True:
+        raise ValueError("purity: keep_unknown goes with threshold")
+    return rule, window, gate
+
+
+def purity_stage(picked, scans, spectra_map, survey, rule, window, gate):
+    """The ``purity=`` request of ``PyAscore.score_batch`` for the spectra of ``pack_hits(picked, scans)``, in its order: the
+    survey records ``survey`` packed as one CSR set, the survey spectrum of every MS2 spectrum
+    (``pyascore_amd.rollup.survey_index``: its ``parent_scan``, else the last survey scan in front of it) and its isolation
+    window -- the record's ``isolation`` as ``target - lower .. target + upper``, else the precursor m/z with the offsets
+    ``window``, else NaN bounds: an inactive query."""
+    survey = list(survey)
+    lens = [np.size(r["mz_values"]) for r in survey]
+    ms1_mz = np.concatenate([np.asarray(r["mz_values"]) for r in survey]) if survey else np.zeros(0)
+    ms1_it = np.concatenate([np.asarray(r["intensity_values"]) for r in survey]) if survey else np.zeros(0)
+    spec_scans, parents, lo, hi = [], [], [], []
+    for i, psm in enumerate(picked):
+        if i and scans[i] == scans[i - 1] and psm["mz"] is picked[i - 1]["mz"] and psm["intensity"] is picked[i - 1]["intensity"]:
+            continue
+        rec = spectra_map[scans[i]]
+        spec_scans.append(scans[i])
+        parents.append(rec.get("parent_scan"))
+        iso, pm = rec.get("isolation"), rec.get("precursor_mz")
+        if iso is not None:
+            lo.append(float(iso[0]) - float(iso[1]))
+            hi.append(float(iso[0]) + float(iso[2]))
+        elif window is not None and pm is not None:
+            lo.append(float(pm) - window[0])
+            hi.append(float(pm) + window[1])
+        else:
+            lo.append(float("nan"))
+            hi.append(float("nan"))
+    prec_mz, prec_z = hit_precursors(picked, scans)
+    stage = dict(rule, ms1_mz=ms1_mz, ms1_intensity=ms1_it, ms1_peak_off=np.concatenate([[0], np.cumsum(lens)]).astype(np.int64),
+                 survey=site_rollup.survey_index([r["scan"] for r in survey], spec_scans, parents), precursor_mz=prec_mz,
+                 precursor_charge=prec_z, window_lo=np.asarray(lo, np.float64), window_hi=np.asarray(hi, np.float64))
+    if gate is not None:
+        stage["gate"] = dict(gate)
+    return stage
+
+
+PURITY_COLUMNS = ["Scan", "SurveyScan", "WindowLo", "WindowHi", "Window", "Precursor", "Ratio", "Peaks", "PrecursorPeaks", "IsoHit",
+                  "OtherMz", "OtherIntensity"]
+
+
+def purity_fields(rec):
+    """One ``PURITY_DTYPE`` record as the fields behind the window bounds of the ``--purity`` table: Window, Precursor, Ratio
+    (empty where the window held nothing), Peaks, PrecursorPeaks, IsoHit (one 0 / 1 per centre, lowest first) and the m/z and
+    intensity of the most intense other peak (empty where there is none)."""
+    ratio = float(site_rollup.purity_ratio(np.asarray([rec], site_rollup.PURITY_DTYPE))[0])
+    other = float(rec["other_intensity"]) > 0.0
+    return [float(rec["window"]), float(rec["precursor"]), "" if ratio != ratio else ratio, int(rec["n_window"]), int(rec["n_precursor"]),
+            format(int(rec["iso_hit"]), "b")[::-1], float(rec["other_mz"]) if other else "", float(rec["other_intensity"]) if other else ""]
+
+
+def write_purity_tsv(purity_rows, path):
+    """The ``--purity`` table: the rows ``localize(..., purity=dict(...), purity_rows=[])`` collected, under ``PURITY_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(PURITY_COLUMNS) + "\n")
+        for row in purity_rows:
+            out.write("\t".join(str(v) for v in row) + "\n")
 
 
 def marker_columns(mz=(), losses=()):

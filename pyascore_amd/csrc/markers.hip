@@ -23,14 +23,7 @@
  * Every 64-bit mask is shifted as a 64-bit value: target 63 is a target like any other.  value[] arrives by value in scalar
  * registers and has no lane-indexed form: lane t picks its entry by an unrolled chain of selects, once per wavefront. */
 #include "deiso_rule.hip.h"
-
-/* a double held by lane `src` (wave-uniform), to every lane: two v_readlane */
-DEV double marker_lane_f64(double v, int src) {
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), src);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | (uint64_t)lo));
-}
+#include "lane_f64.hip.h"
 
 /* the largest and the smallest of v over the wavefront, in every lane (v is no NaN) */
 DEV double marker_wave_max(double v) {

@@ -966,6 +966,96 @@ def marker_values(scorer, d_markers, channel_mask=None, out=None):
     return out
 
 
+def purity(scorer, d_ms1_mz, d_ms1_intensity, ms1_peak_off, d_survey, d_prec_mz, d_prec_z, d_win_lo, d_win_hi, params, out=None):
+    """The precursor purity of isolation windows over survey spectra that live on the device (``pya_purity_spectra``; the rule
+    is ``pya_purity_params``'s in include/pyascore_hip.h): ``d_ms1_mz`` / ``d_ms1_intensity`` / ``ms1_peak_off`` the survey
+    (MS1) spectra as ``deisotope`` takes spectra; ``d_survey`` (int64), ``d_prec_mz`` (float64), ``d_prec_z`` (int32),
+    ``d_win_lo`` / ``d_win_hi`` (float64) one entry per query as device tensors or host arrays (a host array is uploaded);
+    ``params`` of ``pyascore_amd.rollup.purity_params``.  ``out``: a contiguous ``uint8`` device tensor ``[n_query, 48]`` to write
+    into, new when None.  Returns ``(d_purity, d_over)``: the records (``purity_records`` reads a host copy) and an ``int32``
+    tensor of two words (the queries whose survey index lies beyond the survey spectra, and 0xffffffff minus the first of
+    them).  READ-ONLY; one launch on torch's current stream; nothing waits on the host.  ``pyascore_amd.rollup.purity`` gives
+    the same bytes."""
+    import torch
+    from .rollup import PURITY_DTYPE, purity_c_params
+    c_params, device, peak_off, n_survey = _transform_inputs(scorer, purity_c_params, params, d_ms1_mz, d_ms1_intensity, ms1_peak_off)
+    per_query = []
+    for t, np_dtype, dtype in ((d_survey, np.int64, torch.int64), (d_prec_mz, np.float64, torch.float64), (d_prec_z, np.int32, torch.int32),
+                               (d_win_lo, np.float64, torch.float64), (d_win_hi, np.float64, torch.float64)):
+        if not isinstance(t, torch.Tensor):
+            t = _upload(t, np_dtype, device)
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda or (per_query and t.numel() != per_query[0].numel()):
+            raise ValueError("d_survey (int64), d_prec_mz (float64), d_prec_z (int32), d_win_lo and d_win_hi (float64) are contiguous "
+                             "device tensors with one entry per query")
+        per_query.append(t)
+    n_query = per_query[0].numel()
+    shape = (n_query, PURITY_DTYPE.itemsize)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=device)
+        over = torch.zeros(2, dtype=torch.int32, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("out must be a contiguous uint8 device tensor of shape %r" % (shape,))
+    t_in = _lib.TypedSpectra(d_ms1_mz.data_ptr(), d_ms1_intensity.data_ptr(), _lib.spectrum_type(d_ms1_mz.dtype),
+                             _lib.spectrum_type(d_ms1_intensity.dtype))
+    rc = scorer._lib.pya_purity_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_survey, d_ms1_mz.numel(),
+                                        *(t.data_ptr() if n_query else None for t in per_query), n_query, C.byref(c_params),
+                                        torch.cuda.current_stream(device).cuda_stream, out.data_ptr() if n_query else None, over.data_ptr())
+    if rc:
+        scorer._raise(rc)
+    # (the caching allocator keeps uploaded queries for this stream until later work on the stream is done with them)
+    return out, over
+
+
+def purity_gate(scorer, d_purity, threshold, keep_unknown=True, d_values=None, out=None, select=False):
+    """THE GATE of the precursor purity over records that live on the device (``pya_purity_gate``): ``d_purity`` the tensor of
+    ``purity`` (uint8 ``[n_rows, 48]``), ``threshold`` in 0 .. 1, ``d_values`` a contiguous ``torch.float64`` device tensor
+    ``[n_rows, n_channels]`` (what ``marker_values`` returns) or None.  ``out``: such a tensor to write into -- it may be
+    ``d_values`` itself: in place --, new when None.  ``select``: True for a new ``uint8`` tensor ``[n_rows]``, or such a tensor,
+    to take 1 / 0 per row (what ``channel_sums(select=)`` takes); False: none.  Returns ``(out, select)``, None where not asked
+    for: the readings of a passing row copied bit for bit, those of a failing row NaN.  One launch on torch's current stream;
+    nothing waits on the host.  ``pyascore_amd.rollup.purity_gate`` gives the same bytes."""
+    import torch
+    from .rollup import PURITY_DTYPE, check_purity_gate
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    t, keep = check_purity_gate(threshold, keep_unknown)
+    if d_purity.dim() != 2 or d_purity.shape[1] != PURITY_DTYPE.itemsize:
+        raise ValueError("d_purity must be a contiguous uint8 device tensor of shape (n_rows, %d)" % PURITY_DTYPE.itemsize)
+    _channel_tensor(d_purity, None, torch.uint8, "d_purity")
+    n_rows = int(d_purity.shape[0])
+    device = d_purity.device
+    n_ch = 0
+    if d_values is not None:
+        if d_values.dim() != 2 or d_values.shape[0] != n_rows or not 1 <= d_values.shape[1] <= 64:
+            raise ValueError("d_values must be a float64 device tensor of shape (n_rows, n_channels), n_channels in 1 .. 64")
+        _channel_tensor(d_values, None, torch.float64, "d_values")
+        n_ch = int(d_values.shape[1])
+        if out is None:
+            with torch.cuda.device(device):
+                out = torch.empty((n_rows, n_ch), dtype=torch.float64, device=device)
+        _channel_tensor(out, (n_rows, n_ch), torch.float64, "out")
+    elif out is not None:
+        raise ValueError("out goes with d_values")
+    if select is True:
+        with torch.cuda.device(device):
+            select = torch.empty(n_rows, dtype=torch.uint8, device=device)
+    elif select is False or select is None:
+        select = None
+    if select is not None:
+        _channel_tensor(select, (n_rows,), torch.uint8, "select")
+    if d_values is None and select is None:
+        raise ValueError("purity_gate: neither d_values nor select")
+    if not n_rows:                                           # (an empty tensor may have no address to pass)
+        return out, select
+    rc = scorer._lib.pya_purity_gate(scorer._h, d_purity.data_ptr(), n_rows, t, 1 if keep else 0, d_values.data_ptr() if n_ch else None, n_ch,
+                                     out.data_ptr() if n_ch else None, None if select is None else select.data_ptr(),
+                                     torch.cuda.current_stream(device).cuda_stream)
+    if rc:
+        scorer._raise(rc)
+    return out, select
+
+
 def _channel_tensor(t, shape, dtype, what):
     if t.dtype != dtype or (shape is not None and tuple(t.shape) != shape) or not t.is_contiguous() or not t.is_cuda:
         raise ValueError("%s must be a contiguous %s device tensor%s" % (what, str(dtype).replace("torch.", ""),
@@ -1093,6 +1183,16 @@ def marker_records(raw):
     if a.ndim != 3 or a.shape[2] != MARKER_DTYPE.itemsize:
         raise ValueError("expected a uint8 array of shape (n_spectra, n_targets, %d)" % MARKER_DTYPE.itemsize)
     return a.view(MARKER_DTYPE).reshape(a.shape[0], a.shape[1])
+
+
+def purity_records(raw):
+    """A host copy of the tensor of ``purity`` (``.cpu().numpy()``, uint8 ``[n_query, 48]``) as the structured array
+    ``PyAscore.score_batch(..., purity=...)`` returns in ``purity``; a view, no copy."""
+    from .rollup import PURITY_DTYPE
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != PURITY_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % PURITY_DTYPE.itemsize)
+    return a.view(PURITY_DTYPE).reshape(a.shape[0])
 
 
 def marker_spectrum_records(raw):

@@ -7,7 +7,8 @@ percolatorTXT, mokapotTXT) -- and :class:`MassCorrector` with nothing but the st
 (``xml.etree`` streaming, ``base64``, ``zlib``, ``csv``) and numpy.  Output records have the
 reference's schema, field for field:
 
-* spectra: ``{scan, ms_level, precursor_mz, precursor_charge, mz_values f64, intensity_values f64, profile}``,
+* spectra: ``{scan, ms_level, precursor_mz, precursor_charge, mz_values f64, intensity_values f64, profile}``
+  (and, beyond the reference's schema, ``isolation`` and ``parent_scan``),
   sorted by scan (spec_parsers.py:243-282);
 * identifications: ``{scan, charge_state, score, peptide, mod_positions, mod_masses}`` in file order
   within a spectrum, spectra sorted by scan (id_parsers.py:735-815).
@@ -235,10 +236,16 @@ def _as_native(values, width, native_precision):
 _SPECTRUM_MODE = {"MS:1000128": True, "MS:1000127": False}
 
 
+# the three cvParams of an <isolationWindow>, as the places of the record's "isolation": target m/z, lower offset, upper offset
+_ISOLATION = {"MS:1000827": 0, "MS:1000828": 1, "MS:1000829": 2}
+
+
 class MzMLExtractor:
     """<spectrum> element -> record (spec_parsers.py:49-113).  ``native_precision``: each array keeps the precision its
     binaryDataArray declares instead of being widened to float64.  ``profile``: True for a spectrum the file declares
-    profile-mode (cvParam MS:1000128), False for a centroided one (MS:1000127), None where it says neither."""
+    profile-mode (cvParam MS:1000128), False for a centroided one (MS:1000127), None where it says neither.  ``isolation``:
+    ``(target, lower offset, upper offset)`` of the precursor's isolation window (cvParams MS:1000827 / 8 / 9), None where
+    the file does not give all three; ``parent_scan``: the ``scan=N`` of the precursor's ``spectrumRef``, None without one."""
 
     def __init__(self, native_precision=False):
         self.native_precision = native_precision
@@ -258,6 +265,7 @@ class MzMLExtractor:
                 raise AttributeError("no 'scan=' in spectrum id %r" % sid)
         ms_level = int(params["ms level"]) if "ms level" in params else 0
         precursor_mz, precursor_charge = None, None
+        isolation, parent_scan = None, None
         plist = _first(spectrum, "precursorList")
         if plist is not None:
             if int(plist.get("count", "1")) > 1:
@@ -269,6 +277,22 @@ class MzMLExtractor:
                     found[cv.get("name")] = cv.get("value")
             if "selected ion m/z" in found and "charge state" in found:
                 precursor_mz, precursor_charge = float(found["selected ion m/z"]), int(found["charge state"])
+            precursor = _first(plist, "precursor")
+            if precursor is not None:
+                ref = precursor.get("spectrumRef")
+                if ref:
+                    parent_scan = _first_scan_number(ref, liberal=False)
+                window = _first(precursor, "isolationWindow")
+                got_w = {}
+                if window is not None:
+                    for cv in _children(window, "cvParam"):
+                        if cv.get("accession") in _ISOLATION:
+                            try:
+                                got_w[_ISOLATION[cv.get("accession")]] = float(cv.get("value"))
+                            except (TypeError, ValueError):
+                                pass
+                if len(got_w) == 3:
+                    isolation = (got_w[0], got_w[1], got_w[2])
         mz, inten = _EMPTY, _EMPTY
         arrays = _first(spectrum, "binaryDataArrayList")
         got = {}
@@ -285,13 +309,15 @@ class MzMLExtractor:
         if "mz" in got and "int" in got:
             mz, inten = got["mz"], got["int"]
         return {"scan": scan, "ms_level": ms_level, "precursor_mz": precursor_mz,
-                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile}
+                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile,
+                "isolation": isolation, "parent_scan": parent_scan}
 
 
 class MzXMLExtractor:
     """<scan> element -> record (spec_parsers.py:115-172).  ``native_precision``: both arrays keep the precision the
     <peaks> element declares (32 unless it says 64) instead of being widened to float64.  ``profile``: False where the
-    scan's ``centroided`` attribute is 1, True where it is 0, None without it."""
+    scan's ``centroided`` attribute is 1, True where it is 0, None without it.  ``isolation``: ``(precursor m/z, w / 2, w / 2)``
+    from the precursor's ``windowWideness`` w, None without it; ``parent_scan``: its ``precursorScanNum``, None without it."""
 
     def __init__(self, native_precision=False):
         self.native_precision = native_precision
@@ -300,6 +326,7 @@ class MzXMLExtractor:
         num = int(scan.get("num")) if scan.get("num") is not None else -1
         ms_level = int(scan.get("msLevel")) if scan.get("msLevel") is not None else 0
         precursor_mz, precursor_charge = None, None
+        isolation, parent_scan = None, None
         precursors = _children(scan, "precursorMz")
         if precursors:
             if len(precursors) > 1:
@@ -307,6 +334,15 @@ class MzXMLExtractor:
             p = precursors[0]
             if p.get("precursorCharge") is not None:
                 precursor_mz, precursor_charge = float(p.text), int(p.get("precursorCharge"))
+            try:
+                half = float(p.get("windowWideness")) / 2.0
+                isolation = (float(p.text), half, half)
+            except (TypeError, ValueError):
+                pass
+            try:
+                parent_scan = int(p.get("precursorScanNum"))
+            except (TypeError, ValueError):
+                pass
         mz, inten = _EMPTY, _EMPTY
         peaks = _first(scan, "peaks")
         if peaks is not None and (peaks.text or "").strip():
@@ -318,7 +354,8 @@ class MzXMLExtractor:
         centroided = (scan.get("centroided") or "").strip().lower()
         profile = False if centroided in ("1", "true") else (True if centroided in ("0", "false") else None)
         return {"scan": num, "ms_level": ms_level, "precursor_mz": precursor_mz,
-                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile}
+                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile,
+                "isolation": isolation, "parent_scan": parent_scan}
 
 
 def _mzxml_scans(path):

@@ -100,6 +100,10 @@ MARKER_SPECTRUM_DTYPE = np.dtype(_lib.MARKER_SPECTRUM_DTYPE)    # pya_marker_spe
 assert MARKER_DTYPE.itemsize == 24 and MARKER_SPECTRUM_DTYPE.itemsize == 32
 MARKER_MAX_TARGETS = _lib.PYA_MARKER_MAX_TARGETS
 MARKER_ACTIVE, MARKER_PICKED = _lib.PYA_MARKER_ACTIVE, _lib.PYA_MARKER_PICKED
+PURITY_DTYPE = np.dtype(_lib.PURITY_DTYPE)          # pya_purity, 48 bytes
+assert PURITY_DTYPE.itemsize == 48
+PURITY_MAX_CENTRES, PURITY_MAX_BELOW = _lib.PYA_PURITY_MAX_CENTRES, _lib.PYA_PURITY_MAX_BELOW
+PURITY_ACTIVE, PURITY_SEEN = _lib.PYA_PURITY_ACTIVE, _lib.PYA_PURITY_SEEN
 SITE_QUANT_HEAD_DTYPE = np.dtype(_lib.SITE_QUANT_HEAD_DTYPE)   # pya_site_quant_head, 8 bytes
 SITE_QUANT_DTYPE = np.dtype(_lib.SITE_QUANT_DTYPE)             # pya_site_quant, 16 bytes
 assert SITE_QUANT_HEAD_DTYPE.itemsize == 8 and SITE_QUANT_DTYPE.itemsize == 16
@@ -1258,6 +1262,190 @@ def marker_matrix(records, field="intensity"):
     records = np.asarray(records, MARKER_DTYPE)
     picked = (records["flags"] & MARKER_PICKED) != 0
     return np.where(picked, records[field].astype(np.float64), np.nan)
+
+
+def purity_params(tol=0.0, tol_ppm=10.0, isotopes=3, below=0, step=STRIP_STEP):
+    """The parameters of the precursor-purity stage (``pya_purity_params``) as a dict: ``tol`` the half width of a centre's window
+    in m/z units and ``tol_ppm`` in ppm of the centre, added to it; ``isotopes`` the isotope positions above the selected m/z
+    that still count as the precursor, ``below`` those under it (0 .. 4: an instrument that picked the second isotope);
+    ``step`` the isotope spacing at charge 1.  The defaults are choices, not measurements.  ValueError where the library would
+    refuse."""
+    return check_purity_params(dict(tol=tol, tol_ppm=tol_ppm, step=step, below=below, isotopes=isotopes))
+
+
+def check_purity_params(params):
+    """``params`` (a dict as ``purity_params`` makes it) checked against the conditions of ``pya_purity_params``; returns it
+    with plain Python numbers."""
+    try:
+        out = dict(tol=float(params["tol"]), tol_ppm=float(params["tol_ppm"]), step=float(params["step"]), below=params["below"],
+                   isotopes=params["isotopes"])
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("purity: params is the dict of pyascore_amd.rollup.purity_params (tol, tol_ppm, step, below, isotopes)") from None
+    for name in ("tol", "tol_ppm"):
+        if not (np.isfinite(out[name]) and out[name] >= 0.0):
+            raise ValueError("purity: %s = %r is not a finite number >= 0" % (name, out[name]))
+    if not (np.isfinite(out["step"]) and out["step"] > 0.0):
+        raise ValueError("purity: step = %r is not finite and positive" % (out["step"],))
+    for name in ("below", "isotopes"):
+        v = out[name]
+        try:
+            ok = not isinstance(v, (bool, np.bool_)) and int(v) == v and int(v) >= 0
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("purity: %s = %r is not an integer >= 0" % (name, v))
+        out[name] = int(v)
+    if out["below"] > PURITY_MAX_BELOW:
+        raise ValueError("purity: below = %d is not in 0 .. %d" % (out["below"], PURITY_MAX_BELOW))
+    if out["below"] + 1 + out["isotopes"] > PURITY_MAX_CENTRES:
+        raise ValueError("purity: below + 1 + isotopes = %d centres are more than %d" % (out["below"] + 1 + out["isotopes"], PURITY_MAX_CENTRES))
+    return out
+
+
+def purity_c_params(params):
+    """``params`` as the ``pya_purity_params`` structure the library reads."""
+    p = check_purity_params(params)
+    return _lib.PurityParams(p["tol"], p["tol_ppm"], p["step"], p["below"], p["isotopes"], (_lib.C.c_uint32 * 2)(0, 0))
+
+
+def purity_queries(survey, prec_mz, prec_z, win_lo, win_hi, what="purity"):
+    """The five per-query arrays of the purity stage as the library takes them: ``(survey int64, prec_mz float64, prec_z int32,
+    win_lo float64, win_hi float64)``, contiguous and of one length.  ValueError otherwise."""
+    sv, pz = np.asarray(survey), np.asarray(prec_z)
+    try:
+        pm, wl, wh = (np.ascontiguousarray(a, np.float64) for a in (prec_mz, win_lo, win_hi))
+    except (TypeError, ValueError):
+        raise ValueError("%s: prec_mz, win_lo and win_hi are numbers, one per query" % what) from None
+    if (sv.size and sv.dtype.kind not in "iu") or (pz.size and pz.dtype.kind not in "iu"):
+        raise ValueError("%s: survey and prec_z are integers, one per query" % what)
+    if sv.ndim != 1 or any(a.shape != sv.shape for a in (pm, pz, wl, wh)):
+        raise ValueError("%s: survey, prec_mz, prec_z, win_lo and win_hi have one entry per query" % what)
+    if sv.size and (int(sv.max()) > 2 ** 63 - 1):
+        raise ValueError("%s: survey does not fit an int64" % what)
+    return (np.ascontiguousarray(sv, np.int64), pm, np.ascontiguousarray(np.clip(pz, -1, 0x7FFFFFFF), np.int32), wl, wh)
+
+
+def purity(ms1_mz, ms1_intensity, ms1_peak_off, survey, prec_mz, prec_z, win_lo, win_hi, params):
+    """The precursor purity of isolation windows: the rule of ``pya_purity_params``, operation for operation in float64 and
+    plain Python floats, so the bytes are those of ``pya_purity_spectra``.  ``ms1_mz`` / ``ms1_intensity``: the survey (MS1)
+    spectra, float64 or float32 (widened), ``ms1_peak_off[n_survey + 1]``; per query (one per MS2 spectrum) ``survey`` the index
+    of its survey spectrum (negative: none), ``prec_mz`` / ``prec_z`` the selected m/z and charge, ``win_lo`` / ``win_hi`` the
+    absolute m/z bounds of the isolation window; ``params`` of ``purity_params``.  Returns ``(records, over)``:
+    ``PURITY_DTYPE[n_query]`` -- ``window`` the summed intensity of the peaks with ``win_lo <= x <= win_hi`` and ``y > 0``,
+    ``precursor`` that of those inside a centre window (the selected m/z and its isotope positions), both summed in the order of
+    the survey spectrum, the most intense other peak, the counts, ``iso_hit`` and the flags -- and ``over = (count, first)`` for
+    the queries whose ``survey`` is ``>= n_survey`` (their records are zero), ``(0, None)`` when there is none.  The spectra are
+    only read.  ValueError where ``pya_purity_spectra_host`` returns ``PYA_ERR_ARG``."""
+    p = check_purity_params(params)
+    raw_mz, raw_it, rel = _transform_entry("purity", ms1_mz, ms1_intensity, ms1_peak_off)
+    n_survey = rel.size - 1
+    sv, pm, pz, wl, wh = purity_queries(survey, prec_mz, prec_z, win_lo, win_hi)
+    rec = np.zeros(sv.size, PURITY_DTYPE)
+    tol, ppm, step, below = p["tol"], p["tol_ppm"] * 1e-6, p["step"], p["below"]
+    usable = (pz >= 1) & (pz <= STRIP_MAX_CHARGE) & np.isfinite(pm) & (pm > 0.0)
+    with np.errstate(invalid="ignore"):
+        active = (sv >= 0) & usable & (wl <= wh) & np.isfinite(wl) & np.isfinite(wh)
+    beyond = active & (sv >= n_survey)
+    for q in np.flatnonzero(active & ~beyond):
+        a, b = int(rel[sv[q]]), int(rel[sv[q] + 1])
+        xs = raw_mz[a:b].astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            at = np.flatnonzero((wl[q] <= xs) & (xs <= wh[q]))
+        ys = raw_it[a:b][at].astype(np.float64)
+        d = step / float(int(pz[q]))
+        bounds = []
+        for i in range(-below, p["isotopes"] + 1):
+            c = float(pm[q]) + float(i) * d
+            w = tol + ppm * c
+            bounds.append((c - w, c + w))
+        window = precursor = ox = oy = 0.0
+        n_window = n_precursor = iso_hit = 0
+        have_other = False
+        for x, y in zip(xs[at].tolist(), ys.tolist()):                 # (index order: the order of the two sums)
+            if not y > 0.0:
+                continue
+            hit = sum(1 << k for k, (lo, hi) in enumerate(bounds) if lo <= x <= hi)
+            window = window + y
+            n_window += 1
+            if hit:
+                precursor = precursor + y
+                n_precursor += 1
+                iso_hit |= hit
+            elif not have_other or y > oy or (y == oy and x < ox):
+                ox, oy, have_other = x, y, True
+        rec[q] = (window, precursor, ox + 0.0 if have_other else 0.0, oy + 0.0 if have_other else 0.0, n_window, n_precursor, iso_hit,
+                  PURITY_ACTIVE | (PURITY_SEEN if n_precursor else 0))
+    first = np.flatnonzero(beyond)
+    return rec, (int(first.size), int(first[0]) if first.size else None)
+
+
+def purity_ratio(records):
+    """``precursor / window`` of ``PURITY_DTYPE`` records as float64, NaN where ``window`` is not > 0 (an inactive query, an
+    empty window): the number the record itself does not store."""
+    rec = np.asarray(records, PURITY_DTYPE)
+    out = np.full(rec.shape, np.nan)
+    known = rec["window"] > 0.0
+    with np.errstate(invalid="ignore"):
+        out[known] = rec["precursor"][known] / rec["window"][known]
+    return out
+
+
+def check_purity_gate(threshold, keep_unknown=True, what="purity_gate"):
+    """``(threshold, keep_unknown)`` of THE GATE checked: a number in [0, 1] and a boolean."""
+    try:
+        t = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError("%s: threshold is a number in 0 .. 1" % what) from None
+    if isinstance(threshold, (bool, np.bool_)) or not 0.0 <= t <= 1.0:
+        raise ValueError("%s: threshold = %r is not a number in 0 .. 1" % (what, threshold))
+    if not isinstance(keep_unknown, (bool, np.bool_)):
+        raise ValueError("%s: keep_unknown = %r is not a boolean" % (what, keep_unknown))
+    return t, bool(keep_unknown)
+
+
+def purity_gate(records, threshold, keep_unknown=True, values=None):
+    """THE GATE of ``pya_purity_params`` over ``PURITY_DTYPE`` records, the bytes of ``pya_purity_gate``: a row whose record is
+    active with ``window > 0`` passes iff ``precursor >= threshold * window`` (one multiplication, no division); any other row
+    passes iff ``keep_unknown``.  Returns ``(select, values)``: uint8 ``[n_rows]`` and, when ``values`` (float64 ``[n_rows,
+    n_channels]``) is given, a new matrix with the readings of the passing rows copied bit for bit and those of the failing rows
+    NaN (``marker_matrix``'s "no reading"), else None."""
+    t, keep = check_purity_gate(threshold, keep_unknown)
+    rec = np.asarray(records, PURITY_DTYPE)
+    if rec.ndim != 1:
+        raise ValueError("purity_gate: records is one PURITY_DTYPE record per row")
+    known = ((rec["flags"] & PURITY_ACTIVE) != 0) & (rec["window"] > 0.0)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ok = rec["precursor"] >= np.float64(t) * rec["window"]
+    select = np.where(known, ok, keep).astype(np.uint8)
+    if values is None:
+        return select, None
+    v = np.ascontiguousarray(values, np.float64)
+    if v.ndim != 2 or v.shape[0] != rec.size:
+        raise ValueError("purity_gate: values is a float64 matrix with one row per record")
+    out = v.copy()
+    out.view(np.uint64)[select == 0, :] = np.uint64(0x7FF8000000000000)
+    return select, out
+
+
+def survey_index(survey_scans, scans, parent_scans=None):
+    """The survey spectrum of every MS2 scan as an index into ``survey_scans`` (the scan numbers of the MS1 spectra in file
+    order, ascending): the one ``parent_scans`` names where the file names one that is among ``survey_scans`` (None or a
+    negative number: it names none), else the last survey scan in front of the MS2 scan, -1 when there is none.  int64
+    ``[len(scans)]``: the ``survey`` of ``purity``."""
+    sv = np.asarray(survey_scans, np.int64).reshape(-1)
+    sc = np.asarray(scans, np.int64).reshape(-1)
+    if sv.size > 1 and (np.diff(sv) <= 0).any():
+        raise ValueError("survey_index: survey_scans ascend")
+    out = np.searchsorted(sv, sc, side="left").astype(np.int64) - 1           # the last survey scan BEFORE the scan
+    if parent_scans is not None:
+        if len(parent_scans) != sc.size:
+            raise ValueError("survey_index: parent_scans has one entry per scan")
+        par = np.asarray([-1 if p is None else int(p) for p in parent_scans], np.int64)
+        at = np.searchsorted(sv, par, side="left")
+        named = (par >= 0) & (at < sv.size)
+        named[named] = sv[at[named]] == par[named]
+        out[named] = at[named]
+    return out
 
 
 def centroid_params(gap, gap_ppm=0.0, half_width=4, min_height=0.0, area=False):
