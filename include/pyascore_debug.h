@@ -41,6 +41,72 @@ int pya_set_debug(pya_handle *h, const char *key, const char *value);
  * No reference counterpart. */
 int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]);
 
+/* ---- the device building blocks, one at a time (csrc/debug_ops.hip; tests/test_gpu_device_ops.py) ----
+ * Test-only kernels around the functions of csrc/device_common.hip.h, lane_f64.hip.h, tile_sort.hip.h and the ion stage's
+ * scan, with the production headers included as they are.  Each call allocates what it needs, runs on the null stream and
+ * returns when the results are on the host.  No reference counterpart. */
+
+/* The peak lookup.  mz[n], rank[n]: a retained table as the binning leaves one -- n <= PYA_DEBUG_LOOKUP_MAX_N entries, every
+ * m/z finite and not below the one before, every rank below PYA_NO_MATCH = 15; mz_error in (0, 50) as pya_create takes it; query[n_query] any
+ * float32 bit patterns.  Anything else (a NULL array with a count above 0 too) is PYA_ERR_ARG and NOTHING IS LAUNCHED: the
+ * lookup's loops end at the +inf entries behind a table and must not see one production could not build.
+ * A wavefront stages the table in LDS (copy_peak_table, grid_build; LDS above 64 KB allowed as the production launches allow
+ * it) and leaves the grid in global memory; the queries are then looked up by wavefronts that stage it the same way, through
+ * the LDS table and through global_peak_table_at on the table and grid in global memory (behind whose last entry lie four
+ * entries at the last m/z with rank 0, which the global lookup reads and must mask).
+ *   out[4 q + 0]  match_rank_lds(query[q])
+ *   out[4 q + 1]  look4, finished by look_rest where more(); 255 where mz_error > 0.49 (look4 is not for those settings)
+ *   out[4 q + 2]  match_rank_global
+ *   out[4 q + 3]  more() of that look4 (0 / 1; 255 as above)
+ *   cells[0 .. 255] the grid, cells[256] last_cell (cells above last_cell are never read and hold anything) */
+#define PYA_DEBUG_LOOKUP_MAX_N 8192
+int pya_debug_lookup(pya_handle *h, const float *mz, const uint32_t *rank, uint32_t n, float mz_error, const float *query, uint32_t n_query,
+                     uint8_t *out, uint32_t cells[257]);
+
+/* One value per lane: out[i] = op(a[i], b[i]) for i < n, all arrays 64-bit words (a function's 32-bit arguments are the low
+ * halves, its 32-bit result is zero-extended).
+ *   PYA_DBG_FASTDIV        fastdiv(a, fastdiv_make(b))
+ *   PYA_DBG_CHARGE_MZ      the bits of charge_mz(a read as a double, z = b); b = 1 .. 255, else PYA_ERR_ARG
+ *   PYA_DBG_NTH_SET_BIT    nth_set_bit(mask a, n = b)
+ *   PYA_DBG_DEPOSIT_SITES  deposit_sites(bits a, site_mask b)
+ *   PYA_DBG_XCD_SLOT       xcd_slot(block a, blocks b)
+ *   PYA_DBG_NL_BUMP        nl_bump(state a, class b); b = 1 .. 16, else PYA_ERR_ARG
+ *   PYA_DBG_LUT_ROW        lut_row(a)
+ *   PYA_DBG_HIST           hist_add of the (b & 255) <= 16 ranks of 4 bits in a, lowest first, into an empty histogram; then
+ *                          with s = (b >> 8) & 255:  s < 16 hist_get(s),  16 / 17 / 18 the word a / b / c */
+enum { PYA_DBG_FASTDIV = 0, PYA_DBG_CHARGE_MZ, PYA_DBG_NTH_SET_BIT, PYA_DBG_DEPOSIT_SITES, PYA_DBG_XCD_SLOT, PYA_DBG_NL_BUMP,
+       PYA_DBG_LUT_ROW, PYA_DBG_HIST, PYA_DBG_LANE_OPS };
+int pya_debug_lane_ops(pya_handle *h, uint32_t op, const uint64_t *a, const uint64_t *b, uint64_t n, uint64_t *out);
+
+/* One full wavefront: in[PYA_DBG_WAVE_IN], out[PYA_DBG_WAVE_OUT] 64-bit words, lane l's value at in[l] (words no op reads or
+ * writes: ignored / 0).
+ *   PYA_DBG_WAVE_SUM_U64      out[l] = wave_sum_u64 as lane l has it
+ *   PYA_DBG_WAVE_MINMAX_F64   out[l], out[64 + l] = wave_min_f64, wave_max_f64 of the values read as doubles
+ *   PYA_DBG_MARKER_LANE_F64   out[64 s + l] = marker_lane_f64(value, s) as lane l has it, for every source lane s
+ *   PYA_DBG_ION_SCAN_U64      out[l] = ion_wave_excl_scan_u64 (csrc/ions.hip; values below 2^50), out[64 + l] its total
+ *   PYA_DBG_HIST_WAVE_SUM     the three words of lane l's histogram at in[l], in[64 + l], in[128 + l]; the sums likewise
+ *   PYA_DBG_SAME_DIGIT        out[l] = ts_same_digit(digit in[l], in = (in[64 + l] != 0)) */
+enum { PYA_DBG_WAVE_SUM_U64 = 0, PYA_DBG_WAVE_MINMAX_F64, PYA_DBG_MARKER_LANE_F64, PYA_DBG_ION_SCAN_U64, PYA_DBG_HIST_WAVE_SUM,
+       PYA_DBG_SAME_DIGIT, PYA_DBG_WAVE_OPS };
+#define PYA_DBG_WAVE_IN 192
+#define PYA_DBG_WAVE_OUT 4096
+int pya_debug_wave64(pya_handle *h, uint32_t op, const uint64_t *in, uint64_t *out);
+
+/* The scans of csrc/tile_sort.hip.h over two policies of the test kernels' own, entries as 32-bit words:
+ *   PYA_DBG_SCAN_ADD  one word, a + b (wraps);
+ *   PYA_DBG_SCAN_SEG  three words (v, f, last), associative and NOT commutative -- a before b:
+ *                     v = b.f ? b.v : a.v + b.v,  f = a.f | b.f,  last = b.f ? b.last : a.last;  identity (0, 0, 0).
+ * pya_debug_block_scan: ts_block_scan by one workgroup over in[256] entries; out: 257 entries, [0 .. 255] the exclusive
+ * scan, [256] the total.  pya_debug_ts_scan: ts_scan as the stages launch it, the exclusive scan of data[n] in place
+ * (n <= 2^24; three levels from 65 537 entries). */
+enum { PYA_DBG_SCAN_ADD = 0, PYA_DBG_SCAN_SEG = 1 };
+int pya_debug_block_scan(pya_handle *h, uint32_t policy, const uint32_t *in, uint32_t *out);
+int pya_debug_ts_scan(pya_handle *h, uint32_t policy, uint32_t *data, uint64_t n);
+
+/* pya_launch_ions_scan as the ion stage and the spectrum transforms launch it: off[0 .. n) counts in, offsets out, off[n]
+ * their sum (n <= 2^24; the carry loop takes a second trip from 65 537 entries). */
+int pya_debug_ions_scan(pya_handle *h, int64_t *off, uint32_t n);
+
 /* The handle's device tables as they are now: out[0] entries of the signature order table that are on the device, out[1] rows
  * of the score table that are, out[2] uploads of the DevConfig so far, out[3] the device address of the score table as an
  * integer (a table that grows is uploaded into a new allocation).  The tests of live plans read from it that a table grew and

@@ -38,6 +38,14 @@ PYA_FLR_TARGET, PYA_FLR_DECOY, PYA_FLR_LEFT_OUT = 0, 1, 2
 PYA_FLR_REPORTED_ONLY = 1
 PYA_FLR_TILE = 1024          # slots per workgroup and sort pass of csrc/flr.hip
 PYA_FLR_PHASES = 11          # (include/pyascore_debug.h: pya_debug_rollup_flr_timed)
+# (include/pyascore_debug.h: the test-only calls on the device building blocks)
+PYA_DEBUG_LOOKUP_MAX_N = 8192
+(PYA_DBG_FASTDIV, PYA_DBG_CHARGE_MZ, PYA_DBG_NTH_SET_BIT, PYA_DBG_DEPOSIT_SITES, PYA_DBG_XCD_SLOT, PYA_DBG_NL_BUMP, PYA_DBG_LUT_ROW,
+ PYA_DBG_HIST) = range(8)
+(PYA_DBG_WAVE_SUM_U64, PYA_DBG_WAVE_MINMAX_F64, PYA_DBG_MARKER_LANE_F64, PYA_DBG_ION_SCAN_U64, PYA_DBG_HIST_WAVE_SUM,
+ PYA_DBG_SAME_DIGIT) = range(6)
+PYA_DBG_WAVE_IN, PYA_DBG_WAVE_OUT = 192, 4096
+PYA_DBG_SCAN_ADD, PYA_DBG_SCAN_SEG = 0, 1
 PYA_MAX_RANKED = 64
 PYA_RANK_NONE, PYA_RANK_SCORED, PYA_RANK_OVER = 0, 1, 2
 PYA_RANK_TIED_PREV, PYA_RANK_IN_BEST_TIE = 1, 2
@@ -361,6 +369,12 @@ SYMBOLS = {
     "pya_set_debug": (C.c_int, [_vp, C.c_char_p, C.c_char_p]),          # include/pyascore_debug.h (test-only)
     "pya_debug_wave_ops": (C.c_int, [_vp, _vp, _vp]),         # (test-only)
     "pya_debug_last_chunks": (C.c_uint64, [_vp]),             # (test-only)
+    "pya_debug_lookup": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_float, _vp, C.c_uint32, _vp, _vp]),   # (test-only)
+    "pya_debug_lane_ops": (C.c_int, [_vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp]),             # (test-only)
+    "pya_debug_wave64": (C.c_int, [_vp, C.c_uint32, _vp, _vp]),                                # (test-only)
+    "pya_debug_block_scan": (C.c_int, [_vp, C.c_uint32, _vp, _vp]),                            # (test-only)
+    "pya_debug_ts_scan": (C.c_int, [_vp, C.c_uint32, _vp, C.c_uint64]),                        # (test-only)
+    "pya_debug_ions_scan": (C.c_int, [_vp, _vp, C.c_uint32]),                                  # (test-only)
     "pya_debug_table_sizes": (C.c_int, [_vp, _vp]),           # (test-only)
     "pya_debug_span_guard": (C.c_int, [_vp, C.c_char_p, C.c_uint64, _vp, _vp, C.c_uint64, _vp]),   # (test-only)
     "pya_debug_bin_keys": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp]),             # (test-only)

@@ -544,6 +544,122 @@ int pya_debug_wave_ops(pya_handle *h, const int32_t in[64], int32_t out[263]) {
     return PYA_OK;
 }
 
+/* ---- the device building blocks, one at a time (include/pyascore_debug.h; the kernels: debug_ops.hip) ---- */
+int pya_debug_lookup(pya_handle *h, const float *mz, const uint32_t *rank, uint32_t n, float mz_error, const float *query, uint32_t n_query,
+                     uint8_t *out, uint32_t cells[257]) {
+    if (!h) return PYA_ERR_ARG;
+    if (n > PYA_DEBUG_LOOKUP_MAX_N || (n && (!mz || !rank)) || (n_query && (!query || !out)) || !cells)
+        return h->fail(PYA_ERR_ARG, -1, "debug lookup: a NULL array, or more than %d entries", PYA_DEBUG_LOOKUP_MAX_N);
+    if (!(mz_error > 0.f) || !(mz_error < 50.f)) return h->fail(PYA_ERR_ARG, -1, "debug lookup: mz_error must be in (0, 50)");
+    for (uint32_t i = 0; i < n; i++)
+        if (!std::isfinite(mz[i]) || (i && mz[i] < mz[i - 1]) || rank[i] >= PYA_NO_MATCH)
+            return h->fail(PYA_ERR_ARG, (int64_t)i, "debug lookup: entry %u is not one of a retained table (finite, ascending, rank < %d)", i,
+                           PYA_NO_MATCH);
+    /* behind the table: entries that would match if the global lookup did not mask what it reads past the last one */
+    std::vector<PeakEntry> tab((size_t)n + PYA_TABLE_PAD);
+    for (size_t i = 0; i < tab.size(); i++) {
+        tab[i].mz = i < n ? mz[i] : (n ? mz[n - 1] : 0.f);
+        tab[i].rank = i < n ? rank[i] : 0u;
+    }
+    DevConfig cfg;
+    std::memset(&cfg, 0, sizeof cfg);
+    cfg.mz_error = mz_error;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevBuf<PeakEntry> d_tab;
+    DevBuf<DevConfig> d_cfg;
+    DevBuf<uint16_t> d_grid;
+    DevBuf<uint32_t> d_cells;
+    DevBuf<float> d_query;
+    DevBuf<uint8_t> d_out;
+    HIPCHK(h, d_tab.upload(tab.data(), tab.size()));
+    HIPCHK(h, d_cfg.upload(&cfg, 1));
+    HIPCHK(h, d_grid.alloc(PYA_GRID_CELLS));
+    HIPCHK(h, d_cells.alloc(PYA_GRID_CELLS + 1));
+    HIPCHK(h, d_query.upload(query, n_query));
+    HIPCHK(h, d_out.alloc((size_t)n_query * 4));
+    HIPCHK(h, hipMemset(d_out.p, 0xee, n_query ? (size_t)n_query * 4 : 1));
+    int e = pya_launch_debug_lookup(d_tab.p, n, d_cfg.p, d_grid.p, d_cells.p, d_query.p, n_query, d_out.p, nullptr);
+    if (e) return h->hip_fail((hipError_t)e, "debug lookup launch");
+    HIPCHK(h, hipMemcpy(cells, d_cells.p, (PYA_GRID_CELLS + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (n_query) HIPCHK(h, hipMemcpy(out, d_out.p, (size_t)n_query * 4, hipMemcpyDeviceToHost));
+    return PYA_OK;
+}
+
+int pya_debug_lane_ops(pya_handle *h, uint32_t op, const uint64_t *a, const uint64_t *b, uint64_t n, uint64_t *out) {
+    if (!h) return PYA_ERR_ARG;
+    if (op >= PYA_DBG_LANE_OPS || n > ((uint64_t)1 << 28) || (n && (!a || !b || !out))) return h->fail(PYA_ERR_ARG, -1, "debug lane ops: op %u, n", op);
+    for (uint64_t i = 0; i < n; i++)
+        if ((op == PYA_DBG_CHARGE_MZ && (b[i] < 1 || b[i] > 255)) || (op == PYA_DBG_NL_BUMP && (b[i] < 1 || b[i] > 16)))
+            return h->fail(PYA_ERR_ARG, (int64_t)i, "debug lane ops: operand %llu outside the function's domain", (unsigned long long)i);
+    if (n == 0) return PYA_OK;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevBuf<uint64_t> da, db, dout;
+    HIPCHK(h, da.upload(a, n));
+    HIPCHK(h, db.upload(b, n));
+    HIPCHK(h, dout.alloc(n));
+    int e = pya_launch_debug_lane_ops(op, da.p, db.p, n, dout.p, nullptr);
+    if (e) return h->hip_fail((hipError_t)e, "debug lane ops launch");
+    HIPCHK(h, hipMemcpy(out, dout.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PYA_OK;
+}
+
+int pya_debug_wave64(pya_handle *h, uint32_t op, const uint64_t *in, uint64_t *out) {
+    if (!h) return PYA_ERR_ARG;
+    if (op >= PYA_DBG_WAVE_OPS || !in || !out) return h->fail(PYA_ERR_ARG, -1, "debug wave64: op %u", op);
+    HIPCHK(h, hipSetDevice(h->device));
+    DevBuf<uint64_t> di, dout;
+    HIPCHK(h, di.upload(in, PYA_DBG_WAVE_IN));
+    HIPCHK(h, dout.alloc(PYA_DBG_WAVE_OUT));
+    HIPCHK(h, hipMemset(dout.p, 0, PYA_DBG_WAVE_OUT * sizeof(uint64_t)));
+    int e = op == PYA_DBG_ION_SCAN_U64 ? pya_launch_debug_ion_wave_scan(di.p, dout.p, nullptr) : pya_launch_debug_wave64(op, di.p, dout.p, nullptr);
+    if (e) return h->hip_fail((hipError_t)e, "debug wave64 launch");
+    HIPCHK(h, hipMemcpy(out, dout.p, PYA_DBG_WAVE_OUT * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return PYA_OK;
+}
+
+int pya_debug_block_scan(pya_handle *h, uint32_t policy, const uint32_t *in, uint32_t *out) {
+    if (!h) return PYA_ERR_ARG;
+    if (policy > PYA_DBG_SCAN_SEG || !in || !out) return h->fail(PYA_ERR_ARG, -1, "debug block scan: policy %u", policy);
+    const size_t words = policy == PYA_DBG_SCAN_SEG ? 3 : 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevBuf<uint32_t> di, dout;
+    HIPCHK(h, di.upload(in, 256 * words));
+    HIPCHK(h, dout.alloc(257 * words));
+    int e = pya_launch_debug_block_scan(policy, di.p, dout.p, nullptr);
+    if (e) return h->hip_fail((hipError_t)e, "debug block scan launch");
+    HIPCHK(h, hipMemcpy(out, dout.p, 257 * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return PYA_OK;
+}
+
+int pya_debug_ts_scan(pya_handle *h, uint32_t policy, uint32_t *data, uint64_t n) {
+    if (!h) return PYA_ERR_ARG;
+    if (policy > PYA_DBG_SCAN_SEG || n > ((uint64_t)1 << 24) || (n && !data)) return h->fail(PYA_ERR_ARG, -1, "debug ts scan: policy %u, n", policy);
+    if (n == 0) return PYA_OK;
+    const size_t words = policy == PYA_DBG_SCAN_SEG ? 3 : 1;
+    HIPCHK(h, hipSetDevice(h->device));
+    DevBuf<uint32_t> d;
+    HIPCHK(h, d.alloc((size_t)pya_ts_scan_entries(n) * words));
+    HIPCHK(h, hipMemcpy(d.p, data, (size_t)n * words * sizeof(uint32_t), hipMemcpyHostToDevice));
+    int e = pya_launch_debug_ts_scan(policy, d.p, n, nullptr);
+    if (e) return h->hip_fail((hipError_t)e, "debug ts scan launch");
+    HIPCHK(h, hipMemcpy(data, d.p, (size_t)n * words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return PYA_OK;
+}
+
+int pya_debug_ions_scan(pya_handle *h, int64_t *off, uint32_t n) {
+    if (!h) return PYA_ERR_ARG;
+    if (!off || n < 1 || n > (1u << 24)) return h->fail(PYA_ERR_ARG, -1, "debug ions scan: n");
+    HIPCHK(h, hipSetDevice(h->device));
+    DevBuf<int64_t> d;
+    DevBuf<uint64_t> tiles;
+    HIPCHK(h, d.upload(off, (size_t)n + 1));
+    HIPCHK(h, tiles.alloc(pya_ions_scan_tiles(n)));
+    int e = pya_launch_ions_scan(d.p, n, tiles.p, nullptr);
+    if (e) return h->hip_fail((hipError_t)e, "debug ions scan launch");
+    HIPCHK(h, hipMemcpy(off, d.p, ((size_t)n + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return PYA_OK;
+}
+
 int pya_debug_sort(pya_handle *h, const float *keys, uint32_t n, uint32_t *perm) {
     if (!h || !keys || !perm) return PYA_ERR_ARG;
     if (n == 0) return PYA_OK;

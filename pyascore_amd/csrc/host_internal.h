@@ -82,6 +82,15 @@ int pya_launch_debug_sort(const float *d_keys, uint32_t n, uint32_t *d_perm, hip
 int pya_launch_pack_records(const float *best_score, const int32_t *n_sig, const uint64_t *best_sig, const float *ascores,
                             const uint64_t *alt_mask, uint32_t k, uint32_t res_k, uint64_t n_psm, int32_t *out, hipStream_t stream);
 int pya_launch_debug_wave_ops(const int32_t *d_in, int32_t *d_out, hipStream_t stream);
+/* (debug_ops.hip: the test-only kernels behind include/pyascore_debug.h's pya_debug_lookup .. pya_debug_ts_scan) */
+int pya_launch_debug_lookup(const void *d_table, uint32_t n, const DevConfig *d_cfg, uint16_t *d_grid, uint32_t *d_cells, const float *d_query,
+                            uint32_t n_query, uint8_t *d_out, hipStream_t stream);
+int pya_launch_debug_lane_ops(uint32_t op, const uint64_t *d_a, const uint64_t *d_b, uint64_t n, uint64_t *d_out, hipStream_t stream);
+int pya_launch_debug_wave64(uint32_t op, const uint64_t *d_in, uint64_t *d_out, hipStream_t stream);
+int pya_launch_debug_block_scan(uint32_t policy, const uint32_t *d_in, uint32_t *d_out, hipStream_t stream);
+uint64_t pya_ts_scan_entries(uint64_t n);
+int pya_launch_debug_ts_scan(uint32_t policy, uint32_t *d_data, uint64_t n, hipStream_t stream);
+int pya_launch_debug_ion_wave_scan(const uint64_t *d_in, uint64_t *d_out, hipStream_t stream);   /* (ions.hip) */
 size_t pya_score_big_lds_bytes(uint32_t cap, uint32_t pos_cap, uint32_t kc);
 int pya_launch_score_big(const BatchDev *b, const uint32_t *d_ids, uint32_t n_ids, uint32_t cap, uint32_t pos_cap, uint32_t kc,
                          uint32_t inline_on, hipStream_t stream);

@@ -245,6 +245,18 @@ __global__ __launch_bounds__(64) void pya_ions_scan_kernel(int64_t *off, uint32_
     if (blockIdx.x == gridDim.x - 1 && lane == 63) off[n] = (int64_t)(carry + total);
 }
 
+/* test-only: ion_wave_excl_scan_u64 by one full wavefront (include/pyascore_debug.h: pya_debug_wave64, PYA_DBG_ION_SCAN_U64):
+ * out[0 .. 63] the exclusive sums, out[64 .. 127] the total as every lane has it */
+__global__ __launch_bounds__(64) void pya_debug_ion_wave_scan_kernel(const uint64_t *in, uint64_t *out) {
+    uint64_t total;
+    out[lane_id()] = ion_wave_excl_scan_u64(in[lane_id()], &total);
+    out[64 + lane_id()] = total;
+}
+extern "C" int pya_launch_debug_ion_wave_scan(const uint64_t *d_in, uint64_t *d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(pya_debug_ion_wave_scan_kernel, dim3(1), dim3(64), 0, stream, d_in, d_out);
+    return (int)hipGetLastError();
+}
+
 extern "C" size_t pya_ions_lds_bytes(uint32_t l_cap, uint32_t list_cap) { return ions_lds_bytes(l_cap, list_cap); }
 extern "C" uint32_t pya_ions_scan_tiles(uint32_t n) { return (n + ION_SCAN_TILE - 1) / ION_SCAN_TILE; }
 

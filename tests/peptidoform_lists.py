@@ -9,6 +9,10 @@ T = _lib.PYA_PFORM_TILE
 DTYPE = np.dtype(_lib.PEPTIDOFORM_DTYPE)
 SIZES = (0, 1, 2, 63, 64, 65, T - 1, T, T + 1, 2 * T + 1)
 BIG = 256 * T + 1
+# 258 tiles: 257 whole ones and a tail of 19 entries, so that the last two tile totals of the segmented reduction lie in the second
+# block of the level above -- for the kinds whose runs cross tile borders (KINDS_PAST_256_TILES)
+PAST_256_TILES = 257 * T + 19
+KINDS_PAST_256_TILES = ("runs", "group_ends")
 KINDS = ("one_key", "distinct", "sig_top") + tuple("group_byte%d" % b for b in range(4)) + ("group_ends", "runs", "ties", "ascores", "zeros")
 SPECIAL_ASCORES = np.array([0x00000000, 0x80000000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0xBF800000,
                             0xC2C80000, 0x3F800000, 0x00000001, 0x80000001], np.uint32)       # +-0, +-inf, NaNs, -1, -100, 1, denormals
