@@ -352,6 +352,9 @@ DEV int gen_setup_residues(const BatchDev &b, const DevConfig *cfg, const GenLds
         int j = 0;
         for (int i = 0; i < L; i++)
             if (g.sor[i] != 255) {
+                /* (8 bits: read only where L <= 64, for the residue bits of alt_mask in general_psm.hip; above that
+                 * length alt_mask holds site bits, and evidence.hip / sites.hip keep 16-bit residues of their own.
+                 * tests/test_gpu_stage_limits.py runs modifiable residues at 256 and above through every stage) */
                 if (j < GEN_MAX_SITES) g.site_pos[j] = (uint8_t)i;
                 g.sor[i] = (uint8_t)j;
                 j++;
