@@ -855,6 +855,94 @@ typedef struct pya_purity {            /* 48 bytes per query */
 #define PYA_PURITY_ACTIVE 1u
 #define PYA_PURITY_SEEN 2u
 
+/* Precursor XIC: the MS1 intensity of an identified precursor for LABEL-FREE quantification -- the area, the apex and the sum
+ * of its extracted ion chromatogram over the survey scans around the identification, what a search engine or MaxQuant reports
+ * per PSM.  A READ-ONLY stage over the survey spectra beside the purity stage: records out, no workspace, and no kernel of a
+ * run knows of it.  The reference has no counterpart.  Positional phospho-isomers share a precursor m/z and elute a few scans
+ * apart: a trace that is not split at the valley between them credits each isomer's PSMs with both peaks, so the peak rule
+ * has a valley split.
+ * THE RULE.  n_survey survey spectra (pya_typed_spectra + int64 offsets, float32 widened at the load), rt[n_survey] (double,
+ * seconds; not checked, its arithmetic is taken as it is), scan_ok[n_survey] (uint8, what pya_xic_survey_check writes: 1 iff
+ * x[j] <= x[j + 1] for every adjacent pair of the scan's m/z -- a NaN among two or more fails, 0 or 1 peaks pass) and n_query
+ * queries, one per MS2 spectrum: seed[q], scan_lo[q], scan_hi[q] (int64 indices into the survey list; the window is
+ * [scan_lo, scan_hi)), prec_mz[q] (double), prec_z[q] (int32).  All arithmetic is in double, every operation rounded on its
+ * own, in the order written; a comparison with a NaN is false.
+ * SILENT: seed < 0.  The record is all zero bytes and nothing is read.
+ * ACTIVE iff 0 <= scan_lo <= seed < scan_hi <= n_survey, scan_hi - scan_lo <= PYA_XIC_MAX_SCANS, prec_z in
+ * 1 .. PYA_STRIP_MAX_CHARGE and prec_mz finite and > 0.  A query that is not active has an all-zero record.  One with
+ * seed >= 0 that fails the first two conditions (the RANGE) is counted in d_over[0], the smallest such q in d_over[1] as
+ * 0xffffffff - q, as purity reports a survey index beyond the spectra.  An active query one of whose scans had its offsets
+ * clipped to the elements the arrays hold is reported the same way; its record is that of the clipped peaks.
+ * THE TRACE of scan s of the window, for i = 0 .. isotopes:
+ *   d    = step / (double)prec_z
+ *   c_i  = prec_mz + (double)i d
+ *   w_i  = tol + (tol_ppm 1e-6) c_i
+ *   lo_i = c_i - w_i,  hi_i = c_i + w_i
+ *   p_i[s] = the largest y among ALL peaks (x, y) of scan s with lo_i <= x && x <= hi_i && y > 0.0, +0.0 when there is none
+ * -- a maximum over a set: order-free, no tie rule; a NaN x or y never qualifies; an infinite y takes part as arithmetic has
+ * it.  A scan with scan_ok[s] == 0 has no peaks for this purpose, and the record of an active query with such a scan in its
+ * window gets PYA_XIC_UNSORTED.
+ *   present[s] iff p_0[s] > 0.0
+ *   t[s] = p_0[s], then t = t + p_i[s] for i = 1 .. isotopes ascending; +0.0 where s is not present.
+ * START: a0 = seed if present, else the nearest present scan with |s - seed| <= max_gap + 1, the earlier one on a tie.  None:
+ * the record is ACTIVE without SEEN -- flags (ACTIVE, UNSORTED where it applies) and n_present are filled, the rest is zero.
+ * REGION [r_lo, r_hi]: the largest interval around a0 inside the window with no run of more than max_gap consecutive absent
+ * scans in it and both ends present.  Absent scans inside it are skipped by everything below.
+ * VALLEYS, on the present scans v != a0 of the region.  L[v]: the largest t from a0 to v inclusive.  F[v]: the largest t
+ * strictly beyond v, away from a0, inside the region.  n(v): the next present scan beyond v.  v is a VALLEY iff n(v) exists,
+ * t[v] <= t[n(v)], rise t[v] < L[v] and rise t[v] < F[v] (one rounded product).  e_r: the smallest valley above a0, else
+ * r_hi; e_l: the largest valley below a0, else r_lo.  A valley scan belongs to both neighbouring peaks.
+ * THE PEAK, over the present scans of [e_l, e_r] ascending: apex the largest t, the smaller scan on a tie;
+ *   sum:  S = +0.0; S = S + t[u]
+ *   area: A = +0.0; for consecutive present scans u < v: A = A + (0.5 (t[u] + t[v])) (rt[v] - rt[u])
+ * each operation rounded, no contraction -- ONE defined order, the scans'.  (A NaN that the rt arithmetic makes is stored as
+ * the device makes it; its sign and payload are not part of the rule.)
+ * THE RECORD: seed_intensity is t[seed]; the four scans are absolute survey indices; n_points the present scans of the peak,
+ * n_present those of the window; bit i of iso_hit iff p_i[apex] > 0.  Flags: ACTIVE, SEEN (a start was found), SEED_PRESENT,
+ * LEFT_VALLEY / RIGHT_VALLEY (the bound is a valley), LEFT_OPEN iff e_l == scan_lo and it is no valley, RIGHT_OPEN iff
+ * e_r == scan_hi - 1 and it is no valley: the peak may go on outside the window.  No -0.0 reaches a record.
+ * By hand: rt = 0, 1, 2, ..; one peak per scan with intensities 10 100 300 100 20 150 400 150 10; rise 2, isotopes 0, window
+ * [0, 9).  Seed 2: the peak [0, 4], apex scan 2, RIGHT_VALLEY | LEFT_OPEN, area 515.0, sum 530.0.  Seed 6: the peak [4, 8],
+ * apex scan 6, LEFT_VALLEY | RIGHT_OPEN, area 715.0.
+ * The parameters must satisfy: tol and tol_ppm finite and >= 0; step finite and > 0; rise finite and >= 1; isotopes 0 ..
+ * PYA_XIC_MAX_ISOTOPES; max_gap 0 .. PYA_XIC_MAX_GAP.  The defaults of the Python layer (tol 0, tol_ppm 10, isotopes 2, step
+ * PYA_STRIP_STEP, rise 2, max_gap 1) are choices, not measurements.
+ * KNOWN WEAKNESS of the valley rule: a noise dip on a slope that faces a second, higher peak is a valley, and cuts early. */
+#define PYA_XIC_MAX_SCANS 64
+#define PYA_XIC_MAX_ISOTOPES 3
+#define PYA_XIC_MAX_GAP 8
+typedef struct pya_xic_params {        /* 40 bytes */
+    double tol;                                    /* half width of an isotope's window in m/z (Da); finite, >= 0            */
+    double tol_ppm;                                /* and in ppm of its centre, added to it; finite, >= 0                    */
+    double step;                                   /* the isotope spacing at charge 1 (PYA_STRIP_STEP); finite, > 0          */
+    double rise;                                   /* a valley lies below 1 / rise of the maxima on both sides; finite, >= 1 */
+    uint32_t isotopes;                             /* isotope positions above the selected m/z, 0 .. PYA_XIC_MAX_ISOTOPES    */
+    uint32_t max_gap;                              /* absent scans a trace may bridge, 0 .. PYA_XIC_MAX_GAP                  */
+} pya_xic_params;
+typedef struct pya_xic {               /* 64 bytes per query */
+    double area;                                   /* trapezoids over the present scans of the peak, in scan order           */
+    double apex_intensity;                         /* the largest t of the peak                                              */
+    double seed_intensity;                         /* t[seed]; 0.0 where the seed scan is absent                             */
+    double sum_intensity;                          /* t summed over the present scans of the peak, in scan order             */
+    uint32_t apex_scan, left_scan, right_scan;     /* apex, e_l and e_r as survey indices                                    */
+    uint32_t start_scan;                           /* a0 as a survey index                                                   */
+    uint32_t n_points, n_present;                  /* present scans of the peak; of the window                               */
+    uint32_t iso_hit;                              /* bit i: isotope i held a peak in the apex scan                          */
+    uint32_t flags;                                /* PYA_XIC_*                                                              */
+} pya_xic;
+#define PYA_XIC_ACTIVE 1u
+#define PYA_XIC_SEEN 2u
+#define PYA_XIC_SEED_PRESENT 4u
+#define PYA_XIC_LEFT_VALLEY 8u
+#define PYA_XIC_RIGHT_VALLEY 16u
+#define PYA_XIC_UNSORTED 32u
+#define PYA_XIC_LEFT_OPEN 64u
+#define PYA_XIC_RIGHT_OPEN 128u
+#define PYA_XIC_AREA 0u                /* `which` of pya_xic_values */
+#define PYA_XIC_APEX 1u
+#define PYA_XIC_SEED 2u
+#define PYA_XIC_SUM 3u
+
 /* Centroiding (peak picking): the first of the transforms in front of a run.  Everything behind it -- the top-N-per-100-m/z
  * binning, the match window, deisotoping's tol, the strip windows -- takes one (m/z, intensity) pair for one peak.  A
  * profile-mode spectrum (msconvert without a peak-picking filter, older QTOF exports, "profile MS2" methods) has 10 to 20
@@ -1422,6 +1510,44 @@ int pya_purity_spectra_host(pya_handle *h, const pya_typed_spectra *survey_spect
  * 8-byte aligned.  n_rows == 0 is a call that writes nothing. */
 int pya_purity_gate(pya_handle *h, const pya_purity *d_purity, uint64_t n_rows, double threshold, uint32_t keep_unknown,
                     const double *d_values, uint32_t n_channels, double *d_out, uint8_t *d_select, void *hip_stream);
+/* Whether each of n_survey survey spectra on the device ascends in m/z (scan_ok of THE RULE at pya_xic_params above;
+ * csrc/xic.hip): d_scan_ok[n_survey] takes one byte per scan, 1 iff x[j] <= x[j + 1] for every adjacent pair of the scan's
+ * m/z (the offsets clipped to n_survey_peaks).  Only the m/z array of d_survey_spectra is read.  Run once per survey set; it
+ * serves every later pya_xic_spectra call.  One launch on hip_stream, one wavefront per scan, stream-ordered, no host wait, no
+ * allocation; no write lies outside d_scan_ok[0 .. n_survey).  PYA_ERR_ARG, with nothing launched: more than 2^32 - 2 scans,
+ * element types as pya_purity_spectra refuses them, a NULL array.  n_survey == 0 is a call that writes nothing. */
+int pya_xic_survey_check(pya_handle *h, const pya_typed_spectra *d_survey_spectra, const int64_t *d_survey_off, uint64_t n_survey,
+                         uint64_t n_survey_peaks, void *hip_stream, uint8_t *d_scan_ok);
+/* The precursor XIC of n_query queries over n_survey survey spectra on the device (THE RULE at pya_xic_params above;
+ * csrc/xic.hip).  The survey spectra, d_survey_off, n_survey and n_survey_peaks as pya_purity_spectra takes them; d_rt[n_survey]
+ * (double), d_scan_ok[n_survey] (uint8, of pya_xic_survey_check over the same spectra: a byte that says 1 for a scan that does
+ * not ascend makes that scan's trace undefined, nothing else); d_seed, d_scan_lo, d_scan_hi [n_query] (int64), d_prec_mz
+ * [n_query] (double), d_prec_z[n_query] (int32); d_xic[n_query]: one pya_xic per query (8-byte aligned); d_over[2] (zeroed by
+ * the caller) as pya_purity_spectra's.  One launch on hip_stream, one wavefront per query with lane j on survey scan
+ * scan_lo + j, stream-ordered, no host wait, no allocation, no workspace.  The inputs are only read; no write lies outside
+ * d_xic[0 .. n_query) and d_over[0 .. 2).
+ * PYA_ERR_ARG, with nothing launched: more than 2^32 - 2 queries or survey spectra, parameters outside the conditions above,
+ * element types as pya_purity_spectra refuses them, a NULL array, records that are not 8-byte aligned.  n_query == 0 is a
+ * call that writes nothing; n_survey == 0 is allowed (the survey arrays, d_rt and d_scan_ok may then be NULL but for the
+ * offsets: every query is silent or out of range). */
+int pya_xic_spectra(pya_handle *h, const pya_typed_spectra *d_survey_spectra, const int64_t *d_survey_off, uint64_t n_survey,
+                    uint64_t n_survey_peaks, const double *d_rt, const uint8_t *d_scan_ok, const int64_t *d_seed,
+                    const int64_t *d_scan_lo, const int64_t *d_scan_hi, const double *d_prec_mz, const int32_t *d_prec_z,
+                    uint64_t n_query, const pya_xic_params *params, void *hip_stream, pya_xic *d_xic, uint32_t *d_over);
+/* The same over HOST arrays: uploads the survey spectra and the queries once, runs pya_xic_survey_check itself when scan_ok is
+ * NULL (else uploads scan_ok[n_survey]), runs on the handle's stream, downloads only the records and over, and waits.
+ * survey_off[0] must not be negative and the offsets must not descend (PYA_ERR_ARG). */
+int pya_xic_spectra_host(pya_handle *h, const pya_typed_spectra *survey_spectra, const int64_t *survey_off, uint64_t n_survey,
+                         const double *rt, const uint8_t *scan_ok, const int64_t *seed, const int64_t *scan_lo,
+                         const int64_t *scan_hi, const double *prec_mz, const int32_t *prec_z, uint64_t n_query,
+                         const pya_xic_params *params, pya_xic *xic, uint32_t *over);
+/* One column of the records d_xic[n] (device memory, as pya_xic_spectra wrote them) as the one-channel matrix
+ * pya_plan_site_quant and pya_plan_peptidoform_quant take: d_out[n] (doubles) takes the area (which PYA_XIC_AREA), the apex,
+ * the seed or the sum intensity, or the NaN of pya_marker_values (0x7ff8000000000000) where the record is not SEEN or the
+ * value is not > 0.  One launch on hip_stream, stream-ordered, no host wait, no allocation; no write lies outside
+ * d_out[0 .. n).  PYA_ERR_ARG, with nothing launched: which above 3, more than 2^32 - 2 records, a NULL or not 8-byte aligned
+ * array.  n == 0 is a call that writes nothing. */
+int pya_xic_values(pya_handle *h, const pya_xic *d_xic, uint64_t n, uint32_t which, void *hip_stream, double *d_out);
 /* Applies a correction to the channel matrix d_values[n_rows * n_channels] (APPLY of the channel correction above;
  * csrc/channel_correct.hip): d_matrix[n_channels * n_channels] (row-major) or NULL, d_factor[n_channels] or NULL, not both
  * NULL; d_out[n_rows * n_channels] takes the result (all device memory, doubles, 8-byte aligned).  d_out == d_values, exactly

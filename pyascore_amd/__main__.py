@@ -33,7 +33,10 @@ the columns of ``--peptidoform_table``, then the same intensities summed over th
 isotope impurities and brought to equal channel totals before either table sums them) and ``--purity FILE`` with ``--purity_tol``,
 ``--purity_tol_ppm``, ``--purity_isotopes``, ``--purity_below``, ``--purity_window LO,HI``, ``--purity_threshold P`` and
 ``--purity_drop_unknown`` (per PSM the share of its isolation window that was its precursor, read off the survey scans of the
-spectrum file; with a threshold the impure spectra are left out of both quantification tables) are the additions."""
+spectrum file; with a threshold the impure spectra are left out of both quantification tables) and ``--xic FILE`` with
+``--xic_rt_window SECONDS``, ``--xic_tol``, ``--xic_tol_ppm``, ``--xic_isotopes``, ``--xic_rise``, ``--xic_gap`` and ``--xic_channel
+area|apex`` (per PSM the label-free MS1 intensity of its precursor: the chromatographic peak over the survey scans around it, read in
+the pass ``--purity`` makes; with a channel and no ``--marker_mz`` both quantification tables sum that column) are the additions."""
 import argparse
 import re
 import sys
@@ -259,6 +262,26 @@ def build_parser():
     p.add_argument("--purity_drop_unknown", action="store_true",
                    help="with --purity_threshold: also leave out the spectra whose purity is not known (no survey scan, no window, "
                         "an empty window)")
+    p.add_argument("--xic", type=str, default="", metavar="FILE",
+                   help="write the precursor-XIC table to FILE: one line per PSM with its survey (MS1) scan, the survey scans its "
+                        "window reaches, and the area, apex, sum and bounds of the precursor's chromatographic peak there (the survey "
+                        "scans are read in the pass --purity makes, once for both)")
+    p.add_argument("--xic_rt_window", type=float, default=60.0, metavar="SECONDS",
+                   help="with --xic: how far on either side of the survey scan a window reaches in retention time, 64 scans at the most "
+                        "(default 60: a choice, not a measurement)")
+    p.add_argument("--xic_tol", type=float, default=0.0, metavar="DA",
+                   help="with --xic: the half width of the window around an isotope position in m/z (default 0)")
+    p.add_argument("--xic_tol_ppm", type=float, default=10.0, metavar="PPM",
+                   help="with --xic: ... plus this many ppm of the position's m/z (default 10)")
+    p.add_argument("--xic_isotopes", type=int, default=2, metavar="N",
+                   help="with --xic: isotope positions above the precursor's m/z whose intensity is added to the trace, 0 .. 3 (default 2)")
+    p.add_argument("--xic_rise", type=float, default=2.0, metavar="R",
+                   help="with --xic: a scan splits the trace where R times its intensity lies below the maxima on both sides (default 2)")
+    p.add_argument("--xic_gap", type=int, default=1, metavar="N",
+                   help="with --xic: survey scans without the precursor a trace may bridge, 0 .. 8 (default 1)")
+    p.add_argument("--xic_channel", type=str, default="", choices=("", "area", "apex"),
+                   help="with --xic and without --marker_mz: --site_quant / --peptidoform_quant sum this column of the XIC table as "
+                        "their one channel (label-free tables); with --marker_mz the channels are the reporters")
     p.add_argument("spec_file", type=str)
     p.add_argument("ident_file", type=str)
     p.add_argument("out_file", type=str)
@@ -281,6 +304,30 @@ def strip_request(args):
     return req
 
 
+def xic_request(args):
+    """``--xic`` as the dict ``batch_cli.localize(xic=...)`` takes, without the survey records (``run`` reads them), checked; None
+    without the option: the other ``--xic_*`` values are then not looked at -- but for ``--xic_channel``, which is refused
+    without it."""
+    if not getattr(args, "xic", ""):
+        if getattr(args, "xic_channel", ""):
+            raise ValueError("--xic_channel names a column of the table of --xic: give --xic FILE as well")
+        return None
+    from . import batch_cli
+    req = dict(rt_window=args.xic_rt_window, tol=args.xic_tol, tol_ppm=args.xic_tol_ppm, isotopes=args.xic_isotopes, rise=args.xic_rise,
+               max_gap=args.xic_gap, channel=args.xic_channel or None)
+    try:
+        batch_cli.xic_request(dict(req, survey=()), [])
+    except ValueError as e:
+        raise ValueError("--xic: %s" % e) from None
+    return req
+
+
+def label_free(args):
+    """the column ``--site_quant`` / ``--peptidoform_quant`` sum without reporter targets ('xic_area' / 'xic_apex'), or None"""
+    targets = [v for v in getattr(args, "marker_mz", "").split(",") if v.strip()]
+    return "xic_" + args.xic_channel if getattr(args, "xic", "") and getattr(args, "xic_channel", "") and not targets else None
+
+
 def site_quant_request(args):
     """``--site_quant`` as the dict ``batch_cli.localize(site_quant=...)`` takes, checked; None without the option: the other
     ``--site_quant_*`` values are then not looked at."""
@@ -289,9 +336,10 @@ def site_quant_request(args):
     from .rollup import site_quant_params
     if not args.site_table:
         raise ValueError("--site_quant sums over the sites of --site_table: give --site_table FILE as well")
-    channels = [v for v in args.marker_mz.split(",") if v.strip()]
+    channels = [v for v in args.marker_mz.split(",") if v.strip()] or ([label_free(args)] if label_free(args) else [])
     if not channels:
-        raise ValueError("--site_quant sums the intensities of the --marker_mz targets: give --marker_mz M1,M2,... as well")
+        raise ValueError("--site_quant sums the intensities of the --marker_mz targets: give --marker_mz M1,M2,... as well "
+                         "(or --xic FILE --xic_channel area|apex for a label-free table)")
     req = dict(threshold=args.site_quant_threshold, scale_log2=args.site_quant_scale, complete_only=bool(args.site_quant_complete))
     site_quant_params(n_channels=min(len(channels), 64), **req)
     return req
@@ -303,10 +351,10 @@ def peptidoform_quant_request(args):
     if not getattr(args, "peptidoform_quant", ""):
         return None
     from .rollup import site_quant_params
-    channels = [v for v in args.marker_mz.split(",") if v.strip()]
+    channels = [v for v in args.marker_mz.split(",") if v.strip()] or ([label_free(args)] if label_free(args) else [])
     if not channels:
         raise ValueError("--peptidoform_quant sums the intensities of the fixed --marker_mz targets (--marker_losses are no channels): "
-                         "give --marker_mz M1,M2,... as well")
+                         "give --marker_mz M1,M2,... as well (or --xic FILE --xic_channel area|apex for a label-free table)")
     req = dict(threshold=args.peptidoform_quant_threshold, scale_log2=args.peptidoform_quant_scale,
                complete_only=bool(args.peptidoform_quant_complete))
     try:
@@ -342,6 +390,8 @@ def markers_request(args):
     checked; None without the option (and without ``--site_quant`` / ``--peptidoform_quant``, which read the same targets): the
     other ``--marker_*`` values are then not looked at."""
     if not getattr(args, "markers", "") and not getattr(args, "site_quant", "") and not getattr(args, "peptidoform_quant", ""):
+        return None
+    if not getattr(args, "markers", "") and label_free(args):      # (the tables sum the XIC column: no targets are read)
         return None
     from .rollup import marker_params
     lists = {}
@@ -416,6 +466,7 @@ def validate_args(args):
     peptidoform_quant_request(args)
     channels_request(args)
     purity_request(args)
+    xic_request(args)
     if getattr(args, "decharge", False):
         from .rollup import decharge_params
         if getattr(args, "deisotope", False):
@@ -489,9 +540,16 @@ def run(args, log=print):
     pform_quant_rows = [] if pform_quant is not None else None
     purity = purity_request(args)
     purity_rows = [] if purity is not None else None
-    if purity is not None:
+    xic = xic_request(args)
+    xic_rows = [] if xic is not None else None
+    if purity is not None or xic is not None:              # (one pass over the file serves both)
         log("{} -- Reading survey scans from: {}".format(stamp(), args.spec_file))
-        purity["survey"] = ingest.SpectraParser(args.spec_file, args.spec_file_type, ms_level=1, native_precision=True).to_list()
+        survey = ingest.SpectraParser(args.spec_file, args.spec_file_type, ms_level=1, native_precision=True, times=xic is not None).to_list()
+        if purity is not None:
+            purity["survey"] = survey
+        if xic is not None:
+            xic["survey"] = survey
+    quant_channels = dict(named=(label_free(args),)) if label_free(args) else dict(mz=markers["mz"] if markers is not None else ())
     if ranked_rows is not None:
         from .ranked import check_k
         check_k(args.ranked_depth)
@@ -507,7 +565,7 @@ def run(args, log=print):
                               centroid=centroid_request(args), coverage=coverage_rows, markers=markers,
                               marker_rows=marker_rows, site_quant=site_quant, site_quant_rows=site_quant_rows,
                               peptidoform_quant=pform_quant, peptidoform_quant_rows=pform_quant_rows,
-                              channels=channels_request(args), purity=purity, purity_rows=purity_rows)
+                              channels=channels_request(args), purity=purity, purity_rows=purity_rows, xic=xic, xic_rows=xic_rows)
     batch_cli.write_tsv(rows, args.out_file, evidence=args.evidence, reported=args.reported, sites=site_rows is not None,
                         probs=args.probs)
     if site_rows is not None:
@@ -530,9 +588,11 @@ def run(args, log=print):
     if coverage_rows is not None:
         batch_cli.write_coverage_tsv(coverage_rows, args.coverage)
     if site_quant_rows is not None:
-        batch_cli.write_site_quant_tsv(site_quant_rows, args.site_quant, mz=markers["mz"])
+        batch_cli.write_site_quant_tsv(site_quant_rows, args.site_quant, **quant_channels)
     if pform_quant_rows is not None:
-        batch_cli.write_peptidoform_quant_tsv(pform_quant_rows, args.peptidoform_quant, mz=markers["mz"])
+        batch_cli.write_peptidoform_quant_tsv(pform_quant_rows, args.peptidoform_quant, **quant_channels)
+    if xic_rows is not None:
+        batch_cli.write_xic_tsv(xic_rows, args.xic)
     if purity_rows is not None:
         batch_cli.write_purity_tsv(purity_rows, args.purity)
     if marker_rows is not None and args.markers:

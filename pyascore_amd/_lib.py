@@ -338,6 +338,37 @@ assert C.sizeof(Purity) == 48, "pya_purity is a 48-byte record"
 PURITY_DTYPE = [("window", "<f8"), ("precursor", "<f8"), ("other_mz", "<f8"), ("other_intensity", "<f8"), ("n_window", "<u4"),
                 ("n_precursor", "<u4"), ("iso_hit", "<u4"), ("flags", "<u4")]
 
+PYA_XIC_MAX_SCANS = 64
+PYA_XIC_MAX_ISOTOPES = 3
+PYA_XIC_MAX_GAP = 8
+PYA_XIC_ACTIVE, PYA_XIC_SEEN, PYA_XIC_SEED_PRESENT, PYA_XIC_LEFT_VALLEY = 1, 2, 4, 8
+PYA_XIC_RIGHT_VALLEY, PYA_XIC_UNSORTED, PYA_XIC_LEFT_OPEN, PYA_XIC_RIGHT_OPEN = 16, 32, 64, 128
+PYA_XIC_AREA, PYA_XIC_APEX, PYA_XIC_SEED, PYA_XIC_SUM = 0, 1, 2, 3
+
+
+class XicParams(C.Structure):
+    """pya_xic_params: the half width of an isotope's window in Da and in ppm of its centre, the isotope spacing at charge 1, the
+    valley rule's rise, the isotope positions above the selected m/z and the absent scans a trace may bridge"""
+    _fields_ = [("tol", C.c_double), ("tol_ppm", C.c_double), ("step", C.c_double), ("rise", C.c_double), ("isotopes", C.c_uint32),
+                ("max_gap", C.c_uint32)]
+
+
+assert C.sizeof(XicParams) == 40, "pya_xic_params is a 40-byte record"
+
+
+class Xic(C.Structure):
+    """pya_xic: area, apex, seed and summed intensity of a precursor's chromatographic peak, its apex, bounds and start as survey
+    indices, the present scans of the peak and of the window, the isotopes seen at the apex, the flags"""
+    _fields_ = [("area", C.c_double), ("apex_intensity", C.c_double), ("seed_intensity", C.c_double), ("sum_intensity", C.c_double),
+                ("apex_scan", C.c_uint32), ("left_scan", C.c_uint32), ("right_scan", C.c_uint32), ("start_scan", C.c_uint32),
+                ("n_points", C.c_uint32), ("n_present", C.c_uint32), ("iso_hit", C.c_uint32), ("flags", C.c_uint32)]
+
+
+assert C.sizeof(Xic) == 64, "pya_xic is a 64-byte record"
+XIC_DTYPE = [("area", "<f8"), ("apex_intensity", "<f8"), ("seed_intensity", "<f8"), ("sum_intensity", "<f8"), ("apex_scan", "<u4"),
+             ("left_scan", "<u4"), ("right_scan", "<u4"), ("start_scan", "<u4"), ("n_points", "<u4"), ("n_present", "<u4"),
+             ("iso_hit", "<u4"), ("flags", "<u4")]
+
 PYA_CENTROID_MAX_HALF_WIDTH = 8
 
 
@@ -472,6 +503,12 @@ SYMBOLS = {
     "pya_purity_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
                                           C.POINTER(PurityParams), _vp, _vp]),
     "pya_purity_gate": (C.c_int, [_vp, _vp, C.c_uint64, C.c_double, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp]),
+    "pya_xic_survey_check": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.c_uint64, _vp, _vp]),
+    "pya_xic_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                  C.POINTER(XicParams), _vp, _vp, _vp]),
+    "pya_xic_spectra_host": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64,
+                                       C.POINTER(XicParams), _vp, _vp]),
+    "pya_xic_values": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp]),
     "pya_centroid_workspace_bytes": (C.c_uint64, [C.c_uint64, C.c_uint64]),
     "pya_centroid_spectra": (C.c_int, [_vp, C.POINTER(TypedSpectra), _vp, C.c_uint64, _vp, C.POINTER(CentroidParams), _vp, _vp, C.c_uint64,
                                        C.POINTER(TypedSpectra), _vp, _vp]),

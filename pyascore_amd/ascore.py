@@ -356,6 +356,35 @@ def _purity_request(req, n_spec=None, have_quant=True):
     return params, (req["ms1_mz"], req["ms1_intensity"], req["ms1_peak_off"]), queries, gate
 
 
+XIC_CHANNELS = {"xic_area": "area", "xic_apex": "apex"}     # ``values=`` of quant= / peptidoform_quant= beside xic=
+
+
+def _xic_request(req, n_spec=None):
+    """``score_batch(xic=...)`` checked: ``(params, spectra, rt, queries)`` -- the dict of ``pyascore_amd.rollup.xic_params``,
+    ``(ms1_mz, ms1_intensity, ms1_peak_off)`` and ``rt`` as given, the five query arrays of ``pyascore_amd.rollup.xic_queries``
+    (``n_spec`` entries each when it is given)"""
+    from .rollup import xic_params, xic_queries
+    rule_names = ("tol", "tol_ppm", "isotopes", "step", "rise", "max_gap")
+    names = ("ms1_mz", "ms1_intensity", "ms1_peak_off", "rt", "seed", "scan_lo", "scan_hi", "precursor_mz", "precursor_charge") + rule_names
+    if not isinstance(req, dict):
+        raise ValueError("xic takes a dict: " + ", ".join(names))
+    unknown = set(req) - set(names)
+    if unknown:
+        raise ValueError("xic takes " + ", ".join(names) + "; unknown: " + ", ".join(sorted(unknown)))
+    missing = [k for k in names[:9] if req.get(k) is None]
+    if missing:
+        raise ValueError("xic needs " + ", ".join(missing))
+    try:
+        params = xic_params(**{k: req[k] for k in rule_names if req.get(k) is not None})
+    except TypeError:
+        raise ValueError("xic: tol, tol_ppm, step and rise are numbers, isotopes and max_gap integers") from None
+    queries = xic_queries(req["seed"], req["scan_lo"], req["scan_hi"], req["precursor_mz"], req["precursor_charge"])
+    if n_spec is not None and queries[0].size != n_spec:
+        raise ValueError("xic: seed, scan_lo, scan_hi, precursor_mz and precursor_charge have one entry per spectrum (per PSM in a batch "
+                         "without spec_of)")
+    return params, (req["ms1_mz"], req["ms1_intensity"], req["ms1_peak_off"]), req["rt"], queries
+
+
 def _centroid_request(req, n_spec=None):
     """``score_batch(centroid=...)`` checked: ``(params, select)`` -- the dict of ``pyascore_amd.rollup.centroid_params`` and
     the uint8 ``select`` array (one entry per spectrum; ``n_spec`` entries when it is given) or None"""
@@ -749,7 +778,7 @@ class PyAscore:
     def score_batch(self, batch, keep=False, skip_invalid=False, evidence=False, ions=False, named=None, sites=False,
                     site_sig_cap=None, probs=False, ranked=None, rollup=None, peptidoforms=None, mz_profile=None,
                     recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=False, markers=None,
-                    quant=None, peptidoform_quant=None, purity=None):
+                    quant=None, peptidoform_quant=None, purity=None, xic=None):
         """Scores a CSR batch (see pyascore_amd.synth) in one call.
 
         Returns dict(best_score f32[n], best_sig u64[n], n_sig i32[n], ascores f32[n, max_k],
@@ -951,6 +980,18 @@ class PyAscore:
         normalizes.  A ``gate`` without ``quant=`` / ``peptidoform_quant=`` is a ValueError.  A caller whose spectra are resident
         uses ``pyascore_amd.device.purity`` / ``purity_gate``; ``pyascore_amd.rollup.purity`` gives the same bytes on the host.
 
+        ``xic=dict(ms1_mz=, ms1_intensity=, ms1_peak_off=, rt=, seed=, scan_lo=, scan_hi=, precursor_mz=, precursor_charge=, tol=0.0,
+        tol_ppm=10.0, isotopes=2, step=, rise=2.0, max_gap=1)`` adds ``xic`` (``pyascore_amd.rollup.XIC_DTYPE``, the 64-byte
+        ``pya_xic``, shape ``[n_spectra]``): per spectrum the label-free MS1 intensity of its precursor -- area, apex and sum of
+        its chromatographic peak over the survey scans ``[scan_lo, scan_hi)`` around the survey scan ``seed``
+        (``pya_xic_params``; ``rt`` the survey scans' retention times in seconds; ``pyascore_amd.rollup.survey_index`` finds
+        ``seed``, ``xic_windows`` the windows).  READ-ONLY over the survey spectra: every other result of the call is bit-equal
+        with and without it.  ``quant=dict(values="xic_area" | "xic_apex", ...)`` and the same on ``peptidoform_quant=`` take that
+        column (``pyascore_amd.rollup.xic_values``) as their one channel: a label-free site or peptidoform table.  The survey
+        spectra are uploaded once per request: ``purity=`` beside ``xic=`` uploads them a second time (sharing the upload is
+        not built).  A resident pipeline uses ``pyascore_amd.device.xic_survey_check`` / ``xic`` / ``xic_values``;
+        ``pyascore_amd.rollup.xic`` gives the same bytes on the host.
+
         ``coverage=True`` adds ``coverage`` (``COVERAGE_DTYPE``, the 64-byte ``pya_coverage``, shape ``[n]``): per PSM the ion
         current of its spectrum and the part of it that the matched fragments of the reported localisation explain, in all and
         from either terminus, beside peak, fragment and bond counts (``pyascore_amd.rollup.coverage_ratios`` makes the ratios,
@@ -968,12 +1009,40 @@ class PyAscore:
                         site_sig_cap=site_sig_cap, probs=probs, ranked=ranked, rollup=rollup, peptidoforms=peptidoforms,
                         mz_profile=mz_profile, recalibrate=recalibrate, deisotope=deisotope, decharge=decharge, strip=strip,
                         centroid=centroid, coverage=coverage, markers=markers, quant=quant,
-                        peptidoform_quant=peptidoform_quant, purity=purity)
+                        peptidoform_quant=peptidoform_quant, purity=purity, xic=xic)
             rest.update(changed)
             if done is not None:
                 rest[done] = None
             return self.score_batch(dict(batch, mz=spectra[0], intensity=spectra[1], peak_off=spectra[2]), **rest)
 
+        labelfree = {name: req["values"] for name, req in (("quant", quant), ("peptidoform_quant", peptidoform_quant))
+                     if isinstance(req, dict) and isinstance(req.get("values"), str)}
+        for name, column in labelfree.items():
+            if column not in XIC_CHANNELS:
+                raise ValueError(name + ": values is a matrix, or one of " + ", ".join(repr(k) for k in XIC_CHANNELS) + " beside xic=")
+            if xic is None or xic is False:
+                raise ValueError(name + ": values = %r needs xic= in the same call" % column)
+        if xic is not None and xic is not False:
+            # (in front of everything: the stage reads the survey spectra alone, and the column it gives is a matrix to all that
+            # follows.  What follows is checked on a column of the same shape first, so that a refusal launches nothing.)
+            from .rollup import xic_values
+            params, survey_spectra, survey_rt, queries = _xic_request(xic, _n_spectra(batch))
+            blank = np.zeros((queries[0].size, 1))
+            checks = {name: dict(req, values=blank) if name in labelfree else req
+                      for name, req in (("quant", quant), ("peptidoform_quant", peptidoform_quant))}
+            for name, req in checks.items():
+                _channels_request(name, req, markers)
+            if purity is not None and purity is not False:
+                _purity_request(purity, _n_spectra(batch), any(isinstance(req, dict) for req in checks.values()))
+            records, _ = self.precursor_xic(*survey_spectra, survey_rt, *queries, params)
+            # (the rows of the column are the spectra, as beside markers=: a shared batch's PSMs name theirs by spec_of)
+            spec_row = None if batch.get("spec_of") is None else np.asarray(batch["spec_of"]).astype(np.int32)
+            changed = {name: dict(checks[name], values=xic_values(records, XIC_CHANNELS[column]).reshape(-1, 1),
+                                  row=spec_row if checks[name].get("row") is None else checks[name]["row"])
+                       for name, column in labelfree.items()}
+            res = again("xic", (batch["mz"], batch["intensity"], batch["peak_off"]), **changed)
+            res["xic"] = records
+            return res
         channel_reqs = {name: _channels_request(name, req, markers)
                         for name, req in (("quant", quant), ("peptidoform_quant", peptidoform_quant))}
         if purity is not None and purity is not False:
@@ -1631,6 +1700,43 @@ class PyAscore:
         if sv.size:
             rc = self._lib.pya_purity_spectra_host(self._h, C.byref(c.t_in), _as_ptr(c.peak_off), c.n_spec, _as_ptr(sv), _as_ptr(pm), _as_ptr(pz),
                                                    _as_ptr(wl), _as_ptr(wh), sv.size, C.byref(c_params), _as_ptr(records), _as_ptr(c.over))
+            if rc:
+                self._raise(rc)
+        return records, (int(c.over[0]), None if not c.over[0] else 0xFFFFFFFF - int(c.over[1]))
+
+    def precursor_xic(self, ms1_mz, ms1_intensity, ms1_peak_off, rt, seed, scan_lo, scan_hi, precursor_mz, precursor_charge, params,
+                      scan_ok=None):
+        """The precursor XIC -- the label-free MS1 intensity of identified precursors --, read off survey spectra on the device
+        (``pya_xic_spectra_host``; the rule is ``pya_xic_params``'s in include/pyascore_hip.h): ``ms1_mz`` / ``ms1_intensity`` /
+        ``ms1_peak_off`` the survey (MS1) spectra as ``precursor_purity`` takes them, ``rt`` their retention times in seconds;
+        per query (one per MS2 spectrum) ``seed`` the survey scan of the identification (negative: none), ``scan_lo`` /
+        ``scan_hi`` the window of at most 64 survey scans around it (``pyascore_amd.rollup.xic_windows``), ``precursor_mz`` /
+        ``precursor_charge``; ``params`` of ``pyascore_amd.rollup.xic_params``; ``scan_ok``: the bytes of
+        ``pyascore_amd.rollup.survey_ascending`` when they are at hand, None to have the device check the scans.  Returns
+        ``(records, over)``: ``pyascore_amd.rollup.XIC_DTYPE[n_query]`` and ``over = (count, first)`` for the queries whose
+        window is out of range (zero records), ``(0, None)`` when there is none.  The survey spectra and the queries are
+        uploaded once and only the records come back.  ``pyascore_amd.rollup.xic`` gives the same bytes on the host."""
+        from .rollup import XIC_DTYPE, xic_c_params, xic_queries
+        c_params = xic_c_params(params)
+        c = _transform_call("precursor_xic", ms1_mz, ms1_intensity, ms1_peak_off)
+        sd, lo, hi, pm, pz = xic_queries(seed, scan_lo, scan_hi, precursor_mz, precursor_charge, "precursor_xic")
+        try:
+            rt = np.ascontiguousarray(rt, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("precursor_xic: rt is a number per survey spectrum") from None
+        if rt.shape != (c.n_spec,):
+            raise ValueError("precursor_xic: rt has one entry per survey spectrum")
+        if scan_ok is not None:
+            scan_ok = np.ascontiguousarray(scan_ok, np.uint8)
+            if scan_ok.shape != (c.n_spec,):
+                raise ValueError("precursor_xic: scan_ok has one byte per survey spectrum")
+        if sd.size > 0xFFFFFFFE:
+            raise ValueError("precursor_xic: more than 2^32 - 2 queries")
+        records = np.zeros(sd.size, XIC_DTYPE)
+        if sd.size:
+            rc = self._lib.pya_xic_spectra_host(self._h, C.byref(c.t_in), _as_ptr(c.peak_off), c.n_spec, _as_ptr(rt) if c.n_spec else None,
+                                                _as_ptr(scan_ok) if c.n_spec else None, _as_ptr(sd), _as_ptr(lo), _as_ptr(hi), _as_ptr(pm),
+                                                _as_ptr(pz), sd.size, C.byref(c_params), _as_ptr(records), _as_ptr(c.over))
             if rc:
                 self._raise(rc)
         return records, (int(c.over[0]), None if not c.over[0] else 0xFFFFFFFF - int(c.over[1]))

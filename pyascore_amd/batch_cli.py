@@ -199,7 +199,7 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
              site_table_flr=False, site_table_decoys="", peptidoform_table=None, peptidoform_threshold=0.75, mz_profile=None,
              recalibrate=None, deisotope=None, decharge=None, strip=None, centroid=None, coverage=None, markers=None,
              marker_rows=None, site_quant=None, site_quant_rows=None, peptidoform_quant=None, peptidoform_quant_rows=None, channels=None,
-             purity=None, purity_rows=None):
+             purity=None, purity_rows=None, xic=None, xic_rows=None):
     """Scores every selected PSM in one batched call and returns the TSV rows
     ``[scan, localized_sequence, pep_score, "a;b", "1,2;3"]`` in input order.  PSMs the library sets
     aside (invalid, or beyond one of its documented limits) keep their row -- empty localisation, PepScore
@@ -270,7 +270,21 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
     else the last survey scan in front of it (``pyascore_amd.rollup.survey_index``).  ``purity_rows``: the list that then
     receives one ``[scan] + purity_fields`` row per picked PSM (``write_purity_tsv``).  With ``threshold`` the gate of
     ``PyAscore.score_batch(purity=dict(gate=...))`` is applied to what ``site_quant`` / ``peptidoform_quant`` sum; it needs one of
-    them."""
+    them.
+    ``xic``: ``dict(survey=, rt_window=, tol=, tol_ppm=, isotopes=, step=, rise=, max_gap=, channel=None)``: ``survey`` the MS1 records
+    of the spectrum file WITH their retention times (``ingest.SpectraParser(..., ms_level=1, times=True).to_list()``), the rule as
+    ``pyascore_amd.rollup.xic_params`` takes it, ``rt_window`` the seconds on either side of the seed scan a window reaches
+    (``pyascore_amd.rollup.xic_windows``: at most 64 scans); the seed scan of a spectrum is its survey scan as for ``purity``.
+    ``xic_rows``: the list that then receives one ``[scan] + xic_fields`` row per picked PSM (``write_xic_tsv``).  ``channel``:
+    'area' or 'apex' -- where ``markers`` has no fixed targets, ``site_quant`` / ``peptidoform_quant`` then sum that column as
+    their one channel: label-free tables."""
+    label_free = None
+    if xic is not None:                                    # (a bad request is refused before anything is read or scored)
+        xic_rule, xic_rt_window, xic_channel = xic_request(xic, xic_rows)
+        if xic_channel is not None and not (isinstance(markers, dict) and tuple(markers.get("mz", ()))):
+            label_free = "xic_" + xic_channel
+            if channels is not None:
+                raise ValueError("channels corrects reporter channels: it does not go with a label-free xic channel")
     if purity is not None:                                 # (a bad request is refused before anything is read or scored)
         purity_rule, purity_window, purity_gate = purity_request(purity, purity_rows, site_quant is not None or peptidoform_quant is not None)
     if channels is not None:                               # (a bad request is refused before anything is read or scored)
@@ -285,15 +299,15 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         if not isinstance(peptidoform_quant, dict) or set(peptidoform_quant) - {"threshold", "scale_log2", "complete_only"} \
                 or peptidoform_quant_rows is None:
             raise ValueError("peptidoform_quant takes a dict of threshold, scale_log2 and complete_only beside a list peptidoform_quant_rows")
-        if not isinstance(markers, dict) or not tuple(markers.get("mz", ())):
-            raise ValueError("peptidoform_quant needs markers with fixed targets mz (its channels)")
-        site_rollup.site_quant_params(n_channels=len(tuple(markers["mz"])), **peptidoform_quant)
+        if label_free is None and (not isinstance(markers, dict) or not tuple(markers.get("mz", ()))):
+            raise ValueError("peptidoform_quant needs markers with fixed targets mz (its channels), or xic with a channel")
+        site_rollup.site_quant_params(n_channels=1 if label_free else len(tuple(markers["mz"])), **peptidoform_quant)
     if site_quant is not None:                             # (a bad request is refused before anything is read or scored)
         if not isinstance(site_quant, dict) or set(site_quant) - {"threshold", "scale_log2", "complete_only"} or site_quant_rows is None:
             raise ValueError("site_quant takes a dict of threshold, scale_log2 and complete_only beside a list site_quant_rows")
-        if site_table is None or not isinstance(markers, dict) or not tuple(markers.get("mz", ())):
-            raise ValueError("site_quant needs site_table (its slots) and markers with fixed targets mz (its channels)")
-        site_rollup.site_quant_params(n_channels=len(tuple(markers["mz"])), **site_quant)
+        if site_table is None or (label_free is None and (not isinstance(markers, dict) or not tuple(markers.get("mz", ())))):
+            raise ValueError("site_quant needs site_table (its slots) and markers with fixed targets mz (its channels), or xic with a channel")
+        site_rollup.site_quant_params(n_channels=1 if label_free else len(tuple(markers["mz"])), **site_quant)
     if markers is not None:                                # (a bad request is refused before anything is read or scored)
         from .ascore import _markers_request
         if not isinstance(markers, dict) or "precursor_mz" in markers or "precursor_charge" in markers or marker_rows is None:
@@ -357,11 +371,13 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
         stages["markers"] = dict(markers, precursor_mz=prec_mz, precursor_charge=prec_z)
     if purity is not None:
         stages["purity"] = purity_stage(picked, scans, spectra_map, purity["survey"], purity_rule, purity_window, purity_gate)
+    if xic is not None:
+        stages["xic"] = xic_stage(picked, scans, spectra_map, xic["survey"], xic_rule, xic_rt_window)
     corrected = {} if channels is None else dict(channels=dict(channels))
     if site_quant is not None:
-        stages["quant"] = dict(site_quant, values=None, **corrected)
+        stages["quant"] = dict(site_quant, values=label_free, **corrected)
     if peptidoform_quant is not None:
-        stages["peptidoform_quant"] = dict(peptidoform_quant, values=None, **corrected)
+        stages["peptidoform_quant"] = dict(peptidoform_quant, values=label_free, **corrected)
     if site_table is not None:
         peptides = [p["peptide"] for p in picked]
         # (the PSMs the library will set aside have no residue records: the offsets come from its own pre-pass, before anything
@@ -433,6 +449,11 @@ def localize(ascore, psms, spectra_map, residues, mod_mass, hit_depth=1, max_fra
             survey_scan = int(purity["survey"][int(q["survey"][spec])]["scan"]) if q["survey"][spec] >= 0 else ""
             purity_rows.append([scans[i], survey_scan, float(q["window_lo"][spec]), float(q["window_hi"][spec])] +
                                purity_fields(res["purity"][spec]))
+        if xic is not None:                      # (per spectrum, as the marker records)
+            spec = i if batch.get("spec_of") is None else int(batch["spec_of"][i])
+            q = stages["xic"]
+            xic_rows.append([scans[i]] + xic_fields(res["xic"][spec], xic["survey"], int(q["seed"][spec]), int(q["scan_lo"][spec]),
+                                                    int(q["scan_hi"][spec])))
         if ranked is not None:
             ranked.extend([scans[i], hit] + ranked_fields(rk[i, r], rk[i, 0], rk_seqs[i * rk.shape[1] + r])
                           for r in range(int(ranked_lists.lengths(rk[i])[0])))
@@ -502,10 +523,11 @@ def write_site_table_tsv(site_table_rows, path, flr=False):
             out.write("\t".join("%s" % f for f in row) + "\n")
 
 
-def site_quant_columns(mz=()):
+def site_quant_columns(mz=(), named=()):
     """The header of the ``--site_quant`` table: Peptide, Position, Residue, Records, Complete, then the sum of every channel under
-    the name of its target, ``mz<value>``, in the order of ``--marker_mz``."""
-    return ("Peptide", "Position", "Residue", "Records", "Complete") + tuple("mz%r" % float(v) for v in mz)
+    the name of its target, ``mz<value>``, in the order of ``--marker_mz``; ``named``: channels that are no targets, under their
+    own names (the label-free ``xic_area`` / ``xic_apex``)."""
+    return ("Peptide", "Position", "Residue", "Records", "Complete") + tuple("mz%r" % float(v) for v in mz) + tuple(named)
 
 
 def site_quant_fields(key, head, sums):
@@ -518,11 +540,11 @@ def site_quant_fields(key, head, sums):
         ["" if v != v else repr(float(v)) for v in sums]
 
 
-def write_site_quant_tsv(site_quant_rows, path, mz=()):
+def write_site_quant_tsv(site_quant_rows, path, mz=(), named=()):
     """The ``--site_quant`` table: the rows ``localize(..., site_quant=dict(...), site_quant_rows=[])`` collected, under
-    ``site_quant_columns(mz)``."""
+    ``site_quant_columns(mz, named)``."""
     with open(path, "w") as out:
-        out.write("\t".join(site_quant_columns(mz)) + "\n")
+        out.write("\t".join(site_quant_columns(mz, named)) + "\n")
         for row in site_quant_rows:
             out.write("\t".join("%s" % f for f in row) + "\n")
 
@@ -538,10 +560,11 @@ def peptidoform_table_fields(row, scans):
             str(np.float32(row["best_min_ascore"])), str(row["n_isomers"])]
 
 
-def peptidoform_quant_columns(mz=()):
+def peptidoform_quant_columns(mz=(), named=()):
     """The header of the ``--peptidoform_quant`` table: the columns of ``--peptidoform_table``, Records, Complete, then the sum of
-    every channel under the name of its target, ``mz<value>``, in the order of ``--marker_mz``."""
-    return tuple(PEPTIDOFORM_TABLE_COLUMNS) + ("Records", "Complete") + tuple("mz%r" % float(v) for v in mz)
+    every channel under the name of its target, ``mz<value>``, in the order of ``--marker_mz``; ``named`` as for
+    ``site_quant_columns``."""
+    return tuple(PEPTIDOFORM_TABLE_COLUMNS) + ("Records", "Complete") + tuple("mz%r" % float(v) for v in mz) + tuple(named)
 
 
 def peptidoform_quant_fields(row, scans, head, sums):
@@ -553,11 +576,11 @@ def peptidoform_quant_fields(row, scans, head, sums):
         ["" if v != v else repr(float(v)) for v in sums]
 
 
-def write_peptidoform_quant_tsv(peptidoform_quant_rows, path, mz=()):
+def write_peptidoform_quant_tsv(peptidoform_quant_rows, path, mz=(), named=()):
     """The ``--peptidoform_quant`` table: the rows ``localize(..., peptidoform_quant=dict(...), peptidoform_quant_rows=[])``
-    collected, under ``peptidoform_quant_columns(mz)``."""
+    collected, under ``peptidoform_quant_columns(mz, named)``."""
     with open(path, "w") as out:
-        out.write("\t".join(peptidoform_quant_columns(mz)) + "\n")
+        out.write("\t".join(peptidoform_quant_columns(mz, named)) + "\n")
         for row in peptidoform_quant_rows:
             out.write("\t".join("%s" % f for f in row) + "\n")
 
@@ -776,6 +799,85 @@ def purity_stage(picked, scans, spectra_map, survey, rule, window, gate):
     if gate is not None:
         stage["gate"] = dict(gate)
     return stage
+
+
+def xic_request(xic, xic_rows):
+    """``localize(xic=...)`` checked: ``(rule, rt_window, channel)`` -- the dict of ``pyascore_amd.rollup.xic_params``, the
+    seconds on either side of the seed scan, and 'area', 'apex' or None"""
+    rule_names = ("tol", "tol_ppm", "isotopes", "step", "rise", "max_gap")
+    names = ("survey", "rt_window") + rule_names + ("channel",)
+    if not isinstance(xic, dict) or set(xic) - set(names) or xic.get("survey") is None or xic.get("rt_window") is None or xic_rows is None:
+        raise ValueError("xic takes a dict of " + ", ".join(names) + " beside a list xic_rows; survey is the MS1 records with their rt")
+    try:
+        rule = site_rollup.xic_params(**{k: xic[k] for k in rule_names if xic.get(k) is not None})
+        rt_window = float(xic["rt_window"])
+    except TypeError:
+        raise ValueError("xic: rt_window, tol, tol_ppm, step and rise are numbers, isotopes and max_gap integers") from None
+    if not rt_window >= 0.0:
+        raise ValueError("xic: rt_window = %r is not a number of seconds >= 0" % (xic["rt_window"],))
+    if xic.get("channel") not in (None, "area", "apex"):
+        raise ValueError("xic: channel is 'area' or 'apex'")
+    return rule, rt_window, xic.get("channel")
+
+
+def survey_arrays(survey):
+    """the MS1 records ``survey`` packed as one CSR set: ``(ms1_mz, ms1_intensity, ms1_peak_off)``"""
+    lens = [np.size(r["mz_values"]) for r in survey]
+    ms1_mz = np.concatenate([np.asarray(r["mz_values"]) for r in survey]) if survey else np.zeros(0)
+    ms1_it = np.concatenate([np.asarray(r["intensity_values"]) for r in survey]) if survey else np.zeros(0)
+    return ms1_mz, ms1_it, np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+
+
+def xic_stage(picked, scans, spectra_map, survey, rule, rt_window):
+    """The ``xic=`` request of ``PyAscore.score_batch`` for the spectra of ``pack_hits(picked, scans)``, in its order: the survey
+    records packed as one CSR set with their ``rt`` (NaN where the file gave none: such a scan is in no window but its own), the
+    seed scan of every MS2 spectrum (``pyascore_amd.rollup.survey_index``, as for ``purity``) and the window of ``rt_window``
+    seconds around it (``pyascore_amd.rollup.xic_windows``)."""
+    survey = list(survey)
+    ms1_mz, ms1_it, ms1_off = survey_arrays(survey)
+    rt = np.asarray([float("nan") if r.get("rt") is None else float(r["rt"]) for r in survey], np.float64)
+    spec_scans, parents = [], []
+    for i, psm in enumerate(picked):
+        if i and scans[i] == scans[i - 1] and psm["mz"] is picked[i - 1]["mz"] and psm["intensity"] is picked[i - 1]["intensity"]:
+            continue
+        spec_scans.append(scans[i])
+        parents.append(spectra_map[scans[i]].get("parent_scan"))
+    prec_mz, prec_z = hit_precursors(picked, scans)
+    seed = site_rollup.survey_index([r["scan"] for r in survey], spec_scans, parents)
+    lo, hi = site_rollup.xic_windows(rt, seed, rt_window)
+    return dict(rule, ms1_mz=ms1_mz, ms1_intensity=ms1_it, ms1_peak_off=ms1_off, rt=rt, seed=seed, scan_lo=lo, scan_hi=hi, precursor_mz=prec_mz,
+                precursor_charge=prec_z)
+
+
+XIC_TABLE_COLUMNS = ["Scan", "SeedScan", "WindowFirst", "WindowLast", "Area", "Apex", "ApexScan", "ApexRT", "SeedIntensity", "Sum", "LeftScan",
+                     "RightScan", "Points", "Present", "IsoHit", "Flags"]
+
+
+def xic_fields(rec, survey, seed, scan_lo, scan_hi):
+    """One ``XIC_DTYPE`` record as the fields behind the scan of the ``--xic`` table: the scan numbers of the seed and of the
+    window's first and last survey scan (empty without a seed), Area, Apex, the apex's scan number and retention time, the seed
+    scan's intensity, Sum, the scan numbers of the peak's bounds, Points, Present, IsoHit (one 0 / 1 per isotope, lowest first) and
+    the flags as names joined by ``|``; the peak's fields are empty where none was found."""
+    number = lambda s: int(survey[s]["scan"])                              # noqa: E731
+    window = [number(seed), number(scan_lo), number(scan_hi - 1)] if seed >= 0 and scan_hi > scan_lo else ["", "", ""]
+    flags = int(rec["flags"])
+    names = "|".join(n for n, bit in (("active", 1), ("seen", 2), ("seed_present", 4), ("left_valley", 8), ("right_valley", 16), ("unsorted", 32),
+                                      ("left_open", 64), ("right_open", 128)) if flags & bit)
+    if not flags & site_rollup.XIC_SEEN:
+        return window + [""] * 9 + [int(rec["n_present"]) if flags else "", "", names]
+    apex = int(rec["apex_scan"])
+    rt = survey[apex].get("rt")
+    return window + [float(rec["area"]), float(rec["apex_intensity"]), number(apex), "" if rt is None else float(rt), float(rec["seed_intensity"]),
+                     float(rec["sum_intensity"]), number(int(rec["left_scan"])), number(int(rec["right_scan"])), int(rec["n_points"]),
+                     int(rec["n_present"]), format(int(rec["iso_hit"]), "b")[::-1], names]
+
+
+def write_xic_tsv(xic_rows, path):
+    """The ``--xic`` table: the rows ``localize(..., xic=dict(...), xic_rows=[])`` collected, under ``XIC_TABLE_COLUMNS``."""
+    with open(path, "w") as out:
+        out.write("\t".join(XIC_TABLE_COLUMNS) + "\n")
+        for row in xic_rows:
+            out.write("\t".join(str(v) for v in row) + "\n")
 
 
 PURITY_COLUMNS = ["Scan", "SurveyScan", "WindowLo", "WindowHi", "Window", "Precursor", "Ratio", "Peaks", "PrecursorPeaks", "IsoHit",

@@ -1195,6 +1195,115 @@ def purity_records(raw):
     return a.view(PURITY_DTYPE).reshape(a.shape[0])
 
 
+def xic_survey_check(scorer, d_ms1_mz, d_ms1_intensity, ms1_peak_off, out=None):
+    """``scan_ok`` of the XIC stage over survey spectra that live on the device (``pya_xic_survey_check``): a ``uint8`` tensor
+    ``[n_survey]``, 1 where the scan's m/z ascend.  The spectra as ``purity`` takes them; only the m/z are read.  ``out``: such a
+    tensor to write into, new when None.  Run once per survey set: it serves every later ``xic`` call.  One launch on torch's
+    current stream; nothing waits on the host.  ``pyascore_amd.rollup.survey_ascending`` gives the same bytes."""
+    import torch
+    _, device, peak_off, n_survey = _transform_inputs(scorer, lambda p: None, None, d_ms1_mz, d_ms1_intensity, ms1_peak_off)
+    if out is None:
+        with torch.cuda.device(device):
+            out = torch.empty(n_survey, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n_survey,) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("out must be a contiguous uint8 device tensor of shape (%d,)" % n_survey)
+    t_in = _lib.TypedSpectra(d_ms1_mz.data_ptr(), d_ms1_intensity.data_ptr(), _lib.spectrum_type(d_ms1_mz.dtype),
+                             _lib.spectrum_type(d_ms1_intensity.dtype))
+    rc = scorer._lib.pya_xic_survey_check(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_survey, d_ms1_mz.numel(),
+                                          torch.cuda.current_stream(device).cuda_stream, out.data_ptr() if n_survey else None)
+    if rc:
+        scorer._raise(rc)
+    return out
+
+
+def xic(scorer, d_ms1_mz, d_ms1_intensity, ms1_peak_off, d_rt, d_scan_ok, d_seed, d_scan_lo, d_scan_hi, d_prec_mz, d_prec_z, params, out=None):
+    """The precursor XIC over survey spectra that live on the device (``pya_xic_spectra``; the rule is ``pya_xic_params``'s in
+    include/pyascore_hip.h): the survey spectra as ``purity`` takes them; ``d_rt`` (float64 ``[n_survey]``, seconds) and
+    ``d_scan_ok`` (uint8 ``[n_survey]``, of ``xic_survey_check``); ``d_seed`` / ``d_scan_lo`` / ``d_scan_hi`` (int64),
+    ``d_prec_mz`` (float64), ``d_prec_z`` (int32) one entry per query -- device tensors or host arrays (a host array is
+    uploaded); ``params`` of ``pyascore_amd.rollup.xic_params``.  ``out``: a contiguous ``uint8`` device tensor ``[n_query, 64]``
+    to write into, new when None.  Returns ``(d_xic, d_over)``: the records (``xic_records`` reads a host copy; ``xic_values``
+    makes the column the quant stages take) and an ``int32`` tensor of two words (the queries whose window is out of range, and
+    0xffffffff minus the first of them).  READ-ONLY; one launch on torch's current stream; nothing waits on the host.
+    ``pyascore_amd.rollup.xic`` gives the same bytes."""
+    import torch
+    from .rollup import XIC_DTYPE, xic_c_params
+    c_params, device, peak_off, n_survey = _transform_inputs(scorer, xic_c_params, params, d_ms1_mz, d_ms1_intensity, ms1_peak_off)
+    per_scan = []
+    for t, np_dtype, dtype in ((d_rt, np.float64, torch.float64), (d_scan_ok, np.uint8, torch.uint8)):
+        if not isinstance(t, torch.Tensor):
+            t = _upload(t, np_dtype, device)
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda or t.numel() != n_survey:
+            raise ValueError("d_rt (float64) and d_scan_ok (uint8) are contiguous device tensors with one entry per survey spectrum")
+        per_scan.append(t)
+    per_query = []
+    for t, np_dtype, dtype in ((d_seed, np.int64, torch.int64), (d_scan_lo, np.int64, torch.int64), (d_scan_hi, np.int64, torch.int64),
+                               (d_prec_mz, np.float64, torch.float64), (d_prec_z, np.int32, torch.int32)):
+        if not isinstance(t, torch.Tensor):
+            t = _upload(t, np_dtype, device)
+        if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or not t.is_cuda or (per_query and t.numel() != per_query[0].numel()):
+            raise ValueError("d_seed, d_scan_lo, d_scan_hi (int64), d_prec_mz (float64) and d_prec_z (int32) are contiguous device tensors "
+                             "with one entry per query")
+        per_query.append(t)
+    n_query = per_query[0].numel()
+    shape = (n_query, XIC_DTYPE.itemsize)
+    with torch.cuda.device(device):
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=device)
+        over = torch.zeros(2, dtype=torch.int32, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError("out must be a contiguous uint8 device tensor of shape %r" % (shape,))
+    t_in = _lib.TypedSpectra(d_ms1_mz.data_ptr(), d_ms1_intensity.data_ptr(), _lib.spectrum_type(d_ms1_mz.dtype),
+                             _lib.spectrum_type(d_ms1_intensity.dtype))
+    rc = scorer._lib.pya_xic_spectra(scorer._h, C.byref(t_in), peak_off.data_ptr(), n_survey, d_ms1_mz.numel(),
+                                     *(t.data_ptr() if n_survey else None for t in per_scan),
+                                     *(t.data_ptr() if n_query else None for t in per_query), n_query, C.byref(c_params),
+                                     torch.cuda.current_stream(device).cuda_stream, out.data_ptr() if n_query else None, over.data_ptr())
+    if rc:
+        scorer._raise(rc)
+    # (the caching allocator keeps uploaded arrays for this stream until later work on the stream is done with them)
+    return out, over
+
+
+def xic_values(scorer, d_xic, which="area", out=None):
+    """One column of the records of ``xic`` (uint8 ``[n, 64]``) as the one-channel matrix ``DevicePlan.site_quant`` and
+    ``peptidoform_quant`` take (``pya_xic_values``): a ``torch.float64`` device tensor ``[n, 1]``, ``which`` 0 .. 3 or 'area',
+    'apex', 'seed', 'sum'; NaN where the record is not SEEN or the value is not > 0.  ``out``: such a tensor to write into, new
+    when None.  One launch on torch's current stream; nothing waits on the host.  ``pyascore_amd.rollup.xic_values`` gives the
+    same bytes."""
+    import torch
+    from .rollup import XIC_DTYPE
+    if not isinstance(scorer, PyAscore):
+        raise TypeError("scorer must be a pyascore_amd.PyAscore")
+    names = {"area": 0, "apex": 1, "seed": 2, "sum": 3}
+    which = names.get(which, which) if isinstance(which, str) else which
+    if isinstance(which, (bool, str)) or not isinstance(which, (int, np.integer)) or not 0 <= int(which) <= 3:
+        raise ValueError("xic_values: which is 0 .. 3 or one of 'area', 'apex', 'seed', 'sum'")
+    if d_xic.dim() != 2 or d_xic.shape[1] != XIC_DTYPE.itemsize:
+        raise ValueError("d_xic must be a contiguous uint8 device tensor of shape (n, %d)" % XIC_DTYPE.itemsize)
+    _channel_tensor(d_xic, None, torch.uint8, "d_xic")
+    n, device = int(d_xic.shape[0]), d_xic.device
+    if out is None:
+        with torch.cuda.device(device):
+            out = torch.empty((n, 1), dtype=torch.float64, device=device)
+    _channel_tensor(out, (n, 1), torch.float64, "out")
+    rc = scorer._lib.pya_xic_values(scorer._h, d_xic.data_ptr() if n else None, n, int(which), torch.cuda.current_stream(device).cuda_stream,
+                                    out.data_ptr() if n else None)
+    if rc:
+        scorer._raise(rc)
+    return out
+
+
+def xic_records(raw):
+    """A host copy of the tensor of ``xic`` (``.cpu().numpy()``, uint8 ``[n_query, 64]``) as the structured array
+    ``PyAscore.precursor_xic`` returns; a view, no copy."""
+    from .rollup import XIC_DTYPE
+    a = np.ascontiguousarray(raw, np.uint8)
+    if a.ndim != 2 or a.shape[1] != XIC_DTYPE.itemsize:
+        raise ValueError("expected a uint8 array of shape (n, %d)" % XIC_DTYPE.itemsize)
+    return a.view(XIC_DTYPE).reshape(a.shape[0])
+
+
 def marker_spectrum_records(raw):
     """A host copy of the second tensor of ``markers`` (``.cpu().numpy()``, uint8 ``[n_spectra, 32]``) as the structured
     array ``PyAscore.score_batch(..., markers=...)`` returns in ``marker_spectra``; a view, no copy."""

@@ -247,8 +247,9 @@ class MzMLExtractor:
     ``(target, lower offset, upper offset)`` of the precursor's isolation window (cvParams MS:1000827 / 8 / 9), None where
     the file does not give all three; ``parent_scan``: the ``scan=N`` of the precursor's ``spectrumRef``, None without one."""
 
-    def __init__(self, native_precision=False):
+    def __init__(self, native_precision=False, times=False):
         self.native_precision = native_precision
+        self.times = times
 
     def extract(self, spectrum):
         params = {}
@@ -308,9 +309,26 @@ class MzMLExtractor:
                                        dtype, self.native_precision)
         if "mz" in got and "int" in got:
             mz, inten = got["mz"], got["int"]
-        return {"scan": scan, "ms_level": ms_level, "precursor_mz": precursor_mz,
-                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile,
-                "isolation": isolation, "parent_scan": parent_scan}
+        rec = {"scan": scan, "ms_level": ms_level, "precursor_mz": precursor_mz,
+               "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile,
+               "isolation": isolation, "parent_scan": parent_scan}
+        if self.times:
+            rec["rt"] = self._start_time(spectrum)
+        return rec
+
+    @staticmethod
+    def _start_time(spectrum):
+        """the scan start time (cvParam MS:1000016 of the first <scan>) in seconds: minutes where its unit is UO:0000031,
+        seconds where it is UO:0000010 or missing; None without the cvParam or with a value that is no number"""
+        scan = _descend(spectrum, "scanList", "scan")
+        for cv in (_children(scan, "cvParam") if scan is not None else ()):
+            if cv.get("accession") == "MS:1000016":
+                try:
+                    value = float(cv.get("value"))
+                except (TypeError, ValueError):
+                    return None
+                return value * 60.0 if cv.get("unitAccession") == "UO:0000031" else value
+        return None
 
 
 class MzXMLExtractor:
@@ -319,8 +337,9 @@ class MzXMLExtractor:
     scan's ``centroided`` attribute is 1, True where it is 0, None without it.  ``isolation``: ``(precursor m/z, w / 2, w / 2)``
     from the precursor's ``windowWideness`` w, None without it; ``parent_scan``: its ``precursorScanNum``, None without it."""
 
-    def __init__(self, native_precision=False):
+    def __init__(self, native_precision=False, times=False):
         self.native_precision = native_precision
+        self.times = times
 
     def extract(self, scan):
         num = int(scan.get("num")) if scan.get("num") is not None else -1
@@ -353,9 +372,24 @@ class MzXMLExtractor:
             mz, inten = pairs[0::2].copy(), pairs[1::2].copy()
         centroided = (scan.get("centroided") or "").strip().lower()
         profile = False if centroided in ("1", "true") else (True if centroided in ("0", "false") else None)
-        return {"scan": num, "ms_level": ms_level, "precursor_mz": precursor_mz,
-                "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile,
-                "isolation": isolation, "parent_scan": parent_scan}
+        rec = {"scan": num, "ms_level": ms_level, "precursor_mz": precursor_mz,
+               "precursor_charge": precursor_charge, "mz_values": mz, "intensity_values": inten, "profile": profile,
+               "isolation": isolation, "parent_scan": parent_scan}
+        if self.times:
+            rec["rt"] = _duration_seconds(scan.get("retentionTime"))
+        return rec
+
+
+def _duration_seconds(text):
+    """an mzXML ``retentionTime`` ("PT2767.1S"; "PT46M7.1S" is read too) in seconds, None where it is missing or not of that form"""
+    m = re.fullmatch(r"\s*PT(?:([0-9.]+)H)?(?:([0-9.]+)M)?(?:([0-9.]+)S)?\s*", text or "")
+    if m is None or not any(m.groups()):
+        return None
+    try:
+        h, mi, sec = (float(g) if g else 0.0 for g in m.groups())
+    except ValueError:
+        return None
+    return sec if not (h or mi) else (h * 60.0 + mi) * 60.0 + sec
 
 
 def _mzxml_scans(path):
@@ -376,13 +410,16 @@ class SpectraParser:
     record -> bool.  ``to_list()`` is sorted by scan number, ``to_dict()`` maps scan -> record (without
     its "scan" field).  ``native_precision=True``: ``mz_values`` / ``intensity_values`` keep the precision the file
     declares (mzML per array -- msconvert writes 64-bit m/z and 32-bit intensities --, mzXML per ``precision``) instead of
-    the reference's float64; ``PyAscore.score_batch`` takes float32 arrays as they are."""
+    the reference's float64; ``PyAscore.score_batch`` takes float32 arrays as they are.  ``times=True`` adds ``rt`` to every
+    record: the scan's retention time in seconds (mzML: cvParam MS:1000016, minutes or seconds by its unit; mzXML:
+    ``retentionTime="PT...S"``), None where the file gives none -- what ``pyascore_amd.rollup.xic_windows`` and the XIC stage
+    take.  Without it the records are the reference's, as before."""
 
-    def __init__(self, spec_file_name, spec_file_format, ms_level=2, custom_filter=None, native_precision=False):
+    def __init__(self, spec_file_name, spec_file_format, ms_level=2, custom_filter=None, native_precision=False, *, times=False):
         if spec_file_format == "mzML":
-            self._records = lambda: (MzMLExtractor(native_precision).extract(s) for s in _stream(spec_file_name, {"spectrum"}))
+            self._records = lambda: (MzMLExtractor(native_precision, times).extract(s) for s in _stream(spec_file_name, {"spectrum"}))
         elif spec_file_format == "mzXML":
-            self._records = lambda: (MzXMLExtractor(native_precision).extract(s) for s in _mzxml_scans(spec_file_name))
+            self._records = lambda: (MzXMLExtractor(native_precision, times).extract(s) for s in _mzxml_scans(spec_file_name))
         else:
             raise ValueError("{} not supported at this time."
                              " Should be one of: mzML or mzXML".format(spec_file_format))

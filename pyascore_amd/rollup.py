@@ -104,6 +104,13 @@ PURITY_DTYPE = np.dtype(_lib.PURITY_DTYPE)          # pya_purity, 48 bytes
 assert PURITY_DTYPE.itemsize == 48
 PURITY_MAX_CENTRES, PURITY_MAX_BELOW = _lib.PYA_PURITY_MAX_CENTRES, _lib.PYA_PURITY_MAX_BELOW
 PURITY_ACTIVE, PURITY_SEEN = _lib.PYA_PURITY_ACTIVE, _lib.PYA_PURITY_SEEN
+XIC_DTYPE = np.dtype(_lib.XIC_DTYPE)                # pya_xic, 64 bytes
+assert XIC_DTYPE.itemsize == 64
+XIC_MAX_SCANS, XIC_MAX_ISOTOPES, XIC_MAX_GAP = _lib.PYA_XIC_MAX_SCANS, _lib.PYA_XIC_MAX_ISOTOPES, _lib.PYA_XIC_MAX_GAP
+XIC_ACTIVE, XIC_SEEN, XIC_SEED_PRESENT = _lib.PYA_XIC_ACTIVE, _lib.PYA_XIC_SEEN, _lib.PYA_XIC_SEED_PRESENT
+XIC_LEFT_VALLEY, XIC_RIGHT_VALLEY, XIC_UNSORTED = _lib.PYA_XIC_LEFT_VALLEY, _lib.PYA_XIC_RIGHT_VALLEY, _lib.PYA_XIC_UNSORTED
+XIC_LEFT_OPEN, XIC_RIGHT_OPEN = _lib.PYA_XIC_LEFT_OPEN, _lib.PYA_XIC_RIGHT_OPEN
+XIC_COLUMNS = ("area", "apex_intensity", "seed_intensity", "sum_intensity")     # ``which`` 0 .. 3 of ``xic_values``
 SITE_QUANT_HEAD_DTYPE = np.dtype(_lib.SITE_QUANT_HEAD_DTYPE)   # pya_site_quant_head, 8 bytes
 SITE_QUANT_DTYPE = np.dtype(_lib.SITE_QUANT_DTYPE)             # pya_site_quant, 16 bytes
 assert SITE_QUANT_HEAD_DTYPE.itemsize == 8 and SITE_QUANT_DTYPE.itemsize == 16
@@ -1446,6 +1453,269 @@ def survey_index(survey_scans, scans, parent_scans=None):
         named[named] = sv[at[named]] == par[named]
         out[named] = at[named]
     return out
+
+
+def xic_params(tol=0.0, tol_ppm=10.0, isotopes=2, step=STRIP_STEP, rise=2.0, max_gap=1):
+    """The parameters of the precursor-XIC stage (``pya_xic_params``) as a dict: ``tol`` the half width of an isotope's window in
+    m/z units and ``tol_ppm`` in ppm of its centre, added to it; ``isotopes`` the isotope positions above the selected m/z whose
+    intensity is added to the trace (0 .. 3); ``step`` the isotope spacing at charge 1; ``rise``: a scan is a valley when
+    ``rise`` times its intensity lies below the maxima on both sides (>= 1); ``max_gap`` the absent scans a trace may bridge
+    (0 .. 8).  The defaults are choices, not measurements.  ValueError where the library would refuse."""
+    return check_xic_params(dict(tol=tol, tol_ppm=tol_ppm, step=step, rise=rise, isotopes=isotopes, max_gap=max_gap))
+
+
+def check_xic_params(params):
+    """``params`` (a dict as ``xic_params`` makes it) checked against the conditions of ``pya_xic_params``; returns it with
+    plain Python numbers."""
+    try:
+        out = dict(tol=float(params["tol"]), tol_ppm=float(params["tol_ppm"]), step=float(params["step"]), rise=float(params["rise"]),
+                   isotopes=params["isotopes"], max_gap=params["max_gap"])
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("xic: params is the dict of pyascore_amd.rollup.xic_params (tol, tol_ppm, step, rise, isotopes, max_gap)") from None
+    for name in ("tol", "tol_ppm"):
+        if not (np.isfinite(out[name]) and out[name] >= 0.0):
+            raise ValueError("xic: %s = %r is not a finite number >= 0" % (name, out[name]))
+    if not (np.isfinite(out["step"]) and out["step"] > 0.0):
+        raise ValueError("xic: step = %r is not finite and positive" % (out["step"],))
+    if not (np.isfinite(out["rise"]) and out["rise"] >= 1.0):
+        raise ValueError("xic: rise = %r is not a finite number >= 1" % (out["rise"],))
+    for name, most in (("isotopes", XIC_MAX_ISOTOPES), ("max_gap", XIC_MAX_GAP)):
+        v = out[name]
+        try:
+            ok = not isinstance(v, (bool, np.bool_)) and int(v) == v and int(v) >= 0
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("xic: %s = %r is not an integer >= 0" % (name, v))
+        out[name] = int(v)
+        if out[name] > most:
+            raise ValueError("xic: %s = %d is not in 0 .. %d" % (name, out[name], most))
+    return out
+
+
+def xic_c_params(params):
+    """``params`` as the ``pya_xic_params`` structure the library reads."""
+    p = check_xic_params(params)
+    return _lib.XicParams(p["tol"], p["tol_ppm"], p["step"], p["rise"], p["isotopes"], p["max_gap"])
+
+
+def xic_queries(seed, scan_lo, scan_hi, prec_mz, prec_z, what="xic"):
+    """The five per-query arrays of the XIC stage as the library takes them: ``(seed int64, scan_lo int64, scan_hi int64, prec_mz
+    float64, prec_z int32)``, contiguous and of one length.  ValueError otherwise."""
+    ints = [np.asarray(a) for a in (seed, scan_lo, scan_hi, prec_z)]
+    try:
+        pm = np.ascontiguousarray(prec_mz, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: prec_mz is a number per query" % what) from None
+    if any(a.size and a.dtype.kind not in "iu" for a in ints):
+        raise ValueError("%s: seed, scan_lo, scan_hi and prec_z are integers, one per query" % what)
+    if ints[0].ndim != 1 or any(a.shape != ints[0].shape for a in ints[1:] + [pm]):
+        raise ValueError("%s: seed, scan_lo, scan_hi, prec_mz and prec_z have one entry per query" % what)
+    if any(a.size and int(a.max()) > 2 ** 63 - 1 for a in ints[:3]):
+        raise ValueError("%s: seed, scan_lo and scan_hi do not fit an int64" % what)
+    sd, lo, hi = (np.ascontiguousarray(a, np.int64) for a in ints[:3])
+    return sd, lo, hi, pm, np.ascontiguousarray(np.clip(ints[3], -1, 0x7FFFFFFF), np.int32)
+
+
+def survey_ascending(mz, peak_off):
+    """``scan_ok`` of the XIC stage, the bytes of ``pya_xic_survey_check``: uint8 ``[n_survey]``, 1 iff ``x[j] <= x[j + 1]`` for
+    every adjacent pair of the scan's m/z -- a NaN among two or more peaks fails, scans of 0 or 1 peaks pass."""
+    mz = np.asarray(mz)
+    raw_mz, _, rel = _transform_entry("survey_ascending", mz, mz, peak_off)
+    ok = np.ones(rel.size - 1, np.uint8)
+    with np.errstate(invalid="ignore"):
+        for s in range(rel.size - 1):
+            xs = raw_mz[int(rel[s]):int(rel[s + 1])]
+            ok[s] = 1 if bool(np.all(xs[:-1] <= xs[1:])) else 0
+    return ok
+
+
+def xic(ms1_mz, ms1_intensity, ms1_peak_off, rt, seed, scan_lo, scan_hi, prec_mz, prec_z, params, scan_ok=None):
+    """The precursor XIC: the rule of ``pya_xic_params``, operation for operation in float64 and plain Python floats, so the
+    bytes are those of ``pya_xic_spectra``.  ``ms1_mz`` / ``ms1_intensity``: the survey (MS1) spectra, float64 or float32
+    (widened), ``ms1_peak_off[n_survey + 1]``, ``rt[n_survey]`` their retention times in seconds; per query (one per MS2
+    spectrum) ``seed`` the survey scan of the identification (negative: none), ``scan_lo`` / ``scan_hi`` the window
+    ``[scan_lo, scan_hi)`` of at most 64 survey scans around it (``xic_windows`` makes them), ``prec_mz`` / ``prec_z``;
+    ``params`` of ``xic_params``; ``scan_ok``: the bytes of ``survey_ascending``, computed when None.  Returns ``(records,
+    over)``: ``XIC_DTYPE[n_query]`` and ``over = (count, first)`` for the queries with ``seed >= 0`` whose window is out of
+    range (their records are zero), ``(0, None)`` when there is none.  The spectra are only read.  ValueError where
+    ``pya_xic_spectra_host`` returns ``PYA_ERR_ARG``."""
+    p = check_xic_params(params)
+    raw_mz, raw_it, rel = _transform_entry("xic", ms1_mz, ms1_intensity, ms1_peak_off)
+    n_survey = rel.size - 1
+    try:
+        rt = np.ascontiguousarray(rt, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("xic: rt is a number per survey spectrum") from None
+    if rt.shape != (n_survey,):
+        raise ValueError("xic: rt has one entry per survey spectrum")
+    ok = survey_ascending(raw_mz, rel) if scan_ok is None else np.asarray(scan_ok)
+    if ok.shape != (n_survey,):
+        raise ValueError("xic: scan_ok has one byte per survey spectrum")
+    sd, s_lo, s_hi, pm, pz = xic_queries(seed, scan_lo, scan_hi, prec_mz, prec_z)
+    rec = np.zeros(sd.size, XIC_DTYPE)
+    tol, ppm, step, rise = p["tol"], p["tol_ppm"] * 1e-6, p["step"], p["rise"]
+    n_iso, reach = p["isotopes"], p["max_gap"] + 1
+    wide = {}                                                               # survey scan -> its (x, y) widened
+
+    def scan(s):
+        if s not in wide:
+            a, b = int(rel[s]), int(rel[s + 1])
+            wide[s] = (raw_mz[a:b].astype(np.float64), raw_it[a:b].astype(np.float64))
+        return wide[s]
+
+    outside = []
+    for q in range(sd.size):
+        s0, lo, hi = int(sd[q]), int(s_lo[q]), int(s_hi[q])
+        if s0 < 0:
+            continue
+        if not (0 <= lo <= s0 < hi <= n_survey and hi - lo <= XIC_MAX_SCANS):
+            outside.append(q)
+            continue
+        z, m = int(pz[q]), float(pm[q])
+        if not (1 <= z <= STRIP_MAX_CHARGE and np.isfinite(m) and m > 0.0):
+            continue
+        W, sj = hi - lo, s0 - lo
+        # THE TRACE
+        d = step / float(z)
+        bounds = []
+        for i in range(n_iso + 1):
+            c = m + float(i) * d
+            w = tol + ppm * c
+            bounds.append((c - w, c + w))
+        pk = [[0.0] * W for _ in bounds]
+        flags = XIC_ACTIVE
+        for j in range(W):
+            if not ok[lo + j]:
+                flags |= XIC_UNSORTED
+                continue
+            xs, ys = scan(lo + j)
+            for i, (b_lo, b_hi) in enumerate(bounds):
+                with np.errstate(invalid="ignore"):
+                    at = (b_lo <= xs) & (xs <= b_hi) & (ys > 0.0)
+                if at.any():
+                    pk[i][j] = float(ys[at].max())
+        present = [pk[0][j] > 0.0 for j in range(W)]
+        t = [0.0] * W
+        for j in range(W):
+            if present[j]:
+                v = pk[0][j]
+                for i in range(1, n_iso + 1):
+                    v = v + pk[i][j]
+                t[j] = v
+        n_present = sum(present)
+        # START
+        a0 = sj if present[sj] else -1
+        for dd in range(1, reach + 1):
+            if a0 >= 0:
+                break
+            if sj - dd >= 0 and present[sj - dd]:
+                a0 = sj - dd
+            elif sj + dd < W and present[sj + dd]:
+                a0 = sj + dd
+        if a0 < 0:
+            rec[q] = (0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, n_present, 0, flags)
+            continue
+        # REGION
+        r_lo = r_hi = a0
+        gap = 0
+        for j in range(a0 + 1, W):
+            gap = 0 if present[j] else gap + 1
+            if gap > p["max_gap"]:
+                break
+            if present[j]:
+                r_hi = j
+        gap = 0
+        for j in range(a0 - 1, -1, -1):
+            gap = 0 if present[j] else gap + 1
+            if gap > p["max_gap"]:
+                break
+            if present[j]:
+                r_lo = j
+        pts = [j for j in range(r_lo, r_hi + 1) if present[j]]
+        # VALLEYS: the first one on either side of a0
+        bound, valley = [r_lo, r_hi], [False, False]
+        for side, away in ((1, [j for j in pts if j > a0]), (0, [j for j in reversed(pts) if j < a0])):
+            for k, v in enumerate(away[:-1]):
+                nearer, farther = [a0] + away[:k + 1], away[k + 1:]
+                low = rise * t[v]
+                if t[v] <= t[away[k + 1]] and low < max(t[u] for u in nearer) and low < max(t[u] for u in farther):
+                    bound[side], valley[side] = v, True
+                    break
+        e_l, e_r = bound
+        # THE PEAK
+        peak = [j for j in pts if e_l <= j <= e_r]
+        apex = peak[0]
+        for j in peak:
+            if t[j] > t[apex]:
+                apex = j
+        total = area = 0.0
+        for k, j in enumerate(peak):
+            total = total + t[j]
+            if k:
+                u = peak[k - 1]
+                with np.errstate(all="ignore"):
+                    area = area + (0.5 * (t[u] + t[j])) * (np.float64(rt[lo + j]) - np.float64(rt[lo + u]))
+        flags |= XIC_SEEN | (XIC_SEED_PRESENT if a0 == sj else 0) | (XIC_LEFT_VALLEY if valley[0] else 0) | (XIC_RIGHT_VALLEY if valley[1] else 0)
+        flags |= (XIC_LEFT_OPEN if not valley[0] and e_l == 0 else 0) | (XIC_RIGHT_OPEN if not valley[1] and e_r == W - 1 else 0)
+        iso_hit = sum(1 << i for i in range(n_iso + 1) if pk[i][apex] > 0.0)
+        rec[q] = (float(area), t[apex], t[sj], total, lo + apex, lo + e_l, lo + e_r, lo + a0, len(peak), n_present, iso_hit, flags)
+    return rec, (len(outside), outside[0] if outside else None)
+
+
+def xic_values(records, which="area"):
+    """One column of ``XIC_DTYPE`` records as the one-channel matrix ``site_quant`` and ``peptidoform_quant`` take, the bytes of
+    ``pya_xic_values``: float64 ``[n]``, ``which`` 0 .. 3 or 'area', 'apex', 'seed', 'sum'; NaN (``marker_matrix``'s "no
+    reading") where the record is not SEEN or the value is not > 0."""
+    names = {"area": 0, "apex": 1, "seed": 2, "sum": 3}
+    if isinstance(which, str):
+        if which not in names:
+            raise ValueError("xic_values: which is 0 .. 3 or one of 'area', 'apex', 'seed', 'sum'")
+        which = names[which]
+    if isinstance(which, (bool, np.bool_)) or not isinstance(which, (int, np.integer)) or not 0 <= int(which) <= 3:
+        raise ValueError("xic_values: which is 0 .. 3 or one of 'area', 'apex', 'seed', 'sum'")
+    rec = np.asarray(records, XIC_DTYPE)
+    v = rec[XIC_COLUMNS[int(which)]]
+    with np.errstate(invalid="ignore"):
+        take = ((rec["flags"] & XIC_SEEN) != 0) & (v > 0.0)
+    out = np.full(rec.shape, np.nan)
+    out[take] = v[take]
+    return out
+
+
+def xic_windows(survey_rt, seed, half_width_s, run_bounds=None):
+    """The windows of ``xic`` from retention times: for every ``seed`` (an index into ``survey_rt``, seconds in file order) the
+    survey scans around it whose time lies within ``half_width_s`` of the seed's, as ``(scan_lo, scan_hi)`` int64 arrays --
+    contiguous from the seed outwards, never across a run (file) boundary (``run_bounds``: the ascending survey indices
+    ``[n_runs + 1]`` at which the runs begin and the last one ends; None: one run), and cut to the 64 scans nearest the seed:
+    ``scan_lo >= seed - 31``, ``scan_hi <= seed + 33``.  A negative seed (no survey scan) gets ``(0, 0)``."""
+    rt = np.ascontiguousarray(survey_rt, np.float64).reshape(-1)
+    sd = np.asarray(seed)
+    if sd.size and sd.dtype.kind not in "iu":
+        raise ValueError("xic_windows: seed is an integer per query")
+    sd = np.ascontiguousarray(sd, np.int64).reshape(-1)
+    hw = float(half_width_s)
+    if not hw >= 0.0:
+        raise ValueError("xic_windows: half_width_s = %r is not a number >= 0" % (half_width_s,))
+    bounds = np.asarray([0, rt.size] if run_bounds is None else run_bounds, np.int64).reshape(-1)
+    if bounds.size < 2 or bounds[0] != 0 or bounds[-1] != rt.size or (np.diff(bounds) < 0).any():
+        raise ValueError("xic_windows: run_bounds ascend from 0 to the number of survey spectra")
+    if sd.size and int(sd.max()) >= rt.size:
+        raise ValueError("xic_windows: a seed lies beyond the survey spectra")
+    lo, hi = np.zeros(sd.size, np.int64), np.zeros(sd.size, np.int64)
+    for q in range(sd.size):
+        s = int(sd[q])
+        if s < 0:
+            continue
+        run = int(np.searchsorted(bounds, s, side="right")) - 1
+        first, last = max(int(bounds[run]), s - 31), min(int(bounds[run + 1]), s + 33)
+        a, b = s, s + 1
+        while a > first and abs(rt[a - 1] - rt[s]) <= hw:
+            a -= 1
+        while b < last and abs(rt[b] - rt[s]) <= hw:
+            b += 1
+        lo[q], hi[q] = a, b
+    return lo, hi
 
 
 def centroid_params(gap, gap_ppm=0.0, half_width=4, min_height=0.0, area=False):
